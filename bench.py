@@ -18,6 +18,12 @@ covariance and the pose tables are resident in HBM; every step starts from the s
              `--workload config2 --gpus N` strong-scales the shape without planes (2000 point features split over the ranks) -
              the part of the path that shards; the line carries the RCCL rank count and rank 0's time per stage.
 
+A plain run sets up, settles, warms up, times exactly --steps steps and prints the headline.  Everything else the bench measures
+or checks - the second timed window, the per-kernel HIP-event passes and the roofline, the device clock of the two halves of a
+step, the side figures (point_config, config4_1gpu, inputs_resident, euroc_like_frame, propagation), the CPU baseline with the
+accept-set comparison on the timed frame, and with several ranks the stage pass and the strong-scaling references - runs only
+with --full.  --dump-outputs DIR writes what the last timed step handed its caller (rank 0) as DIR/<name>.npy in float64.
+
 Prints ONE JSON line on rank 0."""
 from __future__ import annotations
 
@@ -456,7 +462,20 @@ def step_stats(ts):
             "excess_over_median_ms": 1e3 * sum(t - med for t in ts if t > 1.5 * med)}
 
 
-CPU_BASELINE_RUNS = 3  # 3.7 s (one core) + 1.4 s (all cores) per run of the config-3 frame: ~15 s of CPU work in the default bench
+def dump_outputs(out_dir, pl, pt, P):
+    """--dump-outputs: what the last timed step handed its caller - every array of the point update's results (dx, accept mask,
+    chi2) as point_<key>, of the plane loop's (per-plane dx, decisions, chi2, rows, consumed-feature mask) as plane_<key>, and the
+    covariance it left on the device - as float64 .npy files (under 1 MB for the largest workload), so that two builds can be
+    compared output for output (the frame is seeded: same arguments, same inputs)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {"covariance": P} if P is not None else {}
+    for prefix, res in (("plane", pl), ("point", pt)):
+        arrs.update(("%s_%s" % (prefix, k), v) for k, v in (res or {}).items() if isinstance(v, np.ndarray))
+    for k, v in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray(v, dtype=np.float64))
+
+
+CPU_BASELINE_RUNS = 3  # 3.7 s (one core) + 1.4 s (all cores) per run of the config-3 frame: ~15 s of CPU work in a --full bench
 
 
 def cpu_model():
@@ -610,8 +629,13 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", choices=["auto", "config2", "config3", "config4", "points8000"], default="auto")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side figures (point_config, config4_1gpu, propagation)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline (module docstring): second window, kernel-timer passes and "
+                         "roofline, device clock, side figures, CPU baseline and accept-set comparison, multi-rank stage pass")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the outputs of the last timed step (rank 0) to DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the side figures (point_config, config4_1gpu, propagation)")
     ap.add_argument("--cpu-sample-feats", type=int, default=0, help="0 = the oracle runs every feature of the frame")
     ap.add_argument("--python-gc", choices=["off", "on"], default="off",
                     help="off (default): the Python collector is disabled inside the timed windows (the harness is Python, the path "
@@ -698,22 +722,26 @@ def main():
         pl, pt = last.results() if hasattr(last, "results") else last
         host_acc = run.ctx.host_timing(reset=True)
         gc_w1 = gcw.take()
-        # a second window of the same length right behind the first (reported beside it, never `value`)
-        elapsed2, _, per_step2 = time_steps(be, fn, args.steps, 0, barrier)
-        gc_w2 = gcw.take()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, pl, pt, run.ctx.cov_download() if hasattr(run.ctx, "cov_download") else None)
+        per_step2, gc_w2, k1_n, c2_n, dev_ms, stages = None, None, 0, 0, None, None
+        if args.full:
+            # a second window of the same length right behind the first (reported beside it, never `value`)
+            elapsed2, _, per_step2 = time_steps(be, fn, args.steps, 0, barrier)
+            gc_w2 = gcw.take()
         gc.enable()
         gc.callbacks.remove(gcw)
-        # dominant-kernel launch times with HIP events, in a pass of their own (events between dependent launches cost
-        # microseconds each, they must not sit in the timed region above)
-        run.ctx.kernel_timer(enable=True, reset=True)
-        run.ctx.plane_kernel_timer(enable=1, reset=True)
-        time_steps(be, fn, max(5, min(args.steps, 20)), 0, barrier)
-        k1_ms, k1_n = run.ctx.kernel_timer(enable=False, reset=False)
-        c2_ms, c2_n = run.ctx.plane_kernel_timer(enable=0, reset=False)
+        if args.full:
+            # dominant-kernel launch times with HIP events, in a pass of their own (events between dependent launches cost
+            # microseconds each, they must not sit in the timed region above)
+            run.ctx.kernel_timer(enable=True, reset=True)
+            run.ctx.plane_kernel_timer(enable=1, reset=True)
+            time_steps(be, fn, max(5, min(args.steps, 20)), 0, barrier)
+            k1_ms, k1_n = run.ctx.kernel_timer(enable=False, reset=False)
+            c2_ms, c2_n = run.ctx.plane_kernel_timer(enable=0, reset=False)
         # device clock of the two halves of a step (a pass of its own: one event pair around the plane loop, K1 start .. last
         # kernel of the point update) - what the step would take with a host that is never late
-        dev_ms = None
-        if not sharded:
+        if args.full and not sharded:
             n_ev = max(5, min(args.steps, 20))
             run.ctx.kernel_timer(enable=True, reset=True)
             run.ctx.plane_kernel_timer(enable=2, reset=True)
@@ -728,8 +756,7 @@ def main():
             dev_ms = {"plane_loop_ms": acc["plane_loop_device_ms"] / n_ev if run.has_planes else 0.0,
                       "point_update_ms": sorted(pt_ms)[len(pt_ms) // 2], "steps": n_ev}
             dev_ms["sum_ms"] = dev_ms["plane_loop_ms"] + dev_ms["point_update_ms"]
-        stages = None
-        if sharded:
+        if args.full and sharded:
             # where a multi-GPU step spends its time (a pass of its own: the stages are separated by host synchronisations)
             stages = {}
             n_diag = 5
@@ -740,7 +767,7 @@ def main():
     # the same workload on ONE GPU, measured by rank 0 of this very job (the others wait): the driver's N = 1 line is the headline
     # configuration (config 3), not this one, so the line carries its own strong-scaling reference
     one_gpu = None
-    if sharded:
+    if args.full and sharded:
         if rank == 0:
             with be.stream_ctx(run):
                 els = []
@@ -750,7 +777,7 @@ def main():
             one_gpu = {"ms_per_step": 1e3 * sorted(els)[1], "timing": "median of 3 blocks of 10 unsharded steps on rank 0 while the other ranks wait"}
         dist.barrier()
     point_only = None
-    if sharded and name not in ("config2", "points8000"):
+    if args.full and sharded and name not in ("config2", "points8000"):
         # the part of the path that shards, on the same ranks: config 4's 8000 features WITHOUT its planes, strong-scaled, with its
         # own one-GPU reference (rank 0, unsharded, while the others wait)
         sc2 = be.make_workload("points8000")
@@ -816,14 +843,15 @@ def main():
         st1 = step_stats(per_step)
         line["step_times"] = dict(st1, note="wall time of each of the timed steps (every step ends in a host-visible completion); "
                                             "ms_per_step above is total / steps and includes the closing synchronize + barrier")
-        line["second_window"] = dict(step_stats(per_step2), ms_per_step=1e3 * elapsed2 / args.steps,
-                                     note="the same number of steps timed again right behind the first window")
+        if per_step2 is not None:
+            line["second_window"] = dict(step_stats(per_step2), ms_per_step=1e3 * elapsed2 / args.steps,
+                                         note="the same number of steps timed again right behind the first window")
         line["prewarm"] = {"steps": n_prewarm, "block_medians_ms": [round(b, 4) for b in prewarm_blocks],
                            "rule": "blocks of %d untimed steps until two consecutive block medians agree to 2 %% (>= %d steps, <= %.0f s)"
                                    % (PREWARM_BLOCK, PREWARM_MIN_STEPS, PREWARM_MAX_S)}
         line["python_gc"] = {"inside_timed_windows": args.python_gc, "prewarm": gc_prewarm, "window_1_incl_warmup": gc_w1, "window_2": gc_w2,
                              "note": "pauses of the harness's garbage collector (gc.callbacks); `off` = gc.collect() + gc.disable() in "
-                                     "front of the warm-up steps, re-enabled behind the second window"}
+                                     "front of the warm-up steps, re-enabled behind the timed window(s); window_2 only with --full"}
         kp, kq = max(host_acc["plane_calls"], 1), max(host_acc["point_calls"], 1)  # (the accumulators also cover the warm-up steps)
         line["host"] = {
             "plane_pre_launch_ms": host_acc["plane_pre_ms"] / kp, "plane_enqueue_ms": host_acc["plane_enqueue_ms"] / kp,
@@ -888,14 +916,16 @@ def main():
             }
             if "roofline" not in line:
                 line["roofline"] = line["roofline_point_kernel"]
-        mu = mfma_utilisation(name, world)
+        mu = mfma_utilisation(name, world) if args.full else None
         if mu is not None:
             line["mfma_utilisation"] = mu
-        if stages is not None:
-            tot_st = sum(stages.values()) or 1.0
+        if sharded:
             line["multi_gpu"] = {
                 "rccl_ranks": int(dist.get_world_size()), "backend": dist.get_backend(), "collective": collective,
-                "collective_note": comm_note,
+                "collective_note": comm_note, "rank0_point_shard": int(run.shard_size)}
+        if stages is not None:
+            tot_st = sum(stages.values()) or 1.0
+            line["multi_gpu"].update({
                 "rank0_stage_ms": stages,
                 "serial_fraction": stages.get("plane_loop_ms", 0.0) / tot_st,
                 "serial_fraction_note": "plane loop (replicated on every rank, sequential across planes: update/UpdaterMSCKF.cpp:413-649) / "
@@ -905,13 +935,12 @@ def main():
                 "one_gpu_same_workload": one_gpu,
                 "speedup_vs_one_gpu_same_workload": (one_gpu["ms_per_step"] / ms_per_step) if one_gpu else None,
                 "point_only_scaling": point_only,
-                "rank0_point_shard": int(run.shard_size),
                 "note": "stage times of rank 0 from a separate pass with a host synchronisation behind every stage (plane loop "
                         "replicated on every rank; points_build = feature kernel + information pair of the rank's shard; "
-                        "allreduce = one RCCL all-reduce of (N+1) x ld f64; update = EKF update from the summed pair + results)"}
-        if not sharded and not args.no_extras:
+                        "allreduce = one RCCL all-reduce of (N+1) x ld f64; update = EKF update from the summed pair + results)"})
+        if args.full and not sharded and not args.no_extras:
             extras(line, be, capi, torch, args, local_rank, name)
-        if not sharded and not args.no_cpu_baseline:
+        if args.full and not sharded and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"], ora = cpu_baseline(sc, name, args.cpu_sample_feats if args.cpu_sample_feats > 0 else None)
                 line["speedup_vs_cpu_baseline"] = line["cpu_baseline"]["ms_per_step"] / ms_per_step

@@ -35,7 +35,7 @@ def _bench(args, env_extra=None, timeout=420):
 
 def test_two_ranks_through_bench_main_native_collective(tmp_path):
     dump = str(tmp_path / "rank%d.npz")
-    line, _ = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1"], {"OVP_STANDIN_DUMP": dump})
+    line, _ = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], {"OVP_STANDIN_DUMP": dump})
     assert line["n_gpus"] == 2 and line["steps"] == 3 and line["warmup"] == 1
     assert line["value"] is None and line["data"].startswith("standin")          # nothing measured this way is a result
     assert line["config"]["baseline_config"] == "config4" and line["config"]["planes"] == 3
@@ -74,3 +74,21 @@ def test_one_rank_sharded_path_through_bench_main():
     line, _ = _bench(["--gpus", "1", "--steps", "2", "--warmup", "0", "--sharded-path"])
     assert line["n_gpus"] == 1 and line["multi_gpu"]["rccl_ranks"] == 1
     assert line["multi_gpu"]["collective"].startswith("rccl-native")
+
+
+def test_plain_run_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line holds the headline and nothing that needs passes of its own; --dump-outputs writes the last timed
+    step's outputs as float64 .npy files, the same on every run of the same arguments."""
+    outs = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        line, _ = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--sharded-path", "--dump-outputs", str(d)])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert "second_window" not in line and "rank0_stage_ms" not in line["multi_gpu"]
+        assert line["multi_gpu"]["rccl_ranks"] == 1 and "roofline" not in line and "cpu_baseline" not in line
+        names = sorted(f.name for f in d.iterdir())
+        assert {"point_dx.npy", "point_accepted.npy", "point_chi2.npy", "plane_ok.npy", "plane_used.npy"} <= set(names)
+        outs.append({n: np.load(d / n) for n in names})
+    assert outs[0].keys() == outs[1].keys()
+    for n, a in outs[0].items():
+        assert a.dtype == np.float64 and np.array_equal(a, outs[1][n]), n

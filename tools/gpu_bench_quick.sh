@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box: the config-3 step (50 steps, no CPU leg, no side figures) and the plane-loop tests - a quick A/B line
 wl=${1:-config3}
-timeout 120 python bench.py --workload $wl --steps ${2:-50} --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+timeout 120 python bench.py --workload $wl --steps ${2:-50} --full --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 dc=d.get('device_clock',{})

@@ -15,11 +15,11 @@ stats() {  # name, command...
   db=$(find /tmp/prof_$name -name '*.db' | head -1)
   python $root/tools/rocpd_stats.py $db $out/${tag}_${name}_kernel_stats.csv
 }
-# 1. the driver's command, untouched
-python $root/bench.py > $out/${tag}_bench_driver_cmd.json 2> $out/${tag}_bench_driver_cmd.err
+# 1. the driver's command with everything beside the headline (--full: roofline, side figures, CPU baseline)
+python $root/bench.py --full > $out/${tag}_bench_driver_cmd.json 2> $out/${tag}_bench_driver_cmd.err
 # 2. kernel statistics
 rm -rf /tmp/prof_c3
-rocprofv3 --kernel-trace --stats -d /tmp/prof_c3 -o p -- python $root/bench.py --steps 100 --no-cpu-baseline > $out/${tag}_bench_under_rocprof.json 2> /tmp/prof_c3.log
+rocprofv3 --kernel-trace --stats -d /tmp/prof_c3 -o p -- python $root/bench.py --steps 100 --full --no-cpu-baseline > $out/${tag}_bench_under_rocprof.json 2> /tmp/prof_c3.log
 python $root/tools/rocpd_stats.py $(find /tmp/prof_c3 -name '*.db' | head -1) $out/${tag}_kernel_stats.csv
 stats config2 python $root/bench.py --workload config2 --steps 100 --no-extras --no-cpu-baseline
 stats config4 python $root/bench.py --workload config4 --steps 20 --no-extras --no-cpu-baseline
