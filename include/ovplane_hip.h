@@ -161,6 +161,56 @@ int ovp_msckf_update(ovp_ctx *ctx, const ovp_update_opts *opts, double *dx_host,
 int ovp_msckf_dense_blocks(ovp_ctx *ctx, double chi2_multiplier, int n_blocks, const int *rows, const int *cols, const double *H,
                            const int *col_ids, const double *res, uint8_t *accepted, double *chi2);
 
+/* ---- general point features: any camera, long tracks (device form of the dense blocks above) ---------------------------------
+ * The batch format carries camera 0 and at most OVP_MAX_MEAS views.  A feature outside that - observations of another camera (the
+ * reference loops over every camera of a feature, update/UpdaterHelper.cpp:335-344), a track longer than OVP_MAX_MEAS (stacked
+ * without a limit, update/UpdaterMSCKF.cpp:686-691) - takes these entries instead of ovp_msckf_dense_blocks: rows, nullspace
+ * projection, gate and information pair are formed on the device (csrc/k_feat_gen.hip).
+ * Limits: OVP_MAX_CAMERAS cameras, OVP_GEN_MAX_MEAS observations per feature (2m <= 128 rows: the rows and the packed
+ * (2m+1)-row gate matrix of one feature live in the LDS of its workgroup; the projected rows are staged in global memory, 2m x the
+ * feature's involved columns <= 4 * 14 + 6 * 64). */
+#define OVP_MAX_CAMERAS 4
+#define OVP_GEN_MAX_MEAS 64
+
+/* State::_calib_IMUtoCAM.at(k) / _cam_intrinsics.at(k) / _cam_intrinsics_cameras.at(k) of one camera (state/State.cpp:52-72) */
+typedef struct {
+  double calib_q[4];     /* R_ItoC as JPL quaternion              */
+  double calib_p[3];     /* p_IinC                                */
+  int calib_id;          /* Type::id(); read when do_calib_camera_pose */
+  double intrinsics[8];  /* fx fy cx cy k1 k2 p1 p2 (k1..k4 fisheye) */
+  int intr_id;           /* Type::id(); read when do_calib_camera_intrinsics */
+  int fisheye;           /* 0 = ext CamRadtan, 1 = ext CamEqui    */
+} ovp_camera_tables;
+
+/* camera k of the context = cams[k], k < n_cams <= OVP_MAX_CAMERAS; replaces the previous tables (host pointers, copied).  The
+ * clone tables stay those of ovp_state_upload. */
+int ovp_cameras_upload(ovp_ctx *ctx, int n_cams, const ovp_camera_tables *cams);
+
+/* A vector of UpdaterHelper::UpdaterHelperFeature with per-observation camera (update/UpdaterHelper.h:62-105; GLOBAL_3D), host
+ * pointers, observation k of feature f at [f * max_meas + k]. */
+typedef struct {
+  int n_feats;
+  int max_meas;          /* row pitch of uv / clone_idx / cam_idx */
+  const float *uv;       /* [n_feats*max_meas*2] raw pixels (f32, UpdaterHelper.h:68) */
+  const int *clone_idx;  /* [n_feats*max_meas] clone slot */
+  const int *cam_idx;    /* [n_feats*max_meas] camera of the observation (< n_cams of ovp_cameras_upload) */
+  const int *n_meas;     /* [n_feats] <= OVP_GEN_MAX_MEAS */
+  const double *p_FinG;  /* [n_feats*3] linearisation point (fej == value for MSCKF features) */
+} ovp_general_batch;
+
+/* UpdaterMSCKF::update for features of a general batch (update/UpdaterMSCKF.cpp:695-764): get_feature_jacobian_full over every
+ * camera's observations (update/UpdaterHelper.cpp:195-440: clone columns, per-camera extrinsics / intrinsics as the options say,
+ * whitened by 1/sigma_px), nullspace projection (:515-546, orthogonal projector onto the complement of H_f's range), gate against
+ * the RESIDENT covariance chi2 = r^T (H P H^T + I)^-1 r <= chi2_multiplier * quantile_0.95(2m - 3) (UpdaterMSCKF.cpp:739-757), all
+ * on the device.  Same contract as ovp_msckf_dense_blocks: the information pair of the accepted features (summed in feature order,
+ * no atomics: bit-reproducible) joins the next ovp_msckf_update / ovp_msckf_build_gate_gram_async / ovp_msckf_update_sharded of the
+ * context as ONE EKF update; a call that writes the covariance in between drops it; a second call replaces it.  Features with fewer
+ * than 2 observations are rejected with chi2 = 0.  accepted / chi2 [n_feats], may be NULL.  Needs ovp_state_upload,
+ * ovp_cameras_upload and a covariance.  OVP_E_CAPACITY: n_meas > OVP_GEN_MAX_MEAS; OVP_E_ARG: a camera without tables, a clone slot
+ * outside the tables, n_meas > max_meas (all checked on the host before anything is enqueued). */
+int ovp_msckf_general_features(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp_general_batch *batch, uint8_t *accepted,
+                               double *chi2);
+
 /* Staged form of the same step, for feature-sharded multi-GPU runs:
  *   stage 1 (per rank, local shard): build + project + gate + local information pair
  *            Ab_dev = [A | b], A = sum_f Hp_f^T Hp_f (n_state x n_state), b = sum_f Hp_f^T r_f,
@@ -231,6 +281,14 @@ void ovp_triang_defaults(ovp_triang_opts *o);
  * the linearisation points of the batch on the device (the next update uses them) and are returned in p_FinG_out
  * [n_feats*3] (host, may be NULL); ok[f] = 0 where the reference erases the feature.  Needs ovp_state_upload and a batch. */
 int ovp_triangulate(ovp_ctx *ctx, const ovp_triang_opts *opts, const float *uv_norm, double *p_FinG_out, uint8_t *ok);
+/* ext FeatureInitializer::single_triangulation (+ single_gaussnewton / single_triangulation_1d) over a general batch: every
+ * observation with the pose of its own camera, R_GtoC = R_ItoC(cam) R_GtoI, p_CinG = p_IinG - R_GtoC^T p_IinC(cam)
+ * (update/UpdaterMSCKF.cpp:120-166 over all cameras of the feature).  Anchor: the last observation of the lowest camera index that
+ * saw the feature (ext Feature::anchor_cam_id / anchor_clone_timestamp).  uv_norm in the layout of batch->uv; batch->p_FinG is
+ * not read.  p_FinG_out [n_feats*3] (may be NULL), ok [n_feats]: 0 where the reference erases the feature.  Same limits and
+ * argument checks as ovp_msckf_general_features. */
+int ovp_triangulate_general(ovp_ctx *ctx, const ovp_triang_opts *opts, const ovp_general_batch *batch, const float *uv_norm,
+                            double *p_FinG_out, uint8_t *ok);
 
 /* Planes touched by an update (host pointers): plane k (0-based) has reference id k+1.
  * plane_of_feat[f] = 0 for a free point, else the id of the plane feature f lies on (VioManager's feat2plane map,

@@ -113,6 +113,32 @@ class UpdateInfo(C.Structure):
     ]
 
 
+class CameraTables(C.Structure):
+    _fields_ = [
+        ("calib_q", C.c_double * 4),
+        ("calib_p", C.c_double * 3),
+        ("calib_id", C.c_int),
+        ("intrinsics", C.c_double * 8),
+        ("intr_id", C.c_int),
+        ("fisheye", C.c_int),
+    ]
+
+
+class GeneralBatch(C.Structure):
+    _fields_ = [
+        ("n_feats", C.c_int),
+        ("max_meas", C.c_int),
+        ("uv", C.c_void_p),
+        ("clone_idx", C.c_void_p),
+        ("cam_idx", C.c_void_p),
+        ("n_meas", C.c_void_p),
+        ("p_FinG", C.c_void_p),
+    ]
+
+
+OVP_MAX_CAMERAS = 4
+OVP_GEN_MAX_MEAS = 64
+
 _LIB = None
 
 # every symbol include/ovplane_hip.h declares (checked by the CPU test-suite)
@@ -140,7 +166,8 @@ EXPORTS = [
     "ovp_ctx_stream", "ovp_cov_initialize", "ovp_debug_chol2", "ovp_debug_chol2_floor", "ovp_plane_kernel_timer", "ovp_host_timing", "ovp_triang_defaults", "ovp_triangulate", "ovp_plane_fitting", "ovp_plane_optimize",
     "ovp_slam_update", "ovp_cov_clone_jitter", "ovp_rccl_unique_id", "ovp_rccl_comm_create", "ovp_rccl_comm_destroy",
     "ovp_rccl_allreduce_gram", "ovp_msckf_update_sharded", "ovp_slam_delayed_init", "ovp_shard_range", "ovp_shard_range_of_mask",
-    "ovp_rccl_gather_decisions", "ovp_msckf_dense_blocks",
+    "ovp_rccl_gather_decisions", "ovp_msckf_dense_blocks", "ovp_cameras_upload", "ovp_msckf_general_features",
+    "ovp_triangulate_general",
 ]
 
 
@@ -187,6 +214,10 @@ def lib():
         L.ovp_shard_range.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.ovp_msckf_dense_blocks.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p]
+        L.ovp_cameras_upload.argtypes = [C.c_void_p, C.c_int, C.POINTER(CameraTables)]
+        L.ovp_msckf_general_features.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(GeneralBatch), C.c_void_p, C.c_void_p]
+        L.ovp_triangulate_general.argtypes = [C.c_void_p, C.POINTER(TriangOpts), C.POINTER(GeneralBatch), C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
         L.ovp_shard_range_of_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.ovp_rccl_gather_decisions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ovp_msckf_update_sharded.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -461,6 +492,82 @@ class Context:
                                           np.ascontiguousarray(ids).ctypes.data, res.ctypes.data, acc.ctypes.data, chi2.ctypes.data),
              "ovp_msckf_dense_blocks")
         return acc[:nb].astype(bool), chi2[:nb]
+
+    # -- general point features (any camera, long tracks) ---------------------------------------------------------------------
+    def cameras_upload(self, sc, state=None):
+        """ovp_cameras_upload from a scene: camera 0 = the scene's calibration, camera 1 = sc.cam1 (synth.make_stereo_scene) when
+        present.  `state` overrides the values as in state_upload."""
+        s = sc if state is None else state
+        fish = 1 if sc.get("fisheye", False) else 0
+        cams = [(s["calib_q"], s["calib_p"], s["intr"], sc.ids["calib"], sc.ids["intr"], fish)]
+        c1 = s.get("cam1", None) if state is not None else None
+        c1 = c1 if c1 is not None else sc.get("cam1", None)
+        if c1 is not None:
+            cams.append((c1["calib_q"], c1["calib_p"], c1["intr"], sc.ids["calib1"], sc.ids["intr1"], 0))
+        self.cameras_upload_tables(cams)
+
+    def cameras_upload_tables(self, cams):
+        """cams: list of (calib_q, calib_p, intrinsics, calib_id, intr_id, fisheye), camera k = cams[k]."""
+        arr = (CameraTables * len(cams))()
+        for k, (q, p, intr, cid, iid, fish) in enumerate(cams):
+            arr[k].calib_q[:] = [float(v) for v in q]
+            arr[k].calib_p[:] = [float(v) for v in p]
+            arr[k].calib_id = int(cid)
+            arr[k].intrinsics[:] = [float(v) for v in intr]
+            arr[k].intr_id = int(iid)
+            arr[k].fisheye = int(fish)
+        _chk(lib().ovp_cameras_upload(self._h, len(cams), arr), "ovp_cameras_upload")
+
+    @staticmethod
+    def _general_batch(uv, clone_idx, cam_idx, n_meas, p_FinG=None):
+        uv = np.ascontiguousarray(uv, dtype=np.float32)
+        F = int(uv.shape[0])
+        M = int(uv.shape[1]) if uv.ndim > 1 else 1
+        keep = dict(uv=uv, clone_idx=np.ascontiguousarray(clone_idx, dtype=np.int32),
+                    cam_idx=np.ascontiguousarray(np.zeros((F, M)) if cam_idx is None else cam_idx, dtype=np.int32),
+                    n_meas=np.ascontiguousarray(n_meas, dtype=np.int32),
+                    p_FinG=np.ascontiguousarray(np.zeros((F, 3)) if p_FinG is None else p_FinG, dtype=np.float64))
+        gb = GeneralBatch(F, M, keep["uv"].ctypes.data, keep["clone_idx"].ctypes.data, keep["cam_idx"].ctypes.data,
+                          keep["n_meas"].ctypes.data, keep["p_FinG"].ctypes.data)
+        gb._keep = keep
+        return gb
+
+    def msckf_general_features(self, opts: UpdateOpts, sc=None, feats=None, uv=None, clone_idx=None, cam_idx=None, n_meas=None,
+                               p_FinG=None, raise_on_error=True):
+        """ovp_msckf_general_features on the features `feats` of a scene (fields uv, clone_idx, cam_idx, n_meas, p_FinG; a scene
+        without cam_idx is camera 0 only) or on explicit arrays.  Returns (accepted [bool], chi2, rc); the accepted ones join the
+        next msckf_update."""
+        if sc is not None:
+            sel = slice(None) if feats is None else np.asarray(feats)
+            uv, clone_idx, n_meas, p_FinG = sc.uv[sel], sc.clone_idx[sel], sc.n_meas[sel], sc.p_FinG[sel]
+            cam_idx = sc.cam_idx[sel] if "cam_idx" in sc else None
+        gb = self._general_batch(uv, clone_idx, cam_idx, n_meas, p_FinG)
+        F = gb.n_feats
+        acc = np.zeros(max(F, 1), dtype=np.uint8)
+        chi2 = np.zeros(max(F, 1))
+        rc = lib().ovp_msckf_general_features(self._h, C.byref(opts), C.byref(gb), acc.ctypes.data, chi2.ctypes.data)
+        if rc != 0 and raise_on_error:
+            raise OvpError(rc, "ovp_msckf_general_features")
+        return acc[:F].astype(bool), chi2[:F], rc
+
+    def triangulate_general(self, sc=None, feats=None, uv_norm=None, clone_idx=None, cam_idx=None, n_meas=None, opts=None,
+                            raise_on_error=True):
+        """ovp_triangulate_general on the features `feats` of a scene (uv_norm, clone_idx, cam_idx, n_meas) or on explicit
+        arrays; returns dict(p_FinG [F,3], ok [F], rc)."""
+        if sc is not None:
+            sel = slice(None) if feats is None else np.asarray(feats)
+            uv_norm, clone_idx, n_meas = sc.uv_norm[sel], sc.clone_idx[sel], sc.n_meas[sel]
+            cam_idx = sc.cam_idx[sel] if "cam_idx" in sc else None
+        o = opts if opts is not None else triang_defaults()
+        uvn = np.ascontiguousarray(uv_norm, dtype=np.float32)
+        gb = self._general_batch(uvn, clone_idx, cam_idx, n_meas)
+        F = gb.n_feats
+        p = np.zeros((max(F, 1), 3))
+        ok = np.zeros(max(F, 1), dtype=np.uint8)
+        rc = lib().ovp_triangulate_general(self._h, C.byref(o), C.byref(gb), uvn.ctypes.data, p.ctypes.data, ok.ctypes.data)
+        if rc != 0 and raise_on_error:
+            raise OvpError(rc, "ovp_triangulate_general")
+        return dict(p_FinG=p[:F], ok=ok[:F].astype(bool), rc=rc)
 
     def msckf_update_sharded(self, opts: UpdateOpts, comm, rank=0, world=1, raise_on_error=True):
         """ovp_msckf_update_sharded: this rank's share of the point features -> pair -> ncclAllReduce -> update (comm: handle from

@@ -51,6 +51,9 @@ extern "C" void ovph_set_second_camera(const double *calib_q, const double *cali
   g_cam1_intr = intr;
   g_cam_of_meas = cam_of_meas;
 }
+// next ovph_run_msckf_update: StateOptions::gpu_general_features
+static int g_general = 0;
+extern "C" void ovph_set_general_features(int on) { g_general = on != 0; }
 // next ovph_run_msckf_update: the State lives on this device and the updater takes the sharded point loop on this communicator
 static void *g_comm = nullptr;
 static int g_comm_rank = 0, g_comm_world = 1, g_device = 0, g_last_shard[2] = {0, 0};
@@ -90,6 +93,8 @@ extern "C" int ovph_run_msckf_update(int C, const double *clone_q, const double 
   so.max_state_size = N + 8;
   so.max_features = F + 8;
   so.gpu_device = g_device;
+  so.gpu_general_features = g_general != 0;
+  g_general = 0;
   if (g_cam1_q) so.num_cameras = 2;
   auto state = std::make_shared<State>(so);
   state->_cam_fisheye[0] = g_fisheye != 0;

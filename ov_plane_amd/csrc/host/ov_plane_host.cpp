@@ -736,11 +736,14 @@ void UpdaterMSCKF::update(std::shared_ptr<State> state, std::vector<std::shared_
   // measurements of a feature that go into a batch upload: all of them when the feature fits; for the device TRIANGULATION a
   // feature that does not fit still takes part with its first OVP_MAX_MEAS measurements of camera 0 (a position estimate needs
   // no more; the update below linearises over all of them); for the update's batches it has none
+  // StateOptions::gpu_general_features: such a feature takes the general-feature entries instead, when its track fits them
+  const bool gen_on = state->_options.gpu_general_features;
+  auto fits_general = [&](const ov_core::Feature &f) { return gen_on && (int)f.timestamps.size() <= OVP_GEN_MAX_MEAS; };
   auto batch_meas = [&](const ov_core::Feature &f, bool for_triangulation) {
     std::vector<size_t> sel;
     if (fits_batch(f)) {
       for (size_t k = 0; k < f.timestamps.size(); ++k) sel.push_back(k);
-    } else if (for_triangulation) {
+    } else if (for_triangulation && !fits_general(f)) {
       for (size_t k = 0; k < f.timestamps.size() && (int)sel.size() < OVP_MAX_MEAS; ++k)
         if (f.cam_of(k) == 0) sel.push_back(k);
     }
@@ -766,6 +769,56 @@ void UpdaterMSCKF::update(std::shared_ptr<State> state, std::vector<std::shared_
     ovp_feature_batch fb{F, M, uv.data(), cidx.data(), nm.data(), pf.data()};
     gpu_check(ovp_batch_upload(state->_gpu, &fb), "ovp_batch_upload");
     return M;
+  };
+  // every camera's tables and a general batch of features (all of their measurements) for the general-feature entries
+  auto upload_cameras = [&]() {
+    std::vector<ovp_camera_tables> cams(state->_options.num_cameras);
+    for (int k = 0; k < state->_options.num_cameras; ++k) {
+      auto calib = state->_calib_IMUtoCAM.at(k);
+      auto intr = state->_cam_intrinsics.at(k);
+      memcpy(cams[k].calib_q, calib->quat(), 4 * sizeof(double));
+      memcpy(cams[k].calib_p, calib->pos(), 3 * sizeof(double));
+      cams[k].calib_id = calib->id();
+      memcpy(cams[k].intrinsics, intr->value().data(), 8 * sizeof(double));
+      cams[k].intr_id = intr->id();
+      cams[k].fisheye = (state->_cam_fisheye.count(k) && state->_cam_fisheye.at(k)) ? 1 : 0;
+    }
+    gpu_check(ovp_cameras_upload(state->_gpu, (int)cams.size(), cams.data()), "ovp_cameras_upload");
+  };
+  struct GeneralBatch {
+    std::vector<float> uv, uvn;
+    std::vector<int> cidx, cam, nm;
+    std::vector<double> pf;
+    ovp_general_batch b;
+  };
+  auto general_batch = [&](const std::vector<size_t> &idx, GeneralBatch &g) {
+    const int F = (int)idx.size();
+    int M = 1;
+    for (size_t f : idx) M = std::max(M, (int)feature_vec[f]->timestamps.size());
+    g.uv.assign((size_t)F * M * 2, 0.f);
+    g.uvn.assign((size_t)F * M * 2, 0.f);
+    g.cidx.assign((size_t)F * M, 0);
+    g.cam.assign((size_t)F * M, 0);
+    g.nm.assign(F, 0);
+    g.pf.assign((size_t)F * 3, 0.0);
+    for (int i = 0; i < F; ++i) {
+      const ov_core::Feature &ft = *feature_vec[idx[i]];
+      const bool has_norm = ft.uvs_norm.size() == ft.uvs.size();
+      g.nm[i] = (int)ft.timestamps.size();
+      for (int k = 0; k < g.nm[i]; ++k) {
+        const size_t o = (size_t)i * M + k;
+        g.cidx[o] = clone_slot.at(ft.timestamps[k]);
+        g.cam[o] = ft.cam_of(k);
+        g.uv[2 * o] = ft.uvs[2 * k];
+        g.uv[2 * o + 1] = ft.uvs[2 * k + 1];
+        if (has_norm) {
+          g.uvn[2 * o] = ft.uvs_norm[2 * k];
+          g.uvn[2 * o + 1] = ft.uvs_norm[2 * k + 1];
+        }
+      }
+      memcpy(&g.pf[3 * i], ft.p_FinG, 3 * sizeof(double));
+    }
+    g.b = ovp_general_batch{F, M, g.uv.data(), g.cidx.data(), g.cam.data(), g.nm.data(), g.pf.data()};
   };
   ovp_update_opts o{_options.sigma_pix,
                     _options.chi2_multipler,
@@ -809,6 +862,24 @@ void UpdaterMSCKF::update(std::shared_ptr<State> state, std::vector<std::shared_
       std::vector<double> pf((size_t)F * 3);
       std::vector<uint8_t> okv(F, 0);
       gpu_check(ovp_triangulate(state->_gpu, &to, uvn.data(), pf.data(), okv.data()), "ovp_triangulate");
+      {  // StateOptions::gpu_general_features: the features the batch cannot carry, over every camera's observations
+        std::vector<size_t> gidx;
+        for (int f = 0; f < F; ++f)
+          if (!fits_batch(*feature_vec[f]) && fits_general(*feature_vec[f]) && feature_vec[f]->uvs_norm.size() == feature_vec[f]->uvs.size())
+            gidx.push_back(f);
+        if (!gidx.empty()) {
+          upload_cameras();
+          GeneralBatch g;
+          general_batch(gidx, g);
+          std::vector<double> gpf(gidx.size() * 3);
+          std::vector<uint8_t> gok(gidx.size(), 0);
+          gpu_check(ovp_triangulate_general(state->_gpu, &to, &g.b, g.uvn.data(), gpf.data(), gok.data()), "ovp_triangulate_general");
+          for (size_t i = 0; i < gidx.size(); ++i) {
+            okv[gidx[i]] = gok[i];
+            memcpy(&pf[3 * gidx[i]], &gpf[3 * i], 3 * sizeof(double));
+          }
+        }
+      }
       size_t f = 0;
       auto it1 = feature_vec.begin();
       while (it1 != feature_vec.end()) {
@@ -1142,7 +1213,16 @@ void UpdaterMSCKF::update(std::shared_ptr<State> state, std::vector<std::shared_
   for (size_t f = 0; f < feature_vec.size(); ++f)
     if (!fits_batch(*feature_vec[f])) dense_idx.push_back(f);
   std::vector<uint8_t> dense_ok(dense_idx.size(), 0);
-  if (!dense_idx.empty()) {
+  // StateOptions::gpu_general_features: rows, projection and gate on the device (a frame with a track above OVP_GEN_MAX_MEAS keeps the
+  // host blocks for all of them: the two entries share the one pending pair of the context)
+  bool dense_on_device = gen_on && !dense_idx.empty();
+  for (size_t f : dense_idx) dense_on_device = dense_on_device && fits_general(*feature_vec[f]);
+  if (dense_on_device) {
+    upload_cameras();
+    GeneralBatch g;
+    general_batch(dense_idx, g);
+    gpu_check(ovp_msckf_general_features(state->_gpu, &o, &g.b, dense_ok.data(), nullptr), "ovp_msckf_general_features");
+  } else if (!dense_idx.empty()) {
     std::vector<int> b_rows, b_cols, b_ids;
     std::vector<double> b_H, b_res;
     for (size_t f : dense_idx) {

@@ -61,6 +61,10 @@ struct StateOptions {
   // HIP device the State's context (covariance, pose tables, feature batches) lives on.  One process per GPU: rank r of a
   // multi-GPU job constructs its replica of the filter with gpu_device = its local rank.  Not in the reference.
   int gpu_device = 0;
+  // UpdaterMSCKF::update: features the device batch cannot carry (another camera's observations, more than OVP_MAX_MEAS of them)
+  // are triangulated over every camera (ovp_triangulate_general) and linearised, projected and gated on the device
+  // (ovp_msckf_general_features) instead of as dense blocks built on the host (ovp_msckf_dense_blocks).  Not in the reference.
+  bool gpu_general_features = false;
 };
 
 // update/UpdaterOptions.h:37-53

@@ -115,14 +115,17 @@ __device__ __forceinline__ void ordered_sum(const double* buf, int m, double (&a
   }
 }
 
-__global__ __launch_bounds__(TRI_WAVES * 64) void k_triangulate(const TriParams p) {
-  __shared__ __attribute__((aligned(16))) double stage[TRI_WAVES][OVP_MAX_MEAS * TRI_PITCH];
+// MAXM observations per feature at most; GEN: observation k was taken by camera cam_idx[f][k], whose tables are p.cal + 20 cam
+// (the general batch of ovp_triangulate_general); otherwise every observation is camera 0's and p.cal its tables.
+template <int MAXM, bool GEN>
+__device__ __forceinline__ void triangulate_body(const TriParams& p, const int* cam_idx) {
+  __shared__ __attribute__((aligned(16))) double stage[TRI_WAVES][MAXM * TRI_PITCH];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int f = blockIdx.x * TRI_WAVES + wave;
   if (f >= p.n_feats) return;  // whole wave
   double* buf = stage[wave];
   const int m = p.n_meas[f];
-  if (m < 2 || m > OVP_MAX_MEAS) {
+  if (m < 2 || m > MAXM) {
     if (lane == 0) {
       p.ok[f] = 0;
       p.p_FinG[3 * f] = p.p_FinG[3 * f + 1] = p.p_FinG[3 * f + 2] = 0.0;
@@ -131,9 +134,11 @@ __global__ __launch_bounds__(TRI_WAVES * 64) void k_triangulate(const TriParams 
   }
   const bool act = lane < m;
   const int* cidx = p.clone_idx + (size_t)f * p.max_meas;
-  const double* cal = p.cal;  // [0..8] R_ItoC, [9..11] p_IinC
+  const int* cams = GEN ? cam_idx + (size_t)f * p.max_meas : nullptr;
   // camera pose of a clone slot: R_GtoC = R_ItoC R_GtoI ; p_CinG = p_IinG - R_GtoC^T p_IinC   (UpdaterMSCKF.cpp:129-130)
-  auto cam_pose = [&](int slot, double (&R)[9], double (&pc)[3]) {
+  auto cam_pose = [&](int k, double (&R)[9], double (&pc)[3]) {
+    const int slot = cidx[k];
+    const double* cal = GEN ? p.cal + 20 * cams[k] : p.cal;  // [0..8] R_ItoC, [9..11] p_IinC
     const double* RI = p.clone_R + 9 * slot;
     const double* pI = p.clone_p + 3 * slot;
 #pragma unroll
@@ -143,10 +148,17 @@ __global__ __launch_bounds__(TRI_WAVES * 64) void k_triangulate(const TriParams 
 #pragma unroll
     for (int a = 0; a < 3; ++a) pc[a] = pI[a] - (R[a] * cal[9] + R[3 + a] * cal[10] + R[6 + a] * cal[11]);
   };
+  // anchor = last measurement (of the lowest camera index that saw the feature: ext Feature::anchor_cam_id)
+  int anchor = m - 1;
+  if constexpr (GEN) {
+    int cmin = cams[0];
+    for (int k = 1; k < m; ++k) cmin = cams[k] < cmin ? cams[k] : cmin;
+    while (cams[anchor] != cmin) --anchor;
+  }
   double R_GtoA[9], p_AinG[3];
-  cam_pose(cidx[m - 1], R_GtoA, p_AinG);  // anchor = last measurement
+  cam_pose(anchor, R_GtoA, p_AinG);
   double R_GtoCi[9], p_CiinG[3];
-  cam_pose(cidx[act ? lane : 0], R_GtoCi, p_CiinG);
+  cam_pose(act ? lane : 0, R_GtoCi, p_CiinG);
   const float un = p.uvn[((size_t)f * p.max_meas + (act ? lane : 0)) * 2];
   const float vn = p.uvn[((size_t)f * p.max_meas + (act ? lane : 0)) * 2 + 1];
   // relative pose of this observation's camera with respect to the anchor
@@ -200,7 +212,7 @@ __global__ __launch_bounds__(TRI_WAVES * 64) void k_triangulate(const TriParams 
   if (p.triangulate_1d) {
     // ext single_triangulation_1d: depth d along the anchor bearing a from  sum_i |S_i a|^2 d = sum_i (S_i a).(S_i p_CiinA),
     // S_i = skew(b_i); the anchor's own observation is skipped, no condition-number test
-    const float ua = p.uvn[((size_t)f * p.max_meas + (m - 1)) * 2], va = p.uvn[((size_t)f * p.max_meas + (m - 1)) * 2 + 1];
+    const float ua = p.uvn[((size_t)f * p.max_meas + anchor) * 2], va = p.uvn[((size_t)f * p.max_meas + anchor) * 2 + 1];
     double a[3] = {(double)ua, (double)va, 1.0};
     const double na = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
 #pragma unroll
@@ -217,15 +229,15 @@ __global__ __launch_bounds__(TRI_WAVES * 64) void k_triangulate(const TriParams 
       const double Sa[3] = {bi[1] * a[2] - bi[2] * a[1], bi[2] * a[0] - bi[0] * a[2], bi[0] * a[1] - bi[1] * a[0]};
       const double Sp[3] = {bi[1] * pCinA[2] - bi[2] * pCinA[1], bi[2] * pCinA[0] - bi[0] * pCinA[2],
                             bi[0] * pCinA[1] - bi[1] * pCinA[0]};
-      const bool anchor = lane == m - 1;
-      buf[lane * TRI_PITCH + 0] = anchor ? 0.0 : (Sa[0] * Sa[0] + Sa[1] * Sa[1] + Sa[2] * Sa[2]);
-      buf[lane * TRI_PITCH + 1] = anchor ? 0.0 : (Sa[0] * Sp[0] + Sa[1] * Sp[1] + Sa[2] * Sp[2]);
+      const bool is_anchor = lane == anchor;
+      buf[lane * TRI_PITCH + 0] = is_anchor ? 0.0 : (Sa[0] * Sa[0] + Sa[1] * Sa[1] + Sa[2] * Sa[2]);
+      buf[lane * TRI_PITCH + 1] = is_anchor ? 0.0 : (Sa[0] * Sp[0] + Sa[1] * Sp[1] + Sa[2] * Sp[2]);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     double A1 = 0.0, b1 = 0.0;
-    for (int k = 0; k < m - 1; ++k) {
+    for (int k = 0; k < (GEN ? m : m - 1); ++k) {  // (the anchor's own slot holds zeros)
       A1 += buf[k * TRI_PITCH + 0];
       b1 += buf[k * TRI_PITCH + 1];
     }
@@ -358,7 +370,20 @@ __global__ __launch_bounds__(TRI_WAVES * 64) void k_triangulate(const TriParams 
   }
 }
 
+__global__ __launch_bounds__(TRI_WAVES * 64) void k_triangulate(const TriParams p) { triangulate_body<OVP_MAX_MEAS, false>(p, nullptr); }
+
+__global__ __launch_bounds__(TRI_WAVES * 64) void k_triangulate_gen(const TriParams p, const int* cam_idx) {
+  triangulate_body<OVP_GEN_MAX_MEAS_DEV, true>(p, cam_idx);
+}
+
 }  // namespace ovp
+
+extern "C" hipError_t ovp_launch_triangulate_gen(const ovp::TriParams* p, const int* cam_idx, hipStream_t stream) {
+  if (p->n_feats <= 0) return hipSuccess;
+  hipLaunchKernelGGL(ovp::k_triangulate_gen, dim3((p->n_feats + ovp::TRI_WAVES - 1) / ovp::TRI_WAVES), dim3(ovp::TRI_WAVES * 64), 0,
+                     stream, *p, cam_idx);
+  return hipGetLastError();
+}
 
 extern "C" hipError_t ovp_launch_triangulate(const ovp::TriParams* p, hipStream_t stream) {
   if (p->n_feats <= 0) return hipSuccess;

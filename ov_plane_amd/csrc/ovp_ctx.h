@@ -6,6 +6,7 @@
 //   ovp_api_rccl.hip   feature-sharded update over RCCL
 //   ovp_api_plane.hip  plane loop (ovp_msckf_plane_update) and plane initialisation (ovp_plane_init)
 //   ovp_api_slam.hip   SLAM landmarks (ovp_slam_update, ovp_slam_delayed_init), triangulation
+//   ovp_api_general.hip general point features (any camera, long tracks): camera tables, gate + pending pair, triangulation
 #pragma once
 #include "ovplane_hip.h"
 
@@ -168,6 +169,15 @@ struct ovp_ctx {
   // point update of the same frame (added to Ab behind K2); empty = none
   std::vector<int> dense_cols;
   std::vector<double> dense_A, dense_b;
+  // general features (ovp_api_general.hip): camera tables of ovp_cameras_upload (host copy + device [OVP_MAX_CAMERAS][20] in the
+  // layout of `cal`) and the device scratch of ovp_msckf_general_features / ovp_triangulate_general
+  int gen_ncams = 0;
+  int gen_calib_id[OVP_MAX_CAMERAS] = {-1, -1, -1, -1}, gen_intr_id[OVP_MAX_CAMERAS] = {-1, -1, -1, -1};
+  int gen_fisheye[OVP_MAX_CAMERAS] = {0, 0, 0, 0};
+  double gen_cal_h[OVP_MAX_CAMERAS * 20] = {};
+  double* gen_cal = nullptr;
+  void* gen_buf = nullptr;
+  size_t gen_cap = 0;
   void* slam_res = nullptr;        // ovp_slam_update: per-landmark [chi2 | status]
   double* slam_hscr = nullptr;     // ... blocks that do not fit LDS
   size_t slam_res_cap = 0, slam_hscr_cap = 0;
@@ -301,6 +311,7 @@ static hipError_t dalloc(T** p, size_t count) {
 }
 
 // ---- shared between the entry-point files ------------------------------------------------------------------------------------
+void quat_2_rot(const double q[4], double R[9]);  // JPL quaternion -> row-major rotation (ovp_api_ctx.hip)
 extern "C" int ovp_io_arena(ovp_ctx* c, size_t bytes, void** host, void** dev);  // pinned staging arena (ovp_api_ctx.hip)
 // ovp_api_point.hip
 int fill_feat_params(ovp_ctx* c, const ovp_update_opts* o);

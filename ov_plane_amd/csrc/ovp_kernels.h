@@ -111,6 +111,39 @@ struct TriParams {
   unsigned char* ok;      // [n_feats] out
 };
 
+// arguments of the general-feature kernels (k_feat_gen.hip): any camera per observation, up to OVP_GEN_MAX_MEAS_DEV observations
+#define OVP_GEN_MAX_MEAS_DEV 64
+#define OVP_GEN_MAX_CAMS 4
+struct GenParams {
+  FeatParams fp;              // clone tables, do_fej, white_px, calmask; cal / fisheye / uv / p_FinG are set per observation
+  const double* cam_cal;      // [OVP_GEN_MAX_CAMS][20] per camera, the layout of FeatParams::cal
+  int cam_fisheye[OVP_GEN_MAX_CAMS];
+  int cam_calib_id[OVP_GEN_MAX_CAMS], cam_intr_id[OVP_GEN_MAX_CAMS];
+  // the batch (device)
+  const float* uv;
+  const int* clone_idx;
+  const int* cam_idx;
+  const int* n_meas;
+  const double* p_FinG;
+  int n_feats, max_meas;
+  // gate
+  const double* P;
+  int ldp;
+  const double* chi2_table;
+  double chi2_mult;
+  // projected rows of the accepted features: the union of the involved state columns is numbered 0..nu-1 (upos[state column], -1 =
+  // not involved); feature f owns q[f] of them, local column loc[f * nu + u] (-1 = not its column), and the block hp + hp_off[f]:
+  // Hp [2m x q[f]] column-major, then the projected residual [2m]
+  const int* upos;
+  const int* loc;
+  const int* q;
+  const long long* hp_off;
+  int nu;
+  double* hp;
+  double* chi2;          // [n_feats] out
+  unsigned char* accept;  // [n_feats] out
+};
+
 // per-plane arguments of the plane feature kernel
 struct PlaneParams {
   const int* feat_list;  // [n_local] indices into the feature batch
@@ -141,6 +174,12 @@ int ovp_feat_chol_supported(const ovp::FeatParams* p, int n);
 int ovp_feat_chol_side_capacity(void);
 hipError_t ovp_launch_feat_chol(const ovp::FeatParams* p, const ovp::CholJob* c, hipStream_t stream);
 hipError_t ovp_launch_triangulate(const ovp::TriParams* p, hipStream_t stream);
+// general batch: cam_idx [n_feats][max_meas], p->cal = [OVP_GEN_MAX_CAMS][20] camera tables (k_triang.hip)
+hipError_t ovp_launch_triangulate_gen(const ovp::TriParams* p, const int* cam_idx, hipStream_t stream);
+// k_feat_gen.hip: rows + projection + gate of every feature of a general batch, then the information pair of the accepted ones
+// over the union of their columns: A [nu x nu], b [nu]
+hipError_t ovp_launch_feat_gen(const ovp::GenParams* g, hipStream_t stream);
+hipError_t ovp_launch_gen_pair(const ovp::GenParams* g, double* A, double* b, hipStream_t stream);
 
 // K2a: per-clone structured Gram of the sparse rows. gramS [n_clones][n_chunks][OVP_GRAM_ELEMS]
 hipError_t ovp_launch_struct_gram(const double* rec, int n_clones, int n_feats, int rows_per_chunk, int n_chunks,

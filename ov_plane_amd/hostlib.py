@@ -22,14 +22,17 @@ def lib():
     return _LIB
 
 
-def run_msckf_update(sc, triangulate=False, fit_planes=None, comm=None, rank=0, world=1, device=0):
+def run_msckf_update(sc, triangulate=False, fit_planes=None, comm=None, rank=0, world=1, device=0, general_features=False):
     """Drives ov_plane::UpdaterMSCKF::update (C++ host classes over the C-ABI) on a synth.Scene.
     triangulate=True: the features carry uvs_norm and no position; the updater triangulates them first.
     fit_planes=dict(min_feat, max_cond, variant): no plane estimates are handed over - the updater fits the planes that are
     not in the state (PlaneFitting::plane_fitting) and refines planes and on-plane features (optimize_plane) itself.
     comm / rank / world / device: UpdaterMSCKF::set_communicator + StateOptions::gpu_device - the point loop goes through
-    ovp_msckf_update_sharded on this rank's share (out["shard"] = its index range of the point batch)."""
+    ovp_msckf_update_sharded on this rank's share (out["shard"] = its index range of the point batch).
+    general_features: StateOptions::gpu_general_features - the features the device batch cannot carry (another camera, a track
+    longer than OVP_MAX_MEAS) are triangulated and gated on the device (ovp_triangulate_general / ovp_msckf_general_features)."""
     L = lib()
+    L.ovph_set_general_features(1 if general_features else 0)
     cam1 = sc.get("cam1", None)  # synth.make_stereo_scene: dict(calib_q, calib_p, intr), sc.cam_idx [F, M]
     if cam1 is not None:
         c1q, c1p, c1i = (np.ascontiguousarray(cam1[k], dtype=np.float64) for k in ("calib_q", "calib_p", "intr"))
