@@ -393,6 +393,31 @@ int ovp_slam_update(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp_slam_ba
 int ovp_slam_delayed_init(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp_feature_batch *candidates, uint8_t *ok,
                           double *chi2, int *new_id, double *delta_init, double *dx, int dx_stride);
 
+/* ---- SLAM landmarks seen by any camera (csrc/k_slam.hip k_slam_gate_gen, csrc/k_dinit.hip k_dinit_rows_gen) ----------------------
+ * The two SLAM entries above read camera 0's tables of ovp_state_upload for every observation.  These read EVERY camera, camera 0
+ * included, from the tables of ovp_cameras_upload: observation k of landmark / candidate l was taken by camera
+ * cam_idx[l * max_meas + k] (update/UpdaterHelper.cpp:335-344 loops over the cameras of a feature).  OVP_E_ARG without those tables
+ * or with a cam_idx outside [0, n_cams).
+ *
+ * ovp_slam_update_general: ovp_slam_update's semantics, outputs and status codes (bearing rows, point-on-plane rows of in-state
+ * planes, the no-plane fallback = status 2, host-built pre_* blocks in the same call, one EKF update); a landmark's block spans its
+ * clones, the estimated calibration columns of every camera that observed it, the landmark and its plane.  n_meas <= OVP_MAX_MEAS
+ * per landmark (the new observations of this update).  OVP_E_CAPACITY: a block beyond the gate kernel's LDS - nothing was
+ * enqueued, the covariance is unchanged, the caller may take its dense form. */
+int ovp_slam_update_general(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp_slam_batch *batch, const int *cam_idx,
+                            double *dx_host, uint8_t *status, double *chi2, ovp_update_info *info);
+
+/* ovp_slam_delayed_init_general: ovp_slam_delayed_init's contract (GLOBAL_3D candidates without plane rows, one enqueue, inert
+ * blocks of rejected candidates removed behind the loop, ids handed out in order) for candidates of a general batch (p_FinG = their
+ * triangulated positions).  A candidate's H_x spans the clone blocks of its distinct clones (a clone seen by two cameras is one
+ * block) and the estimated calibration columns of each of its cameras.  Every candidate's commit applies the previous correction
+ * to the pose tables, to camera 0's calibration of ovp_state_upload and to every camera of ovp_cameras_upload: after the call the
+ * device tables are what the caller gets by applying the returned dx in order (ovp_msckf_general_features reads them without a
+ * re-upload).  At most OVP_MAX_MEAS observations per candidate; a candidate beyond that or beyond the one-workgroup S-form
+ * (k_init.hip) gives OVP_E_CAPACITY with nothing touched. */
+int ovp_slam_delayed_init_general(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp_general_batch *candidates, uint8_t *ok,
+                                  double *chi2, int *new_id, double *delta_init, double *dx, int dx_stride);
+
 /* StateHelper::EKFPropagation (state/StateHelper.cpp:41-119): new variables occupy [new_start, new_start+phi_size),
  * Phi is [phi_size x sum(old_sizes)] column-major, Q is [phi_size x phi_size] (upper triangle read). */
 int ovp_cov_propagate(ovp_ctx *ctx, int new_start, int phi_size, const int *old_ids, const int *old_sizes, int n_old,

@@ -167,7 +167,7 @@ EXPORTS = [
     "ovp_slam_update", "ovp_cov_clone_jitter", "ovp_rccl_unique_id", "ovp_rccl_comm_create", "ovp_rccl_comm_destroy",
     "ovp_rccl_allreduce_gram", "ovp_msckf_update_sharded", "ovp_slam_delayed_init", "ovp_shard_range", "ovp_shard_range_of_mask",
     "ovp_rccl_gather_decisions", "ovp_msckf_dense_blocks", "ovp_cameras_upload", "ovp_msckf_general_features",
-    "ovp_triangulate_general",
+    "ovp_triangulate_general", "ovp_slam_update_general", "ovp_slam_delayed_init_general",
 ]
 
 
@@ -224,6 +224,10 @@ def lib():
                                                C.c_void_p, C.POINTER(UpdateInfo), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.ovp_slam_update.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(SlamBatch), C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(UpdateInfo)]
+        L.ovp_slam_update_general.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(SlamBatch), C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.POINTER(UpdateInfo)]
+        L.ovp_slam_delayed_init_general.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(GeneralBatch), C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.ovp_msckf_plane_update.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(PlaneBatch), C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ovp_plane_init.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(PlaneBatch), C.c_double, C.c_double,
@@ -700,6 +704,34 @@ class Context:
         """ovp_slam_update (UpdaterSLAM::update on the device).  pre: optional list with one entry per landmark, None (rows built
         on the device) or (H [rows x cols], col_ids [cols], res [rows]) for a block the host built.
         Returns dict(dx, status [L] (0 rejected / 1 accepted / 2 accepted without its plane), chi2 [L], info, rc)."""
+        sb, keep = self._slam_batch(uv, clone_idx, n_meas, p_FinG, p_FinG_fej, landmark_id, plane_state_id, cp, cp_fej, pre)
+        return self._slam_call("ovp_slam_update", sb, opts, raise_on_error)
+
+    def slam_update_general(self, opts: UpdateOpts, uv, clone_idx, cam_idx, n_meas, p_FinG, p_FinG_fej, landmark_id, plane_state_id=None,
+                            cp=None, cp_fej=None, pre=None, raise_on_error=True):
+        """ovp_slam_update_general: slam_update with the camera of every observation (cam_idx [L, max_meas]), every camera's tables
+        from cameras_upload.  Same results."""
+        sb, keep = self._slam_batch(uv, clone_idx, n_meas, p_FinG, p_FinG_fej, landmark_id, plane_state_id, cp, cp_fej, pre)
+        L, M = sb.n_landmarks, sb.max_meas
+        cam = np.ascontiguousarray(cam_idx, dtype=np.int32).reshape(L, M) if L else np.zeros((0, M), np.int32)
+        return self._slam_call("ovp_slam_update_general", sb, opts, raise_on_error, cam)
+
+    def _slam_call(self, fn, sb, opts, raise_on_error, cam=None):
+        L = sb.n_landmarks
+        n = self.cov_size()
+        dx = np.zeros(n)
+        status = np.zeros(max(L, 1), dtype=np.uint8)
+        chi2 = np.zeros(max(L, 1))
+        info = UpdateInfo()
+        args = (self._h, C.byref(opts), C.byref(sb)) + ((cam.ctypes.data,) if cam is not None else ()) + (
+            dx.ctypes.data, status.ctypes.data, chi2.ctypes.data, C.byref(info))
+        rc = getattr(lib(), fn)(*args)
+        if raise_on_error:
+            _chk(rc, fn)
+        return dict(dx=dx, status=status[:L], chi2=chi2[:L], info=info, rc=rc)
+
+    @staticmethod
+    def _slam_batch(uv, clone_idx, n_meas, p_FinG, p_FinG_fej, landmark_id, plane_state_id=None, cp=None, cp_fej=None, pre=None):
         n_meas = np.ascontiguousarray(n_meas, dtype=np.int32)
         L = int(n_meas.shape[0])
         uv = np.ascontiguousarray(uv, dtype=np.float32)
@@ -736,16 +768,9 @@ class Context:
             pi = np.ascontiguousarray(np.concatenate(ii))
             sb.pre_rows, sb.pre_cols, sb.pre_H, sb.pre_ids = pr.ctypes.data, pc.ctypes.data, ph.ctypes.data, pi.ctypes.data
             keep += [pr, pc, ph, pi]
-        n = self.cov_size()
-        dx = np.zeros(n)
-        status = np.zeros(max(L, 1), dtype=np.uint8)
-        chi2 = np.zeros(max(L, 1))
-        info = UpdateInfo()
-        rc = lib().ovp_slam_update(self._h, C.byref(opts), C.byref(sb), dx.ctypes.data, status.ctypes.data, chi2.ctypes.data,
-                                   C.byref(info))
-        if raise_on_error:
-            _chk(rc, "ovp_slam_update")
-        return dict(dx=dx, status=status[:L], chi2=chi2[:L], info=info, rc=rc)
+        sb._keep = keep
+        keep.append(n_meas)
+        return sb, keep
 
     def slam_delayed_init(self, opts: UpdateOpts, uv, clone_idx, n_meas, p_FinG, raise_on_error=True):
         """ovp_slam_delayed_init: the candidate loop of UpdaterSLAM::delayed_init on the device.  Returns dict(ok [L], chi2 [L],
@@ -768,6 +793,28 @@ class Context:
         if raise_on_error:
             _chk(rc, "ovp_slam_delayed_init")
         return dict(ok=ok[:L].astype(bool), chi2=chi2[:L], new_id=nid[:L], delta_init=dl[:L], dx=dx[:L], rc=rc)
+
+    def slam_delayed_init_general(self, opts: UpdateOpts, uv, clone_idx, cam_idx, n_meas, p_FinG, raise_on_error=True):
+        """ovp_slam_delayed_init_general: slam_delayed_init with the camera of every observation (cam_idx [L, max_meas]), every
+        camera's tables from cameras_upload (and updated on the device by every accepted candidate).  Same results."""
+        gb = self._general_batch(uv, clone_idx, cam_idx, n_meas, p_FinG)
+        L = gb.n_feats
+        stride = self.cov_size() + 3 * L
+        ok = np.zeros(max(L, 1), dtype=np.uint8)
+        chi2 = np.zeros(max(L, 1))
+        nid = -np.ones(max(L, 1), dtype=np.int32)
+        dl = np.zeros((max(L, 1), 3))
+        dx = np.zeros((max(L, 1), stride))
+        rc = lib().ovp_slam_delayed_init_general(self._h, C.byref(opts), C.byref(gb), ok.ctypes.data, chi2.ctypes.data, nid.ctypes.data,
+                                                 dl.ctypes.data, dx.ctypes.data, stride)
+        if raise_on_error:
+            _chk(rc, "ovp_slam_delayed_init_general")
+        return dict(ok=ok[:L].astype(bool), chi2=chi2[:L], new_id=nid[:L], delta_init=dl[:L], dx=dx[:L], rc=rc)
+
+    def camera_tables_download(self, n_cams):
+        """The device's camera tables: (camera 0's of state_upload [20], the n_cams cameras of cameras_upload [n_cams, 20]); layout
+        [R_ItoC row-major (9) | p_IinC (3) | intrinsics (8)]."""
+        return self.debug_read("cal", (20,)), self.debug_read("gen_cal", (n_cams, 20))
 
     def cov_initialize(self, Hx_init, H_up, col_ids, H_Linv, R_init, res_up, r_iso, chi2_threshold, do_update=True):
         """StateHelper::initialize downstream of its Givens split as one device sequence (state/StateHelper.cpp:448-487):

@@ -54,6 +54,12 @@ extern "C" void ovph_set_second_camera(const double *calib_q, const double *cali
 // next ovph_run_msckf_update: StateOptions::gpu_general_features
 static int g_general = 0;
 extern "C" void ovph_set_general_features(int on) { g_general = on != 0; }
+// next ovph_run_updater: StateOptions::gpu_general_slam
+static int g_general_slam = 0;
+extern "C" void ovph_set_general_slam(int on) { g_general_slam = on != 0; }
+// path of the last UpdaterSLAM::update / delayed_init (UpdaterSLAM::Route: 1 device general, 2 device mono, 3 dense host, 4
+// per-candidate host loop, 0 none)
+extern "C" int ovph_last_slam_route() { return UpdaterSLAM::last_route(); }
 // next ovph_run_msckf_update: the State lives on this device and the updater takes the sharded point loop on this communicator
 static void *g_comm = nullptr;
 static int g_comm_rank = 0, g_comm_world = 1, g_device = 0, g_last_shard[2] = {0, 0};
@@ -336,11 +342,24 @@ struct HarnessState {
 int build_harness_state(HarnessState &hs, StateOptions &so, int C, const double *clone_q, const double *clone_p,
                         const double *clone_q_fej, const double *clone_p_fej, const double *calib_q, const double *calib_p,
                         const double *intr, int n_slam, const double *slam_p, const double *slam_p_fej, int n_planes,
-                        const double *cp, const double *cp_fej, int N, const double *P) {
+                        const double *cp, const double *cp_fej, int N, const double *P, bool second_camera = false) {
+  // second_camera: camera 1 of ovph_set_second_camera, its calibration behind camera 0's (= synth.make_stereo_scene's layout)
+  if (second_camera) so.num_cameras = 2;
   hs.state = std::make_shared<State>(so);
   auto &state = hs.state;
   state->_cam_fisheye[0] = g_fisheye != 0;
   g_fisheye = 0;
+  if (second_camera) {
+    VectorXd v1(7, 1), iv1(8, 1);
+    for (int k = 0; k < 4; ++k) v1(k) = g_cam1_q[k];
+    for (int k = 0; k < 3; ++k) v1(4 + k) = g_cam1_p[k];
+    for (int k = 0; k < 8; ++k) iv1(k) = g_cam1_intr[k];
+    state->_calib_IMUtoCAM.at(1)->set_value(v1);
+    state->_calib_IMUtoCAM.at(1)->set_fej(v1);
+    state->_cam_intrinsics.at(1)->set_value(iv1);
+    state->_cam_intrinsics.at(1)->set_fej(iv1);
+    state->_cam_fisheye[1] = false;
+  }
   VectorXd v(7, 1);
   for (int k = 0; k < 4; ++k) v(k) = calib_q[k];
   for (int k = 0; k < 3; ++k) v(4 + k) = calib_p[k];
@@ -400,6 +419,10 @@ int build_harness_state(HarnessState &hs, StateOptions &so, int C, const double 
   order.push_back(state->_calib_dt_CAMtoIMU);
   order.push_back(state->_calib_IMUtoCAM.at(0));
   order.push_back(state->_cam_intrinsics.at(0));
+  if (second_camera) {
+    order.push_back(state->_calib_IMUtoCAM.at(1));
+    order.push_back(state->_cam_intrinsics.at(1));
+  }
   for (auto &c : state->_clones_IMU) order.push_back(c.second);
   for (auto &l : hs.landmarks) order.push_back(l);
   for (auto &p : hs.planes) order.push_back(p);
@@ -410,7 +433,8 @@ int build_harness_state(HarnessState &hs, StateOptions &so, int C, const double 
 }
 
 std::vector<std::shared_ptr<ov_core::Feature>> make_features(const HarnessState &hs, int F, int M, const float *uv, const int *clone_idx,
-                                                             const int *n_meas, const double *p_FinG, size_t id0) {
+                                                             const int *n_meas, const double *p_FinG, size_t id0,
+                                                             const int *cam_of = nullptr) {
   std::vector<std::shared_ptr<ov_core::Feature>> fv;
   for (int f = 0; f < F; ++f) {
     auto ft = std::make_shared<ov_core::Feature>();
@@ -419,6 +443,7 @@ std::vector<std::shared_ptr<ov_core::Feature>> make_features(const HarnessState 
       ft->timestamps.push_back(hs.times[clone_idx[(size_t)f * M + k]]);
       ft->uvs.push_back(uv[((size_t)f * M + k) * 2]);
       ft->uvs.push_back(uv[((size_t)f * M + k) * 2 + 1]);
+      if (cam_of) ft->cam_ids.push_back(cam_of[(size_t)f * M + k]);
     }
     if (g_uv_norm) {  // features as the tracker hands them over: normalised measurements, no position yet
       for (int k = 0; k < n_meas[f]; ++k) {
@@ -451,6 +476,11 @@ void export_state(const HarnessState &hs, double *out_clone_q, double *out_clone
   MatrixXd Pn = StateHelper::get_full_covariance(state);
   memcpy(out_P, Pn.data(), sizeof(double) * (size_t)n2 * n2);
   *out_n = n2;
+  if (state->_options.num_cameras > 1) {  // camera 1 (ovph_last_second_camera)
+    memcpy(g_last_cam1, state->_calib_IMUtoCAM.at(1)->quat(), 4 * sizeof(double));
+    memcpy(g_last_cam1 + 4, state->_calib_IMUtoCAM.at(1)->pos(), 3 * sizeof(double));
+    memcpy(g_last_cam1 + 7, state->_cam_intrinsics.at(1)->value().data(), 8 * sizeof(double));
+  }
 }
 }  // namespace
 
@@ -486,13 +516,20 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
   }
   so.max_state_size = n_cap;
   so.max_features = F + 8;
+  so.gpu_general_slam = g_general_slam != 0;
+  g_general_slam = 0;
+  // ovph_set_second_camera: a stereo state (camera 1's calibration behind camera 0's) and the camera of every measurement
+  const bool cam1 = g_cam1_q != nullptr;
+  const int *cam_of = g_cam_of_meas;
   HarnessState hs;
   int rc = build_harness_state(hs, so, C, clone_q, clone_p, clone_q_fej, clone_p_fej, calib_q, calib_p, intr, n_slam, slam_p,
-                               slam_p_fej, n_planes, cp, cp_fej, N, P);
+                               slam_p_fej, n_planes, cp, cp_fej, N, P, cam1);
+  g_cam1_q = g_cam1_p = g_cam1_intr = nullptr;
+  g_cam_of_meas = nullptr;
   if (rc) return rc;
   auto &state = hs.state;
   const size_t id0 = (mode == 0) ? 9000 : 5000;
-  auto fv = make_features(hs, F, M, uv, clone_idx, n_meas, p_FinG, id0);
+  auto fv = make_features(hs, F, M, uv, clone_idx, n_meas, p_FinG, id0, cam1 ? cam_of : nullptr);
   auto all = fv;
   std::map<size_t, size_t> feat2plane;
   for (int f = 0; f < F; ++f)

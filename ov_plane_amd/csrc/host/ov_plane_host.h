@@ -65,6 +65,11 @@ struct StateOptions {
   // are triangulated over every camera (ovp_triangulate_general) and linearised, projected and gated on the device
   // (ovp_msckf_general_features) instead of as dense blocks built on the host (ovp_msckf_dense_blocks).  Not in the reference.
   bool gpu_general_features = false;
+  // UpdaterSLAM: landmarks and candidates with another camera's observations take the general SLAM entries instead of the host
+  // forms - update() ovp_slam_update_general instead of update_dense, delayed_init() ovp_slam_delayed_init_general instead of the
+  // per-candidate loop, and their triangulation ovp_triangulate_general (every view with its own camera's extrinsics) instead of
+  // ovp_triangulate.  OVP_E_CAPACITY of an entry falls back to the host form.  Not in the reference.
+  bool gpu_general_slam = false;
 };
 
 // update/UpdaterOptions.h:37-53
@@ -246,6 +251,13 @@ public:
   // pose tables of the clone window + camera calibration -> device (ovp_state_upload); clone_slot: timestamp -> clone slot
   static void upload_state_tables(std::shared_ptr<State> state, std::map<double, int> &clone_slot,
                                   std::vector<std::shared_ptr<ov_type::PoseJPL>> &clones);
+  // every camera's calibration -> device (ovp_cameras_upload), for the general entries
+  static void upload_camera_tables(std::shared_ptr<State> state);
+  // which path the last update() / delayed_init() took (tests; not in the reference): ROUTE_DEVICE_GENERAL / ROUTE_DEVICE_MONO = the
+  // general / mono device entry took every landmark or candidate, ROUTE_DENSE_HOST = update_dense, ROUTE_HOST_LOOP = some or all
+  // candidates went through delayed_init_host_loop
+  enum Route { ROUTE_NONE = 0, ROUTE_DEVICE_GENERAL = 1, ROUTE_DEVICE_MONO = 2, ROUTE_DENSE_HOST = 3, ROUTE_HOST_LOOP = 4 };
+  static int last_route() { return _last_route; }
 
 protected:
   // update/UpdaterSLAM.cpp:708-850: new anchor-frame value of the landmark and covariance propagation with the
@@ -258,6 +270,7 @@ protected:
   UpdaterOptions _options_slam, _options_aruco;
   ov_core::FeatureInitializerOptions _featinit;  // ext FeatureInitializer options (the reference keeps an initializer_feat)
   static bool _force_dense;
+  static int _last_route;
   friend struct UpdaterSLAMTestAccess;
 };
 

@@ -497,6 +497,22 @@ void UpdaterSLAM::upload_state_tables(std::shared_ptr<State> state, std::map<dou
   gpu_check2(ovp_state_upload(state->_gpu, &st), "ovp_state_upload");  // (the tables are staged inside the call)
 }
 
+// Every camera's calibration -> device (ovp_cameras_upload): the tables of the general entries
+void UpdaterSLAM::upload_camera_tables(std::shared_ptr<State> state) {
+  std::vector<ovp_camera_tables> cams(state->_options.num_cameras);
+  for (int k = 0; k < state->_options.num_cameras; ++k) {
+    auto calib = state->_calib_IMUtoCAM.at(k);
+    auto intr = state->_cam_intrinsics.at(k);
+    memcpy(cams[k].calib_q, calib->quat(), 4 * sizeof(double));
+    memcpy(cams[k].calib_p, calib->pos(), 3 * sizeof(double));
+    cams[k].calib_id = calib->id();
+    memcpy(cams[k].intrinsics, intr->value().data(), 8 * sizeof(double));
+    cams[k].intr_id = intr->id();
+    cams[k].fisheye = (state->_cam_fisheye.count(k) && state->_cam_fisheye.at(k)) ? 1 : 0;
+  }
+  gpu_check2(ovp_cameras_upload(state->_gpu, (int)cams.size(), cams.data()), "ovp_cameras_upload");
+}
+
 // ---- update/UpdaterSLAM.cpp ----------------------------------------------------------------------
 UpdaterSLAM::UpdaterSLAM(UpdaterOptions &options_slam, UpdaterOptions &options_aruco, ov_core::FeatureInitializerOptions &fio)
     : _options_slam(options_slam), _options_aruco(options_aruco), _featinit(fio) {
@@ -561,12 +577,16 @@ void UpdaterSLAM::update(std::shared_ptr<State> state, std::vector<std::shared_p
     M = std::max(M, (int)f->timestamps.size());
     other_camera = other_camera || !f->only_camera0();
   }
-  // a track longer than one wavefront's rows, or measurements of a camera other than camera 0 (the device batch carries one
-  // calibration block per row): the dense form has neither limit
-  if (M > OVP_MAX_MEAS || other_camera || _force_dense) {
+  // a track longer than one wavefront's rows, or measurements of a camera other than camera 0 (the mono entry carries one
+  // calibration block per row): the dense form has neither limit.  StateOptions::gpu_general_slam: other cameras' measurements
+  // take the general entry (every camera's tables, ovp_slam_update_general) in ONE call with the rest of the batch
+  const bool general = other_camera && state->_options.gpu_general_slam && M <= OVP_MAX_MEAS && !_force_dense;
+  if (!general && (M > OVP_MAX_MEAS || other_camera || _force_dense)) {
+    _last_route = ROUTE_DENSE_HOST;
     update_dense(state, feature_vec, feat2plane);
     return;
   }
+  std::vector<int> camv(general ? (size_t)L * M : 0, 0);  // camera of every measurement (general entry)
   std::vector<float> uv((size_t)L * M * 2, 0.f);
   std::vector<int> cidx((size_t)L * M, -1), nm(L), lmid(L), psid(L, -1), pre_rows(L, 0), pre_cols(L, 0), pre_ids;
   std::vector<double> pv((size_t)L * 3, 0.0), pf((size_t)L * 3, 0.0), cpv((size_t)L * 3, 0.0), cpf((size_t)L * 3, 0.0), pre_H;
@@ -582,6 +602,7 @@ void UpdaterSLAM::update(std::shared_ptr<State> state, std::vector<std::shared_p
       cidx[(size_t)l * M + k] = clone_slot.at(ft.timestamps[k]);
       uv[((size_t)l * M + k) * 2] = ft.uvs[2 * k];
       uv[((size_t)l * M + k) * 2 + 1] = ft.uvs[2 * k + 1];
+      if (general) camv[(size_t)l * M + k] = ft.cam_of(k);
     }
     // :465-475
     if (state->_options.use_plane_constraint && state->_options.use_plane_constraint_slamu && feat2plane.find(ft.featid) != feat2plane.end() &&
@@ -612,6 +633,7 @@ void UpdaterSLAM::update(std::shared_ptr<State> state, std::vector<std::shared_p
     feat.featid = ft.featid;
     feat.uvs = ft.uvs;
     feat.timestamps = ft.timestamps;
+    if (general) feat.cam_ids = ft.cam_ids;
     const bool single = landmark->_feat_representation == LR::ANCHORED_INVERSE_DEPTH_SINGLE;
     feat.feat_representation = single ? LR::ANCHORED_MSCKF_INVERSE_DEPTH : landmark->_feat_representation;  // :478-481
     if (LR::is_relative_representation(feat.feat_representation)) {
@@ -685,16 +707,24 @@ void UpdaterSLAM::update(std::shared_ptr<State> state, std::vector<std::shared_p
   std::vector<double> dx(n, 0.0);
   std::vector<uint8_t> status(L, 0);
   ovp_update_info info;
-  const int rc = ovp_slam_update(state->_gpu, &uo, &sb, dx.data(), status.data(), nullptr, &info);
+  int rc;
+  if (general) {
+    upload_camera_tables(state);
+    rc = ovp_slam_update_general(state->_gpu, &uo, &sb, camv.data(), dx.data(), status.data(), nullptr, &info);
+  } else {
+    rc = ovp_slam_update(state->_gpu, &uo, &sb, dx.data(), status.data(), nullptr, &info);
+  }
   if (rc == OVP_E_NEGDIAG) {
     fprintf(stderr, "StateHelper::EKFUpdate() - negative covariance diagonal\n");
     std::exit(EXIT_FAILURE);
   }
   if (rc == OVP_E_CAPACITY) {  // the gate kernel's LDS bound: nothing was touched, the dense form takes the batch
+    _last_route = ROUTE_DENSE_HOST;
     update_dense(state, feature_vec, feat2plane);
     return;
   }
-  gpu_check2(rc, "ovp_slam_update");
+  gpu_check2(rc, general ? "ovp_slam_update_general" : "ovp_slam_update");
+  _last_route = general ? ROUTE_DEVICE_GENERAL : ROUTE_DEVICE_MONO;
   // :547-624 side effects of the gate, in the order of the vector
   size_t l = 0;
   auto it2 = feature_vec.begin();
@@ -717,6 +747,7 @@ void UpdaterSLAM::update(std::shared_ptr<State> state, std::vector<std::shared_p
 }
 
 bool UpdaterSLAM::_force_dense = false;
+int UpdaterSLAM::_last_route = UpdaterSLAM::ROUTE_NONE;
 
 namespace {
 // one landmark's linearised measurement: [H_x | H_landmark] over `order` (the landmark last), residual
@@ -919,6 +950,37 @@ void UpdaterSLAM::triangulate_on_device(std::shared_ptr<State> state, const ov_c
   to.max_cond_number = fio.max_cond_number;
   std::vector<uint8_t> okv(F, 0);
   gpu_check2(ovp_triangulate(state->_gpu, &to, uvn.data(), pf.data(), okv.data()), "ovp_triangulate");
+  // StateOptions::gpu_general_slam: a feature with another camera's views is triangulated over every view, each with its own
+  // camera's extrinsics (ovp_triangulate_general); the mono kernel would take camera 0's for all of them
+  std::vector<int> gidx;
+  if (state->_options.gpu_general_slam)
+    for (int i = 0; i < F; ++i)
+      if (!feature_vec[i]->only_camera0() && feature_vec[i]->uvs_norm.size() == feature_vec[i]->uvs.size() && nm[i] <= OVP_GEN_MAX_MEAS)
+        gidx.push_back(i);
+  if (!gidx.empty()) {
+    upload_camera_tables(state);
+    const int G = (int)gidx.size();
+    std::vector<int> gci((size_t)G * M, 0), gcam((size_t)G * M, 0), gnm(G);
+    std::vector<float> guvn((size_t)G * M * 2, 0.f);
+    for (int g = 0; g < G; ++g) {
+      const ov_core::Feature &ft = *feature_vec[gidx[g]];
+      gnm[g] = nm[gidx[g]];
+      for (int k = 0; k < gnm[g]; ++k) {
+        gci[(size_t)g * M + k] = cidx[(size_t)gidx[g] * M + k];
+        gcam[(size_t)g * M + k] = ft.cam_of(k);
+        guvn[((size_t)g * M + k) * 2] = ft.uvs_norm[2 * k];
+        guvn[((size_t)g * M + k) * 2 + 1] = ft.uvs_norm[2 * k + 1];
+      }
+    }
+    ovp_general_batch gb{G, M, guvn.data(), gci.data(), gcam.data(), gnm.data(), nullptr};
+    std::vector<double> gpf((size_t)G * 3, 0.0);
+    std::vector<uint8_t> gok(G, 0);
+    gpu_check2(ovp_triangulate_general(state->_gpu, &to, &gb, guvn.data(), gpf.data(), gok.data()), "ovp_triangulate_general");
+    for (int g = 0; g < G; ++g) {
+      okv[gidx[g]] = gok[g];
+      memcpy(&pf[3 * gidx[g]], &gpf[3 * g], 3 * sizeof(double));
+    }
+  }
   size_t f = 0;
   auto it1 = feature_vec.begin();
   while (it1 != feature_vec.end()) {
@@ -957,6 +1019,7 @@ static bool fused_initialize_on() {  // OVP_HOST_INIT_SPLIT=1: the three separat
 
 void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::shared_ptr<ov_core::Feature>> &feature_vec,
                                const std::map<size_t, size_t> &feat2plane) {
+  _last_route = ROUTE_NONE;
   if (feature_vec.empty()) return;
   // :80-118 clean, need >= 2 measurements
   auto it0 = feature_vec.begin();
@@ -1019,9 +1082,11 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
       M = std::max(M, (int)feature_vec[run_begin + l]->timestamps.size());
       other_camera = other_camera || !feature_vec[run_begin + l]->only_camera0();
     }
-    if (M > OVP_MAX_MEAS || other_camera) return (size_t)-1;  // (the per-candidate host loop has neither limit)
+    // (the per-candidate host loop has neither limit; StateOptions::gpu_general_slam: other cameras take the general entry)
+    const bool general = other_camera && state->_options.gpu_general_slam;
+    if (M > OVP_MAX_MEAS || (other_camera && !general)) return (size_t)-1;
     std::vector<float> uv((size_t)L * M * 2, 0.f);
-    std::vector<int> cidx((size_t)L * M, -1), nm(L);
+    std::vector<int> cidx((size_t)L * M, -1), nm(L), camv(general ? (size_t)L * M : 0, 0);
     std::vector<double> pf((size_t)L * 3);
     for (int l = 0; l < L; ++l) {
       ov_core::Feature &ft = *feature_vec[run_begin + l];
@@ -1030,6 +1095,7 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
         cidx[(size_t)l * M + k] = clone_slot.at(ft.timestamps[k]);
         uv[((size_t)l * M + k) * 2] = ft.uvs[2 * k];
         uv[((size_t)l * M + k) * 2 + 1] = ft.uvs[2 * k + 1];
+        if (general) camv[(size_t)l * M + k] = ft.cam_of(k);
       }
       memcpy(&pf[3 * l], ft.p_FinG, 3 * sizeof(double));
     }
@@ -1047,13 +1113,21 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
     std::vector<int> nid(L, -1);
     std::vector<double> dl((size_t)3 * L, 0.0), dxs((size_t)L * stride, 0.0);
     const double t_c = now_s();
-    const int rc = ovp_slam_delayed_init(state->_gpu, &uo, &fb, okv.data(), nullptr, nid.data(), dl.data(), dxs.data(), stride);
+    int rc;
+    if (general) {
+      upload_camera_tables(state);
+      ovp_general_batch gb{L, M, uv.data(), cidx.data(), camv.data(), nm.data(), pf.data()};
+      rc = ovp_slam_delayed_init_general(state->_gpu, &uo, &gb, okv.data(), nullptr, nid.data(), dl.data(), dxs.data(), stride);
+    } else {
+      rc = ovp_slam_delayed_init(state->_gpu, &uo, &fb, okv.data(), nullptr, nid.data(), dl.data(), dxs.data(), stride);
+    }
     if (rc == OVP_E_CAPACITY) return (size_t)-1;  // nothing was touched: the caller takes these candidates one by one
     if (rc == OVP_E_NEGDIAG) {
       fprintf(stderr, "StateHelper::EKFUpdate() - negative covariance diagonal\n");
       std::exit(EXIT_FAILURE);
     }
-    gpu_check2(rc, "ovp_slam_delayed_init");
+    gpu_check2(rc, general ? "ovp_slam_delayed_init_general" : "ovp_slam_delayed_init");
+    _last_route = (general || _last_route == ROUTE_DEVICE_GENERAL) ? ROUTE_DEVICE_GENERAL : ROUTE_DEVICE_MONO;
     g_diprof.t_init += now_s() - t_c;
     g_diprof.cands += L;
     size_t pos = run_begin;
@@ -1106,10 +1180,12 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
     std::vector<std::shared_ptr<ov_core::Feature>> rest(feature_vec.begin() + (long)i, feature_vec.end());
     std::vector<std::shared_ptr<ov_core::Feature>> head(feature_vec.begin(), feature_vec.begin() + (long)i);
     delayed_init_host_loop(state, rest, feat2plane);
+    _last_route = ROUTE_HOST_LOOP;
     feature_vec = head;
     feature_vec.insert(feature_vec.end(), rest.begin(), rest.end());
     return;
   }
+  _last_route = ROUTE_HOST_LOOP;
   delayed_init_host_loop(state, feature_vec, feat2plane);
 }
 

@@ -26,9 +26,24 @@ struct DinitParams {
   double* res;            // this candidate's result block: res[4 + n_max .. +3) = H_L^-1 res_init
 };
 
+// the general instance (ovp_slam_delayed_init_general): candidates with observations of any camera, at most OVP_MAX_MEAS_DEV of them
+struct DinitGenParams {
+  DinitParams dp;         // dp.idv unused; dp.cal = camera 0's table of ovp_state_upload (committed as well)
+  double* cam_cal;        // [OVP_GEN_MAX_CAMS][20] tables of ovp_cameras_upload: the rows read them, every commit updates them
+  int n_cams;
+  int cam_fisheye[OVP_GEN_MAX_CAMS], cam_calib_id[OVP_GEN_MAX_CAMS], cam_intr_id[OVP_GEN_MAX_CAMS];
+  const int* cam_idx;     // [n_feats][max_meas] camera of every observation
+  int cols;               // columns of the candidate's H_x
+  int ocol[OVP_MAX_MEAS_DEV];         // local column of observation a's clone block (a clone seen by two cameras has one block)
+  int ccol[OVP_GEN_MAX_CAMS];         // local column of camera c's first estimated calibration column (-1 = not a camera of it)
+  int idg[6 * OVP_MAX_MEAS_DEV + 14 * OVP_GEN_MAX_CAMS];  // the state columns of the list, by value
+};
+
 }  // namespace ovp
 
 extern "C" {
 size_t ovp_dinit_rows_lds(int m_obs, int ncal);
 hipError_t ovp_launch_dinit_rows(const ovp::DinitParams* dp, size_t lds, hipStream_t stream);
+size_t ovp_dinit_gen_rows_lds(int m_obs, int cols);
+hipError_t ovp_launch_dinit_rows_gen(const ovp::DinitGenParams* gp, size_t lds, hipStream_t stream);
 }

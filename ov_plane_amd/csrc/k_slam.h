@@ -35,9 +35,21 @@ struct SlamParams {
   unsigned char* status;     // [L] 0 = rejected, 1 = accepted, 2 = accepted without its plane (fallback)
 };
 
+// the general instance (ovp_slam_update_general): observation a of landmark l was taken by camera cam_idx[l * max_meas + a], whose
+// tables are cam_cal + 20 * cam (layout of FeatParams::cal) and whose calibration columns start at cam_calib_id / cam_intr_id
+struct SlamGenParams {
+  SlamParams sp;
+  const int* cam_idx;         // [L][max_meas]
+  const int* cam_mask;        // [L] bit c = camera c observes the landmark (its calibration columns are part of the block)
+  const double* cam_cal;      // [OVP_GEN_MAX_CAMS][20]
+  int cam_fisheye[OVP_GEN_MAX_CAMS];
+  int cam_calib_id[OVP_GEN_MAX_CAMS], cam_intr_id[OVP_GEN_MAX_CAMS];
+};
+
 }  // namespace ovp
 
 extern "C" {
 size_t ovp_slam_gate_lds(int rows_max, int cols_max, int with_h);
 hipError_t ovp_launch_slam_gate(const ovp::SlamParams* sp, int n_landmarks, size_t lds, hipStream_t stream);
+hipError_t ovp_launch_slam_gate_gen(const ovp::SlamGenParams* gp, int n_landmarks, size_t lds, hipStream_t stream);
 }

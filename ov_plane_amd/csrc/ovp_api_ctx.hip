@@ -744,6 +744,9 @@ extern "C" long ovp_debug_read(ovp_ctx* c, const char* name, void* host, long ma
   else if (!strcmp(name, "plres")) { src = c->pl_res; bytes = (size_t)4 * c->pl_cap * sizeof(double); if (!src) return OVP_E_STATE; }
   else if (!strcmp(name, "An")) { src = c->pl_An; bytes = nn; if (!src) return OVP_E_STATE; }
   else if (!strcmp(name, "bn")) { src = c->pl_bn; bytes = (size_t)c->n_max * sizeof(double); if (!src) return OVP_E_STATE; }
+  // camera tables on the device: camera 0's of ovp_state_upload / every camera's of ovp_cameras_upload ([k][20], layout of `cal`)
+  else if (!strcmp(name, "cal")) { src = c->cal; bytes = 20 * sizeof(double); if (!src) return OVP_E_STATE; }
+  else if (!strcmp(name, "gen_cal")) { src = c->gen_cal; bytes = (size_t)20 * c->gen_ncams * sizeof(double); if (!src) return OVP_E_STATE; }
   else if (!strcmp(name, "chi2")) {
     hipStreamSynchronize(c->stream);
     bytes = (size_t)c->n_feats * sizeof(double);

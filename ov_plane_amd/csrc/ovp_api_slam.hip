@@ -71,12 +71,15 @@ extern "C" int ovp_triangulate(ovp_ctx* c, const ovp_triang_opts* o, const float
 // ---- UpdaterSLAM::update on the device (update/UpdaterSLAM.cpp:424-673; csrc/k_slam.hip) ------------------------------------
 // Rows and gate of every landmark in ONE launch against the resident covariance (no download of P, no host gate), the accepted rows
 // stacked on the device, StateHelper::EKFUpdate on that stack (S-form up to 80 rows, information form above), one synchronisation.
-extern "C" int ovp_slam_update(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam_batch* b, double* dx_host, uint8_t* status_host,
-                               double* chi2_host, ovp_update_info* info) {
+// cam_idx == nullptr: ovp_slam_update (camera 0's tables of ovp_state_upload); otherwise ovp_slam_update_general: observation a of
+// landmark l by camera cam_idx[l * max_meas + a], every camera's tables (camera 0 included) from ovp_cameras_upload.
+static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam_batch* b, const int* cam_idx, double* dx_host,
+                            uint8_t* status_host, double* chi2_host, ovp_update_info* info) {
   drop_kept_factor(c);  // (writes the covariance: a kept factor no longer belongs to it)
   if (!c || !o || !b || b->n_landmarks < 0) return OVP_E_ARG;
   if (!c->have_state || !c->have_cov) return OVP_E_STATE;
   const int L = b->n_landmarks, n = c->n, M = b->max_meas;
+  const bool gen = cam_idx != nullptr;
   if (info) memset(info, 0, sizeof(*info));
   if (dx_host) memset(dx_host, 0, sizeof(double) * n);
   if (L == 0) return 0;
@@ -84,12 +87,20 @@ extern "C" int ovp_slam_update(ovp_ctx* c, const ovp_update_opts* o, const ovp_s
   const bool any_pre = b->pre_rows != nullptr;
   if (any_pre && (!b->pre_cols || !b->pre_H || !b->pre_ids)) return OVP_E_ARG;
   const unsigned calmask = (o->do_calib_camera_pose ? 0x3Fu : 0u) | (o->do_calib_camera_intrinsics ? (0xFFu << 6) : 0u);
+  const int ncal = __builtin_popcount(calmask);
   int calcol[14];
   for (int k = 0; k < 14; ++k) {
     calcol[k] = (k < 6) ? c->calib_id + k : c->intr_id + (k - 6);
     if (!((calmask >> k) & 1)) calcol[k] = 0;
-    else if (calcol[k] < 0 || calcol[k] >= n) return OVP_E_ARG;
+    else if (!gen && (calcol[k] < 0 || calcol[k] >= n)) return OVP_E_ARG;
   }
+  // general: state column of calibration column k of camera cam
+  auto gcal = [&](int cam, int k) { return k < 6 ? c->gen_calib_id[cam] + k : c->gen_intr_id[cam] + (k - 6); };
+  if (gen)
+    for (int cam = 0; cam < c->gen_ncams; ++cam)
+      for (int k = 0; k < 14; ++k)
+        if (((calmask >> k) & 1) && (gcal(cam, k) < 0 || gcal(cam, k) >= n)) return OVP_E_ARG;
+  std::vector<int> cam_mask(gen ? L : 0, 0);
   const int C = (int)c->h_clone_id.size();
   // ---- host: the call's column list (first-seen order, as Hx_order_big of :634-646), row offsets, kernel geometry
   std::vector<int> gpos(n, -1), gids, row0(L), pre_off(L, 0), pre_ids_off(L, 0);
@@ -125,16 +136,33 @@ extern "C" int ovp_slam_update(ovp_ctx* c, const ovp_update_opts* o, const ovp_s
       const bool plane = b->plane_state_id && b->plane_state_id[l] >= 0;
       if (plane && (!b->cp || !b->cp_fej || b->plane_state_id[l] + 3 > n)) return OVP_E_ARG;
       if (b->landmark_id[l] < 0 || b->landmark_id[l] + 3 > n) return OVP_E_ARG;
+      int camm = 1;  // cameras of the landmark (mono: camera 0)
+      if (gen) {
+        camm = 0;
+        for (int a = 0; a < m; ++a) {
+          const int cam = cam_idx[(size_t)l * M + a];
+          if (cam < 0 || cam >= c->gen_ncams) return OVP_E_ARG;
+          camm |= 1 << cam;
+        }
+        cam_mask[l] = camm;
+      }
       rows = plane ? 3 * m : 2 * m;
-      cols = 6 * m + __builtin_popcount(calmask) + 3 + (plane ? 3 : 0);
+      cols = 6 * m + ncal * __builtin_popcount(camm) + 3 + (plane ? 3 : 0);
       for (int a = 0; a < m; ++a) {
         const int ci = b->clone_idx[(size_t)l * M + a];
         if (ci < 0 || ci >= C) return OVP_E_ARG;
         for (int k = 0; k < 6; ++k) touch(c->h_clone_id[ci] + k);
       }
       if (m > 0) {
-        for (int k = 0; k < 14; ++k)
-          if ((calmask >> k) & 1) touch(calcol[k]);
+        if (gen) {
+          for (int cam = 0; cam < OVP_MAX_CAMERAS; ++cam)
+            if ((camm >> cam) & 1)
+              for (int k = 0; k < 14; ++k)
+                if ((calmask >> k) & 1) touch(gcal(cam, k));
+        } else {
+          for (int k = 0; k < 14; ++k)
+            if ((calmask >> k) & 1) touch(calcol[k]);
+        }
         for (int k = 0; k < 3; ++k) touch(b->landmark_id[l] + k);
         if (plane)
           for (int k = 0; k < 3; ++k) touch(b->plane_state_id[l] + k);
@@ -168,6 +196,7 @@ extern "C" int ovp_slam_update(ovp_ctx* c, const ovp_update_opts* o, const ovp_s
                o_ps = take(sizeof(int) * L), o_r0 = take(sizeof(int) * L), o_gp = take(sizeof(int) * n),
                o_gi = take(sizeof(int) * gcols), o_pr = take(sizeof(int) * L), o_pc = take(sizeof(int) * L),
                o_po = take(sizeof(int) * L), o_pio = take(sizeof(int) * L), o_pid = take(sizeof(int) * (preI + 1));
+  const size_t o_cam = take(gen ? sizeof(int) * (size_t)L * M : 0), o_cm = take(gen ? sizeof(int) * L : 0);  // (general only)
   const size_t stage_bytes = off;
   const size_t res_doubles = 4 + (size_t)c->n_max + 8;
   const size_t lres_bytes = al(sizeof(double) * L) + al((size_t)L);
@@ -181,6 +210,11 @@ extern "C" int ovp_slam_update(ovp_ctx* c, const ovp_update_opts* o, const ovp_s
     memcpy(h + o_pf, b->p_FinG_fej, sizeof(double) * 3 * L);
     memcpy(h + o_uv, b->uv, sizeof(float) * 2 * (size_t)L * M);
     memcpy(h + o_ci, b->clone_idx, sizeof(int) * (size_t)L * M);
+  }
+  if (gen) {
+    for (int l = 0; l < L; ++l)  // (landmarks with a host-built block or without observations: no cameras read)
+      for (int a = 0; a < M; ++a) ((int*)(h + o_cam))[(size_t)l * M + a] = cam_mask[l] && a < b->n_meas[l] ? cam_idx[(size_t)l * M + a] : 0;
+    memcpy(h + o_cm, cam_mask.data(), sizeof(int) * L);
   }
   if (b->cp) memcpy(h + o_cp, b->cp, sizeof(double) * 3 * L);
   if (b->cp_fej) memcpy(h + o_cpf, b->cp_fej, sizeof(double) * 3 * L);
@@ -292,7 +326,22 @@ extern "C" int ovp_slam_update(ovp_ctx* c, const ovp_update_opts* o, const ovp_s
     sp.chi2 = (double*)c->slam_res;
     sp.status = (unsigned char*)c->slam_res + al(sizeof(double) * L);
   }
-  HIPCHK(ovp_launch_slam_gate(&sp, L, ovp_slam_gate_lds(rows_max, cols_max, h_in_lds), s));
+  if (gen) {
+    ovp::SlamGenParams gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.sp = sp;
+    gp.cam_idx = (const int*)(d + o_cam);
+    gp.cam_mask = (const int*)(d + o_cm);
+    gp.cam_cal = c->gen_cal;
+    for (int k = 0; k < OVP_MAX_CAMERAS; ++k) {
+      gp.cam_fisheye[k] = c->gen_fisheye[k];
+      gp.cam_calib_id[k] = c->gen_calib_id[k];
+      gp.cam_intr_id[k] = c->gen_intr_id[k];
+    }
+    HIPCHK(ovp_launch_slam_gate_gen(&gp, L, ovp_slam_gate_lds(rows_max, cols_max, h_in_lds), s));
+  } else {
+    HIPCHK(ovp_launch_slam_gate(&sp, L, ovp_slam_gate_lds(rows_max, cols_max, h_in_lds), s));
+  }
   const int* dgid = (const int*)(d + o_gi);
   char* hres = (char*)c->pl_hres;
   double* hres_d = (double*)hres;
@@ -368,15 +417,32 @@ extern "C" int ovp_slam_update(ovp_ctx* c, const ovp_update_opts* o, const ovp_s
   return 0;
 }
 
+extern "C" int ovp_slam_update(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam_batch* b, double* dx_host, uint8_t* status_host,
+                               double* chi2_host, ovp_update_info* info) {
+  return slam_update_impl(c, o, b, nullptr, dx_host, status_host, chi2_host, info);
+}
+
+extern "C" int ovp_slam_update_general(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam_batch* b, const int* cam_idx,
+                                       double* dx_host, uint8_t* status_host, double* chi2_host, ovp_update_info* info) {
+  if (!c || !o || !b || !cam_idx || c->gen_ncams < 1) return OVP_E_ARG;  // (every camera from the tables of ovp_cameras_upload)
+  return slam_update_impl(c, o, b, cam_idx, dx_host, status_host, chi2_host, info);
+}
+
 // ---- UpdaterSLAM::delayed_init, candidate loop on the device (update/UpdaterSLAM.cpp:204-364; csrc/k_dinit.hip) -----------------
-extern "C" int ovp_slam_delayed_init(ovp_ctx* c, const ovp_update_opts* o, const ovp_feature_batch* b, uint8_t* ok_host,
-                                     double* chi2_host, int* new_id, double* delta_init, double* dx_host, int dx_stride) {
+// The candidate arrays come from an ovp_feature_batch (cam_idx == nullptr: camera 0's tables of ovp_state_upload, ovp_slam_delayed_init)
+// or from an ovp_general_batch (ovp_slam_delayed_init_general: every camera's tables from ovp_cameras_upload; a candidate's columns are
+// the clone blocks of its distinct clones in first-seen order, then the estimated calibration columns of each of its cameras in
+// camera order; every commit updates camera 0's table of ovp_state_upload AND every camera of ovp_cameras_upload).
+static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, int M, const float* b_uv, const int* b_clone_idx,
+                                  const int* cam_idx, const int* b_n_meas, const double* b_p, uint8_t* ok_host, double* chi2_host,
+                                  int* new_id, double* delta_init, double* dx_host, int dx_stride) {
   drop_kept_factor(c);  // (writes the covariance: a kept factor no longer belongs to it)
-  if (!c || !o || !b || b->n_feats < 0) return OVP_E_ARG;
+  if (!c || !o || L < 0) return OVP_E_ARG;
   if (!c->have_state || !c->have_cov) return OVP_E_STATE;
-  const int L = b->n_feats, M = b->max_meas, n0 = c->n, ld = c->ld;
+  const int n0 = c->n, ld = c->ld;
+  const bool gen = cam_idx != nullptr;
   if (L == 0) return 0;
-  if (M < 2 || M > OVP_MAX_MEAS || !b->uv || !b->clone_idx || !b->n_meas || !b->p_FinG) return OVP_E_ARG;
+  if (M < 2 || (!gen && M > OVP_MAX_MEAS) || !b_uv || !b_clone_idx || !b_n_meas || !b_p) return OVP_E_ARG;
   if (dx_host && dx_stride < n0 + 3 * L) return OVP_E_ARG;
   if (n0 + 3 * L > c->n_max) return OVP_E_CAPACITY;
   const unsigned calmask = (o->do_calib_camera_pose ? 0x3Fu : 0u) | (o->do_calib_camera_intrinsics ? (0xFFu << 6) : 0u);
@@ -387,19 +453,61 @@ extern "C" int ovp_slam_delayed_init(ovp_ctx* c, const ovp_update_opts* o, const
     if (!((calmask >> k) & 1)) calcol[k] = 0;
     else if (calcol[k] < 0 || calcol[k] >= n0) return OVP_E_ARG;
   }
+  auto gcal = [&](int cam, int k) { return k < 6 ? c->gen_calib_id[cam] + k : c->gen_intr_id[cam] + (k - 6); };
+  if (gen)
+    for (int cam = 0; cam < c->gen_ncams; ++cam)
+      for (int k = 0; k < 14; ++k)
+        if (((calmask >> k) & 1) && (gcal(cam, k) < 0 || gcal(cam, k) >= n0)) return OVP_E_ARG;
   const int C = (int)c->h_clone_id.size();
+  // every candidate's column list (general: distinct clones, cameras) - ocol / ccol: local column of observation a's clone block /
+  // of camera k's calibration block
+  std::vector<std::vector<int>> cand_ids(L), cand_ocol(gen ? L : 0), cand_ccol(gen ? L : 0);
   int cols_max = 1, rows_max = 4;
   for (int l = 0; l < L; ++l) {
-    const int m = b->n_meas[l];
+    const int m = b_n_meas[l];
     if (m < 2 || m > M) return OVP_E_ARG;  // (update/UpdaterSLAM.cpp:112-118: the caller drops shorter tracks)
     for (int a = 0; a < m; ++a) {
-      const int ci = b->clone_idx[(size_t)l * M + a];
+      const int ci = b_clone_idx[(size_t)l * M + a];
       if (ci < 0 || ci >= C) return OVP_E_ARG;
+      if (gen && (cam_idx[(size_t)l * M + a] < 0 || cam_idx[(size_t)l * M + a] >= c->gen_ncams)) return OVP_E_ARG;
     }
-    const int cols = 6 * m + ncal, rup = 2 * m - 3;
+    std::vector<int>& ids = cand_ids[l];
+    if (!gen) {
+      for (int a = 0; a < m; ++a)
+        for (int k = 0; k < 6; ++k) ids.push_back(c->h_clone_id[b_clone_idx[(size_t)l * M + a]] + k);
+      for (int k = 0; k < 14; ++k)
+        if ((calmask >> k) & 1) ids.push_back(calcol[k]);
+    } else {
+      if (m > OVP_MAX_MEAS_DEV) return OVP_E_CAPACITY;  // (the rows kernel stages at most this many observations)
+      std::vector<int>& oc = cand_ocol[l];
+      std::vector<int>& cc = cand_ccol[l];
+      oc.assign(OVP_MAX_MEAS_DEV, 0);
+      cc.assign(OVP_MAX_CAMERAS, -1);
+      int camm = 0;
+      for (int a = 0; a < m; ++a) {
+        const int ci = b_clone_idx[(size_t)l * M + a];
+        int prev = -1;
+        for (int a2 = 0; a2 < a && prev < 0; ++a2)
+          if (b_clone_idx[(size_t)l * M + a2] == ci) prev = a2;
+        if (prev >= 0) {
+          oc[a] = oc[prev];
+        } else {
+          oc[a] = (int)ids.size();
+          for (int k = 0; k < 6; ++k) ids.push_back(c->h_clone_id[ci] + k);
+        }
+        camm |= 1 << cam_idx[(size_t)l * M + a];
+      }
+      for (int cam = 0; cam < OVP_MAX_CAMERAS; ++cam)
+        if ((camm >> cam) & 1) {
+          cc[cam] = (int)ids.size();
+          for (int k = 0; k < 14; ++k)
+            if ((calmask >> k) & 1) ids.push_back(gcal(cam, k));
+        }
+    }
+    const int cols = (int)ids.size(), rup = 2 * m - 3;
     // outside the one-workgroup S-form (k_init.hip): the caller takes StateHelper::initialize candidate by candidate; nothing touched
     if (rup > ovp_init_max_rows() || ovp_init_core_lds(3, rup, cols) > ovp_init_max_lds() ||
-        ovp_dinit_rows_lds(m, ncal) > OVP_DINIT_DYN_LDS) return OVP_E_CAPACITY;
+        (gen ? ovp_dinit_gen_rows_lds(m, cols) : ovp_dinit_rows_lds(m, ncal)) > OVP_DINIT_DYN_LDS) return OVP_E_CAPACITY;
     cols_max = std::max(cols_max, cols);
     rows_max = std::max(rows_max, 2 * m);
   }
@@ -414,25 +522,19 @@ extern "C" int ovp_slam_delayed_init(ovp_ctx* c, const ovp_update_opts* o, const
   };
   const size_t o_p = take(sizeof(double) * 3 * L), o_uv = take(sizeof(float) * 2 * (size_t)L * M), o_ci = take(sizeof(int) * (size_t)L * M),
                o_nm = take(sizeof(int) * L), o_id = take(sizeof(int) * (size_t)L * cols_max);
+  const size_t o_cam = take(gen ? sizeof(int) * (size_t)L * M : 0);  // (general only)
   const size_t stage_bytes = off;
   const size_t res_doubles = 4 + (size_t)c->n_max + 8;
   int rc = plane2_buffers(c, 0, stage_bytes, sizeof(double) * res_doubles * L + 64);
   if (rc) return rc;
   char* h = (char*)c->pl_hstage;
   char* d = (char*)c->pl_dstage;
-  memcpy(h + o_p, b->p_FinG, sizeof(double) * 3 * L);
-  memcpy(h + o_uv, b->uv, sizeof(float) * 2 * (size_t)L * M);
-  memcpy(h + o_ci, b->clone_idx, sizeof(int) * (size_t)L * M);
-  memcpy(h + o_nm, b->n_meas, sizeof(int) * L);
-  for (int l = 0; l < L; ++l) {
-    int* ids = (int*)(h + o_id) + (size_t)l * cols_max;
-    const int m = b->n_meas[l];
-    for (int a = 0; a < m; ++a)
-      for (int k = 0; k < 6; ++k) ids[6 * a + k] = c->h_clone_id[b->clone_idx[(size_t)l * M + a]] + k;
-    int q = 6 * m;
-    for (int k = 0; k < 14; ++k)
-      if ((calmask >> k) & 1) ids[q++] = calcol[k];
-  }
+  memcpy(h + o_p, b_p, sizeof(double) * 3 * L);
+  memcpy(h + o_uv, b_uv, sizeof(float) * 2 * (size_t)L * M);
+  memcpy(h + o_ci, b_clone_idx, sizeof(int) * (size_t)L * M);
+  memcpy(h + o_nm, b_n_meas, sizeof(int) * L);
+  if (gen) memcpy(h + o_cam, cam_idx, sizeof(int) * (size_t)L * M);
+  for (int l = 0; l < L; ++l) memcpy((int*)(h + o_id) + (size_t)l * cols_max, cand_ids[l].data(), sizeof(int) * cand_ids[l].size());
   // device scratch: [result blocks L x res_doubles | Ht | Mall | Linv | y | Hinv 9 | Rk 9 | resid]
   const size_t n_end = (size_t)n0 + 3 * L;
   const size_t need = res_doubles * L + (size_t)cols_max * rows_max + n_end * rows_max + (size_t)rows_max * rows_max + rows_max + 32 +
@@ -476,16 +578,35 @@ extern "C" int ovp_slam_delayed_init(ovp_ctx* c, const ovp_update_opts* o, const
   dp.Hinv = dHinv;
   dp.Rk = dRk;
   dp.resid = dresid;
+  ovp::DinitGenParams gp;  // (general only)
+  memset(&gp, 0, sizeof(gp));
+  gp.cam_cal = c->gen_cal;
+  gp.n_cams = c->gen_ncams;
+  for (int k = 0; k < OVP_MAX_CAMERAS; ++k) {
+    gp.cam_fisheye[k] = c->gen_fisheye[k];
+    gp.cam_calib_id[k] = c->gen_calib_id[k];
+    gp.cam_intr_id[k] = c->gen_intr_id[k];
+  }
+  gp.cam_idx = (const int*)(d + o_cam);
   for (int l = 0; l < L; ++l) {
-    const int m = b->n_meas[l], cols = 6 * m + ncal, rows = 2 * m, rup = rows - 3, n = n0 + 3 * l;
+    const int m = b_n_meas[l], cols = (int)cand_ids[l].size(), rows = 2 * m, rup = rows - 3, n = n0 + 3 * l;
     dp.cand = l;
     dp.m_obs = m;
     dp.n = n;
     dp.prev_res = l ? dres0 + res_doubles * (l - 1) : nullptr;
     dp.ids = (const int*)(d + o_id) + (size_t)l * cols_max;
-    memcpy(dp.idv, (const int*)(h + o_id) + (size_t)l * cols_max, sizeof(int) * cols);
     dp.res = dres0 + res_doubles * l;
-    HIPCHK(ovp_launch_dinit_rows(&dp, ovp_dinit_rows_lds(m, ncal), s));
+    if (gen) {
+      gp.dp = dp;
+      gp.cols = cols;
+      memcpy(gp.idg, cand_ids[l].data(), sizeof(int) * cols);
+      memcpy(gp.ocol, cand_ocol[l].data(), sizeof(gp.ocol));
+      memcpy(gp.ccol, cand_ccol[l].data(), sizeof(gp.ccol));
+      HIPCHK(ovp_launch_dinit_rows_gen(&gp, ovp_dinit_gen_rows_lds(m, cols), s));
+    } else {
+      memcpy(dp.idv, cand_ids[l].data(), sizeof(int) * cols);
+      HIPCHK(ovp_launch_dinit_rows(&dp, ovp_dinit_rows_lds(m, ncal), s));
+    }
     HIPCHK(ovp_launch_init_m(c->P, ld, n, dp.ids, cols, dHt, rows, dM, s));  // M = P[:, ids] H_all^T on many workgroups
     // chi2 of the update rows with dof = all rows (StateHelper.cpp:471), initialize_invertible, update in place
     const double thr = o->chi2_multiplier * ovp_chi2_quantile_095(rows);
@@ -495,7 +616,12 @@ extern "C" int ovp_slam_delayed_init(ovp_ctx* c, const ovp_update_opts* o, const
   dp.cand = -1;
   dp.n = (int)n_end;
   dp.prev_res = dres0 + res_doubles * (L - 1);
-  HIPCHK(ovp_launch_dinit_rows(&dp, 64, s));
+  if (gen) {
+    gp.dp = dp;
+    HIPCHK(ovp_launch_dinit_rows_gen(&gp, 64, s));
+  } else {
+    HIPCHK(ovp_launch_dinit_rows(&dp, 64, s));
+  }
   double* hres = (double*)c->pl_hres;
   {
     const int rf = ovp_fetch_to_hres(c, dres0, sizeof(double) * res_doubles * L, s);
@@ -535,5 +661,22 @@ extern "C" int ovp_slam_delayed_init(ovp_ctx* c, const ovp_update_opts* o, const
     }
   }
   return negdiag ? OVP_E_NEGDIAG : 0;
+}
+
+extern "C" int ovp_slam_delayed_init(ovp_ctx* c, const ovp_update_opts* o, const ovp_feature_batch* b, uint8_t* ok_host,
+                                     double* chi2_host, int* new_id, double* delta_init, double* dx_host, int dx_stride) {
+  if (!b) {
+    drop_kept_factor(c);
+    return OVP_E_ARG;
+  }
+  return slam_delayed_init_impl(c, o, b->n_feats, b->max_meas, b->uv, b->clone_idx, nullptr, b->n_meas, b->p_FinG, ok_host, chi2_host,
+                                new_id, delta_init, dx_host, dx_stride);
+}
+
+extern "C" int ovp_slam_delayed_init_general(ovp_ctx* c, const ovp_update_opts* o, const ovp_general_batch* b, uint8_t* ok_host,
+                                             double* chi2_host, int* new_id, double* delta_init, double* dx_host, int dx_stride) {
+  if (!c || !o || !b || !b->cam_idx || c->gen_ncams < 1) return OVP_E_ARG;  // (every camera from the tables of ovp_cameras_upload)
+  return slam_delayed_init_impl(c, o, b->n_feats, b->max_meas, b->uv, b->clone_idx, b->cam_idx, b->n_meas, b->p_FinG, ok_host,
+                                chi2_host, new_id, delta_init, dx_host, dx_stride);
 }
 

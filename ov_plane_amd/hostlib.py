@@ -123,7 +123,7 @@ def set_slam_force_dense(on: bool):
 
 
 def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=None, slam=None, slam_rep=None,
-                feat_rep_slam=None):
+                feat_rep_slam=None, general_slam=False, triangulate=False):
     """Drives the C++ host mirrors on a synth scene.
     fit_planes=dict(min_feat, max_cond, variant) (mode "plane_init" only): the features carry normalised measurements and
     no position, no plane estimates are handed over - init_vio_plane triangulates, fits and refines itself.
@@ -131,8 +131,21 @@ def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=
     mode "slam_update": UpdaterSLAM::update on a synth.make_slam_scene (feature f observes landmark f);
     mode "slam_delayed_init": UpdaterSLAM::delayed_init on a plain scene (every feature is a landmark candidate);
     mode "plane_init": UpdaterPlane::init_vio_plane on a scene whose planes are all out of the state.
+
+    A stereo scene (synth.make_stereo_slam_scene / make_stereo_scene: sc.cam1, sc.cam_idx) gets a two-camera state; out["cam1"] is
+    camera 1's [q | p | intrinsics] afterwards.  general_slam: StateOptions::gpu_general_slam (other cameras' landmarks and candidates
+    take ovp_slam_update_general / ovp_slam_delayed_init_general / ovp_triangulate_general); out["route"] = the path UpdaterSLAM took
+    (1 device general, 2 device mono, 3 dense host, 4 per-candidate host loop).  triangulate (mode "slam_delayed_init"): the
+    candidates carry sc.uv_norm and no position, delayed_init triangulates them.
     """
     L = lib()
+    L.ovph_set_general_slam(1 if general_slam else 0)
+    cam1 = sc.get("cam1", None)
+    cam_keep = None
+    if cam1 is not None:
+        cam_keep = [np.ascontiguousarray(cam1[k], dtype=np.float64) for k in ("calib_q", "calib_p", "intr")]
+        cam_keep.append(np.ascontiguousarray(sc.cam_idx, dtype=np.int32))
+        L.ovph_set_second_camera(*(a.ctypes.data_as(C.c_void_p) for a in cam_keep))
     L.ovph_set_fisheye(1 if sc.get("fisheye", False) else 0)
     if slam_rep is not None:  # mode "slam_update": (representation, anchor clone slot) of every landmark; out["slam_p"] are its parameters
         L.ovph_set_slam_rep(int(slam_rep[0]), int(slam_rep[1]))
@@ -142,6 +155,10 @@ def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=
     # scene must have n_slam = k landmark columns) and the scene's in-state planes; needs fit_planes
     m = {"slam_update": 0, "slam_delayed_init": 1, "plane_init": 2, "msckf_fit": 3}[mode]
     uvn_keep = None
+    if triangulate:
+        assert mode == "slam_delayed_init" and fit_planes is None
+        uvn_keep = np.ascontiguousarray(sc.uv_norm, dtype=np.float32)
+        L.ovph_set_uv_norm(uvn_keep.ctypes.data_as(C.c_void_p))
     if fit_planes is not None:
         assert m in (2, 3)
         uvn_keep = np.ascontiguousarray(sc.uv_norm, dtype=np.float32)
@@ -194,8 +211,15 @@ def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=
         p(out["clone_q"]), p(out["clone_p"]), p(out["calib_q"]), p(out["calib_p"]), p(out["intr"]), p(out["slam_p"]),
         p(out["cp"]), p(out["P"]), p(out["n"]), p(out["kept"]), p(out["deleted"]), p(out["should_marg"]),
         p(out["slam_to_plane"]), p(out["new_p"]), p(out["new_id"]))
+    if triangulate:
+        L.ovph_set_uv_norm(None)
     if rc != 0:
         raise RuntimeError("ovph_run_updater failed with %d" % rc)
+    out["route"] = int(L.ovph_last_slam_route())
+    if cam1 is not None:
+        c1 = np.zeros(15)
+        L.ovph_last_second_camera(c1.ctypes.data_as(C.c_void_p))
+        out["cam1"] = c1
     n2 = int(out["n"][0])
     out["n"] = n2
     out["P"] = np.ascontiguousarray(out["P"].reshape(-1)[: n2 * n2].reshape(n2, n2).T)

@@ -644,6 +644,91 @@ def make_slam_scene(C=11, n_slam=12, seed=0, n_planes=0, ragged=True, outliers=0
     return sc
 
 
+def make_stereo_slam_scene(C=11, n_slam=12, seed=0, n_planes=0, stereo_frac=0.5, outliers=0, wrong_plane=0, cam1_only=0, baseline=0.11,
+                           **kw):
+    """make_slam_scene with TWO cameras: the landmarks of the state are re-observed by camera 0 and, for the first
+    round(stereo_frac * n_slam) of them, by camera 1 as well (update/UpdaterHelper.cpp:335-344).  The state is make_slam_scene's with
+    camera 1's 14 calibration columns in front of the clones, as make_stereo_scene lays it out ([imu | dt | cam0 extrinsics,
+    intrinsics | cam1 extrinsics, intrinsics | clones | landmarks | planes]); the covariance is extended with correlated calibration
+    errors for them.  Camera 1 sees a stereo landmark at the newest min(m, 32 - m) of the clones camera 0 sees it at (at most 32 new
+    observations per landmark, ovp_slam_update's limit); the last `cam1_only` stereo landmarks are seen by camera 1 alone (at camera
+    0's clones).  `outliers` (the last landmarks) get gross pixel noise in every camera; planes and `wrong_plane` as make_slam_scene.
+    Extra keys: cam1 = dict(calib_q, calib_p, intr, calib_id, intr_id), cam_idx [F, M], n_stereo, ids["calib1"], ids["intr1"]."""
+    base = make_slam_scene(C=C, n_slam=n_slam, seed=seed, n_planes=n_planes, outliers=outliers, wrong_plane=wrong_plane, **kw)
+    assert base.opts["do_calib_pose"] and not base.get("fisheye", False)
+    rng = np.random.default_rng(9100 + seed)
+    N0, at = int(base.N), 30
+    N = N0 + 14
+    old_of_new = np.r_[np.arange(at), -np.ones(14, dtype=np.int64), np.arange(at, N0)]
+    L = np.linalg.cholesky(base.P)
+    scale = np.r_[np.full(3, 3.0e-3), np.full(3, 5.0e-3), np.full(4, 0.5), np.full(4, 2.0e-3)]
+    Mx = 0.3 * scale[:, None] * rng.standard_normal((14, N0)) / np.sqrt(N0)
+    B = np.zeros((N, N))
+    B[:N0, :N0] = L
+    B[N0:, :N0] = Mx
+    B[N0:, N0:] = np.diag(scale)
+    Pe = np.zeros((N, N))
+    for k in range(N):
+        bk = B[:, k]
+        nz = np.nonzero(bk)[0]
+        Pe[np.ix_(nz, nz)] += np.multiply.outer(bk[nz], bk[nz])
+    Pe = 0.5 * (Pe + Pe.T)
+    src = np.where(old_of_new >= 0, old_of_new, N0 + (np.arange(N) - at))
+    P = Pe[np.ix_(src, src)]
+    R_ItoC0 = T_IMU_CAM[:3, :3].T
+    p_IinC0 = -R_ItoC0 @ T_IMU_CAM[:3, 3]
+    R_ItoC1_true = rotz(0.01) @ roty(-0.008) @ R_ItoC0
+    p_IinC1_true = p_IinC0 - np.array([baseline, 0.0, 0.0])
+    intr1_true = INTRINSICS * np.r_[1.01, 1.01, 0.99, 1.01, 1.0, 1.0, 1.0, 1.0]
+    e1 = 0.85 * scale * rng.standard_normal(14)
+    cam1 = dict(calib_q=quat_boxplus(rot_2_quat(R_ItoC1_true), -e1[:3]), calib_p=p_IinC1_true - e1[3:6], intr=intr1_true - e1[6:],
+                calib_id=at, intr_id=at + 6)
+    F = n_slam
+    n_st = int(round(stereo_frac * F))
+    tr = base.truth
+    uv1_true, _ = project_all(tr["p_f"], tr["R"], tr["p"], R_ItoC1_true, p_IinC1_true, intr1_true, False)
+    Mm = min(2 * int(base.uv.shape[1]), 32)
+    uv = np.zeros((F, Mm, 2), dtype=np.float32)
+    clone_idx = -np.ones((F, Mm), dtype=np.int32)
+    cam_idx = np.zeros((F, Mm), dtype=np.int32)
+    n_meas = base.n_meas.copy()
+    for f in range(F):
+        m = int(base.n_meas[f])
+        ci = base.clone_idx[f, :m]
+        uv1 = (uv1_true[f, ci] + base.opts["sigma_px"] * rng.standard_normal((m, 2))).astype(np.float32)
+        if f >= F - outliers:
+            uv1 += (25.0 * rng.standard_normal((m, 2))).astype(np.float32)
+        if n_st - cam1_only <= f < n_st:  # camera 1 alone
+            uv[f, :m], clone_idx[f, :m], cam_idx[f, :m] = uv1, ci, 1
+            continue
+        uv[f, :m] = base.uv[f, :m]
+        clone_idx[f, :m] = ci
+        if f < n_st:
+            k = min(m, 32 - m)
+            uv[f, m : m + k] = uv1[m - k :]
+            clone_idx[f, m : m + k] = ci[m - k :]
+            cam_idx[f, m : m + k] = 1
+            n_meas[f] = m + k
+    ids = dict(base.ids)
+    ids["calib1"], ids["intr1"] = at, at + 6
+    for key in ("clones", "slam", "planes"):
+        ids[key] = np.asarray(base.ids[key]) + 14
+    ids["N"] = N
+    uv_norm = np.zeros((F, Mm, 2), dtype=np.float32)
+    for cam, intr_c in ((0, base.intr), (1, cam1["intr"])):
+        xn, yn = radtan_undistort(uv[..., 0].astype(np.float64), uv[..., 1].astype(np.float64), intr_c)
+        sel = cam_idx == cam
+        uv_norm[..., 0][sel] = xn[sel].astype(np.float32)
+        uv_norm[..., 1][sel] = yn[sel].astype(np.float32)
+    for f in range(F):
+        uv_norm[f, int(n_meas[f]):] = 0.0
+    pst = np.asarray(base.plane_state_id)
+    sc = Scene(base)
+    sc.update(N=N, ids=ids, P=P, uv=uv, clone_idx=clone_idx, cam_idx=cam_idx, n_meas=n_meas, cam1=cam1, n_stereo=n_st, uv_norm=uv_norm,
+              lm_id=np.asarray(base.lm_id, dtype=np.int32) + 14, plane_state_id=np.where(pst >= 0, pst + 14, -1).astype(pst.dtype))
+    return sc
+
+
 def _rotz(a):
     c, s = np.cos(a), np.sin(a)
     return np.array([[c, -s, 0], [s, c, 0], [0, 0, 1.0]])
