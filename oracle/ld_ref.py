@@ -1,0 +1,249 @@
+"""Extended-precision restatement of the update algebra: the truth the device and the double-precision oracle are measured against.
+
+Everything here computes in np.longdouble (x87 80-bit on x86-64: 64-bit mantissa, eps 1.08e-19).  Inputs may be double (the
+Jacobians of np_ref.feature_jacobian_full, a covariance, a pair read back from the device): the answer is then the exact answer for
+those inputs to ~1e-19 x the conditioning, and nothing is rounded to double before the end.  Nothing here depends on the basis a
+kernel picks for the null space of a feature (no Givens): the pair and the per-feature chi2 come from a Householder basis of the left
+null space of H_f (Hp^T Hp, Hp^T rp, |rp|^2 and chi2 do not depend on the choice).  The projector identity (feature_pair) states the
+same pair without any basis; it loses ~cond(H_f^T H_f) x eps to cancellation on short tracks (3e-15 relative on a two-observation
+feature), so it is the cross-check (tests/test_ld_ref_cpu.py), not the truth.
+
+  chol / solve_lower / solve_upper / inv_spd / solve   the dense pieces (lower Cholesky, Gaussian elimination with pivoting)
+  feature_pair                                         A_f = Hp^T Hp, b_f = Hp^T rp, |rp|^2 of one feature by the projector identity
+  nullspace_rows                                       Hp, rp in a Householder basis of the left null space of H_f
+  point_pair                                           the information pair of a set of point features, per-feature chi2 and dof
+  update_from_pair                                     P+ = (I + P A)^-1 P = (P^-1 + A)^-1, dx = P+ b (no P^-1: singular priors too)
+  update_from_pair_dropping                            the same on the pivot-dropping factor of A (the device's S-form retry)
+  ekf_update_dense                                     StateHelper::EKFUpdate (S-form, R = I) on the columns `cols`
+  err_state / rel_p / err_chi2 / err_pair              the error metrics of tests/test_precision_gpu.py
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from oracle import np_ref
+
+LD = np.longdouble
+
+
+def ld(a):
+    return np.asarray(a, dtype=LD)
+
+
+def sym(A):
+    return (A + A.T) / 2
+
+
+# ---- dense pieces ------------------------------------------------------------------------------------------------------
+def chol(A):
+    """Lower L with L L^T = A (A symmetric positive definite); raises on a non-positive pivot."""
+    A = ld(A)
+    n = A.shape[0]
+    L = np.zeros_like(A)
+    for j in range(n):
+        v = A[j:, j] - L[j:, :j] @ L[j, :j]
+        if not v[0] > 0:
+            raise np.linalg.LinAlgError("chol: pivot %d is %r" % (j, float(v[0])))
+        L[j:, j] = v / np.sqrt(v[0])
+    return L
+
+
+def solve_lower(L, B):
+    X = np.array(B, dtype=LD, copy=True)
+    for i in range(L.shape[0]):
+        X[i] = (X[i] - L[i, :i] @ X[:i]) / L[i, i]
+    return X
+
+
+def solve_upper(U, B):
+    X = np.array(B, dtype=LD, copy=True)
+    for i in range(U.shape[0] - 1, -1, -1):
+        X[i] = (X[i] - U[i, i + 1:] @ X[i + 1:]) / U[i, i]
+    return X
+
+
+def inv_spd(A):
+    Li = solve_lower(chol(A), np.eye(A.shape[0], dtype=LD))
+    return Li.T @ Li
+
+
+def solve(M, B):
+    """M^-1 B by Gaussian elimination with partial pivoting (M square, B a vector or a matrix with M.shape[0] rows)."""
+    M = np.array(M, dtype=LD, copy=True)
+    B = np.array(B, dtype=LD, copy=True)
+    vec = B.ndim == 1
+    if vec:
+        B = B[:, None]
+    n = M.shape[0]
+    for k in range(n):
+        p = k + int(np.argmax(np.abs(M[k:, k])))
+        if M[p, k] == 0:
+            raise np.linalg.LinAlgError("solve: singular at column %d" % k)
+        if p != k:
+            M[[k, p]] = M[[p, k]]
+            B[[k, p]] = B[[p, k]]
+        f = M[k + 1:, k] / M[k, k]
+        M[k + 1:, k:] -= np.outer(f, M[k, k:])
+        B[k + 1:] -= np.outer(f, B[k])
+    X = solve_upper(np.triu(M), B)
+    return X[:, 0] if vec else X
+
+
+# ---- one feature ---------------------------------------------------------------------------------------------------------
+def feature_pair(H_f, H_x, res):
+    """(A_f, b_f, rr_f) = (Hp^T Hp, Hp^T rp, |rp|^2) with [Hp | rp] the rows of [H_x | res] left after projecting out the columns of
+    H_f, by the projector identity Hp^T Hp = H_x^T H_x - (H_f^T H_x)^T (H_f^T H_f)^-1 (H_f^T H_x) (the same for b and rr)."""
+    Hf, Hx, r = ld(H_f), ld(H_x), ld(res)
+    Gi = inv_spd(Hf.T @ Hf)
+    FX, Fr = Hf.T @ Hx, Hf.T @ r
+    A = Hx.T @ Hx - FX.T @ Gi @ FX
+    b = Hx.T @ r - FX.T @ (Gi @ Fr)
+    rr = r @ r - Fr @ (Gi @ Fr)
+    return sym(A), b, rr
+
+
+def nullspace_rows(H_f, H_x, res):
+    """(Hp, rp): [H_x | res] in a Householder basis of the left null space of H_f (rows - cols(H_f) rows)."""
+    Hf, Hx, r = np.array(H_f, dtype=LD), np.array(H_x, dtype=LD), np.array(res, dtype=LD)
+    nf = Hf.shape[1]
+    for k in range(nf):
+        x = Hf[k:, k]
+        nx = np.sqrt(x @ x)
+        v = x.copy()
+        v[0] += nx if x[0] >= 0 else -nx
+        vv = v @ v
+        if vv == 0:
+            continue
+        Hf[k:] -= np.outer(v, (2 / vv) * (v @ Hf[k:]))
+        Hx[k:] -= np.outer(v, (2 / vv) * (v @ Hx[k:]))
+        r[k:] -= v * ((2 / vv) * (v @ r[k:]))
+    return Hx[nf:], r[nf:]
+
+
+def point_pair(sc, feats=None, P=None, with_chi2=True):
+    """The information pair A = sum_f Hp^T Hp, b = sum_f Hp^T rp of the point features `feats` of a scene, in state columns, and
+    per feature (over `feats`, in that order) chi2 = rp^T (Hp P_f Hp^T + I)^-1 rp (P_f the marginal of P on the feature's columns;
+    P defaults to the scene's) and dof = rows - 3.  Returns dict(A, b, rr, chi2, dof)."""
+    feats = range(sc.F) if feats is None else [int(f) for f in feats]
+    P = sc.P if P is None else P
+    N = sc.N
+    A = np.zeros((N, N), dtype=LD)
+    b = np.zeros(N, dtype=LD)
+    rr = LD(0)
+    chi2, dof = [], []
+    for f in feats:
+        H_f, H_x, res, order = np_ref.feature_jacobian_full(sc, f)
+        cols = np_ref.order_cols(order)
+        Hp, rp = nullspace_rows(H_f, H_x, res)
+        A[np.ix_(cols, cols)] += sym(Hp.T @ Hp)
+        b[cols] += Hp.T @ rp
+        rr += rp @ rp
+        dof.append(Hp.shape[0])
+        if with_chi2:
+            S = Hp @ ld(P[np.ix_(cols, cols)]) @ Hp.T + np.eye(Hp.shape[0], dtype=LD)
+            y = solve_lower(chol(sym(S)), rp)
+            chi2.append(y @ y)
+    return dict(A=A, b=b, rr=rr, chi2=np.array(chi2, dtype=LD), dof=np.array(dof, dtype=np.int64))
+
+
+# ---- the EKF tail ----------------------------------------------------------------------------------------------------------
+def update_from_pair(P, A, b, dtype=LD):
+    """P+ = (P^-1 + A)^-1 = (I + P A)^-1 P and dx = P+ b.  The second form needs no P^-1, so it holds for priors that are only
+    positive semi-definite (an exact clone, a clone of a clone): I + P A is regular for any P, A >= 0.  dtype=np.float64 is the same
+    algebra in double through LAPACK (the yardstick of a careful double implementation)."""
+    if dtype == np.float64:
+        P, A, b = (np.asarray(x, dtype=np.float64) for x in (P, A, b))
+        Pp = np.linalg.solve(np.eye(P.shape[0]) + P @ A, P)
+    else:
+        P, A, b = ld(P), ld(A), ld(b)
+        Pp = solve(np.eye(P.shape[0], dtype=LD) + P @ A, P)
+    Pp = sym(Pp)
+    return Pp, Pp @ b
+
+
+def chol_dropping(A, rel):
+    """Lower L with L L^T = A except in the columns whose pivot falls to rel x max diag(A) or below: those are zero (dropped, not
+    flagged).  The rule of the device's pivot-dropping factor (csrc/k_chol2.hip, piv_floor with floor_scale = max diag), in the
+    natural column order.  Returns (L, dropped columns)."""
+    A = ld(A)
+    n = A.shape[0]
+    L = np.zeros_like(A)
+    floor = LD(rel) * np.abs(np.diag(A)).max()
+    dropped = []
+    for j in range(n):
+        v = A[j:, j] - L[j:, :j] @ L[j, :j]
+        if not v[0] > floor:
+            dropped.append(j)
+            continue
+        L[j:, j] = v / np.sqrt(v[0])
+    return L, dropped
+
+
+def update_from_pair_dropping(P, A, b, rel=1e-13):
+    """The update the device's S-form retry (ekf_sform, behind a failed chol(P)) intends: H := La^T with La the pivot-dropping factor
+    of A (chol_dropping), P+ = P - P La (I + La^T P La)^-1 La^T P, dx = P+ b.  It differs from update_from_pair by the information
+    in the dropped directions only: pivots at or below rel x max diag(A), i.e. rounding noise of the pair."""
+    P = ld(P)
+    La, dropped = chol_dropping(A, rel)
+    W = P @ La
+    Pp = sym(P - W @ solve(np.eye(P.shape[0], dtype=LD) + La.T @ W, W.T))
+    return Pp, Pp @ ld(b), dropped
+
+
+def update_from_pair_info(P, A, b):
+    """The information form (P^-1 + A)^-1 of the same update, for positive definite priors."""
+    Pp = sym(inv_spd(sym(inv_spd(ld(P)) + ld(A))))
+    return Pp, Pp @ ld(b)
+
+
+def ekf_update_dense(P, cols, H, r):
+    """StateHelper::EKFUpdate with R = I (state/StateHelper.cpp:121-202), S-form: M = P[:, cols] H^T, S = H P[cols, cols] H^T + I,
+    P+ = P - M S^-1 M^T, dx = M S^-1 r."""
+    P, H, r = ld(P), ld(H), ld(r)
+    cols = np.asarray(cols, dtype=np.int64)
+    M = P[:, cols] @ H.T
+    S = sym(H @ P[np.ix_(cols, cols)] @ H.T + np.eye(H.shape[0], dtype=LD))
+    L = chol(S)
+    W = solve_lower(L, M.T)  # L^-1 M^T
+    y = solve_lower(L, r)
+    return sym(P - W.T @ W), W.T @ y
+
+
+# ---- error metrics ---------------------------------------------------------------------------------------------------------
+def _scale(d):
+    d = np.sqrt(np.abs(np.asarray(d, dtype=np.float64)))
+    d[d == 0] = 1.0
+    return d
+
+
+def err_state(dx, dx_true, P_true):
+    """max_i |dx_i - dx_true_i| / sqrt(P+_true_ii): the state error in standard deviations of the updated state."""
+    return float((np.abs(np.asarray(dx, dtype=LD) - ld(dx_true)) / _scale(np.diag(P_true))).max())
+
+
+def rel_p(P, P_true):
+    """max_ij |P_ij - P_true_ij| / sqrt(P_true_ii P_true_jj) (correlation-normalised, as the parity tests measure it)."""
+    d = _scale(np.diag(P_true))
+    return float((np.abs(np.asarray(P, dtype=LD) - ld(P_true)) / np.outer(d, d)).max())
+
+
+def rel_diag(P, P_true, cols):
+    """max_{i in cols} |P_ii - P_true_ii| / P_true_ii: the diagonal alone, in units of itself."""
+    cols = np.asarray(cols, dtype=np.int64)
+    d = np.abs(np.diag(ld(P_true))[cols])
+    return float((np.abs(np.diag(np.asarray(P, dtype=LD))[cols] - np.diag(ld(P_true))[cols]) / np.where(d > 0, d, 1)).max())
+
+
+def err_chi2(c, c_true):
+    """max_f |chi2_f - chi2_true_f| / max(1, chi2_true_f)."""
+    c_true = ld(c_true)
+    return float((np.abs(np.asarray(c, dtype=LD) - c_true) / np.maximum(1, np.abs(c_true))).max())
+
+
+def err_pair(A, b, A_true, b_true, rr_true):
+    """Pair errors on their natural scales: (max_ij |dA_ij| / sqrt(A_ii A_jj), max_i |db_i| / sqrt(A_ii rr)) with the truth's
+    diagonal and residual energy (|b_i| <= sqrt(A_ii rr) by Cauchy-Schwarz)."""
+    d = _scale(np.diag(A_true))
+    eA = float((np.abs(np.asarray(A, dtype=LD) - ld(A_true)) / np.outer(d, d)).max())
+    eb = float((np.abs(np.asarray(b, dtype=LD) - ld(b_true)) / (d * np.sqrt(max(float(rr_true), 1e-300)))).max())
+    return eA, eb

@@ -745,6 +745,12 @@ extern "C" long ovp_debug_read(ovp_ctx* c, const char* name, void* host, long ma
   else if (!strcmp(name, "An")) { src = c->pl_An; bytes = nn; if (!src) return OVP_E_STATE; }
   else if (!strcmp(name, "bn")) { src = c->pl_bn; bytes = (size_t)c->n_max * sizeof(double); if (!src) return OVP_E_STATE; }
   // camera tables on the device: camera 0's of ovp_state_upload / every camera's of ovp_cameras_upload ([k][20], layout of `cal`)
+  // capacity of the pinned result block the small fetches share (ovp_fetch_to_hres), one size_t
+  else if (!strcmp(name, "pl_hres_cap")) {
+    if ((size_t)max_bytes < sizeof(size_t)) return OVP_E_ARG;
+    memcpy(host, &c->pl_hres_cap, sizeof(size_t));
+    return (long)sizeof(size_t);
+  }
   else if (!strcmp(name, "cal")) { src = c->cal; bytes = 20 * sizeof(double); if (!src) return OVP_E_STATE; }
   else if (!strcmp(name, "gen_cal")) { src = c->gen_cal; bytes = (size_t)20 * c->gen_ncams * sizeof(double); if (!src) return OVP_E_STATE; }
   else if (!strcmp(name, "chi2")) {

@@ -137,13 +137,16 @@ __global__ __launch_bounds__(1024) void k_fetch_block(const unsigned char* __res
   if (threadIdx.x == 0) *seq_host = seq;
 }
 int ovp_fetch_to_hres(ovp_ctx* c, const void* dsrc, size_t bytes, hipStream_t s) {
-  if (!c->pl_hres_dev || bytes + 64 > c->pl_hres_cap || (((size_t)dsrc) & 7) || bytes > (size_t)0x7fffffff) {
+  // the sequence word sits at the start of the block's last whole 64-byte line: a block that reaches it would have its own last
+  // bytes overwritten by the word, so it takes the copy (plane2_buffers keeps the capacity a multiple of 64)
+  const size_t o_seq = c->pl_hres_cap >= 64 ? (c->pl_hres_cap - 64) & ~(size_t)63 : 0;
+  if (!c->pl_hres_dev || bytes > o_seq || (((size_t)dsrc) & 7) || bytes > (size_t)0x7fffffff) {
     HIPCHK(hipMemcpyAsync(c->pl_hres, dsrc, bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
   }
-  const size_t o_seq = (c->pl_hres_cap - 64) & ~(size_t)63;
   volatile unsigned* hseq = (volatile unsigned*)((char*)c->pl_hres + o_seq);
+  *hseq = 0u;  // (payload of an earlier, larger block may have left any value there, the next sequence number included)
   const unsigned seq = ++c->pl_pub_seq;
   hipLaunchKernelGGL(k_fetch_block, dim3(1), dim3(1024), 0, s, (const unsigned char*)dsrc, (unsigned char*)c->pl_hres_dev, (int)bytes,
                      (volatile unsigned*)((char*)c->pl_hres_dev + o_seq), seq);
@@ -197,7 +200,7 @@ int plane2_buffers(ovp_ctx* c, int NP, size_t stage_bytes, size_t res_bytes) {
   if (res_bytes > c->pl_hres_cap) {
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->pl_hres) hipHostFree(c->pl_hres);
-    c->pl_hres_cap = res_bytes + 4096;
+    c->pl_hres_cap = (res_bytes + 4096 + 63) & ~(size_t)63;  // (a multiple of 64: ovp_fetch_to_hres's sequence word ends the block)
     HIPCHK(hipHostMalloc(&c->pl_hres, c->pl_hres_cap, hipHostMallocMapped));
     memset(c->pl_hres, 0, c->pl_hres_cap);
     HIPCHK(hipHostGetDevicePointer(&c->pl_hres_dev, c->pl_hres, 0));
@@ -985,6 +988,7 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
   // (behind `used`, each on a 64-byte line of its own: the flags, the sequence word)
   char* hflags_pub = (char*)hused + (((size_t)F + 63) & ~(size_t)63);
   volatile unsigned* hseq = (volatile unsigned*)(hflags_pub + 64);
+  *hseq = 0u;  // (its offset depends on NP, n and F: an earlier call's payload may have left the next sequence number there)
   const unsigned seq = ++c->pl_pub_seq;
   {
     char* dbase = (char*)c->pl_hres_dev;
