@@ -378,7 +378,8 @@ typedef struct {
 int ovp_slam_update(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp_slam_batch *batch, double *dx_host, uint8_t *status,
                     double *chi2, ovp_update_info *info);
 
-/* UpdaterSLAM::delayed_init downstream of triangulation (update/UpdaterSLAM.cpp:204-364) for GLOBAL_3D landmarks without plane rows:
+/* UpdaterSLAM::delayed_init downstream of triangulation (update/UpdaterSLAM.cpp:204-364) for GLOBAL_3D landmarks without plane rows
+ * (candidates on a plane of the state: ovp_slam_delayed_init_planes below, the same loop with their point-on-plane rows):
  * the candidates of the batch one after the other - get_feature_jacobian_full at the pose tables as the previous candidate left
  * them, StateHelper::initialize (Givens split :434-446, chi2 of the update rows with dof = all rows :464-475,
  * initialize_invertible :489-586, EKFUpdate with the update rows :483-485) - as ONE enqueue with one synchronisation: the loop
@@ -417,6 +418,44 @@ int ovp_slam_update_general(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp
  * (k_init.hip) gives OVP_E_CAPACITY with nothing touched. */
 int ovp_slam_delayed_init_general(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp_general_batch *candidates, uint8_t *ok,
                                   double *chi2, int *new_id, double *delta_init, double *dx, int dx_stride);
+
+/* ---- delayed initialisation of candidates that lie on planes of the state (csrc/k_dinit.hip k_dinit_rows_pl / k_dinit_rows_gen_pl,
+ * csrc/k_init.hip k_init_*_sk) ---------------------------------------------------------------------------------------------------
+ * update/UpdaterSLAM.cpp:204-364 with use_plane_constraint_slamd: a candidate with m observations whose plane is a state variable
+ * gets, behind its 2m bearing rows, m equal point-on-plane rows (update/UpdaterHelper.cpp:447-512: residual -(n^T p - d)/sigma_c at
+ * the current values, H_f = n^T/sigma_c and H_c_plane in the plane's three columns at the first estimates when do_fej - the new
+ * landmark's first estimate is its value, the plane has cp_fej), and StateHelper::initialize runs on those 3m rows (chi2 of the
+ * 3m - 3 update rows against chi2_multiplier * quantile_0.95(3m)).  If that fails the candidate is tried once more without its plane,
+ * linearised at p_FinG_noplane (the position before plane refinement, UpdaterSLAM.cpp:320-321); if that fails too it is rejected.
+ * Every accepted candidate moves the state, the closest points of the planes included (Vec::update is additive): the planes live in
+ * a device table during the call, and the next candidate on the same plane is linearised at the corrected plane. */
+typedef struct {
+  int n_planes;                 /* planes of the STATE the candidates refer to */
+  const int *plane_state_id;    /* [n_planes] Type::id()                       */
+  const double *cp, *cp_fej;    /* [n_planes*3] value() / fej() (cp_fej NULL = cp) */
+  const int *plane_of_cand;     /* [n_feats] 0 = none, else 1-based slot (the convention of ovp_plane_batch::plane_of_feat) */
+  const double *p_FinG_noplane; /* [n_feats*3] linearisation point of the fallback attempt (features_p_FinG_original);
+                                   NULL = the same point as the first attempt */
+} ovp_dinit_planes;
+
+/* The loop of ovp_slam_delayed_init / ovp_slam_delayed_init_general - ONE enqueue, one synchronisation - for candidates with or
+ * without a plane.  candidates->cam_idx == NULL: every observation is camera 0's, tables of ovp_state_upload (the rows of
+ * ovp_slam_delayed_init); otherwise the general rows over ovp_cameras_upload.  At most OVP_MAX_MEAS observations per candidate.
+ * A plane candidate is enqueued as two attempts on the same three-column slot; the second reads the first one's verdict on the
+ * device and does nothing when it was accepted (no host round trip in between).
+ * status[l]: 0 rejected, 1 accepted (with its plane rows if it had a plane), 2 accepted by the fallback without them (the caller
+ * sets _features_SLAM_to_PLANE[featid] = 0) - the codes of ovp_slam_update; chi2[l] = statistic of the attempt that decided.
+ * new_id, delta_init, dx, dx_stride, the removal of rejected candidates' blocks and OVP_E_NEGDIAG as ovp_slam_delayed_init; the dx
+ * of an accepted candidate carries the correction of every plane's closest point at its state id, which the device table has
+ * already taken.  With planes == NULL, n_planes == 0 or plane_of_cand all zero the outputs equal those of ovp_slam_delayed_init /
+ * ovp_slam_delayed_init_general on the same input.
+ * OVP_E_ARG (checked before anything is enqueued): plane_of_cand outside [0, n_planes], a plane_state_id outside the covariance, a
+ * closest point of zero norm.  OVP_E_CAPACITY (nothing touched): as the entries above; a plane candidate has 3m - 3 update rows and
+ * three more columns, and the LDS of k_init_core (ovp_init_core_lds(3, 3m - 3, 6m + 17) against 152 KB) binds first: with all 14
+ * calibration columns estimated a camera-0 plane candidate fits up to m = 22 observations (m = 30 without a plane). */
+int ovp_slam_delayed_init_planes(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp_general_batch *candidates,
+                                 const ovp_dinit_planes *planes, uint8_t *status, double *chi2, int *new_id, double *delta_init,
+                                 double *dx, int dx_stride);
 
 /* StateHelper::EKFPropagation (state/StateHelper.cpp:41-119): new variables occupy [new_start, new_start+phi_size),
  * Phi is [phi_size x sum(old_sizes)] column-major, Q is [phi_size x phi_size] (upper triangle read). */

@@ -136,6 +136,18 @@ class GeneralBatch(C.Structure):
     ]
 
 
+class DinitPlanes(C.Structure):
+    """ovp_dinit_planes: the planes of the state the candidates of ovp_slam_delayed_init_planes refer to."""
+    _fields_ = [
+        ("n_planes", C.c_int),
+        ("plane_state_id", C.c_void_p),
+        ("cp", C.c_void_p),
+        ("cp_fej", C.c_void_p),
+        ("plane_of_cand", C.c_void_p),
+        ("p_FinG_noplane", C.c_void_p),
+    ]
+
+
 OVP_MAX_CAMERAS = 4
 OVP_GEN_MAX_MEAS = 64
 
@@ -168,6 +180,7 @@ EXPORTS = [
     "ovp_rccl_allreduce_gram", "ovp_msckf_update_sharded", "ovp_slam_delayed_init", "ovp_shard_range", "ovp_shard_range_of_mask",
     "ovp_rccl_gather_decisions", "ovp_msckf_dense_blocks", "ovp_cameras_upload", "ovp_msckf_general_features",
     "ovp_triangulate_general", "ovp_slam_update_general", "ovp_slam_delayed_init_general",
+    "ovp_slam_delayed_init_planes",
 ]
 
 
@@ -228,6 +241,8 @@ def lib():
                                               C.c_void_p, C.c_void_p, C.POINTER(UpdateInfo)]
         L.ovp_slam_delayed_init_general.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(GeneralBatch), C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.ovp_slam_delayed_init_planes.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(GeneralBatch), C.POINTER(DinitPlanes),
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.ovp_msckf_plane_update.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(PlaneBatch), C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ovp_plane_init.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(PlaneBatch), C.c_double, C.c_double,
@@ -810,6 +825,46 @@ class Context:
         if raise_on_error:
             _chk(rc, "ovp_slam_delayed_init_general")
         return dict(ok=ok[:L].astype(bool), chi2=chi2[:L], new_id=nid[:L], delta_init=dl[:L], dx=dx[:L], rc=rc)
+
+    def slam_delayed_init_planes(self, opts: UpdateOpts, uv, clone_idx, n_meas, p_FinG, cam_idx=None, plane_of_cand=None,
+                                 plane_state_id=None, cp=None, cp_fej=None, p_FinG_noplane=None, raise_on_error=True):
+        """ovp_slam_delayed_init_planes: the device candidate loop with the point-on-plane rows of candidates on planes of the state
+        and the fallback without them decided on the device.  cam_idx None = camera 0's rows (tables of state_upload), else the
+        general rows (cameras_upload).  plane_of_cand [L]: 0 = none, else 1-based slot into plane_state_id / cp / cp_fej; without
+        planes (plane_state_id None) the call is the plane-free loop.  Returns dict(status [L] 0 / 1 / 2, ok, chi2, new_id,
+        delta_init, dx, rc)."""
+        gb = self._general_batch(uv, clone_idx, cam_idx, n_meas, p_FinG)
+        if cam_idx is None:
+            gb.cam_idx = None
+        L = gb.n_feats
+        keep = []
+        dpl = None
+        if plane_state_id is not None:
+            sid = np.ascontiguousarray(plane_state_id, dtype=np.int32).reshape(-1)
+            cpv = np.ascontiguousarray(cp, dtype=np.float64).reshape(-1, 3)
+            cpf = None if cp_fej is None else np.ascontiguousarray(cp_fej, dtype=np.float64).reshape(-1, 3)
+            poc = np.ascontiguousarray(np.zeros(L) if plane_of_cand is None else plane_of_cand, dtype=np.int32).reshape(-1)
+            pnp = None if p_FinG_noplane is None else np.ascontiguousarray(p_FinG_noplane, dtype=np.float64).reshape(L, 3)
+            keep = [sid, cpv, cpf, poc, pnp]
+            dpl = DinitPlanes(int(sid.shape[0]), sid.ctypes.data, cpv.ctypes.data, None if cpf is None else cpf.ctypes.data,
+                              poc.ctypes.data, None if pnp is None else pnp.ctypes.data)
+        stride = self.cov_size() + 3 * L
+        st = np.zeros(max(L, 1), dtype=np.uint8)
+        chi2 = np.zeros(max(L, 1))
+        nid = -np.ones(max(L, 1), dtype=np.int32)
+        dl = np.zeros((max(L, 1), 3))
+        dx = np.zeros((max(L, 1), stride))
+        rc = lib().ovp_slam_delayed_init_planes(self._h, C.byref(opts), C.byref(gb), None if dpl is None else C.byref(dpl),
+                                                st.ctypes.data, chi2.ctypes.data, nid.ctypes.data, dl.ctypes.data, dx.ctypes.data, stride)
+        del keep
+        if raise_on_error:
+            _chk(rc, "ovp_slam_delayed_init_planes")
+        return dict(status=st[:L].copy(), ok=st[:L] > 0, chi2=chi2[:L], new_id=nid[:L], delta_init=dl[:L], dx=dx[:L], rc=rc)
+
+    def plane_table_download(self, n_planes):
+        """The device plane table of the last slam_delayed_init_planes, as its commits left it: (cp [n, 3], cp_fej [n, 3], id [n])."""
+        tab = self.debug_read("dinit_planes", (n_planes, 8))
+        return tab[:, 0:3].copy(), tab[:, 3:6].copy(), tab[:, 6].astype(np.int64)
 
     def camera_tables_download(self, n_cams):
         """The device's camera tables: (camera 0's of state_upload [20], the n_cams cameras of cameras_upload [n_cams, 20]); layout

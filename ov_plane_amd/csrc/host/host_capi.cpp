@@ -59,6 +59,12 @@ static int g_general_slam = 0;
 extern "C" void ovph_set_general_slam(int on) { g_general_slam = on != 0; }
 // path of the last UpdaterSLAM::update / delayed_init (UpdaterSLAM::Route: 1 device general, 2 device mono, 3 dense host, 4
 // per-candidate host loop, 0 none)
+// next ovph_run_updater: StateOptions::gpu_dinit_planes; mode 1: the positions before plane refinement of the candidates
+// (Feature::p_FinG_original, [F][3]) or nullptr
+static int g_dinit_planes = 0;
+static const double *g_p_noplane = nullptr;
+extern "C" void ovph_set_dinit_planes(int on) { g_dinit_planes = on != 0; }
+extern "C" void ovph_set_p_noplane(const double *p) { g_p_noplane = p; }
 extern "C" int ovph_last_slam_route() { return UpdaterSLAM::last_route(); }
 // next ovph_run_msckf_update: the State lives on this device and the updater takes the sharded point loop on this communicator
 static void *g_comm = nullptr;
@@ -518,6 +524,8 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
   so.max_features = F + 8;
   so.gpu_general_slam = g_general_slam != 0;
   g_general_slam = 0;
+  so.gpu_dinit_planes = g_dinit_planes != 0;
+  g_dinit_planes = 0;
   // ovph_set_second_camera: a stereo state (camera 1's calibration behind camera 0's) and the camera of every measurement
   const bool cam1 = g_cam1_q != nullptr;
   const int *cam_of = g_cam_of_meas;
@@ -531,6 +539,12 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
   const size_t id0 = (mode == 0) ? 9000 : 5000;
   auto fv = make_features(hs, F, M, uv, clone_idx, n_meas, p_FinG, id0, cam1 ? cam_of : nullptr);
   auto all = fv;
+  if (g_p_noplane && mode == 1)
+    for (int f = 0; f < F; ++f) {
+      fv[f]->has_p_FinG_original = true;
+      memcpy(fv[f]->p_FinG_original, g_p_noplane + 3 * f, 3 * sizeof(double));
+    }
+  g_p_noplane = nullptr;
   std::map<size_t, size_t> feat2plane;
   for (int f = 0; f < F; ++f)
     if (plane_of_feat && plane_of_feat[f] > 0) feat2plane[id0 + f] = (size_t)plane_of_feat[f];

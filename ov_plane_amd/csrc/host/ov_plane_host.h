@@ -70,6 +70,11 @@ struct StateOptions {
   // per-candidate loop, and their triangulation ovp_triangulate_general (every view with its own camera's extrinsics) instead of
   // ovp_triangulate.  OVP_E_CAPACITY of an entry falls back to the host form.  Not in the reference.
   bool gpu_general_slam = false;
+  // UpdaterSLAM::delayed_init: candidates that lie on a plane of the state (use_plane_constraint_slamd) stay in the device loop
+  // (ovp_slam_delayed_init_planes: their point-on-plane rows, the fallback without them, the plane commit, all on the device)
+  // instead of ending it - off: the first such candidate and everything behind it take the per-candidate host loop.
+  // OVP_E_CAPACITY falls back to that loop.  Not in the reference.
+  bool gpu_dinit_planes = false;
 };
 
 // update/UpdaterOptions.h:37-53
@@ -256,7 +261,8 @@ public:
   // which path the last update() / delayed_init() took (tests; not in the reference): ROUTE_DEVICE_GENERAL / ROUTE_DEVICE_MONO = the
   // general / mono device entry took every landmark or candidate, ROUTE_DENSE_HOST = update_dense, ROUTE_HOST_LOOP = some or all
   // candidates went through delayed_init_host_loop
-  enum Route { ROUTE_NONE = 0, ROUTE_DEVICE_GENERAL = 1, ROUTE_DEVICE_MONO = 2, ROUTE_DENSE_HOST = 3, ROUTE_HOST_LOOP = 4 };
+  enum Route { ROUTE_NONE = 0, ROUTE_DEVICE_GENERAL = 1, ROUTE_DEVICE_MONO = 2, ROUTE_DENSE_HOST = 3, ROUTE_HOST_LOOP = 4,
+               ROUTE_DEVICE_PLANES = 5 /* delayed_init: the device loop with plane candidates (gpu_dinit_planes) */ };
   static int last_route() { return _last_route; }
 
 protected:

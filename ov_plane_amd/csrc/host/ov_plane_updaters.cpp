@@ -1057,7 +1057,8 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
   // ---- the candidate loop on the device (ovp_slam_delayed_init, csrc/k_dinit.hip): GLOBAL_3D landmarks without plane rows -
   // every shipped configuration's feat_rep_slam - run as ONE enqueue: rows at the device tables, split, gate, augmentation,
   // update and the Type::update of the device tables per candidate without the host in between.  Candidates that carry plane
-  // rows (use_plane_constraint_slamd with the plane in the state) and the other representations take the per-candidate path
+  // rows (use_plane_constraint_slamd with the plane in the state) stay in that loop with StateOptions::gpu_dinit_planes
+  // (ovp_slam_delayed_init_planes); without it they, and the other representations always, take the per-candidate path
   // below (dense Jacobians on the host); the order of the vector is kept (every initialisation moves the state of the next).
   auto wants_plane = [&](const ov_core::Feature &ft) {
     if (!(state->_options.use_plane_constraint && state->_options.use_plane_constraint_slamd)) return false;
@@ -1099,6 +1100,29 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
       }
       memcpy(&pf[3 * l], ft.p_FinG, 3 * sizeof(double));
     }
+    // StateOptions::gpu_dinit_planes: the planes of the run's candidates as a table, every candidate's slot in it, the fallback points
+    const bool planes_on = state->_options.gpu_dinit_planes;
+    std::vector<size_t> pl_ids;  // plane ids of the table's slots
+    std::vector<int> pl_sid, poc(L, 0);
+    std::vector<double> pl_cp, pl_cpf, pnp((size_t)L * 3);
+    bool any_plane = false;
+    if (planes_on)
+      for (int l = 0; l < L; ++l) {
+        ov_core::Feature &ft = *feature_vec[run_begin + l];
+        memcpy(&pnp[3 * l], ft.has_p_FinG_original ? ft.p_FinG_original : ft.p_FinG, 3 * sizeof(double));
+        if (!wants_plane(ft)) continue;
+        const size_t pid = feat2plane.at(ft.featid);
+        size_t q = 0;
+        while (q < pl_ids.size() && pl_ids[q] != pid) ++q;
+        if (q == pl_ids.size()) {
+          const auto pl = state->_features_PLANE.at(pid);
+          pl_ids.push_back(pid);
+          pl_sid.push_back(pl->id());
+          for (int k = 0; k < 3; ++k) pl_cp.push_back(pl->value()(k)), pl_cpf.push_back(pl->fej()(k));
+        }
+        poc[l] = (int)q + 1;
+        any_plane = true;
+      }
     ovp_feature_batch fb{L, M, uv.data(), cidx.data(), nm.data(), pf.data()};
     ovp_update_opts uo;
     memset(&uo, 0, sizeof(uo));
@@ -1114,7 +1138,12 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
     std::vector<double> dl((size_t)3 * L, 0.0), dxs((size_t)L * stride, 0.0);
     const double t_c = now_s();
     int rc;
-    if (general) {
+    if (planes_on) {
+      if (general) upload_camera_tables(state);
+      ovp_general_batch gb{L, M, uv.data(), cidx.data(), general ? camv.data() : nullptr, nm.data(), pf.data()};
+      ovp_dinit_planes dpl{(int)pl_ids.size(), pl_sid.data(), pl_cp.data(), pl_cpf.data(), poc.data(), pnp.data()};
+      rc = ovp_slam_delayed_init_planes(state->_gpu, &uo, &gb, &dpl, okv.data(), nullptr, nid.data(), dl.data(), dxs.data(), stride);
+    } else if (general) {
       upload_camera_tables(state);
       ovp_general_batch gb{L, M, uv.data(), cidx.data(), camv.data(), nm.data(), pf.data()};
       rc = ovp_slam_delayed_init_general(state->_gpu, &uo, &gb, okv.data(), nullptr, nid.data(), dl.data(), dxs.data(), stride);
@@ -1126,24 +1155,29 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
       fprintf(stderr, "StateHelper::EKFUpdate() - negative covariance diagonal\n");
       std::exit(EXIT_FAILURE);
     }
-    gpu_check2(rc, general ? "ovp_slam_delayed_init_general" : "ovp_slam_delayed_init");
-    _last_route = (general || _last_route == ROUTE_DEVICE_GENERAL) ? ROUTE_DEVICE_GENERAL : ROUTE_DEVICE_MONO;
+    gpu_check2(rc, planes_on ? "ovp_slam_delayed_init_planes" : general ? "ovp_slam_delayed_init_general" : "ovp_slam_delayed_init");
+    if (any_plane || _last_route == ROUTE_DEVICE_PLANES) _last_route = ROUTE_DEVICE_PLANES;
+    else _last_route = (general || _last_route == ROUTE_DEVICE_GENERAL) ? ROUTE_DEVICE_GENERAL : ROUTE_DEVICE_MONO;
     g_diprof.t_init += now_s() - t_c;
     g_diprof.cands += L;
     size_t pos = run_begin;
     for (int l = 0; l < L; ++l) {
       ov_core::Feature &ft = *feature_vec[pos];
       ft.to_delete = true;
+      // a plane candidate that did not keep its plane (status 2, or rejected: the reference drops the plane in front of the second
+      // attempt, :316-319); status 1 on a plane records it further down
+      if (poc[l] > 0 && okv[l] != 1) state->_features_SLAM_to_PLANE[ft.featid] = 0;
       if (!okv[l]) {  // :360-363
         feature_vec.erase(feature_vec.begin() + (long)pos);
         continue;
       }
+      const double *p_lin = okv[l] == 2 ? &pnp[3 * l] : ft.p_FinG;  // (the attempt that was accepted was linearised here)
       auto landmark = std::make_shared<Landmark>(3);  // :285-296
       landmark->_featid = ft.featid;
       landmark->_feat_representation = LandmarkRepresentation::Representation::GLOBAL_3D;
       landmark->_unique_camera_id = ft.anchor_cam_id;
-      landmark->set_from_xyz(ft.p_FinG, false);
-      landmark->set_from_xyz(ft.p_FinG, true);
+      landmark->set_from_xyz(p_lin, false);
+      landmark->set_from_xyz(p_lin, true);
       VectorXd d(3, 1);
       for (int k = 0; k < 3; ++k) d(k) = dl[3 * l + k];
       landmark->update(d);  // state/StateHelper.cpp:577
@@ -1151,6 +1185,7 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
       state->_variables.push_back(landmark);
       StateHelper::apply_correction(state, &dxs[(size_t)l * stride]);  // :483-485 Type::update of every variable
       state->_features_SLAM.insert({ft.featid, landmark});
+      if (poc[l] > 0 && okv[l] == 1) state->_features_SLAM_to_PLANE[ft.featid] = pl_ids[poc[l] - 1];
       g_diprof.accepted++;
       ++pos;
     }
@@ -1161,7 +1196,7 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
     bool all_done = true;
     while (i < feature_vec.size()) {
       size_t j = i;
-      while (j < feature_vec.size() && !wants_plane(*feature_vec[j])) ++j;
+      while (j < feature_vec.size() && (state->_options.gpu_dinit_planes || !wants_plane(*feature_vec[j]))) ++j;
       if (j > i) {
         const size_t behind = flush_run(i, j);
         if (behind == (size_t)-1) {
@@ -1268,6 +1303,12 @@ void UpdaterSLAM::delayed_init_host_loop(std::shared_ptr<State> state, std::vect
       if (in_state || pid == 0) break;
       state->_features_SLAM_to_PLANE[ft.featid] = 0;  // the plane is dropped for this feature, whatever the second attempt says
       pid = 0;
+      if (ft.has_p_FinG_original && !anchored) {  // :320-321 back to the position before plane refinement
+        memcpy(value, ft.p_FinG_original, 3 * sizeof(double));
+        memcpy(first, value, 3 * sizeof(double));
+        landmark->set_from_xyz(value, false);
+        landmark->set_from_xyz(first, true);
+      }
     }
     g_diprof.accepted += in_state;
     ft.to_delete = true;

@@ -456,6 +456,10 @@ struct Feature {
     return true;
   }
   double p_FinG[3] = {0, 0, 0};
+  // optional: the position before plane refinement (features_p_FinG_original, update/UpdaterSLAM.cpp:320-321) - the linearisation
+  // point of delayed_init's second attempt, without the plane; unset = p_FinG
+  bool has_p_FinG_original = false;
+  double p_FinG_original[3] = {0, 0, 0};
   // anchor of the triangulated position (ext FeatureInitializer::single_triangulation: the last pose of the camera that saw
   // the feature most); -1 = triangulation has not filled it, p_FinA is then derived from p_FinG where it is needed
   int anchor_cam_id = -1;

@@ -39,6 +39,16 @@ struct DinitGenParams {
   int idg[6 * OVP_MAX_MEAS_DEV + 14 * OVP_GEN_MAX_CAMS];  // the state columns of the list, by value
 };
 
+// the _pl instances (ovp_slam_delayed_init_planes): the device plane table and this attempt's part in it
+#define OVP_DINIT_PLTAB 8  // doubles per plane: cp (3) | cp_fej (3) | Type::id() | -
+struct DinitPlaneParams {
+  double* tab;         // [n_planes][OVP_DINIT_PLTAB]; every accepted candidate's commit adds its correction to every cp
+  int n_planes;
+  int slot;            // plane of this attempt, 1-based (its m point-on-plane rows and three columns), 0 = none
+  double white_c;      // 1 / sigma_constraint
+  const double* skip;  // attempt B of a plane candidate: attempt A's result block (skip[1] > 0.5 = A accepted, nothing to do)
+};
+
 }  // namespace ovp
 
 extern "C" {
@@ -46,4 +56,8 @@ size_t ovp_dinit_rows_lds(int m_obs, int ncal);
 hipError_t ovp_launch_dinit_rows(const ovp::DinitParams* dp, size_t lds, hipStream_t stream);
 size_t ovp_dinit_gen_rows_lds(int m_obs, int cols);
 hipError_t ovp_launch_dinit_rows_gen(const ovp::DinitGenParams* gp, size_t lds, hipStream_t stream);
+// the _pl instances: rows = 2m or 3m, cols = columns of H_x with the plane's three
+size_t ovp_dinit_pl_rows_lds(int rows, int cols);
+hipError_t ovp_launch_dinit_rows_pl(const ovp::DinitParams* dp, const ovp::DinitPlaneParams* pp, size_t lds, hipStream_t stream);
+hipError_t ovp_launch_dinit_rows_gen_pl(const ovp::DinitGenParams* gp, const ovp::DinitPlaneParams* pp, size_t lds, hipStream_t stream);
 }

@@ -62,14 +62,37 @@ __device__ __forceinline__ void di_lds_barrier() { asm volatile("s_waitcnt lgkmc
 // spills the prefetch to scratch - a dispatch that needs scratch behind ones that do not costs tens of microseconds on this stack)
 __global__ __launch_bounds__(DI_T) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_dinit_rows(DinitParams dp) {
 #define DI_GEN 0
+#define DI_PL 0
 #include "k_dinit_body.h"
+#undef DI_PL
 #undef DI_GEN
 }
 
 __global__ __launch_bounds__(DI_T) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_dinit_rows_gen(DinitGenParams gp) {
   const DinitParams& dp = gp.dp;
 #define DI_GEN 1
+#define DI_PL 0
 #include "k_dinit_body.h"
+#undef DI_PL
+#undef DI_GEN
+}
+
+// the two above with the point-on-plane rows, the plane commit and the attempt-B predicate (ovp_slam_delayed_init_planes)
+__global__ __launch_bounds__(DI_T) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_dinit_rows_pl(DinitParams dp, DinitPlaneParams pp) {
+#define DI_GEN 0
+#define DI_PL 1
+#include "k_dinit_body.h"
+#undef DI_PL
+#undef DI_GEN
+}
+
+__global__ __launch_bounds__(DI_T) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_dinit_rows_gen_pl(DinitGenParams gp,
+                                                                                                        DinitPlaneParams pp) {
+  const DinitParams& dp = gp.dp;
+#define DI_GEN 1
+#define DI_PL 1
+#include "k_dinit_body.h"
+#undef DI_PL
 #undef DI_GEN
 }
 
@@ -84,6 +107,33 @@ size_t ovp_dinit_rows_lds(int m_obs, int ncal) {
 size_t ovp_dinit_gen_rows_lds(int m_obs, int cols) {
   const int rows = 2 * m_obs, W = (cols + 4) | 1;
   return sizeof(double) * ((size_t)rows * W + rows + 8 + (size_t)(cols + 2) / 2 + 2);
+}
+
+size_t ovp_dinit_pl_rows_lds(int rows, int cols) {
+  const int W = (cols + 4) | 1;
+  return sizeof(double) * ((size_t)rows * W + rows + 8 + (size_t)(cols + 2) / 2 + 2);
+}
+
+hipError_t ovp_launch_dinit_rows_pl(const ovp::DinitParams* dp, const ovp::DinitPlaneParams* pp, size_t lds, hipStream_t stream) {
+  static unsigned long long attr_mask = 0;  // per device (ovp_kernels.h)
+  if (ovp_lds_attr_needed(&attr_mask)) {
+    (void)hipFuncSetAttribute((const void*)ovp::k_dinit_rows_pl, hipFuncAttributeMaxDynamicSharedMemorySize, OVP_DINIT_DYN_LDS);
+    (void)hipGetLastError();
+    ovp_lds_attr_done(&attr_mask);
+  }
+  hipLaunchKernelGGL(ovp::k_dinit_rows_pl, dim3(1), dim3(DI_T), lds, stream, *dp, *pp);
+  return hipGetLastError();
+}
+
+hipError_t ovp_launch_dinit_rows_gen_pl(const ovp::DinitGenParams* gp, const ovp::DinitPlaneParams* pp, size_t lds, hipStream_t stream) {
+  static unsigned long long attr_mask = 0;  // per device (ovp_kernels.h)
+  if (ovp_lds_attr_needed(&attr_mask)) {
+    (void)hipFuncSetAttribute((const void*)ovp::k_dinit_rows_gen_pl, hipFuncAttributeMaxDynamicSharedMemorySize, OVP_DINIT_DYN_LDS);
+    (void)hipGetLastError();
+    ovp_lds_attr_done(&attr_mask);
+  }
+  hipLaunchKernelGGL(ovp::k_dinit_rows_gen_pl, dim3(1), dim3(DI_T), lds, stream, *gp, *pp);
+  return hipGetLastError();
 }
 
 hipError_t ovp_launch_dinit_rows_gen(const ovp::DinitGenParams* gp, size_t lds, hipStream_t stream) {

@@ -4,10 +4,19 @@
 //             local columns [clone blocks of the distinct clones in first-seen order | estimated calibration columns of every
 //             camera of the candidate, in camera order]; the commit applies the previous correction to camera 0's DinitParams::cal
 //             AND to every camera of the general tables
+//   DI_PL 1   k_dinit_rows_pl(DinitParams dp, DinitPlaneParams pp) / k_dinit_rows_gen_pl(DinitGenParams gp, DinitPlaneParams pp):
+//             the same two for ovp_slam_delayed_init_planes.  pp.slot > 0: the candidate lies on plane pp.slot - 1 of the device plane
+//             table: m point-on-plane rows behind the 2m bearing rows (ovp_feat_model.h build_plane_row, the row of k_slam_body.h),
+//             the plane's three columns behind the calibration columns, the split of H_f over 3m rows.  The commit also adds the
+//             previous correction to the closest point of EVERY plane of the table.  pp.skip != nullptr: this is attempt B of a plane
+//             candidate (no plane rows, linearised at p_FinG_noplane, no commit - attempt A did it): nothing to do when A was accepted.
 // (in the kernel function itself rather than in a device function template, so that the mono instance stays the kernel it was)
   extern __shared__ double sm[];
   const int t = threadIdx.x;
   const FeatParams& p = dp.fp;
+#if DI_PL
+  if (pp.skip && pp.skip[1] > 0.5) return;  // (attempt A stands; k_init_update_sk forwards its result block)
+#endif
 #ifdef OVP_DI_STAMPS
   long long st[12];
   int sti = 0;
@@ -24,7 +33,14 @@
   const int m = dp.m_obs;
   const int C = p.n_clones;
   const int ncal = __popc(p.calmask & 0x3FFFu);
+#if DI_PL
+  const int pl = dp.cand >= 0 ? pp.slot : 0;  // 1-based slot of the candidate's plane, 0 = no plane rows
 #if DI_GEN
+  const int cols = gp.cols, rows = (pl ? 3 : 2) * m, W = (cols + 4) | 1;  // (gp.cols counts the plane's three columns)
+#else
+  const int cols = 6 * m + ncal + (pl ? 3 : 0), rows = (pl ? 3 : 2) * m, W = (cols + 4) | 1;
+#endif
+#elif DI_GEN
   const int cols = gp.cols, rows = 2 * m, W = (cols + 4) | 1;  // (clone blocks of the distinct clones, every camera's calibration)
 #else
   const int cols = 6 * m + ncal, rows = 2 * m, W = (cols + 4) | 1;  // [H_f (3) | H_x (cols) | res], odd pitch (LDS banks)
@@ -38,6 +54,11 @@
 #if DI_GEN
   __shared__ double tabG[20 * OVP_GEN_MAX_CAMS];  // every camera's tables (ovp_cameras_upload), camera 0 included
   __shared__ int cam_s[OVP_MAX_MEAS_DEV];
+#endif
+#if DI_PL
+  __shared__ double pl_s[OVP_DINIT_PLTAB];  // the candidate's plane: cp | cp_fej | id
+  double ldq = 0.0;
+  if (pl && t >= 96 && t < 96 + OVP_DINIT_PLTAB) ldq = pp.tab[(size_t)(pl - 1) * OVP_DINIT_PLTAB + (t - 96)];
 #endif
   // (a) previous result + tables + this candidate's inputs
   double ld0 = 0.0, ld1 = 0.0, ld2 = 0.0, ld3 = 0.0, ld4 = 0.0;
@@ -75,6 +96,9 @@
 #endif
   if (t < C) cid_s[t] = li0;
   if (t == 0) okf = ld4;
+#if DI_PL
+  if (t >= 96 && t < 96 + OVP_DINIT_PLTAB) pl_s[t - 96] = ldq;
+#endif
   if (l >= 0) {
     if (t < m) ci_s[t] = li1;
     if (t < 2 * m) uv_s[t] = lf0;
@@ -115,6 +139,18 @@
         for (int k = 0; k < 20; ++k) gp.cam_cal[20 * c + k] = tc[k];
       }
 #endif
+#if DI_PL
+      else if (t == 65) {  // the candidate's own plane in LDS: the same sum as the table's entry below
+        if (pl)
+          for (int k = 0; k < 3; ++k) pl_s[k] += dxs[(int)pl_s[6] + k];
+      } else if (t >= 256) {  // Vec::update of every plane's closest point (additive), one thread per plane
+        for (int q = t - 256; q < pp.n_planes; q += DI_T - 256) {
+          double* e = pp.tab + (size_t)q * OVP_DINIT_PLTAB;
+          const int id = (int)e[6];
+          for (int k = 0; k < 3; ++k) e[k] += dxs[id + k];
+        }
+      }
+#endif
     } else {
       // rejected: its three columns stay as an inert block (nobody reads it; the host removes it after the loop)
       double* P = dp.P;
@@ -139,7 +175,11 @@
 #endif
   di_lds_barrier();
   DI_STAMP();
+#if DI_PL
+  if (t < 2 * m) {
+#else
   if (t < rows) {
+#endif
     const int a = t >> 1, r = t & 1;
     // the measurement model on the LDS copies: tables as the commit above left them, this candidate's inputs as feature 0
     FeatParams q = p;
@@ -169,6 +209,18 @@
       if ((p.calmask >> k) & 1) h[cc + __popc(p.calmask & ((1u << k) - 1u))] = crow[k];
     h[3 + cols] = res;
   }
+#if DI_PL
+  if (pl && t >= 128 && t < 128 + m) {
+    // point-on-plane row of observation t - 128 (all m equal, UpdaterHelper.cpp:503-511); the new landmark's first estimate is its
+    // value, the plane has its own
+    double hf[3], hc[3], res;
+    build_plane_row(pf_s, pf_s, pl_s, pl_s + 3, p.do_fej, pp.white_c, hf, hc, res);
+    double* h = A + (size_t)(2 * m + (t - 128)) * W;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) h[k] = hf[k], h[3 + cols - 3 + k] = hc[k];
+    h[3 + cols] = res;
+  }
+#endif
   di_lds_barrier();
   DI_STAMP();
   // ---- H_f = Q [R3; 0]: three reflectors applied to [H_f | H_x | res] ----

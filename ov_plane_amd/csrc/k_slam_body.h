@@ -99,28 +99,11 @@
     if (plane && t >= 64 && t < 64 + m) {
       // point-on-plane row (update/UpdaterHelper.cpp:448-512), once per observation (:503-511); the plane is a state variable
       const int a = t - 64;
-      const double* pv = p.p_FinG + 3 * l;
-      const double* cpv = sp.cp + 3 * l;
-      double d = sqrt(cpv[0] * cpv[0] + cpv[1] * cpv[1] + cpv[2] * cpv[2]);
-      double n0 = cpv[0] / d, n1 = cpv[1] / d, n2 = cpv[2] / d;
-      const double res = sp.white_c * (0.0 - (n0 * pv[0] + n1 * pv[1] + n2 * pv[2] - d));
-      double q0 = pv[0], q1 = pv[1], q2 = pv[2];
-      if (p.do_fej) {  // :467-476
-        const double* pf = sp.p_fej + 3 * l;
-        const double* cf = sp.cp_fej + 3 * l;
-        q0 = pf[0], q1 = pf[1], q2 = pf[2];
-        d = sqrt(cf[0] * cf[0] + cf[1] * cf[1] + cf[2] * cf[2]);
-        n0 = cf[0] / d, n1 = cf[1] / d, n2 = cf[2] / d;
-      }
-      const double np = n0 * q0 + n1 * q1 + n2 * q2;
-      const double s = sp.white_c * 1.0 / d;
+      double hf[3], hc[3], res;
+      build_plane_row(p.p_FinG + 3 * l, sp.p_fej + 3 * l, sp.cp + 3 * l, sp.cp_fej + 3 * l, p.do_fej, sp.white_c, hf, hc, res);
       double* h = H + (size_t)(2 * m + a) * cols;
-      h[6 * m + ncal_all + 0] = sp.white_c * n0;  // H_f row (:497)
-      h[6 * m + ncal_all + 1] = sp.white_c * n1;
-      h[6 * m + ncal_all + 2] = sp.white_c * n2;
-      h[6 * m + ncal_all + 3] = s * (q0 - np * n0 - d * n0);  // H_c_plane (:479-481)
-      h[6 * m + ncal_all + 4] = s * (q1 - np * n1 - d * n1);
-      h[6 * m + ncal_all + 5] = s * (q2 - np * n2 - d * n2);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) h[6 * m + ncal_all + k] = hf[k], h[6 * m + ncal_all + 3 + k] = hc[k];
       r0[2 * m + a] = res;
     }
   }

@@ -753,6 +753,12 @@ extern "C" long ovp_debug_read(ovp_ctx* c, const char* name, void* host, long ma
   }
   else if (!strcmp(name, "cal")) { src = c->cal; bytes = 20 * sizeof(double); if (!src) return OVP_E_STATE; }
   else if (!strcmp(name, "gen_cal")) { src = c->gen_cal; bytes = (size_t)20 * c->gen_ncams * sizeof(double); if (!src) return OVP_E_STATE; }
+  // plane table of the last ovp_slam_delayed_init_planes ([n_planes][8]: cp | cp_fej | id | -), valid until the next call that stages
+  else if (!strcmp(name, "dinit_planes")) {
+    if (!c->pl_dstage || c->dinit_nplanes < 1) return OVP_E_STATE;
+    src = (const char*)c->pl_dstage + c->dinit_pltab_off;
+    bytes = (size_t)8 * c->dinit_nplanes * sizeof(double);
+  }
   else if (!strcmp(name, "chi2")) {
     hipStreamSynchronize(c->stream);
     bytes = (size_t)c->n_feats * sizeof(double);

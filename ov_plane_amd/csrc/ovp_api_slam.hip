@@ -433,9 +433,18 @@ extern "C" int ovp_slam_update_general(ovp_ctx* c, const ovp_update_opts* o, con
 // or from an ovp_general_batch (ovp_slam_delayed_init_general: every camera's tables from ovp_cameras_upload; a candidate's columns are
 // the clone blocks of its distinct clones in first-seen order, then the estimated calibration columns of each of its cameras in
 // camera order; every commit updates camera 0's table of ovp_state_upload AND every camera of ovp_cameras_upload).
+//
+// with_planes (ovp_slam_delayed_init_planes; csrc/k_dinit.hip k_dinit_rows_pl / k_dinit_rows_gen_pl, csrc/k_init.hip *_sk): a
+// candidate on a plane of the state (pl->plane_of_cand) is enqueued as TWO attempts on the same three-column slot - A with its m
+// point-on-plane rows and the plane's columns at p_FinG, B without them at p_FinG_noplane; B's four kernels read A's result block
+// on the device and do nothing but forward it when A was accepted, so the loop stays one enqueue.  The planes live in a device
+// table [cp | cp_fej | id] inside the staging block, and every commit adds the accepted correction to every closest point.
+// ok_host then carries the status codes of ovp_slam_update (0 / 1 / 2).  Without with_planes nothing here differs from before.
+#define DINIT_MAX_ROWS_THREADS 1024  // (one thread per row in the rows kernel's workgroup)
 static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, int M, const float* b_uv, const int* b_clone_idx,
                                   const int* cam_idx, const int* b_n_meas, const double* b_p, uint8_t* ok_host, double* chi2_host,
-                                  int* new_id, double* delta_init, double* dx_host, int dx_stride) {
+                                  int* new_id, double* delta_init, double* dx_host, int dx_stride, bool with_planes = false,
+                                  const ovp_dinit_planes* pl = nullptr) {
   drop_kept_factor(c);  // (writes the covariance: a kept factor no longer belongs to it)
   if (!c || !o || L < 0) return OVP_E_ARG;
   if (!c->have_state || !c->have_cov) return OVP_E_STATE;
@@ -459,6 +468,23 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
       for (int k = 0; k < 14; ++k)
         if (((calmask >> k) & 1) && (gcal(cam, k) < 0 || gcal(cam, k) >= n0)) return OVP_E_ARG;
   const int C = (int)c->h_clone_id.size();
+  // the planes of the call: every argument checked before anything is enqueued
+  const int n_pl = with_planes && pl ? pl->n_planes : 0;
+  if (n_pl < 0) return OVP_E_ARG;
+  if (n_pl > 0) {
+    if (!pl->plane_state_id || !pl->cp || !pl->plane_of_cand) return OVP_E_ARG;
+    for (int q = 0; q < n_pl; ++q) {
+      const int id = pl->plane_state_id[q];
+      if (id < 0 || id + 3 > n0 || id + 3 > OVP_LDG_CAP) return OVP_E_ARG;  // (outside the covariance / the commit's staged correction)
+      const double* a = pl->cp + 3 * q;
+      const double* f = (pl->cp_fej ? pl->cp_fej : pl->cp) + 3 * q;
+      if (!(a[0] * a[0] + a[1] * a[1] + a[2] * a[2] > 0.0) || !(f[0] * f[0] + f[1] * f[1] + f[2] * f[2] > 0.0)) return OVP_E_ARG;
+    }
+  }
+  auto slot_of = [&](int l) { return n_pl > 0 ? pl->plane_of_cand[l] : 0; };
+  if (with_planes && pl && pl->plane_of_cand)
+    for (int l = 0; l < L; ++l)
+      if (pl->plane_of_cand[l] < 0 || pl->plane_of_cand[l] > n_pl) return OVP_E_ARG;
   // every candidate's column list (general: distinct clones, cameras) - ocol / ccol: local column of observation a's clone block /
   // of camera k's calibration block
   std::vector<std::vector<int>> cand_ids(L), cand_ocol(gen ? L : 0), cand_ccol(gen ? L : 0);
@@ -510,7 +536,30 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
         (gen ? ovp_dinit_gen_rows_lds(m, cols) : ovp_dinit_rows_lds(m, ncal)) > OVP_DINIT_DYN_LDS) return OVP_E_CAPACITY;
     cols_max = std::max(cols_max, cols);
     rows_max = std::max(rows_max, 2 * m);
+    if (slot_of(l) > 0) {  // attempt A: m more rows, the plane's three columns
+      const int colsA = cols + 3, rowsA = 3 * m;
+      if (rowsA - 3 > ovp_init_max_rows() || ovp_init_core_lds(3, rowsA - 3, colsA) > ovp_init_max_lds() ||
+          ovp_dinit_pl_rows_lds(rowsA, colsA) > OVP_DINIT_DYN_LDS || rowsA > DINIT_MAX_ROWS_THREADS ||
+          colsA > (int)(gen ? sizeof(ovp::DinitGenParams::idg) : sizeof(ovp::DinitParams::idv)) / (int)sizeof(int))
+        return OVP_E_CAPACITY;
+      cols_max = std::max(cols_max, colsA);
+      rows_max = std::max(rows_max, rowsA);
+    }
   }
+  // the attempts of the loop in order: candidate, plane slot (0 = none), result block, block of the attempt it may skip behind
+  struct Attempt {
+    int l, slot, blk, skip_blk;
+  };
+  std::vector<Attempt> att;
+  std::vector<int> blk_final(L), blk_A(L);
+  for (int l = 0; l < L; ++l) {
+    const int sl = slot_of(l);
+    blk_A[l] = (int)att.size();
+    att.push_back({l, sl, (int)att.size(), -1});
+    if (sl > 0) att.push_back({l, 0, (int)att.size(), (int)att.size() - 1});
+    blk_final[l] = (int)att.size() - 1;
+  }
+  const int NA = (int)att.size();
   hipStream_t s = c->stream;
   auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
   // staging: the candidates as a feature batch + their column lists
@@ -521,11 +570,13 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
     return o0;
   };
   const size_t o_p = take(sizeof(double) * 3 * L), o_uv = take(sizeof(float) * 2 * (size_t)L * M), o_ci = take(sizeof(int) * (size_t)L * M),
-               o_nm = take(sizeof(int) * L), o_id = take(sizeof(int) * (size_t)L * cols_max);
+               o_nm = take(sizeof(int) * L), o_id = take(sizeof(int) * (size_t)NA * cols_max);
   const size_t o_cam = take(gen ? sizeof(int) * (size_t)L * M : 0);  // (general only)
+  // (with planes only) the fallback's linearisation points and the plane table
+  const size_t o_p2 = take(with_planes ? sizeof(double) * 3 * L : 0), o_pt = take(sizeof(double) * OVP_DINIT_PLTAB * (size_t)n_pl);
   const size_t stage_bytes = off;
   const size_t res_doubles = 4 + (size_t)c->n_max + 8;
-  int rc = plane2_buffers(c, 0, stage_bytes, sizeof(double) * res_doubles * L + 64);
+  int rc = plane2_buffers(c, 0, stage_bytes, sizeof(double) * res_doubles * NA + 64);
   if (rc) return rc;
   char* h = (char*)c->pl_hstage;
   char* d = (char*)c->pl_dstage;
@@ -534,10 +585,28 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
   memcpy(h + o_ci, b_clone_idx, sizeof(int) * (size_t)L * M);
   memcpy(h + o_nm, b_n_meas, sizeof(int) * L);
   if (gen) memcpy(h + o_cam, cam_idx, sizeof(int) * (size_t)L * M);
-  for (int l = 0; l < L; ++l) memcpy((int*)(h + o_id) + (size_t)l * cols_max, cand_ids[l].data(), sizeof(int) * cand_ids[l].size());
+  for (int a = 0; a < NA; ++a) {
+    int* dst = (int*)(h + o_id) + (size_t)a * cols_max;
+    const std::vector<int>& ids = cand_ids[att[a].l];
+    memcpy(dst, ids.data(), sizeof(int) * ids.size());
+    if (att[a].slot > 0)
+      for (int k = 0; k < 3; ++k) dst[ids.size() + k] = pl->plane_state_id[att[a].slot - 1] + k;
+  }
+  if (with_planes) {
+    memcpy(h + o_p2, pl && pl->p_FinG_noplane ? pl->p_FinG_noplane : b_p, sizeof(double) * 3 * L);
+    double* tab = (double*)(h + o_pt);
+    for (int q = 0; q < n_pl; ++q) {
+      double* e = tab + (size_t)q * OVP_DINIT_PLTAB;
+      for (int k = 0; k < 3; ++k) e[k] = pl->cp[3 * q + k], e[3 + k] = (pl->cp_fej ? pl->cp_fej : pl->cp)[3 * q + k];
+      e[6] = (double)pl->plane_state_id[q];
+      e[7] = 0.0;
+    }
+    c->dinit_pltab_off = o_pt;
+    c->dinit_nplanes = n_pl;
+  }
   // device scratch: [result blocks L x res_doubles | Ht | Mall | Linv | y | Hinv 9 | Rk 9 | resid]
   const size_t n_end = (size_t)n0 + 3 * L;
-  const size_t need = res_doubles * L + (size_t)cols_max * rows_max + n_end * rows_max + (size_t)rows_max * rows_max + rows_max + 32 +
+  const size_t need = res_doubles * NA + (size_t)cols_max * rows_max + n_end * rows_max + (size_t)rows_max * rows_max + rows_max + 32 +
                       rows_max + 64;
   if (need > c->dinit_cap) {
     if (c->dinit_buf) hipFree(c->dinit_buf);
@@ -547,7 +616,7 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
     c->dinit_cap = need + 1024;
   }
   double* dres0 = c->dinit_buf;
-  double* dHt = dres0 + res_doubles * L;
+  double* dHt = dres0 + res_doubles * NA;
   double* dM = dHt + (size_t)cols_max * rows_max;
   double* dLi = dM + n_end * rows_max;
   double* dy = dLi + (size_t)rows_max * rows_max;
@@ -588,43 +657,63 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
     gp.cam_intr_id[k] = c->gen_intr_id[k];
   }
   gp.cam_idx = (const int*)(d + o_cam);
-  for (int l = 0; l < L; ++l) {
-    const int m = b_n_meas[l], cols = (int)cand_ids[l].size(), rows = 2 * m, rup = rows - 3, n = n0 + 3 * l;
+  ovp::DinitPlaneParams pp;  // (with planes only)
+  memset(&pp, 0, sizeof(pp));
+  pp.tab = (double*)(d + o_pt);
+  pp.n_planes = n_pl;
+  pp.white_c = 1.0 / o->sigma_constraint;
+  for (int a = 0; a < NA; ++a) {
+    const int l = att[a].l, sl = att[a].slot;
+    const int m = b_n_meas[l], cols = (int)cand_ids[l].size() + (sl > 0 ? 3 : 0), rows = (sl > 0 ? 3 : 2) * m, rup = rows - 3,
+              n = n0 + 3 * l;
+    const bool second = att[a].skip_blk >= 0;  // attempt B: attempt A has committed the previous candidate
+    const double* skip = second ? dres0 + res_doubles * att[a].skip_blk : nullptr;
     dp.cand = l;
     dp.m_obs = m;
     dp.n = n;
-    dp.prev_res = l ? dres0 + res_doubles * (l - 1) : nullptr;
-    dp.ids = (const int*)(d + o_id) + (size_t)l * cols_max;
-    dp.res = dres0 + res_doubles * l;
+    dp.prev_res = (a && !second) ? dres0 + res_doubles * (a - 1) : nullptr;
+    dp.ids = (const int*)(d + o_id) + (size_t)a * cols_max;
+    dp.res = dres0 + res_doubles * a;
+    dp.fp.p_FinG = (const double*)(d + (second ? o_p2 : o_p));
+    pp.slot = sl;
+    pp.skip = skip;
+    const int* hids = (const int*)(h + o_id) + (size_t)a * cols_max;
     if (gen) {
       gp.dp = dp;
       gp.cols = cols;
-      memcpy(gp.idg, cand_ids[l].data(), sizeof(int) * cols);
+      memcpy(gp.idg, hids, sizeof(int) * cols);
       memcpy(gp.ocol, cand_ocol[l].data(), sizeof(gp.ocol));
       memcpy(gp.ccol, cand_ccol[l].data(), sizeof(gp.ccol));
-      HIPCHK(ovp_launch_dinit_rows_gen(&gp, ovp_dinit_gen_rows_lds(m, cols), s));
+      if (with_planes) HIPCHK(ovp_launch_dinit_rows_gen_pl(&gp, &pp, ovp_dinit_pl_rows_lds(rows, cols), s));
+      else HIPCHK(ovp_launch_dinit_rows_gen(&gp, ovp_dinit_gen_rows_lds(m, cols), s));
     } else {
-      memcpy(dp.idv, cand_ids[l].data(), sizeof(int) * cols);
-      HIPCHK(ovp_launch_dinit_rows(&dp, ovp_dinit_rows_lds(m, ncal), s));
+      memcpy(dp.idv, hids, sizeof(int) * cols);
+      if (with_planes) HIPCHK(ovp_launch_dinit_rows_pl(&dp, &pp, ovp_dinit_pl_rows_lds(rows, cols), s));
+      else HIPCHK(ovp_launch_dinit_rows(&dp, ovp_dinit_rows_lds(m, ncal), s));
     }
-    HIPCHK(ovp_launch_init_m(c->P, ld, n, dp.ids, cols, dHt, rows, dM, s));  // M = P[:, ids] H_all^T on many workgroups
+    HIPCHK(ovp_launch_init_m_sk(skip, c->P, ld, n, dp.ids, cols, dHt, rows, dM, s));  // M = P[:, ids] H_all^T on many workgroups
     // chi2 of the update rows with dof = all rows (StateHelper.cpp:471), initialize_invertible, update in place
     const double thr = o->chi2_multiplier * ovp_chi2_quantile_095(rows);
-    HIPCHK(ovp_launch_init_core(c->P, ld, n, dp.ids, cols, dHt, 3, rup, dM, dHinv, dRk, dresid, 1.0, thr, dLi, dy, dp.res, s));
-    HIPCHK(ovp_launch_init_update(c->P, c->P, ld, n + 3, dM, rows, 3, rup, dLi, dy, dp.res, dp.res + 4, s));
+    HIPCHK(ovp_launch_init_core_sk(skip, c->P, ld, n, dp.ids, cols, dHt, 3, rup, dM, dHinv, dRk, dresid, 1.0, thr, dLi, dy, dp.res, s));
+    HIPCHK(ovp_launch_init_update_sk(skip, (int)res_doubles, c->P, c->P, ld, n + 3, dM, rows, 3, rup, dLi, dy, dp.res, dp.res + 4, s));
   }
   dp.cand = -1;
   dp.n = (int)n_end;
-  dp.prev_res = dres0 + res_doubles * (L - 1);
+  dp.prev_res = dres0 + res_doubles * (NA - 1);
+  dp.fp.p_FinG = (const double*)(d + o_p);
+  pp.slot = 0;
+  pp.skip = nullptr;
   if (gen) {
     gp.dp = dp;
-    HIPCHK(ovp_launch_dinit_rows_gen(&gp, 64, s));
+    if (with_planes) HIPCHK(ovp_launch_dinit_rows_gen_pl(&gp, &pp, 64, s));
+    else HIPCHK(ovp_launch_dinit_rows_gen(&gp, 64, s));
   } else {
-    HIPCHK(ovp_launch_dinit_rows(&dp, 64, s));
+    if (with_planes) HIPCHK(ovp_launch_dinit_rows_pl(&dp, &pp, 64, s));
+    else HIPCHK(ovp_launch_dinit_rows(&dp, 64, s));
   }
   double* hres = (double*)c->pl_hres;
   {
-    const int rf = ovp_fetch_to_hres(c, dres0, sizeof(double) * res_doubles * L, s);
+    const int rf = ovp_fetch_to_hres(c, dres0, sizeof(double) * res_doubles * NA, s);
     if (rf) return rf;
   }
   c->n = (int)n_end;
@@ -632,7 +721,7 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
   std::vector<int> final_id(L, -1);
   int n_acc = 0, negdiag = 0;
   for (int l = 0; l < L; ++l) {
-    const double* r = hres + res_doubles * l;
+    const double* r = hres + res_doubles * blk_final[l];  // (the block of the attempt that decided: B carries A's when A stood)
     if (r[1] > 0.5) final_id[l] = n0 + 3 * n_acc++;
     if (r[1] > 0.5 && r[2] != 0.0) negdiag = 1;
   }
@@ -642,9 +731,11 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
       if (rc) return rc;
     }
   for (int l = 0; l < L; ++l) {
-    const double* r = hres + res_doubles * l;
+    const double* r = hres + res_doubles * blk_final[l];
     const bool ok = r[1] > 0.5;
-    if (ok_host) ok_host[l] = ok ? 1 : 0;
+    // with planes: 1 = accepted (with its plane rows if it had a plane), 2 = accepted by the fallback without them
+    const bool by_B = blk_final[l] != blk_A[l] && !(hres[res_doubles * blk_A[l] + 1] > 0.5);
+    if (ok_host) ok_host[l] = ok ? (by_B ? 2 : 1) : 0;
     if (chi2_host) chi2_host[l] = r[0];
     if (new_id) new_id[l] = final_id[l];
     if (delta_init)
@@ -671,6 +762,17 @@ extern "C" int ovp_slam_delayed_init(ovp_ctx* c, const ovp_update_opts* o, const
   }
   return slam_delayed_init_impl(c, o, b->n_feats, b->max_meas, b->uv, b->clone_idx, nullptr, b->n_meas, b->p_FinG, ok_host, chi2_host,
                                 new_id, delta_init, dx_host, dx_stride);
+}
+
+extern "C" int ovp_slam_delayed_init_planes(ovp_ctx* c, const ovp_update_opts* o, const ovp_general_batch* b, const ovp_dinit_planes* pl,
+                                            uint8_t* status_host, double* chi2_host, int* new_id, double* delta_init, double* dx_host,
+                                            int dx_stride) {
+  if (!c || !o || !b || (b->cam_idx && c->gen_ncams < 1)) {
+    drop_kept_factor(c);
+    return OVP_E_ARG;
+  }
+  return slam_delayed_init_impl(c, o, b->n_feats, b->max_meas, b->uv, b->clone_idx, b->cam_idx, b->n_meas, b->p_FinG, status_host,
+                                chi2_host, new_id, delta_init, dx_host, dx_stride, true, pl);
 }
 
 extern "C" int ovp_slam_delayed_init_general(ovp_ctx* c, const ovp_update_opts* o, const ovp_general_batch* b, uint8_t* ok_host,

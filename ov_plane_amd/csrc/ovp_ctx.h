@@ -98,6 +98,15 @@ hipError_t ovp_launch_init_core(double* P, int ldp, int n, const int* ids, int c
                                 double* y, double* res, hipStream_t stream);
 hipError_t ovp_launch_init_update(const double* Psrc, double* Pdst, int ldp, int n2, const double* Mall, int m, int k, int rup,
                                   const double* Linv, const double* y, double* res, double* dx, hipStream_t stream);
+// the same three behind a device-side predicate (k_init.hip *_sk; skip == nullptr: the plain kernels)
+hipError_t ovp_launch_init_m_sk(const double* skip, const double* P, int ldp, int n, const int* ids, int cols, const double* Ht, int m,
+                                double* Mall, hipStream_t stream);
+hipError_t ovp_launch_init_core_sk(const double* skip, double* P, int ldp, int n, const int* ids, int cols, const double* Ht, int k,
+                                   int rup, double* Mall, const double* Hinv, const double* Rk, const double* resid, double r_iso,
+                                   double thr, double* Linv, double* y, double* res, hipStream_t stream);
+hipError_t ovp_launch_init_update_sk(const double* skip, int res_len, const double* Psrc, double* Pdst, int ldp, int n2,
+                                     const double* Mall, int m, int k, int rup, const double* Linv, const double* y, double* res,
+                                     double* dx, hipStream_t stream);
 size_t ovp_init_core_lds(int k, int rup, int cols);
 size_t ovp_init_max_lds();
 int ovp_init_max_rows();
@@ -183,6 +192,8 @@ struct ovp_ctx {
   size_t slam_res_cap = 0, slam_hscr_cap = 0;
   double* dinit_buf = nullptr;     // ovp_slam_delayed_init: result blocks + shared scratch of the candidate loop
   size_t dinit_cap = 0;
+  size_t dinit_pltab_off = 0;      // ovp_slam_delayed_init_planes: the plane table of the last call inside pl_dstage (debug read)
+  int dinit_nplanes = 0;
   size_t Hd_cap = 0, res_cap = 0;
   int calib_id = -1, intr_id = -1;
   long long* dbg_cycles = nullptr;

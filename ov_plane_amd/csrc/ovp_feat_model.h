@@ -175,4 +175,29 @@ __device__ __forceinline__ void build_bearing_row(const FeatParams& p, int f, in
     }
   }
 
+// Point-on-plane row of a landmark whose plane is a state variable (update/UpdaterHelper.cpp:448-512; the same row once per
+// observation, :503-511): residual at the current values (pv, cpv), Jacobians at the first estimates (pf, cf) when do_fej (:467-476).
+// hf = the landmark's three columns (:497), hc = the closest point's (:479-481).  Shared by the SLAM gate kernels (k_slam_body.h) and
+// the delayed-initialisation row kernels (k_dinit_body.h).
+__device__ __forceinline__ void build_plane_row(const double* pv, const double* pf, const double* cpv, const double* cf, int do_fej,
+                                                double white_c, double (&hf)[3], double (&hc)[3], double& res) {
+  double d = sqrt(cpv[0] * cpv[0] + cpv[1] * cpv[1] + cpv[2] * cpv[2]);
+  double n0 = cpv[0] / d, n1 = cpv[1] / d, n2 = cpv[2] / d;
+  res = white_c * (0.0 - (n0 * pv[0] + n1 * pv[1] + n2 * pv[2] - d));
+  double q0 = pv[0], q1 = pv[1], q2 = pv[2];
+  if (do_fej) {  // :467-476
+    q0 = pf[0], q1 = pf[1], q2 = pf[2];
+    d = sqrt(cf[0] * cf[0] + cf[1] * cf[1] + cf[2] * cf[2]);
+    n0 = cf[0] / d, n1 = cf[1] / d, n2 = cf[2] / d;
+  }
+  const double np = n0 * q0 + n1 * q1 + n2 * q2;
+  const double s = white_c * 1.0 / d;
+  hf[0] = white_c * n0;  // H_f row (:497)
+  hf[1] = white_c * n1;
+  hf[2] = white_c * n2;
+  hc[0] = s * (q0 - np * n0 - d * n0);  // H_c_plane (:479-481)
+  hc[1] = s * (q1 - np * n1 - d * n1);
+  hc[2] = s * (q2 - np * n2 - d * n2);
+}
+
 }  // namespace ovp

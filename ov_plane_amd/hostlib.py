@@ -122,8 +122,12 @@ def set_slam_force_dense(on: bool):
     lib().ovph_set_slam_force_dense(C.c_int(1 if on else 0))
 
 
+# UpdaterSLAM::last_route() (ovph_last_slam_route)
+ROUTE_NONE, ROUTE_DEVICE_GENERAL, ROUTE_DEVICE_MONO, ROUTE_DENSE_HOST, ROUTE_HOST_LOOP, ROUTE_DEVICE_PLANES = 0, 1, 2, 3, 4, 5
+
+
 def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=None, slam=None, slam_rep=None,
-                feat_rep_slam=None, general_slam=False, triangulate=False):
+                feat_rep_slam=None, general_slam=False, triangulate=False, dinit_planes=False, state_planes=False):
     """Drives the C++ host mirrors on a synth scene.
     fit_planes=dict(min_feat, max_cond, variant) (mode "plane_init" only): the features carry normalised measurements and
     no position, no plane estimates are handed over - init_vio_plane triangulates, fits and refines itself.
@@ -135,11 +139,20 @@ def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=
     A stereo scene (synth.make_stereo_slam_scene / make_stereo_scene: sc.cam1, sc.cam_idx) gets a two-camera state; out["cam1"] is
     camera 1's [q | p | intrinsics] afterwards.  general_slam: StateOptions::gpu_general_slam (other cameras' landmarks and candidates
     take ovp_slam_update_general / ovp_slam_delayed_init_general / ovp_triangulate_general); out["route"] = the path UpdaterSLAM took
-    (1 device general, 2 device mono, 3 dense host, 4 per-candidate host loop).  triangulate (mode "slam_delayed_init"): the
+    (1 device general, 2 device mono, 3 dense host, 4 per-candidate host loop, 5 device loop with plane candidates).  triangulate (mode "slam_delayed_init"): the
     candidates carry sc.uv_norm and no position, delayed_init triangulates them.
+    state_planes (mode "slam_delayed_init"): the scene's planes are variables of the state (synth.make_dinit_plane_scene) and the
+    candidates carry sc.p_FinG_noplane as their position before plane refinement; dinit_planes: StateOptions::gpu_dinit_planes
+    (candidates on those planes stay in the device loop, ovp_slam_delayed_init_planes; route 5).
     """
     L = lib()
     L.ovph_set_general_slam(1 if general_slam else 0)
+    L.ovph_set_dinit_planes(1 if dinit_planes else 0)
+    pnp_keep = None
+    if state_planes:
+        assert mode == "slam_delayed_init" and bool(np.all(sc.plane_in_state))
+        pnp_keep = np.ascontiguousarray(sc.get("p_FinG_noplane", sc.p_FinG), dtype=np.float64)
+        L.ovph_set_p_noplane(pnp_keep.ctypes.data_as(C.c_void_p))
     cam1 = sc.get("cam1", None)
     cam_keep = None
     if cam1 is not None:
@@ -170,7 +183,7 @@ def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=
     N, F, M = int(sc.N), int(sc.F), int(sc.uv.shape[1])
     n_slam = F if m == 0 else 0
     n_pl_total = int(sc.cp.shape[0])
-    n_pl_in = n_pl_total if m == 0 else 0
+    n_pl_in = n_pl_total if (m == 0 or state_planes) else 0
     n_pl_out = n_pl_total if m == 2 else 0
     n_cap = N + 3 * F + 3 * n_pl_total + 8
     dummy = np.zeros((1, 3))

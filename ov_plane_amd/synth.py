@@ -543,7 +543,7 @@ def make_stereo_scene(C=8, F=60, seed=0, stereo_frac=0.5, baseline=0.11, **kw):
     (along camera 0's x axis) with slightly different intrinsics.
     Extra keys: cam1 = dict(calib_q, calib_p, intr, calib_id, intr_id), cam_idx [F, M] (M = 2 C), ids["calib1"], ids["intr1"]."""
     base = make_scene(C=C, F=F, seed=seed, **kw)
-    assert base.cp.shape[0] == 0 and base.opts["do_calib_pose"] and not base.get("fisheye", False)
+    assert base.opts["do_calib_pose"] and not base.get("fisheye", False)
     rng = np.random.default_rng(9000 + seed)
     N0, at = int(base.N), 30            # camera 1's block goes in front of the clones (id 30 in the mono layout)
     N = N0 + 14
@@ -597,7 +597,8 @@ def make_stereo_scene(C=8, F=60, seed=0, stereo_frac=0.5, baseline=0.11, **kw):
             n_meas[f] = 2 * m
     ids = dict(base.ids)
     ids["calib1"], ids["intr1"] = at, at + 6
-    ids["clones"] = np.asarray(base.ids["clones"]) + 14
+    for key in ("clones", "slam", "planes"):  # (everything behind camera 1's block moves up by its 14 columns)
+        ids[key] = np.asarray(base.ids[key]) + 14
     ids["N"] = N
     # normalised measurements as the tracker stores them: undistorted with the estimate of the intrinsics of the camera that took them
     uv_norm = np.zeros((F, Mm, 2), dtype=np.float32)
@@ -609,7 +610,9 @@ def make_stereo_scene(C=8, F=60, seed=0, stereo_frac=0.5, baseline=0.11, **kw):
     for f in range(F):
         uv_norm[f, int(n_meas[f]):] = 0.0
     sc = Scene(base)
-    sc.update(N=N, ids=ids, P=P, uv=uv, clone_idx=clone_idx, cam_idx=cam_idx, n_meas=n_meas, cam1=cam1, n_stereo=n_st, uv_norm=uv_norm)
+    pst = np.asarray(base.plane_state_id)
+    sc.update(N=N, ids=ids, P=P, uv=uv, clone_idx=clone_idx, cam_idx=cam_idx, n_meas=n_meas, cam1=cam1, n_stereo=n_st, uv_norm=uv_norm,
+              plane_state_id=np.where(pst >= 0, pst + 14, -1).astype(pst.dtype))
     return sc
 
 
@@ -726,6 +729,37 @@ def make_stereo_slam_scene(C=11, n_slam=12, seed=0, n_planes=0, stereo_frac=0.5,
     sc = Scene(base)
     sc.update(N=N, ids=ids, P=P, uv=uv, clone_idx=clone_idx, cam_idx=cam_idx, n_meas=n_meas, cam1=cam1, n_stereo=n_st, uv_norm=uv_norm,
               lm_id=np.asarray(base.lm_id, dtype=np.int32) + 14, plane_state_id=np.where(pst >= 0, pst + 14, -1).astype(pst.dtype))
+    return sc
+
+
+def make_dinit_plane_scene(C=11, F=14, n_planes=3, wrong_plane=0, outliers=0, seed=0, stereo=False, **kw):
+    """Candidates of UpdaterSLAM::delayed_init that lie on planes of the state (update/UpdaterSLAM.cpp:204-364 with
+    use_plane_constraint_slamd): the F features are NOT in the state, every one of the n_planes planes IS (planes_in_state_frac = 1;
+    cp = truth - err, consistent with P; cp_fej its own small perturbation), and the candidates are dealt to the planes in turn
+    (plane_id[f] = 1 + f % n_planes: several candidates per plane).  The first `wrong_plane` candidates are associated with a plane
+    they do not lie on (the plane rows fail the gate, the attempt without them passes), the last `outliers` get gross pixel noise (both
+    attempts fail).  p_FinG = the triangulated positions; p_FinG_noplane = the linearisation point of the attempt without the plane
+    (features_p_FinG_original; here the same point - a caller that refines p_FinG towards the plane keeps the original in it).
+    stereo=True: make_stereo_scene's two-camera state (camera 1's calibration in front of the clones, the first half of the
+    candidates seen by both cameras: tracks of up to 2 C views), otherwise make_scene's mono state.  Bit-reproducible: the prior is
+    summed without BLAS (_cov)."""
+    assert n_planes >= 1
+    fpp = (F + n_planes - 1) // n_planes
+    args = dict(C=C, F=F, seed=seed, ragged=True, n_planes=n_planes, feats_per_plane=fpp, planes_in_state_frac=1.0, min_meas=min(3, C))
+    args.update(kw)
+    sc = make_stereo_scene(stereo_frac=0.5, **args) if stereo else make_scene(**args)
+    sc = Scene(sc)
+    rng = np.random.default_rng(4100 + seed)
+    uv = sc.uv.copy()
+    for f in range(min(outliers, F)):
+        g = F - 1 - f
+        m = int(sc.n_meas[g])
+        uv[g, :m] += (25.0 * rng.standard_normal((m, 2))).astype(np.float32)
+    plane_id = sc.plane_id.copy()
+    if n_planes > 1:
+        for f in range(min(wrong_plane, F)):
+            plane_id[f] = 1 + (int(plane_id[f]) % n_planes)
+    sc.update(uv=uv, plane_id=plane_id, p_FinG_noplane=sc.p_FinG.copy(), wrong_plane=int(min(wrong_plane, F)), outliers=int(min(outliers, F)))
     return sc
 
 
