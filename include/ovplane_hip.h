@@ -326,6 +326,26 @@ typedef struct {
 int ovp_msckf_plane_update(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp_plane_batch *planes, double *dx_planes,
                            uint8_t *plane_ok, double *plane_chi2, int *plane_dof, uint8_t *feat_used);
 
+/* The same loop with the on-plane features the batch format cannot carry - observations of another camera, tracks of more than
+ * OVP_MAX_MEAS views - stacked behind the batch's: the reference builds the 2m bearing rows of an on-plane MSCKF feature over every
+ * camera that saw it (update/UpdaterHelper.cpp:335-344) and its m point-on-plane rows (:448-512) whatever the length of the track,
+ * and the plane loop (update/UpdaterMSCKF.cpp:411-649) uses them all.  general = such features (ovp_general_batch; p_FinG = their
+ * linearisation points), plane_of_gen[general->n_feats] = 1-based plane slot as plane_of_feat, 0 = not on a plane: ignored by this
+ * call.  For every plane the general features lying on it are linearised at the state the previous plane left (clone tables, every
+ * camera of ovp_cameras_upload, the in-state planes), their rows are projected onto the complement of H_f's range and their
+ * contribution enters the plane's extended pair in front of the Schur complement and the normalisation (csrc/k_plane_feat_gen.hip):
+ * an out-of-state plane, an in-state plane and the gate statistic see batch features and general features as ONE system.  The row
+ * counts of the gate, the column order of the loop and the sub-state form above 287 columns count the general features' clones and
+ * the calibration columns of their cameras.  An accepted plane's commit also corrects the tables of ovp_cameras_upload.
+ * gen_used[general->n_feats] = 1 for the general features an accepted plane consumed (may be NULL); the other outputs as above.
+ * Needs ovp_cameras_upload when a general feature lies on a plane.  Limits of the general entries, checked on the host before
+ * anything is enqueued (covariance and tables untouched): OVP_E_CAPACITY for n_meas > OVP_GEN_MAX_MEAS; OVP_E_ARG for a camera
+ * without tables, a clone slot outside the tables, n_meas > max_meas, plane_of_gen outside [0, n_planes].  With no general feature
+ * on a plane the call enqueues exactly what ovp_msckf_plane_update enqueues and returns the same bits. */
+int ovp_msckf_plane_update_general(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp_plane_batch *planes,
+                                   const ovp_general_batch *general, const int *plane_of_gen, double *dx_planes, uint8_t *plane_ok,
+                                   double *plane_chi2, int *plane_dof, uint8_t *feat_used, uint8_t *gen_used);
+
 /* UpdaterPlane::init_vio_plane, core (update/UpdaterPlane.cpp:296-481): for every plane of the batch (none of them in the
  * state; plane_state_id is ignored), in ascending id: stack the on-plane MSCKF features with sigma_c * const_init_multi,
  * project out the feature, compress, StateHelper::initialize(plane, ..., const_init_chi2) = chi2 test of the part that

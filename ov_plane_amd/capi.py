@@ -180,7 +180,7 @@ EXPORTS = [
     "ovp_rccl_allreduce_gram", "ovp_msckf_update_sharded", "ovp_slam_delayed_init", "ovp_shard_range", "ovp_shard_range_of_mask",
     "ovp_rccl_gather_decisions", "ovp_msckf_dense_blocks", "ovp_cameras_upload", "ovp_msckf_general_features",
     "ovp_triangulate_general", "ovp_slam_update_general", "ovp_slam_delayed_init_general",
-    "ovp_slam_delayed_init_planes",
+    "ovp_slam_delayed_init_planes", "ovp_msckf_plane_update_general",
 ]
 
 
@@ -245,6 +245,8 @@ def lib():
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.ovp_msckf_plane_update.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(PlaneBatch), C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ovp_msckf_plane_update_general.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(PlaneBatch), C.POINTER(GeneralBatch),
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ovp_plane_init.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(PlaneBatch), C.c_double, C.c_double,
                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]
@@ -680,6 +682,59 @@ class Context:
             raise OvpError(rc, "ovp_msckf_plane_update")
         return dict(dx=dx[:npl], ok=ok[:npl].astype(bool), chi2=chi2[:npl], dof=dof[:npl],
                     used=used[: self.n_feats].astype(bool), rc=rc)
+
+    def plane_update_general(self, opts: UpdateOpts, plane_of_feat, cp, cp_fej, plane_state_id, sc=None, feats=None, uv=None,
+                             clone_idx=None, cam_idx=None, n_meas=None, p_FinG=None, plane_of_gen=None, raise_on_error=True,
+                             slam=None, force_decision=None):
+        """ovp_msckf_plane_update_general: the plane loop with the on-plane features of a general batch behind the uploaded batch's.
+        The general batch = the features `feats` of a scene (uv, clone_idx, cam_idx, n_meas, p_FinG; plane_of_gen defaults to their
+        sc.plane_id; a scene without cam_idx is camera 0 only) or explicit arrays; None / empty = no general features.
+        Returns plane_update's dict plus gen_used [bool]."""
+        if sc is not None:
+            sel = np.asarray(feats, dtype=np.int64)
+            uv, clone_idx, n_meas, p_FinG = sc.uv[sel], sc.clone_idx[sel], sc.n_meas[sel], sc.p_FinG[sel]
+            cam_idx = sc.cam_idx[sel] if "cam_idx" in sc else None
+            if plane_of_gen is None:
+                plane_of_gen = sc.plane_id[sel]
+        if uv is None or len(uv) == 0:
+            gb = GeneralBatch(0, 0, None, None, None, None, None)
+            pog = np.zeros(1, dtype=np.int32)
+        else:
+            gb = self._general_batch(uv, clone_idx, cam_idx, n_meas, p_FinG)
+            pog = np.ascontiguousarray(plane_of_gen, dtype=np.int32)
+            assert pog.shape[0] == gb.n_feats
+        GF = gb.n_feats
+        plane_of_feat = np.ascontiguousarray(plane_of_feat, dtype=np.int32)
+        cp = np.ascontiguousarray(cp, dtype=np.float64)
+        cp_fej = np.ascontiguousarray(cp_fej, dtype=np.float64)
+        sid = np.ascontiguousarray(plane_state_id, dtype=np.int32)
+        npl = int(sid.shape[0])
+        n = self.cov_size()
+        dx = np.zeros((max(npl, 1), n))
+        ok = np.zeros(max(npl, 1), dtype=np.uint8)
+        chi2 = np.zeros(max(npl, 1))
+        dof = np.zeros(max(npl, 1), dtype=np.int32)
+        used = np.zeros(max(self.n_feats, 1), dtype=np.uint8)
+        gused = np.zeros(max(GF, 1), dtype=np.uint8)
+        pb = PlaneBatch(npl, plane_of_feat.ctypes.data, cp.ctypes.data, cp_fej.ctypes.data, sid.ctypes.data)
+        if slam is not None and len(slam["id"]):
+            s_pl = np.ascontiguousarray(slam["plane"], dtype=np.int32)
+            s_id = np.ascontiguousarray(slam["id"], dtype=np.int32)
+            s_p = np.ascontiguousarray(slam["p"], dtype=np.float64)
+            s_pf = np.ascontiguousarray(slam["p_fej"], dtype=np.float64)
+            pb.n_slam = len(s_id)
+            pb.slam_plane, pb.slam_state_id = s_pl.ctypes.data, s_id.ctypes.data
+            pb.slam_p, pb.slam_p_fej = s_p.ctypes.data, s_pf.ctypes.data
+        if force_decision is not None:
+            fd = np.ascontiguousarray(force_decision, dtype=np.uint8)
+            assert fd.shape[0] == npl
+            pb.force_decision = fd.ctypes.data
+        rc = lib().ovp_msckf_plane_update_general(self._h, C.byref(opts), C.byref(pb), C.byref(gb), pog.ctypes.data, dx.ctypes.data,
+                                                  ok.ctypes.data, chi2.ctypes.data, dof.ctypes.data, used.ctypes.data, gused.ctypes.data)
+        if rc != 0 and raise_on_error:
+            raise OvpError(rc, "ovp_msckf_plane_update_general")
+        return dict(dx=dx[:npl], ok=ok[:npl].astype(bool), chi2=chi2[:npl], dof=dof[:npl], used=used[: self.n_feats].astype(bool),
+                    gen_used=gused[:GF].astype(bool), rc=rc)
 
     def plane_init(self, opts: UpdateOpts, plane_of_feat, cp, const_init_multi, const_init_chi2):
         """UpdaterPlane::init_vio_plane core. Returns dict(dx [n_planes, stride], ok, chi2, dof, new_ids, cp, used)."""

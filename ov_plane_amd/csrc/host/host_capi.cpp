@@ -54,6 +54,9 @@ extern "C" void ovph_set_second_camera(const double *calib_q, const double *cali
 // next ovph_run_msckf_update: StateOptions::gpu_general_features
 static int g_general = 0;
 extern "C" void ovph_set_general_features(int on) { g_general = on != 0; }
+// next ovph_run_msckf_update: StateOptions::gpu_general_planes
+static int g_general_planes = 0;
+extern "C" void ovph_set_general_planes(int on) { g_general_planes = on != 0; }
 // next ovph_run_updater: StateOptions::gpu_general_slam
 static int g_general_slam = 0;
 extern "C" void ovph_set_general_slam(int on) { g_general_slam = on != 0; }
@@ -107,6 +110,8 @@ extern "C" int ovph_run_msckf_update(int C, const double *clone_q, const double 
   so.gpu_device = g_device;
   so.gpu_general_features = g_general != 0;
   g_general = 0;
+  so.gpu_general_planes = g_general_planes != 0;
+  g_general_planes = 0;
   if (g_cam1_q) so.num_cameras = 2;
   auto state = std::make_shared<State>(so);
   state->_cam_fisheye[0] = g_fisheye != 0;

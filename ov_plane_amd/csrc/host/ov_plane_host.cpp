@@ -1063,15 +1063,31 @@ void UpdaterMSCKF::update(std::shared_ptr<State> state, std::vector<std::shared_
           for (int a = 0; a < 3; ++a) cpv[3 * k + a] = cpfej[3 * k + a] = plane_estimates.at(pid)[a];
         }
       }
+      std::vector<size_t> gen_idx;  // on-plane features for the loop's general batch (gpu_general_planes) and their plane slots
+      std::vector<int> gen_plane;
+      bool gen_fits = true;
       for (size_t f = 0; f < feature_vec.size(); ++f) {
         auto it = feat2plane.find(feature_vec[f]->featid);
         if (it == feat2plane.end()) continue;
         if (fitted_planes.count(it->second) && !plane_feat_kept.count(feature_vec[f]->featid)) continue;  // not an inlier of the fit
         // the plane kernels take a feature's 2 m bearing rows in one wavefront (the constraint row is wave-uniform): a track with
         // more than 32 observations keeps its bearing measurements but not the plane constraint (it goes through the point loop)
-        if (feature_vec[f]->timestamps.size() > 32 || !feature_vec[f]->only_camera0()) continue;
+        // StateOptions::gpu_general_planes: such a feature keeps its constraint through the general batch of the loop, unless its
+        // plane was fitted in this frame (the fit / refinement kernels never saw it)
         auto pos = std::find(used_planes.begin(), used_planes.end(), it->second);
+        if (feature_vec[f]->timestamps.size() > 32 || !feature_vec[f]->only_camera0()) {
+          if (pos != used_planes.end() && !fitted_planes.count(it->second)) {
+            gen_idx.push_back(f);
+            gen_plane.push_back(1 + (int)(pos - used_planes.begin()));
+            gen_fits = gen_fits && (int)feature_vec[f]->timestamps.size() <= OVP_GEN_MAX_MEAS;
+          }
+          continue;
+        }
         if (pos != used_planes.end()) pof[f] = 1 + (int)(pos - used_planes.begin());
+      }
+      if (!state->_options.gpu_general_planes || !gen_fits) {  // (a track above OVP_GEN_MAX_MEAS: the frame keeps the previous route)
+        gen_idx.clear();
+        gen_plane.clear();
       }
       upload_batch(feature_vec);
       const int n = ovp_cov_size(state->_gpu);
@@ -1112,7 +1128,20 @@ void UpdaterMSCKF::update(std::shared_ptr<State> state, std::vector<std::shared_
       pb.slam_p_fej = s_pf.data();
       std::vector<int> pdof(NP, 0);
       {
-        const int rcp = ovp_msckf_plane_update(state->_gpu, &o, &pb, dxp.data(), pok.data(), nullptr, pdof.data(), fused.data());
+        std::vector<uint8_t> gused(gen_idx.size() + 1, 0);
+        int rcp;
+        if (!gen_idx.empty()) {
+          upload_cameras();
+          GeneralBatch g;
+          general_batch(gen_idx, g);
+          rcp = ovp_msckf_plane_update_general(state->_gpu, &o, &pb, &g.b, gen_plane.data(), dxp.data(), pok.data(), nullptr, pdof.data(),
+                                               fused.data(), gused.data());
+          if (rcp == 0)  // consumed by an accepted plane: flagged below with the batch's, not offered to the point update
+            for (size_t i = 0; i < gen_idx.size(); ++i)
+              if (gused[i]) fused[gen_idx[i]] = 1;
+        } else {
+          rcp = ovp_msckf_plane_update(state->_gpu, &o, &pb, dxp.data(), pok.data(), nullptr, pdof.data(), fused.data());
+        }
         if (rcp == OVP_E_CAPACITY) {
           // the planes of this frame involve more than 287 columns (clones + calibration + in-state planes + landmarks on the
           // others; the state itself may be larger): the regularities are not used in this update, every feature takes the

@@ -75,6 +75,11 @@ struct StateOptions {
   // instead of ending it - off: the first such candidate and everything behind it take the per-candidate host loop.
   // OVP_E_CAPACITY falls back to that loop.  Not in the reference.
   bool gpu_dinit_planes = false;
+  // UpdaterMSCKF::update: on-plane features the device batch cannot carry (another camera, more than OVP_MAX_MEAS views) stay in the
+  // plane loop through ovp_msckf_plane_update_general instead of going to the point update without their plane constraint - for
+  // planes whose estimate does not come from this frame's fit (in the state, or handed over in _plane_estimates_cp_inG); a frame with
+  // an on-plane track above OVP_GEN_MAX_MEAS keeps the previous behaviour.  Not in the reference.
+  bool gpu_general_planes = false;
 };
 
 // update/UpdaterOptions.h:37-53

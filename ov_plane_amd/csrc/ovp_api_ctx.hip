@@ -187,7 +187,8 @@ extern "C" int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int
   if (c->n_split > 64) c->n_split = 64;
   {
     const int nt = c->ldg / 16;
-    HIPCHK(dalloc(&c->part, (size_t)c->n_split * (nt * (nt + 1) / 2) * 256));
+    // (one split more than k_gram_pair fills: the general on-plane features of a plane add theirs, k_plane_feat_gen.hip)
+    HIPCHK(dalloc(&c->part, (size_t)(c->n_split + 1) * (nt * (nt + 1) / 2) * 256));
   }
   HIPCHK(dalloc(&c->idbuf, (size_t)4 * c->n_max + 64));
   c->small_cap = (size_t)4 * c->n_max * 64 + (size_t)c->n_max * c->n_max;
@@ -225,7 +226,7 @@ extern "C" int ovp_ctx_destroy(ovp_ctx* c) {
                  c->bcc, c->resd, c->pl_slam_i, c->pl_slam_d, c->sub_ids, c->sub_buf, c->pl_Tbuf, c->pl_crow, c->pl_dxlast,
                  c->pl_cur, c->pl_perm, c->pl_range_done, c->pl_used, c->pl_dstage, c->pl_xbuf, c->pl_xy, c->pl_xflag, c->pl_Asum,
                  c->pl_U, c->pl_sub_tab, c->Lkeep, c->slam_res, c->slam_hscr, c->dinit_buf, c->boost, c->boost_vec,
-                 c->gen_cal, c->gen_buf};
+                 c->gen_cal, c->gen_buf, c->pl_gen_dev};
   for (void* p : dev)
     if (p) hipFree(p);
   if (c->h_res_block) hipHostFree(c->h_res_block);

@@ -23,11 +23,12 @@ extern "C" int ovp_cameras_upload(ovp_ctx* c, int n_cams, const ovp_camera_table
 }
 
 // argument checks of a general batch against the context's tables (host only, nothing enqueued)
-static int check_general_batch(const ovp_ctx* c, const ovp_general_batch* b, bool need_p) {
+int check_general_batch(const ovp_ctx* c, const ovp_general_batch* b, bool need_p, const int* only) {
   if (!b || b->n_feats < 0) return OVP_E_ARG;
   if (b->n_feats == 0) return 0;
   if (b->max_meas < 1 || !b->uv || !b->clone_idx || !b->cam_idx || !b->n_meas || (need_p && !b->p_FinG)) return OVP_E_ARG;
   for (int f = 0; f < b->n_feats; ++f) {
+    if (only && !only[f]) continue;
     const int m = b->n_meas[f];
     if (m > OVP_GEN_MAX_MEAS) return OVP_E_CAPACITY;
     if (m < 0 || m > b->max_meas) return OVP_E_ARG;

@@ -1,5 +1,7 @@
 // C-ABI shim, part 4 (see ovp_ctx.h): the per-plane loop of UpdaterMSCKF::update (update/UpdaterMSCKF.cpp:411-649,
-// update/UpdaterPlane.cpp:296-552) and UpdaterPlane::init_vio_plane.
+// update/UpdaterPlane.cpp:296-552) and UpdaterPlane::init_vio_plane.  ovp_msckf_plane_update_general: the same loop with the on-plane
+// features of a general batch (any camera, tracks of up to OVP_GEN_MAX_MEAS views) stacked behind the batch's, as
+// update/UpdaterHelper.cpp:335-344 and :448-512 stack them whatever camera saw them and however long the track is.
 #include "ovp_ctx.h"
 
 // device sequence shared by the plane update and the plane initialisation: feature kernel, Gram reduction, reduction to the
@@ -74,7 +76,7 @@ static int plane_buffers(ovp_ctx* c, int NP) {
     if (!c->pl_E) {
       const size_t ne = (size_t)(c->n_max + 4) * c->ldg;
       HIPCHK(dalloc(&c->pl_featlist, (size_t)c->f_max));
-      HIPCHK(dalloc(&c->pl_cst, (size_t)c->f_max * 10));
+      HIPCHK(dalloc(&c->pl_cst, ((size_t)c->f_max + 1) * 10));  // (+ the record of a plane's general features)
       HIPCHK(dalloc(&c->pl_cstsum, 16));
       HIPCHK(dalloc(&c->pl_E, ne));
       HIPCHK(dalloc(&c->pl_An, (size_t)(c->n_max + 1) * ld));
@@ -90,7 +92,15 @@ static int plane_buffers(ovp_ctx* c, int NP) {
 // ---- UpdaterMSCKF::update, per-plane loop (second generation) ------------------------------------------------------------
 // See k_plane2.hip for the algebra.  Everything of a call is enqueued without a host synchronisation: the per-call tables go
 // through one pinned staging block, the results come back through one pinned block read after a single stream sync.
-struct PlaneJobH { int pl, start, nf, rows_total, rows_live, rows_u, n_involved, in_state, sid, n_inv_cols, ns_pl; double thr; };
+struct PlaneJobH { int pl, start, nf, rows_total, rows_live, rows_u, n_involved, in_state, sid, n_inv_cols, ns_pl; double thr;
+                   int g_start, ng; /* general features: range in the list of the call */ };
+
+// column of calibration column k of camera `cam` (ovp_cameras_upload) in the running loop's column order
+static inline int gen_cam_col(const ovp_ctx* c, int cam, int k) {
+  const int id = k < 6 ? c->gen_calib_id[cam] + k : c->gen_intr_id[cam] + (k - 6);
+  if (c->pl_gen_pos.empty()) return id;
+  return (id >= 0 && id < (int)c->pl_gen_pos.size()) ? c->pl_gen_pos[id] : -1;
+}
 
 extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, double* dx_planes,
                                       uint8_t* plane_ok, double* plane_chi2, int* plane_dof, uint8_t* feat_used);
@@ -337,6 +347,11 @@ static int plane_update_ordered(ovp_ctx* c, const ovp_update_opts* o, const ovp_
   for (int i = 0; i < C; ++i) place(c->h_clone_id[i], 6);
   if (o->do_calib_camera_pose) place(c->calib_id, 6);
   if (o->do_calib_camera_intrinsics) place(c->intr_id, 8);
+  if (c->pl_gen_b)  // general on-plane features: their cameras' calibration columns are involved, and every accepted plane corrects
+    for (int k = 0; k < c->gen_ncams; ++k) {  // the table of every uploaded camera (k_plane_gen_commit) - all of them take part
+      if (o->do_calib_camera_pose) place(c->gen_calib_id[k], 6);
+      if (o->do_calib_camera_intrinsics) place(c->gen_intr_id[k], 8);
+    }
   for (int q = 0; q < n_slam; ++q)
     if (pb->slam_plane[q] < 1 || pb->slam_plane[q] > NP || pb->slam_state_id[q] < 0 || pb->slam_state_id[q] + 3 > n) return OVP_E_ARG;
   c->pl_nl.assign((size_t)(NP > 0 ? NP : 1), 0);
@@ -416,7 +431,9 @@ static int plane_update_ordered(ovp_ctx* c, const ovp_update_opts* o, const ovp_
   c->pl_scatter_dst = full ? sv.P : nullptr;  // full order: the loop's covariance product is un-permuted straight into the resident P
   c->pl_scatter_ids = d_inv;
   c->pl_t_entry = t_entry;
+  if (c->pl_gen_b) c->pl_gen_pos = pos;
   const int rc = ovp_msckf_plane_update(c, o, &pbs, dx_sub.data(), plane_ok, plane_chi2, plane_dof, feat_used);
+  c->pl_gen_pos.clear();
   c->pl_sub_active = false;
   c->pl_sub_rest = false;
   c->pl_scatter_dst = nullptr;
@@ -529,6 +546,8 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
   }
   // (a cheap look at the batch first: when no plane can qualify - update/UpdaterMSCKF.cpp:316-317, 384-396 - nothing below needs the
   // factor, and a singular prior must not fail a call that has nothing to update)
+  const ovp_general_batch* gbp = c->pl_gen_b;  // general on-plane features (ovp_msckf_plane_update_general), nullptr = none
+  const int GF = gbp ? gbp->n_feats : 0, GM = gbp ? gbp->max_meas : 0;
   bool any_candidate = false;
   {
     std::vector<int> cnt((size_t)NP + 1, 0);
@@ -537,6 +556,8 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
       if (pf >= 1 && pf <= NP && c->h_n_meas[f] >= 2) ++cnt[pf];
     }
     for (int q = 0; q < n_slam; ++q) ++cnt[pb->slam_plane[q]];
+    for (int g = 0; g < GF; ++g)
+      if (c->pl_gen_plane[g] >= 1 && c->pl_gen_plane[g] <= NP && gbp->n_meas[g] >= 2) ++cnt[c->pl_gen_plane[g]];
     for (int pl = 1; pl <= NP && !any_candidate; ++pl)
       any_candidate = cnt[pl] >= (pb->plane_state_id[pl - 1] >= 0 ? 1 : 4);
   }
@@ -601,6 +622,17 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
       if (pf >= 1 && pf <= NP) bucket[fill[pf]++] = f;
     }
   }
+  // the general features by plane, batch order kept
+  std::vector<int> glist, gbucket((size_t)NP + 2, 0), gsorted((size_t)(GF > 0 ? GF : 1));
+  for (int g = 0; g < GF; ++g)
+    if (c->pl_gen_plane[g] >= 1 && c->pl_gen_plane[g] <= NP && gbp->n_meas[g] >= 2) ++gbucket[c->pl_gen_plane[g] + 1];
+  for (int pl = 1; pl <= NP + 1; ++pl) gbucket[pl] += gbucket[pl - 1];
+  {
+    std::vector<int> fill(gbucket.begin(), gbucket.end());
+    for (int g = 0; g < GF; ++g)
+      if (c->pl_gen_plane[g] >= 1 && c->pl_gen_plane[g] <= NP && gbp->n_meas[g] >= 2) gsorted[fill[c->pl_gen_plane[g]]++] = g;
+  }
+  int ng_max = 0;
   for (int pl = 0; pl < NP; ++pl) {
     PlaneJobH j;
     j.pl = pl;
@@ -622,19 +654,36 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
       j.rows_live += 2 * m - 2;  // the m identical constraint rows are one direction (k_chol2 gate)
       for (int k = 0; k < m; ++k) seen |= 1ull << c->h_clone_idx[(size_t)f * M + k];
     }
+    // general features on this plane: same rows per feature, any clone, any camera (its calibration columns are involved)
+    j.g_start = (int)glist.size();
+    j.ng = 0;
+    unsigned cams_seen = j.nf > 0 ? 1u : 0u;  // (the batch's features are camera 0's)
+    for (int gi = gbucket[pl + 1]; gi < gbucket[pl + 2]; ++gi) {
+      const int g = gsorted[gi], m = gbp->n_meas[g];
+      glist.push_back(g);
+      j.ng++;
+      j.rows_total += 3 * m - 3;
+      j.rows_live += 2 * m - 2;
+      for (int k = 0; k < m; ++k) {
+        seen |= 1ull << gbp->clone_idx[(size_t)g * GM + k];
+        cams_seen |= 1u << gbp->cam_idx[(size_t)g * GM + k];
+      }
+    }
+    const int ncal_pl = j.ng > 0 ? ncal * __builtin_popcount(cams_seen) : ncal;
     int ns_pl = 0;  // SLAM landmarks on this (out-of-state) plane: one row and three involved columns each
     if (!j.in_state)
       for (int q = 0; q < n_slam; ++q)
         if (pb->slam_plane[q] == pl + 1) ++ns_pl;
     if (ns_pl > PA_MAXQ) return bail(OVP_E_CAPACITY);
     j.ns_pl = ns_pl;
-    if (j.nf == 0 || (!j.in_state && j.nf + ns_pl < 4)) {  // update/UpdaterMSCKF.cpp:316-317,384-396
+    if (j.nf + j.ng == 0 || (!j.in_state && j.nf + j.ng + ns_pl < 4)) {  // update/UpdaterMSCKF.cpp:316-317,384-396
       featlist.resize(j.start);
+      glist.resize(j.g_start);
       continue;
     }
     j.rows_total += ns_pl;
     j.rows_live += ns_pl;
-    const int c_ref = 6 * __builtin_popcountll(seen) + ncal + 3 * ns_pl;
+    const int c_ref = 6 * __builtin_popcountll(seen) + ncal_pl + 3 * ns_pl;
     const int rows_c = j.rows_total > c_ref ? c_ref : j.rows_total;  // UpdaterPlane::measurement_compress_inplace
     j.rows_u = j.in_state ? rows_c : rows_c - 3;
     j.n_involved = c_ref + (j.in_state ? 3 : 0);
@@ -642,8 +691,10 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
     if (!j.in_state) j.rows_live -= 3;
     if (j.rows_u < 1) {
       featlist.resize(j.start);
+      glist.resize(j.g_start);
       continue;
     }
+    if (j.ng > ng_max) ng_max = j.ng;
     j.thr = o->chi2_multiplier * ovp_chi2_quantile_095(j.rows_u);
     // order of the involved columns in the normalised Gram: everything that is not a clone first, the clones last (a rank
     // deficiency - gauge freedom, planar scene - then shows up in the trailing pivots, k_chol2 mode 2)
@@ -651,10 +702,22 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
       std::vector<int> perm(n, -1);
       int pos = 0;
       std::vector<char> inv(n, 0);
-      if (o->do_calib_camera_pose)
+      // (camera 0's columns: the batch's features are its, and so is every plane without general features as before; a plane whose
+      // general features are all another camera's does not involve them - c_ref above counts the same cameras)
+      const bool cam0 = j.ng == 0 || (cams_seen & 1u);
+      if (o->do_calib_camera_pose && cam0)
         for (int k = 0; k < 6; ++k) inv[c->calib_id + k] = 1;
-      if (o->do_calib_camera_intrinsics)
+      if (o->do_calib_camera_intrinsics && cam0)
         for (int k = 0; k < 8; ++k) inv[c->intr_id + k] = 1;
+      if (j.ng > 0)  // the cameras of this plane's general features
+        for (int cam = 0; cam < c->gen_ncams; ++cam)
+          if ((cams_seen >> cam) & 1u)
+            for (int k = 0; k < 14; ++k) {
+              if (!(k < 6 ? o->do_calib_camera_pose : o->do_calib_camera_intrinsics)) continue;
+              const int col = gen_cam_col(c, cam, k);
+              if (col < 0 || col >= n) return bail(OVP_E_ARG);
+              inv[col] = 1;
+            }
       if (j.in_state)
         for (int k = 0; k < 3; ++k) inv[j.sid + k] = 1;
       if (!j.in_state)
@@ -722,6 +785,69 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
   double* d_cpfej = dd + 3 * NP;
   double* d_slam_p = dd + 6 * NP;
   double* d_slam_pfej = dd + 6 * NP + 3 * n_slam;
+  // ---- general features: the batch and the per-plane lists, the marks and the staged rows ----
+  ovp::PlaneGenParams gp0;
+  ovp::PlaneGenCols gcols;
+  memset(&gp0, 0, sizeof(gp0));
+  memset(&gcols, 0xff, sizeof(gcols));
+  const unsigned gen_calmask = (o->do_calib_camera_pose ? 0x3Fu : 0u) | (o->do_calib_camera_intrinsics ? (0xFFu << 6) : 0u);
+  if (gbp) {
+    for (int cam = 0; cam < c->gen_ncams; ++cam)
+      for (int k = 0; k < 14; ++k)
+        if ((gen_calmask >> k) & 1u) {
+          gcols.col[cam][k] = gen_cam_col(c, cam, k);
+          if (gcols.col[cam][k] < 0 || gcols.col[cam][k] >= n) return bail(OVP_E_ARG);
+        }
+  }
+  if (gbp && !glist.empty()) {
+    auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
+    const size_t GFM = (size_t)GF * GM;
+    const size_t o_uv = 0, o_ci = al(sizeof(float) * 2 * GFM), o_cam = al(o_ci + sizeof(int) * GFM), o_nm = al(o_cam + sizeof(int) * GFM),
+                 o_p = al(o_nm + sizeof(int) * GF), o_list = al(o_p + sizeof(double) * 3 * GF), in_bytes = al(o_list + sizeof(int) * glist.size());
+    const size_t mark_stride = (size_t)((n + 4 + 15) & ~15), hp_stride = (size_t)ovp::PG_ROWS * (n + 4);
+    // inputs through the pinned arena (nobody else uses it while a plane loop is enqueued; the previous user has waited for its
+    // copy), marks and staged rows in a device block of their own: no host synchronisation unless a block has to grow
+    const size_t o_hp = al(sizeof(int) * mark_stride * ng_max), total = o_hp + sizeof(double) * hp_stride * ng_max;
+    if (total > c->pl_gen_cap) {
+      HIPCHK(hipStreamSynchronize(s));
+      if (c->pl_gen_dev) HIPCHK(hipFree(c->pl_gen_dev));
+      c->pl_gen_dev = nullptr;
+      c->pl_gen_cap = 0;
+      HIPCHK(hipMalloc(&c->pl_gen_dev, total + total / 2));
+      c->pl_gen_cap = total + total / 2;
+    }
+    void *ah = nullptr, *ad = nullptr;
+    {
+      const int rca = ovp_io_arena(c, in_bytes, &ah, &ad);
+      if (rca) return bail(rca);
+    }
+    char* h = (char*)ah;
+    memcpy(h + o_uv, gbp->uv, sizeof(float) * 2 * GFM);
+    memcpy(h + o_ci, gbp->clone_idx, sizeof(int) * GFM);
+    memcpy(h + o_cam, gbp->cam_idx, sizeof(int) * GFM);
+    memcpy(h + o_nm, gbp->n_meas, sizeof(int) * GF);
+    memcpy(h + o_p, gbp->p_FinG, sizeof(double) * 3 * GF);
+    memcpy(h + o_list, glist.data(), sizeof(int) * glist.size());
+    HIPCHK(hipMemcpyAsync(ad, ah, in_bytes, hipMemcpyHostToDevice, s));
+    char* d = (char*)ad;
+    char* ds = (char*)c->pl_gen_dev;
+    gp0.fp = fp;
+    gp0.fp.calmask = gen_calmask;
+    gp0.cam_cal = c->gen_cal;
+    for (int k = 0; k < OVP_MAX_CAMERAS; ++k) gp0.cam_fisheye[k] = c->gen_fisheye[k];
+    gp0.cc = gcols;
+    gp0.uv = (const float*)(d + o_uv);
+    gp0.clone_idx = (const int*)(d + o_ci);
+    gp0.cam_idx = (const int*)(d + o_cam);
+    gp0.n_meas = (const int*)(d + o_nm);
+    gp0.p_FinG = (const double*)(d + o_p);
+    gp0.max_meas = GM;
+    gp0.list = (const int*)(d + o_list);
+    gp0.mark = (int*)ds;
+    gp0.mark_stride = (int)mark_stride;
+    gp0.hp = (double*)(ds + o_hp);
+    gp0.hp_stride = hp_stride;
+  }
   const double white_c = 1.0 / o->sigma_constraint;
   // weight of the expected energy of the rounding-decided rows in the gate statistic (k_chol2.hip); OVP_PL_NOISE_SCALE overrides the
   // calibrated constant for the study that produced it (tools/plane_gate_agreement.py --fit)
@@ -745,12 +871,37 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
     ovp::FeatParams fpl = fp;
     fpl.n = nk;
     fpl.P = c->P;
-    HIPCHK(ovp_launch_plane_feat(&fpl, &pp, j.nf, s));
-    // (2) Gram products
-    const int chunks = (2 * j.nf + c->rows_per_chunk - 1) / c->rows_per_chunk;
+    int chunks = (2 * j.nf + c->rows_per_chunk - 1) / c->rows_per_chunk;
     int nsplit = 1;
-    HIPCHK(ovp_launch_gram_pair(c->rec, fp.n_clones, j.nf, c->rows_per_chunk, chunks, c->gramS, c->G, 3 * j.nf, c->ldg, nk + 4,
-                                c->n_split, c->part, &nsplit, s));
+    if (j.nf > 0) {
+      HIPCHK(ovp_launch_plane_feat(&fpl, &pp, j.nf, s));
+      // (2) Gram products
+      HIPCHK(ovp_launch_gram_pair(c->rec, fp.n_clones, j.nf, c->rows_per_chunk, chunks, c->gramS, c->G, 3 * j.nf, c->ldg, nk + 4,
+                                  c->n_split, c->part, &nsplit, s));
+    } else {  // a plane with general features only: an empty structured Gram (one chunk of zeros per clone), no G^T G split
+      chunks = 1;
+      nsplit = 0;
+      HIPCHK(hipMemsetAsync(c->gramS, 0, sizeof(double) * (size_t)fp.n_clones * OVP_GRAM_ELEMS, s));
+    }
+    // (2b) the plane's general features: one more split of the partials and one more moment record (k_plane_feat_gen.hip); a plane
+    // without any enqueues nothing here
+    const int nt16_pl = (nk + 4 + 15) / 16, ntile_pl = nt16_pl * (nt16_pl + 1) / 2;
+    if (j.ng > 0) {
+      ovp::PlaneGenParams g = gp0;
+      g.list = gp0.list + j.g_start;
+      g.n_local = j.ng;
+      g.plane = j.pl;
+      g.in_state = j.in_state;
+      g.plane_sid = j.sid;
+      g.white_c = white_c;
+      g.cp = d_cp;
+      g.cp_fej = d_cpfej;
+      g.n = nk;
+      g.hp_stride = (size_t)ovp::PG_ROWS * (nk + 4);
+      g.part_split = c->part + (size_t)nsplit * ntile_pl * 256;
+      g.cst_rec = c->pl_cst + (size_t)j.nf * 10;
+      HIPCHK(ovp_launch_plane_feat_gen(&g, s));
+    }
     // (3) pair on the state columns, normalised Gram, residual energy
     ovp::PlaneAsm pa;
     memset(&pa, 0, sizeof(pa));
@@ -758,17 +909,14 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
     pa.n_clones = fp.n_clones;
     pa.n_chunks = chunks;
     pa.part = c->part;
-    pa.n_split = nsplit;
-    {
-      const int nt16 = (nk + 4 + 15) / 16;
-      pa.ntile = nt16 * (nt16 + 1) / 2;
-    }
+    pa.n_split = nsplit + (j.ng > 0 ? 1 : 0);
+    pa.ntile = ntile_pl;
     pa.colmap = c->colmap;
     pa.n = nk;
     pa.plane_sid = j.sid;
     pa.in_state = j.in_state;
     pa.cst = c->pl_cst;
-    pa.nf = j.nf;
+    pa.nf = j.nf + (j.ng > 0 ? 1 : 0);
     pa.n_slam = j.in_state ? 0 : n_slam;
     pa.plane1 = j.pl + 1;
     pa.slam_plane = d_spl;
@@ -899,6 +1047,9 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
     }
     HIPCHK(ovp_launch_chol2(&j0, &j1, &ps, s));
     if (c->pl_ktimer == 1) HIPCHK(hipEventRecord(c->pl_ev[2 * jn + 1], s));
+    if (gbp)  // an accepted plane also corrects the tables of ovp_cameras_upload, which the general rows of the planes behind it read
+      HIPCHK(ovp_launch_plane_gen_commit(c->pl_res + 4 * j.pl, c->pl_dx + (size_t)j.pl * n, c->gen_cal, c->gen_ncams, &gcols,
+                                         gen_calmask, s));
     if (c->pl_sub_rest)
       HIPCHK(ovp_launch_plane_sub_accum(c->pl_res + 4 * j.pl, c->Ab, c->pl_Asum, c->pl_dx + (size_t)j.pl * n,
                                         c->pl_U + (size_t)j.pl * ld, nk, ld, s));
@@ -1034,6 +1185,12 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
   c->h_pl_used.assign(hused, hused + F);
   if (dx_planes) memcpy(dx_planes, hdx, sizeof(double) * (size_t)n * NP);
   if (feat_used && F) memcpy(feat_used, hused, (size_t)F);
+  if (gbp) {  // the general features an accepted plane consumed (the host knows each plane's list)
+    c->pl_gen_used.assign((size_t)GF, 0);
+    for (const PlaneJobH& j : jobs)
+      if (hres[4 * j.pl + 1] > 0.5)
+        for (int k = 0; k < j.ng; ++k) c->pl_gen_used[glist[j.g_start + k]] = 1;
+  }
   for (const PlaneJobH& j : jobs) {
     if (plane_ok) plane_ok[j.pl] = hres[4 * j.pl + 1] > 0.5 ? 1 : 0;
     if (plane_chi2) plane_chi2[j.pl] = hres[4 * j.pl];
@@ -1061,6 +1218,41 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
   if (bad) return OVP_E_NOTSPD;
   c->have_factor = factor_enqueued;
   return 0;
+}
+
+// ---- the plane loop with the on-plane features of a general batch behind the batch's (update/UpdaterHelper.cpp:335-344 over every
+// camera, :448-512 the point-on-plane rows; update/UpdaterMSCKF.cpp:411-649 the loop) ----
+extern "C" int ovp_msckf_plane_update_general(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, const ovp_general_batch* gb,
+                                              const int* plane_of_gen, double* dx_planes, uint8_t* plane_ok, double* plane_chi2,
+                                              int* plane_dof, uint8_t* feat_used, uint8_t* gen_used) {
+  if (!c || !o || !pb || !gb || pb->n_planes < 0 || gb->n_feats < 0) return OVP_E_ARG;
+  const int GF = gb->n_feats, NP = pb->n_planes;
+  if (GF > 0 && (!plane_of_gen || !gb->n_meas)) return OVP_E_ARG;
+  bool any = false;
+  for (int g = 0; g < GF; ++g) {
+    if (plane_of_gen[g] < 0 || plane_of_gen[g] > NP) return OVP_E_ARG;
+    any |= plane_of_gen[g] > 0;
+  }
+  if (any) {  // everything that can refuse the general features is looked at before anything is enqueued
+    if (!c->have_state || !c->have_cov || c->gen_ncams < 1) return OVP_E_STATE;
+    const int rc = check_general_batch(c, gb, true, plane_of_gen);
+    if (rc) return rc;
+    for (int k = 0; k < c->gen_ncams; ++k) {  // calibration columns of every camera the options estimate
+      if (o->do_calib_camera_pose && (c->gen_calib_id[k] < 0 || c->gen_calib_id[k] + 6 > c->n)) return OVP_E_ARG;
+      if (o->do_calib_camera_intrinsics && (c->gen_intr_id[k] < 0 || c->gen_intr_id[k] + 8 > c->n)) return OVP_E_ARG;
+    }
+  }
+  if (gen_used && GF > 0) memset(gen_used, 0, (size_t)GF);
+  if (!any) return ovp_msckf_plane_update(c, o, pb, dx_planes, plane_ok, plane_chi2, plane_dof, feat_used);
+  c->pl_gen_b = gb;
+  c->pl_gen_plane = plane_of_gen;
+  c->pl_gen_used.assign((size_t)GF, 0);
+  const int rc = ovp_msckf_plane_update(c, o, pb, dx_planes, plane_ok, plane_chi2, plane_dof, feat_used);
+  c->pl_gen_b = nullptr;
+  c->pl_gen_plane = nullptr;
+  c->pl_gen_pos.clear();
+  if (!rc && gen_used) memcpy(gen_used, c->pl_gen_used.data(), (size_t)GF);
+  return rc;
 }
 
 // ---- UpdaterPlane::init_vio_plane core ----------------------------------------------------------

@@ -26,6 +26,7 @@
 #include "k_plane2.h"
 #include "k_slam.h"
 #include "k_dinit.h"
+#include "k_plane_gen.h"
 
 extern "C" int ovp_dbg_tilechol_skip;
 extern "C" {
@@ -235,6 +236,13 @@ struct ovp_ctx {
   const int* pl_scatter_ids = nullptr;
   double pl_t_entry = 0.0;
   bool pl_psd = false;
+  // general on-plane features of the running ovp_msckf_plane_update_general (k_plane_feat_gen.hip); pl_gen_b == nullptr: none
+  const ovp_general_batch* pl_gen_b = nullptr;
+  const int* pl_gen_plane = nullptr;       // [n_feats of the general batch] 1-based plane slot, 0 = not on a plane
+  std::vector<int> pl_gen_pos;             // state column -> column in the loop's order (plane_update_ordered); empty = identity
+  std::vector<unsigned char> pl_gen_used;  // [n_feats of the general batch] consumed by an accepted plane
+  void* pl_gen_dev = nullptr;              // device: [marks | projected rows] of one plane's general features
+  size_t pl_gen_cap = 0;
   // A factor of the RESIDENT covariance left behind by the plane loop (P = V^T V, Lkeep = V^T in the state's column order): the point
   // update that follows needs some M with M M^T = P, not the Cholesky factor - chol(P) (the longer branch of the fused feature
   // launch at N = 240) is skipped.  Cleared by everything that writes P.
@@ -326,6 +334,9 @@ void quat_2_rot(const double q[4], double R[9]);  // JPL quaternion -> row-major
 extern "C" int ovp_io_arena(ovp_ctx* c, size_t bytes, void** host, void** dev);  // pinned staging arena (ovp_api_ctx.hip)
 // ovp_api_point.hip
 int fill_feat_params(ovp_ctx* c, const ovp_update_opts* o);
+// ovp_api_general.hip: argument checks of a general batch against the context's tables (host only); only != nullptr: features with
+// only[f] == 0 are not looked at
+int check_general_batch(const ovp_ctx* c, const ovp_general_batch* b, bool need_p, const int* only = nullptr);
 int ovp_fetch_to_hres(ovp_ctx* c, const void* dsrc, size_t bytes, hipStream_t s);  // device block -> c->pl_hres, waited for (ovp_api_plane.hip)
 int chol_of_P(ovp_ctx* c, hipStream_t s);
 hipError_t chol_of_T(ovp_ctx* c, const double* T, int n, int ld, int add_identity, const int* cond, hipStream_t s);

@@ -22,7 +22,8 @@ def lib():
     return _LIB
 
 
-def run_msckf_update(sc, triangulate=False, fit_planes=None, comm=None, rank=0, world=1, device=0, general_features=False):
+def run_msckf_update(sc, triangulate=False, fit_planes=None, comm=None, rank=0, world=1, device=0, general_features=False,
+                     general_planes=False):
     """Drives ov_plane::UpdaterMSCKF::update (C++ host classes over the C-ABI) on a synth.Scene.
     triangulate=True: the features carry uvs_norm and no position; the updater triangulates them first.
     fit_planes=dict(min_feat, max_cond, variant): no plane estimates are handed over - the updater fits the planes that are
@@ -30,9 +31,12 @@ def run_msckf_update(sc, triangulate=False, fit_planes=None, comm=None, rank=0, 
     comm / rank / world / device: UpdaterMSCKF::set_communicator + StateOptions::gpu_device - the point loop goes through
     ovp_msckf_update_sharded on this rank's share (out["shard"] = its index range of the point batch).
     general_features: StateOptions::gpu_general_features - the features the device batch cannot carry (another camera, a track
-    longer than OVP_MAX_MEAS) are triangulated and gated on the device (ovp_triangulate_general / ovp_msckf_general_features)."""
+    longer than OVP_MAX_MEAS) are triangulated and gated on the device (ovp_triangulate_general / ovp_msckf_general_features).
+    general_planes: StateOptions::gpu_general_planes - on-plane features of that kind stay in the plane loop
+    (ovp_msckf_plane_update_general) instead of going to the point update without their plane constraint."""
     L = lib()
     L.ovph_set_general_features(1 if general_features else 0)
+    L.ovph_set_general_planes(1 if general_planes else 0)
     cam1 = sc.get("cam1", None)  # synth.make_stereo_scene: dict(calib_q, calib_p, intr), sc.cam_idx [F, M]
     if cam1 is not None:
         c1q, c1p, c1i = (np.ascontiguousarray(cam1[k], dtype=np.float64) for k in ("calib_q", "calib_p", "intr"))

@@ -616,6 +616,23 @@ def make_stereo_scene(C=8, F=60, seed=0, stereo_frac=0.5, baseline=0.11, **kw):
     return sc
 
 
+def make_long_plane_scene(C=40, n_planes=4, feats_per_plane=8, n_free=8, seed=0, min_meas=20, **kw):
+    """Plane scene with long tracks: at least 40 clones, ragged tracks of min_meas .. C views, so that the on-plane features lie on
+    both sides of the device batch's limit of 32 views (the reference stacks an on-plane feature whatever the length of its track,
+    update/UpdaterHelper.cpp:448-512).  Camera 0 only; make_scene's keys.  The caller asserts that both kinds are present."""
+    assert C >= 40
+    return make_scene(C=C, F=n_free + n_planes * feats_per_plane, seed=seed, ragged=True, min_meas=min_meas, n_planes=n_planes,
+                      feats_per_plane=feats_per_plane, **kw)
+
+
+def make_stereo_plane_scene(C=8, n_planes=2, feats_per_plane=10, n_free=4, seed=0, stereo_frac=0.7, **kw):
+    """Plane scene with a second camera (make_stereo_scene's keys): the first round(stereo_frac * F) features - the free points
+    and the on-plane features in front - are also observed by camera 1, so some on-plane features carry camera 1's rows and its
+    14 calibration columns (update/UpdaterHelper.cpp:335-344) and the others are camera 0's."""
+    return make_stereo_scene(C=C, F=n_free + n_planes * feats_per_plane, seed=seed, stereo_frac=stereo_frac, n_planes=n_planes,
+                             feats_per_plane=feats_per_plane, **kw)
+
+
 def make_slam_scene(C=11, n_slam=12, seed=0, n_planes=0, ragged=True, outliers=0, wrong_plane=0, **kw):
     """Scene whose F = n_slam features are new observations of SLAM landmarks that are already in the state.
 

@@ -1,0 +1,190 @@
+"""TEST INFRASTRUCTURE ONLY - sequential numpy reference of the plane loop (update/UpdaterMSCKF.cpp:411-649) over on-plane
+features of ANY camera and ANY track length, one EKF update per plane, built from the pieces of oracle/np_ref.py:
+feature_jacobian_full (with its cp / plane_state_id arguments), nullspace_project_inplace, measurement_compress_inplace, ekf_update,
+apply_dx.  It is pinned against ovo_msckf_plane_update on camera-0 scenes with tracks above 32 views
+(tests/test_general_planes_cpu.py) before anything on the GPU is held to it.
+
+Also: the helpers the GPU tests share (splitting a scene into the device batch and the general batch, applying the per-plane
+corrections the way the caller of the C-ABI does)."""
+from __future__ import annotations
+
+import numpy as np
+
+from oracle import np_ref
+from ov_plane_amd.synth import quat_boxplus
+
+OVP_MAX_MEAS = 32  # the device batch: camera 0, at most this many views (include/ovplane_hip.h)
+
+
+def fits_batch(sc, f):
+    m = int(sc.n_meas[f])
+    cam0 = ("cam_idx" not in sc) or not np.any(sc.cam_idx[f, :m])
+    return cam0 and m <= OVP_MAX_MEAS
+
+
+def split_features(sc, move=None):
+    """(batch, general): indices of the features the device batch carries and of those that need the general batch.  `move` =
+    features that fit the batch but are sent through the general batch all the same."""
+    move = set() if move is None else set(int(f) for f in move)
+    batch = [f for f in range(sc.F) if fits_batch(sc, f) and f not in move]
+    gen = [f for f in range(sc.F) if not (fits_batch(sc, f) and f not in move)]
+    return np.array(batch, dtype=np.int64), np.array(gen, dtype=np.int64)
+
+
+def _state_of(sc):
+    st = dict(clone_q=sc.clone_q.copy(), clone_p=sc.clone_p.copy(), clone_q_fej=sc.clone_q_fej, clone_p_fej=sc.clone_p_fej,
+              calib_q=sc.calib_q.copy(), calib_p=sc.calib_p.copy(), intr=sc.intr.copy())
+    if "cam1" in sc:
+        st["cam1"] = dict(calib_q=np.array(sc.cam1["calib_q"], dtype=np.float64), calib_p=np.array(sc.cam1["calib_p"], dtype=np.float64),
+                          intr=np.array(sc.cam1["intr"], dtype=np.float64))
+    return st
+
+
+def apply_dx_state(sc, st, cp, dx):
+    """ext Type::update of everything the loop's rows read: np_ref.apply_dx for the clones and camera 0, the same rule for camera 1
+    and the in-state planes (Vec::update is additive)."""
+    view = dict(sc)
+    view.update(clone_q=st["clone_q"], clone_p=st["clone_p"], calib_q=st["calib_q"], calib_p=st["calib_p"], intr=st["intr"])
+    out = np_ref.apply_dx(type(sc)(view), dx)
+    new = dict(st)
+    for k in ("clone_q", "clone_p", "calib_q", "calib_p", "intr"):
+        new[k] = out[k]
+    if "cam1" in st:
+        c1, ids = st["cam1"], sc.ids
+        new["cam1"] = dict(calib_q=quat_boxplus(c1["calib_q"], dx[ids["calib1"]:ids["calib1"] + 3]),
+                           calib_p=c1["calib_p"] + dx[ids["calib1"] + 3:ids["calib1"] + 6],
+                           intr=c1["intr"] + dx[ids["intr1"]:ids["intr1"] + 8])
+    cp = cp.copy()
+    for k in range(cp.shape[0]):
+        sid = int(sc.plane_state_id[k])
+        if sid >= 0:
+            cp[k] = cp[k] + dx[sid:sid + 3]
+    return new, cp
+
+
+def plane_loop_ref(sc, force=None, feats=None, use_qr=False, freeze_cam1=False):
+    """The plane loop over the on-plane features `feats` (default: all) of the scene.  force[k] = accept / reject byte imposed
+    instead of the gate's decision; use_qr: Householder instead of the Givens sweep in the compression (same system up to row
+    signs, much quicker in numpy); freeze_cam1: camera 1's table is NOT corrected after an accepted plane (what a loop that forgot
+    it would compute - the GPU tests show they can tell the difference).
+    Returns dict(P, state, cp, dx [n_planes, N], plane_ok, plane_chi2, plane_rows, used [F])."""
+    P = sc.P.copy()
+    st = _state_of(sc)
+    cp = sc.cp.copy()
+    NP = int(sc.cp.shape[0])
+    feats = range(sc.F) if feats is None else [int(f) for f in feats]
+    ok = np.zeros(NP, dtype=bool)
+    chi2s = np.zeros(NP)
+    rows = np.zeros(NP, dtype=np.int32)
+    used = np.zeros(sc.F, dtype=bool)
+    dxs = np.zeros((NP, sc.N))
+    for pl in range(NP):
+        planeid = pl + 1
+        sid = int(sc.plane_state_id[pl])
+        in_state = sid >= 0
+        on = [f for f in feats if sc.plane_id[f] == planeid and sc.n_meas[f] >= 2]
+        if not on or (not in_state and len(on) < 4):  # UpdaterMSCKF.cpp:316-317,384-396
+            continue
+        cpv = cp[pl]
+        cpf = sc.cp_fej[pl] if in_state else cpv     # :467-475
+        order_big, col_of, blocks, ct = [], {}, [], 0
+        for f in on:
+            H_f, H_x, res, order = np_ref.feature_jacobian_full(sc, f, cp=cpv, cp_fej=cpf, plane_state_id=sid, planeid=planeid, state=st)
+            if in_state:  # :518-535 the plane's columns leave H_x
+                c0, keep, H_cp, order2 = 0, [], None, []
+                for vid, sz in order:
+                    if vid == sid:
+                        H_cp = H_x[:, c0:c0 + sz]
+                    else:
+                        keep.extend(range(c0, c0 + sz))
+                        order2.append((vid, sz))
+                    c0 += sz
+                H_x, order = H_x[:, keep], order2
+            else:         # :537-540
+                H_cp = H_f[:, 3:]
+            H_x, res, H_cp = np_ref.nullspace_project_inplace(H_f[:, :3], H_x, res, H_cp=H_cp)  # :559
+            for vid, sz in order:
+                if vid not in col_of:
+                    col_of[vid] = ct
+                    order_big.append((vid, sz))
+                    ct += sz
+            blocks.append((H_x, res, H_cp, order))
+        nrow = sum(b[1].shape[0] for b in blocks)
+        Hx_big, Hcp_big, res_big = np.zeros((nrow, ct)), np.zeros((nrow, 3)), np.zeros(nrow)
+        r0 = 0
+        for H_x, res, H_cp, order in blocks:
+            q, c0 = res.shape[0], 0
+            for vid, sz in order:
+                Hx_big[r0:r0 + q, col_of[vid]:col_of[vid] + sz] = H_x[:, c0:c0 + sz]
+                c0 += sz
+            Hcp_big[r0:r0 + q] = H_cp
+            res_big[r0:r0 + q] = res
+            r0 += q
+        Hc, rc, Hcpc = np_ref.measurement_compress_inplace(Hx_big, res_big, Hcp_big, use_qr=use_qr)  # :588
+        if in_state:  # :593-600
+            Hc = np.hstack([Hc, Hcpc])
+            order_big = order_big + [(sid, 3)]
+        else:         # :602-603
+            Hc, rc = np_ref.nullspace_project_inplace(Hcpc, Hc, rc)
+        Pm = np_ref.get_marginal_covariance(P, order_big)
+        S = Hc @ Pm @ Hc.T + np.eye(Hc.shape[0])
+        chi2 = float(rc @ np.linalg.solve(S, rc))
+        chi2s[pl], rows[pl] = chi2, Hc.shape[0]
+        accept = chi2 <= sc.opts["chi2_mult"] * np_ref.chi2_095(Hc.shape[0])
+        if force is not None:
+            accept = bool(force[pl])
+        if not accept:
+            continue
+        ok[pl] = True
+        used[on] = True
+        P, dx = np_ref.ekf_update(P, order_big, Hc, rc)
+        dxs[pl] = dx
+        cam1_before = st.get("cam1")
+        st, cp = apply_dx_state(sc, st, cp, dx)
+        if freeze_cam1:
+            st["cam1"] = cam1_before
+    return dict(P=P, state=st, cp=cp, dx=dxs, plane_ok=ok, plane_chi2=chi2s, plane_rows=rows, used=used)
+
+
+def apply_plane_dx(sc, dxs, oks):
+    """Host side of the plane loop: ext Type::update applied in plane order (what the caller of the C-ABI does).  Returns the
+    state dict and the closest points."""
+    st, cp = _state_of(sc), sc.cp.copy()
+    for pl in range(dxs.shape[0]):
+        if oks[pl]:
+            st, cp = apply_dx_state(sc, st, cp, dxs[pl])
+    return st, cp
+
+
+def relP(Pa, Pb):
+    d = np.sqrt(np.abs(np.diag(Pb)))
+    return float((np.abs(Pa - Pb) / np.outer(d, d)).max())
+
+
+def run_general(capi, sc, force=None, move=None, n_max=None):
+    """The scene through ovp_msckf_plane_update_general: the features that fit the device batch uploaded as the batch (first
+    OVP_MAX_MEAS columns), the others (and `move`) as the general batch.  Returns the entry's dict plus P, batch, gen, ctx."""
+    batch, gen = split_features(sc, move)
+    ctx = capi.Context(sc.N if n_max is None else n_max, sc.C, max(len(batch), 1))
+    ctx.cov_upload(sc.P)
+    ctx.state_upload(sc)
+    ctx.cameras_upload(sc)
+    W = min(OVP_MAX_MEAS, sc.uv.shape[1])
+    if len(batch):
+        ctx.batch_upload(sc.uv[batch][:, :W], sc.clone_idx[batch][:, :W], sc.n_meas[batch], sc.p_FinG[batch])
+        pof = sc.plane_id[batch]
+    else:  # (the entry needs a batch: one free point nobody looks at)
+        f0 = int(np.argmin(sc.n_meas))
+        ctx.batch_upload(sc.uv[[f0]][:, :W], sc.clone_idx[[f0]][:, :W], np.minimum(sc.n_meas[[f0]], 0), sc.p_FinG[[f0]])
+        pof = np.zeros(1, dtype=np.int32)
+    out = ctx.plane_update_general(capi.opts_from_scene(sc), pof, sc.cp, sc.cp_fej, sc.plane_state_id, sc=sc, feats=gen,
+                                   force_decision=None if force is None else np.asarray(force, dtype=np.uint8))
+    out["P"] = ctx.cov_download()
+    out["batch"], out["gen"], out["ctx"] = batch, gen, ctx
+    used = np.zeros(sc.F, dtype=bool)
+    if len(batch):
+        used[batch] = out["used"][:len(batch)]
+    if len(gen):
+        used[gen] = out["gen_used"]
+    out["used_all"] = used
+    return out
