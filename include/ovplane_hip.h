@@ -561,6 +561,58 @@ typedef struct {
 int ovp_plane_optimize(ovp_ctx *ctx, const ovp_planeopt_batch *batch, double *cp_out, double *p_out, uint8_t *kept,
                        uint8_t *ok, int *iterations);
 
+/* The front end of the plane path for ALL planes of a frame in one device pass: PlaneFitting::plane_fitting
+ * (track_plane/PlaneFitting.cpp:84-199) followed by PlaneFitting::optimize_plane (:201-514), driven as the loop of
+ * update/UpdaterMSCKF.cpp:262-401 drives them, over features of any camera and any track length.  One upload, the launches, one
+ * download, one synchronisation (the per-plane pair ovp_plane_fitting + ovp_plane_optimize costs 2 round trips per plane).
+ *   batch    the planes' features (clone_idx, cam_idx, n_meas, p_FinG; uv is not read); n_meas = 0 marks a SLAM landmark that is
+ *            held constant (:274-279).  No limit on n_meas other than max_meas.
+ *   uv_norm  [n_feats*max_meas*2] f32, in the layout of batch->uv (as for ovp_triangulate_general)
+ *   in       plane k owns the features [feat_start[k], feat_start[k+1]); cp[k] its closest point (read for in-state planes);
+ *            fix_plane[k] != 0: the plane is in the state - RANSAC is skipped and every feature goes to the refinement with cp
+ *            constant (UpdaterMSCKF.cpp:265-316).  A free plane with fewer than 4 features fails (:320-321).  refine = 0: fit
+ *            only (StateOptions::use_refine_plane_feat off).
+ * The camera pose of every observation comes from the resident tables: R_GtoC = R_ItoC(cam) R_GtoI(clone),
+ * p_CinG = p_IinG - R_GtoC^T p_IinC(cam) (clones of ovp_state_upload, cameras of ovp_cameras_upload); the "current camera" of the
+ * inlier tests (:444-453) is camera 0 of those tables at the pose R_GtoI / p_IinG given here.
+ * Device sequence: k_planefit_poses (pose table) -> k_plane_ransac over the free planes -> k_planefit_link (per plane: the inliers
+ * in their order, cp0 = -n d (:352), the observation lists of the refinement with pose and measurement of every item; a plane
+ * whose fit failed gets an empty list) -> k_plane_refine on those device-resident lists.
+ * Outputs (host, any may be NULL).  Per plane: fit_ok (1 for an in-state plane), abcd [4] (RANSAC + refit; zeros when it did not
+ * run or failed), ok (fit and refinement), cp_out [3] (the input cp when not ok), iterations.  Per feature, at its input index:
+ * inlier (RANSAC; 1 on an in-state plane), kept (final), p_out [3] (the refined position if kept, else the input).
+ * poses [n_clones * n_cams * 12]: the pose table, entry (clone slot, camera) = R_GtoC row-major, then p_CinG.
+ * Checked on the host before anything is enqueued - OVP_E_CAPACITY: more than 256 features on one plane; OVP_E_ARG: a camera
+ * without tables, a clone slot outside the tables, n_meas > max_meas, feat_start not ascending or not ending at n_feats;
+ * OVP_E_STATE: no ovp_state_upload / ovp_cameras_upload - both must precede the call (camera 0's extrinsics are read from the
+ * host copy ovp_cameras_upload keeps). */
+typedef struct {
+  int n_planes;
+  const int *feat_start;    /* [n_planes + 1] */
+  const double *cp;         /* [n_planes*3] */
+  const uint8_t *fix_plane; /* [n_planes] */
+  int min_inlier_num;       /* StateOptions::plane_msckf_min_feat / plane_init_min_feat */
+  double max_cond;          /* StateOptions::plane_msckf_max_cond / plane_init_max_cond */
+  int shuffle_variant;      /* as ovp_planefit_batch */
+  int refine;               /* 0 = fit only */
+  double sigma_px_norm;     /* sigma_pix / focal length */
+  double sigma_c;           /* StateOptions::sigma_constraint */
+  double R_GtoI[9], p_IinG[3]; /* current IMU pose (stateI) */
+} ovp_planefront_in;
+typedef struct {
+  uint8_t *fit_ok;   /* [n_planes] */
+  double *abcd;      /* [n_planes*4] */
+  uint8_t *ok;       /* [n_planes] */
+  double *cp_out;    /* [n_planes*3] */
+  int *iterations;   /* [n_planes] */
+  uint8_t *inlier;   /* [n_feats] */
+  uint8_t *kept;     /* [n_feats] */
+  double *p_out;     /* [n_feats*3] */
+  double *poses;     /* [n_clones*n_cams*12] */
+} ovp_planefront_out;
+int ovp_plane_fit_refine(ovp_ctx *ctx, const ovp_general_batch *batch, const float *uv_norm, const ovp_planefront_in *in,
+                         const ovp_planefront_out *out);
+
 /* ---- diagnostics ---------------------------------------------------------------------------- */
 /* copies an internal device buffer to host for tests: name in {"A","b","L","T","Lt","Y","G","rec","chi2",
  * "gramS","syrk"}; returns the byte count copied (or <0). */

@@ -168,6 +168,18 @@ class PlaneOptBatch(C.Structure):
                 ("R_ItoC", C.c_double * 9), ("p_IinC", C.c_double * 3)]
 
 
+class PlaneFrontIn(C.Structure):
+    _fields_ = [("n_planes", C.c_int), ("feat_start", C.c_void_p), ("cp", C.c_void_p), ("fix_plane", C.c_void_p),
+                ("min_inlier_num", C.c_int), ("max_cond", C.c_double), ("shuffle_variant", C.c_int), ("refine", C.c_int),
+                ("sigma_px_norm", C.c_double), ("sigma_c", C.c_double), ("R_GtoI", C.c_double * 9), ("p_IinG", C.c_double * 3)]
+
+
+class PlaneFrontOut(C.Structure):
+    _fields_ = [("fit_ok", C.c_void_p), ("abcd", C.c_void_p), ("ok", C.c_void_p), ("cp_out", C.c_void_p),
+                ("iterations", C.c_void_p), ("inlier", C.c_void_p), ("kept", C.c_void_p), ("p_out", C.c_void_p),
+                ("poses", C.c_void_p)]
+
+
 EXPORTS = [
     "ovp_ctx_create", "ovp_ctx_destroy", "ovp_sync", "ovp_version", "ovp_error_string", "ovp_cov_upload",
     "ovp_cov_download", "ovp_cov_set_device", "ovp_cov_marginal", "ovp_state_upload", "ovp_batch_upload",
@@ -180,7 +192,7 @@ EXPORTS = [
     "ovp_rccl_allreduce_gram", "ovp_msckf_update_sharded", "ovp_slam_delayed_init", "ovp_shard_range", "ovp_shard_range_of_mask",
     "ovp_rccl_gather_decisions", "ovp_msckf_dense_blocks", "ovp_cameras_upload", "ovp_msckf_general_features",
     "ovp_triangulate_general", "ovp_slam_update_general", "ovp_slam_delayed_init_general",
-    "ovp_slam_delayed_init_planes", "ovp_msckf_plane_update_general",
+    "ovp_slam_delayed_init_planes", "ovp_msckf_plane_update_general", "ovp_plane_fit_refine",
 ]
 
 
@@ -269,6 +281,8 @@ def lib():
         L.ovp_plane_fitting.argtypes = [C.c_void_p, C.POINTER(PlaneFitBatch), C.c_void_p, C.c_void_p, C.c_void_p]
         L.ovp_plane_optimize.argtypes = [C.c_void_p, C.POINTER(PlaneOptBatch), C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]
+        L.ovp_plane_fit_refine.argtypes = [C.c_void_p, C.POINTER(GeneralBatch), C.c_void_p, C.POINTER(PlaneFrontIn),
+                                           C.POINTER(PlaneFrontOut)]
         _LIB = L
     return _LIB
 
@@ -1015,6 +1029,38 @@ class Context:
                                       ok.ctypes.data, its.ctypes.data), "ovp_plane_optimize")
         return [dict(ok=bool(ok[k]), cp=cp_out[k].copy(), p_FinG=p_out[fs[k]:fs[k + 1]].copy(),
                      kept=kept[fs[k]:fs[k + 1]].astype(bool), iterations=int(its[k])) for k in range(P)]
+
+    def plane_fit_refine(self, feat_start, uv_norm, clone_idx, cam_idx, n_meas, p_FinG, cp, fix_plane, min_inlier_num, max_cond,
+                         sigma_px_norm, sigma_c, R_GtoI, p_IinG, n_clones, n_cams, refine=True, shuffle_variant=0,
+                         raise_on_error=True):
+        """ovp_plane_fit_refine: RANSAC fit and joint refinement of every plane of a frame in one device pass, over observations
+        of any camera and tracks of any length (the poses come from the resident clone / camera tables).  Plane k owns the
+        features [feat_start[k], feat_start[k+1]).  Returns dict(fit_ok [P], abcd [P,4], ok [P], cp [P,3], iterations [P],
+        inlier [F], kept [F], p_FinG [F,3], poses [n_clones, n_cams, 12], rc)."""
+        fs = np.ascontiguousarray(feat_start, dtype=np.int32)
+        P = len(fs) - 1
+        uvn = np.ascontiguousarray(uv_norm, dtype=np.float32)
+        gb = self._general_batch(uvn, clone_idx, cam_idx, n_meas, p_FinG)
+        F = gb.n_feats
+        cpa = np.ascontiguousarray(np.asarray(cp, dtype=np.float64).reshape(-1, 3))
+        fix = np.ascontiguousarray(np.asarray(fix_plane).astype(np.uint8))
+        assert len(cpa) == P and len(fix) == P
+        pin = PlaneFrontIn(P, fs.ctypes.data, cpa.ctypes.data, fix.ctypes.data, int(min_inlier_num), float(max_cond),
+                           int(shuffle_variant), 1 if refine else 0, float(sigma_px_norm), float(sigma_c))
+        pin.R_GtoI = (C.c_double * 9)(*np.asarray(R_GtoI, dtype=np.float64).reshape(-1))
+        pin.p_IinG = (C.c_double * 3)(*np.asarray(p_IinG, dtype=np.float64).reshape(-1))
+        r = dict(fit_ok=np.zeros(max(P, 1), dtype=np.uint8), abcd=np.zeros((max(P, 1), 4)), ok=np.zeros(max(P, 1), dtype=np.uint8),
+                 cp=np.zeros((max(P, 1), 3)), iterations=np.zeros(max(P, 1), dtype=np.int32), inlier=np.zeros(max(F, 1), dtype=np.uint8),
+                 kept=np.zeros(max(F, 1), dtype=np.uint8), p_FinG=np.zeros((max(F, 1), 3)),
+                 poses=np.zeros((max(int(n_clones), 1), max(int(n_cams), 1), 12)))
+        pout = PlaneFrontOut(*[r[k].ctypes.data for k in ("fit_ok", "abcd", "ok", "cp", "iterations", "inlier", "kept", "p_FinG",
+                                                           "poses")])
+        rc = lib().ovp_plane_fit_refine(self._h, C.byref(gb), uvn.ctypes.data, C.byref(pin), C.byref(pout))
+        if rc != 0 and raise_on_error:
+            raise OvpError(rc, "ovp_plane_fit_refine")
+        return dict(fit_ok=r["fit_ok"][:P].astype(bool), abcd=r["abcd"][:P], ok=r["ok"][:P].astype(bool), cp=r["cp"][:P],
+                    iterations=r["iterations"][:P], inlier=r["inlier"][:F].astype(bool), kept=r["kept"][:F].astype(bool),
+                    p_FinG=r["p_FinG"][:F], poses=r["poses"], rc=rc)
 
     def debug_chol2(self, A, brow=None, add_identity=False, reps=0, piv_floor=0.0):
         """k_chol2 on a host matrix: dict(L [(n+1),(n+1)], z, y, piv, ms, rc).  piv_floor > 0: columns whose pivot falls below it

@@ -57,6 +57,9 @@ extern "C" void ovph_set_general_features(int on) { g_general = on != 0; }
 // next ovph_run_msckf_update: StateOptions::gpu_general_planes
 static int g_general_planes = 0;
 extern "C" void ovph_set_general_planes(int on) { g_general_planes = on != 0; }
+// next ovph_run_msckf_update / ovph_run_updater: StateOptions::gpu_fused_plane_fit
+static int g_fused_plane_fit = 0;
+extern "C" void ovph_set_fused_plane_fit(int on) { g_fused_plane_fit = on != 0; }
 // next ovph_run_updater: StateOptions::gpu_general_slam
 static int g_general_slam = 0;
 extern "C" void ovph_set_general_slam(int on) { g_general_slam = on != 0; }
@@ -112,6 +115,8 @@ extern "C" int ovph_run_msckf_update(int C, const double *clone_q, const double 
   g_general = 0;
   so.gpu_general_planes = g_general_planes != 0;
   g_general_planes = 0;
+  so.gpu_fused_plane_fit = g_fused_plane_fit != 0;
+  g_fused_plane_fit = 0;
   if (g_cam1_q) so.num_cameras = 2;
   auto state = std::make_shared<State>(so);
   state->_cam_fisheye[0] = g_fisheye != 0;
@@ -527,6 +532,8 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
   }
   so.max_state_size = n_cap;
   so.max_features = F + 8;
+  so.gpu_fused_plane_fit = g_fused_plane_fit != 0;
+  g_fused_plane_fit = 0;
   so.gpu_general_slam = g_general_slam != 0;
   g_general_slam = 0;
   so.gpu_dinit_planes = g_dinit_planes != 0;

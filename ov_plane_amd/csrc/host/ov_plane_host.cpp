@@ -914,7 +914,11 @@ void UpdaterMSCKF::update(std::shared_ptr<State> state, std::vector<std::shared_
       for (auto &feat : vec) {
         auto it = feat2plane.find(feat->featid);
         if (it == feat2plane.end()) continue;
-        if (!fits_batch(*feat)) continue;  // (the fit / refinement kernels know camera 0 and 32 views: such a feature stays a point feature)
+        // (the per-plane fit / refinement calls know camera 0 and 32 views: such a feature stays a point feature; the fused
+        // call, StateOptions::gpu_fused_plane_fit, takes every camera and any length when the feature has normalised measurements)
+        if (!fits_batch(*feat) &&
+            (!state->_options.gpu_fused_plane_fit || feat->uvs_norm.size() != 2 * feat->timestamps.size()))
+          continue;
         all_norm = all_norm && (feat->uvs_norm.size() == 2 * feat->timestamps.size());
         plane_feats[it->second].push_back(feat);
       }
@@ -982,15 +986,44 @@ void UpdaterMSCKF::update(std::shared_ptr<State> state, std::vector<std::shared_
       memcpy(stateI + 4, state->_imu->pos(), 3 * sizeof(double));
       memcpy(calib0, calib->quat(), 4 * sizeof(double));
       memcpy(calib0 + 4, calib->pos(), 3 * sizeof(double));
+      // StateOptions::gpu_fused_plane_fit: fit and refinement of every plane in ONE call (ovp_plane_fit_refine), the camera poses
+      // taken from the resident tables; what follows the two PlaneFitting calls of a plane stays in the loop below
+      const bool fused_fit = state->_options.gpu_fused_plane_fit;
+      std::map<size_t, bool> fused_ok;
+      std::map<size_t, std::vector<double>> fused_cp;
+      if (fused_fit) {
+        upload_cameras();
+        std::vector<PlaneFitting::FrontPlane> jobs;
+        for (auto &fp : plane_feats) {
+          PlaneFitting::FrontPlane j;
+          j.id = fp.first;
+          j.feats = &fp.second;
+          j.fixed = state->_features_PLANE.count(fp.first) > 0;
+          if (j.fixed)
+            for (int a = 0; a < 3; ++a) j.cp[a] = state->_features_PLANE.at(fp.first)->value()(a);
+          jobs.push_back(j);
+        }
+        PlaneFitting::fit_refine_all(jobs, clone_slot, state->_options.plane_msckf_min_feat, state->_options.plane_msckf_max_cond,
+                                     state->_options.use_refine_plane_feat, sigma_px_norm, sigma_c, state->_imu->Rot(),
+                                     state->_imu->pos());
+        for (auto &j : jobs) {
+          fused_ok[j.id] = j.ok;
+          fused_cp[j.id] = {j.cp[0], j.cp[1], j.cp[2]};
+        }
+      }
       for (auto &fp : plane_feats) {  // :262-401, std::map order
         const size_t pid = fp.first;
         fitted_planes.insert(pid);
         auto &feats = fp.second;
         double cp[3];
+        if (fused_fit) {
+          if (!fused_ok.at(pid)) continue;
+          for (int a = 0; a < 3; ++a) cp[a] = fused_cp.at(pid)[a];
+        }
         if (state->_features_PLANE.count(pid)) {  // :265-316
           auto pl = state->_features_PLANE.at(pid);
           for (int a = 0; a < 3; ++a) cp[a] = pl->value()(a);
-          if (state->_options.use_refine_plane_feat &&
+          if (!fused_fit && state->_options.use_refine_plane_feat &&
               !PlaneFitting::optimize_plane(feats, cp, clones_cam, sigma_px_norm, sigma_c, true, stateI, calib0))
             continue;
           // :284-302 ground truth for the features (the plane itself is a state variable and keeps its estimate)
@@ -1000,14 +1033,16 @@ void UpdaterMSCKF::update(std::shared_ptr<State> state, std::vector<std::shared_
               if (itt != state->_true_features.end()) memcpy(ft->p_FinG, itt->second.data(), 3 * sizeof(double));
             }
         } else {
-          if (feats.size() < 4) continue;  // :320-321
-          double abcd[4];
-          if (!PlaneFitting::plane_fitting(feats, abcd, state->_options.plane_msckf_min_feat, state->_options.plane_msckf_max_cond))
-            continue;  // :325-327
-          for (int a = 0; a < 3; ++a) cp[a] = -abcd[a] * abcd[3];  // :352
-          if (state->_options.use_refine_plane_feat &&
-              !PlaneFitting::optimize_plane(feats, cp, clones_cam, sigma_px_norm, sigma_c, false, stateI, calib0))
-            continue;  // :355-357
+          if (!fused_fit) {
+            if (feats.size() < 4) continue;  // :320-321
+            double abcd[4];
+            if (!PlaneFitting::plane_fitting(feats, abcd, state->_options.plane_msckf_min_feat, state->_options.plane_msckf_max_cond))
+              continue;  // :325-327
+            for (int a = 0; a < 3; ++a) cp[a] = -abcd[a] * abcd[3];  // :352
+            if (state->_options.use_refine_plane_feat &&
+                !PlaneFitting::optimize_plane(feats, cp, clones_cam, sigma_px_norm, sigma_c, false, stateI, calib0))
+              continue;  // :355-357
+          }
           // :363-380 ground truth for the plane and its features
           if (state->_options.use_groundtruths && !state->_true_planes.empty() && !state->_true_features.empty()) {
             auto itp = state->_true_planes.find(pid);
@@ -1076,7 +1111,7 @@ void UpdaterMSCKF::update(std::shared_ptr<State> state, std::vector<std::shared_
         // plane was fitted in this frame (the fit / refinement kernels never saw it)
         auto pos = std::find(used_planes.begin(), used_planes.end(), it->second);
         if (feature_vec[f]->timestamps.size() > 32 || !feature_vec[f]->only_camera0()) {
-          if (pos != used_planes.end() && !fitted_planes.count(it->second)) {
+          if (pos != used_planes.end() && (!fitted_planes.count(it->second) || state->_options.gpu_fused_plane_fit)) {
             gen_idx.push_back(f);
             gen_plane.push_back(1 + (int)(pos - used_planes.begin()));
             gen_fits = gen_fits && (int)feature_vec[f]->timestamps.size() <= OVP_GEN_MAX_MEAS;

@@ -80,6 +80,12 @@ struct StateOptions {
   // planes whose estimate does not come from this frame's fit (in the state, or handed over in _plane_estimates_cp_inG); a frame with
   // an on-plane track above OVP_GEN_MAX_MEAS keeps the previous behaviour.  Not in the reference.
   bool gpu_general_planes = false;
+  // The front end of the plane path (UpdaterMSCKF.cpp:262-401, UpdaterPlane.cpp:221-290) as ONE call of ovp_plane_fit_refine for all
+  // planes of the frame instead of PlaneFitting::plane_fitting / optimize_plane once per plane: one round trip, and on-plane
+  // features of any camera and any track length take part in the fit (with gpu_general_planes the ones the fit kept then enter
+  // the plane loop for fitted planes too).  A feature the camera-0 batch cannot carry takes part when it has normalised
+  // measurements; one without them stays out of the fit, as every such feature does with the option off.  Not in the reference.
+  bool gpu_fused_plane_fit = false;
 };
 
 // update/UpdaterOptions.h:37-53
@@ -114,6 +120,20 @@ public:
   // stateI = [q_GtoI (JPL), p_IinG], calib0 = [q_ItoC, p_IinC]
   static bool optimize_plane(std::vector<std::shared_ptr<ov_core::Feature>> &feats, double cp_inG[3], ClonesCam &clonesCAM,
                              double sigma_px_norm, double sigma_c, bool fix_plane, const double stateI[7], const double calib0[7]);
+  // StateOptions::gpu_fused_plane_fit: plane_fitting + optimize_plane of ALL planes of a frame in one ovp_plane_fit_refine call, over
+  // every camera's observations (clone_slot: timestamp -> clone slot of the uploaded tables; the camera tables must be uploaded).
+  // A plane with `fixed` is in the state: no fit, cp stays.  On return ok says whether both steps succeeded; then feats holds the
+  // kept features at their refined positions (PlaneFitting.cpp:190, :481, :511) and cp the refined closest point.
+  struct FrontPlane {
+    size_t id = 0;
+    std::vector<std::shared_ptr<ov_core::Feature>> *feats = nullptr;
+    bool fixed = false;
+    double cp[3] = {0, 0, 0};
+    bool ok = false;
+  };
+  static void fit_refine_all(std::vector<FrontPlane> &planes, const std::map<double, int> &clone_slot, int min_inlier_num,
+                             double max_cond, bool refine, double sigma_px_norm, double sigma_c, const double R_GtoI[9],
+                             const double p_IinG[3]);
   // batched forms the updaters use: one launch for all planes
   static void bind(ovp_ctx *gpu, int shuffle_variant) {
     _gpu = gpu;

@@ -167,4 +167,80 @@ bool PlaneFitting::optimize_plane(std::vector<std::shared_ptr<ov_core::Feature>>
   return true;
 }
 
+// update/UpdaterMSCKF.cpp:262-401 / update/UpdaterPlane.cpp:221-290 as one device pass
+void PlaneFitting::fit_refine_all(std::vector<FrontPlane> &planes, const std::map<double, int> &clone_slot, int min_inlier_num,
+                                  double max_cond, bool refine, double sigma_px_norm, double sigma_c, const double R_GtoI[9],
+                                  const double p_IinG[3]) {
+  if (!_gpu) {
+    PRINT_ERROR("PlaneFitting::fit_refine_all() - no device context (construct a State first)\n");
+    std::exit(EXIT_FAILURE);
+  }
+  const int NPL = (int)planes.size();
+  if (NPL == 0) return;
+  std::vector<std::shared_ptr<ov_core::Feature>> flat;
+  std::vector<int> fstart(1, 0);
+  std::vector<double> cps;
+  std::vector<uint8_t> fix;
+  int M = 1;
+  for (auto &pl : planes) {
+    cps.insert(cps.end(), pl.cp, pl.cp + 3);
+    fix.push_back(pl.fixed ? 1 : 0);
+    for (auto &ft : *pl.feats) {
+      flat.push_back(ft);
+      M = std::max(M, (int)ft->timestamps.size());
+    }
+    fstart.push_back((int)flat.size());
+  }
+  const int F = (int)flat.size();
+  std::vector<float> uvn((size_t)F * M * 2, 0.f);
+  std::vector<int> cidx((size_t)F * M, 0), cam((size_t)F * M, 0), nm(F, 0);
+  std::vector<double> pf((size_t)std::max(F, 1) * 3);
+  for (int f = 0; f < F; ++f) {
+    const ov_core::Feature &ft = *flat[f];
+    nm[f] = (int)ft.timestamps.size();  // 0: a SLAM landmark, held constant (:274-279)
+    if (ft.uvs_norm.size() != 2 * ft.timestamps.size()) {
+      PRINT_ERROR("PlaneFitting::fit_refine_all() - feature %zu has no normalised measurements\n", ft.featid);
+      std::exit(EXIT_FAILURE);
+    }
+    for (int k = 0; k < nm[f]; ++k) {
+      const size_t ob = (size_t)f * M + k;
+      cidx[ob] = clone_slot.at(ft.timestamps[k]);
+      cam[ob] = ft.cam_of(k);
+      uvn[2 * ob] = ft.uvs_norm[2 * k];
+      uvn[2 * ob + 1] = ft.uvs_norm[2 * k + 1];
+    }
+    memcpy(&pf[3 * f], ft.p_FinG, 3 * sizeof(double));
+  }
+  ovp_general_batch gb{F, M, uvn.data(), cidx.data(), cam.data(), nm.data(), pf.data()};
+  ovp_planefront_in pin;
+  pin.n_planes = NPL;
+  pin.feat_start = fstart.data();
+  pin.cp = cps.data();
+  pin.fix_plane = fix.data();
+  pin.min_inlier_num = min_inlier_num;
+  pin.max_cond = max_cond;
+  pin.shuffle_variant = _variant;
+  pin.refine = refine ? 1 : 0;
+  pin.sigma_px_norm = sigma_px_norm;
+  pin.sigma_c = sigma_c;
+  memcpy(pin.R_GtoI, R_GtoI, 9 * sizeof(double));
+  memcpy(pin.p_IinG, p_IinG, 3 * sizeof(double));
+  std::vector<uint8_t> okp(NPL, 0), kept(std::max(F, 1), 0);
+  std::vector<double> cpo((size_t)NPL * 3), po((size_t)std::max(F, 1) * 3);
+  ovp_planefront_out pout{nullptr, nullptr, okp.data(), cpo.data(), nullptr, nullptr, kept.data(), po.data(), nullptr};
+  pf_check(ovp_plane_fit_refine(_gpu, &gb, uvn.data(), &pin, &pout), "ovp_plane_fit_refine");
+  for (int k = 0; k < NPL; ++k) {
+    planes[k].ok = okp[k] != 0;
+    if (!planes[k].ok) continue;
+    memcpy(planes[k].cp, &cpo[3 * k], 3 * sizeof(double));
+    std::vector<std::shared_ptr<ov_core::Feature>> in;
+    for (int f = fstart[k]; f < fstart[k + 1]; ++f)
+      if (kept[f]) {
+        memcpy(flat[f]->p_FinG, &po[3 * f], 3 * sizeof(double));
+        in.push_back(flat[f]);
+      }
+    *planes[k].feats = in;
+  }
+}
+
 }  // namespace ov_plane

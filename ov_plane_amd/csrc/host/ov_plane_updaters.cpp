@@ -1610,18 +1610,42 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
     memcpy(stateI + 4, state->_imu->pos(), 3 * sizeof(double));
     memcpy(calib0, calib->quat(), 4 * sizeof(double));
     memcpy(calib0 + 4, calib->pos(), 3 * sizeof(double));
-    for (auto &fp : plane_feats) {
-      bool all_norm = true;
-      for (auto &ft : fp.second) all_norm = all_norm && (ft->uvs_norm.size() == 2 * ft->timestamps.size());
-      if (!all_norm) continue;  // optimize_plane needs the normalised measurements
-      double abcd[4];
-      if (!PlaneFitting::plane_fitting(fp.second, abcd, state->_options.plane_init_min_feat, state->_options.plane_init_max_cond)) continue;
-      double cp0[3] = {-abcd[0] * abcd[3], -abcd[1] * abcd[3], -abcd[2] * abcd[3]};
-      if (!PlaneFitting::optimize_plane(fp.second, cp0, clones_cam, sigma_px_norm, state->_options.sigma_constraint, false, stateI, calib0))
-        continue;
-      state->_plane_estimates_cp_inG[fp.first] = {cp0[0], cp0[1], cp0[2]};
-      todo.push_back(fp.first);
-      for (auto &ft : fp.second) fit_kept.insert(ft->featid);
+    if (state->_options.gpu_fused_plane_fit) {
+      // StateOptions::gpu_fused_plane_fit: every plane in ONE call (ovp_plane_fit_refine), poses from the resident tables, every
+      // camera's observations; the planes without normalised measurements are left out as below
+      UpdaterSLAM::upload_camera_tables(state);
+      std::vector<PlaneFitting::FrontPlane> jobs;
+      for (auto &fp : plane_feats) {
+        bool all_norm = true;
+        for (auto &ft : fp.second) all_norm = all_norm && (ft->uvs_norm.size() == 2 * ft->timestamps.size());
+        if (!all_norm) continue;
+        PlaneFitting::FrontPlane j;
+        j.id = fp.first;
+        j.feats = &fp.second;
+        jobs.push_back(j);
+      }
+      PlaneFitting::fit_refine_all(jobs, clone_slot, state->_options.plane_init_min_feat, state->_options.plane_init_max_cond, true,
+                                   sigma_px_norm, state->_options.sigma_constraint, state->_imu->Rot(), state->_imu->pos());
+      for (auto &j : jobs) {
+        if (!j.ok) continue;
+        state->_plane_estimates_cp_inG[j.id] = {j.cp[0], j.cp[1], j.cp[2]};
+        todo.push_back(j.id);
+        for (auto &ft : *j.feats) fit_kept.insert(ft->featid);
+      }
+    } else {
+      for (auto &fp : plane_feats) {
+        bool all_norm = true;
+        for (auto &ft : fp.second) all_norm = all_norm && (ft->uvs_norm.size() == 2 * ft->timestamps.size());
+        if (!all_norm) continue;  // optimize_plane needs the normalised measurements
+        double abcd[4];
+        if (!PlaneFitting::plane_fitting(fp.second, abcd, state->_options.plane_init_min_feat, state->_options.plane_init_max_cond)) continue;
+        double cp0[3] = {-abcd[0] * abcd[3], -abcd[1] * abcd[3], -abcd[2] * abcd[3]};
+        if (!PlaneFitting::optimize_plane(fp.second, cp0, clones_cam, sigma_px_norm, state->_options.sigma_constraint, false, stateI, calib0))
+          continue;
+        state->_plane_estimates_cp_inG[fp.first] = {cp0[0], cp0[1], cp0[2]};
+        todo.push_back(fp.first);
+        for (auto &ft : fp.second) fit_kept.insert(ft->featid);
+      }
     }
   }
   if (todo.empty()) {

@@ -940,6 +940,139 @@ __global__ __launch_bounds__(256) void k_plane_refine(const RefineJob j) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// ovp_plane_fit_refine: what lies between the RANSAC and the refinement when both stay on the device
+// ------------------------------------------------------------------------------------------------
+// The camera pose of every (clone slot, camera) pair: R_GtoC = R_ItoC R_GtoI, p_CinG = p_IinG - R_GtoC^T p_IinC
+// (update/UpdaterMSCKF.cpp:129-130; the formulas of k_triangulate_gen).  One thread per pair.
+__global__ __launch_bounds__(64) void k_planefit_poses(const PlaneFrontJob j) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= j.n_clones * j.n_cams) return;
+  const int slot = i / j.n_cams, cam = i - slot * j.n_cams;
+  const double* cal = j.cam_cal + 20 * cam;
+  const double* RI = j.clone_R + 9 * slot;
+  const double* pI = j.clone_p + 3 * slot;
+  double R[9];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) R[3 * a + b] = cal[3 * a] * RI[b] + cal[3 * a + 1] * RI[3 + b] + cal[3 * a + 2] * RI[6 + b];
+  double* o = j.poses + (size_t)12 * i;
+#pragma unroll
+  for (int a = 0; a < 9; ++a) o[a] = R[a];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) o[9 + a] = pI[a] - (R[a] * cal[9] + R[3 + a] * cal[10] + R[6 + a] * cal[11]);
+}
+
+// inclusive prefix sums of two ints per thread over the 256 threads of the workgroup (Hillis-Steele in LDS, two buffers)
+__device__ __forceinline__ void pf_scan2(int& a, int& b, int (*buf)[2][256], int tid) {
+  int cur = 0;
+  __syncthreads();  // (the buffers may still be read from the previous use)
+  buf[0][0][tid] = a;
+  buf[0][1][tid] = b;
+  __syncthreads();
+#pragma unroll
+  for (int off = 1; off < 256; off <<= 1) {
+    int va = buf[cur][0][tid], vb = buf[cur][1][tid];
+    if (tid >= off) {
+      va += buf[cur][0][tid - off];
+      vb += buf[cur][1][tid - off];
+    }
+    buf[cur ^ 1][0][tid] = va;
+    buf[cur ^ 1][1][tid] = vb;
+    cur ^= 1;
+    __syncthreads();
+  }
+  a = buf[cur][0][tid];
+  b = buf[cur][1][tid];
+}
+
+// One workgroup per plane, behind k_plane_ransac: the plane's inliers in their order (feats = best_inliers, PlaneFitting.cpp:190;
+// every feature of an in-state plane), the closest point the refinement starts from (update/UpdaterMSCKF.cpp:352) and the
+// observation lists of k_plane_refine, in the order the launcher of ovp_plane_optimize builds them on the host, with the pose and
+// the measurement of every item.  The lists of all planes are dense (k_plane_refine takes a plane's features between two entries
+// of ONE feat_start array), so a plane starts where the planes in front of it end: every workgroup counts the inliers and the
+// observations of those planes itself - no atomics, no waiting on another workgroup, every loop bounded by an input count.  A plane
+// whose fit failed contributes nothing and gets an empty list, which k_plane_refine reports as a failure (:214-217).
+__global__ __launch_bounds__(256) void k_planefit_link(const PlaneFrontJob j) {
+  const int pl = blockIdx.x, tid = threadIdx.x;
+  __shared__ int scan_s[2][2][256];
+  __shared__ int c_item0[256], c_loc[256];  // by compacted feature: first item, position in the plane
+  auto is_in = [&](int q, int i) -> bool {  // feature i of plane q goes to the refinement
+    const int r = j.free_slot[q];
+    if (r < 0) return true;
+    return j.rs_ok[r] != 0 && j.rs_inlier[j.rs_feat_start[r] + i] != 0;
+  };
+  // the planes in front of this one (workgroup k reads the masks of k planes: quadratic in the planes of a call, at most 256 bytes
+  // per plane - a few thousand byte reads at the 20 planes of a crowded frame)
+  int nfeat_before = 0, nitem_before = 0;
+  for (int q = 0; q < pl; ++q) {
+    const int f0q = j.feat_start[q], nq = j.feat_start[q + 1] - f0q;
+    for (int i = tid; i < nq; i += 256)
+      if (is_in(q, i)) {
+        nfeat_before += 1;
+        nitem_before += j.n_meas[f0q + i];
+      }
+  }
+  pf_scan2(nfeat_before, nitem_before, scan_s, tid);
+  const int base_f = scan_s[0][0][255], base_i = scan_s[0][1][255];  // (eight steps: the result is in buffer 0)
+  // this plane
+  const int f0 = j.feat_start[pl], nf = j.feat_start[pl + 1] - f0;  // nf <= 256 (checked by the launcher)
+  const bool in = tid < nf && is_in(pl, tid);
+  const int m = in ? j.n_meas[f0 + tid] : 0;
+  int pos = in ? 1 : 0, it0 = m;
+  pf_scan2(pos, it0, scan_s, tid);
+  const int nc = scan_s[0][0][255], ni = scan_s[0][1][255];
+  pos -= in ? 1 : 0;
+  it0 -= m;
+  if (in) {
+    const int g = base_f + pos;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) j.c_p0[3 * (size_t)g + a] = j.p_in[3 * (size_t)(f0 + tid) + a];
+    j.c_n_obs[g] = m;
+    j.c_src[g] = f0 + tid;
+    j.feat_item0[g] = it0;
+    c_item0[pos] = it0;
+    c_loc[pos] = tid;
+  }
+  __syncthreads();
+  // the items, a pass of 256 at a time: item i belongs to the last compacted feature that starts at or in front of it (the
+  // features without observations in front of that one start at the same item)
+  for (int i = tid; i < ni; i += 256) {
+    int lo = 0, hi = nc - 1;
+    while (lo < hi) {  // at most 8 steps
+      const int mid = (lo + hi + 1) >> 1;
+      if (c_item0[mid] <= i) lo = mid;
+      else hi = mid - 1;
+    }
+    const int k = i - c_item0[lo];
+    const size_t ob = (size_t)(f0 + c_loc[lo]) * j.max_meas + k;
+    const double* pose = j.poses + (size_t)12 * (j.clone_idx[ob] * j.n_cams + j.cam_idx[ob]);
+    const size_t gi = (size_t)base_i + i;
+    j.item_ob[gi] = (int)gi;
+    j.item_lf[gi] = lo;
+    j.it_uv[2 * gi] = (double)j.uvn[2 * ob];
+    j.it_uv[2 * gi + 1] = (double)j.uvn[2 * ob + 1];
+#pragma unroll
+    for (int a = 0; a < 9; ++a) j.it_R[9 * gi + a] = pose[a];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) j.it_p[3 * gi + a] = pose[9 + a];
+  }
+  if (tid == 0) {
+    j.c_feat_start[pl] = base_f;
+    j.item_start[pl] = base_i;
+    if (pl == j.n_planes - 1) {
+      j.c_feat_start[pl + 1] = base_f + nc;
+      j.item_start[pl + 1] = base_i + ni;
+    }
+    const int r = j.free_slot[pl];
+    const bool fitted = r >= 0 && j.rs_ok[r] != 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+      j.cp0[3 * pl + a] = fitted ? -j.rs_abcd[4 * r + a] * j.rs_abcd[4 * r + 3] : j.cp_in[3 * pl + a];  // UpdaterMSCKF.cpp:352
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side of the RANSAC: std::mt19937 + libstdc++'s std::shuffle / uniform_int_distribution, restated so that the
 // hypothesis sets do not depend on the compiler this library is built with (variant 0 = GCC <= 10, the reference's
 // platforms; 1 = GCC >= 11).
@@ -1027,6 +1160,39 @@ static void ovp_shuffle(std::vector<int>& v, Mt19937& g, int variant) {
     }                                     \
   } while (0)
 
+// PlaneFitting.cpp:104-141 for one plane: the 200 shuffles and the greedy 5-point selections (pts = the plane's points)
+extern "C" void ovp_planefit_sets(const double* pts, int n, int min_inlier_num, int shuffle_variant, int* sets) {
+  for (int i = 0; i < ovp::RS_ITERS * 5; ++i) sets[i] = -1;
+  if (n < min_inlier_num) return;  // the kernel reports the failure
+  ovp::Mt19937 g(8888u);
+  std::vector<int> order((size_t)n);
+  bool dead = false;
+  for (int it = 0; it < ovp::RS_ITERS && !dead; ++it) {
+    for (int i = 0; i < n; ++i) order[i] = i;
+    ovp::ovp_shuffle(order, g, shuffle_variant);
+    int set[5], ns = 0;
+    for (int k = 0; k < n && ns < 5; ++k) {
+      const double* p = pts + 3 * (size_t)order[k];
+      bool good = true;
+      for (int q = 0; q < ns; ++q) {
+        const double* r = pts + 3 * (size_t)set[q];
+        const double d0 = r[0] - p[0], d1 = r[1] - p[1], d2 = r[2] - p[2];
+        if (std::sqrt(d0 * d0 + d1 * d1 + d2 * d2) < 0.05) {
+          good = false;
+          break;
+        }
+      }
+      if (ns == 0 || good) set[ns++] = order[k];
+    }
+    int* dst = sets + (size_t)it * 5;
+    if (ns != 5) {
+      dead = true;  // :138-141 - dst stays -1: the call fails at this iteration
+    } else {
+      for (int k = 0; k < 5; ++k) dst[k] = set[k];
+    }
+  }
+}
+
 extern "C" int ovp_plane_fitting(ovp_ctx* c, const ovp_planefit_batch* b, double* abcd, uint8_t* inlier, uint8_t* ok) {
   if (!c || !b || !abcd || !inlier || !ok) return OVP_E_ARG;
   const int P = b->n_planes;
@@ -1039,34 +1205,7 @@ extern "C" int ovp_plane_fitting(ovp_ctx* c, const ovp_planefit_batch* b, double
   std::vector<int> sets((size_t)P * ovp::RS_ITERS * 5, -1);
   for (int pl = 0; pl < P; ++pl) {
     const int f0 = b->feat_start[pl], n = b->feat_start[pl + 1] - f0;
-    if (n < b->min_inlier_num) continue;  // the kernel reports the failure
-    ovp::Mt19937 g(8888u);
-    std::vector<int> order((size_t)n);
-    bool dead = false;
-    for (int it = 0; it < ovp::RS_ITERS && !dead; ++it) {
-      for (int i = 0; i < n; ++i) order[i] = i;
-      ovp::ovp_shuffle(order, g, b->shuffle_variant);
-      int set[5], ns = 0;
-      for (int k = 0; k < n && ns < 5; ++k) {
-        const double* p = b->p_FinG + 3 * (size_t)(f0 + order[k]);
-        bool good = true;
-        for (int q = 0; q < ns; ++q) {
-          const double* r = b->p_FinG + 3 * (size_t)(f0 + set[q]);
-          const double d0 = r[0] - p[0], d1 = r[1] - p[1], d2 = r[2] - p[2];
-          if (std::sqrt(d0 * d0 + d1 * d1 + d2 * d2) < 0.05) {
-            good = false;
-            break;
-          }
-        }
-        if (ns == 0 || good) set[ns++] = order[k];
-      }
-      int* dst = sets.data() + ((size_t)pl * ovp::RS_ITERS + it) * 5;
-      if (ns != 5) {
-        dead = true;  // :138-141 - dst stays -1: the call fails at this iteration
-      } else {
-        for (int k = 0; k < 5; ++k) dst[k] = set[k];
-      }
-    }
+    ovp_planefit_sets(b->p_FinG + 3 * (size_t)f0, n, b->min_inlier_num, b->shuffle_variant, sets.data() + (size_t)pl * ovp::RS_ITERS * 5);
   }
   // one pinned block in, one out (ovp_io_arena): [feat_start | points | hypothesis sets | -> abcd | inlier | ok]
   auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
@@ -1232,4 +1371,54 @@ extern "C" int ovp_plane_optimize(ovp_ctx* c, const ovp_planeopt_batch* b, doubl
   memcpy(ok, hb + o_ok, (size_t)P);
   if (iterations) memcpy(iterations, hb + o_it, sizeof(int) * (size_t)P);
   return 0;
+}
+
+extern "C" hipError_t ovp_launch_planefront(const ovp::PlaneFrontJob* j, hipStream_t s) {
+  const int pairs = j->n_clones * j->n_cams;
+  hipLaunchKernelGGL(ovp::k_planefit_poses, dim3((pairs + 63) / 64), dim3(64), 0, s, *j);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (j->n_free > 0) {
+    ovp::RansacJob rj;
+    rj.feat_start = j->rs_feat_start;
+    rj.pts = j->rs_pts;
+    rj.sets = j->rs_sets;
+    rj.min_inlier_num = j->min_inlier_num;
+    rj.max_cond = j->max_cond;
+    rj.abcd = j->rs_abcd;
+    rj.inlier = j->rs_inlier;
+    rj.ok = j->rs_ok;
+    hipLaunchKernelGGL(ovp::k_plane_ransac, dim3(j->n_free), dim3(256), 0, s, rj);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (!j->refine) return hipSuccess;
+  hipLaunchKernelGGL(ovp::k_planefit_link, dim3(j->n_planes), dim3(256), 0, s, *j);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  ovp::RefineJob f;
+  f.feat_start = j->c_feat_start;
+  f.p0 = j->c_p0;
+  f.obs_start = nullptr;  // (the kernel walks the item lists)
+  f.n_obs = j->c_n_obs;
+  f.uv = j->it_uv;
+  f.Rc = j->it_R;
+  f.pc = j->it_p;
+  f.cp0 = j->cp0;
+  f.fix_plane = j->fix_plane;
+  f.item_start = j->item_start;
+  f.item_ob = j->item_ob;
+  f.item_lf = j->item_lf;
+  f.feat_item0 = j->feat_item0;
+  f.sigma_px_norm = j->sigma_px_norm;
+  f.sigma_c = j->sigma_c;
+  for (int i = 0; i < 9; ++i) f.R_GtoC[i] = j->R_GtoC[i];
+  for (int i = 0; i < 3; ++i) f.p_CinG[i] = j->p_CinG[i];
+  f.cp_out = j->cp_out;
+  f.p_out = j->c_p_out;
+  f.kept = j->c_kept;
+  f.ok = j->ok;
+  f.iterations = j->iterations;
+  hipLaunchKernelGGL(ovp::k_plane_refine, dim3(j->n_planes), dim3(256), 0, s, f);
+  return hipGetLastError();
 }

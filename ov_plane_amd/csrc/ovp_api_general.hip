@@ -23,14 +23,14 @@ extern "C" int ovp_cameras_upload(ovp_ctx* c, int n_cams, const ovp_camera_table
 }
 
 // argument checks of a general batch against the context's tables (host only, nothing enqueued)
-int check_general_batch(const ovp_ctx* c, const ovp_general_batch* b, bool need_p, const int* only) {
+int check_general_batch(const ovp_ctx* c, const ovp_general_batch* b, bool need_p, const int* only, bool any_length) {
   if (!b || b->n_feats < 0) return OVP_E_ARG;
   if (b->n_feats == 0) return 0;
-  if (b->max_meas < 1 || !b->uv || !b->clone_idx || !b->cam_idx || !b->n_meas || (need_p && !b->p_FinG)) return OVP_E_ARG;
+  if (b->max_meas < 1 || (!b->uv && !any_length) || !b->clone_idx || !b->cam_idx || !b->n_meas || (need_p && !b->p_FinG)) return OVP_E_ARG;
   for (int f = 0; f < b->n_feats; ++f) {
     if (only && !only[f]) continue;
     const int m = b->n_meas[f];
-    if (m > OVP_GEN_MAX_MEAS) return OVP_E_CAPACITY;
+    if (m > OVP_GEN_MAX_MEAS && !any_length) return OVP_E_CAPACITY;
     if (m < 0 || m > b->max_meas) return OVP_E_ARG;
     for (int k = 0; k < m; ++k) {
       const size_t o = (size_t)f * b->max_meas + k;
@@ -248,5 +248,200 @@ extern "C" int ovp_triangulate_general(ovp_ctx* c, const ovp_triang_opts* o, con
   HIPCHK(hipStreamSynchronize(c->stream));
   if (p_FinG_out) memcpy(p_FinG_out, h + o_p, sizeof(double) * 3 * F);
   memcpy(ok, h + o_ok, F);
+  return 0;
+}
+
+// PlaneFitting::plane_fitting + optimize_plane for every plane of a frame (update/UpdaterMSCKF.cpp:262-401) as one device sequence
+// (k_planefit.hip): the inputs cross the bus in one copy, the lists that link the RANSAC to the refinement stay on the device
+// (gen_buf), the results come back in one copy behind one synchronisation.
+extern "C" int ovp_plane_fit_refine(ovp_ctx* c, const ovp_general_batch* b, const float* uv_norm, const ovp_planefront_in* in,
+                                    const ovp_planefront_out* out) {
+  if (!c || !b || !in || !out) return OVP_E_ARG;
+  if (!c->have_state || c->gen_ncams < 1) return OVP_E_STATE;
+  const int P = in->n_planes;
+  if (P < 0) return OVP_E_ARG;
+  if (P == 0) return 0;
+  if (!in->feat_start || !in->cp || !in->fix_plane) return OVP_E_ARG;
+  const int F = b->n_feats, M = b->max_meas, NC = c->fp.n_clones, NK = c->gen_ncams;
+  if (F < 0 || in->feat_start[0] != 0 || in->feat_start[P] != F) return OVP_E_ARG;
+  for (int k = 0; k < P; ++k) {
+    if (in->feat_start[k + 1] < in->feat_start[k]) return OVP_E_ARG;
+    if (in->feat_start[k + 1] - in->feat_start[k] > 256) return OVP_E_CAPACITY;  // one thread per feature of a plane
+  }
+  if (F > 0 && !uv_norm) return OVP_E_ARG;
+  {
+    const int rc = check_general_batch(c, b, true, nullptr, true);
+    if (rc) return rc;
+  }
+  size_t O = 0;
+  for (int f = 0; f < F; ++f) O += (size_t)b->n_meas[f];
+  if (O > (size_t)0x7fffffff) return OVP_E_CAPACITY;
+  // the free planes, compacted for the RANSAC
+  std::vector<int> free_slot((size_t)P, -1), rs_fs(1, 0);
+  for (int k = 0; k < P; ++k)
+    if (!in->fix_plane[k]) {
+      free_slot[k] = (int)rs_fs.size() - 1;
+      rs_fs.push_back(rs_fs.back() + in->feat_start[k + 1] - in->feat_start[k]);
+    }
+  const int NF = (int)rs_fs.size() - 1, FR = rs_fs.back();
+  const size_t FM = (size_t)F * M, n_sets = (size_t)NF * 200 * 5;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off = al64(off + bytes);
+    return o;
+  };
+  // arena: inputs ...
+  const size_t o_fs = take(sizeof(int) * (P + 1)), o_slot = take(sizeof(int) * P), o_rfs = take(sizeof(int) * (NF + 1)),
+               o_rpts = take(sizeof(double) * 3 * FR), o_sets = take(sizeof(int) * n_sets), o_nm = take(sizeof(int) * F),
+               o_ci = take(sizeof(int) * FM), o_cam = take(sizeof(int) * FM), o_uv = take(sizeof(float) * 2 * FM),
+               o_p = take(sizeof(double) * 3 * F), o_cp = take(sizeof(double) * 3 * P), o_fix = take((size_t)P);
+  const size_t in_bytes = off;
+  // ... and results
+  const size_t o_pose = take(sizeof(double) * 12 * NC * NK), o_abcd = take(sizeof(double) * 4 * NF), o_rinl = take((size_t)FR),
+               o_rok = take((size_t)NF), o_cfs = take(sizeof(int) * (P + 1)), o_src = take(sizeof(int) * F),
+               o_cpo = take(sizeof(double) * 3 * P), o_po = take(sizeof(double) * 3 * F), o_kept = take((size_t)F),
+               o_ok = take((size_t)P), o_it = take(sizeof(int) * P);
+  const size_t total = off;
+  // device only: the refinement's lists
+  off = 0;
+  const size_t w_p0 = take(sizeof(double) * 3 * F), w_no = take(sizeof(int) * F), w_is = take(sizeof(int) * (P + 1)),
+               w_iob = take(sizeof(int) * O), w_ilf = take(sizeof(int) * O), w_fi0 = take(sizeof(int) * F),
+               w_uv = take(sizeof(double) * 2 * O), w_R = take(sizeof(double) * 9 * O), w_pc = take(sizeof(double) * 3 * O),
+               w_cp0 = take(sizeof(double) * 3 * P);
+  const size_t work = off;
+  void *ah = nullptr, *ad = nullptr;
+  {
+    const int rca = ovp_io_arena(c, total, &ah, &ad);
+    if (rca) return rca;
+    const int rcs = gen_scratch(c, work);
+    if (rcs) return rcs;
+  }
+  char *h = (char*)ah, *d = (char*)ad, *w = (char*)c->gen_buf;
+  memcpy(h + o_fs, in->feat_start, sizeof(int) * (P + 1));
+  memcpy(h + o_slot, free_slot.data(), sizeof(int) * P);
+  memcpy(h + o_rfs, rs_fs.data(), sizeof(int) * (NF + 1));
+  for (int k = 0; k < P; ++k) {
+    const int r = free_slot[k];
+    if (r < 0) continue;
+    const int f0 = in->feat_start[k], n = in->feat_start[k + 1] - f0;
+    double* pts = (double*)(h + o_rpts) + 3 * (size_t)rs_fs[r];
+    int* sets = (int*)(h + o_sets) + (size_t)r * 200 * 5;
+    memcpy(pts, b->p_FinG + 3 * (size_t)f0, sizeof(double) * 3 * n);
+    ovp_planefit_sets(pts, n, in->min_inlier_num, in->shuffle_variant, sets);
+    if (n < 4) sets[0] = -1;  // update/UpdaterMSCKF.cpp:320-321: the RANSAC reports the plane as failed
+  }
+  if (F > 0) {
+    memcpy(h + o_nm, b->n_meas, sizeof(int) * F);
+    memcpy(h + o_ci, b->clone_idx, sizeof(int) * FM);
+    memcpy(h + o_cam, b->cam_idx, sizeof(int) * FM);
+    memcpy(h + o_uv, uv_norm, sizeof(float) * 2 * FM);
+    memcpy(h + o_p, b->p_FinG, sizeof(double) * 3 * F);
+  }
+  memcpy(h + o_cp, in->cp, sizeof(double) * 3 * P);
+  memcpy(h + o_fix, in->fix_plane, (size_t)P);
+  HIPCHK(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, c->stream));
+  ovp::PlaneFrontJob j;
+  memset(&j, 0, sizeof(j));
+  j.n_planes = P;
+  j.n_free = NF;
+  j.n_clones = NC;
+  j.n_cams = NK;
+  j.max_meas = M;
+  j.refine = in->refine ? 1 : 0;
+  j.clone_R = c->clone_R;
+  j.clone_p = c->clone_p;
+  j.cam_cal = c->gen_cal;
+  j.poses = (double*)(d + o_pose);
+  j.rs_feat_start = (const int*)(d + o_rfs);
+  j.rs_pts = (const double*)(d + o_rpts);
+  j.rs_sets = (const int*)(d + o_sets);
+  j.min_inlier_num = in->min_inlier_num;
+  j.max_cond = in->max_cond;
+  j.rs_abcd = (double*)(d + o_abcd);
+  j.rs_inlier = (unsigned char*)(d + o_rinl);
+  j.rs_ok = (unsigned char*)(d + o_rok);
+  j.feat_start = (const int*)(d + o_fs);
+  j.free_slot = (const int*)(d + o_slot);
+  j.n_meas = (const int*)(d + o_nm);
+  j.clone_idx = (const int*)(d + o_ci);
+  j.cam_idx = (const int*)(d + o_cam);
+  j.uvn = (const float*)(d + o_uv);
+  j.p_in = (const double*)(d + o_p);
+  j.cp_in = (const double*)(d + o_cp);
+  j.fix_plane = (const unsigned char*)(d + o_fix);
+  j.c_feat_start = (int*)(d + o_cfs);
+  j.c_src = (int*)(d + o_src);
+  j.c_p0 = (double*)(w + w_p0);
+  j.c_n_obs = (int*)(w + w_no);
+  j.item_start = (int*)(w + w_is);
+  j.item_ob = (int*)(w + w_iob);
+  j.item_lf = (int*)(w + w_ilf);
+  j.feat_item0 = (int*)(w + w_fi0);
+  j.it_uv = (double*)(w + w_uv);
+  j.it_R = (double*)(w + w_R);
+  j.it_p = (double*)(w + w_pc);
+  j.cp0 = (double*)(w + w_cp0);
+  j.sigma_px_norm = in->sigma_px_norm;
+  j.sigma_c = in->sigma_c;
+  // current camera: camera 0 of the tables at the pose given   (PlaneFitting.cpp:444-453)
+  const double* cal0 = c->gen_cal_h;
+  for (int i = 0; i < 3; ++i)
+    for (int k = 0; k < 3; ++k) {
+      double sum = 0.0;
+      for (int q = 0; q < 3; ++q) sum += cal0[3 * i + q] * in->R_GtoI[3 * q + k];
+      j.R_GtoC[3 * i + k] = sum;
+    }
+  for (int i = 0; i < 3; ++i) {
+    double sum = 0.0;
+    for (int q = 0; q < 3; ++q) sum += j.R_GtoC[3 * q + i] * cal0[9 + q];
+    j.p_CinG[i] = in->p_IinG[i] - sum;
+  }
+  j.cp_out = (double*)(d + o_cpo);
+  j.c_p_out = (double*)(d + o_po);
+  j.c_kept = (unsigned char*)(d + o_kept);
+  j.ok = (unsigned char*)(d + o_ok);
+  j.iterations = (int*)(d + o_it);
+  HIPCHK(ovp_launch_planefront(&j, c->stream));
+  const size_t out_end = j.refine ? total : o_cfs;  // (fit only: nothing behind the RANSAC's results was written)
+  HIPCHK(hipMemcpyAsync(h + o_pose, d + o_pose, out_end - o_pose, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (out->poses) memcpy(out->poses, h + o_pose, sizeof(double) * 12 * NC * NK);
+  const double* r_abcd = (const double*)(h + o_abcd);
+  const unsigned char *r_inl = (const unsigned char*)(h + o_rinl), *r_ok = (const unsigned char*)(h + o_rok);
+  const int *cfs = (const int*)(h + o_cfs), *src = (const int*)(h + o_src), *its = (const int*)(h + o_it);
+  const double *d_cpo = (const double*)(h + o_cpo), *d_po = (const double*)(h + o_po);
+  const unsigned char *d_kept = (const unsigned char*)(h + o_kept), *d_ok = (const unsigned char*)(h + o_ok);
+  if (out->p_out && F > 0) memcpy(out->p_out, b->p_FinG, sizeof(double) * 3 * F);
+  if (out->kept && F > 0) memset(out->kept, 0, (size_t)F);
+  for (int k = 0; k < P; ++k) {
+    const int r = free_slot[k], f0 = in->feat_start[k], n = in->feat_start[k + 1] - f0;
+    const bool fitted = r < 0 || r_ok[r] != 0;
+    if (out->fit_ok) out->fit_ok[k] = fitted ? 1 : 0;
+    if (out->abcd)
+      for (int a = 0; a < 4; ++a) out->abcd[4 * k + a] = r >= 0 ? r_abcd[4 * r + a] : 0.0;
+    if (out->inlier)
+      for (int i = 0; i < n; ++i) out->inlier[f0 + i] = r < 0 ? 1 : r_inl[rs_fs[r] + i];
+    bool ok = fitted;
+    if (j.refine) {
+      ok = d_ok[k] != 0;
+      for (int g = cfs[k]; g < cfs[k + 1]; ++g) {
+        const int f = src[g];
+        if (out->kept) out->kept[f] = d_kept[g] ? 1 : 0;
+        if (out->p_out) memcpy(out->p_out + 3 * (size_t)f, d_po + 3 * (size_t)g, sizeof(double) * 3);
+      }
+    } else if (out->kept) {
+      for (int i = 0; i < n; ++i) out->kept[f0 + i] = r < 0 ? 1 : r_inl[rs_fs[r] + i];
+    }
+    if (out->ok) out->ok[k] = ok ? 1 : 0;
+    if (out->iterations) out->iterations[k] = j.refine ? its[k] : 0;
+    if (out->cp_out)
+      for (int a = 0; a < 3; ++a) {
+        double v = in->cp[3 * k + a];  // the input when the plane is not ok
+        if (ok && j.refine) v = d_cpo[3 * k + a];
+        else if (ok && r >= 0) v = -r_abcd[4 * r + a] * r_abcd[4 * r + 3];  // UpdaterMSCKF.cpp:352
+        out->cp_out[3 * k + a] = v;
+      }
+  }
   return 0;
 }

@@ -336,7 +336,8 @@ extern "C" int ovp_io_arena(ovp_ctx* c, size_t bytes, void** host, void** dev); 
 int fill_feat_params(ovp_ctx* c, const ovp_update_opts* o);
 // ovp_api_general.hip: argument checks of a general batch against the context's tables (host only); only != nullptr: features with
 // only[f] == 0 are not looked at
-int check_general_batch(const ovp_ctx* c, const ovp_general_batch* b, bool need_p, const int* only = nullptr);
+// any_length: the batch of ovp_plane_fit_refine - uv is not read and n_meas is bounded by max_meas only
+int check_general_batch(const ovp_ctx* c, const ovp_general_batch* b, bool need_p, const int* only = nullptr, bool any_length = false);
 int ovp_fetch_to_hres(ovp_ctx* c, const void* dsrc, size_t bytes, hipStream_t s);  // device block -> c->pl_hres, waited for (ovp_api_plane.hip)
 int chol_of_P(ovp_ctx* c, hipStream_t s);
 hipError_t chol_of_T(ovp_ctx* c, const double* T, int n, int ld, int add_identity, const int* cond, hipStream_t s);

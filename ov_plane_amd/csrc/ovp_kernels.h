@@ -166,9 +166,65 @@ struct ColMap {
   int pad;
 };
 
+// ovp_plane_fit_refine (k_planefit.hip): every pointer is device memory.  Features / planes / observation items are counted over the
+// whole call: F = feat_start[n_planes], O = sum of n_meas.
+struct PlaneFrontJob {
+  int n_planes, n_free;         // planes of the call; free planes among them (the RANSAC's grid)
+  int n_clones, n_cams, max_meas;
+  int refine;                   // 0: poses + RANSAC only
+  // pose table
+  const double* clone_R;        // [n_clones][9] R_GtoI
+  const double* clone_p;        // [n_clones][3] p_IinG
+  const double* cam_cal;        // [n_cams][20]: R_ItoC (9), p_IinC (3), intrinsics
+  double* poses;                // [n_clones][n_cams][12] out: R_GtoC, p_CinG
+  // RANSAC over the free planes (compacted: free plane r owns the points [rs_feat_start[r], rs_feat_start[r+1]))
+  const int* rs_feat_start;     // [n_free + 1]
+  const double* rs_pts;         // [free features][3]
+  const int* rs_sets;           // [n_free][200][5]
+  int min_inlier_num;
+  double max_cond;
+  double* rs_abcd;              // [n_free][4] out
+  unsigned char* rs_inlier;     // [free features] out
+  unsigned char* rs_ok;         // [n_free] out
+  // link
+  const int* feat_start;        // [n_planes + 1]
+  const int* free_slot;         // [n_planes] index among the free planes, -1 = in-state plane
+  const int* n_meas;            // [F]
+  const int* clone_idx;         // [F][max_meas]
+  const int* cam_idx;           // [F][max_meas]
+  const float* uvn;             // [F][max_meas][2]
+  const double* p_in;           // [F][3]
+  const double* cp_in;          // [n_planes][3]
+  const unsigned char* fix_plane;  // [n_planes]
+  int* c_feat_start;            // [n_planes + 1] the refinement's lists: compacted features ...
+  double* c_p0;                 // [F][3]
+  int* c_n_obs;                 // [F]
+  int* c_src;                   // [F] input index of a compacted feature
+  int* item_start;              // [n_planes + 1] ... and observation items
+  int* item_ob;                 // [O]
+  int* item_lf;                 // [O]
+  int* feat_item0;              // [F]
+  double* it_uv;                // [O][2]
+  double* it_R;                 // [O][9]
+  double* it_p;                 // [O][3]
+  double* cp0;                  // [n_planes][3]
+  // refinement
+  double sigma_px_norm, sigma_c;
+  double R_GtoC[9], p_CinG[3];  // current camera
+  double* cp_out;               // [n_planes][3]
+  double* c_p_out;              // [F][3] compacted index
+  unsigned char* c_kept;        // [F] compacted index
+  unsigned char* ok;            // [n_planes]
+  int* iterations;              // [n_planes]
+};
+
 }  // namespace ovp
 
 extern "C" {
+// k_planefit.hip: the device sequence of ovp_plane_fit_refine, enqueued on `stream`; the hypothesis sets of one plane's RANSAC
+// (PlaneFitting.cpp:104-141; dst [200][5], -1 = the call fails at that iteration)
+hipError_t ovp_launch_planefront(const ovp::PlaneFrontJob* j, hipStream_t stream);
+void ovp_planefit_sets(const double* pts, int n, int min_inlier_num, int shuffle_variant, int* dst);
 hipError_t ovp_launch_feat_gate(const ovp::FeatParams* p, hipStream_t stream);
 int ovp_feat_chol_supported(const ovp::FeatParams* p, int n);
 int ovp_feat_chol_side_capacity(void);

@@ -23,7 +23,7 @@ def lib():
 
 
 def run_msckf_update(sc, triangulate=False, fit_planes=None, comm=None, rank=0, world=1, device=0, general_features=False,
-                     general_planes=False):
+                     general_planes=False, fused_plane_fit=False):
     """Drives ov_plane::UpdaterMSCKF::update (C++ host classes over the C-ABI) on a synth.Scene.
     triangulate=True: the features carry uvs_norm and no position; the updater triangulates them first.
     fit_planes=dict(min_feat, max_cond, variant): no plane estimates are handed over - the updater fits the planes that are
@@ -33,8 +33,11 @@ def run_msckf_update(sc, triangulate=False, fit_planes=None, comm=None, rank=0, 
     general_features: StateOptions::gpu_general_features - the features the device batch cannot carry (another camera, a track
     longer than OVP_MAX_MEAS) are triangulated and gated on the device (ovp_triangulate_general / ovp_msckf_general_features).
     general_planes: StateOptions::gpu_general_planes - on-plane features of that kind stay in the plane loop
-    (ovp_msckf_plane_update_general) instead of going to the point update without their plane constraint."""
+    (ovp_msckf_plane_update_general) instead of going to the point update without their plane constraint.
+    fused_plane_fit: StateOptions::gpu_fused_plane_fit - with fit_planes, every plane of the frame is fitted and refined by one
+    ovp_plane_fit_refine call, over on-plane features of any camera and any track length."""
     L = lib()
+    L.ovph_set_fused_plane_fit(1 if fused_plane_fit else 0)
     L.ovph_set_general_features(1 if general_features else 0)
     L.ovph_set_general_planes(1 if general_planes else 0)
     cam1 = sc.get("cam1", None)  # synth.make_stereo_scene: dict(calib_q, calib_p, intr), sc.cam_idx [F, M]
@@ -131,7 +134,8 @@ ROUTE_NONE, ROUTE_DEVICE_GENERAL, ROUTE_DEVICE_MONO, ROUTE_DENSE_HOST, ROUTE_HOS
 
 
 def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=None, slam=None, slam_rep=None,
-                feat_rep_slam=None, general_slam=False, triangulate=False, dinit_planes=False, state_planes=False):
+                feat_rep_slam=None, general_slam=False, triangulate=False, dinit_planes=False, state_planes=False,
+                fused_plane_fit=False):
     """Drives the C++ host mirrors on a synth scene.
     fit_planes=dict(min_feat, max_cond, variant) (mode "plane_init" only): the features carry normalised measurements and
     no position, no plane estimates are handed over - init_vio_plane triangulates, fits and refines itself.
@@ -151,6 +155,7 @@ def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=
     """
     L = lib()
     L.ovph_set_general_slam(1 if general_slam else 0)
+    L.ovph_set_fused_plane_fit(1 if fused_plane_fit else 0)  # StateOptions::gpu_fused_plane_fit (mode "plane_init" with fit_planes)
     L.ovph_set_dinit_planes(1 if dinit_planes else 0)
     pnp_keep = None
     if state_planes:

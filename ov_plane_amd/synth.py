@@ -903,6 +903,116 @@ def make_planefit_problem(seed=0, n_feats=24, n_obs=9, n_slam=0, ragged=True, ou
     )
 
 
+def _mm3(A, B):
+    """3 x 3 product with elementwise operations only (no BLAS: the same bits wherever the generator runs)."""
+    return A[:, 0:1] * B[0:1, :] + A[:, 1:2] * B[1:2, :] + A[:, 2:3] * B[2:3, :]
+
+
+def _mv3(A, v):
+    return A[:, 0] * v[0] + A[:, 1] * v[1] + A[:, 2] * v[2]
+
+
+def make_plane_frontend_scene(C=11, planes=None, seed=0, baseline=0.11, px_noise=0.25, sigma_px=1.0, focal=458.0, pt_noise=0.02,
+                              cp_noise=0.01, sigma_c=0.05, min_inlier_num=5, max_cond=200.0):
+    """A frame in front of the plane path (update/UpdaterMSCKF.cpp:262-401): the on-plane features of several planes with their
+    triangulated positions and normalised measurements, seen by a stereo pair from a window of C clones - the input of
+    ovp_plane_fit_refine.  planes = list of dicts, one per plane:
+        n         features (default 12)            kind   "free" (default), "fixed" (in the state), "scatter" (points that are on no
+        outliers  of them off the plane                    plane: the RANSAC fails), "noisy" (pixel noise at the Cauchy scale: the
+        n_slam    SLAM landmarks (no measurements)         refinement does not converge)
+        stereo    features also seen by camera 1   short  features with a camera-0 track of 2 .. 4 views only (the others are
+        cam1only  features seen by camera 1 only          seen by every clone: up to 2 C views for a stereo feature)
+    Observation k of feature f is [f, k] of clone_idx / cam_idx / uv_norm (camera 0's clones ascending, then camera 1's).
+    Bit-reproducible: numpy's Generator and elementwise arithmetic only."""
+    rng = np.random.default_rng(seed)
+    if planes is None:
+        planes = [dict(n=14, outliers=2, stereo=5), dict(n=10, kind="fixed", n_slam=2, stereo=3), dict(n=12, kind="scatter"),
+                  dict(n=3), dict(n=12, kind="noisy"), dict(n=16, stereo=6, cam1only=2, short=4)]
+    # the window: IMU poses moving sideways, looking along +z; extrinsics of the two cameras
+    RI, pI = [], []
+    for k in range(C):
+        ang = 0.03 * (k - C / 2) + 0.01 * rng.standard_normal()
+        RI.append(_mm3(_mm3(rotz(0.02 * rng.standard_normal()), roty(ang)), rotx(0.01 * rng.standard_normal())))
+        pI.append(np.array([0.08 * k - 0.3, 0.02 * np.sin(k), 0.01 * k]) + 0.01 * rng.standard_normal(3))
+    RI, pI = np.array(RI), np.array(pI)
+    clone_q = np.array([rot_2_quat(R) for R in RI])
+    RI = np.array([quat_2_rot(q) for q in clone_q])  # (the rotation the quaternion stands for)
+    cal_q = [rot_2_quat(_mm3(rotz(0.01), rotx(-0.008))), rot_2_quat(_mm3(roty(0.012), rotx(0.006)))]
+    cal_p = [np.array([0.02, -0.01, 0.005]), np.array([0.02 - baseline, -0.012, 0.004])]
+    Rc = [quat_2_rot(q) for q in cal_q]
+    # camera poses (clone, camera): R_GtoC = R_ItoC R_GtoI, p_CinG = p_IinG - R_GtoC^T p_IinC
+    R_GtoC = np.zeros((C, 2, 3, 3))
+    p_CinG = np.zeros((C, 2, 3))
+    for k in range(C):
+        for c in range(2):
+            R_GtoC[k, c] = _mm3(Rc[c], RI[k])
+            p_CinG[k, c] = pI[k] - _mv3(R_GtoC[k, c].T, cal_p[c])
+    M = 2 * C
+    fs, P_true, P0, nmeas, cidx, cam, uvn, is_short, sees1, kinds, cp_true_all, cp0_all, fix = [0], [], [], [], [], [], [], [], [], [], [], [], []
+    for ip, spec in enumerate(planes):
+        n, kind = int(spec.get("n", 12)), spec.get("kind", "free")
+        nrm = np.array([0.2, 0.1, 1.0]) + 0.2 * rng.standard_normal(3)
+        nrm /= np.sqrt((nrm * nrm).sum())
+        dist = 3.5 + 0.5 * rng.random()
+        cp_true = nrm * dist
+        a = np.cross(nrm, [1.0, 0.0, 0.0])
+        a /= np.sqrt((a * a).sum())
+        b = np.cross(nrm, a)
+        st = rng.uniform(-1.2, 1.2, size=(n, 2))
+        p_true = cp_true[None, :] + st[:, :1] * a[None, :] + st[:, 1:] * b[None, :]
+        if kind == "scatter":
+            p_true = rng.uniform(-1.5, 1.5, size=(n, 3)) + np.array([0.0, 0.0, 5.0])
+        for k in range(int(spec.get("outliers", 0))):
+            p_true[n - 1 - k] += nrm * (0.25 + 0.1 * k) * (1 if k % 2 else -1)
+        n_slam, n_st, n_c1, n_sh = (int(spec.get(k, 0)) for k in ("n_slam", "stereo", "cam1only", "short"))
+        act_n = (4.0 * sigma_px if kind == "noisy" else px_noise) / focal
+        for f in range(n):
+            slam = f < n_slam
+            st1 = (not slam) and n_slam <= f < n_slam + n_st          # both cameras
+            only1 = (not slam) and n_slam + n_st <= f < n_slam + n_st + n_c1
+            short = (not slam) and f >= n - n_sh
+            obs = []
+            if not slam and not only1:
+                if short:
+                    m0 = int(rng.integers(2, 5))
+                    k0 = int(rng.integers(0, C - m0 + 1))
+                    obs += [(k, 0) for k in range(k0, k0 + m0)]
+                else:
+                    obs += [(k, 0) for k in range(C)]
+            if st1 or only1:
+                obs += [(k, 1) for k in range(C)]
+            row_c, row_cam, row_uv = np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.int32), np.zeros((M, 2), dtype=np.float32)
+            for i, (k, c) in enumerate(obs):
+                pc = _mv3(R_GtoC[k, c], p_true[f] - p_CinG[k, c])
+                row_c[i], row_cam[i] = k, c
+                row_uv[i] = np.float32(pc[:2] / pc[2] + act_n * rng.standard_normal(2))  # stored as f32 in the reference
+            nmeas.append(len(obs)); cidx.append(row_c); cam.append(row_cam); uvn.append(row_uv)
+            is_short.append(bool(short and not st1 and not only1)); sees1.append(bool(st1 or only1))
+        # estimates as a triangulation leaves them: mostly wrong along the viewing ray, little across it
+        ray = p_true - p_CinG[C // 2, 0][None, :]
+        ray /= np.sqrt((ray * ray).sum(axis=1, keepdims=True))
+        p0 = p_true + pt_noise * rng.standard_normal((n, 1)) * ray + 0.1 * pt_noise * rng.standard_normal((n, 3))
+        if n_slam:
+            p0[:n_slam] = p_true[:n_slam] + 0.005 * rng.standard_normal((n_slam, 3))
+        P_true.append(p_true); P0.append(p0); kinds.append(kind)
+        cp_true_all.append(cp_true); cp0_all.append(cp_true + cp_noise * rng.standard_normal(3)); fix.append(kind == "fixed")
+        fs.append(fs[-1] + n)
+    N = 15 + 6 * C + 28
+    ids = dict(clones=np.array([15 + 6 * k for k in range(C)], dtype=np.int32), calib=15 + 6 * C, intr=15 + 6 * C + 6,
+               calib1=15 + 6 * C + 14, intr1=15 + 6 * C + 20)
+    intr = np.array([focal, focal, 367.215, 248.375, -0.28, 0.07, 0.0002, 0.00002])
+    return Scene(
+        C=C, N=N, ids=ids, F=fs[-1], n_planes=len(planes), kinds=kinds, feat_start=np.array(fs, dtype=np.int32),
+        clone_q=clone_q, clone_p=pI.copy(), clone_q_fej=clone_q.copy(), clone_p_fej=pI.copy(),
+        calib_q=cal_q[0], calib_p=cal_p[0], intr=intr, cam1=dict(calib_q=cal_q[1], calib_p=cal_p[1], intr=intr.copy()),
+        R_GtoC=R_GtoC, p_CinG=p_CinG, n_meas=np.array(nmeas, dtype=np.int32), clone_idx=np.array(cidx), cam_idx=np.array(cam),
+        uv_norm=np.array(uvn), uv=np.zeros((fs[-1], M, 2), dtype=np.float32), p_FinG=np.ascontiguousarray(np.concatenate(P0)),
+        p_true=np.concatenate(P_true), cp=np.array(cp0_all), cp_true=np.array(cp_true_all), fix_plane=np.array(fix),
+        is_short=np.array(is_short), sees_cam1=np.array(sees1), sigma_px_norm=float(sigma_px / focal), sigma_c=float(sigma_c),
+        min_inlier_num=int(min_inlier_num), max_cond=float(max_cond), R_GtoI=RI[-1].copy(), p_IinG=pI[-1].copy(),
+    )
+
+
 def slam_rows_on_planes(sc, k_rows, seed=1):
     """SLAM landmarks of a make_scene(n_slam=..., n_planes=...) state placed on its out-of-state planes: the extra rows of
     the MSCKF plane update (update/UpdaterMSCKF.cpp:232-252).  Returns dict(plane [k] 1-based, id [k], p [k,3], p_fej [k,3])."""

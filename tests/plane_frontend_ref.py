@@ -1,0 +1,103 @@
+"""TEST INFRASTRUCTURE ONLY - the front end of the plane path (update/UpdaterMSCKF.cpp:262-401) chained from the oracle's pieces,
+plane by plane: oracle.plane_fitting -> cp = -n d -> oracle.optimize_plane on the inliers in their order, with the camera pose of
+every observation handed in as a table [n_clones, n_cams, 12] (R_GtoC row-major, p_CinG).  The same chain over the device's
+per-plane pair of calls (ovp_plane_fitting, ovp_plane_optimize) is what ovp_plane_fit_refine must reproduce bit for bit.
+
+Also: the pose table in numpy, and the arguments of Context.plane_fit_refine from a synth.make_plane_frontend_scene scene."""
+from __future__ import annotations
+
+import numpy as np
+
+from ov_plane_amd.synth import quat_2_rot
+
+
+def pose_table(sc):
+    """[C, n_cams, 12] from the scene's quaternions: R_GtoC = R_ItoC R_GtoI, p_CinG = p_IinG - R_GtoC^T p_IinC."""
+    cams = [(sc.calib_q, sc.calib_p)] + ([(sc.cam1["calib_q"], sc.cam1["calib_p"])] if "cam1" in sc else [])
+    T = np.zeros((sc.C, len(cams), 12))
+    for k in range(sc.C):
+        RI = quat_2_rot(sc.clone_q[k])
+        for c, (q, p) in enumerate(cams):
+            R = quat_2_rot(q) @ RI
+            T[k, c, :9] = R.reshape(-1)
+            T[k, c, 9:] = sc.clone_p[k] - R.T @ np.asarray(p)
+    return T
+
+
+def plane_problem(sc, feats, poses, cp, fix_plane, cams=None, max_views=None):
+    """The ovp_plane_optimize / oracle.optimize_plane problem of the features `feats` (scene indices, in order).  cams: keep only
+    the observations of these cameras; max_views: drop features with more views (what the camera-0 device batch can carry)."""
+    feats = [int(f) for f in feats]
+    uv, Rc, pc, n_obs = [], [], [], []
+    for f in feats:
+        m = 0
+        for k in range(int(sc.n_meas[f])):
+            c, cam = int(sc.clone_idx[f, k]), int(sc.cam_idx[f, k])
+            if cams is not None and cam not in cams:
+                continue
+            uv.append(np.asarray(sc.uv_norm[f, k], dtype=np.float64))
+            Rc.append(poses[c, cam, :9])
+            pc.append(poses[c, cam, 9:])
+            m += 1
+        n_obs.append(m)
+    n_obs = np.array(n_obs, dtype=np.int32).reshape(-1)
+    obs_start = np.zeros(len(feats), dtype=np.int32)
+    if len(feats) > 1:
+        obs_start[1:] = np.cumsum(n_obs)[:-1]
+    R0 = quat_2_rot(sc.calib_q)
+    return dict(n_feats=len(feats), p_FinG=np.asarray(sc.p_FinG[feats], dtype=np.float64).reshape(-1, 3), obs_start=obs_start, n_obs=n_obs,
+                uv_norm=np.array(uv, dtype=np.float64).reshape(-1, 2), R_GtoC=np.array(Rc, dtype=np.float64).reshape(-1, 9),
+                p_CinG=np.array(pc, dtype=np.float64).reshape(-1, 3), cp=np.asarray(cp, dtype=np.float64), fix_plane=bool(fix_plane),
+                sigma_px_norm=sc.sigma_px_norm, sigma_c=sc.sigma_c, R_GtoI=sc.R_GtoI, p_IinG=sc.p_IinG, R_ItoC=R0,
+                p_IinC=np.asarray(sc.calib_p, dtype=np.float64))
+
+
+def chain(sc, poses, fit, optimize, refine=True, variant=0, select=None):
+    """The loop of update/UpdaterMSCKF.cpp:262-401 over the scene's planes.  fit(pts, min_inlier_num, max_cond, variant) ->
+    dict(ok, abcd, inlier); optimize(problem) -> dict(ok, cp, p_FinG, kept, iterations) (the oracle's functions, or the device's
+    per-plane calls).  select(f) -> bool restricts the features that take part (default: all).  Returns the outputs of
+    ovp_plane_fit_refine: fit_ok, abcd, ok, cp, iterations per plane; inlier, kept, p_FinG per feature."""
+    P, F = sc.n_planes, sc.F
+    out = dict(fit_ok=np.zeros(P, dtype=bool), abcd=np.zeros((P, 4)), ok=np.zeros(P, dtype=bool), cp=np.array(sc.cp, dtype=np.float64),
+               iterations=np.zeros(P, dtype=np.int32), inlier=np.zeros(F, dtype=bool), kept=np.zeros(F, dtype=bool),
+               p_FinG=np.array(sc.p_FinG, dtype=np.float64))
+    for k in range(P):
+        feats = [f for f in range(int(sc.feat_start[k]), int(sc.feat_start[k + 1])) if select is None or select(f)]
+        fixed = bool(sc.fix_plane[k])
+        if fixed:  # :265-316
+            out["fit_ok"][k] = True
+            out["inlier"][feats] = True
+            cp0 = np.array(sc.cp[k], dtype=np.float64)
+        else:
+            if len(feats) < 4:  # :320-321
+                continue
+            r = fit(sc.p_FinG[feats], sc.min_inlier_num, sc.max_cond, variant)
+            if not r["ok"]:
+                continue
+            out["fit_ok"][k] = True
+            out["abcd"][k] = r["abcd"]
+            feats = [f for f, i in zip(feats, r["inlier"]) if i]  # PlaneFitting.cpp:190
+            out["inlier"][feats] = True
+            cp0 = -r["abcd"][:3] * r["abcd"][3]  # :352
+        if not refine:
+            out["ok"][k], out["cp"][k] = True, cp0
+            out["kept"][feats] = True
+            continue
+        o = optimize(plane_problem(sc, feats, poses, cp0, fixed))
+        out["iterations"][k] = o["iterations"]
+        if not o["ok"]:
+            continue
+        out["ok"][k], out["cp"][k] = True, o["cp"]
+        for f, kp, p in zip(feats, o["kept"], o["p_FinG"]):
+            if kp:
+                out["kept"][f] = True
+                out["p_FinG"][f] = p
+    return out
+
+
+def fused_args(sc, **over):
+    a = dict(feat_start=sc.feat_start, uv_norm=sc.uv_norm, clone_idx=sc.clone_idx, cam_idx=sc.cam_idx, n_meas=sc.n_meas, p_FinG=sc.p_FinG,
+             cp=sc.cp, fix_plane=sc.fix_plane, min_inlier_num=sc.min_inlier_num, max_cond=sc.max_cond, sigma_px_norm=sc.sigma_px_norm,
+             sigma_c=sc.sigma_c, R_GtoI=sc.R_GtoI, p_IinG=sc.p_IinG, n_clones=sc.C, n_cams=2)
+    a.update(over)
+    return a
