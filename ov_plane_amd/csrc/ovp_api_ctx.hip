@@ -223,8 +223,8 @@ extern "C" int ovp_ctx_destroy(ovp_ctx* c) {
   hipStreamSynchronize(c->stream2);
   void* dev[] = {c->P, c->P_tmp, c->Ab, c->L, c->W1, c->T, c->Lt, c->Y, c->res_block, c->ticket, c->uvn, c->tri_ok, c->state_block, c->batch_block,
                  c->chi2_table, c->G, c->Bscr, c->rec, c->gramS, c->gramR, c->Dinv, c->Ltp, c->part, c->idbuf, c->smallbuf, c->Hd, c->Acc,
-                 c->bcc, c->resd, c->pl_slam_i, c->pl_slam_d, c->sub_ids, c->sub_buf, c->pl_Tbuf, c->pl_crow, c->pl_dxlast,
-                 c->pl_cur, c->pl_perm, c->pl_range_done, c->pl_used, c->pl_dstage, c->pl_xbuf, c->pl_xy, c->pl_xflag, c->pl_Asum,
+                 c->bcc, c->resd, c->sub_ids, c->sub_buf, c->pl_Tbuf, c->pl_crow, c->pl_dxlast,
+                 c->pl_cur, c->pl_range_done, c->pl_used, c->pl_dstage, c->pl_xbuf, c->pl_xy, c->pl_xflag, c->pl_Asum,
                  c->pl_U, c->pl_sub_tab, c->Lkeep, c->slam_res, c->slam_hscr, c->dinit_buf, c->boost, c->boost_vec,
                  c->gen_cal, c->gen_buf, c->pl_gen_dev};
   for (void* p : dev)
@@ -562,16 +562,8 @@ extern "C" int ovp_cov_propagate(ovp_ctx* c, int new_start, int phi_size, const 
     const unsigned seq = ++c->prop_seq;
     HIPCHK(ovp_launch_propagate_publish(c->P, c->ld, n, new_start, phi_size, (const int*)((char*)ad + o_id), nold, dPhi, dQ, dCPT, dPCP,
                                         c->flags + 1, hw_dev, seq, c->stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (__atomic_load_n((const unsigned*)hw, __ATOMIC_ACQUIRE) != seq) {
-      if ((++spins & 0xFFFu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-        HIPCHK(hipStreamSynchronize(c->stream));  // error path: surface a fault instead of spinning forever
-        if (__atomic_load_n((const unsigned*)hw, __ATOMIC_ACQUIRE) != seq) return OVP_E_STATE;
-        break;
-      }
-      __builtin_ia32_pause();
-    }
+    const int rw = ovp_wait_seq(hw, seq, c->stream);
+    if (rw) return rw;
     const int neg = (int)hw[1];
     if (neg_diag) *neg_diag = neg;
     return neg ? OVP_E_NEGDIAG : 0;
@@ -673,7 +665,7 @@ extern "C" int ovp_cov_initialize(ovp_ctx* c, const double* Hx_init, const doubl
   const size_t oHt = 0, oHi = oHt + (size_t)cols * m, oRk = oHi + 36, oRes = oRk + 36, oId = oRes + rup + 8;
   const size_t bytes = oId * sizeof(double) + sizeof(int) * (size_t)cols + 64;
   const size_t res_doubles = 4 + (size_t)c->n_max + 8;
-  int rc = plane2_buffers(c, 0, bytes, res_doubles * sizeof(double));  // the plane loop's pinned staging and result blocks
+  int rc = plane2_buffers(c, bytes, res_doubles * sizeof(double));  // the plane loop's pinned staging and result blocks
   if (rc) return rc;
   double* h = (double*)c->pl_hstage;
   double* d = (double*)c->pl_dstage;

@@ -35,10 +35,6 @@ static int plane_job_device(ovp_ctx* c, const ovp_update_opts* o, const ovp::Fea
   HIPCHK(ovp_launch_syrk(c->G, 3 * nf, ldg, n + 4, nsplit, c->part, s));
   HIPCHK(ovp_launch_reduce_cst(c->pl_cst, nf, c->pl_cstsum, s));
   HIPCHK(ovp_launch_assemble_ext(c->gramR, fp.n_clones, c->part, nsplit, c->colmap, n, sid, c->pl_cstsum, c->pl_E, ldg, s));
-  if (!in_state && c->pl_n_slam > 0)  // landmarks lying on this plane: one constraint row each (UpdaterMSCKF.cpp:545-552)
-    HIPCHK(ovp_launch_plane_slam_rows(c->pl_E, ldg, n, pl + 1, c->pl_n_slam, c->pl_slam_i, c->pl_slam_i + c->pl_slam_cap,
-                                      c->pl_slam_d, c->pl_slam_d + 3 * (size_t)c->pl_slam_cap, c->pl_cp + 3 * pl,
-                                      c->pl_cp_fej + 3 * pl, white_c, fp.do_fej, c->pl_cstsum, s));
   HIPCHK(ovp_launch_plane_reduce_to_state(c->pl_E, ldg, n, in_state, c->Ab, ld, c->pl_cstsum + 9, c->pl_scal, s));
   // range part of the residual (regularised, diagonally normalised): its own Cholesky, independent of the update's -
   // side stream, joined before the gate (the two write different words of pl_scal)
@@ -89,22 +85,38 @@ static int plane_buffers(ovp_ctx* c, int NP) {
   return 0;
 }
 
-// ---- UpdaterMSCKF::update, per-plane loop (second generation) ------------------------------------------------------------
-// See k_plane2.hip for the algebra.  Everything of a call is enqueued without a host synchronisation: the per-call tables go
-// through one pinned staging block, the results come back through one pinned block read after a single stream sync.
+// ---- UpdaterMSCKF::update, per-plane loop (second generation): the host structures, the result kernels, the buffers; the loop itself
+// (plane_loop) is further down, behind the column-order route into it ----
 struct PlaneJobH { int pl, start, nf, rows_total, rows_live, rows_u, n_involved, in_state, sid, n_inv_cols, ns_pl; double thr;
                    int g_start, ng; /* general features: range in the list of the call */ };
 
-// column of calibration column k of camera `cam` (ovp_cameras_upload) in the running loop's column order
-static inline int gen_cam_col(const ovp_ctx* c, int cam, int k) {
+// What tells the routes into the plane loop apart, as arguments: ovp_msckf_plane_update and ovp_msckf_plane_update_general fill in the
+// general batch, plane_update_ordered the column order, the retry on a positive semi-definite prior sets psd.  None of it is kept in
+// the context, so no call can leave any of it behind for the next.
+struct PlaneLoopView {
+  bool ordered = false;               // the loop runs in its own column order (plane_update_ordered: remapped tables, c->P = permuted copy)
+  bool marginal = false;              // ... on a marginal: the rest of the state follows by push-through (k_plane_sub_accum per plane)
+  const int* nl = nullptr;            // ordered: [plane] leading columns involved up to and including that plane (loop order)
+  double* scatter_dst = nullptr;      // full order: where the covariance product of the loop is un-permuted to
+  const int* scatter_ids = nullptr;   // ... and the inverse id table (device) for that
+  bool boost = false;                 // full order: the columns behind the involved ones carry the diagonal boost (c->boost_vec)
+  double t_entry = 0.0;               // host clock at the entry point (ovp_host_timing)
+  bool psd = false;                   // second attempt of a loop whose chol(P) failed: pivot-dropping factor of the PSD prior
+  const ovp_general_batch* gen = nullptr;  // general on-plane features (k_plane_feat_gen.hip), nullptr = none
+  const int* plane_of_gen = nullptr;  // [gen->n_feats] 1-based plane slot, 0 = not on a plane
+  const int* gen_pos = nullptr;       // [n_state] state column -> column in the loop's order, nullptr = identity
+  int n_state = 0;
+  unsigned char* gen_used = nullptr;  // [gen->n_feats] out: consumed by an accepted plane
+};
+// the caller's result arrays of a plane entry point (each may be nullptr)
+struct PlaneOut { double* dx_planes; uint8_t* plane_ok; double* plane_chi2; int* plane_dof; uint8_t* feat_used; };
+
+// column of calibration column k of camera `cam` (ovp_cameras_upload) in the loop's column order (pos: PlaneLoopView::gen_pos)
+static inline int gen_cam_col(const ovp_ctx* c, const int* pos, int n_pos, int cam, int k) {
   const int id = k < 6 ? c->gen_calib_id[cam] + k : c->gen_intr_id[cam] + (k - 6);
-  if (c->pl_gen_pos.empty()) return id;
-  return (id >= 0 && id < (int)c->pl_gen_pos.size()) ? c->pl_gen_pos[id] : -1;
+  if (!pos) return id;
+  return (id >= 0 && id < n_pos) ? pos[id] : -1;
 }
-
-extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, double* dx_planes,
-                                      uint8_t* plane_ok, double* plane_chi2, int* plane_dof, uint8_t* feat_used);
-
 // The plane loop's results go to the host as the point update's do (ovp_api_point.hip: k_publish_results): ONE kernel behind the
 // loop writes [chi2, decision, ... per plane | dx per plane | consumed features | flags] into mapped pinned memory and then a
 // sequence number the host spins on - instead of four copy commands (a blit kernel of ~4 us each on the stream) and a stream
@@ -161,25 +173,14 @@ int ovp_fetch_to_hres(ovp_ctx* c, const void* dsrc, size_t bytes, hipStream_t s)
   hipLaunchKernelGGL(k_fetch_block, dim3(1), dim3(1024), 0, s, (const unsigned char*)dsrc, (unsigned char*)c->pl_hres_dev, (int)bytes,
                      (volatile unsigned*)((char*)c->pl_hres_dev + o_seq), seq);
   HIPCHK(hipGetLastError());
-  const auto t0 = std::chrono::steady_clock::now();
-  unsigned spins = 0;
-  while (__atomic_load_n((const unsigned*)hseq, __ATOMIC_ACQUIRE) != seq) {
-    if ((++spins & 0xFFFu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-      HIPCHK(hipStreamSynchronize(s));  // error path: surface a fault instead of spinning forever
-      if (__atomic_load_n((const unsigned*)hseq, __ATOMIC_ACQUIRE) != seq) return OVP_E_STATE;
-      break;
-    }
-    __builtin_ia32_pause();
-  }
-  return 0;
+  return ovp_wait_seq(hseq, seq, s);
 }
-
 static int ensure_pl_used(ovp_ctx* c) {
   if (!c->pl_used) HIPCHK(hipMalloc((void**)&c->pl_used, (size_t)c->f_max + 16));
   return 0;
 }
 
-int plane2_buffers(ovp_ctx* c, int NP, size_t stage_bytes, size_t res_bytes) {
+int plane2_buffers(ovp_ctx* c, size_t stage_bytes, size_t res_bytes) {
   const int ld = c->ld;
   if (!c->pl_Tbuf) {
     const size_t nn = (size_t)(c->n_max + 1) * ld;
@@ -193,11 +194,6 @@ int plane2_buffers(ovp_ctx* c, int NP, size_t stage_bytes, size_t res_bytes) {
     HIPCHK(dalloc(&c->pl_xy, (size_t)c->n_max + 32));
     HIPCHK(hipMalloc((void**)&c->pl_xflag, sizeof(unsigned) * 64));
     HIPCHK(hipMemset(c->pl_xflag, 0, sizeof(unsigned) * 64));
-  }
-  if (NP > c->pl2_cap) {
-    if (c->pl_perm) hipFree(c->pl_perm);
-    c->pl2_cap = NP + 8;
-    HIPCHK(hipMalloc((void**)&c->pl_perm, sizeof(int) * (size_t)c->pl2_cap * c->n_max));
   }
   if (stage_bytes > c->pl_stage_cap) {
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -311,6 +307,80 @@ static void sub_leave(ovp_ctx* c, const SubSaved& sv) {
   c->h_clone_id = sv.h_clone_id;
 }
 
+static hipError_t ensure_events(std::vector<hipEvent_t>& ev, size_t count) {  // the kernel timers' events, created on first use
+  while (ev.size() < count) {
+    hipEvent_t e;
+    if (hipError_t err = hipEventCreate(&e)) return err;
+    ev.push_back(e);
+  }
+  return hipSuccess;
+}
+
+// sub_enter / sub_leave as a scope: every way out restores the context's view of the state (refill: and the feature parameters'
+// calibration columns with it)
+struct SubScope {
+  ovp_ctx* c;
+  const ovp_update_opts* refill;
+  SubSaved sv;
+  bool in = false;
+  void enter(const SubTables& t, int ns, double* Psub) {
+    sv = sub_enter(c, t, ns, Psub);
+    in = true;
+  }
+  int leave() {
+    if (!in) return 0;
+    in = false;
+    sub_leave(c, sv);
+    return refill ? fill_feat_params(c, refill) : 0;
+  }
+  ~SubScope() { (void)leave(); }
+};
+
+// A column order by first involvement: ids = the state columns in that order, pos = its inverse (-1 = not placed).
+struct ColumnOrder {
+  int n;  // state size the ids are checked against
+  std::vector<int> ids, pos;
+  bool bad_id = false;
+  ColumnOrder(int n_, int pos_size) : n(n_), pos((size_t)pos_size, -1) { ids.reserve((size_t)n_); }
+  void place(int id, int sz) {
+    if (id < 0 || id + sz > n) {
+      bad_id = true;
+      return;
+    }
+    for (int k = 0; k < sz; ++k)
+      if (pos[id + k] < 0) {
+        pos[id + k] = (int)ids.size();
+        ids.push_back(id + k);
+      }
+  }
+  void place_clones_and_calibration(const ovp_ctx* c, const ovp_update_opts* o) {
+    for (int i = 0; i < c->fp.n_clones; ++i) place(c->h_clone_id[i], 6);
+    if (o->do_calib_camera_pose) place(c->calib_id, 6);
+    if (o->do_calib_camera_intrinsics) place(c->intr_id, 8);
+  }
+};
+
+// The rest of the state behind an update on the selection s (ns columns, device ids d_ids) by the push-through identity:
+//   Lambda = A - A Pss+ A ;  P -= G Lambda G^T ;  dx = G u     (A = the pair accumulated in c->pl_Asum, G = P0[:, s])
+// push_through_lambda leaves Lambda in c->T and G in c->Y (the caller's dx product reads it there), push_through_commit updates P.
+static int push_through_lambda(ovp_ctx* c, const double* Pss_new, const int* d_ids, int ns, hipStream_t s) {
+  const int n = c->n, ld = c->ld;
+  HIPCHK(ovp_launch_gemm4(0, 0, ns, ns, ns, c->pl_Asum, ld, Pss_new, ld, c->W1, ld, 0, 0, s));
+  HIPCHK(ovp_launch_gemm4(0, 0, ns, ns, ns, c->W1, ld, c->pl_Asum, ld, c->T, ld, 0, 1, s));
+  HIPCHK(ovp_launch_mat_sub(c->pl_Asum, c->T, c->T, ns, ns, ld, s));
+  HIPCHK(ovp_launch_gather_cols(c->P, ld, d_ids, n, ns, c->Y, ld, s));
+  return 0;
+}
+static int push_through_commit(ovp_ctx* c, int ns, hipStream_t s) {
+  const int n = c->n, ld = c->ld;
+  HIPCHK(ovp_launch_gemm4(0, 0, n, ns, ns, c->Y, ld, c->T, ld, c->W1, ld, 0, 0, s));
+  HIPCHK(ovp_launch_gemm4(0, 1, n, n, ns, c->W1, ld, c->Y, ld, c->L, ld, 0, 1, s));
+  HIPCHK(ovp_launch_sub_sym(c->P, c->L, n, ld, s));
+  return 0;
+}
+
+static int plane_loop(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, const PlaneLoopView& v, const PlaneOut& out);
+
 // ---- the plane loop in the loop's own column order (update/UpdaterMSCKF.cpp:413-649 has no size limit) --------------------------
 // A plane's rows touch the clones, the calibration, its own closest point when it is a state variable and the SLAM landmarks lying
 // on it (out-of-state planes).  Two things follow:
@@ -323,46 +393,33 @@ static void sub_leave(ovp_ctx* c, const SubSaved& sv) {
 //  (2) SUB-STATE.  Above the factorization's limit (n > 287) the loop runs on the marginal P0[s, s] of the involved columns s
 //      (ns <= 287; same order) - same kernels, the state tables addressed through remapped column ids - and the rest of the state
 //      follows from the push-through identity (k_plane_sub_accum for dx, the point path's  P -= G (A - A Pss+ A) G^T  for P).
-static int plane_update_ordered(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, double* dx_planes,
-                                uint8_t* plane_ok, double* plane_chi2, int* plane_dof, uint8_t* feat_used) {
-  const double t_entry = host_now_ms();
-  const int n = c->n, ld = c->ld, NP = pb->n_planes, C = c->fp.n_clones;
+// vin: the entry's view (entry time, general features); the column order is added here.
+static int plane_update_ordered(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, const PlaneLoopView& vin,
+                                const PlaneOut& out) {
+  const int n = c->n, ld = c->ld, NP = pb->n_planes;
   const int n_slam = pb->n_slam > 0 ? pb->n_slam : 0;
   if (n_slam > 0 && (!pb->slam_plane || !pb->slam_state_id || !pb->slam_p || !pb->slam_p_fej)) return OVP_E_ARG;
   // ---- column order: first involvement ----
-  std::vector<int> ids, pos((size_t)n, -1);
-  ids.reserve((size_t)n);
-  bool bad_id = false;
-  auto place = [&](int id, int sz) {
-    if (id < 0 || id + sz > n) {
-      bad_id = true;
-      return;
-    }
-    for (int k = 0; k < sz; ++k)
-      if (pos[id + k] < 0) {
-        pos[id + k] = (int)ids.size();
-        ids.push_back(id + k);
-      }
-  };
-  for (int i = 0; i < C; ++i) place(c->h_clone_id[i], 6);
-  if (o->do_calib_camera_pose) place(c->calib_id, 6);
-  if (o->do_calib_camera_intrinsics) place(c->intr_id, 8);
-  if (c->pl_gen_b)  // general on-plane features: their cameras' calibration columns are involved, and every accepted plane corrects
+  ColumnOrder co(n, n);
+  std::vector<int>& ids = co.ids;
+  std::vector<int>& pos = co.pos;
+  co.place_clones_and_calibration(c, o);
+  if (vin.gen)  // general on-plane features: their cameras' calibration columns are involved, and every accepted plane corrects
     for (int k = 0; k < c->gen_ncams; ++k) {  // the table of every uploaded camera (k_plane_gen_commit) - all of them take part
-      if (o->do_calib_camera_pose) place(c->gen_calib_id[k], 6);
-      if (o->do_calib_camera_intrinsics) place(c->gen_intr_id[k], 8);
+      if (o->do_calib_camera_pose) co.place(c->gen_calib_id[k], 6);
+      if (o->do_calib_camera_intrinsics) co.place(c->gen_intr_id[k], 8);
     }
   for (int q = 0; q < n_slam; ++q)
     if (pb->slam_plane[q] < 1 || pb->slam_plane[q] > NP || pb->slam_state_id[q] < 0 || pb->slam_state_id[q] + 3 > n) return OVP_E_ARG;
-  c->pl_nl.assign((size_t)(NP > 0 ? NP : 1), 0);
+  std::vector<int> nl((size_t)(NP > 0 ? NP : 1), 0);
   for (int k = 0; k < NP; ++k) {
-    if (pb->plane_state_id[k] >= 0) place(pb->plane_state_id[k], 3);
+    if (pb->plane_state_id[k] >= 0) co.place(pb->plane_state_id[k], 3);
     else
       for (int q = 0; q < n_slam; ++q)
-        if (pb->slam_plane[q] == k + 1) place(pb->slam_state_id[q], 3);
-    c->pl_nl[k] = (int)ids.size();
+        if (pb->slam_plane[q] == k + 1) co.place(pb->slam_state_id[q], 3);
+    nl[k] = (int)ids.size();
   }
-  if (bad_id) return OVP_E_ARG;
+  if (co.bad_id) return OVP_E_ARG;
   const int n_inv = (int)ids.size();
   const bool full = n <= ovp_chol2_max_n();  // the whole state fits one factorization: the rest rides along behind the leading block
   if (!full && n_inv > ovp_chol2_max_n()) return OVP_E_CAPACITY;  // the planes of this call involve more columns than one factorization holds
@@ -392,11 +449,7 @@ static int plane_update_ordered(ovp_ctx* c, const ovp_update_opts* o, const ovp_
     slam_sub[q] = p0 >= 0 ? p0 : 0;
   }
   if (c->pl_ktimer) {
-    while (c->pl_ev_loop.size() < 2) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      c->pl_ev_loop.push_back(e);
-    }
+    HIPCHK(ensure_events(c->pl_ev_loop, 2));
     HIPCHK(hipEventRecord(c->pl_ev_loop[0], s));
   }
   // ---- remapped tables: [ids | inverse | clone ids | column map] ----
@@ -406,11 +459,20 @@ static int plane_update_ordered(ovp_ctx* c, const ovp_update_opts* o, const ovp_
     if (rt) return rt;
   }
   const int* d_ids = st.d_ids;
-  const int* d_inv = st.d_inv;
+  PlaneLoopView v = vin;
+  v.ordered = true;
+  v.marginal = !full;
+  v.nl = nl.data();
+  v.scatter_dst = full ? c->P : nullptr;  // full order: the loop's covariance product is un-permuted straight into the resident P
+  v.scatter_ids = st.d_inv;
+  if (vin.gen) {
+    v.gen_pos = pos.data();
+    v.n_state = n;
+  }
   // full order: the columns behind the involved ones take a diagonal boost that the un-permutation behind the loop takes off
   // again (k_gather_block_boost) - an exact stochastic clone then factors at the first attempt
-  c->pl_boost_active = full && n_inv < ns;
-  if (c->pl_boost_active) {
+  v.boost = full && n_inv < ns;
+  if (v.boost) {
     if (!c->boost_vec) HIPCHK(dalloc(&c->boost_vec, (size_t)c->n_max + 16));
     HIPCHK(ovp_launch_gather_block_boost(c->P, ld, d_ids, ns, c->P_tmp, ld, n_inv, 1e-9, c->boost_vec, s));
   } else {
@@ -425,103 +487,85 @@ static int plane_update_ordered(ovp_ctx* c, const ovp_update_opts* o, const ovp_
   pbs.plane_state_id = sid_sub.data();
   pbs.slam_state_id = slam_sub.data();
   std::vector<double> dx_sub((size_t)ns * (NP > 0 ? NP : 1), 0.0);
-  SubSaved sv = sub_enter(c, st, ns, c->P_tmp);
-  c->pl_sub_active = true;
-  c->pl_sub_rest = !full;
-  c->pl_scatter_dst = full ? sv.P : nullptr;  // full order: the loop's covariance product is un-permuted straight into the resident P
-  c->pl_scatter_ids = d_inv;
-  c->pl_t_entry = t_entry;
-  if (c->pl_gen_b) c->pl_gen_pos = pos;
-  const int rc = ovp_msckf_plane_update(c, o, &pbs, dx_sub.data(), plane_ok, plane_chi2, plane_dof, feat_used);
-  c->pl_gen_pos.clear();
-  c->pl_sub_active = false;
-  c->pl_sub_rest = false;
-  c->pl_scatter_dst = nullptr;
-  double* Pss_new = c->P;  // = P_tmp: the marginal after the loop
-  sub_leave(c, sv);
-  if (rc) return rc;  // the resident covariance was not touched (the device tables may have been: a loop that fails after
-                      // accepting planes has marked them invalid, have_state = false - INTEGRATION.md section 5)
-  if (full) {
-    if (dx_planes)
-      for (int k = 0; k < NP; ++k)
-        for (int i = 0; i < ns; ++i) dx_planes[(size_t)k * n + ids[i]] = dx_sub[(size_t)k * ns + i];
-    return 0;
+  double* const dx_planes = out.dx_planes;
+  {
+    SubScope sub{c, nullptr};
+    sub.enter(st, ns, c->P_tmp);
+    const PlaneOut out_sub{dx_sub.data(), out.plane_ok, out.plane_chi2, out.plane_dof, out.feat_used};
+    const int rc = plane_loop(c, o, &pbs, v, out_sub);
+    if (rc) return rc;  // the resident covariance was not touched (the device tables may have been: a loop that fails after
+                        // accepting planes has marked them invalid, have_state = false - INTEGRATION.md section 5)
   }
-  // ---- the rest of the state ----
-  // Lambda = Asum - Asum Pss+ Asum ;  P -= G Lambda G^T ;  dx_k = G u_k     (G = P0[:, s] in Y)
-  HIPCHK(ovp_launch_gemm4(0, 0, ns, ns, ns, c->pl_Asum, ld, Pss_new, ld, c->W1, ld, 0, 0, s));
-  HIPCHK(ovp_launch_gemm4(0, 0, ns, ns, ns, c->W1, ld, c->pl_Asum, ld, c->T, ld, 0, 1, s));
-  HIPCHK(ovp_launch_mat_sub(c->pl_Asum, c->T, c->T, ns, ns, ld, s));
-  HIPCHK(ovp_launch_gather_cols(c->P, ld, d_ids, n, ns, c->Y, ld, s));
-  if (dx_planes && NP > 0) {
-    // rows = planes: DX (NP x n) = U (NP x ns) G^T
-    HIPCHK(ovp_launch_gemm4(0, 1, NP, n, ns, c->pl_U, ld, c->Y, ld, c->Lt, ld, 0, 0, s));
-    HIPCHK(hipMemcpy2DAsync(dx_planes, sizeof(double) * n, c->Lt, sizeof(double) * ld, sizeof(double) * n, NP, hipMemcpyDeviceToHost, s));
+  if (!full) {
+    // ---- the rest of the state (c->P_tmp: the marginal after the loop) ----
+    if (const int r = push_through_lambda(c, c->P_tmp, d_ids, ns, s)) return r;
+    if (dx_planes && NP > 0) {
+      // rows = planes: DX (NP x n) = U (NP x ns) G^T
+      HIPCHK(ovp_launch_gemm4(0, 1, NP, n, ns, c->pl_U, ld, c->Y, ld, c->Lt, ld, 0, 0, s));
+      HIPCHK(hipMemcpy2DAsync(dx_planes, sizeof(double) * n, c->Lt, sizeof(double) * ld, sizeof(double) * n, NP, hipMemcpyDeviceToHost, s));
+    }
+    if (const int r = push_through_commit(c, ns, s)) return r;
+    HIPCHK(hipStreamSynchronize(s));
   }
-  HIPCHK(ovp_launch_gemm4(0, 0, n, ns, ns, c->Y, ld, c->T, ld, c->W1, ld, 0, 0, s));
-  HIPCHK(ovp_launch_gemm4(0, 1, n, n, ns, c->W1, ld, c->Y, ld, c->L, ld, 0, 1, s));
-  HIPCHK(ovp_launch_sub_sym(c->P, c->L, n, ld, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (dx_planes)  // the involved entries straight from the loop (the product above agrees with them to rounding)
+  if (dx_planes)  // the involved entries straight from the loop (on a marginal the product above agrees with them to rounding)
     for (int k = 0; k < NP; ++k)
       for (int i = 0; i < ns; ++i) dx_planes[(size_t)k * n + ids[i]] = dx_sub[(size_t)k * ns + i];
   return 0;
 }
 
-extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, double* dx_planes,
-                                      uint8_t* plane_ok, double* plane_chi2, int* plane_dof, uint8_t* feat_used) {
-  if (!c || !o || !pb || pb->n_planes < 0) return OVP_E_ARG;
-  if (!c->have_state || !c->have_cov || !c->have_batch) return OVP_E_STATE;
-  if (c->h_n_meas.empty() && c->n_feats > 0) return OVP_E_STATE;  // needs ovp_batch_upload (host copy of the layout)
-  const double t_entry = c->pl_sub_active ? c->pl_t_entry : host_now_ms();
-  c->have_factor = false;
-  const int n = c->n, ld = c->ld, F = c->n_feats, NP = pb->n_planes, M = c->max_meas;
-  // skip_plane_used is an option of the POINT update that follows; the plane loop itself produces the mask
-  ovp_update_opts o_local = *o;
-  o_local.skip_plane_used = 0;
-  o = &o_local;
-  c->pl_used_valid = false;
-  int rcu = ensure_pl_used(c);
-  if (rcu) return rcu;
-  const bool natural_order = getenv("OVP_PL_NATURAL_ORDER") != nullptr;  // A/B: the loop on all n columns in the state's order
-  if (!c->pl_sub_active && NP > 0 && (n > ovp_chol2_max_n() || !natural_order))
-    return plane_update_ordered(c, o, pb, dx_planes, plane_ok, plane_chi2, plane_dof, feat_used);
-  if (n > ovp_chol2_max_n()) return OVP_E_CAPACITY;  // (plane_update_ordered hands over a sub-state the factorization can take)
-  if (feat_used) memset(feat_used, 0, (size_t)F);
-  for (int pl = 0; pl < NP; ++pl) {
-    if (plane_ok) plane_ok[pl] = 0;
-    if (plane_chi2) plane_chi2[pl] = 0.0;
-    if (plane_dof) plane_dof[pl] = 0;
+// ---- the loop body, in stages -----------------------------------------------------------------------------------------------
+// L0 = chol(P) runs on the side stream beside the first plane's front end (plane_prelaunch).  Every way out of plane_loop behind the
+// fork - HIPCHK returns included - makes the loop's stream wait for the side stream: the next call must not race a factorization
+// that is still writing c->L / c->flags.
+struct ForkGuard {
+  hipStream_t s;
+  hipEvent_t ev_join;
+  hipStream_t side;
+  bool forked;
+  ~ForkGuard() {
+    if (!forked) return;
+    (void)hipEventRecord(ev_join, side);  // (a second record behind whatever the side stream got: harmless when the first one made it)
+    (void)hipStreamWaitEvent(s, ev_join, 0);
   }
-  if (dx_planes && NP > 0) memset(dx_planes, 0, sizeof(double) * (size_t)n * NP);
-  if (NP == 0) {  // a frame without planes: nothing is consumed, and a point update with skip_plane_used may follow
-    if (F) HIPCHK(hipMemsetAsync(c->pl_used, 0, (size_t)F, c->stream));
-    c->h_pl_used.assign((size_t)F, 0);
-    c->pl_used_valid = true;
-    return 0;
-  }
+};
+static hipError_t join_chol(ForkGuard& fork) {
+  if (!fork.forked) return hipSuccess;
+  fork.forked = false;
+  return hipStreamWaitEvent(fork.s, fork.ev_join, 0);
+}
+// a refusal behind the fork: chol(P) has run - a flag it may have raised (singular prior) must not outlive the call
+static int plane_bail(ovp_ctx* c, ForkGuard& fork, int code) {
+  (void)join_chol(fork);
+  (void)hipMemsetAsync(c->flags, 0, sizeof(int) * 4, fork.s);
+  return code;
+}
+
+struct PlanePre { ovp::FeatParams fp; int n_slam = 0; size_t res_bytes = 0, tstride = 0; double t_first = 0.0; bool any_candidate = false; };
+// What does not depend on the grouping goes to the device first: the fills and chol(P) (~70 us) run while the host sorts the features
+// by plane and builds the per-plane tables (~40 us at config 3, during which the stream used to be idle).
+static int plane_prelaunch(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, const PlaneLoopView& v, ForkGuard& fork,
+                           PlanePre* pre) {
+  const int n = c->n, ld = c->ld, F = c->n_feats, NP = pb->n_planes;
   for (int k = 0; k < NP; ++k)
     if (pb->plane_state_id[k] >= 0 && pb->plane_state_id[k] + 3 > n) return OVP_E_ARG;
-  const int n_slam = pb->n_slam > 0 ? pb->n_slam : 0;
+  const int n_slam = pre->n_slam = pb->n_slam > 0 ? pb->n_slam : 0;
   if (n_slam > 0 && (!pb->slam_plane || !pb->slam_state_id || !pb->slam_p || !pb->slam_p_fej)) return OVP_E_ARG;
   for (int q = 0; q < n_slam; ++q)
     if (pb->slam_state_id[q] < 0 || pb->slam_state_id[q] + 3 > n || pb->slam_plane[q] < 1 || pb->slam_plane[q] > NP) return OVP_E_ARG;
   int rc = fill_feat_params(c, o);
   if (rc) return rc;
-  ovp::FeatParams fp = c->fp;
-  fp.skip = nullptr;
-  fp.range_lo = 0;  // the plane loop always walks the whole batch
-  fp.range_hi = 0x7fffffff;
-  // ---- what does not depend on the grouping goes to the device first: the fills and chol(P) (~70 us) run while the host sorts the
-  // features by plane and builds the per-plane tables (~40 us at config 3, during which the stream used to be idle) ----
-  const size_t res_bytes = sizeof(double) * (4 * (size_t)NP + (size_t)n * NP) + (size_t)F + 64 + 256;  // (+ flags and sequence word)
+  pre->fp = c->fp;
+  pre->fp.skip = nullptr;
+  pre->fp.range_lo = 0;  // the plane loop always walks the whole batch
+  pre->fp.range_hi = 0x7fffffff;
+  pre->res_bytes = sizeof(double) * (4 * (size_t)NP + (size_t)n * NP) + (size_t)F + 64 + 256;  // (+ flags and sequence word)
   rc = plane_buffers(c, NP);  // shared with the first generation: pl_res, pl_dx, pl_cst, pl_An, ...
   if (rc) return rc;
-  rc = plane2_buffers(c, NP, 0, res_bytes);
+  rc = plane2_buffers(c, 0, pre->res_bytes);
   if (rc) return rc;
   hipStream_t s = c->stream;
-  const double t_first = host_now_ms();
-  const size_t tstride = (size_t)(c->n_max + 1) * ld;
+  pre->t_first = host_now_ms();
+  const size_t tstride = pre->tstride = (size_t)(c->n_max + 1) * ld;
   {
     // results, per-plane corrections, used-feature mask (rounded up to whole words: the buffer is f_max + 64 bytes), flags,
     // [0] current T buffer + [1..2] factor bookkeeping (PlaneSolve::cond), half 0 of T (sum of the accepted L0^T A L0): one launch
@@ -531,25 +575,19 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
     void* zp[8] = {c->pl_res, c->pl_dx, c->pl_used, c->flags, c->pl_cur, c->pl_Tbuf, c->Ltp, c->Dinv};
     const size_t zb[8] = {sizeof(double) * 4 * NP, sizeof(double) * (size_t)n * NP, ((size_t)F + 3) & ~(size_t)3, sizeof(int) * 4,
                           3 * sizeof(int), sizeof(double) * (tstride + (size_t)n * ld),
-                          c->pl_sub_active ? sizeof(double) * 256 * (size_t)(ntn * (ntn + 1) / 2) : 0,
-                          c->pl_sub_active ? sizeof(double) * 256 * (size_t)ntn : 0};
+                          v.ordered ? sizeof(double) * 256 * (size_t)(ntn * (ntn + 1) / 2) : 0,
+                          v.ordered ? sizeof(double) * 256 * (size_t)ntn : 0};
     const int zpat[8] = {0, 0, 0, 0, 0, 0, 2, 1};
     HIPCHK(ovp_launch_fill_regions(zp, zb, zpat, 8, ntn, s));
   }
   if (c->pl_ktimer) {  // [0 | 1] = the whole loop on the device clock (first launch .. covariance product), then a pair per plane
-    while (c->pl_ev_loop.size() < 2) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      c->pl_ev_loop.push_back(e);
-    }
-    if (!c->pl_sub_active) HIPCHK(hipEventRecord(c->pl_ev_loop[0], s));  // (plane_update_ordered: in front of its permutation)
+    HIPCHK(ensure_events(c->pl_ev_loop, 2));
+    if (!v.ordered) HIPCHK(hipEventRecord(c->pl_ev_loop[0], s));  // (plane_update_ordered: in front of its permutation)
   }
   // (a cheap look at the batch first: when no plane can qualify - update/UpdaterMSCKF.cpp:316-317, 384-396 - nothing below needs the
   // factor, and a singular prior must not fail a call that has nothing to update)
-  const ovp_general_batch* gbp = c->pl_gen_b;  // general on-plane features (ovp_msckf_plane_update_general), nullptr = none
-  const int GF = gbp ? gbp->n_feats : 0, GM = gbp ? gbp->max_meas : 0;
-  bool any_candidate = false;
   {
+    const int GF = v.gen ? v.gen->n_feats : 0;
     std::vector<int> cnt((size_t)NP + 1, 0);
     for (int f = 0; f < F; ++f) {
       const int pf = pb->plane_of_feat[f];
@@ -557,116 +595,103 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
     }
     for (int q = 0; q < n_slam; ++q) ++cnt[pb->slam_plane[q]];
     for (int g = 0; g < GF; ++g)
-      if (c->pl_gen_plane[g] >= 1 && c->pl_gen_plane[g] <= NP && gbp->n_meas[g] >= 2) ++cnt[c->pl_gen_plane[g]];
-    for (int pl = 1; pl <= NP && !any_candidate; ++pl)
-      any_candidate = cnt[pl] >= (pb->plane_state_id[pl - 1] >= 0 ? 1 : 4);
+      if (v.plane_of_gen[g] >= 1 && v.plane_of_gen[g] <= NP && v.gen->n_meas[g] >= 2) ++cnt[v.plane_of_gen[g]];
+    for (int pl = 1; pl <= NP && !pre->any_candidate; ++pl)
+      pre->any_candidate = cnt[pl] >= (pb->plane_state_id[pl - 1] >= 0 ? 1 : 4);
   }
   // L0 = chol(P), dense lower triangular in c->L.  Nothing needs it before the first plane's W = A L0, so it runs on the side
   // stream beside that plane's rows / Gram pair / assembly (round 5; one workgroup - the small kernels of the front end leave it a
   // CU on every XCD) and is joined in front of that product (A/B in round 5: config 3 2.776 -> 2.719 ms).
-  // (every way out of this function behind the fork - HIPCHK returns included - makes the loop's stream wait for the side stream:
-  // the next call must not race a factorization that is still writing c->L / c->flags)
-  struct ForkGuard {
-    hipStream_t s;
-    hipEvent_t ev_join;
-    hipStream_t side;
-    bool forked;
-    ~ForkGuard() {
-      if (!forked) return;
-      (void)hipEventRecord(ev_join, side);  // (a second record behind whatever the side stream got: harmless when the first one made it)
-      (void)hipStreamWaitEvent(s, ev_join, 0);
-    }
-  } fork_guard{s, c->ev_join, c->stream2, false};
-  bool& chol_forked = fork_guard.forked;
-  if (any_candidate) {
+  if (pre->any_candidate) {
     if (s == c->stream) {
       HIPCHK(hipEventRecord(c->ev_fork, s));
       HIPCHK(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-      chol_forked = true;
-      rc = chol_of_P(c, c->stream2);
+      fork.forked = true;
+      rc = chol_of_P(c, c->stream2, v.psd);
       if (rc) return rc;
       HIPCHK(hipEventRecord(c->ev_join, c->stream2));
     } else {
-      rc = chol_of_P(c, s);
+      rc = chol_of_P(c, s, v.psd);
       if (rc) return rc;
     }
   }
-  auto join_chol = [&]() -> hipError_t {
-    if (!chol_forked) return hipSuccess;
-    chol_forked = false;
-    return hipStreamWaitEvent(s, c->ev_join, 0);
-  };
-  // a refusal from here on: chol(P) has run - a flag it may have raised (singular prior) must not outlive the call
-  auto bail = [&](int code) {
-    (void)join_chol();
-    (void)hipMemsetAsync(c->flags, 0, sizeof(int) * 4, s);
-    return code;
-  };
-  // ---- host-side grouping (update/UpdaterMSCKF.cpp:204-229) ----
+  return 0;
+}
+
+// items 0 .. count-1 bucketed by 1-based plane slot (slot(i) outside 1 .. NP: left out) in one pass, order kept: plane pl (0-based)
+// has items[start[pl + 1] .. start[pl + 2])  (a scan of the whole batch per plane was 0.4 ms of host time in front of the first
+// launch at 8000 features x 50 planes)
+struct PlaneBuckets { std::vector<int> start, items; };
+template <class Slot>
+static PlaneBuckets bucket_by_plane(int count, int NP, Slot slot) {
+  PlaneBuckets b;
+  b.start.assign((size_t)NP + 2, 0);
+  b.items.resize((size_t)(count > 0 ? count : 1));
+  for (int i = 0; i < count; ++i) {
+    const int p = slot(i);
+    if (p >= 1 && p <= NP) ++b.start[p + 1];
+  }
+  for (int pl = 1; pl <= NP + 1; ++pl) b.start[pl] += b.start[pl - 1];
+  std::vector<int> fill(b.start.begin(), b.start.end());
+  for (int i = 0; i < count; ++i) {
+    const int p = slot(i);
+    if (p >= 1 && p <= NP) b.items[fill[p]++] = i;
+  }
+  return b;
+}
+
+// ---- host-side grouping (update/UpdaterMSCKF.cpp:204-229): no HIP call, nothing of the context written ----
+struct PlaneGroups {
   std::vector<PlaneJobH> jobs;
-  std::vector<int> featlist;
-  std::vector<int> perms;  // per job: n entries
-  const int ncal = (o->do_calib_camera_pose ? 6 : 0) + (o->do_calib_camera_intrinsics ? 8 : 0);
-  // features bucketed by plane in one pass, batch order kept (a scan of the whole batch per plane was 0.4 ms of host time in
-  // front of the first launch at 8000 features x 50 planes)
-  std::vector<int> bucket_start((size_t)NP + 2, 0), bucket((size_t)(F > 0 ? F : 1));
-  for (int f = 0; f < F; ++f) {
-    const int pf = pb->plane_of_feat[f];
-    if (pf >= 1 && pf <= NP) ++bucket_start[pf + 1];
-  }
-  for (int pl = 1; pl <= NP + 1; ++pl) bucket_start[pl] += bucket_start[pl - 1];
-  {
-    std::vector<int> fill(bucket_start.begin(), bucket_start.end());
-    for (int f = 0; f < F; ++f) {
-      const int pf = pb->plane_of_feat[f];
-      if (pf >= 1 && pf <= NP) bucket[fill[pf]++] = f;
-    }
-  }
-  // the general features by plane, batch order kept
-  std::vector<int> glist, gbucket((size_t)NP + 2, 0), gsorted((size_t)(GF > 0 ? GF : 1));
-  for (int g = 0; g < GF; ++g)
-    if (c->pl_gen_plane[g] >= 1 && c->pl_gen_plane[g] <= NP && gbp->n_meas[g] >= 2) ++gbucket[c->pl_gen_plane[g] + 1];
-  for (int pl = 1; pl <= NP + 1; ++pl) gbucket[pl] += gbucket[pl - 1];
-  {
-    std::vector<int> fill(gbucket.begin(), gbucket.end());
-    for (int g = 0; g < GF; ++g)
-      if (c->pl_gen_plane[g] >= 1 && c->pl_gen_plane[g] <= NP && gbp->n_meas[g] >= 2) gsorted[fill[c->pl_gen_plane[g]]++] = g;
-  }
+  std::vector<int> featlist;  // batch features of the jobs, by job
+  std::vector<int> glist;     // general features of the jobs, by job
+  std::vector<int> perms;     // per job: n entries
   int ng_max = 0;
+};
+// returns a refusal code (the caller bails) or 0
+static int plane_group(const ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, const PlaneLoopView& v, int n_slam,
+                       PlaneGroups* groups) {
+  PlaneGroups& g = *groups;
+  const int n = c->n, F = c->n_feats, NP = pb->n_planes, M = c->max_meas;
+  const ovp_general_batch* gbp = v.gen;
+  const int GF = gbp ? gbp->n_feats : 0, GM = gbp ? gbp->max_meas : 0;
+  const int ncal = (o->do_calib_camera_pose ? 6 : 0) + (o->do_calib_camera_intrinsics ? 8 : 0);
+  const PlaneBuckets bf = bucket_by_plane(F, NP, [&](int f) { return pb->plane_of_feat[f]; });
+  const PlaneBuckets bg = bucket_by_plane(GF, NP, [&](int i) { return gbp->n_meas[i] >= 2 ? v.plane_of_gen[i] : 0; });
   for (int pl = 0; pl < NP; ++pl) {
     PlaneJobH j;
     j.pl = pl;
-    j.start = (int)featlist.size();
+    j.start = (int)g.featlist.size();
     j.nf = 0;
     j.rows_total = 0;
     j.rows_live = 0;
     j.sid = pb->plane_state_id[pl];
     j.in_state = j.sid >= 0;
     unsigned long long seen = 0ull;
-    for (int bi = bucket_start[pl + 1]; bi < bucket_start[pl + 2]; ++bi) {
-      const int f = bucket[bi];
+    for (int bi = bf.start[pl + 1]; bi < bf.start[pl + 2]; ++bi) {
+      const int f = bf.items[bi];
       const int m = c->h_n_meas[f];
       if (m < 2) continue;
-      if (m > OVP_MAX_MEAS_DEV) return bail(OVP_E_CAPACITY);  // 2m bearing rows = one wavefront (the constraint row is wave-uniform)
-      featlist.push_back(f);
+      if (m > OVP_MAX_MEAS_DEV) return OVP_E_CAPACITY;  // 2m bearing rows = one wavefront (the constraint row is wave-uniform)
+      g.featlist.push_back(f);
       j.nf++;
       j.rows_total += 3 * m - 3;
       j.rows_live += 2 * m - 2;  // the m identical constraint rows are one direction (k_chol2 gate)
       for (int k = 0; k < m; ++k) seen |= 1ull << c->h_clone_idx[(size_t)f * M + k];
     }
     // general features on this plane: same rows per feature, any clone, any camera (its calibration columns are involved)
-    j.g_start = (int)glist.size();
+    j.g_start = (int)g.glist.size();
     j.ng = 0;
     unsigned cams_seen = j.nf > 0 ? 1u : 0u;  // (the batch's features are camera 0's)
-    for (int gi = gbucket[pl + 1]; gi < gbucket[pl + 2]; ++gi) {
-      const int g = gsorted[gi], m = gbp->n_meas[g];
-      glist.push_back(g);
+    for (int gi = bg.start[pl + 1]; gi < bg.start[pl + 2]; ++gi) {
+      const int gf = bg.items[gi], m = gbp->n_meas[gf];
+      g.glist.push_back(gf);
       j.ng++;
       j.rows_total += 3 * m - 3;
       j.rows_live += 2 * m - 2;
       for (int k = 0; k < m; ++k) {
-        seen |= 1ull << gbp->clone_idx[(size_t)g * GM + k];
-        cams_seen |= 1u << gbp->cam_idx[(size_t)g * GM + k];
+        seen |= 1ull << gbp->clone_idx[(size_t)gf * GM + k];
+        cams_seen |= 1u << gbp->cam_idx[(size_t)gf * GM + k];
       }
     }
     const int ncal_pl = j.ng > 0 ? ncal * __builtin_popcount(cams_seen) : ncal;
@@ -674,11 +699,11 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
     if (!j.in_state)
       for (int q = 0; q < n_slam; ++q)
         if (pb->slam_plane[q] == pl + 1) ++ns_pl;
-    if (ns_pl > PA_MAXQ) return bail(OVP_E_CAPACITY);
+    if (ns_pl > PA_MAXQ) return OVP_E_CAPACITY;
     j.ns_pl = ns_pl;
     if (j.nf + j.ng == 0 || (!j.in_state && j.nf + j.ng + ns_pl < 4)) {  // update/UpdaterMSCKF.cpp:316-317,384-396
-      featlist.resize(j.start);
-      glist.resize(j.g_start);
+      g.featlist.resize(j.start);
+      g.glist.resize(j.g_start);
       continue;
     }
     j.rows_total += ns_pl;
@@ -690,11 +715,11 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
     if (!j.in_state) j.rows_total -= 3;
     if (!j.in_state) j.rows_live -= 3;
     if (j.rows_u < 1) {
-      featlist.resize(j.start);
-      glist.resize(j.g_start);
+      g.featlist.resize(j.start);
+      g.glist.resize(j.g_start);
       continue;
     }
-    if (j.ng > ng_max) ng_max = j.ng;
+    if (j.ng > g.ng_max) g.ng_max = j.ng;
     j.thr = o->chi2_multiplier * ovp_chi2_quantile_095(j.rows_u);
     // order of the involved columns in the normalised Gram: everything that is not a clone first, the clones last (a rank
     // deficiency - gauge freedom, planar scene - then shows up in the trailing pivots, k_chol2 mode 2)
@@ -714,8 +739,8 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
           if ((cams_seen >> cam) & 1u)
             for (int k = 0; k < 14; ++k) {
               if (!(k < 6 ? o->do_calib_camera_pose : o->do_calib_camera_intrinsics)) continue;
-              const int col = gen_cam_col(c, cam, k);
-              if (col < 0 || col >= n) return bail(OVP_E_ARG);
+              const int col = gen_cam_col(c, v.gen_pos, v.n_state, cam, k);
+              if (col < 0 || col >= n) return OVP_E_ARG;
               inv[col] = 1;
             }
       if (j.in_state)
@@ -733,40 +758,44 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
             if (col >= 0 && col < n && perm[col] < 0) perm[col] = pos++;
           }
       j.n_inv_cols = pos;
-      perms.insert(perms.end(), perm.begin(), perm.end());
+      g.perms.insert(g.perms.end(), perm.begin(), perm.end());
     }
-    jobs.push_back(j);
+    g.jobs.push_back(j);
   }
-  const int NJ = (int)jobs.size();
-  if (NJ == 0 && any_candidate) {  // chol(P)'s verdict concerns nobody
-    HIPCHK(join_chol());
-    HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 4, s));
-  }
-  // ---- staging layout: ints [featlist | sid NP | perms NJ*n | slam_plane | slam_id], doubles [cp | cp_fej | slam_p | slam_p_fej] ----
-  const size_t n_int = featlist.size() + (size_t)NP + perms.size() + 2 * (size_t)n_slam;
+  return 0;
+}
+
+// ---- staging: ints [featlist | sid NP | perms NJ*n | slam_plane | slam_id], doubles [cp | cp_fej | slam_p | slam_p_fej] ----
+struct PlaneStage {  // device addresses of the tables inside c->pl_dstage
+  const int *feat, *sid, *perm, *slam_plane, *slam_id;
+  double *cp, *cp_fej, *slam_p, *slam_p_fej;
+};
+static int plane_stage_upload(ovp_ctx* c, const ovp_plane_batch* pb, const PlaneGroups& g, const PlanePre& pre, PlaneStage* st) {
+  const int NP = pb->n_planes, n_slam = pre.n_slam;
+  const size_t n_int = g.featlist.size() + (size_t)NP + g.perms.size() + 2 * (size_t)n_slam;
   const size_t int_bytes = ((n_int * sizeof(int) + 15) / 16) * 16;
   const size_t n_dbl = 6 * (size_t)NP + 6 * (size_t)n_slam;
   const size_t stage_bytes = int_bytes + n_dbl * sizeof(double);
-  rc = plane2_buffers(c, NP, stage_bytes, res_bytes);  // (grows the staging block when this frame needs more)
+  const int rc = plane2_buffers(c, stage_bytes, pre.res_bytes);  // (grows the staging block when this frame needs more)
   if (rc) return rc;
   int* hi = (int*)c->pl_hstage;
   double* hd = (double*)((char*)c->pl_hstage + int_bytes);
   int* di = (int*)c->pl_dstage;
   double* dd = (double*)((char*)c->pl_dstage + int_bytes);
   size_t io = 0;
-  const size_t o_feat = io;
-  memcpy(hi + io, featlist.data(), sizeof(int) * featlist.size());
-  io += featlist.size();
-  const size_t o_sid = io;
+  st->feat = di + io;
+  memcpy(hi + io, g.featlist.data(), sizeof(int) * g.featlist.size());
+  io += g.featlist.size();
+  st->sid = di + io;
   memcpy(hi + io, pb->plane_state_id, sizeof(int) * NP);
   io += NP;
-  const size_t o_perm = io;
-  if (!perms.empty()) memcpy(hi + io, perms.data(), sizeof(int) * perms.size());
-  io += perms.size();
-  const size_t o_spl = io;
+  st->perm = di + io;
+  if (!g.perms.empty()) memcpy(hi + io, g.perms.data(), sizeof(int) * g.perms.size());
+  io += g.perms.size();
+  st->slam_plane = di + io;
   if (n_slam) memcpy(hi + io, pb->slam_plane, sizeof(int) * n_slam);
   io += n_slam;
-  const size_t o_sidx = io;
+  st->slam_id = di + io;
   if (n_slam) memcpy(hi + io, pb->slam_state_id, sizeof(int) * n_slam);
   io += n_slam;
   memcpy(hd, pb->cp, sizeof(double) * 3 * NP);
@@ -775,400 +804,435 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
     memcpy(hd + 6 * NP, pb->slam_p, sizeof(double) * 3 * n_slam);
     memcpy(hd + 6 * NP + 3 * n_slam, pb->slam_p_fej, sizeof(double) * 3 * n_slam);
   }
-  HIPCHK(hipMemcpyAsync(c->pl_dstage, c->pl_hstage, stage_bytes, hipMemcpyHostToDevice, s));
-  const int* d_feat = di + o_feat;
-  const int* d_sid = di + o_sid;
-  const int* d_perm = di + o_perm;
-  const int* d_spl = di + o_spl;
-  const int* d_sidx = di + o_sidx;
-  double* d_cp = dd;
-  double* d_cpfej = dd + 3 * NP;
-  double* d_slam_p = dd + 6 * NP;
-  double* d_slam_pfej = dd + 6 * NP + 3 * n_slam;
-  // ---- general features: the batch and the per-plane lists, the marks and the staged rows ----
-  ovp::PlaneGenParams gp0;
-  ovp::PlaneGenCols gcols;
-  memset(&gp0, 0, sizeof(gp0));
-  memset(&gcols, 0xff, sizeof(gcols));
-  const unsigned gen_calmask = (o->do_calib_camera_pose ? 0x3Fu : 0u) | (o->do_calib_camera_intrinsics ? (0xFFu << 6) : 0u);
+  HIPCHK(hipMemcpyAsync(c->pl_dstage, c->pl_hstage, stage_bytes, hipMemcpyHostToDevice, c->stream));
+  st->cp = dd;
+  st->cp_fej = dd + 3 * NP;
+  st->slam_p = dd + 6 * NP;
+  st->slam_p_fej = dd + 6 * NP + 3 * n_slam;
+  return 0;
+}
+
+// ---- general features: the batch and the per-plane lists, the marks and the staged rows ----
+struct PlaneGenStage {
+  ovp::PlaneGenParams gp0;   // everything but the per-plane fields (plane_gen_params)
+  ovp::PlaneGenCols cols;
+  unsigned calmask = 0;
+};
+static int plane_gen_upload(ovp_ctx* c, const ovp_update_opts* o, const PlaneLoopView& v, const PlanePre& pre, const PlaneGroups& g,
+                            ForkGuard& fork, PlaneGenStage* gs) {
+  const int n = c->n;
+  const ovp_general_batch* gbp = v.gen;
+  hipStream_t s = c->stream;
+  memset(&gs->gp0, 0, sizeof(gs->gp0));
+  memset(&gs->cols, 0xff, sizeof(gs->cols));
+  gs->calmask = (o->do_calib_camera_pose ? 0x3Fu : 0u) | (o->do_calib_camera_intrinsics ? (0xFFu << 6) : 0u);
   if (gbp) {
     for (int cam = 0; cam < c->gen_ncams; ++cam)
       for (int k = 0; k < 14; ++k)
-        if ((gen_calmask >> k) & 1u) {
-          gcols.col[cam][k] = gen_cam_col(c, cam, k);
-          if (gcols.col[cam][k] < 0 || gcols.col[cam][k] >= n) return bail(OVP_E_ARG);
+        if ((gs->calmask >> k) & 1u) {
+          gs->cols.col[cam][k] = gen_cam_col(c, v.gen_pos, v.n_state, cam, k);
+          if (gs->cols.col[cam][k] < 0 || gs->cols.col[cam][k] >= n) return plane_bail(c, fork, OVP_E_ARG);
         }
   }
-  if (gbp && !glist.empty()) {
-    auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    const size_t GFM = (size_t)GF * GM;
-    const size_t o_uv = 0, o_ci = al(sizeof(float) * 2 * GFM), o_cam = al(o_ci + sizeof(int) * GFM), o_nm = al(o_cam + sizeof(int) * GFM),
-                 o_p = al(o_nm + sizeof(int) * GF), o_list = al(o_p + sizeof(double) * 3 * GF), in_bytes = al(o_list + sizeof(int) * glist.size());
-    const size_t mark_stride = (size_t)((n + 4 + 15) & ~15), hp_stride = (size_t)ovp::PG_ROWS * (n + 4);
-    // inputs through the pinned arena (nobody else uses it while a plane loop is enqueued; the previous user has waited for its
-    // copy), marks and staged rows in a device block of their own: no host synchronisation unless a block has to grow
-    const size_t o_hp = al(sizeof(int) * mark_stride * ng_max), total = o_hp + sizeof(double) * hp_stride * ng_max;
-    if (total > c->pl_gen_cap) {
-      HIPCHK(hipStreamSynchronize(s));
-      if (c->pl_gen_dev) HIPCHK(hipFree(c->pl_gen_dev));
-      c->pl_gen_dev = nullptr;
-      c->pl_gen_cap = 0;
-      HIPCHK(hipMalloc(&c->pl_gen_dev, total + total / 2));
-      c->pl_gen_cap = total + total / 2;
-    }
-    void *ah = nullptr, *ad = nullptr;
-    {
-      const int rca = ovp_io_arena(c, in_bytes, &ah, &ad);
-      if (rca) return bail(rca);
-    }
-    char* h = (char*)ah;
-    memcpy(h + o_uv, gbp->uv, sizeof(float) * 2 * GFM);
-    memcpy(h + o_ci, gbp->clone_idx, sizeof(int) * GFM);
-    memcpy(h + o_cam, gbp->cam_idx, sizeof(int) * GFM);
-    memcpy(h + o_nm, gbp->n_meas, sizeof(int) * GF);
-    memcpy(h + o_p, gbp->p_FinG, sizeof(double) * 3 * GF);
-    memcpy(h + o_list, glist.data(), sizeof(int) * glist.size());
-    HIPCHK(hipMemcpyAsync(ad, ah, in_bytes, hipMemcpyHostToDevice, s));
-    char* d = (char*)ad;
-    char* ds = (char*)c->pl_gen_dev;
-    gp0.fp = fp;
-    gp0.fp.calmask = gen_calmask;
-    gp0.cam_cal = c->gen_cal;
-    for (int k = 0; k < OVP_MAX_CAMERAS; ++k) gp0.cam_fisheye[k] = c->gen_fisheye[k];
-    gp0.cc = gcols;
-    gp0.uv = (const float*)(d + o_uv);
-    gp0.clone_idx = (const int*)(d + o_ci);
-    gp0.cam_idx = (const int*)(d + o_cam);
-    gp0.n_meas = (const int*)(d + o_nm);
-    gp0.p_FinG = (const double*)(d + o_p);
-    gp0.max_meas = GM;
-    gp0.list = (const int*)(d + o_list);
-    gp0.mark = (int*)ds;
-    gp0.mark_stride = (int)mark_stride;
-    gp0.hp = (double*)(ds + o_hp);
-    gp0.hp_stride = hp_stride;
+  if (!gbp || g.glist.empty()) return 0;
+  const int GF = gbp->n_feats, GM = gbp->max_meas;
+  auto al = [](size_t b) { return (b + 63) & ~(size_t)63; };
+  const size_t GFM = (size_t)GF * GM;
+  const size_t o_uv = 0, o_ci = al(sizeof(float) * 2 * GFM), o_cam = al(o_ci + sizeof(int) * GFM), o_nm = al(o_cam + sizeof(int) * GFM),
+               o_p = al(o_nm + sizeof(int) * GF), o_list = al(o_p + sizeof(double) * 3 * GF), in_bytes = al(o_list + sizeof(int) * g.glist.size());
+  const size_t mark_stride = (size_t)((n + 4 + 15) & ~15), hp_stride = (size_t)ovp::PG_ROWS * (n + 4);
+  // inputs through the pinned arena (nobody else uses it while a plane loop is enqueued; the previous user has waited for its
+  // copy), marks and staged rows in a device block of their own: no host synchronisation unless a block has to grow
+  const size_t o_hp = al(sizeof(int) * mark_stride * g.ng_max), total = o_hp + sizeof(double) * hp_stride * g.ng_max;
+  if (total > c->pl_gen_cap) {
+    HIPCHK(hipStreamSynchronize(s));
+    if (c->pl_gen_dev) HIPCHK(hipFree(c->pl_gen_dev));
+    c->pl_gen_dev = nullptr;
+    c->pl_gen_cap = 0;
+    HIPCHK(hipMalloc(&c->pl_gen_dev, total + total / 2));
+    c->pl_gen_cap = total + total / 2;
   }
-  const double white_c = 1.0 / o->sigma_constraint;
-  // weight of the expected energy of the rounding-decided rows in the gate statistic (k_chol2.hip); OVP_PL_NOISE_SCALE overrides the
-  // calibrated constant for the study that produced it (tools/plane_gate_agreement.py --fit)
-  double noise_scale = OVP_PLANE_NOISE_KAPPA;
-  if (const char* ns_env = getenv("OVP_PL_NOISE_SCALE")) noise_scale = atof(ns_env);  // (read per call)
-  for (int jn = 0; jn < NJ; ++jn) {
-    const PlaneJobH& j = jobs[jn];
-    // leading block this plane's products and factorization run on (plane_update_ordered): every column involved so far
-    const int nk = c->pl_sub_active ? c->pl_nl[j.pl] : n;
-    // (1) per-feature rows
-    ovp::PlaneParams pp;
-    pp.feat_list = d_feat + j.start;
-    pp.n_local = j.nf;
-    pp.plane = j.pl;
-    pp.in_state = j.in_state;
-    pp.plane_sid = j.sid;
-    pp.white_c = white_c;
-    pp.cp = d_cp;
-    pp.cp_fej = d_cpfej;
-    pp.cst = c->pl_cst;
-    ovp::FeatParams fpl = fp;
-    fpl.n = nk;
-    fpl.P = c->P;
-    int chunks = (2 * j.nf + c->rows_per_chunk - 1) / c->rows_per_chunk;
-    int nsplit = 1;
-    if (j.nf > 0) {
-      HIPCHK(ovp_launch_plane_feat(&fpl, &pp, j.nf, s));
-      // (2) Gram products
-      HIPCHK(ovp_launch_gram_pair(c->rec, fp.n_clones, j.nf, c->rows_per_chunk, chunks, c->gramS, c->G, 3 * j.nf, c->ldg, nk + 4,
-                                  c->n_split, c->part, &nsplit, s));
-    } else {  // a plane with general features only: an empty structured Gram (one chunk of zeros per clone), no G^T G split
-      chunks = 1;
-      nsplit = 0;
-      HIPCHK(hipMemsetAsync(c->gramS, 0, sizeof(double) * (size_t)fp.n_clones * OVP_GRAM_ELEMS, s));
-    }
-    // (2b) the plane's general features: one more split of the partials and one more moment record (k_plane_feat_gen.hip); a plane
-    // without any enqueues nothing here
-    const int nt16_pl = (nk + 4 + 15) / 16, ntile_pl = nt16_pl * (nt16_pl + 1) / 2;
-    if (j.ng > 0) {
-      ovp::PlaneGenParams g = gp0;
-      g.list = gp0.list + j.g_start;
-      g.n_local = j.ng;
-      g.plane = j.pl;
-      g.in_state = j.in_state;
-      g.plane_sid = j.sid;
-      g.white_c = white_c;
-      g.cp = d_cp;
-      g.cp_fej = d_cpfej;
-      g.n = nk;
-      g.hp_stride = (size_t)ovp::PG_ROWS * (nk + 4);
-      g.part_split = c->part + (size_t)nsplit * ntile_pl * 256;
-      g.cst_rec = c->pl_cst + (size_t)j.nf * 10;
-      HIPCHK(ovp_launch_plane_feat_gen(&g, s));
-    }
-    // (3) pair on the state columns, normalised Gram, residual energy
-    ovp::PlaneAsm pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.gramS = c->gramS;
-    pa.n_clones = fp.n_clones;
-    pa.n_chunks = chunks;
-    pa.part = c->part;
-    pa.n_split = nsplit + (j.ng > 0 ? 1 : 0);
-    pa.ntile = ntile_pl;
-    pa.colmap = c->colmap;
-    pa.n = nk;
-    pa.plane_sid = j.sid;
-    pa.in_state = j.in_state;
-    pa.cst = c->pl_cst;
-    pa.nf = j.nf + (j.ng > 0 ? 1 : 0);
-    pa.n_slam = j.in_state ? 0 : n_slam;
-    pa.plane1 = j.pl + 1;
-    pa.slam_plane = d_spl;
-    pa.slam_id = d_sidx;
-    pa.slam_p = d_slam_p;
-    pa.slam_p_fej = d_slam_pfej;
-    pa.cp = d_cp + 3 * j.pl;
-    pa.cp_fej = d_cpfej + 3 * j.pl;
-    pa.white_c = white_c;
-    pa.do_fej = fp.do_fej;
-    pa.Ab = c->Ab;
-    pa.lda = ld;
-    pa.perm = d_perm + (size_t)jn * n;
-    pa.An = c->pl_An;
-    pa.ldn = ld;
-    pa.bn = c->pl_bn;
-    pa.eps = 1e-12;
-    pa.scal = c->pl_scal;
-    HIPCHK(ovp_launch_plane_assemble2(&pa, s));
-    // (4) W = A L0 ;  T_try = T_cur + L0^T W ;  c = L0^T b
-    HIPCHK(join_chol());  // (first plane: L0 comes from the side stream)
-    HIPCHK(ovp_launch_gemm4(0, 0, nk, nk, nk, c->Ab, ld, c->L, ld, c->W1, ld, 0, 0, s));
-    HIPCHK(ovp_launch_plane_dT(nk, c->L, ld, c->W1, c->Ab + (size_t)nk * ld, c->pl_Tbuf, tstride, c->pl_cur, c->pl_crow, s));
-    // (5) both factorizations, gate, solve, commit
-    ovp::Chol2Job j0, j1;
-    memset(&j0, 0, sizeof(j0));
-    memset(&j1, 0, sizeof(j1));
-    j0.A = c->pl_Tbuf;
-    j0.sel = c->pl_cur;
-    j0.sel_xor = 1;
-    j0.sel_stride = tstride;
-    j0.n = nk;
-    j0.ld = ld;
-    j0.add_identity = 1;
-    j0.mode = 1;
-    j0.brow = c->pl_crow;
-    j0.flag = c->flags;
-    j1.A = c->pl_An;
-    j1.n = j.n_inv_cols;
-    j1.ld = ld;
-    j1.add_identity = 0;
-    j1.mode = 2;
-    j1.brow = c->pl_bn;
-    j1.flag = c->flags + 2;
-    j1.piv_floor = 1e-5;
-    ovp::PlaneSolve ps;
-    memset(&ps, 0, sizeof(ps));
-    ps.scal = c->pl_scal;
-    ps.range_done = c->pl_range_done;
-    ps.seq = ++c->pl_seq;
-    {
-      // The update part on two workgroups: tile columns < h and the rest (k_chol2.hip).  Measured (r03, A/B in one call): at 16 tile
-      // columns (N = 240) nothing is gained (2.91 against 2.81 ms per config-3 plane loop for h = 5 .. 8: exports + a second gate
-      // hand-over cost what the second CU's f64 pipe gives), so one workgroup stays the default there; from 17 tile columns on
-      // (N > 255) the tile registers of one workgroup spill and the split wins (config 4, N = 285: 7.91 ms for h = 5 or 6, 8.10 for
-      // 7 or 8, 8.69 unsplit).  OVP_C2_SPLIT: 0 = never, h = forced.
-      const char* split_s = getenv("OVP_C2_SPLIT");  // (read per call: the tests switch it)
-      const int split_env = split_s ? atoi(split_s) : -1;
-      const int nb = nk + 1, ntb = (nb + 15) / 16;
-      const int nst = (nb % 16 == 1) ? ntb - 1 : ntb;  // a border row alone in its tile row takes no step
-      int h = ntb >= 17 ? nst / 3 : 0;  // part B also runs the back half of the chain: 5 - 6 of 18 steps measured best (7.91 ms per
-                                        // config-4 plane loop against 8.10 for 7 or 8 and 8.69 unsplit)
-      if (split_env >= 0) h = split_env < ntb - 1 ? split_env : 0;
-      if (h > 9) h = 9;  // pl_xbuf holds nine exported steps
-      j0.split_h = h;
-      j0.xbuf = c->pl_xbuf;
-      j0.xflag = c->pl_xflag;
-      j0.xseq = ps.seq;
-      ps.xzz = c->pl_xy;
-      ps.xy = c->pl_xy + 16;
-      ps.xsync = c->pl_xflag + 32;
-    }
-    ps.thr = j.thr;
-    ps.rows_live = j.rows_live;
-    ps.rows_u = j.rows_u;
-    ps.n_involved = j.n_inv_cols;
-    ps.force = pb->force_decision ? (int)pb->force_decision[j.pl] : -1;
-    ps.noise_scale = noise_scale;
-    ps.tol_strict = 1e-5;
-    ps.tol_loose = 1e-5;
-    ps.res_out = c->pl_res + 4 * j.pl;
-    ps.L0 = c->L;
-    ps.ld0 = ld;
-    ps.n_full = n;
-    ps.dx_out = c->pl_dx + (size_t)j.pl * n;
-    ps.dx_last = c->pl_dxlast;
-    ps.cur = c->pl_cur;
-    // The covariance product behind the loop needs the factor of the last ACCEPTED T.  The last few planes leave theirs behind when
-    // they are accepted (~8 us of stores each); if one of them stays the last accepted plane, the k_tilechol behind the loop
-    // (94 us at N = 240) finds nothing to do.  Which plane that is, is decided on the device.
-    const int emit_last = 4;
-    ps.cond = c->pl_cur + 1;
-    ps.seq_plane = jn + 1;
-    ps.emit = (jn >= NJ - emit_last) ? 1 : 0;
-    ps.Lpack = c->Ltp;
-    ps.Dinv = c->Dinv;
-    ps.feat_list = d_feat + j.start;
-    ps.n_feat_local = j.nf;
-    ps.feat_used = c->pl_used;
-    ps.clone_R = c->clone_R;
-    ps.clone_p = c->clone_p;
-    ps.clone_id = c->clone_id;
-    ps.n_clones = fp.n_clones;
-    ps.cal = c->cal;
-    ps.calib_id = o->do_calib_camera_pose ? c->calib_id : -1;
-    ps.intr_id = o->do_calib_camera_intrinsics ? c->intr_id : -1;
-    ps.cp = d_cp;
-    ps.plane_sid = d_sid;
-    ps.n_planes = NP;
-    ps.n_slam = n_slam;
-    ps.slam_id = d_sidx;
-    ps.slam_p = d_slam_p;
-    if (c->pl_ktimer == 1) {
-      while ((int)c->pl_ev.size() < 2 * (jn + 1)) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        c->pl_ev.push_back(e);
-      }
-      HIPCHK(hipEventRecord(c->pl_ev[2 * jn], s));
-    }
-    // diagnostics: cycle stamps of the last plane's launch - only a library whose k_chol2 was compiled with them writes any
-    // (tools/build_c2_stamps.sh; the product build leaves them out: their tests cost 1 us per launch)
-    static const bool pl_stamps = getenv("OVP_PL_STAMPS") != nullptr && ovp_chol2_stamps_compiled();
-    static long long* d_stamps = nullptr;
-    if (pl_stamps) {
-      if (!d_stamps) HIPCHK(hipMalloc((void**)&d_stamps, sizeof(long long) * 2 * 16 * 32));
-      j0.stamps = d_stamps;
-    }
-    HIPCHK(ovp_launch_chol2(&j0, &j1, &ps, s));
-    if (c->pl_ktimer == 1) HIPCHK(hipEventRecord(c->pl_ev[2 * jn + 1], s));
-    if (gbp)  // an accepted plane also corrects the tables of ovp_cameras_upload, which the general rows of the planes behind it read
-      HIPCHK(ovp_launch_plane_gen_commit(c->pl_res + 4 * j.pl, c->pl_dx + (size_t)j.pl * n, c->gen_cal, c->gen_ncams, &gcols,
-                                         gen_calmask, s));
-    if (c->pl_sub_rest)
-      HIPCHK(ovp_launch_plane_sub_accum(c->pl_res + 4 * j.pl, c->Ab, c->pl_Asum, c->pl_dx + (size_t)j.pl * n,
-                                        c->pl_U + (size_t)j.pl * ld, nk, ld, s));
-    if (pl_stamps && jn == NJ - 1) {
-      long long h[2 * 16 * 32];
-      HIPCHK(hipStreamSynchronize(s));
-      HIPCHK(hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost));
-      const int ntb = (nk + 1 + 15) / 16;
-      const long long* e = h + (ntb + 1) * 16;
-      fprintf(stderr, "[plane tail, cycles] factor %lld | gate %lld | back substitution %lld | dx = L0 y %lld | commit %lld\n",
-              e[0] - h[0], e[1] - e[0], e[2] - e[1], e[3] - e[2], e[4] - e[3]);
-      if (atoi(getenv("OVP_PL_STAMPS")) >= 2) {
-        // per step, both parts of a split factorization, relative to part A's first stamp: elimination wave 0 [start | column
-        // there | eliminated | signalled], tile wave 0 [start | panel there | next column updated | published | step done]
-        const long long t0 = h[0];
-        for (int part = 0; part < (j0.split_h > 0 ? 2 : 1); ++part) {
-          const long long* hp = h + part * 16 * 32;
-          fprintf(stderr, " part %c: prologue stamps %lld %lld %lld\n", part ? 'B' : 'A', hp[13] - t0, hp[14] - t0, hp[15] - t0);
-          for (int k = 0; k < ntb; ++k) {
-            const long long* q = hp + k * 16;
-            if (!q[0] && !q[8]) continue;
-            // arrival word of the elimination step: what was missing of {column, panel, trailing} when wave 0 first looked (0 = there)
-            const long long aw = q[4] - 500500500;
-            const long long am = llround((double)aw / 1e6), ar = aw - am * 1000000, ap = llround((double)ar / 1e3), at = ar - ap * 1000;
-            fprintf(stderr, "  k=%2d E %7lld %7lld %7lld %7lld [%3lld %3lld %3lld] | T %7lld %7lld %7lld %7lld %7lld | T7 %7lld %7lld %7lld\n", k,
-                    q[0] - t0, q[1] - t0, q[2] - t0, q[3] - t0, am, ap, at, q[8] - t0, q[9] - t0, q[10] - t0, q[11] - t0, q[12] - t0,
-                    q[7] - t0, q[5] - t0, q[6] - t0);
-            if (k >= 2 && atoi(getenv("OVP_PL_STAMPS")) >= 3) fprintf(stderr, "        T own tiles final %7lld, column k+1 taken %7lld\n", q[13] - t0, q[14] - t0);
-          }
-          const long long* m = hp + (ntb + 1) * 16;
-          fprintf(stderr, "  tail: factor done %lld, gate %lld, backsolve %lld, dx %lld, commit %lld\n", m[0] - t0, m[1] - t0, m[2] - t0,
-                  m[3] - t0, m[4] - t0);
-        }
-      }
-      HIPCHK(hipMemset(d_stamps, 0, sizeof(long long) * 2 * 16 * 32));
-    }
-  }
-  // ---- the covariance, once:  P = L0 T^-1 L0^T = V^T V,  V = Lt^-1 L0^T ----
-  bool factor_enqueued = false;
-  if (NJ > 0) {
-    {
-      // chol of the accepted T (+ I) unless the last accepted plane left its factor behind; the second-generation kernel reads the
-      // current half of the double buffer itself (Chol2Job::sel) - no copy into c->T in front of it
-      if (n <= ovp_chol2_max_n() + 1) {
-        ovp::Chol2Job jt;
-        memset(&jt, 0, sizeof(jt));
-        jt.A = c->pl_Tbuf;
-        jt.sel = c->pl_cur;
-        jt.sel_xor = 0;
-        jt.sel_stride = tstride;
-        jt.n = n;
-        jt.ld = ld;
-        jt.add_identity = 1;
-        jt.mode = 0;
-        jt.flag = c->flags;
-        jt.Lpack = c->Ltp;
-        jt.Dinv_out = c->Dinv;
-        jt.skip_cond = c->pl_cur + 1;
-        HIPCHK(ovp_launch_chol2(&jt, nullptr, nullptr, s));
-      } else {
-        HIPCHK(ovp_launch_select_copy(c->T, c->pl_Tbuf, tstride, c->pl_cur, n, ld, 1, s));
-        HIPCHK(chol_of_T(c, c->T, n, ld, 1, c->pl_cur + 1, s));
-      }
-    }
-    HIPCHK(ovp_launch_fwdsub(c->Ltp, c->Dinv, c->L, c->Y, n, ld, 0, s));
-    HIPCHK(ovp_launch_gemm4c(1, 0, n, n, n, c->Y, ld, c->Y, ld, c->P, ld, 0, 1, c->flags, s));
-    // back into the state's own column order (unless a factorization failed: the resident P stays), and the factor of the
-    // covariance just formed for the point update behind the loop (P = V^T V: M = V^T, rows in state order) - one launch for both
-    const bool keep_factor = getenv("OVP_NO_KEPT_FACTOR") == nullptr;  // (read per call: the tests switch it)
-    const bool want_factor = keep_factor && !c->pl_sub_rest && n <= OVP_TILECHOL_NMAX;
-    if (want_factor && !c->Lkeep) HIPCHK(dalloc(&c->Lkeep, (size_t)c->n_max * ld));
-    if (c->pl_scatter_dst) {
-      HIPCHK(ovp_launch_unpermute_pair(c->P, c->Y, ld, c->pl_scatter_ids, n, c->pl_scatter_dst, want_factor ? c->Lkeep : nullptr, ld,
-                                       c->flags, c->pl_boost_active ? c->boost_vec : nullptr, s));
-      c->kept_boost = want_factor && c->pl_boost_active;  // Lkeep is a factor of P + diag(boost_vec): the point update on it
-                                                          // takes the amounts off at its end (ekf_from_gram)
-    } else if (want_factor) {
-      HIPCHK(ovp_launch_factor_from_V(c->Y, ld, nullptr, n, c->Lkeep, ld, s));
-    }
-    factor_enqueued = want_factor;
-  }
-  if (c->pl_ktimer) HIPCHK(hipEventRecord(c->pl_ev_loop[1], s));
-  // ---- results: one pinned block, one synchronisation ----
-  double* hres = (double*)c->pl_hres;
-  double* hdx = hres + 4 * (size_t)NP;
-  unsigned char* hused = (unsigned char*)(hdx + (size_t)n * NP);
-  // (behind `used`, each on a 64-byte line of its own: the flags, the sequence word)
-  char* hflags_pub = (char*)hused + (((size_t)F + 63) & ~(size_t)63);
-  volatile unsigned* hseq = (volatile unsigned*)(hflags_pub + 64);
-  *hseq = 0u;  // (its offset depends on NP, n and F: an earlier call's payload may have left the next sequence number there)
-  const unsigned seq = ++c->pl_pub_seq;
+  void *ah = nullptr, *ad = nullptr;
   {
-    char* dbase = (char*)c->pl_hres_dev;
-    auto dev_of = [&](const void* hp) { return dbase + ((const char*)hp - (const char*)c->pl_hres); };
-    hipLaunchKernelGGL(k_publish_plane_results, dim3(1), dim3(1024), 0, s, c->pl_res, 4 * NP, c->pl_dx, dx_planes ? n * NP : 0, c->pl_used,
-                       F, c->flags, (double*)dev_of(hres), (double*)dev_of(hdx), (unsigned char*)dev_of(hused), (int*)dev_of(hflags_pub),
-                       (volatile unsigned*)dev_of((const void*)hseq), seq);
-    HIPCHK(hipGetLastError());
+    const int rca = ovp_io_arena(c, in_bytes, &ah, &ad);
+    if (rca) return plane_bail(c, fork, rca);
   }
-  const double t_enq = host_now_ms();
-  {
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (__atomic_load_n((const unsigned*)hseq, __ATOMIC_ACQUIRE) != seq) {
-      if ((++spins & 0xFFFu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-        HIPCHK(hipStreamSynchronize(s));  // error path: surface a fault instead of spinning forever
-        if (__atomic_load_n((const unsigned*)hseq, __ATOMIC_ACQUIRE) != seq) return OVP_E_STATE;
-        break;
+  char* h = (char*)ah;
+  memcpy(h + o_uv, gbp->uv, sizeof(float) * 2 * GFM);
+  memcpy(h + o_ci, gbp->clone_idx, sizeof(int) * GFM);
+  memcpy(h + o_cam, gbp->cam_idx, sizeof(int) * GFM);
+  memcpy(h + o_nm, gbp->n_meas, sizeof(int) * GF);
+  memcpy(h + o_p, gbp->p_FinG, sizeof(double) * 3 * GF);
+  memcpy(h + o_list, g.glist.data(), sizeof(int) * g.glist.size());
+  HIPCHK(hipMemcpyAsync(ad, ah, in_bytes, hipMemcpyHostToDevice, s));
+  char* d = (char*)ad;
+  char* ds = (char*)c->pl_gen_dev;
+  ovp::PlaneGenParams& gp0 = gs->gp0;
+  gp0.fp = pre.fp;
+  gp0.fp.calmask = gs->calmask;
+  gp0.cam_cal = c->gen_cal;
+  for (int k = 0; k < OVP_MAX_CAMERAS; ++k) gp0.cam_fisheye[k] = c->gen_fisheye[k];
+  gp0.cc = gs->cols;
+  gp0.uv = (const float*)(d + o_uv);
+  gp0.clone_idx = (const int*)(d + o_ci);
+  gp0.cam_idx = (const int*)(d + o_cam);
+  gp0.n_meas = (const int*)(d + o_nm);
+  gp0.p_FinG = (const double*)(d + o_p);
+  gp0.max_meas = GM;
+  gp0.list = (const int*)(d + o_list);
+  gp0.mark = (int*)ds;
+  gp0.mark_stride = (int)mark_stride;
+  gp0.hp = (double*)(ds + o_hp);
+  gp0.hp_stride = hp_stride;
+  return 0;
+}
+
+// ---- one plane's enqueue: the parameter blocks of its launches ----
+struct PlaneCall {  // what every plane of a call shares
+  const ovp_update_opts* o; const ovp_plane_batch* pb; const PlaneLoopView* v; const PlanePre* pre; const PlaneStage* st;
+  const PlaneGenStage* gs; int NJ; double white_c, noise_scale;
+};
+static ovp::PlaneParams plane_feat_params(const ovp_ctx* c, const PlaneCall& k, const PlaneJobH& j) {
+  ovp::PlaneParams pp;
+  pp.feat_list = k.st->feat + j.start;
+  pp.n_local = j.nf;
+  pp.plane = j.pl;
+  pp.in_state = j.in_state;
+  pp.plane_sid = j.sid;
+  pp.white_c = k.white_c;
+  pp.cp = k.st->cp;
+  pp.cp_fej = k.st->cp_fej;
+  pp.cst = c->pl_cst;
+  return pp;
+}
+static ovp::PlaneGenParams plane_gen_params(const ovp_ctx* c, const PlaneCall& k, const PlaneJobH& j, int nk, int nsplit, int ntile_pl) {
+  ovp::PlaneGenParams g = k.gs->gp0;
+  g.list = k.gs->gp0.list + j.g_start;
+  g.n_local = j.ng;
+  g.plane = j.pl;
+  g.in_state = j.in_state;
+  g.plane_sid = j.sid;
+  g.white_c = k.white_c;
+  g.cp = k.st->cp;
+  g.cp_fej = k.st->cp_fej;
+  g.n = nk;
+  g.hp_stride = (size_t)ovp::PG_ROWS * (nk + 4);
+  g.part_split = c->part + (size_t)nsplit * ntile_pl * 256;
+  g.cst_rec = c->pl_cst + (size_t)j.nf * 10;
+  return g;
+}
+static ovp::PlaneAsm plane_asm_params(const ovp_ctx* c, const PlaneCall& k, const PlaneJobH& j, int jn, int nk, int chunks, int nsplit,
+                                      int ntile_pl) {
+  const int ld = c->ld;
+  ovp::PlaneAsm pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.gramS = c->gramS;
+  pa.n_clones = k.pre->fp.n_clones;
+  pa.n_chunks = chunks;
+  pa.part = c->part;
+  pa.n_split = nsplit + (j.ng > 0 ? 1 : 0);
+  pa.ntile = ntile_pl;
+  pa.colmap = c->colmap;
+  pa.n = nk;
+  pa.plane_sid = j.sid;
+  pa.in_state = j.in_state;
+  pa.cst = c->pl_cst;
+  pa.nf = j.nf + (j.ng > 0 ? 1 : 0);
+  pa.n_slam = j.in_state ? 0 : k.pre->n_slam;
+  pa.plane1 = j.pl + 1;
+  pa.slam_plane = k.st->slam_plane;
+  pa.slam_id = k.st->slam_id;
+  pa.slam_p = k.st->slam_p;
+  pa.slam_p_fej = k.st->slam_p_fej;
+  pa.cp = k.st->cp + 3 * j.pl;
+  pa.cp_fej = k.st->cp_fej + 3 * j.pl;
+  pa.white_c = k.white_c;
+  pa.do_fej = k.pre->fp.do_fej;
+  pa.Ab = c->Ab;
+  pa.lda = ld;
+  pa.perm = k.st->perm + (size_t)jn * c->n;
+  pa.An = c->pl_An;
+  pa.ldn = ld;
+  pa.bn = c->pl_bn;
+  pa.eps = 1e-12;
+  pa.scal = c->pl_scal;
+  return pa;
+}
+// both factorizations of a plane: j0 = the update's T_try on the leading block (with the split over two workgroups), j1 = the range part
+static void plane_chol_jobs(const ovp_ctx* c, const PlaneCall& k, const PlaneJobH& j, int nk, unsigned seq, ovp::Chol2Job* j0,
+                            ovp::Chol2Job* j1) {
+  const int ld = c->ld;
+  memset(j0, 0, sizeof(*j0));
+  memset(j1, 0, sizeof(*j1));
+  j0->A = c->pl_Tbuf;
+  j0->sel = c->pl_cur;
+  j0->sel_xor = 1;
+  j0->sel_stride = k.pre->tstride;
+  j0->n = nk;
+  j0->ld = ld;
+  j0->add_identity = 1;
+  j0->mode = 1;
+  j0->brow = c->pl_crow;
+  j0->flag = c->flags;
+  j1->A = c->pl_An;
+  j1->n = j.n_inv_cols;
+  j1->ld = ld;
+  j1->add_identity = 0;
+  j1->mode = 2;
+  j1->brow = c->pl_bn;
+  j1->flag = c->flags + 2;
+  j1->piv_floor = 1e-5;
+  // The update part on two workgroups: tile columns < h and the rest (k_chol2.hip).  Measured (r03, A/B in one call): at 16 tile
+  // columns (N = 240) nothing is gained (2.91 against 2.81 ms per config-3 plane loop for h = 5 .. 8: exports + a second gate
+  // hand-over cost what the second CU's f64 pipe gives), so one workgroup stays the default there; from 17 tile columns on
+  // (N > 255) the tile registers of one workgroup spill and the split wins (config 4, N = 285: 7.91 ms for h = 5 or 6, 8.10 for
+  // 7 or 8, 8.69 unsplit).  OVP_C2_SPLIT: 0 = never, h = forced.
+  const char* split_s = getenv("OVP_C2_SPLIT");  // (read per call: the tests switch it)
+  const int split_env = split_s ? atoi(split_s) : -1;
+  const int nb = nk + 1, ntb = (nb + 15) / 16;
+  const int nst = (nb % 16 == 1) ? ntb - 1 : ntb;  // a border row alone in its tile row takes no step
+  int h = ntb >= 17 ? nst / 3 : 0;  // part B also runs the back half of the chain: 5 - 6 of 18 steps measured best (7.91 ms per
+                                    // config-4 plane loop against 8.10 for 7 or 8 and 8.69 unsplit)
+  if (split_env >= 0) h = split_env < ntb - 1 ? split_env : 0;
+  if (h > 9) h = 9;  // pl_xbuf holds nine exported steps
+  j0->split_h = h;
+  j0->xbuf = c->pl_xbuf;
+  j0->xflag = c->pl_xflag;
+  j0->xseq = seq;
+}
+static ovp::PlaneSolve plane_solve_params(const ovp_ctx* c, const PlaneCall& k, const PlaneJobH& j, int jn, unsigned seq) {
+  const int n = c->n;
+  ovp::PlaneSolve ps;
+  memset(&ps, 0, sizeof(ps));
+  ps.scal = c->pl_scal;
+  ps.range_done = c->pl_range_done;
+  ps.seq = seq;
+  ps.xzz = c->pl_xy;
+  ps.xy = c->pl_xy + 16;
+  ps.xsync = c->pl_xflag + 32;
+  ps.thr = j.thr;
+  ps.rows_live = j.rows_live;
+  ps.rows_u = j.rows_u;
+  ps.n_involved = j.n_inv_cols;
+  ps.force = k.pb->force_decision ? (int)k.pb->force_decision[j.pl] : -1;
+  ps.noise_scale = k.noise_scale;
+  ps.tol_strict = 1e-5;
+  ps.tol_loose = 1e-5;
+  ps.res_out = c->pl_res + 4 * j.pl;
+  ps.L0 = c->L;
+  ps.ld0 = c->ld;
+  ps.n_full = n;
+  ps.dx_out = c->pl_dx + (size_t)j.pl * n;
+  ps.dx_last = c->pl_dxlast;
+  ps.cur = c->pl_cur;
+  // The covariance product behind the loop needs the factor of the last ACCEPTED T.  The last few planes leave theirs behind when
+  // they are accepted (~8 us of stores each); if one of them stays the last accepted plane, the k_tilechol behind the loop
+  // (94 us at N = 240) finds nothing to do.  Which plane that is, is decided on the device.
+  const int emit_last = 4;
+  ps.cond = c->pl_cur + 1;
+  ps.seq_plane = jn + 1;
+  ps.emit = (jn >= k.NJ - emit_last) ? 1 : 0;
+  ps.Lpack = c->Ltp;
+  ps.Dinv = c->Dinv;
+  ps.feat_list = k.st->feat + j.start;
+  ps.n_feat_local = j.nf;
+  ps.feat_used = c->pl_used;
+  ps.clone_R = c->clone_R;
+  ps.clone_p = c->clone_p;
+  ps.clone_id = c->clone_id;
+  ps.n_clones = k.pre->fp.n_clones;
+  ps.cal = c->cal;
+  ps.calib_id = k.o->do_calib_camera_pose ? c->calib_id : -1;
+  ps.intr_id = k.o->do_calib_camera_intrinsics ? c->intr_id : -1;
+  ps.cp = k.st->cp;
+  ps.plane_sid = k.st->sid;
+  ps.n_planes = k.pb->n_planes;
+  ps.n_slam = k.pre->n_slam;
+  ps.slam_id = k.st->slam_id;
+  ps.slam_p = k.st->slam_p;
+  return ps;
+}
+
+// diagnostics: cycle stamps of the last plane's launch - only a library whose k_chol2 was compiled with them writes any
+// (tools/build_c2_stamps.sh; the product build leaves them out: their tests cost 1 us per launch).  *out = nullptr: off.
+static int plane_stamps_buffer(long long** out) {
+  static const bool pl_stamps = getenv("OVP_PL_STAMPS") != nullptr && ovp_chol2_stamps_compiled();
+  static long long* d_stamps = nullptr;
+  if (pl_stamps && !d_stamps) HIPCHK(hipMalloc((void**)&d_stamps, sizeof(long long) * 2 * 16 * 32));
+  *out = pl_stamps ? d_stamps : nullptr;
+  return 0;
+}
+static int plane_stamps_dump(long long* d_stamps, int nk, int split_h, hipStream_t s) {
+  long long h[2 * 16 * 32];
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost));
+  const int ntb = (nk + 1 + 15) / 16;
+  const long long* e = h + (ntb + 1) * 16;
+  fprintf(stderr, "[plane tail, cycles] factor %lld | gate %lld | back substitution %lld | dx = L0 y %lld | commit %lld\n",
+          e[0] - h[0], e[1] - e[0], e[2] - e[1], e[3] - e[2], e[4] - e[3]);
+  if (atoi(getenv("OVP_PL_STAMPS")) >= 2) {
+    // per step, both parts of a split factorization, relative to part A's first stamp: elimination wave 0 [start | column
+    // there | eliminated | signalled], tile wave 0 [start | panel there | next column updated | published | step done]
+    const long long t0 = h[0];
+    for (int part = 0; part < (split_h > 0 ? 2 : 1); ++part) {
+      const long long* hp = h + part * 16 * 32;
+      fprintf(stderr, " part %c: prologue stamps %lld %lld %lld\n", part ? 'B' : 'A', hp[13] - t0, hp[14] - t0, hp[15] - t0);
+      for (int k = 0; k < ntb; ++k) {
+        const long long* q = hp + k * 16;
+        if (!q[0] && !q[8]) continue;
+        // arrival word of the elimination step: what was missing of {column, panel, trailing} when wave 0 first looked (0 = there)
+        const long long aw = q[4] - 500500500;
+        const long long am = llround((double)aw / 1e6), ar = aw - am * 1000000, ap = llround((double)ar / 1e3), at = ar - ap * 1000;
+        fprintf(stderr, "  k=%2d E %7lld %7lld %7lld %7lld [%3lld %3lld %3lld] | T %7lld %7lld %7lld %7lld %7lld | T7 %7lld %7lld %7lld\n", k,
+                q[0] - t0, q[1] - t0, q[2] - t0, q[3] - t0, am, ap, at, q[8] - t0, q[9] - t0, q[10] - t0, q[11] - t0, q[12] - t0,
+                q[7] - t0, q[5] - t0, q[6] - t0);
+        if (k >= 2 && atoi(getenv("OVP_PL_STAMPS")) >= 3) fprintf(stderr, "        T own tiles final %7lld, column k+1 taken %7lld\n", q[13] - t0, q[14] - t0);
       }
-      __builtin_ia32_pause();
+      const long long* m = hp + (ntb + 1) * 16;
+      fprintf(stderr, "  tail: factor done %lld, gate %lld, backsolve %lld, dx %lld, commit %lld\n", m[0] - t0, m[1] - t0, m[2] - t0,
+              m[3] - t0, m[4] - t0);
     }
-    memcpy(c->h_flags, hflags_pub, sizeof(int) * 4);
   }
-  {
-    c->host_acc[0] += t_first - t_entry;
-    c->host_acc[1] += t_enq - t_entry;
-    c->host_acc[2] += host_now_ms() - t_enq;
-    c->host_acc[3] += 1.0;
+  HIPCHK(hipMemset(d_stamps, 0, sizeof(long long) * 2 * 16 * 32));
+  return 0;
+}
+
+static int plane_enqueue(ovp_ctx* c, const PlaneCall& k, const PlaneJobH& j, int jn, ForkGuard& fork) {
+  const int n = c->n, ld = c->ld;
+  const ovp::FeatParams& fp = k.pre->fp;
+  hipStream_t s = c->stream;
+  // leading block this plane's products and factorization run on (plane_update_ordered): every column involved so far
+  const int nk = k.v->ordered ? k.v->nl[j.pl] : n;
+  // (1) per-feature rows
+  const ovp::PlaneParams pp = plane_feat_params(c, k, j);
+  ovp::FeatParams fpl = fp;
+  fpl.n = nk;
+  fpl.P = c->P;
+  int chunks = (2 * j.nf + c->rows_per_chunk - 1) / c->rows_per_chunk;
+  int nsplit = 1;
+  if (j.nf > 0) {
+    HIPCHK(ovp_launch_plane_feat(&fpl, &pp, j.nf, s));
+    // (2) Gram products
+    HIPCHK(ovp_launch_gram_pair(c->rec, fp.n_clones, j.nf, c->rows_per_chunk, chunks, c->gramS, c->G, 3 * j.nf, c->ldg, nk + 4,
+                                c->n_split, c->part, &nsplit, s));
+  } else {  // a plane with general features only: an empty structured Gram (one chunk of zeros per clone), no G^T G split
+    chunks = 1;
+    nsplit = 0;
+    HIPCHK(hipMemsetAsync(c->gramS, 0, sizeof(double) * (size_t)fp.n_clones * OVP_GRAM_ELEMS, s));
   }
+  // (2b) the plane's general features: one more split of the partials and one more moment record (k_plane_feat_gen.hip); a plane
+  // without any enqueues nothing here
+  const int nt16_pl = (nk + 4 + 15) / 16, ntile_pl = nt16_pl * (nt16_pl + 1) / 2;
+  if (j.ng > 0) {
+    const ovp::PlaneGenParams g = plane_gen_params(c, k, j, nk, nsplit, ntile_pl);
+    HIPCHK(ovp_launch_plane_feat_gen(&g, s));
+  }
+  // (3) pair on the state columns, normalised Gram, residual energy
+  const ovp::PlaneAsm pa = plane_asm_params(c, k, j, jn, nk, chunks, nsplit, ntile_pl);
+  HIPCHK(ovp_launch_plane_assemble2(&pa, s));
+  // (4) W = A L0 ;  T_try = T_cur + L0^T W ;  c = L0^T b
+  HIPCHK(join_chol(fork));  // (first plane: L0 comes from the side stream)
+  HIPCHK(ovp_launch_gemm4(0, 0, nk, nk, nk, c->Ab, ld, c->L, ld, c->W1, ld, 0, 0, s));
+  HIPCHK(ovp_launch_plane_dT(nk, c->L, ld, c->W1, c->Ab + (size_t)nk * ld, c->pl_Tbuf, k.pre->tstride, c->pl_cur, c->pl_crow, s));
+  // (5) both factorizations, gate, solve, commit
+  const unsigned seq = ++c->pl_seq;
+  ovp::Chol2Job j0, j1;
+  plane_chol_jobs(c, k, j, nk, seq, &j0, &j1);
+  const ovp::PlaneSolve ps = plane_solve_params(c, k, j, jn, seq);
+  if (c->pl_ktimer == 1) {
+    HIPCHK(ensure_events(c->pl_ev, 2 * (size_t)(jn + 1)));
+    HIPCHK(hipEventRecord(c->pl_ev[2 * jn], s));
+  }
+  long long* d_stamps = nullptr;
+  if (const int r = plane_stamps_buffer(&d_stamps)) return r;
+  if (d_stamps) j0.stamps = d_stamps;
+  HIPCHK(ovp_launch_chol2(&j0, &j1, &ps, s));
+  if (c->pl_ktimer == 1) HIPCHK(hipEventRecord(c->pl_ev[2 * jn + 1], s));
+  if (k.v->gen)  // an accepted plane also corrects the tables of ovp_cameras_upload, which the general rows of the planes behind it read
+    HIPCHK(ovp_launch_plane_gen_commit(c->pl_res + 4 * j.pl, c->pl_dx + (size_t)j.pl * n, c->gen_cal, c->gen_ncams, &k.gs->cols,
+                                       k.gs->calmask, s));
+  if (k.v->marginal)
+    HIPCHK(ovp_launch_plane_sub_accum(c->pl_res + 4 * j.pl, c->Ab, c->pl_Asum, c->pl_dx + (size_t)j.pl * n,
+                                      c->pl_U + (size_t)j.pl * ld, nk, ld, s));
+  if (d_stamps && jn == k.NJ - 1) return plane_stamps_dump(d_stamps, nk, j0.split_h, s);
+  return 0;
+}
+
+// ---- the covariance, once:  P = L0 T^-1 L0^T = V^T V,  V = Lt^-1 L0^T ----
+static int plane_cov_product(ovp_ctx* c, const PlaneLoopView& v, size_t tstride, bool* factor_enqueued) {
+  const int n = c->n, ld = c->ld;
+  hipStream_t s = c->stream;
+  // chol of the accepted T (+ I) unless the last accepted plane left its factor behind; the second-generation kernel reads the
+  // current half of the double buffer itself (Chol2Job::sel) - no copy into c->T in front of it
+  if (n <= ovp_chol2_max_n() + 1) {
+    ovp::Chol2Job jt;
+    memset(&jt, 0, sizeof(jt));
+    jt.A = c->pl_Tbuf;
+    jt.sel = c->pl_cur;
+    jt.sel_xor = 0;
+    jt.sel_stride = tstride;
+    jt.n = n;
+    jt.ld = ld;
+    jt.add_identity = 1;
+    jt.mode = 0;
+    jt.flag = c->flags;
+    jt.Lpack = c->Ltp;
+    jt.Dinv_out = c->Dinv;
+    jt.skip_cond = c->pl_cur + 1;
+    HIPCHK(ovp_launch_chol2(&jt, nullptr, nullptr, s));
+  } else {
+    HIPCHK(ovp_launch_select_copy(c->T, c->pl_Tbuf, tstride, c->pl_cur, n, ld, 1, s));
+    HIPCHK(chol_of_T(c, c->T, n, ld, 1, c->pl_cur + 1, s));
+  }
+  HIPCHK(ovp_launch_fwdsub(c->Ltp, c->Dinv, c->L, c->Y, n, ld, 0, s));
+  HIPCHK(ovp_launch_gemm4c(1, 0, n, n, n, c->Y, ld, c->Y, ld, c->P, ld, 0, 1, c->flags, s));
+  // back into the state's own column order (unless a factorization failed: the resident P stays), and the factor of the
+  // covariance just formed for the point update behind the loop (P = V^T V: M = V^T, rows in state order) - one launch for both
+  const bool keep_factor = getenv("OVP_NO_KEPT_FACTOR") == nullptr;  // (read per call: the tests switch it)
+  const bool want_factor = keep_factor && !v.marginal && n <= OVP_TILECHOL_NMAX;
+  if (want_factor && !c->Lkeep) HIPCHK(dalloc(&c->Lkeep, (size_t)c->n_max * ld));
+  if (v.scatter_dst) {
+    HIPCHK(ovp_launch_unpermute_pair(c->P, c->Y, ld, v.scatter_ids, n, v.scatter_dst, want_factor ? c->Lkeep : nullptr, ld,
+                                     c->flags, v.boost ? c->boost_vec : nullptr, s));
+    c->kept_boost = want_factor && v.boost;  // Lkeep is a factor of P + diag(boost_vec): the point update on it
+                                             // takes the amounts off at its end (ekf_from_gram)
+  } else if (want_factor) {
+    HIPCHK(ovp_launch_factor_from_V(c->Y, ld, nullptr, n, c->Lkeep, ld, s));
+  }
+  *factor_enqueued = want_factor;
+  return 0;
+}
+
+// ---- results: one pinned block, one wait ----
+// [chi2, decision, .. per plane | dx per plane | consumed features], and behind `used`, each on a 64-byte line of its own: the
+// flags, the sequence word
+struct PlaneResBlock { double *res, *dx; unsigned char* used; char* flags; volatile unsigned* seq; };
+static PlaneResBlock plane_res_block(const ovp_ctx* c, int NP) {
+  PlaneResBlock b;
+  b.res = (double*)c->pl_hres;
+  b.dx = b.res + 4 * (size_t)NP;
+  b.used = (unsigned char*)(b.dx + (size_t)c->n * NP);
+  b.flags = (char*)b.used + (((size_t)c->n_feats + 63) & ~(size_t)63);
+  b.seq = (volatile unsigned*)(b.flags + 64);
+  return b;
+}
+static int plane_publish(ovp_ctx* c, const PlaneResBlock& b, int NP, bool want_dx, unsigned* seq_out) {
+  *b.seq = 0u;  // (its offset depends on NP, n and F: an earlier call's payload may have left the next sequence number there)
+  const unsigned seq = *seq_out = ++c->pl_pub_seq;
+  char* dbase = (char*)c->pl_hres_dev;
+  auto dev_of = [&](const void* hp) { return dbase + ((const char*)hp - (const char*)c->pl_hres); };
+  hipLaunchKernelGGL(k_publish_plane_results, dim3(1), dim3(1024), 0, c->stream, c->pl_res, 4 * NP, c->pl_dx, want_dx ? c->n * NP : 0,
+                     c->pl_used, c->n_feats, c->flags, (double*)dev_of(b.res), (double*)dev_of(b.dx), (unsigned char*)dev_of(b.used),
+                     (int*)dev_of(b.flags), (volatile unsigned*)dev_of((const void*)b.seq), seq);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// host clocks and device timers of the call that has just been waited for
+static void plane_account(ovp_ctx* c, double t_entry, double t_first, double t_enq, int NJ) {
+  c->host_acc[0] += t_first - t_entry;
+  c->host_acc[1] += t_enq - t_entry;
+  c->host_acc[2] += host_now_ms() - t_enq;
+  c->host_acc[3] += 1.0;
   if (c->pl_ktimer) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, c->pl_ev_loop[0], c->pl_ev_loop[1]) == hipSuccess) c->host_acc[7] += ms;
@@ -1181,20 +1245,27 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
         c->pl_klaunches += 1;
       }
     }
+}
+// The pinned block into the caller's arrays, and what a failed factorization means.  *retry_psd: nothing was committed and chol(P)
+// hit a non-positive pivot - the caller runs the same loop once more on the pivot-dropping factor.
+static int plane_unpack(ovp_ctx* c, const PlaneLoopView& v, const PlaneGroups& g, const PlaneResBlock& b, int NP, const PlaneOut& out,
+                        bool factor_enqueued, bool* retry_psd) {
+  const int n = c->n, F = c->n_feats;
+  const double* hres = b.res;
   c->pl_used_valid = true;
-  c->h_pl_used.assign(hused, hused + F);
-  if (dx_planes) memcpy(dx_planes, hdx, sizeof(double) * (size_t)n * NP);
-  if (feat_used && F) memcpy(feat_used, hused, (size_t)F);
-  if (gbp) {  // the general features an accepted plane consumed (the host knows each plane's list)
-    c->pl_gen_used.assign((size_t)GF, 0);
-    for (const PlaneJobH& j : jobs)
+  c->h_pl_used.assign(b.used, b.used + F);
+  if (out.dx_planes) memcpy(out.dx_planes, b.dx, sizeof(double) * (size_t)n * NP);
+  if (out.feat_used && F) memcpy(out.feat_used, b.used, (size_t)F);
+  if (v.gen && v.gen_used) {  // the general features an accepted plane consumed (the host knows each plane's list)
+    memset(v.gen_used, 0, (size_t)v.gen->n_feats);
+    for (const PlaneJobH& j : g.jobs)
       if (hres[4 * j.pl + 1] > 0.5)
-        for (int k = 0; k < j.ng; ++k) c->pl_gen_used[glist[j.g_start + k]] = 1;
+        for (int k = 0; k < j.ng; ++k) v.gen_used[g.glist[j.g_start + k]] = 1;
   }
-  for (const PlaneJobH& j : jobs) {
-    if (plane_ok) plane_ok[j.pl] = hres[4 * j.pl + 1] > 0.5 ? 1 : 0;
-    if (plane_chi2) plane_chi2[j.pl] = hres[4 * j.pl];
-    if (plane_dof) plane_dof[j.pl] = j.rows_u;
+  for (const PlaneJobH& j : g.jobs) {
+    if (out.plane_ok) out.plane_ok[j.pl] = hres[4 * j.pl + 1] > 0.5 ? 1 : 0;
+    if (out.plane_chi2) out.plane_chi2[j.pl] = hres[4 * j.pl];
+    if (out.plane_dof) out.plane_dof[j.pl] = j.rows_u;
   }
   const int bad = c->h_flags[0] | c->h_flags[2];  // (the device words were cleared by the publishing kernel)
   if (bad) {
@@ -1203,21 +1274,116 @@ extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, cons
     // committed their corrections to the device tables: those no longer belong to the resident covariance - the caller must
     // upload the state again (OVP_E_STATE until then).  chol(P) itself failing (singular prior) happens in front of every plane.
     bool any_committed = false;
-    for (const PlaneJobH& j : jobs) any_committed |= hres[4 * j.pl + 1] > 0.5;
+    for (const PlaneJobH& j : g.jobs) any_committed |= hres[4 * j.pl + 1] > 0.5;
     if (any_committed) c->have_state = false;
-    if (bad == 1 && !any_committed && !c->pl_psd) {
+    if (bad == 1 && !any_committed && !v.psd) {
       // chol(P) hit a non-positive pivot: the prior is only positive SEMI-definite.  Nothing was committed and the resident
-      // covariance was not written - the same loop once more on the pivot-dropping factor (chol_of_P).
-      c->pl_psd = true;
-      const int rc2 = ovp_msckf_plane_update(c, o, pb, dx_planes, plane_ok, plane_chi2, plane_dof, feat_used);
-      c->pl_psd = false;
-      return rc2;
+      // covariance was not written.
+      *retry_psd = true;
+      return 0;
     }
   }
   if (bad & 2) return OVP_E_TIMEOUT;
   if (bad) return OVP_E_NOTSPD;
   c->have_factor = factor_enqueued;
   return 0;
+}
+
+// ---- UpdaterMSCKF::update, per-plane loop (second generation) ------------------------------------------------------------
+// See k_plane2.hip for the algebra.  Everything of a call is enqueued without a host synchronisation: the per-call tables go
+// through one pinned staging block, the results come back through one pinned block the host waits for on a sequence word.
+// The caller has checked c, o, pb and the context's state (plane_update_entry).
+static int plane_loop(ovp_ctx* c, const ovp_update_opts* o_in, const ovp_plane_batch* pb, const PlaneLoopView& v, const PlaneOut& out) {
+  const int n = c->n, F = c->n_feats, NP = pb->n_planes;
+  // skip_plane_used is an option of the POINT update that follows; the plane loop itself produces the mask
+  ovp_update_opts o_local = *o_in;
+  o_local.skip_plane_used = 0;
+  const ovp_update_opts* o = &o_local;
+  c->pl_used_valid = false;  // (also the retry's: the first attempt's mask no longer counts)
+  if (n > ovp_chol2_max_n()) return OVP_E_CAPACITY;  // (plane_update_ordered hands over a sub-state the factorization can take)
+  if (out.feat_used) memset(out.feat_used, 0, (size_t)F);
+  for (int pl = 0; pl < NP; ++pl) {
+    if (out.plane_ok) out.plane_ok[pl] = 0;
+    if (out.plane_chi2) out.plane_chi2[pl] = 0.0;
+    if (out.plane_dof) out.plane_dof[pl] = 0;
+  }
+  if (out.dx_planes && NP > 0) memset(out.dx_planes, 0, sizeof(double) * (size_t)n * NP);
+  if (NP == 0) {  // a frame without planes: nothing is consumed, and a point update with skip_plane_used may follow
+    if (F) HIPCHK(hipMemsetAsync(c->pl_used, 0, (size_t)F, c->stream));
+    c->h_pl_used.assign((size_t)F, 0);
+    c->pl_used_valid = true;
+    return 0;
+  }
+  hipStream_t s = c->stream;
+  ForkGuard fork{s, c->ev_join, c->stream2, false};
+  PlanePre pre;
+  int rc = plane_prelaunch(c, o, pb, v, fork, &pre);
+  if (rc) return rc;
+  PlaneGroups g;
+  rc = plane_group(c, o, pb, v, pre.n_slam, &g);
+  if (rc) return plane_bail(c, fork, rc);
+  const int NJ = (int)g.jobs.size();
+  if (NJ == 0 && pre.any_candidate) {  // chol(P)'s verdict concerns nobody
+    HIPCHK(join_chol(fork));
+    HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 4, s));
+  }
+  PlaneStage st;
+  rc = plane_stage_upload(c, pb, g, pre, &st);
+  if (rc) return rc;
+  PlaneGenStage gs;
+  rc = plane_gen_upload(c, o, v, pre, g, fork, &gs);
+  if (rc) return rc;
+  // weight of the expected energy of the rounding-decided rows in the gate statistic (k_chol2.hip); OVP_PL_NOISE_SCALE overrides the
+  // calibrated constant for the study that produced it (tools/plane_gate_agreement.py --fit)
+  double noise_scale = OVP_PLANE_NOISE_KAPPA;
+  if (const char* ns_env = getenv("OVP_PL_NOISE_SCALE")) noise_scale = atof(ns_env);  // (read per call)
+  const PlaneCall call{o, pb, &v, &pre, &st, &gs, NJ, 1.0 / o->sigma_constraint, noise_scale};
+  for (int jn = 0; jn < NJ; ++jn) {
+    rc = plane_enqueue(c, call, g.jobs[jn], jn, fork);
+    if (rc) return rc;
+  }
+  bool factor_enqueued = false;
+  if (NJ > 0) {
+    rc = plane_cov_product(c, v, pre.tstride, &factor_enqueued);
+    if (rc) return rc;
+  }
+  if (c->pl_ktimer) HIPCHK(hipEventRecord(c->pl_ev_loop[1], s));
+  const PlaneResBlock blk = plane_res_block(c, NP);
+  unsigned seq = 0;
+  rc = plane_publish(c, blk, NP, out.dx_planes != nullptr, &seq);
+  if (rc) return rc;
+  const double t_enq = host_now_ms();
+  rc = ovp_wait_seq(blk.seq, seq, s);
+  if (rc) return rc;
+  memcpy(c->h_flags, blk.flags, sizeof(int) * 4);
+  plane_account(c, v.t_entry, pre.t_first, t_enq, NJ);
+  bool retry_psd = false;
+  rc = plane_unpack(c, v, g, blk, NP, out, factor_enqueued, &retry_psd);
+  if (!retry_psd) return rc;
+  PlaneLoopView v2 = v;  // the same loop once more on the pivot-dropping factor (chol_of_P)
+  v2.psd = true;
+  if (!v.ordered) v2.t_entry = host_now_ms();
+  return plane_loop(c, o, pb, v2, out);
+}
+
+// what both entry points share behind their argument checks: v carries the general features, if any
+static int plane_update_entry(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, PlaneLoopView v, const PlaneOut& out) {
+  if (!c->have_state || !c->have_cov || !c->have_batch) return OVP_E_STATE;
+  if (c->h_n_meas.empty() && c->n_feats > 0) return OVP_E_STATE;  // needs ovp_batch_upload (host copy of the layout)
+  v.t_entry = host_now_ms();
+  c->have_factor = false;
+  c->pl_used_valid = false;
+  const int rcu = ensure_pl_used(c);
+  if (rcu) return rcu;
+  const bool natural_order = getenv("OVP_PL_NATURAL_ORDER") != nullptr;  // A/B: the loop on all n columns in the state's order
+  if (pb->n_planes > 0 && (c->n > ovp_chol2_max_n() || !natural_order)) return plane_update_ordered(c, o, pb, v, out);
+  return plane_loop(c, o, pb, v, out);
+}
+
+extern "C" int ovp_msckf_plane_update(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, double* dx_planes,
+                                      uint8_t* plane_ok, double* plane_chi2, int* plane_dof, uint8_t* feat_used) {
+  if (!c || !o || !pb || pb->n_planes < 0) return OVP_E_ARG;
+  return plane_update_entry(c, o, pb, PlaneLoopView{}, PlaneOut{dx_planes, plane_ok, plane_chi2, plane_dof, feat_used});
 }
 
 // ---- the plane loop with the on-plane features of a general batch behind the batch's (update/UpdaterHelper.cpp:335-344 over every
@@ -1243,15 +1409,15 @@ extern "C" int ovp_msckf_plane_update_general(ovp_ctx* c, const ovp_update_opts*
     }
   }
   if (gen_used && GF > 0) memset(gen_used, 0, (size_t)GF);
-  if (!any) return ovp_msckf_plane_update(c, o, pb, dx_planes, plane_ok, plane_chi2, plane_dof, feat_used);
-  c->pl_gen_b = gb;
-  c->pl_gen_plane = plane_of_gen;
-  c->pl_gen_used.assign((size_t)GF, 0);
-  const int rc = ovp_msckf_plane_update(c, o, pb, dx_planes, plane_ok, plane_chi2, plane_dof, feat_used);
-  c->pl_gen_b = nullptr;
-  c->pl_gen_plane = nullptr;
-  c->pl_gen_pos.clear();
-  if (!rc && gen_used) memcpy(gen_used, c->pl_gen_used.data(), (size_t)GF);
+  const PlaneOut out{dx_planes, plane_ok, plane_chi2, plane_dof, feat_used};
+  PlaneLoopView v;
+  if (!any) return plane_update_entry(c, o, pb, v, out);
+  std::vector<unsigned char> marks((size_t)GF, 0);  // (the caller's array is written only by a call that succeeds)
+  v.gen = gb;
+  v.plane_of_gen = plane_of_gen;
+  v.gen_used = marks.data();
+  const int rc = plane_update_entry(c, o, pb, v, out);
+  if (!rc && gen_used) memcpy(gen_used, marks.data(), (size_t)GF);
   return rc;
 }
 
@@ -1274,12 +1440,11 @@ extern "C" int ovp_plane_init(ovp_ctx* c, const ovp_update_opts* o, const ovp_pl
     if (dx_planes) memset(dx_planes + (size_t)pl * dx_stride, 0, sizeof(double) * dx_stride);
   }
   if (NP == 0) return 0;
-  c->pl_n_slam = 0;
   int rc = fill_feat_params(c, o);
   if (rc) return rc;
   rc = plane_buffers(c, NP);
   if (rc) return rc;
-  rc = plane2_buffers(c, NP, 0, 0);  // (pl_crow: scale vector of the pivot-dropping factor, chol_of_P on a semi-definite prior)
+  rc = plane2_buffers(c, 0, 0);  // (pl_crow: scale vector of the pivot-dropping factor, chol_of_P on a semi-definite prior)
   if (rc) return rc;
   hipStream_t s = c->stream;
   const int ncal = (o->do_calib_camera_pose ? 6 : 0) + (o->do_calib_camera_intrinsics ? 8 : 0);
@@ -1297,31 +1462,15 @@ extern "C" int ovp_plane_init(ovp_ctx* c, const ovp_update_opts* o, const ovp_pl
   // planes, per frame: 0.198 ms against 0.216 on the whole state.  OVP_PLANE_INIT_SUB=0: the whole state (<= 288 columns; A/B, tests).
   const char* sub_env = getenv("OVP_PLANE_INIT_SUB");  // (read per call)
   const bool whole_state = sub_env && sub_env[0] == '0' && c->n <= OVP_TILECHOL_NMAX;
-  std::vector<int> sub_ids, sub_pos;
   SubTables sub_t;
   int ns = 0;
   if (!whole_state) {
-    const int n = c->n;
-    sub_pos.assign((size_t)c->n_max, -1);
-    bool bad_id = false;
-    auto place = [&](int id, int sz) {
-      if (id < 0 || id + sz > n) {
-        bad_id = true;
-        return;
-      }
-      for (int k = 0; k < sz; ++k)
-        if (sub_pos[id + k] < 0) {
-          sub_pos[id + k] = (int)sub_ids.size();
-          sub_ids.push_back(id + k);
-        }
-    };
-    for (int i = 0; i < c->fp.n_clones; ++i) place(c->h_clone_id[i], 6);
-    if (o->do_calib_camera_pose) place(c->calib_id, 6);
-    if (o->do_calib_camera_intrinsics) place(c->intr_id, 8);
-    if (bad_id) return OVP_E_ARG;
-    ns = (int)sub_ids.size();
+    ColumnOrder co(c->n, c->n_max);
+    co.place_clones_and_calibration(c, o);
+    if (co.bad_id) return OVP_E_ARG;
+    ns = (int)co.ids.size();
     if (ns > OVP_TILECHOL_NMAX) return OVP_E_CAPACITY;
-    rc = sub_tables_upload(c, o, sub_ids, sub_pos, &sub_t, s);
+    rc = sub_tables_upload(c, o, co.ids, co.pos, &sub_t, s);
     if (rc) return rc;
     if (!c->pl_Asum) HIPCHK(dalloc(&c->pl_Asum, (size_t)c->n_max * ld));
     if (c->pl_U_cap < 1) {
@@ -1358,27 +1507,21 @@ extern "C" int ovp_plane_init(ovp_ctx* c, const ovp_update_opts* o, const ovp_pl
     // running filter) fails chol(P) before anything is committed: the plane runs once more on the pivot-dropping factor of the
     // unit-diagonal form (chol_of_P, as the plane loop does), and so do the planes behind it.
     const int nj = ns ? ns : n;  // the size the plane's kernels run on
-    SubSaved sub_sv;
+    SubScope sub{c, o};  // (leaving it also puts the state's calibration columns back into c->fp)
     if (ns) {  // the marginal of the selection stands in for the state
       HIPCHK(ovp_launch_gather_block(c->P, ld, sub_t.d_ids, ns, c->P_tmp, ld, s));
-      sub_sv = sub_enter(c, sub_t, ns, c->P_tmp);
+      sub.enter(sub_t, ns, c->P_tmp);
       rc = fill_feat_params(c, o);  // (the calibration columns of the selection)
-      if (rc) {
-        sub_leave(c, sub_sv);
-        (void)fill_feat_params(c, o);
-        return rc;
-      }
+      if (rc) return rc;
       fp = c->fp;
     }
     for (int attempt = 0; attempt < 2; ++attempt) {
-      c->pl_psd = psd_prior;
       rc = (int)hipMemsetAsync(c->flags, 0, sizeof(int) * 4, s);
       if (!rc) rc = (int)hipMemsetAsync(c->pl_res + 4 * pl, 0, sizeof(double) * 4, s);
-      if (!rc) rc = chol_of_P(c, s);
+      if (!rc) rc = chol_of_P(c, s, psd_prior);
       if (!rc)
         rc = plane_job_device(c, o, fp, pl, 0, nf, 0, -1, 1.0 / (const_init_multi * o->sigma_constraint), c->L, 0, thr, rows_live - 3,
                               rows_c - 3, c_ref);
-      c->pl_psd = false;
       if (!rc) rc = (int)hipMemcpyAsync(res4.data(), c->pl_res + 4 * pl, sizeof(double) * 4, hipMemcpyDeviceToHost, s);
       if (!rc) rc = (int)hipMemcpyAsync(c->h_flags, c->flags, sizeof(int) * 4, hipMemcpyDeviceToHost, s);
       if (!rc) rc = (int)hipStreamSynchronize(s);
@@ -1387,8 +1530,7 @@ extern "C" int ovp_plane_init(ovp_ctx* c, const ovp_update_opts* o, const ovp_pl
       psd_prior = true;
     }
     if (ns) {
-      sub_leave(c, sub_sv);
-      const int rf = fill_feat_params(c, o);
+      const int rf = sub.leave();
       if (!rc) rc = rf;
       fp = c->fp;
     }
@@ -1407,15 +1549,10 @@ extern "C" int ovp_plane_init(ovp_ctx* c, const ovp_update_opts* o, const ovp_pl
       HIPCHK(ovp_launch_gemm4(1, 0, ns, ns, ns, c->Y, ld, c->Y, ld, c->P_tmp, ld, 0, 1, s));
       HIPCHK(hipMemsetAsync(c->pl_Asum, 0, sizeof(double) * (size_t)ns * ld, s));
       HIPCHK(ovp_launch_plane_sub_accum(c->pl_res + 4 * pl, c->Ab, c->pl_Asum, c->dx, c->pl_U, ns, ld, s));  // (Asum = A from here)
-      HIPCHK(ovp_launch_gemm4(0, 0, ns, ns, ns, c->pl_Asum, ld, c->P_tmp, ld, c->W1, ld, 0, 0, s));
-      HIPCHK(ovp_launch_gemm4(0, 0, ns, ns, ns, c->W1, ld, c->pl_Asum, ld, c->T, ld, 0, 1, s));
-      HIPCHK(ovp_launch_mat_sub(c->pl_Asum, c->T, c->T, ns, ns, ld, s));
-      HIPCHK(ovp_launch_gather_cols(c->P, ld, sub_t.d_ids, n, ns, c->Y, ld, s));
+      if (const int r = push_through_lambda(c, c->P_tmp, sub_t.d_ids, ns, s)) return r;
       HIPCHK(ovp_launch_gemm4(0, 1, 1, n, ns, c->pl_U, ld, c->Y, ld, c->Lt, ld, 0, 0, s));
       HIPCHK(hipMemcpyAsync(c->dx, c->Lt, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-      HIPCHK(ovp_launch_gemm4(0, 0, n, ns, ns, c->Y, ld, c->T, ld, c->W1, ld, 0, 0, s));
-      HIPCHK(ovp_launch_gemm4(0, 1, n, n, ns, c->W1, ld, c->Y, ld, c->L, ld, 0, 1, s));
-      HIPCHK(ovp_launch_sub_sym(c->P, c->L, n, ld, s));
+      if (const int r = push_through_commit(c, ns, s)) return r;
       HIPCHK(ovp_launch_plane_init_augment(c->pl_E, c->ldg, ns, sub_t.d_ids, n, c->P, ld, c->dx, c->pl_scal + 4, s));
     } else {
       HIPCHK(ovp_launch_gemm4(1, 0, n, n, n, c->Y, ld, c->Y, ld, c->P, ld, 0, 1, s));
@@ -1439,4 +1576,3 @@ extern "C" int ovp_plane_init(ovp_ctx* c, const ovp_update_opts* o, const ovp_pl
   }
   return 0;
 }
-

@@ -33,9 +33,9 @@ int set_substate(ovp_ctx* c, const std::vector<int>& ids) {
   return 0;
 }
 
-int chol_of_P(ovp_ctx* c, hipStream_t s) {
+int chol_of_P(ovp_ctx* c, hipStream_t s, bool psd) {
   const int n = c->n, ld = c->ld;
-  if (c->pl_psd && n <= ovp_chol2_max_n() + 1) {
+  if (psd && n <= ovp_chol2_max_n() + 1) {
     // Positive SEMI-definite prior (plane loop, second attempt: state/StateHelper.cpp:159-187 never factors P, so the reference
     // updates such a covariance - right after StateHelper::clone the newest pose is an exact copy, :346-396).  ANY factor with
     // L0 L0^T = P serves the loop (P_k = L0 (I + L0^T A L0)^-1 L0^T is the matrix inversion lemma, no inverse of P in it): the
@@ -628,16 +628,8 @@ extern "C" int ovp_msckf_fetch_results(ovp_ctx* c, double* dx_host, uint8_t* acc
       HIPCHK(hipGetLastError());
     }
     c->pub_pending = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (__atomic_load_n((const unsigned*)c->h_seq, __ATOMIC_ACQUIRE) != seq) {
-      if ((++spins & 0xFFFu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-        HIPCHK(hipStreamSynchronize(c->stream));  // error path: surface a fault instead of spinning forever
-        if (__atomic_load_n((const unsigned*)c->h_seq, __ATOMIC_ACQUIRE) != seq) return OVP_E_STATE;
-        break;
-      }
-      __builtin_ia32_pause();
-    }
+    const int rw = ovp_wait_seq(c->h_seq, seq, c->stream);
+    if (rw) return rw;
   }
   if (c->h_flags[0]) {
     // chol(P) failed: the prior is only positive semi-definite.  Same update in the reference's S-form (no factor of P needed).
@@ -721,7 +713,7 @@ extern "C" int ovp_ekf_update(ovp_ctx* c, const double* H_host, int rows, int co
     const size_t oHt = 0, oRes = oHt + (size_t)cols * rows, oId = oRes + rows + 8;
     const size_t bytes = oId * sizeof(double) + sizeof(int) * (size_t)cols + 64;
     const size_t res_doubles = 4 + (size_t)c->n_max + 8;
-    int rc = plane2_buffers(c, 0, bytes, res_doubles * sizeof(double));
+    int rc = plane2_buffers(c, bytes, res_doubles * sizeof(double));
     if (rc) return rc;
     double* h = (double*)c->pl_hstage;
     double* d = (double*)c->pl_dstage;

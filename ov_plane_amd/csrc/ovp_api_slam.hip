@@ -200,7 +200,7 @@ static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam
   const size_t stage_bytes = off;
   const size_t res_doubles = 4 + (size_t)c->n_max + 8;
   const size_t lres_bytes = al(sizeof(double) * L) + al((size_t)L);
-  int rc = plane2_buffers(c, 0, stage_bytes, res_doubles * sizeof(double) + lres_bytes + 64);
+  int rc = plane2_buffers(c, stage_bytes, res_doubles * sizeof(double) + lres_bytes + 64);
   if (rc) return rc;
   char* h = (char*)c->pl_hstage;
   char* d = (char*)c->pl_dstage;
@@ -576,7 +576,7 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
   const size_t o_p2 = take(with_planes ? sizeof(double) * 3 * L : 0), o_pt = take(sizeof(double) * OVP_DINIT_PLTAB * (size_t)n_pl);
   const size_t stage_bytes = off;
   const size_t res_doubles = 4 + (size_t)c->n_max + 8;
-  int rc = plane2_buffers(c, 0, stage_bytes, sizeof(double) * res_doubles * NA + 64);
+  int rc = plane2_buffers(c, stage_bytes, sizeof(double) * res_doubles * NA + 64);
   if (rc) return rc;
   char* h = (char*)c->pl_hstage;
   char* d = (char*)c->pl_dstage;

@@ -205,13 +205,9 @@ struct ovp_ctx {
   double *pl_An = nullptr, *pl_bn = nullptr, *pl_Lr = nullptr, *pl_Dinv2 = nullptr, *pl_scal = nullptr;
   double *pl_res = nullptr, *pl_dx = nullptr;
   int pl_cap = 0;
-  // SLAM landmarks on out-of-state planes (ovp_msckf_plane_update): [plane | id] ints and [p | p_fej] doubles
-  int *pl_slam_i = nullptr;
-  double *pl_slam_d = nullptr;
-  int pl_slam_cap = 0, pl_n_slam = 0;
   // second-generation plane loop (k_plane2.hip / k_chol2.hip)
   double *pl_Tbuf = nullptr, *pl_crow = nullptr, *pl_dxlast = nullptr;
-  int *pl_cur = nullptr, *pl_perm = nullptr;
+  int* pl_cur = nullptr;
   unsigned* pl_range_done = nullptr;
   unsigned pl_seq = 0;
   int range_lo = -1, range_hi = -1;   // ovp_batch_set_range (-1, -1 = whole batch)
@@ -220,7 +216,6 @@ struct ovp_ctx {
   int* h_slot = nullptr;              // [f_max] host-mapped: row block of a feature in the compacted rec / G of a point update (-1: none)
   int* d_slot = nullptr;              // its device address
   bool pl_used_valid = false;         // pl_used refers to the uploaded batch
-  int pl2_cap = 0;
   // plane loop on a sub-state (n above the tile factorization's limit): accumulated pair, u rows, remapped id tables
   void *io_h = nullptr, *io_d = nullptr;         // ovp_io_arena: pinned host block + device block of the small entry points
   size_t io_cap = 0;
@@ -229,19 +224,8 @@ struct ovp_ctx {
   double *pl_Asum = nullptr, *pl_U = nullptr;
   int pl_U_cap = 0;
   void *pl_sub_tab = nullptr, *pl_sub_htab = nullptr;  // [ids | inverse | clone ids | column map] of the loop's column order
-  bool pl_sub_active = false;   // ovp_msckf_plane_update runs inside plane_update_ordered (remapped tables, c->P = permuted copy)
-  bool pl_sub_rest = false;     // ... on a marginal: the rest of the state follows by push-through (k_plane_sub_accum per plane)
-  std::vector<int> pl_nl;       // [plane] leading columns involved up to and including that plane (loop order)
-  double* pl_scatter_dst = nullptr;   // full order: where the covariance product of the loop is un-permuted to
-  const int* pl_scatter_ids = nullptr;
-  double pl_t_entry = 0.0;
-  bool pl_psd = false;
-  // general on-plane features of the running ovp_msckf_plane_update_general (k_plane_feat_gen.hip); pl_gen_b == nullptr: none
-  const ovp_general_batch* pl_gen_b = nullptr;
-  const int* pl_gen_plane = nullptr;       // [n_feats of the general batch] 1-based plane slot, 0 = not on a plane
-  std::vector<int> pl_gen_pos;             // state column -> column in the loop's order (plane_update_ordered); empty = identity
-  std::vector<unsigned char> pl_gen_used;  // [n_feats of the general batch] consumed by an accepted plane
-  void* pl_gen_dev = nullptr;              // device: [marks | projected rows] of one plane's general features
+  // (what tells the plane loop's routes apart is an argument of the loop, PlaneLoopView in ovp_api_plane.hip, not context state)
+  void* pl_gen_dev = nullptr;              // device: [marks | projected rows] of one plane's general features of the running loop
   size_t pl_gen_cap = 0;
   // A factor of the RESIDENT covariance left behind by the plane loop (P = V^T V, Lkeep = V^T in the state's column order): the point
   // update that follows needs some M with M M^T = P, not the Cholesky factor - chol(P) (the longer branch of the fused feature
@@ -250,11 +234,11 @@ struct ovp_ctx {
   bool have_factor = false, use_kept_factor = false;
   double clone_jitter = 0.0;  // ovp_cov_clone_jitter: relative inflation of a cloned block's diagonal (0 = exact copy, the reference)
   double* boost_vec = nullptr;  // [n_max] k_gather_block_boost: the plane loop's diagonal boost by STATE column (zero where none)
-  bool pl_boost_active = false, kept_boost = false;
+  bool kept_boost = false;  // Lkeep is a factor of P + diag(boost_vec): the point update on it takes the amounts off at its end
   double* boost = nullptr;   // CholJob::boost: the amounts the reversed-order chol(P) added to the diagonal in front of the batch's columns
   int point_boost_n = 0;
   int point_nl = 0;  // > 0: chol(P) of the running point update was taken in reversed index order (CholJob::flip) and the update's
-                     // T = I + L^T A L is the identity outside its leading point_nl columns          // second attempt of a plane loop whose chol(P) failed: pivot-dropping factor of the PSD prior
+                     // T = I + L^T A L is the identity outside its leading point_nl columns
   hipEvent_t ev_subtab = nullptr;     // behind the upload of pl_sub_htab (the pinned block is rewritten by the next call)
   void *pl_hstage = nullptr, *pl_dstage = nullptr;  // pinned host / device staging of the per-call tables
   size_t pl_stage_cap = 0;
@@ -329,6 +313,18 @@ static hipError_t dalloc(T** p, size_t count) {
   return hipMalloc((void**)p, count * sizeof(T));
 }
 
+// Wait for the sequence number a kernel on stream s writes into mapped pinned memory behind its payload.  Error path: after two
+// seconds one stream synchronisation surfaces a fault instead of spinning forever, OVP_E_STATE when the word still is not there.
+static inline int ovp_wait_seq(const volatile unsigned* word, unsigned seq, hipStream_t s) {
+  const auto t0 = std::chrono::steady_clock::now();
+  for (unsigned spins = 0; __atomic_load_n((const unsigned*)word, __ATOMIC_ACQUIRE) != seq; __builtin_ia32_pause())
+    if ((++spins & 0xFFFu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
+      HIPCHK(hipStreamSynchronize(s));
+      return __atomic_load_n((const unsigned*)word, __ATOMIC_ACQUIRE) != seq ? OVP_E_STATE : 0;
+    }
+  return 0;
+}
+
 // ---- shared between the entry-point files ------------------------------------------------------------------------------------
 void quat_2_rot(const double q[4], double R[9]);  // JPL quaternion -> row-major rotation (ovp_api_ctx.hip)
 extern "C" int ovp_io_arena(ovp_ctx* c, size_t bytes, void** host, void** dev);  // pinned staging arena (ovp_api_ctx.hip)
@@ -339,10 +335,10 @@ int fill_feat_params(ovp_ctx* c, const ovp_update_opts* o);
 // any_length: the batch of ovp_plane_fit_refine - uv is not read and n_meas is bounded by max_meas only
 int check_general_batch(const ovp_ctx* c, const ovp_general_batch* b, bool need_p, const int* only = nullptr, bool any_length = false);
 int ovp_fetch_to_hres(ovp_ctx* c, const void* dsrc, size_t bytes, hipStream_t s);  // device block -> c->pl_hres, waited for (ovp_api_plane.hip)
-int chol_of_P(ovp_ctx* c, hipStream_t s);
+int chol_of_P(ovp_ctx* c, hipStream_t s, bool psd = false);  // psd: pivot-dropping factor of a positive semi-definite P (plane path)
 hipError_t chol_of_T(ovp_ctx* c, const double* T, int n, int ld, int add_identity, const int* cond, hipStream_t s);
 int set_substate(ovp_ctx* c, const std::vector<int>& ids);
 int ekf_from_gram(ovp_ctx* c, bool chol_p_done_on_stream2, bool publish = false);
 int ekf_sform(ovp_ctx* c);
 // ovp_api_plane.hip
-int plane2_buffers(ovp_ctx* c, int NP, size_t stage_bytes, size_t res_bytes);
+int plane2_buffers(ovp_ctx* c, size_t stage_bytes, size_t res_bytes);

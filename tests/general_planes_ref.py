@@ -161,11 +161,13 @@ def relP(Pa, Pb):
     return float((np.abs(Pa - Pb) / np.outer(d, d)).max())
 
 
-def run_general(capi, sc, force=None, move=None, n_max=None):
+def run_general(capi, sc, force=None, move=None, n_max=None, ctx=None):
     """The scene through ovp_msckf_plane_update_general: the features that fit the device batch uploaded as the batch (first
-    OVP_MAX_MEAS columns), the others (and `move`) as the general batch.  Returns the entry's dict plus P, batch, gen, ctx."""
+    OVP_MAX_MEAS columns), the others (and `move`) as the general batch.  Returns the entry's dict plus P, batch, gen, ctx.
+    ctx: an existing context to run on instead of a fresh one."""
     batch, gen = split_features(sc, move)
-    ctx = capi.Context(sc.N if n_max is None else n_max, sc.C, max(len(batch), 1))
+    if ctx is None:
+        ctx = capi.Context(sc.N if n_max is None else n_max, sc.C, max(len(batch), 1))
     ctx.cov_upload(sc.P)
     ctx.state_upload(sc)
     ctx.cameras_upload(sc)

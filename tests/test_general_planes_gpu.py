@@ -308,3 +308,75 @@ def test_64_observation_stereo_tracks(hiplib):
     assert _state_err(sc, out, npr["state"], npr["cp"]) < TOL_DX
     assert R.relP(out["P"], npr["P"]) < TOL_P
     out["ctx"].close()
+
+
+def _exact_clone_scene():
+    """The prior of tests/test_gpu_parity.py::test_plane_loop_on_a_positive_semidefinite_prior, case exact_clone below the
+    factorization's limit: chol(P) fails and the loop runs once more on the pivot-dropping factor."""
+    sc = make_scene(C=9, F=150, seed=43, n_planes=3, feats_per_plane=25, planes_in_state_frac=0.67, chi2_mult=99999.0)
+    assert sc.N <= 287
+    a, b = sc.ids["clones"][-2], sc.ids["clones"][-1]
+    idx = np.arange(sc.N)
+    idx[b:b + 6] = np.arange(a, a + 6)
+    sc["P"] = sc.P[np.ix_(idx, idx)]
+    for k in ("clone_q", "clone_p", "clone_q_fej", "clone_p_fej"):
+        sc[k][-1] = sc[k][-2]
+    assert np.linalg.eigvalsh(sc.P).min() < 1e-12 * np.linalg.eigvalsh(sc.P).max()
+    return sc
+
+
+def test_no_route_into_the_loop_leaves_anything_behind_for_the_next(hiplib, monkeypatch):
+    """ONE context through every route into the plane loop, one after the other: general features in the loop's own column order,
+    a plain call, the same in the state's order (OVP_PL_NATURAL_ORDER), a positive semi-definite prior (the retry), ovp_plane_init,
+    the plain call again.  Covariance, state and batch are uploaded afresh before each call; every output of every step equals
+    BIT FOR BIT what the same call gives on a fresh context of the same capacity."""
+    stereo = make_stereo_plane_scene(C=8, n_planes=2, feats_per_plane=10, n_free=4, seed=3, planes_in_state_frac=0.5, chi2_mult=1.0)
+    small = make_scene(C=8, F=90, seed=73, n_planes=3, feats_per_plane=15, chi2_mult=99999.0)
+    psd = _exact_clone_scene()
+    fresh_planes = make_scene(C=8, F=80, seed=16, n_planes=2, feats_per_plane=25, planes_in_state_frac=0.0, chi2_mult=1.0, ragged=True)
+    cap = (max(s.N for s in (stereo, small, psd, fresh_planes)) + 6, 9, 150)
+
+    def general(ctx):
+        out = R.run_general(hiplib, stereo, force=np.array([1, 1], dtype=np.uint8), ctx=ctx)
+        return {k: v for k, v in out.items() if k != "ctx"}
+
+    def plain(sc, init=False):
+        def run(ctx):
+            ctx.cov_upload(sc.P)
+            ctx.state_upload(sc)
+            ctx.batch_upload_scene(sc)
+            o = hiplib.opts_from_scene(sc)
+            out = ctx.plane_init(o, sc.plane_id, sc.cp, 5.0, 1e9) if init else \
+                ctx.plane_update(o, sc.plane_id, sc.cp, sc.cp_fej, sc.plane_state_id)
+            out["P"] = ctx.cov_download()
+            return out
+        return run
+
+    steps = [("general", general, False), ("plain", plain(small), False), ("natural_order", plain(small), True),
+             ("semidefinite_retry", plain(psd), False), ("plane_init", plain(fresh_planes, init=True), False),
+             ("plain_again", plain(small), False)]
+
+    def run_step(ctx, fn, natural):
+        if natural:
+            monkeypatch.setenv("OVP_PL_NATURAL_ORDER", "1")
+        else:
+            monkeypatch.delenv("OVP_PL_NATURAL_ORDER", raising=False)
+        try:
+            return fn(ctx)
+        finally:
+            monkeypatch.delenv("OVP_PL_NATURAL_ORDER", raising=False)
+
+    one = hiplib.Context(*cap)
+    chained = [run_step(one, fn, natural) for _, fn, natural in steps]
+    one.close()
+    assert chained[0]["ok"].all() and chained[0]["gen_used"].any()
+    assert chained[1]["ok"].any() and chained[3]["ok"].all() and chained[4]["ok"].all()
+    assert np.array_equal(chained[4]["new_ids"], fresh_planes.N + 3 * np.arange(2))
+    for (name, fn, natural), got in zip(steps, chained):
+        ctx = hiplib.Context(*cap)
+        want = run_step(ctx, fn, natural)
+        ctx.close()
+        for k in ("ok", "chi2", "dof", "dx", "used", "gen_used", "P", "new_ids", "cp"):
+            assert (k in got) == (k in want)
+            if k in want:
+                assert np.asarray(got[k]).tobytes() == np.asarray(want[k]).tobytes(), (name, k)
