@@ -86,7 +86,8 @@ extern "C" int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, device));
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return OVP_E_NODEVICE;  // gfx950-only build, no fallback
-  ovp_ctx* c = new ovp_ctx();
+  std::unique_ptr<ovp_ctx> owner(new ovp_ctx());  // (every early return below releases what was created so far)
+  ovp_ctx* c = owner.get();
   c->device = device;
   // Two streams: the main one carries K1/K2/K3, the side stream the measurement-independent chol(P).  (Pinning the side
   // stream to one CU with hipExtStreamCreateWithCUMask was tried: the driver keeps CU masks symmetric across shader
@@ -110,18 +111,18 @@ extern "C" int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int
   c->ldg = round_up(n_state_max + 4, 16);  // state columns | residual | 3 out-of-state plane columns
   if (c->ldg > OVP_LDG_CAP) return OVP_E_CAPACITY;  // the feature kernels stage 3 projector rows in LDS  // K1 stages the projector rows in its 64x65/2 LDS triangle
   const size_t nn = (size_t)(c->n_max + 1) * c->ld;
-  HIPCHK(dalloc(&c->P, nn));
-  HIPCHK(dalloc(&c->P_tmp, nn));
-  HIPCHK(dalloc(&c->Ab, nn + 8));  // (+ the peer-error word the sharded update sums along with the pair)
-  HIPCHK(dalloc(&c->L, nn));
-  HIPCHK(dalloc(&c->W1, nn));
-  HIPCHK(dalloc(&c->T, nn));
-  HIPCHK(dalloc(&c->Lt, nn));
-  HIPCHK(dalloc(&c->Y, nn));
+  HIPCHK(c->P.alloc(nn));
+  HIPCHK(c->P_tmp.alloc(nn));
+  HIPCHK(c->Ab.alloc(nn + 8));  // (+ the peer-error word the sharded update sums along with the pair)
+  HIPCHK(c->L.alloc(nn));
+  HIPCHK(c->W1.alloc(nn));
+  HIPCHK(c->T.alloc(nn));
+  HIPCHK(c->Lt.alloc(nn));
+  HIPCHK(c->Y.alloc(nn));
   // results of an update live in ONE block [flags 4 x i32 | dx n_max | chi2 f_max | accept f_max] so that
   // ovp_msckf_fetch_results is a single device-to-host copy (four small copies cost ~5 us each)
   c->res_bytes = 16 + sizeof(double) * ((size_t)c->n_max + n_feats_max) + (size_t)n_feats_max;
-  HIPCHK(hipMalloc((void**)&c->res_block, c->res_bytes));
+  HIPCHK(c->res_block.alloc(c->res_bytes));
   HIPCHK(hipMemset(c->res_block, 0, c->res_bytes));
   c->flags = (int*)c->res_block;
   c->dx = (double*)((char*)c->res_block + 16);
@@ -129,26 +130,18 @@ extern "C" int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int
   c->accept = (unsigned char*)(c->chi2 + n_feats_max);
   {
     // pose tables: [R | R_fej | p | p_fej | cal(32) | clone_id | colmap], fixed offsets (capacities), uploaded as one block
-    auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    size_t o = 0;
-    c->so_R = o;
-    o = al(o + sizeof(double) * 9 * n_clones_max);
-    c->so_Rf = o;
-    o = al(o + sizeof(double) * 9 * n_clones_max);
-    c->so_p = o;
-    o = al(o + sizeof(double) * 3 * n_clones_max);
-    c->so_pf = o;
-    o = al(o + sizeof(double) * 3 * n_clones_max);
-    c->so_cal = o;
-    o = al(o + sizeof(double) * 32);
-    c->so_id = o;
-    o = al(o + sizeof(int) * n_clones_max);
-    c->so_cm = o;
-    o = al(o + sizeof(ovp::ColMap) * c->n_max);
-    c->state_bytes = o;
-    HIPCHK(hipMalloc(&c->state_block, o));
+    StageLayout lay;
+    c->so_R = lay.take(sizeof(double) * 9 * n_clones_max);
+    c->so_Rf = lay.take(sizeof(double) * 9 * n_clones_max);
+    c->so_p = lay.take(sizeof(double) * 3 * n_clones_max);
+    c->so_pf = lay.take(sizeof(double) * 3 * n_clones_max);
+    c->so_cal = lay.take(sizeof(double) * 32);
+    c->so_id = lay.take(sizeof(int) * n_clones_max);
+    c->so_cm = lay.take(sizeof(ovp::ColMap) * c->n_max);
+    const size_t o = c->state_bytes = lay.bytes();
+    HIPCHK(c->state_block.alloc(o));
     HIPCHK(hipMemset(c->state_block, 0, o));
-    HIPCHK(hipHostMalloc(&c->h_state_stage, o, hipHostMallocDefault));
+    HIPCHK(c->h_state_stage.alloc(o));
     char* b = (char*)c->state_block;
     c->clone_R = (double*)(b + c->so_R);
     c->clone_R_fej = (double*)(b + c->so_Rf);
@@ -160,27 +153,27 @@ extern "C" int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int
     HIPCHK(hipEventCreateWithFlags(&c->ev_state, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_batch, hipEventDisableTiming));
   }
-  HIPCHK(dalloc(&c->chi2_table, (size_t)OVP_CHI2_TABLE + 1));
+  HIPCHK(c->chi2_table.alloc((size_t)OVP_CHI2_TABLE + 1));
   {
     // feature batch: [p_FinG | n_meas | clone_idx | uv], compact per upload (p_FinG always first: ovp_triangulate writes it)
     const size_t F = (size_t)n_feats_max, M = OVP_MAX_MEAS;
-    c->batch_cap = sizeof(double) * 3 * F + sizeof(int) * F + sizeof(int) * F * M + sizeof(float) * 2 * F * M + 256;
-    HIPCHK(hipMalloc(&c->batch_block, c->batch_cap));
-    HIPCHK(hipHostMalloc(&c->h_batch_stage, c->batch_cap, hipHostMallocDefault));
+    const size_t cap = sizeof(double) * 3 * F + sizeof(int) * F + sizeof(int) * F * M + sizeof(float) * 2 * F * M + 256;
+    HIPCHK(c->batch_block.alloc(cap));
+    HIPCHK(c->h_batch_stage.alloc(cap));
     c->p_FinG = (double*)c->batch_block;
   }
-  HIPCHK(dalloc(&c->G, (size_t)3 * n_feats_max * c->ldg));
-  HIPCHK(dalloc(&c->Bscr, (size_t)n_feats_max * OVP_BSCR));
-  HIPCHK(dalloc(&c->rec, (size_t)n_clones_max * n_feats_max * 2 * 21));
+  HIPCHK(c->G.alloc((size_t)3 * n_feats_max * c->ldg));
+  HIPCHK(c->Bscr.alloc((size_t)n_feats_max * OVP_BSCR));
+  HIPCHK(c->rec.alloc((size_t)n_clones_max * n_feats_max * 2 * 21));
   // reduction geometry: fixed per context so the summation order (hence the result bits) is reproducible
   c->rows_per_chunk = 128;  // 32 rows = 8 MFMA steps per wave of k_gram_pair
   c->n_chunks = (2 * n_feats_max + c->rows_per_chunk - 1) / c->rows_per_chunk;
-  HIPCHK(dalloc(&c->gramS, (size_t)n_clones_max * c->n_chunks * OVP_GRAM_ELEMS));
-  HIPCHK(dalloc(&c->gramR, (size_t)n_clones_max * OVP_GRAM_ELEMS));
-  HIPCHK(dalloc(&c->Dinv, (size_t)(c->ld / 16 + 1) * 256));
+  HIPCHK(c->gramS.alloc((size_t)n_clones_max * c->n_chunks * OVP_GRAM_ELEMS));
+  HIPCHK(c->gramR.alloc((size_t)n_clones_max * OVP_GRAM_ELEMS));
+  HIPCHK(c->Dinv.alloc((size_t)(c->ld / 16 + 1) * 256));
   {
     const size_t ntm = (size_t)c->ld / 16 + 1;
-    HIPCHK(dalloc(&c->Ltp, ntm * (ntm + 1) / 2 * 256));  // tile-packed factor for k_fwdsub
+    HIPCHK(c->Ltp.alloc(ntm * (ntm + 1) / 2 * 256));  // tile-packed factor for k_fwdsub
   }
   c->n_split = (3 * n_feats_max + 63) / 64;  // split-K partials of the dense Gram product (k_gram_pair: ~256 blocks)
   if (c->n_split < 1) c->n_split = 1;
@@ -188,18 +181,15 @@ extern "C" int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int
   {
     const int nt = c->ldg / 16;
     // (one split more than k_gram_pair fills: the general on-plane features of a plane add theirs, k_plane_feat_gen.hip)
-    HIPCHK(dalloc(&c->part, (size_t)(c->n_split + 1) * (nt * (nt + 1) / 2) * 256));
+    HIPCHK(c->part.alloc((size_t)(c->n_split + 1) * (nt * (nt + 1) / 2) * 256));
   }
-  HIPCHK(dalloc(&c->idbuf, (size_t)4 * c->n_max + 64));
-  c->small_cap = (size_t)4 * c->n_max * 64 + (size_t)c->n_max * c->n_max;
-  HIPCHK(dalloc(&c->smallbuf, c->small_cap));
-  HIPCHK(hipMalloc((void**)&c->ticket, 16));
+  HIPCHK(c->idbuf.alloc((size_t)4 * c->n_max + 64));
+  HIPCHK(c->smallbuf.alloc((size_t)4 * c->n_max * 64 + (size_t)c->n_max * c->n_max));
+  HIPCHK(c->ticket.alloc(4));
   HIPCHK(hipMemset(c->ticket, 0, 16));
-  HIPCHK(hipHostMalloc((void**)&c->h_res_block, c->res_bytes + 64, hipHostMallocMapped));  // pinned mirror of res_block
+  HIPCHK(c->h_res_block.alloc(c->res_bytes + 64));  // pinned mirror of res_block
   memset(c->h_res_block, 0, c->res_bytes + 64);
-  HIPCHK(hipHostGetDevicePointer(&c->h_res_block_dev, c->h_res_block, 0));
-  HIPCHK(hipHostMalloc((void**)&c->h_slot, sizeof(int) * (size_t)(n_feats_max + 16), hipHostMallocMapped));
-  HIPCHK(hipHostGetDevicePointer((void**)&c->d_slot, c->h_slot, 0));
+  HIPCHK(c->h_slot.alloc((size_t)(n_feats_max + 16)));
   c->h_seq = (volatile unsigned*)((char*)c->h_res_block + ((c->res_bytes + 15) & ~(size_t)15));
   c->h_flags = (int*)c->h_res_block;
   c->h_dx = (double*)((char*)c->h_res_block + 16);
@@ -212,7 +202,7 @@ extern "C" int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int
     HIPCHK(hipMemcpy(c->chi2_table, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
   }
   memset(&c->fp, 0, sizeof(c->fp));
-  *out = c;
+  *out = owner.release();
   return 0;
 }
 
@@ -221,35 +211,6 @@ extern "C" int ovp_ctx_destroy(ovp_ctx* c) {
   hipSetDevice(c->device);
   hipStreamSynchronize(c->stream);
   hipStreamSynchronize(c->stream2);
-  void* dev[] = {c->P, c->P_tmp, c->Ab, c->L, c->W1, c->T, c->Lt, c->Y, c->res_block, c->ticket, c->uvn, c->tri_ok, c->state_block, c->batch_block,
-                 c->chi2_table, c->G, c->Bscr, c->rec, c->gramS, c->gramR, c->Dinv, c->Ltp, c->part, c->idbuf, c->smallbuf, c->Hd, c->Acc,
-                 c->bcc, c->resd, c->sub_ids, c->sub_buf, c->pl_Tbuf, c->pl_crow, c->pl_dxlast,
-                 c->pl_cur, c->pl_range_done, c->pl_used, c->pl_dstage, c->pl_xbuf, c->pl_xy, c->pl_xflag, c->pl_Asum,
-                 c->pl_U, c->pl_sub_tab, c->Lkeep, c->slam_res, c->slam_hscr, c->dinit_buf, c->boost, c->boost_vec,
-                 c->gen_cal, c->gen_buf, c->pl_gen_dev};
-  for (void* p : dev)
-    if (p) hipFree(p);
-  if (c->h_res_block) hipHostFree(c->h_res_block);
-  if (c->h_slot) hipHostFree(c->h_slot);
-  if (c->h_state_stage) hipHostFree(c->h_state_stage);
-  if (c->h_batch_stage) hipHostFree(c->h_batch_stage);
-  if (c->ev_state) hipEventDestroy(c->ev_state);
-  if (c->ev_batch) hipEventDestroy(c->ev_batch);
-  if (c->pl_hstage) hipHostFree(c->pl_hstage);
-  if (c->pl_hres) hipHostFree(c->pl_hres);
-  if (c->pl_sub_htab) hipHostFree(c->pl_sub_htab);
-  if (c->ev_subtab) hipEventDestroy(c->ev_subtab);
-  for (hipEvent_t e : c->pl_ev) hipEventDestroy(e);
-  for (hipEvent_t e : c->pl_ev_loop) hipEventDestroy(e);
-  if (c->io_h) hipHostFree(c->io_h);
-  if (c->io_d) hipFree(c->io_d);
-  hipEventDestroy(c->ev_fork);
-  hipEventDestroy(c->ev_join);
-  for (int i = 0; i < 6; ++i) hipEventDestroy(c->ev_t[i]);
-  hipEventDestroy(c->ev_k0);
-  hipEventDestroy(c->ev_k1);
-  hipStreamDestroy(c->stream2);
-  if (c->own_stream) hipStreamDestroy(c->stream);
   delete c;
   return 0;
 }
@@ -325,9 +286,9 @@ extern "C" int ovp_cov_marginal(ovp_ctx* c, const int* ids, const int* sizes, in
       cols.push_back(ids[i] + k);
     }
   const int m = (int)cols.size();
-  if (m > c->n_max || (size_t)m * m > c->small_cap) return OVP_E_CAPACITY;
+  if (m > c->n_max || (size_t)m * m > c->smallbuf.capacity()) return OVP_E_CAPACITY;
   void *ah = nullptr, *ad = nullptr;
-  const size_t o_out = ((sizeof(int) * (size_t)m + 63) / 64) * 64, bytes = o_out + sizeof(double) * (size_t)m * m;
+  const size_t o_out = StageLayout::al(sizeof(int) * (size_t)m), bytes = o_out + sizeof(double) * (size_t)m * m;
   {
     const int rca = ovp_io_arena(c, bytes, &ah, &ad);
     if (rca) return rca;
@@ -428,16 +389,10 @@ extern "C" int ovp_state_upload(ovp_ctx* c, const ovp_state_tables* st) {
 // planes, a quarter of its GPU time) and, in the plane-fitting entries, a hipMalloc / hipFree pair per call.
 extern "C" int ovp_io_arena(ovp_ctx* c, size_t bytes, void** host, void** dev) {
   if (!c || !host || !dev) return OVP_E_ARG;
-  if (bytes > c->io_cap) {
+  if (bytes > c->io_d.capacity()) {  // (io_d grows last: its capacity stands for both halves)
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->io_h) hipHostFree(c->io_h);
-    if (c->io_d) hipFree(c->io_d);
-    c->io_h = c->io_d = nullptr;
-    c->io_cap = 0;
-    const size_t cap = bytes + bytes / 2 + 4096;
-    HIPCHK(hipHostMalloc(&c->io_h, cap, hipHostMallocDefault));
-    HIPCHK(hipMalloc(&c->io_d, cap));
-    c->io_cap = cap;
+    HIPCHK(c->io_h.reserve(bytes, bytes / 2 + 4096));
+    HIPCHK(c->io_d.reserve(bytes, bytes / 2 + 4096));
   }
   *host = c->io_h;
   *dev = c->io_d;
@@ -451,10 +406,10 @@ extern "C" int ovp_batch_upload(ovp_ctx* c, const ovp_feature_batch* b) {
   const size_t F = (size_t)b->n_feats, M = (size_t)b->max_meas;
   // compact layout [p_FinG | n_meas | clone_idx | uv] in one pinned block, one copy, no synchronisation: the caller's arrays
   // are free again on return because they were copied into the staging block
-  auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-  const size_t o_p = 0, o_nm = al(o_p + sizeof(double) * 3 * F), o_ci = al(o_nm + sizeof(int) * F),
-               o_uv = al(o_ci + sizeof(int) * F * M), total = al(o_uv + sizeof(float) * 2 * F * M);
-  if (total > c->batch_cap) return OVP_E_CAPACITY;
+  StageLayout lay;
+  const size_t o_p = lay.take(sizeof(double) * 3 * F), o_nm = lay.take(sizeof(int) * F), o_ci = lay.take(sizeof(int) * F * M),
+               o_uv = lay.take(sizeof(float) * 2 * F * M), total = lay.bytes();
+  if (total > c->batch_block.capacity()) return OVP_E_CAPACITY;
   char* d = (char*)c->batch_block;
   c->p_FinG = (double*)(d + o_p);
   c->n_meas = (int*)(d + o_nm);
@@ -540,13 +495,13 @@ extern "C" int ovp_cov_propagate(ovp_ctx* c, int new_start, int phi_size, const 
   if (nold > 4 * c->n_max) return OVP_E_CAPACITY;
   double* dCPT = c->smallbuf;
   double* dPCP = dCPT + (size_t)n * phi_size;
-  if ((size_t)(dPCP + (size_t)phi_size * phi_size - c->smallbuf) > c->small_cap) return OVP_E_CAPACITY;
+  if ((size_t)(dPCP + (size_t)phi_size * phi_size - c->smallbuf) > c->smallbuf.capacity()) return OVP_E_CAPACITY;
   HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 4, c->stream));
   {
     // [Phi | Q | ids] packed into the pinned arena, one copy; the kernels read them from the device half of the arena
     void *ah = nullptr, *ad = nullptr;
     const size_t b_pq = sizeof(double) * ((size_t)phi_size * nold + (size_t)phi_size * phi_size);
-    const size_t o_id = ((b_pq + 63) / 64) * 64, bytes = o_id + sizeof(int) * (size_t)nold;
+    const size_t o_id = StageLayout::al(b_pq), bytes = o_id + sizeof(int) * (size_t)nold;
     const int rca = ovp_io_arena(c, bytes, &ah, &ad);
     if (rca) return rca;
     memcpy(ah, Phi_host, sizeof(double) * phi_size * nold);
@@ -558,7 +513,7 @@ extern "C" int ovp_cov_propagate(ovp_ctx* c, int new_start, int phi_size, const 
     // the verdict comes back through mapped pinned memory (two words 16 bytes behind the point update's sequence word, in the same
     // 64-byte slack of the result block) and a sequence number of its own: no copy command, no stream synchronisation
     volatile unsigned* hw = c->h_seq + 4;
-    unsigned* hw_dev = (unsigned*)((char*)c->h_res_block_dev + ((char*)hw - (char*)c->h_res_block));
+    unsigned* hw_dev = (unsigned*)((char*)c->h_res_block.dev() + ((char*)hw - (char*)c->h_res_block));
     const unsigned seq = ++c->prop_seq;
     HIPCHK(ovp_launch_propagate_publish(c->P, c->ld, n, new_start, phi_size, (const int*)((char*)ad + o_id), nold, dPhi, dQ, dCPT, dPCP,
                                         c->flags + 1, hw_dev, seq, c->stream));
@@ -593,9 +548,7 @@ extern "C" int ovp_cov_marginalize(ovp_ctx* c, int id, int size) {
   if (!c->have_cov) return OVP_E_STATE;
   if (id + size > c->n) return OVP_E_ARG;
   HIPCHK(ovp_launch_cov_marginalize(c->P, c->P_tmp, c->ld, c->n, id, size, c->stream));
-  double* t = c->P;
-  c->P = c->P_tmp;
-  c->P_tmp = t;
+  c->P.swap(c->P_tmp);
   c->n -= size;
   return 0;
 }
@@ -623,7 +576,7 @@ extern "C" int ovp_cov_initialize_invertible(ovp_ctx* c, const double* H_R, int 
   double* dHi = dHR + (size_t)k * cols;
   double* dRk = dHi + 36;
   double* dMa = dRk + 36;
-  if ((size_t)(dMa + (size_t)6 * n - c->smallbuf) > c->small_cap) return OVP_E_CAPACITY;
+  if ((size_t)(dMa + (size_t)6 * n - c->smallbuf) > c->smallbuf.capacity()) return OVP_E_CAPACITY;
   HIPCHK(hipMemcpyAsync(dHR, hr.data(), sizeof(double) * hr.size(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(dHi, hi.data(), sizeof(double) * hi.size(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(dRk, rk.data(), sizeof(double) * rk.size(), hipMemcpyHostToDevice, c->stream));
@@ -688,7 +641,7 @@ extern "C" int ovp_cov_initialize(ovp_ctx* c, const double* Hx_init, const doubl
   double* dM = dres + res_doubles;
   double* dLi = dM + (size_t)n2 * m;
   double* dy = dLi + (size_t)rup * rup;
-  if ((size_t)(dy + rup + 8 - c->smallbuf) > c->small_cap) return OVP_E_CAPACITY;
+  if ((size_t)(dy + rup + 8 - c->smallbuf) > c->smallbuf.capacity()) return OVP_E_CAPACITY;
   HIPCHK(hipMemcpyAsync(c->pl_dstage, c->pl_hstage, bytes, hipMemcpyHostToDevice, s));
   HIPCHK(ovp_launch_init_m(c->P, ld, n, did, cols, d + oHt, m, dM, s));
   HIPCHK(ovp_launch_init_core(c->P, ld, n, did, cols, d + oHt, k, rup, dM, d + oHi, d + oRk, d + oRes, r_iso > 0.0 ? r_iso : 1.0,
@@ -708,9 +661,7 @@ extern "C" int ovp_cov_initialize(ovp_ctx* c, const double* Hx_init, const doubl
   if (!ok) return 0;
   c->n = n2;
   if (upd) {
-    double* t = c->P;
-    c->P = c->P_tmp;
-    c->P_tmp = t;
+    c->P.swap(c->P_tmp);
   }
   if (dx_host) {
     if (upd) memcpy(dx_host, hres + 4, sizeof(double) * n2);
@@ -734,14 +685,15 @@ extern "C" long ovp_debug_read(ovp_ctx* c, const char* name, void* host, long ma
   else if (!strcmp(name, "P")) { src = c->P; bytes = nn; }
   else if (!strcmp(name, "G")) { src = c->G; bytes = (size_t)3 * c->n_feats * c->ldg * sizeof(double); }
   else if (!strcmp(name, "rec")) { src = c->rec; bytes = (size_t)c->fp.n_clones * c->n_feats * 2 * 21 * sizeof(double); }
-  else if (!strcmp(name, "plres")) { src = c->pl_res; bytes = (size_t)4 * c->pl_cap * sizeof(double); if (!src) return OVP_E_STATE; }
+  else if (!strcmp(name, "plres")) { src = c->pl_res; bytes = c->pl_res.capacity() * sizeof(double); if (!src) return OVP_E_STATE; }
   else if (!strcmp(name, "An")) { src = c->pl_An; bytes = nn; if (!src) return OVP_E_STATE; }
   else if (!strcmp(name, "bn")) { src = c->pl_bn; bytes = (size_t)c->n_max * sizeof(double); if (!src) return OVP_E_STATE; }
   // camera tables on the device: camera 0's of ovp_state_upload / every camera's of ovp_cameras_upload ([k][20], layout of `cal`)
   // capacity of the pinned result block the small fetches share (ovp_fetch_to_hres), one size_t
   else if (!strcmp(name, "pl_hres_cap")) {
     if ((size_t)max_bytes < sizeof(size_t)) return OVP_E_ARG;
-    memcpy(host, &c->pl_hres_cap, sizeof(size_t));
+    const size_t cap = c->pl_hres.capacity();
+    memcpy(host, &cap, sizeof(size_t));
     return (long)sizeof(size_t);
   }
   else if (!strcmp(name, "cal")) { src = c->cal; bytes = 20 * sizeof(double); if (!src) return OVP_E_STATE; }
@@ -778,9 +730,13 @@ extern "C" long ovp_debug_read(ovp_ctx* c, const char* name, void* host, long ma
     hipEventDestroy(e1);
     return 8;
   }
-  else if (!strcmp(name, "cycles_on")) {
-    if (!c->dbg_cycles && hipMalloc((void**)&c->dbg_cycles, (size_t)c->f_max * 10 * sizeof(long long)) != hipSuccess) return OVP_E_STATE;
-    return 0;
+  else if (!strcmp(name, "cycles_on")) return c->dbg_cycles.alloc((size_t)c->f_max * 10) != hipSuccess ? OVP_E_STATE : 0;
+  // bytes the process holds through the owning buffers of ovp_buf.h: [device | pinned], two int64; no stream is touched
+  else if (!strcmp(name, "live_bytes")) {
+    if (max_bytes < 16) return OVP_E_ARG;
+    const long long live[2] = {ovp_live_bytes().device.load(), ovp_live_bytes().pinned.load()};
+    memcpy(host, live, 16);
+    return 16;
   }
   else if (!strcmp(name, "cycles")) { src = c->dbg_cycles; bytes = (size_t)c->n_feats * 10 * sizeof(long long); if (!src) return OVP_E_STATE; }
   else return OVP_E_ARG;
@@ -801,10 +757,10 @@ extern "C" int ovp_debug_chol2(ovp_ctx* c, const double* A_host, int n, int lda,
   if (!c || !A_host || n < 1 || lda < n) return OVP_E_ARG;
   const int nb = brow_host ? n + 1 : n;
   if (nb > ovp_chol2_max_n() + 1) return OVP_E_CAPACITY;
-  double *dA = nullptr, *dL = nullptr, *dv = nullptr;
-  HIPCHK(dalloc(&dA, (size_t)n * n));
-  HIPCHK(dalloc(&dL, (size_t)nb * nb));
-  HIPCHK(dalloc(&dv, (size_t)4 * n + 16));
+  DevBuf<double> dA, dL, dv;
+  HIPCHK(dA.alloc((size_t)n * n));
+  HIPCHK(dL.alloc((size_t)nb * nb));
+  HIPCHK(dv.alloc((size_t)4 * n + 16));
   HIPCHK(hipMemcpy2D(dA, sizeof(double) * n, A_host, sizeof(double) * lda, sizeof(double) * n, n, hipMemcpyHostToDevice));
   if (brow_host) HIPCHK(hipMemcpy(dv, brow_host, sizeof(double) * n, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(dL, 0, sizeof(double) * (size_t)nb * nb));
@@ -827,8 +783,8 @@ extern "C" int ovp_debug_chol2(ovp_ctx* c, const double* A_host, int n, int lda,
   HIPCHK(ovp_launch_chol2(&j, nullptr, nullptr, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (getenv("OVP_C2_STAMPS")) {
-    long long* st = nullptr;
-    HIPCHK(hipMalloc((void**)&st, sizeof(long long) * 16 * 32));
+    DevBuf<long long> st;
+    HIPCHK(st.alloc(16 * 32));
     HIPCHK(hipMemset(st, 0, sizeof(long long) * 16 * 32));
     ovp::Chol2Job jt = j;
     jt.Ldense = nullptr;
@@ -838,7 +794,6 @@ extern "C" int ovp_debug_chol2(ovp_ctx* c, const double* A_host, int n, int lda,
     HIPCHK(hipStreamSynchronize(c->stream));
     long long h[16 * 32];
     HIPCHK(hipMemcpy(h, st, sizeof(h), hipMemcpyDeviceToHost));
-    hipFree(st);
     const int nt = (nb + 15) / 16;
     fprintf(stderr, "chol2 stamps (cycles): elimination wave 0 [wait column | read+eliminate | write] ; tile wave 0 [wait panel | reload + next column | wait buffer + publish | rest]\n");
     fprintf(stderr, " tile wave 0 prologue: issue loads %lld, patch special tiles %lld, publish column 0 %lld (elimination wave 0 starts waiting at %lld after the tile wave)\n",
@@ -879,9 +834,6 @@ extern "C" int ovp_debug_chol2(ovp_ctx* c, const double* A_host, int n, int lda,
   int fl[4];
   HIPCHK(hipMemcpy(fl, c->flags, sizeof(fl), hipMemcpyDeviceToHost));
   HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 4, c->stream));
-  hipFree(dA);
-  hipFree(dL);
-  hipFree(dv);
   return (fl[0] & 2) ? OVP_E_TIMEOUT : (fl[0] ? OVP_E_NOTSPD : 0);
 }
 

@@ -6,7 +6,7 @@
 
 extern "C" int ovp_cameras_upload(ovp_ctx* c, int n_cams, const ovp_camera_tables* cams) {
   if (!c || !cams || n_cams < 1 || n_cams > OVP_MAX_CAMERAS) return OVP_E_ARG;
-  if (!c->gen_cal) HIPCHK(dalloc(&c->gen_cal, (size_t)20 * OVP_MAX_CAMERAS));
+  HIPCHK(c->gen_cal.alloc((size_t)20 * OVP_MAX_CAMERAS));
   HIPCHK(hipStreamSynchronize(c->stream));  // (the previous tables may still be on their way: gen_cal_h is the source of the copy)
   for (int k = 0; k < n_cams; ++k) {
     double* cal = c->gen_cal_h + 20 * k;
@@ -42,18 +42,11 @@ int check_general_batch(const ovp_ctx* c, const ovp_general_batch* b, bool need_
 }
 
 static int gen_scratch(ovp_ctx* c, size_t bytes) {
-  if (bytes <= c->gen_cap) return 0;
+  if (bytes <= c->gen_buf.capacity()) return 0;
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->gen_buf) HIPCHK(hipFree(c->gen_buf));
-  c->gen_buf = nullptr;
-  c->gen_cap = 0;
-  const size_t cap = bytes + bytes / 2 + 4096;
-  HIPCHK(hipMalloc(&c->gen_buf, cap));
-  c->gen_cap = cap;
+  HIPCHK(c->gen_buf.reserve(bytes, bytes / 2 + 4096));
   return 0;
 }
-
-static inline size_t al64(size_t v) { return (v + 63) & ~(size_t)63; }
 
 extern "C" int ovp_msckf_general_features(ovp_ctx* c, const ovp_update_opts* o, const ovp_general_batch* b, uint8_t* accepted,
                                           double* chi2) {
@@ -64,11 +57,8 @@ extern "C" int ovp_msckf_general_features(ovp_ctx* c, const ovp_update_opts* o, 
     if (rc) return rc;
   }
   const int n = c->n, F = b->n_feats, M = b->max_meas;
-  const unsigned calmask = (o->do_calib_camera_pose ? 0x3Fu : 0u) | (o->do_calib_camera_intrinsics ? (0xFFu << 6) : 0u);
-  for (int k = 0; k < c->gen_ncams; ++k) {  // calibration columns of every camera the options estimate
-    if ((calmask & 0x3Fu) && (c->gen_calib_id[k] < 0 || c->gen_calib_id[k] + 6 > n)) return OVP_E_ARG;
-    if ((calmask >> 6) && (c->gen_intr_id[k] < 0 || c->gen_intr_id[k] + 8 > n)) return OVP_E_ARG;
-  }
+  const CalCols cc(c, o);
+  if (cc.check(n, true)) return OVP_E_ARG;  // calibration columns of every camera the options estimate
   c->dense_cols.clear();  // (a second call replaces the pending pair, as ovp_msckf_dense_blocks does)
   if (F == 0) return 0;
   // involved state columns of every feature (UpdaterHelper.cpp:205-277) and their union, ascending; a feature's local columns are
@@ -90,7 +80,7 @@ extern "C" int ovp_msckf_general_features(ovp_ctx* c, const ovp_update_opts* o, 
       const int cid = c->h_clone_id[b->clone_idx[ob]], cam = b->cam_idx[ob];
       for (int j = 0; j < 6; ++j) add(cid + j);
       for (int j = 0; j < 14; ++j)
-        if ((calmask >> j) & 1) add(j < 6 ? c->gen_calib_id[cam] + j : c->gen_intr_id[cam] + (j - 6));
+        if (cc.on(j)) add(cc.col_of(cam, j));
     }
     std::sort(cf.begin(), cf.end());
     q[f] = (int)cf.size();
@@ -112,13 +102,14 @@ extern "C" int ovp_msckf_general_features(ovp_ctx* c, const ovp_update_opts* o, 
   }
   // inputs: one pinned block, one copy [uv | clone_idx | cam_idx | n_meas | p_FinG | upos | loc | q | hp_off]; results behind them
   const size_t FM = (size_t)F * M;
-  const size_t o_uv = 0, o_ci = al64(o_uv + sizeof(float) * 2 * FM), o_cam = al64(o_ci + sizeof(int) * FM),
-               o_nm = al64(o_cam + sizeof(int) * FM), o_p = al64(o_nm + sizeof(int) * F), o_up = al64(o_p + sizeof(double) * 3 * F),
-               o_loc = al64(o_up + sizeof(int) * n), o_q = al64(o_loc + sizeof(int) * loc.size()),
-               o_off = al64(o_q + sizeof(int) * F), in_bytes = al64(o_off + sizeof(long long) * F);
+  StageLayout lay;
+  const size_t o_uv = lay.take(sizeof(float) * 2 * FM), o_ci = lay.take(sizeof(int) * FM), o_cam = lay.take(sizeof(int) * FM),
+               o_nm = lay.take(sizeof(int) * F), o_p = lay.take(sizeof(double) * 3 * F), o_up = lay.take(sizeof(int) * n),
+               o_loc = lay.take(sizeof(int) * loc.size()), o_q = lay.take(sizeof(int) * F),
+               o_off = lay.take(sizeof(long long) * F), in_bytes = lay.bytes();
   // device scratch [A | b | chi2 | accept | hp]: the first four come back to the host in one copy
   const size_t s_A = 0, s_b = s_A + sizeof(double) * (size_t)nu * nu, s_chi2 = s_b + sizeof(double) * nu,
-               s_acc = s_chi2 + sizeof(double) * F, out_bytes = al64(s_acc + F), s_hp = out_bytes,
+               s_acc = s_chi2 + sizeof(double) * F, out_bytes = StageLayout::al(s_acc + F), s_hp = out_bytes,
                scratch = s_hp + sizeof(double) * (size_t)hp_tot;
   void *ah = nullptr, *ad = nullptr;
   {
@@ -144,14 +135,9 @@ extern "C" int ovp_msckf_general_features(ovp_ctx* c, const ovp_update_opts* o, 
   memset(&g, 0, sizeof(g));
   g.fp = c->fp;
   g.fp.do_fej = o->do_fej;
-  g.fp.calmask = calmask;
+  g.fp.calmask = cc.mask;
   g.fp.white_px = 1.0 / o->sigma_px;
-  for (int k = 0; k < OVP_MAX_CAMERAS; ++k) {
-    g.cam_fisheye[k] = c->gen_fisheye[k];
-    g.cam_calib_id[k] = c->gen_calib_id[k];
-    g.cam_intr_id[k] = c->gen_intr_id[k];
-  }
-  g.cam_cal = c->gen_cal;
+  cc.fill_cameras_and_columns(g);
   g.uv = (const float*)(d + o_uv);
   g.clone_idx = (const int*)(d + o_ci);
   g.cam_idx = (const int*)(d + o_cam);
@@ -206,8 +192,10 @@ extern "C" int ovp_triangulate_general(ovp_ctx* c, const ovp_triang_opts* o, con
   if (F == 0) return 0;
   // arena: [uv_norm | clone_idx | cam_idx | n_meas] in, [p_FinG | ok] out
   const size_t FM = (size_t)F * M;
-  const size_t o_uv = 0, o_ci = al64(sizeof(float) * 2 * FM), o_cam = al64(o_ci + sizeof(int) * FM), o_nm = al64(o_cam + sizeof(int) * FM),
-               o_p = al64(o_nm + sizeof(int) * F), o_ok = o_p + sizeof(double) * 3 * F, total = al64(o_ok + F);
+  StageLayout lay;
+  const size_t o_uv = lay.take(sizeof(float) * 2 * FM), o_ci = lay.take(sizeof(int) * FM), o_cam = lay.take(sizeof(int) * FM),
+               o_nm = lay.take(sizeof(int) * F), o_p = lay.take(sizeof(double) * 3 * F + F), o_ok = o_p + sizeof(double) * 3 * F,
+               total = lay.bytes();  // (ok directly behind p_FinG: the two come back in one copy)
   void *ah = nullptr, *ad = nullptr;
   {
     const int rca = ovp_io_arena(c, total, &ah, &ad);
@@ -285,31 +273,25 @@ extern "C" int ovp_plane_fit_refine(ovp_ctx* c, const ovp_general_batch* b, cons
     }
   const int NF = (int)rs_fs.size() - 1, FR = rs_fs.back();
   const size_t FM = (size_t)F * M, n_sets = (size_t)NF * 200 * 5;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = al64(off + bytes);
-    return o;
-  };
+  StageLayout lay, wlay;
   // arena: inputs ...
-  const size_t o_fs = take(sizeof(int) * (P + 1)), o_slot = take(sizeof(int) * P), o_rfs = take(sizeof(int) * (NF + 1)),
-               o_rpts = take(sizeof(double) * 3 * FR), o_sets = take(sizeof(int) * n_sets), o_nm = take(sizeof(int) * F),
-               o_ci = take(sizeof(int) * FM), o_cam = take(sizeof(int) * FM), o_uv = take(sizeof(float) * 2 * FM),
-               o_p = take(sizeof(double) * 3 * F), o_cp = take(sizeof(double) * 3 * P), o_fix = take((size_t)P);
-  const size_t in_bytes = off;
+  const size_t o_fs = lay.take(sizeof(int) * (P + 1)), o_slot = lay.take(sizeof(int) * P), o_rfs = lay.take(sizeof(int) * (NF + 1)),
+               o_rpts = lay.take(sizeof(double) * 3 * FR), o_sets = lay.take(sizeof(int) * n_sets), o_nm = lay.take(sizeof(int) * F),
+               o_ci = lay.take(sizeof(int) * FM), o_cam = lay.take(sizeof(int) * FM), o_uv = lay.take(sizeof(float) * 2 * FM),
+               o_p = lay.take(sizeof(double) * 3 * F), o_cp = lay.take(sizeof(double) * 3 * P), o_fix = lay.take((size_t)P);
+  const size_t in_bytes = lay.bytes();
   // ... and results
-  const size_t o_pose = take(sizeof(double) * 12 * NC * NK), o_abcd = take(sizeof(double) * 4 * NF), o_rinl = take((size_t)FR),
-               o_rok = take((size_t)NF), o_cfs = take(sizeof(int) * (P + 1)), o_src = take(sizeof(int) * F),
-               o_cpo = take(sizeof(double) * 3 * P), o_po = take(sizeof(double) * 3 * F), o_kept = take((size_t)F),
-               o_ok = take((size_t)P), o_it = take(sizeof(int) * P);
-  const size_t total = off;
+  const size_t o_pose = lay.take(sizeof(double) * 12 * NC * NK), o_abcd = lay.take(sizeof(double) * 4 * NF), o_rinl = lay.take((size_t)FR),
+               o_rok = lay.take((size_t)NF), o_cfs = lay.take(sizeof(int) * (P + 1)), o_src = lay.take(sizeof(int) * F),
+               o_cpo = lay.take(sizeof(double) * 3 * P), o_po = lay.take(sizeof(double) * 3 * F), o_kept = lay.take((size_t)F),
+               o_ok = lay.take((size_t)P), o_it = lay.take(sizeof(int) * P);
+  const size_t total = lay.bytes();
   // device only: the refinement's lists
-  off = 0;
-  const size_t w_p0 = take(sizeof(double) * 3 * F), w_no = take(sizeof(int) * F), w_is = take(sizeof(int) * (P + 1)),
-               w_iob = take(sizeof(int) * O), w_ilf = take(sizeof(int) * O), w_fi0 = take(sizeof(int) * F),
-               w_uv = take(sizeof(double) * 2 * O), w_R = take(sizeof(double) * 9 * O), w_pc = take(sizeof(double) * 3 * O),
-               w_cp0 = take(sizeof(double) * 3 * P);
-  const size_t work = off;
+  const size_t w_p0 = wlay.take(sizeof(double) * 3 * F), w_no = wlay.take(sizeof(int) * F), w_is = wlay.take(sizeof(int) * (P + 1)),
+               w_iob = wlay.take(sizeof(int) * O), w_ilf = wlay.take(sizeof(int) * O), w_fi0 = wlay.take(sizeof(int) * F),
+               w_uv = wlay.take(sizeof(double) * 2 * O), w_R = wlay.take(sizeof(double) * 9 * O), w_pc = wlay.take(sizeof(double) * 3 * O),
+               w_cp0 = wlay.take(sizeof(double) * 3 * P);
+  const size_t work = wlay.bytes();
   void *ah = nullptr, *ad = nullptr;
   {
     const int rca = ovp_io_arena(c, total, &ah, &ad);

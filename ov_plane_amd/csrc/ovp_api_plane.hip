@@ -57,31 +57,21 @@ static int plane_job_device(ovp_ctx* c, const ovp_update_opts* o, const ovp::Fea
 }
 
 static int plane_buffers(ovp_ctx* c, int NP) {
-  const int ld = c->ld;
-  if (NP > c->pl_cap || !c->pl_E) {
-    void* olds[] = {c->pl_sid, c->pl_cp, c->pl_cp_fej, c->pl_res, c->pl_dx};
-    for (void* p : olds)
-      if (p) hipFree(p);
-    const int cap = NP + 8;
-    HIPCHK(dalloc(&c->pl_sid, (size_t)cap));
-    HIPCHK(dalloc(&c->pl_cp, (size_t)3 * cap));
-    HIPCHK(dalloc(&c->pl_cp_fej, (size_t)3 * cap));
-    HIPCHK(dalloc(&c->pl_res, (size_t)4 * cap));
-    HIPCHK(dalloc(&c->pl_dx, (size_t)c->n_max * cap));
-    c->pl_cap = cap;
-    if (!c->pl_E) {
-      const size_t ne = (size_t)(c->n_max + 4) * c->ldg;
-      HIPCHK(dalloc(&c->pl_featlist, (size_t)c->f_max));
-      HIPCHK(dalloc(&c->pl_cst, ((size_t)c->f_max + 1) * 10));  // (+ the record of a plane's general features)
-      HIPCHK(dalloc(&c->pl_cstsum, 16));
-      HIPCHK(dalloc(&c->pl_E, ne));
-      HIPCHK(dalloc(&c->pl_An, (size_t)(c->n_max + 1) * ld));
-      HIPCHK(dalloc(&c->pl_bn, (size_t)c->n_max));
-      HIPCHK(dalloc(&c->pl_Lr, (size_t)(c->n_max + 1) * ld));
-      HIPCHK(dalloc(&c->pl_Dinv2, (size_t)(ld / 16 + 1) * 256));
-      HIPCHK(dalloc(&c->pl_scal, 8));
-    }
-  }
+  const size_t ld = (size_t)c->ld, np = (size_t)NP, n_max = (size_t)c->n_max;
+  HIPCHK(c->pl_sid.reserve(np, 8));  // the per-plane tables: NP + 8 planes
+  HIPCHK(c->pl_cp.reserve(3 * np, 3 * 8));
+  HIPCHK(c->pl_cp_fej.reserve(3 * np, 3 * 8));
+  HIPCHK(c->pl_res.reserve(4 * np, 4 * 8));
+  HIPCHK(c->pl_dx.reserve(n_max * np, n_max * 8));
+  HIPCHK(c->pl_featlist.alloc((size_t)c->f_max));
+  HIPCHK(c->pl_cst.alloc(((size_t)c->f_max + 1) * 10));  // (+ the record of a plane's general features)
+  HIPCHK(c->pl_cstsum.alloc(16));
+  HIPCHK(c->pl_E.alloc((n_max + 4) * c->ldg));
+  HIPCHK(c->pl_An.alloc((n_max + 1) * ld));
+  HIPCHK(c->pl_bn.alloc(n_max));
+  HIPCHK(c->pl_Lr.alloc((n_max + 1) * ld));
+  HIPCHK(c->pl_Dinv2.alloc((ld / 16 + 1) * 256));
+  HIPCHK(c->pl_scal.alloc(8));
   return 0;
 }
 
@@ -112,8 +102,8 @@ struct PlaneLoopView {
 struct PlaneOut { double* dx_planes; uint8_t* plane_ok; double* plane_chi2; int* plane_dof; uint8_t* feat_used; };
 
 // column of calibration column k of camera `cam` (ovp_cameras_upload) in the loop's column order (pos: PlaneLoopView::gen_pos)
-static inline int gen_cam_col(const ovp_ctx* c, const int* pos, int n_pos, int cam, int k) {
-  const int id = k < 6 ? c->gen_calib_id[cam] + k : c->gen_intr_id[cam] + (k - 6);
+static inline int gen_cam_col(const CalCols& cc, const int* pos, int n_pos, int cam, int k) {
+  const int id = cc.col_of(cam, k);
   if (!pos) return id;
   return (id >= 0 && id < n_pos) ? pos[id] : -1;
 }
@@ -160,9 +150,9 @@ __global__ __launch_bounds__(1024) void k_fetch_block(const unsigned char* __res
 }
 int ovp_fetch_to_hres(ovp_ctx* c, const void* dsrc, size_t bytes, hipStream_t s) {
   // the sequence word sits at the start of the block's last whole 64-byte line: a block that reaches it would have its own last
-  // bytes overwritten by the word, so it takes the copy (plane2_buffers keeps the capacity a multiple of 64)
-  const size_t o_seq = c->pl_hres_cap >= 64 ? (c->pl_hres_cap - 64) & ~(size_t)63 : 0;
-  if (!c->pl_hres_dev || bytes > o_seq || (((size_t)dsrc) & 7) || bytes > (size_t)0x7fffffff) {
+  // bytes overwritten by the word, so it takes the copy (plane2_buffers keeps the capacity a multiple of 64: the last line is whole)
+  const size_t o_seq = c->pl_hres.capacity() >= 64 ? c->pl_hres.capacity() - 64 : 0;
+  if (!c->pl_hres.dev() || bytes > o_seq || (((size_t)dsrc) & 7) || bytes > (size_t)0x7fffffff) {
     HIPCHK(hipMemcpyAsync(c->pl_hres, dsrc, bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
@@ -170,46 +160,40 @@ int ovp_fetch_to_hres(ovp_ctx* c, const void* dsrc, size_t bytes, hipStream_t s)
   volatile unsigned* hseq = (volatile unsigned*)((char*)c->pl_hres + o_seq);
   *hseq = 0u;  // (payload of an earlier, larger block may have left any value there, the next sequence number included)
   const unsigned seq = ++c->pl_pub_seq;
-  hipLaunchKernelGGL(k_fetch_block, dim3(1), dim3(1024), 0, s, (const unsigned char*)dsrc, (unsigned char*)c->pl_hres_dev, (int)bytes,
-                     (volatile unsigned*)((char*)c->pl_hres_dev + o_seq), seq);
+  hipLaunchKernelGGL(k_fetch_block, dim3(1), dim3(1024), 0, s, (const unsigned char*)dsrc, (unsigned char*)c->pl_hres.dev(), (int)bytes,
+                     (volatile unsigned*)((char*)c->pl_hres.dev() + o_seq), seq);
   HIPCHK(hipGetLastError());
   return ovp_wait_seq(hseq, seq, s);
 }
 static int ensure_pl_used(ovp_ctx* c) {
-  if (!c->pl_used) HIPCHK(hipMalloc((void**)&c->pl_used, (size_t)c->f_max + 16));
+  HIPCHK(c->pl_used.alloc((size_t)c->f_max + 16));
   return 0;
 }
 
 int plane2_buffers(ovp_ctx* c, size_t stage_bytes, size_t res_bytes) {
   const int ld = c->ld;
-  if (!c->pl_Tbuf) {
+  if (!c->pl_xflag) {  // first use (pl_xflag comes last: a call that failed half-way is taken up again by the next)
     const size_t nn = (size_t)(c->n_max + 1) * ld;
-    HIPCHK(dalloc(&c->pl_Tbuf, 2 * nn));
-    HIPCHK(dalloc(&c->pl_crow, (size_t)c->n_max + 16));
-    HIPCHK(dalloc(&c->pl_dxlast, (size_t)c->n_max + 16));
-    HIPCHK(hipMalloc((void**)&c->pl_cur, 16));
-    HIPCHK(hipMalloc((void**)&c->pl_range_done, 16));
+    HIPCHK(c->pl_Tbuf.alloc(2 * nn));
+    HIPCHK(c->pl_crow.alloc((size_t)c->n_max + 16));
+    HIPCHK(c->pl_dxlast.alloc((size_t)c->n_max + 16));
+    HIPCHK(c->pl_cur.alloc(4));
+    HIPCHK(c->pl_range_done.alloc(4));
     HIPCHK(hipMemset(c->pl_range_done, 0, 16));
-    HIPCHK(dalloc(&c->pl_xbuf, (size_t)9 * 18 * 256));
-    HIPCHK(dalloc(&c->pl_xy, (size_t)c->n_max + 32));
-    HIPCHK(hipMalloc((void**)&c->pl_xflag, sizeof(unsigned) * 64));
+    HIPCHK(c->pl_xbuf.alloc((size_t)9 * 18 * 256));
+    HIPCHK(c->pl_xy.alloc((size_t)c->n_max + 32));
+    HIPCHK(c->pl_xflag.alloc(64));
     HIPCHK(hipMemset(c->pl_xflag, 0, sizeof(unsigned) * 64));
   }
-  if (stage_bytes > c->pl_stage_cap) {
+  if (stage_bytes > c->pl_dstage.capacity()) {  // (pl_dstage grows last: its capacity stands for both halves)
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->pl_hstage) hipHostFree(c->pl_hstage);
-    if (c->pl_dstage) hipFree(c->pl_dstage);
-    c->pl_stage_cap = stage_bytes + 4096;
-    HIPCHK(hipHostMalloc(&c->pl_hstage, c->pl_stage_cap, hipHostMallocDefault));
-    HIPCHK(hipMalloc(&c->pl_dstage, c->pl_stage_cap));
+    HIPCHK(c->pl_hstage.reserve(stage_bytes, 4096));
+    HIPCHK(c->pl_dstage.reserve(stage_bytes, 4096));
   }
-  if (res_bytes > c->pl_hres_cap) {
+  if (res_bytes > c->pl_hres.capacity()) {
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->pl_hres) hipHostFree(c->pl_hres);
-    c->pl_hres_cap = (res_bytes + 4096 + 63) & ~(size_t)63;  // (a multiple of 64: ovp_fetch_to_hres's sequence word ends the block)
-    HIPCHK(hipHostMalloc(&c->pl_hres, c->pl_hres_cap, hipHostMallocMapped));
-    memset(c->pl_hres, 0, c->pl_hres_cap);
-    HIPCHK(hipHostGetDevicePointer(&c->pl_hres_dev, c->pl_hres, 0));
+    HIPCHK(c->pl_hres.reserve(StageLayout::al(res_bytes + 4096), 0));  // (a multiple of 64: ovp_fetch_to_hres's sequence word ends the block)
+    memset(c->pl_hres, 0, c->pl_hres.capacity());
   }
   return 0;
 }
@@ -231,10 +215,8 @@ static int sub_tables_upload(ovp_ctx* c, const ovp_update_opts* o, const std::ve
   const size_t o_ids = 0, o_inv = sizeof(int) * (size_t)(c->n_max + 16), o_tab = 2 * o_inv;
   const size_t tab_bytes = sizeof(int) * (size_t)(c->c_max + 16) + sizeof(ovp::ColMap) * (size_t)c->n_max;
   const size_t blk_bytes = o_tab + tab_bytes;
-  if (!c->pl_sub_tab) {
-    HIPCHK(hipMalloc(&c->pl_sub_tab, blk_bytes));
-    HIPCHK(hipHostMalloc(&c->pl_sub_htab, blk_bytes, hipHostMallocDefault));
-  }
+  HIPCHK(c->pl_sub_tab.alloc(blk_bytes));
+  HIPCHK(c->pl_sub_htab.alloc(blk_bytes));
   if (c->ev_subtab) HIPCHK(hipEventSynchronize(c->ev_subtab));  // the pinned block fed the copy of the previous call (long done)
   else HIPCHK(hipEventCreateWithFlags(&c->ev_subtab, hipEventDisableTiming));
   char* hb = (char*)c->pl_sub_htab;
@@ -278,16 +260,18 @@ static int sub_tables_upload(ovp_ctx* c, const ovp_update_opts* o, const std::ve
 // the context's view of the state while a selection stands in for it, and back
 struct SubSaved {
   int n, calib_id, intr_id;
-  double* P;
+  const double* P;  // the resident block (c->P on entry)
   int* clone_id;
   ovp::ColMap* colmap;
   const int* fp_clone_id;
   std::vector<int> h_clone_id;
 };
-static SubSaved sub_enter(ovp_ctx* c, const SubTables& t, int ns, double* Psub) {
+// (the selection's covariance was gathered into c->P_tmp: the two buffers change places for as long as it stands in, and nothing
+// in between addresses c->P_tmp)
+static SubSaved sub_enter(ovp_ctx* c, const SubTables& t, int ns) {
   SubSaved sv{c->n, c->calib_id, c->intr_id, c->P, c->clone_id, c->colmap, c->fp.clone_id, c->h_clone_id};
   c->n = ns;
-  c->P = Psub;
+  c->P.swap(c->P_tmp);
   c->calib_id = t.calib_sub;
   c->intr_id = t.intr_sub;
   c->clone_id = t.d_clone_id;
@@ -298,7 +282,7 @@ static SubSaved sub_enter(ovp_ctx* c, const SubTables& t, int ns, double* Psub) 
 }
 static void sub_leave(ovp_ctx* c, const SubSaved& sv) {
   c->n = sv.n;
-  c->P = sv.P;
+  if (c->P.get() != sv.P) c->P.swap(c->P_tmp);  // (the resident block comes back whatever happened to the pair in between)
   c->calib_id = sv.calib_id;
   c->intr_id = sv.intr_id;
   c->clone_id = sv.clone_id;
@@ -323,8 +307,8 @@ struct SubScope {
   const ovp_update_opts* refill;
   SubSaved sv;
   bool in = false;
-  void enter(const SubTables& t, int ns, double* Psub) {
-    sv = sub_enter(c, t, ns, Psub);
+  void enter(const SubTables& t, int ns) {
+    sv = sub_enter(c, t, ns);
     in = true;
   }
   int leave() {
@@ -432,12 +416,8 @@ static int plane_update_ordered(ovp_ctx* c, const ovp_update_opts* o, const ovp_
   const int ns = (int)ids.size();
   hipStream_t s = c->stream;
   if (!full) {
-    if (!c->pl_Asum) HIPCHK(dalloc(&c->pl_Asum, (size_t)c->n_max * ld));
-    if (NP > c->pl_U_cap) {
-      if (c->pl_U) hipFree(c->pl_U);
-      c->pl_U_cap = NP + 8;
-      HIPCHK(dalloc(&c->pl_U, (size_t)c->pl_U_cap * ld));
-    }
+    HIPCHK(c->pl_Asum.alloc((size_t)c->n_max * ld));
+    HIPCHK(c->pl_U.reserve((size_t)NP * ld, (size_t)8 * ld));
   }
   std::vector<int> sid_sub(NP > 0 ? NP : 1, -1), slam_sub(n_slam > 0 ? n_slam : 1, 0);
   for (int k = 0; k < NP; ++k) sid_sub[k] = pb->plane_state_id[k] >= 0 ? pos[pb->plane_state_id[k]] : -1;
@@ -473,7 +453,7 @@ static int plane_update_ordered(ovp_ctx* c, const ovp_update_opts* o, const ovp_
   // again (k_gather_block_boost) - an exact stochastic clone then factors at the first attempt
   v.boost = full && n_inv < ns;
   if (v.boost) {
-    if (!c->boost_vec) HIPCHK(dalloc(&c->boost_vec, (size_t)c->n_max + 16));
+    HIPCHK(c->boost_vec.alloc((size_t)c->n_max + 16));
     HIPCHK(ovp_launch_gather_block_boost(c->P, ld, d_ids, ns, c->P_tmp, ld, n_inv, 1e-9, c->boost_vec, s));
   } else {
     HIPCHK(ovp_launch_gather_block(c->P, ld, d_ids, ns, c->P_tmp, ld, s));
@@ -490,7 +470,7 @@ static int plane_update_ordered(ovp_ctx* c, const ovp_update_opts* o, const ovp_
   double* const dx_planes = out.dx_planes;
   {
     SubScope sub{c, nullptr};
-    sub.enter(st, ns, c->P_tmp);
+    sub.enter(st, ns);
     const PlaneOut out_sub{dx_sub.data(), out.plane_ok, out.plane_chi2, out.plane_dof, out.feat_used};
     const int rc = plane_loop(c, o, &pbs, v, out_sub);
     if (rc) return rc;  // the resident covariance was not touched (the device tables may have been: a loop that fails after
@@ -658,6 +638,7 @@ static int plane_group(const ovp_ctx* c, const ovp_update_opts* o, const ovp_pla
   const int ncal = (o->do_calib_camera_pose ? 6 : 0) + (o->do_calib_camera_intrinsics ? 8 : 0);
   const PlaneBuckets bf = bucket_by_plane(F, NP, [&](int f) { return pb->plane_of_feat[f]; });
   const PlaneBuckets bg = bucket_by_plane(GF, NP, [&](int i) { return gbp->n_meas[i] >= 2 ? v.plane_of_gen[i] : 0; });
+  const CalCols cc(c, o);
   for (int pl = 0; pl < NP; ++pl) {
     PlaneJobH j;
     j.pl = pl;
@@ -738,8 +719,8 @@ static int plane_group(const ovp_ctx* c, const ovp_update_opts* o, const ovp_pla
         for (int cam = 0; cam < c->gen_ncams; ++cam)
           if ((cams_seen >> cam) & 1u)
             for (int k = 0; k < 14; ++k) {
-              if (!(k < 6 ? o->do_calib_camera_pose : o->do_calib_camera_intrinsics)) continue;
-              const int col = gen_cam_col(c, v.gen_pos, v.n_state, cam, k);
+              if (!cc.on(k)) continue;
+              const int col = gen_cam_col(cc, v.gen_pos, v.n_state, cam, k);
               if (col < 0 || col >= n) return OVP_E_ARG;
               inv[col] = 1;
             }
@@ -825,32 +806,30 @@ static int plane_gen_upload(ovp_ctx* c, const ovp_update_opts* o, const PlaneLoo
   hipStream_t s = c->stream;
   memset(&gs->gp0, 0, sizeof(gs->gp0));
   memset(&gs->cols, 0xff, sizeof(gs->cols));
-  gs->calmask = (o->do_calib_camera_pose ? 0x3Fu : 0u) | (o->do_calib_camera_intrinsics ? (0xFFu << 6) : 0u);
+  const CalCols cc(c, o);
+  gs->calmask = cc.mask;
   if (gbp) {
     for (int cam = 0; cam < c->gen_ncams; ++cam)
       for (int k = 0; k < 14; ++k)
-        if ((gs->calmask >> k) & 1u) {
-          gs->cols.col[cam][k] = gen_cam_col(c, v.gen_pos, v.n_state, cam, k);
+        if (cc.on(k)) {
+          gs->cols.col[cam][k] = gen_cam_col(cc, v.gen_pos, v.n_state, cam, k);
           if (gs->cols.col[cam][k] < 0 || gs->cols.col[cam][k] >= n) return plane_bail(c, fork, OVP_E_ARG);
         }
   }
   if (!gbp || g.glist.empty()) return 0;
   const int GF = gbp->n_feats, GM = gbp->max_meas;
-  auto al = [](size_t b) { return (b + 63) & ~(size_t)63; };
   const size_t GFM = (size_t)GF * GM;
-  const size_t o_uv = 0, o_ci = al(sizeof(float) * 2 * GFM), o_cam = al(o_ci + sizeof(int) * GFM), o_nm = al(o_cam + sizeof(int) * GFM),
-               o_p = al(o_nm + sizeof(int) * GF), o_list = al(o_p + sizeof(double) * 3 * GF), in_bytes = al(o_list + sizeof(int) * g.glist.size());
+  StageLayout lay;
+  const size_t o_uv = lay.take(sizeof(float) * 2 * GFM), o_ci = lay.take(sizeof(int) * GFM), o_cam = lay.take(sizeof(int) * GFM),
+               o_nm = lay.take(sizeof(int) * GF), o_p = lay.take(sizeof(double) * 3 * GF), o_list = lay.take(sizeof(int) * g.glist.size()),
+               in_bytes = lay.bytes();
   const size_t mark_stride = (size_t)((n + 4 + 15) & ~15), hp_stride = (size_t)ovp::PG_ROWS * (n + 4);
   // inputs through the pinned arena (nobody else uses it while a plane loop is enqueued; the previous user has waited for its
   // copy), marks and staged rows in a device block of their own: no host synchronisation unless a block has to grow
-  const size_t o_hp = al(sizeof(int) * mark_stride * g.ng_max), total = o_hp + sizeof(double) * hp_stride * g.ng_max;
-  if (total > c->pl_gen_cap) {
+  const size_t o_hp = StageLayout::al(sizeof(int) * mark_stride * g.ng_max), total = o_hp + sizeof(double) * hp_stride * g.ng_max;
+  if (total > c->pl_gen_dev.capacity()) {
     HIPCHK(hipStreamSynchronize(s));
-    if (c->pl_gen_dev) HIPCHK(hipFree(c->pl_gen_dev));
-    c->pl_gen_dev = nullptr;
-    c->pl_gen_cap = 0;
-    HIPCHK(hipMalloc(&c->pl_gen_dev, total + total / 2));
-    c->pl_gen_cap = total + total / 2;
+    HIPCHK(c->pl_gen_dev.reserve(total, total / 2));
   }
   void *ah = nullptr, *ad = nullptr;
   {
@@ -870,8 +849,7 @@ static int plane_gen_upload(ovp_ctx* c, const ovp_update_opts* o, const PlaneLoo
   ovp::PlaneGenParams& gp0 = gs->gp0;
   gp0.fp = pre.fp;
   gp0.fp.calmask = gs->calmask;
-  gp0.cam_cal = c->gen_cal;
-  for (int k = 0; k < OVP_MAX_CAMERAS; ++k) gp0.cam_fisheye[k] = c->gen_fisheye[k];
+  cc.fill_cameras(gp0);
   gp0.cc = gs->cols;
   gp0.uv = (const float*)(d + o_uv);
   gp0.clone_idx = (const int*)(d + o_ci);
@@ -1190,7 +1168,7 @@ static int plane_cov_product(ovp_ctx* c, const PlaneLoopView& v, size_t tstride,
   // covariance just formed for the point update behind the loop (P = V^T V: M = V^T, rows in state order) - one launch for both
   const bool keep_factor = getenv("OVP_NO_KEPT_FACTOR") == nullptr;  // (read per call: the tests switch it)
   const bool want_factor = keep_factor && !v.marginal && n <= OVP_TILECHOL_NMAX;
-  if (want_factor && !c->Lkeep) HIPCHK(dalloc(&c->Lkeep, (size_t)c->n_max * ld));
+  if (want_factor) HIPCHK(c->Lkeep.alloc((size_t)c->n_max * ld));
   if (v.scatter_dst) {
     HIPCHK(ovp_launch_unpermute_pair(c->P, c->Y, ld, v.scatter_ids, n, v.scatter_dst, want_factor ? c->Lkeep : nullptr, ld,
                                      c->flags, v.boost ? c->boost_vec : nullptr, s));
@@ -1212,14 +1190,14 @@ static PlaneResBlock plane_res_block(const ovp_ctx* c, int NP) {
   b.res = (double*)c->pl_hres;
   b.dx = b.res + 4 * (size_t)NP;
   b.used = (unsigned char*)(b.dx + (size_t)c->n * NP);
-  b.flags = (char*)b.used + (((size_t)c->n_feats + 63) & ~(size_t)63);
+  b.flags = (char*)b.used + StageLayout::al((size_t)c->n_feats);
   b.seq = (volatile unsigned*)(b.flags + 64);
   return b;
 }
 static int plane_publish(ovp_ctx* c, const PlaneResBlock& b, int NP, bool want_dx, unsigned* seq_out) {
   *b.seq = 0u;  // (its offset depends on NP, n and F: an earlier call's payload may have left the next sequence number there)
   const unsigned seq = *seq_out = ++c->pl_pub_seq;
-  char* dbase = (char*)c->pl_hres_dev;
+  char* dbase = (char*)c->pl_hres.dev();
   auto dev_of = [&](const void* hp) { return dbase + ((const char*)hp - (const char*)c->pl_hres); };
   hipLaunchKernelGGL(k_publish_plane_results, dim3(1), dim3(1024), 0, c->stream, c->pl_res, 4 * NP, c->pl_dx, want_dx ? c->n * NP : 0,
                      c->pl_used, c->n_feats, c->flags, (double*)dev_of(b.res), (double*)dev_of(b.dx), (unsigned char*)dev_of(b.used),
@@ -1403,10 +1381,7 @@ extern "C" int ovp_msckf_plane_update_general(ovp_ctx* c, const ovp_update_opts*
     if (!c->have_state || !c->have_cov || c->gen_ncams < 1) return OVP_E_STATE;
     const int rc = check_general_batch(c, gb, true, plane_of_gen);
     if (rc) return rc;
-    for (int k = 0; k < c->gen_ncams; ++k) {  // calibration columns of every camera the options estimate
-      if (o->do_calib_camera_pose && (c->gen_calib_id[k] < 0 || c->gen_calib_id[k] + 6 > c->n)) return OVP_E_ARG;
-      if (o->do_calib_camera_intrinsics && (c->gen_intr_id[k] < 0 || c->gen_intr_id[k] + 8 > c->n)) return OVP_E_ARG;
-    }
+    if (CalCols(c, o).check(c->n, true)) return OVP_E_ARG;  // calibration columns of every camera the options estimate
   }
   if (gen_used && GF > 0) memset(gen_used, 0, (size_t)GF);
   const PlaneOut out{dx_planes, plane_ok, plane_chi2, plane_dof, feat_used};
@@ -1472,11 +1447,8 @@ extern "C" int ovp_plane_init(ovp_ctx* c, const ovp_update_opts* o, const ovp_pl
     if (ns > OVP_TILECHOL_NMAX) return OVP_E_CAPACITY;
     rc = sub_tables_upload(c, o, co.ids, co.pos, &sub_t, s);
     if (rc) return rc;
-    if (!c->pl_Asum) HIPCHK(dalloc(&c->pl_Asum, (size_t)c->n_max * ld));
-    if (c->pl_U_cap < 1) {
-      c->pl_U_cap = 8;
-      HIPCHK(dalloc(&c->pl_U, (size_t)c->pl_U_cap * ld));
-    }
+    HIPCHK(c->pl_Asum.alloc((size_t)c->n_max * ld));
+    HIPCHK(c->pl_U.alloc((size_t)8 * ld));
   }
   for (int pl = 0; pl < NP; ++pl) {
     const int n = c->n;
@@ -1510,7 +1482,7 @@ extern "C" int ovp_plane_init(ovp_ctx* c, const ovp_update_opts* o, const ovp_pl
     SubScope sub{c, o};  // (leaving it also puts the state's calibration columns back into c->fp)
     if (ns) {  // the marginal of the selection stands in for the state
       HIPCHK(ovp_launch_gather_block(c->P, ld, sub_t.d_ids, ns, c->P_tmp, ld, s));
-      sub.enter(sub_t, ns, c->P_tmp);
+      sub.enter(sub_t, ns);
       rc = fill_feat_params(c, o);  // (the calibration columns of the selection)
       if (rc) return rc;
       fp = c->fp;

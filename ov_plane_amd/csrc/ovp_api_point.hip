@@ -25,8 +25,8 @@ static bool substate_ok(const ovp_ctx* c) { return c->n > OVP_TILECHOL_NMAX && c
 int set_substate(ovp_ctx* c, const std::vector<int>& ids) {
   c->sub_ns = 0;
   if (c->n <= OVP_TILECHOL_NMAX || ids.empty() || (int)ids.size() > OVP_TILECHOL_NMAX) return 0;
-  if (!c->sub_ids) HIPCHK(hipMalloc((void**)&c->sub_ids, sizeof(int) * (OVP_TILECHOL_NMAX + 16)));
-  if (!c->sub_buf) HIPCHK(dalloc(&c->sub_buf, (size_t)6 * OVP_TILECHOL_NMAX * OVP_TILECHOL_NMAX));
+  HIPCHK(c->sub_ids.alloc(OVP_TILECHOL_NMAX + 16));
+  HIPCHK(c->sub_buf.alloc((size_t)6 * OVP_TILECHOL_NMAX * OVP_TILECHOL_NMAX));
   HIPCHK(hipMemcpyAsync(c->sub_ids, ids.data(), sizeof(int) * ids.size(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));  // ids is the caller's temporary
   c->sub_ns = (int)ids.size();
@@ -161,8 +161,8 @@ int ekf_from_gram(ovp_ctx* c, bool chol_p_done_on_stream2, bool publish) {
       // the last block of the dx kernel also publishes [flags | dx] to the pinned host block (no separate launch)
       const int words = (int)((16 + sizeof(double) * (size_t)n + 7) / 8);
       c->pub_seq = ++c->seq;
-      HIPCHK(ovp_launch_dx_rows_boost(c->P, n, ld, b, c->dx, c->flags + 1, c->ticket, c->res_block, c->h_res_block_dev, words,
-                                      (char*)c->h_res_block_dev + ((char*)c->h_seq - (char*)c->h_res_block), c->pub_seq, boost_ptr,
+      HIPCHK(ovp_launch_dx_rows_boost(c->P, n, ld, b, c->dx, c->flags + 1, c->ticket, c->res_block, c->h_res_block.dev(), words,
+                                      (char*)c->h_res_block.dev() + ((char*)c->h_seq - (char*)c->h_res_block), c->pub_seq, boost_ptr,
                                       boost_n, c->flags, c->stream));
       c->pub_pending = true;
     } else {
@@ -177,8 +177,8 @@ int ekf_from_gram(ovp_ctx* c, bool chol_p_done_on_stream2, bool publish) {
     if (publish) {
       const int words = (int)((16 + sizeof(double) * (size_t)n + 7) / 8);
       c->pub_seq = ++c->seq;
-      HIPCHK(ovp_launch_dx_rows(c->P, n, ld, b, c->dx, c->flags + 1, c->ticket, c->res_block, c->h_res_block_dev, words,
-                                (char*)c->h_res_block_dev + ((char*)c->h_seq - (char*)c->h_res_block), c->pub_seq, c->stream));
+      HIPCHK(ovp_launch_dx_rows(c->P, n, ld, b, c->dx, c->flags + 1, c->ticket, c->res_block, c->h_res_block.dev(), words,
+                                (char*)c->h_res_block.dev() + ((char*)c->h_seq - (char*)c->h_res_block), c->pub_seq, c->stream));
       c->pub_pending = true;
     } else {
       HIPCHK(ovp_launch_dx_rows(c->P, n, ld, b, c->dx, c->flags + 1, nullptr, nullptr, nullptr, 0, nullptr, 0u, c->stream));
@@ -266,12 +266,9 @@ int fill_feat_params(ovp_ctx* c, const ovp_update_opts* o) {
   fp.n_feats = F;
   fp.max_meas = c->max_meas;
   fp.do_fej = o->do_fej;
-  fp.calmask = (o->do_calib_camera_pose ? 0x3Fu : 0u) | (o->do_calib_camera_intrinsics ? (0xFFu << 6) : 0u);
-  for (int k = 0; k < 14; ++k) {
-    fp.calcol[k] = (k < 6) ? c->calib_id + k : c->intr_id + (k - 6);
-    if (!((fp.calmask >> k) & 1)) fp.calcol[k] = 0;
-    else if (fp.calcol[k] < 0 || fp.calcol[k] >= n) return OVP_E_ARG;
-  }
+  const CalCols cc(c, o);
+  if (cc.check(n, false)) return OVP_E_ARG;
+  cc.fill(fp);
   fp.white_px = 1.0 / o->sigma_px;
   fp.chi2_mult = o->chi2_multiplier;
   fp.chi2_table = c->chi2_table;
@@ -283,8 +280,8 @@ int fill_feat_params(ovp_ctx* c, const ovp_update_opts* o) {
   fp.ldg = c->ldg;
   fp.rec = c->rec;
   // per-feature results straight into the pinned host block (same layout as res_block): they cross PCIe while K1 runs
-  fp.chi2 = (double*)((char*)c->h_res_block_dev + ((char*)c->chi2 - (char*)c->res_block));
-  fp.accept = (unsigned char*)c->h_res_block_dev + ((char*)c->accept - (char*)c->res_block);
+  fp.chi2 = (double*)((char*)c->h_res_block.dev() + ((char*)c->chi2 - (char*)c->res_block));
+  fp.accept = (unsigned char*)c->h_res_block.dev() + ((char*)c->accept - (char*)c->res_block);
   fp.dbg_cycles = c->dbg_cycles;
   fp.slot = nullptr;
   fp.n_out = 0;
@@ -325,7 +322,7 @@ static int build_gate_gram_tail_impl(ovp_ctx* c, int n, int F) {
       int k = 0;
       for (int f = 0; f < F; ++f) c->h_slot[f] = (f >= lo && f < hi && !(masked && c->h_pl_used[f])) ? k++ : -1;
       Fa = k;
-      fp.slot = c->d_slot;
+      fp.slot = c->h_slot.dev();
       fp.n_out = Fa;
     }
   }
@@ -399,7 +396,7 @@ static int build_gate_gram_tail_impl(ovp_ctx* c, int n, int F) {
         // takes off again (CholJob::boost): exact, and an exact stochastic clone (IMU pose == newest clone) factors on this path
         const bool no_boost = getenv("OVP_POINT_NO_BOOST") != nullptr;  // (read per call: the tests switch it)
         if (!no_boost && s0 <= 64) {
-          if (!c->boost) HIPCHK(dalloc(&c->boost, 64));
+          HIPCHK(c->boost.alloc(64));
           cj.boost = c->boost;
           cj.boost_n = s0;
           cj.boost_rel = 1e-9;
@@ -470,8 +467,8 @@ static int build_gate_gram_tail_impl(ovp_ctx* c, int n, int F) {
   if (!c->dense_cols.empty()) {
     // the pair of the dense blocks accepted by ovp_msckf_dense_blocks joins the batch's (same update, update/UpdaterMSCKF.cpp:767-814)
     const int m = (int)c->dense_cols.size();
-    if (!c->Acc) HIPCHK(dalloc(&c->Acc, (size_t)c->n_max * c->n_max));
-    if (!c->bcc) HIPCHK(dalloc(&c->bcc, (size_t)c->n_max));
+    HIPCHK(c->Acc.alloc((size_t)c->n_max * c->n_max));
+    HIPCHK(c->bcc.alloc((size_t)c->n_max));
     HIPCHK(hipMemcpyAsync(c->Acc, c->dense_A.data(), sizeof(double) * (size_t)m * m, hipMemcpyHostToDevice, s2k));
     HIPCHK(hipMemcpyAsync(c->bcc, c->dense_b.data(), sizeof(double) * m, hipMemcpyHostToDevice, s2k));
     HIPCHK(hipMemcpyAsync(c->idbuf, c->dense_cols.data(), sizeof(int) * m, hipMemcpyHostToDevice, s2k));
@@ -623,7 +620,7 @@ extern "C" int ovp_msckf_fetch_results(ovp_ctx* c, double* dx_host, uint8_t* acc
       const int words = (int)((16 + sizeof(double) * (size_t)n + 7) / 8);
       seq = ++c->seq;
       hipLaunchKernelGGL(k_publish_results, dim3(1), dim3(1024), 0, c->stream, (unsigned long long*)c->res_block,
-                         (unsigned long long*)c->h_res_block_dev, words, (volatile unsigned*)((char*)c->h_res_block_dev +
+                         (unsigned long long*)c->h_res_block.dev(), words, (volatile unsigned*)((char*)c->h_res_block.dev() +
                          ((char*)c->h_seq - (char*)c->h_res_block)), seq);
       HIPCHK(hipGetLastError());
     }
@@ -725,7 +722,7 @@ extern "C" int ovp_ekf_update(ovp_ctx* c, const double* H_host, int rows, int co
     double* dM = dres + res_doubles;
     double* dLi = dM + (size_t)n * rows;
     double* dy = dLi + (size_t)rows * rows;
-    if ((size_t)(dy + rows + 8 - c->smallbuf) > c->small_cap) return OVP_E_CAPACITY;
+    if ((size_t)(dy + rows + 8 - c->smallbuf) > c->smallbuf.capacity()) return OVP_E_CAPACITY;
     HIPCHK(hipMemcpyAsync(c->pl_dstage, c->pl_hstage, bytes, hipMemcpyHostToDevice, s));
     HIPCHK(ovp_launch_init_m(c->P, c->ld, n, did, cols, d + oHt, rows, dM, s));
     HIPCHK(ovp_launch_init_core(c->P, c->ld, n, did, cols, d + oHt, 0, rows, dM, d + oRes /* unused: k = 0 */, d + oRes, d + oRes, 1.0,
@@ -744,25 +741,15 @@ extern "C" int ovp_ekf_update(ovp_ctx* c, const double* H_host, int rows, int co
       info->neg_diag = hres[2] != 0.0;
     }
     if (!(hres[1] > 0.5)) return OVP_E_NOTSPD;  // S = H P H^T + I lost definiteness: P is not a covariance; nothing was written
-    double* t = c->P;
-    c->P = c->P_tmp;
-    c->P_tmp = t;
+    c->P.swap(c->P_tmp);
     if (dx_host) memcpy(dx_host, hres + 4, sizeof(double) * n);
     return hres[2] != 0.0 ? OVP_E_NEGDIAG : 0;
   }
   const size_t need = (size_t)ld * cols;
-  if (need > c->Hd_cap) {
-    if (c->Hd) hipFree(c->Hd);
-    HIPCHK(dalloc(&c->Hd, need));
-    c->Hd_cap = need;
-  }
-  if ((size_t)rows > c->res_cap) {
-    if (c->resd) hipFree(c->resd);
-    HIPCHK(dalloc(&c->resd, (size_t)rows + 64));
-    c->res_cap = (size_t)rows + 64;
-  }
-  if (!c->Acc) HIPCHK(dalloc(&c->Acc, (size_t)c->n_max * c->n_max));
-  if (!c->bcc) HIPCHK(dalloc(&c->bcc, (size_t)c->n_max));
+  HIPCHK(c->Hd.reserve(need, 0));
+  HIPCHK(c->resd.reserve((size_t)rows, 64));
+  HIPCHK(c->Acc.alloc((size_t)c->n_max * c->n_max));
+  HIPCHK(c->bcc.alloc((size_t)c->n_max));
   HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 4, c->stream));
   HIPCHK(hipMemcpyAsync(c->Hd, H_host, sizeof(double) * need, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->resd, res_host, sizeof(double) * rows, hipMemcpyHostToDevice, c->stream));

@@ -25,8 +25,10 @@ extern "C" int ovp_triangulate(ovp_ctx* c, const ovp_triang_opts* o, const float
   const size_t F = (size_t)c->n_feats, M = (size_t)c->max_meas;
   if (F == 0) return 0;
   // arena: [uv_norm | -> p_FinG | ok]
-  auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-  const size_t b_uv = sizeof(float) * F * M * 2, o_p = al(b_uv), o_ok = al(o_p + sizeof(double) * 3 * F), total = al(o_ok + F);
+  StageLayout lay;
+  const size_t b_uv = sizeof(float) * F * M * 2;
+  lay.take(b_uv);
+  const size_t o_p = lay.take(sizeof(double) * 3 * F), o_ok = lay.take(F), total = lay.bytes();
   void *ah = nullptr, *ad = nullptr;
   {
     const int rca = ovp_io_arena(c, total, &ah, &ad);
@@ -86,20 +88,9 @@ static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam
   if (M < 1 || M > OVP_MAX_MEAS || !b->n_meas || !b->landmark_id) return OVP_E_ARG;
   const bool any_pre = b->pre_rows != nullptr;
   if (any_pre && (!b->pre_cols || !b->pre_H || !b->pre_ids)) return OVP_E_ARG;
-  const unsigned calmask = (o->do_calib_camera_pose ? 0x3Fu : 0u) | (o->do_calib_camera_intrinsics ? (0xFFu << 6) : 0u);
-  const int ncal = __builtin_popcount(calmask);
-  int calcol[14];
-  for (int k = 0; k < 14; ++k) {
-    calcol[k] = (k < 6) ? c->calib_id + k : c->intr_id + (k - 6);
-    if (!((calmask >> k) & 1)) calcol[k] = 0;
-    else if (!gen && (calcol[k] < 0 || calcol[k] >= n)) return OVP_E_ARG;
-  }
-  // general: state column of calibration column k of camera cam
-  auto gcal = [&](int cam, int k) { return k < 6 ? c->gen_calib_id[cam] + k : c->gen_intr_id[cam] + (k - 6); };
-  if (gen)
-    for (int cam = 0; cam < c->gen_ncams; ++cam)
-      for (int k = 0; k < 14; ++k)
-        if (((calmask >> k) & 1) && (gcal(cam, k) < 0 || gcal(cam, k) >= n)) return OVP_E_ARG;
+  const CalCols cc(c, o);
+  if (cc.check(n, gen)) return OVP_E_ARG;
+  const int ncal = cc.ncal;
   std::vector<int> cam_mask(gen ? L : 0, 0);
   const int C = (int)c->h_clone_id.size();
   // ---- host: the call's column list (first-seen order, as Hx_order_big of :634-646), row offsets, kernel geometry
@@ -158,10 +149,10 @@ static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam
           for (int cam = 0; cam < OVP_MAX_CAMERAS; ++cam)
             if ((camm >> cam) & 1)
               for (int k = 0; k < 14; ++k)
-                if ((calmask >> k) & 1) touch(gcal(cam, k));
+                if (cc.on(k)) touch(cc.col_of(cam, k));
         } else {
           for (int k = 0; k < 14; ++k)
-            if ((calmask >> k) & 1) touch(calcol[k]);
+            if (cc.on(k)) touch(cc.col[k]);
         }
         for (int k = 0; k < 3; ++k) touch(b->landmark_id[l] + k);
         if (plane)
@@ -183,23 +174,19 @@ static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam
   const int h_in_lds = ovp_slam_gate_lds(rows_max, cols_max, 1) <= 150 * 1024 ? 1 : 0;
   hipStream_t s = c->stream;
   // ---- one pinned staging block -> one copy
-  auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o0 = off;
-    off = al(off + bytes);
-    return o0;
-  };
-  const size_t o_p = take(sizeof(double) * 3 * L), o_pf = take(sizeof(double) * 3 * L), o_cp = take(sizeof(double) * 3 * L),
-               o_cpf = take(sizeof(double) * 3 * L), o_preH = take(sizeof(double) * (preH + 1)), o_uv = take(sizeof(float) * 2 * (size_t)L * M),
-               o_ci = take(sizeof(int) * (size_t)L * M), o_nm = take(sizeof(int) * L), o_lm = take(sizeof(int) * L),
-               o_ps = take(sizeof(int) * L), o_r0 = take(sizeof(int) * L), o_gp = take(sizeof(int) * n),
-               o_gi = take(sizeof(int) * gcols), o_pr = take(sizeof(int) * L), o_pc = take(sizeof(int) * L),
-               o_po = take(sizeof(int) * L), o_pio = take(sizeof(int) * L), o_pid = take(sizeof(int) * (preI + 1));
-  const size_t o_cam = take(gen ? sizeof(int) * (size_t)L * M : 0), o_cm = take(gen ? sizeof(int) * L : 0);  // (general only)
-  const size_t stage_bytes = off;
+  StageLayout lay;
+  const size_t o_p = lay.take(sizeof(double) * 3 * L), o_pf = lay.take(sizeof(double) * 3 * L), o_cp = lay.take(sizeof(double) * 3 * L),
+               o_cpf = lay.take(sizeof(double) * 3 * L), o_preH = lay.take(sizeof(double) * (preH + 1)), o_uv = lay.take(sizeof(float) * 2 * (size_t)L * M),
+               o_ci = lay.take(sizeof(int) * (size_t)L * M), o_nm = lay.take(sizeof(int) * L), o_lm = lay.take(sizeof(int) * L),
+               o_ps = lay.take(sizeof(int) * L), o_r0 = lay.take(sizeof(int) * L), o_gp = lay.take(sizeof(int) * n),
+               o_gi = lay.take(sizeof(int) * gcols), o_pr = lay.take(sizeof(int) * L), o_pc = lay.take(sizeof(int) * L),
+               o_po = lay.take(sizeof(int) * L), o_pio = lay.take(sizeof(int) * L), o_pid = lay.take(sizeof(int) * (preI + 1));
+  const size_t o_cam = lay.take(gen ? sizeof(int) * (size_t)L * M : 0), o_cm = lay.take(gen ? sizeof(int) * L : 0);  // (general only)
+  const size_t stage_bytes = lay.bytes();
   const size_t res_doubles = 4 + (size_t)c->n_max + 8;
-  const size_t lres_bytes = al(sizeof(double) * L) + al((size_t)L);
+  StageLayout lres;  // per-landmark results: [chi2 | status]
+  lres.take(sizeof(double) * L);
+  const size_t o_status = lres.take((size_t)L), lres_bytes = lres.bytes();
   int rc = plane2_buffers(c, stage_bytes, res_doubles * sizeof(double) + lres_bytes + 64);
   if (rc) return rc;
   char* h = (char*)c->pl_hstage;
@@ -234,37 +221,10 @@ static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam
   }
   // ---- device buffers: the stacked system (Hd = H^T [gcols][m_total], resd), per-landmark results, block scratch
   const size_t need = (size_t)gcols * m_total;
-  if (need > c->Hd_cap) {
-    if (c->Hd) hipFree(c->Hd);
-    c->Hd = nullptr;
-    c->Hd_cap = 0;
-    HIPCHK(dalloc(&c->Hd, need + 64));
-    c->Hd_cap = need + 64;
-  }
-  if ((size_t)m_total > c->res_cap) {
-    if (c->resd) hipFree(c->resd);
-    c->resd = nullptr;
-    c->res_cap = 0;
-    HIPCHK(dalloc(&c->resd, (size_t)m_total + 64));
-    c->res_cap = (size_t)m_total + 64;
-  }
-  if (lres_bytes > c->slam_res_cap) {
-    if (c->slam_res) hipFree(c->slam_res);
-    c->slam_res = nullptr;
-    c->slam_res_cap = 0;
-    HIPCHK(hipMalloc(&c->slam_res, lres_bytes + 4096));
-    c->slam_res_cap = lres_bytes + 4096;
-  }
-  if (!h_in_lds) {
-    const size_t hs = (size_t)L * rows_max * cols_max;
-    if (hs > c->slam_hscr_cap) {
-      if (c->slam_hscr) hipFree(c->slam_hscr);
-      c->slam_hscr = nullptr;
-      c->slam_hscr_cap = 0;
-      HIPCHK(dalloc(&c->slam_hscr, hs + 64));
-      c->slam_hscr_cap = hs + 64;
-    }
-  }
+  HIPCHK(c->Hd.reserve(need, 64));
+  HIPCHK(c->resd.reserve((size_t)m_total, 64));
+  HIPCHK(c->slam_res.reserve(lres_bytes, 4096));
+  if (!h_in_lds) HIPCHK(c->slam_hscr.reserve((size_t)L * rows_max * cols_max, 64));
   HIPCHK(hipMemcpyAsync(d, h, stage_bytes, hipMemcpyHostToDevice, s));
   ovp::SlamParams sp;
   memset(&sp, 0, sizeof(sp));
@@ -276,8 +236,7 @@ static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam
   sp.fp.n_feats = L;
   sp.fp.max_meas = M;
   sp.fp.do_fej = o->do_fej;
-  sp.fp.calmask = calmask;
-  for (int k = 0; k < 14; ++k) sp.fp.calcol[k] = calcol[k];
+  cc.fill(sp.fp);
   sp.fp.white_px = 1.0 / o->sigma_px;
   sp.fp.chi2_mult = o->chi2_multiplier;
   sp.fp.chi2_table = c->chi2_table;
@@ -317,14 +276,14 @@ static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam
   double* dM = (double*)((char*)(dres + res_doubles) + lres_bytes);
   double* dLi = dM + (size_t)n * m_total;
   double* dy = dLi + (size_t)m_total * m_total;
-  const bool sform_fits = (size_t)(dy + m_total + 8 - c->smallbuf) <= c->small_cap;
+  const bool sform_fits = (size_t)(dy + m_total + 8 - c->smallbuf) <= c->smallbuf.capacity();
   if (sform && sform_fits) {
     sp.chi2 = dres + res_doubles;
-    sp.status = (unsigned char*)(dres + res_doubles) + al(sizeof(double) * L);
+    sp.status = (unsigned char*)(dres + res_doubles) + o_status;
     sp.Mall = dM;
   } else {
     sp.chi2 = (double*)c->slam_res;
-    sp.status = (unsigned char*)c->slam_res + al(sizeof(double) * L);
+    sp.status = (unsigned char*)c->slam_res + o_status;
   }
   if (gen) {
     ovp::SlamGenParams gp;
@@ -332,12 +291,7 @@ static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam
     gp.sp = sp;
     gp.cam_idx = (const int*)(d + o_cam);
     gp.cam_mask = (const int*)(d + o_cm);
-    gp.cam_cal = c->gen_cal;
-    for (int k = 0; k < OVP_MAX_CAMERAS; ++k) {
-      gp.cam_fisheye[k] = c->gen_fisheye[k];
-      gp.cam_calib_id[k] = c->gen_calib_id[k];
-      gp.cam_intr_id[k] = c->gen_intr_id[k];
-    }
+    cc.fill_cameras_and_columns(gp);
     HIPCHK(ovp_launch_slam_gate_gen(&gp, L, ovp_slam_gate_lds(rows_max, cols_max, h_in_lds), s));
   } else {
     HIPCHK(ovp_launch_slam_gate(&sp, L, ovp_slam_gate_lds(rows_max, cols_max, h_in_lds), s));
@@ -348,11 +302,11 @@ static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam
   char* hl = hres + res_doubles * sizeof(double);  // [chi2 L | status L]
   auto finish_landmarks = [&]() {
     if (chi2_host) memcpy(chi2_host, hl, sizeof(double) * L);
-    if (status_host) memcpy(status_host, hl + al(sizeof(double) * L), L);
+    if (status_host) memcpy(status_host, hl + o_status, L);
     if (info) {
       info->n_cols = gcols;
       for (int l = 0; l < L; ++l) {
-        const unsigned char st = ((unsigned char*)(hl + al(sizeof(double) * L)))[l];
+        const unsigned char st = ((unsigned char*)(hl + o_status))[l];
         if (!st) continue;
         info->n_accepted++;
         const int rows_l = (l + 1 < L ? row0[l + 1] : m_total) - row0[l];
@@ -376,15 +330,13 @@ static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam
       info->neg_diag = hres_d[2] != 0.0;
     }
     if (!(hres_d[1] > 0.5)) return OVP_E_NOTSPD;  // S = H P H^T + I lost definiteness: P is not a covariance; nothing was written
-    double* t = c->P;
-    c->P = c->P_tmp;
-    c->P_tmp = t;
+    c->P.swap(c->P_tmp);
     if (dx_host) memcpy(dx_host, hres_d + 4, sizeof(double) * n);
     return hres_d[2] != 0.0 ? OVP_E_NEGDIAG : 0;
   }
   // information form: A = H^T H, b = H^T r on the call's columns, scattered to the state
-  if (!c->Acc) HIPCHK(dalloc(&c->Acc, (size_t)c->n_max * c->n_max));
-  if (!c->bcc) HIPCHK(dalloc(&c->bcc, (size_t)c->n_max));
+  HIPCHK(c->Acc.alloc((size_t)c->n_max * c->n_max));
+  HIPCHK(c->bcc.alloc((size_t)c->n_max));
   HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 4, s));
   HIPCHK(ovp_launch_gemm(0, 1, gcols, gcols, m_total, c->Hd, m_total, c->Hd, m_total, c->Acc, gcols, 0, s));
   HIPCHK(ovp_launch_gemm(0, 0, gcols, 1, m_total, c->Hd, m_total, c->resd, 1, c->bcc, 1, 0, s));
@@ -454,19 +406,9 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
   if (M < 2 || (!gen && M > OVP_MAX_MEAS) || !b_uv || !b_clone_idx || !b_n_meas || !b_p) return OVP_E_ARG;
   if (dx_host && dx_stride < n0 + 3 * L) return OVP_E_ARG;
   if (n0 + 3 * L > c->n_max) return OVP_E_CAPACITY;
-  const unsigned calmask = (o->do_calib_camera_pose ? 0x3Fu : 0u) | (o->do_calib_camera_intrinsics ? (0xFFu << 6) : 0u);
-  const int ncal = __builtin_popcount(calmask);
-  int calcol[14];
-  for (int k = 0; k < 14; ++k) {
-    calcol[k] = (k < 6) ? c->calib_id + k : c->intr_id + (k - 6);
-    if (!((calmask >> k) & 1)) calcol[k] = 0;
-    else if (calcol[k] < 0 || calcol[k] >= n0) return OVP_E_ARG;
-  }
-  auto gcal = [&](int cam, int k) { return k < 6 ? c->gen_calib_id[cam] + k : c->gen_intr_id[cam] + (k - 6); };
-  if (gen)
-    for (int cam = 0; cam < c->gen_ncams; ++cam)
-      for (int k = 0; k < 14; ++k)
-        if (((calmask >> k) & 1) && (gcal(cam, k) < 0 || gcal(cam, k) >= n0)) return OVP_E_ARG;
+  const CalCols cal(c, o);
+  if (cal.check(n0, false) || (gen && cal.check(n0, true))) return OVP_E_ARG;
+  const int ncal = cal.ncal;
   const int C = (int)c->h_clone_id.size();
   // the planes of the call: every argument checked before anything is enqueued
   const int n_pl = with_planes && pl ? pl->n_planes : 0;
@@ -502,7 +444,7 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
       for (int a = 0; a < m; ++a)
         for (int k = 0; k < 6; ++k) ids.push_back(c->h_clone_id[b_clone_idx[(size_t)l * M + a]] + k);
       for (int k = 0; k < 14; ++k)
-        if ((calmask >> k) & 1) ids.push_back(calcol[k]);
+        if (cal.on(k)) ids.push_back(cal.col[k]);
     } else {
       if (m > OVP_MAX_MEAS_DEV) return OVP_E_CAPACITY;  // (the rows kernel stages at most this many observations)
       std::vector<int>& oc = cand_ocol[l];
@@ -527,7 +469,7 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
         if ((camm >> cam) & 1) {
           cc[cam] = (int)ids.size();
           for (int k = 0; k < 14; ++k)
-            if ((calmask >> k) & 1) ids.push_back(gcal(cam, k));
+            if (cal.on(k)) ids.push_back(cal.col_of(cam, k));
         }
     }
     const int cols = (int)ids.size(), rup = 2 * m - 3;
@@ -561,20 +503,14 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
   }
   const int NA = (int)att.size();
   hipStream_t s = c->stream;
-  auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
   // staging: the candidates as a feature batch + their column lists
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o0 = off;
-    off = al(off + bytes);
-    return o0;
-  };
-  const size_t o_p = take(sizeof(double) * 3 * L), o_uv = take(sizeof(float) * 2 * (size_t)L * M), o_ci = take(sizeof(int) * (size_t)L * M),
-               o_nm = take(sizeof(int) * L), o_id = take(sizeof(int) * (size_t)NA * cols_max);
-  const size_t o_cam = take(gen ? sizeof(int) * (size_t)L * M : 0);  // (general only)
+  StageLayout lay;
+  const size_t o_p = lay.take(sizeof(double) * 3 * L), o_uv = lay.take(sizeof(float) * 2 * (size_t)L * M), o_ci = lay.take(sizeof(int) * (size_t)L * M),
+               o_nm = lay.take(sizeof(int) * L), o_id = lay.take(sizeof(int) * (size_t)NA * cols_max);
+  const size_t o_cam = lay.take(gen ? sizeof(int) * (size_t)L * M : 0);  // (general only)
   // (with planes only) the fallback's linearisation points and the plane table
-  const size_t o_p2 = take(with_planes ? sizeof(double) * 3 * L : 0), o_pt = take(sizeof(double) * OVP_DINIT_PLTAB * (size_t)n_pl);
-  const size_t stage_bytes = off;
+  const size_t o_p2 = lay.take(with_planes ? sizeof(double) * 3 * L : 0), o_pt = lay.take(sizeof(double) * OVP_DINIT_PLTAB * (size_t)n_pl);
+  const size_t stage_bytes = lay.bytes();
   const size_t res_doubles = 4 + (size_t)c->n_max + 8;
   int rc = plane2_buffers(c, stage_bytes, sizeof(double) * res_doubles * NA + 64);
   if (rc) return rc;
@@ -608,13 +544,7 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
   const size_t n_end = (size_t)n0 + 3 * L;
   const size_t need = res_doubles * NA + (size_t)cols_max * rows_max + n_end * rows_max + (size_t)rows_max * rows_max + rows_max + 32 +
                       rows_max + 64;
-  if (need > c->dinit_cap) {
-    if (c->dinit_buf) hipFree(c->dinit_buf);
-    c->dinit_buf = nullptr;
-    c->dinit_cap = 0;
-    HIPCHK(dalloc(&c->dinit_buf, need + 1024));
-    c->dinit_cap = need + 1024;
-  }
+  HIPCHK(c->dinit_buf.reserve(need, 1024));
   double* dres0 = c->dinit_buf;
   double* dHt = dres0 + res_doubles * NA;
   double* dM = dHt + (size_t)cols_max * rows_max;
@@ -634,8 +564,7 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
   dp.fp.n_feats = L;
   dp.fp.max_meas = M;
   dp.fp.do_fej = o->do_fej;
-  dp.fp.calmask = calmask;
-  for (int k = 0; k < 14; ++k) dp.fp.calcol[k] = calcol[k];
+  cal.fill(dp.fp);
   dp.fp.white_px = 1.0 / o->sigma_px;
   dp.fp.ldp = ld;
   dp.n_max = c->n_max;
@@ -649,13 +578,8 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
   dp.resid = dresid;
   ovp::DinitGenParams gp;  // (general only)
   memset(&gp, 0, sizeof(gp));
-  gp.cam_cal = c->gen_cal;
+  cal.fill_cameras_and_columns(gp);
   gp.n_cams = c->gen_ncams;
-  for (int k = 0; k < OVP_MAX_CAMERAS; ++k) {
-    gp.cam_fisheye[k] = c->gen_fisheye[k];
-    gp.cam_calib_id[k] = c->gen_calib_id[k];
-    gp.cam_intr_id[k] = c->gen_intr_id[k];
-  }
   gp.cam_idx = (const int*)(d + o_cam);
   ovp::DinitPlaneParams pp;  // (with planes only)
   memset(&pp, 0, sizeof(pp));

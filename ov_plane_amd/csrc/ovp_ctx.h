@@ -19,8 +19,10 @@
 
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <vector>
 
+#include "ovp_buf.h"
 #include "ovp_kernels.h"
 #include "k_chol2.h"
 #include "k_plane2.h"
@@ -139,6 +141,18 @@ static const int OVP_TILECHOL_NMAX = 288;  // register-resident factorization li
 
 static inline int round_up(int v, int m) { return ((v + m - 1) / m) * m; }
 
+// Blocks of one staging buffer, each starting on a 64-byte line: take(bytes) returns the offset of the next block, bytes() the total.
+struct StageLayout {
+  size_t o = 0;
+  static size_t al(size_t v) { return (v + 63) & ~(size_t)63; }
+  size_t take(size_t bytes) {
+    const size_t at = o;
+    o = al(o + bytes);
+    return at;
+  }
+  size_t bytes() const { return o; }
+};
+
 // ------------------------------------------------------------------------------------------------
 struct ovp_ctx {
   int device = 0;
@@ -148,33 +162,34 @@ struct ovp_ctx {
   hipEvent_t ev_t[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int n_max = 0, c_max = 0, f_max = 0;
   int n = 0, ld = 0;  // current covariance size, leading dimension of every n x n buffer
-  double *P = nullptr, *P_tmp = nullptr;
-  // state tables
+  // Memory: every buffer the context owns is a DevBuf / PinnedBuf (ovp_buf.h) and goes with the context; a raw pointer below is a
+  // view into one of them and says into which.
+  DevBuf<double> P, P_tmp;
+  // state tables: views into state_block
   double *clone_R = nullptr, *clone_p = nullptr, *clone_R_fej = nullptr, *clone_p_fej = nullptr;
   int* clone_id = nullptr;
   double* cal = nullptr;  // [20] camera extrinsics / intrinsics values
   ovp::ColMap* colmap = nullptr;
-  double* chi2_table = nullptr;
+  DevBuf<double> chi2_table;
   ovp::FeatParams fp;
   bool have_state = false, have_cov = false, have_batch = false;
-  // feature batch
+  // feature batch: views into batch_block
   float* uv = nullptr;
   int *clone_idx = nullptr, *n_meas = nullptr;
   double* p_FinG = nullptr;
   int n_feats = 0, max_meas = 0;
   // work buffers
-  double *G = nullptr, *rec = nullptr, *chi2 = nullptr, *Bscr = nullptr;
+  DevBuf<double> G, rec, Bscr;
+  double* chi2 = nullptr;           // views into res_block: flags, dx, chi2, accept
   unsigned char* accept = nullptr;
-  float* uvn = nullptr;            // normalised measurements for ovp_triangulate (allocated on first use)
-  unsigned char* tri_ok = nullptr;
   int ldg = 0;
-  double *gramS = nullptr, *gramR = nullptr, *part = nullptr, *Dinv = nullptr, *Ltp = nullptr;
+  DevBuf<double> gramS, gramR, part, Dinv, Ltp;
   int n_chunks = 0, rows_per_chunk = 0, n_split = 0;
-  double* Ab = nullptr;  // (n_max+1) x ld
-  double *L = nullptr, *W1 = nullptr, *T = nullptr, *Lt = nullptr, *Y = nullptr;
+  DevBuf<double> Ab;  // (n_max+1) x ld
+  DevBuf<double> L, W1, T, Lt, Y;
   double* dx = nullptr;
   int* flags = nullptr;  // [0] not spd, [1] neg diag
-  double *Hd = nullptr, *Acc = nullptr, *bcc = nullptr, *resd = nullptr;  // dense-H path
+  DevBuf<double> Hd, Acc, bcc, resd;  // dense-H path
   // ovp_msckf_dense_blocks: the information pair of the accepted dense blocks over the union of their columns, waiting for the
   // point update of the same frame (added to Ab behind K2); empty = none
   std::vector<int> dense_cols;
@@ -185,96 +200,87 @@ struct ovp_ctx {
   int gen_calib_id[OVP_MAX_CAMERAS] = {-1, -1, -1, -1}, gen_intr_id[OVP_MAX_CAMERAS] = {-1, -1, -1, -1};
   int gen_fisheye[OVP_MAX_CAMERAS] = {0, 0, 0, 0};
   double gen_cal_h[OVP_MAX_CAMERAS * 20] = {};
-  double* gen_cal = nullptr;
-  void* gen_buf = nullptr;
-  size_t gen_cap = 0;
-  void* slam_res = nullptr;        // ovp_slam_update: per-landmark [chi2 | status]
-  double* slam_hscr = nullptr;     // ... blocks that do not fit LDS
-  size_t slam_res_cap = 0, slam_hscr_cap = 0;
-  double* dinit_buf = nullptr;     // ovp_slam_delayed_init: result blocks + shared scratch of the candidate loop
-  size_t dinit_cap = 0;
+  DevBuf<double> gen_cal;
+  DevBuf<void> gen_buf;
+  DevBuf<void> slam_res;           // ovp_slam_update: per-landmark [chi2 | status]
+  DevBuf<double> slam_hscr;        // ... blocks that do not fit LDS
+  DevBuf<double> dinit_buf;        // ovp_slam_delayed_init: result blocks + shared scratch of the candidate loop
   size_t dinit_pltab_off = 0;      // ovp_slam_delayed_init_planes: the plane table of the last call inside pl_dstage (debug read)
   int dinit_nplanes = 0;
-  size_t Hd_cap = 0, res_cap = 0;
   int calib_id = -1, intr_id = -1;
-  long long* dbg_cycles = nullptr;
+  DevBuf<long long> dbg_cycles;
   // plane path
   std::vector<int> h_n_meas, h_clone_idx;  // host copies of the uploaded batch (plane grouping is host logic)
-  int *pl_featlist = nullptr, *pl_sid = nullptr;
-  double *pl_cp = nullptr, *pl_cp_fej = nullptr, *pl_cst = nullptr, *pl_cstsum = nullptr, *pl_E = nullptr;
-  double *pl_An = nullptr, *pl_bn = nullptr, *pl_Lr = nullptr, *pl_Dinv2 = nullptr, *pl_scal = nullptr;
-  double *pl_res = nullptr, *pl_dx = nullptr;
-  int pl_cap = 0;
+  DevBuf<int> pl_featlist, pl_sid;  // (pl_sid: its capacity is the plane capacity of the per-plane tables below)
+  DevBuf<double> pl_cp, pl_cp_fej, pl_cst, pl_cstsum, pl_E;
+  DevBuf<double> pl_An, pl_bn, pl_Lr, pl_Dinv2, pl_scal;
+  DevBuf<double> pl_res, pl_dx;
   // second-generation plane loop (k_plane2.hip / k_chol2.hip)
-  double *pl_Tbuf = nullptr, *pl_crow = nullptr, *pl_dxlast = nullptr;
-  int* pl_cur = nullptr;
-  unsigned* pl_range_done = nullptr;
+  DevBuf<double> pl_Tbuf, pl_crow, pl_dxlast;
+  DevBuf<int> pl_cur;
+  DevBuf<unsigned> pl_range_done;
   unsigned pl_seq = 0;
   int range_lo = -1, range_hi = -1;   // ovp_batch_set_range (-1, -1 = whole batch)
-  unsigned char* pl_used = nullptr;   // [f_max] features consumed by accepted planes (device)
+  DevBuf<unsigned char> pl_used;      // [f_max] features consumed by accepted planes (device)
   std::vector<unsigned char> h_pl_used;  // host copy of it behind the last plane loop (ovp_msckf_update_sharded splits the leftovers)
-  int* h_slot = nullptr;              // [f_max] host-mapped: row block of a feature in the compacted rec / G of a point update (-1: none)
-  int* d_slot = nullptr;              // its device address
+  PinnedBuf<int> h_slot{true};        // [f_max] host-mapped: row block of a feature in the compacted rec / G of a point update (-1: none)
   bool pl_used_valid = false;         // pl_used refers to the uploaded batch
   // plane loop on a sub-state (n above the tile factorization's limit): accumulated pair, u rows, remapped id tables
-  void *io_h = nullptr, *io_d = nullptr;         // ovp_io_arena: pinned host block + device block of the small entry points
-  size_t io_cap = 0;
-  double *pl_xbuf = nullptr, *pl_xy = nullptr;   // split plane solve: exported panels, [xzz(2) | y blocks]
-  unsigned* pl_xflag = nullptr;                  // [32 step flags | 2 sync words]
-  double *pl_Asum = nullptr, *pl_U = nullptr;
-  int pl_U_cap = 0;
-  void *pl_sub_tab = nullptr, *pl_sub_htab = nullptr;  // [ids | inverse | clone ids | column map] of the loop's column order
+  PinnedBuf<void> io_h;                          // ovp_io_arena: pinned host block + device block of the small entry points
+  DevBuf<void> io_d;
+  DevBuf<double> pl_xbuf, pl_xy;                 // split plane solve: exported panels, [xzz(2) | y blocks]
+  DevBuf<unsigned> pl_xflag;                     // [32 step flags | 2 sync words]
+  DevBuf<double> pl_Asum, pl_U;
+  DevBuf<void> pl_sub_tab;                       // [ids | inverse | clone ids | column map] of the loop's column order
+  PinnedBuf<void> pl_sub_htab;
   // (what tells the plane loop's routes apart is an argument of the loop, PlaneLoopView in ovp_api_plane.hip, not context state)
-  void* pl_gen_dev = nullptr;              // device: [marks | projected rows] of one plane's general features of the running loop
-  size_t pl_gen_cap = 0;
+  DevBuf<void> pl_gen_dev;                 // device: [marks | projected rows] of one plane's general features of the running loop
   // A factor of the RESIDENT covariance left behind by the plane loop (P = V^T V, Lkeep = V^T in the state's column order): the point
   // update that follows needs some M with M M^T = P, not the Cholesky factor - chol(P) (the longer branch of the fused feature
   // launch at N = 240) is skipped.  Cleared by everything that writes P.
-  double* Lkeep = nullptr;
+  DevBuf<double> Lkeep;
   bool have_factor = false, use_kept_factor = false;
   double clone_jitter = 0.0;  // ovp_cov_clone_jitter: relative inflation of a cloned block's diagonal (0 = exact copy, the reference)
-  double* boost_vec = nullptr;  // [n_max] k_gather_block_boost: the plane loop's diagonal boost by STATE column (zero where none)
+  DevBuf<double> boost_vec;  // [n_max] k_gather_block_boost: the plane loop's diagonal boost by STATE column (zero where none)
   bool kept_boost = false;  // Lkeep is a factor of P + diag(boost_vec): the point update on it takes the amounts off at its end
-  double* boost = nullptr;   // CholJob::boost: the amounts the reversed-order chol(P) added to the diagonal in front of the batch's columns
+  DevBuf<double> boost;   // CholJob::boost: the amounts the reversed-order chol(P) added to the diagonal in front of the batch's columns
   int point_boost_n = 0;
   int point_nl = 0;  // > 0: chol(P) of the running point update was taken in reversed index order (CholJob::flip) and the update's
                      // T = I + L^T A L is the identity outside its leading point_nl columns
   hipEvent_t ev_subtab = nullptr;     // behind the upload of pl_sub_htab (the pinned block is rewritten by the next call)
-  void *pl_hstage = nullptr, *pl_dstage = nullptr;  // pinned host / device staging of the per-call tables
-  size_t pl_stage_cap = 0;
-  void* pl_hres = nullptr;            // pinned host copy of the plane results
-  void* pl_hres_dev = nullptr;        // ... its device address (mapped: the plane loop publishes its results into it from a kernel)
+  PinnedBuf<void> pl_hstage;          // pinned host / device staging of the per-call tables
+  DevBuf<void> pl_dstage;
+  PinnedBuf<void> pl_hres{true};      // pinned host copy of the plane results (mapped: the plane loop publishes into it from a kernel)
   unsigned pl_pub_seq = 0;            // sequence number of the plane loop's last publication
-  size_t pl_hres_cap = 0;
   // one device block + one pinned staging block each for the pose tables and for the feature batch (a single copy per upload)
-  void *state_block = nullptr, *h_state_stage = nullptr, *batch_block = nullptr, *h_batch_stage = nullptr;
-  size_t state_bytes = 0, batch_cap = 0;
+  DevBuf<void> state_block, batch_block;
+  PinnedBuf<void> h_state_stage, h_batch_stage;
+  size_t state_bytes = 0;
   size_t so_R = 0, so_Rf = 0, so_p = 0, so_pf = 0, so_cal = 0, so_id = 0, so_cm = 0;
   hipEvent_t ev_state = nullptr, ev_batch = nullptr;
   int pl_ktimer = 0;  // 1 = events around every k_chol2 launch and around the loop, 2 = around the loop only
   std::vector<hipEvent_t> pl_ev, pl_ev_loop;
   double pl_ktime_ms = 0.0;
   int pl_klaunches = 0;
-  int* idbuf = nullptr;      // scratch ints (ids)
-  double* smallbuf = nullptr;  // scratch doubles (Phi, Q, CPT, PCP, marginal)
-  size_t small_cap = 0;
+  DevBuf<int> idbuf;         // scratch ints (ids)
+  DevBuf<double> smallbuf;   // scratch doubles (Phi, Q, CPT, PCP, marginal)
   // sub-state update (n above the tile factorization's limit): involved state columns and six ns x ns scratch matrices
-  int* sub_ids = nullptr;
+  DevBuf<int> sub_ids;
   int sub_ns = 0;
   std::vector<int> h_clone_id;  // host copy of the clone columns (ovp_state_upload)
-  double* sub_buf = nullptr;
-  // pinned host staging
+  DevBuf<double> sub_buf;
+  // pinned host staging: views into h_res_block
   double *h_dx = nullptr, *h_chi2 = nullptr;
   unsigned char* h_accept = nullptr;
   int* h_flags = nullptr;
-  void *res_block = nullptr, *h_res_block = nullptr;  // [flags | dx | chi2 | accept], device and pinned host
-  void* h_res_block_dev = nullptr;                    // device address of the pinned block
-  volatile unsigned* h_seq = nullptr;                 // sequence word behind it (written last by k_publish_results)
+  DevBuf<void> res_block;                             // [flags | dx | chi2 | accept]
+  PinnedBuf<void> h_res_block{true};                  // ... its pinned mirror (mapped)
+  volatile unsigned* h_seq = nullptr;                 // sequence word behind it (written last by k_publish_results), view into h_res_block
   unsigned prop_seq = 0;                              // ovp_cov_propagate's own sequence (words [4], [5] behind h_seq: seq, verdict)
   unsigned seq = 0, pub_seq = 0;
   bool pub_pending = false;      // the running update publishes its results itself (k_dx_rows)
   bool need_join = false;     // chol(P) / K2 of the current update finish on stream2 (ev_join) rather than on the main stream
-  unsigned* ticket = nullptr;    // block counter of the publishing kernel
+  DevBuf<unsigned> ticket;       // block counter of the publishing kernel
   std::vector<int> h_nmeas;                           // host copy of n_meas of the current batch (row count of `info`)
   bool h_nmeas_valid = false;
   size_t res_bytes = 0;
@@ -289,6 +295,58 @@ struct ovp_ctx {
   // host-side clock of the two update entry points, accumulated (ovp_host_timing): plane loop [entry -> first launch | entry -> last
   // launch enqueued | wait for the device | calls], point update [enqueue | wait | calls]
   double host_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+  ovp_ctx() = default;
+  ovp_ctx(const ovp_ctx&) = delete;
+  ovp_ctx& operator=(const ovp_ctx&) = delete;
+  ~ovp_ctx() {  // the events and the streams; the buffers free themselves behind this
+    for (hipEvent_t e : {ev_fork, ev_join, ev_t[0], ev_t[1], ev_t[2], ev_t[3], ev_t[4], ev_t[5], ev_k0, ev_k1, ev_state, ev_batch, ev_subtab})
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : pl_ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : pl_ev_loop) (void)hipEventDestroy(e);
+    if (stream2) (void)hipStreamDestroy(stream2);
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+// The calibration columns an update estimates (ovp_update_opts): bit k of `mask` = column k of a camera's [extrinsics 6 |
+// intrinsics 8]; col[] = camera 0's state columns (ovp_state_upload; 0 where not estimated), col_of = those of an uploaded camera.
+struct CalCols {
+  const ovp_ctx* c;
+  unsigned mask;
+  int ncal, col[14];
+  CalCols(const ovp_ctx* ctx, const ovp_update_opts* o)
+      : c(ctx), mask((o->do_calib_camera_pose ? 0x3Fu : 0u) | (o->do_calib_camera_intrinsics ? (0xFFu << 6) : 0u)),
+        ncal(__builtin_popcount(mask)) {
+    for (int k = 0; k < 14; ++k) col[k] = on(k) ? (k < 6 ? c->calib_id + k : c->intr_id + (k - 6)) : 0;
+  }
+  bool on(int k) const { return (mask >> k) & 1u; }
+  int col_of(int cam, int k) const { return k < 6 ? c->gen_calib_id[cam] + k : c->gen_intr_id[cam] + (k - 6); }
+  // every estimated column lies in a state of n columns: camera 0's, or (general) those of every uploaded camera
+  int check(int n, bool general) const {
+    for (int cam = 0; cam < (general ? c->gen_ncams : 1); ++cam)
+      for (int k = 0; k < 14; ++k) {
+        const int id = general ? col_of(cam, k) : col[k];
+        if (on(k) && (id < 0 || id >= n)) return OVP_E_ARG;
+      }
+    return 0;
+  }
+  void fill(ovp::FeatParams& fp) const {
+    fp.calmask = mask;
+    for (int k = 0; k < 14; ++k) fp.calcol[k] = col[k];
+  }
+  // the uploaded cameras' tables into a general parameter struct (SlamGenParams, DinitGenParams, GenParams: and where their
+  // calibration columns start)
+  template <class GP>
+  void fill_cameras(GP& gp) const {
+    gp.cam_cal = c->gen_cal;
+    for (int k = 0; k < OVP_MAX_CAMERAS; ++k) gp.cam_fisheye[k] = c->gen_fisheye[k];
+  }
+  template <class GP>
+  void fill_cameras_and_columns(GP& gp) const {
+    fill_cameras(gp);
+    for (int k = 0; k < OVP_MAX_CAMERAS; ++k) gp.cam_calib_id[k] = c->gen_calib_id[k], gp.cam_intr_id[k] = c->gen_intr_id[k];
+  }
 };
 
 // Everything that writes the covariance calls this: the factor the plane loop left (Lkeep) and the bookkeeping of a staged point
@@ -307,11 +365,6 @@ static inline double host_now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-
-template <class T>
-static hipError_t dalloc(T** p, size_t count) {
-  return hipMalloc((void**)p, count * sizeof(T));
-}
 
 // Wait for the sequence number a kernel on stream s writes into mapped pinned memory behind its payload.  Error path: after two
 // seconds one stream synchronisation surfaces a fault instead of spinning forever, OVP_E_STATE when the word still is not there.
