@@ -613,6 +613,73 @@ typedef struct {
 int ovp_plane_fit_refine(ovp_ctx *ctx, const ovp_general_batch *batch, const float *uv_norm, const ovp_planefront_in *in,
                          const ovp_planefront_out *out);
 
+/* ---- plane detection from tracked features ----------------------------------------------------- */
+/* TrackPlaneOptions (track_plane/TrackPlaneOptions.h:44-80), same names and defaults (ovp_trackplane_defaults). */
+typedef struct {
+  int max_tri_side_px;       /* 200  */
+  int max_norm_count;        /* 5, at most OVP_DET_MAX_NORMS */
+  double max_norm_avg_max;   /* 25.0 */
+  double max_norm_avg_var;   /* 25.0 */
+  double max_norm_deg;       /* 25.0 */
+  double max_dist_between_z; /* 0.10 */
+  int max_pairwise_px;       /* 100  */
+  int min_norms;             /* 3    */
+  int check_old_feats;       /* 1    */
+  int filter_num_feat;       /* 4, in 2 .. OVP_DET_MAX_FILTER_K */
+  double filter_z_thresh;    /* 1.2  */
+  int feat_init_min_obs;     /* 4    */
+  double min_dist;           /* 0.10 */
+  double max_dist;           /* 60   */
+  double max_cond_number;    /* 8000 */
+} ovp_trackplane_opts;
+#define OVP_DET_MAX_POINTS 1024  /* tracked points of one frame (and so active features of one plane) */
+#define OVP_DET_MAX_NORMS 16     /* normals kept per feature */
+#define OVP_DET_MAX_FILTER_K 16  /* neighbours averaged by the spatial filter */
+void ovp_trackplane_defaults(ovp_trackplane_opts *opts);
+/* The per-feature history of TrackPlane (hist_feat_linsys_A / _b / _count, hist_feat_inG, hist_feat_norms_inG: track_plane/
+ * TrackPlane.h) as a device table of feature slots, with the feature id -> slot map, hist_feat_to_plane, hist_plane_to_oldplanes
+ * and the plane id counter on the host.  One detector per context; it goes with ovp_ctx_destroy.  _reset forgets every feature and plane. */
+int ovp_plane_detector_create(ovp_ctx *ctx, const ovp_trackplane_opts *opts);
+int ovp_plane_detector_destroy(ovp_ctx *ctx);
+int ovp_plane_detector_reset(ovp_ctx *ctx);
+/* First call of a frame: TrackPlane::perform_plane_detection_monocular, track_plane/TrackPlane.cpp:608-708 (remove_feats, the
+ * linear triangulation systems and their gates).  ids [n] distinct feature ids, uv [2n] pixel positions (f32), uv_norm [2n] the
+ * undistorted normalised coordinates of the same points (f64 here; the reference's undistort_cv returns a cv::Point2f, so a caller
+ * who wants the reference's numbers rounds them to f32 first), R_GtoC [9] row-major and p_CinG [3] the newest clone's camera pose.
+ * Outputs (either may be NULL): has_est [n]: bit 0 = the feature has a 3-D estimate, bit 1 = this frame's solution passed the gates (the vertices of the frame's triangulation are these
+ * points, in this order), p_FinG [3n].  n > OVP_DET_MAX_POINTS: OVP_E_CAPACITY and nothing is touched; n = 0 returns at once, as
+ * the reference does. */
+int ovp_plane_detect_triangulate(ovp_ctx *ctx, int n, const int64_t *ids, const float *uv, const double *uv_norm, const double *R_GtoC,
+                                 const double *p_CinG, uint8_t *has_est, double *p_FinG);
+/* Second call of a frame: TrackPlane.cpp:728-1095 (triangle normals, per-feature normal history and avg_norm, pairwise matching,
+ * greedy merge, spatial filter, pruning).  tris [3*n_tris] index the vertices of the preceding ovp_plane_detect_triangulate;
+ * tris = NULL: the library triangulates them itself (ovp_delaunay). */
+int ovp_plane_detect_planes(ovp_ctx *ctx, int n_tris, const int32_t *tris);
+/* TrackPlane::get_feature2plane (track_plane/TrackPlane.h:140-143): ascending feature id; *n = entries (also when cap is smaller) */
+int ovp_plane_detector_map(ovp_ctx *ctx, int64_t *ids, int64_t *planes, int cap, int *n);
+/* TrackPlane::get_plane2oldplane (track_plane/TrackPlane.h:145-149): the merge history of the planes in the map as (surviving id,
+ * old id) pairs, pairs [2*cap]; *n = pairs (also when cap is smaller).  With the values of ovp_plane_detector_map (the active planes)
+ * this is what StateHelper::merge_planes_and_marginalize takes every frame (core/VioManager.cpp:513-534). */
+int ovp_plane_detector_merges(ovp_ctx *ctx, int64_t *pairs, int cap, int *n);
+/* DIAGNOSTICS / TESTS, not part of a frame (a frame is the two calls above): the spatial filter alone (TrackPlane.cpp:1003-1058)
+ * on planes given as point lists: plane k = p_FinG rows feat_start[k] ..
+ * feat_start[k+1]; mean_dist [n] = mean of the filter_num_feat smallest squared f32 distances to the plane's other points, flagged
+ * [n] = fails the z-test.  A plane of at most filter_num_feat points is left alone (zeros); more than OVP_DET_MAX_POINTS in one
+ * plane: OVP_E_CAPACITY.  Uses the staging of the context's detector (OVP_E_STATE without one), none of its history. */
+int ovp_plane_spatial_filter(ovp_ctx *ctx, int n_planes, const int *feat_start, const double *p_FinG, int filter_num_feat,
+                             double filter_z_thresh, double *mean_dist, uint8_t *flagged);
+/* Delaunay triangulation of n pixel positions (incremental Bowyer-Watson, host arithmetic only - no context): tris [3*cap], each
+ * triangle positively oriented in (x, y), its smallest index first, the list sorted (a point at the position of an earlier one
+ * is left out, a zero-area triangle of a point exactly on a hull edge is dropped); *n_tris = count (OVP_E_CAPACITY above cap;
+ * 2n always suffices).  Stands where the reference calls CDT (TrackPlane.cpp:717-723). */
+int ovp_delaunay(int n, const float *xy, int32_t *tris, int cap, int *n_tris);
+/* tests: what = "feat": out = [count, valid, p_FinG(3), n_norms, avg_norm(3), normals(3*n_norms)] of feature id; "filter": out =
+ * [id, plane, mean of the neighbour distances, z-score flag] per point of every plane the last frame's filter looked at; "timer": id != 0
+ * puts events around the kernels (and a stream synchronisation behind each publication) from the next frame on, "time": GPU
+ * milliseconds of the last timed frame's kernels [triangulate, normals, match, filter] ([3] also behind a timed
+ * ovp_plane_spatial_filter).  Returns the number of doubles (or < 0). */
+long ovp_plane_detector_debug(ovp_ctx *ctx, const char *what, int64_t id, double *out, long cap);
+
 /* ---- diagnostics ---------------------------------------------------------------------------- */
 /* copies an internal device buffer to host for tests: name in {"A","b","L","T","Lt","Y","G","rec","chi2",
  * "gramS","syrk"}; returns the byte count copied (or <0). */

@@ -180,6 +180,17 @@ class PlaneFrontOut(C.Structure):
                 ("poses", C.c_void_p)]
 
 
+class TrackPlaneOpts(C.Structure):
+    """ovp_trackplane_opts: TrackPlaneOptions of the reference, same names (defaults: trackplane_defaults())."""
+    _fields_ = [("max_tri_side_px", C.c_int), ("max_norm_count", C.c_int), ("max_norm_avg_max", C.c_double),
+                ("max_norm_avg_var", C.c_double), ("max_norm_deg", C.c_double), ("max_dist_between_z", C.c_double),
+                ("max_pairwise_px", C.c_int), ("min_norms", C.c_int), ("check_old_feats", C.c_int), ("filter_num_feat", C.c_int),
+                ("filter_z_thresh", C.c_double), ("feat_init_min_obs", C.c_int), ("min_dist", C.c_double), ("max_dist", C.c_double),
+                ("max_cond_number", C.c_double)]
+
+
+OVP_DET_MAX_POINTS, OVP_DET_MAX_NORMS, OVP_DET_MAX_FILTER_K = 1024, 16, 16
+
 EXPORTS = [
     "ovp_ctx_create", "ovp_ctx_destroy", "ovp_sync", "ovp_version", "ovp_error_string", "ovp_cov_upload",
     "ovp_cov_download", "ovp_cov_set_device", "ovp_cov_marginal", "ovp_state_upload", "ovp_batch_upload",
@@ -193,6 +204,8 @@ EXPORTS = [
     "ovp_rccl_gather_decisions", "ovp_msckf_dense_blocks", "ovp_cameras_upload", "ovp_msckf_general_features",
     "ovp_triangulate_general", "ovp_slam_update_general", "ovp_slam_delayed_init_general",
     "ovp_slam_delayed_init_planes", "ovp_msckf_plane_update_general", "ovp_plane_fit_refine",
+    "ovp_trackplane_defaults", "ovp_plane_detector_create", "ovp_plane_detector_destroy", "ovp_plane_detector_reset",
+    "ovp_plane_detect_triangulate", "ovp_plane_detect_planes", "ovp_plane_detector_map", "ovp_delaunay", "ovp_plane_detector_debug", "ovp_plane_spatial_filter", "ovp_plane_detector_merges",
 ]
 
 
@@ -283,6 +296,19 @@ def lib():
                                          C.c_void_p, C.c_void_p]
         L.ovp_plane_fit_refine.argtypes = [C.c_void_p, C.POINTER(GeneralBatch), C.c_void_p, C.POINTER(PlaneFrontIn),
                                            C.POINTER(PlaneFrontOut)]
+        L.ovp_trackplane_defaults.argtypes = [C.POINTER(TrackPlaneOpts)]
+        L.ovp_trackplane_defaults.restype = None
+        L.ovp_plane_detector_create.argtypes = [C.c_void_p, C.POINTER(TrackPlaneOpts)]
+        L.ovp_plane_detector_destroy.argtypes = [C.c_void_p]
+        L.ovp_plane_detector_reset.argtypes = [C.c_void_p]
+        L.ovp_plane_detect_triangulate.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        L.ovp_plane_detect_planes.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.ovp_plane_detector_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.ovp_delaunay.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.ovp_plane_spatial_filter.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
+        L.ovp_plane_detector_merges.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.ovp_plane_detector_debug.restype = C.c_long
+        L.ovp_plane_detector_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_long]
         _LIB = L
     return _LIB
 
@@ -290,6 +316,126 @@ def lib():
 def _chk(code, where):
     if code != 0:
         raise OvpError(code, where)
+
+
+def trackplane_defaults(**over) -> TrackPlaneOpts:
+    """TrackPlaneOptions' defaults (ovp_trackplane_defaults), with the named fields replaced."""
+    o = TrackPlaneOpts()
+    lib().ovp_trackplane_defaults(C.byref(o))
+    for k, v in over.items():
+        if k not in dict(TrackPlaneOpts._fields_):
+            raise KeyError(k)
+        setattr(o, k, v)
+    return o
+
+
+def delaunay(xy):
+    """ovp_delaunay: Delaunay triangles of the pixel positions xy [n, 2] (f32), canonical order; host arithmetic, no GPU."""
+    xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+    cap = max(2 * len(xy), 1)
+    tris = np.zeros((cap, 3), dtype=np.int32)
+    nt = C.c_int(0)
+    _chk(lib().ovp_delaunay(len(xy), xy.ctypes.data, tris.ctypes.data, cap, C.byref(nt)), "ovp_delaunay")
+    return tris[:nt.value].copy()
+
+
+class PlaneDetector:
+    """The plane detector of a context (ovp_plane_detector_*): TrackPlane::perform_plane_detection_monocular on the device.
+    feed() is one frame; feature2plane() the reference's get_feature2plane()."""
+
+    def __init__(self, ctx, opts=None):
+        self.ctx = ctx
+        self.opts = opts if opts is not None else trackplane_defaults()
+        _chk(lib().ovp_plane_detector_create(ctx.handle, C.byref(self.opts)), "ovp_plane_detector_create")
+
+    def close(self):
+        _chk(lib().ovp_plane_detector_destroy(self.ctx.handle), "ovp_plane_detector_destroy")
+
+    def reset(self):
+        _chk(lib().ovp_plane_detector_reset(self.ctx.handle), "ovp_plane_detector_reset")
+
+    def triangulate(self, ids, uv, uv_norm, R_GtoC, p_CinG):
+        """first call of a frame -> (has_est [n] bool, p_FinG [n, 3])"""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        n = len(ids)
+        uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(n, 2)
+        uvn = np.ascontiguousarray(uv_norm, dtype=np.float64).reshape(n, 2)
+        R = np.ascontiguousarray(R_GtoC, dtype=np.float64).reshape(3, 3)
+        p = np.ascontiguousarray(p_CinG, dtype=np.float64).reshape(3)
+        has = np.zeros(n, dtype=np.uint8)
+        pf = np.zeros((n, 3))
+        _chk(lib().ovp_plane_detect_triangulate(self.ctx.handle, n, ids.ctypes.data, uv.ctypes.data, uvn.ctypes.data, R.ctypes.data,
+                                                p.ctypes.data, has.ctypes.data, pf.ctypes.data), "ovp_plane_detect_triangulate")
+        self.accepted = (has & 2) != 0  # this frame's solution passed the gates
+        return (has & 1) != 0, pf
+
+    def planes(self, tris=None):
+        """second call of a frame; tris [nt, 3] over the frame's vertices (None: the library's own Delaunay triangulation)"""
+        if tris is None:
+            _chk(lib().ovp_plane_detect_planes(self.ctx.handle, 0, None), "ovp_plane_detect_planes")
+        else:
+            tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+            _chk(lib().ovp_plane_detect_planes(self.ctx.handle, len(tris), tris.ctypes.data), "ovp_plane_detect_planes")
+
+    def feed(self, ids, uv, uv_norm, R_GtoC, p_CinG):
+        if len(ids) == 0:
+            return self.feature2plane()
+        self.triangulate(ids, uv, uv_norm, R_GtoC, p_CinG)
+        self.planes()
+        return self.feature2plane()
+
+    def feature2plane(self):
+        n = C.c_int(0)
+        _chk(lib().ovp_plane_detector_map(self.ctx.handle, None, None, 0, C.byref(n)), "ovp_plane_detector_map")
+        ids, pl = np.zeros(max(n.value, 1), dtype=np.int64), np.zeros(max(n.value, 1), dtype=np.int64)
+        _chk(lib().ovp_plane_detector_map(self.ctx.handle, ids.ctypes.data, pl.ctypes.data, n.value, C.byref(n)), "ovp_plane_detector_map")
+        return {int(a): int(b) for a, b in zip(ids[:n.value], pl[:n.value])}
+
+    def plane2oldplane(self):
+        """TrackPlane::get_plane2oldplane: {surviving plane id: set of the ids merged into it}"""
+        n = C.c_int(0)
+        _chk(lib().ovp_plane_detector_merges(self.ctx.handle, None, 0, C.byref(n)), "ovp_plane_detector_merges")
+        pairs = np.zeros((max(n.value, 1), 2), dtype=np.int64)
+        _chk(lib().ovp_plane_detector_merges(self.ctx.handle, pairs.ctypes.data, n.value, C.byref(n)), "ovp_plane_detector_merges")
+        out = {}
+        for a, b in pairs[:n.value]:
+            out.setdefault(int(a), set()).add(int(b))
+        return out
+
+    def _debug(self, what, fid, cap):
+        out = np.zeros(cap)
+        k = lib().ovp_plane_detector_debug(self.ctx.handle, what, int(fid), out.ctypes.data, cap)
+        if k < 0:
+            raise OvpError(int(k), "ovp_plane_detector_debug")
+        return out[:k]
+
+    def feature(self, fid):
+        """tests: the history of one feature -> dict(count, valid, p_FinG, avg_norm, normals [k, 3] oldest first)"""
+        o = self._debug(b"feat", fid, 9 + 3 * OVP_DET_MAX_NORMS)
+        return dict(count=int(o[0]), valid=bool(o[1]), p_FinG=o[2:5].copy(), avg_norm=o[6:9].copy(), normals=o[9:].reshape(-1, 3).copy())
+
+    def filter_rows(self):
+        """tests: [feature id, plane id, mean neighbour distance, flagged] per point the last frame's spatial filter looked at"""
+        return self._debug(b"filter", 0, 4 * OVP_DET_MAX_POINTS).reshape(-1, 4)
+
+    def timer(self, on=True):
+        """events around the kernels from the next frame on (diagnostics: adds a stream synchronisation per publication)"""
+        self._debug(b"timer", 1 if on else 0, 1)
+
+    def kernel_ms(self):
+        """GPU milliseconds of the last timed frame's kernels [triangulate, normals, match, filter]"""
+        return self._debug(b"time", 0, 4)
+
+    def spatial_filter(self, planes, filter_num_feat=None, filter_z_thresh=None):
+        """ovp_plane_spatial_filter on a list of [n_k, 3] point arrays -> list of (mean_dist [n_k], flagged [n_k] bool)"""
+        start = np.concatenate([[0], np.cumsum([len(p) for p in planes])]).astype(np.int32)
+        P = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.float64).reshape(-1, 3) for p in planes]))
+        dist, flag = np.zeros(len(P)), np.zeros(len(P), dtype=np.uint8)
+        k = self.opts.filter_num_feat if filter_num_feat is None else filter_num_feat
+        z = self.opts.filter_z_thresh if filter_z_thresh is None else filter_z_thresh
+        _chk(lib().ovp_plane_spatial_filter(self.ctx.handle, len(planes), start.ctypes.data, P.ctypes.data, int(k), float(z),
+                                            dist.ctypes.data, flag.ctypes.data), "ovp_plane_spatial_filter")
+        return [(dist[a:b].copy(), flag[a:b].astype(bool)) for a, b in zip(start[:-1], start[1:])]
 
 
 def rccl_unique_id() -> bytes:

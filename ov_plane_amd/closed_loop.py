@@ -109,11 +109,23 @@ def schedule(frames, C, min_meas=3, max_feats=None):
     return out
 
 
-def run(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, max_feats=None, planes=0, plane_min_feat=6, sigma_c=0.01):
+def run(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, max_feats=None, planes=0, plane_min_feat=6, sigma_c=0.01,
+        detect_planes=False):
     """Simulate, estimate, score.  Returns dict with per-frame truth / estimate / errors and the summary numbers.
     planes: 0 = points only; 1 = the simulator's point-to-plane associations become feat2plane and UpdaterMSCKF uses the
     planar regularities (planes estimated per update, StateOptions::use_plane_constraint_msckf); 2 = UpdaterPlane::init_vio_plane
-    also puts the planes into the state (use_plane_slam_feats)."""
+    also puts the planes into the state (use_plane_slam_feats).
+    detect_planes: the feature -> plane map comes from the device plane detector instead of the simulator's labels.  That is
+    run_session(..., detect_planes=True): the RESULT IS run_session's dict (counts, n_feats, detected_per_frame, ...; no
+    kept_per_frame / final), planes must be 1 or 2 and max_feats must be None (ValueError otherwise)."""
+    if detect_planes:
+        # the detector needs every frame's tracked points, which only the frame-by-frame session hands over
+        if max_feats is not None:
+            raise ValueError("detect_planes runs the frame-by-frame session, which has no max_feats")
+        if not planes:
+            raise ValueError("detect_planes needs planes = 1 or 2: with planes = 0 the map would not be used")
+        return run_session(sim, n_frames=n_frames, C=C, po=po, sigma_px=sigma_px, chi2_mult=chi2_mult, planes=planes,
+                           plane_min_feat=plane_min_feat, sigma_c=sigma_c, detect_planes=True)
     from . import hostlib
     from .sim import log_so3
     from .synth import PROP_OPTS, quat_2_rot
@@ -154,7 +166,8 @@ def run(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, max_feats=
 
 
 def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, planes=0, plane_min_feat=6, sigma_c=0.01,
-                max_slam=0, feat_rep_slam=0, min_meas=3, out_dir=None, zupt=None, track_planes=True, forget_planes_at=None):
+                max_slam=0, feat_rep_slam=0, min_meas=3, out_dir=None, zupt=None, track_planes=True, forget_planes_at=None,
+                detect_planes=False, detect_opts=None, feed_plane_tracks=None):
     """Closed loop through hostlib.Session, frame by frame, with the tracker-side bookkeeping of core/VioManager.cpp:360-506:
     a track is an MSCKF feature once it is lost or reaches back to the clone about to be marginalised; a track that spans the
     whole window (more than max_clone_size measurements) becomes a SLAM landmark while there is room (max_slam), and from then
@@ -165,6 +178,10 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
     track_planes: hand the planes of all live tracks to the session every frame (the tracker's feature -> plane map,
     core/VioManager.cpp:513-534), so that a plane nobody observes any more leaves the state; forget_planes_at = frame index from
     which the tracker reports no plane at all (test hook: every plane of the state must then be marginalised).
+    detect_planes: StateOptions::gpu_plane_detection - the feature -> plane map comes from the device plane detector, fed every
+    frame with all tracked points; the simulator's plane labels are NOT handed to the session (detect_opts: capi.TrackPlaneOpts).
+    feed_plane_tracks (default: detect_planes) hands the tracked points over whether or not the option is on - with it off they
+    are ignored.  The result then also holds detected_per_frame [K, 2] = (features of the step on a detected plane, entries of the map).
     zupt: dict of Session.enable_zupt keywords (or {}) = VioManagerOptions::try_zupt: a frame at which the platform is found
     standing still gets a zero-velocity update instead of a clone (core/VioManager.cpp:311-331) and its measurements are dropped."""
     from . import hostlib
@@ -181,6 +198,8 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
                           sigma_c=sigma_c, max_slam=max_slam, feat_rep_slam=feat_rep_slam, cam_dt=1.0 / sim.params["sim_freq_cam"])
     if zupt is not None:
         ses.enable_zupt(po, **zupt)
+    if detect_planes:
+        ses.enable_plane_detection(detect_opts)
     ses.feed_imu(imu)
     if out_dir is not None:
         import os
@@ -205,6 +224,7 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
     traj, posecov, counts = np.zeros((K, 16)), np.zeros((K, 6, 6)), np.zeros((K, 6), dtype=np.int32)
     n_feats = np.zeros((K, 3), dtype=np.int32)
     zupt_frames = np.zeros(K, dtype=bool)
+    detected = np.zeros((K, 2), dtype=np.int32)
     for k in range(C, len(frames)):
         t_k, seen = frames[k]
         i = k - C
@@ -265,7 +285,19 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
             active = {plane_of[int(f)] for f in live if plane_of[int(f)] > 0}
             if forget_planes_at is not None and i >= forget_planes_at:
                 active, pl = set(), np.zeros(len(fid), dtype=np.int32)
+        if detect_planes or feed_plane_tracks:
+            s_id = np.array(sorted(seen), dtype=np.int64)
+            s_uv = np.array([seen[int(f)] for f in s_id], dtype=np.float32).reshape(-1, 2)
+            sx, sy = radtan_undistort(s_uv[:, 0], s_uv[:, 1], init["intr"])
+            ses.feed_plane_tracks(t_k, s_id + FID_OFFSET, s_uv, np.stack([sx, sy], axis=-1))
+        if detect_planes:
+            pl, active = None, None
         out = ses.step(t_k, uv, uvn, slot, nm, fid + FID_OFFSET, kind, pl, truth, active_planes=active)
+        if detect_planes:
+            info = ses.plane_detection_info()
+            if info["rc"] != 0:
+                raise RuntimeError("plane detection failed with %d" % info["rc"])
+            detected[i] = info["planar"], info["mapped"]
         window = win[1:]
         slam_ids = {i_ - FID_OFFSET for i_ in out["slam_ids"]}
         for f in slam_ids:
@@ -283,5 +315,6 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
         nees_p[i] = dp @ np.linalg.solve(posecov[i][3:6, 3:6], dp)
         nees_o[i] = dth @ np.linalg.solve(posecov[i][0:3, 0:3], dth)
     return dict(times=times, traj=traj, posecov=posecov, counts=counts, n_feats=n_feats, zupt_frames=zupt_frames, e_pos=e_pos,
+                detected_per_frame=detected,
                 e_ori=e_ori, nees_pos=nees_p, nees_ori=nees_o, rmse_pos=float(np.sqrt(np.mean(e_pos**2))),
                 rmse_ori_deg=float(np.degrees(np.sqrt(np.mean(e_ori**2)))))

@@ -75,6 +75,10 @@ struct StateOptions {
   // instead of ending it - off: the first such candidate and everything behind it take the per-candidate host loop.
   // OVP_E_CAPACITY falls back to that loop.  Not in the reference.
   bool gpu_dinit_planes = false;
+  // The feature -> plane map of a session frame comes from the device plane detector (TrackPlane::feed_plane_detection on the
+  // tracks handed over by ovph_session_feed_plane_tracks) in place of the map the caller passes.  In the reference this is
+  // TrackPlaneOptions::track_planes of the front end.
+  bool gpu_plane_detection = false;
   // UpdaterMSCKF::update: on-plane features the device batch cannot carry (another camera, more than OVP_MAX_MEAS views) stay in the
   // plane loop through ovp_msckf_plane_update_general instead of going to the point update without their plane constraint - for
   // planes whose estimate does not come from this frame's fit (in the state, or handed over in _plane_estimates_cp_inG); a frame with
@@ -179,6 +183,7 @@ public:
   // simulation ground truth (state/State.h:120-121), read by UpdaterMSCKF::update when StateOptions::use_groundtruths is set
   std::unordered_map<size_t, std::array<double, 3>> _true_planes;
   std::unordered_map<size_t, std::array<double, 3>> _true_features;
+  ovp_ctx *gpu() const { return _gpu; }  // the device context of the covariance (what TrackPlane's detector is created on)
 
 private:
   friend class StateHelper;

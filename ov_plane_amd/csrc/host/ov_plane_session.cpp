@@ -19,6 +19,7 @@
 
 #include "ov_plane_host.h"
 #include "ov_plane_io.h"
+#include "ov_plane_trackplane.h"
 
 using namespace ov_plane;
 using namespace ov_type;
@@ -33,6 +34,12 @@ struct Session {
   std::unique_ptr<UpdaterZeroVelocity> zupt;              // only with try_zupt (VioManagerOptions::try_zupt)
   std::shared_ptr<ov_core::FeatureDatabase> db;           // raw tracks of the last frames: the disparity test of the detector
   int C = 0, plane_mode = 0;
+  // StateOptions::gpu_plane_detection: the detector and the tracked points of the frame about to be stepped
+  std::unique_ptr<TrackPlane> track;
+  double track_time = -1.0;
+  std::vector<size_t> track_ids;
+  std::vector<float> track_uv, track_uvn;
+  int detect_rc = 0, detect_planar = 0;
   // what a run of the reference leaves behind (ros/ROSVisualizerHelper.cpp:152-302, core/VioManager.cpp:110-118, 911-927)
   std::ofstream of_est, of_std, of_gt, of_timing;
   bool files = false;
@@ -161,6 +168,44 @@ extern "C" int ovph_session_feed_tracks(void *h, double frame_time, int n, const
     if (f.timestamps.empty()) it = all.erase(it);
     else ++it;
   }
+  return 0;
+}
+
+// StateOptions::gpu_plane_detection on: opts = ovp_trackplane_opts (NULL: the defaults).  From then on a frame whose tracked points
+// were handed over by ovph_session_feed_plane_tracks takes its feature -> plane map from the detector, not from `plane` of the step.
+extern "C" int ovph_session_enable_plane_detection(void *h, const ovp_trackplane_opts *opts) {
+  auto *s = static_cast<Session *>(h);
+  ovp_trackplane_opts o;
+  ovp_trackplane_defaults(&o);
+  if (opts) o = *opts;
+  if (!s->state->gpu()) return -31;
+  s->track.reset();
+  s->track = std::make_unique<TrackPlane>(s->state->gpu(), o);
+  if (!s->track->ok()) {
+    s->track.reset();
+    return -31;
+  }
+  s->state->_options.gpu_plane_detection = true;
+  return 0;
+}
+
+// every point tracked into the frame at frame_time (not only the tracks the step uses): ids, pixels, normalised coordinates
+extern "C" int ovph_session_feed_plane_tracks(void *h, double frame_time, int n, const long long *fid, const float *uv,
+                                              const float *uv_norm) {
+  auto *s = static_cast<Session *>(h);
+  if (n < 0 || (n > 0 && (!fid || !uv || !uv_norm))) return -21;
+  s->track_time = frame_time;
+  s->track_ids.assign(fid, fid + n);
+  s->track_uv.assign(uv, uv + 2 * (size_t)n);
+  s->track_uvn.assign(uv_norm, uv_norm + 2 * (size_t)n);
+  return 0;
+}
+
+// [0] return code of the last frame's detection, [1] features of the last step that the detector put on a plane, [2] entries of
+// the detector's map
+extern "C" int ovph_session_plane_detection_info(void *h, int *out3) {
+  auto *s = static_cast<Session *>(h);
+  out3[0] = s->detect_rc, out3[1] = s->detect_planar, out3[2] = s->track ? (int)s->track->get_feature2plane().size() : 0;
   return 0;
 }
 
@@ -299,6 +344,35 @@ extern "C" int ovph_session_step2(void *h, double frame_time, int F, int M, cons
       f_msckf.push_back(ft);
     }
   }
+  bool detected = false;
+  std::map<size_t, std::set<size_t>> detected_merges;
+  if (state->_options.gpu_plane_detection && s->track && s->track_time != frame_time) {
+    // the option is on and no tracked points were handed over for THIS frame: the caller's map is not a substitute
+    s->detect_rc = OVP_E_STATE;
+    s->detect_planar = 0;
+    feat2plane.clear();
+  }
+  if (state->_options.gpu_plane_detection && s->track && s->track_time == frame_time) {
+    // the detector runs on the newest clone (TrackPlane.cpp:612-624) and its map stands in for the caller's
+    const auto &clone = state->_clones_IMU.at(state->_timestamp);
+    const double *Rgi = clone->Rot(), *pig = clone->pos(), *Ric = state->_calib_IMUtoCAM.at(0)->Rot(),
+                 *pic = state->_calib_IMUtoCAM.at(0)->pos();
+    double Rgc[9], pcg[3];
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) Rgc[3 * r + c] = Ric[3 * r] * Rgi[c] + Ric[3 * r + 1] * Rgi[3 + c] + Ric[3 * r + 2] * Rgi[6 + c];
+    for (int c = 0; c < 3; ++c) pcg[c] = pig[c] - (Rgc[c] * pic[0] + Rgc[3 + c] * pic[1] + Rgc[6 + c] * pic[2]);
+    s->track->feed_pose(frame_time, Rgc, pcg);
+    s->detect_rc = s->track->feed_plane_detection(frame_time, s->track_ids, s->track_uv, s->track_uvn);
+    feat2plane.clear();
+    s->detect_planar = 0;
+    if (s->plane_mode) {
+      feat2plane = s->track->get_feature2plane();
+      for (int f = 0; f < F; ++f) s->detect_planar += (int)feat2plane.count((size_t)gfid[f]);
+    }
+    s->track_time = -1.0;
+    detected = s->detect_rc == 0 && s->plane_mode == 2;
+    if (detected) detected_merges = s->track->get_plane2oldplane();
+  }
   // VioManager.cpp:463-485 landmarks that were not tracked into this frame leave the state
   int n_marg = 0;
   for (auto &lm : state->_features_SLAM)
@@ -308,7 +382,10 @@ extern "C" int ovph_session_step2(void *h, double frame_time, int F, int M, cons
     }
   StateHelper::marginalize_slam(state);
   // :513-534 planes the front end merged are fused, planes that are no longer observed leave the state
-  if (n_active >= 0 && s->plane_mode == 2) {
+  if (detected) {
+    // the detector's own bookkeeping: the planes of its map are the active ones, its merge history says which ids were fused
+    StateHelper::merge_planes_and_marginalize(state, feat2plane, detected_merges);
+  } else if (n_active >= 0 && s->plane_mode == 2) {
     std::map<size_t, size_t> f2p_active = feat2plane;
     size_t fake = (size_t)-1;  // ids that cannot collide with tracker ids: only the VALUES of the map are read
     for (int k = 0; k < n_active; ++k) f2p_active[fake--] = (size_t)active_planes[k];

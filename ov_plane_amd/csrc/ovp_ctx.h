@@ -7,6 +7,7 @@
 //   ovp_api_plane.hip  plane loop (ovp_msckf_plane_update) and plane initialisation (ovp_plane_init)
 //   ovp_api_slam.hip   SLAM landmarks (ovp_slam_update, ovp_slam_delayed_init), triangulation
 //   ovp_api_general.hip general point features (any camera, long tracks): camera tables, gate + pending pair, triangulation
+//   k_plane_detect.hip plane detection from the tracked features: its kernels and its entry points
 #pragma once
 #include "ovplane_hip.h"
 
@@ -295,6 +296,7 @@ struct ovp_ctx {
   // host-side clock of the two update entry points, accumulated (ovp_host_timing): plane loop [entry -> first launch | entry -> last
   // launch enqueued | wait for the device | calls], point update [enqueue | wait | calls]
   double host_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::shared_ptr<void> plane_det;  // ovp_plane_detector_create (k_plane_detect.hip): the detector and its buffers, freed with the context
 
   ovp_ctx() = default;
   ovp_ctx(const ovp_ctx&) = delete;

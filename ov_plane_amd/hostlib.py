@@ -604,6 +604,32 @@ class Session:
             raise RuntimeError("ovph_session_step failed with %d" % rc)
         return dict(counts=counts, x16=x16, posecov=pc.reshape(6, 6), slam_ids=[int(i) for i in ids[:counts[4]]])
 
+    def enable_plane_detection(self, opts=None):
+        """StateOptions::gpu_plane_detection: frames whose tracked points were handed over by feed_plane_tracks take their
+        feature -> plane map from the device plane detector (TrackPlane::feed_plane_detection), not from `plane` of step().
+        opts: capi.TrackPlaneOpts (None: TrackPlaneOptions' defaults)."""
+        rc = self._L.ovph_session_enable_plane_detection(C.c_void_p(self._h), C.byref(opts) if opts is not None else None)
+        if rc != 0:
+            raise RuntimeError("ovph_session_enable_plane_detection failed with %d" % rc)
+
+    def feed_plane_tracks(self, frame_time, fid, uv, uv_norm):
+        """every point tracked into the frame about to be stepped: ids, pixel positions, undistorted normalised coordinates"""
+        fid = np.ascontiguousarray(fid, dtype=np.int64)
+        uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+        uvn = np.ascontiguousarray(uv_norm, dtype=np.float32).reshape(-1, 2)
+        rc = self._L.ovph_session_feed_plane_tracks(C.c_void_p(self._h), C.c_double(frame_time), C.c_int(len(fid)),
+                                                    fid.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p),
+                                                    uvn.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise RuntimeError("ovph_session_feed_plane_tracks failed with %d" % rc)
+
+    def plane_detection_info(self):
+        """dict(rc of the last frame's detection, planar = features of the last step the detector put on a plane, mapped = entries
+        of the detector's map)"""
+        o = np.zeros(3, dtype=np.int32)
+        self._L.ovph_session_plane_detection_info(C.c_void_p(self._h), o.ctypes.data_as(C.c_void_p))
+        return dict(rc=int(o[0]), planar=int(o[1]), mapped=int(o[2]))
+
     def close(self):
         if self._h:
             self._L.ovph_session_close(C.c_void_p(self._h))
