@@ -357,6 +357,33 @@ int ovp_plane_init(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp_plane_ba
                    double const_init_chi2, double *dx_planes, int dx_stride, uint8_t *plane_ok, double *plane_chi2,
                    int *plane_dof, int *new_ids, double *cp_new, uint8_t *feat_used);
 
+/* The same initialisation in one device pass, over features of any camera and any track length up to OVP_GEN_MAX_MEAS views: the
+ * reference stacks every measurement of every camera of an on-plane feature (update/UpdaterHelper.cpp:335-344, 448-512) and
+ * init_vio_plane (update/UpdaterPlane.cpp:296-481) uses them all.  general / plane_of_gen / gen_used as in
+ * ovp_msckf_plane_update_general (general == NULL or an empty batch: the uploaded camera-0 batch only); the other arguments as in
+ * ovp_plane_init.
+ * For every plane in ascending id the on-plane features of the batch and of the general batch form ONE system, linearised at the
+ * state the previous accepted plane left (clone tables, calibration, the tables of ovp_cameras_upload); the gate is
+ * ovp_plane_init's (threshold const_init_chi2 * q95(rows_c), plane_dof = rows_c, counted over both kinds of features and the
+ * calibration columns of the cameras that saw them; fewer than 3 features or rows_c - 3 < 1: skipped).  Initialising a plane is
+ * the plane loop's out-of-state update with a flat prior on the plane, so everything in front of the gate is that loop
+ * (its column order, diagonal boost, retry on a semi-definite prior, marginal + push-through above 288 columns); behind the last
+ * plane the accepted planes are appended from the device-resident decisions (csrc/k_plane_init2.hip): with Z_k = E_xc,k E_cc,k^-1
+ * and P+ the loop's final covariance, cross block -P+ Z_k, plane blocks Z_j^T P+ Z_k + delta_jk E_cc,k^-1,
+ * d cp_k = E_cc,k^-1 (b_c,k - E_cx,k dx_k), and an earlier plane j receives -Z_j^T dx_k from every later accepted plane k.
+ * One enqueue, and the host waits once (a state above 288 columns: twice, as the plane loop there); it does not read a plane's
+ * decision to enqueue the next.  dx_planes[k*dx_stride ..] covers the variables that existed before plane k, the planes
+ * initialised earlier in the same call included.
+ * Refused on the host before anything is enqueued, covariance, size and tables untouched: OVP_E_CAPACITY for a general feature
+ * above OVP_GEN_MAX_MEAS views, for more than 287 involved columns (clones + calibration of every uploaded camera), for
+ * n + 3 * (planes with at least 3 features) > n_state_max; OVP_E_ARG as ovp_msckf_plane_update_general.  A failed factorization
+ * or a timed-out hand-over rejects its plane and every later one as in the plane loop: no column is written then and
+ * ovp_cov_size is unchanged. */
+int ovp_plane_init_general(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp_plane_batch *planes, double const_init_multi,
+                           double const_init_chi2, double *dx_planes, int dx_stride, uint8_t *plane_ok, double *plane_chi2,
+                           int *plane_dof, int *new_ids, double *cp_new, uint8_t *feat_used, const ovp_general_batch *general,
+                           const int *plane_of_gen, uint8_t *gen_used);
+
 /* StateHelper::EKFUpdate (state/StateHelper.cpp:121-202) for a dense H handed over by the host
  * (UpdaterSLAM::update, StateHelper::initialize, merge_planes...): H is [rows x cols] column-major with leading
  * dimension ld, col_ids[cols] gives the state column of every H column, R = I. */

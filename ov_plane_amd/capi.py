@@ -206,6 +206,7 @@ EXPORTS = [
     "ovp_slam_delayed_init_planes", "ovp_msckf_plane_update_general", "ovp_plane_fit_refine",
     "ovp_trackplane_defaults", "ovp_plane_detector_create", "ovp_plane_detector_destroy", "ovp_plane_detector_reset",
     "ovp_plane_detect_triangulate", "ovp_plane_detect_planes", "ovp_plane_detector_map", "ovp_delaunay", "ovp_plane_detector_debug", "ovp_plane_spatial_filter", "ovp_plane_detector_merges",
+    "ovp_plane_init_general",
 ]
 
 
@@ -275,6 +276,9 @@ def lib():
         L.ovp_plane_init.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(PlaneBatch), C.c_double, C.c_double,
                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]
+        L.ovp_plane_init_general.argtypes = [C.c_void_p, C.POINTER(UpdateOpts), C.POINTER(PlaneBatch), C.c_double, C.c_double,
+                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.POINTER(GeneralBatch), C.c_void_p, C.c_void_p]
         L.ovp_cov_propagate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                         C.c_void_p, C.POINTER(C.c_int)]
         L.ovp_cov_clone.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -916,6 +920,48 @@ class Context:
                                   dof.ctypes.data, nid.ctypes.data, cpn.ctypes.data, used.ctypes.data), "ovp_plane_init")
         return dict(dx=dx[:npl], ok=ok[:npl].astype(bool), chi2=chi2[:npl], dof=dof[:npl], new_ids=nid[:npl], cp=cpn[:npl],
                     used=used[: self.n_feats].astype(bool))
+
+    def plane_init_general(self, opts: UpdateOpts, plane_of_feat, cp, const_init_multi, const_init_chi2, sc=None, feats=None,
+                           uv=None, clone_idx=None, cam_idx=None, n_meas=None, p_FinG=None, plane_of_gen=None, raise_on_error=True):
+        """ovp_plane_init_general: init_vio_plane's core in one device pass over the uploaded batch's on-plane features and those of
+        a general batch (any camera, long tracks), given as in plane_update_general; None / empty = no general features.
+        Returns plane_init's dict plus gen_used [bool] and rc."""
+        if sc is not None:
+            sel = np.asarray(feats, dtype=np.int64)
+            uv, clone_idx, n_meas, p_FinG = sc.uv[sel], sc.clone_idx[sel], sc.n_meas[sel], sc.p_FinG[sel]
+            cam_idx = sc.cam_idx[sel] if "cam_idx" in sc else None
+            if plane_of_gen is None:
+                plane_of_gen = sc.plane_id[sel]
+        if uv is None or len(uv) == 0:
+            gb = GeneralBatch(0, 0, None, None, None, None, None)
+            pog = np.zeros(1, dtype=np.int32)
+        else:
+            gb = self._general_batch(uv, clone_idx, cam_idx, n_meas, p_FinG)
+            pog = np.ascontiguousarray(plane_of_gen, dtype=np.int32)
+            assert pog.shape[0] == gb.n_feats
+        GF = gb.n_feats
+        plane_of_feat = np.ascontiguousarray(plane_of_feat, dtype=np.int32)
+        cp = np.ascontiguousarray(cp, dtype=np.float64)
+        npl = int(cp.shape[0])
+        sid = -np.ones(max(npl, 1), dtype=np.int32)
+        stride = self.n_state_max
+        dx = np.zeros((max(npl, 1), stride))
+        ok = np.zeros(max(npl, 1), dtype=np.uint8)
+        chi2 = np.zeros(max(npl, 1))
+        dof = np.zeros(max(npl, 1), dtype=np.int32)
+        nid = np.zeros(max(npl, 1), dtype=np.int32)
+        cpn = np.zeros((max(npl, 1), 3))
+        used = np.zeros(max(self.n_feats, 1), dtype=np.uint8)
+        gused = np.zeros(max(GF, 1), dtype=np.uint8)
+        pb = PlaneBatch(npl, plane_of_feat.ctypes.data, cp.ctypes.data, cp.ctypes.data, sid.ctypes.data)
+        rc = lib().ovp_plane_init_general(self._h, C.byref(opts), C.byref(pb), C.c_double(const_init_multi),
+                                          C.c_double(const_init_chi2), dx.ctypes.data, C.c_int(stride), ok.ctypes.data,
+                                          chi2.ctypes.data, dof.ctypes.data, nid.ctypes.data, cpn.ctypes.data, used.ctypes.data,
+                                          C.byref(gb), pog.ctypes.data, gused.ctypes.data)
+        if rc != 0 and raise_on_error:
+            raise OvpError(rc, "ovp_plane_init_general")
+        return dict(dx=dx[:npl], ok=ok[:npl].astype(bool), chi2=chi2[:npl], dof=dof[:npl], new_ids=nid[:npl], cp=cpn[:npl],
+                    used=used[: self.n_feats].astype(bool), gen_used=gused[:GF].astype(bool), rc=rc)
 
     def ekf_update(self, H, col_ids, res):
         """StateHelper::EKFUpdate with a dense H (rows x cols) and per-column state ids."""

@@ -57,6 +57,9 @@ extern "C" void ovph_set_general_features(int on) { g_general = on != 0; }
 // next ovph_run_msckf_update: StateOptions::gpu_general_planes
 static int g_general_planes = 0;
 extern "C" void ovph_set_general_planes(int on) { g_general_planes = on != 0; }
+// next ovph_run_updater: StateOptions::gpu_general_plane_init
+static int g_general_plane_init = 0;
+extern "C" void ovph_set_general_plane_init(int on) { g_general_plane_init = on != 0; }
 // next ovph_run_msckf_update / ovph_run_updater: StateOptions::gpu_fused_plane_fit
 static int g_fused_plane_fit = 0;
 extern "C" void ovph_set_fused_plane_fit(int on) { g_fused_plane_fit = on != 0; }
@@ -538,6 +541,8 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
   g_general_slam = 0;
   so.gpu_dinit_planes = g_dinit_planes != 0;
   g_dinit_planes = 0;
+  so.gpu_general_plane_init = g_general_plane_init != 0;
+  g_general_plane_init = 0;
   // ovph_set_second_camera: a stereo state (camera 1's calibration behind camera 0's) and the camera of every measurement
   const bool cam1 = g_cam1_q != nullptr;
   const int *cam_of = g_cam_of_meas;

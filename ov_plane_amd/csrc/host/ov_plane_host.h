@@ -84,6 +84,11 @@ struct StateOptions {
   // planes whose estimate does not come from this frame's fit (in the state, or handed over in _plane_estimates_cp_inG); a frame with
   // an on-plane track above OVP_GEN_MAX_MEAS keeps the previous behaviour.  Not in the reference.
   bool gpu_general_planes = false;
+  // UpdaterPlane::init_vio_plane: the on-plane features the device batch cannot carry (another camera's observations, more than
+  // OVP_MAX_MEAS views; at most OVP_GEN_MAX_MEAS) are triangulated over every camera, take part in the fit when gpu_fused_plane_fit
+  // is on, and initialise their plane together with the batch's in one device pass (ovp_plane_init_general).  Off: ovp_plane_init,
+  // which takes every feature as camera 0's
+  bool gpu_general_plane_init = false;
   // The front end of the plane path (UpdaterMSCKF.cpp:262-401, UpdaterPlane.cpp:221-290) as ONE call of ovp_plane_fit_refine for all
   // planes of the frame instead of PlaneFitting::plane_fitting / optimize_plane once per plane: one round trip, and on-plane
   // features of any camera and any track length take part in the fit (with gpu_general_planes the ones the fit kept then enter

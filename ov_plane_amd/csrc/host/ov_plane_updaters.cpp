@@ -1495,15 +1495,26 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
   auto calib = state->_calib_IMUtoCAM.at(0);
   auto intr = state->_cam_intrinsics.at(0);
   const int C = (int)clones.size();
+  // StateOptions::gpu_general_plane_init: what the device batch cannot carry goes through the general batch (in the batch such a
+  // feature is present with no measurements); off: every feature is a batch row of camera 0, as before
+  const bool gen_on = state->_options.gpu_general_plane_init;
+  // off_batch: the batch cannot carry it (with the option on such a feature has no measurements there); is_general: the general
+  // batch can.  A track above OVP_GEN_MAX_MEAS views fits neither: it takes no part in the fit or the initialisation and stays in
+  // the vector for the update that follows
+  auto off_batch = [&](const ov_core::Feature &f) {
+    return gen_on && !(f.only_camera0() && (int)f.timestamps.size() <= OVP_MAX_MEAS);
+  };
+  auto is_general = [&](const ov_core::Feature &f) { return off_batch(f) && (int)f.timestamps.size() <= OVP_GEN_MAX_MEAS; };
   auto upload = [&](const std::vector<std::shared_ptr<ov_core::Feature>> &fv, int &M_out) {
     const int Fn = (int)fv.size();
     int Mx = 1;
-    for (auto &f : fv) Mx = std::max(Mx, (int)f->timestamps.size());
+    for (auto &f : fv)
+      if (!off_batch(*f)) Mx = std::max(Mx, (int)f->timestamps.size());
     std::vector<float> uvb((size_t)Fn * Mx * 2, 0.f);
     std::vector<int> cidxb((size_t)Fn * Mx, -1), nmb(Fn);
     std::vector<double> pfb((size_t)Fn * 3);
     for (int f = 0; f < Fn; ++f) {
-      nmb[f] = (int)fv[f]->timestamps.size();
+      nmb[f] = off_batch(*fv[f]) ? 0 : (int)fv[f]->timestamps.size();
       for (int k = 0; k < nmb[f]; ++k) {
         cidxb[(size_t)f * Mx + k] = clone_slot.at(fv[f]->timestamps[k]);
         uvb[((size_t)f * Mx + k) * 2] = fv[f]->uvs[2 * k];
@@ -1553,8 +1564,10 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
       upload(valid, Mv);
       const int Fv = (int)valid.size();
       std::vector<float> uvn((size_t)Fv * Mv * 2, 0.f);
-      for (int f = 0; f < Fv; ++f)
+      for (int f = 0; f < Fv; ++f) {
+        if (off_batch(*valid[f])) continue;  // (no measurements in the batch; its row is Mv wide, its track may be longer)
         for (size_t k = 0; k < valid[f]->uvs_norm.size(); ++k) uvn[(size_t)f * Mv * 2 + k] = valid[f]->uvs_norm[k];
+      }
       ovp_triang_opts to;
       to.refine_features = _featinit.refine_features ? 1 : 0;
       to.triangulate_1d = _featinit.triangulate_1d ? 1 : 0;
@@ -1572,6 +1585,35 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
       std::vector<double> pfv((size_t)Fv * 3);
       std::vector<uint8_t> okv(Fv, 0);
       gpu_check2(ovp_triangulate(state->_gpu, &to, uvn.data(), pfv.data(), okv.data()), "ovp_triangulate");
+      std::vector<int> tg;  // gpu_general_plane_init: over every view, each with its own camera's extrinsics
+      for (int f = 0; f < Fv; ++f)
+        if (is_general(*valid[f]) && valid[f]->uvs_norm.size() == valid[f]->uvs.size()) tg.push_back(f);
+      if (!tg.empty()) {
+        UpdaterSLAM::upload_camera_tables(state);
+        const int G = (int)tg.size();
+        int GM = 1;
+        for (int f : tg) GM = std::max(GM, (int)valid[f]->timestamps.size());
+        std::vector<int> gci((size_t)G * GM, 0), gcam((size_t)G * GM, 0), gnm(G);
+        std::vector<float> guvn((size_t)G * GM * 2, 0.f);
+        for (int g = 0; g < G; ++g) {
+          const ov_core::Feature &ft = *valid[tg[g]];
+          gnm[g] = (int)ft.timestamps.size();
+          for (int k = 0; k < gnm[g]; ++k) {
+            gci[(size_t)g * GM + k] = clone_slot.at(ft.timestamps[k]);
+            gcam[(size_t)g * GM + k] = ft.cam_of(k);
+            guvn[((size_t)g * GM + k) * 2] = ft.uvs_norm[2 * k];
+            guvn[((size_t)g * GM + k) * 2 + 1] = ft.uvs_norm[2 * k + 1];
+          }
+        }
+        ovp_general_batch gb{G, GM, guvn.data(), gci.data(), gcam.data(), gnm.data(), nullptr};
+        std::vector<double> gpf((size_t)G * 3, 0.0);
+        std::vector<uint8_t> gok(G, 0);
+        gpu_check2(ovp_triangulate_general(state->_gpu, &to, &gb, guvn.data(), gpf.data(), gok.data()), "ovp_triangulate_general");
+        for (int g = 0; g < G; ++g) {
+          okv[tg[g]] = gok[g];
+          memcpy(&pfv[3 * tg[g]], &gpf[3 * g], 3 * sizeof(double));
+        }
+      }
       std::vector<std::shared_ptr<ov_core::Feature>> good;
       for (int f = 0; f < Fv; ++f) {
         const bool had_norm = !valid[f]->uvs_norm.empty();
@@ -1590,6 +1632,8 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
     std::map<size_t, std::vector<std::shared_ptr<ov_core::Feature>>> plane_feats;
     for (auto &feat : valid) {
       const size_t planeid = feat2plane.at(feat->featid);
+      // (the host fit and its refinement know camera 0 only: a general feature takes part in the fused fit, or in none)
+      if (off_batch(*feat) && !(is_general(*feat) && state->_options.gpu_fused_plane_fit)) continue;
       if ((int)plane_feat_count[planeid] > state->_options.max_msckf_plane) continue;
       plane_feat_count[planeid]++;
       plane_feats[planeid].push_back(feat);
@@ -1660,7 +1704,8 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
     auto it = feat2plane.find(feature_vec[f]->featid);
     if (it != feat2plane.end()) {
       auto pos = std::find(todo.begin(), todo.end(), it->second);
-      if (pos != todo.end() && (!fitted || fit_kept.count(feature_vec[f]->featid))) pof[f] = 1 + (int)(pos - todo.begin());
+      if (pos != todo.end() && (!fitted || fit_kept.count(feature_vec[f]->featid)) && (!off_batch(*feature_vec[f]) || is_general(*feature_vec[f])))
+        pof[f] = 1 + (int)(pos - todo.begin());
     }
   }
   const int NP = (int)todo.size();
@@ -1679,9 +1724,44 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
   std::vector<double> dxp((size_t)NP * stride, 0.0);
   std::vector<uint8_t> pok(NP, 0), fused(F, 0);
   ovp_plane_batch pb{NP, pof.data(), cpv.data(), cpv.data(), sid.data()};
-  gpu_check2(ovp_plane_init(state->_gpu, &o, &pb, state->_options.const_init_multi, state->_options.const_init_chi2, dxp.data(), stride,
-                            pok.data(), nullptr, nullptr, nid.data(), cpn.data(), fused.data()),
-             "ovp_plane_init");
+  std::vector<int> gidx;  // features of the general batch (their pof entry names the plane; the batch holds them without measurements)
+  for (int f = 0; f < F; ++f)
+    if (pof[f] > 0 && is_general(*feature_vec[f])) gidx.push_back(f);
+  if (gen_on) {
+    // one call over both kinds of features (update/UpdaterHelper.cpp:335-344: every camera's measurements of a feature)
+    UpdaterSLAM::upload_camera_tables(state);
+    const int G = (int)gidx.size();
+    int GM = 1;
+    for (int f : gidx) GM = std::max(GM, (int)feature_vec[f]->timestamps.size());
+    std::vector<float> guv((size_t)std::max(G, 1) * GM * 2, 0.f);
+    std::vector<int> gci((size_t)std::max(G, 1) * GM, 0), gcam((size_t)std::max(G, 1) * GM, 0), gnm(std::max(G, 1), 0), gpl(std::max(G, 1), 0);
+    std::vector<double> gpf((size_t)std::max(G, 1) * 3, 0.0);
+    std::vector<uint8_t> gused(std::max(G, 1), 0);
+    for (int g = 0; g < G; ++g) {
+      const ov_core::Feature &ft = *feature_vec[gidx[g]];
+      gnm[g] = (int)ft.timestamps.size();
+      gpl[g] = pof[gidx[g]];
+      pof[gidx[g]] = 0;
+      for (int k = 0; k < gnm[g]; ++k) {
+        gci[(size_t)g * GM + k] = clone_slot.at(ft.timestamps[k]);
+        gcam[(size_t)g * GM + k] = ft.cam_of(k);
+        guv[((size_t)g * GM + k) * 2] = ft.uvs[2 * k];
+        guv[((size_t)g * GM + k) * 2 + 1] = ft.uvs[2 * k + 1];
+      }
+      memcpy(&gpf[3 * g], ft.p_FinG, 3 * sizeof(double));
+    }
+    ovp_general_batch gb{G, GM, guv.data(), gci.data(), gcam.data(), gnm.data(), gpf.data()};
+    gpu_check2(ovp_plane_init_general(state->_gpu, &o, &pb, state->_options.const_init_multi, state->_options.const_init_chi2, dxp.data(),
+                                      stride, pok.data(), nullptr, nullptr, nid.data(), cpn.data(), fused.data(), &gb, gpl.data(),
+                                      gused.data()),
+               "ovp_plane_init_general");
+    for (int g = 0; g < G; ++g)
+      if (gused[g]) fused[gidx[g]] = 1;  // consumed like the batch's: feature_vec_used below
+  } else {
+    gpu_check2(ovp_plane_init(state->_gpu, &o, &pb, state->_options.const_init_multi, state->_options.const_init_chi2, dxp.data(),
+                              stride, pok.data(), nullptr, nullptr, nid.data(), cpn.data(), fused.data()),
+               "ovp_plane_init");
+  }
   for (int k = 0; k < NP; ++k) {
     if (!pok[k]) continue;
     // Type::update of the variables that existed before this plane, then the plane itself joins the state (:441-449)

@@ -696,6 +696,10 @@ extern "C" long ovp_debug_read(ovp_ctx* c, const char* name, void* host, long ma
     memcpy(host, &cap, sizeof(size_t));
     return (long)sizeof(size_t);
   }
+  // clone tables on the device ([n_clones][9] row-major rotations, [n_clones][3] positions), as the last commit left them
+  // (their size is the clone count of ovp_state_upload)
+  else if (!strcmp(name, "clone_R")) { src = c->clone_R; bytes = (size_t)9 * c->h_clone_id.size() * sizeof(double); if (!src || !c->have_state) return OVP_E_STATE; }
+  else if (!strcmp(name, "clone_p")) { src = c->clone_p; bytes = (size_t)3 * c->h_clone_id.size() * sizeof(double); if (!src || !c->have_state) return OVP_E_STATE; }
   else if (!strcmp(name, "cal")) { src = c->cal; bytes = 20 * sizeof(double); if (!src) return OVP_E_STATE; }
   else if (!strcmp(name, "gen_cal")) { src = c->gen_cal; bytes = (size_t)20 * c->gen_ncams * sizeof(double); if (!src) return OVP_E_STATE; }
   // plane table of the last ovp_slam_delayed_init_planes ([n_planes][8]: cp | cp_fej | id | -), valid until the next call that stages

@@ -3,6 +3,7 @@
 // features of a general batch (any camera, tracks of up to OVP_GEN_MAX_MEAS views) stacked behind the batch's, as
 // update/UpdaterHelper.cpp:335-344 and :448-512 stack them whatever camera saw them and however long the track is.
 #include "ovp_ctx.h"
+#include "k_plane_init2.h"
 
 // device sequence shared by the plane update and the plane initialisation: feature kernel, Gram reduction, reduction to the
 // state columns, range-energy factorisation, information-form update with the factor Mf (P = Mf Mf^T), gate.
@@ -78,7 +79,21 @@ static int plane_buffers(ovp_ctx* c, int NP) {
 // ---- UpdaterMSCKF::update, per-plane loop (second generation): the host structures, the result kernels, the buffers; the loop itself
 // (plane_loop) is further down, behind the column-order route into it ----
 struct PlaneJobH { int pl, start, nf, rows_total, rows_live, rows_u, n_involved, in_state, sid, n_inv_cols, ns_pl; double thr;
-                   int g_start, ng; /* general features: range in the list of the call */ };
+                   int g_start, ng; /* general features: range in the list of the call */
+                   int dof; /* what plane_dof reports: rows_u, initialisation: all rows_c (StateHelper::initialize's chi2) */ };
+
+// The loop as the front of a plane initialisation (ovp_plane_init_general): every plane of the call is outside the state, its
+// constraint rows carry const_init_multi, the gate is StateHelper::initialize's, and behind the last plane the accepted ones are
+// appended to the resident covariance (k_plane_init2.hip).
+struct PlaneInitView {
+  double multi = 1.0, chi2 = 1.0;  // const_init_multi, const_init_chi2
+  double* keep = nullptr;          // device [n_planes][3][nk + 4]: the plane rows of every plane's extended pair
+  int* slot = nullptr;             // device [2 n_planes]: numbering of the accepted planes
+  int extra = 0;                   // doubles behind the loop's 4 n_planes results, published with them: [d cp | plane-by-plane corrections]
+  double* P = nullptr;             // the resident covariance and its size
+  int n_state = 0;
+  const int* d_ids = nullptr;      // device: loop column -> state column
+};
 
 // What tells the routes into the plane loop apart, as arguments: ovp_msckf_plane_update and ovp_msckf_plane_update_general fill in the
 // general batch, plane_update_ordered the column order, the retry on a positive semi-definite prior sets psd.  None of it is kept in
@@ -97,6 +112,7 @@ struct PlaneLoopView {
   const int* gen_pos = nullptr;       // [n_state] state column -> column in the loop's order, nullptr = identity
   int n_state = 0;
   unsigned char* gen_used = nullptr;  // [gen->n_feats] out: consumed by an accepted plane
+  const PlaneInitView* init = nullptr;  // the loop initialises its planes (nullptr: it updates with them)
 };
 // the caller's result arrays of a plane entry point (each may be nullptr)
 struct PlaneOut { double* dx_planes; uint8_t* plane_ok; double* plane_chi2; int* plane_dof; uint8_t* feat_used; };
@@ -364,6 +380,7 @@ static int push_through_commit(ovp_ctx* c, int ns, hipStream_t s) {
 }
 
 static int plane_loop(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, const PlaneLoopView& v, const PlaneOut& out);
+static int plane_init_tail(ovp_ctx* c, const PlaneLoopView& v, int NP, bool solve, bool columns, const int* flags);
 
 // ---- the plane loop in the loop's own column order (update/UpdaterMSCKF.cpp:413-649 has no size limit) --------------------------
 // A plane's rows touch the clones, the calibration, its own closest point when it is a state variable and the SLAM landmarks lying
@@ -451,6 +468,14 @@ static int plane_update_ordered(ovp_ctx* c, const ovp_update_opts* o, const ovp_
   }
   // full order: the columns behind the involved ones take a diagonal boost that the un-permutation behind the loop takes off
   // again (k_gather_block_boost) - an exact stochastic clone then factors at the first attempt
+  PlaneInitView iv;
+  if (vin.init) {  // (c->P: still the resident block, the loop's view of the state is entered below)
+    iv = *vin.init;
+    iv.P = c->P;
+    iv.n_state = n;
+    iv.d_ids = d_ids;
+    v.init = &iv;
+  }
   v.boost = full && n_inv < ns;
   if (v.boost) {
     HIPCHK(c->boost_vec.alloc((size_t)c->n_max + 16));
@@ -485,6 +510,8 @@ static int plane_update_ordered(ovp_ctx* c, const ovp_update_opts* o, const ovp_
       HIPCHK(hipMemcpy2DAsync(dx_planes, sizeof(double) * n, c->Lt, sizeof(double) * ld, sizeof(double) * n, NP, hipMemcpyDeviceToHost, s));
     }
     if (const int r = push_through_commit(c, ns, s)) return r;
+    if (v.init && NP > 0)  // (a loop whose factorization failed has returned above: the decisions stand)
+      if (const int r = plane_init_tail(c, v, NP, /*solve=*/false, /*columns=*/true, nullptr)) return r;
     HIPCHK(hipStreamSynchronize(s));
   }
   if (dx_planes)  // the involved entries straight from the loop (on a marginal the product above agrees with them to rounding)
@@ -538,7 +565,8 @@ static int plane_prelaunch(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane
   pre->fp.skip = nullptr;
   pre->fp.range_lo = 0;  // the plane loop always walks the whole batch
   pre->fp.range_hi = 0x7fffffff;
-  pre->res_bytes = sizeof(double) * (4 * (size_t)NP + (size_t)n * NP) + (size_t)F + 64 + 256;  // (+ flags and sequence word)
+  const size_t n_extra = v.init ? (size_t)v.init->extra : 0;
+  pre->res_bytes = sizeof(double) * (4 * (size_t)NP + n_extra + (size_t)n * NP) + (size_t)F + 64 + 256;  // (+ flags and sequence word)
   rc = plane_buffers(c, NP);  // shared with the first generation: pl_res, pl_dx, pl_cst, pl_An, ...
   if (rc) return rc;
   rc = plane2_buffers(c, 0, pre->res_bytes);
@@ -553,7 +581,7 @@ static int plane_prelaunch(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane
     // the packed factor / inverted diagonal blocks behind the loop start out as the identity for the same reason
     const int ntn = (n + 15) / 16;
     void* zp[8] = {c->pl_res, c->pl_dx, c->pl_used, c->flags, c->pl_cur, c->pl_Tbuf, c->Ltp, c->Dinv};
-    const size_t zb[8] = {sizeof(double) * 4 * NP, sizeof(double) * (size_t)n * NP, ((size_t)F + 3) & ~(size_t)3, sizeof(int) * 4,
+    const size_t zb[8] = {sizeof(double) * (4 * NP + n_extra), sizeof(double) * (size_t)n * NP, ((size_t)F + 3) & ~(size_t)3, sizeof(int) * 4,
                           3 * sizeof(int), sizeof(double) * (tstride + (size_t)n * ld),
                           v.ordered ? sizeof(double) * 256 * (size_t)(ntn * (ntn + 1) / 2) : 0,
                           v.ordered ? sizeof(double) * 256 * (size_t)ntn : 0};
@@ -577,7 +605,7 @@ static int plane_prelaunch(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane
     for (int g = 0; g < GF; ++g)
       if (v.plane_of_gen[g] >= 1 && v.plane_of_gen[g] <= NP && v.gen->n_meas[g] >= 2) ++cnt[v.plane_of_gen[g]];
     for (int pl = 1; pl <= NP && !pre->any_candidate; ++pl)
-      pre->any_candidate = cnt[pl] >= (pb->plane_state_id[pl - 1] >= 0 ? 1 : 4);
+      pre->any_candidate = cnt[pl] >= (v.init ? 3 : (pb->plane_state_id[pl - 1] >= 0 ? 1 : 4));
   }
   // L0 = chol(P), dense lower triangular in c->L.  Nothing needs it before the first plane's W = A L0, so it runs on the side
   // stream beside that plane's rows / Gram pair / assembly (round 5; one workgroup - the small kernels of the front end leave it a
@@ -682,7 +710,9 @@ static int plane_group(const ovp_ctx* c, const ovp_update_opts* o, const ovp_pla
         if (pb->slam_plane[q] == pl + 1) ++ns_pl;
     if (ns_pl > PA_MAXQ) return OVP_E_CAPACITY;
     j.ns_pl = ns_pl;
-    if (j.nf + j.ng == 0 || (!j.in_state && j.nf + j.ng + ns_pl < 4)) {  // update/UpdaterMSCKF.cpp:316-317,384-396
+    const bool too_few = v.init ? j.nf + j.ng < 3  // update/UpdaterPlane.cpp:303
+                                : (j.nf + j.ng == 0 || (!j.in_state && j.nf + j.ng + ns_pl < 4));  // update/UpdaterMSCKF.cpp:316-317,384-396
+    if (too_few) {
       g.featlist.resize(j.start);
       g.glist.resize(j.g_start);
       continue;
@@ -701,7 +731,9 @@ static int plane_group(const ovp_ctx* c, const ovp_update_opts* o, const ovp_pla
       continue;
     }
     if (j.ng > g.ng_max) g.ng_max = j.ng;
-    j.thr = o->chi2_multiplier * ovp_chi2_quantile_095(j.rows_u);
+    // (initialisation: the chi2 of StateHelper::initialize covers the rows that do not involve the plane, with dof = all rows, :471)
+    j.dof = v.init ? rows_c : j.rows_u;
+    j.thr = v.init ? v.init->chi2 * ovp_chi2_quantile_095(rows_c) : o->chi2_multiplier * ovp_chi2_quantile_095(j.rows_u);
     // order of the involved columns in the normalised Gram: everything that is not a clone first, the clones last (a rank
     // deficiency - gauge freedom, planar scene - then shows up in the trailing pivots, k_chol2 mode 2)
     {
@@ -1108,6 +1140,8 @@ static int plane_enqueue(ovp_ctx* c, const PlaneCall& k, const PlaneJobH& j, int
   // (3) pair on the state columns, normalised Gram, residual energy
   const ovp::PlaneAsm pa = plane_asm_params(c, k, j, jn, nk, chunks, nsplit, ntile_pl);
   HIPCHK(ovp_launch_plane_assemble2(&pa, s));
+  if (k.v->init)  // initialisation: the plane rows of the extended pair stay behind for the tail (same partials, same moments)
+    HIPCHK(ovp_launch_plane_init_keep(&pa, k.v->init->keep + (size_t)j.pl * 3 * (nk + 4), s));
   // (4) W = A L0 ;  T_try = T_cur + L0^T W ;  c = L0^T b
   HIPCHK(join_chol(fork));  // (first plane: L0 comes from the side stream)
   HIPCHK(ovp_launch_gemm4(0, 0, nk, nk, nk, c->Ab, ld, c->L, ld, c->W1, ld, 0, 0, s));
@@ -1185,21 +1219,21 @@ static int plane_cov_product(ovp_ctx* c, const PlaneLoopView& v, size_t tstride,
 // [chi2, decision, .. per plane | dx per plane | consumed features], and behind `used`, each on a 64-byte line of its own: the
 // flags, the sequence word
 struct PlaneResBlock { double *res, *dx; unsigned char* used; char* flags; volatile unsigned* seq; };
-static PlaneResBlock plane_res_block(const ovp_ctx* c, int NP) {
+static PlaneResBlock plane_res_block(const ovp_ctx* c, int NP, int n_extra) {
   PlaneResBlock b;
   b.res = (double*)c->pl_hres;
-  b.dx = b.res + 4 * (size_t)NP;
+  b.dx = b.res + 4 * (size_t)NP + n_extra;
   b.used = (unsigned char*)(b.dx + (size_t)c->n * NP);
   b.flags = (char*)b.used + StageLayout::al((size_t)c->n_feats);
   b.seq = (volatile unsigned*)(b.flags + 64);
   return b;
 }
-static int plane_publish(ovp_ctx* c, const PlaneResBlock& b, int NP, bool want_dx, unsigned* seq_out) {
+static int plane_publish(ovp_ctx* c, const PlaneResBlock& b, int NP, int n_extra, bool want_dx, unsigned* seq_out) {
   *b.seq = 0u;  // (its offset depends on NP, n and F: an earlier call's payload may have left the next sequence number there)
   const unsigned seq = *seq_out = ++c->pl_pub_seq;
   char* dbase = (char*)c->pl_hres.dev();
   auto dev_of = [&](const void* hp) { return dbase + ((const char*)hp - (const char*)c->pl_hres); };
-  hipLaunchKernelGGL(k_publish_plane_results, dim3(1), dim3(1024), 0, c->stream, c->pl_res, 4 * NP, c->pl_dx, want_dx ? c->n * NP : 0,
+  hipLaunchKernelGGL(k_publish_plane_results, dim3(1), dim3(1024), 0, c->stream, c->pl_res, 4 * NP + n_extra, c->pl_dx, want_dx ? c->n * NP : 0,
                      c->pl_used, c->n_feats, c->flags, (double*)dev_of(b.res), (double*)dev_of(b.dx), (unsigned char*)dev_of(b.used),
                      (int*)dev_of(b.flags), (volatile unsigned*)dev_of((const void*)b.seq), seq);
   HIPCHK(hipGetLastError());
@@ -1243,7 +1277,7 @@ static int plane_unpack(ovp_ctx* c, const PlaneLoopView& v, const PlaneGroups& g
   for (const PlaneJobH& j : g.jobs) {
     if (out.plane_ok) out.plane_ok[j.pl] = hres[4 * j.pl + 1] > 0.5 ? 1 : 0;
     if (out.plane_chi2) out.plane_chi2[j.pl] = hres[4 * j.pl];
-    if (out.plane_dof) out.plane_dof[j.pl] = j.rows_u;
+    if (out.plane_dof) out.plane_dof[j.pl] = j.dof;
   }
   const int bad = c->h_flags[0] | c->h_flags[2];  // (the device words were cleared by the publishing kernel)
   if (bad) {
@@ -1264,6 +1298,32 @@ static int plane_unpack(ovp_ctx* c, const PlaneLoopView& v, const PlaneGroups& g
   if (bad & 2) return OVP_E_TIMEOUT;
   if (bad) return OVP_E_NOTSPD;
   c->have_factor = factor_enqueued;
+  return 0;
+}
+
+// ---- the tail of a plane initialisation (k_plane_init2.hip): from the device-resident decisions, no host round trip ----
+// solve: numbering, Z, d cp, corrections between the new planes (loop order; results go out with the loop's);  columns: the new
+// rows and columns of the resident covariance (needs the covariance behind the last plane in place).  Inside the loop c->n is the
+// loop's size and c->pl_dx its stride.
+static int plane_init_tail(ovp_ctx* c, const PlaneLoopView& v, int NP, bool solve, bool columns, const int* flags) {
+  const PlaneInitView& iv = *v.init;
+  ovp::PlaneInitTail t;
+  memset(&t, 0, sizeof(t));
+  t.res = c->pl_res;
+  t.n_planes = NP;
+  t.keep = iv.keep;
+  t.nk = v.nl[NP - 1];
+  t.dx = c->pl_dx;
+  t.dx_stride = c->n;
+  t.flags = flags;
+  t.slot = iv.slot;
+  t.extra = c->pl_res + 4 * (size_t)NP;
+  t.P = iv.P;
+  t.ldp = c->ld;
+  t.n_state = iv.n_state;
+  t.ids = iv.d_ids;
+  if (solve) HIPCHK(ovp_launch_plane_init_solve(&t, c->stream));
+  if (columns) HIPCHK(ovp_launch_plane_init_columns(&t, c->stream));
   return 0;
 }
 
@@ -1315,7 +1375,8 @@ static int plane_loop(ovp_ctx* c, const ovp_update_opts* o_in, const ovp_plane_b
   // calibrated constant for the study that produced it (tools/plane_gate_agreement.py --fit)
   double noise_scale = OVP_PLANE_NOISE_KAPPA;
   if (const char* ns_env = getenv("OVP_PL_NOISE_SCALE")) noise_scale = atof(ns_env);  // (read per call)
-  const PlaneCall call{o, pb, &v, &pre, &st, &gs, NJ, 1.0 / o->sigma_constraint, noise_scale};
+  const double sigma_c = v.init ? v.init->multi * o->sigma_constraint : o->sigma_constraint;
+  const PlaneCall call{o, pb, &v, &pre, &st, &gs, NJ, 1.0 / sigma_c, noise_scale};
   for (int jn = 0; jn < NJ; ++jn) {
     rc = plane_enqueue(c, call, g.jobs[jn], jn, fork);
     if (rc) return rc;
@@ -1324,11 +1385,16 @@ static int plane_loop(ovp_ctx* c, const ovp_update_opts* o_in, const ovp_plane_b
   if (NJ > 0) {
     rc = plane_cov_product(c, v, pre.tstride, &factor_enqueued);
     if (rc) return rc;
+    if (v.init) {  // the accepted planes become state variables (on a marginal the columns wait for the push-through)
+      rc = plane_init_tail(c, v, NP, /*solve=*/true, /*columns=*/!v.marginal, c->flags);
+      if (rc) return rc;
+    }
   }
   if (c->pl_ktimer) HIPCHK(hipEventRecord(c->pl_ev_loop[1], s));
-  const PlaneResBlock blk = plane_res_block(c, NP);
+  const int n_extra = v.init ? v.init->extra : 0;
+  const PlaneResBlock blk = plane_res_block(c, NP, n_extra);
   unsigned seq = 0;
-  rc = plane_publish(c, blk, NP, out.dx_planes != nullptr, &seq);
+  rc = plane_publish(c, blk, NP, n_extra, out.dx_planes != nullptr, &seq);
   if (rc) return rc;
   const double t_enq = host_now_ms();
   rc = ovp_wait_seq(blk.seq, seq, s);
@@ -1546,5 +1612,139 @@ extern "C" int ovp_plane_init(ovp_ctx* c, const ovp_update_opts* o, const ovp_pl
     if (feat_used)
       for (int f : featlist) feat_used[f] = 1;
   }
+  return 0;
+}
+
+// ---- UpdaterPlane::init_vio_plane core in one device pass, any camera (update/UpdaterPlane.cpp:296-481 over the rows of
+// update/UpdaterHelper.cpp:335-344, 448-512) ----
+// Initialisation is the loop's out-of-state plane update with a flat prior on the plane (white_c = 1 / (const_init_multi sigma_c),
+// StateHelper::initialize's gate), so everything in front of the gate is plane_loop in the column order of plane_update_ordered; the
+// accepted planes are appended behind the last plane from the device-resident decisions (k_plane_init2.hip).
+extern "C" int ovp_plane_init_general(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, double const_init_multi,
+                                      double const_init_chi2, double* dx_planes, int dx_stride, uint8_t* plane_ok, double* plane_chi2,
+                                      int* plane_dof, int* new_ids, double* cp_new, uint8_t* feat_used, const ovp_general_batch* gb,
+                                      const int* plane_of_gen, uint8_t* gen_used) {
+  if (!c || !o || !pb || pb->n_planes < 0 || (gb && gb->n_feats < 0)) return OVP_E_ARG;
+  if (!pb->cp || (dx_planes && dx_stride < 0)) return OVP_E_ARG;
+  const int GF = gb ? gb->n_feats : 0, NP = pb->n_planes, F = c->n_feats, n = c->n;
+  if (GF > 0 && (!plane_of_gen || !gb->n_meas)) return OVP_E_ARG;
+  bool any = false;
+  int cand = 0;  // planes with at least three features: the only ones that can append columns
+  for (int g = 0; g < GF; ++g) {
+    if (plane_of_gen[g] < 0 || plane_of_gen[g] > NP) return OVP_E_ARG;
+    any |= plane_of_gen[g] > 0;
+  }
+  if (!c->have_state || !c->have_cov || !c->have_batch) return OVP_E_STATE;
+  if (c->h_n_meas.empty() && F > 0) return OVP_E_STATE;
+  if (F > 0 && !pb->plane_of_feat) return OVP_E_ARG;
+  // ---- everything that can refuse the call, before anything is enqueued or written ----
+  if (any) {
+    if (c->gen_ncams < 1) return OVP_E_STATE;
+    const int rc = check_general_batch(c, gb, true, plane_of_gen);  // (a track above OVP_GEN_MAX_MEAS: OVP_E_CAPACITY)
+    if (rc) return rc;
+    if (CalCols(c, o).check(n, true)) return OVP_E_ARG;
+  }
+  {
+    std::vector<int> cnt((size_t)NP + 1, 0);
+    for (int f = 0; f < F; ++f) {
+      const int pf = pb->plane_of_feat[f];
+      if (pf >= 1 && pf <= NP && c->h_n_meas[f] >= 2) ++cnt[pf];
+    }
+    for (int g = 0; g < GF; ++g)
+      if (plane_of_gen[g] >= 1 && gb->n_meas[g] >= 2) ++cnt[plane_of_gen[g]];
+    for (int pl = 1; pl <= NP; ++pl) cand += cnt[pl] >= 3;
+    if (n + 3 * cand > c->n_max) return OVP_E_CAPACITY;
+    ColumnOrder co(n, n);  // the involved columns: one factorization has to hold them (plane_update_ordered places the same)
+    co.place_clones_and_calibration(c, o);
+    if (any)
+      for (int k = 0; k < c->gen_ncams; ++k) {
+        if (o->do_calib_camera_pose) co.place(c->gen_calib_id[k], 6);
+        if (o->do_calib_camera_intrinsics) co.place(c->gen_intr_id[k], 8);
+      }
+    if (co.bad_id) return OVP_E_ARG;
+    if ((int)co.ids.size() > ovp_chol2_max_n()) return OVP_E_CAPACITY;
+  }
+  if (feat_used && F) memset(feat_used, 0, (size_t)F);
+  if (gen_used && GF) memset(gen_used, 0, (size_t)GF);
+  for (int pl = 0; pl < NP; ++pl) {
+    if (new_ids) new_ids[pl] = -1;
+    if (cp_new) memcpy(cp_new + 3 * pl, pb->cp + 3 * pl, 3 * sizeof(double));
+    if (dx_planes) memset(dx_planes + (size_t)pl * dx_stride, 0, sizeof(double) * dx_stride);
+    if (plane_ok) plane_ok[pl] = 0;
+    if (plane_chi2) plane_chi2[pl] = 0.0;
+    if (plane_dof) plane_dof[pl] = 0;
+  }
+  if (NP == 0 || cand == 0) return 0;  // update/UpdaterPlane.cpp:303: no plane of the call can be initialised
+  drop_kept_factor(c);  // (writes the covariance: a kept factor no longer belongs to it)
+  c->pl_used_valid = false;
+  if (const int rcu = ensure_pl_used(c)) return rcu;
+  // per-call device buffers of the tail: the kept plane rows of every plane, the numbering of the accepted ones; its results ride
+  // behind the loop's in c->pl_res
+  const int nk_max = (n < ovp_chol2_max_n() ? n : ovp_chol2_max_n()) + 4;
+  PlaneInitView iv;
+  iv.multi = const_init_multi;
+  iv.chi2 = const_init_chi2;
+  iv.extra = 3 * NP + 3 * NP * NP;
+  HIPCHK(c->pl_init_keep.reserve((size_t)NP * 3 * nk_max, (size_t)4 * 3 * nk_max));
+  HIPCHK(c->pl_init_slot.reserve(2 * (size_t)NP, 16));
+  HIPCHK(c->pl_res.reserve(4 * (size_t)NP + iv.extra, 64));
+  iv.keep = c->pl_init_keep;
+  iv.slot = c->pl_init_slot;
+  // no plane numbered until k_plane_init_solve has run: a loop that enqueues no plane (rows_c - 3 < 1 for all of them) leaves it so,
+  // and the column kernels behind a marginal's push-through then find nothing to append
+  HIPCHK(hipMemsetAsync(c->pl_init_slot, 0xff, sizeof(int) * 2 * (size_t)NP, c->stream));
+  // the loop's batch: every plane outside the state, no first estimate of its own, no landmark rows
+  std::vector<int> sid((size_t)NP, -1);
+  ovp_plane_batch pbi = *pb;
+  pbi.plane_state_id = sid.data();
+  pbi.cp_fej = pb->cp;
+  pbi.n_slam = 0;
+  pbi.slam_plane = pbi.slam_state_id = nullptr;
+  pbi.slam_p = pbi.slam_p_fej = nullptr;
+  pbi.force_decision = nullptr;
+  std::vector<double> dxp((size_t)NP * n, 0.0);
+  std::vector<uint8_t> ok((size_t)NP, 0);
+  std::vector<unsigned char> marks((size_t)(GF > 0 ? GF : 1), 0);
+  PlaneLoopView v;
+  v.t_entry = host_now_ms();
+  v.init = &iv;
+  if (any) {
+    v.gen = gb;
+    v.plane_of_gen = plane_of_gen;
+    v.gen_used = marks.data();
+  }
+  const int rc = plane_update_ordered(c, o, &pbi, v, PlaneOut{dxp.data(), ok.data(), plane_chi2, plane_dof, feat_used});
+  c->have_factor = false;  // (the loop's factor is the n x n block's; the state has grown)
+  if (rc) {
+    if (feat_used && F) memset(feat_used, 0, (size_t)F);
+    for (int pl = 0; pl < NP; ++pl) {
+      if (plane_chi2) plane_chi2[pl] = 0.0;
+      if (plane_dof) plane_dof[pl] = 0;
+    }
+    return rc;
+  }
+  // ---- the accepted planes, numbered as the device numbered them ----
+  const double* extra = (const double*)c->pl_hres + 4 * (size_t)NP;  // [d cp | corrections between the new planes]
+  int q = 0;
+  std::vector<int> nid((size_t)NP, -1);
+  for (int pl = 0; pl < NP; ++pl)
+    if (ok[pl]) nid[pl] = n + 3 * q++;
+  for (int pl = 0; pl < NP; ++pl) {
+    if (plane_ok) plane_ok[pl] = ok[pl];
+    if (!ok[pl]) continue;
+    if (new_ids) new_ids[pl] = nid[pl];
+    if (cp_new)
+      for (int k = 0; k < 3; ++k) cp_new[3 * pl + k] = pb->cp[3 * pl + k] + extra[3 * pl + k];
+    if (dx_planes) {  // the variables that existed before this plane: the state, then the planes initialised earlier in the call
+      double* row = dx_planes + (size_t)pl * dx_stride;
+      memcpy(row, dxp.data() + (size_t)pl * n, sizeof(double) * (size_t)(n < dx_stride ? n : dx_stride));
+      for (int pj = 0; pj < pl; ++pj)
+        if (ok[pj])
+          for (int k = 0; k < 3; ++k)
+            if (nid[pj] + k < dx_stride) row[nid[pj] + k] = extra[3 * NP + ((size_t)pj * NP + pl) * 3 + k];
+    }
+  }
+  if (gen_used && any) memcpy(gen_used, marks.data(), (size_t)GF);
+  c->n = n + 3 * q;
   return 0;
 }

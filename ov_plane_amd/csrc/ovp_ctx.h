@@ -4,7 +4,8 @@
 //                      initialize), pose tables, feature batch, diagnostics
 //   ovp_api_point.hip  point update: K1 -> information pair -> EKF update (ovp_msckf_update and its staged form), ovp_ekf_update
 //   ovp_api_rccl.hip   feature-sharded update over RCCL
-//   ovp_api_plane.hip  plane loop (ovp_msckf_plane_update) and plane initialisation (ovp_plane_init)
+//   ovp_api_plane.hip  plane loop (ovp_msckf_plane_update) and plane initialisation (ovp_plane_init; ovp_plane_init_general: the
+//                      loop as its front, k_plane_init2.hip as its tail)
 //   ovp_api_slam.hip   SLAM landmarks (ovp_slam_update, ovp_slam_delayed_init), triangulation
 //   ovp_api_general.hip general point features (any camera, long tracks): camera tables, gate + pending pair, triangulation
 //   k_plane_detect.hip plane detection from the tracked features: its kernels and its entry points
@@ -232,6 +233,8 @@ struct ovp_ctx {
   DevBuf<double> pl_xbuf, pl_xy;                 // split plane solve: exported panels, [xzz(2) | y blocks]
   DevBuf<unsigned> pl_xflag;                     // [32 step flags | 2 sync words]
   DevBuf<double> pl_Asum, pl_U;
+  DevBuf<double> pl_init_keep;                   // ovp_plane_init_general: [plane][3][nk + 4] plane rows of the extended pairs of the call
+  DevBuf<int> pl_init_slot;                      // ... and the numbering of its accepted planes (k_plane_init2.hip)
   DevBuf<void> pl_sub_tab;                       // [ids | inverse | clone ids | column map] of the loop's column order
   PinnedBuf<void> pl_sub_htab;
   // (what tells the plane loop's routes apart is an argument of the loop, PlaneLoopView in ovp_api_plane.hip, not context state)

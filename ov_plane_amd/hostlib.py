@@ -135,8 +135,10 @@ ROUTE_NONE, ROUTE_DEVICE_GENERAL, ROUTE_DEVICE_MONO, ROUTE_DENSE_HOST, ROUTE_HOS
 
 def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=None, slam=None, slam_rep=None,
                 feat_rep_slam=None, general_slam=False, triangulate=False, dinit_planes=False, state_planes=False,
-                fused_plane_fit=False):
+                fused_plane_fit=False, general_plane_init=False):
     """Drives the C++ host mirrors on a synth scene.
+    general_plane_init (mode "plane_init"): StateOptions::gpu_general_plane_init - on-plane features of another camera or of more
+    than 32 views initialise their plane with the batch's through ovp_plane_init_general.
     fit_planes=dict(min_feat, max_cond, variant) (mode "plane_init" only): the features carry normalised measurements and
     no position, no plane estimates are handed over - init_vio_plane triangulates, fits and refines itself.
 
@@ -157,6 +159,7 @@ def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=
     L.ovph_set_general_slam(1 if general_slam else 0)
     L.ovph_set_fused_plane_fit(1 if fused_plane_fit else 0)  # StateOptions::gpu_fused_plane_fit (mode "plane_init" with fit_planes)
     L.ovph_set_dinit_planes(1 if dinit_planes else 0)
+    L.ovph_set_general_plane_init(1 if general_plane_init else 0)
     pnp_keep = None
     if state_planes:
         assert mode == "slam_delayed_init" and bool(np.all(sc.plane_in_state))
