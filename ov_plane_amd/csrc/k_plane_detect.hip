@@ -7,7 +7,7 @@
 //                         :1123-1171)
 //   k_det_match           one thread per directed neighbour edge: the validity tests and the three predicates (:850-886)
 //   k_det_spatial_filter  one workgroup per plane: k nearest squared f32 distances by brute force, z-test (:1003-1058)
-//   k_det_publish         result block -> mapped pinned memory, then the sequence word in front of it
+// The result block of each stage goes to the host through the detector's Mailbox (ovp_mailbox.h, k_publish.hip).
 // No atomics, every order fixed: two runs give the same bits.
 #include "ovp_ctx.h"
 #include "host/ov_plane_delaunay.h"
@@ -309,28 +309,18 @@ __global__ __launch_bounds__(256) void k_det_spatial_filter(const int* __restric
   }
 }
 
-// payload words -> mapped pinned memory, then the sequence word (which sits in FRONT of the payload, at a fixed place)
-__global__ __launch_bounds__(1024) void k_det_publish(const unsigned* __restrict__ src, unsigned* __restrict__ dst, int words,
-                                                      volatile unsigned* seq_host, unsigned seq) {
-  for (int i = threadIdx.x; i < words; i += 1024) dst[i] = src[i];
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) *seq_host = seq;
-}
-
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 constexpr int S = OVP_DET_MAX_POINTS;          // feature slots: a feature not in the frame gives its slot back, so a frame's points fit
 constexpr int MAX_TRIS = 2 * S, MAX_EDGES = 6 * MAX_TRIS;
-constexpr size_t SEQ_BYTES = 64;               // the sequence word's line in front of the pinned payload
 
 struct Detector {
   ovp_trackplane_opts o;
   DevBuf<double> A, b, p, ring, avg;
   DevBuf<int> count, valid, ring_n;
-  PinnedBuf<void> hstage, hres{true};
+  PinnedBuf<void> hstage;
+  Mailbox hres;  // the results of a stage: payload from byte 0, channel 0
   DevBuf<void> dstage, dres;
   size_t stage_cap = 0, res_cap = 0;
-  unsigned seq = 0;
   hipEvent_t ev[8] = {};
   float ms[4] = {0, 0, 0, 0};
   bool timed = false;  // ovp_plane_detector_debug "timer": events around the kernels, read behind a stream synchronisation
@@ -368,11 +358,10 @@ Detector* det_of(ovp_ctx* c) { return c ? (Detector*)c->plane_det.get() : nullpt
 
 // device result block -> pinned, waited for
 int publish_and_wait(ovp_ctx* c, Detector* d, size_t bytes) {
-  const unsigned seq = ++d->seq;
-  hipLaunchKernelGGL(k_det_publish, dim3(1), dim3(1024), 0, c->stream, (const unsigned*)d->dres.get(),
-                     (unsigned*)((char*)d->hres.dev() + SEQ_BYTES), (int)((bytes + 3) / 4), (volatile unsigned*)d->hres.dev(), seq);
-  HIPCHK(hipGetLastError());
-  return ovp_wait_seq((const volatile unsigned*)d->hres.get(), seq, c->stream);
+  SeqChannel& ch = d->hres.channel(0);
+  const unsigned seq = ch.arm();
+  HIPCHK(ovp_launch_publish_block(d->dres.get(), d->hres.dev(d->hres.payload()), bytes, ch.word_dev(), seq, 0, c->stream));
+  return ch.wait(c->stream);
 }
 
 }  // namespace
@@ -406,8 +395,7 @@ extern "C" int ovp_plane_detector_create(ovp_ctx* c, const ovp_trackplane_opts* 
   HIPCHK(d->hstage.alloc(d->stage_cap));
   HIPCHK(d->dstage.alloc(d->stage_cap));
   HIPCHK(d->dres.alloc(d->res_cap));
-  HIPCHK(d->hres.alloc(SEQ_BYTES + d->res_cap));
-  memset(d->hres.get(), 0, SEQ_BYTES);
+  HIPCHK(d->hres.alloc(d->res_cap));
   for (hipEvent_t& e : d->ev) HIPCHK(hipEventCreate(&e));
   HIPCHK(hipMemsetAsync(d->valid.get(), 0, sizeof(int) * S, c->stream));
   HIPCHK(hipMemsetAsync(d->ring_n.get(), 0, sizeof(int) * S, c->stream));
@@ -496,7 +484,7 @@ extern "C" int ovp_plane_detect_triangulate(ovp_ctx* c, int n, const int64_t* id
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipEventElapsedTime(&d->ms[0], d->ev[0], d->ev[1]));
   }
-  const char* hr = (const char*)d->hres.get() + SEQ_BYTES;
+  const char* hr = (const char*)d->hres.payload();
   const double* rp = (const double*)(hr + r_p);
   const int* rf = (const int*)(hr + r_flag);
   d->v_id.clear(), d->v_slot.clear(), d->v_px.clear();
@@ -554,7 +542,7 @@ extern "C" int ovp_plane_detect_planes(ovp_ctx* c, int n_tris, const int32_t* tr
   char* h = (char*)d->hstage.get();
   char* dv = (char*)d->dstage.get();
   char* dr = (char*)d->dres.get();
-  const char* hr = (const char*)d->hres.get() + SEQ_BYTES;
+  const char* hr = (const char*)d->hres.payload();
   std::vector<std::vector<int>> nb(nv);  // feat_to_close_feat: neighbours, ascending feature id
   std::vector<unsigned char> match;
   std::vector<int> e_ptr(nv + 1, 0);
@@ -788,7 +776,7 @@ extern "C" int ovp_plane_spatial_filter(ovp_ctx* c, int n_planes, const int* fea
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipEventElapsedTime(&d->ms[3], d->ev[5], d->ev[6]));
   }
-  const char* hr = (const char*)d->hres.get() + SEQ_BYTES;
+  const char* hr = (const char*)d->hres.payload();
   for (int i = 0; i < mm; ++i) mean_dist[src[i]] = ((const double*)(hr + r_d))[i], flagged[src[i]] = ((const unsigned char*)(hr + r_f))[i];
   return 0;
 }

@@ -187,12 +187,10 @@ extern "C" int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int
   HIPCHK(c->smallbuf.alloc((size_t)4 * c->n_max * 64 + (size_t)c->n_max * c->n_max));
   HIPCHK(c->ticket.alloc(4));
   HIPCHK(hipMemset(c->ticket, 0, 16));
-  HIPCHK(c->h_res_block.alloc(c->res_bytes + 64));  // pinned mirror of res_block
-  memset(c->h_res_block, 0, c->res_bytes + 64);
+  HIPCHK(c->h_res_block.alloc(c->res_bytes));  // pinned mirror of res_block
   HIPCHK(c->h_slot.alloc((size_t)(n_feats_max + 16)));
-  c->h_seq = (volatile unsigned*)((char*)c->h_res_block + ((c->res_bytes + 15) & ~(size_t)15));
-  c->h_flags = (int*)c->h_res_block;
-  c->h_dx = (double*)((char*)c->h_res_block + 16);
+  c->h_flags = (int*)c->h_res_block.payload();
+  c->h_dx = (double*)((char*)c->h_res_block.payload() + 16);
   c->h_chi2 = c->h_dx + c->n_max;
   c->h_accept = (unsigned char*)(c->h_chi2 + n_feats_max);
   // chi2 table
@@ -510,16 +508,15 @@ extern "C" int ovp_cov_propagate(ovp_ctx* c, int new_start, int phi_size, const 
     HIPCHK(hipMemcpyAsync(ad, ah, bytes, hipMemcpyHostToDevice, c->stream));
     const double* dPhi = (const double*)ad;
     const double* dQ = dPhi + (size_t)phi_size * nold;
-    // the verdict comes back through mapped pinned memory (two words 16 bytes behind the point update's sequence word, in the same
-    // 64-byte slack of the result block) and a sequence number of its own: no copy command, no stream synchronisation
-    volatile unsigned* hw = c->h_seq + 4;
-    unsigned* hw_dev = (unsigned*)((char*)c->h_res_block.dev() + ((char*)hw - (char*)c->h_res_block));
-    const unsigned seq = ++c->prop_seq;
+    // the verdict comes back through mapped pinned memory (the auxiliary word of the result block's channel 1) and a sequence
+    // number of its own: no copy command, no stream synchronisation
+    SeqChannel& ch = c->h_res_block.channel(1);
+    const unsigned seq = ch.arm();
     HIPCHK(ovp_launch_propagate_publish(c->P, c->ld, n, new_start, phi_size, (const int*)((char*)ad + o_id), nold, dPhi, dQ, dCPT, dPCP,
-                                        c->flags + 1, hw_dev, seq, c->stream));
-    const int rw = ovp_wait_seq(hw, seq, c->stream);
+                                        c->flags + 1, ch.word_dev(), seq, c->stream));
+    const int rw = ch.wait(c->stream);
     if (rw) return rw;
-    const int neg = (int)hw[1];
+    const int neg = (int)ch.aux();
     if (neg_diag) *neg_diag = neg;
     return neg ? OVP_E_NEGDIAG : 0;
   }
@@ -646,7 +643,7 @@ extern "C" int ovp_cov_initialize(ovp_ctx* c, const double* Hx_init, const doubl
   HIPCHK(ovp_launch_init_m(c->P, ld, n, did, cols, d + oHt, m, dM, s));
   HIPCHK(ovp_launch_init_core(c->P, ld, n, did, cols, d + oHt, k, rup, dM, d + oHi, d + oRk, d + oRes, r_iso > 0.0 ? r_iso : 1.0,
                               chi2_threshold, dLi, dy, dres, s));
-  double* hres = (double*)c->pl_hres;
+  double* hres = (double*)c->pl_hres.payload();
   if (upd) {
     // P+ = P - W W^T goes to the second covariance buffer (a tile reads entries other tiles overwrite)
     HIPCHK(ovp_launch_init_update(c->P, c->P_tmp, ld, n2, dM, m, k, rup, dLi, dy, dres, dres + 4, s));

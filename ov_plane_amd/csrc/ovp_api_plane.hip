@@ -123,7 +123,7 @@ static inline int gen_cam_col(const CalCols& cc, const int* pos, int n_pos, int 
   if (!pos) return id;
   return (id >= 0 && id < n_pos) ? pos[id] : -1;
 }
-// The plane loop's results go to the host as the point update's do (ovp_api_point.hip: k_publish_results): ONE kernel behind the
+// The plane loop's results go to the host as the point update's do (ovp_mailbox.h): ONE kernel behind the
 // loop writes [chi2, decision, ... per plane | dx per plane | consumed features | flags] into mapped pinned memory and then a
 // sequence number the host spins on - instead of four copy commands (a blit kernel of ~4 us each on the stream) and a stream
 // synchronisation (interrupt + wake-up).  It also clears the device flags for the next call (was a fill command).
@@ -152,34 +152,20 @@ __global__ __launch_bounds__(1024) void k_publish_plane_results(const double* __
 
 // A device block -> the start of the pinned result block (c->pl_hres), by a kernel + sequence word instead of a copy command and a
 // stream synchronisation (the entry points with a handful of results: SLAM update, delayed initialisation, initialize, dense update).
-// Falls back to the copy when the block has no room for the sequence word.
-__global__ __launch_bounds__(1024) void k_fetch_block(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, int bytes,
-                                                     volatile unsigned* seq_host, unsigned seq) {
-  const int w = bytes >> 3;
-  const unsigned long long* s8 = reinterpret_cast<const unsigned long long*>(src);
-  unsigned long long* d8 = reinterpret_cast<unsigned long long*>(dst);
-  for (int i = threadIdx.x; i < w; i += 1024) d8[i] = s8[i];
-  for (int i = 8 * w + threadIdx.x; i < bytes; i += 1024) dst[i] = src[i];
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) *seq_host = seq;
-}
+// A source the kernel cannot take (misaligned, 2 GiB) goes by copy + synchronisation; a block the caller reserved no payload for
+// (plane2_buffers) is an error - it would run over the channels' line.
 int ovp_fetch_to_hres(ovp_ctx* c, const void* dsrc, size_t bytes, hipStream_t s) {
-  // the sequence word sits at the start of the block's last whole 64-byte line: a block that reaches it would have its own last
-  // bytes overwritten by the word, so it takes the copy (plane2_buffers keeps the capacity a multiple of 64: the last line is whole)
-  const size_t o_seq = c->pl_hres.capacity() >= 64 ? c->pl_hres.capacity() - 64 : 0;
-  if (!c->pl_hres.dev() || bytes > o_seq || (((size_t)dsrc) & 7) || bytes > (size_t)0x7fffffff) {
-    HIPCHK(hipMemcpyAsync(c->pl_hres, dsrc, bytes, hipMemcpyDeviceToHost, s));
+  Mailbox& m = c->pl_hres;
+  if (bytes > m.payload_capacity()) return OVP_E_CAPACITY;
+  if ((((size_t)dsrc) & 7) || bytes > (size_t)0x7fffffff) {
+    HIPCHK(hipMemcpyAsync(m.payload(), dsrc, bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
   }
-  volatile unsigned* hseq = (volatile unsigned*)((char*)c->pl_hres + o_seq);
-  *hseq = 0u;  // (payload of an earlier, larger block may have left any value there, the next sequence number included)
-  const unsigned seq = ++c->pl_pub_seq;
-  hipLaunchKernelGGL(k_fetch_block, dim3(1), dim3(1024), 0, s, (const unsigned char*)dsrc, (unsigned char*)c->pl_hres.dev(), (int)bytes,
-                     (volatile unsigned*)((char*)c->pl_hres.dev() + o_seq), seq);
-  HIPCHK(hipGetLastError());
-  return ovp_wait_seq(hseq, seq, s);
+  SeqChannel& ch = m.channel(0);
+  const unsigned seq = ch.arm();
+  HIPCHK(ovp_launch_publish_block(dsrc, m.dev(m.payload()), bytes, ch.word_dev(), seq, 0, s));
+  return ch.wait(s);
 }
 static int ensure_pl_used(ovp_ctx* c) {
   HIPCHK(c->pl_used.alloc((size_t)c->f_max + 16));
@@ -206,10 +192,11 @@ int plane2_buffers(ovp_ctx* c, size_t stage_bytes, size_t res_bytes) {
     HIPCHK(c->pl_hstage.reserve(stage_bytes, 4096));
     HIPCHK(c->pl_dstage.reserve(stage_bytes, 4096));
   }
-  if (res_bytes > c->pl_hres.capacity()) {
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(c->pl_hres.reserve(StageLayout::al(res_bytes + 4096), 0));  // (a multiple of 64: ovp_fetch_to_hres's sequence word ends the block)
-    memset(c->pl_hres, 0, c->pl_hres.capacity());
+  // (res_bytes is the callers' size of the whole result block, the line of the sequence word included)
+  const size_t payload = res_bytes > Mailbox::LINE ? res_bytes - Mailbox::LINE : 0;
+  if (payload > c->pl_hres.payload_capacity()) {
+    HIPCHK(hipStreamSynchronize(c->stream));  // a kernel of an earlier call may still write the old block
+    HIPCHK(c->pl_hres.reserve(payload, 4096));
   }
   return 0;
 }
@@ -1216,26 +1203,24 @@ static int plane_cov_product(ovp_ctx* c, const PlaneLoopView& v, size_t tstride,
 }
 
 // ---- results: one pinned block, one wait ----
-// [chi2, decision, .. per plane | dx per plane | consumed features], and behind `used`, each on a 64-byte line of its own: the
-// flags, the sequence word
-struct PlaneResBlock { double *res, *dx; unsigned char* used; char* flags; volatile unsigned* seq; };
+// [chi2, decision, .. per plane | dx per plane | consumed features], and behind `used`, on a 64-byte line of their own, the flags:
+// the payload of c->pl_hres, posted on its channel 0
+struct PlaneResBlock { double *res, *dx; unsigned char* used; char* flags; };
 static PlaneResBlock plane_res_block(const ovp_ctx* c, int NP, int n_extra) {
   PlaneResBlock b;
-  b.res = (double*)c->pl_hres;
+  b.res = (double*)c->pl_hres.payload();
   b.dx = b.res + 4 * (size_t)NP + n_extra;
   b.used = (unsigned char*)(b.dx + (size_t)c->n * NP);
   b.flags = (char*)b.used + StageLayout::al((size_t)c->n_feats);
-  b.seq = (volatile unsigned*)(b.flags + 64);
   return b;
 }
-static int plane_publish(ovp_ctx* c, const PlaneResBlock& b, int NP, int n_extra, bool want_dx, unsigned* seq_out) {
-  *b.seq = 0u;  // (its offset depends on NP, n and F: an earlier call's payload may have left the next sequence number there)
-  const unsigned seq = *seq_out = ++c->pl_pub_seq;
-  char* dbase = (char*)c->pl_hres.dev();
-  auto dev_of = [&](const void* hp) { return dbase + ((const char*)hp - (const char*)c->pl_hres); };
+static int plane_publish(ovp_ctx* c, const PlaneResBlock& b, int NP, int n_extra, bool want_dx) {
+  const Mailbox& m = c->pl_hres;
+  SeqChannel& ch = c->pl_hres.channel(0);
+  const unsigned seq = ch.arm();
   hipLaunchKernelGGL(k_publish_plane_results, dim3(1), dim3(1024), 0, c->stream, c->pl_res, 4 * NP + n_extra, c->pl_dx, want_dx ? c->n * NP : 0,
-                     c->pl_used, c->n_feats, c->flags, (double*)dev_of(b.res), (double*)dev_of(b.dx), (unsigned char*)dev_of(b.used),
-                     (int*)dev_of(b.flags), (volatile unsigned*)dev_of((const void*)b.seq), seq);
+                     c->pl_used, c->n_feats, c->flags, (double*)m.dev(b.res), (double*)m.dev(b.dx), (unsigned char*)m.dev(b.used),
+                     (int*)m.dev(b.flags), (volatile unsigned*)ch.word_dev(), seq);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1393,11 +1378,10 @@ static int plane_loop(ovp_ctx* c, const ovp_update_opts* o_in, const ovp_plane_b
   if (c->pl_ktimer) HIPCHK(hipEventRecord(c->pl_ev_loop[1], s));
   const int n_extra = v.init ? v.init->extra : 0;
   const PlaneResBlock blk = plane_res_block(c, NP, n_extra);
-  unsigned seq = 0;
-  rc = plane_publish(c, blk, NP, n_extra, out.dx_planes != nullptr, &seq);
+  rc = plane_publish(c, blk, NP, n_extra, out.dx_planes != nullptr);
   if (rc) return rc;
   const double t_enq = host_now_ms();
-  rc = ovp_wait_seq(blk.seq, seq, s);
+  rc = c->pl_hres.channel(0).wait(s);
   if (rc) return rc;
   memcpy(c->h_flags, blk.flags, sizeof(int) * 4);
   plane_account(c, v.t_entry, pre.t_first, t_enq, NJ);
@@ -1724,7 +1708,7 @@ extern "C" int ovp_plane_init_general(ovp_ctx* c, const ovp_update_opts* o, cons
     return rc;
   }
   // ---- the accepted planes, numbered as the device numbered them ----
-  const double* extra = (const double*)c->pl_hres + 4 * (size_t)NP;  // [d cp | corrections between the new planes]
+  const double* extra = (const double*)c->pl_hres.payload() + 4 * (size_t)NP;  // [d cp | corrections between the new planes]
   int q = 0;
   std::vector<int> nid((size_t)NP, -1);
   for (int pl = 0; pl < NP; ++pl)

@@ -2,18 +2,8 @@
 // (update/UpdaterMSCKF.cpp:671-814, state/StateHelper.cpp:121-202) and StateHelper::EKFUpdate with a dense host H.
 #include "ovp_ctx.h"
 
-// Results go to the host without a copy command: the last kernel of an update writes the result block into mapped pinned
-// memory and then a sequence number; ovp_msckf_fetch_results spins on that word (a hipMemcpyAsync + hipStreamSynchronize
-// pair costs ~25 us of launch, blit and wake-up latency per update, this ~5).
-__global__ __launch_bounds__(1024) void k_publish_results(unsigned long long* __restrict__ src,
-                                                         unsigned long long* __restrict__ dst, int words,
-                                                         volatile unsigned* seq_host, unsigned seq) {
-  for (int i = threadIdx.x; i < words; i += 1024) dst[i] = src[i];
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) *seq_host = seq;
-  if (threadIdx.x < 2) src[threadIdx.x] = 0ull;  // the four flag words, cleared for the next update
-}
+// Results go to the host without a copy command: the last kernel of an update writes the result block into the pinned mirror
+// (c->h_res_block, a Mailbox) and then the sequence number of its channel 0; ovp_msckf_fetch_results waits on that channel.
 
 // ---- the update step ---------------------------------------------------------------------------
 // States above the tile factorization's limit (N > 288: e.g. 30 clones plus 50 landmarks).  A measurement batch never
@@ -160,10 +150,10 @@ int ekf_from_gram(ovp_ctx* c, bool chol_p_done_on_stream2, bool publish) {
     if (publish) {
       // the last block of the dx kernel also publishes [flags | dx] to the pinned host block (no separate launch)
       const int words = (int)((16 + sizeof(double) * (size_t)n + 7) / 8);
-      c->pub_seq = ++c->seq;
-      HIPCHK(ovp_launch_dx_rows_boost(c->P, n, ld, b, c->dx, c->flags + 1, c->ticket, c->res_block, c->h_res_block.dev(), words,
-                                      (char*)c->h_res_block.dev() + ((char*)c->h_seq - (char*)c->h_res_block), c->pub_seq, boost_ptr,
-                                      boost_n, c->flags, c->stream));
+      SeqChannel& ch = c->h_res_block.channel(0);
+      const unsigned seq = ch.arm();
+      HIPCHK(ovp_launch_dx_rows_boost(c->P, n, ld, b, c->dx, c->flags + 1, c->ticket, c->res_block, c->h_res_block.dev(c->h_flags), words,
+                                      ch.word_dev(), seq, boost_ptr, boost_n, c->flags, c->stream));
       c->pub_pending = true;
     } else {
       HIPCHK(ovp_launch_dx_rows_boost(c->P, n, ld, b, c->dx, c->flags + 1, nullptr, nullptr, nullptr, 0, nullptr, 0u, boost_ptr, boost_n,
@@ -176,9 +166,10 @@ int ekf_from_gram(ovp_ctx* c, bool chol_p_done_on_stream2, bool publish) {
     if (rc) return rc;
     if (publish) {
       const int words = (int)((16 + sizeof(double) * (size_t)n + 7) / 8);
-      c->pub_seq = ++c->seq;
-      HIPCHK(ovp_launch_dx_rows(c->P, n, ld, b, c->dx, c->flags + 1, c->ticket, c->res_block, c->h_res_block.dev(), words,
-                                (char*)c->h_res_block.dev() + ((char*)c->h_seq - (char*)c->h_res_block), c->pub_seq, c->stream));
+      SeqChannel& ch = c->h_res_block.channel(0);
+      const unsigned seq = ch.arm();
+      HIPCHK(ovp_launch_dx_rows(c->P, n, ld, b, c->dx, c->flags + 1, c->ticket, c->res_block, c->h_res_block.dev(c->h_flags), words,
+                                ch.word_dev(), seq, c->stream));
       c->pub_pending = true;
     } else {
       HIPCHK(ovp_launch_dx_rows(c->P, n, ld, b, c->dx, c->flags + 1, nullptr, nullptr, nullptr, 0, nullptr, 0u, c->stream));
@@ -280,8 +271,8 @@ int fill_feat_params(ovp_ctx* c, const ovp_update_opts* o) {
   fp.ldg = c->ldg;
   fp.rec = c->rec;
   // per-feature results straight into the pinned host block (same layout as res_block): they cross PCIe while K1 runs
-  fp.chi2 = (double*)((char*)c->h_res_block.dev() + ((char*)c->chi2 - (char*)c->res_block));
-  fp.accept = (unsigned char*)c->h_res_block.dev() + ((char*)c->accept - (char*)c->res_block);
+  fp.chi2 = (double*)c->h_res_block.dev(c->h_chi2);
+  fp.accept = (unsigned char*)c->h_res_block.dev(c->h_accept);
   fp.dbg_cycles = c->dbg_cycles;
   fp.slot = nullptr;
   fp.n_out = 0;
@@ -615,17 +606,15 @@ extern "C" int ovp_msckf_fetch_results(ovp_ctx* c, double* dx_host, uint8_t* acc
   {
     // [flags | dx] are published by the last block of the dx kernel (or, on the fallback path, by a publish kernel);
     // chi2 / accept were written into the pinned block by K1 itself
-    unsigned seq = c->pub_seq;
+    SeqChannel& ch = c->h_res_block.channel(0);
     if (!c->pub_pending) {
-      const int words = (int)((16 + sizeof(double) * (size_t)n + 7) / 8);
-      seq = ++c->seq;
-      hipLaunchKernelGGL(k_publish_results, dim3(1), dim3(1024), 0, c->stream, (unsigned long long*)c->res_block,
-                         (unsigned long long*)c->h_res_block.dev(), words, (volatile unsigned*)((char*)c->h_res_block.dev() +
-                         ((char*)c->h_seq - (char*)c->h_res_block)), seq);
-      HIPCHK(hipGetLastError());
+      const size_t words = (16 + sizeof(double) * (size_t)n + 7) / 8;
+      const unsigned seq = ch.arm();
+      // (also clears the four flag words of the device block for the next update)
+      HIPCHK(ovp_launch_publish_block(c->res_block, c->h_res_block.dev(c->h_flags), 8 * words, ch.word_dev(), seq, 2, c->stream));
     }
     c->pub_pending = false;
-    const int rw = ovp_wait_seq(c->h_seq, seq, c->stream);
+    const int rw = ch.wait(c->stream);
     if (rw) return rw;
   }
   if (c->h_flags[0]) {
@@ -728,7 +717,7 @@ extern "C" int ovp_ekf_update(ovp_ctx* c, const double* H_host, int rows, int co
     HIPCHK(ovp_launch_init_core(c->P, c->ld, n, did, cols, d + oHt, 0, rows, dM, d + oRes /* unused: k = 0 */, d + oRes, d + oRes, 1.0,
                                 1e300, dLi, dy, dres, s));
     HIPCHK(ovp_launch_init_update(c->P, c->P_tmp, c->ld, n, dM, rows, 0, rows, dLi, dy, dres, dres + 4, s));
-    double* hres = (double*)c->pl_hres;
+    double* hres = (double*)c->pl_hres.payload();
     {
       const int rf = ovp_fetch_to_hres(c, dres, sizeof(double) * (4 + (size_t)n), s);
       if (rf) return rf;

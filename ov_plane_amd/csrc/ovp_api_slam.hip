@@ -297,7 +297,7 @@ static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam
     HIPCHK(ovp_launch_slam_gate(&sp, L, ovp_slam_gate_lds(rows_max, cols_max, h_in_lds), s));
   }
   const int* dgid = (const int*)(d + o_gi);
-  char* hres = (char*)c->pl_hres;
+  char* hres = (char*)c->pl_hres.payload();
   double* hres_d = (double*)hres;
   char* hl = hres + res_doubles * sizeof(double);  // [chi2 L | status L]
   auto finish_landmarks = [&]() {
@@ -635,7 +635,7 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, int L, i
     if (with_planes) HIPCHK(ovp_launch_dinit_rows_pl(&dp, &pp, 64, s));
     else HIPCHK(ovp_launch_dinit_rows(&dp, 64, s));
   }
-  double* hres = (double*)c->pl_hres;
+  double* hres = (double*)c->pl_hres.payload();
   {
     const int rf = ovp_fetch_to_hres(c, dres0, sizeof(double) * res_doubles * NA, s);
     if (rf) return rf;

@@ -9,6 +9,7 @@
 //   ovp_api_slam.hip   SLAM landmarks (ovp_slam_update, ovp_slam_delayed_init), triangulation
 //   ovp_api_general.hip general point features (any camera, long tracks): camera tables, gate + pending pair, triangulation
 //   k_plane_detect.hip plane detection from the tracked features: its kernels and its entry points
+// Results reach the host through ovp_mailbox.h (Mailbox / SeqChannel; the copy-and-post kernel is k_publish.hip).
 #pragma once
 #include "ovplane_hip.h"
 
@@ -25,6 +26,7 @@
 #include <vector>
 
 #include "ovp_buf.h"
+#include "ovp_mailbox.h"
 #include "ovp_kernels.h"
 #include "k_chol2.h"
 #include "k_plane2.h"
@@ -254,8 +256,7 @@ struct ovp_ctx {
   hipEvent_t ev_subtab = nullptr;     // behind the upload of pl_sub_htab (the pinned block is rewritten by the next call)
   PinnedBuf<void> pl_hstage;          // pinned host / device staging of the per-call tables
   DevBuf<void> pl_dstage;
-  PinnedBuf<void> pl_hres{true};      // pinned host copy of the plane results (mapped: the plane loop publishes into it from a kernel)
-  unsigned pl_pub_seq = 0;            // sequence number of the plane loop's last publication
+  Mailbox pl_hres;                    // the plane results and the small fetches (ovp_fetch_to_hres): payload from byte 0, channel 0
   // one device block + one pinned staging block each for the pose tables and for the feature batch (a single copy per upload)
   DevBuf<void> state_block, batch_block;
   PinnedBuf<void> h_state_stage, h_batch_stage;
@@ -273,16 +274,13 @@ struct ovp_ctx {
   int sub_ns = 0;
   std::vector<int> h_clone_id;  // host copy of the clone columns (ovp_state_upload)
   DevBuf<double> sub_buf;
-  // pinned host staging: views into h_res_block
+  // pinned host staging: views into h_res_block's payload
   double *h_dx = nullptr, *h_chi2 = nullptr;
   unsigned char* h_accept = nullptr;
   int* h_flags = nullptr;
   DevBuf<void> res_block;                             // [flags | dx | chi2 | accept]
-  PinnedBuf<void> h_res_block{true};                  // ... its pinned mirror (mapped)
-  volatile unsigned* h_seq = nullptr;                 // sequence word behind it (written last by k_publish_results), view into h_res_block
-  unsigned prop_seq = 0;                              // ovp_cov_propagate's own sequence (words [4], [5] behind h_seq: seq, verdict)
-  unsigned seq = 0, pub_seq = 0;
-  bool pub_pending = false;      // the running update publishes its results itself (k_dx_rows)
+  Mailbox h_res_block;                                // ... its pinned mirror; channel 0: the point update, channel 1: ovp_cov_propagate
+  bool pub_pending = false;      // channel 0 is armed and a kernel of the running update will post it (k_dx_rows)
   bool need_join = false;     // chol(P) / K2 of the current update finish on stream2 (ev_join) rather than on the main stream
   DevBuf<unsigned> ticket;       // block counter of the publishing kernel
   std::vector<int> h_nmeas;                           // host copy of n_meas of the current batch (row count of `info`)
@@ -370,18 +368,6 @@ static inline double host_now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-
-// Wait for the sequence number a kernel on stream s writes into mapped pinned memory behind its payload.  Error path: after two
-// seconds one stream synchronisation surfaces a fault instead of spinning forever, OVP_E_STATE when the word still is not there.
-static inline int ovp_wait_seq(const volatile unsigned* word, unsigned seq, hipStream_t s) {
-  const auto t0 = std::chrono::steady_clock::now();
-  for (unsigned spins = 0; __atomic_load_n((const unsigned*)word, __ATOMIC_ACQUIRE) != seq; __builtin_ia32_pause())
-    if ((++spins & 0xFFFu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-      HIPCHK(hipStreamSynchronize(s));
-      return __atomic_load_n((const unsigned*)word, __ATOMIC_ACQUIRE) != seq ? OVP_E_STATE : 0;
-    }
-  return 0;
-}
 
 // ---- shared between the entry-point files ------------------------------------------------------------------------------------
 void quat_2_rot(const double q[4], double R[9]);  // JPL quaternion -> row-major rotation (ovp_api_ctx.hip)

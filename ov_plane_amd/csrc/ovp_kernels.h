@@ -221,6 +221,10 @@ struct PlaneFrontJob {
 }  // namespace ovp
 
 extern "C" {
+// k_publish.hip: `bytes` of the device block src -> dst (mapped pinned memory), then seq into *word; src, dst 8-byte aligned;
+// clear8 leading 8-byte words of src are zeroed behind the post
+hipError_t ovp_launch_publish_block(const void* src, void* dst, size_t bytes, unsigned* word, unsigned seq, int clear8,
+                                    hipStream_t stream);
 // k_planefit.hip: the device sequence of ovp_plane_fit_refine, enqueued on `stream`; the hypothesis sets of one plane's RANSAC
 // (PlaneFitting.cpp:104-141; dst [200][5], -1 = the call fails at that iteration)
 hipError_t ovp_launch_planefront(const ovp::PlaneFrontJob* j, hipStream_t stream);
