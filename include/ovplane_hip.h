@@ -680,8 +680,15 @@ int ovp_plane_detect_triangulate(ovp_ctx *ctx, int n, const int64_t *ids, const 
                                  const double *p_CinG, uint8_t *has_est, double *p_FinG);
 /* Second call of a frame: TrackPlane.cpp:728-1095 (triangle normals, per-feature normal history and avg_norm, pairwise matching,
  * greedy merge, spatial filter, pruning).  tris [3*n_tris] index the vertices of the preceding ovp_plane_detect_triangulate;
- * tris = NULL: the library triangulates them itself (ovp_delaunay). */
+ * tris = NULL: the library triangulates them itself (ovp_delaunay; with ovp_plane_detector_set_device_delaunay on, the triangles
+ * the first call's device triangulation left). */
 int ovp_plane_detect_planes(ovp_ctx *ctx, int n_tris, const int32_t *tris);
+/* on != 0: ovp_plane_detect_triangulate also triangulates the frame's vertices on the device (k_det_delaunay behind
+ * k_det_triangulate: the vertices compacted on the device, pixel positions from `uv`, the triangles in the same result block and
+ * the same wait), and ovp_plane_detect_planes(ctx, 0, NULL) uses those triangles where it otherwise calls the host triangulation
+ * - the same triangles, so the same planes.  A frame whose device triangulation reported an overflow of its table takes the
+ * host triangulation as before; explicit tris are used as before.  Default off; OVP_E_STATE without a detector. */
+int ovp_plane_detector_set_device_delaunay(ovp_ctx *ctx, int on);
 /* TrackPlane::get_feature2plane (track_plane/TrackPlane.h:140-143): ascending feature id; *n = entries (also when cap is smaller) */
 int ovp_plane_detector_map(ovp_ctx *ctx, int64_t *ids, int64_t *planes, int cap, int *n);
 /* TrackPlane::get_plane2oldplane (track_plane/TrackPlane.h:145-149): the merge history of the planes in the map as (surviving id,
@@ -700,11 +707,19 @@ int ovp_plane_spatial_filter(ovp_ctx *ctx, int n_planes, const int *feat_start, 
  * is left out, a zero-area triangle of a point exactly on a hull edge is dropped); *n_tris = count (OVP_E_CAPACITY above cap;
  * 2n always suffices).  Stands where the reference calls CDT (TrackPlane.cpp:717-723). */
 int ovp_delaunay(int n, const float *xy, int32_t *tris, int cap, int *n_tris);
+/* The same triangulation on the device (k_det_delaunay: one workgroup, the same algorithm, insertion order and predicates - the
+ * triangles of ovp_delaunay, bit for bit): one upload, one launch, one publication.  Needs a context, no detector.
+ * n > OVP_DET_MAX_POINTS: OVP_E_CAPACITY, nothing enqueued; n < 3: no triangles, no launch.  No fallback to the host: an overflow
+ * of the kernel's triangle table (possible only after inconsistent predicate signs) is OVP_E_CAPACITY. */
+int ovp_delaunay_device(ovp_ctx *ctx, int n, const float *xy, int32_t *tris, int cap, int *n_tris);
 /* tests: what = "feat": out = [count, valid, p_FinG(3), n_norms, avg_norm(3), normals(3*n_norms)] of feature id; "filter": out =
  * [id, plane, mean of the neighbour distances, z-score flag] per point of every plane the last frame's filter looked at; "timer": id != 0
  * puts events around the kernels (and a stream synchronisation behind each publication) from the next frame on, "time": GPU
  * milliseconds of the last timed frame's kernels [triangulate, normals, match, filter] ([3] also behind a timed
- * ovp_plane_spatial_filter).  Returns the number of doubles (or < 0). */
+ * ovp_plane_spatial_filter); "time_delaunay": GPU milliseconds of k_det_delaunay [in the last timed frame, in the last timed
+ * ovp_delaunay_device of this context]; "tris": [source of the last ovp_plane_detect_planes' triangles: 0 the caller's, 1 the host
+ * triangulation, 2 the device's; device triangulation on; of the last frame's device triangulation: overflow, vertices, most
+ * table slots in use, largest cavity].  Returns the number of doubles (or < 0). */
 long ovp_plane_detector_debug(ovp_ctx *ctx, const char *what, int64_t id, double *out, long cap);
 
 /* ---- diagnostics ---------------------------------------------------------------------------- */

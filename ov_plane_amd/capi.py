@@ -206,7 +206,7 @@ EXPORTS = [
     "ovp_slam_delayed_init_planes", "ovp_msckf_plane_update_general", "ovp_plane_fit_refine",
     "ovp_trackplane_defaults", "ovp_plane_detector_create", "ovp_plane_detector_destroy", "ovp_plane_detector_reset",
     "ovp_plane_detect_triangulate", "ovp_plane_detect_planes", "ovp_plane_detector_map", "ovp_delaunay", "ovp_plane_detector_debug", "ovp_plane_spatial_filter", "ovp_plane_detector_merges",
-    "ovp_plane_init_general",
+    "ovp_plane_init_general", "ovp_delaunay_device", "ovp_plane_detector_set_device_delaunay",
 ]
 
 
@@ -311,6 +311,8 @@ def lib():
         L.ovp_delaunay.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.ovp_plane_spatial_filter.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
         L.ovp_plane_detector_merges.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.ovp_delaunay_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.ovp_plane_detector_set_device_delaunay.argtypes = [C.c_void_p, C.c_int]
         L.ovp_plane_detector_debug.restype = C.c_long
         L.ovp_plane_detector_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_long]
         _LIB = L
@@ -343,6 +345,16 @@ def delaunay(xy):
     return tris[:nt.value].copy()
 
 
+def delaunay_device(ctx, xy):
+    """ovp_delaunay_device: the triangles of delaunay(xy), computed by the device kernel of the context (no fallback to the host)."""
+    xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+    cap = max(2 * len(xy), 1)
+    tris = np.zeros((cap, 3), dtype=np.int32)
+    nt = C.c_int(0)
+    _chk(lib().ovp_delaunay_device(ctx.handle, len(xy), xy.ctypes.data, tris.ctypes.data, cap, C.byref(nt)), "ovp_delaunay_device")
+    return tris[:nt.value].copy()
+
+
 class PlaneDetector:
     """The plane detector of a context (ovp_plane_detector_*): TrackPlane::perform_plane_detection_monocular on the device.
     feed() is one frame; feature2plane() the reference's get_feature2plane()."""
@@ -357,6 +369,10 @@ class PlaneDetector:
 
     def reset(self):
         _chk(lib().ovp_plane_detector_reset(self.ctx.handle), "ovp_plane_detector_reset")
+
+    def set_device_delaunay(self, on=True):
+        """the frame's triangles come from the device triangulation behind the first call (default off: the host's)"""
+        _chk(lib().ovp_plane_detector_set_device_delaunay(self.ctx.handle, 1 if on else 0), "ovp_plane_detector_set_device_delaunay")
 
     def triangulate(self, ids, uv, uv_norm, R_GtoC, p_CinG):
         """first call of a frame -> (has_est [n] bool, p_FinG [n, 3])"""
@@ -429,6 +445,17 @@ class PlaneDetector:
     def kernel_ms(self):
         """GPU milliseconds of the last timed frame's kernels [triangulate, normals, match, filter]"""
         return self._debug(b"time", 0, 4)
+
+    def delaunay_ms(self):
+        """GPU milliseconds of the Delaunay kernel [in the last timed frame, in the last timed delaunay_device of the context]"""
+        return self._debug(b"time_delaunay", 0, 2)
+
+    def tris_info(self):
+        """the last planes() call's triangles: dict(source = "caller" / "host" / "device", device_on, and of the frame's device
+        triangulation overflow, vertices, peak_slots, max_cavity)"""
+        o = self._debug(b"tris", 0, 6)
+        return dict(source=("caller", "host", "device")[int(o[0])], device_on=bool(o[1]), overflow=int(o[2]), vertices=int(o[3]),
+                    peak_slots=int(o[4]), max_cavity=int(o[5]))
 
     def spatial_filter(self, planes, filter_num_feat=None, filter_z_thresh=None):
         """ovp_plane_spatial_filter on a list of [n_k, 3] point arrays -> list of (mean_dist [n_k], flagged [n_k] bool)"""

@@ -167,7 +167,7 @@ def run(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, max_feats=
 
 def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, planes=0, plane_min_feat=6, sigma_c=0.01,
                 max_slam=0, feat_rep_slam=0, min_meas=3, out_dir=None, zupt=None, track_planes=True, forget_planes_at=None,
-                detect_planes=False, detect_opts=None, feed_plane_tracks=None):
+                detect_planes=False, detect_opts=None, feed_plane_tracks=None, device_delaunay=False):
     """Closed loop through hostlib.Session, frame by frame, with the tracker-side bookkeeping of core/VioManager.cpp:360-506:
     a track is an MSCKF feature once it is lost or reaches back to the clone about to be marginalised; a track that spans the
     whole window (more than max_clone_size measurements) becomes a SLAM landmark while there is room (max_slam), and from then
@@ -182,6 +182,7 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
     frame with all tracked points; the simulator's plane labels are NOT handed to the session (detect_opts: capi.TrackPlaneOpts).
     feed_plane_tracks (default: detect_planes) hands the tracked points over whether or not the option is on - with it off they
     are ignored.  The result then also holds detected_per_frame [K, 2] = (features of the step on a detected plane, entries of the map).
+    device_delaunay: StateOptions::gpu_device_delaunay - with detect_planes, the detector triangulates on the device.
     zupt: dict of Session.enable_zupt keywords (or {}) = VioManagerOptions::try_zupt: a frame at which the platform is found
     standing still gets a zero-velocity update instead of a clone (core/VioManager.cpp:311-331) and its measurements are dropped."""
     from . import hostlib
@@ -198,6 +199,8 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
                           sigma_c=sigma_c, max_slam=max_slam, feat_rep_slam=feat_rep_slam, cam_dt=1.0 / sim.params["sim_freq_cam"])
     if zupt is not None:
         ses.enable_zupt(po, **zupt)
+    if device_delaunay:
+        ses.set_device_delaunay(True)
     if detect_planes:
         ses.enable_plane_detection(detect_opts)
     ses.feed_imu(imu)

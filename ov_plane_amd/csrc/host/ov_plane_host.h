@@ -79,6 +79,9 @@ struct StateOptions {
   // tracks handed over by ovph_session_feed_plane_tracks) in place of the map the caller passes.  In the reference this is
   // TrackPlaneOptions::track_planes of the front end.
   bool gpu_plane_detection = false;
+  // gpu_plane_detection: the Delaunay triangulation of the frame's points runs on the device behind the detector's first call
+  // (ovp_plane_detector_set_device_delaunay) instead of on the host between its two calls - the same triangles.  Not in the reference.
+  bool gpu_device_delaunay = false;
   // UpdaterMSCKF::update: on-plane features the device batch cannot carry (another camera, more than OVP_MAX_MEAS views) stay in the
   // plane loop through ovp_msckf_plane_update_general instead of going to the point update without their plane constraint - for
   // planes whose estimate does not come from this frame's fit (in the state, or handed over in _plane_estimates_cp_inG); a frame with

@@ -186,6 +186,15 @@ extern "C" int ovph_session_enable_plane_detection(void *h, const ovp_trackplane
     return -31;
   }
   s->state->_options.gpu_plane_detection = true;
+  if (s->state->_options.gpu_device_delaunay && s->track->set_device_delaunay(true)) return -31;
+  return 0;
+}
+
+// StateOptions::gpu_device_delaunay: the detector (now, or when ovph_session_enable_plane_detection makes it) triangulates on the device
+extern "C" int ovph_session_set_device_delaunay(void *h, int on) {
+  auto *s = static_cast<Session *>(h);
+  s->state->_options.gpu_device_delaunay = on != 0;
+  if (s->track && s->track->set_device_delaunay(on != 0)) return -31;
   return 0;
 }
 

@@ -2,7 +2,8 @@
 // perform_plane_detection_monocular (track_plane/TrackPlane.cpp:580-1121) on the tracked points of one frame - no images - and
 // get_feature2plane() the reference's accessor.  The per-feature history and the plane maps live in the detector of the device
 // context (ovp_plane_detector_*); this class hands it the frame, triangulates the points that have a position (Delaunay,
-// ov_plane_delaunay.h, where the reference calls CDT) and reads the map back.
+// ov_plane_delaunay.h, where the reference calls CDT) and reads the map back.  With set_device_delaunay the triangulation is the
+// detector's own, on the device behind its first call: no has_est round trip and no triangles to hand over.
 #pragma once
 #include <array>
 #include <cstdint>
@@ -25,6 +26,13 @@ class TrackPlane {
   TrackPlane(const TrackPlane &) = delete;
   TrackPlane &operator=(const TrackPlane &) = delete;
   bool ok() const { return _rc == 0; }
+  // StateOptions::gpu_device_delaunay
+  int set_device_delaunay(bool on) {
+    if (_rc) return _rc;
+    const int rc = ovp_plane_detector_set_device_delaunay(_gpu, on ? 1 : 0);
+    if (rc == 0) _device_delaunay = on;
+    return rc;
+  }
 
   // the camera pose of the newest clone (hist_state and hist_calib of the reference, TrackPlane.cpp:612-624, already combined):
   // R_GtoC row-major, p_CinG
@@ -46,6 +54,10 @@ class TrackPlane {
     if (n == 0) return 0;
     std::vector<int64_t> id64(ids.begin(), ids.end());
     std::vector<double> uvn(uv_norm.begin(), uv_norm.end());  // (undistort_cv returns f32: the values stay f32-rounded)
+    if (_device_delaunay) {
+      const int rc = ovp_plane_detect_triangulate(_gpu, n, id64.data(), uv.data(), uvn.data(), _R, _p, nullptr, nullptr);
+      return rc ? rc : ovp_plane_detect_planes(_gpu, 0, nullptr);
+    }
     std::vector<uint8_t> has(n);
     int rc = ovp_plane_detect_triangulate(_gpu, n, id64.data(), uv.data(), uvn.data(), _R, _p, has.data(), nullptr);
     if (rc) return rc;
@@ -82,7 +94,7 @@ class TrackPlane {
  private:
   ovp_ctx *_gpu;
   int _rc = 0;
-  bool _have_pose = false;
+  bool _have_pose = false, _device_delaunay = false;
   double _pose_time = 0.0, _R[9], _p[3];
 };
 

@@ -1,6 +1,8 @@
 // Plane detection from a frame's tracked features: TrackPlane::perform_plane_detection_monocular (track_plane/TrackPlane.cpp:
-// 580-1121) restated.  The data-parallel pieces are the kernels below; the Delaunay triangulation (host/ov_plane_delaunay.h), the greedy
-// merge and the pruning are sequential by definition and stay on the host, in the entry points at the end of this file.
+// 580-1121) restated.  The data-parallel pieces are the kernels below; the greedy merge and the pruning are sequential by
+// definition and stay on the host, in the entry points at the end of this file.  The Delaunay triangulation runs on the host
+// (host/ov_plane_delaunay.h) or, with ovp_plane_detector_set_device_delaunay, on the device behind k_det_triangulate
+// (k_det_delaunay, k_delaunay.hip: the same algorithm, the same triangles).
 //   k_det_triangulate     one thread per tracked point: accumulate the linear triangulation system, solve and gate it (:632-681)
 //   k_det_tri_normals     one thread per triangle: side test, unit normal, sign towards the camera (:733-776)
 //   k_det_vertex_norms    one thread per vertex: its triangles' normals into its history, in triangle order, and avg_norm (:778-806,
@@ -11,6 +13,7 @@
 // No atomics, every order fixed: two runs give the same bits.
 #include "ovp_ctx.h"
 #include "host/ov_plane_delaunay.h"
+#include "k_delaunay.h"
 
 #include <map>
 #include <set>
@@ -323,6 +326,7 @@ struct Detector {
   size_t stage_cap = 0, res_cap = 0;
   hipEvent_t ev[8] = {};
   float ms[4] = {0, 0, 0, 0};
+  float ms_delaunay[2] = {0, 0};  // k_det_delaunay of the last timed frame / of the last timed ovp_delaunay_device
   bool timed = false;  // ovp_plane_detector_debug "timer": events around the kernels, read behind a stream synchronisation
   // host state of TrackPlane
   std::map<int64_t, int> slot_of;
@@ -337,6 +341,11 @@ struct Detector {
   std::vector<float> v_px;
   double pose[12];
   std::vector<double> filt_dbg;
+  // ovp_plane_detector_set_device_delaunay: the frame's triangles as the first call's kernel left them
+  bool dev_delaunay = false, dev_tris_ok = false;
+  std::vector<int> dev_tris;
+  int dev_hdr[OVP_DL_HDR] = {};
+  int tri_source = 0;  // of the last ovp_plane_detect_planes: 0 the caller's, 1 ovp_delaunay_host, 2 the device's
   DetState st() const { return DetState{A.get(), b.get(), p.get(), count.get(), valid.get(), ring.get(), avg.get(), ring_n.get()}; }
   ~Detector() {
     for (hipEvent_t e : ev)
@@ -350,7 +359,20 @@ struct Detector {
     plane2old.clear();
     currplaneid = 0;
     have_frame = false;
+    dev_tris_ok = false;
     v_id.clear(), v_slot.clear(), v_px.clear(), filt_dbg.clear();
+  }
+};
+
+// ovp_delaunay_device: staging, result block and mailbox of its own (a context without a detector has none), made on first use
+struct DelaunayIo {
+  PinnedBuf<void> hstage;
+  DevBuf<void> dstage, dres;
+  Mailbox hres;
+  hipEvent_t ev[2] = {};
+  ~DelaunayIo() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
   }
 };
 
@@ -390,8 +412,11 @@ extern "C" int ovp_plane_detector_create(ovp_ctx* c, const ovp_trackplane_opts* 
   HIPCHK(d->valid.alloc(S));
   HIPCHK(d->ring_n.alloc(S));
   // the largest of the three staged tables / result blocks (second call: triangles, two CSR lists, edge ends)
-  d->stage_cap = 64 * 16 + sizeof(int) * ((size_t)S * 4 + 3 * MAX_TRIS * 2 + 2 * MAX_EDGES + 2 * (S + 1)) + sizeof(double) * (2 * S + 12);
-  d->res_cap = 64 * 8 + sizeof(double) * 3 * MAX_TRIS + MAX_TRIS + MAX_EDGES + sizeof(double) * 3 * S + sizeof(int) * S;
+  // (and the first call's with the device triangulation: the pixel positions in, the header and the triangles out)
+  d->stage_cap = 64 * 16 + sizeof(int) * ((size_t)S * 4 + 3 * MAX_TRIS * 2 + 2 * MAX_EDGES + 2 * (S + 1)) + sizeof(double) * (2 * S + 12) +
+                 sizeof(float) * 2 * S;
+  d->res_cap = 64 * 8 + sizeof(double) * 3 * MAX_TRIS + MAX_TRIS + MAX_EDGES + sizeof(double) * 3 * S + sizeof(int) * S +
+               sizeof(int) * (OVP_DL_HDR + 3 * MAX_TRIS);
   HIPCHK(d->hstage.alloc(d->stage_cap));
   HIPCHK(d->dstage.alloc(d->stage_cap));
   HIPCHK(d->dres.alloc(d->res_cap));
@@ -437,6 +462,7 @@ extern "C" int ovp_plane_detect_triangulate(ovp_ctx* c, int n, const int64_t* id
   if ((int)now.size() != n) return OVP_E_ARG;  // two points of one feature would share a slot
   HIPCHK(hipSetDevice(c->device));
   d->have_frame = false;
+  d->dev_tris_ok = false;
   // remove_feats: a feature not seen in this frame gives its slot back
   {
     for (auto it = d->slot_of.begin(); it != d->slot_of.end();)
@@ -450,6 +476,11 @@ extern "C" int ovp_plane_detect_triangulate(ovp_ctx* c, int n, const int64_t* id
   const size_t o_slot = L.take(sizeof(int) * n), o_fresh = L.take(n), o_uvn = L.take(sizeof(double) * 2 * n), o_pose = L.take(sizeof(double) * 12);
   StageLayout Rl;
   const size_t r_p = Rl.take(sizeof(double) * 3 * n), r_flag = Rl.take(sizeof(int) * n);
+  // device triangulation: the pixel positions behind the rest, the header and the triangles behind the flags - same block, same wait
+  const bool dl = d->dev_delaunay;
+  const int dl_cap = 2 * n;
+  const size_t o_uv = dl ? L.take(sizeof(float) * 2 * n) : 0, r_dhdr = dl ? Rl.take(sizeof(int) * OVP_DL_HDR) : 0,
+               r_dtri = dl ? Rl.take(sizeof(int) * 3 * dl_cap) : 0;
   if (L.bytes() > d->stage_cap || Rl.bytes() > d->res_cap) return OVP_E_CAPACITY;
   char* h = (char*)d->hstage.get();
   int* h_slot = (int*)(h + o_slot);
@@ -468,6 +499,7 @@ extern "C" int ovp_plane_detect_triangulate(ovp_ctx* c, int n, const int64_t* id
   memcpy(h + o_pose, R_GtoC, sizeof(double) * 9);
   memcpy(h + o_pose + sizeof(double) * 9, p_CinG, sizeof(double) * 3);
   memcpy(d->pose, h + o_pose, sizeof(double) * 12);
+  if (dl) memcpy(h + o_uv, uv, sizeof(float) * 2 * n);
   char* dv = (char*)d->dstage.get();
   char* dr = (char*)d->dres.get();
   HIPCHK(hipMemcpyAsync(dv, h, L.bytes(), hipMemcpyHostToDevice, c->stream));
@@ -477,12 +509,19 @@ extern "C" int ovp_plane_detect_triangulate(ovp_ctx* c, int n, const int64_t* id
                      d->o.feat_init_min_obs, d->o.max_cond_number, d->o.min_dist, d->o.max_dist, (double*)(dr + r_p), (int*)(dr + r_flag));
   HIPCHK(hipGetLastError());
   if (d->timed) HIPCHK(hipEventRecord(d->ev[1], c->stream));
+  if (dl) {  // the vertices are the points whose flag bit 0 the kernel above has just set, in point order
+    HIPCHK(ovp_launch_delaunay(n, (const float*)(dv + o_uv), (const int*)(dr + r_flag), (int*)(dr + r_dhdr), (int*)(dr + r_dtri), dl_cap,
+                               c->stream));
+    if (d->timed) HIPCHK(hipEventRecord(d->ev[7], c->stream));
+  }
   const int rw = publish_and_wait(c, d, Rl.bytes());
   if (rw) return rw;
   d->ms[0] = d->ms[1] = d->ms[2] = d->ms[3] = 0.f;
+  d->ms_delaunay[0] = 0.f;
   if (d->timed) {
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipEventElapsedTime(&d->ms[0], d->ev[0], d->ev[1]));
+    if (dl) HIPCHK(hipEventElapsedTime(&d->ms_delaunay[0], d->ev[1], d->ev[7]));
   }
   const char* hr = (const char*)d->hres.payload();
   const double* rp = (const double*)(hr + r_p);
@@ -500,6 +539,13 @@ extern "C" int ovp_plane_detect_triangulate(ovp_ctx* c, int n, const int64_t* id
       d->v_px.push_back(uv[2 * i + 1]);
     }
   }
+  if (dl) {  // (an overflow - inconsistent predicate signs - leaves the frame to ovp_delaunay_host)
+    const int* hd = (const int*)(hr + r_dhdr);
+    memcpy(d->dev_hdr, hd, sizeof(d->dev_hdr));
+    const int nt = hd[0];
+    d->dev_tris_ok = !hd[1] && hd[2] == (int)d->v_id.size() && nt >= 0 && nt <= dl_cap;
+    if (d->dev_tris_ok) d->dev_tris.assign((const int*)(hr + r_dtri), (const int*)(hr + r_dtri) + 3 * (size_t)nt);
+  }
   d->have_frame = true;
   return 0;
 }
@@ -515,6 +561,60 @@ extern "C" int ovp_delaunay(int n, const float* xy, int32_t* tris, int cap, int*
   return 0;
 }
 
+extern "C" int ovp_plane_detector_set_device_delaunay(ovp_ctx* c, int on) {
+  Detector* d = det_of(c);
+  if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
+  d->dev_delaunay = on != 0;
+  d->dev_tris_ok = false;  // (a frame between its two calls keeps the route it was staged for: the host's)
+  return 0;
+}
+
+// ovp_delaunay on the device: one upload, one launch, one publication.  No fallback: an overflow of the kernel's table is
+// OVP_E_CAPACITY, so a caller can tell this result from the host's.
+extern "C" int ovp_delaunay_device(ovp_ctx* c, int n, const float* xy, int32_t* tris, int cap, int* n_tris) {
+  if (!c || n < 0 || (n > 0 && !xy) || !n_tris || cap < 0 || (cap > 0 && !tris)) return OVP_E_ARG;
+  if (n > OVP_DET_MAX_POINTS) return OVP_E_CAPACITY;
+  *n_tris = 0;
+  if (n < 3) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  if (!c->delaunay_io) {
+    auto io = std::make_shared<DelaunayIo>();
+    const size_t res = sizeof(int) * (OVP_DL_HDR + 3 * (size_t)MAX_TRIS);
+    HIPCHK(io->hstage.alloc(sizeof(float) * 2 * S));
+    HIPCHK(io->dstage.alloc(sizeof(float) * 2 * S));
+    HIPCHK(io->dres.alloc(res));
+    HIPCHK(io->hres.alloc(res));
+    for (hipEvent_t& e : io->ev) HIPCHK(hipEventCreate(&e));
+    c->delaunay_io = io;
+  }
+  DelaunayIo* io = (DelaunayIo*)c->delaunay_io.get();
+  Detector* d = det_of(c);
+  const bool timed = d && d->timed;
+  const int dl_cap = 2 * n;
+  int* dhdr = (int*)io->dres.get();
+  memcpy(io->hstage.get(), xy, sizeof(float) * 2 * n);
+  HIPCHK(hipMemcpyAsync(io->dstage.get(), io->hstage.get(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
+  if (timed) HIPCHK(hipEventRecord(io->ev[0], c->stream));
+  HIPCHK(ovp_launch_delaunay(n, (const float*)io->dstage.get(), nullptr, dhdr, dhdr + OVP_DL_HDR, dl_cap, c->stream));
+  if (timed) HIPCHK(hipEventRecord(io->ev[1], c->stream));
+  SeqChannel& ch = io->hres.channel(0);
+  const unsigned seq = ch.arm();
+  HIPCHK(ovp_launch_publish_block(dhdr, io->hres.dev(io->hres.payload()), sizeof(int) * (OVP_DL_HDR + 3 * (size_t)dl_cap), ch.word_dev(), seq,
+                                  0, c->stream));
+  const int rw = ch.wait(c->stream);
+  if (rw) return rw;
+  if (timed) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipEventElapsedTime(&d->ms_delaunay[1], io->ev[0], io->ev[1]));
+  }
+  const int* hd = (const int*)io->hres.payload();
+  if (hd[1] || hd[0] < 0 || hd[0] > dl_cap) return OVP_E_CAPACITY;
+  *n_tris = hd[0];
+  if (hd[0] > cap) return OVP_E_CAPACITY;
+  memcpy(tris, hd + OVP_DL_HDR, sizeof(int32_t) * 3 * (size_t)hd[0]);
+  return 0;
+}
+
 extern "C" int ovp_plane_detect_planes(ovp_ctx* c, int n_tris, const int32_t* tris_in) {
   Detector* d = det_of(c);
   if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
@@ -525,10 +625,15 @@ extern "C" int ovp_plane_detect_planes(ovp_ctx* c, int n_tris, const int32_t* tr
     if (n_tris < 0) return OVP_E_ARG;
     if (n_tris > MAX_TRIS) return OVP_E_CAPACITY;
     tris.assign(tris_in, tris_in + 3 * (size_t)n_tris);
+    d->tri_source = 0;
+  } else if (d->dev_delaunay && d->dev_tris_ok) {
+    tris = d->dev_tris;
+    d->tri_source = 2;
   } else {
     std::vector<std::array<int, 3>> out;
     ovp_delaunay_host(nv, d->v_px.data(), out);
     for (const auto& t : out) tris.insert(tris.end(), t.begin(), t.end());
+    d->tri_source = 1;
   }
   const int nt = (int)tris.size() / 3;
   if (nt > MAX_TRIS) return OVP_E_CAPACITY;
@@ -826,6 +931,17 @@ extern "C" long ovp_plane_detector_debug(ovp_ctx* c, const char* what, int64_t i
     if (cap < 4) return OVP_E_ARG;
     for (int k = 0; k < 4; ++k) out[k] = d->ms[k];
     return 4;
+  }
+  if (!strcmp(what, "time_delaunay")) {
+    if (cap < 2) return OVP_E_ARG;
+    out[0] = d->ms_delaunay[0], out[1] = d->ms_delaunay[1];
+    return 2;
+  }
+  if (!strcmp(what, "tris")) {
+    if (cap < 6) return OVP_E_ARG;
+    out[0] = d->tri_source, out[1] = d->dev_delaunay ? 1 : 0;
+    for (int k = 0; k < 4; ++k) out[2 + k] = d->dev_hdr[k + 1];
+    return 6;
   }
   if (strcmp(what, "feat")) return OVP_E_ARG;
   auto it = d->slot_of.find(id);

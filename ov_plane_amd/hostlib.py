@@ -615,6 +615,12 @@ class Session:
         if rc != 0:
             raise RuntimeError("ovph_session_enable_plane_detection failed with %d" % rc)
 
+    def set_device_delaunay(self, on=True):
+        """StateOptions::gpu_device_delaunay: the plane detector triangulates a frame's points on the device (default off)"""
+        rc = self._L.ovph_session_set_device_delaunay(C.c_void_p(self._h), C.c_int(1 if on else 0))
+        if rc != 0:
+            raise RuntimeError("ovph_session_set_device_delaunay failed with %d" % rc)
+
     def feed_plane_tracks(self, frame_time, fid, uv, uv_norm):
         """every point tracked into the frame about to be stepped: ids, pixel positions, undistorted normalised coordinates"""
         fid = np.ascontiguousarray(fid, dtype=np.int64)
