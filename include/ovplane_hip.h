@@ -722,6 +722,78 @@ int ovp_delaunay_device(ovp_ctx *ctx, int n, const float *xy, int32_t *tris, int
  * table slots in use, largest cavity].  Returns the number of doubles (or < 0). */
 long ovp_plane_detector_debug(ovp_ctx *ctx, const char *what, int64_t id, double *out, long cap);
 
+/* ---- re-triangulation of a frame's active tracks ------------------------------------------------ */
+/* VioManager::retriangulate_active_tracks (core/VioManagerHelper.cpp:220-418): every point tracked into the frame becomes a
+ * position in G (active_tracks_posinG) and, when camera 0 sees it in this frame, a (u, v, depth) triple (active_tracks_uvd).
+ * Not built: the display images (:229-234) and the distort_d branch at :387-391, which the `continue` at :376 makes unreachable. */
+#define OVP_AT_MAX_POINTS 1024     /* distinct tracked features of one camera in one frame */
+#define OVP_AT_MAX_LANDMARKS 1024  /* SLAM landmarks of the state */
+/* The history active_feat_linsys_A / _b / _count (core/VioManager.h) as a device table of feature slots - A's upper triangle, b,
+ * count - with the feature id -> slot map on the host.  One object per context; it goes with ovp_ctx_destroy.  _reset forgets
+ * every feature (a VioManager that starts again). */
+int ovp_active_tracks_create(ovp_ctx *ctx);
+int ovp_active_tracks_destroy(ovp_ctx *ctx);
+int ovp_active_tracks_reset(ovp_ctx *ctx);
+typedef struct {
+  /* :240-241, :251, :268 the frame's observations (get_last_obs / get_last_ids), camera by camera in the caller's sensor_ids
+   * order - a feature's observations are walked in this order, and the order decides what it keeps (see ovp_active_tracks_update) */
+  int n_obs;
+  const int32_t *cam_idx;  /* [n_obs] camera id, 0 .. n_cams - 1; camera 0's pixels are feat_uvs_in_cam0 (:273-275) */
+  const int64_t *feat_id;  /* [n_obs] at most one observation per feature and camera */
+  const float *uv;         /* [2 n_obs] raw pixel (cv::Point2f pt_d, :272) */
+  const double *uv_norm;   /* [2 n_obs] undistorted normalised coordinates (:283; f64 here - the reference's undistort_cv returns a
+                              cv::Point2f, so a caller who wants the reference's numbers rounds them to f32 first) */
+  /* :254-263 per camera id: R_GtoCi = R_ItoC R_GtoI and p_CiinG of the newest clone.  Arguments, not the context's resident tables:
+   * the stage runs after the updaters have corrected the host state */
+  int n_cams;              /* 1 .. OVP_MAX_CAMERAS */
+  const double *R_GtoC;    /* [n_cams * 9] row-major */
+  const double *p_CinG;    /* [n_cams * 3] */
+  /* :360-368 camera 0's extrinsics and the newest clone, :399-400 camera 0's image size */
+  double R_ItoC0[9], p_IinC0[3], R_GtoI[9], p_IinG[3];
+  int width, height;
+  /* :321-322 featinit_options */
+  double min_dist, max_dist, max_cond_number;
+  /* :342-357 the SLAM landmarks of the state */
+  int n_slam;
+  const int64_t *slam_id;        /* [n_slam] distinct */
+  const double *slam_xyz;        /* [3 n_slam] get_xyz(false): in G, or in the anchor camera for a relative representation */
+  const uint8_t *slam_relative;  /* [n_slam] LandmarkRepresentation::is_relative_representation */
+  /* of the relative ones (entries of the others are not read; all four may be NULL when none is relative): the anchor clone
+   * (_anchor_clone_timestamp) and the anchor camera's extrinsics (_anchor_cam_id), :348-352 */
+  const double *slam_anchor_R_GtoI, *slam_anchor_p_IinG, *slam_anchor_R_ItoC, *slam_anchor_p_IinC; /* [9 n_slam], [3 n_slam], ... */
+} ovp_active_tracks_in;
+typedef struct {
+  int cap;          /* in: entries the arrays hold */
+  int n_feats, n;   /* out: distinct tracked features; entries = n_feats + n_slam (set also when cap is too small) */
+  int64_t *ids;     /* [cap] the distinct tracked features in order of first appearance, then the landmarks in input order */
+  uint8_t *flags;   /* [cap] bit 0: the id has a position (active_tracks_posinG), bit 1: it has a uvd (active_tracks_uvd) */
+  double *p_FinG;   /* [3 cap] zeros without bit 0 */
+  double *uvd;      /* [3 cap] (u_raw, v_raw, depth in camera 0 of the newest clone); zeros without bit 1 */
+} ovp_active_tracks_out;
+/* One frame, as the reference - its quirks included:
+ *  - :277-280 a tracked feature whose id is a SLAM landmark gives camera 0 its pixel but no row to any system; it leaves the table,
+ *    its tracked entry has no flag, and its position and uvd are reported in the landmark's entry;
+ *  - :293-301 per observation the frame's system is OLD + A_i with count OLD + 1, "old" being what the previous frame left: a feature
+ *    seen by several cameras in one frame keeps only its LAST observation's term.  A feature the previous frame did not leave is
+ *    inserted with std::map::insert, which does not replace: it keeps its FIRST observation's term, count 1;
+ *  - :304 the system is solved after each observation once the count is above 3 (a literal, not feat_init_min_obs), gated in the
+ *    observing camera (:321-322: condition number, min_dist <= z <= max_dist, finite norm); the last solve that passes stays;
+ *  - :331-334 a feature not observed in this frame leaves the table and starts again from nothing;
+ *  - :342-357 the landmarks' positions (global, or anchored -> global) overwrite or extend the position set;
+ *  - :372-410 a position whose id camera 0 sees is dropped from the uvd set for depth < 0.1, u < 0, (int) u >= width, v < 0,
+ *    (int) v >= height.
+ * n_obs = 0 with landmarks still reports the landmarks (:338).  Checked on the host before anything is touched or enqueued -
+ * OVP_E_CAPACITY: more than OVP_AT_MAX_POINTS observations of one camera, more than OVP_AT_MAX_LANDMARKS landmarks, out->cap too
+ * small; OVP_E_ARG: a camera id outside the call's, two observations of one feature in one camera, a repeated landmark id, a relative
+ * landmark without the anchor arrays.  OVP_E_STATE without ovp_active_tracks_create.  One upload, one compute launch
+ * (k_active_tracks), one publication through the object's own mailbox; two runs give the same bits. */
+int ovp_active_tracks_update(ovp_ctx *ctx, const ovp_active_tracks_in *in, ovp_active_tracks_out *out);
+/* tests: what = "feat": out = [count, A upper triangle (00 01 02 11 12 22), b(3)] of feature id's slot (returns 0 when the id has
+ * none); "size": [features in the table]; "timer": id != 0 puts events around the kernel (and a stream synchronisation behind the
+ * publication) from the next frame on, "time": GPU milliseconds of the last timed frame's kernel.  Returns the number of doubles
+ * (or < 0). */
+long ovp_active_tracks_debug(ovp_ctx *ctx, const char *what, int64_t id, double *out, long cap);
+
 /* ---- diagnostics ---------------------------------------------------------------------------- */
 /* copies an internal device buffer to host for tests: name in {"A","b","L","T","Lt","Y","G","rec","chi2",
  * "gramS","syrk"}; returns the byte count copied (or <0). */

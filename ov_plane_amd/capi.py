@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import time
 
 import numpy as np
 
@@ -190,6 +191,25 @@ class TrackPlaneOpts(C.Structure):
 
 
 OVP_DET_MAX_POINTS, OVP_DET_MAX_NORMS, OVP_DET_MAX_FILTER_K = 1024, 16, 16
+OVP_AT_MAX_POINTS, OVP_AT_MAX_LANDMARKS, OVP_MAX_CAMERAS = 1024, 1024, 4
+
+
+class ActiveTracksIn(C.Structure):
+    """ovp_active_tracks_in"""
+    _fields_ = [("n_obs", C.c_int), ("cam_idx", C.c_void_p), ("feat_id", C.c_void_p), ("uv", C.c_void_p), ("uv_norm", C.c_void_p),
+                ("n_cams", C.c_int), ("R_GtoC", C.c_void_p), ("p_CinG", C.c_void_p),
+                ("R_ItoC0", C.c_double * 9), ("p_IinC0", C.c_double * 3), ("R_GtoI", C.c_double * 9), ("p_IinG", C.c_double * 3),
+                ("width", C.c_int), ("height", C.c_int),
+                ("min_dist", C.c_double), ("max_dist", C.c_double), ("max_cond_number", C.c_double),
+                ("n_slam", C.c_int), ("slam_id", C.c_void_p), ("slam_xyz", C.c_void_p), ("slam_relative", C.c_void_p),
+                ("slam_anchor_R_GtoI", C.c_void_p), ("slam_anchor_p_IinG", C.c_void_p), ("slam_anchor_R_ItoC", C.c_void_p),
+                ("slam_anchor_p_IinC", C.c_void_p)]
+
+
+class ActiveTracksOut(C.Structure):
+    """ovp_active_tracks_out"""
+    _fields_ = [("cap", C.c_int), ("n_feats", C.c_int), ("n", C.c_int), ("ids", C.c_void_p), ("flags", C.c_void_p),
+                ("p_FinG", C.c_void_p), ("uvd", C.c_void_p)]
 
 EXPORTS = [
     "ovp_ctx_create", "ovp_ctx_destroy", "ovp_sync", "ovp_version", "ovp_error_string", "ovp_cov_upload",
@@ -207,6 +227,8 @@ EXPORTS = [
     "ovp_trackplane_defaults", "ovp_plane_detector_create", "ovp_plane_detector_destroy", "ovp_plane_detector_reset",
     "ovp_plane_detect_triangulate", "ovp_plane_detect_planes", "ovp_plane_detector_map", "ovp_delaunay", "ovp_plane_detector_debug", "ovp_plane_spatial_filter", "ovp_plane_detector_merges",
     "ovp_plane_init_general", "ovp_delaunay_device", "ovp_plane_detector_set_device_delaunay",
+    "ovp_active_tracks_create", "ovp_active_tracks_destroy", "ovp_active_tracks_reset", "ovp_active_tracks_update",
+    "ovp_active_tracks_debug",
 ]
 
 
@@ -315,6 +337,12 @@ def lib():
         L.ovp_plane_detector_set_device_delaunay.argtypes = [C.c_void_p, C.c_int]
         L.ovp_plane_detector_debug.restype = C.c_long
         L.ovp_plane_detector_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_long]
+        L.ovp_active_tracks_create.argtypes = [C.c_void_p]
+        L.ovp_active_tracks_destroy.argtypes = [C.c_void_p]
+        L.ovp_active_tracks_reset.argtypes = [C.c_void_p]
+        L.ovp_active_tracks_update.argtypes = [C.c_void_p, C.POINTER(ActiveTracksIn), C.POINTER(ActiveTracksOut)]
+        L.ovp_active_tracks_debug.restype = C.c_long
+        L.ovp_active_tracks_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_long]
         _LIB = L
     return _LIB
 
@@ -467,6 +495,93 @@ class PlaneDetector:
         _chk(lib().ovp_plane_spatial_filter(self.ctx.handle, len(planes), start.ctypes.data, P.ctypes.data, int(k), float(z),
                                             dist.ctypes.data, flag.ctypes.data), "ovp_plane_spatial_filter")
         return [(dist[a:b].copy(), flag[a:b].astype(bool)) for a, b in zip(start[:-1], start[1:])]
+
+
+class ActiveTracks:
+    """The active tracks of a context (ovp_active_tracks_*): VioManager::retriangulate_active_tracks on the device.  update() is
+    one frame; the per-feature history stays on the device between frames."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        _chk(lib().ovp_active_tracks_create(ctx.handle), "ovp_active_tracks_create")
+
+    def close(self):
+        _chk(lib().ovp_active_tracks_destroy(self.ctx.handle), "ovp_active_tracks_destroy")
+
+    def reset(self):
+        _chk(lib().ovp_active_tracks_reset(self.ctx.handle), "ovp_active_tracks_reset")
+
+    def update(self, cam_idx, ids, uv, uv_norm, R_GtoC, p_CinG, R_ItoC0, p_IinC0, R_GtoI, p_IinG, width, height, min_dist=0.1,
+               max_dist=60.0, max_cond_number=10000.0, slam_ids=(), slam_xyz=(), slam_relative=None, slam_anchor=None):
+        """One frame.  Observations in the caller's order: cam_idx [n], ids [n], uv [n, 2] raw pixels, uv_norm [n, 2]; R_GtoC
+        [n_cams, 3, 3] / p_CinG [n_cams, 3] by camera id; camera 0's extrinsics, the newest clone, the image size, the gates
+        (featinit_options); the landmarks: slam_ids, slam_xyz [m, 3], slam_relative [m] and, for the relative ones, slam_anchor =
+        (R_GtoI [m, 3, 3], p_IinG [m, 3], R_ItoC [m, 3, 3], p_IinC [m, 3]).
+        Returns dict(posinG {id: (3,)}, uvd {id: (3,)}, and the raw arrays ids, flags, p_FinG, uvd_all, n_feats)."""
+        f64 = lambda a, *sh: np.ascontiguousarray(a, dtype=np.float64).reshape(*sh)  # noqa: E731
+        cam = np.ascontiguousarray(cam_idx, dtype=np.int32).reshape(-1)
+        n = len(cam)
+        fid = np.ascontiguousarray(ids, dtype=np.int64).reshape(n)
+        uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(n, 2)
+        uvn = f64(uv_norm, n, 2)
+        R, p = f64(R_GtoC, -1, 3, 3), f64(p_CinG, -1, 3)
+        sid = np.ascontiguousarray(slam_ids, dtype=np.int64).reshape(-1)
+        m = len(sid)
+        sx = f64(slam_xyz, m, 3)
+        rel = np.ascontiguousarray(slam_relative if slam_relative is not None else np.zeros(m), dtype=np.uint8).reshape(m)
+        a = ActiveTracksIn()
+        a.n_obs, a.cam_idx, a.feat_id, a.uv, a.uv_norm = n, cam.ctypes.data, fid.ctypes.data, uv.ctypes.data, uvn.ctypes.data
+        a.n_cams, a.R_GtoC, a.p_CinG = len(R), R.ctypes.data, p.ctypes.data
+        a.R_ItoC0[:], a.p_IinC0[:] = list(f64(R_ItoC0, 9)), list(f64(p_IinC0, 3))
+        a.R_GtoI[:], a.p_IinG[:] = list(f64(R_GtoI, 9)), list(f64(p_IinG, 3))
+        a.width, a.height = int(width), int(height)
+        a.min_dist, a.max_dist, a.max_cond_number = float(min_dist), float(max_dist), float(max_cond_number)
+        a.n_slam, a.slam_id, a.slam_xyz, a.slam_relative = m, sid.ctypes.data, sx.ctypes.data, rel.ctypes.data
+        keep = None
+        if slam_anchor is not None:
+            keep = (f64(slam_anchor[0], m, 3, 3), f64(slam_anchor[1], m, 3), f64(slam_anchor[2], m, 3, 3), f64(slam_anchor[3], m, 3))
+            a.slam_anchor_R_GtoI, a.slam_anchor_p_IinG, a.slam_anchor_R_ItoC, a.slam_anchor_p_IinC = (k.ctypes.data for k in keep)
+        cap = max(len(set(fid.tolist())) + m, 1)
+        o = ActiveTracksOut()
+        out_ids, flags = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.uint8)
+        pf, uvd = np.zeros((cap, 3)), np.zeros((cap, 3))
+        o.cap, o.ids, o.flags, o.p_FinG, o.uvd = cap, out_ids.ctypes.data, flags.ctypes.data, pf.ctypes.data, uvd.ctypes.data
+        t0 = time.perf_counter()
+        rc = lib().ovp_active_tracks_update(self.ctx.handle, C.byref(a), C.byref(o))
+        self.last_call_ms = 1e3 * (time.perf_counter() - t0)  # the entry alone, without this method's array and dict work
+        _chk(rc, "ovp_active_tracks_update")
+        k = o.n
+        out_ids, flags, pf, uvd = out_ids[:k], flags[:k], pf[:k], uvd[:k]
+        return dict(posinG={int(i): pf[j].copy() for j, i in enumerate(out_ids) if flags[j] & 1},
+                    uvd={int(i): uvd[j].copy() for j, i in enumerate(out_ids) if flags[j] & 2},
+                    ids=out_ids, flags=flags, p_FinG=pf, uvd_all=uvd, n_feats=int(o.n_feats))
+
+    def _debug(self, what, fid, cap):
+        out = np.zeros(cap)
+        k = lib().ovp_active_tracks_debug(self.ctx.handle, what, int(fid), out.ctypes.data, cap)
+        if k < 0:
+            raise OvpError(int(k), "ovp_active_tracks_debug")
+        return out[:k]
+
+    def debug(self, fid):
+        """tests: the slot of one feature -> dict(count, A [3, 3], b [3]), or None when the table does not hold the id"""
+        o = self._debug(b"feat", fid, 10)
+        if len(o) == 0:
+            return None
+        a = o[1:7]
+        return dict(count=int(o[0]), A=np.array([[a[0], a[1], a[2]], [a[1], a[3], a[4]], [a[2], a[4], a[5]]]), b=o[7:10].copy())
+
+    def size(self):
+        """features in the table"""
+        return int(self._debug(b"size", 0, 1)[0])
+
+    def timer(self, on=True):
+        """events around the kernel from the next frame on (diagnostics: adds a stream synchronisation per frame)"""
+        self._debug(b"timer", 1 if on else 0, 1)
+
+    def kernel_ms(self):
+        """GPU milliseconds of the last timed frame's kernel"""
+        return float(self._debug(b"time", 0, 1)[0])
 
 
 def rccl_unique_id() -> bytes:

@@ -167,7 +167,8 @@ def run(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, max_feats=
 
 def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, planes=0, plane_min_feat=6, sigma_c=0.01,
                 max_slam=0, feat_rep_slam=0, min_meas=3, out_dir=None, zupt=None, track_planes=True, forget_planes_at=None,
-                detect_planes=False, detect_opts=None, feed_plane_tracks=None, device_delaunay=False):
+                detect_planes=False, detect_opts=None, feed_plane_tracks=None, device_delaunay=False, active_tracks=False,
+                active_tracks_skip=()):
     """Closed loop through hostlib.Session, frame by frame, with the tracker-side bookkeeping of core/VioManager.cpp:360-506:
     a track is an MSCKF feature once it is lost or reaches back to the clone about to be marginalised; a track that spans the
     whole window (more than max_clone_size measurements) becomes a SLAM landmark while there is room (max_slam), and from then
@@ -183,6 +184,11 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
     feed_plane_tracks (default: detect_planes) hands the tracked points over whether or not the option is on - with it off they
     are ignored.  The result then also holds detected_per_frame [K, 2] = (features of the step on a detected plane, entries of the map).
     device_delaunay: StateOptions::gpu_device_delaunay - with detect_planes, the detector triangulates on the device.
+    active_tracks: StateOptions::gpu_active_tracks - every frame's tracked points are handed over (as for detect_planes, the same
+    hand-over) and re-triangulated on the device (VioManager::retriangulate_active_tracks).  The result then also holds
+    active_per_frame [K, 2] = (positions, uvd entries), active_depth_err [K] = median |depth - true depth| over the frame's uvd
+    entries of simulated points (NaN without any), and active_frames = every frame's Session.active_tracks().
+    active_tracks_skip: frame indices at which no points are handed over (test hook: such a step's maps are empty).
     zupt: dict of Session.enable_zupt keywords (or {}) = VioManagerOptions::try_zupt: a frame at which the platform is found
     standing still gets a zero-velocity update instead of a clone (core/VioManager.cpp:311-331) and its measurements are dropped."""
     from . import hostlib
@@ -203,6 +209,8 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
         ses.set_device_delaunay(True)
     if detect_planes:
         ses.enable_plane_detection(detect_opts)
+    if active_tracks:
+        ses.enable_active_tracks(int(sim.params["width"]), int(sim.params["height"]))
     ses.feed_imu(imu)
     if out_dir is not None:
         import os
@@ -228,6 +236,7 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
     n_feats = np.zeros((K, 3), dtype=np.int32)
     zupt_frames = np.zeros(K, dtype=bool)
     detected = np.zeros((K, 2), dtype=np.int32)
+    active_n, active_err, active_all = np.zeros((K, 2), dtype=np.int32), np.full(K, np.nan), []
     for k in range(C, len(frames)):
         t_k, seen = frames[k]
         i = k - C
@@ -288,7 +297,7 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
             active = {plane_of[int(f)] for f in live if plane_of[int(f)] > 0}
             if forget_planes_at is not None and i >= forget_planes_at:
                 active, pl = set(), np.zeros(len(fid), dtype=np.int32)
-        if detect_planes or feed_plane_tracks:
+        if detect_planes or feed_plane_tracks or (active_tracks and i not in active_tracks_skip):
             s_id = np.array(sorted(seen), dtype=np.int64)
             s_uv = np.array([seen[int(f)] for f in s_id], dtype=np.float32).reshape(-1, 2)
             sx, sy = radtan_undistort(s_uv[:, 0], s_uv[:, 1], init["intr"])
@@ -301,6 +310,15 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
             if info["rc"] != 0:
                 raise RuntimeError("plane detection failed with %d" % info["rc"])
             detected[i] = info["planar"], info["mapped"]
+        if active_tracks:
+            active_last = ses.active_tracks()
+            active_all.append(active_last)
+            active_n[i] = len(active_last["posinG"]), len(active_last["uvd"])
+            Rc = sim.R_ItoC @ quat_2_rot(gt["q"])               # depth of the simulator's points in the true camera 0
+            err = [abs(d[2] - (Rc @ (sim.featmap[f - FID_OFFSET][:3] - gt["p"]) + sim.p_IinC)[2])
+                   for f, d in active_last["uvd"].items() if f - FID_OFFSET in sim.featmap]
+            if err:
+                active_err[i] = float(np.median(err))
         window = win[1:]
         slam_ids = {i_ - FID_OFFSET for i_ in out["slam_ids"]}
         for f in slam_ids:
@@ -318,6 +336,6 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
         nees_p[i] = dp @ np.linalg.solve(posecov[i][3:6, 3:6], dp)
         nees_o[i] = dth @ np.linalg.solve(posecov[i][0:3, 0:3], dth)
     return dict(times=times, traj=traj, posecov=posecov, counts=counts, n_feats=n_feats, zupt_frames=zupt_frames, e_pos=e_pos,
-                detected_per_frame=detected,
+                detected_per_frame=detected, active_per_frame=active_n, active_depth_err=active_err, active_frames=active_all,
                 e_ori=e_ori, nees_pos=nees_p, nees_ori=nees_o, rmse_pos=float(np.sqrt(np.mean(e_pos**2))),
                 rmse_ori_deg=float(np.degrees(np.sqrt(np.mean(e_ori**2)))))

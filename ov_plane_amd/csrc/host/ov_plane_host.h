@@ -82,6 +82,11 @@ struct StateOptions {
   // gpu_plane_detection: the Delaunay triangulation of the frame's points runs on the device behind the detector's first call
   // (ovp_plane_detector_set_device_delaunay) instead of on the host between its two calls - the same triangles.  Not in the reference.
   bool gpu_device_delaunay = false;
+  // A session frame whose tracked points were handed over (ovph_session_feed_plane_tracks) runs
+  // VioManager::retriangulate_active_tracks on the device (ov_plane::ActiveTracks, ovp_active_tracks_update) between the SLAM
+  // delayed initialisation and the anchor change: active_tracks_posinG / active_tracks_uvd of every tracked point.  The filter
+  // does not read them.  In the reference the stage always runs (core/VioManager.cpp:757).
+  bool gpu_active_tracks = false;
   // UpdaterMSCKF::update: on-plane features the device batch cannot carry (another camera, more than OVP_MAX_MEAS views) stay in the
   // plane loop through ovp_msckf_plane_update_general instead of going to the point update without their plane constraint - for
   // planes whose estimate does not come from this frame's fit (in the state, or handed over in _plane_estimates_cp_inG); a frame with

@@ -20,6 +20,7 @@
 #include "ov_plane_host.h"
 #include "ov_plane_io.h"
 #include "ov_plane_trackplane.h"
+#include "ov_plane_activetracks.h"
 
 using namespace ov_plane;
 using namespace ov_type;
@@ -40,6 +41,10 @@ struct Session {
   std::vector<size_t> track_ids;
   std::vector<float> track_uv, track_uvn;
   int detect_rc = 0, detect_planar = 0;
+  // StateOptions::gpu_active_tracks: VioManager's active tracks of the last step, from the same hand-over
+  std::unique_ptr<ActiveTracks> active;
+  int active_rc = 0;
+  ov_core::FeatureInitializerOptions featinit;  // VioManagerOptions::featinit_options
   // what a run of the reference leaves behind (ros/ROSVisualizerHelper.cpp:152-302, core/VioManager.cpp:110-118, 911-927)
   std::ofstream of_est, of_std, of_gt, of_timing;
   bool files = false;
@@ -131,6 +136,7 @@ extern "C" void *ovph_session_open(int C, const double *clone_q, const double *c
   s->msckf = std::make_unique<UpdaterMSCKF>(um, fio);
   s->slam = std::make_unique<UpdaterSLAM>(us, us, fio);
   s->plane = std::make_unique<UpdaterPlane>(um, fio);
+  s->featinit = fio;
   return s.release();
 }
 
@@ -195,6 +201,64 @@ extern "C" int ovph_session_set_device_delaunay(void *h, int on) {
   auto *s = static_cast<Session *>(h);
   s->state->_options.gpu_device_delaunay = on != 0;
   if (s->track && s->track->set_device_delaunay(on != 0)) return -31;
+  return 0;
+}
+
+// StateOptions::gpu_active_tracks on: from then on a step whose tracked points were handed over by ovph_session_feed_plane_tracks for
+// its timestamp runs VioManager::retriangulate_active_tracks (core/VioManager.cpp:757) on the device, between the SLAM delayed
+// initialisation and the anchor change, and ovph_session_active_tracks returns its maps.  Camera 0's image size is the simulator's
+// (752 x 480) unless ovph_session_set_image_size says otherwise.
+extern "C" int ovph_session_enable_active_tracks(void *h) {
+  auto *s = static_cast<Session *>(h);
+  if (!s->state->gpu()) return -31;
+  s->active.reset();
+  s->active = std::make_unique<ActiveTracks>(s->state->gpu());
+  if (!s->active->ok()) {
+    s->active.reset();
+    return -31;
+  }
+  s->state->_options.gpu_active_tracks = true;
+  return 0;
+}
+
+extern "C" int ovph_session_set_image_size(void *h, int width, int height) {
+  auto *s = static_cast<Session *>(h);
+  if (!s->active || width < 1 || height < 1) return -21;
+  s->active->set_image_size(width, height);
+  return 0;
+}
+
+// VioManager::get_active_tracks after the last step: *n = entries (also when cap is smaller), ids [cap], flags [cap] (bit 0: in
+// active_tracks_posinG, bit 1: in active_tracks_uvd), p [3 cap], uvd [3 cap], ascending id.  Returns 0; 1 when the last step did
+// not run the stage (option off, or no points handed over for its timestamp: the maps are empty); an OVP_E_* code when it failed.
+extern "C" int ovph_session_active_tracks(void *h, int cap, long long *ids, unsigned char *flags, double *p, double *uvd, int *n) {
+  auto *s = static_cast<Session *>(h);
+  if (!n || cap < 0 || (cap > 0 && (!ids || !flags || !p || !uvd))) return -21;
+  *n = 0;
+  if (!s->active) return 1;
+  if (s->active_rc) return s->active_rc;
+  std::map<size_t, int> all;
+  for (const auto &e : s->active->active_tracks_posinG) all[e.first] |= 1;
+  for (const auto &e : s->active->active_tracks_uvd) all[e.first] |= 2;
+  *n = (int)all.size();
+  int i = 0;
+  for (const auto &e : all) {
+    if (i >= cap) break;
+    ids[i] = (long long)e.first, flags[i] = (unsigned char)e.second;
+    for (int k = 0; k < 3; ++k) {
+      p[3 * i + k] = (e.second & 1) ? s->active->active_tracks_posinG.at(e.first)[k] : 0.0;
+      uvd[3 * i + k] = (e.second & 2) ? s->active->active_tracks_uvd.at(e.first)[k] : 0.0;
+    }
+    ++i;
+  }
+  return s->active->active_tracks_time < 0 ? 1 : 0;
+}
+
+// the pose the last retriangulated step projected with: [R_ItoC 9 | p_IinC 3] of camera 0, [R_GtoI 9 | p_IinG 3] of the newest clone
+extern "C" int ovph_session_active_tracks_pose(void *h, double *out24) {
+  auto *s = static_cast<Session *>(h);
+  if (!s->active || !out24) return -21;
+  memcpy(out24, s->active->last_pose, sizeof(s->active->last_pose));
   return 0;
 }
 
@@ -353,6 +417,8 @@ extern "C" int ovph_session_step2(void *h, double frame_time, int F, int M, cons
       f_msckf.push_back(ft);
     }
   }
+  // the tracked points were handed over for THIS frame (the detector below consumes the hand-over; the active tracks share it)
+  const bool have_tracks = s->track_time == frame_time;
   bool detected = false;
   std::map<size_t, std::set<size_t>> detected_merges;
   if (state->_options.gpu_plane_detection && s->track && s->track_time != frame_time) {
@@ -438,6 +504,15 @@ extern "C" int ovph_session_step2(void *h, double frame_time, int F, int M, cons
   counts[1] = n_up;
   counts[2] = (int)(state->_features_SLAM.size() - before);
   counts[3] = n_marg;
+  if (state->_options.gpu_active_tracks && s->active) {  // :757 retriangulate_active_tracks; its time falls into tr.marg (rT7 -> rT8)
+    if (have_tracks) {
+      s->active_rc = s->active->retriangulate(state, state->_timestamp, s->featinit, {0}, {s->track_ids}, {s->track_uv}, {s->track_uvn});
+      s->track_time = -1.0;
+    } else {
+      s->active->clear();
+      s->active_rc = 0;
+    }
+  }
   s->slam->change_anchors(state);             // :861
   StateHelper::marginalize_old_clone(state);  // :864-872
   lap(tr.marg);

@@ -14,6 +14,7 @@
 #include "ovp_ctx.h"
 #include "host/ov_plane_delaunay.h"
 #include "k_delaunay.h"
+#include "k_tri3.h"
 
 #include <map>
 #include <set>
@@ -28,20 +29,6 @@ struct DetState {  // per feature slot
 };
 
 constexpr double kRad2Deg = 180.0 / 3.14159265358979323846;
-
-// one Jacobi rotation of the symmetric 3x3 (p, q the rotated pair, r the third index)
-#define OVP_DET_JACOBI(app, aqq, apq, arp, arq)                                   \
-  if (apq != 0.0) {                                                               \
-    const double th = (aqq - app) / (2.0 * apq);                                  \
-    const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0)); \
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;                          \
-    app -= t * apq;                                                               \
-    aqq += t * apq;                                                               \
-    apq = 0.0;                                                                    \
-    const double rp = c * arp - s * arq, rq = s * arp + c * arq;                  \
-    arp = rp;                                                                     \
-    arq = rq;                                                                     \
-  }
 
 __global__ __launch_bounds__(256) void k_det_triangulate(DetState st, int n, const int* __restrict__ slot,
                                                          const unsigned char* __restrict__ fresh, const double* __restrict__ uvn,
@@ -84,40 +71,10 @@ __global__ __launch_bounds__(256) void k_det_triangulate(DetState st, int n, con
   if (valid)
     for (int k = 0; k < 3; ++k) p[k] = st.p[s * 3 + k];
   if (cnt >= min_obs) {
-    // A x = b by elimination with row pivoting
-    double M[3][4] = {{A[0], A[1], A[2], b[0]}, {A[1], A[3], A[4], b[1]}, {A[2], A[4], A[5], b[2]}};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-      for (int r = c + 1; r < 3; ++r)
-        if (fabs(M[r][c]) > fabs(M[c][c])) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const double t = M[c][k];
-            M[c][k] = M[r][k];
-            M[r][k] = t;
-          }
-        }
-#pragma unroll
-      for (int r = c + 1; r < 3; ++r) {
-        const double f = M[r][c] / M[c][c];
-#pragma unroll
-        for (int k = c; k < 4; ++k) M[r][k] -= f * M[c][k];
-      }
-    }
+    // A x = b by row-pivoted elimination, the condition number from the eigenvalues of the symmetric A (k_tri3.h)
     double q[3];
-    q[2] = M[2][3] / M[2][2];
-    q[1] = (M[1][3] - M[1][2] * q[2]) / M[1][1];
-    q[0] = (M[0][3] - M[0][1] * q[1] - M[0][2] * q[2]) / M[0][0];
-    // the singular values of the symmetric A are the magnitudes of its eigenvalues: cyclic Jacobi
-    double a00 = A[0], a01 = A[1], a02 = A[2], a11 = A[3], a12 = A[4], a22 = A[5];
-    for (int sweep = 0; sweep < 8; ++sweep) {
-      OVP_DET_JACOBI(a00, a11, a01, a02, a12)
-      OVP_DET_JACOBI(a00, a22, a02, a01, a12)
-      OVP_DET_JACOBI(a11, a22, a12, a01, a02)
-    }
-    const double e0 = fabs(a00), e1 = fabs(a11), e2 = fabs(a22);
-    const double cond = fmax(e0, fmax(e1, e2)) / fmin(e0, fmin(e1, e2));
+    ovp_tri3_solve(A, b, q);
+    const double cond = ovp_tri3_cond(A);
     const double d0 = q[0] - pc[0], d1 = q[1] - pc[1], d2 = q[2] - pc[2];
     const double cx = R[0] * d0 + R[1] * d1 + R[2] * d2, cy = R[3] * d0 + R[4] * d1 + R[5] * d2, cz = R[6] * d0 + R[7] * d1 + R[8] * d2;
     const double nrm = sqrt(cx * cx + cy * cy + cz * cz);

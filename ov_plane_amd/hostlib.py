@@ -632,6 +632,40 @@ class Session:
         if rc != 0:
             raise RuntimeError("ovph_session_feed_plane_tracks failed with %d" % rc)
 
+    def enable_active_tracks(self, width=752, height=480):
+        """StateOptions::gpu_active_tracks: a step whose tracked points were handed over by feed_plane_tracks for its timestamp
+        runs VioManager::retriangulate_active_tracks on the device (width, height: camera 0's image); active_tracks() reads the
+        maps."""
+        rc = self._L.ovph_session_enable_active_tracks(C.c_void_p(self._h))
+        if rc == 0:
+            rc = self._L.ovph_session_set_image_size(C.c_void_p(self._h), C.c_int(int(width)), C.c_int(int(height)))
+        if rc != 0:
+            raise RuntimeError("ovph_session_enable_active_tracks failed with %d" % rc)
+
+    def active_tracks(self):
+        """VioManager::get_active_tracks after the last step -> dict(valid, posinG {id: (3,)}, uvd {id: (3,)}, pose).  valid is
+        False when the step did not run the stage (option off, or no points handed over for its timestamp): the maps are then
+        empty.  pose: what the stage projected with - dict(R_ItoC, p_IinC of camera 0, R_GtoI, p_IinG of the newest clone)."""
+        n = C.c_int(0)
+        f = self._L.ovph_session_active_tracks
+        f.restype = C.c_int
+        rc = f(C.c_void_p(self._h), C.c_int(0), None, None, None, None, C.byref(n))
+        if rc < 0:
+            raise RuntimeError("ovph_session_active_tracks failed with %d" % rc)
+        cap = max(n.value, 1)
+        ids, flags = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.uint8)
+        p, uvd = np.zeros((cap, 3)), np.zeros((cap, 3))
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = f(C.c_void_p(self._h), C.c_int(cap), vp(ids), vp(flags), vp(p), vp(uvd), C.byref(n))
+        if rc < 0:
+            raise RuntimeError("ovph_session_active_tracks failed with %d" % rc)
+        k = n.value
+        ps = np.zeros(24)
+        self._L.ovph_session_active_tracks_pose(C.c_void_p(self._h), vp(ps))
+        pose = dict(R_ItoC=ps[0:9].reshape(3, 3).copy(), p_IinC=ps[9:12].copy(), R_GtoI=ps[12:21].reshape(3, 3).copy(), p_IinG=ps[21:24].copy())
+        return dict(valid=rc == 0, pose=pose, posinG={int(ids[i]): p[i].copy() for i in range(k) if flags[i] & 1},
+                    uvd={int(ids[i]): uvd[i].copy() for i in range(k) if flags[i] & 2})
+
     def plane_detection_info(self):
         """dict(rc of the last frame's detection, planar = features of the last step the detector put on a plane, mapped = entries
         of the detector's map)"""
