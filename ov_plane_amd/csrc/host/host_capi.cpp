@@ -1,94 +1,271 @@
-// Harness entry point for the host mirror (tests only need a C symbol to drive the C++ classes from ctypes).
-// It builds an ov_plane::State the way VioManager would (clone by clone through StateHelper::augment_clone), installs the
-// given covariance, wraps the measurements in ov_core::Feature objects and calls UpdaterMSCKF::update.
+// Harness over the host mirror (tests only need C symbols to drive the C++ classes from ctypes).  An entry builds an
+// ov_plane::State the way VioManager would (clone by clone through StateHelper::augment_clone), installs the given covariance, wraps
+// the measurements in ov_core::Feature objects and calls the class under test.
+//
+// The harness holds no state of its own: what used to be armed for "the next call" travels in the ovph_run_opts the entry is handed
+// (host_capi.h), its per-call results (camera 1, the shard range) come back in the same struct, and the struct's pointers are
+// borrowed for that call only.  build_harness_state is the one place here that makes a State, export_state the one place that
+// copies one out.
+#include <cstddef>
 #include <cstring>
 
+#include "host_capi.h"
 #include "ov_plane_host.h"
 
 using namespace ov_plane;
 using namespace ov_type;
 
-// When set, the next ovph_run_msckf_update hands the features over with normalised measurements and NO position, i.e. the
-// updater triangulates them itself (update/UpdaterMSCKF.cpp:120-166) before the update.
-static const float *g_uv_norm = nullptr;
-extern "C" void ovph_set_uv_norm(const float *uv_norm /* [F][M][2] or NULL */) { g_uv_norm = uv_norm; }
-// next ovph_run_msckf_update: no plane estimates are handed over, UpdaterMSCKF::update runs plane_fitting / optimize_plane itself
-static int g_fit_planes = 0, g_fit_min_feat = 20, g_fit_variant = 0;
-static double g_fit_max_cond = 100.0;
-// lens model of camera 0 for the next harness call (0 = radtan, 1 = equidistant)
-static int g_fisheye = 0;
-extern "C" void ovph_set_fisheye(int fisheye) { g_fisheye = fisheye; }
-// mode 0 of ovph_run_updater: hold every landmark in this ext LandmarkRepresentation (1..4), anchored in this clone slot
-static int g_slam_rep = 0, g_slam_anchor = 0;
-extern "C" void ovph_set_slam_rep(int rep, int anchor_ci) {
-  g_slam_rep = rep;
-  g_slam_anchor = anchor_ci;
+extern "C" void ovph_run_opts_defaults(ovph_run_opts *o) {
+  memset(o, 0, sizeof(*o));
+  o->size = sizeof(*o);
+  o->fit_min_feat = 20;
+  o->fit_max_cond = 100.0;
+  o->comm_world = 1;
+  o->seq_plane_min_feat = 20;
+  o->seq_sigma_c = 0.01;
 }
-// mode 1 of ovph_run_updater: StateOptions::feat_rep_slam of the landmarks delayed_init creates
-static int g_feat_rep_slam = 0;
-extern "C" void ovph_set_feat_rep_slam(int rep) { g_feat_rep_slam = rep; }
-// mode 3 of ovph_run_updater: plane of every SLAM landmark (0 = none)
-static const int *g_slam_plane = nullptr;
-extern "C" void ovph_set_slam_planes(const int *plane_of_landmark) { g_slam_plane = plane_of_landmark; }
-// UpdaterSLAM::update takes its dense form (the one a batch the device entry refuses falls back to) until switched off again
+extern "C" int ovph_run_opts_size(void) { return (int)sizeof(ovph_run_opts); }
+extern "C" int ovph_run_opts_layout(int *offsets, int cap) {
+#define OVPH_OFF(m) (int)offsetof(ovph_run_opts, m)
+  const int off[] = {OVPH_OFF(size), OVPH_OFF(fisheye), OVPH_OFF(uv_norm), OVPH_OFF(fit_planes), OVPH_OFF(fit_min_feat),
+                     OVPH_OFF(fit_max_cond), OVPH_OFF(fit_variant), OVPH_OFF(slam_rep), OVPH_OFF(slam_anchor), OVPH_OFF(feat_rep_slam),
+                     OVPH_OFF(slam_plane), OVPH_OFF(cam1_q), OVPH_OFF(cam1_p), OVPH_OFF(cam1_intr), OVPH_OFF(cam_of_meas),
+                     OVPH_OFF(general_features), OVPH_OFF(general_planes), OVPH_OFF(general_plane_init), OVPH_OFF(fused_plane_fit),
+                     OVPH_OFF(general_slam), OVPH_OFF(dinit_planes), OVPH_OFF(p_noplane), OVPH_OFF(comm), OVPH_OFF(comm_rank),
+                     OVPH_OFF(comm_world), OVPH_OFF(device), OVPH_OFF(seq_traj), OVPH_OFF(seq_posecov), OVPH_OFF(seq_uv_norm),
+                     OVPH_OFF(seq_plane), OVPH_OFF(seq_plane_mode), OVPH_OFF(seq_plane_min_feat), OVPH_OFF(seq_sigma_c),
+                     OVPH_OFF(seq_planes_in_state), OVPH_OFF(last_shard), OVPH_OFF(last_cam1)};
+#undef OVPH_OFF
+  const int n = (int)(sizeof(off) / sizeof(off[0]));
+  for (int i = 0; i < n && i < cap; ++i) offsets[i] = off[i];
+  return n;
+}
+
+// These two wrap statics of UpdaterSLAM itself, not harness state: its update takes the dense form (the one a batch the device entry
+// refuses falls back to) until switched off again; path of the last UpdaterSLAM::update / delayed_init (UpdaterSLAM::Route: 1 device
+// general, 2 device mono, 3 dense host, 4 per-candidate host loop, 5 device loop with plane candidates, 0 none)
 extern "C" void ovph_set_slam_force_dense(int on) { UpdaterSLAM::force_dense_for_tests(on != 0); }
-extern "C" void ovph_set_plane_fit(int enable, int min_feat, double max_cond, int shuffle_variant) {
-  g_fit_planes = enable;
-  g_fit_min_feat = min_feat;
-  g_fit_max_cond = max_cond;
-  g_fit_variant = shuffle_variant;
-}
-
-// next ovph_run_msckf_update: a second camera (num_cameras = 2) with these calibration values; cam_of_meas[F][M] says which camera
-// took each measurement of the feature batch
-static const double *g_cam1_q = nullptr, *g_cam1_p = nullptr, *g_cam1_intr = nullptr;
-static const int *g_cam_of_meas = nullptr;
-static double g_last_cam1[15];  // [q (4) | p (3) | intrinsics (8)] of camera 1 after the last run that had one
-extern "C" void ovph_last_second_camera(double *out15) { memcpy(out15, g_last_cam1, sizeof(g_last_cam1)); }
-extern "C" void ovph_set_second_camera(const double *calib_q, const double *calib_p, const double *intr, const int *cam_of_meas) {
-  g_cam1_q = calib_q;
-  g_cam1_p = calib_p;
-  g_cam1_intr = intr;
-  g_cam_of_meas = cam_of_meas;
-}
-// next ovph_run_msckf_update: StateOptions::gpu_general_features
-static int g_general = 0;
-extern "C" void ovph_set_general_features(int on) { g_general = on != 0; }
-// next ovph_run_msckf_update: StateOptions::gpu_general_planes
-static int g_general_planes = 0;
-extern "C" void ovph_set_general_planes(int on) { g_general_planes = on != 0; }
-// next ovph_run_updater: StateOptions::gpu_general_plane_init
-static int g_general_plane_init = 0;
-extern "C" void ovph_set_general_plane_init(int on) { g_general_plane_init = on != 0; }
-// next ovph_run_msckf_update / ovph_run_updater: StateOptions::gpu_fused_plane_fit
-static int g_fused_plane_fit = 0;
-extern "C" void ovph_set_fused_plane_fit(int on) { g_fused_plane_fit = on != 0; }
-// next ovph_run_updater: StateOptions::gpu_general_slam
-static int g_general_slam = 0;
-extern "C" void ovph_set_general_slam(int on) { g_general_slam = on != 0; }
-// path of the last UpdaterSLAM::update / delayed_init (UpdaterSLAM::Route: 1 device general, 2 device mono, 3 dense host, 4
-// per-candidate host loop, 0 none)
-// next ovph_run_updater: StateOptions::gpu_dinit_planes; mode 1: the positions before plane refinement of the candidates
-// (Feature::p_FinG_original, [F][3]) or nullptr
-static int g_dinit_planes = 0;
-static const double *g_p_noplane = nullptr;
-extern "C" void ovph_set_dinit_planes(int on) { g_dinit_planes = on != 0; }
-extern "C" void ovph_set_p_noplane(const double *p) { g_p_noplane = p; }
 extern "C" int ovph_last_slam_route() { return UpdaterSLAM::last_route(); }
-// next ovph_run_msckf_update: the State lives on this device and the updater takes the sharded point loop on this communicator
-static void *g_comm = nullptr;
-static int g_comm_rank = 0, g_comm_world = 1, g_device = 0, g_last_shard[2] = {0, 0};
-extern "C" void ovph_set_shard_comm(void *nccl_comm, int rank, int world, int device) {
-  g_comm = nccl_comm;
-  g_comm_rank = rank;
-  g_comm_world = world;
-  g_device = device;
-}
-extern "C" void ovph_last_shard(int *lo, int *hi) {
-  *lo = g_last_shard[0];
-  *hi = g_last_shard[1];
+
+namespace ov_plane {
+struct StateTestAccess {
+  static void replace_last_variable(std::shared_ptr<State> state, std::shared_ptr<Type> v) { state->_variables.back() = v; }
+};
+}  // namespace ov_plane
+
+namespace {
+// the options an entry works with: the caller's (results are written back into them) or, for NULL, defaults in `local`;
+// nullptr when the caller's struct is not this build's
+ovph_run_opts *use_opts(ovph_run_opts *given, ovph_run_opts *local) {
+  if (!given) {
+    ovph_run_opts_defaults(local);
+    return local;
+  }
+  return given->size == sizeof(ovph_run_opts) ? given : nullptr;
 }
 
+struct HarnessState {
+  std::shared_ptr<State> state;
+  std::vector<double> times;  // of the clones, oldest first
+  std::vector<std::shared_ptr<Landmark>> landmarks;
+  std::vector<std::shared_ptr<Vec>> planes;
+  std::vector<std::shared_ptr<Type>> order;  // imu, dt, calib0, intr0, [calib1, intr1], clones, landmarks, planes (= synth.state_layout)
+};
+
+// What a State is built from.  Where the entries differ, the difference is a member here.
+struct StateSpec {
+  int C = 0;
+  const double *clone_q = nullptr, *clone_p = nullptr;          // [C][4], [C][3], oldest first
+  const double *clone_q_fej = nullptr, *clone_p_fej = nullptr;  // nullptr: first estimate = value
+  const double *calib_q = nullptr, *calib_p = nullptr, *intr = nullptr;  // camera 0; nullptr: what State's constructor gave it
+  bool second_camera = false;  // camera 1 of the options (cam1_q / cam1_p / cam1_intr), its variables behind camera 0's
+  bool set_fej = true;         // false (ovph_format_state_files): values only, no first estimate is written anywhere
+  // IMU value at t_state (propagation / ZUPT / sequence entries).  With it the window ends one camera period (0.1) before t_state
+  // - clone i at t_state - 0.1 (C - i) - and the state's time and camera time offset are set; without it clone i is at 100 + 0.1 i
+  // and neither is touched.
+  const double *imu_x16 = nullptr, *imu_x16_fej = nullptr;
+  double calib_dt = 0.0, t_state = 0.0;
+  int n_slam = 0;  // SLAM landmarks, GLOBAL_3D, ids 9000 + k
+  const double *slam_p = nullptr, *slam_p_fej = nullptr;  // nullptr: first estimate = value
+  int n_planes = 0;  // planes of the state
+  const double *cp = nullptr, *cp_fej = nullptr;  // nullptr: first estimate = value
+  const size_t *plane_ids = nullptr;              // nullptr: k + 1
+  int N = 0;  // size the covariance must come out at, and the covariance
+  const double *P = nullptr;
+};
+
+VectorXd vec_of(const double *a, int na, const double *b = nullptr, int nb = 0) {
+  VectorXd v(na + nb, 1);
+  for (int k = 0; k < na; ++k) v(k) = a[k];
+  for (int k = 0; k < nb; ++k) v(na + k) = b[k];
+  return v;
+}
+
+// The only place of this file that makes a State.
+int build_harness_state(HarnessState &hs, StateOptions &so, const StateSpec &sp, const ovph_run_opts &o) {
+  if (sp.second_camera) so.num_cameras = 2;
+  hs.state = std::make_shared<State>(so);
+  auto &state = hs.state;
+  auto put = [&](const std::shared_ptr<Type> &var, const VectorXd &v, const VectorXd &vf) {
+    var->set_value(v);
+    if (sp.set_fej) var->set_fej(vf);
+  };
+  state->_cam_fisheye[0] = o.fisheye != 0;
+  if (sp.second_camera) {
+    const VectorXd v1 = vec_of(o.cam1_q, 4, o.cam1_p, 3), iv1 = vec_of(o.cam1_intr, 8);
+    put(state->_calib_IMUtoCAM.at(1), v1, v1);
+    put(state->_cam_intrinsics.at(1), iv1, iv1);
+    state->_cam_fisheye[1] = false;
+  }
+  if (sp.calib_q) {
+    const VectorXd v = vec_of(sp.calib_q, 4, sp.calib_p, 3), iv = vec_of(sp.intr, 8);
+    put(state->_calib_IMUtoCAM.at(0), v, v);
+    put(state->_cam_intrinsics.at(0), iv, iv);
+  }
+  // clones, oldest first, through the reference's own entry point
+  const double w0[3] = {0, 0, 0};
+  const double *qf = sp.clone_q_fej ? sp.clone_q_fej : sp.clone_q, *pf = sp.clone_p_fej ? sp.clone_p_fej : sp.clone_p;
+  hs.times.resize(sp.C);
+  for (int i = 0; i < sp.C; ++i) {
+    put(state->_imu->pose(), vec_of(sp.clone_q + 4 * i, 4, sp.clone_p + 3 * i, 3), vec_of(qf + 4 * i, 4, pf + 3 * i, 3));
+    hs.times[i] = sp.imu_x16 ? sp.t_state - 0.1 * (sp.C - i) : 100.0 + 0.1 * i;
+    state->_timestamp = hs.times[i];
+    StateHelper::augment_clone(state, w0);
+  }
+  // 3-dof variables: grow the covariance through StateHelper::clone of the IMU position (sizes match; the block is overwritten
+  // below), then swap the cloned Vec for the variable type the updaters expect at the same id, or relabel its value
+  for (int k = 0; k < sp.n_slam; ++k) {
+    std::shared_ptr<Type> t = StateHelper::clone(state, state->_imu->p());
+    auto lm = std::make_shared<Landmark>(3);
+    lm->set_local_id(t->id());
+    lm->_featid = 9000 + k;
+    lm->set_from_xyz(sp.slam_p + 3 * k, false);
+    lm->set_from_xyz((sp.slam_p_fej ? sp.slam_p_fej : sp.slam_p) + 3 * k, true);
+    StateTestAccess::replace_last_variable(state, lm);
+    state->_features_SLAM[lm->_featid] = lm;
+    hs.landmarks.push_back(lm);
+  }
+  for (int k = 0; k < sp.n_planes; ++k) {
+    auto pl = std::dynamic_pointer_cast<Vec>(StateHelper::clone(state, state->_imu->p()));
+    if (!pl) return -10;
+    put(pl, vec_of(sp.cp + 3 * k, 3), vec_of((sp.cp_fej ? sp.cp_fej : sp.cp) + 3 * k, 3));
+    state->_features_PLANE[sp.plane_ids ? sp.plane_ids[k] : (size_t)(k + 1)] = pl;
+    hs.planes.push_back(pl);
+  }
+  if (state->max_covariance_size() != sp.N) return -11;
+  if (sp.imu_x16) {
+    put(state->_imu, vec_of(sp.imu_x16, 16), vec_of(sp.imu_x16_fej, 16));
+    const VectorXd dtv = vec_of(&sp.calib_dt, 1);
+    put(state->_calib_dt_CAMtoIMU, dtv, dtv);
+    state->_timestamp = sp.t_state;
+  }
+  auto &order = hs.order;
+  order.push_back(state->_imu);
+  order.push_back(state->_calib_dt_CAMtoIMU);
+  order.push_back(state->_calib_IMUtoCAM.at(0));
+  order.push_back(state->_cam_intrinsics.at(0));
+  if (sp.second_camera) {
+    order.push_back(state->_calib_IMUtoCAM.at(1));
+    order.push_back(state->_cam_intrinsics.at(1));
+  }
+  for (auto &c : state->_clones_IMU) order.push_back(c.second);
+  for (auto &l : hs.landmarks) order.push_back(l);
+  for (auto &p : hs.planes) order.push_back(p);
+  MatrixXd Pm(sp.N, sp.N);
+  memcpy(Pm.data(), sp.P, sizeof(double) * (size_t)sp.N * sp.N);
+  StateHelper::set_initial_covariance(state, Pm, order);
+  return 0;
+}
+
+// Feature f of the batch gets id id0 + f.  cam_of [F][M]: camera of every measurement, or nullptr.  uv_norm [F][M][2]: features as
+// the tracker hands them over - normalised measurements, no position yet; else p_FinG [F][3] (or nullptr)
+std::vector<std::shared_ptr<ov_core::Feature>> make_features(const HarnessState &hs, int F, int M, const float *uv, const int *clone_idx,
+                                                             const int *n_meas, const double *p_FinG, size_t id0, const int *cam_of,
+                                                             const float *uv_norm) {
+  std::vector<std::shared_ptr<ov_core::Feature>> fv;
+  for (int f = 0; f < F; ++f) {
+    auto ft = std::make_shared<ov_core::Feature>();
+    ft->featid = id0 + f;
+    for (int k = 0; k < n_meas[f]; ++k) {
+      ft->timestamps.push_back(hs.times[clone_idx[(size_t)f * M + k]]);
+      ft->uvs.push_back(uv[((size_t)f * M + k) * 2]);
+      ft->uvs.push_back(uv[((size_t)f * M + k) * 2 + 1]);
+      if (cam_of) ft->cam_ids.push_back(cam_of[(size_t)f * M + k]);
+    }
+    if (uv_norm) {
+      for (int k = 0; k < n_meas[f]; ++k) {
+        ft->uvs_norm.push_back(uv_norm[((size_t)f * M + k) * 2]);
+        ft->uvs_norm.push_back(uv_norm[((size_t)f * M + k) * 2 + 1]);
+      }
+    } else if (p_FinG) {
+      memcpy(ft->p_FinG, p_FinG + 3 * f, 3 * sizeof(double));
+    }
+    fv.push_back(ft);
+  }
+  return fv;
+}
+
+// Where export_state copies the state to; a nullptr member is skipped.  P is column-major at the state's size, which goes to n.
+struct StateOut {
+  double *clone_q = nullptr, *clone_p = nullptr, *calib_q = nullptr, *calib_p = nullptr, *intr = nullptr;
+  double *slam_p = nullptr, *cp = nullptr, *P = nullptr;
+  int *n = nullptr;
+};
+
+// The only place of this file that copies clones, calibration, intrinsics, landmarks, planes and the covariance out; camera 1 of a
+// state that has one goes to o.last_cam1.
+void export_state(const HarnessState &hs, const StateOut &out, ovph_run_opts &o) {
+  auto &state = hs.state;
+  int i = 0;
+  for (auto &c : state->_clones_IMU) {
+    if (out.clone_q) memcpy(out.clone_q + 4 * i, c.second->quat(), 4 * sizeof(double));
+    if (out.clone_p) memcpy(out.clone_p + 3 * i, c.second->pos(), 3 * sizeof(double));
+    ++i;
+  }
+  if (out.calib_q) memcpy(out.calib_q, state->_calib_IMUtoCAM.at(0)->quat(), 4 * sizeof(double));
+  if (out.calib_p) memcpy(out.calib_p, state->_calib_IMUtoCAM.at(0)->pos(), 3 * sizeof(double));
+  if (out.intr) memcpy(out.intr, state->_cam_intrinsics.at(0)->value().data(), 8 * sizeof(double));
+  for (size_t k = 0; k < hs.landmarks.size() && out.slam_p; ++k)
+    memcpy(out.slam_p + 3 * k, hs.landmarks[k]->value().data(), 3 * sizeof(double));
+  for (size_t k = 0; k < hs.planes.size() && out.cp; ++k) memcpy(out.cp + 3 * k, hs.planes[k]->value().data(), 3 * sizeof(double));
+  const int n2 = state->max_covariance_size();
+  if (out.P) {
+    MatrixXd Pn = StateHelper::get_full_covariance(state);
+    memcpy(out.P, Pn.data(), sizeof(double) * (size_t)n2 * n2);
+  }
+  if (out.n) *out.n = n2;
+  if (state->_options.num_cameras > 1) {
+    memcpy(o.last_cam1, state->_calib_IMUtoCAM.at(1)->quat(), 4 * sizeof(double));
+    memcpy(o.last_cam1 + 4, state->_calib_IMUtoCAM.at(1)->pos(), 3 * sizeof(double));
+    memcpy(o.last_cam1 + 7, state->_cam_intrinsics.at(1)->value().data(), 8 * sizeof(double));
+  }
+}
+
+NoiseManager noise_of(const double *sigmas4 /* w a wb ab */) {
+  NoiseManager nm;
+  nm.sigma_w = sigmas4[0];
+  nm.sigma_a = sigmas4[1];
+  nm.sigma_wb = sigmas4[2];
+  nm.sigma_ab = sigmas4[3];
+  return nm;
+}
+
+template <class Sink> void feed_imu_rows(Sink &sink, int n_imu, const double *imu /* rows (t, wm, am) */) {
+  for (int i = 0; i < n_imu; ++i) {
+    ov_core::ImuData d;
+    d.timestamp = imu[7 * i];
+    for (int k = 0; k < 3; ++k) {
+      d.wm[k] = imu[7 * i + 1 + k];
+      d.am[k] = imu[7 * i + 4 + k];
+    }
+    sink.feed_imu(d);
+  }
+}
+}  // namespace
+
+// UpdaterMSCKF::update.  In-state planes carry the ids plane_ids_state; the estimates of the planes outside the state are handed
+// over unless the options ask the updater to fit them (fit_planes).  Options read: fisheye, uv_norm, fit_*, cam1_* / cam_of_meas,
+// general_features, general_planes, fused_plane_fit, comm / comm_rank / comm_world / device; written: last_shard, last_cam1.
 extern "C" int ovph_run_msckf_update(int C, const double *clone_q, const double *clone_p, const double *clone_q_fej,
                                      const double *clone_p_fej, const double *calib_q, const double *calib_p,
                                      const double *intr, int n_planes_in_state, const double *cp_state,
@@ -99,168 +276,58 @@ extern "C" int ovph_run_msckf_update(int C, const double *clone_q, const double 
                                      double chi2_mult, double sigma_c, int do_fej,
                                      /* outputs */ double *out_clone_q, double *out_clone_p, double *out_calib_q,
                                      double *out_calib_p, double *out_intr, double *out_cp_state, double *out_P,
-                                     unsigned char *feat_kept, unsigned char *feat_used, unsigned char *feat_deleted) {
+                                     unsigned char *feat_kept, unsigned char *feat_used, unsigned char *feat_deleted,
+                                     ovph_run_opts *opts) {
+  ovph_run_opts dflt, *op = use_opts(opts, &dflt);
+  if (!op) return OVPH_E_OPTS;
+  ovph_run_opts &o = *op;
   StateOptions so;
   so.do_fej = do_fej != 0;
   so.do_calib_camera_pose = so.do_calib_camera_intrinsics = so.do_calib_camera_timeoffset = true;
   so.max_clone_size = C;
   so.use_plane_constraint = so.use_plane_constraint_msckf = true;
   so.sigma_constraint = sigma_c;
-  if (g_fit_planes) {
-    so.plane_msckf_min_feat = g_fit_min_feat;
-    so.plane_msckf_max_cond = g_fit_max_cond;
-    so.planefit_shuffle_variant = g_fit_variant;
+  if (o.fit_planes) {
+    so.plane_msckf_min_feat = o.fit_min_feat;
+    so.plane_msckf_max_cond = o.fit_max_cond;
+    so.planefit_shuffle_variant = o.fit_variant;
   }
   so.max_state_size = N + 8;
   so.max_features = F + 8;
-  so.gpu_device = g_device;
-  so.gpu_general_features = g_general != 0;
-  g_general = 0;
-  so.gpu_general_planes = g_general_planes != 0;
-  g_general_planes = 0;
-  so.gpu_fused_plane_fit = g_fused_plane_fit != 0;
-  g_fused_plane_fit = 0;
-  if (g_cam1_q) so.num_cameras = 2;
-  auto state = std::make_shared<State>(so);
-  state->_cam_fisheye[0] = g_fisheye != 0;
-  if (g_cam1_q) {
-    VectorXd v(7, 1), iv(8, 1);
-    for (int k = 0; k < 4; ++k) v(k) = g_cam1_q[k];
-    for (int k = 0; k < 3; ++k) v(4 + k) = g_cam1_p[k];
-    for (int k = 0; k < 8; ++k) iv(k) = g_cam1_intr[k];
-    state->_calib_IMUtoCAM.at(1)->set_value(v);
-    state->_calib_IMUtoCAM.at(1)->set_fej(v);
-    state->_cam_intrinsics.at(1)->set_value(iv);
-    state->_cam_intrinsics.at(1)->set_fej(iv);
-    state->_cam_fisheye[1] = false;
-  }
-  g_fisheye = 0;
-  // calibration values
-  {
-    VectorXd v(7, 1);
-    for (int k = 0; k < 4; ++k) v(k) = calib_q[k];
-    for (int k = 0; k < 3; ++k) v(4 + k) = calib_p[k];
-    state->_calib_IMUtoCAM.at(0)->set_value(v);
-    state->_calib_IMUtoCAM.at(0)->set_fej(v);
-    VectorXd iv(8, 1);
-    for (int k = 0; k < 8; ++k) iv(k) = intr[k];
-    state->_cam_intrinsics.at(0)->set_value(iv);
-    state->_cam_intrinsics.at(0)->set_fej(iv);
-  }
-  // clones, oldest first, through the reference's own entry point
-  const double w0[3] = {0, 0, 0};
-  std::vector<double> times(C);
-  for (int i = 0; i < C; ++i) {
-    VectorXd v(7, 1), vf(7, 1);
-    for (int k = 0; k < 4; ++k) {
-      v(k) = clone_q[4 * i + k];
-      vf(k) = clone_q_fej[4 * i + k];
-    }
-    for (int k = 0; k < 3; ++k) {
-      v(4 + k) = clone_p[3 * i + k];
-      vf(4 + k) = clone_p_fej[3 * i + k];
-    }
-    state->_imu->pose()->set_value(v);
-    state->_imu->pose()->set_fej(vf);
-    times[i] = 100.0 + 0.1 * i;
-    state->_timestamp = times[i];
-    StateHelper::augment_clone(state, w0);
-  }
-  // in-state planes: grow the state by cloning the 3-dof position block of the IMU (sizes match), then relabel the new
-  // variable's value; the covariance is overwritten below
-  std::vector<std::shared_ptr<Vec>> planes;
-  for (int k = 0; k < n_planes_in_state; ++k) {
-    std::shared_ptr<Type> t = StateHelper::clone(state, state->_imu->p());
-    auto pl = std::dynamic_pointer_cast<Vec>(t);
-    if (!pl) return -10;
-    VectorXd v(3, 1), vf(3, 1);
-    for (int a = 0; a < 3; ++a) {
-      v(a) = cp_state[3 * k + a];
-      vf(a) = cp_state_fej[3 * k + a];
-    }
-    pl->set_value(v);
-    pl->set_fej(vf);
-    state->_features_PLANE[plane_ids_state[k]] = pl;
-    planes.push_back(pl);
-  }
-  if (!g_fit_planes)  // otherwise UpdaterMSCKF::update fits / refines the planes itself (UpdaterMSCKF.cpp:196-400)
+  so.gpu_device = o.device;
+  so.gpu_general_features = o.general_features != 0;
+  so.gpu_general_planes = o.general_planes != 0;
+  so.gpu_fused_plane_fit = o.fused_plane_fit != 0;
+  StateSpec sp;
+  sp.C = C, sp.clone_q = clone_q, sp.clone_p = clone_p, sp.clone_q_fej = clone_q_fej, sp.clone_p_fej = clone_p_fej;
+  sp.calib_q = calib_q, sp.calib_p = calib_p, sp.intr = intr, sp.second_camera = o.cam1_q != nullptr;
+  sp.n_planes = n_planes_in_state, sp.cp = cp_state, sp.cp_fej = cp_state_fej, sp.plane_ids = plane_ids_state;
+  sp.N = N, sp.P = P;
+  HarnessState hs;
+  if (int rc = build_harness_state(hs, so, sp, o)) return rc;
+  auto &state = hs.state;
+  if (!o.fit_planes)  // otherwise UpdaterMSCKF::update fits / refines the planes itself (UpdaterMSCKF.cpp:196-400)
     for (int k = 0; k < n_planes_out; ++k)
       state->_plane_estimates_cp_inG[plane_ids_out[k]] = {cp_out[3 * k], cp_out[3 * k + 1], cp_out[3 * k + 2]};
-  if (state->max_covariance_size() != N) return -11;
-  {
-    std::vector<std::shared_ptr<Type>> order;
-    order.push_back(state->_imu);
-    order.push_back(state->_calib_dt_CAMtoIMU);
-    order.push_back(state->_calib_IMUtoCAM.at(0));
-    order.push_back(state->_cam_intrinsics.at(0));
-    if (g_cam1_q) {
-      order.push_back(state->_calib_IMUtoCAM.at(1));
-      order.push_back(state->_cam_intrinsics.at(1));
-    }
-    for (auto &c : state->_clones_IMU) order.push_back(c.second);
-    for (auto &p : planes) order.push_back(p);
-    MatrixXd Pm(N, N);
-    memcpy(Pm.data(), P, sizeof(double) * (size_t)N * N);
-    StateHelper::set_initial_covariance(state, Pm, order);
-  }
-  // features
-  std::vector<std::shared_ptr<ov_core::Feature>> fv, fextra, fused;
+  // unlike ovph_run_updater, the camera of a measurement is handed on whenever it is given, second camera or not
+  auto fv = make_features(hs, F, M, uv, clone_idx, n_meas, p_FinG, 5000, o.cam_of_meas, o.uv_norm);
+  const auto all = fv;
+  std::vector<std::shared_ptr<ov_core::Feature>> fextra, fused;
   std::map<size_t, size_t> feat2plane;
-  for (int f = 0; f < F; ++f) {
-    auto ft = std::make_shared<ov_core::Feature>();
-    ft->featid = 5000 + f;
-    for (int k = 0; k < n_meas[f]; ++k) {
-      ft->timestamps.push_back(times[clone_idx[(size_t)f * M + k]]);
-      ft->uvs.push_back(uv[((size_t)f * M + k) * 2]);
-      ft->uvs.push_back(uv[((size_t)f * M + k) * 2 + 1]);
-      if (g_cam_of_meas) ft->cam_ids.push_back(g_cam_of_meas[(size_t)f * M + k]);
-    }
-    if (g_uv_norm) {
-      for (int k = 0; k < n_meas[f]; ++k) {
-        ft->uvs_norm.push_back(g_uv_norm[((size_t)f * M + k) * 2]);
-        ft->uvs_norm.push_back(g_uv_norm[((size_t)f * M + k) * 2 + 1]);
-      }
-    } else {
-      memcpy(ft->p_FinG, p_FinG + 3 * f, 3 * sizeof(double));
-    }
-    if (plane_of_feat[f] > 0) feat2plane[ft->featid] = (size_t)plane_of_feat[f];
-    fv.push_back(ft);
-  }
-  std::vector<std::shared_ptr<ov_core::Feature>> all = fv;
+  for (int f = 0; f < F; ++f)
+    if (plane_of_feat[f] > 0) feat2plane[5000 + f] = (size_t)plane_of_feat[f];
   UpdaterOptions uo;
   uo.sigma_pix = sigma_px;
   uo.chi2_multipler = chi2_mult;
   ov_core::FeatureInitializerOptions fio;
   UpdaterMSCKF updater(uo, fio);
-  if (g_comm || g_comm_world > 1) updater.set_communicator(g_comm, g_comm_rank, g_comm_world);
+  if (o.comm || o.comm_world > 1) updater.set_communicator(o.comm, o.comm_rank, o.comm_world);
   updater.update(state, fv, fextra, fused, feat2plane);
-  updater.last_shard(g_last_shard[0], g_last_shard[1]);
-  if (g_cam1_q) {
-    memcpy(g_last_cam1, state->_calib_IMUtoCAM.at(1)->quat(), 4 * sizeof(double));
-    memcpy(g_last_cam1 + 4, state->_calib_IMUtoCAM.at(1)->pos(), 3 * sizeof(double));
-    memcpy(g_last_cam1 + 7, state->_cam_intrinsics.at(1)->value().data(), 8 * sizeof(double));
-  }
-  g_cam1_q = g_cam1_p = g_cam1_intr = nullptr;
-  g_cam_of_meas = nullptr;
-  g_comm = nullptr;
-  g_comm_rank = 0;
-  g_comm_world = 1;
-  g_device = 0;
-  g_uv_norm = nullptr;
-  g_fit_planes = 0;
-  // outputs
-  int i = 0;
-  for (auto &c : state->_clones_IMU) {
-    memcpy(out_clone_q + 4 * i, c.second->quat(), 4 * sizeof(double));
-    memcpy(out_clone_p + 3 * i, c.second->pos(), 3 * sizeof(double));
-    ++i;
-  }
-  memcpy(out_calib_q, state->_calib_IMUtoCAM.at(0)->quat(), 4 * sizeof(double));
-  memcpy(out_calib_p, state->_calib_IMUtoCAM.at(0)->pos(), 3 * sizeof(double));
-  memcpy(out_intr, state->_cam_intrinsics.at(0)->value().data(), 8 * sizeof(double));
-  for (int k = 0; k < n_planes_in_state; ++k) memcpy(out_cp_state + 3 * k, planes[k]->value().data(), 3 * sizeof(double));
-  MatrixXd Pn = StateHelper::get_full_covariance(state);
-  memcpy(out_P, Pn.data(), sizeof(double) * (size_t)N * N);
+  updater.last_shard(o.last_shard[0], o.last_shard[1]);
+  StateOut out;
+  out.clone_q = out_clone_q, out.clone_p = out_clone_p, out.calib_q = out_calib_q, out.calib_p = out_calib_p, out.intr = out_intr;
+  out.cp = out_cp_state, out.P = out_P;
+  export_state(hs, out, o);
   for (int f = 0; f < F; ++f) {
     feat_kept[f] = 0;
     feat_used[f] = 0;
@@ -271,46 +338,30 @@ extern "C" int ovph_run_msckf_update(int C, const double *clone_q, const double 
   return 0;
 }
 
-
-// Harness for StateHelper::initialize: state with C clones + calibration, covariance P (N x N), a new Vec(k) variable.
-// order_ids[n_order] select the measuring variables by Type::id() (clones / calibration / intrinsics).
+// Harness for StateHelper::initialize: state with C clones (first estimate = value) and the calibration State's constructor gives,
+// covariance P (N x N), a new Vec(k) variable.  order_ids[n_order] select the measuring variables by Type::id() (clones /
+// calibration / intrinsics).  Options read: fisheye.
 extern "C" int ovph_run_initialize(int C, const double *clone_q, const double *clone_p, int N, const double *P, int n_order,
                                    const int *order_ids, int rows, int cols, const double *H_R, int k, const double *H_L,
                                    const double *res, double r_iso, double chi2_mult, const double *new_value0,
                                    double *out_P /* (N+k)^2 */, double *out_new_value, double *out_clone_q,
-                                   double *out_clone_p, double *out_calib_p, double *out_intr) {
+                                   double *out_clone_p, double *out_calib_p, double *out_intr, ovph_run_opts *opts) {
+  ovph_run_opts dflt, *op = use_opts(opts, &dflt);
+  if (!op) return OVPH_E_OPTS;
   StateOptions so;
   so.do_calib_camera_pose = so.do_calib_camera_intrinsics = so.do_calib_camera_timeoffset = true;
   so.max_clone_size = C;
   so.max_state_size = N + 16;
   so.max_features = 16;
-  auto state = std::make_shared<State>(so);
-  const double w0[3] = {0, 0, 0};
-  for (int i = 0; i < C; ++i) {
-    VectorXd v(7, 1);
-    for (int q = 0; q < 4; ++q) v(q) = clone_q[4 * i + q];
-    for (int q = 0; q < 3; ++q) v(4 + q) = clone_p[3 * i + q];
-    state->_imu->pose()->set_value(v);
-    state->_imu->pose()->set_fej(v);
-    state->_timestamp = 100.0 + 0.1 * i;
-    StateHelper::augment_clone(state, w0);
-  }
-  if (state->max_covariance_size() != N) return -11;
-  std::vector<std::shared_ptr<Type>> all;
-  all.push_back(state->_imu);
-  all.push_back(state->_calib_dt_CAMtoIMU);
-  all.push_back(state->_calib_IMUtoCAM.at(0));
-  all.push_back(state->_cam_intrinsics.at(0));
-  for (auto &c : state->_clones_IMU) all.push_back(c.second);
-  {
-    MatrixXd Pm(N, N);
-    memcpy(Pm.data(), P, sizeof(double) * (size_t)N * N);
-    StateHelper::set_initial_covariance(state, Pm, all);
-  }
+  StateSpec sp;
+  sp.C = C, sp.clone_q = clone_q, sp.clone_p = clone_p, sp.N = N, sp.P = P;
+  HarnessState hs;
+  if (int rc = build_harness_state(hs, so, sp, *op)) return rc;
+  auto &state = hs.state;
   std::vector<std::shared_ptr<Type>> H_order;
   for (int i = 0; i < n_order; ++i) {
     std::shared_ptr<Type> found;
-    for (auto &v : all)
+    for (auto &v : hs.order)
       if (v->id() == order_ids[i]) found = v;
     if (!found) return -12;
     H_order.push_back(found);
@@ -322,193 +373,26 @@ extern "C" int ovph_run_initialize(int C, const double *clone_q, const double *c
   memcpy(r.data(), res, sizeof(double) * rows);
   for (int i = 0; i < rows; ++i) R(i, i) = r_iso;
   auto nv = std::make_shared<Vec>(k);
-  VectorXd v0(k, 1);
-  for (int i = 0; i < k; ++i) v0(i) = new_value0[i];
+  const VectorXd v0 = vec_of(new_value0, k);
   nv->set_value(v0);
   nv->set_fej(v0);
   const bool ok = StateHelper::initialize(state, nv, H_order, HR, HL, R, r, chi2_mult, true);
-  const int n2 = state->max_covariance_size();
-  MatrixXd Pn = StateHelper::get_full_covariance(state);
-  memcpy(out_P, Pn.data(), sizeof(double) * (size_t)n2 * n2);
   memcpy(out_new_value, nv->value().data(), sizeof(double) * k);
-  int i = 0;
-  for (auto &c : state->_clones_IMU) {
-    memcpy(out_clone_q + 4 * i, c.second->quat(), 4 * sizeof(double));
-    memcpy(out_clone_p + 3 * i, c.second->pos(), 3 * sizeof(double));
-    ++i;
-  }
-  memcpy(out_calib_p, state->_calib_IMUtoCAM.at(0)->pos(), 3 * sizeof(double));
-  memcpy(out_intr, state->_cam_intrinsics.at(0)->value().data(), 8 * sizeof(double));
+  StateOut out;
+  out.clone_q = out_clone_q, out.clone_p = out_clone_p, out.calib_p = out_calib_p, out.intr = out_intr, out.P = out_P;
+  export_state(hs, out, *op);
   return ok ? 1 : 0;
 }
 
-// ---- shared state construction for the SLAM / plane-init harnesses ----------------------------------
-namespace ov_plane {
-struct StateTestAccess {
-  static void replace_last_variable(std::shared_ptr<State> state, std::shared_ptr<Type> v) { state->_variables.back() = v; }
-};
-}  // namespace ov_plane
-
-namespace {
-struct HarnessState {
-  std::shared_ptr<State> state;
-  std::vector<double> times;
-  std::vector<std::shared_ptr<Landmark>> landmarks;
-  std::vector<std::shared_ptr<Vec>> planes;
-};
-
-// Order of the state: imu, dt, calib, intrinsics, clones (oldest first), SLAM landmarks, planes (= synth.state_layout).
-int build_harness_state(HarnessState &hs, StateOptions &so, int C, const double *clone_q, const double *clone_p,
-                        const double *clone_q_fej, const double *clone_p_fej, const double *calib_q, const double *calib_p,
-                        const double *intr, int n_slam, const double *slam_p, const double *slam_p_fej, int n_planes,
-                        const double *cp, const double *cp_fej, int N, const double *P, bool second_camera = false) {
-  // second_camera: camera 1 of ovph_set_second_camera, its calibration behind camera 0's (= synth.make_stereo_scene's layout)
-  if (second_camera) so.num_cameras = 2;
-  hs.state = std::make_shared<State>(so);
-  auto &state = hs.state;
-  state->_cam_fisheye[0] = g_fisheye != 0;
-  g_fisheye = 0;
-  if (second_camera) {
-    VectorXd v1(7, 1), iv1(8, 1);
-    for (int k = 0; k < 4; ++k) v1(k) = g_cam1_q[k];
-    for (int k = 0; k < 3; ++k) v1(4 + k) = g_cam1_p[k];
-    for (int k = 0; k < 8; ++k) iv1(k) = g_cam1_intr[k];
-    state->_calib_IMUtoCAM.at(1)->set_value(v1);
-    state->_calib_IMUtoCAM.at(1)->set_fej(v1);
-    state->_cam_intrinsics.at(1)->set_value(iv1);
-    state->_cam_intrinsics.at(1)->set_fej(iv1);
-    state->_cam_fisheye[1] = false;
-  }
-  VectorXd v(7, 1);
-  for (int k = 0; k < 4; ++k) v(k) = calib_q[k];
-  for (int k = 0; k < 3; ++k) v(4 + k) = calib_p[k];
-  state->_calib_IMUtoCAM.at(0)->set_value(v);
-  state->_calib_IMUtoCAM.at(0)->set_fej(v);
-  VectorXd iv(8, 1);
-  for (int k = 0; k < 8; ++k) iv(k) = intr[k];
-  state->_cam_intrinsics.at(0)->set_value(iv);
-  state->_cam_intrinsics.at(0)->set_fej(iv);
-  const double w0[3] = {0, 0, 0};
-  hs.times.resize(C);
-  for (int i = 0; i < C; ++i) {
-    VectorXd a(7, 1), af(7, 1);
-    for (int k = 0; k < 4; ++k) {
-      a(k) = clone_q[4 * i + k];
-      af(k) = clone_q_fej[4 * i + k];
-    }
-    for (int k = 0; k < 3; ++k) {
-      a(4 + k) = clone_p[3 * i + k];
-      af(4 + k) = clone_p_fej[3 * i + k];
-    }
-    state->_imu->pose()->set_value(a);
-    state->_imu->pose()->set_fej(af);
-    hs.times[i] = 100.0 + 0.1 * i;
-    state->_timestamp = hs.times[i];
-    StateHelper::augment_clone(state, w0);
-  }
-  // 3-dof variables: grow the covariance through StateHelper::clone (the block is overwritten below), then swap the cloned
-  // Vec for the variable type the updaters expect at the same id
-  for (int k = 0; k < n_slam; ++k) {
-    std::shared_ptr<Type> t = StateHelper::clone(state, state->_imu->p());
-    auto lm = std::make_shared<Landmark>(3);
-    lm->set_local_id(t->id());
-    lm->_featid = 9000 + k;
-    lm->set_from_xyz(slam_p + 3 * k, false);
-    lm->set_from_xyz(slam_p_fej + 3 * k, true);
-    StateTestAccess::replace_last_variable(state, lm);
-    state->_features_SLAM[lm->_featid] = lm;
-    hs.landmarks.push_back(lm);
-  }
-  for (int k = 0; k < n_planes; ++k) {
-    auto pl = std::dynamic_pointer_cast<Vec>(StateHelper::clone(state, state->_imu->p()));
-    if (!pl) return -10;
-    VectorXd a(3, 1), af(3, 1);
-    for (int q = 0; q < 3; ++q) {
-      a(q) = cp[3 * k + q];
-      af(q) = cp_fej[3 * k + q];
-    }
-    pl->set_value(a);
-    pl->set_fej(af);
-    state->_features_PLANE[(size_t)(k + 1)] = pl;
-    hs.planes.push_back(pl);
-  }
-  if (state->max_covariance_size() != N) return -11;
-  std::vector<std::shared_ptr<Type>> order;
-  order.push_back(state->_imu);
-  order.push_back(state->_calib_dt_CAMtoIMU);
-  order.push_back(state->_calib_IMUtoCAM.at(0));
-  order.push_back(state->_cam_intrinsics.at(0));
-  if (second_camera) {
-    order.push_back(state->_calib_IMUtoCAM.at(1));
-    order.push_back(state->_cam_intrinsics.at(1));
-  }
-  for (auto &c : state->_clones_IMU) order.push_back(c.second);
-  for (auto &l : hs.landmarks) order.push_back(l);
-  for (auto &p : hs.planes) order.push_back(p);
-  MatrixXd Pm(N, N);
-  memcpy(Pm.data(), P, sizeof(double) * (size_t)N * N);
-  StateHelper::set_initial_covariance(state, Pm, order);
-  return 0;
-}
-
-std::vector<std::shared_ptr<ov_core::Feature>> make_features(const HarnessState &hs, int F, int M, const float *uv, const int *clone_idx,
-                                                             const int *n_meas, const double *p_FinG, size_t id0,
-                                                             const int *cam_of = nullptr) {
-  std::vector<std::shared_ptr<ov_core::Feature>> fv;
-  for (int f = 0; f < F; ++f) {
-    auto ft = std::make_shared<ov_core::Feature>();
-    ft->featid = id0 + f;
-    for (int k = 0; k < n_meas[f]; ++k) {
-      ft->timestamps.push_back(hs.times[clone_idx[(size_t)f * M + k]]);
-      ft->uvs.push_back(uv[((size_t)f * M + k) * 2]);
-      ft->uvs.push_back(uv[((size_t)f * M + k) * 2 + 1]);
-      if (cam_of) ft->cam_ids.push_back(cam_of[(size_t)f * M + k]);
-    }
-    if (g_uv_norm) {  // features as the tracker hands them over: normalised measurements, no position yet
-      for (int k = 0; k < n_meas[f]; ++k) {
-        ft->uvs_norm.push_back(g_uv_norm[((size_t)f * M + k) * 2]);
-        ft->uvs_norm.push_back(g_uv_norm[((size_t)f * M + k) * 2 + 1]);
-      }
-    } else if (p_FinG) {
-      memcpy(ft->p_FinG, p_FinG + 3 * f, 3 * sizeof(double));
-    }
-    fv.push_back(ft);
-  }
-  return fv;
-}
-
-void export_state(const HarnessState &hs, double *out_clone_q, double *out_clone_p, double *out_calib_q, double *out_calib_p,
-                  double *out_intr, double *out_slam_p, double *out_cp, double *out_P, int *out_n) {
-  auto &state = hs.state;
-  int i = 0;
-  for (auto &c : state->_clones_IMU) {
-    memcpy(out_clone_q + 4 * i, c.second->quat(), 4 * sizeof(double));
-    memcpy(out_clone_p + 3 * i, c.second->pos(), 3 * sizeof(double));
-    ++i;
-  }
-  memcpy(out_calib_q, state->_calib_IMUtoCAM.at(0)->quat(), 4 * sizeof(double));
-  memcpy(out_calib_p, state->_calib_IMUtoCAM.at(0)->pos(), 3 * sizeof(double));
-  memcpy(out_intr, state->_cam_intrinsics.at(0)->value().data(), 8 * sizeof(double));
-  for (size_t k = 0; k < hs.landmarks.size(); ++k) memcpy(out_slam_p + 3 * k, hs.landmarks[k]->value().data(), 3 * sizeof(double));
-  for (size_t k = 0; k < hs.planes.size(); ++k) memcpy(out_cp + 3 * k, hs.planes[k]->value().data(), 3 * sizeof(double));
-  const int n2 = state->max_covariance_size();
-  MatrixXd Pn = StateHelper::get_full_covariance(state);
-  memcpy(out_P, Pn.data(), sizeof(double) * (size_t)n2 * n2);
-  *out_n = n2;
-  if (state->_options.num_cameras > 1) {  // camera 1 (ovph_last_second_camera)
-    memcpy(g_last_cam1, state->_calib_IMUtoCAM.at(1)->quat(), 4 * sizeof(double));
-    memcpy(g_last_cam1 + 4, state->_calib_IMUtoCAM.at(1)->pos(), 3 * sizeof(double));
-    memcpy(g_last_cam1 + 7, state->_cam_intrinsics.at(1)->value().data(), 8 * sizeof(double));
-  }
-}
-}  // namespace
-
-// mode 3: UpdaterMSCKF::update on a state that also holds SLAM landmarks (ids 9000 + k, planes from ovph_set_slam_planes) and
+// mode 3: UpdaterMSCKF::update on a state that also holds SLAM landmarks (ids 9000 + k, planes from the options' slam_plane) and
 // n_planes in-state planes (ids 1..n_planes); the features carry normalised measurements, the updater triangulates, fits and
-// refines (ovph_set_plane_fit must be on).
+// refines (fit_planes must be on).
 // mode 0: UpdaterSLAM::update (feature f observes landmark f, n_slam == F); mode 1: UpdaterSLAM::delayed_init (n_slam == 0,
 // out_new_p [F*3] / out_new_id [F] describe the landmarks that joined the state); mode 2: UpdaterPlane::init_vio_plane
 // (n_planes in-state planes must be 0; cp_out_est [n_planes_out*3] are the upstream plane estimates with ids 1..n).
+// Options read: fisheye, uv_norm, fit_*, cam1_* / cam_of_meas (a stereo state and the camera of every measurement), fused_plane_fit,
+// general_slam, dinit_planes, general_plane_init; slam_rep / slam_anchor (mode 0), feat_rep_slam / p_noplane (mode 1), slam_plane
+// (mode 3); written: last_cam1.
 extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const double *clone_p, const double *clone_q_fej,
                                 const double *clone_p_fej, const double *calib_q, const double *calib_p, const double *intr,
                                 int n_slam, const double *slam_p, const double *slam_p_fej, int n_planes, const double *cp,
@@ -519,7 +403,10 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
                                 /* outputs */ double *out_clone_q, double *out_clone_p, double *out_calib_q, double *out_calib_p,
                                 double *out_intr, double *out_slam_p, double *out_cp, double *out_P, int *out_n,
                                 unsigned char *feat_kept, unsigned char *feat_deleted, unsigned char *lm_should_marg,
-                                int *slam_to_plane, double *out_new_p, int *out_new_id) {
+                                int *slam_to_plane, double *out_new_p, int *out_new_id, ovph_run_opts *opts) {
+  ovph_run_opts dflt, *op = use_opts(opts, &dflt);
+  if (!op) return OVPH_E_OPTS;
+  ovph_run_opts &o = *op;
   StateOptions so;
   so.do_fej = do_fej != 0;
   so.do_calib_camera_pose = so.do_calib_camera_intrinsics = so.do_calib_camera_timeoffset = true;
@@ -528,40 +415,33 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
   so.sigma_constraint = sigma_c;
   so.const_init_multi = const_init_multi;
   so.const_init_chi2 = const_init_chi2;
-  if (g_fit_planes) {
-    so.plane_init_min_feat = so.plane_msckf_min_feat = g_fit_min_feat;
-    so.plane_init_max_cond = so.plane_msckf_max_cond = g_fit_max_cond;
-    so.planefit_shuffle_variant = g_fit_variant;
+  if (o.fit_planes) {
+    so.plane_init_min_feat = so.plane_msckf_min_feat = o.fit_min_feat;
+    so.plane_init_max_cond = so.plane_msckf_max_cond = o.fit_max_cond;
+    so.planefit_shuffle_variant = o.fit_variant;
   }
   so.max_state_size = n_cap;
   so.max_features = F + 8;
-  so.gpu_fused_plane_fit = g_fused_plane_fit != 0;
-  g_fused_plane_fit = 0;
-  so.gpu_general_slam = g_general_slam != 0;
-  g_general_slam = 0;
-  so.gpu_dinit_planes = g_dinit_planes != 0;
-  g_dinit_planes = 0;
-  so.gpu_general_plane_init = g_general_plane_init != 0;
-  g_general_plane_init = 0;
-  // ovph_set_second_camera: a stereo state (camera 1's calibration behind camera 0's) and the camera of every measurement
-  const bool cam1 = g_cam1_q != nullptr;
-  const int *cam_of = g_cam_of_meas;
+  so.gpu_fused_plane_fit = o.fused_plane_fit != 0;
+  so.gpu_general_slam = o.general_slam != 0;
+  so.gpu_dinit_planes = o.dinit_planes != 0;
+  so.gpu_general_plane_init = o.general_plane_init != 0;
+  StateSpec sp;
+  sp.C = C, sp.clone_q = clone_q, sp.clone_p = clone_p, sp.clone_q_fej = clone_q_fej, sp.clone_p_fej = clone_p_fej;
+  sp.calib_q = calib_q, sp.calib_p = calib_p, sp.intr = intr, sp.second_camera = o.cam1_q != nullptr;
+  sp.n_slam = n_slam, sp.slam_p = slam_p, sp.slam_p_fej = slam_p_fej, sp.n_planes = n_planes, sp.cp = cp, sp.cp_fej = cp_fej;
+  sp.N = N, sp.P = P;
   HarnessState hs;
-  int rc = build_harness_state(hs, so, C, clone_q, clone_p, clone_q_fej, clone_p_fej, calib_q, calib_p, intr, n_slam, slam_p,
-                               slam_p_fej, n_planes, cp, cp_fej, N, P, cam1);
-  g_cam1_q = g_cam1_p = g_cam1_intr = nullptr;
-  g_cam_of_meas = nullptr;
-  if (rc) return rc;
+  if (int rc = build_harness_state(hs, so, sp, o)) return rc;
   auto &state = hs.state;
   const size_t id0 = (mode == 0) ? 9000 : 5000;
-  auto fv = make_features(hs, F, M, uv, clone_idx, n_meas, p_FinG, id0, cam1 ? cam_of : nullptr);
+  auto fv = make_features(hs, F, M, uv, clone_idx, n_meas, p_FinG, id0, sp.second_camera ? o.cam_of_meas : nullptr, o.uv_norm);
   auto all = fv;
-  if (g_p_noplane && mode == 1)
+  if (o.p_noplane && mode == 1)
     for (int f = 0; f < F; ++f) {
       fv[f]->has_p_FinG_original = true;
-      memcpy(fv[f]->p_FinG_original, g_p_noplane + 3 * f, 3 * sizeof(double));
+      memcpy(fv[f]->p_FinG_original, o.p_noplane + 3 * f, 3 * sizeof(double));
     }
-  g_p_noplane = nullptr;
   std::map<size_t, size_t> feat2plane;
   for (int f = 0; f < F; ++f)
     if (plane_of_feat && plane_of_feat[f] > 0) feat2plane[id0 + f] = (size_t)plane_of_feat[f];
@@ -570,18 +450,18 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
   uo.chi2_multipler = chi2_mult;
   ua = uo;
   ov_core::FeatureInitializerOptions fio;
+  StateOut out;
+  out.clone_q = out_clone_q, out.clone_p = out_clone_p, out.calib_q = out_calib_q, out.calib_p = out_calib_p, out.intr = out_intr;
+  out.slam_p = out_slam_p, out.cp = out_cp, out.P = out_P, out.n = out_n;
   if (mode == 3) {
-    for (int k = 0; k < n_slam && g_slam_plane; ++k)
-      if (g_slam_plane[k] > 0) feat2plane[9000 + k] = (size_t)g_slam_plane[k];
+    for (int k = 0; k < n_slam && o.slam_plane; ++k)
+      if (o.slam_plane[k] > 0) feat2plane[9000 + k] = (size_t)o.slam_plane[k];
     UpdaterMSCKF up(uo, fio);
     std::vector<std::shared_ptr<ov_core::Feature>> fextra, fused;
     up.update(state, fv, fextra, fused, feat2plane);
-    g_fit_planes = 0;
-    g_uv_norm = nullptr;
-    g_slam_plane = nullptr;
     std::set<size_t> left;
     for (auto &ft : fv) left.insert(ft->featid);
-    export_state(hs, out_clone_q, out_clone_p, out_calib_q, out_calib_p, out_intr, out_slam_p, out_cp, out_P, out_n);
+    export_state(hs, out, o);
     for (int f = 0; f < F; ++f) {
       feat_kept[f] = left.count(id0 + f) ? 1 : 0;
       feat_deleted[f] = all[f]->to_delete ? 1 : 0;
@@ -593,18 +473,18 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
     }
     return 0;
   }
-  if (mode == 0 && g_slam_rep != 0) {
+  if (mode == 0 && o.slam_rep != 0) {
     // re-express the landmarks (built as GLOBAL_3D from their global value / first estimate) in the requested representation
     auto calib = state->_calib_IMUtoCAM.at(0);
-    auto anchor = state->_clones_IMU.at(hs.times[g_slam_anchor]);
+    auto anchor = state->_clones_IMU.at(hs.times[o.slam_anchor]);
     for (auto &lm : hs.landmarks) {
       double pg[3], pgf[3], pa[3], paf[3], t[3];
       lm->get_xyz(false, pg);
       lm->get_xyz(true, pgf);
-      lm->_feat_representation = (LandmarkRepresentation::Representation)g_slam_rep;
+      lm->_feat_representation = (LandmarkRepresentation::Representation)o.slam_rep;
       if (LandmarkRepresentation::is_relative_representation(lm->_feat_representation)) {
         lm->_anchor_cam_id = 0;
-        lm->_anchor_clone_timestamp = hs.times[g_slam_anchor];
+        lm->_anchor_clone_timestamp = hs.times[o.slam_anchor];
         for (int pass = 0; pass < 2; ++pass) {
           const double *R = pass ? anchor->Rot_fej() : anchor->Rot(), *pp = pass ? anchor->pos_fej() : anchor->pos();
           const double *src = pass ? pgf : pg;
@@ -621,15 +501,13 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
         lm->set_from_xyz(pgf, true);
       }
     }
-    g_slam_rep = 0;
   }
   if (mode == 0) {
     UpdaterSLAM up(uo, ua, fio);
     up.update(state, fv, feat2plane);
   } else if (mode == 1) {
     UpdaterSLAM up(uo, ua, fio);
-    state->_options.feat_rep_slam = (LandmarkRepresentation::Representation)g_feat_rep_slam;
-    g_feat_rep_slam = 0;
+    state->_options.feat_rep_slam = (LandmarkRepresentation::Representation)o.feat_rep_slam;
     up.delayed_init(state, fv, feat2plane);
     for (int f = 0; f < F; ++f) {
       out_new_id[f] = -1;
@@ -639,14 +517,12 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
       memcpy(out_new_p + 3 * f, it->second->value().data(), (size_t)it->second->size() * sizeof(double));
     }
   } else {
-    if (!g_fit_planes)  // otherwise init_vio_plane triangulates, fits and refines itself (UpdaterPlane.cpp:76-290)
+    if (!o.fit_planes)  // otherwise init_vio_plane triangulates, fits and refines itself (UpdaterPlane.cpp:76-290)
       for (int k = 0; k < n_planes_out; ++k)
         state->_plane_estimates_cp_inG[(size_t)(k + 1)] = {cp_out_est[3 * k], cp_out_est[3 * k + 1], cp_out_est[3 * k + 2]};
     UpdaterPlane up(uo, fio);
     std::vector<std::shared_ptr<ov_core::Feature>> used;
     up.init_vio_plane(state, fv, used, feat2plane);
-    g_fit_planes = 0;
-    g_uv_norm = nullptr;
     for (int k = 0; k < n_planes_out; ++k) {
       out_new_id[k] = -1;
       auto it = state->_features_PLANE.find((size_t)(k + 1));
@@ -655,7 +531,7 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
       memcpy(out_new_p + 3 * k, it->second->value().data(), 3 * sizeof(double));
     }
   }
-  export_state(hs, out_clone_q, out_clone_p, out_calib_q, out_calib_p, out_intr, out_slam_p, out_cp, out_P, out_n);
+  export_state(hs, out, o);
   for (int f = 0; f < F; ++f) {
     feat_kept[f] = 0;
     feat_deleted[f] = all[f]->to_delete ? 1 : 0;
@@ -668,14 +544,17 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
   return 0;
 }
 
-// Propagator::propagate_and_clone harness: state with C clones (+ calibration), IMU state x16 / x16_fej, covariance P,
-// n_imu readings rows (t, wm, am).  state->_timestamp = t_state, camera time offset dt_cam_imu; propagates to `timestamp`.
+// Propagator::propagate_and_clone harness: state with C clones (first estimate = value; State's own calibration), IMU state
+// x16 / x16_fej, covariance P, n_imu readings rows (t, wm, am).  state->_timestamp = t_state, camera time offset calib_dt;
+// propagates to `timestamp`.
 extern "C" int ovph_run_propagate(int C, const double *clone_q, const double *clone_p, const double *imu_x16, const double *imu_x16_fej,
                                   double calib_dt, int N, const double *P, int n_imu, const double *imu, double t_state,
                                   double timestamp, const double *sigmas4 /* w a wb ab */, double gravity_mag, int use_rk4,
                                   int imu_avg, int do_fej,
                                   /* outputs */ double *out_x16, double *out_x16_fej, double *out_Phi, double *out_Qd, double *out_last_w,
                                   double *out_P /* (N+6)^2 */, double *out_new_clone7) {
+  ovph_run_opts o;
+  ovph_run_opts_defaults(&o);
   StateOptions so;
   so.do_fej = do_fej != 0;
   so.do_calib_camera_pose = so.do_calib_camera_intrinsics = so.do_calib_camera_timeoffset = true;
@@ -684,63 +563,24 @@ extern "C" int ovph_run_propagate(int C, const double *clone_q, const double *cl
   so.imu_avg = imu_avg != 0;
   so.max_state_size = N + 16;
   so.max_features = 16;
-  auto state = std::make_shared<State>(so);
-  const double w0[3] = {0, 0, 0};
-  for (int i = 0; i < C; ++i) {
-    VectorXd v(7, 1);
-    for (int q = 0; q < 4; ++q) v(q) = clone_q[4 * i + q];
-    for (int q = 0; q < 3; ++q) v(4 + q) = clone_p[3 * i + q];
-    state->_imu->pose()->set_value(v);
-    state->_imu->pose()->set_fej(v);
-    state->_timestamp = t_state - 0.1 * (C - i);
-    StateHelper::augment_clone(state, w0);
-  }
-  if (state->max_covariance_size() != N) return -11;
-  VectorXd x(16, 1), xf(16, 1), dtv(1, 1);
-  for (int k = 0; k < 16; ++k) {
-    x(k) = imu_x16[k];
-    xf(k) = imu_x16_fej[k];
-  }
-  state->_imu->set_value(x);
-  state->_imu->set_fej(xf);
-  dtv(0) = calib_dt;
-  state->_calib_dt_CAMtoIMU->set_value(dtv);
-  state->_calib_dt_CAMtoIMU->set_fej(dtv);
-  state->_timestamp = t_state;
-  std::vector<std::shared_ptr<Type>> all;
-  all.push_back(state->_imu);
-  all.push_back(state->_calib_dt_CAMtoIMU);
-  all.push_back(state->_calib_IMUtoCAM.at(0));
-  all.push_back(state->_cam_intrinsics.at(0));
-  for (auto &c : state->_clones_IMU) all.push_back(c.second);
-  MatrixXd Pm(N, N);
-  memcpy(Pm.data(), P, sizeof(double) * (size_t)N * N);
-  StateHelper::set_initial_covariance(state, Pm, all);
-  NoiseManager nm;
-  nm.sigma_w = sigmas4[0];
-  nm.sigma_a = sigmas4[1];
-  nm.sigma_wb = sigmas4[2];
-  nm.sigma_ab = sigmas4[3];
-  Propagator prop(nm, gravity_mag);
-  for (int i = 0; i < n_imu; ++i) {
-    ov_core::ImuData d;
-    d.timestamp = imu[7 * i];
-    for (int k = 0; k < 3; ++k) {
-      d.wm[k] = imu[7 * i + 1 + k];
-      d.am[k] = imu[7 * i + 4 + k];
-    }
-    prop.feed_imu(d);
-  }
+  StateSpec sp;
+  sp.C = C, sp.clone_q = clone_q, sp.clone_p = clone_p, sp.N = N, sp.P = P;
+  sp.imu_x16 = imu_x16, sp.imu_x16_fej = imu_x16_fej, sp.calib_dt = calib_dt, sp.t_state = t_state;
+  HarnessState hs;
+  if (int rc = build_harness_state(hs, so, sp, o)) return rc;
+  auto &state = hs.state;
+  Propagator prop(noise_of(sigmas4), gravity_mag);
+  feed_imu_rows(prop, n_imu, imu);
   prop.propagate_and_clone(state, timestamp);
   memcpy(out_x16, state->_imu->value().data(), 16 * sizeof(double));
   memcpy(out_x16_fej, state->_imu->fej().data(), 16 * sizeof(double));
   memcpy(out_Phi, prop.last_Phi(), 225 * sizeof(double));
   memcpy(out_Qd, prop.last_Qd(), 225 * sizeof(double));
   memcpy(out_last_w, prop.last_w(), 3 * sizeof(double));
-  const int n2 = state->max_covariance_size();
-  if (n2 != N + 6) return -12;
-  MatrixXd Pn = StateHelper::get_full_covariance(state);
-  memcpy(out_P, Pn.data(), sizeof(double) * (size_t)n2 * n2);
+  if (state->max_covariance_size() != N + 6) return -12;
+  StateOut out;
+  out.P = out_P;
+  export_state(hs, out, o);
   auto nc = state->_clones_IMU.at(timestamp);
   memcpy(out_new_clone7, nc->value().data(), 7 * sizeof(double));
   return 0;
@@ -757,49 +597,21 @@ extern "C" int ovph_run_zupt(int C, const double *clone_q, const double *clone_p
                              const float *uv1,
                              /* outputs */ int *out_accepted, double *out_chi2, double *out_x16, double *out_calib_dt, double *out_P,
                              double *out_timestamp, int *out_meas_at_t1) {
+  ovph_run_opts o;
+  ovph_run_opts_defaults(&o);
   StateOptions so;
   so.do_fej = do_fej != 0;
   so.do_calib_camera_pose = so.do_calib_camera_intrinsics = so.do_calib_camera_timeoffset = true;
   so.max_clone_size = C + 1;
   so.max_state_size = N + 16;
   so.max_features = 16;
-  auto state = std::make_shared<State>(so);
-  const double w0[3] = {0, 0, 0};
-  for (int i = 0; i < C; ++i) {
-    VectorXd v(7, 1);
-    for (int q = 0; q < 4; ++q) v(q) = clone_q[4 * i + q];
-    for (int q = 0; q < 3; ++q) v(4 + q) = clone_p[3 * i + q];
-    state->_imu->pose()->set_value(v);
-    state->_imu->pose()->set_fej(v);
-    state->_timestamp = t_state - 0.1 * (C - i);
-    StateHelper::augment_clone(state, w0);
-  }
-  if (state->max_covariance_size() != N) return -11;
-  VectorXd x(16, 1), xf(16, 1), dtv(1, 1);
-  for (int k = 0; k < 16; ++k) {
-    x(k) = imu_x16[k];
-    xf(k) = imu_x16_fej[k];
-  }
-  state->_imu->set_value(x);
-  state->_imu->set_fej(xf);
-  dtv(0) = calib_dt;
-  state->_calib_dt_CAMtoIMU->set_value(dtv);
-  state->_calib_dt_CAMtoIMU->set_fej(dtv);
-  state->_timestamp = t_state;
-  std::vector<std::shared_ptr<Type>> all;
-  all.push_back(state->_imu);
-  all.push_back(state->_calib_dt_CAMtoIMU);
-  all.push_back(state->_calib_IMUtoCAM.at(0));
-  all.push_back(state->_cam_intrinsics.at(0));
-  for (auto &c : state->_clones_IMU) all.push_back(c.second);
-  MatrixXd Pm(N, N);
-  memcpy(Pm.data(), P, sizeof(double) * (size_t)N * N);
-  StateHelper::set_initial_covariance(state, Pm, all);
-  NoiseManager nm;
-  nm.sigma_w = sigmas4[0];
-  nm.sigma_a = sigmas4[1];
-  nm.sigma_wb = sigmas4[2];
-  nm.sigma_ab = sigmas4[3];
+  StateSpec sp;
+  sp.C = C, sp.clone_q = clone_q, sp.clone_p = clone_p, sp.N = N, sp.P = P;
+  sp.imu_x16 = imu_x16, sp.imu_x16_fej = imu_x16_fej, sp.calib_dt = calib_dt, sp.t_state = t_state;
+  HarnessState hs;
+  if (int rc = build_harness_state(hs, so, sp, o)) return rc;
+  auto &state = hs.state;
+  NoiseManager nm = noise_of(sigmas4);
   auto prop = std::make_shared<Propagator>(nm, gravity_mag);
   auto db = std::make_shared<ov_core::FeatureDatabase>();
   for (int f = 0; f < n_tracks; ++f) {
@@ -809,15 +621,7 @@ extern "C" int ovph_run_zupt(int C, const double *clone_q, const double *clone_p
   UpdaterOptions uo;
   uo.chi2_multipler = chi2_mult;
   UpdaterZeroVelocity zupt(uo, nm, db, prop, gravity_mag, max_velocity, noise_mult, max_disparity);
-  for (int i = 0; i < n_imu; ++i) {
-    ov_core::ImuData d;
-    d.timestamp = imu[7 * i];
-    for (int k = 0; k < 3; ++k) {
-      d.wm[k] = imu[7 * i + 1 + k];
-      d.am[k] = imu[7 * i + 4 + k];
-    }
-    zupt.feed_imu(d);
-  }
+  feed_imu_rows(zupt, n_imu, imu);
   for (int k = 0; k < n_calls; ++k) {
     out_accepted[k] = zupt.try_update(state, timestamps[k]) ? 1 : 0;
     out_chi2[k] = zupt.last_chi2();
@@ -825,16 +629,18 @@ extern "C" int ovph_run_zupt(int C, const double *clone_q, const double *clone_p
   memcpy(out_x16, state->_imu->value().data(), 16 * sizeof(double));
   *out_calib_dt = state->_calib_dt_CAMtoIMU->value()(0);
   if (state->max_covariance_size() != N) return -12;
-  MatrixXd Pn = StateHelper::get_full_covariance(state);
-  memcpy(out_P, Pn.data(), sizeof(double) * (size_t)N * N);
+  StateOut out;
+  out.P = out_P;
+  export_state(hs, out, o);
   *out_timestamp = state->_timestamp;
   *out_meas_at_t1 = (int)db->features_containing(timestamps[0]).size();
   return 0;
 }
 
 // StateHelper::marginalize_slam + merge_planes_and_marginalize harness.  State: clones, n_slam landmarks (should_marg flags),
-// n_planes in-state planes (ids 1..n).  merge_pairs [n_pairs x 2] = (old id, new id); active_planes = ids observed by features.
-// Outputs: final P / n, for every plane id 1..n+8 its Type::id() (or -1) and value, landmark ids (or -1).
+// n_planes in-state planes (ids 1..n), every first estimate = value.  merge_pairs [n_pairs x 2] = (old id, new id);
+// active_planes = ids observed by features.
+// Outputs: final P / n, for every plane id 1..n+8 its Type::id() (or -1) and value, landmark ids (or -1).  Options read: fisheye.
 extern "C" int ovph_run_state_maintenance(int C, const double *clone_q, const double *clone_p, const double *calib_q,
                                           const double *calib_p, const double *intr, int n_slam, const double *slam_p,
                                           const unsigned char *should_marg, int n_planes, const double *cp, int N, const double *P,
@@ -842,7 +648,9 @@ extern "C" int ovph_run_state_maintenance(int C, const double *clone_q, const do
                                           double sigma_plane_merge, double plane_merge_chi2, double plane_merge_deg_max,
                                           double *out_P, int *out_n, int *out_plane_state_id /* [n_planes+8] */,
                                           double *out_plane_cp /* [(n_planes+8)*3] */, int *out_slam_state_id,
-                                          int *out_slam_to_plane) {
+                                          int *out_slam_to_plane, ovph_run_opts *opts) {
+  ovph_run_opts dflt, *op = use_opts(opts, &dflt);
+  if (!op) return OVPH_E_OPTS;
   StateOptions so;
   so.do_calib_camera_pose = so.do_calib_camera_intrinsics = so.do_calib_camera_timeoffset = true;
   so.max_clone_size = C;
@@ -852,10 +660,11 @@ extern "C" int ovph_run_state_maintenance(int C, const double *clone_q, const do
   so.plane_merge_deg_max = plane_merge_deg_max;
   so.max_state_size = N + 8;
   so.max_features = 16;
+  StateSpec sp;
+  sp.C = C, sp.clone_q = clone_q, sp.clone_p = clone_p, sp.calib_q = calib_q, sp.calib_p = calib_p, sp.intr = intr;
+  sp.n_slam = n_slam, sp.slam_p = slam_p, sp.n_planes = n_planes, sp.cp = cp, sp.N = N, sp.P = P;
   HarnessState hs;
-  int rc = build_harness_state(hs, so, C, clone_q, clone_p, clone_q, clone_p, calib_q, calib_p, intr, n_slam, slam_p, slam_p,
-                               n_planes, cp, cp, N, P);
-  if (rc) return rc;
+  if (int rc = build_harness_state(hs, so, sp, *op)) return rc;
   auto &state = hs.state;
   for (int k = 0; k < n_slam; ++k) {
     hs.landmarks[k]->should_marg = should_marg[k] != 0;
@@ -867,10 +676,9 @@ extern "C" int ovph_run_state_maintenance(int C, const double *clone_q, const do
   std::map<size_t, std::set<size_t>> plane2oldplane;
   for (int k = 0; k < n_pairs; ++k) plane2oldplane[(size_t)merge_pairs[2 * k + 1]].insert((size_t)merge_pairs[2 * k]);
   StateHelper::merge_planes_and_marginalize(state, feat2plane, plane2oldplane);
-  const int n2 = state->max_covariance_size();
-  MatrixXd Pn = StateHelper::get_full_covariance(state);
-  memcpy(out_P, Pn.data(), sizeof(double) * (size_t)n2 * n2);
-  *out_n = n2;
+  StateOut out;
+  out.P = out_P, out.n = out_n;
+  export_state(hs, out, *op);
   for (int k = 0; k < n_planes + 8; ++k) {
     out_plane_state_id[k] = -1;
     auto it = state->_features_PLANE.find((size_t)(k + 1));
@@ -912,35 +720,12 @@ extern "C" int ovph_run_plane_givens(int op /* 0 nullspace, 1 compress */, int r
   return ro;
 }
 
-// ovph_run_sequence extras: per-frame IMU value [K][16] and IMU pose covariance [K][36] (column-major) after each frame; with
-// uv_norm [F][M][2] the features arrive untriangulated (uvs_norm set, no position) and UpdaterMSCKF::update triangulates them
-static double *g_seq_traj = nullptr, *g_seq_posecov = nullptr;
-static const float *g_seq_uv_norm = nullptr;
-extern "C" void ovph_set_sequence_trace(double *traj, double *posecov, const float *uv_norm) {
-  g_seq_traj = traj;
-  g_seq_posecov = posecov;
-  g_seq_uv_norm = uv_norm;
-}
-// ... planar regularities in the loop: plane id (0 = none) of every feature of the concatenated list -> feat2plane.
-// mode 1: point-on-plane constraints with planes estimated per update (UpdaterMSCKF, planes stay out of the state);
-// mode 2: additionally UpdaterPlane::init_vio_plane before the update (core/VioManager.cpp:583-588), planes join the state
-// (the final covariance is then larger than N and not returned; out_planes_in_state [1] receives how many planes it holds)
-static const int *g_seq_plane = nullptr;
-static int g_seq_plane_mode = 0, g_seq_plane_min_feat = 20;
-static int *g_seq_planes_in_state = nullptr;
-static double g_seq_sigma_c = 0.01;
-extern "C" void ovph_set_sequence_planes(const int *plane_of_feat, int mode, int min_feat, double sigma_c, int *out_planes_in_state) {
-  g_seq_plane = plane_of_feat;
-  g_seq_plane_mode = mode;
-  g_seq_plane_min_feat = min_feat;
-  g_seq_sigma_c = sigma_c;
-  g_seq_planes_in_state = out_planes_in_state;
-}
-
 // Closed loop over several camera frames with the reference's own call order (core/VioManager.cpp:348 propagate_and_clone,
 // :670 UpdaterMSCKF::update, :864-866 marginalize_old_clone): state with C clones, IMU state, covariance P (N = 30 + 6 C).
 // Frame k: propagate + clone to frame_time[k], update with that frame's features (slots index the C+1 clones of the window,
 // oldest first; positions given), marginalize the oldest clone.  Outputs the final filter state and covariance.
+// Options read: seq_traj, seq_posecov, seq_uv_norm, seq_plane, seq_plane_mode, seq_plane_min_feat, seq_sigma_c, fisheye; written:
+// seq_planes_in_state.
 extern "C" int ovph_run_sequence(int C, const double *clone_q, const double *clone_p, const double *clone_q_fej,
                                  const double *clone_p_fej, const double *calib_q, const double *calib_p, const double *intr,
                                  const double *imu_x16, const double *imu_x16_fej, double calib_dt, int N, const double *P,
@@ -949,7 +734,11 @@ extern "C" int ovph_run_sequence(int C, const double *clone_q, const double *clo
                                  int M, const float *uv, const int *clone_slot, const int *n_meas, const double *p_FinG,
                                  double sigma_px, double chi2_mult,
                                  /* outputs */ double *out_clone_q, double *out_clone_p, double *out_x16, double *out_calib_q,
-                                 double *out_calib_p, double *out_intr, double *out_dt, double *out_P, int *n_kept_per_frame) {
+                                 double *out_calib_p, double *out_intr, double *out_dt, double *out_P, int *n_kept_per_frame,
+                                 ovph_run_opts *opts) {
+  ovph_run_opts dflt, *op = use_opts(opts, &dflt);
+  if (!op) return OVPH_E_OPTS;
+  ovph_run_opts &o = *op;
   StateOptions so;
   so.do_fej = do_fej != 0;
   so.do_calib_camera_pose = so.do_calib_camera_intrinsics = so.do_calib_camera_timeoffset = true;
@@ -957,80 +746,23 @@ extern "C" int ovph_run_sequence(int C, const double *clone_q, const double *clo
   so.use_rk4_integration = use_rk4 != 0;
   so.max_state_size = N + 16 + 3 * 16;
   so.max_features = 4096;
-  const int plane_mode = g_seq_plane ? g_seq_plane_mode : 0;
+  const int plane_mode = o.seq_plane ? o.seq_plane_mode : 0;
   if (plane_mode) {
     so.use_plane_constraint = so.use_plane_constraint_msckf = true;
     so.use_plane_constraint_slamu = so.use_plane_constraint_slamd = true;
     so.use_plane_slam_feats = plane_mode == 2;
-    so.sigma_constraint = g_seq_sigma_c;
-    so.plane_init_min_feat = so.plane_msckf_min_feat = g_seq_plane_min_feat;
+    so.sigma_constraint = o.seq_sigma_c;
+    so.plane_init_min_feat = so.plane_msckf_min_feat = o.seq_plane_min_feat;
   }
-  auto state = std::make_shared<State>(so);
-  {
-    VectorXd v(7, 1);
-    for (int k = 0; k < 4; ++k) v(k) = calib_q[k];
-    for (int k = 0; k < 3; ++k) v(4 + k) = calib_p[k];
-    state->_calib_IMUtoCAM.at(0)->set_value(v);
-    state->_calib_IMUtoCAM.at(0)->set_fej(v);
-    VectorXd iv(8, 1);
-    for (int k = 0; k < 8; ++k) iv(k) = intr[k];
-    state->_cam_intrinsics.at(0)->set_value(iv);
-    state->_cam_intrinsics.at(0)->set_fej(iv);
-  }
-  const double w0[3] = {0, 0, 0};
-  for (int i = 0; i < C; ++i) {
-    VectorXd a(7, 1), af(7, 1);
-    for (int k = 0; k < 4; ++k) {
-      a(k) = clone_q[4 * i + k];
-      af(k) = clone_q_fej[4 * i + k];
-    }
-    for (int k = 0; k < 3; ++k) {
-      a(4 + k) = clone_p[3 * i + k];
-      af(4 + k) = clone_p_fej[3 * i + k];
-    }
-    state->_imu->pose()->set_value(a);
-    state->_imu->pose()->set_fej(af);
-    state->_timestamp = t_state - 0.1 * (C - i);
-    StateHelper::augment_clone(state, w0);
-  }
-  if (state->max_covariance_size() != N) return -11;
-  VectorXd x(16, 1), xf(16, 1), dtv(1, 1);
-  for (int k = 0; k < 16; ++k) {
-    x(k) = imu_x16[k];
-    xf(k) = imu_x16_fej[k];
-  }
-  state->_imu->set_value(x);
-  state->_imu->set_fej(xf);
-  dtv(0) = calib_dt;
-  state->_calib_dt_CAMtoIMU->set_value(dtv);
-  state->_calib_dt_CAMtoIMU->set_fej(dtv);
-  state->_timestamp = t_state;
-  {
-    std::vector<std::shared_ptr<Type>> all;
-    all.push_back(state->_imu);
-    all.push_back(state->_calib_dt_CAMtoIMU);
-    all.push_back(state->_calib_IMUtoCAM.at(0));
-    all.push_back(state->_cam_intrinsics.at(0));
-    for (auto &c : state->_clones_IMU) all.push_back(c.second);
-    MatrixXd Pm(N, N);
-    memcpy(Pm.data(), P, sizeof(double) * (size_t)N * N);
-    StateHelper::set_initial_covariance(state, Pm, all);
-  }
-  NoiseManager nm;
-  nm.sigma_w = sigmas4[0];
-  nm.sigma_a = sigmas4[1];
-  nm.sigma_wb = sigmas4[2];
-  nm.sigma_ab = sigmas4[3];
-  Propagator prop(nm, gravity_mag);
-  for (int i = 0; i < n_imu; ++i) {
-    ov_core::ImuData d;
-    d.timestamp = imu[7 * i];
-    for (int k = 0; k < 3; ++k) {
-      d.wm[k] = imu[7 * i + 1 + k];
-      d.am[k] = imu[7 * i + 4 + k];
-    }
-    prop.feed_imu(d);
-  }
+  StateSpec sp;
+  sp.C = C, sp.clone_q = clone_q, sp.clone_p = clone_p, sp.clone_q_fej = clone_q_fej, sp.clone_p_fej = clone_p_fej;
+  sp.calib_q = calib_q, sp.calib_p = calib_p, sp.intr = intr, sp.N = N, sp.P = P;
+  sp.imu_x16 = imu_x16, sp.imu_x16_fej = imu_x16_fej, sp.calib_dt = calib_dt, sp.t_state = t_state;
+  HarnessState hs;
+  if (int rc = build_harness_state(hs, so, sp, o)) return rc;
+  auto &state = hs.state;
+  Propagator prop(noise_of(sigmas4), gravity_mag);
+  feed_imu_rows(prop, n_imu, imu);
   UpdaterOptions uo;
   uo.sigma_pix = sigma_px;
   uo.chi2_multipler = chi2_mult;
@@ -1052,13 +784,13 @@ extern "C" int ovph_run_sequence(int C, const double *clone_q, const double *clo
         ft->uvs.push_back(uv[((size_t)f * M + q) * 2]);
         ft->uvs.push_back(uv[((size_t)f * M + q) * 2 + 1]);
       }
-      if (g_seq_uv_norm) {
-        for (int q = 0; q < 2 * n_meas[f]; ++q) ft->uvs_norm.push_back(g_seq_uv_norm[(size_t)f * M * 2 + q]);
+      if (o.seq_uv_norm) {
+        for (int q = 0; q < 2 * n_meas[f]; ++q) ft->uvs_norm.push_back(o.seq_uv_norm[(size_t)f * M * 2 + q]);
       } else {
         memcpy(ft->p_FinG, p_FinG + 3 * f, 3 * sizeof(double));
       }
       fv.push_back(ft);
-      if (plane_mode && g_seq_plane[f] > 0) feat2plane[ft->featid] = (size_t)g_seq_plane[f];
+      if (plane_mode && o.seq_plane[f] > 0) feat2plane[ft->featid] = (size_t)o.seq_plane[f];
     }
     if (plane_mode == 2) {  // VioManager.cpp:543-600: planar candidates first try to initialise their planes
       std::vector<std::shared_ptr<ov_core::Feature>> fplane, finit_used;
@@ -1075,36 +807,25 @@ extern "C" int ovph_run_sequence(int C, const double *clone_q, const double *clo
     updater.update(state, fv, fextra, fused, feat2plane);  // VioManager.cpp:670
     n_kept_per_frame[k] = (int)fv.size();
     StateHelper::marginalize_old_clone(state);  // VioManager.cpp:864-866
-    if (g_seq_traj) memcpy(g_seq_traj + 16 * (size_t)k, state->_imu->value().data(), 16 * sizeof(double));
-    if (g_seq_posecov) {
+    if (o.seq_traj) memcpy(o.seq_traj + 16 * (size_t)k, state->_imu->value().data(), 16 * sizeof(double));
+    if (o.seq_posecov) {
       std::vector<std::shared_ptr<Type>> po;
       po.push_back(state->_imu->pose());
       MatrixXd Pp = StateHelper::get_marginal_covariance(state, po);
-      memcpy(g_seq_posecov + 36 * (size_t)k, Pp.data(), 36 * sizeof(double));
+      memcpy(o.seq_posecov + 36 * (size_t)k, Pp.data(), 36 * sizeof(double));
     }
   }
-  g_seq_traj = g_seq_posecov = nullptr;
-  g_seq_uv_norm = nullptr;
-  if (g_seq_planes_in_state) *g_seq_planes_in_state = (int)state->_features_PLANE.size();
-  g_seq_plane = nullptr;
-  g_seq_planes_in_state = nullptr;
-  int i = 0;
-  for (auto &c : state->_clones_IMU) {
-    memcpy(out_clone_q + 4 * i, c.second->quat(), 4 * sizeof(double));
-    memcpy(out_clone_p + 3 * i, c.second->pos(), 3 * sizeof(double));
-    ++i;
-  }
-  if (i != C) return -13;
+  o.seq_planes_in_state = (int)state->_features_PLANE.size();
+  if ((int)state->_clones_IMU.size() != C) return -13;
   memcpy(out_x16, state->_imu->value().data(), 16 * sizeof(double));
-  memcpy(out_calib_q, state->_calib_IMUtoCAM.at(0)->quat(), 4 * sizeof(double));
-  memcpy(out_calib_p, state->_calib_IMUtoCAM.at(0)->pos(), 3 * sizeof(double));
-  memcpy(out_intr, state->_cam_intrinsics.at(0)->value().data(), 8 * sizeof(double));
   *out_dt = state->_calib_dt_CAMtoIMU->value()(0);
-  if (plane_mode == 2) return 0;  // planes joined the state: the covariance is larger than the caller's buffer
-  if (state->max_covariance_size() != N) return -12;
-  MatrixXd Pn = StateHelper::get_full_covariance(state);
-  memcpy(out_P, Pn.data(), sizeof(double) * (size_t)N * N);
-  return 0;
+  StateOut out;
+  out.clone_q = out_clone_q, out.clone_p = out_clone_p, out.calib_q = out_calib_q, out.calib_p = out_calib_p, out.intr = out_intr;
+  // plane_mode 2: planes joined the state, the covariance is larger than the caller's buffer and is not returned
+  const bool fits = state->max_covariance_size() == N;
+  if (plane_mode != 2 && fits) out.P = out_P;
+  export_state(hs, out, o);
+  return (plane_mode == 2 || fits) ? 0 : -12;
 }
 
 
@@ -1165,51 +886,27 @@ extern "C" int ovph_trace_copy(const char *in, const char *out) {
   return n;
 }
 
-// needs the device: a state as ovph_run_msckf_update builds it (no planes), one line of each of the three files
+// needs the device: a state as ovph_run_msckf_update builds it (no planes) but with values only - no first estimate is set -, one
+// line of each of the three files
 extern "C" int ovph_format_state_files(int C, const double *clone_q, const double *clone_p, const double *calib_q, const double *calib_p,
                                        const double *intr, int N, const double *P, double timestamp, double dt, int with_gt,
                                        char *est, char *sd, char *gt, int cap) {
   using namespace ov_plane;
+  ovph_run_opts o;
+  ovph_run_opts_defaults(&o);
   StateOptions so;
   so.do_calib_camera_pose = so.do_calib_camera_intrinsics = so.do_calib_camera_timeoffset = true;
   so.max_clone_size = C;
   so.max_state_size = N + 8;
   so.max_features = 16;
-  auto state = std::make_shared<State>(so);
-  {
-    VectorXd v(7, 1);
-    for (int k = 0; k < 4; ++k) v(k) = calib_q[k];
-    for (int k = 0; k < 3; ++k) v(4 + k) = calib_p[k];
-    state->_calib_IMUtoCAM.at(0)->set_value(v);
-    VectorXd iv(8, 1);
-    for (int k = 0; k < 8; ++k) iv(k) = intr[k];
-    state->_cam_intrinsics.at(0)->set_value(iv);
-    VectorXd d(1, 1);
-    d(0) = dt;
-    state->_calib_dt_CAMtoIMU->set_value(d);
-  }
-  const double w0[3] = {0, 0, 0};
-  for (int i = 0; i < C; ++i) {
-    VectorXd v(7, 1);
-    for (int k = 0; k < 4; ++k) v(k) = clone_q[4 * i + k];
-    for (int k = 0; k < 3; ++k) v(4 + k) = clone_p[3 * i + k];
-    state->_imu->pose()->set_value(v);
-    state->_timestamp = 100.0 + 0.1 * i;
-    StateHelper::augment_clone(state, w0);
-  }
+  StateSpec sp;
+  sp.C = C, sp.clone_q = clone_q, sp.clone_p = clone_p, sp.calib_q = calib_q, sp.calib_p = calib_p, sp.intr = intr;
+  sp.set_fej = false, sp.N = N, sp.P = P;
+  HarnessState hs;
+  if (int rc = build_harness_state(hs, so, sp, o)) return rc;
+  auto &state = hs.state;
+  state->_calib_dt_CAMtoIMU->set_value(vec_of(&dt, 1));
   state->_timestamp = timestamp;
-  if (state->max_covariance_size() != N) return -11;
-  {
-    std::vector<std::shared_ptr<Type>> order;
-    order.push_back(state->_imu);
-    order.push_back(state->_calib_dt_CAMtoIMU);
-    order.push_back(state->_calib_IMUtoCAM.at(0));
-    order.push_back(state->_cam_intrinsics.at(0));
-    for (auto &c : state->_clones_IMU) order.push_back(c.second);
-    MatrixXd Pm(N, N);
-    memcpy(Pm.data(), P, sizeof(double) * (size_t)N * N);
-    StateHelper::set_initial_covariance(state, Pm, order);
-  }
   SimTruth sim;
   for (int k = 0; k < 17; ++k) sim.state_gt[k] = 0.5 + 0.125 * k;
   sim.calib_camimu_dt = 0.0123456;
@@ -1227,22 +924,26 @@ extern "C" int ovph_format_state_files(int C, const double *clone_q, const doubl
 
 // UpdaterHelper::get_feature_jacobian_full for ONE feature held in landmark representation `rep` anchored in clone slot
 // anchor_ci (ext LandmarkRepresentation 0..5).  Outputs column-major: H_f [rows x hf_cols], H_x [rows x cols], res [rows],
-// order ids / sizes of the H_x columns.  Needs the device only because a State owns a context.
+// order ids / sizes of the H_x columns.  Needs the device only because a State owns a context.  Options read: fisheye.
 extern "C" int ovph_feature_jacobian_rep(int C, const double *clone_q, const double *clone_p, const double *clone_q_fej,
                                          const double *clone_p_fej, const double *calib_q, const double *calib_p, const double *intr,
                                          int N, const double *P, int m, const float *uv, const int *clone_idx, const double *p_FinG,
                                          int rep, int anchor_ci, double sigma_px, int do_fej, double *H_f, double *H_x, double *res,
-                                         int *rows_out, int *cols_out, int *hf_cols_out, int *order_id, int *order_size, int *n_order) {
+                                         int *rows_out, int *cols_out, int *hf_cols_out, int *order_id, int *order_size, int *n_order,
+                                         ovph_run_opts *opts) {
+  ovph_run_opts dflt, *op = use_opts(opts, &dflt);
+  if (!op) return OVPH_E_OPTS;
   StateOptions so;
   so.do_fej = do_fej != 0;
   so.do_calib_camera_pose = so.do_calib_camera_intrinsics = so.do_calib_camera_timeoffset = true;
   so.max_clone_size = C;
   so.max_state_size = N + 8;
   so.max_features = 16;
+  StateSpec sp;
+  sp.C = C, sp.clone_q = clone_q, sp.clone_p = clone_p, sp.clone_q_fej = clone_q_fej, sp.clone_p_fej = clone_p_fej;
+  sp.calib_q = calib_q, sp.calib_p = calib_p, sp.intr = intr, sp.N = N, sp.P = P;
   HarnessState hs;
-  int rc = build_harness_state(hs, so, C, clone_q, clone_p, clone_q_fej, clone_p_fej, calib_q, calib_p, intr, 0, nullptr, nullptr, 0,
-                               nullptr, nullptr, N, P);
-  if (rc) return rc;
+  if (int rc = build_harness_state(hs, so, sp, *op)) return rc;
   auto &state = hs.state;
   UpdaterHelper::UpdaterHelperFeature feat;
   feat.featid = 5000;
@@ -1287,22 +988,25 @@ extern "C" int ovph_feature_jacobian_rep(int C, const double *clone_q, const dou
 // UpdaterSLAM::change_anchors on a state whose first landmark is held in the anchored representation `rep` (2..4) and anchored
 // in the oldest clone, with one clone more than max_clone_size in the window: the landmark moves to the newest clone.
 // lm_p_FinA / lm_p_FinA_fej: its position in the old anchor camera frame.  Outputs: landmark value / fej (representation
-// parameters), its new anchor clone slot, the covariance.
+// parameters), its new anchor clone slot, the covariance.  Options read: fisheye.
 extern "C" int ovph_run_change_anchors(int C, const double *clone_q, const double *clone_p, const double *clone_q_fej,
                                        const double *clone_p_fej, const double *calib_q, const double *calib_p, const double *intr,
                                        int n_slam, const double *slam_p, int N, const double *P, int rep, const double *lm_p_FinA,
                                        const double *lm_p_FinA_fej, int do_fej, double *out_value, double *out_fej, int *out_anchor_ci,
-                                       double *out_P) {
+                                       double *out_P, ovph_run_opts *opts) {
+  ovph_run_opts dflt, *op = use_opts(opts, &dflt);
+  if (!op) return OVPH_E_OPTS;
   StateOptions so;
   so.do_fej = do_fej != 0;
   so.do_calib_camera_pose = so.do_calib_camera_intrinsics = so.do_calib_camera_timeoffset = true;
   so.max_clone_size = C - 1;
   so.max_state_size = N + 8;
   so.max_features = 16;
+  StateSpec sp;
+  sp.C = C, sp.clone_q = clone_q, sp.clone_p = clone_p, sp.clone_q_fej = clone_q_fej, sp.clone_p_fej = clone_p_fej;
+  sp.calib_q = calib_q, sp.calib_p = calib_p, sp.intr = intr, sp.n_slam = n_slam, sp.slam_p = slam_p, sp.N = N, sp.P = P;
   HarnessState hs;
-  int rc = build_harness_state(hs, so, C, clone_q, clone_p, clone_q_fej, clone_p_fej, calib_q, calib_p, intr, n_slam, slam_p, slam_p, 0,
-                               nullptr, nullptr, N, P);
-  if (rc) return rc;
+  if (int rc = build_harness_state(hs, so, sp, *op)) return rc;
   auto &state = hs.state;
   auto lm = hs.landmarks.at(0);
   lm->_feat_representation = (LandmarkRepresentation::Representation)rep;
@@ -1321,7 +1025,8 @@ extern "C" int ovph_run_change_anchors(int C, const double *clone_q, const doubl
   *out_anchor_ci = -1;
   for (int i = 0; i < C; ++i)
     if (hs.times[i] == lm->_anchor_clone_timestamp) *out_anchor_ci = i;
-  MatrixXd Pn = StateHelper::get_full_covariance(state);
-  memcpy(out_P, Pn.data(), sizeof(double) * (size_t)N * N);
+  StateOut out;
+  out.P = out_P;
+  export_state(hs, out, *op);
   return lm->has_had_anchor_change ? 0 : -20;
 }

@@ -1,0 +1,67 @@
+// Options and per-call results of the test harness over the host mirror (host_capi.cpp; hostlib.RunOpts mirrors the layout).
+// Internal: the harness is not part of the shipped boundary (include/ovplane_hip.h).
+//
+// The harness keeps no state between calls.  Every ovph_run_* entry that takes options takes them as its last argument (NULL =
+// ovph_run_opts_defaults); a struct whose `size` is not sizeof(ovph_run_opts) is refused with OVPH_E_OPTS before anything is
+// touched.  Pointers in the struct are borrowed for the duration of the call only.  An all-zero struct with `size` set behaves as
+// the defaults do: the fields whose default is not zero are only read behind a switch that is off by default.
+#pragma once
+#include <stdint.h>
+
+#define OVPH_E_OPTS (-40)
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct ovph_run_opts {
+  uint32_t size;     // sizeof(ovph_run_opts)
+  int32_t fisheye;   // lens model of camera 0 (0 = radtan, 1 = equidistant)
+  // features arrive with normalised measurements [F][M][2] and NO position: the updater triangulates them itself
+  // (update/UpdaterMSCKF.cpp:120-166) before the update
+  const float *uv_norm;
+  // no plane estimates are handed over, the updater runs plane_fitting / optimize_plane itself
+  int32_t fit_planes, fit_min_feat;
+  double fit_max_cond;
+  int32_t fit_variant;
+  // ovph_run_updater mode 0: hold every landmark in this ext LandmarkRepresentation (1..4), anchored in this clone slot
+  int32_t slam_rep, slam_anchor;
+  int32_t feat_rep_slam;      // mode 1: StateOptions::feat_rep_slam of the landmarks delayed_init creates
+  const int32_t *slam_plane;  // mode 3: plane of every SLAM landmark (0 = none)
+  // a second camera (num_cameras = 2) with these calibration values, its variables behind camera 0's; cam_of_meas [F][M] says
+  // which camera took each measurement of the feature batch
+  const double *cam1_q, *cam1_p, *cam1_intr;
+  const int32_t *cam_of_meas;
+  // StateOptions::gpu_<name>
+  int32_t general_features, general_planes, general_plane_init, fused_plane_fit, general_slam, dinit_planes;
+  const double *p_noplane;  // mode 1: positions before plane refinement of the candidates (Feature::p_FinG_original, [F][3])
+  // ovph_run_msckf_update: the State lives on `device` and the updater takes the sharded point loop on this communicator
+  void *comm;
+  int32_t comm_rank, comm_world, device;
+  // ovph_run_sequence: per-frame IMU value [K][16] and IMU pose covariance [K][36] (column-major) after each frame; with
+  // seq_uv_norm [F][M][2] the features arrive untriangulated
+  double *seq_traj, *seq_posecov;
+  const float *seq_uv_norm;
+  // ... planar regularities in the loop: plane id (0 = none) of every feature of the concatenated list -> feat2plane.
+  // seq_plane_mode 1: point-on-plane constraints with planes estimated per update (UpdaterMSCKF, planes stay out of the state);
+  // 2: additionally UpdaterPlane::init_vio_plane before the update (core/VioManager.cpp:583-588), planes join the state (the final
+  // covariance is then larger than N and not returned)
+  const int32_t *seq_plane;
+  int32_t seq_plane_mode, seq_plane_min_feat;
+  double seq_sigma_c;
+  // ---- results of the call ----
+  int32_t seq_planes_in_state;  // ovph_run_sequence: planes the state holds at the end
+  int32_t last_shard[2];        // ovph_run_msckf_update: this rank's index range of the point batch
+  double last_cam1[15];         // [q (4) | p (3) | intrinsics (8)] of camera 1 after a run that had one (untouched otherwise)
+} ovph_run_opts;
+
+// size set, fit_min_feat = 20, fit_max_cond = 100, comm_world = 1, seq_plane_min_feat = 20, seq_sigma_c = 0.01, the rest zero
+void ovph_run_opts_defaults(ovph_run_opts *o);
+// what a mirror of the struct has to agree with: sizeof, and offsetof of every member in declaration order (returns the member
+// count; writes at most `cap` offsets)
+int ovph_run_opts_size(void);
+int ovph_run_opts_layout(int *offsets, int cap);
+
+#ifdef __cplusplus
+}
+#endif

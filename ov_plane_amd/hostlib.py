@@ -19,7 +19,75 @@ def lib():
             raise ImportError("libovplane_host.so is not built (run __graft_entry__.build())")
         C.CDLL(os.path.join(_HERE, "libovplane_hip.so"), mode=C.RTLD_GLOBAL)
         _LIB = C.CDLL(LIB_PATH)
+        _LIB.ovph_session_open.restype = C.c_void_p
+        _LIB.ovph_set_slam_force_dense.argtypes = [C.c_int]
+        _LIB.ovph_run_opts_defaults.argtypes = [C.POINTER(RunOpts)]
+        _LIB.ovph_run_opts_defaults.restype = None
+        _LIB.ovph_run_opts_layout.argtypes = [C.POINTER(C.c_int), C.c_int]
     return _LIB
+
+
+OVPH_E_OPTS = -40  # an entry was handed a RunOpts whose size is not the library's
+
+
+class RunOpts(C.Structure):
+    """ovph_run_opts (csrc/host/host_capi.h): what an ovph_run_* entry is told beyond its arrays, and what it reports back
+    (last_shard, last_cam1, seq_planes_in_state).  The library keeps nothing between calls and borrows the pointers for the call
+    only; borrow() holds the arrays they point into on this object."""
+    _fields_ = [("size", C.c_uint32), ("fisheye", C.c_int32), ("uv_norm", C.c_void_p), ("fit_planes", C.c_int32),
+                ("fit_min_feat", C.c_int32), ("fit_max_cond", C.c_double), ("fit_variant", C.c_int32), ("slam_rep", C.c_int32),
+                ("slam_anchor", C.c_int32), ("feat_rep_slam", C.c_int32), ("slam_plane", C.c_void_p), ("cam1_q", C.c_void_p),
+                ("cam1_p", C.c_void_p), ("cam1_intr", C.c_void_p), ("cam_of_meas", C.c_void_p), ("general_features", C.c_int32),
+                ("general_planes", C.c_int32), ("general_plane_init", C.c_int32), ("fused_plane_fit", C.c_int32),
+                ("general_slam", C.c_int32), ("dinit_planes", C.c_int32), ("p_noplane", C.c_void_p), ("comm", C.c_void_p),
+                ("comm_rank", C.c_int32), ("comm_world", C.c_int32), ("device", C.c_int32), ("seq_traj", C.c_void_p),
+                ("seq_posecov", C.c_void_p), ("seq_uv_norm", C.c_void_p), ("seq_plane", C.c_void_p), ("seq_plane_mode", C.c_int32),
+                ("seq_plane_min_feat", C.c_int32), ("seq_sigma_c", C.c_double), ("seq_planes_in_state", C.c_int32),
+                ("last_shard", C.c_int32 * 2), ("last_cam1", C.c_double * 15)]
+
+    def __init__(self, sc=None, fit_planes=None, **fields):
+        """The library's defaults; then sc: a synth scene's lens model and second camera (sc.cam1 = dict(calib_q, calib_p, intr),
+        sc.cam_idx [F, M]); fit_planes = dict(min_feat, max_cond, variant); then `fields`, integer members by name."""
+        super().__init__()
+        lib().ovph_run_opts_defaults(C.byref(self))
+        self._held = []
+        if sc is not None:
+            self.fisheye = 1 if sc.get("fisheye", False) else 0
+            cam1 = sc.get("cam1", None)
+            if cam1 is not None:
+                for k in ("calib_q", "calib_p", "intr"):
+                    self.borrow("cam1_" + k.replace("calib_", ""), cam1[k], np.float64)
+                self.borrow("cam_of_meas", sc.cam_idx, np.int32)
+        if fit_planes is not None:
+            self.fit_planes, self.fit_min_feat = 1, int(fit_planes["min_feat"])
+            self.fit_max_cond, self.fit_variant = float(fit_planes["max_cond"]), int(fit_planes.get("variant", 0))
+        for k, v in fields.items():
+            setattr(self, k, int(v))
+
+    def borrow(self, field, array, dtype):
+        """points `field` at `array` (made contiguous, of dtype) and keeps it alive as long as this object"""
+        a = np.ascontiguousarray(array, dtype=dtype)
+        self._held.append(a)
+        setattr(self, field, a.ctypes.data)
+        return a
+
+    def cam1(self):
+        return np.array(self.last_cam1)
+
+
+def run_opts_layout(L=None):
+    """(sizeof, {member: offset}) of ovph_run_opts as the library L (default: lib()) reports them"""
+    L = L or lib()
+    off = (C.c_int * 64)()
+    n = L.ovph_run_opts_layout(off, 64)
+    assert n == len(RunOpts._fields_), (n, len(RunOpts._fields_))
+    return int(L.ovph_run_opts_size()), {f[0]: int(off[i]) for i, f in enumerate(RunOpts._fields_)}
+
+
+def carries_option(name, L=None):
+    """the library L (default: lib()) and RunOpts agree on the struct's size and on where member `name` lies"""
+    size, offsets = run_opts_layout(L)
+    return size == C.sizeof(RunOpts) and name in offsets and getattr(RunOpts, name).offset == offsets[name]
 
 
 def run_msckf_update(sc, triangulate=False, fit_planes=None, comm=None, rank=0, world=1, device=0, general_features=False,
@@ -37,23 +105,11 @@ def run_msckf_update(sc, triangulate=False, fit_planes=None, comm=None, rank=0, 
     fused_plane_fit: StateOptions::gpu_fused_plane_fit - with fit_planes, every plane of the frame is fitted and refined by one
     ovp_plane_fit_refine call, over on-plane features of any camera and any track length."""
     L = lib()
-    L.ovph_set_fused_plane_fit(1 if fused_plane_fit else 0)
-    L.ovph_set_general_features(1 if general_features else 0)
-    L.ovph_set_general_planes(1 if general_planes else 0)
-    cam1 = sc.get("cam1", None)  # synth.make_stereo_scene: dict(calib_q, calib_p, intr), sc.cam_idx [F, M]
-    if cam1 is not None:
-        c1q, c1p, c1i = (np.ascontiguousarray(cam1[k], dtype=np.float64) for k in ("calib_q", "calib_p", "intr"))
-        cam_of = np.ascontiguousarray(sc.cam_idx, dtype=np.int32)
-        L.ovph_set_second_camera(c1q.ctypes.data_as(C.c_void_p), c1p.ctypes.data_as(C.c_void_p), c1i.ctypes.data_as(C.c_void_p),
-                                 cam_of.ctypes.data_as(C.c_void_p))
-    L.ovph_set_shard_comm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    L.ovph_set_shard_comm(C.c_void_p(comm) if comm else None, int(rank), int(world), int(device))
-    L.ovph_set_fisheye(1 if sc.get("fisheye", False) else 0)
-    if fit_planes is not None:
-        L.ovph_set_plane_fit.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int]
-        L.ovph_set_plane_fit(1, int(fit_planes["min_feat"]), float(fit_planes["max_cond"]), int(fit_planes.get("variant", 0)))
-    uvn = np.ascontiguousarray(sc.uv_norm, dtype=np.float32) if triangulate else None
-    L.ovph_set_uv_norm(uvn.ctypes.data_as(C.c_void_p) if triangulate else None)
+    ro = RunOpts(sc, fit_planes, fused_plane_fit=fused_plane_fit, general_features=general_features, general_planes=general_planes,
+                 comm_rank=rank, comm_world=world, device=device)
+    ro.comm = comm if comm else None
+    if triangulate:
+        ro.borrow("uv_norm", sc.uv_norm, np.float32)
     f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
     in_state = np.where(sc.plane_in_state)[0]
     out_state = np.where(~sc.plane_in_state)[0]
@@ -74,24 +130,20 @@ def run_msckf_update(sc, triangulate=False, fit_planes=None, comm=None, rank=0, 
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     cq, cp_, cqf, cpf = f64(sc.clone_q), f64(sc.clone_p), f64(sc.clone_q_fej), f64(sc.clone_p_fej)
     calq, calp, intr = f64(sc.calib_q), f64(sc.calib_p), f64(sc.intr)
-    L.ovph_run_msckf_update.restype = C.c_int
     rc = L.ovph_run_msckf_update(
         C.c_int(sc.C), p(cq), p(cp_), p(cqf), p(cpf), p(calq), p(calp), p(intr), C.c_int(len(in_state)), p(cp_in), p(cpf_in),
         p(ids_in), C.c_int(len(out_state)), p(cp_out), p(ids_out), C.c_int(N), p(P), C.c_int(F), C.c_int(M), p(uv), p(cidx),
         p(nm), p(pf), p(pof), C.c_double(o["sigma_px"]), C.c_double(o["chi2_mult"]), C.c_double(o["sigma_c"]),
         C.c_int(int(o["do_fej"])), p(out["clone_q"]), p(out["clone_p"]), p(out["calib_q"]), p(out["calib_p"]), p(out["intr"]),
-        p(out["cp_state"]), p(out["P"]), p(out["kept"]), p(out["used"]), p(out["deleted"]))
+        p(out["cp_state"]), p(out["P"]), p(out["kept"]), p(out["used"]), p(out["deleted"]), C.byref(ro))
     if rc != 0:
         raise RuntimeError("ovph_run_msckf_update failed with %d" % rc)
     out["cp_state"] = out["cp_state"][: len(in_state)]
     for k in ("kept", "used", "deleted"):
         out[k] = out[k].astype(bool)
-    lo, hi = C.c_int(0), C.c_int(0)
-    L.ovph_last_shard(C.byref(lo), C.byref(hi))
-    out["shard"] = (lo.value, hi.value)
-    if cam1 is not None:
-        c1 = np.zeros(15)
-        L.ovph_last_second_camera(c1.ctypes.data_as(C.c_void_p))
+    out["shard"] = (ro.last_shard[0], ro.last_shard[1])
+    if ro.cam1_q:
+        c1 = ro.cam1()
         out["cam1"] = dict(calib_q=c1[:4].copy(), calib_p=c1[4:7].copy(), intr=c1[7:].copy())
     return out
 
@@ -113,11 +165,10 @@ def run_initialize(sc, order, H_R, H_L, res, r_iso, chi2_mult, new_value0):
     v0 = f64(new_value0)
     out = dict(P=np.zeros((N + k, N + k)), new_value=np.zeros(k), clone_q=np.zeros((sc.C, 4)), clone_p=np.zeros((sc.C, 3)),
                calib_p=np.zeros(3), intr=np.zeros(8))
-    L.ovph_run_initialize.restype = C.c_int
     rc = L.ovph_run_initialize(C.c_int(sc.C), p(cq), p(cp_), C.c_int(N), p(P), C.c_int(len(order)), p(oid), C.c_int(rows),
                                C.c_int(cols), p(HR), C.c_int(k), p(HL), p(r), C.c_double(r_iso), C.c_double(chi2_mult), p(v0),
                                p(out["P"]), p(out["new_value"]), p(out["clone_q"]), p(out["clone_p"]), p(out["calib_p"]),
-                               p(out["intr"]))
+                               p(out["intr"]), None)
     if rc < 0:
         raise RuntimeError("ovph_run_initialize failed with %d" % rc)
     out["ok"] = rc
@@ -126,7 +177,7 @@ def run_initialize(sc, order, H_R, H_L, res, r_iso, chi2_mult, new_value0):
 
 def set_slam_force_dense(on: bool):
     """UpdaterSLAM::update through its dense form (the fallback of batches the device entry refuses) until switched off."""
-    lib().ovph_set_slam_force_dense(C.c_int(1 if on else 0))
+    lib().ovph_set_slam_force_dense(1 if on else 0)
 
 
 # UpdaterSLAM::last_route() (ovph_last_slam_route)
@@ -156,40 +207,24 @@ def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=
     (candidates on those planes stay in the device loop, ovp_slam_delayed_init_planes; route 5).
     """
     L = lib()
-    L.ovph_set_general_slam(1 if general_slam else 0)
-    L.ovph_set_fused_plane_fit(1 if fused_plane_fit else 0)  # StateOptions::gpu_fused_plane_fit (mode "plane_init" with fit_planes)
-    L.ovph_set_dinit_planes(1 if dinit_planes else 0)
-    L.ovph_set_general_plane_init(1 if general_plane_init else 0)
-    pnp_keep = None
+    ro = RunOpts(sc, fit_planes, general_slam=general_slam, fused_plane_fit=fused_plane_fit, dinit_planes=dinit_planes,
+                 general_plane_init=general_plane_init)
     if state_planes:
         assert mode == "slam_delayed_init" and bool(np.all(sc.plane_in_state))
-        pnp_keep = np.ascontiguousarray(sc.get("p_FinG_noplane", sc.p_FinG), dtype=np.float64)
-        L.ovph_set_p_noplane(pnp_keep.ctypes.data_as(C.c_void_p))
-    cam1 = sc.get("cam1", None)
-    cam_keep = None
-    if cam1 is not None:
-        cam_keep = [np.ascontiguousarray(cam1[k], dtype=np.float64) for k in ("calib_q", "calib_p", "intr")]
-        cam_keep.append(np.ascontiguousarray(sc.cam_idx, dtype=np.int32))
-        L.ovph_set_second_camera(*(a.ctypes.data_as(C.c_void_p) for a in cam_keep))
-    L.ovph_set_fisheye(1 if sc.get("fisheye", False) else 0)
+        ro.borrow("p_noplane", sc.get("p_FinG_noplane", sc.p_FinG), np.float64)
     if slam_rep is not None:  # mode "slam_update": (representation, anchor clone slot) of every landmark; out["slam_p"] are its parameters
-        L.ovph_set_slam_rep(int(slam_rep[0]), int(slam_rep[1]))
+        ro.slam_rep, ro.slam_anchor = int(slam_rep[0]), int(slam_rep[1])
     if feat_rep_slam is not None:  # mode "slam_delayed_init": StateOptions::feat_rep_slam; out["new_p"] are landmark parameters
-        L.ovph_set_feat_rep_slam(int(feat_rep_slam))
+        ro.feat_rep_slam = int(feat_rep_slam)
     # "msckf_fit": UpdaterMSCKF::update on a state with SLAM landmarks (slam = dict(p [k,3], p_fej [k,3], plane [k]); the
     # scene must have n_slam = k landmark columns) and the scene's in-state planes; needs fit_planes
     m = {"slam_update": 0, "slam_delayed_init": 1, "plane_init": 2, "msckf_fit": 3}[mode]
-    uvn_keep = None
     if triangulate:
         assert mode == "slam_delayed_init" and fit_planes is None
-        uvn_keep = np.ascontiguousarray(sc.uv_norm, dtype=np.float32)
-        L.ovph_set_uv_norm(uvn_keep.ctypes.data_as(C.c_void_p))
     if fit_planes is not None:
         assert m in (2, 3)
-        uvn_keep = np.ascontiguousarray(sc.uv_norm, dtype=np.float32)
-        L.ovph_set_uv_norm(uvn_keep.ctypes.data_as(C.c_void_p))
-        L.ovph_set_plane_fit.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int]
-        L.ovph_set_plane_fit(1, int(fit_planes["min_feat"]), float(fit_planes["max_cond"]), int(fit_planes.get("variant", 0)))
+    if triangulate or fit_planes is not None:
+        ro.borrow("uv_norm", sc.uv_norm, np.float32)
     f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     N, F, M = int(sc.N), int(sc.F), int(sc.uv.shape[1])
@@ -201,15 +236,13 @@ def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=
     dummy = np.zeros((1, 3))
     slam_p = f64(sc.slam_p if n_slam else dummy)
     slam_pf = f64(sc["p_FinG_fej"] if n_slam else dummy)
-    slam_pl_keep = None
     if m == 3:
         assert fit_planes is not None and slam is not None
         n_slam = len(slam["plane"])
         n_pl_in = int(np.sum(sc.plane_in_state))
         assert sc.plane_in_state[:n_pl_in].all()
         slam_p, slam_pf = f64(slam["p"]), f64(slam["p_fej"])
-        slam_pl_keep = np.ascontiguousarray(slam["plane"], dtype=np.int32)
-        L.ovph_set_slam_planes(slam_pl_keep.ctypes.data_as(C.c_void_p))
+        ro.borrow("slam_plane", slam["plane"], np.int32)
     cp = f64(sc.cp if n_pl_total else dummy)
     cpf = f64(sc.cp_fej if n_pl_total else dummy)
     P = np.asfortranarray(sc.P)
@@ -227,7 +260,6 @@ def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=
                slam_to_plane=np.zeros(F, dtype=np.int32), new_p=np.zeros((nout, 3)), new_id=np.zeros(nout, dtype=np.int32))
     cq, cp_, cqf, cpf_ = f64(sc.clone_q), f64(sc.clone_p), f64(sc.clone_q_fej), f64(sc.clone_p_fej)
     calq, calp, intr = f64(sc.calib_q), f64(sc.calib_p), f64(sc.intr)
-    L.ovph_run_updater.restype = C.c_int
     rc = L.ovph_run_updater(
         C.c_int(m), C.c_int(sc.C), p(cq), p(cp_), p(cqf), p(cpf_), p(calq), p(calp), p(intr), C.c_int(n_slam), p(slam_p),
         p(slam_pf), C.c_int(n_pl_in), p(cp), p(cpf), C.c_int(n_pl_out), p(cp), C.c_int(N), p(P), C.c_int(F), C.c_int(M), p(uv),
@@ -235,16 +267,12 @@ def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=
         C.c_int(int(o["do_fej"])), C.c_double(const_init_multi), C.c_double(const_init_chi2), C.c_int(n_cap),
         p(out["clone_q"]), p(out["clone_p"]), p(out["calib_q"]), p(out["calib_p"]), p(out["intr"]), p(out["slam_p"]),
         p(out["cp"]), p(out["P"]), p(out["n"]), p(out["kept"]), p(out["deleted"]), p(out["should_marg"]),
-        p(out["slam_to_plane"]), p(out["new_p"]), p(out["new_id"]))
-    if triangulate:
-        L.ovph_set_uv_norm(None)
+        p(out["slam_to_plane"]), p(out["new_p"]), p(out["new_id"]), C.byref(ro))
     if rc != 0:
         raise RuntimeError("ovph_run_updater failed with %d" % rc)
     out["route"] = int(L.ovph_last_slam_route())
-    if cam1 is not None:
-        c1 = np.zeros(15)
-        L.ovph_last_second_camera(c1.ctypes.data_as(C.c_void_p))
-        out["cam1"] = c1
+    if ro.cam1_q:
+        out["cam1"] = ro.cam1()
     n2 = int(out["n"][0])
     out["n"] = n2
     out["P"] = np.ascontiguousarray(out["P"].reshape(-1)[: n2 * n2].reshape(n2, n2).T)
@@ -271,7 +299,6 @@ def run_propagate(sc, x, imu, t_state, timestamp, calib_dt, po):
     cq, cp_ = f64(sc.clone_q), f64(sc.clone_p)
     out = dict(x16=np.zeros(16), x16_fej=np.zeros(16), Phi=np.zeros((15, 15)), Q=np.zeros((15, 15)), last_w=np.zeros(3),
                P=np.zeros((N + 6, N + 6)), new_clone=np.zeros(7))
-    L.ovph_run_propagate.restype = C.c_int
     rc = L.ovph_run_propagate(C.c_int(sc.C), p(cq), p(cp_), p(x16), p(x16f), C.c_double(calib_dt), C.c_int(N), p(P),
                               C.c_int(imu.shape[0]), p(imu), C.c_double(t_state), C.c_double(timestamp), p(sig),
                               C.c_double(po["gravity_mag"]), C.c_int(int(po["use_rk4"])), C.c_int(int(po["imu_avg"])),
@@ -307,7 +334,6 @@ def run_zupt(sc, x, imu, t_state, timestamps, calib_dt, po, noise_mult=10.0, chi
     chi2 = np.zeros(len(ts))
     out = dict(x16=np.zeros(16), P=np.zeros((N, N)))
     dt_out, t_out, n_meas = C.c_double(0), C.c_double(0), C.c_int(0)
-    L.ovph_run_zupt.restype = C.c_int
     rc = L.ovph_run_zupt(C.c_int(sc.C), p(cq), p(cp_), p(x16), p(x16f), C.c_double(calib_dt), C.c_int(N), p(P),
                          C.c_int(imu.shape[0]), p(imu), C.c_double(t_state), C.c_int(len(ts)), p(ts), p(sig),
                          C.c_double(po["gravity_mag"]), C.c_int(int(po["do_fej"])), C.c_double(noise_mult), C.c_double(chi2_mult),
@@ -338,12 +364,11 @@ def run_state_maintenance(sc, should_marg, merge_pairs, active_planes, sigma_pla
                slam_to_plane=np.zeros(max(n_slam, 1), dtype=np.int32))
     cq, cp_, calq, calp, intr = f64(sc.clone_q), f64(sc.clone_p), f64(sc.calib_q), f64(sc.calib_p), f64(sc.intr)
     slam_p, cp = f64(sc.slam_p if n_slam else np.zeros((1, 3))), f64(sc.cp if n_pl else np.zeros((1, 3)))
-    L.ovph_run_state_maintenance.restype = C.c_int
     rc = L.ovph_run_state_maintenance(
         C.c_int(sc.C), p(cq), p(cp_), p(calq), p(calp), p(intr), C.c_int(n_slam), p(slam_p), p(sm), C.c_int(n_pl), p(cp),
         C.c_int(N), p(P), C.c_int(mp.shape[0]), p(mp), C.c_int(len(ap)), p(ap), C.c_double(sigma_plane_merge),
         C.c_double(plane_merge_chi2), C.c_double(plane_merge_deg_max), p(out["P"]), p(out["n"]), p(out["plane_id"]),
-        p(out["plane_cp"]), p(out["slam_id"]), p(out["slam_to_plane"]))
+        p(out["plane_cp"]), p(out["slam_id"]), p(out["slam_to_plane"]), None)
     if rc != 0:
         raise RuntimeError("ovph_run_state_maintenance failed with %d" % rc)
     n2 = int(out["n"][0])
@@ -364,7 +389,6 @@ def run_plane_givens(op, H_f, H_x, H_cp, res):
     Hc = np.asfortranarray(H_cp if H_cp is not None else np.zeros((rows, 1)), dtype=np.float64).copy(order="F")
     r = np.ascontiguousarray(res, dtype=np.float64).copy()
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    L.ovph_run_plane_givens.restype = C.c_int
     ro = L.ovph_run_plane_givens(C.c_int(op), C.c_int(rows), C.c_int(0 if H_f is None else H_f.shape[1]), p(Hf), C.c_int(cols),
                                  p(Hx), C.c_int(0 if H_cp is None else H_cp.shape[1]), p(Hc), p(r))
     return Hx[:ro].copy(), (Hc[:ro].copy() if H_cp is not None else None), r[:ro].copy()
@@ -422,26 +446,25 @@ def run_sequence(init, imu, frame_time, frames, po, sigma_px=1.0, chi2_mult=1.0,
                intr=np.zeros(8), dt=np.zeros(1), P=np.zeros((N, N)), kept=np.zeros(len(frames), dtype=np.int32))
     K = len(frames)
     traj, posecov = np.zeros((K, 16)), np.zeros((K, 36))
-    uvn = np.ascontiguousarray(np.concatenate(uvn_l), dtype=np.float32) if with_norm else None
-    if trace or with_norm:
-        L.ovph_set_sequence_trace(p(traj) if trace else None, p(posecov) if trace else None, p(uvn) if with_norm else None)
-    n_in_state = C.c_int(0)
+    ro = RunOpts()
+    if trace:
+        ro.seq_traj, ro.seq_posecov = traj.ctypes.data, posecov.ctypes.data
+    if with_norm:
+        ro.borrow("seq_uv_norm", np.concatenate(uvn_l), np.float32)
     if plane_mode:
-        pl = np.ascontiguousarray(np.concatenate([np.asarray(fr["plane"], dtype=np.int32) for fr in frames]), dtype=np.int32)
-        L.ovph_set_sequence_planes(p(pl), C.c_int(int(plane_mode)), C.c_int(int(plane_min_feat)), C.c_double(sigma_c),
-                                   C.byref(n_in_state))
-    L.ovph_run_sequence.restype = C.c_int
+        ro.borrow("seq_plane", np.concatenate([np.asarray(fr["plane"], dtype=np.int32) for fr in frames]), np.int32)
+        ro.seq_plane_mode, ro.seq_plane_min_feat, ro.seq_sigma_c = int(plane_mode), int(plane_min_feat), float(sigma_c)
     rc = L.ovph_run_sequence(
         C.c_int(Cn), p(cq), p(cp_), p(cqf), p(cpf), p(calq), p(calp), p(intr), p(x16), p(x16f), C.c_double(init["dt"]),
         C.c_int(N), p(P), C.c_int(imu.shape[0]), p(imu), C.c_double(init["t_state"]), p(sig), C.c_double(po["gravity_mag"]),
         C.c_int(int(po["use_rk4"])), C.c_int(int(po["do_fej"])), C.c_int(len(frames)), p(ft), p(offs), C.c_int(M), p(uv),
         p(slot), p(nm), p(pf), C.c_double(sigma_px), C.c_double(chi2_mult), p(out["clone_q"]), p(out["clone_p"]), p(out["x16"]),
-        p(out["calib_q"]), p(out["calib_p"]), p(out["intr"]), p(out["dt"]), p(out["P"]), p(out["kept"]))
+        p(out["calib_q"]), p(out["calib_p"]), p(out["intr"]), p(out["dt"]), p(out["P"]), p(out["kept"]), C.byref(ro))
     if rc != 0:
         raise RuntimeError("ovph_run_sequence failed with %d" % rc)
     out["P"] = np.ascontiguousarray(out["P"].T)
     out["dt"] = float(out["dt"][0])
-    out["planes_in_state"] = n_in_state.value
+    out["planes_in_state"] = int(ro.seq_planes_in_state) if plane_mode else 0
     if trace:
         out["traj"] = traj
         out["posecov"] = posecov.reshape(K, 6, 6)   # symmetric: the column-major layout does not matter
@@ -466,11 +489,10 @@ def feature_jacobian_rep(sc, f, rep, anchor_ci):
     H_f, H_x, res = np.zeros(maxr * 3), np.zeros(maxr * maxc), np.zeros(maxr)
     rows, cols, hfc, no = C.c_int(), C.c_int(), C.c_int(), C.c_int()
     oid, osz = np.zeros(m + 4, dtype=np.int32), np.zeros(m + 4, dtype=np.int32)
-    L.ovph_feature_jacobian_rep.restype = C.c_int
     rc = L.ovph_feature_jacobian_rep(C.c_int(sc.C), p(cq), p(cp_), p(cqf), p(cpf_), p(calq), p(calp), p(intr), C.c_int(N), p(P),
                                      C.c_int(m), p(uv), p(cidx), p(pf), C.c_int(rep), C.c_int(anchor_ci),
                                      C.c_double(sc.opts["sigma_px"]), C.c_int(int(sc.opts["do_fej"])), p(H_f), p(H_x), p(res),
-                                     C.byref(rows), C.byref(cols), C.byref(hfc), p(oid), p(osz), C.byref(no))
+                                     C.byref(rows), C.byref(cols), C.byref(hfc), p(oid), p(osz), C.byref(no), None)
     if rc != 0:
         raise RuntimeError("ovph_feature_jacobian_rep failed with %d" % rc)
     r, c, h, n = rows.value, cols.value, hfc.value, no.value
@@ -491,10 +513,9 @@ def run_change_anchors(sc, rep, p_FinA, p_FinA_fej):
     pa, pf = f64(p_FinA), f64(p_FinA_fej)
     out = dict(value=np.zeros(3), fej=np.zeros(3), P=np.zeros((N, N)))
     anchor = C.c_int(-1)
-    L.ovph_run_change_anchors.restype = C.c_int
     rc = L.ovph_run_change_anchors(C.c_int(sc.C), p(cq), p(cp_), p(cqf), p(cpf_), p(calq), p(calp), p(intr), C.c_int(len(slam)),
                                    p(slam), C.c_int(N), p(P), C.c_int(rep), p(pa), p(pf), C.c_int(int(sc.opts["do_fej"])),
-                                   p(out["value"]), p(out["fej"]), C.byref(anchor), p(out["P"]))
+                                   p(out["value"]), p(out["fej"]), C.byref(anchor), p(out["P"]), None)
     if rc != 0:
         raise RuntimeError("ovph_run_change_anchors failed with %d" % rc)
     out["anchor_ci"] = anchor.value
@@ -507,7 +528,6 @@ def load_trajectory(path, cap=200000):
     (sim/Simulator.cpp load_data; data/udel_arl_short.txt is such a file).  Returns [n, 8]."""
     out = np.zeros((cap, 8))
     L = lib()
-    L.ovph_load_trajectory.restype = C.c_int
     n = L.ovph_load_trajectory(str(path).encode(), out.ctypes.data_as(C.c_void_p), C.c_int(cap))
     if n < 0:
         raise FileNotFoundError(path)
@@ -530,7 +550,6 @@ class Session:
         od = f64([po["sigma_w"], po["sigma_a"], po["sigma_wb"], po["sigma_ab"], po["gravity_mag"], sigma_px, chi2_mult,
                   chi2_mult_slam, sigma_c, cam_dt])
         P = np.asfortranarray(init["P"])
-        L.ovph_session_open.restype = C.c_void_p
         self._L = L
         self.C = int(init["C"])
         self.max_slam = max_slam
@@ -564,7 +583,6 @@ class Session:
         """None when the frame has to be processed normally, else dict(x16, posecov, chi2): the zero-velocity update was
         applied and the frame is not cloned."""
         x16, pc, chi2 = np.zeros(16), np.zeros(36), C.c_double(0)
-        self._L.ovph_session_try_zupt.restype = C.c_int
         did = self._L.ovph_session_try_zupt(C.c_void_p(self._h), C.c_double(frame_time), x16.ctypes.data_as(C.c_void_p),
                                             pc.ctypes.data_as(C.c_void_p), C.byref(chi2))
         return dict(x16=x16, posecov=pc.reshape(6, 6), chi2=chi2.value) if did else None
@@ -597,7 +615,6 @@ class Session:
         ids = -np.ones(cap, dtype=np.int64)
         act = None if active_planes is None else np.ascontiguousarray(sorted(set(int(a) for a in active_planes)), dtype=np.int64)
         mrg = np.ascontiguousarray(merged_planes if merged_planes is not None else np.zeros((0, 2)), dtype=np.int64).reshape(-1, 2)
-        self._L.ovph_session_step2.restype = C.c_int
         rc = self._L.ovph_session_step2(C.c_void_p(self._h), C.c_double(frame_time), C.c_int(F), C.c_int(M), p(uv), p(uvn), p(slot),
                                         p(nm), p(gf), p(kd), p(pl), p(counts), p(x16), p(pc), C.c_int(cap), p(ids),
                                         p(np.ascontiguousarray(truth, dtype=np.float64)) if truth is not None else None,
@@ -648,7 +665,6 @@ class Session:
         empty.  pose: what the stage projected with - dict(R_ItoC, p_IinC of camera 0, R_GtoI, p_IinG of the newest clone)."""
         n = C.c_int(0)
         f = self._L.ovph_session_active_tracks
-        f.restype = C.c_int
         rc = f(C.c_void_p(self._h), C.c_int(0), None, None, None, None, C.byref(n))
         if rc < 0:
             raise RuntimeError("ovph_session_active_tracks failed with %d" % rc)

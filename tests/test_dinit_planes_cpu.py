@@ -99,10 +99,8 @@ def test_host_wrapper_takes_the_plane_delayed_init_option():
     build_host()
     from ov_plane_amd import hostlib
 
-    L = hostlib.lib()
-    assert hasattr(L, "ovph_set_dinit_planes") and hasattr(L, "ovph_set_p_noplane")
-    L.ovph_set_dinit_planes(1)
-    L.ovph_set_dinit_planes(0)
+    assert hostlib.carries_option("dinit_planes") and hostlib.carries_option("p_noplane")
+    assert hostlib.RunOpts().dinit_planes == 0 and not hostlib.RunOpts().p_noplane
     assert hostlib.ROUTE_DEVICE_PLANES == 5
     assert (hostlib.ROUTE_NONE, hostlib.ROUTE_DEVICE_GENERAL, hostlib.ROUTE_DEVICE_MONO, hostlib.ROUTE_DENSE_HOST,
             hostlib.ROUTE_HOST_LOOP) == (0, 1, 2, 3, 4)

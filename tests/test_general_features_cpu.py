@@ -54,10 +54,8 @@ def test_host_wrapper_takes_the_general_features_option():
     build_host()
     from ov_plane_amd import hostlib
 
-    L = hostlib.lib()
-    assert hasattr(L, "ovph_set_general_features")
-    L.ovph_set_general_features(1)
-    L.ovph_set_general_features(0)
+    assert hostlib.carries_option("general_features")
+    assert hostlib.RunOpts().general_features == 0 and hostlib.RunOpts(general_features=True).general_features == 1
     import inspect
 
     assert inspect.signature(hostlib.run_msckf_update).parameters["general_features"].default is False

@@ -30,10 +30,11 @@ def test_host_wrapper_takes_the_general_slam_option():
     from ov_plane_amd import hostlib
 
     L = hostlib.lib()
-    assert hasattr(L, "ovph_set_general_slam") and hasattr(L, "ovph_last_slam_route")
-    L.ovph_set_general_slam(1)
-    L.ovph_set_general_slam(0)
-    assert L.ovph_last_slam_route() in (0, 1, 2, 3, 4)
+    assert hostlib.carries_option("general_slam") and hasattr(L, "ovph_last_slam_route")
+    assert hostlib.RunOpts().general_slam == 0 and hostlib.RunOpts(general_slam=True).general_slam == 1
+    # a static of UpdaterSLAM: whatever the last SLAM call of this process took, any Route
+    assert L.ovph_last_slam_route() in (hostlib.ROUTE_NONE, hostlib.ROUTE_DEVICE_GENERAL, hostlib.ROUTE_DEVICE_MONO,
+                                        hostlib.ROUTE_DENSE_HOST, hostlib.ROUTE_HOST_LOOP, hostlib.ROUTE_DEVICE_PLANES)
     params = inspect.signature(hostlib.run_updater).parameters
     assert params["general_slam"].default is False
     assert params["triangulate"].default is False

@@ -105,7 +105,7 @@ def test_host_mirror_switch_is_exported_and_bound():
     from ov_plane_amd.build import build_host
 
     lib = ctypes.CDLL(build_host())
-    assert hasattr(lib, "ovph_set_fused_plane_fit")
+    assert hostlib.carries_option("fused_plane_fit", lib)
     assert inspect.signature(hostlib.run_msckf_update).parameters["fused_plane_fit"].default is False
     assert inspect.signature(hostlib.run_updater).parameters["fused_plane_fit"].default is False
     hdr = open(os.path.join(ROOT, "ov_plane_amd", "csrc", "host", "ov_plane_host.h")).read()

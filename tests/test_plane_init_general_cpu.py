@@ -83,5 +83,5 @@ def test_host_mirror_has_the_option():
     from ov_plane_amd import hostlib
     import inspect
 
-    assert hasattr(hostlib.lib(), "ovph_set_general_plane_init")
+    assert hostlib.carries_option("general_plane_init")
     assert "general_plane_init" in inspect.signature(hostlib.run_updater).parameters
