@@ -178,12 +178,25 @@ def feature_jacobian_full(sc, f, sigma_c=None, p_FinG=None, cp=None, cp_fej=None
     m = int(sc.n_meas[f])
     idx = sc.clone_idx[f, :m]
     ids = sc.ids
-    # which camera took measurement k (synth.make_stereo_scene: sc.cam_idx, sc.cam1); UpdaterHelper.cpp:335-344 loops over the
+    # which camera took measurement k (synth.make_stereo_scene: sc.cam_idx, sc.cam1; sc.cams); UpdaterHelper.cpp:335-344 loops over the
     # cameras of a feature, each with its own extrinsics / intrinsics (State.cpp:52-72)
     cam_of = sc.cam_idx[f, :m] if "cam_idx" in sc else np.zeros(m, dtype=np.int64)
     cams = sorted(set(int(c) for c in cam_of)) or [0]
 
+    # a scene with `cams` (tests/multicam.py: any number of cameras, a lens model each) takes every table from that list; a
+    # `state` given with it carries the list too (its calib_q / intr / cam1 say nothing about cameras 2 and 3, and reading the
+    # scene's list instead would linearise at a calibration the caller meant to replace)
+    if "cams" in sc and state is not None and "cams" not in state:
+        raise ValueError("the scene has `cams`: a `state` override must carry its own `cams` list")
+    cams_tab = st["cams"] if "cams" in sc else None
+
+    def lens(c):
+        return bool(cams_tab[c]["fisheye"]) if cams_tab is not None else bool(sc.get("fisheye", False))
+
     def cam_tables(c):
+        if cams_tab is not None:
+            t = cams_tab[c]
+            return quat_2_rot(t["calib_q"]), np.asarray(t["calib_p"]), np.asarray(t["intr"]), t["calib_id"], t["intr_id"]
         if c == 0:
             return quat_2_rot(st["calib_q"]), np.asarray(st["calib_p"]), np.asarray(st["intr"]), ids["calib"], ids["intr"]
         c1 = state["cam1"] if (state is not None and "cam1" in state) else sc.cam1
@@ -233,7 +246,7 @@ def feature_jacobian_full(sc, f, sigma_c=None, p_FinG=None, cp=None, cp_fej=None
         p_FinIi = R_GtoIi @ (p_f - p_IiinG)
         p_FinCi = R_ItoC @ p_FinIi + p_IinC
         uv_norm = np.array([p_FinCi[0] / p_FinCi[2], p_FinCi[1] / p_FinCi[2]])
-        uv_dist = (equi_distort_d if sc.get("fisheye", False) else radtan_distort_d)(uv_norm, intr)
+        uv_dist = (equi_distort_d if lens(cam) else radtan_distort_d)(uv_norm, intr)
         uv_m = sc.uv[f, k].astype(np.float64)
         res[c : c + 2] = white * (uv_m - uv_dist)
         if o["do_fej"]:
@@ -241,7 +254,7 @@ def feature_jacobian_full(sc, f, sigma_c=None, p_FinG=None, cp=None, cp_fej=None
             p_IiinG = st["clone_p_fej"][ci]
             p_FinIi = R_GtoIi @ (p_f_fej - p_IiinG)
             p_FinCi = R_ItoC @ p_FinIi + p_IinC
-        dz_dzn, dz_dzeta = (equi_distort_jacobian if sc.get("fisheye", False) else radtan_distort_jacobian)(uv_norm, intr)  # non-FEJ uv_norm (:383,389)
+        dz_dzn, dz_dzeta = (equi_distort_jacobian if lens(cam) else radtan_distort_jacobian)(uv_norm, intr)  # non-FEJ uv_norm (:383,389)
         z = p_FinCi[2]
         dzn_dpfc = np.array([[1 / z, 0, -p_FinCi[0] / (z * z)], [0, 1 / z, -p_FinCi[1] / (z * z)]])
         dpfc_dpfg = R_ItoC @ R_GtoIi

@@ -823,8 +823,16 @@ class Context:
     # -- general point features (any camera, long tracks) ---------------------------------------------------------------------
     def cameras_upload(self, sc, state=None):
         """ovp_cameras_upload from a scene: camera 0 = the scene's calibration, camera 1 = sc.cam1 (synth.make_stereo_scene) when
-        present.  `state` overrides the values as in state_upload."""
+        present.  A scene with `cams` (a list of dicts calib_q, calib_p, intr, calib_id, intr_id, fisheye: any number of cameras,
+        a lens model each) uploads that list instead, camera k = cams[k].  `state` overrides the values as in state_upload; for a
+        scene with `cams` it must carry the list as well."""
         s = sc if state is None else state
+        if "cams" in sc:
+            if "cams" not in s:
+                raise ValueError("the scene has `cams`: a `state` override must carry its own `cams` list")
+            self.cameras_upload_tables([(t["calib_q"], t["calib_p"], t["intr"], t["calib_id"], t["intr_id"], 1 if t["fisheye"] else 0)
+                                        for t in s["cams"]])
+            return
         fish = 1 if sc.get("fisheye", False) else 0
         cams = [(s["calib_q"], s["calib_p"], s["intr"], sc.ids["calib"], sc.ids["intr"], fish)]
         c1 = s.get("cam1", None) if state is not None else None

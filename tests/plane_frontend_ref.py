@@ -12,8 +12,12 @@ from ov_plane_amd.synth import quat_2_rot
 
 
 def pose_table(sc):
-    """[C, n_cams, 12] from the scene's quaternions: R_GtoC = R_ItoC R_GtoI, p_CinG = p_IinG - R_GtoC^T p_IinC."""
-    cams = [(sc.calib_q, sc.calib_p)] + ([(sc.cam1["calib_q"], sc.cam1["calib_p"])] if "cam1" in sc else [])
+    """[C, n_cams, 12] from the scene's quaternions: R_GtoC = R_ItoC R_GtoI, p_CinG = p_IinG - R_GtoC^T p_IinC.  A scene with `cams`
+    (tests/multicam.py) gives one column per entry of that list."""
+    if "cams" in sc:
+        cams = [(t["calib_q"], t["calib_p"]) for t in sc.cams]
+    else:
+        cams = [(sc.calib_q, sc.calib_p)] + ([(sc.cam1["calib_q"], sc.cam1["calib_p"])] if "cam1" in sc else [])
     T = np.zeros((sc.C, len(cams), 12))
     for k in range(sc.C):
         RI = quat_2_rot(sc.clone_q[k])

@@ -157,7 +157,9 @@ def triangulate_general_np(sc, f, opts=None):
         return False, np.zeros(3)
     camk = sc.cam_idx[f, :m] if "cam_idx" in sc else np.zeros(m, dtype=int)
     tabs = {0: (_q2R(sc.calib_q), np.asarray(sc.calib_p))}
-    if "cam1" in sc:
+    if "cams" in sc:
+        tabs = {k: (_q2R(t["calib_q"]), np.asarray(t["calib_p"])) for k, t in enumerate(sc.cams)}
+    elif "cam1" in sc:
         tabs[1] = (_q2R(sc.cam1["calib_q"]), np.asarray(sc.cam1["calib_p"]))
     cams = []
     for k in range(m):
