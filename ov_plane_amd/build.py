@@ -58,8 +58,8 @@ def build_lib(force=False, verbose=False):
 
 
 HOST_DIR = os.path.join(CSRC, "host")
-HOST_SOURCES = ["ov_plane_host.cpp", "ov_plane_updaters.cpp", "ov_plane_propagator.cpp", "ov_plane_zupt.cpp", "ov_plane_planefit.cpp", "ov_plane_io.cpp", "ov_plane_session.cpp", "host_capi.cpp"]
-HOST_HEADERS = ["host_capi.h", "ov_plane_host.h", "ov_types.h", "ov_plane_trackplane.h", "ov_plane_activetracks.h", "ov_plane_delaunay.h"]
+HOST_SOURCES = ["ov_plane_host.cpp", "ov_plane_pack.cpp", "ov_plane_updaters.cpp", "ov_plane_propagator.cpp", "ov_plane_zupt.cpp", "ov_plane_planefit.cpp", "ov_plane_io.cpp", "ov_plane_session.cpp", "host_capi.cpp"]
+HOST_HEADERS = ["host_capi.h", "ov_plane_host.h", "ov_plane_pack.h", "ov_types.h", "ov_plane_trackplane.h", "ov_plane_activetracks.h", "ov_plane_delaunay.h"]
 HOST_OUT = os.path.join(_HERE, "libovplane_host.so")
 
 

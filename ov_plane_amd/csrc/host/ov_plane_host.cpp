@@ -1,5 +1,6 @@
 #include "ov_plane_host.h"
 #include "ov_plane_io.h"
+#include "ov_plane_pack.h"
 #include <fstream>
 
 #include <algorithm>
@@ -652,669 +653,463 @@ static bool update_trace_take_header() {
   return h;
 }
 
+// ---- the stages of UpdaterMSCKF::update, in the order of update/UpdaterMSCKF.cpp ---------------------------------------------
+namespace {
+
+// what the device batch can carry: camera 0's measurements, at most OVP_MAX_MEAS of them (one wavefront's rows).  Everything
+// else takes the dense side channel of the point update (ovp_msckf_dense_blocks); in the uploads in front of it (device
+// triangulation, plane loop) such a feature is present with NO measurements, i.e. it takes no part there
+bool fits_batch(const ov_core::Feature &f) { return f.only_camera0() && (int)f.timestamps.size() <= OVP_MAX_MEAS; }
+// StateOptions::gpu_general_features: such a feature takes the general-feature entries instead, when its track fits them
+bool fits_general(const StateOptions &so, const ov_core::Feature &f) {
+  return so.gpu_general_features && (int)f.timestamps.size() <= OVP_GEN_MAX_MEAS;
+}
+
+// the camera-0 batch of the plane loop and of the point update -> device
+FeaturePack upload_batch(const std::shared_ptr<State> &state, const CloneWindow &window, const FeatureVec &fv) {
+  PackSite site;
+  site.which = [](const ov_core::Feature &f) { return fits_batch(f) ? Meas::ALL : Meas::NONE; };
+  FeaturePack b = pack_features(feature_range(fv), window.clone_slot, site);
+  const ovp_feature_batch fb = b.as_feature_batch();
+  gpu_check(ovp_batch_upload(state->gpu(), &fb), "ovp_batch_upload");
+  return b;
+}
+// the features at idx, all of their measurements of every camera, for the general entries (the camera tables go up with it)
+FeaturePack general_batch(const std::shared_ptr<State> &state, const CloneWindow &window, const FeatureVec &fv,
+                          const std::vector<size_t> &idx) {
+  upload_camera_tables(state);
+  PackSite site;
+  site.pad = 0;
+  return pack_features(feature_range(fv, idx), window.clone_slot, site);
+}
+
+// 1. :74-100 (:101-118 for the extra vector)  keep measurements at existing clone times, drop features with < 2 of them
+void window_cleanup(const CloneWindow &window, FeatureVec &fv, bool flag_dropped) {
+  FeatureVec kept;
+  for (auto &ft : fv) {
+    keep_window_measurements(*ft, window.clone_slot);
+    if (ft->timestamps.size() >= 2) kept.push_back(ft);
+    else if (flag_dropped) ft->to_delete = true;
+  }
+  fv = kept;
+}
+
+// 2. :120-166  triangulate (+ refine) the features that arrive with normalised measurements; failures are erased.  A feature
+// the batch cannot carry still takes part with its first OVP_MAX_MEAS measurements of camera 0 (a position estimate needs no
+// more; the update linearises over all of them), or - gpu_general_features - over every camera's observations
+void triangulate(const std::shared_ptr<State> &state, const CloneWindow &window, const ov_core::FeatureInitializerOptions &fio,
+                 FeatureVec &fv) {
+  const StateOptions &so = state->_options;
+  TriangulationSite site;
+  site.mono = [&so](const ov_core::Feature &f) { return fits_batch(f) ? Meas::ALL : fits_general(so, f) ? Meas::NONE : Meas::CAM0_CAPPED; };
+  site.general = [&so](const ov_core::Feature &f) { return !fits_batch(f) && fits_general(so, f); };
+  site.general_pixels = true;
+  triangulate_on_device(state, window, fio, fv, site);
+}
+
+// what stage 3 leaves for the plane loop
+struct PlaneLinPoints {
+  std::map<size_t, std::vector<double>> estimates;  // closest point of every plane that has one
+  std::set<size_t> fitted;                          // planes whose feature set went through the fit
+  std::set<size_t> feat_kept;                       // their surviving features (plane_feats.at(planeid) of :421)
+  std::map<size_t, std::vector<size_t>> slam_kept;  // SLAM landmarks among them (planes outside the state only)
+};
+
+// 3. :196-400 plane linearisation points.
+// Planes in the state: their features are refined against the (fixed) plane.  Other planes: RANSAC fit of the triangulated
+// points, then joint refinement of plane and points; a plane that fails either step is skipped this frame.  Runs when the
+// on-plane features carry normalised measurements (the tracker's uvs_norm) and the caller has not handed estimates over in
+// state->_plane_estimates_cp_inG (the pre-fitted entry point used when the fit happens elsewhere).
+PlaneLinPoints plane_linearisation_points(const std::shared_ptr<State> &state, const UpdaterOptions &options, const CloneWindow &window,
+                                          FeatureVec &feature_vec, FeatureVec &feature_vec_extra, const std::map<size_t, size_t> &feat2plane) {
+  PlaneLinPoints out;
+  out.estimates = state->_plane_estimates_cp_inG;
+  if (!(state->_options.use_plane_constraint && state->_options.use_plane_constraint_msckf && !feat2plane.empty() &&
+        state->_plane_estimates_cp_inG.empty()))
+    return out;
+  std::map<size_t, FeatureVec> plane_feats;  // :198
+  bool all_norm = true;
+  auto collect = [&](FeatureVec &vec) {  // :206-228
+    for (auto &feat : vec) {
+      auto it = feat2plane.find(feat->featid);
+      if (it == feat2plane.end()) continue;
+      // (the per-plane fit / refinement calls know camera 0 and 32 views: such a feature stays a point feature; the fused
+      // call, StateOptions::gpu_fused_plane_fit, takes every camera and any length when the feature has normalised measurements)
+      if (!fits_batch(*feat) && (!state->_options.gpu_fused_plane_fit || feat->uvs_norm.size() != 2 * feat->timestamps.size())) continue;
+      all_norm = all_norm && (feat->uvs_norm.size() == 2 * feat->timestamps.size());
+      plane_feats[it->second].push_back(feat);
+    }
+  };
+  collect(feature_vec);
+  window_cleanup(window, feature_vec_extra, false);  // :101-118 the extra features get the same clean-up as the main vector
+  collect(feature_vec_extra);
+  if (!all_norm || plane_feats.empty()) return out;
+  // :232-252 SLAM features of planes that are not in the state take part in the fit as constants
+  if (state->_options.use_plane_constraint_slamu) {
+    for (auto &lm : state->_features_SLAM) {
+      auto it = feat2plane.find(lm.first);
+      if (it == feat2plane.end() || state->_features_PLANE.count(it->second)) continue;
+      auto bad = state->_features_SLAM_to_PLANE.find(lm.first);
+      if (bad != state->_features_SLAM_to_PLANE.end() && bad->second == 0) continue;
+      auto fp = std::make_shared<ov_core::Feature>();
+      fp->featid = lm.first;
+      lm.second->get_xyz(false, fp->p_FinG);
+      plane_feats[it->second].push_back(fp);
+    }
+  }
+  ClonesInCamera0 cam0 = clones_in_camera0(state);  // :122-141
+  const double focal_length = state->_cam_intrinsics.at(0)->value()(0);  // :269-272
+  const double sigma_px_norm = options.sigma_pix / focal_length;
+  const double sigma_c = state->_options.sigma_constraint;
+  // StateOptions::gpu_fused_plane_fit: fit and refinement of every plane in ONE call (ovp_plane_fit_refine), the camera poses
+  // taken from the resident tables; what follows the two PlaneFitting calls of a plane stays in the loop below
+  const bool fused_fit = state->_options.gpu_fused_plane_fit;
+  std::map<size_t, bool> fused_ok;
+  std::map<size_t, std::vector<double>> fused_cp;
+  if (fused_fit) {
+    upload_camera_tables(state);
+    std::vector<PlaneFitting::FrontPlane> jobs;
+    for (auto &fp : plane_feats) {
+      PlaneFitting::FrontPlane j;
+      j.id = fp.first;
+      j.feats = &fp.second;
+      j.fixed = state->_features_PLANE.count(fp.first) > 0;
+      if (j.fixed)
+        for (int a = 0; a < 3; ++a) j.cp[a] = state->_features_PLANE.at(fp.first)->value()(a);
+      jobs.push_back(j);
+    }
+    PlaneFitting::fit_refine_all(jobs, window.clone_slot, state->_options.plane_msckf_min_feat, state->_options.plane_msckf_max_cond,
+                                 state->_options.use_refine_plane_feat, sigma_px_norm, sigma_c, state->_imu->Rot(), state->_imu->pos());
+    for (auto &j : jobs) {
+      fused_ok[j.id] = j.ok;
+      fused_cp[j.id] = {j.cp[0], j.cp[1], j.cp[2]};
+    }
+  }
+  const bool use_truth = state->_options.use_groundtruths && !state->_true_planes.empty() && !state->_true_features.empty();
+  auto features_to_truth = [&](FeatureVec &feats) {
+    for (auto &ft : feats) {
+      auto itt = state->_true_features.find(ft->featid);
+      if (itt != state->_true_features.end()) memcpy(ft->p_FinG, itt->second.data(), 3 * sizeof(double));
+    }
+  };
+  for (auto &fp : plane_feats) {  // :262-401, std::map order
+    const size_t pid = fp.first;
+    out.fitted.insert(pid);
+    auto &feats = fp.second;
+    double cp[3];
+    if (fused_fit) {
+      if (!fused_ok.at(pid)) continue;
+      for (int a = 0; a < 3; ++a) cp[a] = fused_cp.at(pid)[a];
+    }
+    if (state->_features_PLANE.count(pid)) {  // :265-316
+      auto pl = state->_features_PLANE.at(pid);
+      for (int a = 0; a < 3; ++a) cp[a] = pl->value()(a);
+      if (!fused_fit && state->_options.use_refine_plane_feat &&
+          !PlaneFitting::optimize_plane(feats, cp, cam0.clones_cam, sigma_px_norm, sigma_c, true, cam0.stateI, cam0.calib0))
+        continue;
+      // :284-302 ground truth for the features (the plane itself is a state variable and keeps its estimate)
+      if (use_truth) features_to_truth(feats);
+    } else {
+      if (!fused_fit) {
+        if (feats.size() < 4) continue;  // :320-321
+        double abcd[4];
+        if (!PlaneFitting::plane_fitting(feats, abcd, state->_options.plane_msckf_min_feat, state->_options.plane_msckf_max_cond))
+          continue;  // :325-327
+        for (int a = 0; a < 3; ++a) cp[a] = -abcd[a] * abcd[3];  // :352
+        if (state->_options.use_refine_plane_feat &&
+            !PlaneFitting::optimize_plane(feats, cp, cam0.clones_cam, sigma_px_norm, sigma_c, false, cam0.stateI, cam0.calib0))
+          continue;  // :355-357
+      }
+      // :363-380 ground truth for the plane and its features
+      if (use_truth) {
+        auto itp = state->_true_planes.find(pid);
+        if (itp != state->_true_planes.end()) memcpy(cp, itp->second.data(), 3 * sizeof(double));
+        features_to_truth(feats);
+      }
+      bool has_msckf_feat = false;  // :384-392
+      for (auto &ft : feats) has_msckf_feat = has_msckf_feat || !state->_features_SLAM.count(ft->featid);
+      if (!has_msckf_feat || feats.size() < 4) continue;  // :395-396
+    }
+    out.estimates[pid] = {cp[0], cp[1], cp[2]};
+    for (auto &ft : feats) {
+      out.feat_kept.insert(ft->featid);
+      if (ft->timestamps.empty() && state->_features_SLAM.count(ft->featid)) out.slam_kept[pid].push_back(ft->featid);
+    }
+  }
+  // on-plane extra features that survived join the batch of the plane loop (plane_feats.at(planeid), :421)
+  for (auto &ft : feature_vec_extra)
+    if (out.feat_kept.count(ft->featid) && out.estimates.count(feat2plane.at(ft->featid))) feature_vec.push_back(ft);
+  return out;
+}
+
+// 4. :411-649 plane loop: one device call over every plane that has an estimate; the corrections of the accepted planes are
+// applied in order.  Returns the ids of the features the accepted planes consumed (flagged, appended to feature_vec_used).
+std::set<size_t> plane_loop(const std::shared_ptr<State> &state, const ovp_update_opts &o, const CloneWindow &window, const PlaneLinPoints &lin,
+                            const FeatureVec &feature_vec, FeatureVec &feature_vec_used, const std::map<size_t, size_t> &feat2plane) {
+  std::set<size_t> features_used_already;
+  if (!(state->_options.use_plane_constraint && state->_options.use_plane_constraint_msckf && !feat2plane.empty())) return features_used_already;
+  // planes that have an estimate: in the state (when no fit ran), fitted above, or handed over by the caller
+  std::vector<size_t> plane_ids;
+  for (const auto &fp : feat2plane)
+    if (std::find(plane_ids.begin(), plane_ids.end(), fp.second) == plane_ids.end()) plane_ids.push_back(fp.second);
+  std::sort(plane_ids.begin(), plane_ids.end());  // std::map iteration order of plane_estimates_cp_inG (:413)
+  std::vector<size_t> used_planes;
+  for (size_t pid : plane_ids) {
+    const bool in_state = state->_features_PLANE.count(pid) > 0;
+    if (lin.fitted.empty() ? (in_state || lin.estimates.count(pid)) : lin.estimates.count(pid) > 0) used_planes.push_back(pid);
+  }
+  if (used_planes.empty()) return features_used_already;
+  const int NP = (int)used_planes.size();
+  std::vector<int> pof(feature_vec.size(), 0), sid(NP, -1);
+  std::vector<double> cpv(3 * NP), cpfej(3 * NP);
+  for (int k = 0; k < NP; ++k) {
+    const size_t pid = used_planes[k];
+    if (state->_features_PLANE.count(pid)) {
+      auto pl = state->_features_PLANE.at(pid);
+      sid[k] = pl->id();
+      for (int a = 0; a < 3; ++a) {
+        cpv[3 * k + a] = pl->value()(a);
+        cpfej[3 * k + a] = pl->fej()(a);
+      }
+    } else {
+      for (int a = 0; a < 3; ++a) cpv[3 * k + a] = cpfej[3 * k + a] = lin.estimates.at(pid)[a];
+    }
+  }
+  std::vector<size_t> gen_idx;  // on-plane features for the loop's general batch (gpu_general_planes) and their plane slots
+  std::vector<int> gen_plane;
+  bool gen_fits = true;
+  for (size_t f = 0; f < feature_vec.size(); ++f) {
+    auto it = feat2plane.find(feature_vec[f]->featid);
+    if (it == feat2plane.end()) continue;
+    if (lin.fitted.count(it->second) && !lin.feat_kept.count(feature_vec[f]->featid)) continue;  // not an inlier of the fit
+    // the plane kernels take a feature's 2 m bearing rows in one wavefront (the constraint row is wave-uniform): a track with
+    // more than 32 observations keeps its bearing measurements but not the plane constraint (it goes through the point loop)
+    // StateOptions::gpu_general_planes: such a feature keeps its constraint through the general batch of the loop, unless its
+    // plane was fitted in this frame (the fit / refinement kernels never saw it)
+    auto pos = std::find(used_planes.begin(), used_planes.end(), it->second);
+    if (feature_vec[f]->timestamps.size() > 32 || !feature_vec[f]->only_camera0()) {
+      if (pos != used_planes.end() && (!lin.fitted.count(it->second) || state->_options.gpu_fused_plane_fit)) {
+        gen_idx.push_back(f);
+        gen_plane.push_back(1 + (int)(pos - used_planes.begin()));
+        gen_fits = gen_fits && (int)feature_vec[f]->timestamps.size() <= OVP_GEN_MAX_MEAS;
+      }
+      continue;
+    }
+    if (pos != used_planes.end()) pof[f] = 1 + (int)(pos - used_planes.begin());
+  }
+  if (!state->_options.gpu_general_planes || !gen_fits) {  // (a track above OVP_GEN_MAX_MEAS: the frame keeps the previous route)
+    gen_idx.clear();
+    gen_plane.clear();
+  }
+  upload_batch(state, window, feature_vec);
+  const int n = ovp_cov_size(state->gpu());
+  std::vector<double> dxp((size_t)NP * n, 0.0);
+  std::vector<uint8_t> pok(NP, 0), fused(feature_vec.size(), 0);
+  ovp_plane_batch pb{NP, pof.data(), cpv.data(), cpfej.data(), sid.data()};
+  // SLAM landmarks lying on planes that are not in the state: one constraint row each inside that plane's update (:454-552)
+  std::vector<int> s_plane, s_id;
+  std::vector<size_t> s_featid;
+  std::vector<double> s_p, s_pf;
+  for (int k = 0; k < NP; ++k) {
+    auto itp = lin.slam_kept.find(used_planes[k]);
+    if (itp == lin.slam_kept.end() || sid[k] >= 0) continue;
+    int n_on_plane = 0;
+    for (size_t fid : itp->second) {
+      // the device loop takes OVP_PLANE_MAX_SLAM landmark rows per plane; a more crowded plane keeps the first ones (the
+      // others stay plain SLAM landmarks of this frame) instead of losing every plane constraint of the frame
+      if (++n_on_plane > OVP_PLANE_MAX_SLAM) {
+        PRINT_WARNING("UpdaterMSCKF::update() - plane %zu: more than %d SLAM landmarks, the rest is not constrained\n", used_planes[k],
+                      OVP_PLANE_MAX_SLAM);
+        break;
+      }
+      auto lm = state->_features_SLAM.at(fid);
+      double v[3], vf[3];
+      lm->get_xyz(false, v);
+      lm->get_xyz(true, vf);
+      s_plane.push_back(k + 1);
+      s_id.push_back(lm->id());
+      s_featid.push_back(fid);
+      s_p.insert(s_p.end(), v, v + 3);
+      s_pf.insert(s_pf.end(), vf, vf + 3);
+    }
+  }
+  pb.n_slam = (int)s_id.size();
+  pb.slam_plane = s_plane.data();
+  pb.slam_state_id = s_id.data();
+  pb.slam_p = s_p.data();
+  pb.slam_p_fej = s_pf.data();
+  std::vector<int> pdof(NP, 0);
+  int rcp;
+  if (!gen_idx.empty()) {
+    std::vector<uint8_t> gused(gen_idx.size() + 1, 0);
+    const FeaturePack g = general_batch(state, window, feature_vec, gen_idx);
+    const ovp_general_batch gb = g.as_general_batch();
+    rcp = ovp_msckf_plane_update_general(state->gpu(), &o, &pb, &gb, gen_plane.data(), dxp.data(), pok.data(), nullptr, pdof.data(),
+                                         fused.data(), gused.data());
+    if (rcp == 0)  // consumed by an accepted plane: flagged below with the batch's, not offered to the point update
+      for (size_t i = 0; i < gen_idx.size(); ++i)
+        if (gused[i]) fused[gen_idx[i]] = 1;
+  } else {
+    rcp = ovp_msckf_plane_update(state->gpu(), &o, &pb, dxp.data(), pok.data(), nullptr, pdof.data(), fused.data());
+  }
+  if (rcp == OVP_E_CAPACITY) {
+    // the planes of this frame involve more than 287 columns (clones + calibration + in-state planes + landmarks on the
+    // others; the state itself may be larger): the regularities are not used in this update, every feature takes the
+    // point loop - the filter degrades to plain MSCKF instead of stopping
+    PRINT_ERROR("UpdaterMSCKF::update() - the planes of this frame involve too many columns (state: %d), skipped\n", n);
+    std::fill(pok.begin(), pok.end(), 0);
+    std::fill(fused.begin(), fused.end(), 0);
+  } else {
+    gpu_check(rcp, "ovp_msckf_plane_update");
+  }
+  for (int k = 0; k < NP; ++k)
+    if (pok[k]) StateHelper::apply_correction(state, &dxp[(size_t)k * n]);  // :648 per accepted plane, in order
+  for (size_t q = 0; q < s_id.size(); ++q) {  // :626-639
+    const int k = s_plane[q] - 1;
+    if (pok[k]) state->_features_SLAM_to_PLANE[s_featid[q]] = used_planes[k];
+    else if (pdof[k] > 0) state->_features_SLAM_to_PLANE[s_featid[q]] = 0;  // the plane ran and failed its chi2 test
+  }
+  for (size_t f = 0; f < feature_vec.size(); ++f)
+    if (fused[f]) {  // :640-644
+      feature_vec[f]->to_delete = true;
+      features_used_already.insert(feature_vec[f]->featid);
+      feature_vec_used.push_back(feature_vec[f]);
+    }
+  return features_used_already;
+}
+
+// 5a. the features the batch format cannot carry (a second camera's measurements, a track longer than OVP_MAX_MEAS): the reference
+// treats them like any other (:695-786 - Jacobian over every camera's measurements, nullspace projection, gate); here each
+// becomes a dense block beside the batch and joins the same EKF update.  StateOptions::gpu_general_features: rows, projection and
+// gate on the device (a frame with a track above OVP_GEN_MAX_MEAS keeps the host blocks for all of them: the two entries share
+// the one pending pair of the context).  Returns the gate decisions, one per entry of dense_idx.
+std::vector<uint8_t> side_channel(const std::shared_ptr<State> &state, const UpdaterOptions &options, const ovp_update_opts &o,
+                                  const CloneWindow &window, const FeatureVec &feature_vec, const std::vector<size_t> &dense_idx) {
+  std::vector<uint8_t> dense_ok(dense_idx.size(), 0);
+  if (dense_idx.empty()) return dense_ok;
+  bool on_device = true;
+  for (size_t f : dense_idx) on_device = on_device && fits_general(state->_options, *feature_vec[f]);
+  if (on_device) {
+    const FeaturePack g = general_batch(state, window, feature_vec, dense_idx);
+    const ovp_general_batch gb = g.as_general_batch();
+    gpu_check(ovp_msckf_general_features(state->gpu(), &o, &gb, dense_ok.data(), nullptr), "ovp_msckf_general_features");
+    return dense_ok;
+  }
+  std::vector<int> b_rows, b_cols, b_ids;
+  std::vector<double> b_H, b_res;
+  for (size_t f : dense_idx) {
+    const ov_core::Feature &ft = *feature_vec[f];
+    UpdaterHelper::UpdaterHelperFeature hf;
+    hf.featid = ft.featid;
+    hf.uvs = ft.uvs;
+    hf.timestamps = ft.timestamps;
+    hf.cam_ids = ft.cam_ids;
+    hf.feat_representation = LandmarkRepresentation::GLOBAL_3D;  // (the projected system of an MSCKF feature does not depend on it)
+    memcpy(hf.p_FinG, ft.p_FinG, 3 * sizeof(double));
+    memcpy(hf.p_FinG_fej, ft.p_FinG, 3 * sizeof(double));  // :721-722
+    MatrixXd H_f, H_x;
+    VectorXd r;
+    std::vector<std::shared_ptr<Type>> order;
+    UpdaterHelper::get_feature_jacobian_full(state, hf, options.sigma_pix, state->_options.sigma_constraint, H_f, H_x, r, order);
+    UpdaterHelper::nullspace_project_inplace(H_f, H_x, r);  // :730
+    b_rows.push_back(H_x.rows());
+    b_cols.push_back(H_x.cols());
+    b_H.insert(b_H.end(), H_x.data(), H_x.data() + (size_t)H_x.rows() * H_x.cols());
+    b_res.insert(b_res.end(), r.data(), r.data() + r.rows());
+    for (const auto &v : order)
+      for (int k = 0; k < v->size(); ++k) b_ids.push_back(v->id() + k);
+  }
+  gpu_check(ovp_msckf_dense_blocks(state->gpu(), options.chi2_multipler, (int)dense_idx.size(), b_rows.data(), b_cols.data(), b_H.data(),
+                                   b_ids.data(), b_res.data(), dense_ok.data(), nullptr),
+            "ovp_msckf_dense_blocks");
+  return dense_ok;
+}
+
+// 6. optional per-frame trace (ov_plane_io.h FrameTrace): everything the point update reads (b: its uploaded batch) ...
+FrameTrace trace_inputs(const std::shared_ptr<State> &state, const ovp_update_opts &o, const CloneWindow &window, const FeaturePack &b) {
+  FrameTrace tr;
+  const int n = ovp_cov_size(state->gpu());
+  tr.timestamp = state->_timestamp;
+  tr.C = window.size();
+  tr.F = b.F;
+  tr.M = b.M;
+  tr.N = n;
+  const CloneTables t(window);
+  tr.clone_q = t.q;
+  tr.clone_p = t.p;
+  tr.clone_q_fej = t.q_fej;
+  tr.clone_p_fej = t.p_fej;
+  tr.clone_id.assign(t.id.begin(), t.id.end());
+  auto calib = state->_calib_IMUtoCAM.at(0);
+  auto intr = state->_cam_intrinsics.at(0);
+  memcpy(tr.calib_q, calib->quat(), 4 * sizeof(double));
+  memcpy(tr.calib_p, calib->pos(), 3 * sizeof(double));
+  memcpy(tr.intrinsics, intr->value().data(), 8 * sizeof(double));
+  tr.calib_id = state->_options.do_calib_camera_pose ? calib->id() : -1;
+  tr.intr_id = state->_options.do_calib_camera_intrinsics ? intr->id() : -1;
+  tr.P.assign((size_t)n * n, 0.0);
+  gpu_check(ovp_cov_download(state->gpu(), tr.P.data(), n, n), "ovp_cov_download");
+  tr.uv = b.uv;
+  tr.clone_idx.assign(b.cidx.begin(), b.cidx.end());
+  tr.n_meas.assign(b.nm.begin(), b.nm.end());
+  tr.p_FinG = b.pf;
+  tr.sigma_px = o.sigma_px;
+  tr.chi2_mult = o.chi2_multiplier;
+  tr.sigma_c = o.sigma_constraint;
+  tr.do_fej = o.do_fej;
+  tr.do_calib_pose = o.do_calib_camera_pose;
+  tr.do_calib_intr = o.do_calib_camera_intrinsics;
+  return tr;
+}
+// ... and what it returned
+void trace_outputs(const std::shared_ptr<State> &state, std::ostream &os, FrameTrace &tr, const std::vector<double> &dx,
+                   const std::vector<uint8_t> &ok, const std::vector<double> &chi2v) {
+  tr.dx = dx;
+  tr.accepted = ok;
+  tr.chi2 = chi2v;
+  tr.P_after.assign((size_t)tr.N * tr.N, 0.0);
+  gpu_check(ovp_cov_download(state->gpu(), tr.P_after.data(), tr.N, tr.N), "ovp_cov_download");
+  write_frame_trace(os, tr, update_trace_take_header());
+}
+
+}  // namespace
+
 void UpdaterMSCKF::update(std::shared_ptr<State> state, std::vector<std::shared_ptr<ov_core::Feature>> &feature_vec,
                           std::vector<std::shared_ptr<ov_core::Feature>> &feature_vec_extra,
                           std::vector<std::shared_ptr<ov_core::Feature>> &feature_vec_used, const std::map<size_t, size_t> &feat2plane) {
   if (feature_vec.empty()) return;  // :70-71
-
-  // :74-100  keep measurements at existing clone times, drop features with < 2 of them
-  std::map<double, int> clone_slot;
-  std::vector<std::shared_ptr<PoseJPL>> clones;
-  for (const auto &c : state->_clones_IMU) {
-    clone_slot[c.first] = (int)clones.size();
-    clones.push_back(c.second);
-  }
-  auto it0 = feature_vec.begin();
-  while (it0 != feature_vec.end()) {
-    auto &ft = **it0;
-    std::vector<float> uv2, uvn2;
-    std::vector<double> ts2;
-    std::vector<int> cam2;
-    const bool has_norm = ft.uvs_norm.size() == ft.uvs.size();
-    for (size_t k = 0; k < ft.timestamps.size(); ++k)
-      if (clone_slot.count(ft.timestamps[k])) {
-        ts2.push_back(ft.timestamps[k]);
-        if (!ft.cam_ids.empty()) cam2.push_back(ft.cam_of(k));
-        uv2.push_back(ft.uvs[2 * k]);
-        uv2.push_back(ft.uvs[2 * k + 1]);
-        if (has_norm) {
-          uvn2.push_back(ft.uvs_norm[2 * k]);
-          uvn2.push_back(ft.uvs_norm[2 * k + 1]);
-        }
-      }
-    ft.timestamps = ts2;
-    ft.cam_ids = cam2;
-    ft.uvs = uv2;
-    ft.uvs_norm = uvn2;
-    if (ts2.size() < 2) {
-      ft.to_delete = true;
-      it0 = feature_vec.erase(it0);
-    } else {
-      it0++;
-    }
-  }
+  const CloneWindow window(state->_clones_IMU);
+  window_cleanup(window, feature_vec, true);
   if (feature_vec.empty()) return;
-
-  // ---- pack the pose tables and the feature batch for the device ----
-  const int C = (int)clones.size();
-  std::vector<double> cq(4 * C), cp(3 * C), cqf(4 * C), cpf(3 * C);
-  std::vector<int> cid(C);
-  for (int i = 0; i < C; ++i) {
-    memcpy(&cq[4 * i], clones[i]->quat(), 4 * sizeof(double));
-    memcpy(&cp[3 * i], clones[i]->pos(), 3 * sizeof(double));
-    memcpy(&cqf[4 * i], clones[i]->quat_fej(), 4 * sizeof(double));
-    memcpy(&cpf[3 * i], clones[i]->pos_fej(), 3 * sizeof(double));
-    cid[i] = clones[i]->id();
-  }
-  auto pack_tables = [&]() {
-    ovp_state_tables st;
-    st.n_state = ovp_cov_size(state->_gpu);
-    st.n_clones = C;
-    for (int i = 0; i < C; ++i) {  // values may have changed after the plane loop
-      memcpy(&cq[4 * i], clones[i]->quat(), 4 * sizeof(double));
-      memcpy(&cp[3 * i], clones[i]->pos(), 3 * sizeof(double));
-    }
-    st.clone_q = cq.data();
-    st.clone_p = cp.data();
-    st.clone_q_fej = cqf.data();
-    st.clone_p_fej = cpf.data();
-    st.clone_id = cid.data();
-    auto calib = state->_calib_IMUtoCAM.at(0);
-    auto intr = state->_cam_intrinsics.at(0);
-    memcpy(st.calib_q, calib->quat(), 4 * sizeof(double));
-    memcpy(st.calib_p, calib->pos(), 3 * sizeof(double));
-    st.calib_id = calib->id();
-    memcpy(st.intrinsics, intr->value().data(), 8 * sizeof(double));
-    st.intr_id = intr->id();
-    st.cam_fisheye = (state->_cam_fisheye.count(0) && state->_cam_fisheye.at(0)) ? 1 : 0;
-    gpu_check(ovp_state_upload(state->_gpu, &st), "ovp_state_upload");
-  };
-  // what the device batch can carry: camera 0's measurements, at most OVP_MAX_MEAS of them (one wavefront's rows).  Everything
-  // else takes the dense side channel of the point update below (ovp_msckf_dense_blocks); in the uploads in front of it (device
-  // triangulation, plane loop) such a feature is present with NO measurements, i.e. it takes no part there
-  auto fits_batch = [](const ov_core::Feature &f) { return f.only_camera0() && (int)f.timestamps.size() <= OVP_MAX_MEAS; };
-  // measurements of a feature that go into a batch upload: all of them when the feature fits; for the device TRIANGULATION a
-  // feature that does not fit still takes part with its first OVP_MAX_MEAS measurements of camera 0 (a position estimate needs
-  // no more; the update below linearises over all of them); for the update's batches it has none
-  // StateOptions::gpu_general_features: such a feature takes the general-feature entries instead, when its track fits them
-  const bool gen_on = state->_options.gpu_general_features;
-  auto fits_general = [&](const ov_core::Feature &f) { return gen_on && (int)f.timestamps.size() <= OVP_GEN_MAX_MEAS; };
-  auto batch_meas = [&](const ov_core::Feature &f, bool for_triangulation) {
-    std::vector<size_t> sel;
-    if (fits_batch(f)) {
-      for (size_t k = 0; k < f.timestamps.size(); ++k) sel.push_back(k);
-    } else if (for_triangulation && !fits_general(f)) {
-      for (size_t k = 0; k < f.timestamps.size() && (int)sel.size() < OVP_MAX_MEAS; ++k)
-        if (f.cam_of(k) == 0) sel.push_back(k);
-    }
-    return sel;
-  };
-  auto upload_batch = [&](const std::vector<std::shared_ptr<ov_core::Feature>> &fv, bool for_triangulation = false) {
-    const int F = (int)fv.size();
-    int M = 1;
-    for (auto &f : fv) M = std::max(M, (int)batch_meas(*f, for_triangulation).size());
-    std::vector<float> uv((size_t)F * M * 2, 0.f);
-    std::vector<int> cidx((size_t)F * M, -1), nm(F);
-    std::vector<double> pf((size_t)F * 3);
-    for (int f = 0; f < F; ++f) {
-      const std::vector<size_t> sel = batch_meas(*fv[f], for_triangulation);
-      nm[f] = (int)sel.size();
-      for (int k = 0; k < nm[f]; ++k) {
-        cidx[(size_t)f * M + k] = clone_slot.at(fv[f]->timestamps[sel[k]]);
-        uv[((size_t)f * M + k) * 2] = fv[f]->uvs[2 * sel[k]];
-        uv[((size_t)f * M + k) * 2 + 1] = fv[f]->uvs[2 * sel[k] + 1];
-      }
-      memcpy(&pf[3 * f], fv[f]->p_FinG, 3 * sizeof(double));
-    }
-    ovp_feature_batch fb{F, M, uv.data(), cidx.data(), nm.data(), pf.data()};
-    gpu_check(ovp_batch_upload(state->_gpu, &fb), "ovp_batch_upload");
-    return M;
-  };
-  // every camera's tables and a general batch of features (all of their measurements) for the general-feature entries
-  auto upload_cameras = [&]() {
-    std::vector<ovp_camera_tables> cams(state->_options.num_cameras);
-    for (int k = 0; k < state->_options.num_cameras; ++k) {
-      auto calib = state->_calib_IMUtoCAM.at(k);
-      auto intr = state->_cam_intrinsics.at(k);
-      memcpy(cams[k].calib_q, calib->quat(), 4 * sizeof(double));
-      memcpy(cams[k].calib_p, calib->pos(), 3 * sizeof(double));
-      cams[k].calib_id = calib->id();
-      memcpy(cams[k].intrinsics, intr->value().data(), 8 * sizeof(double));
-      cams[k].intr_id = intr->id();
-      cams[k].fisheye = (state->_cam_fisheye.count(k) && state->_cam_fisheye.at(k)) ? 1 : 0;
-    }
-    gpu_check(ovp_cameras_upload(state->_gpu, (int)cams.size(), cams.data()), "ovp_cameras_upload");
-  };
-  struct GeneralBatch {
-    std::vector<float> uv, uvn;
-    std::vector<int> cidx, cam, nm;
-    std::vector<double> pf;
-    ovp_general_batch b;
-  };
-  auto general_batch = [&](const std::vector<size_t> &idx, GeneralBatch &g) {
-    const int F = (int)idx.size();
-    int M = 1;
-    for (size_t f : idx) M = std::max(M, (int)feature_vec[f]->timestamps.size());
-    g.uv.assign((size_t)F * M * 2, 0.f);
-    g.uvn.assign((size_t)F * M * 2, 0.f);
-    g.cidx.assign((size_t)F * M, 0);
-    g.cam.assign((size_t)F * M, 0);
-    g.nm.assign(F, 0);
-    g.pf.assign((size_t)F * 3, 0.0);
-    for (int i = 0; i < F; ++i) {
-      const ov_core::Feature &ft = *feature_vec[idx[i]];
-      const bool has_norm = ft.uvs_norm.size() == ft.uvs.size();
-      g.nm[i] = (int)ft.timestamps.size();
-      for (int k = 0; k < g.nm[i]; ++k) {
-        const size_t o = (size_t)i * M + k;
-        g.cidx[o] = clone_slot.at(ft.timestamps[k]);
-        g.cam[o] = ft.cam_of(k);
-        g.uv[2 * o] = ft.uvs[2 * k];
-        g.uv[2 * o + 1] = ft.uvs[2 * k + 1];
-        if (has_norm) {
-          g.uvn[2 * o] = ft.uvs_norm[2 * k];
-          g.uvn[2 * o + 1] = ft.uvs_norm[2 * k + 1];
-        }
-      }
-      memcpy(&g.pf[3 * i], ft.p_FinG, 3 * sizeof(double));
-    }
-    g.b = ovp_general_batch{F, M, g.uv.data(), g.cidx.data(), g.cam.data(), g.nm.data(), g.pf.data()};
-  };
-  ovp_update_opts o{_options.sigma_pix,
-                    _options.chi2_multipler,
-                    state->_options.sigma_constraint,
-                    state->_options.do_fej ? 1 : 0,
-                    state->_options.do_calib_camera_pose ? 1 : 0,
-                    state->_options.do_calib_camera_intrinsics ? 1 : 0,
-                    0};
-  pack_tables();
-
-  // ---- :120-166 triangulate (+ refine) the features that arrive with normalised measurements; failures are erased ----
-  {
-    bool any_norm = false;
-    for (auto &f : feature_vec) any_norm = any_norm || (!f->uvs_norm.empty() && f->uvs_norm.size() == f->uvs.size());
-    if (any_norm) {
-      const int M = upload_batch(feature_vec, true);
-      const int F = (int)feature_vec.size();
-      std::vector<float> uvn((size_t)F * M * 2, 0.f);
-      for (int f = 0; f < F; ++f) {
-        if (feature_vec[f]->uvs_norm.size() != feature_vec[f]->uvs.size()) continue;  // (position handed over)
-        const std::vector<size_t> sel = batch_meas(*feature_vec[f], true);
-        for (size_t k = 0; k < sel.size(); ++k) {
-          uvn[((size_t)f * M + k) * 2] = feature_vec[f]->uvs_norm[2 * sel[k]];
-          uvn[((size_t)f * M + k) * 2 + 1] = feature_vec[f]->uvs_norm[2 * sel[k] + 1];
-        }
-      }
-      ovp_triang_opts to;
-      to.refine_features = _featinit.refine_features ? 1 : 0;
-      to.triangulate_1d = _featinit.triangulate_1d ? 1 : 0;
-      to.reserved = 0;
-      to.max_runs = _featinit.max_runs;
-      to.init_lamda = _featinit.init_lamda;
-      to.max_lamda = _featinit.max_lamda;
-      to.min_dx = _featinit.min_dx;
-      to.min_dcost = _featinit.min_dcost;
-      to.lam_mult = _featinit.lam_mult;
-      to.min_dist = _featinit.min_dist;
-      to.max_dist = _featinit.max_dist;
-      to.max_baseline = _featinit.max_baseline;
-      to.max_cond_number = _featinit.max_cond_number;
-      std::vector<double> pf((size_t)F * 3);
-      std::vector<uint8_t> okv(F, 0);
-      gpu_check(ovp_triangulate(state->_gpu, &to, uvn.data(), pf.data(), okv.data()), "ovp_triangulate");
-      {  // StateOptions::gpu_general_features: the features the batch cannot carry, over every camera's observations
-        std::vector<size_t> gidx;
-        for (int f = 0; f < F; ++f)
-          if (!fits_batch(*feature_vec[f]) && fits_general(*feature_vec[f]) && feature_vec[f]->uvs_norm.size() == feature_vec[f]->uvs.size())
-            gidx.push_back(f);
-        if (!gidx.empty()) {
-          upload_cameras();
-          GeneralBatch g;
-          general_batch(gidx, g);
-          std::vector<double> gpf(gidx.size() * 3);
-          std::vector<uint8_t> gok(gidx.size(), 0);
-          gpu_check(ovp_triangulate_general(state->_gpu, &to, &g.b, g.uvn.data(), gpf.data(), gok.data()), "ovp_triangulate_general");
-          for (size_t i = 0; i < gidx.size(); ++i) {
-            okv[gidx[i]] = gok[i];
-            memcpy(&pf[3 * gidx[i]], &gpf[3 * i], 3 * sizeof(double));
-          }
-        }
-      }
-      size_t f = 0;
-      auto it1 = feature_vec.begin();
-      while (it1 != feature_vec.end()) {
-        const bool had_norm = !(*it1)->uvs_norm.empty();
-        if (had_norm && !okv[f]) {
-          (*it1)->to_delete = true;  // :161-165
-          it1 = feature_vec.erase(it1);
-        } else {
-          if (had_norm) memcpy((*it1)->p_FinG, &pf[3 * f], 3 * sizeof(double));
-          it1++;
-        }
-        ++f;
-      }
-      if (feature_vec.empty()) return;
-    }
-  }
-
-  // ---- :196-400 plane linearisation points ----
-  // Planes in the state: their features are refined against the (fixed) plane.  Other planes: RANSAC fit of the triangulated
-  // points, then joint refinement of plane and points; a plane that fails either step is skipped this frame.  Runs when the
-  // on-plane features carry normalised measurements (the tracker's uvs_norm) and the caller has not handed estimates over in
-  // state->_plane_estimates_cp_inG (the pre-fitted entry point used when the fit happens elsewhere).
-  std::map<size_t, std::vector<double>> plane_estimates = state->_plane_estimates_cp_inG;
-  std::set<size_t> fitted_planes;       // planes whose feature set went through the fit below
-  std::set<size_t> plane_feat_kept;     // their surviving features (plane_feats.at(planeid) of :421)
-  std::map<size_t, std::vector<size_t>> plane_slam_kept;  // SLAM landmarks among them (planes outside the state only)
-  if (state->_options.use_plane_constraint && state->_options.use_plane_constraint_msckf && !feat2plane.empty() &&
-      state->_plane_estimates_cp_inG.empty()) {
-    std::map<size_t, std::vector<std::shared_ptr<ov_core::Feature>>> plane_feats;  // :198
-    bool all_norm = true;
-    auto collect = [&](std::vector<std::shared_ptr<ov_core::Feature>> &vec) {  // :206-228
-      for (auto &feat : vec) {
-        auto it = feat2plane.find(feat->featid);
-        if (it == feat2plane.end()) continue;
-        // (the per-plane fit / refinement calls know camera 0 and 32 views: such a feature stays a point feature; the fused
-        // call, StateOptions::gpu_fused_plane_fit, takes every camera and any length when the feature has normalised measurements)
-        if (!fits_batch(*feat) &&
-            (!state->_options.gpu_fused_plane_fit || feat->uvs_norm.size() != 2 * feat->timestamps.size()))
-          continue;
-        all_norm = all_norm && (feat->uvs_norm.size() == 2 * feat->timestamps.size());
-        plane_feats[it->second].push_back(feat);
-      }
-    };
-    collect(feature_vec);
-    {  // :101-118 the extra features get the same clean-up as the main vector
-      auto itx = feature_vec_extra.begin();
-      while (itx != feature_vec_extra.end()) {
-        auto &ft = **itx;
-        std::vector<float> uv2, uvn2;
-        std::vector<double> ts2;
-        std::vector<int> cam2;
-        const bool has_norm = ft.uvs_norm.size() == ft.uvs.size();
-        for (size_t k = 0; k < ft.timestamps.size(); ++k)
-          if (clone_slot.count(ft.timestamps[k])) {
-            ts2.push_back(ft.timestamps[k]);
-            if (!ft.cam_ids.empty()) cam2.push_back(ft.cam_of(k));
-            uv2.push_back(ft.uvs[2 * k]);
-            uv2.push_back(ft.uvs[2 * k + 1]);
-            if (has_norm) {
-              uvn2.push_back(ft.uvs_norm[2 * k]);
-              uvn2.push_back(ft.uvs_norm[2 * k + 1]);
-            }
-          }
-        ft.timestamps = ts2;
-        ft.cam_ids = cam2;
-        ft.uvs = uv2;
-        ft.uvs_norm = uvn2;
-        if (ts2.size() < 2) itx = feature_vec_extra.erase(itx);
-        else itx++;
-      }
-    }
-    collect(feature_vec_extra);
-    if (all_norm && !plane_feats.empty()) {
-      // :232-252 SLAM features of planes that are not in the state take part in the fit as constants
-      if (state->_options.use_plane_constraint_slamu) {
-        for (auto &lm : state->_features_SLAM) {
-          auto it = feat2plane.find(lm.first);
-          if (it == feat2plane.end() || state->_features_PLANE.count(it->second)) continue;
-          auto bad = state->_features_SLAM_to_PLANE.find(lm.first);
-          if (bad != state->_features_SLAM_to_PLANE.end() && bad->second == 0) continue;
-          auto fp = std::make_shared<ov_core::Feature>();
-          fp->featid = lm.first;
-          lm.second->get_xyz(false, fp->p_FinG);
-          plane_feats[it->second].push_back(fp);
-        }
-      }
-      // camera poses of the clones (:122-141): R_GtoCi = R_ItoC R_GtoIi, p_CiinG = p_IiinG - R_GtoCi^T p_IinC
-      PlaneFitting::ClonesCam clones_cam;
-      auto calib = state->_calib_IMUtoCAM.at(0);
-      for (const auto &cl : state->_clones_IMU) {
-        PlaneFitting::ClonePose cpose;
-        const double *Ri = cl.second->Rot(), *Rc = calib->Rot(), *pi = cl.second->pos(), *pc = calib->pos();
-        for (int i = 0; i < 3; ++i)
-          for (int k = 0; k < 3; ++k) cpose.R[3 * i + k] = Rc[3 * i] * Ri[k] + Rc[3 * i + 1] * Ri[3 + k] + Rc[3 * i + 2] * Ri[6 + k];
-        for (int i = 0; i < 3; ++i)
-          cpose.p[i] = pi[i] - (cpose.R[i] * pc[0] + cpose.R[3 + i] * pc[1] + cpose.R[6 + i] * pc[2]);
-        clones_cam[0][cl.first] = cpose;
-      }
-      const double focal_length = state->_cam_intrinsics.at(0)->value()(0);  // :269-272
-      const double sigma_px_norm = _options.sigma_pix / focal_length;
-      const double sigma_c = state->_options.sigma_constraint;
-      double stateI[7], calib0[7];
-      memcpy(stateI, state->_imu->quat(), 4 * sizeof(double));
-      memcpy(stateI + 4, state->_imu->pos(), 3 * sizeof(double));
-      memcpy(calib0, calib->quat(), 4 * sizeof(double));
-      memcpy(calib0 + 4, calib->pos(), 3 * sizeof(double));
-      // StateOptions::gpu_fused_plane_fit: fit and refinement of every plane in ONE call (ovp_plane_fit_refine), the camera poses
-      // taken from the resident tables; what follows the two PlaneFitting calls of a plane stays in the loop below
-      const bool fused_fit = state->_options.gpu_fused_plane_fit;
-      std::map<size_t, bool> fused_ok;
-      std::map<size_t, std::vector<double>> fused_cp;
-      if (fused_fit) {
-        upload_cameras();
-        std::vector<PlaneFitting::FrontPlane> jobs;
-        for (auto &fp : plane_feats) {
-          PlaneFitting::FrontPlane j;
-          j.id = fp.first;
-          j.feats = &fp.second;
-          j.fixed = state->_features_PLANE.count(fp.first) > 0;
-          if (j.fixed)
-            for (int a = 0; a < 3; ++a) j.cp[a] = state->_features_PLANE.at(fp.first)->value()(a);
-          jobs.push_back(j);
-        }
-        PlaneFitting::fit_refine_all(jobs, clone_slot, state->_options.plane_msckf_min_feat, state->_options.plane_msckf_max_cond,
-                                     state->_options.use_refine_plane_feat, sigma_px_norm, sigma_c, state->_imu->Rot(),
-                                     state->_imu->pos());
-        for (auto &j : jobs) {
-          fused_ok[j.id] = j.ok;
-          fused_cp[j.id] = {j.cp[0], j.cp[1], j.cp[2]};
-        }
-      }
-      for (auto &fp : plane_feats) {  // :262-401, std::map order
-        const size_t pid = fp.first;
-        fitted_planes.insert(pid);
-        auto &feats = fp.second;
-        double cp[3];
-        if (fused_fit) {
-          if (!fused_ok.at(pid)) continue;
-          for (int a = 0; a < 3; ++a) cp[a] = fused_cp.at(pid)[a];
-        }
-        if (state->_features_PLANE.count(pid)) {  // :265-316
-          auto pl = state->_features_PLANE.at(pid);
-          for (int a = 0; a < 3; ++a) cp[a] = pl->value()(a);
-          if (!fused_fit && state->_options.use_refine_plane_feat &&
-              !PlaneFitting::optimize_plane(feats, cp, clones_cam, sigma_px_norm, sigma_c, true, stateI, calib0))
-            continue;
-          // :284-302 ground truth for the features (the plane itself is a state variable and keeps its estimate)
-          if (state->_options.use_groundtruths && !state->_true_planes.empty() && !state->_true_features.empty())
-            for (auto &ft : feats) {
-              auto itt = state->_true_features.find(ft->featid);
-              if (itt != state->_true_features.end()) memcpy(ft->p_FinG, itt->second.data(), 3 * sizeof(double));
-            }
-        } else {
-          if (!fused_fit) {
-            if (feats.size() < 4) continue;  // :320-321
-            double abcd[4];
-            if (!PlaneFitting::plane_fitting(feats, abcd, state->_options.plane_msckf_min_feat, state->_options.plane_msckf_max_cond))
-              continue;  // :325-327
-            for (int a = 0; a < 3; ++a) cp[a] = -abcd[a] * abcd[3];  // :352
-            if (state->_options.use_refine_plane_feat &&
-                !PlaneFitting::optimize_plane(feats, cp, clones_cam, sigma_px_norm, sigma_c, false, stateI, calib0))
-              continue;  // :355-357
-          }
-          // :363-380 ground truth for the plane and its features
-          if (state->_options.use_groundtruths && !state->_true_planes.empty() && !state->_true_features.empty()) {
-            auto itp = state->_true_planes.find(pid);
-            if (itp != state->_true_planes.end()) memcpy(cp, itp->second.data(), 3 * sizeof(double));
-            for (auto &ft : feats) {
-              auto itt = state->_true_features.find(ft->featid);
-              if (itt != state->_true_features.end()) memcpy(ft->p_FinG, itt->second.data(), 3 * sizeof(double));
-            }
-          }
-          bool has_msckf_feat = false;  // :384-392
-          for (auto &ft : feats) has_msckf_feat = has_msckf_feat || !state->_features_SLAM.count(ft->featid);
-          if (!has_msckf_feat || feats.size() < 4) continue;  // :395-396
-        }
-        plane_estimates[pid] = {cp[0], cp[1], cp[2]};
-        for (auto &ft : feats) {
-          plane_feat_kept.insert(ft->featid);
-          if (ft->timestamps.empty() && state->_features_SLAM.count(ft->featid)) plane_slam_kept[pid].push_back(ft->featid);
-        }
-      }
-      // on-plane extra features that survived join the batch of the plane loop (plane_feats.at(planeid), :421)
-      for (auto &ft : feature_vec_extra)
-        if (plane_feat_kept.count(ft->featid) && plane_estimates.count(feat2plane.at(ft->featid))) feature_vec.push_back(ft);
-    }
-  }
-
-  // ---- plane loop (:411-649) ----
-  std::set<size_t> features_used_already;
-  if (state->_options.use_plane_constraint && state->_options.use_plane_constraint_msckf && !feat2plane.empty()) {
-    // planes that have an estimate: in the state (when no fit ran), fitted above, or handed over by the caller
-    std::vector<size_t> plane_ids;
-    for (const auto &fp : feat2plane)
-      if (std::find(plane_ids.begin(), plane_ids.end(), fp.second) == plane_ids.end()) plane_ids.push_back(fp.second);
-    std::sort(plane_ids.begin(), plane_ids.end());  // std::map iteration order of plane_estimates_cp_inG (:413)
-    std::vector<size_t> used_planes;
-    for (size_t pid : plane_ids) {
-      const bool in_state = state->_features_PLANE.count(pid) > 0;
-      if (fitted_planes.empty() ? (in_state || plane_estimates.count(pid)) : plane_estimates.count(pid) > 0) used_planes.push_back(pid);
-    }
-    if (!used_planes.empty()) {
-      const int NP = (int)used_planes.size();
-      std::vector<int> pof(feature_vec.size(), 0), sid(NP, -1);
-      std::vector<double> cpv(3 * NP), cpfej(3 * NP);
-      for (int k = 0; k < NP; ++k) {
-        const size_t pid = used_planes[k];
-        if (state->_features_PLANE.count(pid)) {
-          auto pl = state->_features_PLANE.at(pid);
-          sid[k] = pl->id();
-          for (int a = 0; a < 3; ++a) {
-            cpv[3 * k + a] = pl->value()(a);
-            cpfej[3 * k + a] = pl->fej()(a);
-          }
-        } else {
-          for (int a = 0; a < 3; ++a) cpv[3 * k + a] = cpfej[3 * k + a] = plane_estimates.at(pid)[a];
-        }
-      }
-      std::vector<size_t> gen_idx;  // on-plane features for the loop's general batch (gpu_general_planes) and their plane slots
-      std::vector<int> gen_plane;
-      bool gen_fits = true;
-      for (size_t f = 0; f < feature_vec.size(); ++f) {
-        auto it = feat2plane.find(feature_vec[f]->featid);
-        if (it == feat2plane.end()) continue;
-        if (fitted_planes.count(it->second) && !plane_feat_kept.count(feature_vec[f]->featid)) continue;  // not an inlier of the fit
-        // the plane kernels take a feature's 2 m bearing rows in one wavefront (the constraint row is wave-uniform): a track with
-        // more than 32 observations keeps its bearing measurements but not the plane constraint (it goes through the point loop)
-        // StateOptions::gpu_general_planes: such a feature keeps its constraint through the general batch of the loop, unless its
-        // plane was fitted in this frame (the fit / refinement kernels never saw it)
-        auto pos = std::find(used_planes.begin(), used_planes.end(), it->second);
-        if (feature_vec[f]->timestamps.size() > 32 || !feature_vec[f]->only_camera0()) {
-          if (pos != used_planes.end() && (!fitted_planes.count(it->second) || state->_options.gpu_fused_plane_fit)) {
-            gen_idx.push_back(f);
-            gen_plane.push_back(1 + (int)(pos - used_planes.begin()));
-            gen_fits = gen_fits && (int)feature_vec[f]->timestamps.size() <= OVP_GEN_MAX_MEAS;
-          }
-          continue;
-        }
-        if (pos != used_planes.end()) pof[f] = 1 + (int)(pos - used_planes.begin());
-      }
-      if (!state->_options.gpu_general_planes || !gen_fits) {  // (a track above OVP_GEN_MAX_MEAS: the frame keeps the previous route)
-        gen_idx.clear();
-        gen_plane.clear();
-      }
-      upload_batch(feature_vec);
-      const int n = ovp_cov_size(state->_gpu);
-      std::vector<double> dxp((size_t)NP * n, 0.0);
-      std::vector<uint8_t> pok(NP, 0), fused(feature_vec.size(), 0);
-      ovp_plane_batch pb{NP, pof.data(), cpv.data(), cpfej.data(), sid.data()};
-      // SLAM landmarks lying on planes that are not in the state: one constraint row each inside that plane's update (:454-552)
-      std::vector<int> s_plane, s_id;
-      std::vector<size_t> s_featid;
-      std::vector<double> s_p, s_pf;
-      for (int k = 0; k < NP; ++k) {
-        auto itp = plane_slam_kept.find(used_planes[k]);
-        if (itp == plane_slam_kept.end() || sid[k] >= 0) continue;
-        int n_on_plane = 0;
-        for (size_t fid : itp->second) {
-          // the device loop takes OVP_PLANE_MAX_SLAM landmark rows per plane; a more crowded plane keeps the first ones (the
-          // others stay plain SLAM landmarks of this frame) instead of losing every plane constraint of the frame
-          if (++n_on_plane > OVP_PLANE_MAX_SLAM) {
-            PRINT_WARNING("UpdaterMSCKF::update() - plane %zu: more than %d SLAM landmarks, the rest is not constrained\n",
-                          used_planes[k], OVP_PLANE_MAX_SLAM);
-            break;
-          }
-          auto lm = state->_features_SLAM.at(fid);
-          double v[3], vf[3];
-          lm->get_xyz(false, v);
-          lm->get_xyz(true, vf);
-          s_plane.push_back(k + 1);
-          s_id.push_back(lm->id());
-          s_featid.push_back(fid);
-          s_p.insert(s_p.end(), v, v + 3);
-          s_pf.insert(s_pf.end(), vf, vf + 3);
-        }
-      }
-      pb.n_slam = (int)s_id.size();
-      pb.slam_plane = s_plane.data();
-      pb.slam_state_id = s_id.data();
-      pb.slam_p = s_p.data();
-      pb.slam_p_fej = s_pf.data();
-      std::vector<int> pdof(NP, 0);
-      {
-        std::vector<uint8_t> gused(gen_idx.size() + 1, 0);
-        int rcp;
-        if (!gen_idx.empty()) {
-          upload_cameras();
-          GeneralBatch g;
-          general_batch(gen_idx, g);
-          rcp = ovp_msckf_plane_update_general(state->_gpu, &o, &pb, &g.b, gen_plane.data(), dxp.data(), pok.data(), nullptr, pdof.data(),
-                                               fused.data(), gused.data());
-          if (rcp == 0)  // consumed by an accepted plane: flagged below with the batch's, not offered to the point update
-            for (size_t i = 0; i < gen_idx.size(); ++i)
-              if (gused[i]) fused[gen_idx[i]] = 1;
-        } else {
-          rcp = ovp_msckf_plane_update(state->_gpu, &o, &pb, dxp.data(), pok.data(), nullptr, pdof.data(), fused.data());
-        }
-        if (rcp == OVP_E_CAPACITY) {
-          // the planes of this frame involve more than 287 columns (clones + calibration + in-state planes + landmarks on the
-          // others; the state itself may be larger): the regularities are not used in this update, every feature takes the
-          // point loop - the filter degrades to plain MSCKF instead of stopping
-          PRINT_ERROR("UpdaterMSCKF::update() - the planes of this frame involve too many columns (state: %d), skipped\n", n);
-          std::fill(pok.begin(), pok.end(), 0);
-          std::fill(fused.begin(), fused.end(), 0);
-        } else {
-          gpu_check(rcp, "ovp_msckf_plane_update");
-        }
-      }
-      for (int k = 0; k < NP; ++k)
-        if (pok[k]) StateHelper::apply_correction(state, &dxp[(size_t)k * n]);  // :648 per accepted plane, in order
-      for (size_t q = 0; q < s_id.size(); ++q) {  // :626-639
-        const int k = s_plane[q] - 1;
-        if (pok[k]) state->_features_SLAM_to_PLANE[s_featid[q]] = used_planes[k];
-        else if (pdof[k] > 0) state->_features_SLAM_to_PLANE[s_featid[q]] = 0;  // the plane ran and failed its chi2 test
-      }
-      for (size_t f = 0; f < feature_vec.size(); ++f)
-        if (fused[f]) {  // :640-644
-          feature_vec[f]->to_delete = true;
-          features_used_already.insert(feature_vec[f]->featid);
-          feature_vec_used.push_back(feature_vec[f]);
-        }
-    }
-  }
+  const ovp_update_opts o = make_update_opts(_options, state->_options);
+  upload_state_tables(state, window);
+  triangulate(state, window, _featinit, feature_vec);
+  if (feature_vec.empty()) return;
+  const PlaneLinPoints lin = plane_linearisation_points(state, _options, window, feature_vec, feature_vec_extra, feat2plane);
+  const std::set<size_t> features_used_already = plane_loop(state, o, window, lin, feature_vec, feature_vec_used, feat2plane);
 
   // :657-668 remove features already used
-  std::vector<std::shared_ptr<ov_core::Feature>> feature_vec_tmp;
+  FeatureVec feature_vec_tmp;
   for (auto const &feature : feature_vec)
     if (features_used_already.find(feature->featid) == features_used_already.end()) feature_vec_tmp.push_back(feature);
   feature_vec = feature_vec_tmp;
   if (feature_vec.empty()) return;
 
-  // ---- point loop, gate, compression, update (:671-814) ----
-  if (!features_used_already.empty()) pack_tables();  // the plane loop moved the linearisation points
-  upload_batch(feature_vec);
+  // ---- 5. point loop, gate, compression, update (:671-814) ----
+  if (!features_used_already.empty()) upload_state_tables(state, window);  // the plane loop moved the linearisation points
+  const FeaturePack b = upload_batch(state, window, feature_vec);
   const int n = ovp_cov_size(state->_gpu);
   std::vector<double> dx(n, 0.0);
   std::vector<uint8_t> ok(feature_vec.size(), 0);
   ovp_update_info info;
-  // optional per-frame trace (ov_plane_io.h FrameTrace): everything this update reads, and below what it returned
-  FrameTrace tr;
   std::ostream *tos = update_trace_stream();
-  if (tos) {
-    const int F = (int)feature_vec.size();
-    int M = 1;
-    for (auto &f : feature_vec)
-      if (fits_batch(*f)) M = std::max(M, (int)f->timestamps.size());
-    tr.timestamp = state->_timestamp;
-    tr.C = C;
-    tr.F = F;
-    tr.M = M;
-    tr.N = n;
-    for (int i = 0; i < C; ++i) {
-      memcpy(&cq[4 * i], clones[i]->quat(), 4 * sizeof(double));
-      memcpy(&cp[3 * i], clones[i]->pos(), 3 * sizeof(double));
-    }
-    tr.clone_q = cq;
-    tr.clone_p = cp;
-    tr.clone_q_fej = cqf;
-    tr.clone_p_fej = cpf;
-    tr.clone_id.assign(cid.begin(), cid.end());
-    auto calib = state->_calib_IMUtoCAM.at(0);
-    auto intr = state->_cam_intrinsics.at(0);
-    memcpy(tr.calib_q, calib->quat(), 4 * sizeof(double));
-    memcpy(tr.calib_p, calib->pos(), 3 * sizeof(double));
-    memcpy(tr.intrinsics, intr->value().data(), 8 * sizeof(double));
-    tr.calib_id = state->_options.do_calib_camera_pose ? calib->id() : -1;
-    tr.intr_id = state->_options.do_calib_camera_intrinsics ? intr->id() : -1;
-    tr.P.assign((size_t)n * n, 0.0);
-    gpu_check(ovp_cov_download(state->_gpu, tr.P.data(), n, n), "ovp_cov_download");
-    tr.uv.assign((size_t)F * M * 2, 0.f);
-    tr.clone_idx.assign((size_t)F * M, -1);
-    tr.n_meas.assign(F, 0);
-    tr.p_FinG.assign((size_t)F * 3, 0.0);
-    for (int f = 0; f < F; ++f) {
-      tr.n_meas[f] = fits_batch(*feature_vec[f]) ? (int)feature_vec[f]->timestamps.size() : 0;
-      for (int k = 0; k < tr.n_meas[f]; ++k) {
-        tr.clone_idx[(size_t)f * M + k] = clone_slot.at(feature_vec[f]->timestamps[k]);
-        tr.uv[((size_t)f * M + k) * 2] = feature_vec[f]->uvs[2 * k];
-        tr.uv[((size_t)f * M + k) * 2 + 1] = feature_vec[f]->uvs[2 * k + 1];
-      }
-      memcpy(&tr.p_FinG[3 * f], feature_vec[f]->p_FinG, 3 * sizeof(double));
-    }
-    tr.sigma_px = o.sigma_px;
-    tr.chi2_mult = o.chi2_multiplier;
-    tr.sigma_c = o.sigma_constraint;
-    tr.do_fej = o.do_fej;
-    tr.do_calib_pose = o.do_calib_camera_pose;
-    tr.do_calib_intr = o.do_calib_camera_intrinsics;
-  }
+  FrameTrace tr;
+  if (tos) tr = trace_inputs(state, o, window, b);
   std::vector<double> chi2v(tos ? feature_vec.size() : 0, 0.0);
-  // ---- features the batch format cannot carry (a second camera's measurements, a track longer than OVP_MAX_MEAS): the reference
-  // treats them like any other (:695-786 - Jacobian over every camera's measurements, nullspace projection, gate); here each
-  // becomes a dense block beside the batch and joins the same EKF update (ovp_msckf_dense_blocks) ----
   std::vector<size_t> dense_idx;
   for (size_t f = 0; f < feature_vec.size(); ++f)
     if (!fits_batch(*feature_vec[f])) dense_idx.push_back(f);
-  std::vector<uint8_t> dense_ok(dense_idx.size(), 0);
-  // StateOptions::gpu_general_features: rows, projection and gate on the device (a frame with a track above OVP_GEN_MAX_MEAS keeps the
-  // host blocks for all of them: the two entries share the one pending pair of the context)
-  bool dense_on_device = gen_on && !dense_idx.empty();
-  for (size_t f : dense_idx) dense_on_device = dense_on_device && fits_general(*feature_vec[f]);
-  if (dense_on_device) {
-    upload_cameras();
-    GeneralBatch g;
-    general_batch(dense_idx, g);
-    gpu_check(ovp_msckf_general_features(state->_gpu, &o, &g.b, dense_ok.data(), nullptr), "ovp_msckf_general_features");
-  } else if (!dense_idx.empty()) {
-    std::vector<int> b_rows, b_cols, b_ids;
-    std::vector<double> b_H, b_res;
-    for (size_t f : dense_idx) {
-      const ov_core::Feature &ft = *feature_vec[f];
-      UpdaterHelper::UpdaterHelperFeature hf;
-      hf.featid = ft.featid;
-      hf.uvs = ft.uvs;
-      hf.timestamps = ft.timestamps;
-      hf.cam_ids = ft.cam_ids;
-      hf.feat_representation = LandmarkRepresentation::GLOBAL_3D;  // (the projected system of an MSCKF feature does not depend on it)
-      memcpy(hf.p_FinG, ft.p_FinG, 3 * sizeof(double));
-      memcpy(hf.p_FinG_fej, ft.p_FinG, 3 * sizeof(double));  // :721-722
-      MatrixXd H_f, H_x;
-      VectorXd r;
-      std::vector<std::shared_ptr<Type>> order;
-      UpdaterHelper::get_feature_jacobian_full(state, hf, _options.sigma_pix, state->_options.sigma_constraint, H_f, H_x, r, order);
-      UpdaterHelper::nullspace_project_inplace(H_f, H_x, r);  // :730
-      b_rows.push_back(H_x.rows());
-      b_cols.push_back(H_x.cols());
-      b_H.insert(b_H.end(), H_x.data(), H_x.data() + (size_t)H_x.rows() * H_x.cols());
-      b_res.insert(b_res.end(), r.data(), r.data() + r.rows());
-      for (const auto &v : order)
-        for (int k = 0; k < v->size(); ++k) b_ids.push_back(v->id() + k);
-    }
-    gpu_check(ovp_msckf_dense_blocks(state->_gpu, _options.chi2_multipler, (int)dense_idx.size(), b_rows.data(), b_cols.data(), b_H.data(),
-                                     b_ids.data(), b_res.data(), dense_ok.data(), nullptr),
-              "ovp_msckf_dense_blocks");
-  }
+  const std::vector<uint8_t> dense_ok = side_channel(state, _options, o, window, feature_vec, dense_idx);
   int rc;
   if (_comm || _world > 1) {
     // feature-sharded point loop: the batch above is the same on every replica; accepted / chi2 come back for this rank's share
@@ -1335,20 +1130,13 @@ void UpdaterMSCKF::update(std::shared_ptr<State> state, std::vector<std::shared_
     std::exit(EXIT_FAILURE);
   }
   gpu_check(rc, "ovp_msckf_update");
-  for (size_t i = 0; i < dense_idx.size(); ++i) {  // the dense blocks' gate decisions take their places in the vector's order
+  for (size_t i = 0; i < dense_idx.size(); ++i) {  // the side channel's gate decisions take their places in the vector's order
     ok[dense_idx[i]] = dense_ok[i];
     info.n_accepted += dense_ok[i] ? 1 : 0;
   }
-  if (tos) {
-    tr.dx = dx;
-    tr.accepted = ok;
-    tr.chi2 = chi2v;
-    tr.P_after.assign((size_t)n * n, 0.0);
-    gpu_check(ovp_cov_download(state->_gpu, tr.P_after.data(), n, n), "ovp_cov_download");
-    write_frame_trace(*tos, tr, update_trace_take_header());
-  }
+  if (tos) trace_outputs(state, *tos, tr, dx, ok, chi2v);
   // :755-757 rejected features are flagged and erased, :791-793 the rest is flagged as used
-  std::vector<std::shared_ptr<ov_core::Feature>> kept;
+  FeatureVec kept;
   for (size_t f = 0; f < feature_vec.size(); ++f) {
     feature_vec[f]->to_delete = true;
     if (ok[f]) kept.push_back(feature_vec[f]);

@@ -296,11 +296,6 @@ public:
   // GLOBAL_3D and candidates with plane rows; delayed_init itself runs GLOBAL_3D candidates as one device loop
   void delayed_init_host_loop(std::shared_ptr<State> state, std::vector<std::shared_ptr<ov_core::Feature>> &feature_vec,
                               const std::map<size_t, size_t> &feat2plane);
-  // pose tables of the clone window + camera calibration -> device (ovp_state_upload); clone_slot: timestamp -> clone slot
-  static void upload_state_tables(std::shared_ptr<State> state, std::map<double, int> &clone_slot,
-                                  std::vector<std::shared_ptr<ov_type::PoseJPL>> &clones);
-  // every camera's calibration -> device (ovp_cameras_upload), for the general entries
-  static void upload_camera_tables(std::shared_ptr<State> state);
   // which path the last update() / delayed_init() took (tests; not in the reference): ROUTE_DEVICE_GENERAL / ROUTE_DEVICE_MONO = the
   // general / mono device entry took every landmark or candidate, ROUTE_DENSE_HOST = update_dense, ROUTE_HOST_LOOP = some or all
   // candidates went through delayed_init_host_loop
@@ -313,9 +308,6 @@ protected:
   // anchor-change Jacobian  Phi = H_f,new^-1 [H_x,old | H_f,old | -H_x,new]
   void perform_anchor_change(std::shared_ptr<State> state, std::shared_ptr<ov_type::Landmark> landmark, double new_anchor_timestamp,
                              size_t new_cam_id);
-  // update/UpdaterSLAM.cpp:120-166: triangulation (+ refinement) of the features that carry normalised measurements
-  static void triangulate_on_device(std::shared_ptr<State> state, const ov_core::FeatureInitializerOptions &fio,
-                                    std::vector<std::shared_ptr<ov_core::Feature>> &feature_vec);
   UpdaterOptions _options_slam, _options_aruco;
   ov_core::FeatureInitializerOptions _featinit;  // ext FeatureInitializer options (the reference keeps an initializer_feat)
   static bool _force_dense;

@@ -2,6 +2,7 @@
 // signatures, same side effects on the feature vectors (feats becomes the inlier set, feat->p_FinG is overwritten for the
 // kept features, cp_inG only on success).
 #include "ov_plane_host.h"
+#include "ov_plane_pack.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -181,37 +182,25 @@ void PlaneFitting::fit_refine_all(std::vector<FrontPlane> &planes, const std::ma
   std::vector<int> fstart(1, 0);
   std::vector<double> cps;
   std::vector<uint8_t> fix;
-  int M = 1;
   for (auto &pl : planes) {
     cps.insert(cps.end(), pl.cp, pl.cp + 3);
     fix.push_back(pl.fixed ? 1 : 0);
     for (auto &ft : *pl.feats) {
+      if (ft->uvs_norm.size() != 2 * ft->timestamps.size()) {
+        PRINT_ERROR("PlaneFitting::fit_refine_all() - feature %zu has no normalised measurements\n", ft->featid);
+        std::exit(EXIT_FAILURE);
+      }
       flat.push_back(ft);
-      M = std::max(M, (int)ft->timestamps.size());
     }
     fstart.push_back((int)flat.size());
   }
   const int F = (int)flat.size();
-  std::vector<float> uvn((size_t)F * M * 2, 0.f);
-  std::vector<int> cidx((size_t)F * M, 0), cam((size_t)F * M, 0), nm(F, 0);
-  std::vector<double> pf((size_t)std::max(F, 1) * 3);
-  for (int f = 0; f < F; ++f) {
-    const ov_core::Feature &ft = *flat[f];
-    nm[f] = (int)ft.timestamps.size();  // 0: a SLAM landmark, held constant (:274-279)
-    if (ft.uvs_norm.size() != 2 * ft.timestamps.size()) {
-      PRINT_ERROR("PlaneFitting::fit_refine_all() - feature %zu has no normalised measurements\n", ft.featid);
-      std::exit(EXIT_FAILURE);
-    }
-    for (int k = 0; k < nm[f]; ++k) {
-      const size_t ob = (size_t)f * M + k;
-      cidx[ob] = clone_slot.at(ft.timestamps[k]);
-      cam[ob] = ft.cam_of(k);
-      uvn[2 * ob] = ft.uvs_norm[2 * k];
-      uvn[2 * ob + 1] = ft.uvs_norm[2 * k + 1];
-    }
-    memcpy(&pf[3 * f], ft.p_FinG, 3 * sizeof(double));
-  }
-  ovp_general_batch gb{F, M, uvn.data(), cidx.data(), cam.data(), nm.data(), pf.data()};
+  PackSite site;  // (a feature without measurements is a SLAM landmark, held constant, :274-279)
+  site.pad = 0;
+  site.uv_norm = true;
+  site.empty_rows = 1;
+  const FeaturePack g = pack_features(feature_range(flat), clone_slot, site);
+  const ovp_general_batch gb = g.as_general_batch();
   ovp_planefront_in pin;
   pin.n_planes = NPL;
   pin.feat_start = fstart.data();
@@ -228,7 +217,7 @@ void PlaneFitting::fit_refine_all(std::vector<FrontPlane> &planes, const std::ma
   std::vector<uint8_t> okp(NPL, 0), kept(std::max(F, 1), 0);
   std::vector<double> cpo((size_t)NPL * 3), po((size_t)std::max(F, 1) * 3);
   ovp_planefront_out pout{nullptr, nullptr, okp.data(), cpo.data(), nullptr, nullptr, kept.data(), po.data(), nullptr};
-  pf_check(ovp_plane_fit_refine(_gpu, &gb, uvn.data(), &pin, &pout), "ovp_plane_fit_refine");
+  pf_check(ovp_plane_fit_refine(_gpu, &gb, g.uv.data(), &pin, &pout), "ovp_plane_fit_refine");
   for (int k = 0; k < NPL; ++k) {
     planes[k].ok = okp[k] != 0;
     if (!planes[k].ok) continue;

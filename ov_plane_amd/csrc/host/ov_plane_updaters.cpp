@@ -9,6 +9,7 @@
 #include <set>
 
 #include "ov_plane_host.h"
+#include "ov_plane_pack.h"
 
 using namespace ov_type;
 
@@ -459,87 +460,11 @@ void UpdaterHelper::measurement_compress_inplace(MatrixXd &H_x, VectorXd &res) {
   res = res.block(0, 0, r, 1);
 }
 
-// Pose tables of the clone window + camera calibration -> device (ovp_state_upload); clone_slot: timestamp -> clone slot
-void UpdaterSLAM::upload_state_tables(std::shared_ptr<State> state, std::map<double, int> &clone_slot,
-                                      std::vector<std::shared_ptr<PoseJPL>> &clones) {
-  clone_slot.clear();
-  clones.clear();
-  for (const auto &c : state->_clones_IMU) {
-    clone_slot[c.first] = (int)clones.size();
-    clones.push_back(c.second);
-  }
-  const int C = (int)clones.size();
-  std::vector<double> cq(4 * C), cp(3 * C), cqf(4 * C), cpf(3 * C);
-  std::vector<int> cid(C);
-  for (int i = 0; i < C; ++i) {
-    memcpy(&cq[4 * i], clones[i]->quat(), 4 * sizeof(double));
-    memcpy(&cp[3 * i], clones[i]->pos(), 3 * sizeof(double));
-    memcpy(&cqf[4 * i], clones[i]->quat_fej(), 4 * sizeof(double));
-    memcpy(&cpf[3 * i], clones[i]->pos_fej(), 3 * sizeof(double));
-    cid[i] = clones[i]->id();
-  }
-  ovp_state_tables st;
-  st.n_state = ovp_cov_size(state->_gpu);
-  st.n_clones = C;
-  st.clone_q = cq.data();
-  st.clone_p = cp.data();
-  st.clone_q_fej = cqf.data();
-  st.clone_p_fej = cpf.data();
-  st.clone_id = cid.data();
-  auto calib = state->_calib_IMUtoCAM.at(0);
-  auto intr = state->_cam_intrinsics.at(0);
-  memcpy(st.calib_q, calib->quat(), 4 * sizeof(double));
-  memcpy(st.calib_p, calib->pos(), 3 * sizeof(double));
-  st.calib_id = calib->id();
-  memcpy(st.intrinsics, intr->value().data(), 8 * sizeof(double));
-  st.intr_id = intr->id();
-  st.cam_fisheye = (state->_cam_fisheye.count(0) && state->_cam_fisheye.at(0)) ? 1 : 0;
-  gpu_check2(ovp_state_upload(state->_gpu, &st), "ovp_state_upload");  // (the tables are staged inside the call)
-}
-
-// Every camera's calibration -> device (ovp_cameras_upload): the tables of the general entries
-void UpdaterSLAM::upload_camera_tables(std::shared_ptr<State> state) {
-  std::vector<ovp_camera_tables> cams(state->_options.num_cameras);
-  for (int k = 0; k < state->_options.num_cameras; ++k) {
-    auto calib = state->_calib_IMUtoCAM.at(k);
-    auto intr = state->_cam_intrinsics.at(k);
-    memcpy(cams[k].calib_q, calib->quat(), 4 * sizeof(double));
-    memcpy(cams[k].calib_p, calib->pos(), 3 * sizeof(double));
-    cams[k].calib_id = calib->id();
-    memcpy(cams[k].intrinsics, intr->value().data(), 8 * sizeof(double));
-    cams[k].intr_id = intr->id();
-    cams[k].fisheye = (state->_cam_fisheye.count(k) && state->_cam_fisheye.at(k)) ? 1 : 0;
-  }
-  gpu_check2(ovp_cameras_upload(state->_gpu, (int)cams.size(), cams.data()), "ovp_cameras_upload");
-}
-
 // ---- update/UpdaterSLAM.cpp ----------------------------------------------------------------------
 UpdaterSLAM::UpdaterSLAM(UpdaterOptions &options_slam, UpdaterOptions &options_aruco, ov_core::FeatureInitializerOptions &fio)
     : _options_slam(options_slam), _options_aruco(options_aruco), _featinit(fio) {
   _options_slam.sigma_pix_sq = std::pow(_options_slam.sigma_pix, 2);
   _options_aruco.sigma_pix_sq = std::pow(_options_aruco.sigma_pix, 2);
-}
-
-static void clean_old_measurements(ov_core::Feature &ft, const std::map<double, std::shared_ptr<PoseJPL>> &clones) {
-  std::vector<float> uv2, uvn2;
-  std::vector<double> ts2;
-  std::vector<int> cam2;
-  const bool has_norm = ft.uvs_norm.size() == ft.uvs.size();
-  for (size_t k = 0; k < ft.timestamps.size(); ++k)
-    if (clones.count(ft.timestamps[k])) {
-      ts2.push_back(ft.timestamps[k]);
-      if (!ft.cam_ids.empty()) cam2.push_back(ft.cam_of(k));
-      uv2.push_back(ft.uvs[2 * k]);
-      uv2.push_back(ft.uvs[2 * k + 1]);
-      if (has_norm) {
-        uvn2.push_back(ft.uvs_norm[2 * k]);
-        uvn2.push_back(ft.uvs_norm[2 * k + 1]);
-      }
-    }
-  ft.timestamps = ts2;
-  ft.cam_ids = cam2;
-  ft.uvs = uv2;
-  ft.uvs_norm = uvn2;
 }
 
 // update/UpdaterSLAM.cpp:376-682.  The rows of a GLOBAL_3D landmark, every chi2 test (against the RESIDENT covariance), the
@@ -553,7 +478,7 @@ void UpdaterSLAM::update(std::shared_ptr<State> state, std::vector<std::shared_p
   // :391-419
   auto it0 = feature_vec.begin();
   while (it0 != feature_vec.end()) {
-    clean_old_measurements(**it0, state->_clones_IMU);
+    keep_window_measurements(**it0, state->_clones_IMU);
     const int ct_meas = (int)(*it0)->timestamps.size();
     std::shared_ptr<Landmark> landmark = state->_features_SLAM.at((*it0)->featid);
     const int required_meas = (landmark->_feat_representation == LR::ANCHORED_INVERSE_DEPTH_SINGLE) ? 2 : 1;  // :409-410
@@ -567,16 +492,13 @@ void UpdaterSLAM::update(std::shared_ptr<State> state, std::vector<std::shared_p
     }
   }
   if (feature_vec.empty()) return;
-  std::map<double, int> clone_slot;
-  std::vector<std::shared_ptr<PoseJPL>> clones;
-  UpdaterSLAM::upload_state_tables(state, clone_slot, clones);
+  const CloneWindow window(state->_clones_IMU);
+  upload_state_tables(state, window);
   const int L = (int)feature_vec.size();
-  int M = 1;
+  const FeaturePack b = pack_features(feature_range(feature_vec), window.clone_slot);
+  const int M = b.M;
   bool other_camera = false;
-  for (auto &f : feature_vec) {
-    M = std::max(M, (int)f->timestamps.size());
-    other_camera = other_camera || !f->only_camera0();
-  }
+  for (auto &f : feature_vec) other_camera = other_camera || !f->only_camera0();
   // a track longer than one wavefront's rows, or measurements of a camera other than camera 0 (the mono entry carries one
   // calibration block per row): the dense form has neither limit.  StateOptions::gpu_general_slam: other cameras' measurements
   // take the general entry (every camera's tables, ovp_slam_update_general) in ONE call with the rest of the batch
@@ -586,9 +508,7 @@ void UpdaterSLAM::update(std::shared_ptr<State> state, std::vector<std::shared_p
     update_dense(state, feature_vec, feat2plane);
     return;
   }
-  std::vector<int> camv(general ? (size_t)L * M : 0, 0);  // camera of every measurement (general entry)
-  std::vector<float> uv((size_t)L * M * 2, 0.f);
-  std::vector<int> cidx((size_t)L * M, -1), nm(L), lmid(L), psid(L, -1), pre_rows(L, 0), pre_cols(L, 0), pre_ids;
+  std::vector<int> lmid(L), psid(L, -1), pre_rows(L, 0), pre_cols(L, 0), pre_ids;
   std::vector<double> pv((size_t)L * 3, 0.0), pf((size_t)L * 3, 0.0), cpv((size_t)L * 3, 0.0), cpf((size_t)L * 3, 0.0), pre_H;
   std::vector<size_t> planeid(L, 0);
   bool any_pre = false, any_plane = false;
@@ -596,14 +516,7 @@ void UpdaterSLAM::update(std::shared_ptr<State> state, std::vector<std::shared_p
   for (int l = 0; l < L; ++l) {
     ov_core::Feature &ft = *feature_vec[l];
     std::shared_ptr<Landmark> landmark = state->_features_SLAM.at(ft.featid);
-    nm[l] = (int)ft.timestamps.size();
     lmid[l] = landmark->id();
-    for (int k = 0; k < nm[l]; ++k) {
-      cidx[(size_t)l * M + k] = clone_slot.at(ft.timestamps[k]);
-      uv[((size_t)l * M + k) * 2] = ft.uvs[2 * k];
-      uv[((size_t)l * M + k) * 2 + 1] = ft.uvs[2 * k + 1];
-      if (general) camv[(size_t)l * M + k] = ft.cam_of(k);
-    }
     // :465-475
     if (state->_options.use_plane_constraint && state->_options.use_plane_constraint_slamu && feat2plane.find(ft.featid) != feat2plane.end() &&
         state->_features_PLANE.find(feat2plane.at(ft.featid)) != state->_features_PLANE.end()) {
@@ -678,9 +591,9 @@ void UpdaterSLAM::update(std::shared_ptr<State> state, std::vector<std::shared_p
   memset(&sb, 0, sizeof(sb));
   sb.n_landmarks = L;
   sb.max_meas = M;
-  sb.uv = uv.data();
-  sb.clone_idx = cidx.data();
-  sb.n_meas = nm.data();
+  sb.uv = b.uv.data();
+  sb.clone_idx = b.cidx.data();
+  sb.n_meas = b.nm.data();
   sb.p_FinG = pv.data();
   sb.p_FinG_fej = pf.data();
   sb.landmark_id = lmid.data();
@@ -695,14 +608,7 @@ void UpdaterSLAM::update(std::shared_ptr<State> state, std::vector<std::shared_p
     sb.pre_H = pre_H.data();
     sb.pre_ids = pre_ids.data();
   }
-  ovp_update_opts uo;
-  memset(&uo, 0, sizeof(uo));
-  uo.sigma_px = _options_slam.sigma_pix;
-  uo.chi2_multiplier = _options_slam.chi2_multipler;
-  uo.sigma_constraint = sigma_c;
-  uo.do_fej = state->_options.do_fej ? 1 : 0;
-  uo.do_calib_camera_pose = state->_options.do_calib_camera_pose ? 1 : 0;
-  uo.do_calib_camera_intrinsics = state->_options.do_calib_camera_intrinsics ? 1 : 0;
+  const ovp_update_opts uo = make_update_opts(_options_slam, state->_options);
   const int n = ovp_cov_size(state->_gpu);
   std::vector<double> dx(n, 0.0);
   std::vector<uint8_t> status(L, 0);
@@ -710,7 +616,7 @@ void UpdaterSLAM::update(std::shared_ptr<State> state, std::vector<std::shared_p
   int rc;
   if (general) {
     upload_camera_tables(state);
-    rc = ovp_slam_update_general(state->_gpu, &uo, &sb, camv.data(), dx.data(), status.data(), nullptr, &info);
+    rc = ovp_slam_update_general(state->_gpu, &uo, &sb, b.cam.data(), dx.data(), status.data(), nullptr, &info);
   } else {
     rc = ovp_slam_update(state->_gpu, &uo, &sb, dx.data(), status.data(), nullptr, &info);
   }
@@ -905,97 +811,6 @@ void UpdaterSLAM::update_dense(std::shared_ptr<State> state, std::vector<std::sh
   StateHelper::EKFUpdate(state, big_order, H_big, r_big, R_big);  // :673
 }
 
-// update/UpdaterSLAM.cpp:120-166 (the same block opens UpdaterMSCKF::update and UpdaterPlane::init_vio_plane): features that
-// arrive with normalised measurements are triangulated (+ refined) on the device against the clone window; failures are flagged
-// and leave the vector.  Features whose position was handed over (no uvs_norm) pass through.
-void UpdaterSLAM::triangulate_on_device(std::shared_ptr<State> state, const ov_core::FeatureInitializerOptions &fio,
-                                        std::vector<std::shared_ptr<ov_core::Feature>> &feature_vec) {
-  bool any_norm = false;
-  for (auto &f : feature_vec) any_norm = any_norm || (!f->uvs_norm.empty() && f->uvs_norm.size() == f->uvs.size());
-  if (!any_norm) return;
-  std::map<double, int> clone_slot;
-  std::vector<std::shared_ptr<PoseJPL>> clones;
-  UpdaterSLAM::upload_state_tables(state, clone_slot, clones);
-  const int C = (int)clones.size(), F = (int)feature_vec.size();
-  int M = 1;
-  for (auto &f : feature_vec) M = std::max(M, (int)f->timestamps.size());
-  std::vector<float> uv((size_t)F * M * 2, 0.f), uvn((size_t)F * M * 2, 0.f);
-  std::vector<int> cidx((size_t)F * M, -1), nm(F);
-  std::vector<double> pf((size_t)F * 3);
-  for (int f = 0; f < F; ++f) {
-    nm[f] = (int)feature_vec[f]->timestamps.size();
-    for (int k = 0; k < nm[f]; ++k) {
-      cidx[(size_t)f * M + k] = clone_slot.at(feature_vec[f]->timestamps[k]);
-      uv[((size_t)f * M + k) * 2] = feature_vec[f]->uvs[2 * k];
-      uv[((size_t)f * M + k) * 2 + 1] = feature_vec[f]->uvs[2 * k + 1];
-    }
-    for (size_t k = 0; k < feature_vec[f]->uvs_norm.size(); ++k) uvn[(size_t)f * M * 2 + k] = feature_vec[f]->uvs_norm[k];
-    memcpy(&pf[3 * f], feature_vec[f]->p_FinG, 3 * sizeof(double));
-  }
-  ovp_feature_batch fb{F, M, uv.data(), cidx.data(), nm.data(), pf.data()};
-  gpu_check2(ovp_batch_upload(state->_gpu, &fb), "ovp_batch_upload");
-  ovp_triang_opts to;
-  to.refine_features = fio.refine_features ? 1 : 0;
-  to.triangulate_1d = fio.triangulate_1d ? 1 : 0;
-  to.reserved = 0;
-  to.max_runs = fio.max_runs;
-  to.init_lamda = fio.init_lamda;
-  to.max_lamda = fio.max_lamda;
-  to.min_dx = fio.min_dx;
-  to.min_dcost = fio.min_dcost;
-  to.lam_mult = fio.lam_mult;
-  to.min_dist = fio.min_dist;
-  to.max_dist = fio.max_dist;
-  to.max_baseline = fio.max_baseline;
-  to.max_cond_number = fio.max_cond_number;
-  std::vector<uint8_t> okv(F, 0);
-  gpu_check2(ovp_triangulate(state->_gpu, &to, uvn.data(), pf.data(), okv.data()), "ovp_triangulate");
-  // StateOptions::gpu_general_slam: a feature with another camera's views is triangulated over every view, each with its own
-  // camera's extrinsics (ovp_triangulate_general); the mono kernel would take camera 0's for all of them
-  std::vector<int> gidx;
-  if (state->_options.gpu_general_slam)
-    for (int i = 0; i < F; ++i)
-      if (!feature_vec[i]->only_camera0() && feature_vec[i]->uvs_norm.size() == feature_vec[i]->uvs.size() && nm[i] <= OVP_GEN_MAX_MEAS)
-        gidx.push_back(i);
-  if (!gidx.empty()) {
-    upload_camera_tables(state);
-    const int G = (int)gidx.size();
-    std::vector<int> gci((size_t)G * M, 0), gcam((size_t)G * M, 0), gnm(G);
-    std::vector<float> guvn((size_t)G * M * 2, 0.f);
-    for (int g = 0; g < G; ++g) {
-      const ov_core::Feature &ft = *feature_vec[gidx[g]];
-      gnm[g] = nm[gidx[g]];
-      for (int k = 0; k < gnm[g]; ++k) {
-        gci[(size_t)g * M + k] = cidx[(size_t)gidx[g] * M + k];
-        gcam[(size_t)g * M + k] = ft.cam_of(k);
-        guvn[((size_t)g * M + k) * 2] = ft.uvs_norm[2 * k];
-        guvn[((size_t)g * M + k) * 2 + 1] = ft.uvs_norm[2 * k + 1];
-      }
-    }
-    ovp_general_batch gb{G, M, guvn.data(), gci.data(), gcam.data(), gnm.data(), nullptr};
-    std::vector<double> gpf((size_t)G * 3, 0.0);
-    std::vector<uint8_t> gok(G, 0);
-    gpu_check2(ovp_triangulate_general(state->_gpu, &to, &gb, guvn.data(), gpf.data(), gok.data()), "ovp_triangulate_general");
-    for (int g = 0; g < G; ++g) {
-      okv[gidx[g]] = gok[g];
-      memcpy(&pf[3 * gidx[g]], &gpf[3 * g], 3 * sizeof(double));
-    }
-  }
-  size_t f = 0;
-  auto it1 = feature_vec.begin();
-  while (it1 != feature_vec.end()) {
-    const bool had_norm = !(*it1)->uvs_norm.empty();
-    if (had_norm && !okv[f]) {
-      (*it1)->to_delete = true;  // :161-165
-      it1 = feature_vec.erase(it1);
-    } else {
-      if (had_norm) memcpy((*it1)->p_FinG, &pf[3 * f], 3 * sizeof(double));
-      it1++;
-    }
-    ++f;
-  }
-}
-
 // OVP_HOST_PROFILE=1: wall-clock split of UpdaterSLAM::delayed_init, printed when the process exits
 namespace {
 struct DelayedInitProfile {
@@ -1024,7 +839,7 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
   // :80-118 clean, need >= 2 measurements
   auto it0 = feature_vec.begin();
   while (it0 != feature_vec.end()) {
-    clean_old_measurements(**it0, state->_clones_IMU);
+    keep_window_measurements(**it0, state->_clones_IMU);
     if ((*it0)->timestamps.size() < 2) {
       (*it0)->to_delete = true;
       it0 = feature_vec.erase(it0);
@@ -1035,7 +850,17 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
   // :120-166 triangulation of the features that come with normalised measurements (the joint point / plane refinement
   // :168-202 is not repeated here: positions handed over, or triangulated, are used as they are)
   const double t_a = now_s();
-  triangulate_on_device(state, _featinit, feature_vec);
+  if (any_wants_triangulation(feature_vec)) {
+    // update/UpdaterSLAM.cpp:120-166.  StateOptions::gpu_general_slam: a feature with another camera's views is triangulated over
+    // every view, each with its own camera's extrinsics; the mono kernel would take camera 0's for all of them
+    const CloneWindow window(state->_clones_IMU);
+    upload_state_tables(state, window);
+    TriangulationSite site;
+    const bool gen = state->_options.gpu_general_slam;
+    site.general = [gen](const ov_core::Feature &f) { return gen && !f.only_camera0() && (int)f.timestamps.size() <= OVP_GEN_MAX_MEAS; };
+    site.general_M_of_mono = true;
+    triangulate_on_device(state, window, _featinit, feature_vec, site);
+  }
   g_diprof.t_tri += now_s() - t_a;
   g_diprof.calls++;
   if (feature_vec.empty()) return;
@@ -1074,32 +899,17 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
   auto flush_run = [&](size_t run_begin, size_t run_end) -> size_t {
     const int L = (int)(run_end - run_begin);
     if (L <= 0) return run_end;
-    std::map<double, int> clone_slot;
-    std::vector<std::shared_ptr<PoseJPL>> clones;
-    upload_state_tables(state, clone_slot, clones);
-    int M = 2;
+    const CloneWindow window(state->_clones_IMU);
+    upload_state_tables(state, window);
+    PackSite site;
+    site.min_M = 2;
+    const FeaturePack b = pack_features(feature_range(feature_vec, run_begin, run_end), window.clone_slot, site);
+    const int M = b.M;
     bool other_camera = false;
-    for (int l = 0; l < L; ++l) {
-      M = std::max(M, (int)feature_vec[run_begin + l]->timestamps.size());
-      other_camera = other_camera || !feature_vec[run_begin + l]->only_camera0();
-    }
+    for (int l = 0; l < L; ++l) other_camera = other_camera || !feature_vec[run_begin + l]->only_camera0();
     // (the per-candidate host loop has neither limit; StateOptions::gpu_general_slam: other cameras take the general entry)
     const bool general = other_camera && state->_options.gpu_general_slam;
     if (M > OVP_MAX_MEAS || (other_camera && !general)) return (size_t)-1;
-    std::vector<float> uv((size_t)L * M * 2, 0.f);
-    std::vector<int> cidx((size_t)L * M, -1), nm(L), camv(general ? (size_t)L * M : 0, 0);
-    std::vector<double> pf((size_t)L * 3);
-    for (int l = 0; l < L; ++l) {
-      ov_core::Feature &ft = *feature_vec[run_begin + l];
-      nm[l] = (int)ft.timestamps.size();
-      for (int k = 0; k < nm[l]; ++k) {
-        cidx[(size_t)l * M + k] = clone_slot.at(ft.timestamps[k]);
-        uv[((size_t)l * M + k) * 2] = ft.uvs[2 * k];
-        uv[((size_t)l * M + k) * 2 + 1] = ft.uvs[2 * k + 1];
-        if (general) camv[(size_t)l * M + k] = ft.cam_of(k);
-      }
-      memcpy(&pf[3 * l], ft.p_FinG, 3 * sizeof(double));
-    }
     // StateOptions::gpu_dinit_planes: the planes of the run's candidates as a table, every candidate's slot in it, the fallback points
     const bool planes_on = state->_options.gpu_dinit_planes;
     std::vector<size_t> pl_ids;  // plane ids of the table's slots
@@ -1123,15 +933,9 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
         poc[l] = (int)q + 1;
         any_plane = true;
       }
-    ovp_feature_batch fb{L, M, uv.data(), cidx.data(), nm.data(), pf.data()};
-    ovp_update_opts uo;
-    memset(&uo, 0, sizeof(uo));
-    uo.sigma_px = _options_slam.sigma_pix;
-    uo.chi2_multiplier = _options_slam.chi2_multipler;
-    uo.sigma_constraint = state->_options.sigma_constraint;
-    uo.do_fej = state->_options.do_fej ? 1 : 0;
-    uo.do_calib_camera_pose = state->_options.do_calib_camera_pose ? 1 : 0;
-    uo.do_calib_camera_intrinsics = state->_options.do_calib_camera_intrinsics ? 1 : 0;
+    const ovp_feature_batch fb = b.as_feature_batch();
+    const ovp_general_batch gb = b.as_general_batch(general, true);
+    const ovp_update_opts uo = make_update_opts(_options_slam, state->_options);
     const int stride = ovp_cov_size(state->_gpu) + 3 * L;
     std::vector<uint8_t> okv(L, 0);
     std::vector<int> nid(L, -1);
@@ -1140,12 +944,10 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
     int rc;
     if (planes_on) {
       if (general) upload_camera_tables(state);
-      ovp_general_batch gb{L, M, uv.data(), cidx.data(), general ? camv.data() : nullptr, nm.data(), pf.data()};
       ovp_dinit_planes dpl{(int)pl_ids.size(), pl_sid.data(), pl_cp.data(), pl_cpf.data(), poc.data(), pnp.data()};
       rc = ovp_slam_delayed_init_planes(state->_gpu, &uo, &gb, &dpl, okv.data(), nullptr, nid.data(), dl.data(), dxs.data(), stride);
     } else if (general) {
       upload_camera_tables(state);
-      ovp_general_batch gb{L, M, uv.data(), cidx.data(), camv.data(), nm.data(), pf.data()};
       rc = ovp_slam_delayed_init_general(state->_gpu, &uo, &gb, okv.data(), nullptr, nid.data(), dl.data(), dxs.data(), stride);
     } else {
       rc = ovp_slam_delayed_init(state->_gpu, &uo, &fb, okv.data(), nullptr, nid.data(), dl.data(), dxs.data(), stride);
@@ -1489,12 +1291,8 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
                                   std::vector<std::shared_ptr<ov_core::Feature>> &feature_vec_used,
                                   const std::map<size_t, size_t> &feat2plane) {
   if (feature_vec.empty() || feat2plane.empty()) return;
-  std::map<double, int> clone_slot;
-  std::vector<std::shared_ptr<PoseJPL>> clones;
-  UpdaterSLAM::upload_state_tables(state, clone_slot, clones);
-  auto calib = state->_calib_IMUtoCAM.at(0);
-  auto intr = state->_cam_intrinsics.at(0);
-  const int C = (int)clones.size();
+  const CloneWindow window(state->_clones_IMU);
+  upload_state_tables(state, window);
   // StateOptions::gpu_general_plane_init: what the device batch cannot carry goes through the general batch (in the batch such a
   // feature is present with no measurements); off: every feature is a batch row of camera 0, as before
   const bool gen_on = state->_options.gpu_general_plane_init;
@@ -1505,27 +1303,7 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
     return gen_on && !(f.only_camera0() && (int)f.timestamps.size() <= OVP_MAX_MEAS);
   };
   auto is_general = [&](const ov_core::Feature &f) { return off_batch(f) && (int)f.timestamps.size() <= OVP_GEN_MAX_MEAS; };
-  auto upload = [&](const std::vector<std::shared_ptr<ov_core::Feature>> &fv, int &M_out) {
-    const int Fn = (int)fv.size();
-    int Mx = 1;
-    for (auto &f : fv)
-      if (!off_batch(*f)) Mx = std::max(Mx, (int)f->timestamps.size());
-    std::vector<float> uvb((size_t)Fn * Mx * 2, 0.f);
-    std::vector<int> cidxb((size_t)Fn * Mx, -1), nmb(Fn);
-    std::vector<double> pfb((size_t)Fn * 3);
-    for (int f = 0; f < Fn; ++f) {
-      nmb[f] = off_batch(*fv[f]) ? 0 : (int)fv[f]->timestamps.size();
-      for (int k = 0; k < nmb[f]; ++k) {
-        cidxb[(size_t)f * Mx + k] = clone_slot.at(fv[f]->timestamps[k]);
-        uvb[((size_t)f * Mx + k) * 2] = fv[f]->uvs[2 * k];
-        uvb[((size_t)f * Mx + k) * 2 + 1] = fv[f]->uvs[2 * k + 1];
-      }
-      memcpy(&pfb[3 * f], fv[f]->p_FinG, 3 * sizeof(double));
-    }
-    ovp_feature_batch fbb{Fn, Mx, uvb.data(), cidxb.data(), nmb.data(), pfb.data()};
-    gpu_check2(ovp_batch_upload(state->_gpu, &fbb), "ovp_batch_upload");
-    M_out = Mx;
-  };
+  const auto batch_meas = [&](const ov_core::Feature &f) { return off_batch(f) ? Meas::NONE : Meas::ALL; };
 
   // planes to initialise, ascending id (:297 iterates a std::map), and the features each of them may use
   std::vector<size_t> todo;
@@ -1535,20 +1313,19 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
     // pre-fitted entry point: the caller ran the fit (or owns better estimates)
     for (const auto &pe : state->_plane_estimates_cp_inG)
       if (state->_features_PLANE.find(pe.first) == state->_features_PLANE.end()) todo.push_back(pe.first);
-    for (auto &f : feature_vec) clean_old_measurements(*f, state->_clones_IMU);
+    for (auto &f : feature_vec) keep_window_measurements(*f, state->_clones_IMU);
   } else {
     fitted = true;
     // :76-107 on-plane features of planes that are not in the state, with at least two measurements in the window
     std::vector<std::shared_ptr<ov_core::Feature>> valid;
     auto it0 = feature_vec.begin();
     while (it0 != feature_vec.end()) {
+      keep_window_measurements(**it0, state->_clones_IMU);  // (every feature: the batch below needs window measurements only)
       auto fp = feat2plane.find((*it0)->featid);
       if (fp == feat2plane.end() || state->_features_PLANE.count(fp->second)) {
-        clean_old_measurements(**it0, state->_clones_IMU);  // (the batch below needs window measurements only)
         it0++;
         continue;
       }
-      clean_old_measurements(**it0, state->_clones_IMU);
       if ((*it0)->timestamps.size() < 2) {
         it0 = feature_vec.erase(it0);
       } else {
@@ -1557,72 +1334,11 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
       }
     }
     // :126-149 triangulate + refine; failures only leave the candidate set
-    bool any_norm = false;
-    for (auto &f : valid) any_norm = any_norm || (!f->uvs_norm.empty() && f->uvs_norm.size() == f->uvs.size());
-    if (any_norm && !valid.empty()) {
-      int Mv = 1;
-      upload(valid, Mv);
-      const int Fv = (int)valid.size();
-      std::vector<float> uvn((size_t)Fv * Mv * 2, 0.f);
-      for (int f = 0; f < Fv; ++f) {
-        if (off_batch(*valid[f])) continue;  // (no measurements in the batch; its row is Mv wide, its track may be longer)
-        for (size_t k = 0; k < valid[f]->uvs_norm.size(); ++k) uvn[(size_t)f * Mv * 2 + k] = valid[f]->uvs_norm[k];
-      }
-      ovp_triang_opts to;
-      to.refine_features = _featinit.refine_features ? 1 : 0;
-      to.triangulate_1d = _featinit.triangulate_1d ? 1 : 0;
-      to.reserved = 0;
-      to.max_runs = _featinit.max_runs;
-      to.init_lamda = _featinit.init_lamda;
-      to.max_lamda = _featinit.max_lamda;
-      to.min_dx = _featinit.min_dx;
-      to.min_dcost = _featinit.min_dcost;
-      to.lam_mult = _featinit.lam_mult;
-      to.min_dist = _featinit.min_dist;
-      to.max_dist = _featinit.max_dist;
-      to.max_baseline = _featinit.max_baseline;
-      to.max_cond_number = _featinit.max_cond_number;
-      std::vector<double> pfv((size_t)Fv * 3);
-      std::vector<uint8_t> okv(Fv, 0);
-      gpu_check2(ovp_triangulate(state->_gpu, &to, uvn.data(), pfv.data(), okv.data()), "ovp_triangulate");
-      std::vector<int> tg;  // gpu_general_plane_init: over every view, each with its own camera's extrinsics
-      for (int f = 0; f < Fv; ++f)
-        if (is_general(*valid[f]) && valid[f]->uvs_norm.size() == valid[f]->uvs.size()) tg.push_back(f);
-      if (!tg.empty()) {
-        UpdaterSLAM::upload_camera_tables(state);
-        const int G = (int)tg.size();
-        int GM = 1;
-        for (int f : tg) GM = std::max(GM, (int)valid[f]->timestamps.size());
-        std::vector<int> gci((size_t)G * GM, 0), gcam((size_t)G * GM, 0), gnm(G);
-        std::vector<float> guvn((size_t)G * GM * 2, 0.f);
-        for (int g = 0; g < G; ++g) {
-          const ov_core::Feature &ft = *valid[tg[g]];
-          gnm[g] = (int)ft.timestamps.size();
-          for (int k = 0; k < gnm[g]; ++k) {
-            gci[(size_t)g * GM + k] = clone_slot.at(ft.timestamps[k]);
-            gcam[(size_t)g * GM + k] = ft.cam_of(k);
-            guvn[((size_t)g * GM + k) * 2] = ft.uvs_norm[2 * k];
-            guvn[((size_t)g * GM + k) * 2 + 1] = ft.uvs_norm[2 * k + 1];
-          }
-        }
-        ovp_general_batch gb{G, GM, guvn.data(), gci.data(), gcam.data(), gnm.data(), nullptr};
-        std::vector<double> gpf((size_t)G * 3, 0.0);
-        std::vector<uint8_t> gok(G, 0);
-        gpu_check2(ovp_triangulate_general(state->_gpu, &to, &gb, guvn.data(), gpf.data(), gok.data()), "ovp_triangulate_general");
-        for (int g = 0; g < G; ++g) {
-          okv[tg[g]] = gok[g];
-          memcpy(&pfv[3 * tg[g]], &gpf[3 * g], 3 * sizeof(double));
-        }
-      }
-      std::vector<std::shared_ptr<ov_core::Feature>> good;
-      for (int f = 0; f < Fv; ++f) {
-        const bool had_norm = !valid[f]->uvs_norm.empty();
-        if (had_norm && !okv[f]) continue;
-        if (had_norm) memcpy(valid[f]->p_FinG, &pfv[3 * f], 3 * sizeof(double));
-        good.push_back(valid[f]);
-      }
-      valid = good;
-    }
+    TriangulationSite tri;
+    tri.mono = batch_meas;
+    tri.general = is_general;  // gpu_general_plane_init: over every view, each with its own camera's extrinsics
+    tri.flag_failures = false;
+    triangulate_on_device(state, window, _featinit, valid, tri);
     // :167-176 shortest tracks first (std::sort like the reference: the order of equal tracks is libstdc++'s)
     std::sort(valid.begin(), valid.end(), [](const std::shared_ptr<ov_core::Feature> &a, const std::shared_ptr<ov_core::Feature> &b) {
       return a->timestamps.size() < b->timestamps.size();
@@ -1639,25 +1355,12 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
       plane_feats[planeid].push_back(feat);
     }
     // :221-290 initial guess of every plane: RANSAC fit, then joint refinement with its features
-    PlaneFitting::ClonesCam clones_cam;
-    for (const auto &cl : state->_clones_IMU) {
-      PlaneFitting::ClonePose cpose;
-      const double *Ri = cl.second->Rot(), *Rc = calib->Rot(), *pi = cl.second->pos(), *pc = calib->pos();
-      for (int i = 0; i < 3; ++i)
-        for (int k = 0; k < 3; ++k) cpose.R[3 * i + k] = Rc[3 * i] * Ri[k] + Rc[3 * i + 1] * Ri[3 + k] + Rc[3 * i + 2] * Ri[6 + k];
-      for (int i = 0; i < 3; ++i) cpose.p[i] = pi[i] - (cpose.R[i] * pc[0] + cpose.R[3 + i] * pc[1] + cpose.R[6 + i] * pc[2]);
-      clones_cam[0][cl.first] = cpose;
-    }
-    const double sigma_px_norm = _options.sigma_pix / intr->value()(0);
-    double stateI[7], calib0[7];
-    memcpy(stateI, state->_imu->quat(), 4 * sizeof(double));
-    memcpy(stateI + 4, state->_imu->pos(), 3 * sizeof(double));
-    memcpy(calib0, calib->quat(), 4 * sizeof(double));
-    memcpy(calib0 + 4, calib->pos(), 3 * sizeof(double));
+    ClonesInCamera0 cam0 = clones_in_camera0(state);
+    const double sigma_px_norm = _options.sigma_pix / state->_cam_intrinsics.at(0)->value()(0);
     if (state->_options.gpu_fused_plane_fit) {
       // StateOptions::gpu_fused_plane_fit: every plane in ONE call (ovp_plane_fit_refine), poses from the resident tables, every
       // camera's observations; the planes without normalised measurements are left out as below
-      UpdaterSLAM::upload_camera_tables(state);
+      upload_camera_tables(state);
       std::vector<PlaneFitting::FrontPlane> jobs;
       for (auto &fp : plane_feats) {
         bool all_norm = true;
@@ -1668,7 +1371,7 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
         j.feats = &fp.second;
         jobs.push_back(j);
       }
-      PlaneFitting::fit_refine_all(jobs, clone_slot, state->_options.plane_init_min_feat, state->_options.plane_init_max_cond, true,
+      PlaneFitting::fit_refine_all(jobs, window.clone_slot, state->_options.plane_init_min_feat, state->_options.plane_init_max_cond, true,
                                    sigma_px_norm, state->_options.sigma_constraint, state->_imu->Rot(), state->_imu->pos());
       for (auto &j : jobs) {
         if (!j.ok) continue;
@@ -1684,7 +1387,7 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
         double abcd[4];
         if (!PlaneFitting::plane_fitting(fp.second, abcd, state->_options.plane_init_min_feat, state->_options.plane_init_max_cond)) continue;
         double cp0[3] = {-abcd[0] * abcd[3], -abcd[1] * abcd[3], -abcd[2] * abcd[3]};
-        if (!PlaneFitting::optimize_plane(fp.second, cp0, clones_cam, sigma_px_norm, state->_options.sigma_constraint, false, stateI, calib0))
+        if (!PlaneFitting::optimize_plane(fp.second, cp0, cam0.clones_cam, sigma_px_norm, state->_options.sigma_constraint, false, cam0.stateI, cam0.calib0))
           continue;
         state->_plane_estimates_cp_inG[fp.first] = {cp0[0], cp0[1], cp0[2]};
         todo.push_back(fp.first);
@@ -1697,8 +1400,11 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
     return;
   }
   const int F = (int)feature_vec.size();
-  int M = 1;
-  upload(feature_vec, M);
+  PackSite batch_site;
+  batch_site.which = batch_meas;
+  const FeaturePack b = pack_features(feature_range(feature_vec), window.clone_slot, batch_site);
+  const ovp_feature_batch fb = b.as_feature_batch();
+  gpu_check2(ovp_batch_upload(state->_gpu, &fb), "ovp_batch_upload");
   std::vector<int> pof(F, 0);
   for (int f = 0; f < F; ++f) {
     auto it = feat2plane.find(feature_vec[f]->featid);
@@ -1713,13 +1419,7 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
   std::vector<int> sid(NP, -1), nid(NP, -1);
   for (int k = 0; k < NP; ++k)
     for (int a = 0; a < 3; ++a) cpv[3 * k + a] = state->_plane_estimates_cp_inG.at(todo[k])[a];
-  ovp_update_opts o{_options.sigma_pix,
-                    _options.chi2_multipler,
-                    state->_options.sigma_constraint,
-                    state->_options.do_fej ? 1 : 0,
-                    state->_options.do_calib_camera_pose ? 1 : 0,
-                    state->_options.do_calib_camera_intrinsics ? 1 : 0,
-                    0};
+  const ovp_update_opts o = make_update_opts(_options, state->_options);
   const int stride = state->_options.max_state_size;
   std::vector<double> dxp((size_t)NP * stride, 0.0);
   std::vector<uint8_t> pok(NP, 0), fused(F, 0);
@@ -1729,28 +1429,19 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
     if (pof[f] > 0 && is_general(*feature_vec[f])) gidx.push_back(f);
   if (gen_on) {
     // one call over both kinds of features (update/UpdaterHelper.cpp:335-344: every camera's measurements of a feature)
-    UpdaterSLAM::upload_camera_tables(state);
+    upload_camera_tables(state);
     const int G = (int)gidx.size();
-    int GM = 1;
-    for (int f : gidx) GM = std::max(GM, (int)feature_vec[f]->timestamps.size());
-    std::vector<float> guv((size_t)std::max(G, 1) * GM * 2, 0.f);
-    std::vector<int> gci((size_t)std::max(G, 1) * GM, 0), gcam((size_t)std::max(G, 1) * GM, 0), gnm(std::max(G, 1), 0), gpl(std::max(G, 1), 0);
-    std::vector<double> gpf((size_t)std::max(G, 1) * 3, 0.0);
+    PackSite gen_site;
+    gen_site.pad = 0;
+    gen_site.empty_rows = 1;
+    const FeaturePack g = pack_features(feature_range(feature_vec, gidx), window.clone_slot, gen_site);
+    const ovp_general_batch gb = g.as_general_batch();
+    std::vector<int> gpl(std::max(G, 1), 0);
     std::vector<uint8_t> gused(std::max(G, 1), 0);
-    for (int g = 0; g < G; ++g) {
-      const ov_core::Feature &ft = *feature_vec[gidx[g]];
-      gnm[g] = (int)ft.timestamps.size();
-      gpl[g] = pof[gidx[g]];
-      pof[gidx[g]] = 0;
-      for (int k = 0; k < gnm[g]; ++k) {
-        gci[(size_t)g * GM + k] = clone_slot.at(ft.timestamps[k]);
-        gcam[(size_t)g * GM + k] = ft.cam_of(k);
-        guv[((size_t)g * GM + k) * 2] = ft.uvs[2 * k];
-        guv[((size_t)g * GM + k) * 2 + 1] = ft.uvs[2 * k + 1];
-      }
-      memcpy(&gpf[3 * g], ft.p_FinG, 3 * sizeof(double));
+    for (int i = 0; i < G; ++i) {
+      gpl[i] = pof[gidx[i]];
+      pof[gidx[i]] = 0;
     }
-    ovp_general_batch gb{G, GM, guv.data(), gci.data(), gcam.data(), gnm.data(), gpf.data()};
     gpu_check2(ovp_plane_init_general(state->_gpu, &o, &pb, state->_options.const_init_multi, state->_options.const_init_chi2, dxp.data(),
                                       stride, pok.data(), nullptr, nullptr, nid.data(), cpn.data(), fused.data(), &gb, gpl.data(),
                                       gused.data()),

@@ -5,7 +5,8 @@ import ctypes as C
 
 import numpy as np
 
-from ov_plane_amd.synth import PROP_OPTS, make_imu_scenario, make_scene, make_slam_scene, make_stereo_slam_scene, slam_rows_on_planes
+from ov_plane_amd.synth import (PROP_OPTS, make_imu_scenario, make_scene, make_slam_scene, make_stereo_plane_scene, make_stereo_slam_scene,
+                                slam_rows_on_planes)
 
 FIT = dict(min_feat=5, max_cond=200.0, variant=0)  # tests/test_plane_frontend_gpu.py
 
@@ -40,6 +41,9 @@ def scene(name):
             maintenance=_maintenance_scene, anchors=lambda: make_scene(C=6, F=4, seed=5, n_slam=2, do_fej=True),
             jacobian=lambda: make_scene(C=7, F=4, seed=5, do_fej=True, ragged=True),
             files=lambda: make_scene(C=5, F=4, seed=9),
+            # tests/test_plane_init_general_gpu.py: C = 34, the smallest window with tracks above the batch's 32 views; camera-1 views
+            long_tracks=lambda: make_scene(C=34, F=4 + 2 * 8, seed=3, ragged=True, min_meas=28, n_planes=2, feats_per_plane=8, chi2_mult=1.0),
+            stereo_plane=lambda: make_stereo_plane_scene(C=8, n_planes=2, feats_per_plane=10, planes_in_state_frac=0.0),
         )
         _SCENES[name] = make[name]()
     return _SCENES[name]
@@ -157,6 +161,14 @@ def _session(H):
     return {k: r[k] for k in ("traj", "counts")}
 
 
+def _slam_update_dense(H):
+    H.set_slam_force_dense(True)
+    try:
+        return H.run_updater(scene("slam"), "slam_update")
+    finally:
+        H.set_slam_force_dense(False)
+
+
 def cases(H):
     """H: ov_plane_amd.hostlib (of the checkout under test)"""
     S = scene
@@ -168,10 +180,16 @@ def cases(H):
     yield "msckf_update/stereo", lambda: H.run_msckf_update(S("stereo_fit"))
     yield "msckf_update/stereo+general", lambda: H.run_msckf_update(
         S("stereo_fit"), triangulate=True, fit_planes=FIT, general_features=True, general_planes=True, fused_plane_fit=True)
+    # tracks above OVP_MAX_MEAS views: camera 0's first 32 views triangulate them and the host's dense blocks gate them, or
+    # (general_features) both happen on the device
+    yield "msckf_update/long_tracks", lambda: H.run_msckf_update(S("long_tracks"), triangulate=True)
+    yield "msckf_update/long_tracks+general", lambda: H.run_msckf_update(S("long_tracks"), triangulate=True, general_features=True,
+                                                                         general_planes=True)
     yield "initialize", lambda: _initialize(H)
     yield "updater/slam_update", lambda: H.run_updater(S("slam"), "slam_update")
     for rep in (1, 2, 3, 4):
         yield "updater/slam_update/slam_rep=%d" % rep, lambda rep=rep: H.run_updater(S("slam"), "slam_update", slam_rep=(rep, 2))
+    yield "updater/slam_update/force_dense", lambda: _slam_update_dense(H)
     yield "updater/slam_update/stereo", lambda: H.run_updater(S("stereo_slam"), "slam_update")
     yield "updater/slam_update/general_slam", lambda: H.run_updater(S("stereo_slam"), "slam_update", general_slam=True)
     yield "updater/slam_delayed_init", lambda: H.run_updater(S("candidates"), "slam_delayed_init")
@@ -188,6 +206,10 @@ def cases(H):
     yield "updater/plane_init/fit_planes", lambda: H.run_updater(S("plane_init_fit"), "plane_init", 5.0, 1.0, fit_planes=FIT)
     yield "updater/plane_init/fused+general", lambda: H.run_updater(S("plane_init_fit"), "plane_init", 5.0, 1.0, fit_planes=FIT,
                                                                     fused_plane_fit=True, general_plane_init=True)
+    # camera-1 views on the planes: the general batch of ovp_plane_init_general is not empty, the triangulation takes its second pass
+    yield "updater/plane_init/stereo+general", lambda: H.run_updater(S("stereo_plane"), "plane_init", 5.0, 1.0, general_plane_init=True)
+    yield "updater/plane_init/stereo+fused+general", lambda: H.run_updater(S("stereo_plane"), "plane_init", 5.0, 1.0, fit_planes=FIT,
+                                                                           fused_plane_fit=True, general_plane_init=True)
     yield "updater/msckf_fit", lambda: H.run_updater(S("fit_slam"), "msckf_fit", fit_planes=FIT, slam=slam_rows_on_planes(S("fit_slam"), 2))
     yield "propagate", lambda: _propagate(H)
     yield "zupt", lambda: _zupt(H)
