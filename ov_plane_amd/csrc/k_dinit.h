@@ -2,8 +2,6 @@
 #pragma once
 #include "ovp_kernels.h"
 
-#define OVP_DINIT_DYN_LDS (138 * 1024)  // dynamic LDS of k_dinit_rows (160 KB minus its static tables)
-
 namespace ovp {
 
 struct DinitParams {
@@ -52,12 +50,8 @@ struct DinitPlaneParams {
 }  // namespace ovp
 
 extern "C" {
-size_t ovp_dinit_rows_lds(int m_obs, int ncal);
 hipError_t ovp_launch_dinit_rows(const ovp::DinitParams* dp, size_t lds, hipStream_t stream);
-size_t ovp_dinit_gen_rows_lds(int m_obs, int cols);
 hipError_t ovp_launch_dinit_rows_gen(const ovp::DinitGenParams* gp, size_t lds, hipStream_t stream);
-// the _pl instances: rows = 2m or 3m, cols = columns of H_x with the plane's three
-size_t ovp_dinit_pl_rows_lds(int rows, int cols);
 hipError_t ovp_launch_dinit_rows_pl(const ovp::DinitParams* dp, const ovp::DinitPlaneParams* pp, size_t lds, hipStream_t stream);
 hipError_t ovp_launch_dinit_rows_gen_pl(const ovp::DinitGenParams* gp, const ovp::DinitPlaneParams* pp, size_t lds, hipStream_t stream);
 }

@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "k_dinit.h"
+#include "ovp_lds_sizes.h"
 #include "ovp_feat_model.h"
 
 namespace ovp {
@@ -99,21 +100,6 @@ __global__ __launch_bounds__(DI_T) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
 }  // namespace ovp
 
 extern "C" {
-size_t ovp_dinit_rows_lds(int m_obs, int ncal) {
-  const int rows = 2 * m_obs, cols = 6 * m_obs + ncal, W = (cols + 4) | 1;
-  return sizeof(double) * ((size_t)rows * W + rows + 8 + (size_t)(cols + 2) / 2 + 2);
-}
-
-size_t ovp_dinit_gen_rows_lds(int m_obs, int cols) {
-  const int rows = 2 * m_obs, W = (cols + 4) | 1;
-  return sizeof(double) * ((size_t)rows * W + rows + 8 + (size_t)(cols + 2) / 2 + 2);
-}
-
-size_t ovp_dinit_pl_rows_lds(int rows, int cols) {
-  const int W = (cols + 4) | 1;
-  return sizeof(double) * ((size_t)rows * W + rows + 8 + (size_t)(cols + 2) / 2 + 2);
-}
-
 hipError_t ovp_launch_dinit_rows_pl(const ovp::DinitParams* dp, const ovp::DinitPlaneParams* pp, size_t lds, hipStream_t stream) {
   static unsigned long long attr_mask = 0;  // per device (ovp_kernels.h)
   if (ovp_lds_attr_needed(&attr_mask)) {

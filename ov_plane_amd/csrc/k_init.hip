@@ -15,6 +15,7 @@
 
 #include "ovp_dev.h"
 #include "ovp_kernels.h"
+#include "ovp_lds_sizes.h"
 
 namespace ovp {
 
@@ -131,13 +132,6 @@ __global__ __launch_bounds__(256) void k_init_update_sk(const double* __restrict
 }  // namespace ovp
 
 extern "C" {
-// LDS bytes of k_init_core without / with its copy of H^T; the caller refuses problems above ovp_init_max_lds()
-size_t ovp_init_core_lds(int k, int rup, int cols) {
-  return sizeof(double) * ((size_t)cols * (k + rup) + (size_t)rup * (2 * rup + 2));
-}
-size_t ovp_init_max_lds() { return 152 * 1024; }
-int ovp_init_max_rows() { return 80; }
-
 // skip == nullptr: the plain kernels; otherwise their _sk instances, which do nothing when skip[1] > 0.5 (k_init_update_sk then
 // copies skip[0 .. res_len) to res)
 hipError_t ovp_launch_init_m_sk(const double* skip, const double* P, int ldp, int n, const int* ids, int cols, const double* Ht, int m,

@@ -49,7 +49,6 @@ struct SlamGenParams {
 }  // namespace ovp
 
 extern "C" {
-size_t ovp_slam_gate_lds(int rows_max, int cols_max, int with_h);
 hipError_t ovp_launch_slam_gate(const ovp::SlamParams* sp, int n_landmarks, size_t lds, hipStream_t stream);
 hipError_t ovp_launch_slam_gate_gen(const ovp::SlamGenParams* gp, int n_landmarks, size_t lds, hipStream_t stream);
 }

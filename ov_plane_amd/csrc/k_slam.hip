@@ -17,11 +17,10 @@
 #include <stdint.h>
 
 #include "k_slam.h"
+#include "ovp_lds_sizes.h"
 #include "ovp_feat_model.h"
 
 namespace ovp {
-
-#define SL_CW 16  // columns of P_marg staged per chunk
 
 __global__ __launch_bounds__(256) void k_slam_gate(SlamParams sp) {
 #define SLAM_GEN 0
@@ -39,13 +38,6 @@ __global__ __launch_bounds__(256) void k_slam_gate_gen(SlamGenParams gp) {
 }  // namespace ovp
 
 extern "C" {
-size_t ovp_slam_gate_lds(int rows_max, int cols_max, int with_h) {
-  size_t d = (size_t)rows_max * (rows_max + 2) + rows_max + (size_t)rows_max * SL_CW + (size_t)cols_max * SL_CW +
-             (size_t)((cols_max + 1) / 2 + 1);
-  if (with_h) d += (size_t)rows_max * cols_max;
-  return d * sizeof(double);
-}
-
 hipError_t ovp_launch_slam_gate(const ovp::SlamParams* sp, int n_landmarks, size_t lds, hipStream_t stream) {
   static unsigned long long attr_mask = 0;  // per device (ovp_kernels.h)
   if (ovp_lds_attr_needed(&attr_mask)) {

@@ -606,7 +606,7 @@ extern "C" int ovp_cov_initialize(ovp_ctx* c, const double* Hx_init, const doubl
   if (n2 > c->n_max || cols > c->n_max) return OVP_E_CAPACITY;
   // S = H P H^T + R and the gathered rows of P H^T live in the LDS of one workgroup: the caller takes the three separate calls
   // for more rows than that holds (OVP_E_CAPACITY, nothing has been touched)
-  if (rup > ovp_init_max_rows() || ovp_init_core_lds(k, rup, cols) > ovp_init_max_lds()) return OVP_E_CAPACITY;
+  if (!ovp_init_fits(k, rup, cols)) return OVP_E_CAPACITY;
   for (int j = 0; j < cols; ++j)
     if (col_ids[j] < 0 || col_ids[j] >= n) return OVP_E_ARG;
   hipStream_t s = c->stream;

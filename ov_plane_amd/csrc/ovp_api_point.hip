@@ -692,9 +692,7 @@ extern "C" int ovp_ekf_update(ovp_ctx* c, const double* H_host, int rows, int co
     if (col_ids[j] < 0 || col_ids[j] >= n) return OVP_E_ARG;
   // few rows (a frame's landmark re-observations, a zero-velocity update): the reference's own S-form on the kernels of
   // csrc/k_init.hip - S = H P H^T + I in LDS, P+ = P - W W^T - instead of two N x N factorizations
-  const char* form_env = getenv("OVP_EKF_INFO_FORM");  // read per call: the tests run both forms in one process
-  const bool info_form_only = form_env && form_env[0] == '1';
-  if (!info_form_only && rows <= ovp_init_max_rows() && ovp_init_core_lds(0, rows, cols) <= ovp_init_max_lds() && cols <= c->n_max) {
+  if (!ekf_info_form_only() && ovp_init_fits(0, rows, cols) && cols <= c->n_max) {
     hipStream_t s = c->stream;
     const size_t oHt = 0, oRes = oHt + (size_t)cols * rows, oId = oRes + rows + 8;
     const size_t bytes = oId * sizeof(double) + sizeof(int) * (size_t)cols + 64;

@@ -35,6 +35,7 @@
 #include "k_slam.h"
 #include "k_dinit.h"
 #include "k_plane_gen.h"
+#include "ovp_lds_sizes.h"
 
 extern "C" int ovp_dbg_tilechol_skip;
 extern "C" {
@@ -116,9 +117,6 @@ hipError_t ovp_launch_init_core_sk(const double* skip, double* P, int ldp, int n
 hipError_t ovp_launch_init_update_sk(const double* skip, int res_len, const double* Psrc, double* Pdst, int ldp, int n2,
                                      const double* Mall, int m, int k, int rup, const double* Linv, const double* y, double* res,
                                      double* dx, hipStream_t stream);
-size_t ovp_init_core_lds(int k, int rup, int cols);
-size_t ovp_init_max_lds();
-int ovp_init_max_rows();
 hipError_t ovp_launch_gemm4c(int transA, int transB, int M, int N, int K, const double* A, int lda, const double* B, int ldb,
                              double* C, int ldc, int add_identity, int symmetric, const int* cancel, hipStream_t stream);
 hipError_t ovp_launch_plane_gate(const double* scal, const int* flags, double thr, int rows_live, int rows_u,
@@ -366,6 +364,13 @@ static inline void drop_kept_factor(ovp_ctx* c) {
   c->point_boost_n = 0;
   c->kept_boost = false;
   c->dense_cols.clear();  // (a pending dense pair was gated against the covariance that is being replaced)
+}
+
+// StateHelper::EKFUpdate takes the information form whatever the size (ovp_ekf_update, ovp_slam_update); read per call: the tests
+// run both forms in one process
+static inline bool ekf_info_form_only() {
+  const char* form_env = getenv("OVP_EKF_INFO_FORM");
+  return form_env && form_env[0] == '1';
 }
 
 static inline double host_now_ms() {
