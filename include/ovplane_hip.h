@@ -518,6 +518,46 @@ int ovp_cov_clone(ovp_ctx *ctx, int src_id, int size);
 int ovp_cov_clone_jitter(ovp_ctx *ctx, double relative_inflation);
 /* StateHelper::marginalize (state/StateHelper.cpp:276-344): removes rows/cols [id, id+size). */
 int ovp_cov_marginalize(ovp_ctx *ctx, int id, int size);
+/* StateHelper::marginalize (state/StateHelper.cpp:276-344) for several variables at once: removes the rows/cols of every range
+ * [ids[r], ids[r]+sizes[r]) in ONE pass over the covariance (k_retire.hip), where a loop of ovp_cov_marginalize copies it once
+ * per variable.  ids / sizes use the numbering the state has BEFORE the call and may come in any order.  The covariance and
+ * ovp_cov_size afterwards are bit-equal to ovp_cov_marginalize called once per range in descending order of id.
+ * Checked on the host before anything is touched: a range outside [0, n), a size below 1 or two ranges that overlap ->
+ * OVP_E_ARG; no covariance -> OVP_E_STATE; n_ranges == 0 -> 0, and nothing is launched or written.  Does not wait for the device. */
+int ovp_cov_marginalize_many(ovp_ctx *ctx, int n_ranges, const int *ids, const int *sizes);
+
+/* StateHelper::merge_planes_and_marginalize (state/StateHelper.cpp:654-757) from the first fused pair to the last retired plane,
+ * one enqueue and one wait.  The caller has run the reference's two loops as a plan (none of its renames, erasures or retirements
+ * depends on a pair's acceptance) and names the pairs in the order the reference meets them; all columns are those the state has
+ * BEFORE the call.
+ * Per pair (:693-734): res = (0 - (cp_new - cp_old)) / sigma, H = [I, -I] / sigma over the two planes' columns,
+ * S = H P H^T + I, chi2 = res^T S^-1 res, the angle of the two unit normals in degrees; accepted when
+ * chi2 < plane_merge_chi2 * chi2_0.95(3) AND angle < plane_merge_deg_max, and then a three-row StateHelper::EKFUpdate (:121-202).
+ * Pair k+1 sees the covariance and the closest points pair k left (cp += dx, closest points are Vec(3)); a plane may take part
+ * in several pairs, but none after it was fused away.  Removing rows / columns changes no other entry of the covariance, so the
+ * removals are deferred: behind the last pair every range of retire_* leaves in one pass, as ovp_cov_marginalize_many does it.  The
+ * old plane of every pair must be among them (it leaves whether or not its pair was accepted).
+ * Outputs per pair: accepted, chi2, angle_deg, and dx [n] at dx + k * dx_stride (dx_stride >= n = ovp_cov_size before the call),
+ * zero for a rejected pair.  The caller applies the accepted corrections IN ORDER through its variables' update: a quaternion
+ * update does not add, so they cannot be summed.
+ * Checked on the host before anything is touched: a column outside the state, new == old (or overlapping), an old column missing
+ * from retire_*, overlapping retire ranges, a pair naming a plane not in plane_col or one an earlier pair fused away ->
+ * OVP_E_ARG; more than 64 pairs -> OVP_E_CAPACITY.  A negative diagonal after a merge is OVP_E_NEGDIAG behind the wait, with the
+ * call carried out, as ovp_ekf_update reports it. */
+typedef struct {
+  int n_pairs;            /* merges, in the order the reference meets them          */
+  const int *new_col;     /* [n_pairs] first column of the surviving plane           */
+  const int *old_col;     /* [n_pairs] first column of the plane that is fused away  */
+  int n_planes;           /* distinct planes named above                             */
+  const int *plane_col;   /* [n_planes] their first columns                          */
+  const double *cp;       /* [3 * n_planes] their closest points (values) at entry   */
+  double sigma_plane_merge, plane_merge_chi2, plane_merge_deg_max;
+  int n_retire;           /* ranges that leave behind the merges (olds included)     */
+  const int *retire_ids, *retire_sizes;
+} ovp_plane_merge_in;
+int ovp_planes_merge_retire(ovp_ctx *ctx, const ovp_plane_merge_in *in, uint8_t *accepted /* [n_pairs] */,
+                            double *chi2 /* [n_pairs] */, double *angle_deg /* [n_pairs] */,
+                            double *dx /* [n_pairs * dx_stride] */, int dx_stride);
 /* StateHelper::augment_clone, time-offset part (state/StateHelper.cpp:613-624):
  *   Cov[:, pose..pose+5] += Cov[:, dt] * dnc_dt^T ;  Cov[pose..pose+5, :] += dnc_dt * Cov[dt, :]   (in that order) */
 int ovp_cov_augment_dt(ovp_ctx *ctx, int pose_id, int dt_id, const double dnc_dt[6]);

@@ -211,6 +211,13 @@ class ActiveTracksOut(C.Structure):
     _fields_ = [("cap", C.c_int), ("n_feats", C.c_int), ("n", C.c_int), ("ids", C.c_void_p), ("flags", C.c_void_p),
                 ("p_FinG", C.c_void_p), ("uvd", C.c_void_p)]
 
+class PlaneMergeIn(C.Structure):
+    """ovp_plane_merge_in"""
+    _fields_ = [("n_pairs", C.c_int), ("new_col", C.c_void_p), ("old_col", C.c_void_p), ("n_planes", C.c_int),
+                ("plane_col", C.c_void_p), ("cp", C.c_void_p), ("sigma_plane_merge", C.c_double), ("plane_merge_chi2", C.c_double),
+                ("plane_merge_deg_max", C.c_double), ("n_retire", C.c_int), ("retire_ids", C.c_void_p), ("retire_sizes", C.c_void_p)]
+
+
 EXPORTS = [
     "ovp_ctx_create", "ovp_ctx_destroy", "ovp_sync", "ovp_version", "ovp_error_string", "ovp_cov_upload",
     "ovp_cov_download", "ovp_cov_set_device", "ovp_cov_marginal", "ovp_state_upload", "ovp_batch_upload",
@@ -229,6 +236,7 @@ EXPORTS = [
     "ovp_plane_init_general", "ovp_delaunay_device", "ovp_plane_detector_set_device_delaunay",
     "ovp_active_tracks_create", "ovp_active_tracks_destroy", "ovp_active_tracks_reset", "ovp_active_tracks_update",
     "ovp_active_tracks_debug",
+    "ovp_cov_marginalize_many", "ovp_planes_merge_retire",
 ]
 
 
@@ -305,6 +313,9 @@ def lib():
                                         C.c_void_p, C.POINTER(C.c_int)]
         L.ovp_cov_clone.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.ovp_cov_marginalize.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.ovp_cov_marginalize_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.ovp_planes_merge_retire.argtypes = [C.c_void_p, C.POINTER(PlaneMergeIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int]
         L.ovp_cov_size.argtypes = [C.c_void_p]
         L.ovp_cov_initialize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int),
@@ -710,6 +721,34 @@ class Context:
 
     def cov_marginalize(self, vid, size):
         _chk(lib().ovp_cov_marginalize(self._h, int(vid), int(size)), "ovp_cov_marginalize")
+
+    def cov_marginalize_many(self, ids, sizes):
+        """StateHelper::marginalize for several variables in one pass (ids / sizes in the numbering before the call, any order)"""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        sizes = np.ascontiguousarray(sizes, dtype=np.int32)
+        assert ids.shape == sizes.shape and ids.ndim == 1
+        _chk(lib().ovp_cov_marginalize_many(self._h, len(ids), ids.ctypes.data, sizes.ctypes.data), "ovp_cov_marginalize_many")
+
+    def planes_merge_retire(self, new_col, old_col, plane_col, cp, sigma, chi2_mult, deg_max, retire_ids, retire_sizes):
+        """StateHelper::merge_planes_and_marginalize from the first fused pair to the last retired plane (ovp_planes_merge_retire).
+        Returns dict(accepted [n_pairs] bool, chi2, angle_deg, dx [n_pairs, n], neg_diag); every column is the one the state has
+        before the call."""
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+        new_col, old_col, plane_col, retire_ids, retire_sizes = map(i32, (new_col, old_col, plane_col, retire_ids, retire_sizes))
+        cp = np.ascontiguousarray(cp, dtype=np.float64).reshape(-1)
+        assert len(new_col) == len(old_col) and len(cp) == 3 * len(plane_col) and len(retire_ids) == len(retire_sizes)
+        m = PlaneMergeIn()
+        m.n_pairs, m.new_col, m.old_col = len(new_col), new_col.ctypes.data, old_col.ctypes.data
+        m.n_planes, m.plane_col, m.cp = len(plane_col), plane_col.ctypes.data, cp.ctypes.data
+        m.sigma_plane_merge, m.plane_merge_chi2, m.plane_merge_deg_max = float(sigma), float(chi2_mult), float(deg_max)
+        m.n_retire, m.retire_ids, m.retire_sizes = len(retire_ids), retire_ids.ctypes.data, retire_sizes.ctypes.data
+        n, k = self.cov_size(), max(len(new_col), 1)
+        acc, chi2, ang, dx = np.zeros(k, np.uint8), np.zeros(k), np.zeros(k), np.zeros((k, n))
+        rc = lib().ovp_planes_merge_retire(self._h, C.byref(m), acc.ctypes.data, chi2.ctypes.data, ang.ctypes.data, dx.ctypes.data, n)
+        if rc not in (0, OVP_E_NEGDIAG):
+            raise OvpError(rc, "ovp_planes_merge_retire")
+        k = len(new_col)
+        return dict(accepted=acc[:k].astype(bool), chi2=chi2[:k], angle_deg=ang[:k], dx=dx[:k], neg_diag=rc == OVP_E_NEGDIAG)
 
     # -- state / batch ---------------------------------------------------------------------------
     def state_upload(self, sc, state=None):

@@ -15,6 +15,7 @@ from .synth import radtan_undistort, state_layout
 # ids up to 4 * max_aruco_features (1024 by default) belong to ArUco corners, which are never marginalised
 # (state/StateHelper.cpp:638-652); ext TrackSIM shifts the simulator's map ids past them the same way
 FID_OFFSET = 4 * 1024 + 1
+PLANE_SPLIT = 1000  # run_session(split_planes_until=...): the second id a plane is reported under
 
 
 def collect(sim, n_frames):
@@ -168,7 +169,7 @@ def run(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, max_feats=
 def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, planes=0, plane_min_feat=6, sigma_c=0.01,
                 max_slam=0, feat_rep_slam=0, min_meas=3, out_dir=None, zupt=None, track_planes=True, forget_planes_at=None,
                 detect_planes=False, detect_opts=None, feed_plane_tracks=None, device_delaunay=False, active_tracks=False,
-                active_tracks_skip=()):
+                active_tracks_skip=(), batched_retire=False, split_planes_until=None):
     """Closed loop through hostlib.Session, frame by frame, with the tracker-side bookkeeping of core/VioManager.cpp:360-506:
     a track is an MSCKF feature once it is lost or reaches back to the clone about to be marginalised; a track that spans the
     whole window (more than max_clone_size measurements) becomes a SLAM landmark while there is room (max_slam), and from then
@@ -189,6 +190,12 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
     active_per_frame [K, 2] = (positions, uvd entries), active_depth_err [K] = median |depth - true depth| over the frame's uvd
     entries of simulated points (NaN without any), and active_frames = every frame's Session.active_tracks().
     active_tracks_skip: frame indices at which no points are handed over (test hook: such a step's maps are empty).
+    split_planes_until = frame index m (test hook, planes = 2 without the detector): before frame m the tracker reports every plane
+    under two ids - features with an odd id carry plane p as p + PLANE_SPLIT - so the state comes to hold two variables per
+    physical plane; at frame m the tracker fuses them (merged_planes (p, p + PLANE_SPLIT) for every p, the way the detector fuses
+    ids as tracks grow) and reports p alone from then on.  The result's plane_ids_per_frame = the state's plane ids behind every frame.
+    batched_retire: StateOptions::gpu_batched_retire - a frame's landmarks leave in one pass over the covariance, its plane merges and
+    the planes' removal are one device call.
     zupt: dict of Session.enable_zupt keywords (or {}) = VioManagerOptions::try_zupt: a frame at which the platform is found
     standing still gets a zero-velocity update instead of a clone (core/VioManager.cpp:311-331) and its measurements are dropped."""
     from . import hostlib
@@ -211,6 +218,8 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
         ses.enable_plane_detection(detect_opts)
     if active_tracks:
         ses.enable_active_tracks(int(sim.params["width"]), int(sim.params["height"]))
+    if batched_retire:
+        ses.enable_batched_retire()
     ses.feed_imu(imu)
     if out_dir is not None:
         import os
@@ -231,6 +240,7 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
         fk = frames[C - 1]
         ses.feed_tracks(fk[0], np.array(list(fk[1]), dtype=np.int64) + FID_OFFSET, np.array(list(fk[1].values())).reshape(-1, 2))
     slam_ids = set()
+    slam_frames, plane_frames = [], []  # the landmark ids / the plane ids the state holds behind every frame
     K = len(frames) - C
     traj, posecov, counts = np.zeros((K, 16)), np.zeros((K, 6, 6)), np.zeros((K, 6), dtype=np.int32)
     n_feats = np.zeros((K, 3), dtype=np.int32)
@@ -288,13 +298,15 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
         uvn = np.stack([xn, yn], axis=-1).astype(np.float32)
         fid = np.array([it[0] for it in items], dtype=np.int64)
         kind = np.array([it[1] for it in items], dtype=np.int32)
-        pl = np.array([max(plane_of[int(f)], 0) for f in fid], dtype=np.int32) if planes else None
+        split = split_planes_until is not None and i < split_planes_until
+        label = lambda f: plane_of[int(f)] + (PLANE_SPLIT if split and int(f) % 2 and plane_of[int(f)] > 0 else 0)  # noqa: E731
+        pl = np.array([max(label(f), 0) for f in fid], dtype=np.int32) if planes else None
         gt = sim.get_state(t_k + sim.params["calib_camimu_dt"])
         truth = np.concatenate([[gt["t"]], gt["q"], gt["p"], gt["v"], gt["bg"], gt["ba"], truth_tail])
         active = None
         if planes == 2 and track_planes:
             live = set(seen) | set(tracks) | {it[0] for it in items}
-            active = {plane_of[int(f)] for f in live if plane_of[int(f)] > 0}
+            active = {label(f) for f in live if plane_of[int(f)] > 0}
             if forget_planes_at is not None and i >= forget_planes_at:
                 active, pl = set(), np.zeros(len(fid), dtype=np.int32)
         if detect_planes or feed_plane_tracks or (active_tracks and i not in active_tracks_skip):
@@ -304,7 +316,11 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
             ses.feed_plane_tracks(t_k, s_id + FID_OFFSET, s_uv, np.stack([sx, sy], axis=-1))
         if detect_planes:
             pl, active = None, None
-        out = ses.step(t_k, uv, uvn, slot, nm, fid + FID_OFFSET, kind, pl, truth, active_planes=active)
+        merged = None
+        if split_planes_until is not None and i == split_planes_until:
+            merged = [(p_, p_ + PLANE_SPLIT) for p_ in sorted({v for v in plane_of.values() if v > 0})]
+        out = ses.step(t_k, uv, uvn, slot, nm, fid + FID_OFFSET, kind, pl, truth, active_planes=active, merged_planes=merged)
+        plane_frames.append(ses.plane_ids())
         if detect_planes:
             info = ses.plane_detection_info()
             if info["rc"] != 0:
@@ -321,6 +337,7 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
                 active_err[i] = float(np.median(err))
         window = win[1:]
         slam_ids = {i_ - FID_OFFSET for i_ in out["slam_ids"]}
+        slam_frames.append(sorted(slam_ids))
         for f in slam_ids:
             tracks.pop(f, None)
         traj[i], posecov[i], counts[i] = out["x16"], out["posecov"], out["counts"]
@@ -337,5 +354,5 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
         nees_o[i] = dth @ np.linalg.solve(posecov[i][0:3, 0:3], dth)
     return dict(times=times, traj=traj, posecov=posecov, counts=counts, n_feats=n_feats, zupt_frames=zupt_frames, e_pos=e_pos,
                 detected_per_frame=detected, active_per_frame=active_n, active_depth_err=active_err, active_frames=active_all,
-                e_ori=e_ori, nees_pos=nees_p, nees_ori=nees_o, rmse_pos=float(np.sqrt(np.mean(e_pos**2))),
+                slam_ids_per_frame=slam_frames, plane_ids_per_frame=plane_frames, e_ori=e_ori, nees_pos=nees_p, nees_ori=nees_o, rmse_pos=float(np.sqrt(np.mean(e_pos**2))),
                 rmse_ori_deg=float(np.degrees(np.sqrt(np.mean(e_ori**2)))))

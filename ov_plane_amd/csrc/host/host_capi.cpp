@@ -31,7 +31,7 @@ extern "C" int ovph_run_opts_layout(int *offsets, int cap) {
                      OVPH_OFF(fit_max_cond), OVPH_OFF(fit_variant), OVPH_OFF(slam_rep), OVPH_OFF(slam_anchor), OVPH_OFF(feat_rep_slam),
                      OVPH_OFF(slam_plane), OVPH_OFF(cam1_q), OVPH_OFF(cam1_p), OVPH_OFF(cam1_intr), OVPH_OFF(cam_of_meas),
                      OVPH_OFF(general_features), OVPH_OFF(general_planes), OVPH_OFF(general_plane_init), OVPH_OFF(fused_plane_fit),
-                     OVPH_OFF(general_slam), OVPH_OFF(dinit_planes), OVPH_OFF(p_noplane), OVPH_OFF(comm), OVPH_OFF(comm_rank),
+                     OVPH_OFF(general_slam), OVPH_OFF(dinit_planes), OVPH_OFF(batched_retire), OVPH_OFF(p_noplane), OVPH_OFF(comm), OVPH_OFF(comm_rank),
                      OVPH_OFF(comm_world), OVPH_OFF(device), OVPH_OFF(seq_traj), OVPH_OFF(seq_posecov), OVPH_OFF(seq_uv_norm),
                      OVPH_OFF(seq_plane), OVPH_OFF(seq_plane_mode), OVPH_OFF(seq_plane_min_feat), OVPH_OFF(seq_sigma_c),
                      OVPH_OFF(seq_planes_in_state), OVPH_OFF(last_shard), OVPH_OFF(last_cam1)};
@@ -640,7 +640,8 @@ extern "C" int ovph_run_zupt(int C, const double *clone_q, const double *clone_p
 // StateHelper::marginalize_slam + merge_planes_and_marginalize harness.  State: clones, n_slam landmarks (should_marg flags),
 // n_planes in-state planes (ids 1..n), every first estimate = value.  merge_pairs [n_pairs x 2] = (old id, new id);
 // active_planes = ids observed by features.
-// Outputs: final P / n, for every plane id 1..n+8 its Type::id() (or -1) and value, landmark ids (or -1).  Options read: fisheye.
+// Outputs: final P / n, for every plane id 1..n+8 its Type::id() (or -1) and value, landmark ids (or -1).  Options read: fisheye,
+// batched_retire.
 extern "C" int ovph_run_state_maintenance(int C, const double *clone_q, const double *clone_p, const double *calib_q,
                                           const double *calib_p, const double *intr, int n_slam, const double *slam_p,
                                           const unsigned char *should_marg, int n_planes, const double *cp, int N, const double *P,
@@ -658,6 +659,7 @@ extern "C" int ovph_run_state_maintenance(int C, const double *clone_q, const do
   so.sigma_plane_merge = sigma_plane_merge;
   so.plane_merge_chi2 = plane_merge_chi2;
   so.plane_merge_deg_max = plane_merge_deg_max;
+  so.gpu_batched_retire = op->batched_retire != 0;
   so.max_state_size = N + 8;
   so.max_features = 16;
   StateSpec sp;

@@ -33,7 +33,7 @@ typedef struct ovph_run_opts {
   const double *cam1_q, *cam1_p, *cam1_intr;
   const int32_t *cam_of_meas;
   // StateOptions::gpu_<name>
-  int32_t general_features, general_planes, general_plane_init, fused_plane_fit, general_slam, dinit_planes;
+  int32_t general_features, general_planes, general_plane_init, fused_plane_fit, general_slam, dinit_planes, batched_retire;
   const double *p_noplane;  // mode 1: positions before plane refinement of the candidates (Feature::p_FinG_original, [F][3])
   // ovph_run_msckf_update: the State lives on `device` and the updater takes the sharded point loop on this communicator
   void *comm;

@@ -1,4 +1,5 @@
 #include "ov_plane_host.h"
+#include "ov_plane_retire_plan.h"
 #include "ov_plane_io.h"
 #include "ov_plane_pack.h"
 #include <fstream>
@@ -241,6 +242,37 @@ void StateHelper::marginalize(std::shared_ptr<State> state, std::shared_ptr<Type
   marg->set_local_id(-1);
 }
 
+// The variables leave _variables and what stays moves up, as marginalize does it for one: applied in descending order of id, so
+// that every id read is still the one the caller's numbering gave it.
+void StateHelper::forget_variables(std::shared_ptr<State> state, const std::vector<std::shared_ptr<Type>> &margs) {
+  auto &vars = state->_variables;
+  std::vector<std::shared_ptr<Type>> order = margs;
+  std::sort(order.begin(), order.end(), [](const std::shared_ptr<Type> &a, const std::shared_ptr<Type> &b) { return a->id() > b->id(); });
+  for (auto &marg : order) {
+    const auto where = std::find(vars.begin(), vars.end(), marg);
+    if (where == vars.end()) {
+      PRINT_ERROR("StateHelper::marginalize_many() - a variable is not part of the state\n");
+      std::exit(EXIT_FAILURE);
+    }
+    const int gone_at = marg->id(), gone = marg->size();
+    vars.erase(where);
+    for (auto &v : vars)
+      if (v->id() > gone_at) v->set_local_id(v->id() - gone);
+    marg->set_local_id(-1);
+  }
+}
+
+void StateHelper::marginalize_many(std::shared_ptr<State> state, const std::vector<std::shared_ptr<Type>> &margs) {
+  if (margs.empty()) return;
+  std::vector<int> ids, sizes;
+  for (const auto &m : margs) {
+    ids.push_back(m->id());
+    sizes.push_back(m->size());
+  }
+  gpu_check(ovp_cov_marginalize_many(state->_gpu, (int)ids.size(), ids.data(), sizes.data()), "ovp_cov_marginalize_many");
+  forget_variables(state, margs);
+}
+
 // ---- state/StateHelper.cpp:346-396 -------------------------------------------------------------
 // The variable to copy is either a state variable itself or a sub-variable of one (the IMU's pose): the first state variable that
 // owns it decides where its block sits; the copy goes to the end of the covariance.
@@ -300,6 +332,16 @@ void StateHelper::marginalize_slam(std::shared_ptr<State> state) {
   std::vector<size_t> leaving;
   for (const auto &lm : state->_features_SLAM)
     if (lm.second->should_marg && (int)lm.first > 4 * state->_options.max_aruco_features) leaving.push_back(lm.first);
+  if (state->_options.gpu_batched_retire) {  // the same landmarks, one pass over the covariance
+    std::vector<std::shared_ptr<Type>> vars;
+    for (size_t id : leaving) vars.push_back(state->_features_SLAM.at(id));
+    StateHelper::marginalize_many(state, vars);
+    for (size_t id : leaving) {
+      state->_features_SLAM_to_PLANE.erase(id);
+      state->_features_SLAM.erase(id);
+    }
+    return;
+  }
   for (size_t id : leaving) {
     StateHelper::marginalize(state, state->_features_SLAM.at(id));
     state->_features_SLAM_to_PLANE.erase(id);
@@ -311,6 +353,7 @@ void StateHelper::marginalize_slam(std::shared_ptr<State> state) {
 void StateHelper::merge_planes_and_marginalize(std::shared_ptr<State> state, const std::map<size_t, size_t> &feat2plane,
                                                const std::map<size_t, std::set<size_t>> &plane2oldplane) {
   if (state->_features_PLANE.empty()) return;
+  if (state->_options.gpu_batched_retire) return merge_planes_and_marginalize_batched(state, feat2plane, plane2oldplane);
   auto it5 = state->_features_PLANE.begin();
   while (it5 != state->_features_PLANE.end()) {
     const size_t planeid = (*it5).first;
@@ -395,6 +438,59 @@ void StateHelper::merge_planes_and_marginalize(std::shared_ptr<State> state, con
       it5++;
     }
   }
+}
+
+// StateOptions::gpu_batched_retire: the two loops above as a plan (ov_plane_retire_plan.h), the merges and every removal in one
+// ovp_planes_merge_retire, then the corrections, the renames and the erasures in the reference's order.
+void StateHelper::merge_planes_and_marginalize_batched(std::shared_ptr<State> state, const std::map<size_t, size_t> &feat2plane,
+                                                       const std::map<size_t, std::set<size_t>> &plane2oldplane) {
+  auto &planes = state->_features_PLANE;
+  std::map<size_t, int> cols;
+  std::map<int, std::shared_ptr<Vec>> var_at;
+  for (const auto &p : planes) {
+    cols[p.first] = p.second->id();
+    var_at[p.second->id()] = p.second;
+  }
+  const RetirePlan plan = plan_plane_retire(cols, feat2plane, plane2oldplane);
+  if (!plan.retire_col.empty()) {
+    const int n = ovp_cov_size(state->_gpu), np = (int)plan.pairs.size();
+    std::vector<int> new_col, old_col, sizes(plan.retire_col.size(), 3);
+    for (const auto &pr : plan.pairs) {
+      new_col.push_back(pr.new_col);
+      old_col.push_back(pr.old_col);
+    }
+    std::vector<double> cp;
+    for (int c : plan.plane_col)
+      for (int k = 0; k < 3; ++k) cp.push_back(var_at.at(c)->value()(k));
+    ovp_plane_merge_in in;
+    in.n_pairs = np, in.new_col = new_col.data(), in.old_col = old_col.data();
+    in.n_planes = (int)plan.plane_col.size(), in.plane_col = plan.plane_col.data(), in.cp = cp.data();
+    in.sigma_plane_merge = state->_options.sigma_plane_merge;
+    in.plane_merge_chi2 = state->_options.plane_merge_chi2;
+    in.plane_merge_deg_max = state->_options.plane_merge_deg_max;
+    in.n_retire = (int)plan.retire_col.size(), in.retire_ids = plan.retire_col.data(), in.retire_sizes = sizes.data();
+    std::vector<uint8_t> accepted(std::max(np, 1));
+    std::vector<double> chi2(std::max(np, 1)), angle(std::max(np, 1)), dx((size_t)std::max(np, 1) * n);
+    const int rc = ovp_planes_merge_retire(state->_gpu, &in, accepted.data(), chi2.data(), angle.data(), dx.data(), n);
+    if (rc == OVP_E_NEGDIAG) {
+      PRINT_ERROR("StateHelper::EKFUpdate() - negative covariance diagonal\n");
+      std::exit(EXIT_FAILURE);
+    }
+    gpu_check(rc, "ovp_planes_merge_retire");
+    // every variable is still where the corrections address it: the bookkeeping comes behind them
+    for (int k = 0; k < np; ++k)
+      if (accepted[k]) apply_correction(state, dx.data() + (size_t)k * n);
+  }
+  std::vector<std::shared_ptr<Type>> leaving;
+  for (const auto &op : plan.ops) {
+    if (op.rename) {
+      planes.insert({op.new_id, planes.at(op.id)});
+    } else {
+      leaving.push_back(planes.at(op.id));
+    }
+    planes.erase(op.id);
+  }
+  forget_variables(state, leaving);
 }
 
 // ---- Eigen pieces used by initialize ----------------------------------------

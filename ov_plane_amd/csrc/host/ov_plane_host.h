@@ -87,6 +87,11 @@ struct StateOptions {
   // delayed initialisation and the anchor change: active_tracks_posinG / active_tracks_uvd of every tracked point.  The filter
   // does not read them.  In the reference the stage always runs (core/VioManager.cpp:757).
   bool gpu_active_tracks = false;
+  // StateHelper::marginalize_slam retires its landmarks in one pass over the covariance (ovp_cov_marginalize_many) and
+  // StateHelper::merge_planes_and_marginalize runs as a plan (ov_plane_retire_plan.h), one ovp_planes_merge_retire call - every
+  // merge in sequence, then one compaction - and the bookkeeping, instead of a marginal download, a host gate, an EKFUpdate and
+  // a marginalize per plane.  Not in the reference.
+  bool gpu_batched_retire = false;
   // UpdaterMSCKF::update: on-plane features the device batch cannot carry (another camera, more than OVP_MAX_MEAS views) stay in the
   // plane loop through ovp_msckf_plane_update_general instead of going to the point update without their plane constraint - for
   // planes whose estimate does not come from this frame's fit (in the state, or handed over in _plane_estimates_cp_inG); a frame with
@@ -222,6 +227,9 @@ public:
                                           const std::vector<std::shared_ptr<ov_type::Type>> &small_variables);
   static MatrixXd get_full_covariance(std::shared_ptr<State> state);
   static void marginalize(std::shared_ptr<State> state, std::shared_ptr<ov_type::Type> marg);
+  // state/StateHelper.cpp:276-344 applied to each variable: the bookkeeping of marginalize per variable, the covariance in one
+  // ovp_cov_marginalize_many
+  static void marginalize_many(std::shared_ptr<State> state, const std::vector<std::shared_ptr<ov_type::Type>> &margs);
   static std::shared_ptr<ov_type::Type> clone(std::shared_ptr<State> state, std::shared_ptr<ov_type::Type> variable_to_clone);
   static void augment_clone(std::shared_ptr<State> state, const double last_w[3]);
   static void marginalize_old_clone(std::shared_ptr<State> state);
@@ -241,6 +249,10 @@ public:
   static void apply_correction(std::shared_ptr<State> state, const double *dx);
 
 private:
+  // the host half of marginalize for variables whose rows / columns the device has already dropped (or is about to)
+  static void forget_variables(std::shared_ptr<State> state, const std::vector<std::shared_ptr<ov_type::Type>> &margs);
+  static void merge_planes_and_marginalize_batched(std::shared_ptr<State> state, const std::map<size_t, size_t> &feat2plane,
+                                                   const std::map<size_t, std::set<size_t>> &plane2oldplane);
   StateHelper() {}
 };
 

@@ -221,6 +221,26 @@ extern "C" int ovph_session_enable_active_tracks(void *h) {
   return 0;
 }
 
+// The ids of the planes the state holds, ascending (State::_features_PLANE); returns their number (at most `cap` are written).
+extern "C" int ovph_session_plane_ids(void *h, int cap, long long *ids) {
+  auto *s = static_cast<Session *>(h);
+  int n = 0;
+  for (const auto &p : s->state->_features_PLANE) {
+    if (n < cap) ids[n] = (long long)p.first;
+    ++n;
+  }
+  return n;
+}
+
+// StateOptions::gpu_batched_retire on (or off again): from the next step on marginalize_slam and merge_planes_and_marginalize retire
+// their variables in one device pass each.
+extern "C" int ovph_session_enable_batched_retire(void *h, int on) {
+  auto *s = static_cast<Session *>(h);
+  if (!s->state->gpu()) return -31;
+  s->state->_options.gpu_batched_retire = on != 0;
+  return 0;
+}
+
 extern "C" int ovph_session_set_image_size(void *h, int width, int height) {
   auto *s = static_cast<Session *>(h);
   if (!s->active || width < 1 || height < 1) return -21;

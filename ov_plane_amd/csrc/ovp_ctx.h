@@ -11,6 +11,7 @@
 //   k_plane_detect.hip plane detection from the tracked features: its kernels and its entry points
 //   k_delaunay.hip     the Delaunay triangulation of a frame's vertices in one workgroup (ovp_launch_delaunay, k_delaunay.h)
 //   k_active_tracks.hip re-triangulation of a frame's active tracks (ovp_active_tracks_*): its kernel and its entry points
+//   k_retire.hip       a frame's retirements in one compaction, its plane merges in sequence in front of it: kernels and entry points
 // Results reach the host through ovp_mailbox.h (Mailbox / SeqChannel; the copy-and-post kernel is k_publish.hip).
 #pragma once
 #include "ovplane_hip.h"
@@ -300,6 +301,7 @@ struct ovp_ctx {
   std::shared_ptr<void> plane_det;  // ovp_plane_detector_create (k_plane_detect.hip): the detector and its buffers, freed with the context
   std::shared_ptr<void> delaunay_io;  // ovp_delaunay_device (k_plane_detect.hip): its staging and mailbox, made on first use
   std::shared_ptr<void> active_tracks;  // ovp_active_tracks_create (k_active_tracks.hip): the slot table, its staging and mailbox, freed with the context
+  std::shared_ptr<void> retire;  // ovp_cov_marginalize_many / ovp_planes_merge_retire (k_retire.hip): their staging, scratch and mailbox, made on first use
 
   ovp_ctx() = default;
   ovp_ctx(const ovp_ctx&) = delete;

@@ -39,7 +39,7 @@ class RunOpts(C.Structure):
                 ("slam_anchor", C.c_int32), ("feat_rep_slam", C.c_int32), ("slam_plane", C.c_void_p), ("cam1_q", C.c_void_p),
                 ("cam1_p", C.c_void_p), ("cam1_intr", C.c_void_p), ("cam_of_meas", C.c_void_p), ("general_features", C.c_int32),
                 ("general_planes", C.c_int32), ("general_plane_init", C.c_int32), ("fused_plane_fit", C.c_int32),
-                ("general_slam", C.c_int32), ("dinit_planes", C.c_int32), ("p_noplane", C.c_void_p), ("comm", C.c_void_p),
+                ("general_slam", C.c_int32), ("dinit_planes", C.c_int32), ("batched_retire", C.c_int32), ("p_noplane", C.c_void_p), ("comm", C.c_void_p),
                 ("comm_rank", C.c_int32), ("comm_world", C.c_int32), ("device", C.c_int32), ("seq_traj", C.c_void_p),
                 ("seq_posecov", C.c_void_p), ("seq_uv_norm", C.c_void_p), ("seq_plane", C.c_void_p), ("seq_plane_mode", C.c_int32),
                 ("seq_plane_min_feat", C.c_int32), ("seq_sigma_c", C.c_double), ("seq_planes_in_state", C.c_int32),
@@ -347,10 +347,12 @@ def run_zupt(sc, x, imu, t_state, timestamps, calib_dt, po, noise_mult=10.0, chi
 
 
 def run_state_maintenance(sc, should_marg, merge_pairs, active_planes, sigma_plane_merge=0.001, plane_merge_chi2=1.0,
-                          plane_merge_deg_max=1.0):
+                          plane_merge_deg_max=1.0, batched_retire=False):
     """StateHelper::marginalize_slam followed by merge_planes_and_marginalize on a make_slam_scene-like state
-    (n_slam landmarks + all planes in the state)."""
+    (n_slam landmarks + all planes in the state).  batched_retire: StateOptions::gpu_batched_retire - the landmarks leave in one
+    ovp_cov_marginalize_many, the merges and the planes' removal are one ovp_planes_merge_retire."""
     L = lib()
+    ro = RunOpts(batched_retire=batched_retire)
     f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     N = int(sc.N)
@@ -368,7 +370,7 @@ def run_state_maintenance(sc, should_marg, merge_pairs, active_planes, sigma_pla
         C.c_int(sc.C), p(cq), p(cp_), p(calq), p(calp), p(intr), C.c_int(n_slam), p(slam_p), p(sm), C.c_int(n_pl), p(cp),
         C.c_int(N), p(P), C.c_int(mp.shape[0]), p(mp), C.c_int(len(ap)), p(ap), C.c_double(sigma_plane_merge),
         C.c_double(plane_merge_chi2), C.c_double(plane_merge_deg_max), p(out["P"]), p(out["n"]), p(out["plane_id"]),
-        p(out["plane_cp"]), p(out["slam_id"]), p(out["slam_to_plane"]), None)
+        p(out["plane_cp"]), p(out["slam_id"]), p(out["slam_to_plane"]), C.byref(ro))
     if rc != 0:
         raise RuntimeError("ovph_run_state_maintenance failed with %d" % rc)
     n2 = int(out["n"][0])
@@ -648,6 +650,21 @@ class Session:
                                                     uvn.ctypes.data_as(C.c_void_p))
         if rc != 0:
             raise RuntimeError("ovph_session_feed_plane_tracks failed with %d" % rc)
+
+    def plane_ids(self):
+        """ids of the planes the state holds (State::_features_PLANE), ascending"""
+        ids = np.zeros(256, dtype=np.int64)
+        n = self._L.ovph_session_plane_ids(C.c_void_p(self._h), C.c_int(len(ids)), ids.ctypes.data_as(C.c_void_p))
+        if n < 0 or n > len(ids):
+            raise RuntimeError("ovph_session_plane_ids failed with %d" % n)
+        return [int(i) for i in ids[:n]]
+
+    def enable_batched_retire(self, on=True):
+        """StateOptions::gpu_batched_retire: marginalize_slam and merge_planes_and_marginalize of every later step retire their
+        variables in one device pass each (ovp_cov_marginalize_many, ovp_planes_merge_retire)."""
+        rc = self._L.ovph_session_enable_batched_retire(C.c_void_p(self._h), C.c_int(1 if on else 0))
+        if rc != 0:
+            raise RuntimeError("ovph_session_enable_batched_retire failed with %d" % rc)
 
     def enable_active_tracks(self, width=752, height=480):
         """StateOptions::gpu_active_tracks: a step whose tracked points were handed over by feed_plane_tracks for its timestamp
