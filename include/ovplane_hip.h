@@ -558,6 +558,53 @@ typedef struct {
 int ovp_planes_merge_retire(ovp_ctx *ctx, const ovp_plane_merge_in *in, uint8_t *accepted /* [n_pairs] */,
                             double *chi2 /* [n_pairs] */, double *angle_deg /* [n_pairs] */,
                             double *dx /* [n_pairs * dx_stride] */, int dx_stride);
+
+/* UpdaterZeroVelocity::try_update from the stacked system to the corrected covariance (update/UpdaterZeroVelocity.cpp:119-265),
+ * gate and update in one device pass: one upload, one enqueue, one wait.  The caller keeps the preamble (:71-111), selects the
+ * readings (Propagator::select_imu_readings, :99-101), runs the disparity test (:207-227) and compares |v| with
+ * zupt_max_velocity BEFORE the call - both are inputs of the decision - and does the bookkeeping behind it (:245-247, :267-271).
+ * Every interval i of the n_readings - 1 contributes the same 6 x 9 block H0 = [[0, -I, 0], [-skew(R_jac g), 0, -I]] over
+ * [theta, b_g, b_a] (columns imu_id + {0..2, 9..14}), the residual r_i = -[w_i - b_g ; a_i - b_a - R g] of its FIRST reading
+ * (:141-166) and the noise zupt_noise_multiplier * sigma^2 / dt_i (:168-180).  With T = sum dt_i, rbar = sum dt_i r_i / T,
+ * D = diag(1 / (mult sigma_w^2) I3, 1 / (mult sigma_a^2) I3), Rbar = (T D)^-1 and P' = P + Q_bias on the bias block,
+ * Q_bias = T diag(sigma_wb I3, sigma_ab I3) (sigmas, not squares, as :184-186 has it), the stacked form equals, exactly,
+ *   chi2 = sum dt_i (r_i - rbar)^T D (r_i - rbar) + rbar^T Sbar^-1 rbar,   Sbar = H0 P'_ss H0^T + Rbar  (6 x 6, = Lbar Lbar^T)
+ *   P+ = P' - Y Y^T,  dx = Y z,   Y = P'_{:,s} H0^T Lbar^-T (n x 6),  z = Lbar^-1 rbar
+ * with 6 (n_readings - 1) degrees of freedom (:191-204, :256-265).  The sums run over a fixed tree in a fixed order, no atomics:
+ * two calls on the same input return the same bits.
+ *   accepted = disparity_passed || (chi2 <= chi2_threshold && vel_ok)                                       (:231-236)
+ * chi2_threshold = chi2_multipler * ovp_chi2_quantile_095(6 (n_readings - 1)), computed by the caller.
+ * Rejected: the covariance, the device tables and a factor the plane loop left are bit for bit as before, dx_host is zero.
+ * Accepted: P is the reference's EKFPropagation (Phi = I) followed by its EKFUpdate, dx_host [ovp_cov_size] the correction the
+ * caller applies through its variables' update; a negative diagonal is OVP_E_NEGDIAG behind the wait with the call carried out, as
+ * ovp_ekf_update reports it.  A non-positive pivot of Sbar ends the call as rejected with OVP_E_NOTSPD (out and info are filled).
+ * Checked on the host before anything is enqueued: fewer than two readings, a dt_i <= 0, imu_id < 0 or imu_id + 15 > n ->
+ * OVP_E_ARG; more than OVP_ZUPT_MAX_READINGS readings -> OVP_E_CAPACITY; no covariance -> OVP_E_STATE.
+ * info (may be NULL): n_rows = 6 (n_readings - 1), n_cols = 9, n_accepted, not_spd, neg_diag. */
+#define OVP_ZUPT_MAX_READINGS 4096 /* readings of one call (the staging block; a 400 Hz IMU / 10 Hz camera window holds 42) */
+typedef struct {
+  int n_readings;          /* readings Propagator::select_imu_readings returned                    */
+  const double *readings;  /* [n_readings][7] rows (t, w_m xyz, a_m xyz)                            */
+  int imu_id;              /* Type::id() of the IMU (error order th p v bg ba)                      */
+  double R_GtoI[9];        /* row-major rotation of the residual (value)                            */
+  double R_GtoI_jac[9];    /* ... of the Jacobian: the first estimate with do_fej, else the value   */
+  double b_g[3], b_a[3];
+  double gravity_mag;
+  double sigma_w, sigma_a, sigma_wb, sigma_ab; /* continuous-time noise densities (NoiseManager)    */
+  double zupt_noise_multiplier;
+  double chi2_threshold;
+  int vel_ok;              /* |v| <= zupt_max_velocity                                              */
+  int disparity_passed;    /* :207-227                                                              */
+  int time_kernels;        /* diagnostics: events around the three kernels (adds a synchronisation) */
+} ovp_zupt_in;
+typedef struct {
+  int accepted;
+  int rows;                /* 6 (n_readings - 1)                                                    */
+  double chi2;
+  float kernel_ms[3];      /* with time_kernels: gate, rows, apply; else 0                          */
+} ovp_zupt_out;
+int ovp_zupt_update(ovp_ctx *ctx, const ovp_zupt_in *in, double *dx_host, ovp_zupt_out *out, ovp_update_info *info);
+
 /* StateHelper::augment_clone, time-offset part (state/StateHelper.cpp:613-624):
  *   Cov[:, pose..pose+5] += Cov[:, dt] * dnc_dt^T ;  Cov[pose..pose+5, :] += dnc_dt * Cov[dt, :]   (in that order) */
 int ovp_cov_augment_dt(ovp_ctx *ctx, int pose_id, int dt_id, const double dnc_dt[6]);

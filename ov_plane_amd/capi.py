@@ -218,6 +218,23 @@ class PlaneMergeIn(C.Structure):
                 ("plane_merge_deg_max", C.c_double), ("n_retire", C.c_int), ("retire_ids", C.c_void_p), ("retire_sizes", C.c_void_p)]
 
 
+OVP_ZUPT_MAX_READINGS = 4096
+
+
+class ZuptIn(C.Structure):
+    """ovp_zupt_in"""
+    _fields_ = [("n_readings", C.c_int), ("readings", C.c_void_p), ("imu_id", C.c_int), ("R_GtoI", C.c_double * 9),
+                ("R_GtoI_jac", C.c_double * 9), ("b_g", C.c_double * 3), ("b_a", C.c_double * 3), ("gravity_mag", C.c_double),
+                ("sigma_w", C.c_double), ("sigma_a", C.c_double), ("sigma_wb", C.c_double), ("sigma_ab", C.c_double),
+                ("zupt_noise_multiplier", C.c_double), ("chi2_threshold", C.c_double), ("vel_ok", C.c_int),
+                ("disparity_passed", C.c_int), ("time_kernels", C.c_int)]
+
+
+class ZuptOut(C.Structure):
+    """ovp_zupt_out"""
+    _fields_ = [("accepted", C.c_int), ("rows", C.c_int), ("chi2", C.c_double), ("kernel_ms", C.c_float * 3)]
+
+
 EXPORTS = [
     "ovp_ctx_create", "ovp_ctx_destroy", "ovp_sync", "ovp_version", "ovp_error_string", "ovp_cov_upload",
     "ovp_cov_download", "ovp_cov_set_device", "ovp_cov_marginal", "ovp_state_upload", "ovp_batch_upload",
@@ -236,7 +253,7 @@ EXPORTS = [
     "ovp_plane_init_general", "ovp_delaunay_device", "ovp_plane_detector_set_device_delaunay",
     "ovp_active_tracks_create", "ovp_active_tracks_destroy", "ovp_active_tracks_reset", "ovp_active_tracks_update",
     "ovp_active_tracks_debug",
-    "ovp_cov_marginalize_many", "ovp_planes_merge_retire",
+    "ovp_cov_marginalize_many", "ovp_planes_merge_retire", "ovp_zupt_update",
 ]
 
 
@@ -316,6 +333,7 @@ def lib():
         L.ovp_cov_marginalize_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.ovp_planes_merge_retire.argtypes = [C.c_void_p, C.POINTER(PlaneMergeIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_int]
+        L.ovp_zupt_update.argtypes = [C.c_void_p, C.POINTER(ZuptIn), C.c_void_p, C.POINTER(ZuptOut), C.POINTER(UpdateInfo)]
         L.ovp_cov_size.argtypes = [C.c_void_p]
         L.ovp_cov_initialize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int),
@@ -749,6 +767,30 @@ class Context:
             raise OvpError(rc, "ovp_planes_merge_retire")
         k = len(new_col)
         return dict(accepted=acc[:k].astype(bool), chi2=chi2[:k], angle_deg=ang[:k], dx=dx[:k], neg_diag=rc == OVP_E_NEGDIAG)
+
+    def zupt_update(self, readings, imu_id, R_GtoI, R_GtoI_jac, b_g, b_a, po, chi2_threshold, noise_mult=10.0, vel_ok=True,
+                    disparity_passed=False, time_kernels=False):
+        """UpdaterZeroVelocity::try_update's gate and update in one device pass (ovp_zupt_update).  readings [n, 7] = what
+        Propagator::select_imu_readings returned; R_GtoI [3, 3] the value and R_GtoI_jac the rotation of the Jacobian (the first
+        estimate with do_fej); po: dict with sigma_w, sigma_a, sigma_wb, sigma_ab, gravity_mag; chi2_threshold =
+        chi2_multipler * chi2_quantile_095(6 (n - 1)).  Returns dict(accepted, chi2, rows, dx [n], neg_diag, kernel_ms [3])."""
+        f64 = lambda a, *sh: np.ascontiguousarray(a, dtype=np.float64).reshape(*sh)  # noqa: E731
+        rd = f64(readings, -1, 7)
+        z = ZuptIn()
+        z.n_readings, z.readings, z.imu_id = len(rd), rd.ctypes.data, int(imu_id)
+        z.R_GtoI[:], z.R_GtoI_jac[:] = list(f64(R_GtoI, 9)), list(f64(R_GtoI_jac, 9))
+        z.b_g[:], z.b_a[:] = list(f64(b_g, 3)), list(f64(b_a, 3))
+        z.gravity_mag = float(po["gravity_mag"])
+        z.sigma_w, z.sigma_a, z.sigma_wb, z.sigma_ab = (float(po[k]) for k in ("sigma_w", "sigma_a", "sigma_wb", "sigma_ab"))
+        z.zupt_noise_multiplier, z.chi2_threshold = float(noise_mult), float(chi2_threshold)
+        z.vel_ok, z.disparity_passed, z.time_kernels = int(bool(vel_ok)), int(bool(disparity_passed)), int(bool(time_kernels))
+        o, info = ZuptOut(), UpdateInfo()
+        dx = np.zeros(max(self.cov_size(), 1))
+        rc = lib().ovp_zupt_update(self._h, C.byref(z), dx.ctypes.data, C.byref(o), C.byref(info))
+        if rc not in (0, OVP_E_NEGDIAG):
+            raise OvpError(rc, "ovp_zupt_update")
+        return dict(accepted=bool(o.accepted), chi2=o.chi2, rows=o.rows, dx=dx[:self.cov_size()], neg_diag=rc == OVP_E_NEGDIAG,
+                    kernel_ms=np.array(o.kernel_ms[:]), info=info)
 
     # -- state / batch ---------------------------------------------------------------------------
     def state_upload(self, sc, state=None):

@@ -7,6 +7,7 @@
 // borrowed for that call only.  build_harness_state is the one place here that makes a State, export_state the one place that
 // copies one out.
 #include <cstddef>
+#include <chrono>
 #include <cstring>
 
 #include "host_capi.h"
@@ -590,17 +591,19 @@ extern "C" int ovph_run_propagate(int C, const double *clone_q, const double *cl
 // timestamps[k]; the feature database holds n_tracks tracks seen at t_state (uv0), timestamps[0] (uv1) and, with two calls,
 // timestamps[1] (uv1 again).  Outputs per call: accepted, chi2; final IMU value, calib_dt, covariance, state timestamp, and
 // how many measurements the database still holds at timestamps[0] (cleanup_measurements_exact on the second acceptance).
-extern "C" int ovph_run_zupt(int C, const double *clone_q, const double *clone_p, const double *imu_x16, const double *imu_x16_fej,
-                             double calib_dt, int N, const double *P, int n_imu, const double *imu, double t_state, int n_calls,
-                             const double *timestamps, const double *sigmas4, double gravity_mag, int do_fej, double noise_mult,
-                             double chi2_mult, double max_velocity, double max_disparity, int n_tracks, const float *uv0,
-                             const float *uv1,
-                             /* outputs */ int *out_accepted, double *out_chi2, double *out_x16, double *out_calib_dt, double *out_P,
-                             double *out_timestamp, int *out_meas_at_t1) {
+// gpu_zupt: StateOptions::gpu_zupt (ovph_run_zupt_opt; ovph_run_zupt is the same call with the option off); n_calls may exceed 2
+// when the stream covers that many camera periods (tools/zupt_timing.py).
+static int run_zupt(int C, const double *clone_q, const double *clone_p, const double *imu_x16, const double *imu_x16_fej,
+                    double calib_dt, int N, const double *P, int n_imu, const double *imu, double t_state, int n_calls,
+                    const double *timestamps, const double *sigmas4, double gravity_mag, int do_fej, double noise_mult,
+                    double chi2_mult, double max_velocity, double max_disparity, int n_tracks, const float *uv0, const float *uv1,
+                    /* outputs */ int *out_accepted, double *out_chi2, double *out_x16, double *out_calib_dt, double *out_P,
+                    double *out_timestamp, int *out_meas_at_t1, int gpu_zupt, double *out_try_update_ms) {
   ovph_run_opts o;
   ovph_run_opts_defaults(&o);
   StateOptions so;
   so.do_fej = do_fej != 0;
+  so.gpu_zupt = gpu_zupt != 0;
   so.do_calib_camera_pose = so.do_calib_camera_intrinsics = so.do_calib_camera_timeoffset = true;
   so.max_clone_size = C + 1;
   so.max_state_size = N + 16;
@@ -623,7 +626,9 @@ extern "C" int ovph_run_zupt(int C, const double *clone_q, const double *clone_p
   UpdaterZeroVelocity zupt(uo, nm, db, prop, gravity_mag, max_velocity, noise_mult, max_disparity);
   feed_imu_rows(zupt, n_imu, imu);
   for (int k = 0; k < n_calls; ++k) {
+    const auto t_in = std::chrono::steady_clock::now();
     out_accepted[k] = zupt.try_update(state, timestamps[k]) ? 1 : 0;
+    if (out_try_update_ms) out_try_update_ms[k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
     out_chi2[k] = zupt.last_chi2();
   }
   memcpy(out_x16, state->_imu->value().data(), 16 * sizeof(double));
@@ -635,6 +640,31 @@ extern "C" int ovph_run_zupt(int C, const double *clone_q, const double *clone_p
   *out_timestamp = state->_timestamp;
   *out_meas_at_t1 = (int)db->features_containing(timestamps[0]).size();
   return 0;
+}
+
+extern "C" int ovph_run_zupt(int C, const double *clone_q, const double *clone_p, const double *imu_x16, const double *imu_x16_fej,
+                             double calib_dt, int N, const double *P, int n_imu, const double *imu, double t_state, int n_calls,
+                             const double *timestamps, const double *sigmas4, double gravity_mag, int do_fej, double noise_mult,
+                             double chi2_mult, double max_velocity, double max_disparity, int n_tracks, const float *uv0,
+                             const float *uv1,
+                             /* outputs */ int *out_accepted, double *out_chi2, double *out_x16, double *out_calib_dt, double *out_P,
+                             double *out_timestamp, int *out_meas_at_t1) {
+  return run_zupt(C, clone_q, clone_p, imu_x16, imu_x16_fej, calib_dt, N, P, n_imu, imu, t_state, n_calls, timestamps, sigmas4,
+                  gravity_mag, do_fej, noise_mult, chi2_mult, max_velocity, max_disparity, n_tracks, uv0, uv1, out_accepted, out_chi2,
+                  out_x16, out_calib_dt, out_P, out_timestamp, out_meas_at_t1, 0, nullptr);
+}
+
+extern "C" int ovph_run_zupt_opt(int C, const double *clone_q, const double *clone_p, const double *imu_x16, const double *imu_x16_fej,
+                                 double calib_dt, int N, const double *P, int n_imu, const double *imu, double t_state, int n_calls,
+                                 const double *timestamps, const double *sigmas4, double gravity_mag, int do_fej, double noise_mult,
+                                 double chi2_mult, double max_velocity, double max_disparity, int n_tracks, const float *uv0,
+                                 const float *uv1,
+                                 /* outputs */ int *out_accepted, double *out_chi2, double *out_x16, double *out_calib_dt,
+                                 double *out_P, double *out_timestamp, int *out_meas_at_t1, int gpu_zupt,
+                                 double *out_try_update_ms /* [n_calls] host clock around each try_update, or NULL */) {
+  return run_zupt(C, clone_q, clone_p, imu_x16, imu_x16_fej, calib_dt, N, P, n_imu, imu, t_state, n_calls, timestamps, sigmas4,
+                  gravity_mag, do_fej, noise_mult, chi2_mult, max_velocity, max_disparity, n_tracks, uv0, uv1, out_accepted, out_chi2,
+                  out_x16, out_calib_dt, out_P, out_timestamp, out_meas_at_t1, gpu_zupt, out_try_update_ms);
 }
 
 // StateHelper::marginalize_slam + merge_planes_and_marginalize harness.  State: clones, n_slam landmarks (should_marg flags),

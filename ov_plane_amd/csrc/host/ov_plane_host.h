@@ -92,6 +92,10 @@ struct StateOptions {
   // merge in sequence, then one compaction - and the bookkeeping, instead of a marginal download, a host gate, an EKFUpdate and
   // a marginalize per plane.  Not in the reference.
   bool gpu_batched_retire = false;
+  // UpdaterZeroVelocity::try_update: the chi2 test, the decision, the bias random walk and the update are one device pass
+  // (ovp_zupt_update: one upload, one enqueue, one wait) instead of a marginal download, a 6 (n - 1)-row factorization on the host,
+  // an EKFPropagation and an EKFUpdate of the stacked rows.  Not in the reference.
+  bool gpu_zupt = false;
   // UpdaterMSCKF::update: on-plane features the device batch cannot carry (another camera, more than OVP_MAX_MEAS views) stay in the
   // plane loop through ovp_msckf_plane_update_general instead of going to the point update without their plane constraint - for
   // planes whose estimate does not come from this frame's fit (in the state, or handed over in _plane_estimates_cp_inG); a frame with
@@ -455,6 +459,8 @@ public:
   double last_chi2() const { return _last_chi2; }                          // diagnostics and tests
 
 protected:
+  // StateOptions::gpu_zupt: everything behind the preamble through ovp_zupt_update
+  bool try_update_device(std::shared_ptr<State> state, double timestamp, const std::vector<ov_core::ImuData> &imu_recent);
   UpdaterOptions _options;
   NoiseManager _noises;
   std::shared_ptr<ov_core::FeatureDatabase> _db;

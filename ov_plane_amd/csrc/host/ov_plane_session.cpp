@@ -241,6 +241,15 @@ extern "C" int ovph_session_enable_batched_retire(void *h, int on) {
   return 0;
 }
 
+// StateOptions::gpu_zupt on (or off again): from the next ovph_session_try_zupt on, UpdaterZeroVelocity::try_update gates and
+// updates in one device pass (ovp_zupt_update).
+extern "C" int ovph_session_enable_gpu_zupt(void *h, int on) {
+  auto *s = static_cast<Session *>(h);
+  if (!s->state->gpu()) return -31;
+  s->state->_options.gpu_zupt = on != 0;
+  return 0;
+}
+
 extern "C" int ovph_session_set_image_size(void *h, int width, int height) {
   auto *s = static_cast<Session *>(h);
   if (!s->active || width < 1 || height < 1) return -21;

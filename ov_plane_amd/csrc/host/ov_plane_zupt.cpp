@@ -3,7 +3,8 @@
 // the bias random walk is a StateHelper::EKFPropagation and the stacked IMU rows are one StateHelper::EKFUpdate, both on the
 // device.  The reference hard-codes integrated_accel_constraint = false, model_time_varying_bias = true,
 // override_with_disparity_check = true, explicitly_enforce_zero_motion = false (:113-116); the branches those constants
-// switch off are not built.
+// switch off are not built.  With StateOptions::gpu_zupt everything behind the preamble is one device pass (ovp_zupt_update:
+// try_update_device below).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -49,6 +50,7 @@ bool UpdaterZeroVelocity::try_update(std::shared_ptr<State> state, double timest
     PRINT_WARNING("[ZUPT]: fewer than two IMU readings between the state and the image: no zero-velocity test\n");
     return no_update();
   }
+  if (state->_options.gpu_zupt) return try_update_device(state, timestamp, imu_recent);
   // :119-125 order [q, bg, ba]
   const std::vector<std::shared_ptr<Type>> Hx_order{state->_imu->q(), state->_imu->bg(), state->_imu->ba()};
   const int h_size = 9, n_int = (int)imu_recent.size() - 1, m_size = 6 * n_int;
@@ -152,6 +154,69 @@ bool UpdaterZeroVelocity::try_update(std::shared_ptr<State> state, double timest
     StateHelper::EKFPropagation(state, biases, biases, MatrixXd::Identity(6, 6), Q_bias);
   }
   StateHelper::EKFUpdate(state, Hx_order, H, res, R);  // :265
+  state->_timestamp = timestamp;
+  last_zupt_state_timestamp = timestamp;
+  return true;
+}
+
+// StateOptions::gpu_zupt: try_update behind its preamble with the test, the decision and the update in one device pass
+// (ovp_zupt_update).  The disparity test (:207-227) and the velocity bound (:231) are inputs of the decision, so they run first.
+bool UpdaterZeroVelocity::try_update_device(std::shared_ptr<State> state, double timestamp,
+                                            const std::vector<ov_core::ImuData> &imu_recent) {
+  const int n_int = (int)imu_recent.size() - 1, m_size = 6 * n_int;
+  bool disparity_passed = false;
+  {
+    int num_features = 0;
+    double average_disparity = 0.0, variance_disparity = 0.0;
+    if (_db) ov_core::FeatureHelper::compute_disparity(_db, state->_timestamp, timestamp, average_disparity, variance_disparity, num_features);
+    disparity_passed = (average_disparity < _zupt_max_disparity && num_features > 20);
+  }
+  const double *v = state->_imu->vel();
+  const double vnorm = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+  std::vector<double> rows(7 * imu_recent.size());
+  for (size_t i = 0; i < imu_recent.size(); ++i) {
+    rows[7 * i] = imu_recent[i].timestamp;
+    for (int k = 0; k < 3; ++k) {
+      rows[7 * i + 1 + k] = imu_recent[i].wm[k];
+      rows[7 * i + 4 + k] = imu_recent[i].am[k];
+    }
+  }
+  ovp_zupt_in in;
+  memset(&in, 0, sizeof(in));
+  in.n_readings = (int)imu_recent.size();
+  in.readings = rows.data();
+  in.imu_id = state->_imu->id();
+  memcpy(in.R_GtoI, state->_imu->Rot(), 9 * sizeof(double));
+  memcpy(in.R_GtoI_jac, state->_options.do_fej ? state->_imu->Rot_fej() : state->_imu->Rot(), 9 * sizeof(double));  // :141-176
+  for (int k = 0; k < 3; ++k) {
+    in.b_g[k] = state->_imu->bias_g()[k];
+    in.b_a[k] = state->_imu->bias_a()[k];
+  }
+  in.gravity_mag = _gravity[2];
+  in.sigma_w = _noises.sigma_w, in.sigma_a = _noises.sigma_a, in.sigma_wb = _noises.sigma_wb, in.sigma_ab = _noises.sigma_ab;
+  in.zupt_noise_multiplier = _zupt_noise_multiplier;
+  in.chi2_threshold = _options.chi2_multipler * ovp_chi2_quantile_095(m_size);  // :197-204
+  in.vel_ok = vnorm > _zupt_max_velocity ? 0 : 1;
+  in.disparity_passed = disparity_passed ? 1 : 0;
+  std::vector<double> dx(ovp_cov_size(state->gpu()), 0.0);
+  ovp_zupt_out out;
+  const int rc = ovp_zupt_update(state->gpu(), &in, dx.data(), &out, nullptr);
+  if (rc == OVP_E_NOTSPD) {  // S lost definiteness: no update, as the host form leaves it
+    last_zupt_state_timestamp = 0.0;
+    return false;
+  }
+  if (rc != 0) {
+    fprintf(stderr, "ov_plane(gpu): ovp_zupt_update failed: %s\n", ovp_error_string(rc));
+    std::exit(EXIT_FAILURE);  // (a negative diagonal among them: StateHelper::EKFUpdate, state/StateHelper.cpp:185-187)
+  }
+  _last_chi2 = out.chi2;
+  if (!out.accepted) {
+    last_zupt_state_timestamp = 0.0;
+    return false;
+  }
+  // :245-247 we will not clone at this time: drop the measurements taken at the previous zero-velocity time
+  if (last_zupt_state_timestamp > 0.0 && _db) _db->cleanup_measurements_exact(last_zupt_state_timestamp);
+  StateHelper::apply_correction(state, dx.data());
   state->_timestamp = timestamp;
   last_zupt_state_timestamp = timestamp;
   return true;

@@ -187,7 +187,9 @@ extern "C" int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int
   HIPCHK(c->smallbuf.alloc((size_t)4 * c->n_max * 64 + (size_t)c->n_max * c->n_max));
   HIPCHK(c->ticket.alloc(4));
   HIPCHK(hipMemset(c->ticket, 0, 16));
-  HIPCHK(c->h_res_block.alloc(c->res_bytes));  // pinned mirror of res_block
+  // pinned mirror of res_block, and behind it (on a line of its own) the result block of ovp_zupt_update
+  c->zupt_res_off = StageLayout::al(c->res_bytes);
+  HIPCHK(c->h_res_block.alloc(c->zupt_res_off + sizeof(double) * (OVP_ZUPT_RES_HEAD + (size_t)c->n_max)));
   HIPCHK(c->h_slot.alloc((size_t)(n_feats_max + 16)));
   c->h_flags = (int*)c->h_res_block.payload();
   c->h_dx = (double*)((char*)c->h_res_block.payload() + 16);
@@ -548,6 +550,123 @@ extern "C" int ovp_cov_marginalize(ovp_ctx* c, int id, int size) {
   c->P.swap(c->P_tmp);
   c->n -= size;
   return 0;
+}
+
+// ---- zero-velocity update (k_zupt.hip) ------------------------------------------------------------
+namespace {
+
+// The entry's own buffers, made on first use and freed with the context.  Every call waits for its result, so the staging block
+// is free again when the next one fills it.
+struct Zupt {
+  PinnedBuf<void> hstage;
+  DevBuf<void> dstage;
+  DevBuf<double> work, Y, res;
+  DevBuf<unsigned> ticket;
+  size_t o_rd = 0, stage_bytes = 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // time_kernels: around the three kernels
+  ~Zupt() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+int zupt_of(ovp_ctx* c, Zupt** out) {
+  if (!c->zupt) {
+    auto d = std::make_shared<Zupt>();
+    StageLayout lay;
+    lay.take(sizeof(ovp::ZuptParams));
+    d->o_rd = lay.take(sizeof(double) * 7 * (size_t)OVP_ZUPT_MAX_READINGS);
+    d->stage_bytes = lay.bytes();
+    HIPCHK(d->hstage.alloc(d->stage_bytes));
+    HIPCHK(d->dstage.alloc(d->stage_bytes));
+    HIPCHK(d->work.alloc(OVP_ZW_DOUBLES));
+    HIPCHK(d->Y.alloc(6 * (size_t)c->n_max + 8));
+    HIPCHK(d->res.alloc(OVP_ZUPT_RES_HEAD + (size_t)c->n_max));
+    HIPCHK(d->ticket.alloc(4));
+    HIPCHK(hipMemset(d->ticket, 0, 16));
+    c->zupt = d;
+  }
+  *out = (Zupt*)c->zupt.get();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int ovp_zupt_update(ovp_ctx* c, const ovp_zupt_in* in, double* dx_host, ovp_zupt_out* out, ovp_update_info* info) {
+  if (!c || !in || !dx_host || !out) return OVP_E_ARG;
+  if (!c->have_cov) return OVP_E_STATE;
+  // ---- every check before anything is touched or enqueued ----
+  const int n = c->n, nr = in->n_readings;
+  if (nr < 2 || !in->readings || in->imu_id < 0 || in->imu_id + 15 > n) return OVP_E_ARG;
+  if (nr > OVP_ZUPT_MAX_READINGS) return OVP_E_CAPACITY;
+  for (int i = 0; i + 1 < nr; ++i)
+    if (!(in->readings[7 * (size_t)(i + 1)] - in->readings[7 * (size_t)i] > 0.0)) return OVP_E_ARG;
+  if (!(in->sigma_w > 0.0) || !(in->sigma_a > 0.0) || !(in->zupt_noise_multiplier > 0.0)) return OVP_E_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  Zupt* d = nullptr;
+  if (const int rc = zupt_of(c, &d)) return rc;
+  if (in->time_kernels && !d->ev[0])
+    for (hipEvent_t& e : d->ev) HIPCHK(hipEventCreate(&e));
+  // ---- one staged block [parameters | readings], one copy ----
+  char* h = (char*)d->hstage.get();
+  ovp::ZuptParams zp;
+  memset(&zp, 0, sizeof(zp));
+  const double* Rv = in->R_GtoI;
+  const double* Rj = in->R_GtoI_jac;
+  double Rjg[3];
+  for (int k = 0; k < 3; ++k) {
+    zp.bg[k] = in->b_g[k];
+    zp.ba[k] = in->b_a[k];
+    zp.Rg[k] = Rv[3 * k + 2] * in->gravity_mag;  // R [0 0 g]^T
+    Rjg[k] = Rj[3 * k + 2] * in->gravity_mag;
+  }
+  const double S3[9] = {0, -Rjg[2], Rjg[1], Rjg[2], 0, -Rjg[0], -Rjg[1], Rjg[0], 0};
+  memcpy(zp.S3, S3, sizeof(S3));
+  zp.d_w = 1.0 / (in->zupt_noise_multiplier * in->sigma_w * in->sigma_w);
+  zp.d_a = 1.0 / (in->zupt_noise_multiplier * in->sigma_a * in->sigma_a);
+  zp.q_wb = in->sigma_wb;
+  zp.q_ab = in->sigma_ab;
+  zp.thr = in->chi2_threshold;
+  zp.n_readings = nr;
+  zp.imu_id = in->imu_id;
+  zp.vel_ok = in->vel_ok != 0;
+  zp.disparity_passed = in->disparity_passed != 0;
+  memcpy(h, &zp, sizeof(zp));
+  memcpy(h + d->o_rd, in->readings, sizeof(double) * 7 * (size_t)nr);
+  const size_t bytes = d->o_rd + sizeof(double) * 7 * (size_t)nr;
+  hipStream_t s = c->stream;
+  char* dv = (char*)d->dstage.get();
+  HIPCHK(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, s));
+  // ---- one enqueue, one wait: the verdict and dx come back through the result mailbox's channel 2 ----
+  SeqChannel& ch = c->h_res_block.channel(2);
+  const unsigned seq = ch.arm();
+  const double* hres = (const double*)((const char*)c->h_res_block.payload() + c->zupt_res_off);
+  HIPCHK(ovp_launch_zupt(c->P, c->ld, n, in->imu_id, (const ovp::ZuptParams*)dv, (const double*)(dv + d->o_rd), d->work, d->Y, d->res,
+                         d->ticket, c->h_res_block.dev(hres), ch.word_dev(), seq, in->time_kernels ? d->ev : nullptr, s));
+  const int rw = ch.wait(s);
+  if (rw) return rw;
+  const bool acc = hres[0] != 0.0, neg = acc && hres[3] != 0.0, notspd = hres[4] != 0.0;
+  if (acc) drop_kept_factor(c);  // (the covariance was written: a kept factor no longer belongs to it; a rejected call keeps it)
+  memset(out, 0, sizeof(*out));
+  out->accepted = acc ? 1 : 0;
+  out->chi2 = hres[1];
+  out->rows = (int)hres[2];
+  if (acc) memcpy(dx_host, hres + OVP_ZUPT_RES_HEAD, sizeof(double) * n);
+  else memset(dx_host, 0, sizeof(double) * n);
+  if (in->time_kernels) {
+    HIPCHK(hipEventSynchronize(d->ev[3]));
+    for (int k = 0; k < 3; ++k) HIPCHK(hipEventElapsedTime(&out->kernel_ms[k], d->ev[k], d->ev[k + 1]));
+  }
+  if (info) {
+    memset(info, 0, sizeof(*info));
+    info->n_accepted = acc ? 1 : 0;
+    info->n_rows = out->rows;
+    info->n_cols = 9;
+    info->neg_diag = neg ? 1 : 0;
+    info->not_spd = notspd ? 1 : 0;
+  }
+  if (notspd) return OVP_E_NOTSPD;
+  return neg ? OVP_E_NEGDIAG : 0;
 }
 
 extern "C" int ovp_cov_initialize_invertible(ovp_ctx* c, const double* H_R, int k, int cols, int ld, const int* col_ids,

@@ -12,6 +12,7 @@
 //   k_delaunay.hip     the Delaunay triangulation of a frame's vertices in one workgroup (ovp_launch_delaunay, k_delaunay.h)
 //   k_active_tracks.hip re-triangulation of a frame's active tracks (ovp_active_tracks_*): its kernel and its entry points
 //   k_retire.hip       a frame's retirements in one compaction, its plane merges in sequence in front of it: kernels and entry points
+//   k_zupt.hip         the zero-velocity update's gate, rows and apply kernels (entry point: ovp_zupt_update in ovp_api_ctx.hip)
 // Results reach the host through ovp_mailbox.h (Mailbox / SeqChannel; the copy-and-post kernel is k_publish.hip).
 #pragma once
 #include "ovplane_hip.h"
@@ -280,7 +281,9 @@ struct ovp_ctx {
   unsigned char* h_accept = nullptr;
   int* h_flags = nullptr;
   DevBuf<void> res_block;                             // [flags | dx | chi2 | accept]
-  Mailbox h_res_block;                                // ... its pinned mirror; channel 0: the point update, channel 1: ovp_cov_propagate
+  Mailbox h_res_block;                                // ... its pinned mirror; channel 0: the point update, channel 1: ovp_cov_propagate,
+                                                      // channel 2: ovp_zupt_update, whose block [head 8 | dx n_max] starts at zupt_res_off
+  size_t zupt_res_off = 0;
   bool pub_pending = false;      // channel 0 is armed and a kernel of the running update will post it (k_dx_rows)
   bool need_join = false;     // chol(P) / K2 of the current update finish on stream2 (ev_join) rather than on the main stream
   DevBuf<unsigned> ticket;       // block counter of the publishing kernel
@@ -302,6 +305,7 @@ struct ovp_ctx {
   std::shared_ptr<void> delaunay_io;  // ovp_delaunay_device (k_plane_detect.hip): its staging and mailbox, made on first use
   std::shared_ptr<void> active_tracks;  // ovp_active_tracks_create (k_active_tracks.hip): the slot table, its staging and mailbox, freed with the context
   std::shared_ptr<void> retire;  // ovp_cov_marginalize_many / ovp_planes_merge_retire (k_retire.hip): their staging, scratch and mailbox, made on first use
+  std::shared_ptr<void> zupt;    // ovp_zupt_update (ovp_api_ctx.hip, k_zupt.hip): its staging and device blocks, made on first use
 
   ovp_ctx() = default;
   ovp_ctx(const ovp_ctx&) = delete;

@@ -218,9 +218,35 @@ struct PlaneFrontJob {
   int* iterations;              // [n_planes]
 };
 
+// ovp_zupt_update (k_zupt.hip).  The head of the call's staged block; the readings [n_readings][7] follow on the next 64-byte line.
+struct ZuptParams {
+  double bg[3], ba[3];
+  double Rg[3];          // R_GtoI g (the residual's rotation)
+  double S3[9];          // skew(R_jac g) row-major (the Jacobian's rotation: the first estimate with do_fej)
+  double d_w, d_a;       // D: 1 / (mult sigma_w^2), 1 / (mult sigma_a^2)
+  double q_wb, q_ab;     // Q_bias / T: sigma_wb, sigma_ab
+  double thr;            // chi2_multipler * quantile(6 (n - 1))
+  int n_readings, imu_id, vel_ok, disparity_passed;
+};
+// the device blocks of a call, in doubles.  Result (published to the host): [accepted | chi2 | rows | negative diagonal | not spd |
+// - - -] and dx [n] behind it.  Work: Lbar (6 x 6 lower, row-major), z, H0 (6 x 9), the diagonal of Q_bias, G = H0^T Lbar^-T (9 x 6).
+#define OVP_ZUPT_RES_HEAD 8
+#define OVP_ZW_L 0
+#define OVP_ZW_Z 36
+#define OVP_ZW_H0 42
+#define OVP_ZW_Q 96
+#define OVP_ZW_G 102
+#define OVP_ZW_DOUBLES 160
+
 }  // namespace ovp
 
 extern "C" {
+// k_zupt.hip: gate, rows and apply of one ovp_zupt_update, enqueued on `stream` with nothing waiting in between; the last step
+// copies OVP_ZUPT_RES_HEAD (+ n when accepted) doubles of res into host_block and stores seq into *word.  ticket: one zeroed word
+// the apply kernel counts its workgroups in and clears again.  ev: nullptr, or four events recorded around the three kernels.
+hipError_t ovp_launch_zupt(double* P, int ld, int n, int imu_id, const ovp::ZuptParams* zp, const double* readings, double* work,
+                           double* Y, double* res, unsigned* ticket, void* host_block, unsigned* word, unsigned seq, hipEvent_t* ev,
+                           hipStream_t stream);
 // k_publish.hip: `bytes` of the device block src -> dst (mapped pinned memory), then seq into *word; src, dst 8-byte aligned;
 // clear8 leading 8-byte words of src are zeroed behind the post
 hipError_t ovp_launch_publish_block(const void* src, void* dst, size_t bytes, unsigned* word, unsigned seq, int clear8,

@@ -313,10 +313,12 @@ def run_propagate(sc, x, imu, t_state, timestamp, calib_dt, po):
 
 
 def run_zupt(sc, x, imu, t_state, timestamps, calib_dt, po, noise_mult=10.0, chi2_mult=1.0, max_velocity=0.5, max_disparity=1.0,
-             uv0=None, uv1=None):
+             uv0=None, uv1=None, gpu_zupt=False, timing=False):
     """Drives ov_plane::UpdaterZeroVelocity::try_update (C++ host mirror; covariance on the device) at the camera times
     `timestamps` (1 or 2) on the clone window / covariance of a synth scene with IMU state x and readings imu [n,7]; uv0 / uv1
-    [n,2]: pixel positions of the tracks the feature database holds at t_state and at the new camera times."""
+    [n,2]: pixel positions of the tracks the feature database holds at t_state and at the new camera times.
+    gpu_zupt: StateOptions::gpu_zupt - gate and update in one device pass (ovp_zupt_update, through ovph_run_zupt_opt).
+    timing: also return try_update_ms [len(timestamps)], the host clock around each try_update (either route, ovph_run_zupt_opt)."""
     L = lib()
     f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
@@ -334,15 +336,22 @@ def run_zupt(sc, x, imu, t_state, timestamps, calib_dt, po, noise_mult=10.0, chi
     chi2 = np.zeros(len(ts))
     out = dict(x16=np.zeros(16), P=np.zeros((N, N)))
     dt_out, t_out, n_meas = C.c_double(0), C.c_double(0), C.c_int(0)
-    rc = L.ovph_run_zupt(C.c_int(sc.C), p(cq), p(cp_), p(x16), p(x16f), C.c_double(calib_dt), C.c_int(N), p(P),
-                         C.c_int(imu.shape[0]), p(imu), C.c_double(t_state), C.c_int(len(ts)), p(ts), p(sig),
-                         C.c_double(po["gravity_mag"]), C.c_int(int(po["do_fej"])), C.c_double(noise_mult), C.c_double(chi2_mult),
-                         C.c_double(max_velocity), C.c_double(max_disparity), C.c_int(uv0.shape[0]), p(uv0), p(uv1), p(acc),
-                         p(chi2), p(out["x16"]), C.byref(dt_out), p(out["P"]), C.byref(t_out), C.byref(n_meas))
+    args = (C.c_int(sc.C), p(cq), p(cp_), p(x16), p(x16f), C.c_double(calib_dt), C.c_int(N), p(P),
+            C.c_int(imu.shape[0]), p(imu), C.c_double(t_state), C.c_int(len(ts)), p(ts), p(sig),
+            C.c_double(po["gravity_mag"]), C.c_int(int(po["do_fej"])), C.c_double(noise_mult), C.c_double(chi2_mult),
+            C.c_double(max_velocity), C.c_double(max_disparity), C.c_int(uv0.shape[0]), p(uv0), p(uv1), p(acc),
+            p(chi2), p(out["x16"]), C.byref(dt_out), p(out["P"]), C.byref(t_out), C.byref(n_meas))
+    ms = np.zeros(len(ts))
+    if gpu_zupt or timing:
+        rc = L.ovph_run_zupt_opt(*args, C.c_int(1 if gpu_zupt else 0), p(ms) if timing else None)
+    else:
+        rc = L.ovph_run_zupt(*args)
     if rc != 0:
         raise RuntimeError("ovph_run_zupt failed with %d" % rc)
     out["P"] = np.ascontiguousarray(out["P"].T)
     out.update(accepted=acc.astype(bool), chi2=chi2, calib_dt=dt_out.value, timestamp=t_out.value, meas_at_t1=n_meas.value)
+    if timing:
+        out["try_update_ms"] = ms
     return out
 
 
@@ -665,6 +674,12 @@ class Session:
         rc = self._L.ovph_session_enable_batched_retire(C.c_void_p(self._h), C.c_int(1 if on else 0))
         if rc != 0:
             raise RuntimeError("ovph_session_enable_batched_retire failed with %d" % rc)
+
+    def enable_gpu_zupt(self, on=True):
+        """StateOptions::gpu_zupt: every later try_zupt gates and updates in one device pass (ovp_zupt_update)."""
+        rc = self._L.ovph_session_enable_gpu_zupt(C.c_void_p(self._h), C.c_int(1 if on else 0))
+        if rc != 0:
+            raise RuntimeError("ovph_session_enable_gpu_zupt failed with %d" % rc)
 
     def enable_active_tracks(self, width=752, height=480):
         """StateOptions::gpu_active_tracks: a step whose tracked points were handed over by feed_plane_tracks for its timestamp
