@@ -606,7 +606,8 @@ typedef struct {
 int ovp_zupt_update(ovp_ctx *ctx, const ovp_zupt_in *in, double *dx_host, ovp_zupt_out *out, ovp_update_info *info);
 
 /* StateHelper::augment_clone, time-offset part (state/StateHelper.cpp:613-624):
- *   Cov[:, pose..pose+5] += Cov[:, dt] * dnc_dt^T ;  Cov[pose..pose+5, :] += dnc_dt * Cov[dt, :]   (in that order) */
+ *   Cov[:, pose..pose+5] += Cov[:, dt] * dnc_dt^T ;  Cov[pose..pose+5, :] += dnc_dt * Cov[dt, :]   (in that order)
+ * OVP_E_ARG when the pose block or dt_id leaves the state, or dt_id lies inside the pose block. */
 int ovp_cov_augment_dt(ovp_ctx *ctx, int pose_id, int dt_id, const double dnc_dt[6]);
 /* StateHelper::initialize_invertible, covariance part (state/StateHelper.cpp:520-573): appends a k-dimensional variable
  * (k <= 6) at the end of the state.  H_R [k x cols] column-major (ld) with per-column state ids, H_Linv [k x k] and

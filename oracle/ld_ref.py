@@ -15,6 +15,7 @@ feature), so it is the cross-check (tests/test_ld_ref_cpu.py), not the truth.
   update_from_pair                                     P+ = (I + P A)^-1 P = (P^-1 + A)^-1, dx = P+ b (no P^-1: singular priors too)
   update_from_pair_dropping                            the same on the pivot-dropping factor of A (the device's S-form retry)
   ekf_update_dense                                     StateHelper::EKFUpdate (S-form, R = I) on the columns `cols`
+  ekf_propagation / augment_dt / initialize_invertible the covariance bookkeeping (StateHelper), each with its absolute companion
   err_state / rel_p / err_chi2 / err_pair              the error metrics of tests/test_precision_gpu.py
 """
 from __future__ import annotations
@@ -207,6 +208,74 @@ def ekf_update_dense(P, cols, H, r):
     W = solve_lower(L, M.T)  # L^-1 M^T
     y = solve_lower(L, r)
     return sym(P - W.T @ W), W.T @ y
+
+
+# ---- covariance bookkeeping ------------------------------------------------------------------------------------------------
+# Each returns (truth, companion).  The companion is the same expression with |.| of every operand, element by element (so every
+# sign of the expression becomes a plus): the quantity the rounding bound of a sum of products is a multiple of.  An element the
+# operation only copies has the companion |P_ij|.
+def _upper_view(M):
+    return np.triu(M) + np.triu(M, 1).T
+
+
+def _propagation(P, new_start, old, Phi, Q):
+    phi = Phi.shape[0]
+    CPT = P[:, old] @ Phi.T                      # Cov * Phi^T over the old columns            (n x phi)
+    PCP = Phi @ CPT[old, :] + _upper_view(Q)     # Phi * Cov * Phi^T + Q.selfadjointView<Upper>
+    Pn = P.copy()
+    s = slice(new_start, new_start + phi)
+    Pn[s, :] = CPT.T
+    Pn[:, s] = CPT
+    Pn[s, s] = PCP
+    return Pn
+
+
+def ekf_propagation(P, new_start, old_cols, Phi, Q):
+    """StateHelper::EKFPropagation (state/StateHelper.cpp:41-119) with the old variables flattened to their state columns
+    `old_cols` (any order, repeats allowed; Phi [phi x len(old_cols)] in that order): the rows and columns [new_start,
+    new_start + phi) become Phi P[old, :] and its transpose, the block Phi P[old, old] Phi^T + Q.selfadjointView<Upper>."""
+    old = np.asarray(old_cols, dtype=np.int64)
+    P, Phi, Q = ld(P), ld(Phi), ld(Q)
+    assert Phi.shape[1] == len(old) and Q.shape == (Phi.shape[0], Phi.shape[0])
+    return _propagation(P, new_start, old, Phi, Q), _propagation(np.abs(P), new_start, old, np.abs(Phi), np.abs(Q))
+
+
+def _augment_dt(P, pose_id, dt_id, d):
+    Pn = P.copy()
+    Pn[:, pose_id:pose_id + 6] += np.outer(Pn[:, dt_id], d)   # Cov.block(0, pose, n, 6) += Cov.col(dt) d^T
+    Pn[pose_id:pose_id + 6, :] += np.outer(d, Pn[dt_id, :])   # Cov.block(pose, 0, 6, n) += d Cov.row(dt), the row after step one
+    return Pn
+
+
+def augment_dt(P, pose_id, dt_id, d):
+    """StateHelper::augment_clone's time-offset Jacobian on a clone already in the state: the column step, then the row step on
+    the row dt the column step left.  dt_id must lie outside [pose_id, pose_id + 6)."""
+    assert not pose_id <= dt_id < pose_id + 6
+    P, d = ld(P), ld(d).reshape(6)
+    return _augment_dt(P, pose_id, dt_id, d), _augment_dt(np.abs(P), pose_id, dt_id, np.abs(d))
+
+
+def _initialize_invertible(P, cols, H_R, H_Linv, R, sign):
+    n, k = P.shape[0], H_R.shape[0]
+    M_a = P[:, cols] @ H_R.T                                   # P H^T                                     (n x k)
+    M = _upper_view(H_R @ M_a[cols, :] + R)                    # (H_R P H_R^T + R).selfadjointView<Upper>
+    Pn = np.zeros((n + k, n + k), dtype=P.dtype)
+    Pn[:n, :n] = P
+    Pn[n:, n:] = H_Linv @ M @ H_Linv.T
+    Pn[:n, n:] = sign * (M_a @ H_Linv.T)
+    Pn[n:, :n] = Pn[:n, n:].T
+    return Pn
+
+
+def initialize_invertible(P, cols, H_R, H_Linv, R):
+    """StateHelper::initialize_invertible (state/StateHelper.cpp:520-573) on the state columns `cols` (H_R [k x len(cols)] in that
+    order, H_Linv and R [k x k]): the covariance with the k new columns appended, P_LL = H_L^-1 M H_L^-T with the upper view of
+    M = H_R P[cols, cols] H_R^T + R, cross block -P[:, cols] H_R^T H_L^-T."""
+    cols = np.asarray(cols, dtype=np.int64)
+    P, H_R, H_Linv, R = ld(P), ld(H_R), ld(H_Linv), ld(R)
+    assert H_R.shape[1] == len(cols) and H_Linv.shape == R.shape == (H_R.shape[0], H_R.shape[0])
+    return (_initialize_invertible(P, cols, H_R, H_Linv, R, -1),
+            _initialize_invertible(np.abs(P), cols, np.abs(H_R), np.abs(H_Linv), np.abs(R), 1))
 
 
 # ---- error metrics ---------------------------------------------------------------------------------------------------------

@@ -335,6 +335,9 @@ def lib():
                                               C.c_int]
         L.ovp_zupt_update.argtypes = [C.c_void_p, C.POINTER(ZuptIn), C.c_void_p, C.POINTER(ZuptOut), C.POINTER(UpdateInfo)]
         L.ovp_cov_size.argtypes = [C.c_void_p]
+        L.ovp_cov_augment_dt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.ovp_cov_initialize_invertible.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]
         L.ovp_cov_initialize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int),
                                          C.POINTER(C.c_double), C.c_void_p]
@@ -693,19 +696,54 @@ class Context:
         return self._h
 
     # -- covariance -----------------------------------------------------------------------------
-    def cov_upload(self, P):
+    def cov_upload(self, P, ld=None):
+        """ld: leading dimension of the host copy the entry reads (>= n, default n); the rows are laid out with it first"""
         P = np.ascontiguousarray(P, dtype=np.float64)
         n = P.shape[0]
+        if ld is not None and int(ld) != n:
+            ld = int(ld)
+            host = np.full((n, max(ld, n)), np.nan)
+            host[:, :n] = P
+            _chk(lib().ovp_cov_upload(self._h, host.ctypes.data, n, ld), "ovp_cov_upload")
+            return
         _chk(lib().ovp_cov_upload(self._h, P.ctypes.data, n, n), "ovp_cov_upload")
 
     def cov_set_device(self, dev_ptr, n, ld):
         _chk(lib().ovp_cov_set_device(self._h, C.c_void_p(dev_ptr), n, ld), "ovp_cov_set_device")
 
-    def cov_download(self):
+    def cov_download(self, ld=None):
+        """ld: leading dimension of the host copy the entry writes (>= n, default n); the n x n block is returned either way"""
         n = lib().ovp_cov_size(self._h)
+        if ld is not None and int(ld) != n:
+            ld = int(ld)
+            host = np.full((n, max(ld, n)), np.nan)
+            _chk(lib().ovp_cov_download(self._h, host.ctypes.data, n, ld), "ovp_cov_download")
+            assert np.isnan(host[:, n:]).all()  # the entry writes the n columns of a row only
+            return np.ascontiguousarray(host[:, :n])
         P = np.zeros((n, n))
         _chk(lib().ovp_cov_download(self._h, P.ctypes.data, n, n), "ovp_cov_download")
         return P
+
+    def cov_augment_dt(self, pose_id, dt_id, dnc_dt):
+        """StateHelper::augment_clone's time-offset Jacobian on the pose block at pose_id (ovp_cov_augment_dt)"""
+        d = np.ascontiguousarray(dnc_dt, dtype=np.float64).reshape(6)
+        _chk(lib().ovp_cov_augment_dt(self._h, int(pose_id), int(dt_id), d.ctypes.data), "ovp_cov_augment_dt")
+
+    def cov_initialize_invertible(self, H_R, col_ids, H_Linv, R, ld=None):
+        """StateHelper::initialize_invertible's covariance part (ovp_cov_initialize_invertible): H_R [k, cols] with the state
+        column of each of its columns, H_Linv and R [k, k]; the covariance grows by k.  ld: leading dimension of the column-major
+        H_R the entry reads (>= k, default k)."""
+        H_R = np.asarray(H_R, dtype=np.float64)
+        k, cols = H_R.shape
+        ld = k if ld is None else int(ld)
+        hr = np.full((cols, max(ld, k)), np.nan)  # row a = column a of H_R, ld apart
+        hr[:, :k] = H_R.T
+        col_ids = np.ascontiguousarray(col_ids, dtype=np.int32).reshape(-1)
+        assert len(col_ids) == cols
+        Hi = np.asfortranarray(np.asarray(H_Linv, dtype=np.float64).reshape(k, k))
+        Rk = np.asfortranarray(np.asarray(R, dtype=np.float64).reshape(k, k))
+        _chk(lib().ovp_cov_initialize_invertible(self._h, hr.ctypes.data, k, cols, ld, col_ids.ctypes.data, Hi.ctypes.data,
+                                                 Rk.ctypes.data), "ovp_cov_initialize_invertible")
 
     def cov_size(self):
         return lib().ovp_cov_size(self._h)

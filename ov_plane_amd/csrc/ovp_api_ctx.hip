@@ -708,6 +708,8 @@ extern "C" int ovp_cov_augment_dt(ovp_ctx* c, int pose_id, int dt_id, const doub
   if (!c || !dnc_dt) return OVP_E_ARG;
   if (!c->have_cov) return OVP_E_STATE;
   if (pose_id < 0 || pose_id + 6 > c->n || dt_id < 0 || dt_id >= c->n) return OVP_E_ARG;
+  // (a time offset inside the pose block has no meaning, and the two steps would read the columns and rows they write)
+  if (dt_id >= pose_id && dt_id < pose_id + 6) return OVP_E_ARG;
   HIPCHK(ovp_launch_augment_dt(c->P, c->ld, c->n, pose_id, dt_id, dnc_dt, c->stream));
   return 0;
 }

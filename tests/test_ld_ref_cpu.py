@@ -162,3 +162,155 @@ def test_pivot_dropping_update_equals_the_plain_one_on_an_exact_pair():
     Pd, dxd, dropped = ld_ref.update_from_pair_dropping(sc.P, pair["A"], pair["b"])
     assert set(range(16)) <= set(dropped)
     assert ld_ref.err_state(dxd, dxt, Pt) < 1e-11 and ld_ref.rel_p(Pd, Pt) < 1e-12
+
+
+# ---- covariance bookkeeping: the restatements of tests/test_cov_bookkeeping_gpu.py, their bounds, and the mutations the bounds catch ----
+import cov_bookkeeping_cases as B  # noqa: E402
+
+
+def _embed(n, rows, block):
+    F = np.eye(n, dtype=LD)
+    F[rows, :] = 0
+    F[rows, :] = block
+    return F
+
+
+@pytest.mark.parametrize("c", B.prop_cases(), ids=lambda c: c["name"])
+def test_propagation_restatement_against_the_double_one_and_F_P_Ft(c):
+    """ld_ref.ekf_propagation == np_ref.ekf_propagation to double rounding (inside the derived bound), == F P F^T + Q embedded in
+    the state with F the identity whose rows [new_start, new_start + phi) are replaced by Phi scattered to the old columns, and its
+    companion is the same computation on absolute values."""
+    P, Phi, Q = B.prop_inputs(c)
+    old, a, phi, n = B.flat(c["old"]), c["start"], c["phi"], c["n"]
+    T, comp = ld_ref.ekf_propagation(P, a, old, Phi, Q)
+    assert T.dtype == LD and comp.dtype == LD and (comp >= np.abs(T)).all()
+    Pd = np_ref.ekf_propagation(P, a, phi, c["old"], Phi, Q)
+    assert B.ratio(Pd, T, comp, B.prop_K(c)) <= 1.0
+    touched = np.zeros((n, n), dtype=bool)
+    touched[a:a + phi, :] = touched[:, a:a + phi] = True
+    assert np.array_equal(np.asarray(T, dtype=np.float64)[~touched], P[~touched])
+    # the independent definition: rows of F outside the block are the identity's; a repeated old column adds its Phi columns
+    Fb = np.zeros((phi, n), dtype=LD)
+    for k, col in enumerate(old):
+        Fb[:, col] += ld_ref.ld(Phi[:, k])
+    F = _embed(n, slice(a, a + phi), Fb)
+    Qe = np.zeros((n, n), dtype=LD)
+    Qe[a:a + phi, a:a + phi] = np.triu(ld_ref.ld(Q)) + np.triu(ld_ref.ld(Q), 1).T
+    T2 = F @ ld_ref.ld(P) @ F.T + Qe
+    assert np.abs(T2 - T).max() == 0 or (np.abs(T2 - T) <= 64 * np.finfo(LD).eps * (len(old) + 2) * comp).all()
+    T3, comp3 = ld_ref.ekf_propagation(np.abs(P), a, old, np.abs(Phi), np.abs(Q))
+    assert np.array_equal(T3, comp) and np.array_equal(comp3, comp)
+
+
+@pytest.mark.parametrize("c", B.augment_cases(), ids=lambda c: c["name"])
+def test_augment_dt_restatement_is_J_P_Jt(c):
+    P, d = B.augment_inputs(c)
+    n, p, t = c["n"], c["pose"], c["dt"]
+    T, comp = ld_ref.augment_dt(P, p, t, d)
+    J = np.eye(n, dtype=LD)
+    J[p:p + 6, t] += ld_ref.ld(d)
+    T2 = J @ ld_ref.ld(P) @ J.T
+    assert (np.abs(T2 - T) <= 64 * np.finfo(LD).eps * comp).all()
+    assert (np.abs(T - T.T) <= 64 * np.finfo(LD).eps * comp).all()  # symmetric in, symmetric out (to long-double rounding in the pose block)
+    untouched = np.ones((n, n), dtype=bool)
+    untouched[p:p + 6, :] = untouched[:, p:p + 6] = False
+    assert np.array_equal(np.asarray(T, dtype=np.float64)[untouched], P[untouched])
+    Ja = np.eye(n, dtype=LD)
+    Ja[p:p + 6, t] += np.abs(ld_ref.ld(d))
+    assert (np.abs(Ja @ np.abs(ld_ref.ld(P)) @ Ja.T - comp) <= 64 * np.finfo(LD).eps * comp).all()
+    with pytest.raises(AssertionError):
+        ld_ref.augment_dt(P, p, p + 2, d)
+
+
+@pytest.mark.parametrize("c", B.init_cases(), ids=lambda c: c["name"])
+def test_initialize_invertible_restatement_is_J_blkdiag_Jt(c):
+    """The new variable is x_L = H_L^-1 (r - H_R x - n): its error is -H_L^-1 (H_R dx + n), so the grown covariance is
+    J blkdiag(P, R) J^T with J = [[I, 0], [-H_L^-1 H_R (scattered), -H_L^-1]] and R the upper view."""
+    P, H_R, H_Linv, R = B.init_inputs(c)
+    n, k, cols = c["n"], c["k"], np.asarray(c["cols"])
+    T, comp = ld_ref.initialize_invertible(P, cols, H_R, H_Linv, R)
+    assert T.shape == (n + k, n + k) and (comp >= np.abs(T)).all()
+    Hs = np.zeros((k, n), dtype=LD)
+    Hs[:, cols] = ld_ref.ld(H_R)
+    Hi = ld_ref.ld(H_Linv)
+    J = np.zeros((n + k, n + k), dtype=LD)
+    J[:n, :n] = np.eye(n, dtype=LD)
+    J[n:, :n] = -Hi @ Hs
+    J[n:, n:] = -Hi
+    blk = np.zeros((n + k, n + k), dtype=LD)
+    blk[:n, :n] = ld_ref.ld(P)
+    blk[n:, n:] = np.triu(ld_ref.ld(R)) + np.triu(ld_ref.ld(R), 1).T
+    T2 = J @ blk @ J.T
+    assert (np.abs(T2 - T) <= 64 * np.finfo(LD).eps * (len(cols) + k) ** 2 * comp).all()
+    assert np.array_equal(np.asarray(T[:n, :n], dtype=np.float64), P)
+
+
+@pytest.mark.parametrize("k", [1, 3])
+def test_initialize_invertible_restatement_against_the_oracle(oracle, k):
+    """pyoracle.initialize(..., do_update=False) with as many rows as new columns is initialize_invertible behind a Givens rotation
+    of the rows, which the appended block does not depend on when R is isotropic."""
+    rng = np.random.default_rng(70 + k)
+    sc = make_scene(C=4, F=4, seed=71)
+    order = [(int(sc.ids["clones"][1]), 6), (int(sc.ids["calib"]), 6)]
+    cols = np_ref.order_cols(order)
+    H_R = rng.standard_normal((k, len(cols)))
+    H_L = rng.standard_normal((k, k)) + 2 * np.eye(k)
+    r_iso = 0.7
+    ref = oracle.initialize(sc.P, order, H_R, H_L, rng.standard_normal(k), r_iso, 1e9, do_update=False)
+    assert ref["P"].shape == (sc.N + k, sc.N + k)
+    T, comp = ld_ref.initialize_invertible(sc.P, cols, H_R, np.linalg.inv(H_L), r_iso * np.eye(k))
+    assert ld_ref.rel_p(ref["P"], T) < 1e-10
+
+
+def _all_cases():
+    for c in B.prop_cases():
+        yield "prop", c
+    for c in B.augment_cases():
+        yield "augment", c
+    for c in B.init_cases():
+        yield "init", c
+
+
+def _model_ratio(kind, c, **mut):
+    if kind == "prop":
+        P, Phi, Q = B.prop_inputs(c)
+        old = B.flat(c["old"])
+        T, comp = ld_ref.ekf_propagation(P, c["start"], old, Phi, Q)
+        return B.ratio(B.prop_model(P, c["start"], old, Phi, Q, **mut), T, comp, B.prop_K(c))
+    if kind == "augment":
+        P, d = B.augment_inputs(c)
+        T, comp = ld_ref.augment_dt(P, c["pose"], c["dt"], d)
+        return B.ratio(B.augment_model(P, c["pose"], c["dt"], d, **mut), T, comp, B.augment_K(c))
+    P, H_R, H_Linv, R = B.init_inputs(c)
+    T, comp = ld_ref.initialize_invertible(P, c["cols"], H_R, H_Linv, R)
+    return B.ratio(B.init_model(P, c["cols"], H_R, H_Linv, R, **mut), T, comp, B.init_K(c))
+
+
+@pytest.mark.parametrize("kind,c", list(_all_cases()), ids=lambda v: v if isinstance(v, str) else v["name"])
+def test_plain_float64_evaluation_stays_inside_the_bound(kind, c):
+    """the bound alone rejects nothing correct: numpy in double, whatever order its products sum in"""
+    r = _model_ratio(kind, c)
+    print("BOOKKEEPING-CPU %s/%s %.3f" % (kind, c["name"], r))
+    assert r <= 1.0
+
+
+def test_jitter_bound_holds_in_float64():
+    v = B.spd(40, 9).diagonal()
+    T, comp = B.jitter_truth(v, 1e-11)
+    assert B.ratio(v * (1.0 + 1e-11), T, comp, B.JITTER_K) <= 1.0
+    assert B.ratio(v, T, comp, B.JITTER_K) > 1e3  # (the jitter itself is far outside rounding)
+
+
+@pytest.mark.parametrize("kind,mut", [
+    ("prop", dict(q_lower=True)), ("init", dict(r_lower=True)), ("augment", dict(stale_row=True)), ("prop", dict(phi_transposed=True)),
+    ("prop", dict(skip=0)), ("init", dict(no_sign=True)), ("init", dict(hinv_plain=True))], ids=lambda v: v if isinstance(v, str) else next(iter(v)))
+def test_the_bound_catches_each_mutated_model(kind, mut):
+    """the lower triangle of Q or of R read, augment_dt's row step on the row dt from before the column step, Phi transposed, one
+    old column skipped, the cross block without its sign, H_Linv not transposed: each leaves the bound in at least one case"""
+    worst = 0.0
+    for kd, c in _all_cases():
+        if kd != kind or ("phi_transposed" in mut and c["phi"] != len(B.flat(c["old"]))):
+            continue
+        worst = max(worst, _model_ratio(kind, c, **mut))
+    print("mutation %s: worst error / bound %.3g" % (mut, worst))
+    assert worst > 1.0
