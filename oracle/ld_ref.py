@@ -16,6 +16,12 @@ feature), so it is the cross-check (tests/test_ld_ref_cpu.py), not the truth.
   update_from_pair_dropping                            the same on the pivot-dropping factor of A (the device's S-form retry)
   ekf_update_dense                                     StateHelper::EKFUpdate (S-form, R = I) on the columns `cols`
   ekf_propagation / augment_dt / initialize_invertible the covariance bookkeeping (StateHelper), each with its absolute companion
+  zupt_compressed / zupt_stacked                       the zero-velocity update: the compressed form ovp_zupt_update computes, and the
+                                                       reference's stacked 6 (n - 1)-row system through ekf_update_dense
+  plane_merge / plane_merge_steps                      StateHelper::merge_planes_and_marginalize's pairs in order, each through
+                                                       ekf_update_dense, with the quantities the rounding bounds of the tests need;
+                                                       the n x n companion of each accepted pair, replayed one at a time
+  eigvals_sym                                          eigenvalues of a small symmetric matrix (Jacobi), for kappa of S
   err_state / rel_p / err_chi2 / err_pair              the error metrics of tests/test_precision_gpu.py
 """
 from __future__ import annotations
@@ -276,6 +282,181 @@ def initialize_invertible(P, cols, H_R, H_Linv, R):
     assert H_R.shape[1] == len(cols) and H_Linv.shape == R.shape == (H_R.shape[0], H_R.shape[0])
     return (_initialize_invertible(P, cols, H_R, H_Linv, R, -1),
             _initialize_invertible(np.abs(P), cols, np.abs(H_R), np.abs(H_Linv), np.abs(R), 1))
+
+
+# ---- the zero-velocity update ----------------------------------------------------------------------------------------------
+# (update/UpdaterZeroVelocity.cpp:119-265; include/ovplane_hip.h has the algebra of the compressed form)
+def _zupt_cols(imu_id):
+    return int(imu_id) + np.array([0, 1, 2, 9, 10, 11, 12, 13, 14], dtype=np.int64)  # theta | b_g | b_a
+
+
+def _zupt_parts(sel, R, Rj, bg, ba, po, noise_mult):
+    """dt [ni], r [ni, 6] (the residual of an interval is that of its first reading), rho [ni, 6] (|.| of every operand of r), the
+    weights D [6], the per-second bias noise q [6] and H0 [6, 9]"""
+    sel = ld(sel)
+    g = np.array([0, 0, po["gravity_mag"]], dtype=LD)
+    Rg, Rjg = ld(R) @ g, ld(Rj) @ g
+    bg, ba = ld(bg), ld(ba)
+    dt = np.diff(sel[:, 0])
+    r = -np.concatenate([sel[:-1, 1:4] - bg, sel[:-1, 4:7] - ba - Rg], axis=1)
+    rho = np.concatenate([np.abs(sel[:-1, 1:4]) + np.abs(bg), np.abs(sel[:-1, 4:7]) + np.abs(ba) + np.abs(Rg)], axis=1)
+    m = LD(noise_mult)
+    D = np.concatenate([np.full(3, 1 / (m * LD(po["sigma_w"]) ** 2)), np.full(3, 1 / (m * LD(po["sigma_a"]) ** 2))])
+    q = np.concatenate([np.full(3, LD(po["sigma_wb"])), np.full(3, LD(po["sigma_ab"]))])  # sigmas, not squares (:184-186)
+    S3 = np.array([[0, -Rjg[2], Rjg[1]], [Rjg[2], 0, -Rjg[0]], [-Rjg[1], Rjg[0], 0]], dtype=LD)
+    H0 = np.zeros((6, 9), dtype=LD)
+    H0[0:3, 3:6] = -np.eye(3, dtype=LD)
+    H0[3:6, 0:3] = -S3
+    H0[3:6, 6:9] = -np.eye(3, dtype=LD)
+    return dt, r, rho, D, q, H0
+
+
+def eigvals_sym(S):
+    """The eigenvalues of a small symmetric matrix in long double, ascending, by cyclic Jacobi rotations (numpy's eigvalsh has no
+    long-double path)."""
+    A = np.array(S, dtype=LD, copy=True)
+    n = A.shape[0]
+    for _ in range(60):
+        off = np.sqrt(((A - np.diag(np.diag(A))) ** 2).sum())
+        if off <= np.finfo(LD).eps * np.abs(np.diag(A)).max():
+            break
+        for p in range(n - 1):
+            for q in range(p + 1, n):
+                if A[p, q] == 0:
+                    continue
+                theta = (A[q, q] - A[p, p]) / (2 * A[p, q])
+                t = (1 if theta >= 0 else -1) / (np.abs(theta) + np.sqrt(theta * theta + 1))
+                c = 1 / np.sqrt(t * t + 1)
+                J = np.eye(n, dtype=LD)
+                J[p, p] = J[q, q] = c
+                J[p, q], J[q, p] = t * c, -t * c
+                A = sym(J.T @ A @ J)
+    return np.sort(np.diag(A))
+
+
+def _cond2(S):
+    """(2-norm condition number, smallest eigenvalue, largest) of a small SPD matrix: computed in long double (eigvals_sym), then
+    rounded to double"""
+    w = eigvals_sym(S)
+    return float(w[-1] / w[0]), float(w[0]), float(w[-1])
+
+
+def zupt_compressed(P, sel, imu_id, R, Rj, bg, ba, po, noise_mult):
+    """The algebra of tests/zupt_ref.py::compressed: T = sum dt_i, rbar = sum dt_i r_i / T, the scatter about rbar, P' = P + Q_bias
+    on the bias diagonal, Sbar = H0 P'_ss H0^T + (T D)^-1 = L L^T, z = L^-1 rbar, chi2 = scatter + |z|^2, Y = P'_{:,s} H0^T L^-T,
+    dx = Y z, P+ = P' - Y Y^T.  No inverse is formed: Y comes from a triangular solve.  Returns (truth, companion):
+      truth      dict(chi2, rows, dx, P, kappa, ...) with kappa the 2-norm condition number of Sbar rounded to double, and the
+                 intermediate values the derivation of a bound refers to: T, rbar, scatter, z, Y, Pp (= P'), Sbar, lam_min, lam_max, Tq (= diag Q_bias)
+      companion  dict(P = |P'| + |Y| |Y|^T element by element; rbar = sum dt_i rho_i / T with rho_i the |.| of the operands of r_i;
+                 scatter_lin = sum dt_i D |r_i - rbar| (rho_i + rbar's), scatter_sq = sum dt_i D (rho_i + rbar's)^2: what an error
+                 of r_i - rbar is multiplied by; Sbar = |H0| |P'_ss| |H0|^T + (T D)^-1; SbarT = its part that is a multiple of the summed
+                 T: (T D)^-1 + |H0| Q_bias |H0|^T; M = |P'_{:,s}| |H0|^T [n, 6]; z = |L^-1| rbar's companion [6], which is what z is
+                 conditioned by when rbar is a small difference of readings and gravity: L^-1 here is a companion only, no truth
+                 value passes through it)"""
+    P = ld(P)
+    dt, r, rho, D, q, H0 = _zupt_parts(sel, R, Rj, bg, ba, po, noise_mult)
+    T = dt.sum()
+    rbar = (dt[:, None] * r).sum(axis=0) / T
+    rhobar = (dt[:, None] * rho).sum(axis=0) / T
+    e = r - rbar
+    scatter = (dt[:, None] * e * e * D).sum()
+    s = _zupt_cols(imu_id)
+    Pp = P.copy()
+    Pp[s[3:], s[3:]] += T * q
+    Rbar = np.diag(1 / (T * D))
+    Sbar = sym(H0 @ Pp[np.ix_(s, s)] @ H0.T + Rbar)
+    L = chol(Sbar)
+    z = solve_lower(L, rbar)
+    M = Pp[:, s] @ H0.T                     # [n, 6]
+    Y = solve_lower(L, M.T).T               # M L^-T
+    kappa, lam_min, lam_max = _cond2(Sbar)
+    truth = dict(chi2=scatter + z @ z, rows=6 * len(dt), dx=Y @ z, P=sym(Pp - Y @ Y.T), kappa=kappa, T=T, rbar=rbar, scatter=scatter,
+                 z=z, Y=Y, Pp=Pp, Sbar=Sbar, lam_min=lam_min, lam_max=lam_max, Tq=T * q)
+    w = rho + rhobar
+    comp = dict(P=np.abs(Pp) + np.abs(Y) @ np.abs(Y).T, rbar=rhobar, scatter_lin=(dt[:, None] * D * np.abs(e) * w).sum(),
+                scatter_sq=(dt[:, None] * D * w * w).sum(), Sbar=np.abs(H0) @ np.abs(Pp[np.ix_(s, s)]) @ np.abs(H0).T + Rbar,
+                M=np.abs(Pp[:, s]) @ np.abs(H0).T, z=np.abs(solve_lower(L, np.eye(6, dtype=LD))) @ rhobar, SbarT=Rbar + np.abs(H0[:, 3:]) @ np.diag(T * q) @ np.abs(H0[:, 3:]).T)
+    return truth, comp
+
+
+def zupt_stacked(P, sel, imu_id, R, Rj, bg, ba, po, noise_mult):
+    """The reference's own system: 6 rows per interval, H = H0 over [theta, b_g, b_a], noise noise_mult sigma^2 / dt_i, whitened
+    row by row with sqrt(dt_i D) so that R = I, on P + Q_bias, through ekf_update_dense; chi2 = res^T S^-1 res of the whitened
+    rows.  Returns dict(chi2, rows, dx, P)."""
+    P = ld(P)
+    dt, r, _, D, q, H0 = _zupt_parts(sel, R, Rj, bg, ba, po, noise_mult)
+    s = _zupt_cols(imu_id)
+    Pp = P.copy()
+    Pp[s[3:], s[3:]] += dt.sum() * q
+    w = np.sqrt(dt[:, None] * D[None, :])                  # [ni, 6]
+    H = (w[:, :, None] * H0[None, :, :]).reshape(-1, 9)
+    res = (w * r).reshape(-1)
+    Pn, dx = ekf_update_dense(Pp, s, H, res)
+    S = sym(H @ Pp[np.ix_(s, s)] @ H.T + np.eye(H.shape[0], dtype=LD))
+    y = solve_lower(chol(S), res)
+    return dict(chi2=y @ y, rows=H.shape[0], dx=dx, P=Pn)
+
+
+# ---- the plane merge -------------------------------------------------------------------------------------------------------
+def plane_merge(P, pairs, plane_col, cp, sigma, chi2_mult, deg_max, chi2_095_3=7.814727903251179):
+    """StateHelper::merge_planes_and_marginalize's pairs (state/StateHelper.cpp:693-734), in order: for the pair (new, old) the
+    angle of the two closest points' directions, H = [I, -I] / sigma over [new..new+3, old..old+3], res = (0 - (cp_new - cp_old)) /
+    sigma, chi2 = res^T S^-1 res, the decision chi2 < chi2_mult chi2_095(3) and angle < deg_max, and on acceptance
+    ekf_update_dense on the P the pair before left and cp += dx for every plane of the table.  Returns (truth, companion):
+      truth      dict(accepted [np], chi2, angle_deg, dot, dx [np, n], P (un-compacted), cp (as the last pair left them), and per
+                 pair the small values a bound refers to: S, kappa, lam_min, lam_max, y (= L^-1 res), res, cp_new, cp_old, and
+                 W (= M L^-T [n, 3]; None for a rejected pair))
+      companion  per pair dict(M = (|P_in[:, new]| + |P_in[:, old]|) / sigma [n, 3], S = (|P_nn| + |P_no| + |P_on| + |P_oo|) /
+                 sigma^2 + I), P_in the P the pair read.  The n x n companion |P_in| + |W| |W|^T of an accepted pair is not kept per
+                 pair (64 pairs at n = 399 would hold 160 MB): plane_merge_steps replays P_in and yields it pair by pair."""
+    P = ld(P).copy()
+    n = P.shape[0]
+    wc = 1 / LD(sigma)
+    thr = LD(chi2_mult) * LD(chi2_095_3)
+    cur = {int(c): ld(v).copy() for c, v in zip(plane_col, np.reshape(np.asarray(cp, dtype=np.float64), (-1, 3)))}
+    H = np.hstack([wc * np.eye(3, dtype=LD), -wc * np.eye(3, dtype=LD)])
+    keys = ("accepted", "chi2", "angle_deg", "dot", "S", "kappa", "lam_min", "lam_max", "y", "res", "W", "cp_new", "cp_old", "dx")
+    t = {k: [] for k in keys}
+    comps = []
+    for cn, co in pairs:
+        cn, co = int(cn), int(co)
+        c1, c0 = cur[cn], cur[co]
+        dot = (c1 / np.sqrt(c1 @ c1)) @ (c0 / np.sqrt(c0 @ c0))
+        with np.errstate(invalid="ignore"):
+            angle = (LD(180) / np.arccos(LD(-1))) * np.arccos(dot)  # (a dot product rounded above 1 is NaN here as in :701, and a rejection)
+        idx = np.r_[cn:cn + 3, co:co + 3]
+        res = wc * (0 - (c1 - c0))
+        S = sym(H @ P[np.ix_(idx, idx)] @ H.T + np.eye(3, dtype=LD))
+        L = chol(S)
+        y = solve_lower(L, res)
+        chi2 = y @ y
+        ok = bool(chi2 < thr and angle < LD(deg_max))
+        kappa, lam_min, lam_max = _cond2(S)
+        An, Ao = np.abs(P[:, cn:cn + 3]), np.abs(P[:, co:co + 3])
+        comps.append(dict(M=wc * (An + Ao), S=wc * wc * (An[cn:cn + 3] + Ao[cn:cn + 3] + An[co:co + 3] + Ao[co:co + 3]) + np.eye(3, dtype=LD)))
+        W, dx = None, np.zeros(n, dtype=LD)
+        if ok:
+            W = solve_lower(L, (P[:, idx] @ H.T).T).T
+            P, dx = ekf_update_dense(P, idx, H, res)
+            for c in cur:
+                cur[c] = cur[c] + dx[c:c + 3]
+        for k, v in zip(keys, (ok, chi2, angle, dot, S, kappa, lam_min, lam_max, y, res, W, c1.copy(), c0.copy(), dx)):
+            t[k].append(v)
+    truth = dict(t, accepted=np.array(t["accepted"], dtype=bool), chi2=np.array(t["chi2"], dtype=LD), angle_deg=np.array(t["angle_deg"], dtype=LD),
+                 dx=np.array(t["dx"], dtype=LD).reshape(-1, n), P=P, cp=cur, chi2_thr=thr)
+    return truth, comps
+
+
+def plane_merge_steps(P, truth):
+    """For every accepted pair k of a plane_merge truth on P, in order: (k, P_in, |P_in| + |W| |W|^T), P_in the covariance the pair
+    read and the second the companion of its step.  P_in is replayed as sym(P_in - W W^T), the expression ekf_update_dense
+    evaluates (bit for bit: the last one equals truth["P"])."""
+    P = ld(P).copy()
+    for k, W in enumerate(truth["W"]):
+        if W is None:
+            continue
+        yield k, P, np.abs(P) + np.abs(W) @ np.abs(W).T
+        P = sym(P - W @ W.T)
 
 
 # ---- error metrics ---------------------------------------------------------------------------------------------------------

@@ -314,3 +314,193 @@ def test_the_bound_catches_each_mutated_model(kind, mut):
         worst = max(worst, _model_ratio(kind, c, **mut))
     print("mutation %s: worst error / bound %.3g" % (mut, worst))
     assert worst > 1.0
+
+
+# ---- the zero-velocity update and the plane merge: the truths of tests/test_zupt_precision_gpu.py and tests/test_retire_precision_gpu.py,
+# ---- their bounds, and the faulty models the bounds catch ----
+import retire_cases as RC  # noqa: E402
+import retire_ref as RR  # noqa: E402
+import zupt_cases as ZC  # noqa: E402
+import zupt_ref as ZR  # noqa: E402
+
+EPS_LD = float(np.finfo(LD).eps)
+
+
+def _zupt_args(c):
+    P, rd, kw = ZC.inputs(c)
+    x = ZC.imu_state()
+    return (P, rd, c["imu_id"], x["R"], x["Rj"], x["bg"], x["ba"], ZR.PO, ZR.NOISE_MULT), kw
+
+
+def _ld_ratio(got, truth, comp, K):
+    """cov_bookkeeping_cases.ratio with the long-double unit roundoff 2^-64 in place of u: max |got - truth| / (K 2^-64 comp)"""
+    err = np.abs(got - truth)
+    bound = K * LD(EPS_LD / 2) * comp
+    r = np.where(err == 0, 0.0, err / np.where(bound > 0, bound, 1))
+    return float(np.max(np.where((bound == 0) & (err > 0), np.inf, r)))
+
+
+@pytest.mark.parametrize("c", [c for c in ZC.cases() if c["readings"] <= 258], ids=lambda c: c["name"])
+def test_zupt_compressed_equals_the_stacked_system_in_long_double(c):
+    """zupt_compressed == zupt_stacked (the reference's own 6 (n - 1)-row system, whitened, through ekf_update_dense) at long-double
+    level, element by element on the companions of the compressed form, with the metric of cov_bookkeeping_cases.ratio at the
+    long-double unit roundoff 2^-64 and K = 2 (ni + 6) roundings, no condition number: 7.6e-19 relative for two readings, 2.9e-17
+    for 258.  The counts: each formulation sums ni terms per element and solves with 6 (or 6 ni, banded by construction) unknowns,
+    hence ni + 6 each.  chi2: relative to itself.  P: against comp.P = |P'| + |Y| |Y|^T.  dx = Y z: against |Y| comp.z with
+    comp.z = |L^-1| rhobar, not |Y| |z|: standing, rbar is what is left of readings and gravity that cancel to 1e-4 of their size,
+    and z inherits the rounding of the operands (rhobar), in either formulation.
+    The stacked system of 4096 readings has 24570 rows and is too large to factor here: at 4096 the compressed truth stands
+    alone, held up by the 257 / 258-reading cases (the same code, the same strides) and by the double restatement below."""
+    args, _ = _zupt_args(c)
+    t, comp = ld_ref.zupt_compressed(*args)
+    s = ld_ref.zupt_stacked(*args)
+    ni = c["readings"] - 1
+    K = 2 * (ni + 6)
+    assert s["rows"] == t["rows"] == 6 * ni
+    r = [_ld_ratio(s["chi2"], t["chi2"], t["chi2"], K), _ld_ratio(s["dx"], t["dx"], np.abs(t["Y"]) @ comp["z"], K),
+         _ld_ratio(s["P"], t["P"], comp["P"], K)]
+    print("ZUPT-LD %s: chi2 %.3f dx %.3f P %.3f of %d x 2^-64" % (c["name"], r[0], r[1], r[2], K))
+    assert max(r) <= 1.0
+    assert (comp["P"] >= np.abs(t["P"])).all() and t["P"].dtype == LD
+    assert (np.abs(t["Y"]) @ comp["z"] >= np.abs(t["Y"]) @ np.abs(t["z"])).all()
+
+
+@pytest.mark.parametrize("c", ZC.cases(), ids=lambda c: c["name"])
+def test_zupt_cases_have_their_margin_and_the_double_restatements_stay_inside_the_bound(oracle, c):
+    """Every gated case: the truth's chi2 outside thr (1 -+ 1e-9), the decision the case is named after.  Then zupt_ref.compressed,
+    the model of zupt_cases.py without a fault and - up to 258 readings, where its stacked system is small enough - the C oracle's
+    zupt_update through the derived bounds: ratio <= 1."""
+    args, kw = _zupt_args(c)
+    t, _, _ = ZC.truth(c)
+    thr = ZC.threshold(c)
+    assert abs(float(t["chi2"]) / thr - 1.0) > ZC.MARGIN
+    acc = ZC.decision(c, float(t["chi2"]))
+    assert acc == ZC.expected(c)
+    assert (float(t["chi2"]) <= thr) == (c["kind"] in ("accept", "reject_vel"))
+    ref = ZR.compressed(*args[:-1])
+    m = ZC.model(c)
+    assert ref["spd"] and m["accepted"] == acc
+    for what, got in (("restatement", ref), ("model", m)):
+        r = ZC.ratios(c, got["chi2"], got["dx"] if acc else None, got["P"] if acc else None)
+        print("ZUPT-CPU %s %s %s" % (c["name"], what, " ".join("%.4f" % v for v in r)))
+        assert max(r) <= 1.0
+    # the C oracle selects its own readings: a stream with one more reading on either side gives the case's readings back
+    # unchanged for their own first and last time stamp; its stacked system has 6 (n - 1) rows, so the 4096-reading cases stay out
+    P, rd = args[0], args[1]
+    if c["readings"] <= 258:
+        pre, post = rd[:1].copy(), rd[-1:].copy()
+        pre[0, 0] -= 2.5e-3
+        post[0, 0] += 2.5e-3
+        stream = np.vstack([pre, rd, post])
+        assert np.array_equal(oracle.select_imu_readings(stream, rd[0, 0], rd[-1, 0]), rd)
+        x = ZR.scenario(True)[0]
+        if not kw["vel_ok"]:  # the oracle takes the velocity estimate and the limit, not the flag: an estimate over the limit
+            x = dict(x, v=np.array([0.0, 0.0, 2 * ZR.MAX_VELOCITY]))
+        o = oracle.zupt_update(x, ZR.PO, P, stream, rd[0, 0], rd[-1, 0], imu_id=c["imu_id"], disparity_passed=kw["disparity_passed"])
+        assert o["accepted"] == acc and o["rows"] == t["rows"]
+        r = ZC.ratios(c, o["chi2"], o["dx"] if acc else None, o["P"] if acc else None)
+        print("ZUPT-CPU %s oracle %s" % (c["name"], " ".join("%.4f" % v for v in r)))
+        assert max(r) <= 1.0
+
+
+@pytest.mark.parametrize("fault", ZC.FAULTS)
+def test_the_zupt_bound_catches_each_faulty_model(fault):
+    """one fault each (zupt_cases.model): at least one case leaves the bound or flips its decision"""
+    worst, flipped = 0.0, False
+    for c in ZC.cases():
+        t, _, _ = ZC.truth(c)
+        acc = ZC.decision(c, float(t["chi2"]))
+        m = ZC.model(c, fault)
+        if m["accepted"] != acc:
+            flipped = True
+            continue
+        worst = max(worst, max(ZC.ratios(c, m["chi2"], m["dx"] if acc else None, m["P"] if acc else None)))
+    print("zupt fault %s: worst error / bound %.3g, decision flipped %s" % (fault, worst, flipped))
+    assert worst > 1.0 or flipped
+
+
+WELL_CONDITIONED = ["n63_behind_first_last", "n65_across64", "n129_chain_chi2", "n257_to_254"]
+
+
+@pytest.mark.parametrize("name", WELL_CONDITIONED)
+def test_plane_merge_equals_the_information_form(name):
+    """every accepted pair of plane_merge against update_from_pair_info on A = H^T H, b = H^T res scattered into the state: the same
+    update without S.  The covariances of these cases have a condition number of ~1e17 over their eight decades of scales, so the
+    comparison runs on the correlation-scaled problem (D P D, D^-1 H: the same update, exactly, with D a diagonal of powers of two)."""
+    c = RC.case(name)
+    t, _, _ = RC.truth(name)
+    n = c["n"]
+    wc = 1 / LD(c["sigma"])
+    steps = list(ld_ref.plane_merge_steps(c["P"], t))
+    assert len(steps) == int(t["accepted"].sum())
+    for j, (k, Pin, comp_P) in enumerate(steps):
+        cn, co = c["pairs"][k]
+        d = 2.0 ** -np.round(np.log2(np.sqrt(np.asarray(np.diag(Pin), dtype=np.float64))))
+        D = ld_ref.ld(d)
+        H = np.zeros((3, n), dtype=LD)
+        H[:, cn:cn + 3] = wc * np.eye(3, dtype=LD)
+        H[:, co:co + 3] = -wc * np.eye(3, dtype=LD)
+        Hs = H / D[None, :]
+        Pi, dxi = ld_ref.update_from_pair_info(Pin * np.outer(D, D), Hs.T @ Hs, Hs.T @ t["res"][k])
+        Pn = steps[j + 1][1] if j + 1 < len(steps) else t["P"]
+        if j + 1 == len(steps):  # the replay is ekf_update_dense's own expression: the last step lands on the truth's P, bit for bit
+            assert np.array_equal(ld_ref.sym(Pin - t["W"][k] @ t["W"][k].T), t["P"])
+        assert (comp_P >= np.abs(Pn)).all()
+        e_P = ld_ref.rel_p(Pi / np.outer(D, D), Pn)
+        e_dx = ld_ref.err_state(dxi / D, t["dx"][k], Pn)
+        print("MERGE-LD %s pair %d: P %.1e dx %.1e" % (name, k, e_P, e_dx))
+        assert e_P < 1e-15 and e_dx < 1e-14
+
+
+@pytest.mark.parametrize("name", RC.names())
+def test_merge_cases_have_their_margins_and_the_double_restatements_stay_inside_the_bound(name):
+    """chi2 outside thr (1 -+ 1e-9) and the angle outside deg_max (1 -+ 1e-9) for every pair, the decisions the case is built for,
+    the first-order angle bound in its range (delta << 1 - dot), the exactly parallel pair at dot = 1 and 0.0 degrees; then
+    retire_ref.merge_ref and the model of retire_cases.py without a fault through the derived bounds: ratio <= 1."""
+    c = RC.case(name)
+    t, _, b = RC.truth(name)
+    thr = float(t["chi2_thr"])
+    assert t["accepted"].tolist() == RC.expected(c)
+    for k, kind in enumerate(c["kinds"]):
+        assert abs(float(t["chi2"][k]) / thr - 1.0) > RC.MARGIN and abs(float(t["angle_deg"][k]) / c["deg_max"] - 1.0) > RC.MARGIN
+        assert (float(t["chi2"][k]) < thr) == (kind != "chi2") and (float(t["angle_deg"][k]) < c["deg_max"]) == (kind != "angle")
+        if kind == "parallel":
+            assert t["dot"][k] == 1 and t["angle_deg"][k] == 0 and b["angle"][k] == 0
+        else:
+            assert float(b["angle"][k]) * RC.U * np.pi / 180 * np.sqrt(float(1 - t["dot"][k] ** 2)) < 1e-3 * float(1 - t["dot"][k])
+        if kind == "near":
+            assert 0.5e-3 < float(t["angle_deg"][k]) < 2e-3
+    ref = RR.merge_ref(c["P"], c["pairs"], c["plane_col"], c["cp"], c["sigma"], c["chi2_mult"], c["deg_max"], c["retire_ids"], c["retire_sizes"])
+    m = RC.model(name)
+    for what, got in (("restatement", ref), ("model", m)):
+        assert got["accepted"].tolist() == t["accepted"].tolist()
+        r = RC.ratios(name, got["chi2"], got["angle_deg"], got["dx"], got["P"])
+        print("RETIRE-CPU %s %s %s" % (name, what, " ".join("%.4f" % v for v in r)))
+        assert max(r) <= 1.0
+
+
+@pytest.mark.parametrize("fault", RC.FAULTS)
+def test_the_merge_bound_catches_each_faulty_model(fault):
+    worst, flipped = 0.0, False
+    for name in RC.names():
+        t, _, _ = RC.truth(name)
+        m = RC.model(name, fault)
+        if m["accepted"].tolist() != t["accepted"].tolist():
+            flipped = True
+            continue
+        worst = max(worst, max(RC.ratios(name, m["chi2"], m["angle_deg"], m["dx"], m["P"])))
+    print("merge fault %s: worst error / bound %.3g, decision flipped %s" % (fault, worst, flipped))
+    assert worst > 1.0 or flipped
+
+
+def test_a_compaction_map_that_restarts_at_column_256_is_caught():
+    """compact_model == compact_ref on every compaction case; with the restart it differs wherever n_out > 256 and something was
+    removed in front of output column 256"""
+    caught = 0
+    for name, (n, ids, sizes) in RC.compact_cases().items():
+        P = B.spd(n, 60 + n + len(ids))
+        want = RR.compact_ref(P, ids, sizes)
+        assert want.shape[0] == n - sum(sizes)
+        assert np.array_equal(RC.compact_model(P, ids, sizes), want), name
+        caught += not np.array_equal(RC.compact_model(P, ids, sizes, restart=True), want)
+    assert caught >= 5
