@@ -605,6 +605,51 @@ typedef struct {
 } ovp_zupt_out;
 int ovp_zupt_update(ovp_ctx *ctx, const ovp_zupt_in *in, double *dx_host, ovp_zupt_out *out, ovp_update_info *info);
 
+/* Propagator::propagate_and_clone behind its preamble (state/Propagator.cpp:37-126), from the selected IMU readings to the
+ * augmented clone, in one device pass: one upload (readings, IMU state and scalars in one staged block), one enqueue, one wait.
+ * It replaces the host integration of the window (:84-102, predict_and_compute :343-454 with predict_mean_discrete / _rk4),
+ * StateHelper::EKFPropagation (state/StateHelper.cpp:41-119) on the IMU's 15 columns and StateHelper::augment_clone (:588-625).
+ * The caller keeps the two fatal checks, the time offsets and Propagator::select_imu_readings (:39-82) and, behind the call, sets
+ * the IMU's value and first estimate from `out`, the timestamp, and registers the clone at out->clone_id.
+ * The reference's sequence, nothing reordered.  Per interval of the n_readings - 1: the mean (discrete, honouring imu_avg and the
+ * small-angle branch of the quaternion integrator, or RK4), F in its FEJ form (the first estimates are the inputs' for the first
+ * interval and the propagated mean afterwards, :447-453) or its plain form, Qd = G Qc G^T symmetrised; Phi <- F Phi,
+ * Q <- 1/2 ((F Q F^T + Qd) + (.)^T).  last_w is the second-to-last reading minus b_g, the only reading minus b_g, or zero (:108-114).
+ * Then EKFPropagation with Phi, Q; with `clone` an exact copy of the pose block [imu_id, imu_id + 6) appended at the end
+ * (ovp_cov_clone_jitter honoured as ovp_cov_clone does); with dt_id >= 0 the time-offset term of ovp_cov_augment_dt on the new
+ * block with dnc_dt = [last_w ; v propagated].  Phi, Q and dnc_dt stay on the device between the kernels; the wait brings back
+ * [mean | last_w | Phi | Q | verdict] through a mailbox.  Fixed order, no atomics: two calls on the same input return the same bits;
+ * Q and the covariance are symmetric to the bit.  n_readings of 0 or 1 is legal: Phi = I, Q = 0, the mean unchanged.
+ * Drops a kept factor, as everything that writes the covariance; does not touch the device pose tables (the caller uploads its
+ * tables before the next update).
+ * Refused on the host before anything is enqueued, the covariance, its size and a kept factor bit for bit as before: a NULL
+ * argument, imu_id < 0 or imu_id + 15 > n, dt_id inside the IMU block or >= n (or < -1), a non-increasing time stamp -> OVP_E_ARG;
+ * n_readings > OVP_PROP_MAX_READINGS, or clone and n + 6 > n_state_max -> OVP_E_CAPACITY; no covariance -> OVP_E_STATE.  A negative
+ * diagonal is OVP_E_NEGDIAG behind the wait with the call carried out (clone included, size grown) and `out` filled, as
+ * ovp_cov_propagate reports it. */
+#define OVP_PROP_MAX_READINGS 4096
+typedef struct {
+  int n_readings;          /* what Propagator::select_imu_readings returned; 0 and 1 are legal (Phi = I, Q = 0) */
+  const double *readings;  /* [n_readings][7] (t, w_m xyz, a_m xyz), the layout of ovp_zupt_in::readings */
+  int imu_id;              /* Type::id() of the IMU, error order th p v bg ba */
+  double q[4], p[3], v[3], bg[3], ba[3];   /* State::_imu value (JPL q_GtoI) */
+  double q_fej[4], p_fej[3], v_fej[3];     /* first estimates (read with do_fej) */
+  double gravity_mag;
+  double sigma_w, sigma_a, sigma_wb, sigma_ab;  /* continuous-time densities (NoiseManager) */
+  int use_rk4, imu_avg, do_fej;
+  int clone;               /* 1: StateHelper::augment_clone behind the propagation; 0: propagation only */
+  int dt_id;               /* Type::id() of calib_dt_CAMtoIMU, -1 = not estimated (no rank-one term) */
+  int time_kernels;        /* diagnostics as in ovp_zupt_in */
+} ovp_propagate_in;
+typedef struct {
+  double q[4], p[3], v[3]; /* propagated mean (value and first estimate both become it, Propagator.cpp:447-453) */
+  double last_w[3];        /* :108-114 */
+  int n_intervals, clone_id /* id of the appended pose, -1 without clone */, neg_diag;
+  double Phi[225], Q[225]; /* Phi_summed / Qd_summed, column-major 15 x 15, for the tests and the trace */
+  float kernel_ms[4];      /* with time_kernels: integration, EKFPropagation, clone + time offset, publish; else 0 */
+} ovp_propagate_out;
+int ovp_propagate_and_clone(ovp_ctx *ctx, const ovp_propagate_in *in, ovp_propagate_out *out);
+
 /* StateHelper::augment_clone, time-offset part (state/StateHelper.cpp:613-624):
  *   Cov[:, pose..pose+5] += Cov[:, dt] * dnc_dt^T ;  Cov[pose..pose+5, :] += dnc_dt * Cov[dt, :]   (in that order)
  * OVP_E_ARG when the pose block or dt_id leaves the state, or dt_id lies inside the pose block. */

@@ -235,6 +235,25 @@ class ZuptOut(C.Structure):
     _fields_ = [("accepted", C.c_int), ("rows", C.c_int), ("chi2", C.c_double), ("kernel_ms", C.c_float * 3)]
 
 
+OVP_PROP_MAX_READINGS = 4096
+
+
+class PropagateIn(C.Structure):
+    """ovp_propagate_in"""
+    _fields_ = [("n_readings", C.c_int), ("readings", C.c_void_p), ("imu_id", C.c_int), ("q", C.c_double * 4), ("p", C.c_double * 3),
+                ("v", C.c_double * 3), ("bg", C.c_double * 3), ("ba", C.c_double * 3), ("q_fej", C.c_double * 4),
+                ("p_fej", C.c_double * 3), ("v_fej", C.c_double * 3), ("gravity_mag", C.c_double), ("sigma_w", C.c_double),
+                ("sigma_a", C.c_double), ("sigma_wb", C.c_double), ("sigma_ab", C.c_double), ("use_rk4", C.c_int),
+                ("imu_avg", C.c_int), ("do_fej", C.c_int), ("clone", C.c_int), ("dt_id", C.c_int), ("time_kernels", C.c_int)]
+
+
+class PropagateOut(C.Structure):
+    """ovp_propagate_out"""
+    _fields_ = [("q", C.c_double * 4), ("p", C.c_double * 3), ("v", C.c_double * 3), ("last_w", C.c_double * 3),
+                ("n_intervals", C.c_int), ("clone_id", C.c_int), ("neg_diag", C.c_int), ("Phi", C.c_double * 225),
+                ("Q", C.c_double * 225), ("kernel_ms", C.c_float * 4)]
+
+
 EXPORTS = [
     "ovp_ctx_create", "ovp_ctx_destroy", "ovp_sync", "ovp_version", "ovp_error_string", "ovp_cov_upload",
     "ovp_cov_download", "ovp_cov_set_device", "ovp_cov_marginal", "ovp_state_upload", "ovp_batch_upload",
@@ -254,6 +273,7 @@ EXPORTS = [
     "ovp_active_tracks_create", "ovp_active_tracks_destroy", "ovp_active_tracks_reset", "ovp_active_tracks_update",
     "ovp_active_tracks_debug",
     "ovp_cov_marginalize_many", "ovp_planes_merge_retire", "ovp_zupt_update",
+    "ovp_propagate_and_clone",
 ]
 
 
@@ -334,6 +354,7 @@ def lib():
         L.ovp_planes_merge_retire.argtypes = [C.c_void_p, C.POINTER(PlaneMergeIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_int]
         L.ovp_zupt_update.argtypes = [C.c_void_p, C.POINTER(ZuptIn), C.c_void_p, C.POINTER(ZuptOut), C.POINTER(UpdateInfo)]
+        L.ovp_propagate_and_clone.argtypes = [C.c_void_p, C.POINTER(PropagateIn), C.POINTER(PropagateOut)]
         L.ovp_cov_size.argtypes = [C.c_void_p]
         L.ovp_cov_augment_dt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.ovp_cov_initialize_invertible.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -829,6 +850,30 @@ class Context:
             raise OvpError(rc, "ovp_zupt_update")
         return dict(accepted=bool(o.accepted), chi2=o.chi2, rows=o.rows, dx=dx[:self.cov_size()], neg_diag=rc == OVP_E_NEGDIAG,
                     kernel_ms=np.array(o.kernel_ms[:]), info=info)
+
+    def propagate_and_clone(self, readings, imu_id, x, po, clone=True, dt_id=-1, time_kernels=False):
+        """Propagator::propagate_and_clone behind its preamble in one device pass (ovp_propagate_and_clone).  readings [n, 7] =
+        what Propagator::select_imu_readings returned (n = 0 and 1 are legal); x: dict with q, p, v, bg, ba, q_fej, p_fej, v_fej
+        (JPL q_GtoI); po: dict with sigma_w, sigma_a, sigma_wb, sigma_ab, gravity_mag, use_rk4, imu_avg, do_fej.  Returns
+        dict(q, p, v, last_w, Phi [15, 15], Q [15, 15], n_intervals, clone_id, neg_diag, kernel_ms [4])."""
+        f64 = lambda a, *sh: np.ascontiguousarray(a, dtype=np.float64).reshape(*sh)  # noqa: E731
+        rd = f64(readings, -1, 7)
+        z = PropagateIn()
+        z.n_readings, z.readings, z.imu_id = len(rd), (rd.ctypes.data if len(rd) else None), int(imu_id)
+        for k, m in (("q", 4), ("p", 3), ("v", 3), ("bg", 3), ("ba", 3), ("q_fej", 4), ("p_fej", 3), ("v_fej", 3)):
+            getattr(z, k)[:] = list(f64(x[k], m))
+        z.gravity_mag = float(po["gravity_mag"])
+        z.sigma_w, z.sigma_a, z.sigma_wb, z.sigma_ab = (float(po[k]) for k in ("sigma_w", "sigma_a", "sigma_wb", "sigma_ab"))
+        z.use_rk4, z.imu_avg, z.do_fej = (int(bool(po[k])) for k in ("use_rk4", "imu_avg", "do_fej"))
+        z.clone, z.dt_id, z.time_kernels = int(bool(clone)), int(dt_id), int(bool(time_kernels))
+        o = PropagateOut()
+        rc = lib().ovp_propagate_and_clone(self._h, C.byref(z), C.byref(o))
+        if rc not in (0, OVP_E_NEGDIAG):
+            raise OvpError(rc, "ovp_propagate_and_clone")
+        return dict(q=np.array(o.q[:]), p=np.array(o.p[:]), v=np.array(o.v[:]), last_w=np.array(o.last_w[:]),
+                    Phi=np.array(o.Phi[:]).reshape(15, 15).T.copy(), Q=np.array(o.Q[:]).reshape(15, 15).T.copy(),
+                    n_intervals=o.n_intervals, clone_id=o.clone_id, neg_diag=rc == OVP_E_NEGDIAG,
+                    kernel_ms=np.array(o.kernel_ms[:]))
 
     # -- state / batch ---------------------------------------------------------------------------
     def state_upload(self, sc, state=None):

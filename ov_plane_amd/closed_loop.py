@@ -169,7 +169,7 @@ def run(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, max_feats=
 def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, planes=0, plane_min_feat=6, sigma_c=0.01,
                 max_slam=0, feat_rep_slam=0, min_meas=3, out_dir=None, zupt=None, track_planes=True, forget_planes_at=None,
                 detect_planes=False, detect_opts=None, feed_plane_tracks=None, device_delaunay=False, active_tracks=False,
-                active_tracks_skip=(), batched_retire=False, split_planes_until=None, gpu_zupt=False):
+                active_tracks_skip=(), batched_retire=False, split_planes_until=None, gpu_zupt=False, gpu_propagate=False):
     """Closed loop through hostlib.Session, frame by frame, with the tracker-side bookkeeping of core/VioManager.cpp:360-506:
     a track is an MSCKF feature once it is lost or reaches back to the clone about to be marginalised; a track that spans the
     whole window (more than max_clone_size measurements) becomes a SLAM landmark while there is room (max_slam), and from then
@@ -198,7 +198,8 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
     the planes' removal are one device call.
     zupt: dict of Session.enable_zupt keywords (or {}) = VioManagerOptions::try_zupt: a frame at which the platform is found
     standing still gets a zero-velocity update instead of a clone (core/VioManager.cpp:311-331) and its measurements are dropped.
-    gpu_zupt: StateOptions::gpu_zupt - with zupt, the test, the decision and the update of such a frame are one device call."""
+    gpu_zupt: StateOptions::gpu_zupt - with zupt, the test, the decision and the update of such a frame are one device call.
+    gpu_propagate: StateOptions::gpu_propagate - every frame's IMU integration, propagation and clone are one device call."""
     from . import hostlib
     from .sim import log_so3
     from .synth import PROP_OPTS, quat_2_rot
@@ -223,6 +224,8 @@ def run_session(sim, n_frames=60, C=11, po=None, sigma_px=1.0, chi2_mult=1.0, pl
         ses.enable_batched_retire()
     if gpu_zupt:
         ses.enable_gpu_zupt()
+    if gpu_propagate:
+        ses.enable_gpu_propagate()
     ses.feed_imu(imu)
     if out_dir is not None:
         import os

@@ -548,15 +548,18 @@ extern "C" int ovph_run_updater(int mode, int C, const double *clone_q, const do
 // Propagator::propagate_and_clone harness: state with C clones (first estimate = value; State's own calibration), IMU state
 // x16 / x16_fej, covariance P, n_imu readings rows (t, wm, am).  state->_timestamp = t_state, camera time offset calib_dt;
 // propagates to `timestamp`.
-extern "C" int ovph_run_propagate(int C, const double *clone_q, const double *clone_p, const double *imu_x16, const double *imu_x16_fej,
-                                  double calib_dt, int N, const double *P, int n_imu, const double *imu, double t_state,
-                                  double timestamp, const double *sigmas4 /* w a wb ab */, double gravity_mag, int use_rk4,
-                                  int imu_avg, int do_fej,
-                                  /* outputs */ double *out_x16, double *out_x16_fej, double *out_Phi, double *out_Qd, double *out_last_w,
-                                  double *out_P /* (N+6)^2 */, double *out_new_clone7) {
+// gpu_propagate: StateOptions::gpu_propagate (ovph_run_propagate_opt; ovph_run_propagate is the same call with the option off);
+// out_new_clone_id: Type::id() of the clone registered at `timestamp`; out_ms: host clock around propagate_and_clone (may be NULL)
+static int run_propagate(int C, const double *clone_q, const double *clone_p, const double *imu_x16, const double *imu_x16_fej,
+                         double calib_dt, int N, const double *P, int n_imu, const double *imu, double t_state, double timestamp,
+                         const double *sigmas4 /* w a wb ab */, double gravity_mag, int use_rk4, int imu_avg, int do_fej,
+                         /* outputs */ double *out_x16, double *out_x16_fej, double *out_Phi, double *out_Qd, double *out_last_w,
+                         double *out_P /* (N+6)^2 */, double *out_new_clone7, int gpu_propagate, int *out_new_clone_id,
+                         double *out_ms) {
   ovph_run_opts o;
   ovph_run_opts_defaults(&o);
   StateOptions so;
+  so.gpu_propagate = gpu_propagate != 0;
   so.do_fej = do_fej != 0;
   so.do_calib_camera_pose = so.do_calib_camera_intrinsics = so.do_calib_camera_timeoffset = true;
   so.max_clone_size = C + 1;
@@ -572,7 +575,9 @@ extern "C" int ovph_run_propagate(int C, const double *clone_q, const double *cl
   auto &state = hs.state;
   Propagator prop(noise_of(sigmas4), gravity_mag);
   feed_imu_rows(prop, n_imu, imu);
+  const auto t_start = std::chrono::steady_clock::now();
   prop.propagate_and_clone(state, timestamp);
+  if (out_ms) *out_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
   memcpy(out_x16, state->_imu->value().data(), 16 * sizeof(double));
   memcpy(out_x16_fej, state->_imu->fej().data(), 16 * sizeof(double));
   memcpy(out_Phi, prop.last_Phi(), 225 * sizeof(double));
@@ -584,7 +589,30 @@ extern "C" int ovph_run_propagate(int C, const double *clone_q, const double *cl
   export_state(hs, out, o);
   auto nc = state->_clones_IMU.at(timestamp);
   memcpy(out_new_clone7, nc->value().data(), 7 * sizeof(double));
+  if (out_new_clone_id) *out_new_clone_id = nc->id();
   return 0;
+}
+
+extern "C" int ovph_run_propagate(int C, const double *clone_q, const double *clone_p, const double *imu_x16, const double *imu_x16_fej,
+                                  double calib_dt, int N, const double *P, int n_imu, const double *imu, double t_state,
+                                  double timestamp, const double *sigmas4 /* w a wb ab */, double gravity_mag, int use_rk4,
+                                  int imu_avg, int do_fej,
+                                  /* outputs */ double *out_x16, double *out_x16_fej, double *out_Phi, double *out_Qd, double *out_last_w,
+                                  double *out_P /* (N+6)^2 */, double *out_new_clone7) {
+  return run_propagate(C, clone_q, clone_p, imu_x16, imu_x16_fej, calib_dt, N, P, n_imu, imu, t_state, timestamp, sigmas4, gravity_mag,
+                       use_rk4, imu_avg, do_fej, out_x16, out_x16_fej, out_Phi, out_Qd, out_last_w, out_P, out_new_clone7, 0, nullptr,
+                       nullptr);
+}
+
+extern "C" int ovph_run_propagate_opt(int C, const double *clone_q, const double *clone_p, const double *imu_x16,
+                                      const double *imu_x16_fej, double calib_dt, int N, const double *P, int n_imu, const double *imu,
+                                      double t_state, double timestamp, const double *sigmas4, double gravity_mag, int use_rk4,
+                                      int imu_avg, int do_fej, double *out_x16, double *out_x16_fej, double *out_Phi, double *out_Qd,
+                                      double *out_last_w, double *out_P, double *out_new_clone7, int gpu_propagate, int *out_new_clone_id,
+                                      double *out_ms) {
+  return run_propagate(C, clone_q, clone_p, imu_x16, imu_x16_fej, calib_dt, N, P, n_imu, imu, t_state, timestamp, sigmas4, gravity_mag,
+                       use_rk4, imu_avg, do_fej, out_x16, out_x16_fej, out_Phi, out_Qd, out_last_w, out_P, out_new_clone7, gpu_propagate,
+                       out_new_clone_id, out_ms);
 }
 
 // UpdaterZeroVelocity::try_update harness: the state of ovph_run_propagate, n_calls (1 or 2) consecutive camera times

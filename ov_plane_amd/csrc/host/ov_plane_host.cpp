@@ -316,6 +316,22 @@ void StateHelper::augment_clone(std::shared_ptr<State> state, const double last_
   gpu_check(ovp_cov_augment_dt(state->_gpu, pose->id(), state->_calib_dt_CAMtoIMU->id(), dnc_dt), "ovp_cov_augment_dt");
 }
 
+void StateHelper::register_clone(std::shared_ptr<State> state, int appended_at) {
+  const double now = state->_timestamp;
+  if (state->_clones_IMU.count(now)) {
+    PRINT_ERROR("StateHelper::augment_clone() - there is a clone at this time already\n");
+    std::exit(EXIT_FAILURE);
+  }
+  auto pose = std::dynamic_pointer_cast<PoseJPL>(state->_imu->pose()->clone());
+  if (!pose) {
+    PRINT_ERROR("StateHelper::augment_clone() - the clone of the IMU pose is not a pose\n");
+    std::exit(EXIT_FAILURE);
+  }
+  pose->set_local_id(appended_at);
+  state->_variables.push_back(pose);
+  state->_clones_IMU[now] = pose;
+}
+
 // ---- state/StateHelper.cpp:627-636 -------------------------------------------------------------
 // One clone more than the window holds: the oldest goes (std::map keeps the clones ordered by time).
 void StateHelper::marginalize_old_clone(std::shared_ptr<State> state) {

@@ -96,6 +96,10 @@ struct StateOptions {
   // (ovp_zupt_update: one upload, one enqueue, one wait) instead of a marginal download, a 6 (n - 1)-row factorization on the host,
   // an EKFPropagation and an EKFUpdate of the stacked rows.  Not in the reference.
   bool gpu_zupt = false;
+  // Propagator::propagate_and_clone: the integration of the IMU window, EKFPropagation, the clone and its time-offset term are one
+  // device pass (ovp_propagate_and_clone: one upload, one enqueue, one wait) instead of a host integration and three calls.  Not in
+  // the reference.
+  bool gpu_propagate = false;
   // UpdaterMSCKF::update: on-plane features the device batch cannot carry (another camera, more than OVP_MAX_MEAS views) stay in the
   // plane loop through ovp_msckf_plane_update_general instead of going to the point update without their plane constraint - for
   // planes whose estimate does not come from this frame's fit (in the state, or handed over in _plane_estimates_cp_inG); a frame with
@@ -236,6 +240,9 @@ public:
   static void marginalize_many(std::shared_ptr<State> state, const std::vector<std::shared_ptr<ov_type::Type>> &margs);
   static std::shared_ptr<ov_type::Type> clone(std::shared_ptr<State> state, std::shared_ptr<ov_type::Type> variable_to_clone);
   static void augment_clone(std::shared_ptr<State> state, const double last_w[3]);
+  // StateOptions::gpu_propagate: augment_clone's bookkeeping alone (:378-394, :600-612) behind ovp_propagate_and_clone, which has
+  // appended the covariance block at appended_at: the copy of the IMU pose joins the variables and the clone window
+  static void register_clone(std::shared_ptr<State> state, int appended_at);
   static void marginalize_old_clone(std::shared_ptr<State> state);
   static void marginalize_slam(std::shared_ptr<State> state);  // state/StateHelper.cpp:638-652
   // state/StateHelper.cpp:654-776: planes whose id was re-assigned by the tracker are merged into their new id (a 3-row
@@ -433,6 +440,9 @@ public:
   const double *last_w() const { return _last_w; }
 
 protected:
+  // StateOptions::gpu_propagate: everything behind the preamble through ovp_propagate_and_clone
+  void propagate_and_clone_device(std::shared_ptr<State> state, double timestamp, double t_off_new,
+                                  const std::vector<ov_core::ImuData> &prop_data);
   void predict_mean_discrete(std::shared_ptr<State> state, double dt, const double w1[3], const double a1[3], const double w2[3],
                              const double a2[3], double new_q[4], double new_v[3], double new_p[3]);  // :456-488
   void predict_mean_rk4(std::shared_ptr<State> state, double dt, const double w1[3], const double a1[3], const double w2[3],

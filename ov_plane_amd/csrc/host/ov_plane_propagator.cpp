@@ -1,6 +1,7 @@
 // Host mirror of ov_plane::Propagator (state/Propagator.cpp).  The per-interval work is a handful of 3x3 / 15x15 products
 // (about 40 intervals per camera frame), so it stays on the host exactly as SURVEY.md §8 a11 scopes it; the only part that
-// touches the covariance is StateHelper::EKFPropagation + augment_clone, which run on the device-resident P.
+// touches the covariance is StateHelper::EKFPropagation + augment_clone, which run on the device-resident P.  With
+// StateOptions::gpu_propagate (default off) everything behind the preamble is one device pass instead (ovp_propagate_and_clone).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -197,6 +198,10 @@ void Propagator::propagate_and_clone(std::shared_ptr<State> state, double timest
     std::lock_guard<std::mutex> lck(imu_data_mtx);
     prop_data = Propagator::select_imu_readings(imu_data, time0, time1);
   }
+  if (state->_options.gpu_propagate) {
+    propagate_and_clone_device(state, timestamp, t_off_new, prop_data);
+    return;
+  }
   // Phi_summed = F_i Phi_summed ; Qd_summed = F_i Qd_summed F_i^T + Qd_i, symmetrised every interval (:92-102)
   double F[225], Qdi[225], T[225], T2[225];
   memset(_Phi, 0, sizeof(_Phi));
@@ -230,6 +235,64 @@ void Propagator::propagate_and_clone(std::shared_ptr<State> state, double timest
   state->_timestamp = timestamp;
   last_prop_time_offset = t_off_new;
   StateHelper::augment_clone(state, _last_w);
+}
+
+// StateOptions::gpu_propagate: everything behind the preamble in one device pass (ovp_propagate_and_clone: one upload, one enqueue,
+// one wait), then the bookkeeping of predict_and_compute (:447-453), propagate_and_clone (:116-124) and StateHelper::augment_clone
+// (:588-612) on the host: the IMU's value and first estimate, the timestamp, the clone's variable at the id the entry appended it at.
+void Propagator::propagate_and_clone_device(std::shared_ptr<State> state, double timestamp, double t_off_new,
+                                            const std::vector<ov_core::ImuData> &prop_data) {
+  std::vector<double> rows(7 * prop_data.size());
+  for (size_t i = 0; i < prop_data.size(); ++i) {
+    rows[7 * i] = prop_data[i].timestamp;
+    for (int k = 0; k < 3; ++k) {
+      rows[7 * i + 1 + k] = prop_data[i].wm[k];
+      rows[7 * i + 4 + k] = prop_data[i].am[k];
+    }
+  }
+  if (state->_clones_IMU.count(timestamp)) {
+    PRINT_ERROR("StateHelper::augment_clone() - there is a clone at this time already\n");
+    std::exit(EXIT_FAILURE);
+  }
+  ovp_propagate_in in;
+  memset(&in, 0, sizeof(in));
+  in.n_readings = (int)prop_data.size();
+  in.readings = rows.empty() ? nullptr : rows.data();
+  in.imu_id = state->_imu->id();
+  memcpy(in.q, state->_imu->quat(), sizeof(in.q));
+  memcpy(in.q_fej, state->_imu->quat_fej(), sizeof(in.q_fej));
+  for (int k = 0; k < 3; ++k) {
+    in.p[k] = state->_imu->pos()[k], in.v[k] = state->_imu->vel()[k];
+    in.p_fej[k] = state->_imu->pos_fej()[k], in.v_fej[k] = state->_imu->vel_fej()[k];
+    in.bg[k] = state->_imu->bias_g()[k], in.ba[k] = state->_imu->bias_a()[k];
+  }
+  in.gravity_mag = _gravity[2];
+  in.sigma_w = _noises.sigma_w, in.sigma_a = _noises.sigma_a, in.sigma_wb = _noises.sigma_wb, in.sigma_ab = _noises.sigma_ab;
+  in.use_rk4 = state->_options.use_rk4_integration, in.imu_avg = state->_options.imu_avg, in.do_fej = state->_options.do_fej;
+  in.clone = 1;
+  in.dt_id = state->_options.do_calib_camera_timeoffset ? state->_calib_dt_CAMtoIMU->id() : -1;
+  ovp_propagate_out out;
+  const int rc = ovp_propagate_and_clone(state->gpu(), &in, &out);
+  if (rc != 0) {
+    fprintf(stderr, "ov_plane(gpu): ovp_propagate_and_clone failed: %s\n", ovp_error_string(rc));
+    std::exit(EXIT_FAILURE);  // (a negative diagonal among them: StateHelper::EKFPropagation, state/StateHelper.cpp:107-117)
+  }
+  memcpy(_Phi, out.Phi, sizeof(_Phi));
+  memcpy(_Qs, out.Q, sizeof(_Qs));
+  memcpy(_last_w, out.last_w, sizeof(_last_w));
+  if (out.n_intervals > 0) {  // value and first estimate both become the propagated mean (:447-453)
+    VectorXd imu_x = state->_imu->value();
+    for (int k = 0; k < 4; ++k) imu_x(k) = out.q[k];
+    for (int k = 0; k < 3; ++k) {
+      imu_x(4 + k) = out.p[k];
+      imu_x(7 + k) = out.v[k];
+    }
+    state->_imu->set_value(imu_x);
+    state->_imu->set_fej(imu_x);
+  }
+  state->_timestamp = timestamp;
+  last_prop_time_offset = t_off_new;
+  StateHelper::register_clone(state, out.clone_id);
 }
 
 void Propagator::predict_and_compute(std::shared_ptr<State> state, const ov_core::ImuData &data_minus, const ov_core::ImuData &data_plus,

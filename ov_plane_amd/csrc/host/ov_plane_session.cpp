@@ -250,6 +250,15 @@ extern "C" int ovph_session_enable_gpu_zupt(void *h, int on) {
   return 0;
 }
 
+// StateOptions::gpu_propagate on (or off again): from the next step on, Propagator::propagate_and_clone integrates, propagates and
+// clones in one device pass (ovp_propagate_and_clone).
+extern "C" int ovph_session_enable_gpu_propagate(void *h, int on) {
+  auto *s = static_cast<Session *>(h);
+  if (!s->state->gpu()) return -31;
+  s->state->_options.gpu_propagate = on != 0;
+  return 0;
+}
+
 extern "C" int ovph_session_set_image_size(void *h, int width, int height) {
   auto *s = static_cast<Session *>(h);
   if (!s->active || width < 1 || height < 1) return -21;

@@ -323,6 +323,10 @@ __global__ void k_prop_cpt(const double* __restrict__ P, int ldp, int n, const i
   CPT[(size_t)r * phi + j] = s;
 }
 // step 2: PCP[i][j] = Qsym[i][j] + sum_k Phi[i][k] CPT[oldcol[k]][j]
+// (element (i, j) and element (j, i) are two different sums: the block is symmetric to rounding only, as the reference's is.
+//  ovp_propagate_and_clone promises a covariance symmetric to the bit and therefore has its own pair for the 15 contiguous IMU
+//  columns, k_prop15_cpt / k_prop15_write in k_propagate.hip, which forms the block on the ordered pair (lo, hi); changing this
+//  kernel instead would change the bits ovp_cov_propagate has always returned.)
 __global__ void k_prop_pcp(const double* __restrict__ CPT, const int* __restrict__ oldcol, int nold,
                            const double* __restrict__ Phi, const double* __restrict__ Q, int phi,
                            double* __restrict__ PCP) {

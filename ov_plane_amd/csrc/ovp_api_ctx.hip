@@ -669,6 +669,129 @@ extern "C" int ovp_zupt_update(ovp_ctx* c, const ovp_zupt_in* in, double* dx_hos
   return neg ? OVP_E_NEGDIAG : 0;
 }
 
+// ---- propagate and clone (k_propagate.hip) ---------------------------------------------------------
+namespace {
+
+// The entry's own buffers, made on first use and freed with the context.  Every call waits for its result, so the staging block
+// is free again when the next one fills it.
+struct Prop {
+  PinnedBuf<void> hstage;
+  DevBuf<void> dstage;
+  DevBuf<double> res;
+  Mailbox hres;  // payload: the result block, channel 0
+  size_t o_rd = 0, stage_bytes = 0;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // time_kernels: around the four steps
+  ~Prop() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+int prop_of(ovp_ctx* c, Prop** out) {
+  if (!c->prop) {
+    auto d = std::make_shared<Prop>();
+    StageLayout lay;
+    lay.take(sizeof(ovp::PropParams));
+    d->o_rd = lay.take(sizeof(double) * 7 * (size_t)OVP_PROP_MAX_READINGS);
+    d->stage_bytes = lay.bytes();
+    HIPCHK(d->hstage.alloc(d->stage_bytes));
+    HIPCHK(d->dstage.alloc(d->stage_bytes));
+    HIPCHK(d->res.alloc(OVP_PR_DOUBLES));
+    HIPCHK(d->hres.alloc(sizeof(double) * OVP_PR_DOUBLES));
+    c->prop = d;
+  }
+  *out = (Prop*)c->prop.get();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int ovp_propagate_and_clone(ovp_ctx* c, const ovp_propagate_in* in, ovp_propagate_out* out) {
+  // ---- every check before anything is touched or enqueued (a refused call keeps a kept factor too) ----
+  if (!c || !in || !out) return OVP_E_ARG;
+  if (!c->have_cov) return OVP_E_STATE;
+  const int n = c->n, nr = in->n_readings, imu = in->imu_id, dt_id = in->dt_id;
+  if (nr < 0 || (nr > 0 && !in->readings) || imu < 0 || imu + 15 > n) return OVP_E_ARG;
+  if (dt_id < -1 || dt_id >= n || (dt_id >= imu && dt_id < imu + 15)) return OVP_E_ARG;
+  if (nr > OVP_PROP_MAX_READINGS) return OVP_E_CAPACITY;
+  for (int i = 0; i + 1 < nr; ++i)
+    if (!(in->readings[7 * (size_t)(i + 1)] - in->readings[7 * (size_t)i] > 0.0)) return OVP_E_ARG;
+  const bool clone = in->clone != 0;
+  if (clone && n + 6 > c->n_max) return OVP_E_CAPACITY;
+  double* dCPT = c->smallbuf;
+  if ((size_t)n * 15 > c->smallbuf.capacity()) return OVP_E_CAPACITY;
+  HIPCHK(hipSetDevice(c->device));
+  Prop* d = nullptr;
+  if (const int rc = prop_of(c, &d)) return rc;
+  if (in->time_kernels && !d->ev[0])
+    for (hipEvent_t& e : d->ev) HIPCHK(hipEventCreate(&e));
+  drop_kept_factor(c);  // (writes the covariance: a kept factor no longer belongs to it)
+  // ---- one staged block [parameters | readings], one copy ----
+  char* h = (char*)d->hstage.get();
+  ovp::PropParams pp;
+  memset(&pp, 0, sizeof(pp));
+  memcpy(pp.q, in->q, sizeof(pp.q));
+  memcpy(pp.p, in->p, sizeof(pp.p));
+  memcpy(pp.v, in->v, sizeof(pp.v));
+  memcpy(pp.bg, in->bg, sizeof(pp.bg));
+  memcpy(pp.ba, in->ba, sizeof(pp.ba));
+  memcpy(pp.q_fej, in->q_fej, sizeof(pp.q_fej));
+  memcpy(pp.p_fej, in->p_fej, sizeof(pp.p_fej));
+  memcpy(pp.v_fej, in->v_fej, sizeof(pp.v_fej));
+  pp.g = in->gravity_mag;
+  pp.sw2 = in->sigma_w * in->sigma_w;
+  pp.sa2 = in->sigma_a * in->sigma_a;
+  pp.swb2 = in->sigma_wb * in->sigma_wb;
+  pp.sab2 = in->sigma_ab * in->sigma_ab;
+  pp.n_readings = nr;
+  pp.use_rk4 = in->use_rk4 != 0;
+  pp.imu_avg = in->imu_avg != 0;
+  pp.do_fej = in->do_fej != 0;
+  memcpy(h, &pp, sizeof(pp));
+  if (nr > 0) memcpy(h + d->o_rd, in->readings, sizeof(double) * 7 * (size_t)nr);
+  const size_t bytes = d->o_rd + sizeof(double) * 7 * (size_t)nr;
+  hipStream_t s = c->stream;
+  char* dv = (char*)d->dstage.get();
+  HIPCHK(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(c->flags + 1, 0, sizeof(int), s));
+  // ---- one enqueue, one wait: integration -> EKFPropagation -> clone and time offset -> the result block ----
+  SeqChannel& ch = d->hres.channel(0);
+  const unsigned seq = ch.arm();
+  hipEvent_t* ev = in->time_kernels ? d->ev : nullptr;
+  double* res = d->res;
+  memset(out, 0, sizeof(*out));
+  out->clone_id = -1;
+  if (ev) HIPCHK(hipEventRecord(ev[0], s));
+  HIPCHK(ovp_launch_prop_integrate((const ovp::PropParams*)dv, (const double*)(dv + d->o_rd), res, s));
+  if (ev) HIPCHK(hipEventRecord(ev[1], s));
+  HIPCHK(ovp_launch_prop_cov15(c->P, c->ld, n, imu, res, dCPT, c->flags + 1, s));
+  if (ev) HIPCHK(hipEventRecord(ev[2], s));
+  if (clone) {
+    HIPCHK(ovp_launch_prop_clone_dt(c->P, c->ld, n, imu, dt_id, c->clone_jitter, res, s));
+    c->n = n + 6;  // (the size goes with the launch that grows the matrix, whatever follows: an error return behind this line
+    out->clone_id = n;  //  leaves the grown size and the clone's id, the rest of `out` zero)
+  }
+  if (ev) HIPCHK(hipEventRecord(ev[3], s));
+  HIPCHK(ovp_launch_prop_finish(res, c->flags + 1, d->hres.dev(d->hres.payload()), ch.word_dev(), seq, s));
+  if (ev) HIPCHK(hipEventRecord(ev[4], s));
+  const int rw = ch.wait(s);
+  if (rw) return rw;
+  const double* hr = (const double*)d->hres.payload();
+  memcpy(out->q, hr + OVP_PR_Q, sizeof(out->q));
+  memcpy(out->p, hr + OVP_PR_P, sizeof(out->p));
+  memcpy(out->v, hr + OVP_PR_V, sizeof(out->v));
+  memcpy(out->last_w, hr + OVP_PR_LW, sizeof(out->last_w));
+  memcpy(out->Phi, hr + OVP_PR_PHI, sizeof(out->Phi));
+  memcpy(out->Q, hr + OVP_PR_QS, sizeof(out->Q));
+  out->n_intervals = (int)hr[OVP_PR_NI];
+  out->neg_diag = hr[OVP_PR_VERDICT] != 0.0 ? 1 : 0;
+  if (ev) {
+    HIPCHK(hipEventSynchronize(ev[4]));
+    for (int k = 0; k < 4; ++k) HIPCHK(hipEventElapsedTime(&out->kernel_ms[k], ev[k], ev[k + 1]));
+  }
+  return out->neg_diag ? OVP_E_NEGDIAG : 0;
+}
+
 extern "C" int ovp_cov_initialize_invertible(ovp_ctx* c, const double* H_R, int k, int cols, int ld, const int* col_ids,
                                              const double* H_Linv, const double* R) {
   drop_kept_factor(c);  // (writes the covariance: a kept factor no longer belongs to it)

@@ -238,6 +238,27 @@ struct ZuptParams {
 #define OVP_ZW_G 102
 #define OVP_ZW_DOUBLES 160
 
+// ovp_propagate_and_clone (k_propagate.hip).  The head of the call's staged block; the readings [n_readings][7] follow on the next
+// 64-byte line.
+struct PropParams {
+  double q[4], p[3], v[3], bg[3], ba[3];
+  double q_fej[4], p_fej[3], v_fej[3];
+  double g;                        // gravity magnitude (along +z of the global frame)
+  double sw2, sa2, swb2, sab2;     // squared continuous-time densities (NoiseManager::with_squares)
+  int n_readings, use_rk4, imu_avg, do_fej;
+};
+// the device result block of a call, in doubles: [q 4 | p 3 | v 3 | last_w 3 | - 3 | Phi 225 | Q 225 | verdict | intervals]; Phi, Q
+// column-major 15 x 15.  dnc_dt of the time-offset term is [last_w ; v] of this block, read where it lies.
+#define OVP_PR_Q 0
+#define OVP_PR_P 4
+#define OVP_PR_V 7
+#define OVP_PR_LW 10
+#define OVP_PR_PHI 16
+#define OVP_PR_QS 241
+#define OVP_PR_VERDICT 466
+#define OVP_PR_NI 467
+#define OVP_PR_DOUBLES 468
+
 }  // namespace ovp
 
 extern "C" {
@@ -247,6 +268,17 @@ extern "C" {
 hipError_t ovp_launch_zupt(double* P, int ld, int n, int imu_id, const ovp::ZuptParams* zp, const double* readings, double* work,
                            double* Y, double* res, unsigned* ticket, void* host_block, unsigned* word, unsigned seq, hipEvent_t* ev,
                            hipStream_t stream);
+// k_propagate.hip.  ovp_launch_prop_integrate: the IMU window of one ovp_propagate_and_clone into the mean, last_w, Phi and Q of
+// `res` (one workgroup, intervals in order).  ovp_launch_prop_clone_dt: the exact copy of the pose block [src, src + 6) appended at
+// n (jitter as ovp_launch_cov_clone) and, with dt >= 0, the time-offset term of ovp_launch_augment_dt on the new block with
+// dnc_dt = [last_w ; v] read from res.  ovp_launch_prop_finish: res[VERDICT] from *negdiag (cleared), the block into host_block,
+// seq into *word.
+hipError_t ovp_launch_prop_integrate(const ovp::PropParams* pp, const double* readings, double* res, hipStream_t stream);
+// ... ovp_launch_prop_cov15: StateHelper::EKFPropagation on the 15 contiguous columns at imu with Phi, Q of res; CPT: n x 15
+// doubles of scratch; the 15 x 15 block comes out symmetric to the bit; *negdiag is set on a negative diagonal element
+hipError_t ovp_launch_prop_cov15(double* P, int ld, int n, int imu, const double* res, double* CPT, int* negdiag, hipStream_t stream);
+hipError_t ovp_launch_prop_clone_dt(double* P, int ld, int n, int src, int dt, double jitter, const double* res, hipStream_t stream);
+hipError_t ovp_launch_prop_finish(double* res, int* negdiag, void* host_block, unsigned* word, unsigned seq, hipStream_t stream);
 // k_publish.hip: `bytes` of the device block src -> dst (mapped pinned memory), then seq into *word; src, dst 8-byte aligned;
 // clear8 leading 8-byte words of src are zeroed behind the post
 hipError_t ovp_launch_publish_block(const void* src, void* dst, size_t bytes, unsigned* word, unsigned seq, int clear8,

@@ -284,9 +284,12 @@ def run_updater(sc, mode, const_init_multi=5.0, const_init_chi2=1.0, fit_planes=
     return out
 
 
-def run_propagate(sc, x, imu, t_state, timestamp, calib_dt, po):
+def run_propagate(sc, x, imu, t_state, timestamp, calib_dt, po, gpu_propagate=False, timing=False):
     """Drives ov_plane::Propagator::propagate_and_clone (C++ host mirror; covariance on the device) on the clone window and
-    covariance of a synth scene (no planes / SLAM) with IMU state x (dict: q p v bg ba + *_fej) and readings imu [n,7]."""
+    covariance of a synth scene (no planes / SLAM) with IMU state x (dict: q p v bg ba + *_fej) and readings imu [n,7].
+    gpu_propagate: StateOptions::gpu_propagate - integration, propagation and clone in one device pass (ovp_propagate_and_clone,
+    through ovph_run_propagate_opt); the result then also holds new_clone_id.
+    timing: also return propagate_ms, the host clock around propagate_and_clone (either route, ovph_run_propagate_opt)."""
     L = lib()
     f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
@@ -299,11 +302,19 @@ def run_propagate(sc, x, imu, t_state, timestamp, calib_dt, po):
     cq, cp_ = f64(sc.clone_q), f64(sc.clone_p)
     out = dict(x16=np.zeros(16), x16_fej=np.zeros(16), Phi=np.zeros((15, 15)), Q=np.zeros((15, 15)), last_w=np.zeros(3),
                P=np.zeros((N + 6, N + 6)), new_clone=np.zeros(7))
-    rc = L.ovph_run_propagate(C.c_int(sc.C), p(cq), p(cp_), p(x16), p(x16f), C.c_double(calib_dt), C.c_int(N), p(P),
-                              C.c_int(imu.shape[0]), p(imu), C.c_double(t_state), C.c_double(timestamp), p(sig),
-                              C.c_double(po["gravity_mag"]), C.c_int(int(po["use_rk4"])), C.c_int(int(po["imu_avg"])),
-                              C.c_int(int(po["do_fej"])), p(out["x16"]), p(out["x16_fej"]), p(out["Phi"]), p(out["Q"]),
-                              p(out["last_w"]), p(out["P"]), p(out["new_clone"]))
+    args = (C.c_int(sc.C), p(cq), p(cp_), p(x16), p(x16f), C.c_double(calib_dt), C.c_int(N), p(P),
+            C.c_int(imu.shape[0]), p(imu), C.c_double(t_state), C.c_double(timestamp), p(sig),
+            C.c_double(po["gravity_mag"]), C.c_int(int(po["use_rk4"])), C.c_int(int(po["imu_avg"])),
+            C.c_int(int(po["do_fej"])), p(out["x16"]), p(out["x16_fej"]), p(out["Phi"]), p(out["Q"]),
+            p(out["last_w"]), p(out["P"]), p(out["new_clone"]))
+    if gpu_propagate or timing:
+        cid, ms = C.c_int(-1), C.c_double(0.0)
+        rc = L.ovph_run_propagate_opt(*args, C.c_int(1 if gpu_propagate else 0), C.byref(cid), C.byref(ms))
+        out["new_clone_id"] = cid.value
+        if timing:
+            out["propagate_ms"] = ms.value
+    else:
+        rc = L.ovph_run_propagate(*args)
     if rc != 0:
         raise RuntimeError("ovph_run_propagate failed with %d" % rc)
     out["Phi"] = np.ascontiguousarray(out["Phi"].T)   # column-major on the C++ side
@@ -674,6 +685,13 @@ class Session:
         rc = self._L.ovph_session_enable_batched_retire(C.c_void_p(self._h), C.c_int(1 if on else 0))
         if rc != 0:
             raise RuntimeError("ovph_session_enable_batched_retire failed with %d" % rc)
+
+    def enable_gpu_propagate(self, on=True):
+        """StateOptions::gpu_propagate: every later step integrates, propagates and clones in one device pass
+        (ovp_propagate_and_clone)."""
+        rc = self._L.ovph_session_enable_gpu_propagate(C.c_void_p(self._h), C.c_int(1 if on else 0))
+        if rc != 0:
+            raise RuntimeError("ovph_session_enable_gpu_propagate failed with %d" % rc)
 
     def enable_gpu_zupt(self, on=True):
         """StateOptions::gpu_zupt: every later try_zupt gates and updates in one device pass (ovp_zupt_update)."""
