@@ -927,6 +927,46 @@ int ovp_active_tracks_update(ovp_ctx *ctx, const ovp_active_tracks_in *in, ovp_a
  * (or < 0). */
 long ovp_active_tracks_debug(ovp_ctx *ctx, const char *what, int64_t id, double *out, long cap);
 
+/* ---- image front end: equalisation, image pyramid, pyramidal KLT ---------------------------------- */
+/* TrackPlane::feed_new_camera (track_plane/TrackPlane.cpp:40-92: cv::equalizeHist :65, cv::buildOpticalFlowPyramid) and the
+ * cv::calcOpticalFlowPyrLK call of perform_matching (:1299-1357).  OpenCV is not in the reference tree: the stage is restated from
+ * its published form (Bouguet's pyramidal Lucas-Kanade with OpenCV's externally visible conventions: Scharr gradients, reflect-101
+ * image borders, zero gradient borders, 30 iterations / 0.01 px, minEigThreshold 1e-4) and is UNPINNED; tests/klt_ref.py is the
+ * restatement it is held to.  Not built: CLAHE, FAST detection (:1173-1297), the RANSAC of :1344, stereo, the display images. */
+#define OVP_KLT_MAX_POINTS 4096
+#define OVP_KLT_MAX_LEVELS 8
+#define OVP_KLT_HIST_NONE 0       /* TrackBase::HistogramMethod, in its order */
+#define OVP_KLT_HIST_HISTOGRAM 1
+#define OVP_KLT_HIST_CLAHE 2      /* not built: OVP_E_ARG */
+/* One tracker per context (a second create that succeeds replaces the first, one that fails leaves the first in place and usable;
+ * the tracker goes with ovp_ctx_destroy): two pyramids of n_levels images
+ * (n_levels = maxLevel + 1: the reference's pyr_levels = 5 is 6; 1..OVP_KLT_MAX_LEVELS, every level at least 2 x 2), previous and
+ * current, swapped by index and never copied.  win: the window's side (:1326 win_size), odd, 3..21 - a lane of the point's wave
+ * holds ceil(win^2 / 64) <= 7 window pixels in registers.  max_points <= OVP_KLT_MAX_POINTS.  OVP_E_ARG outside these.
+ * _reset forgets both images. */
+int ovp_klt_create(ovp_ctx *ctx, int width, int height, int n_levels, int win, int max_points);
+int ovp_klt_destroy(ovp_ctx *ctx);
+int ovp_klt_reset(ovp_ctx *ctx);
+/* :40-92 one 8-bit image (height rows of `stride` bytes): uploaded, equalised (:65; OVP_KLT_HIST_NONE skips it), the pyramid built
+ * into the "current" half; the former current half is "previous" from here on.  One upload and one enqueue (histogram, LUT + apply,
+ * one launch per level), no wait.  The image is copied before the call returns.  OVP_E_STATE without ovp_klt_create; OVP_E_ARG for
+ * CLAHE, a null image, stride < width. */
+int ovp_klt_feed_image(ovp_ctx *ctx, const uint8_t *img, int stride, int hist_method);
+/* :1326-1330 n points of the previous image (pts_prev [2n] f32 pixels) into the current one, starting at guess [2n] (NULL: pts_prev,
+ * as the reference passes pts1 = pts0 with OPTFLOW_USE_INITIAL_FLOW): pts_out [2n], status [n] (1 found; 0: the window left the
+ * image at level 0 or the texture gate refused level 0 - pts_out then holds where the coarser levels left the point).  The error
+ * output the reference ignores (:1327) is not computed.  One upload, one launch (k_klt_track, one wave per point), one publication
+ * through the tracker's mailbox; f32, every sum in a fixed order: two runs give the same bits.  Decided on the host with nothing
+ * enqueued and the outputs untouched: OVP_E_STATE before two images were fed, OVP_E_CAPACITY for n > max_points, OVP_E_ARG for a
+ * non-finite coordinate; n = 0 returns at once.  No point or guess, however far outside, makes the kernel read outside a level. */
+int ovp_klt_track(ovp_ctx *ctx, int n, const float *pts_prev, const float *guess, float *pts_out, uint8_t *status);
+/* tests: what = "cur" / "prev": the bytes of pyramid level `level` of that half (rows packed); "equalized": level 0 of the current
+ * half; "dims": int32 [width, height] of the level; "iters": uint8 [n][8] iterations per level of the last ovp_klt_track;
+ * "timer": level != 0 puts events around the kernels (and a stream synchronisation behind each entry) from the next call on,
+ * "time": float [3] GPU milliseconds of the last timed calls [equalise, pyramid launches together, k_klt_track].  Returns the
+ * number of bytes (or < 0). */
+long ovp_klt_debug(ovp_ctx *ctx, const char *what, int level, void *out, long cap);
+
 /* ---- diagnostics ---------------------------------------------------------------------------- */
 /* copies an internal device buffer to host for tests: name in {"A","b","L","T","Lt","Y","G","rec","chi2",
  * "gramS","syrk"}; returns the byte count copied (or <0). */

@@ -274,6 +274,7 @@ EXPORTS = [
     "ovp_active_tracks_debug",
     "ovp_cov_marginalize_many", "ovp_planes_merge_retire", "ovp_zupt_update",
     "ovp_propagate_and_clone",
+    "ovp_klt_create", "ovp_klt_destroy", "ovp_klt_reset", "ovp_klt_feed_image", "ovp_klt_track", "ovp_klt_debug",
 ]
 
 
@@ -396,6 +397,13 @@ def lib():
         L.ovp_active_tracks_update.argtypes = [C.c_void_p, C.POINTER(ActiveTracksIn), C.POINTER(ActiveTracksOut)]
         L.ovp_active_tracks_debug.restype = C.c_long
         L.ovp_active_tracks_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_long]
+        L.ovp_klt_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.ovp_klt_destroy.argtypes = [C.c_void_p]
+        L.ovp_klt_reset.argtypes = [C.c_void_p]
+        L.ovp_klt_feed_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.ovp_klt_track.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ovp_klt_debug.restype = C.c_long
+        L.ovp_klt_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_long]
         _LIB = L
     return _LIB
 
@@ -635,6 +643,104 @@ class ActiveTracks:
     def kernel_ms(self):
         """GPU milliseconds of the last timed frame's kernel"""
         return float(self._debug(b"time", 0, 1)[0])
+
+
+class KltTracker:
+    """The image front end of a context (ovp_klt_*): TrackPlane::feed_new_camera's equalisation and pyramid, the
+    cv::calcOpticalFlowPyrLK call of perform_matching and the keep rule of feed_monocular, on the device.  The algorithm is restated
+    from its published form and unpinned (include/ovplane_hip.h).  Detection is the caller's: add_points seeds or tops up."""
+
+    HIST = {"NONE": 0, "HISTOGRAM": 1, "CLAHE": 2}
+
+    def __init__(self, ctx, width, height, n_levels=6, win=15, max_points=4096):
+        self.ctx, self.width, self.height, self.n_levels, self.win = ctx, int(width), int(height), int(n_levels), int(win)
+        _chk(lib().ovp_klt_create(ctx.handle, self.width, self.height, self.n_levels, self.win, int(max_points)), "ovp_klt_create")
+        self.ids_last = np.zeros(0, dtype=np.int64)
+        self.pts_last = np.zeros((0, 2), dtype=np.float32)
+        self._fed = 0
+
+    def close(self):
+        _chk(lib().ovp_klt_destroy(self.ctx.handle), "ovp_klt_destroy")
+
+    def reset(self):
+        _chk(lib().ovp_klt_reset(self.ctx.handle), "ovp_klt_reset")
+        self.ids_last, self.pts_last, self._fed = np.zeros(0, dtype=np.int64), np.zeros((0, 2), dtype=np.float32), 0
+
+    def feed_image(self, img, hist="HISTOGRAM"):
+        """one 8-bit image [height, width]: equalised, its pyramid built into the current half; does not wait for the device"""
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.shape != (self.height, self.width):
+            raise ValueError("an 8-bit image of %d x %d is expected" % (self.width, self.height))
+        if img.strides[1] != 1 or img.strides[0] < self.width:
+            img = np.ascontiguousarray(img)
+        t0 = time.perf_counter()
+        rc = lib().ovp_klt_feed_image(self.ctx.handle, img.ctypes.data, int(img.strides[0]), self.HIST[hist])
+        self.last_feed_ms = 1e3 * (time.perf_counter() - t0)
+        _chk(rc, "ovp_klt_feed_image")
+        self._fed += 1
+
+    def track(self, pts_prev, guess=None):
+        """pts_prev [n, 2] of the previous image into the current one, from guess (None: pts_prev) -> (pts [n, 2] f32, status [n])"""
+        p = np.ascontiguousarray(pts_prev, dtype=np.float32).reshape(-1, 2)
+        n = len(p)
+        g = None if guess is None else np.ascontiguousarray(guess, dtype=np.float32).reshape(n, 2)
+        out, st = np.zeros((n, 2), dtype=np.float32), np.zeros(n, dtype=np.uint8)
+        t0 = time.perf_counter()
+        rc = lib().ovp_klt_track(self.ctx.handle, n, p.ctypes.data, None if g is None else g.ctypes.data, out.ctypes.data, st.ctypes.data)
+        self.last_track_ms = 1e3 * (time.perf_counter() - t0)
+        _chk(rc, "ovp_klt_track")
+        return out, st
+
+    def add_points(self, ids, uv):
+        """seeds or tops up the tracked set with points of the last image fed (detection is the caller's)"""
+        self.ids_last = np.concatenate([self.ids_last, np.asarray(ids, dtype=np.int64).reshape(-1)])
+        self.pts_last = np.concatenate([self.pts_last, np.asarray(uv, dtype=np.float32).reshape(-1, 2)])
+
+    def step(self, img, mask=None, hist="HISTOGRAM"):
+        """feed_monocular :505-567 minus detection and the epipolar check: feeds img, tracks pts_last into it with guess = pts_last,
+        keeps a point unless x < 0, y < 0, (int) x >= cols, (int) y >= rows, mask > 127 at the truncated pixel, or status 0.
+        Returns (ids, pts) of the kept points, which are pts_last / ids_last from here on."""
+        self.feed_image(img, hist)
+        self.last_match = (np.zeros((0, 2), dtype=np.float32), np.zeros(0, dtype=np.uint8))
+        if self._fed < 2 or len(self.ids_last) == 0:
+            return self.ids_last.copy(), self.pts_last.copy()
+        p, st = self.track(self.pts_last, self.pts_last)
+        self.last_match = (p, st)  # of the points that went into this step, in their order
+        x, y = p[:, 0], p[:, 1]
+        xi, yi = np.clip(x, 0, self.width - 1).astype(np.int64), np.clip(y, 0, self.height - 1).astype(np.int64)
+        keep = (st != 0) & ~(x < 0) & ~(y < 0) & (np.trunc(x) < self.width) & (np.trunc(y) < self.height)
+        if mask is not None:
+            keep &= ~(np.asarray(mask)[yi, xi] > 127)
+        self.ids_last, self.pts_last = self.ids_last[keep], p[keep]
+        return self.ids_last.copy(), self.pts_last.copy()
+
+    def _debug(self, what, level, nbytes, dtype=np.uint8):
+        out = np.zeros(max(nbytes, 1), dtype=np.uint8)
+        k = lib().ovp_klt_debug(self.ctx.handle, what, int(level), out.ctypes.data, nbytes)
+        if k < 0:
+            raise OvpError(int(k), "ovp_klt_debug")
+        return out[:k].view(dtype)
+
+    def level(self, level, half="cur"):
+        """tests: pyramid level `level` of the current ("cur") or previous ("prev") half -> [h, w] uint8"""
+        w, h = self._debug(b"dims", level, 8, np.int32)
+        return self._debug(half.encode(), level, int(w) * int(h)).reshape(int(h), int(w)).copy()
+
+    def equalized(self):
+        return self._debug(b"equalized", 0, self.width * self.height).reshape(self.height, self.width).copy()
+
+    def iters(self, n):
+        """iterations per level [n, n_levels] of the last track of n points"""
+        return self._debug(b"iters", 0, 8 * n).reshape(n, 8)[:, :self.n_levels].astype(np.int32)
+
+    def timer(self, on=True):
+        """events around the kernels from the next call on (diagnostics: adds a stream synchronisation per entry)"""
+        self._debug(b"timer", 1 if on else 0, 0)
+
+    def kernel_ms(self):
+        """GPU milliseconds of the last timed calls: dict(equalize, pyramid, track)"""
+        t = self._debug(b"time", 0, 12, np.float32)
+        return dict(equalize=float(t[0]), pyramid=float(t[1]), track=float(t[2]))
 
 
 def rccl_unique_id() -> bytes:

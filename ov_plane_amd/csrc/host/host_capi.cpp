@@ -12,6 +12,7 @@
 
 #include "host_capi.h"
 #include "ov_plane_host.h"
+#include "ov_plane_trackplane.h"
 
 using namespace ov_plane;
 using namespace ov_type;
@@ -1089,4 +1090,41 @@ extern "C" int ovph_run_change_anchors(int C, const double *clone_q, const doubl
   out.P = out_P;
   export_state(hs, out, *op);
   return lm->has_had_anchor_change ? 0 : -20;
+}
+
+// TrackPlane's image half on a sequence of frames (host_capi.h)
+extern "C" int ovph_run_klt_sequence(int device, int width, int height, int n_frames, const uint8_t *frames, const uint8_t *mask,
+                                     int pyr_levels, int win_size, int hist_method, int n_pts, const int64_t *ids, const float *uv,
+                                     int32_t *n_kept, int64_t *kept_ids, float *kept_uv, int32_t *n_match, float *match_uv,
+                                     uint8_t *match_mask) {
+  ovp_ctx *gpu = nullptr;
+  int rc = ovp_ctx_create(device, 64, 4, 8, nullptr, &gpu);
+  if (rc) return rc;
+  {
+    ovp_trackplane_opts to;
+    ovp_trackplane_defaults(&to);
+    TrackPlane tp(gpu, to);
+    rc = tp.ok() ? tp.set_klt_options(pyr_levels, win_size, hist_method, std::max(n_pts, 1)) : OVP_E_STATE;
+    const size_t px = (size_t)width * height;
+    for (int f = 0; f < n_frames && rc == 0; ++f) {
+      rc = tp.feed_new_camera(0.1 * f, frames + px * f, width, height, width, mask);
+      if (rc) break;
+      if (f == 0) {
+        std::vector<size_t> id(ids, ids + n_pts);
+        std::vector<float> p(uv, uv + 2 * (size_t)n_pts);
+        tp.add_points(id, p);
+      }
+      const auto &ki = tp.get_last_ids();
+      const auto &kp = tp.get_last_pts();
+      const auto &mp = tp.get_last_match_pts();
+      const auto &mm = tp.get_last_match_mask();
+      n_kept[f] = (int32_t)ki.size(), n_match[f] = (int32_t)mm.size();
+      for (size_t i = 0; i < ki.size(); ++i) kept_ids[(size_t)f * n_pts + i] = (int64_t)ki[i];
+      if (!kp.empty()) memcpy(kept_uv + 2 * (size_t)f * n_pts, kp.data(), sizeof(float) * kp.size());
+      if (!mp.empty()) memcpy(match_uv + 2 * (size_t)f * n_pts, mp.data(), sizeof(float) * mp.size());
+      if (!mm.empty()) memcpy(match_mask + (size_t)f * n_pts, mm.data(), mm.size());
+    }
+  }
+  ovp_ctx_destroy(gpu);
+  return rc;
 }

@@ -62,6 +62,15 @@ void ovph_run_opts_defaults(ovph_run_opts *o);
 int ovph_run_opts_size(void);
 int ovph_run_opts_layout(int *offsets, int cap);
 
+// ov_plane::TrackPlane's image half (ov_plane_trackplane.h) on a sequence of n_frames images [n_frames][height][width] with one
+// mask [height][width] (NULL: none), on a context of its own on `device`: frame 0 is fed, the n_pts points (ids, uv [n_pts][2]) are
+// added, every later frame is fed.  Per frame f: n_kept[f] kept ids / points in kept_ids[f][n_pts] / kept_uv[f][n_pts][2], and what
+// perform_matching_klt returned for the points that went in: n_match[f], match_uv[f][n_pts][2], match_mask[f][n_pts].
+// pyr_levels is the reference's (images - 1).  Returns 0 or the first failing call's code.
+int ovph_run_klt_sequence(int device, int width, int height, int n_frames, const uint8_t *frames, const uint8_t *mask, int pyr_levels,
+                          int win_size, int hist_method, int n_pts, const int64_t *ids, const float *uv, int32_t *n_kept,
+                          int64_t *kept_ids, float *kept_uv, int32_t *n_match, float *match_uv, uint8_t *match_mask);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,452 @@
+// The image front end of a camera frame: TrackPlane::feed_new_camera (track_plane/TrackPlane.cpp:40-92: cv::equalizeHist and
+// cv::buildOpticalFlowPyramid), the cv::calcOpticalFlowPyrLK call of perform_matching (:1299-1357) - kernels and entry points
+// (ovp_klt_*).  OpenCV is not in the reference tree: the algorithm is restated from its published form (Bouguet's pyramidal
+// Lucas-Kanade with OpenCV's externally visible conventions) and is UNPINNED; tests/klt_ref.py is the restatement the device is
+// held to, and names every recalled convention in one place.
+//   k_klt_hist      256-bin histogram of the uploaded image: integer atomics in LDS per workgroup, then global - order-independent
+//   k_klt_equalize  the LUT of cv::equalizeHist from that histogram (every workgroup builds its own copy), applied
+//   k_klt_pyrdown   one level of cv::pyrDown on 8-bit data: [1 4 6 4 1] x [1 4 6 4 1], reflect-101, (sum + 128) >> 8
+//   k_klt_track     one wave per point, coarse to fine: a lane owns ceil(w^2 / 64) window pixels, the previous image's patch and its
+//                   two Scharr gradient patches stay in registers over a level's iterations, the current image is read with four
+//                   plain loads per pixel and iteration (every level of a 752 x 480 pyramid fits in L2), the five sums go through
+//                   a fixed xor butterfly.  No LDS, no barrier, no atomics: two runs give the same bits.
+// Address safety: every image address of every kernel goes through klt_reflect, which maps ANY int into [0, n) - whatever the
+// point, the guess or the level size, no read leaves a level's allocation.
+#include "ovp_ctx.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int KLT_MAX_LEVELS = 8, KLT_MAX_POINTS = 4096, KLT_MIN_WIN = 3, KLT_MAX_WIN = 21;  // 21^2 = 441 pixels: 7 per lane
+constexpr int KLT_MAX_ITERS = 30;                   // term_crit (:1328)
+constexpr float KLT_STOP_EPS = 0.01f, KLT_OSC_EPS = 0.01f, KLT_MIN_EIG = 1e-4f, KLT_GATE_SCALE = 1.0f / 1024.0f;
+constexpr float KLT_FLT_EPSILON = 1.1920929e-07f;
+
+// BORDER_REFLECT_101 of any int into [0, n)
+__host__ __device__ __forceinline__ int klt_reflect(int i, int n) {
+  if (n == 1) return 0;
+  const int p = 2 * (n - 1);
+  i %= p;
+  if (i < 0) i += p;
+  return i >= n ? p - i : i;
+}
+
+__global__ __launch_bounds__(256) void k_klt_hist(const unsigned char* __restrict__ img, int n, unsigned* __restrict__ hist) {
+  __shared__ unsigned h[256];
+  h[threadIdx.x] = 0u;
+  __syncthreads();
+  const int n16 = n >> 4;
+  const uint4* v = reinterpret_cast<const uint4*>(img);  // (the block is 256-byte aligned)
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n16; i += gridDim.x * 256) {
+    const uint4 q = v[i];
+    const unsigned wds[4] = {q.x, q.y, q.z, q.w};
+    for (int k = 0; k < 4; ++k)
+      for (int b = 0; b < 4; ++b) atomicAdd(&h[(wds[k] >> (8 * b)) & 255u], 1u);
+  }
+  if (blockIdx.x == 0)
+    for (int i = 16 * n16 + threadIdx.x; i < n; i += 256) atomicAdd(&h[img[i]], 1u);
+  __syncthreads();
+  if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(256) void k_klt_equalize(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, int n,
+                                                      const unsigned* __restrict__ hist) {
+  __shared__ unsigned h[256];
+  __shared__ unsigned char lut[256];
+  const int t = threadIdx.x;
+  h[t] = hist[t];
+  __syncthreads();
+  int first = 0;
+  while (first < 255 && h[first] == 0u) ++first;
+  const unsigned rest = (unsigned)n - h[first];
+  if (rest == 0u) {
+    lut[t] = (unsigned char)t;  // a constant image maps to itself
+  } else {
+    unsigned s = 0u;
+    for (int i = first + 1; i <= t; ++i) s += h[i];
+    const float scale = __fdiv_rn(255.0f, (float)rest);
+    lut[t] = (unsigned char)fminf(255.0f, rintf(__fmul_rn((float)s, scale)));  // (0 up to and including the first bin)
+  }
+  __syncthreads();
+  const int n16 = n >> 4;
+  const uint4* v = reinterpret_cast<const uint4*>(src);
+  uint4* o = reinterpret_cast<uint4*>(dst);
+  for (int i = blockIdx.x * 256 + t; i < n16; i += gridDim.x * 256) {
+    const uint4 q = v[i];
+    unsigned wds[4] = {q.x, q.y, q.z, q.w};
+    for (int k = 0; k < 4; ++k) {
+      unsigned r = 0u;
+      for (int b = 0; b < 4; ++b) r |= (unsigned)lut[(wds[k] >> (8 * b)) & 255u] << (8 * b);
+      wds[k] = r;
+    }
+    o[i] = make_uint4(wds[0], wds[1], wds[2], wds[3]);
+  }
+  if (blockIdx.x == 0)
+    for (int i = 16 * n16 + t; i < n; i += 256) dst[i] = lut[src[i]];
+}
+
+__global__ __launch_bounds__(256) void k_klt_pyrdown(const unsigned char* __restrict__ src, int w, int h, unsigned char* __restrict__ dst,
+                                                     int wo, int ho) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= wo * ho) return;
+  const int y = i / wo, x = i - y * wo;
+  int xs[5];
+  for (int k = 0; k < 5; ++k) xs[k] = klt_reflect(2 * x + k - 2, w);
+  int sum = 0;
+  for (int k = 0; k < 5; ++k) {
+    const unsigned char* row = src + (size_t)klt_reflect(2 * y + k - 2, h) * w;
+    const int r = row[xs[0]] + 4 * row[xs[1]] + 6 * row[xs[2]] + 4 * row[xs[3]] + row[xs[4]];
+    sum += (k == 0 || k == 4 ? 1 : (k == 2 ? 6 : 4)) * r;
+  }
+  dst[i] = (unsigned char)((sum + 128) >> 8);
+}
+
+struct KltTrackArgs {
+  const unsigned char *prev[KLT_MAX_LEVELS], *cur[KLT_MAX_LEVELS];
+  int w[KLT_MAX_LEVELS], h[KLT_MAX_LEVELS];
+  int n_levels, n, win;
+  const float *pts, *guess;  // [2n] each
+  float* out;                // [2n]
+  unsigned char *status, *iters;  // [n], [n * KLT_MAX_LEVELS] iterations run per level
+};
+
+__device__ __forceinline__ float klt_wave_sum(float v) {  // xor butterfly: a fixed order, the same bits in every lane
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// the window rule on a corner, on floats (which is the rule on its floor); false for a non-finite corner
+__device__ __forceinline__ bool klt_inside(float x, float y, int win, int cols, int rows) {
+  return x >= (float)-win && x < (float)cols && y >= (float)-win && y < (float)rows;
+}
+
+template <int NPL>
+__global__ __launch_bounds__(256) void k_klt_track(KltTrackArgs a) {
+  const int lane = threadIdx.x & 63, pt = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (pt >= a.n) return;  // (wave-uniform; the kernel has no barrier)
+  const float px = a.pts[2 * pt], py = a.pts[2 * pt + 1], g0x = a.guess[2 * pt], g0y = a.guess[2 * pt + 1];
+  const int win = a.win, top = a.n_levels - 1;
+  if (!(isfinite(px) && isfinite(py) && isfinite(g0x) && isfinite(g0y))) {  // refused on the host; status 0 before any image load
+    if (lane == 0) {
+      a.out[2 * pt] = g0x, a.out[2 * pt + 1] = g0y, a.status[pt] = 0;
+      for (int l = 0; l < KLT_MAX_LEVELS; ++l) a.iters[pt * KLT_MAX_LEVELS + l] = 0;
+    }
+    return;
+  }
+  int pr[NPL], pc[NPL];
+  bool valid[NPL];
+  for (int j = 0; j < NPL; ++j) {
+    const int k = lane + 64 * j;
+    valid[j] = k < win * win;
+    pr[j] = k / win, pc[j] = k - pr[j] * win;
+  }
+  const float half = (float)(win - 1) * 0.5f;
+  float gx = g0x * (1.0f / (float)(1 << top)), gy = g0y * (1.0f / (float)(1 << top));
+  bool st = true;
+  for (int lvl = top; lvl >= 0; --lvl) {
+    if (lvl != top) gx *= 2.0f, gy *= 2.0f;
+    int it = 0;
+    do {
+      const int cols = a.w[lvl], rows = a.h[lvl];
+      const unsigned char *I = a.prev[lvl], *J = a.cur[lvl];
+      const float s = 1.0f / (float)(1 << lvl);
+      const float pwx = px * s - half, pwy = py * s - half;
+      if (!klt_inside(pwx, pwy, win, cols, rows)) {
+        if (lvl == 0) st = false;
+        break;
+      }
+      const float fx = floorf(pwx), fy = floorf(pwy);
+      const int ipx = (int)fx, ipy = (int)fy;  // (in [-win, size): the rule above)
+      const float ca = pwx - fx, cb = pwy - fy;
+      const float w00 = (1.0f - ca) * (1.0f - cb), w01 = ca * (1.0f - cb), w10 = (1.0f - ca) * cb, w11 = ca * cb;
+      float Iw[NPL], Ix[NPL], Iy[NPL];
+      float sxx = 0.f, sxy = 0.f, syy = 0.f;
+      for (int j = 0; j < NPL; ++j) {
+        Iw[j] = Ix[j] = Iy[j] = 0.f;
+        if (!valid[j]) continue;
+        const int X = ipx + pc[j], Y = ipy + pr[j];
+        float v[4][4];
+        int xs[4];
+        for (int q = 0; q < 4; ++q) xs[q] = klt_reflect(X - 1 + q, cols);
+        for (int r = 0; r < 4; ++r) {
+          const unsigned char* row = I + (size_t)klt_reflect(Y - 1 + r, rows) * cols;
+          for (int q = 0; q < 4; ++q) v[r][q] = (float)row[xs[q]];
+        }
+        Iw[j] = w00 * v[1][1] + w01 * v[1][2] + w10 * v[2][1] + w11 * v[2][2];
+        // Scharr (3, 10, 3) x (-1, 0, 1) / 32 at the four pixels of the bilinear cell; a gradient pixel outside the level is zero
+        float dxv[2][2], dyv[2][2];
+        for (int dy = 0; dy < 2; ++dy)
+          for (int dx = 0; dx < 2; ++dx) {
+            const bool in = X + dx >= 0 && X + dx < cols && Y + dy >= 0 && Y + dy < rows;
+            const float ddx = 3.f * (v[dy][dx + 2] - v[dy][dx]) + 10.f * (v[dy + 1][dx + 2] - v[dy + 1][dx]) + 3.f * (v[dy + 2][dx + 2] - v[dy + 2][dx]);
+            const float ddy = 3.f * (v[dy + 2][dx] - v[dy][dx]) + 10.f * (v[dy + 2][dx + 1] - v[dy][dx + 1]) + 3.f * (v[dy + 2][dx + 2] - v[dy][dx + 2]);
+            dxv[dy][dx] = in ? ddx * (1.0f / 32.0f) : 0.f;
+            dyv[dy][dx] = in ? ddy * (1.0f / 32.0f) : 0.f;
+          }
+        Ix[j] = w00 * dxv[0][0] + w01 * dxv[0][1] + w10 * dxv[1][0] + w11 * dxv[1][1];
+        Iy[j] = w00 * dyv[0][0] + w01 * dyv[0][1] + w10 * dyv[1][0] + w11 * dyv[1][1];
+        sxx += Ix[j] * Ix[j], sxy += Ix[j] * Iy[j], syy += Iy[j] * Iy[j];
+      }
+      const float A11 = klt_wave_sum(sxx) * KLT_GATE_SCALE, A12 = klt_wave_sum(sxy) * KLT_GATE_SCALE, A22 = klt_wave_sum(syy) * KLT_GATE_SCALE;
+      const float D = A11 * A22 - A12 * A12;
+      const float min_eig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * win * win);
+      if (min_eig < KLT_MIN_EIG || D < KLT_FLT_EPSILON) {  // the texture gate
+        if (lvl == 0) st = false;
+        break;
+      }
+      float vx = gx - half, vy = gy - half, pdx = 0.f, pdy = 0.f;
+      for (int j = 0; j < KLT_MAX_ITERS; ++j) {
+        if (!klt_inside(vx, vy, win, cols, rows)) {
+          if (lvl == 0) st = false;
+          break;
+        }
+        ++it;
+        const float qx = floorf(vx), qy = floorf(vy);
+        const int iqx = (int)qx, iqy = (int)qy;
+        const float ja = vx - qx, jb = vy - qy;
+        const float u00 = (1.0f - ja) * (1.0f - jb), u01 = ja * (1.0f - jb), u10 = (1.0f - ja) * jb, u11 = ja * jb;
+        float b1 = 0.f, b2 = 0.f;
+        for (int k = 0; k < NPL; ++k) {
+          if (!valid[k]) continue;
+          const int x0 = klt_reflect(iqx + pc[k], cols), x1 = klt_reflect(iqx + pc[k] + 1, cols);
+          const unsigned char *r0 = J + (size_t)klt_reflect(iqy + pr[k], rows) * cols, *r1 = J + (size_t)klt_reflect(iqy + pr[k] + 1, rows) * cols;
+          const float jv = u00 * (float)r0[x0] + u01 * (float)r0[x1] + u10 * (float)r1[x0] + u11 * (float)r1[x1];
+          const float diff = jv - Iw[k];
+          b1 += diff * Ix[k], b2 += diff * Iy[k];
+        }
+        b1 = klt_wave_sum(b1) * KLT_GATE_SCALE, b2 = klt_wave_sum(b2) * KLT_GATE_SCALE;
+        const float dx = (A12 * b2 - A22 * b1) / D, dy = (A12 * b1 - A11 * b2) / D;
+        vx += dx, vy += dy;
+        if (dx * dx + dy * dy <= KLT_STOP_EPS * KLT_STOP_EPS) break;
+        if (j > 0 && fabsf(dx + pdx) < KLT_OSC_EPS && fabsf(dy + pdy) < KLT_OSC_EPS) {
+          vx -= dx * 0.5f, vy -= dy * 0.5f;
+          break;
+        }
+        pdx = dx, pdy = dy;
+      }
+      gx = vx + half, gy = vy + half;
+    } while (0);
+    if (lane == 0) a.iters[pt * KLT_MAX_LEVELS + lvl] = (unsigned char)it;
+  }
+  if (lane == 0) {
+    a.out[2 * pt] = gx, a.out[2 * pt + 1] = gy, a.status[pt] = st ? 1 : 0;
+    for (int l = a.n_levels; l < KLT_MAX_LEVELS; ++l) a.iters[pt * KLT_MAX_LEVELS + l] = 0;
+  }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+struct Klt {
+  int width = 0, height = 0, n_levels = 0, win = 0, max_points = 0;
+  int lw[KLT_MAX_LEVELS] = {}, lh[KLT_MAX_LEVELS] = {};
+  size_t loff[KLT_MAX_LEVELS] = {};  // a level's offset in a half (256-byte aligned)
+  size_t half_bytes = 0;
+  DevBuf<unsigned char> pyr[2], raw;  // the two halves, swapped by index; the uploaded image in front of the equalisation
+  DevBuf<unsigned> hist;
+  PinnedBuf<unsigned char> himg;  // the upload's staging, rows packed
+  PinnedBuf<void> hstage;
+  DevBuf<void> dstage, dres;
+  Mailbox hres;
+  size_t stage_cap = 0, res_cap = 0;
+  int cur = 0, fed = 0;  // index of the current half; images fed since create / reset
+  hipEvent_t ev_up = nullptr;
+  hipEvent_t ev_eq0 = nullptr, ev_eq1 = nullptr, ev_pyr1 = nullptr, ev_trk0 = nullptr, ev_trk1 = nullptr;  // timed mode
+  bool up_pending = false, timed = false;
+  float ms[3] = {0.f, 0.f, 0.f};  // equalise, pyramid launches together, k_klt_track
+  int last_n = 0;
+  ~Klt() {
+    for (hipEvent_t e : {ev_up, ev_eq0, ev_eq1, ev_pyr1, ev_trk0, ev_trk1})
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+Klt* klt_of(ovp_ctx* c) { return c ? (Klt*)c->klt.get() : nullptr; }
+
+}  // namespace
+
+extern "C" int ovp_klt_create(ovp_ctx* c, int width, int height, int n_levels, int win, int max_points) {
+  if (!c) return OVP_E_ARG;
+  if (width < 2 || height < 2 || width > 16384 || height > 16384 || n_levels < 1 || n_levels > KLT_MAX_LEVELS) return OVP_E_ARG;
+  if (win < KLT_MIN_WIN || win > KLT_MAX_WIN || !(win & 1) || max_points < 1 || max_points > KLT_MAX_POINTS) return OVP_E_ARG;
+  auto d = std::make_shared<Klt>();
+  d->width = width, d->height = height, d->n_levels = n_levels, d->win = win, d->max_points = max_points;
+  size_t off = 0;
+  for (int l = 0, w = width, h = height; l < n_levels; ++l, w = (w + 1) / 2, h = (h + 1) / 2) {
+    if (w < 2 || h < 2) return OVP_E_ARG;  // a level smaller than 2 x 2
+    d->lw[l] = w, d->lh[l] = h, d->loff[l] = off;
+    off += ((size_t)w * h + 255) & ~(size_t)255;
+  }
+  d->half_bytes = off;
+  HIPCHK(hipSetDevice(c->device));
+  if (c->klt) HIPCHK(hipStreamSynchronize(c->stream));  // (a second create replaces the first - once it has succeeded: a failure below leaves the first in place)
+  for (auto& p : d->pyr) HIPCHK(p.alloc(off));
+  HIPCHK(d->raw.alloc(((size_t)width * height + 255) & ~(size_t)255));
+  HIPCHK(d->hist.alloc(256));
+  HIPCHK(d->himg.alloc((size_t)width * height));
+  d->stage_cap = 64 * 2 + sizeof(float) * 4 * (size_t)max_points;
+  d->res_cap = 64 * 3 + sizeof(float) * 2 * (size_t)max_points + (size_t)max_points * (1 + KLT_MAX_LEVELS);
+  HIPCHK(d->hstage.alloc(d->stage_cap));
+  HIPCHK(d->dstage.alloc(d->stage_cap));
+  HIPCHK(d->dres.alloc(d->res_cap));
+  HIPCHK(d->hres.alloc(d->res_cap));
+  HIPCHK(hipEventCreateWithFlags(&d->ev_up, hipEventDisableTiming));
+  for (hipEvent_t* e : {&d->ev_eq0, &d->ev_eq1, &d->ev_pyr1, &d->ev_trk0, &d->ev_trk1}) HIPCHK(hipEventCreate(e));
+  c->klt = d;
+  return 0;
+}
+
+extern "C" int ovp_klt_destroy(ovp_ctx* c) {
+  if (!c) return OVP_E_ARG;
+  if (!c->klt) return OVP_E_STATE;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->klt.reset();
+  return 0;
+}
+
+extern "C" int ovp_klt_reset(ovp_ctx* c) {
+  Klt* d = klt_of(c);
+  if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
+  d->fed = 0;  // (a half is overwritten when an image takes it)
+  return 0;
+}
+
+extern "C" int ovp_klt_feed_image(ovp_ctx* c, const uint8_t* img, int stride, int hist_method) {
+  Klt* d = klt_of(c);
+  if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
+  if (!img || stride < d->width) return OVP_E_ARG;
+  if (hist_method != OVP_KLT_HIST_NONE && hist_method != OVP_KLT_HIST_HISTOGRAM) return OVP_E_ARG;  // CLAHE is not built
+  HIPCHK(hipSetDevice(c->device));
+  if (d->up_pending) HIPCHK(hipEventSynchronize(d->ev_up));  // the staging block is free once the previous upload has left it
+  const int w = d->width, h = d->height, n = w * h;
+  for (int y = 0; y < h; ++y) memcpy(d->himg.get() + (size_t)y * w, img + (size_t)y * stride, w);
+  const int nxt = d->cur ^ 1;  // the former current half becomes "previous" by index: nothing is copied
+  unsigned char* lv0 = d->pyr[nxt].get();
+  const bool eq = hist_method == OVP_KLT_HIST_HISTOGRAM;
+  HIPCHK(hipMemcpyAsync(eq ? d->raw.get() : lv0, d->himg.get(), n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipEventRecord(d->ev_up, c->stream));
+  d->up_pending = true;
+  if (d->timed) HIPCHK(hipEventRecord(d->ev_eq0, c->stream));
+  if (eq) {
+    HIPCHK(hipMemsetAsync(d->hist.get(), 0, 256 * sizeof(unsigned), c->stream));
+    const int blocks = std::max(1, std::min(256, (n / 16 + 255) / 256));
+    hipLaunchKernelGGL(k_klt_hist, dim3(blocks), dim3(256), 0, c->stream, (const unsigned char*)d->raw.get(), n, d->hist.get());
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_klt_equalize, dim3(blocks), dim3(256), 0, c->stream, (const unsigned char*)d->raw.get(), lv0, n,
+                       (const unsigned*)d->hist.get());
+    HIPCHK(hipGetLastError());
+  }
+  if (d->timed) HIPCHK(hipEventRecord(d->ev_eq1, c->stream));
+  for (int l = 1; l < d->n_levels; ++l) {
+    const int m = d->lw[l] * d->lh[l];
+    hipLaunchKernelGGL(k_klt_pyrdown, dim3((m + 255) / 256), dim3(256), 0, c->stream, (const unsigned char*)(lv0 + d->loff[l - 1]),
+                       d->lw[l - 1], d->lh[l - 1], lv0 + d->loff[l], d->lw[l], d->lh[l]);
+    HIPCHK(hipGetLastError());
+  }
+  d->cur = nxt;
+  if (d->fed < 2) ++d->fed;
+  if (d->timed) {
+    HIPCHK(hipEventRecord(d->ev_pyr1, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipEventElapsedTime(&d->ms[0], d->ev_eq0, d->ev_eq1));
+    HIPCHK(hipEventElapsedTime(&d->ms[1], d->ev_eq1, d->ev_pyr1));
+  }
+  return 0;
+}
+
+extern "C" int ovp_klt_track(ovp_ctx* c, int n, const float* pts_prev, const float* guess, float* pts_out, uint8_t* status) {
+  Klt* d = klt_of(c);
+  if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
+  // ---- every check before anything is touched or enqueued ----
+  if (n < 0) return OVP_E_ARG;
+  if (d->fed < 2) return OVP_E_STATE;
+  if (n > d->max_points) return OVP_E_CAPACITY;
+  if (n == 0) return 0;
+  if (!pts_prev || !pts_out || !status) return OVP_E_ARG;
+  for (int i = 0; i < 2 * n; ++i)
+    if (!std::isfinite(pts_prev[i]) || (guess && !std::isfinite(guess[i]))) return OVP_E_ARG;
+  StageLayout L;
+  const size_t o_pts = L.take(sizeof(float) * 2 * n), o_guess = L.take(sizeof(float) * 2 * n);
+  StageLayout R;
+  const size_t r_out = R.take(sizeof(float) * 2 * n), r_st = R.take(n), r_it = R.take((size_t)n * KLT_MAX_LEVELS);
+  if (L.bytes() > d->stage_cap || R.bytes() > d->res_cap) return OVP_E_CAPACITY;  // (cannot happen below max_points)
+  // ---- from here on the call goes through ----
+  HIPCHK(hipSetDevice(c->device));
+  char* h = (char*)d->hstage.get();
+  memcpy(h + o_pts, pts_prev, sizeof(float) * 2 * n);
+  memcpy(h + o_guess, guess ? guess : pts_prev, sizeof(float) * 2 * n);  // :1329 the reference passes pts1 = pts0
+  char *dv = (char*)d->dstage.get(), *dr = (char*)d->dres.get();
+  HIPCHK(hipMemcpyAsync(dv, h, L.bytes(), hipMemcpyHostToDevice, c->stream));
+  KltTrackArgs a;
+  const unsigned char *pc = d->pyr[d->cur].get(), *pp = d->pyr[d->cur ^ 1].get();
+  for (int l = 0; l < KLT_MAX_LEVELS; ++l) {
+    const int q = l < d->n_levels ? l : 0;
+    a.prev[l] = pp + d->loff[q], a.cur[l] = pc + d->loff[q], a.w[l] = d->lw[q], a.h[l] = d->lh[q];
+  }
+  a.n_levels = d->n_levels, a.n = n, a.win = d->win;
+  a.pts = (const float*)(dv + o_pts), a.guess = (const float*)(dv + o_guess);
+  a.out = (float*)(dr + r_out), a.status = (unsigned char*)(dr + r_st), a.iters = (unsigned char*)(dr + r_it);
+  if (d->timed) HIPCHK(hipEventRecord(d->ev_trk0, c->stream));
+  const dim3 grid((n + 3) / 4), block(256);
+  const int npl = (d->win * d->win + 63) / 64;
+  if (npl <= 1) hipLaunchKernelGGL(k_klt_track<1>, grid, block, 0, c->stream, a);
+  else if (npl <= 2) hipLaunchKernelGGL(k_klt_track<2>, grid, block, 0, c->stream, a);
+  else if (npl <= 4) hipLaunchKernelGGL(k_klt_track<4>, grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL(k_klt_track<7>, grid, block, 0, c->stream, a);
+  HIPCHK(hipGetLastError());
+  if (d->timed) HIPCHK(hipEventRecord(d->ev_trk1, c->stream));
+  SeqChannel& ch = d->hres.channel(0);
+  const unsigned seq = ch.arm();
+  HIPCHK(ovp_launch_publish_block(dr, d->hres.dev(d->hres.payload()), R.bytes(), ch.word_dev(), seq, 0, c->stream));
+  const int rw = ch.wait(c->stream);
+  if (rw) return rw;
+  if (d->timed) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipEventElapsedTime(&d->ms[2], d->ev_trk0, d->ev_trk1));
+  }
+  const char* hr = (const char*)d->hres.payload();
+  memcpy(pts_out, hr + r_out, sizeof(float) * 2 * n);
+  memcpy(status, hr + r_st, n);
+  d->last_n = n;
+  return 0;
+}
+
+extern "C" long ovp_klt_debug(ovp_ctx* c, const char* what, int level, void* out, long cap) {
+  Klt* d = klt_of(c);
+  if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
+  if (!what || !out || cap < 0) return OVP_E_ARG;
+  if (!strcmp(what, "timer")) {
+    d->timed = level != 0;
+    return 0;
+  }
+  if (!strcmp(what, "time")) {
+    if (cap < (long)sizeof(d->ms)) return OVP_E_ARG;
+    memcpy(out, d->ms, sizeof(d->ms));
+    return (long)sizeof(d->ms);
+  }
+  if (!strcmp(what, "iters")) {  // of the last ovp_klt_track: [n][8] iterations per level (the mailbox still holds them)
+    const size_t off = StageLayout::al(sizeof(float) * 2 * d->last_n) + StageLayout::al(d->last_n), bytes = (size_t)d->last_n * KLT_MAX_LEVELS;
+    if ((size_t)cap < bytes) return OVP_E_ARG;
+    if (bytes) memcpy(out, (const char*)d->hres.payload() + off, bytes);
+    return (long)bytes;
+  }
+  if (!strcmp(what, "dims")) {
+    if (level < 0 || level >= d->n_levels || cap < (long)(2 * sizeof(int))) return OVP_E_ARG;
+    const int wh[2] = {d->lw[level], d->lh[level]};
+    memcpy(out, wh, sizeof(wh));
+    return (long)sizeof(wh);
+  }
+  int half;
+  if (!strcmp(what, "cur")) half = d->cur;
+  else if (!strcmp(what, "prev")) half = d->cur ^ 1;
+  else if (!strcmp(what, "equalized")) half = d->cur, level = 0;  // the equalised image is level 0 of the current half
+  else return OVP_E_ARG;
+  if (level < 0 || level >= d->n_levels) return OVP_E_ARG;
+  if (d->fed < (half == d->cur ? 1 : 2)) return OVP_E_STATE;
+  const size_t bytes = (size_t)d->lw[level] * d->lh[level];
+  if ((size_t)cap < bytes) return OVP_E_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(out, d->pyr[half].get() + d->loff[level], bytes, hipMemcpyDeviceToHost));
+  return (long)bytes;
+}

@@ -11,6 +11,7 @@
 //   k_plane_detect.hip plane detection from the tracked features: its kernels and its entry points
 //   k_delaunay.hip     the Delaunay triangulation of a frame's vertices in one workgroup (ovp_launch_delaunay, k_delaunay.h)
 //   k_active_tracks.hip re-triangulation of a frame's active tracks (ovp_active_tracks_*): its kernel and its entry points
+//   k_klt.hip          the image front end (ovp_klt_*): equalisation, image pyramid and pyramidal Lucas-Kanade, kernels and entry points
 //   k_retire.hip       a frame's retirements in one compaction, its plane merges in sequence in front of it: kernels and entry points
 //   k_zupt.hip         the zero-velocity update's gate, rows and apply kernels (entry point: ovp_zupt_update in ovp_api_ctx.hip)
 //   k_propagate.hip    the IMU integration, clone-plus-time-offset and publishing kernels of ovp_propagate_and_clone (ovp_api_ctx.hip)
@@ -307,6 +308,7 @@ struct ovp_ctx {
   std::shared_ptr<void> active_tracks;  // ovp_active_tracks_create (k_active_tracks.hip): the slot table, its staging and mailbox, freed with the context
   std::shared_ptr<void> retire;  // ovp_cov_marginalize_many / ovp_planes_merge_retire (k_retire.hip): their staging, scratch and mailbox, made on first use
   std::shared_ptr<void> zupt;    // ovp_zupt_update (ovp_api_ctx.hip, k_zupt.hip): its staging and device blocks, made on first use
+  std::shared_ptr<void> klt;     // ovp_klt_create (k_klt.hip): the two image pyramids, staging, result block and mailbox, freed with the context
   std::shared_ptr<void> prop;    // ovp_propagate_and_clone (ovp_api_ctx.hip, k_propagate.hip): its staging, result block and mailbox, made on first use
 
   ovp_ctx() = default;

@@ -416,6 +416,31 @@ def run_plane_givens(op, H_f, H_x, H_cp, res):
     return Hx[:ro].copy(), (Hc[:ro].copy() if H_cp is not None else None), r[:ro].copy()
 
 
+def run_klt_sequence(frames, mask, ids, uv, pyr_levels=5, win=15, hist="HISTOGRAM", device=0):
+    """ov_plane::TrackPlane's image half (feed_new_camera, add_points, perform_matching_klt) on frames [K, h, w] uint8 with one mask
+    [h, w] (None: none): frame 0 is fed, the points added, every later frame fed.  Returns a list of K dicts(ids, pts: what the frame
+    kept; match_pts, match_mask: what perform_matching_klt returned for the points that went into it)."""
+    L = lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    K, h, w = fr.shape
+    mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(h, w)
+    id64 = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+    n = len(id64)
+    p = np.ascontiguousarray(uv, dtype=np.float32).reshape(n, 2)
+    m = max(n, 1)
+    n_kept, n_match = np.zeros(K, dtype=np.int32), np.zeros(K, dtype=np.int32)
+    kept_ids, kept_uv = np.zeros((K, m), dtype=np.int64), np.zeros((K, m, 2), dtype=np.float32)
+    match_uv, match_mask = np.zeros((K, m, 2), dtype=np.float32), np.zeros((K, m), dtype=np.uint8)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    rc = L.ovph_run_klt_sequence(C.c_int(device), C.c_int(w), C.c_int(h), C.c_int(K), vp(fr), vp(mk), C.c_int(pyr_levels), C.c_int(win),
+                                 C.c_int({"NONE": 0, "HISTOGRAM": 1, "CLAHE": 2}[hist]), C.c_int(n), vp(id64), vp(p), vp(n_kept),
+                                 vp(kept_ids), vp(kept_uv), vp(n_match), vp(match_uv), vp(match_mask))
+    if rc:
+        raise RuntimeError("ovph_run_klt_sequence failed with %d" % rc)
+    return [dict(ids=kept_ids[f, :n_kept[f]].copy(), pts=kept_uv[f, :n_kept[f]].copy(), match_pts=match_uv[f, :n_match[f]].copy(),
+                 match_mask=match_mask[f, :n_match[f]].copy()) for f in range(K)]
+
+
 def run_sequence(init, imu, frame_time, frames, po, sigma_px=1.0, chi2_mult=1.0, trace=False, plane_mode=0, plane_min_feat=20,
                  sigma_c=0.01):
     """Closed loop over several frames through the C++ host mirror (Propagator::propagate_and_clone ->

@@ -1,0 +1,190 @@
+"""GPU tests of the image front end (ovp_klt_*, capi.KltTracker): images bit-equal to the restatement (tests/klt_ref.py), status and
+positions against its float64 run and against the scenes' closed form (tests/klt_cases.py), determinism, refusals, the keep rule
+of step(), and the independence of contexts.
+
+Bounds: position against the restatement min(4 x F32_SPREAD_PX, 0.02 px) - the float32 spread of the restatement itself, four
+times for a summation order other than numpy's, capped at two stopping steps; against the closed form the per-scene figure the CPU
+test measured (klt_cases.CLOSED_FORM_PX) plus that bound.  Status: identical except on points the restatement flags near a
+decision (at most 2 % of a scene, test_klt_cpu.py)."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import klt_cases  # noqa: E402
+import klt_ref  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+RESTATEMENT_PX = min(4 * klt_cases.F32_SPREAD_PX, 0.02)
+
+
+@pytest.fixture(scope="module")
+def ctx(hiplib):
+    c = hiplib.Context(64, 4, 8)
+    yield c
+    c.close()
+
+
+def _tracker(hiplib, ctx, sc, max_points=256):
+    kt = hiplib.KltTracker(ctx, sc.width, sc.height, sc.levels, klt_cases.WIN, max_points)
+    kt.feed_image(sc.img0, sc.hist)
+    kt.feed_image(sc.img1, sc.hist)
+    return kt
+
+
+@pytest.mark.parametrize("name", klt_cases.NAMES)
+def test_scene(hiplib, ctx, name):
+    sc = klt_cases.scene(name)
+    pyr0, pyr1 = sc.pyramids
+    kt = _tracker(hiplib, ctx, sc)
+    # every level of both halves and the equalised image, bit for bit
+    for lvl in range(sc.levels):
+        assert np.array_equal(kt.level(lvl, "prev"), pyr0[lvl]), "previous half, level %d" % lvl
+        assert np.array_equal(kt.level(lvl, "cur"), pyr1[lvl]), "current half, level %d" % lvl
+    assert np.array_equal(kt.equalized(), pyr1[0])
+    ref_p, ref_s, rep = sc.reference(np.float64)
+    p, st = kt.track(sc.pts, sc.guess)
+    near = rep["near"]
+    cmp = ~near
+    print("%s: %d of %d points near a decision left out of the status comparison: %s" % (name, near.sum(), len(near), np.nonzero(near)[0].tolist()))
+    assert np.array_equal(st[cmp], ref_s[cmp])
+    ok = (st == 1) & (ref_s == 1)
+    d_ref = float(np.abs(p[ok].astype(np.float64) - ref_p[ok]).max())
+    reg = ok & sc.regular
+    d_cf = float(np.abs(p[reg].astype(np.float64) - sc.truth[reg]).max())
+    print("%s: worst |device - restatement| %.3e px (bound %.3e), worst |device - closed form| %.5f px (bound %.5f)" % (
+        name, d_ref, RESTATEMENT_PX, d_cf, klt_cases.CLOSED_FORM_PX[name] + RESTATEMENT_PX))
+    assert d_ref <= RESTATEMENT_PX
+    assert d_cf <= klt_cases.CLOSED_FORM_PX[name] + RESTATEMENT_PX
+    # determinism; guess = None is guess = pts_prev
+    p2, st2 = kt.track(sc.pts, sc.guess)
+    assert p.tobytes() == p2.tobytes() and st.tobytes() == st2.tobytes()
+    if sc.guess is None:
+        p3, st3 = kt.track(sc.pts, sc.pts)
+        assert p.tobytes() == p3.tobytes() and st.tobytes() == st3.tobytes()
+    # packing edges: a call's points do not depend on how many share it
+    if name == "subpixel_64x48":
+        for m in (1, 63, 64):
+            pm, sm = kt.track(sc.pts[:m])
+            assert pm.tobytes() == p[:m].tobytes() and sm.tobytes() == st[:m].tobytes(), m
+    # a third image: the halves swap, the oldest image is gone
+    kt.feed_image(sc.img0, sc.hist)
+    for lvl in range(sc.levels):
+        assert np.array_equal(kt.level(lvl, "prev"), pyr1[lvl]) and np.array_equal(kt.level(lvl, "cur"), pyr0[lvl])
+    kt.close()
+
+
+def test_equalise_edges_and_strided_upload(hiplib, ctx):
+    rng = np.random.default_rng(5)
+    kt = hiplib.KltTracker(ctx, 47, 31, 3, klt_cases.WIN, 8)
+    const = np.full((31, 47), 91, dtype=np.uint8)
+    two = np.where(rng.random((31, 47)) < 0.4, 30, 180).astype(np.uint8)
+    wide = rng.integers(0, 256, size=(31, 64)).astype(np.uint8)
+    for img in (const, two, wide[:, 3:50]):  # (the last one: rows 64 bytes apart)
+        kt.feed_image(img, "HISTOGRAM")
+        pyr = klt_ref.build_pyramid(np.ascontiguousarray(img), 3, "HISTOGRAM")
+        for lvl in range(3):
+            assert np.array_equal(kt.level(lvl), pyr[lvl])
+    assert np.array_equal(kt.equalized(), klt_ref.equalize_hist(np.ascontiguousarray(wide[:, 3:50])))
+    with pytest.raises(hiplib.OvpError) as e:
+        kt.feed_image(const, "CLAHE")
+    assert e.value.code == -1
+    kt.close()
+
+
+def test_refusals(hiplib, ctx):
+    sc = klt_cases.scene("subpixel_64x48")
+    L = hiplib.lib()
+    for bad in ((64, 48, 0, 15, 8), (64, 48, 9, 15, 8), (64, 48, 3, 14, 8), (64, 48, 3, 23, 8), (64, 48, 3, 15, 4097), (64, 48, 7, 15, 8)):
+        assert L.ovp_klt_create(ctx.handle, *bad) == -1, bad  # (the last one: a level smaller than 2 x 2)
+    kt = hiplib.KltTracker(ctx, 64, 48, 3, klt_cases.WIN, 64)
+    kt.feed_image(sc.img0, "NONE")
+    with pytest.raises(hiplib.OvpError) as e:
+        kt.track(sc.pts[:4])
+    assert e.value.code == -6  # OVP_E_STATE before the second image
+    kt.feed_image(sc.img1, "NONE")
+    p, st = kt.track(sc.pts[:64])
+    with pytest.raises(hiplib.OvpError) as e:
+        kt.track(sc.pts[:65])
+    assert e.value.code == -2  # OVP_E_CAPACITY
+    bad = sc.pts[:8].copy()
+    bad[5, 1] = np.nan
+    out, s = np.full((8, 2), 7.0, dtype=np.float32), np.full(8, 9, dtype=np.uint8)
+    assert L.ovp_klt_track(ctx.handle, 8, bad.ctypes.data, None, out.ctypes.data, s.ctypes.data) == -1
+    assert (out == 7.0).all() and (s == 9).all(), "a refused call wrote its outputs"
+    g = sc.pts[:8].copy()
+    g[0, 0] = np.inf
+    assert L.ovp_klt_track(ctx.handle, 8, sc.pts[:8].ctypes.data, g.ctypes.data, out.ctypes.data, s.ctypes.data) == -1
+    assert L.ovp_klt_track(ctx.handle, 0, None, None, None, None) == 0  # n = 0 returns at once
+    p2, st2 = kt.track(sc.pts[:64])
+    assert p.tobytes() == p2.tobytes() and st.tobytes() == st2.tobytes(), "a refused call left something behind"
+    kt.reset()
+    with pytest.raises(hiplib.OvpError) as e:
+        kt.track(sc.pts[:4])
+    assert e.value.code == -6
+    kt.close()
+    assert L.ovp_klt_feed_image(ctx.handle, sc.img0.ctypes.data, 64, 1) == -6  # OVP_E_STATE without ovp_klt_create
+
+
+def test_step_keeps_what_the_restatements_bookkeeping_keeps(hiplib, ctx):
+    q = klt_cases.sequence()
+    rt = klt_ref.RefTracker(q["width"], q["height"], q["levels"], klt_cases.WIN)
+    kt = hiplib.KltTracker(ctx, q["width"], q["height"], q["levels"], klt_cases.WIN, 64)
+    rt.step(q["frames"][0], q["mask"]), kt.step(q["frames"][0], q["mask"])
+    rt.add_points(q["ids"], q["pts"]), kt.add_points(q["ids"], q["pts"])
+    for k in (1, 2):
+        # the restatement starts every step from the points the device kept in the step before: one step's bound holds per step
+        rt.ids, rt.pts = kt.ids_last.copy(), kt.pts_last.copy()
+        rid, rp = rt.step(q["frames"][k], q["mask"])
+        gid, gp = kt.step(q["frames"][k], q["mask"])
+        print("frame %d: %d of %d points near a decision" % (k, rt.near.sum(), len(rt.near)))
+        assert rt.near.sum() <= 1  # (the cap of a scene below 50 points)
+        sure = rt.tracked_ids[~rt.near]
+        assert np.array_equal(gid[np.isin(gid, sure)], rid[np.isin(rid, sure)]), "frame %d" % k
+        assert np.abs(gp[np.isin(gid, rid)].astype(np.float64) - rp[np.isin(rid, gid)]).max() <= RESTATEMENT_PX
+    assert 112 not in gid and 113 not in gid and len(gid) == 12
+    kt.close()
+
+
+def test_cpp_mirror_equals_the_python_binding_bit_for_bit(hiplib, ctx):
+    """ov_plane::TrackPlane::feed_new_camera / add_points / perform_matching_klt through the harness entry, on the same three frames"""
+    from ov_plane_amd import hostlib
+    from ov_plane_amd.build import build_host
+
+    build_host()
+    q = klt_cases.sequence()
+    mirror = hostlib.run_klt_sequence(np.stack(q["frames"]), q["mask"], q["ids"], q["pts"], pyr_levels=q["levels"] - 1, win=klt_cases.WIN)
+    kt = hiplib.KltTracker(ctx, q["width"], q["height"], q["levels"], klt_cases.WIN, 64)
+    for k in range(3):
+        gid, gp = kt.step(q["frames"][k], q["mask"])
+        if k == 0:
+            kt.add_points(q["ids"], q["pts"])
+            gid, gp = kt.ids_last, kt.pts_last
+        mp, mm = kt.last_match
+        m = mirror[k]
+        assert np.array_equal(m["ids"], gid) and m["pts"].tobytes() == gp.tobytes(), "frame %d: kept points" % k
+        assert m["match_pts"].tobytes() == mp.tobytes() and m["match_mask"].tobytes() == mm.tobytes(), "frame %d: points and masks" % k
+    assert len(mirror[2]["ids"]) == 12 and len(mirror[1]["match_mask"]) == 14
+    kt.close()
+
+
+def test_contexts_are_independent(hiplib, ctx):
+    sc = klt_cases.scene("rot2_47x31")
+    other = klt_cases.scene("subpixel_64x48")
+    kt = _tracker(hiplib, ctx, sc)
+    p, st = kt.track(sc.pts)
+    kt.close()
+    kt = _tracker(hiplib, ctx, sc)  # destroyed and re-created inside one context
+    ctx2 = hiplib.Context(64, 4, 8)
+    kt2 = _tracker(hiplib, ctx2, other)  # a second context beside it, on another scene
+    p_o, st_o = kt2.track(other.pts)
+    p2, st2 = kt.track(sc.pts)
+    assert p.tobytes() == p2.tobytes() and st.tobytes() == st2.tobytes()
+    ref_p, ref_s, _ = other.reference(np.float64)
+    assert np.array_equal(st_o, ref_s) and np.abs(p_o.astype(np.float64) - ref_p).max() <= RESTATEMENT_PX
+    kt2.close()
+    ctx2.close()
+    kt.close()
