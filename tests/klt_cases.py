@@ -23,6 +23,15 @@ CLOSED_FORM_PX = {
 }
 # largest position difference between the restatement in float32 and in float64 over all scenes (status-1 points of both)
 F32_SPREAD_PX = 3.026e-05
+# the same per scene over the status-1 points outside near | near_stop, where that sets a sharper bound than F32_SPREAD_PX (not
+# trans12_752x480: its worst point is the one F32_SPREAD_PX records)
+SCENE_SPREAD_PX = {
+    "subpixel_64x48": 3.215e-06,
+    "rot2_47x31": 2.724e-06,
+    "scale5_96x64_l1": 3.533e-06,
+    "mixed3px_96x64": 2.327e-06,
+    "ramp3px_96x64": 4.404e-06,
+}
 
 
 def _mat3(a, b):
@@ -130,10 +139,10 @@ class Scene:
         return klt_ref.build_pyramid(self.img0, self.levels, self.hist), klt_ref.build_pyramid(self.img1, self.levels, self.hist)
 
     @functools.lru_cache(maxsize=None)
-    def reference(self, dtype=np.float64):
+    def reference(self, dtype=np.float64, win=WIN):
         """(pts, status, report) of the restatement, computed once and shared (do not write into it)"""
-        p, s, r = klt_ref.lk_track(*self.pyramids, self.pts, self.guess, WIN, dtype)
-        for a in (p, s, r["near"], r["iters"]):
+        p, s, r = klt_ref.lk_track(*self.pyramids, self.pts, self.guess, win, dtype)
+        for a in (p, s, *r.values()):
             a.setflags(write=False)
         return p, s, r
 
@@ -151,8 +160,178 @@ SMALL = NAMES[:-1]
 
 
 @functools.lru_cache(maxsize=None)
-def scene(name):
-    return Scene(**next(s for s in SPECS if s["name"] == name))
+def scene(name, levels=None):
+    """the scene of that name; levels: the same images and points under a pyramid of another depth"""
+    spec = next(s for s in SPECS if s["name"] == name)
+    return Scene(**(spec if levels is None else dict(spec, levels=levels)))
+
+
+# ---- window cases: (scene, levels, win[, points]) - every odd width 3..21, at least three cases per k_klt_track instantiation
+# (<1>: 3 5 7, <2>: 9 11, <4>: 13 15, <7>: 17 19 21), every width on two scenes.  A case is in the table only if it holds the caps
+# test_klt_cpu.py checks on the float64 restatement (near and near_stop at most 2 % of its points, 1 below 50; float32 equal to
+# float64 in status outside near and in iterations outside near | near_stop).  Not in it for that reason: subpixel_64x48 at
+# three levels with win 3, 5, 9, 13, 17, 19, rot2_47x31 at five levels with win 3, 5, mixed3px_96x64 at four levels with win 7, 9, 19 and at three with win 7,
+# ramp3px_96x64 with win 3.  rot2_47x31 at five levels has a 3 x 2 top level, subpixel_64x48 at six levels a 2 x 2 one: levels smaller
+# than any window, where every read wraps several times.  Under six levels most points of subpixel_64x48 wander for 30 iterations
+# over the 2 x 2 and 4 x 3 levels and a quarter of them end where the number format decides; those cases take the listed points,
+# on which the float64 run, the float32 run and a float32 run that sums the window in reverse order agree in status and iterations
+# (win 3: less point 64, whose float32 and float64 flows enter level 0 3e-5 px apart), and of those the ones no level of which runs
+# out its 30 iterations: every such level there still moves 0.2 to 2.3 px per step on a 4 x 3 or 2 x 2 image, and the flow it hands
+# down is rounding's (on the device three such points ran one iteration more or less at the level below, positions equal).
+# Exhausted levels are covered by the whole-scene cases: mixed3px_96x64, rot2_47x31 and ramp3px_96x64 at five levels (6 x 4 top).
+_DEEP_W3 = [0, 1, 5, 8, 9, 11, 12, 15, 16, 19, 20, 21, 23, 26, 27, 29, 30, 31, 32, 33, 36, 37, 38, 39, 40, 41, 42, 43, 47, 48, 49, 50, 52,
+            53, 54, 62, 63]
+_DEEP_W9 = [0, 1, 2, 4, 5, 8, 9, 10, 11, 12, 15, 16, 19, 20, 21, 30, 31, 33, 34, 35, 36, 37, 38, 39, 40, 42, 45, 48, 49, 52, 53, 54, 55,
+            57, 59, 60, 61, 63, 64]
+_DEEP_W13 = [0, 1, 2, 4, 5, 8, 9, 10, 11, 12, 16, 19, 20, 21, 31, 33, 34, 37, 38, 42, 44, 45, 48, 49, 52, 53, 54, 55, 57, 59, 60, 61, 63,
+             64]  # (and less the four points that leave the 4 x 3 level: one of them does so after 17 steps of over 2 px)
+_DEEP_W21 = [0, 1, 2, 4, 5, 8, 9, 11, 12, 15, 16, 19, 20, 21, 24, 30, 31, 33, 36, 37, 38, 40, 41, 42, 44, 45, 48, 49, 52, 53, 54, 55, 57,
+             59, 63, 64]
+WINDOW_CASES = [
+    # <1>
+    ("mixed3px_96x64", 4, 3), ("scale5_96x64_l1", 1, 3), ("subpixel_64x48", 6, 3, _DEEP_W3),
+    ("mixed3px_96x64", 4, 5), ("rot2_47x31", 3, 5), ("ramp3px_96x64", 3, 5),
+    ("subpixel_64x48", 3, 7), ("rot2_47x31", 5, 7), ("ramp3px_96x64", 3, 7),
+    # <2>
+    ("rot2_47x31", 5, 9), ("mixed3px_96x64", 3, 9), ("ramp3px_96x64", 5, 9), ("subpixel_64x48", 6, 9, _DEEP_W9),
+    ("mixed3px_96x64", 4, 11), ("rot2_47x31", 5, 11), ("subpixel_64x48", 3, 11),
+    # <4> (win 13: three live slots of four)
+    ("mixed3px_96x64", 4, 13), ("rot2_47x31", 5, 13), ("ramp3px_96x64", 3, 13), ("ramp3px_96x64", 5, 13), ("subpixel_64x48", 6, 13, _DEEP_W13),
+    ("mixed3px_96x64", 4, 15), ("subpixel_64x48", 3, 15), ("rot2_47x31", 5, 15),
+    # <7> (win 17, 19: five and six live slots of seven)
+    ("mixed3px_96x64", 4, 17), ("rot2_47x31", 5, 17), ("ramp3px_96x64", 5, 17),
+    ("mixed3px_96x64", 3, 19), ("rot2_47x31", 5, 19), ("ramp3px_96x64", 3, 19),
+    ("mixed3px_96x64", 4, 21), ("rot2_47x31", 5, 21), ("subpixel_64x48", 6, 21, _DEEP_W21),
+]
+CASE_IDS = ["%s-L%d-w%d" % c[:3] for c in WINDOW_CASES]
+# worst float32 - float64 position difference of the restatement over a case's status-1 points outside near | near_stop (measured on
+# the CPU; test_klt_cpu.py re-measures each to within +0.1 % / -5 %).  The GPU test allows four times it.
+SPREAD_PX = {
+    "mixed3px_96x64-L4-w3": 5.887e-06,  # 40 points, 0 near, 0 near_stop
+    "scale5_96x64_l1-L1-w3": 4.054e-06,  # 30 points, 0 near, 0 near_stop
+    "subpixel_64x48-L6-w3": 5.688e-06,  # 37 points, 0 near, 1 near_stop
+    "mixed3px_96x64-L4-w5": 8.008e-06,  # 40 points, 0 near, 1 near_stop
+    "rot2_47x31-L3-w5": 4.283e-06,  # 20 points, 1 near, 0 near_stop
+    "ramp3px_96x64-L3-w5": 4.532e-06,  # 30 points, 1 near, 1 near_stop
+    "subpixel_64x48-L3-w7": 2.873e-06,  # 65 points, 0 near, 0 near_stop
+    "rot2_47x31-L5-w7": 2.426e-06,  # 20 points, 0 near, 1 near_stop
+    "ramp3px_96x64-L3-w7": 4.687e-06,  # 30 points, 1 near, 0 near_stop
+    "rot2_47x31-L5-w9": 2.086e-06,  # 20 points, 0 near, 0 near_stop
+    "mixed3px_96x64-L3-w9": 3.775e-06,  # 40 points, 1 near, 0 near_stop
+    "ramp3px_96x64-L5-w9": 4.026e-06,  # 30 points, 1 near, 0 near_stop
+    "subpixel_64x48-L6-w9": 2.222e-06,  # 39 points, 0 near, 0 near_stop
+    "mixed3px_96x64-L4-w11": 3.555e-06,  # 40 points, 0 near, 0 near_stop
+    "rot2_47x31-L5-w11": 1.752e-06,  # 20 points, 0 near, 1 near_stop
+    "subpixel_64x48-L3-w11": 2.805e-06,  # 65 points, 1 near, 1 near_stop
+    "mixed3px_96x64-L4-w13": 3.173e-06,  # 40 points, 0 near, 0 near_stop
+    "rot2_47x31-L5-w13": 2.289e-06,  # 20 points, 0 near, 0 near_stop
+    "ramp3px_96x64-L3-w13": 3.903e-06,  # 30 points, 0 near, 0 near_stop
+    "ramp3px_96x64-L5-w13": 4.083e-06,  # 30 points, 1 near, 0 near_stop
+    "subpixel_64x48-L6-w13": 2.927e-06,  # 34 points, 0 near, 0 near_stop
+    "mixed3px_96x64-L4-w15": 2.327e-06,  # 40 points, 0 near, 0 near_stop
+    "subpixel_64x48-L3-w15": 3.215e-06,  # 65 points, 0 near, 1 near_stop
+    "rot2_47x31-L5-w15": 1.347e-06,  # 20 points, 0 near, 1 near_stop
+    "mixed3px_96x64-L4-w17": 3.093e-06,  # 40 points, 0 near, 0 near_stop
+    "rot2_47x31-L5-w17": 2.063e-06,  # 20 points, 0 near, 0 near_stop
+    "ramp3px_96x64-L5-w17": 5.695e-06,  # 30 points, 0 near, 1 near_stop
+    "mixed3px_96x64-L3-w19": 4.295e-06,  # 40 points, 0 near, 0 near_stop
+    "rot2_47x31-L5-w19": 1.267e-06,  # 20 points, 0 near, 0 near_stop
+    "ramp3px_96x64-L3-w19": 5.488e-06,  # 30 points, 0 near, 1 near_stop
+    "mixed3px_96x64-L4-w21": 3.362e-06,  # 40 points, 0 near, 0 near_stop
+    "rot2_47x31-L5-w21": 1.138e-06,  # 20 points, 0 near, 0 near_stop
+    "subpixel_64x48-L6-w21": 2.723e-06,  # 36 points, 0 near, 0 near_stop
+}
+
+
+@functools.lru_cache(maxsize=None)
+def case(case_id):
+    return Case(*WINDOW_CASES[CASE_IDS.index(case_id)])
+
+
+def instantiation(win):
+    """window pixels per lane of the k_klt_track instantiation ovp_klt_track dispatches a window width to"""
+    npl = (win * win + 63) // 64
+    return 1 if npl <= 1 else 2 if npl <= 2 else 4 if npl <= 4 else 7
+
+
+def near_cap(n):
+    """the points of a case that may sit near a decision: 2 %, 1 point below 50 points"""
+    return int(0.02 * n) if n >= 50 else 1
+
+
+class Case:
+    """a window case: a small scene under a pyramid depth and a window width of its own, all of its points or a subset"""
+
+    def __init__(self, name, levels, win, points=None):
+        self.scene, self.levels, self.win = scene(name, levels), levels, win
+        self.id = "%s-L%d-w%d" % (name, levels, win)
+        sc = self.scene
+        self.idx = np.arange(len(sc.pts)) if points is None else np.asarray(points)
+        self.pts = sc.pts[self.idx]
+        self.guess = None if sc.guess is None else sc.guess[self.idx]
+        self.width, self.height, self.hist, self.img0, self.img1 = sc.width, sc.height, sc.hist, sc.img0, sc.img1
+
+    @property
+    def pyramids(self):
+        return self.scene.pyramids
+
+    @functools.lru_cache(maxsize=None)
+    def reference(self, dtype=np.float64):
+        """(pts, status, report) of the restatement, computed once and shared (do not write into it)"""
+        p, s, r = klt_ref.lk_track(*self.pyramids, self.pts, self.guess, self.win, dtype)
+        for a in (p, s, *r.values()):
+            a.setflags(write=False)
+        return p, s, r
+
+
+def compare(case, p, st, iters):
+    """what the GPU test asserts of a run (p [n, 2], st [n], iters [n, levels]) of a window case against the float64 restatement:
+    status outside `near`, iterations outside `near | near_stop`, positions of status-1 points within 4 x SPREAD_PX[case] outside
+    `near | near_stop` and within 2 x STOP_EPS on `near_stop` points.  Returns dict(failures [str], worst, bound, excluded)."""
+    ref_p, ref_s, rep = case.reference(np.float64)
+    near, ns = rep["near"], rep["near_stop"] & ~rep["near"]
+    sure = ~near & ~ns
+    fails = []
+    if not np.array_equal(np.asarray(st)[~near], ref_s[~near]):
+        fails.append("status differs on points %s" % np.nonzero((np.asarray(st) != ref_s) & ~near)[0].tolist())
+    bad_it = (np.asarray(iters) != rep["iters"]).any(axis=1) & sure
+    if bad_it.any():
+        fails.append("iterations differ on points %s" % "; ".join("%d: %s for %s (|delta| ended %s)" % (
+            i, np.asarray(iters)[i].tolist(), rep["iters"][i].tolist(), np.round(rep["dnorm"][i], 5).tolist()) for i in np.nonzero(bad_it)[0]))
+    err = np.abs(np.asarray(p, dtype=np.float64) - ref_p).max(axis=1)
+    ok = (np.asarray(st) == 1) & (ref_s == 1)
+    bound = 4 * SPREAD_PX[case.id]
+    worst = float(err[ok & sure].max()) if (ok & sure).any() else 0.0
+    worst_ns = float(err[ok & ns].max()) if (ok & ns).any() else 0.0
+    if not worst <= bound:
+        fails.append("position %.3e px off, bound %.3e" % (worst, bound))
+    if not worst_ns <= 2 * klt_ref.STOP_EPS:
+        fails.append("position of a point near the stop threshold %.3e px off, bound %.3e" % (worst_ns, 2 * klt_ref.STOP_EPS))
+    return dict(failures=fails, worst=worst, bound=bound, worst_near_stop=worst_ns, near=np.nonzero(near)[0].tolist(),
+                near_stop=np.nonzero(ns)[0].tolist())
+
+
+@functools.lru_cache(maxsize=None)
+def image_cases():
+    """the images the GPU test of the image kernels uploads: {id: (image, levels)} - the regimes of k_klt_hist / k_klt_equalize
+    (16-byte body, tail of block 0, grid cap of 256 blocks of 256 lanes of 16 pixels) and the histogram's edges"""
+    rng = np.random.default_rng(17)
+    rnd = lambda w, h: rng.integers(0, 256, size=(h, w)).astype(np.uint8)  # noqa: E731
+    one = np.full((7, 9), 100, dtype=np.uint8)
+    one[3, 4] = 200
+    return {
+        "4x3_tail_only": (rnd(4, 3), 1),
+        "4x4_no_tail": (rnd(4, 4), 1),
+        "15x17": (rnd(15, 17), 1),
+        "1039x1011_grid_cap": (rnd(1039, 1011), 1),           # 1 050 429 pixels: more than 256 x 256 x 16, 13 in the tail
+        "all_equal_but_one": (one, 1),                        # total - hist[first] == 1
+        "constant_255": (np.full((5, 8), 255, dtype=np.uint8), 1),
+        "constant_0": (np.zeros((5, 8), dtype=np.uint8), 1),
+        "only_0_and_255": (np.where(rng.random((11, 13)) < 0.3, 0, 255).astype(np.uint8), 1),
+        "first_bin_254": (np.where(rng.random((11, 13)) < 0.6, 254, 255).astype(np.uint8), 1),
+        "47x31_to_3x2": (scene("rot2_47x31").img0, 5),
+        "64x48_to_2x2": (scene("subpixel_64x48").img0, 6),
+    }
 
 
 @functools.lru_cache(maxsize=None)

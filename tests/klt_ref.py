@@ -15,6 +15,7 @@ SCHARR_NORM = 32.0
 MAX_ITERS = 30                  # term_crit (TrackPlane.cpp:1328): COUNT 30 ...
 STOP_EPS = 0.01                 # ... + EPS 0.01, compared as |delta|^2 <= STOP_EPS^2
 OSC_EPS = 0.01                  # from the second iteration on: |delta + delta_prev| < OSC_EPS in both axes -> back by delta / 2
+OSC_FROM, OSC_BACK = 1, 0.5     # (the second iteration is index 1; the back-step is OSC_BACK x delta)
 MIN_EIG_THRESHOLD = 1e-4        # calcOpticalFlowPyrLK's default minEigThreshold
 GATE_SCALE = 1024.0             # OpenCV's fixed-point scale: A = G / GATE_SCALE, minEig = lambda_min(A) / w^2, det(A) < FLT_EPSILON
 FLT_EPSILON = float(np.finfo(np.float32).eps)
@@ -27,6 +28,40 @@ NEAR_GATE_REL = 0.01
 NEAR_CORNER_PX = 1e-3
 NEAR_OSC = 1e-4
 NEAR_KEEP_PX = 1e-3
+# |delta| / STOP_EPS within NEAR_STOP_REL of 1 at some iteration: the stop decision may fall either way in another arithmetic.
+# NEAR_STOP_MEASURED is the largest float32 - float64 difference of |delta| / STOP_EPS at the iteration that stopped level 0, over
+# the status-1 points outside `near` of the window cases of tests/klt_cases.py whose iteration counts agree (level 0: both runs
+# enter it with the same flow to within the position spread; above it a wandering point's differing entry flow, not the
+# arithmetic, sets the difference - up to 0.38 there).  Times 4 for a summation order other than numpy's, as the position bound has
+# it.  tests/test_klt_cpu.py re-measures it.
+NEAR_STOP_MEASURED = 1.145e-3
+NEAR_STOP_REL = 4 * NEAR_STOP_MEASURED
+
+
+def _corner_floor(x):
+    """a window corner's integer part: floor, not truncation (a negative corner rounds down)"""
+    return np.floor(x)
+
+
+def _top_scale(top, T):
+    """the initial flow is guess / 2^top at the top level"""
+    return T(1.0 / (1 << top))
+
+
+def _window(win):
+    """(rows, cols) of the window's pixels, row-major: pixel k is row k / win, column k % win, k < win^2 (on the device lane + 64 j)"""
+    k = np.arange(win * win)
+    return k // win, k % win
+
+
+def _window_cur(win):
+    """the same pixels where the current image is read in the iterations (one layout, two sites on the device)"""
+    return _window(win)
+
+
+def _lut_round(x):
+    """cv::saturate_cast<uchar>(float): to nearest, ties to even"""
+    return np.rint(x)
 
 
 def reflect101(i, n):
@@ -53,7 +88,7 @@ def equalize_hist(img):
     s = 0
     for i in range(first + 1, 256):
         s += int(hist[i])
-        lut[i] = np.uint8(min(255.0, float(np.rint(np.float32(s) * scale))))
+        lut[i] = np.uint8(min(255.0, float(_lut_round(np.float32(s) * scale))))
     return lut[img]
 
 
@@ -98,12 +133,11 @@ def scharr(img, T):
     return (sx(xp) - sx(xm)) / T(SCHARR_NORM), (sy(yp) - sy(ym)) / T(SCHARR_NORM)
 
 
-def _bilinear(read, ix, iy, a, b, win, T):
-    """[m, win, win] samples of `read(xi, yi)` at (ix + c + a, iy + r + b)"""
-    r = np.arange(win)
-    X = ix[:, None, None] + r[None, None, :] + np.zeros((1, win, 1), dtype=np.int64)
-    Y = iy[:, None, None] + r[None, :, None] + np.zeros((1, 1, win), dtype=np.int64)
-    a, b = a[:, None, None], b[:, None, None]
+def _bilinear(read, ix, iy, a, b, pix, T):
+    """[m, len(pix)] samples of `read(xi, yi)` at (ix + c + a, iy + r + b) for the window pixels pix = (r, c)"""
+    X = ix[:, None] + pix[1][None, :]
+    Y = iy[:, None] + pix[0][None, :]
+    a, b = a[:, None], b[:, None]
     one = T(1)
     w00, w01, w10, w11 = (one - a) * (one - b), a * (one - b), (one - a) * b, a * b
     return w00 * read(X, Y) + w01 * read(X + 1, Y) + w10 * read(X, Y + 1) + w11 * read(X + 1, Y + 1)
@@ -135,10 +169,32 @@ def _near_corner(c, win, cols, rows):
     return (np.abs(c[:, None, :] - lim[None, :, :]) < NEAR_CORNER_PX).any(axis=(1, 2))
 
 
+def _border_grad(ip, a, b, pix, cols, rows):
+    """[m] bool: a gradient read of the window at corner ip + (a, b) falls outside the level with a non-zero bilinear weight"""
+    X, Y = ip[:, 0, None] + pix[1][None, :], ip[:, 1, None] + pix[0][None, :]
+    ox0, ox1, oy0, oy1 = (X < 0) | (X >= cols), (X + 1 < 0) | (X + 1 >= cols), (Y < 0) | (Y >= rows), (Y + 1 < 0) | (Y + 1 >= rows)
+    pa, pb = (a > 0)[:, None], (b > 0)[:, None]
+    return ((ox0 | oy0) | (pa & (ox1 | oy0)) | (pb & (ox0 | oy1)) | (pa & pb & (ox1 | oy1))).any(axis=1)
+
+
+def _neg_corner(c, fl):
+    """[m] bool: a coordinate of the corner c is negative and no integer - floor and truncation differ"""
+    return ((c < 0) & (c != fl)).any(axis=1)
+
+
 def lk_track(pyr_prev, pyr_cur, pts_prev, guess=None, win=15, dtype=np.float64):
     """cv::calcOpticalFlowPyrLK(pyr_prev, pyr_cur, pts_prev, guess, OPTFLOW_USE_INITIAL_FLOW) for every point at once.
     Returns (pts [n, 2] dtype, status [n] uint8, report) with report = dict(near [n] bool: a gated quantity of the point sat near its
-    threshold at some level, iters [n, levels] iterations run per level, level 0 first)."""
+    threshold at some level, iters [n, levels] iterations run per level, level 0 first) and what the run did, per point:
+      near_stop [n] bool        |delta| / STOP_EPS within NEAR_STOP_REL of 1 at some iteration
+      osc [n] int               back-steps taken
+      exhausted [n] bool        a level ran MAX_ITERS iterations and neither the stop nor the back-step ended it
+      gate_upper, gate_l0       the texture gate failed above / at level 0
+      left_upper, left_l0       the window rule failed above / at level 0 (at the point's own window or in the iterations)
+      left_in_loop              the window rule failed inside the iteration loop
+      neg_corner                a window corner with a negative non-integer coordinate was floored
+      border_grad               a gradient read outside a level returned zero with a non-zero bilinear weight
+      dnorm [n, levels] f64     |delta| of the last iteration a level ran (nan where it ran none)"""
     T = dtype
     pts_prev = np.asarray(pts_prev, dtype=np.float32).reshape(-1, 2)
     guess = pts_prev if guess is None else np.asarray(guess, dtype=np.float32).reshape(-1, 2)
@@ -148,11 +204,17 @@ def lk_track(pyr_prev, pyr_cur, pts_prev, guess=None, win=15, dtype=np.float64):
     status = alive.astype(np.uint8)
     near = np.zeros(n, dtype=bool)
     iters = np.zeros((n, nl), dtype=np.int32)
+    flags = {k: np.zeros(n, dtype=bool) for k in ("near_stop", "exhausted", "gate_upper", "gate_l0", "left_upper", "left_l0",
+                                                   "left_in_loop", "neg_corner", "border_grad")}
+    n_osc = np.zeros(n, dtype=np.int32)
+    dnorm = np.full((n, nl), np.nan)
+    pix, pix_cur = _window(win), _window_cur(win)
     P = np.where(alive[:, None], pts_prev, 0).astype(T)
     with np.errstate(over="ignore", invalid="ignore"):
-        g = np.where(alive[:, None], guess, 0).astype(T) * T(1.0 / (1 << top))
+        g = np.where(alive[:, None], guess, 0).astype(T) * _top_scale(top, T)
     half = T((win - 1) * 0.5)
     for lvl in range(top, -1, -1):
+        gate_f, left_f = (flags["gate_l0"], flags["left_l0"]) if lvl == 0 else (flags["gate_upper"], flags["left_upper"])
         with np.errstate(over="ignore", invalid="ignore"):
             if lvl != top:
                 g = g * T(2)
@@ -161,25 +223,29 @@ def lk_track(pyr_prev, pyr_cur, pts_prev, guess=None, win=15, dtype=np.float64):
         pw = P * T(1.0 / (1 << lvl)) - half
         ins = _inside(pw, win, cols, rows)
         near |= alive & _near_corner(pw, win, cols, rows)
+        left_f |= alive & ~ins
         if lvl == 0:
             status[alive & ~ins] = 0
         act = np.nonzero(alive & ins)[0]
         if len(act) == 0:
             continue
         gx, gy = scharr(I8, T)
-        fl = np.floor(pw[act])
+        fl = _corner_floor(pw[act])
         ip = fl.astype(np.int64)
         a, b = (pw[act] - fl)[:, 0], (pw[act] - fl)[:, 1]
-        Iw = _bilinear(_img_reader(I8, T), ip[:, 0], ip[:, 1], a, b, win, T)
-        Ix = _bilinear(_grad_reader(gx), ip[:, 0], ip[:, 1], a, b, win, T)
-        Iy = _bilinear(_grad_reader(gy), ip[:, 0], ip[:, 1], a, b, win, T)
+        flags["neg_corner"][act] |= _neg_corner(pw[act], np.floor(pw[act]))
+        flags["border_grad"][act] |= _border_grad(ip, a, b, pix, cols, rows)
+        Iw = _bilinear(_img_reader(I8, T), ip[:, 0], ip[:, 1], a, b, pix, T)
+        Ix = _bilinear(_grad_reader(gx), ip[:, 0], ip[:, 1], a, b, pix, T)
+        Iy = _bilinear(_grad_reader(gy), ip[:, 0], ip[:, 1], a, b, pix, T)
         sc = T(1.0 / GATE_SCALE)
-        A11, A12, A22 = (Ix * Ix).sum(axis=(1, 2)) * sc, (Ix * Iy).sum(axis=(1, 2)) * sc, (Iy * Iy).sum(axis=(1, 2)) * sc
+        A11, A12, A22 = (Ix * Ix).sum(axis=1) * sc, (Ix * Iy).sum(axis=1) * sc, (Iy * Iy).sum(axis=1) * sc
         D = A11 * A22 - A12 * A12
         min_eig = (A22 + A11 - np.sqrt((A11 - A22) * (A11 - A22) + T(4) * A12 * A12)) / T(2 * win * win)
         bad = (min_eig < T(MIN_EIG_THRESHOLD)) | (D < T(FLT_EPSILON))
         near[act] |= (np.abs(min_eig.astype(np.float64) / MIN_EIG_THRESHOLD - 1) < NEAR_GATE_REL) | \
                      (np.abs(D.astype(np.float64) / FLT_EPSILON - 1) < NEAR_GATE_REL)
+        gate_f[act[bad]] = True
         if lvl == 0:
             status[act[bad]] = 0
         keep = ~bad
@@ -194,6 +260,8 @@ def lk_track(pyr_prev, pyr_cur, pts_prev, guess=None, win=15, dtype=np.float64):
             ins = _inside(v, win, cols, rows)
             near[act[run]] |= _near_corner(v[run], win, cols, rows)
             out = run & ~ins
+            left_f[act[out]] = True
+            flags["left_in_loop"][act[out]] = True
             if lvl == 0:
                 status[act[out]] = 0
             run = run & ins
@@ -201,24 +269,32 @@ def lk_track(pyr_prev, pyr_cur, pts_prev, guess=None, win=15, dtype=np.float64):
             if len(k) == 0:
                 break
             iters[act[k], lvl] += 1
-            fl = np.floor(v[k])
+            fl = _corner_floor(v[k])
             iq = fl.astype(np.int64)
-            Jw = _bilinear(Jr, iq[:, 0], iq[:, 1], (v[k] - fl)[:, 0], (v[k] - fl)[:, 1], win, T)
+            flags["neg_corner"][act[k]] |= _neg_corner(v[k], np.floor(v[k]))
+            Jw = _bilinear(Jr, iq[:, 0], iq[:, 1], (v[k] - fl)[:, 0], (v[k] - fl)[:, 1], pix_cur, T)
             diff = Jw - Iw[k]
-            b1, b2 = (diff * Ix[k]).sum(axis=(1, 2)) * sc, (diff * Iy[k]).sum(axis=(1, 2)) * sc
+            b1, b2 = (diff * Ix[k]).sum(axis=1) * sc, (diff * Iy[k]).sum(axis=1) * sc
             d = np.stack([(A12[k] * b2 - A22[k] * b1) / D[k], (A12[k] * b1 - A11[k] * b2) / D[k]], axis=1)
             v[k] = v[k] + d
             stop = (d * d).sum(axis=1) <= T(STOP_EPS * STOP_EPS)
+            dn = np.sqrt((d.astype(np.float64) ** 2).sum(axis=1))
+            dnorm[act[k], lvl] = dn
+            with np.errstate(invalid="ignore"):
+                flags["near_stop"][act[k]] |= np.abs(dn / STOP_EPS - 1) < NEAR_STOP_REL
             s = np.abs(d + pd[k])
-            osc = (j > 0) & ~stop & (s[:, 0] < T(OSC_EPS)) & (s[:, 1] < T(OSC_EPS))
-            if j > 0:
+            osc = (j >= OSC_FROM) & ~stop & (s[:, 0] < T(OSC_EPS)) & (s[:, 1] < T(OSC_EPS))
+            if j >= OSC_FROM:
                 # (the test is max(|sx|, |sy|) < OSC_EPS: that maximum is what sits near the threshold or does not)
                 near[act[k]] |= ~stop & (np.abs(s.astype(np.float64).max(axis=1) - OSC_EPS) < NEAR_OSC)
-            v[k[osc]] = v[k[osc]] - d[osc] * T(0.5)
+            v[k[osc]] = v[k[osc]] - d[osc] * T(OSC_BACK)
+            n_osc[act[k[osc]]] += 1
             pd[k] = d
             run[k[stop | osc]] = False
+        else:
+            flags["exhausted"][act[run]] = True
         g[act] = v + half
-    return g, status, dict(near=near, iters=iters)
+    return g, status, dict(near=near, iters=iters, osc=n_osc, dnorm=dnorm, **flags)
 
 
 def keep_rule(pts, status, cols, rows, mask=None):

@@ -5,7 +5,12 @@ of step(), and the independence of contexts.
 Bounds: position against the restatement min(4 x F32_SPREAD_PX, 0.02 px) - the float32 spread of the restatement itself, four
 times for a summation order other than numpy's, capped at two stopping steps; against the closed form the per-scene figure the CPU
 test measured (klt_cases.CLOSED_FORM_PX) plus that bound.  Status: identical except on points the restatement flags near a
-decision (at most 2 % of a scene, test_klt_cpu.py)."""
+decision (at most 2 % of a scene, test_klt_cpu.py).
+
+Window cases (klt_cases.WINDOW_CASES: every odd window 3..21, so all four k_klt_track instantiations, pyramids down to 3 x 2 and
+2 x 2): status outside `near`, iterations per level outside `near | near_stop`, positions within four times the case's own float32
+spread (klt_cases.SPREAD_PX) and within 2 x STOP_EPS = 0.02 px on `near_stop` points - klt_cases.compare, the comparison the
+mutants of test_klt_cpu.py are shown to fail."""
 import os
 import sys
 
@@ -59,6 +64,15 @@ def test_scene(hiplib, ctx, name):
         name, d_ref, RESTATEMENT_PX, d_cf, klt_cases.CLOSED_FORM_PX[name] + RESTATEMENT_PX))
     assert d_ref <= RESTATEMENT_PX
     assert d_cf <= klt_cases.CLOSED_FORM_PX[name] + RESTATEMENT_PX
+    # iterations per level, and the scene's own spread where one is recorded, outside near | near_stop
+    sure = ~(near | rep["near_stop"])
+    print("%s: %d points near the stop threshold left out of the iteration comparison: %s" % (
+        name, (rep["near_stop"] & ~near).sum(), np.nonzero(rep["near_stop"] & ~near)[0].tolist()))
+    assert np.array_equal(kt.iters(len(sc.pts))[sure], rep["iters"][sure])
+    if name in klt_cases.SCENE_SPREAD_PX:
+        d_sure = float(np.abs(p[ok & sure].astype(np.float64) - ref_p[ok & sure]).max())
+        print("%s: worst |device - restatement| outside near | near_stop %.3e px (bound %.3e)" % (name, d_sure, 4 * klt_cases.SCENE_SPREAD_PX[name]))
+        assert d_sure <= 4 * klt_cases.SCENE_SPREAD_PX[name]
     # determinism; guess = None is guess = pts_prev
     p2, st2 = kt.track(sc.pts, sc.guess)
     assert p.tobytes() == p2.tobytes() and st.tobytes() == st2.tobytes()
@@ -74,6 +88,80 @@ def test_scene(hiplib, ctx, name):
     kt.feed_image(sc.img0, sc.hist)
     for lvl in range(sc.levels):
         assert np.array_equal(kt.level(lvl, "prev"), pyr1[lvl]) and np.array_equal(kt.level(lvl, "cur"), pyr0[lvl])
+    kt.close()
+
+
+def _case_tracker(hiplib, ctx, c, max_points=256):
+    kt = hiplib.KltTracker(ctx, c.width, c.height, c.levels, c.win, max_points)
+    kt.feed_image(c.img0, c.hist)
+    kt.feed_image(c.img1, c.hist)
+    return kt
+
+
+@pytest.mark.parametrize("cid", klt_cases.CASE_IDS)
+def test_window_case(hiplib, ctx, cid):
+    c = klt_cases.case(cid)
+    pyr0, pyr1 = c.pyramids
+    kt = _case_tracker(hiplib, ctx, c)
+    for lvl in range(c.levels):
+        assert np.array_equal(kt.level(lvl, "prev"), pyr0[lvl]), "previous half, level %d" % lvl
+        assert np.array_equal(kt.level(lvl, "cur"), pyr1[lvl]), "current half, level %d" % lvl
+    p, st = kt.track(c.pts, c.guess)
+    it = kt.iters(len(c.pts))
+    res = klt_cases.compare(c, p, st, it)
+    print("%s <%d>: near %s, near_stop %s left out; worst |device - restatement| %.3e px of %.3e (%.2f), on near_stop points %.3e of %.3e" % (
+        cid, klt_cases.instantiation(c.win), res["near"], res["near_stop"], res["worst"], res["bound"], res["worst"] / res["bound"],
+        res["worst_near_stop"], 2 * klt_ref.STOP_EPS))
+    assert not res["failures"], res["failures"]
+    p2, st2 = kt.track(c.pts, c.guess)
+    assert p.tobytes() == p2.tobytes() and st.tobytes() == st2.tobytes() and it.tobytes() == kt.iters(len(c.pts)).tobytes()
+    kt.close()
+
+
+def test_a_second_create_replaces_the_tracker(hiplib, ctx):
+    a, b = klt_cases.case("mixed3px_96x64-L4-w21"), klt_cases.case("rot2_47x31-L3-w5")
+    run = lambda kt, c: kt.track(c.pts, c.guess) + (kt.iters(len(c.pts)),)  # noqa: E731
+    ra = run(_case_tracker(hiplib, ctx, a), a)
+    rb = run(_case_tracker(hiplib, ctx, b), b)   # (no destroy in between: another window, size and depth in the same context)
+    ctx2 = hiplib.Context(64, 4, 8)
+    kt2 = _case_tracker(hiplib, ctx2, b)
+    rf = run(kt2, b)
+    kt2.close()
+    ctx2.close()
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(rb, rf)), "the replacing tracker differs from a fresh context's"
+    assert not klt_cases.compare(b, *rb)["failures"]
+    kt = _case_tracker(hiplib, ctx, a)
+    ra2 = run(kt, a)
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(ra, ra2)), "back at window 21 the first result is not reproduced"
+    kt.close()
+
+
+def test_capacity_every_copy_carries_the_small_calls_bits(hiplib, ctx):
+    c = klt_cases.case("mixed3px_96x64-L4-w5")
+    m, n = len(c.pts), 4096
+    kt = _case_tracker(hiplib, ctx, c, max_points=n)
+    p, st = kt.track(c.pts, c.guess)
+    it = kt.iters(m)
+    rep = np.arange(n) % m
+    pb, sb = kt.track(c.pts[rep], c.guess[rep])
+    ib = kt.iters(n)
+    assert pb.tobytes() == p[rep].tobytes() and sb.tobytes() == st[rep].tobytes() and ib.tobytes() == it[rep].tobytes()
+    kt.close()
+
+
+@pytest.mark.parametrize("key", list(klt_cases.image_cases()))
+def test_image_kernels(hiplib, ctx, key):
+    img, levels = klt_cases.image_cases()[key]
+    h, w = img.shape
+    kt = hiplib.KltTracker(ctx, w, h, levels, 3, 1)
+    for hist in ("HISTOGRAM", "NONE"):
+        kt.feed_image(img, hist)
+        pyr = klt_ref.build_pyramid(img, levels, hist)
+        for lvl in range(levels):
+            assert np.array_equal(kt.level(lvl), pyr[lvl]), "%s, level %d" % (hist, lvl)
+        if hist == "HISTOGRAM":
+            assert np.array_equal(kt.equalized(), klt_ref.equalize_hist(img))
+    assert kt.level(levels - 1).shape == ((h - 1 >> levels - 1) + 1, (w - 1 >> levels - 1) + 1)
     kt.close()
 
 
