@@ -932,7 +932,8 @@ long ovp_active_tracks_debug(ovp_ctx *ctx, const char *what, int64_t id, double 
  * cv::calcOpticalFlowPyrLK call of perform_matching (:1299-1357).  OpenCV is not in the reference tree: the stage is restated from
  * its published form (Bouguet's pyramidal Lucas-Kanade with OpenCV's externally visible conventions: Scharr gradients, reflect-101
  * image borders, zero gradient borders, 30 iterations / 0.01 px, minEigThreshold 1e-4) and is UNPINNED; tests/klt_ref.py is the
- * restatement it is held to.  Not built: CLAHE, FAST detection (:1173-1297), the RANSAC of :1344, stereo, the display images. */
+ * restatement it is held to.  Detection (:1173-1297) is ovp_klt_detect below.  Not built: CLAHE, the RANSAC of :1344, stereo, the
+ * display images. */
 #define OVP_KLT_MAX_POINTS 4096
 #define OVP_KLT_MAX_LEVELS 8
 #define OVP_KLT_HIST_NONE 0       /* TrackBase::HistogramMethod, in its order */
@@ -960,11 +961,35 @@ int ovp_klt_feed_image(ovp_ctx *ctx, const uint8_t *img, int stride, int hist_me
  * enqueued and the outputs untouched: OVP_E_STATE before two images were fed, OVP_E_CAPACITY for n > max_points, OVP_E_ARG for a
  * non-finite coordinate; n = 0 returns at once.  No point or guess, however far outside, makes the kernel read outside a level. */
 int ovp_klt_track(ovp_ctx *ctx, int n, const float *pts_prev, const float *guess, float *pts_out, uint8_t *status);
+/* Grider_FAST::perform_griding as perform_detection_monocular calls it (track_plane/TrackPlane.cpp:1262; the stage replaces the
+ * device part of :1173-1297): cv::FAST (9 of 16, non-maximum suppression) on every grid cell of level 0 of a half (0: current,
+ * 1: previous), the K strongest corners of a cell, cv::cornerSubPix ((5,5), 20 iterations, 0.001) on each.  Grider_FAST and OpenCV
+ * are not in the reference tree: the stage is RECALLED from its published form and UNPINNED; tests/fast_ref.py is the restatement
+ * it is held to.  Ties of equal score go in raster order (row, then column) - this library's own rule, the reference leaves them to
+ * std::sort.  num_features < grid_x grid_y shrinks the grid as Grider_FAST does; K = (int)(num_features / cells) + 1; cells of
+ * (width / grid_x) x (height / grid_y) pixels, as many as fit (more than grid_x per row when the division leaves a remainder).
+ * Returns EVERY selected candidate - at most K per cell, whatever the mask (the mask test, the occupancy grid and the ids are the
+ * caller's: ov_plane::TrackPlane::perform_detection_monocular, capi.KltTracker.detect) - in output order (cell ascending, then
+ * score descending): n_out, xy_int [2n] the corner's pixel, response [n] its score (the largest threshold it is still a corner
+ * at), xy_refined [2n] f32, cell [n]; the arrays hold `cap` points.  Three launches (k_fast_score_nms, k_fast_select,
+ * k_fast_subpix: one wave per point) and one publication through the tracker's mailbox: one enqueue, one wait.  The integer outputs
+ * are the same bytes on every run, and so are the refined positions (every sum in a fixed order).  Decided on the host with nothing
+ * enqueued and the outputs untouched: OVP_E_STATE without a tracker or without an image in that half; OVP_E_ARG for a threshold
+ * outside 0..255, num_features or a grid dimension below 1, a grid dimension above the image's, half outside 0..1, a null output;
+ * OVP_E_CAPACITY for more than OVP_FAST_MAX_CELLS cells, K above OVP_FAST_MAX_K, K cells above cap or above the tracker's
+ * max_points.  n_out = 0 is a success.  Every image read is clamped into the level. */
+#define OVP_FAST_MAX_CELLS 4096
+#define OVP_FAST_MAX_K 256
+int ovp_klt_detect(ovp_ctx *ctx, int half, int num_features, int grid_x, int grid_y, int threshold, int *n_out, int32_t *xy_int,
+                   int32_t *response, float *xy_refined, int32_t *cell, int cap);
 /* tests: what = "cur" / "prev": the bytes of pyramid level `level` of that half (rows packed); "equalized": level 0 of the current
- * half; "dims": int32 [width, height] of the level; "iters": uint8 [n][8] iterations per level of the last ovp_klt_track;
+ * half; "dims": int32 [width, height] of the level; "iters": uint8 [n][8] iterations per level of the last ovp_klt_track (none
+ * behind an ovp_klt_detect, which takes the mailbox); "score" / "nms": uint8 [height][width], the level-0 score map of the last
+ * ovp_klt_detect and the same after suppression (OVP_E_STATE before one); "refine" (TESTS ONLY: synchronous, and it overwrites the mailbox's device block): k_fast_subpix on level = n points of the
+ * caller's on level 0 of the current half - out holds float [2n] starting positions on entry and the refined ones on return;
  * "timer": level != 0 puts events around the kernels (and a stream synchronisation behind each entry) from the next call on,
- * "time": float [3] GPU milliseconds of the last timed calls [equalise, pyramid launches together, k_klt_track].  Returns the
- * number of bytes (or < 0). */
+ * "time": float GPU milliseconds of the last timed calls [equalise, pyramid launches together, k_klt_track, k_fast_score_nms,
+ * k_fast_select, k_fast_subpix] - as many as cap holds, at least the first 3.  Returns the number of bytes (or < 0). */
 long ovp_klt_debug(ovp_ctx *ctx, const char *what, int level, void *out, long cap);
 
 /* ---- diagnostics ---------------------------------------------------------------------------- */

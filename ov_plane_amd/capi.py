@@ -274,7 +274,7 @@ EXPORTS = [
     "ovp_active_tracks_debug",
     "ovp_cov_marginalize_many", "ovp_planes_merge_retire", "ovp_zupt_update",
     "ovp_propagate_and_clone",
-    "ovp_klt_create", "ovp_klt_destroy", "ovp_klt_reset", "ovp_klt_feed_image", "ovp_klt_track", "ovp_klt_debug",
+    "ovp_klt_create", "ovp_klt_destroy", "ovp_klt_reset", "ovp_klt_feed_image", "ovp_klt_track", "ovp_klt_debug", "ovp_klt_detect",
 ]
 
 
@@ -402,6 +402,8 @@ def lib():
         L.ovp_klt_reset.argtypes = [C.c_void_p]
         L.ovp_klt_feed_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.ovp_klt_track.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ovp_klt_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int]
         L.ovp_klt_debug.restype = C.c_long
         L.ovp_klt_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_long]
         _LIB = L
@@ -648,12 +650,19 @@ class ActiveTracks:
 class KltTracker:
     """The image front end of a context (ovp_klt_*): TrackPlane::feed_new_camera's equalisation and pyramid, the
     cv::calcOpticalFlowPyrLK call of perform_matching and the keep rule of feed_monocular, on the device.  The algorithm is restated
-    from its published form and unpinned (include/ovplane_hip.h).  Detection is the caller's: add_points seeds or tops up."""
+    from its published form and unpinned (include/ovplane_hip.h).  add_points seeds or tops up with a caller's points; detect()
+    is perform_detection_monocular (:1173-1297) on the device's candidates (ovp_klt_detect: recalled and unpinned as well), and
+    step(detect=True) feed_monocular's use of it.  detector: dict(num_features, grid_x, grid_y, threshold, min_px_dist)."""
 
     HIST = {"NONE": 0, "HISTOGRAM": 1, "CLAHE": 2}
+    DETECTOR_KEYS = ("num_features", "grid_x", "grid_y", "threshold", "min_px_dist")
 
-    def __init__(self, ctx, width, height, n_levels=6, win=15, max_points=4096):
+    def __init__(self, ctx, width, height, n_levels=6, win=15, max_points=4096, detector=None):
         self.ctx, self.width, self.height, self.n_levels, self.win = ctx, int(width), int(height), int(n_levels), int(win)
+        self.max_points = int(max_points)
+        self.detector = None if detector is None else {k: int(detector[k]) for k in self.DETECTOR_KEYS}
+        self.currid = 0          # :1292 ++currid: the first id is 1
+        self._mask_last = None   # img_mask_last: the mask of the previous image, for the top-up
         _chk(lib().ovp_klt_create(ctx.handle, self.width, self.height, self.n_levels, self.win, int(max_points)), "ovp_klt_create")
         self.ids_last = np.zeros(0, dtype=np.int64)
         self.pts_last = np.zeros((0, 2), dtype=np.float32)
@@ -665,6 +674,7 @@ class KltTracker:
     def reset(self):
         _chk(lib().ovp_klt_reset(self.ctx.handle), "ovp_klt_reset")
         self.ids_last, self.pts_last, self._fed = np.zeros(0, dtype=np.int64), np.zeros((0, 2), dtype=np.float32), 0
+        self.currid, self._mask_last = 0, None
 
     def feed_image(self, img, hist="HISTOGRAM"):
         """one 8-bit image [height, width]: equalised, its pyramid built into the current half; does not wait for the device"""
@@ -696,12 +706,90 @@ class KltTracker:
         self.ids_last = np.concatenate([self.ids_last, np.asarray(ids, dtype=np.int64).reshape(-1)])
         self.pts_last = np.concatenate([self.pts_last, np.asarray(uv, dtype=np.float32).reshape(-1, 2)])
 
-    def step(self, img, mask=None, hist="HISTOGRAM"):
+    def detect_candidates(self, half=0, num_features=None, grid_x=None, grid_y=None, threshold=None, cap=None):
+        """ovp_klt_detect on a half (0 current, 1 previous): every selected candidate, mask-independent, in output order ->
+        dict(xy [n, 2] int32, response [n] int32, refined [n, 2] f32, cell [n] int32).  Options default to the detector's."""
+        o = self.detector or {}
+        nf, gx, gy, th = (int(o[k] if v is None else v) for k, v in zip(self.DETECTOR_KEYS, (num_features, grid_x, grid_y, threshold)))
+        cap = self.max_points if cap is None else int(cap)
+        m = max(cap, 1)
+        n = C.c_int(-1)
+        xy, resp = np.full((m, 2), -1, dtype=np.int32), np.full(m, -1, dtype=np.int32)
+        ref, cell = np.full((m, 2), -1.0, dtype=np.float32), np.full(m, -1, dtype=np.int32)
+        t0 = time.perf_counter()
+        rc = lib().ovp_klt_detect(self.ctx.handle, int(half), nf, gx, gy, th, C.byref(n), xy.ctypes.data, resp.ctypes.data, ref.ctypes.data,
+                                  cell.ctypes.data, cap)
+        self.last_detect_ms = 1e3 * (time.perf_counter() - t0)
+        self.last_detect_raw = (n.value, xy, resp, ref, cell)  # (tests: untouched by a refusal)
+        _chk(rc, "ovp_klt_detect")
+        k = n.value
+        return dict(xy=xy[:k].copy(), response=resp[:k].copy(), refined=ref[:k].copy(), cell=cell[:k].copy())
+
+    def detect(self, half=0, mask=None, pts=None, ids=None):
+        """TrackPlane::perform_detection_monocular (:1173-1297) on level 0 of a half: walks pts / ids (None: none) through the
+        occupancy grid, returns them when fewer than 5 % of num_features are missing, else accepts the device's candidates in order
+        and numbers them ++currid.  Returns (pts [m, 2] f32, ids [m] int64).  Every candidate is refined on the device and the
+        masked ones are dropped afterwards; the reference drops them before the refinement, which is the same: cornerSubPix treats
+        each point on its own."""
+        o = self.detector
+        if o is None:
+            raise ValueError("the tracker was made without detector options")
+        cols, rows, mpd = self.width, self.height, o["min_px_dist"]
+        pts = np.zeros((0, 2), dtype=np.float32) if pts is None else np.asarray(pts, dtype=np.float32).reshape(-1, 2)
+        ids = np.zeros(0, dtype=np.int64) if ids is None else np.asarray(ids, dtype=np.int64).reshape(-1)
+        mask = np.zeros((rows, cols), dtype=np.uint8) if mask is None else np.asarray(mask, dtype=np.uint8)
+        f32 = np.float32
+        wc, hc = int(f32(cols) / f32(mpd)), int(f32(rows) / f32(mpd))                      # :1180-1181 size_close
+        sx, sy = f32(cols) / f32(o["grid_x"]), f32(rows) / f32(o["grid_y"])                  # :1183-1184
+        occ = np.zeros((hc, wc), dtype=bool)
+        upd = mask.copy()
+        kp, ki = [], []
+        for p, i in zip(pts, ids):
+            x, y = int(p[0]), int(p[1])
+            if x < 10 or x >= cols - 10 or y < 10 or y >= rows - 10:                        # :1195-1199
+                continue
+            xc, yc = int(p[0] / f32(mpd)), int(p[1] / f32(mpd))
+            if xc < 0 or xc >= wc or yc < 0 or yc >= hc:                                    # :1203-1207
+                continue
+            xg, yg = int(np.floor(p[0] / sx)), int(np.floor(p[1] / sy))
+            if xg < 0 or xg >= o["grid_x"] or yg < 0 or yg >= o["grid_y"]:                  # :1211-1215
+                continue
+            if occ[yc, xc] or mask[y, x] > 127:                                             # :1217-1228
+                continue
+            occ[yc, xc] = True
+            if x - mpd >= 0 and x + mpd < cols and y - mpd >= 0 and y + mpd < rows:        # :1235-1239 the rectangle, when it fits
+                upd[y - mpd:y + mpd + 1, x - mpd:x + mpd + 1] = 255
+            kp.append(p), ki.append(int(i))
+        self.last_detected = False
+        if (o["num_features"] - len(ki)) >= o["num_features"] * (1.0 - 0.95):              # :1246-1249
+            c = self.detect_candidates(half)
+            self.last_detected = True
+            for (x, y), p in zip(c["xy"], c["refined"]):
+                if upd[y, x] > 127:                                                 # Grider_FAST's mask test, on the corner's pixel
+                    continue
+                xc, yc = int(p[0] / f32(mpd)), int(p[1] / f32(mpd))                         # :1265-1281
+                if xc < 0 or xc >= wc or yc < 0 or yc >= hc or occ[yc, xc]:
+                    continue
+                occ[yc, xc] = True
+                self.currid += 1                                                            # :1292
+                kp.append(p), ki.append(self.currid)
+        return np.array(kp, dtype=np.float32).reshape(-1, 2), np.array(ki, dtype=np.int64)
+
+    def step(self, img, mask=None, hist="HISTOGRAM", detect=False):
         """feed_monocular :505-567 minus detection and the epipolar check: feeds img, tracks pts_last into it with guess = pts_last,
         keeps a point unless x < 0, y < 0, (int) x >= cols, (int) y >= rows, mask > 127 at the truncated pixel, or status 0.
-        Returns (ids, pts) of the kept points, which are pts_last / ids_last from here on."""
+        Returns (ids, pts) of the kept points, which are pts_last / ids_last from here on.
+        detect=True is feed_monocular :477-567 minus the epipolar check: without points it detects on the current image and returns
+        (:477-491); otherwise it tops pts_last up on the previous half under the previous image's mask (:505-507), then tracks."""
         self.feed_image(img, hist)
         self.last_match = (np.zeros((0, 2), dtype=np.float32), np.zeros(0, dtype=np.uint8))
+        if detect:
+            mask_prev, self._mask_last = self._mask_last, (None if mask is None else np.array(mask, dtype=np.uint8))
+            if len(self.ids_last) == 0:
+                self.pts_last, self.ids_last = self.detect(0, mask)
+                return self.ids_last.copy(), self.pts_last.copy()
+            self.pts_last, self.ids_last = self.detect(1, mask_prev, self.pts_last, self.ids_last)
+            self.last_topped = (self.ids_last.copy(), self.pts_last.copy())
         if self._fed < 2 or len(self.ids_last) == 0:
             return self.ids_last.copy(), self.pts_last.copy()
         p, st = self.track(self.pts_last, self.pts_last)
@@ -738,9 +826,21 @@ class KltTracker:
         self._debug(b"timer", 1 if on else 0, 0)
 
     def kernel_ms(self):
-        """GPU milliseconds of the last timed calls: dict(equalize, pyramid, track)"""
-        t = self._debug(b"time", 0, 12, np.float32)
-        return dict(equalize=float(t[0]), pyramid=float(t[1]), track=float(t[2]))
+        """GPU milliseconds of the last timed calls: dict(equalize, pyramid, track, score_nms, select, subpix)"""
+        t = self._debug(b"time", 0, 24, np.float32)
+        return dict(zip(("equalize", "pyramid", "track", "score_nms", "select", "subpix"), (float(v) for v in t)))
+
+    def refine(self, xy):
+        """tests: k_fast_subpix from the starting positions xy [n, 2] on level 0 of the current half -> [n, 2] f32"""
+        buf = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2).copy()
+        k = lib().ovp_klt_debug(self.ctx.handle, b"refine", len(buf), buf.ctypes.data, buf.nbytes)
+        if k < 0:
+            raise OvpError(int(k), "ovp_klt_debug")
+        return buf
+
+    def score_map(self, what="score"):
+        """tests: the level-0 score map ("score") of the last detect, or the same after suppression ("nms") -> [h, w] uint8"""
+        return self._debug(what.encode(), 0, self.width * self.height).reshape(self.height, self.width).copy()
 
 
 def rccl_unique_id() -> bytes:

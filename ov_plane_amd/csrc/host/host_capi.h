@@ -70,6 +70,12 @@ int ovph_run_opts_layout(int *offsets, int cap);
 int ovph_run_klt_sequence(int device, int width, int height, int n_frames, const uint8_t *frames, const uint8_t *mask, int pyr_levels,
                           int win_size, int hist_method, int n_pts, const int64_t *ids, const float *uv, int32_t *n_kept,
                           int64_t *kept_ids, float *kept_uv, int32_t *n_match, float *match_uv, uint8_t *match_mask);
+// the same with the mirror's own detection (feed_new_camera(.., detect = true) from an empty tracker): detector5 = [num_features,
+// grid_x, grid_y, threshold, min_px_dist]; per frame f the ids / points held behind it in kept_ids[f][max_points] /
+// kept_uv[f][max_points][2].  OVP_E_CAPACITY when a frame holds more than max_points.
+int ovph_run_klt_detect_sequence(int device, int width, int height, int n_frames, const uint8_t *frames, const uint8_t *mask,
+                                 int pyr_levels, int win_size, int hist_method, int max_points, const int32_t *detector5, int32_t *n_kept,
+                                 int64_t *kept_ids, float *kept_uv);
 
 #ifdef __cplusplus
 }

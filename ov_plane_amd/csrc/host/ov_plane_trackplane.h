@@ -6,10 +6,13 @@
 // detector's own, on the device behind its first call: no has_est round trip and no triangles to hand over.
 // The image half: feed_new_camera() is TrackPlane::feed_new_camera (:40-92) followed by the bookkeeping of feed_monocular
 // (:505-567) minus detection and the epipolar check, perform_matching_klt() the cv::calcOpticalFlowPyrLK call of perform_matching
-// (:1326-1330, :1352-1356); both pyramids live in the tracker of the device context (ovp_klt_*).  Detection is the caller's:
-// add_points() seeds or tops up pts_last / ids_last.
+// (:1326-1330, :1352-1356); both pyramids live in the tracker of the device context (ovp_klt_*).  add_points() seeds or tops up
+// pts_last / ids_last with a caller's points; perform_detection_monocular() is :1173-1297 on the device's candidates
+// (ovp_klt_detect: Grider_FAST and OpenCV are not in the reference tree, that stage is recalled and unpinned), and
+// feed_new_camera(.., detect = true) feed_monocular's use of it (:477-491, :505-507).
 #pragma once
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <map>
 #include <set>
@@ -94,7 +97,83 @@ class TrackPlane {
     return 0;
   }
 
-  // the caller's detection (perform_detection_monocular, :1173-1297, is not built): points of the last image fed
+  // TrackBase's num_features, grid_x, grid_y, threshold and min_px_dist
+  void set_detector_options(int num_features, int grid_x, int grid_y, int threshold, int min_px_dist) {
+    _num_features = num_features, _grid_x = grid_x, _grid_y = grid_y, _threshold = threshold, _min_px_dist = min_px_dist;
+  }
+
+  // :1173-1297 on level 0 of a half of the tracker (0: the current image, 1: the previous one): walks pts [2n] / ids through the
+  // occupancy grid, returns when fewer than 5 % of num_features are missing, else accepts the device's candidates in order and
+  // numbers them ++currid (which starts at 0: the first id is 1).  mask: h x w, NULL for none.  Every candidate is refined on the
+  // device and the masked ones are dropped afterwards; the reference drops them before the refinement, which is the same:
+  // cornerSubPix treats each point on its own.
+  int perform_detection_monocular(int half, const uint8_t *mask, std::vector<float> &pts, std::vector<size_t> &ids) {
+    if (!_klt_made) return OVP_E_STATE;
+    const int cap = _klt_max_points;
+    return detection_monocular(_klt_w, _klt_h, _num_features, _grid_x, _grid_y, _min_px_dist, mask, pts, ids, _currid, _last_detected,
+                               [&](std::vector<int32_t> &xy, std::vector<float> &ref) {
+                                 std::vector<int32_t> resp(cap), cell(cap);
+                                 xy.resize(2 * (size_t)cap), ref.resize(2 * (size_t)cap);
+                                 int n = 0;
+                                 const int rc = ovp_klt_detect(_gpu, half, _num_features, _grid_x, _grid_y, _threshold, &n, xy.data(), resp.data(),
+                                                               ref.data(), cell.data(), cap);
+                                 xy.resize(rc ? 0 : 2 * (size_t)n), ref.resize(rc ? 0 : 2 * (size_t)n);
+                                 return rc;
+                               });
+  }
+
+  // the host half of the above on its own (no device: tests hand the candidates in): candidates(xy_int [2n], refined [2n]) -> 0 or
+  // a code, called only behind the 5 % return
+  template <class Candidates>
+  static int detection_monocular(int cols, int rows, int num_features, int grid_x, int grid_y, int min_px_dist, const uint8_t *mask,
+                                 std::vector<float> &pts, std::vector<size_t> &ids, size_t &currid, bool &detected, Candidates &&candidates) {
+    if (min_px_dist < 1 || grid_x < 1 || grid_y < 1 || pts.size() != 2 * ids.size()) return OVP_E_ARG;
+    const int mpd = min_px_dist;
+    const int wc = (int)((float)cols / (float)mpd), hc = (int)((float)rows / (float)mpd);  // :1180-1181 size_close
+    const float size_x = (float)cols / (float)grid_x, size_y = (float)rows / (float)grid_y;
+    std::vector<uint8_t> close((size_t)std::max(wc, 0) * std::max(hc, 0), 0);
+    std::vector<uint8_t> upd((size_t)cols * rows, 0);
+    if (mask) upd.assign(mask, mask + (size_t)cols * rows);
+    std::vector<float> kp;
+    std::vector<size_t> ki;
+    for (size_t i = 0; i < ids.size(); ++i) {
+      const float fx = pts[2 * i], fy = pts[2 * i + 1];
+      const int x = (int)fx, y = (int)fy, edge = 10;
+      if (x < edge || x >= cols - edge || y < edge || y >= rows - edge) continue;          // :1195-1199
+      const int xc = (int)(fx / (float)mpd), yc = (int)(fy / (float)mpd);
+      if (xc < 0 || xc >= wc || yc < 0 || yc >= hc) continue;                               // :1203-1207
+      const int xg = (int)std::floor(fx / size_x), yg = (int)std::floor(fy / size_y);
+      if (xg < 0 || xg >= grid_x || yg < 0 || yg >= grid_y) continue;                       // :1211-1215
+      if (close[(size_t)yc * wc + xc] > 127) continue;                                      // :1217-1221
+      if (mask && mask[(size_t)y * cols + x] > 127) continue;                               // :1224-1228
+      close[(size_t)yc * wc + xc] = 255;
+      if (x - mpd >= 0 && x + mpd < cols && y - mpd >= 0 && y + mpd < rows)                 // :1235-1239 the rectangle, when it fits
+        for (int r = y - mpd; r <= y + mpd; ++r)
+          for (int q = x - mpd; q <= x + mpd; ++q) upd[(size_t)r * cols + q] = 255;
+      kp.push_back(fx), kp.push_back(fy), ki.push_back(ids[i]);
+    }
+    detected = false;
+    if (num_features - (int)ki.size() >= num_features * (1.0 - 0.95)) {                     // :1246-1249
+      std::vector<int32_t> xy;
+      std::vector<float> ref;
+      const int rc = candidates(xy, ref);
+      if (rc) return rc;
+      detected = true;
+      for (size_t j = 0; 2 * j + 1 < xy.size(); ++j) {
+        if (xy[2 * j] < 0 || xy[2 * j] >= cols || xy[2 * j + 1] < 0 || xy[2 * j + 1] >= rows) continue;
+        if (upd[(size_t)xy[2 * j + 1] * cols + xy[2 * j]] > 127) continue;                  // Grider_FAST's mask test, on the corner's pixel
+        const int xc = (int)(ref[2 * j] / (float)mpd), yc = (int)(ref[2 * j + 1] / (float)mpd);  // :1265-1281
+        if (xc < 0 || xc >= wc || yc < 0 || yc >= hc || close[(size_t)yc * wc + xc] > 127) continue;
+        close[(size_t)yc * wc + xc] = 255;
+        kp.push_back(ref[2 * j]), kp.push_back(ref[2 * j + 1]), ki.push_back(++currid);     // :1292
+      }
+    }
+    pts.swap(kp), ids.swap(ki);
+    return 0;
+  }
+  bool last_detected() const { return _last_detected; }
+
+  // a caller's own detection: points of the last image fed
   void add_points(const std::vector<size_t> &ids, const std::vector<float> &uv) {
     for (size_t i = 0; i < ids.size() && 2 * i + 1 < uv.size(); ++i) {
       _ids_last.push_back(ids[i]);
@@ -119,7 +198,9 @@ class TrackPlane {
   // One camera image (8-bit, h rows of `stride` bytes) and its mask (h x w, NULL: none; a value above 127 masks the pixel):
   // :40-92 equalise and build the pyramid, then :514-567 track pts_last into it and keep a point unless x < 0, y < 0,
   // (int) x >= cols, (int) y >= rows, it lies in the mask, or its status is 0.  Returns 0 or an OVP_E_* code.
-  int feed_new_camera(double time, const uint8_t *img, int w, int h, int stride, const uint8_t *mask = nullptr) {
+  // detect: feed_monocular :477-567 minus the epipolar check - without points, detection on this image and return (:477-491);
+  // otherwise pts_last is topped up on the previous image under its mask (:505-507) before it is tracked.
+  int feed_new_camera(double time, const uint8_t *img, int w, int h, int stride, const uint8_t *mask = nullptr, bool detect = false) {
     if (!_klt_made) {
       const int rc = ovp_klt_create(_gpu, w, h, _pyr_levels + 1, _win_size, _klt_max_points);
       if (rc) return rc;
@@ -130,7 +211,16 @@ class TrackPlane {
     if (rc) return rc;
     _time_last = time;
     _match_pts.clear(), _match_mask.clear();
-    if (++_n_images < 2 || _ids_last.empty()) return 0;
+    ++_n_images;
+    if (detect) {
+      std::vector<uint8_t> mask_prev;
+      mask_prev.swap(_mask_last);
+      if (mask) _mask_last.assign(mask, mask + (size_t)w * h);
+      if (_ids_last.empty()) return perform_detection_monocular(0, mask, _pts_last, _ids_last);
+      rc = perform_detection_monocular(1, mask_prev.empty() ? nullptr : mask_prev.data(), _pts_last, _ids_last);
+      if (rc) return rc;
+    }
+    if (_n_images < 2 || _ids_last.empty()) return 0;
     std::vector<float> pts_new = _pts_last;  // :512 pts_left_new = pts_left_old
     rc = perform_matching_klt(_pts_last, pts_new, _match_mask);
     if (rc) return rc;
@@ -176,6 +266,11 @@ class TrackPlane {
   std::vector<size_t> _ids_last;
   std::vector<float> _pts_last, _match_pts;
   std::vector<uint8_t> _match_mask;
+  // detection
+  int _num_features = 200, _grid_x = 12, _grid_y = 12, _threshold = 15, _min_px_dist = 15;
+  size_t _currid = 0;
+  bool _last_detected = false;
+  std::vector<uint8_t> _mask_last;  // img_mask_last: the previous image's mask, for the top-up
 };
 
 }  // namespace ov_plane

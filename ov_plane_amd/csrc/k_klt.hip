@@ -16,6 +16,8 @@
 
 #include <cmath>
 
+#include "k_fast.h"  // detection: k_fast_score_nms, k_fast_select, k_fast_subpix (ovp_klt_detect below)
+
 namespace {
 
 constexpr int KLT_MAX_LEVELS = 8, KLT_MAX_POINTS = 4096, KLT_MIN_WIN = 3, KLT_MAX_WIN = 21;  // 21^2 = 441 pixels: 7 per lane
@@ -243,6 +245,8 @@ struct Klt {
   size_t half_bytes = 0;
   DevBuf<unsigned char> pyr[2], raw;  // the two halves, swapped by index; the uploaded image in front of the equalisation
   DevBuf<unsigned> hist;
+  DevBuf<unsigned char> score, nms;  // ovp_klt_detect: the level-0 score map and the same after suppression
+  bool det_done = false;
   PinnedBuf<unsigned char> himg;  // the upload's staging, rows packed
   PinnedBuf<void> hstage;
   DevBuf<void> dstage, dres;
@@ -251,11 +255,12 @@ struct Klt {
   int cur = 0, fed = 0;  // index of the current half; images fed since create / reset
   hipEvent_t ev_up = nullptr;
   hipEvent_t ev_eq0 = nullptr, ev_eq1 = nullptr, ev_pyr1 = nullptr, ev_trk0 = nullptr, ev_trk1 = nullptr;  // timed mode
+  hipEvent_t ev_det[4] = {nullptr, nullptr, nullptr, nullptr};
   bool up_pending = false, timed = false;
-  float ms[3] = {0.f, 0.f, 0.f};  // equalise, pyramid launches together, k_klt_track
+  float ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // equalise, pyramid launches together, k_klt_track, k_fast_score_nms, k_fast_select, k_fast_subpix
   int last_n = 0;
   ~Klt() {
-    for (hipEvent_t e : {ev_up, ev_eq0, ev_eq1, ev_pyr1, ev_trk0, ev_trk1})
+    for (hipEvent_t e : {ev_up, ev_eq0, ev_eq1, ev_pyr1, ev_trk0, ev_trk1, ev_det[0], ev_det[1], ev_det[2], ev_det[3]})
       if (e) (void)hipEventDestroy(e);
   }
 };
@@ -282,15 +287,18 @@ extern "C" int ovp_klt_create(ovp_ctx* c, int width, int height, int n_levels, i
   for (auto& p : d->pyr) HIPCHK(p.alloc(off));
   HIPCHK(d->raw.alloc(((size_t)width * height + 255) & ~(size_t)255));
   HIPCHK(d->hist.alloc(256));
+  HIPCHK(d->score.alloc((size_t)width * height));
+  HIPCHK(d->nms.alloc((size_t)width * height));
   HIPCHK(d->himg.alloc((size_t)width * height));
   d->stage_cap = 64 * 2 + sizeof(float) * 4 * (size_t)max_points;
-  d->res_cap = 64 * 3 + sizeof(float) * 2 * (size_t)max_points + (size_t)max_points * (1 + KLT_MAX_LEVELS);
+  d->res_cap = 64 * 3 + std::max(sizeof(float) * 2 + 1 + KLT_MAX_LEVELS, sizeof(int) * 3 + sizeof(float) * 2) * (size_t)max_points;  // a track's results or a detection's
   HIPCHK(d->hstage.alloc(d->stage_cap));
   HIPCHK(d->dstage.alloc(d->stage_cap));
   HIPCHK(d->dres.alloc(d->res_cap));
   HIPCHK(d->hres.alloc(d->res_cap));
   HIPCHK(hipEventCreateWithFlags(&d->ev_up, hipEventDisableTiming));
-  for (hipEvent_t* e : {&d->ev_eq0, &d->ev_eq1, &d->ev_pyr1, &d->ev_trk0, &d->ev_trk1}) HIPCHK(hipEventCreate(e));
+  for (hipEvent_t* e : {&d->ev_eq0, &d->ev_eq1, &d->ev_pyr1, &d->ev_trk0, &d->ev_trk1, &d->ev_det[0], &d->ev_det[1], &d->ev_det[2], &d->ev_det[3]})
+    HIPCHK(hipEventCreate(e));
   c->klt = d;
   return 0;
 }
@@ -308,6 +316,7 @@ extern "C" int ovp_klt_reset(ovp_ctx* c) {
   Klt* d = klt_of(c);
   if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
   d->fed = 0;  // (a half is overwritten when an image takes it)
+  d->det_done = false;
   return 0;
 }
 
@@ -411,6 +420,96 @@ extern "C" int ovp_klt_track(ovp_ctx* c, int n, const float* pts_prev, const flo
   return 0;
 }
 
+// the cells of Grider_FAST::perform_griding (recalled): false when a cell would be empty
+static bool fast_grid(int cols, int rows, int num_features, int grid_x, int grid_y, FastGrid* g) {
+  if (num_features < grid_x * (long long)grid_y) {
+    const double ratio = (double)grid_x / (double)grid_y;
+    grid_y = (int)std::ceil(std::sqrt(num_features / ratio));
+    grid_x = (int)std::ceil(grid_y * ratio);
+  }
+  if (grid_x < 1 || grid_y < 1 || grid_x > cols || grid_y > rows) return false;
+  g->cols = cols, g->rows = rows;
+  const long long k = (long long)(num_features / (double)((long long)grid_x * grid_y)) + 1;
+  g->K = (int)std::min<long long>(k, FAST_MAX_K + 1);  // (anything above the limit is refused: no overflow on the way there)
+  g->size_x = cols / grid_x, g->size_y = rows / grid_y;
+  g->ct_cols = cols / g->size_x, g->ct_rows = rows / g->size_y;
+  return true;
+}
+
+// cornerSubPix's window weights per axis: exp(-x^2), x = (j - 5) / 5 in float
+static void fast_subpix_weights(float* w) {
+  for (int j = 0; j < FAST_SUB_WIN; ++j) {
+    const float x = (float)(j - FAST_SUB_HALF) / (float)FAST_SUB_HALF;
+    w[j] = (float)std::exp(-(double)(x * x));  // one rounding to float: the same bits from every libm
+  }
+}
+
+extern "C" int ovp_klt_detect(ovp_ctx* c, int half, int num_features, int grid_x, int grid_y, int threshold, int* n_out, int32_t* xy_int,
+                              int32_t* response, float* xy_refined, int32_t* cell, int cap) {
+  Klt* d = klt_of(c);
+  if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
+  // ---- every check before anything is touched or enqueued ----
+  if (half != 0 && half != 1) return OVP_E_ARG;
+  if (d->fed < 1 + half) return OVP_E_STATE;
+  if (threshold < 0 || threshold > 255 || num_features < 1 || grid_x < 1 || grid_y < 1 || cap < 0) return OVP_E_ARG;
+  if (grid_x > d->width || grid_y > d->height) return OVP_E_ARG;
+  if (!n_out || !xy_int || !response || !xy_refined || !cell) return OVP_E_ARG;
+  FastGrid g;
+  if (!fast_grid(d->width, d->height, num_features, grid_x, grid_y, &g)) return OVP_E_ARG;
+  const long long cells = (long long)g.ct_cols * g.ct_rows;
+  if (cells > FAST_MAX_CELLS || g.K > FAST_MAX_K) return OVP_E_CAPACITY;
+  const long long slots = cells * g.K;
+  if (slots > cap || slots > d->max_points) return OVP_E_CAPACITY;
+  const int n = (int)slots;
+  StageLayout R;
+  const size_t r_xy = R.take(sizeof(int) * 2 * n), r_resp = R.take(sizeof(int) * n), r_ref = R.take(sizeof(float) * 2 * n);
+  if (R.bytes() > d->res_cap) return OVP_E_CAPACITY;  // (cannot happen below max_points)
+  // ---- from here on the call goes through ----
+  HIPCHK(hipSetDevice(c->device));
+  const unsigned char* img = d->pyr[half ? d->cur ^ 1 : d->cur].get();  // level 0 of that half
+  char* dr = (char*)d->dres.get();
+  if (d->timed) HIPCHK(hipEventRecord(d->ev_det[0], c->stream));
+  hipLaunchKernelGGL(k_fast_score_nms, dim3((d->width + FAST_TW - 1) / FAST_TW, (d->height + FAST_TH - 1) / FAST_TH), dim3(256), 0, c->stream,
+                     img, g, threshold, d->score.get(), d->nms.get());
+  HIPCHK(hipGetLastError());
+  if (d->timed) HIPCHK(hipEventRecord(d->ev_det[1], c->stream));
+  hipLaunchKernelGGL(k_fast_select, dim3((unsigned)cells), dim3(256), 0, c->stream, (const unsigned char*)d->nms.get(), g, (int*)(dr + r_xy),
+                     (int*)(dr + r_resp));
+  HIPCHK(hipGetLastError());
+  if (d->timed) HIPCHK(hipEventRecord(d->ev_det[2], c->stream));
+  FastSubpixArgs a;
+  a.img = img, a.cols = d->width, a.rows = d->height, a.n = n;
+  a.xy = (const int*)(dr + r_xy), a.resp = (const int*)(dr + r_resp), a.out = (float*)(dr + r_ref), a.start = nullptr;
+  fast_subpix_weights(a.w);
+  hipLaunchKernelGGL(k_fast_subpix, dim3((n + 3) / 4), dim3(256), 0, c->stream, a);
+  HIPCHK(hipGetLastError());
+  if (d->timed) HIPCHK(hipEventRecord(d->ev_det[3], c->stream));
+  SeqChannel& ch = d->hres.channel(0);
+  const unsigned seq = ch.arm();
+  HIPCHK(ovp_launch_publish_block(dr, d->hres.dev(d->hres.payload()), R.bytes(), ch.word_dev(), seq, 0, c->stream));
+  const int rw = ch.wait(c->stream);
+  if (rw) return rw;
+  if (d->timed) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 3; ++k) HIPCHK(hipEventElapsedTime(&d->ms[3 + k], d->ev_det[k], d->ev_det[k + 1]));
+  }
+  // the slots in output order (cell ascending, then selection order), the empty ones gone
+  const char* hr = (const char*)d->hres.payload();
+  const int32_t *sxy = (const int32_t*)(hr + r_xy), *sresp = (const int32_t*)(hr + r_resp);
+  const float* sref = (const float*)(hr + r_ref);
+  int m = 0;
+  for (int s = 0; s < n; ++s) {
+    if (sresp[s] == 0) continue;
+    xy_int[2 * m] = sxy[2 * s], xy_int[2 * m + 1] = sxy[2 * s + 1], response[m] = sresp[s];
+    xy_refined[2 * m] = sref[2 * s], xy_refined[2 * m + 1] = sref[2 * s + 1], cell[m] = s / g.K;
+    ++m;
+  }
+  *n_out = m;
+  d->last_n = 0;  // (the mailbox no longer holds a track's iterations)
+  d->det_done = true;
+  return 0;
+}
+
 extern "C" long ovp_klt_debug(ovp_ctx* c, const char* what, int level, void* out, long cap) {
   Klt* d = klt_of(c);
   if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
@@ -420,9 +519,43 @@ extern "C" long ovp_klt_debug(ovp_ctx* c, const char* what, int level, void* out
     return 0;
   }
   if (!strcmp(what, "time")) {
-    if (cap < (long)sizeof(d->ms)) return OVP_E_ARG;
-    memcpy(out, d->ms, sizeof(d->ms));
-    return (long)sizeof(d->ms);
+    if (cap < (long)(3 * sizeof(float))) return OVP_E_ARG;  // [3] of the tracker alone, [6] with the detector's kernels
+    const size_t bytes = std::min((size_t)cap / sizeof(float), sizeof(d->ms) / sizeof(float)) * sizeof(float);
+    memcpy(out, d->ms, bytes);
+    return (long)bytes;
+  }
+  if (!strcmp(what, "refine")) {  // k_fast_subpix on `level` points of the caller's: out holds float [2n] starts, then float [2n]
+    const int n = level;
+    if (n < 1 || n > d->max_points || (size_t)cap < sizeof(float) * 2 * (size_t)n) return OVP_E_ARG;
+    if (d->fed < 1) return OVP_E_STATE;
+    StageLayout R;
+    const size_t r_xy = R.take(sizeof(int) * 2 * n), r_resp = R.take(sizeof(int) * n), r_ref = R.take(sizeof(float) * 2 * n);
+    if (R.bytes() > d->res_cap) return OVP_E_CAPACITY;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    char* dr = (char*)d->dres.get();
+    for (int i = 0; i < 2 * n; ++i)
+      if (!std::isfinite(((const float*)out)[i])) return OVP_E_ARG;
+    HIPCHK(hipMemcpy(dr + r_xy, out, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dr + r_resp, 1, sizeof(int) * n));  // (every slot is taken)
+    FastSubpixArgs a;
+    a.img = d->pyr[d->cur].get(), a.cols = d->width, a.rows = d->height, a.n = n;
+    a.xy = nullptr, a.start = (const float*)(dr + r_xy), a.resp = (const int*)(dr + r_resp), a.out = (float*)(dr + r_ref);
+    fast_subpix_weights(a.w);
+    hipLaunchKernelGGL(k_fast_subpix, dim3((n + 3) / 4), dim3(256), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out, dr + r_ref, sizeof(float) * 2 * n, hipMemcpyDeviceToHost));
+    return (long)(sizeof(float) * 2 * n);
+  }
+  if (!strcmp(what, "score") || !strcmp(what, "nms")) {  // of the last ovp_klt_detect, level 0
+    if (!d->det_done) return OVP_E_STATE;
+    const size_t bytes = (size_t)d->width * d->height;
+    if ((size_t)cap < bytes) return OVP_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out, what[0] == 's' ? d->score.get() : d->nms.get(), bytes, hipMemcpyDeviceToHost));
+    return (long)bytes;
   }
   if (!strcmp(what, "iters")) {  // of the last ovp_klt_track: [n][8] iterations per level (the mailbox still holds them)
     const size_t off = StageLayout::al(sizeof(float) * 2 * d->last_n) + StageLayout::al(d->last_n), bytes = (size_t)d->last_n * KLT_MAX_LEVELS;
