@@ -107,7 +107,8 @@ typedef struct {
  * resident factorizations, larger ones the sub-state update (a batch may then touch at most 288 columns to stay fast);
  * ovp_msckf_plane_update above 287 columns runs its loop on the columns the planes of the call involve (clones, calibration, the
  * planes that are state variables, the SLAM landmarks on the others: at most 287 of them, OVP_E_CAPACITY beyond) and carries the
- * rest of the state along; ovp_plane_init runs on the marginal of the clone and calibration columns at any state size. */
+ * rest of the state along; ovp_plane_init and ovp_plane_init_general are that loop on planes outside the state (any state size, at
+ * most 287 clone and calibration columns). */
 int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int n_feats_max, void *stream, ovp_ctx **out);
 int ovp_ctx_destroy(ovp_ctx *ctx);
 int ovp_sync(ovp_ctx *ctx);
@@ -352,7 +353,10 @@ int ovp_msckf_plane_update_general(ovp_ctx *ctx, const ovp_update_opts *opts, co
  * does not involve the plane, covariance augmentation by 3 and EKF update with the remaining rows.
  * Every accepted plane appends 3 columns to the state (new_ids[k] = its Type::id(), else -1); cp_new[3k..] is its
  * initialised value; dx_planes[k*dx_stride ..] the correction of the pre-existing variables to apply with Type::update
- * (dx_stride >= final state size).  Upstream triangulation / plane fitting is the caller's job. */
+ * (dx_stride >= final state size).  Upstream triangulation / plane fitting is the caller's job.
+ * This is ovp_plane_init_general (below) with general == NULL: the same code, the same bits, the same refusals.  In particular
+ * plane_chi2 of a rejected plane is a finite statistic, and the capacity check is made up front and is all-or-nothing:
+ * n + 3 * (planes with at least 3 usable features) > n_state_max returns OVP_E_CAPACITY before anything is written. */
 int ovp_plane_init(ovp_ctx *ctx, const ovp_update_opts *opts, const ovp_plane_batch *planes, double const_init_multi,
                    double const_init_chi2, double *dx_planes, int dx_stride, uint8_t *plane_ok, double *plane_chi2,
                    int *plane_dof, int *new_ids, double *cp_new, uint8_t *feat_used);

@@ -1420,8 +1420,9 @@ class Context:
         return dict(dx=dx[:npl], ok=ok[:npl].astype(bool), chi2=chi2[:npl], dof=dof[:npl], used=used[: self.n_feats].astype(bool),
                     gen_used=gused[:GF].astype(bool), rc=rc)
 
-    def plane_init(self, opts: UpdateOpts, plane_of_feat, cp, const_init_multi, const_init_chi2):
-        """UpdaterPlane::init_vio_plane core. Returns dict(dx [n_planes, stride], ok, chi2, dof, new_ids, cp, used)."""
+    def plane_init(self, opts: UpdateOpts, plane_of_feat, cp, const_init_multi, const_init_chi2, raise_on_error=True):
+        """UpdaterPlane::init_vio_plane core (ovp_plane_init: ovp_plane_init_general without a general batch).
+        Returns dict(dx [n_planes, stride], ok, chi2, dof, new_ids, cp, used, rc)."""
         plane_of_feat = np.ascontiguousarray(plane_of_feat, dtype=np.int32)
         cp = np.ascontiguousarray(cp, dtype=np.float64)
         npl = int(cp.shape[0])
@@ -1435,11 +1436,13 @@ class Context:
         cpn = np.zeros((max(npl, 1), 3))
         used = np.zeros(max(self.n_feats, 1), dtype=np.uint8)
         pb = PlaneBatch(npl, plane_of_feat.ctypes.data, cp.ctypes.data, cp.ctypes.data, sid.ctypes.data)
-        _chk(lib().ovp_plane_init(self._h, C.byref(opts), C.byref(pb), C.c_double(const_init_multi),
+        rc = lib().ovp_plane_init(self._h, C.byref(opts), C.byref(pb), C.c_double(const_init_multi),
                                   C.c_double(const_init_chi2), dx.ctypes.data, C.c_int(stride), ok.ctypes.data, chi2.ctypes.data,
-                                  dof.ctypes.data, nid.ctypes.data, cpn.ctypes.data, used.ctypes.data), "ovp_plane_init")
+                                  dof.ctypes.data, nid.ctypes.data, cpn.ctypes.data, used.ctypes.data)
+        if rc != 0 and raise_on_error:
+            raise OvpError(rc, "ovp_plane_init")
         return dict(dx=dx[:npl], ok=ok[:npl].astype(bool), chi2=chi2[:npl], dof=dof[:npl], new_ids=nid[:npl], cp=cpn[:npl],
-                    used=used[: self.n_feats].astype(bool))
+                    used=used[: self.n_feats].astype(bool), rc=rc)
 
     def plane_init_general(self, opts: UpdateOpts, plane_of_feat, cp, const_init_multi, const_init_chi2, sc=None, feats=None,
                            uv=None, clone_idx=None, cam_idx=None, n_meas=None, p_FinG=None, plane_of_gen=None, raise_on_error=True):

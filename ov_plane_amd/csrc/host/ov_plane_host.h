@@ -107,8 +107,8 @@ struct StateOptions {
   bool gpu_general_planes = false;
   // UpdaterPlane::init_vio_plane: the on-plane features the device batch cannot carry (another camera's observations, more than
   // OVP_MAX_MEAS views; at most OVP_GEN_MAX_MEAS) are triangulated over every camera, take part in the fit when gpu_fused_plane_fit
-  // is on, and initialise their plane together with the batch's in one device pass (ovp_plane_init_general).  Off: ovp_plane_init,
-  // which takes every feature as camera 0's
+  // is on, and initialise their plane together with the batch's in one device pass (ovp_plane_init_general).  Off: the same
+  // call with an empty general batch, every feature taken as camera 0's
   bool gpu_general_plane_init = false;
   // The front end of the plane path (UpdaterMSCKF.cpp:262-401, UpdaterPlane.cpp:221-290) as ONE call of ovp_plane_fit_refine for all
   // planes of the frame instead of PlaneFitting::plane_fitting / optimize_plane once per plane: one round trip, and on-plane

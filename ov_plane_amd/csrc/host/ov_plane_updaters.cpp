@@ -1427,32 +1427,27 @@ void UpdaterPlane::init_vio_plane(std::shared_ptr<State> state, std::vector<std:
   std::vector<int> gidx;  // features of the general batch (their pof entry names the plane; the batch holds them without measurements)
   for (int f = 0; f < F; ++f)
     if (pof[f] > 0 && is_general(*feature_vec[f])) gidx.push_back(f);
-  if (gen_on) {
-    // one call over both kinds of features (update/UpdaterHelper.cpp:335-344: every camera's measurements of a feature)
-    upload_camera_tables(state);
-    const int G = (int)gidx.size();
-    PackSite gen_site;
-    gen_site.pad = 0;
-    gen_site.empty_rows = 1;
-    const FeaturePack g = pack_features(feature_range(feature_vec, gidx), window.clone_slot, gen_site);
-    const ovp_general_batch gb = g.as_general_batch();
-    std::vector<int> gpl(std::max(G, 1), 0);
-    std::vector<uint8_t> gused(std::max(G, 1), 0);
-    for (int i = 0; i < G; ++i) {
-      gpl[i] = pof[gidx[i]];
-      pof[gidx[i]] = 0;
-    }
-    gpu_check2(ovp_plane_init_general(state->_gpu, &o, &pb, state->_options.const_init_multi, state->_options.const_init_chi2, dxp.data(),
-                                      stride, pok.data(), nullptr, nullptr, nid.data(), cpn.data(), fused.data(), &gb, gpl.data(),
-                                      gused.data()),
-               "ovp_plane_init_general");
-    for (int g = 0; g < G; ++g)
-      if (gused[g]) fused[gidx[g]] = 1;  // consumed like the batch's: feature_vec_used below
-  } else {
-    gpu_check2(ovp_plane_init(state->_gpu, &o, &pb, state->_options.const_init_multi, state->_options.const_init_chi2, dxp.data(),
-                              stride, pok.data(), nullptr, nullptr, nid.data(), cpn.data(), fused.data()),
-               "ovp_plane_init");
+  // one call over both kinds of features (update/UpdaterHelper.cpp:335-344: every camera's measurements of a feature); with the
+  // option off no feature is a general one and the general batch is empty
+  if (!gidx.empty()) upload_camera_tables(state);
+  const int G = (int)gidx.size();
+  PackSite gen_site;
+  gen_site.pad = 0;
+  gen_site.empty_rows = 1;
+  const FeaturePack g = pack_features(feature_range(feature_vec, gidx), window.clone_slot, gen_site);
+  const ovp_general_batch gb = g.as_general_batch();
+  std::vector<int> gpl(std::max(G, 1), 0);
+  std::vector<uint8_t> gused(std::max(G, 1), 0);
+  for (int i = 0; i < G; ++i) {
+    gpl[i] = pof[gidx[i]];
+    pof[gidx[i]] = 0;
   }
+  gpu_check2(ovp_plane_init_general(state->_gpu, &o, &pb, state->_options.const_init_multi, state->_options.const_init_chi2, dxp.data(),
+                                    stride, pok.data(), nullptr, nullptr, nid.data(), cpn.data(), fused.data(), &gb, gpl.data(),
+                                    gused.data()),
+             "ovp_plane_init_general");
+  for (int i = 0; i < G; ++i)
+    if (gused[i]) fused[gidx[i]] = 1;  // consumed like the batch's: feature_vec_used below
   for (int k = 0; k < NP; ++k) {
     if (!pok[k]) continue;
     // Type::update of the variables that existed before this plane, then the plane itself joins the state (:441-449)

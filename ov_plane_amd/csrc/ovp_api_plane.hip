@@ -5,78 +5,19 @@
 #include "ovp_ctx.h"
 #include "k_plane_init2.h"
 
-// device sequence shared by the plane update and the plane initialisation: feature kernel, Gram reduction, reduction to the
-// state columns, range-energy factorisation, information-form update with the factor Mf (P = Mf Mf^T), gate.
-// Leaves: V in c->Y, dx in c->dx, [chi2, ok, n_deg, pr] in c->pl_res + 4*pl, the extended Gram in c->pl_E.
-static int plane_job_device(ovp_ctx* c, const ovp_update_opts* o, const ovp::FeatParams& fp, int pl, int start, int nf,
-                            int in_state, int sid, double white_c, const double* Mf, int factor_dense, double thr,
-                            int rows_live, int rows_u, int n_involved, int force = -1) {
-  const int n = c->n, ld = c->ld, ldg = c->ldg;
-  hipStream_t s = c->stream;
-  ovp::PlaneParams pp;
-  pp.feat_list = c->pl_featlist + start;
-  pp.n_local = nf;
-  pp.plane = pl;
-  pp.in_state = in_state;
-  pp.plane_sid = sid;
-  pp.white_c = white_c;
-  pp.cp = c->pl_cp;
-  pp.cp_fej = c->pl_cp_fej;
-  pp.cst = c->pl_cst;
-  ovp::FeatParams fpl = fp;
-  fpl.n = n;
-  fpl.P = c->P;
-  HIPCHK(ovp_launch_plane_feat(&fpl, &pp, nf, s));
-  const int chunks = (2 * nf + c->rows_per_chunk - 1) / c->rows_per_chunk;
-  HIPCHK(ovp_launch_struct_gram(c->rec, fp.n_clones, nf, c->rows_per_chunk, chunks, c->gramS, s));
-  HIPCHK(ovp_launch_reduce_gram(c->gramS, fp.n_clones, chunks, c->gramR, s));
-  int nsplit = (3 * nf + 511) / 512;
-  if (nsplit < 1) nsplit = 1;
-  if (nsplit > c->n_split) nsplit = c->n_split;
-  HIPCHK(ovp_launch_syrk(c->G, 3 * nf, ldg, n + 4, nsplit, c->part, s));
-  HIPCHK(ovp_launch_reduce_cst(c->pl_cst, nf, c->pl_cstsum, s));
-  HIPCHK(ovp_launch_assemble_ext(c->gramR, fp.n_clones, c->part, nsplit, c->colmap, n, sid, c->pl_cstsum, c->pl_E, ldg, s));
-  HIPCHK(ovp_launch_plane_reduce_to_state(c->pl_E, ldg, n, in_state, c->Ab, ld, c->pl_cstsum + 9, c->pl_scal, s));
-  // range part of the residual (regularised, diagonally normalised): its own Cholesky, independent of the update's -
-  // side stream, joined before the gate (the two write different words of pl_scal)
-  hipStream_t s2 = c->stream2;
-  HIPCHK(hipEventRecord(c->ev_fork, s));
-  HIPCHK(hipStreamWaitEvent(s2, c->ev_fork, 0));
-  HIPCHK(ovp_launch_normalize_reg(c->Ab, ld, n, 1e-10, c->pl_An, c->pl_bn, s2));
-  HIPCHK(ovp_launch_tilechol(c->pl_An, c->pl_Lr, c->pl_Dinv2, nullptr, n, ld, c->flags + 2, 0, s2));
-  HIPCHK(ovp_launch_range_energy(c->pl_Lr, c->pl_Dinv2, c->pl_bn, n, ld, 1e-8, c->pl_scal, s2));
-  HIPCHK(hipEventRecord(c->ev_join, s2));
-  // EKF update in information form with the chained factor
-  HIPCHK(ovp_launch_gemm4(0, 0, n, n, n, c->Ab, ld, Mf, ld, c->W1, ld, 0, 0, s));
-  HIPCHK(ovp_launch_gemm4(1, 0, n, n, n, Mf, ld, c->W1, ld, c->T, ld, 1, 1, s));
-  HIPCHK(chol_of_T(c, c->T, n, ld, 0, nullptr, s));  // (second-generation factorization where it fits, like every other chol(T))
-  HIPCHK(ovp_launch_fwdsub(c->Ltp, c->Dinv, Mf, c->Y, n, ld, factor_dense, s));
-  HIPCHK(ovp_launch_dx_from_factor(c->Y, n, ld, c->Ab + (size_t)n * ld, c->dx, c->pl_scal, s));
-  HIPCHK(hipStreamWaitEvent(s, c->ev_join, 0));
-  HIPCHK(ovp_launch_plane_gate(c->pl_scal, c->flags, thr, rows_live, rows_u, n_involved, force, c->pl_res + 4 * pl, s));
-  return 0;
-}
-
+// the loop's per-plane results and the buffers of a plane's front end (the per-call tables travel in c->pl_dstage, plane_stage_upload)
 static int plane_buffers(ovp_ctx* c, int NP) {
   const size_t ld = (size_t)c->ld, np = (size_t)NP, n_max = (size_t)c->n_max;
-  HIPCHK(c->pl_sid.reserve(np, 8));  // the per-plane tables: NP + 8 planes
-  HIPCHK(c->pl_cp.reserve(3 * np, 3 * 8));
-  HIPCHK(c->pl_cp_fej.reserve(3 * np, 3 * 8));
-  HIPCHK(c->pl_res.reserve(4 * np, 4 * 8));
+  HIPCHK(c->pl_res.reserve(4 * np, 4 * 8));  // NP + 8 planes
   HIPCHK(c->pl_dx.reserve(n_max * np, n_max * 8));
-  HIPCHK(c->pl_featlist.alloc((size_t)c->f_max));
   HIPCHK(c->pl_cst.alloc(((size_t)c->f_max + 1) * 10));  // (+ the record of a plane's general features)
-  HIPCHK(c->pl_cstsum.alloc(16));
-  HIPCHK(c->pl_E.alloc((n_max + 4) * c->ldg));
   HIPCHK(c->pl_An.alloc((n_max + 1) * ld));
   HIPCHK(c->pl_bn.alloc(n_max));
-  HIPCHK(c->pl_Lr.alloc((n_max + 1) * ld));
-  HIPCHK(c->pl_Dinv2.alloc((ld / 16 + 1) * 256));
   HIPCHK(c->pl_scal.alloc(8));
   return 0;
 }
 
-// ---- UpdaterMSCKF::update, per-plane loop (second generation): the host structures, the result kernels, the buffers; the loop itself
+// ---- UpdaterMSCKF::update, per-plane loop: the host structures, the result kernels, the buffers; the loop itself
 // (plane_loop) is further down, behind the column-order route into it ----
 struct PlaneJobH { int pl, start, nf, rows_total, rows_live, rows_u, n_involved, in_state, sid, n_inv_cols, ns_pl; double thr;
                    int g_start, ng; /* general features: range in the list of the call */
@@ -201,7 +142,7 @@ int plane2_buffers(ovp_ctx* c, size_t stage_bytes, size_t res_bytes) {
   return 0;
 }
 
-// ---- a selection of state columns as a state of its own (plane loop in its own order, plane initialisation on the marginal) ----
+// ---- a selection of state columns as a state of its own (the plane loop in its own order) ----
 // Device block [ids | inverse | clone ids | column map] of the selection `ids` (pos = its inverse, -1 = not selected), staged in the
 // context's pinned block and sent on stream s; the kernels then address the selection through these tables instead of the state's.
 struct SubTables {
@@ -303,24 +244,18 @@ static hipError_t ensure_events(std::vector<hipEvent_t>& ev, size_t count) {  //
   return hipSuccess;
 }
 
-// sub_enter / sub_leave as a scope: every way out restores the context's view of the state (refill: and the feature parameters'
-// calibration columns with it)
+// sub_enter / sub_leave as a scope: every way out restores the context's view of the state
 struct SubScope {
   ovp_ctx* c;
-  const ovp_update_opts* refill;
   SubSaved sv;
   bool in = false;
   void enter(const SubTables& t, int ns) {
     sv = sub_enter(c, t, ns);
     in = true;
   }
-  int leave() {
-    if (!in) return 0;
-    in = false;
-    sub_leave(c, sv);
-    return refill ? fill_feat_params(c, refill) : 0;
+  ~SubScope() {
+    if (in) sub_leave(c, sv);
   }
-  ~SubScope() { (void)leave(); }
 };
 
 // A column order by first involvement: ids = the state columns in that order, pos = its inverse (-1 = not placed).
@@ -481,7 +416,7 @@ static int plane_update_ordered(ovp_ctx* c, const ovp_update_opts* o, const ovp_
   std::vector<double> dx_sub((size_t)ns * (NP > 0 ? NP : 1), 0.0);
   double* const dx_planes = out.dx_planes;
   {
-    SubScope sub{c, nullptr};
+    SubScope sub{c};
     sub.enter(st, ns);
     const PlaneOut out_sub{dx_sub.data(), out.plane_ok, out.plane_chi2, out.plane_dof, out.feat_used};
     const int rc = plane_loop(c, o, &pbs, v, out_sub);
@@ -554,7 +489,7 @@ static int plane_prelaunch(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane
   pre->fp.range_hi = 0x7fffffff;
   const size_t n_extra = v.init ? (size_t)v.init->extra : 0;
   pre->res_bytes = sizeof(double) * (4 * (size_t)NP + n_extra + (size_t)n * NP) + (size_t)F + 64 + 256;  // (+ flags and sequence word)
-  rc = plane_buffers(c, NP);  // shared with the first generation: pl_res, pl_dx, pl_cst, pl_An, ...
+  rc = plane_buffers(c, NP);
   if (rc) return rc;
   rc = plane2_buffers(c, 0, pre->res_bytes);
   if (rc) return rc;
@@ -1446,159 +1381,6 @@ extern "C" int ovp_msckf_plane_update_general(ovp_ctx* c, const ovp_update_opts*
   return rc;
 }
 
-// ---- UpdaterPlane::init_vio_plane core ----------------------------------------------------------
-extern "C" int ovp_plane_init(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, double const_init_multi,
-                              double const_init_chi2, double* dx_planes, int dx_stride, uint8_t* plane_ok, double* plane_chi2,
-                              int* plane_dof, int* new_ids, double* cp_new, uint8_t* feat_used) {
-  drop_kept_factor(c);  // (writes the covariance: a kept factor no longer belongs to it)
-  if (!c || !o || !pb || pb->n_planes < 0) return OVP_E_ARG;
-  if (!c->have_state || !c->have_cov || !c->have_batch) return OVP_E_STATE;
-  if (c->h_n_meas.empty() && c->n_feats > 0) return OVP_E_STATE;
-  const int ld = c->ld, F = c->n_feats, NP = pb->n_planes, M = c->max_meas;
-  if (feat_used) memset(feat_used, 0, (size_t)F);
-  for (int pl = 0; pl < NP; ++pl) {
-    if (plane_ok) plane_ok[pl] = 0;
-    if (plane_chi2) plane_chi2[pl] = 0.0;
-    if (plane_dof) plane_dof[pl] = 0;
-    if (new_ids) new_ids[pl] = -1;
-    if (cp_new) memcpy(cp_new + 3 * pl, pb->cp + 3 * pl, 3 * sizeof(double));
-    if (dx_planes) memset(dx_planes + (size_t)pl * dx_stride, 0, sizeof(double) * dx_stride);
-  }
-  if (NP == 0) return 0;
-  int rc = fill_feat_params(c, o);
-  if (rc) return rc;
-  rc = plane_buffers(c, NP);
-  if (rc) return rc;
-  rc = plane2_buffers(c, 0, 0);  // (pl_crow: scale vector of the pivot-dropping factor, chol_of_P on a semi-definite prior)
-  if (rc) return rc;
-  hipStream_t s = c->stream;
-  const int ncal = (o->do_calib_camera_pose ? 6 : 0) + (o->do_calib_camera_intrinsics ? 8 : 0);
-  std::vector<int> sid(NP, -1);
-  HIPCHK(hipMemcpyAsync(c->pl_sid, sid.data(), sizeof(int) * NP, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(c->pl_cp, pb->cp, sizeof(double) * 3 * NP, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(c->pl_cp_fej, pb->cp, sizeof(double) * 3 * NP, hipMemcpyHostToDevice, s));
-  HIPCHK(hipStreamSynchronize(s));
-  std::vector<double> res4(4), dxh(c->n_max), dcp(3);
-  bool psd_prior = false;
-  // The plane runs on the MARGINAL of the columns its rows can touch (clones and calibration: at most 6 * 32 + 14 of them) and the
-  // rest of the state follows from the push-through identity, like the plane loop's sub-state (plane_update_ordered):
-  // update/UpdaterPlane.cpp:296-481 has no size limit, the factorizations are those of ~80 columns instead of the state's, and the
-  // marginal of a prior with an exact stochastic clone is positive definite (no second attempt).  Closed-loop session with two
-  // planes, per frame: 0.198 ms against 0.216 on the whole state.  OVP_PLANE_INIT_SUB=0: the whole state (<= 288 columns; A/B, tests).
-  const char* sub_env = getenv("OVP_PLANE_INIT_SUB");  // (read per call)
-  const bool whole_state = sub_env && sub_env[0] == '0' && c->n <= OVP_TILECHOL_NMAX;
-  SubTables sub_t;
-  int ns = 0;
-  if (!whole_state) {
-    ColumnOrder co(c->n, c->n_max);
-    co.place_clones_and_calibration(c, o);
-    if (co.bad_id) return OVP_E_ARG;
-    ns = (int)co.ids.size();
-    if (ns > OVP_TILECHOL_NMAX) return OVP_E_CAPACITY;
-    rc = sub_tables_upload(c, o, co.ids, co.pos, &sub_t, s);
-    if (rc) return rc;
-    HIPCHK(c->pl_Asum.alloc((size_t)c->n_max * ld));
-    HIPCHK(c->pl_U.alloc((size_t)8 * ld));
-  }
-  for (int pl = 0; pl < NP; ++pl) {
-    const int n = c->n;
-    if ((n > OVP_TILECHOL_NMAX && !ns) || n + 3 > c->n_max) return OVP_E_CAPACITY;
-    std::vector<int> featlist;
-    int rows_total = 0, rows_live = 0;
-    unsigned long long seen = 0ull;
-    for (int f = 0; f < F; ++f) {
-      if (pb->plane_of_feat[f] != pl + 1) continue;
-      const int m = c->h_n_meas[f];
-      if (m < 2) continue;
-      if (m > OVP_MAX_MEAS_DEV) return OVP_E_CAPACITY;
-      featlist.push_back(f);
-      rows_total += 3 * m - 3;
-      rows_live += 2 * m - 2;
-      for (int k = 0; k < m; ++k) seen |= 1ull << c->h_clone_idx[(size_t)f * M + k];
-    }
-    const int nf = (int)featlist.size();
-    if (nf < 3) continue;  // update/UpdaterPlane.cpp:303
-    const int c_ref = 6 * __builtin_popcountll(seen) + ncal;
-    const int rows_c = rows_total > c_ref ? c_ref : rows_total;
-    if (rows_c - 3 < 1) continue;
-    // the chi2 of StateHelper::initialize covers the rows that do not involve the plane, with dof = all rows (:471)
-    const double thr = const_init_chi2 * ovp_chi2_quantile_095(rows_c);
-    HIPCHK(hipMemcpyAsync(c->pl_featlist, featlist.data(), sizeof(int) * nf, hipMemcpyHostToDevice, s));
-    ovp::FeatParams fp = c->fp;
-    // A prior that is only positive SEMI-definite (an exact stochastic clone in front of the next propagation: every frame of a
-    // running filter) fails chol(P) before anything is committed: the plane runs once more on the pivot-dropping factor of the
-    // unit-diagonal form (chol_of_P, as the plane loop does), and so do the planes behind it.
-    const int nj = ns ? ns : n;  // the size the plane's kernels run on
-    SubScope sub{c, o};  // (leaving it also puts the state's calibration columns back into c->fp)
-    if (ns) {  // the marginal of the selection stands in for the state
-      HIPCHK(ovp_launch_gather_block(c->P, ld, sub_t.d_ids, ns, c->P_tmp, ld, s));
-      sub.enter(sub_t, ns);
-      rc = fill_feat_params(c, o);  // (the calibration columns of the selection)
-      if (rc) return rc;
-      fp = c->fp;
-    }
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      rc = (int)hipMemsetAsync(c->flags, 0, sizeof(int) * 4, s);
-      if (!rc) rc = (int)hipMemsetAsync(c->pl_res + 4 * pl, 0, sizeof(double) * 4, s);
-      if (!rc) rc = chol_of_P(c, s, psd_prior);
-      if (!rc)
-        rc = plane_job_device(c, o, fp, pl, 0, nf, 0, -1, 1.0 / (const_init_multi * o->sigma_constraint), c->L, 0, thr, rows_live - 3,
-                              rows_c - 3, c_ref);
-      if (!rc) rc = (int)hipMemcpyAsync(res4.data(), c->pl_res + 4 * pl, sizeof(double) * 4, hipMemcpyDeviceToHost, s);
-      if (!rc) rc = (int)hipMemcpyAsync(c->h_flags, c->flags, sizeof(int) * 4, hipMemcpyDeviceToHost, s);
-      if (!rc) rc = (int)hipStreamSynchronize(s);
-      if (rc) break;  // (the selection's tables are taken off below before the error goes out)
-      if (!c->h_flags[0] || psd_prior || nj > ovp_chol2_max_n() + 1) break;
-      psd_prior = true;
-    }
-    if (ns) {
-      const int rf = sub.leave();
-      if (!rc) rc = rf;
-      fp = c->fp;
-    }
-    if (rc) return rc;
-    if (c->h_flags[0]) {
-      (void)hipMemsetAsync(c->flags, 0, sizeof(int) * 4, s);
-      return OVP_E_NOTSPD;
-    }
-    if (plane_chi2) plane_chi2[pl] = res4[0];
-    if (plane_dof) plane_dof[pl] = rows_c;
-    if (res4[1] < 0.5) continue;  // chi2 rejected: StateHelper::initialize returns false
-    // accepted: P <- P+ = V^T V, append the plane, update the device tables like Type::update would
-    if (ns) {
-      // the selection's posterior Pss+ = V^T V; the whole state by the push-through identity (G = P[:, s], A|b = the plane's pair on s):
-      //   u = b - A dx_s,  dx = G u ;  Lambda = A - A Pss+ A,  P -= G Lambda G^T
-      HIPCHK(ovp_launch_gemm4(1, 0, ns, ns, ns, c->Y, ld, c->Y, ld, c->P_tmp, ld, 0, 1, s));
-      HIPCHK(hipMemsetAsync(c->pl_Asum, 0, sizeof(double) * (size_t)ns * ld, s));
-      HIPCHK(ovp_launch_plane_sub_accum(c->pl_res + 4 * pl, c->Ab, c->pl_Asum, c->dx, c->pl_U, ns, ld, s));  // (Asum = A from here)
-      if (const int r = push_through_lambda(c, c->P_tmp, sub_t.d_ids, ns, s)) return r;
-      HIPCHK(ovp_launch_gemm4(0, 1, 1, n, ns, c->pl_U, ld, c->Y, ld, c->Lt, ld, 0, 0, s));
-      HIPCHK(hipMemcpyAsync(c->dx, c->Lt, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-      if (const int r = push_through_commit(c, ns, s)) return r;
-      HIPCHK(ovp_launch_plane_init_augment(c->pl_E, c->ldg, ns, sub_t.d_ids, n, c->P, ld, c->dx, c->pl_scal + 4, s));
-    } else {
-      HIPCHK(ovp_launch_gemm4(1, 0, n, n, n, c->Y, ld, c->Y, ld, c->P, ld, 0, 1, s));
-      HIPCHK(ovp_launch_plane_init_augment(c->pl_E, c->ldg, n, nullptr, n, c->P, ld, c->dx, c->pl_scal + 4, s));
-    }
-    HIPCHK(ovp_launch_plane_commit(c->pl_res + 4 * pl, nullptr /* no factor is chained here */, nullptr, n, ld, c->dx,
-                                   c->pl_dx + (size_t)pl * c->n_max, c->clone_R, c->clone_p, c->clone_id, fp.n_clones, c->cal,
-                                   o->do_calib_camera_pose ? c->calib_id : -1, o->do_calib_camera_intrinsics ? c->intr_id : -1,
-                                   c->pl_cp, c->pl_sid, 0, s));
-    HIPCHK(hipMemcpyAsync(dxh.data(), c->dx, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(dcp.data(), c->pl_scal + 4, sizeof(double) * 3, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    c->n = n + 3;
-    if (plane_ok) plane_ok[pl] = 1;
-    if (new_ids) new_ids[pl] = n;
-    if (cp_new)
-      for (int k = 0; k < 3; ++k) cp_new[3 * pl + k] = pb->cp[3 * pl + k] + dcp[k];
-    if (dx_planes) memcpy(dx_planes + (size_t)pl * dx_stride, dxh.data(), sizeof(double) * (n < dx_stride ? n : dx_stride));
-    if (feat_used)
-      for (int f : featlist) feat_used[f] = 1;
-  }
-  return 0;
-}
-
 // ---- UpdaterPlane::init_vio_plane core in one device pass, any camera (update/UpdaterPlane.cpp:296-481 over the rows of
 // update/UpdaterHelper.cpp:335-344, 448-512) ----
 // Initialisation is the loop's out-of-state plane update with a flat prior on the plane (white_c = 1 / (const_init_multi sigma_c),
@@ -1731,4 +1513,12 @@ extern "C" int ovp_plane_init_general(ovp_ctx* c, const ovp_update_opts* o, cons
   if (gen_used && any) memcpy(gen_used, marks.data(), (size_t)GF);
   c->n = n + 3 * q;
   return 0;
+}
+
+// The batch's features alone (UpdaterPlane::init_vio_plane core, camera 0): ovp_plane_init_general without a general batch.
+extern "C" int ovp_plane_init(ovp_ctx* c, const ovp_update_opts* o, const ovp_plane_batch* pb, double const_init_multi,
+                              double const_init_chi2, double* dx_planes, int dx_stride, uint8_t* plane_ok, double* plane_chi2,
+                              int* plane_dof, int* new_ids, double* cp_new, uint8_t* feat_used) {
+  return ovp_plane_init_general(c, o, pb, const_init_multi, const_init_chi2, dx_planes, dx_stride, plane_ok, plane_chi2, plane_dof,
+                                new_ids, cp_new, feat_used, nullptr, nullptr, nullptr);
 }

@@ -4,8 +4,8 @@
 //                      initialize), pose tables, feature batch, diagnostics
 //   ovp_api_point.hip  point update: K1 -> information pair -> EKF update (ovp_msckf_update and its staged form), ovp_ekf_update
 //   ovp_api_rccl.hip   feature-sharded update over RCCL
-//   ovp_api_plane.hip  plane loop (ovp_msckf_plane_update) and plane initialisation (ovp_plane_init; ovp_plane_init_general: the
-//                      loop as its front, k_plane_init2.hip as its tail)
+//   ovp_api_plane.hip  plane loop (ovp_msckf_plane_update) and plane initialisation (ovp_plane_init_general: the loop as its front,
+//                      k_plane_init2.hip as its tail; ovp_plane_init: the same without a general batch)
 //   ovp_api_slam.hip   SLAM landmarks (ovp_slam_update, ovp_slam_delayed_init), triangulation
 //   ovp_api_general.hip general point features (any camera, long tracks): camera tables, gate + pending pair, triangulation
 //   k_plane_detect.hip plane detection from the tracked features: its kernels and its entry points
@@ -93,18 +93,6 @@ hipError_t ovp_launch_dx_rows(const double* P, int n, int ldp, const double* b, 
                               hipStream_t stream);
 hipError_t ovp_launch_reduce_gram(const double* gramS, int n_clones, int n_chunks, double* gramR, hipStream_t stream);
 hipError_t ovp_launch_plane_feat(const ovp::FeatParams* p, const ovp::PlaneParams* pp, int n_local, hipStream_t stream);
-hipError_t ovp_launch_reduce_cst(const double* cst, int nf, double* out, hipStream_t stream);
-hipError_t ovp_launch_assemble_ext(const double* gramR, int n_clones, const double* part, int n_split,
-                                   const ovp::ColMap* colmap, int n, int plane_sid, const double* cstsum, double* E,
-                                   int lde, hipStream_t stream);
-hipError_t ovp_launch_plane_reduce_to_state(const double* E, int lde, int n, int in_state, double* Ab, int lda,
-                                            const double* rr_in, double* scal, hipStream_t stream);
-hipError_t ovp_launch_normalize_reg(const double* Ab, int lda, int n, double eps, double* An, double* bn,
-                                    hipStream_t stream);
-hipError_t ovp_launch_range_energy(const double* Lr, const double* Dinv, const double* bn, int n, int ld, double tol,
-                                   double* scal, hipStream_t stream);
-hipError_t ovp_launch_dx_from_factor(const double* V, int n, int ld, const double* b, double* dx, double* scal,
-                                     hipStream_t stream);
 hipError_t ovp_launch_init_m(const double* P, int ldp, int n, const int* ids, int cols, const double* Ht, int m, double* Mall,
                              hipStream_t stream);
 hipError_t ovp_launch_init_core(double* P, int ldp, int n, const int* ids, int cols, const double* Ht, int k, int rup, double* Mall,
@@ -123,19 +111,6 @@ hipError_t ovp_launch_init_update_sk(const double* skip, int res_len, const doub
                                      double* dx, hipStream_t stream);
 hipError_t ovp_launch_gemm4c(int transA, int transB, int M, int N, int K, const double* A, int lda, const double* B, int ldb,
                              double* C, int ldc, int add_identity, int symmetric, const int* cancel, hipStream_t stream);
-hipError_t ovp_launch_plane_gate(const double* scal, const int* flags, double thr, int rows_live, int rows_u,
-                                 int n_involved, int force, double* res_out, hipStream_t stream);
-hipError_t ovp_launch_plane_init_augment(const double* E, int lde, int ns, const int* ids, int n, double* P, int ldp, const double* dx, double* out,
-                                         hipStream_t stream);
-hipError_t ovp_launch_plane_slam_rows(double* E, int lde, int n, int plane1, int n_slam, const int* slam_plane, const int* slam_id,
-                                      const double* slam_p, const double* slam_p_fej, const double* cp, const double* cp_fej,
-                                      double white_c, int do_fej, double* cstsum, hipStream_t stream);
-hipError_t ovp_launch_plane_commit_slam(const double* res, const double* dx, int n_slam, const int* slam_id, double* slam_p,
-                                        hipStream_t stream);
-hipError_t ovp_launch_plane_commit(const double* res, const double* V, double* M, int n, int ld, const double* dx,
-                                   double* dx_out, double* clone_R, double* clone_p, const int* clone_id, int n_clones,
-                                   double* cal, int calib_id, int intr_id, double* cp, const int* plane_sid,
-                                   int n_planes, hipStream_t stream);
 }
 
 
@@ -219,11 +194,9 @@ struct ovp_ctx {
   DevBuf<long long> dbg_cycles;
   // plane path
   std::vector<int> h_n_meas, h_clone_idx;  // host copies of the uploaded batch (plane grouping is host logic)
-  DevBuf<int> pl_featlist, pl_sid;  // (pl_sid: its capacity is the plane capacity of the per-plane tables below)
-  DevBuf<double> pl_cp, pl_cp_fej, pl_cst, pl_cstsum, pl_E;
-  DevBuf<double> pl_An, pl_bn, pl_Lr, pl_Dinv2, pl_scal;
+  // plane loop (k_plane2.hip / k_chol2.hip): constraint-row moments, the range part's normalised pair, gate scalars, per-plane results
+  DevBuf<double> pl_cst, pl_An, pl_bn, pl_scal;
   DevBuf<double> pl_res, pl_dx;
-  // second-generation plane loop (k_plane2.hip / k_chol2.hip)
   DevBuf<double> pl_Tbuf, pl_crow, pl_dxlast;
   DevBuf<int> pl_cur;
   DevBuf<unsigned> pl_range_done;

@@ -9,7 +9,7 @@
 #define OVP_GRAM_ELEMS 231   // 21*22/2: packed upper triangle of the per-clone 21x21 Gram
 #define OVP_TC_MAX_TILES 18  // tile rows the register-resident Cholesky handles (N <= 288)
 #define OVP_BSCR 2112        // doubles of per-feature scratch for B (k_feat.hip LCOLS)
-// Plane-level gate (k_chol2.hip, k_plane.hip): weight of the expected energy of the reference's rounding-decided rows; 1 = the plain
+// Plane-level gate (k_chol2.hip): weight of the expected energy of the reference's rounding-decided rows; 1 = the plain
 // expectation (rounds 2-5: +0.35 +- 0.06 above the mean of four roundings of the oracle).  Round 6: the weight that zeroes that
 // difference on 1000 planes of config 3's shape is 0.9606 (in-state planes alone 0.9614, out-of-state 0.9598, least squares 0.9598);
 // on the 350 held-out planes of configs 3 and 4 it leaves +0.01 +- 0.13 (profiles/r06_plane_gate_kappa_fit.json,

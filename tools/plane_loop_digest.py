@@ -5,8 +5,8 @@ print the same list (the second one selected with OVP_LIB_AB):
     OVP_LIB_AB=path/to/other/libovplane_hip.so python tools/plane_loop_digest.py --out b.json
 Fixed small scenes, one per route: the loop's own column order, the state's order (OVP_PL_NATURAL_ORDER), the marginal of the involved
 columns (N = 300), SLAM landmarks on out-of-state planes, general features, a plane with general features only, the retry on a
-positive semi-definite prior, forced decisions, the forced two-workgroup solve (OVP_C2_SPLIT), ovp_plane_init on the marginal and
-on the whole state (OVP_PLANE_INIT_SUB=0), a frame without planes."""
+positive semi-definite prior, forced decisions, the forced two-workgroup solve (OVP_C2_SPLIT), ovp_plane_init, a frame without
+planes."""
 import argparse
 import contextlib
 import hashlib
@@ -106,9 +106,7 @@ def routes(capi):
         yield "c2_split_forced", plain(capi, make_scene(C=30, F=360, seed=21, n_planes=6, feats_per_plane=40, planes_in_state_frac=0.5,
                                                         chi2_mult=1.0))
     si = make_scene(C=8, F=80, seed=16, n_planes=2, feats_per_plane=25, planes_in_state_frac=0.0, chi2_mult=1.0, ragged=True)
-    yield "plane_init_marginal", plain(capi, si, init=True)
-    with env(OVP_PLANE_INIT_SUB="0"):
-        yield "plane_init_whole_state", plain(capi, si, init=True)
+    yield "plane_init", plain(capi, si, init=True)
     none = make_scene(C=8, F=40, seed=7, chi2_mult=1.0)
     assert none.cp.shape[0] == 0
     yield "no_plane", plain(capi, none)
