@@ -936,8 +936,8 @@ long ovp_active_tracks_debug(ovp_ctx *ctx, const char *what, int64_t id, double 
  * cv::calcOpticalFlowPyrLK call of perform_matching (:1299-1357).  OpenCV is not in the reference tree: the stage is restated from
  * its published form (Bouguet's pyramidal Lucas-Kanade with OpenCV's externally visible conventions: Scharr gradients, reflect-101
  * image borders, zero gradient borders, 30 iterations / 0.01 px, minEigThreshold 1e-4) and is UNPINNED; tests/klt_ref.py is the
- * restatement it is held to.  Detection (:1173-1297) is ovp_klt_detect below.  Not built: CLAHE, the RANSAC of :1344, stereo, the
- * display images. */
+ * restatement it is held to.  Detection (:1173-1297) is ovp_klt_detect below, the epipolar check (:1331-1350) ovp_klt_epipolar.  Not built: CLAHE,
+ * stereo, the display images. */
 #define OVP_KLT_MAX_POINTS 4096
 #define OVP_KLT_MAX_LEVELS 8
 #define OVP_KLT_HIST_NONE 0       /* TrackBase::HistogramMethod, in its order */
@@ -986,6 +986,49 @@ int ovp_klt_track(ovp_ctx *ctx, int n, const float *pts_prev, const float *guess
 #define OVP_FAST_MAX_K 256
 int ovp_klt_detect(ovp_ctx *ctx, int half, int num_features, int grid_x, int grid_y, int threshold, int *n_out, int32_t *xy_int,
                    int32_t *response, float *xy_refined, int32_t *cell, int cap);
+/* The epipolar check of perform_matching (:1331-1350): undistort_cv of both point sets, cv::findFundamentalMat(FM_RANSAC, threshold,
+ * confidence) on the normalised points, mask_out = status & mask_rsc.  OpenCV and ov_core are not in the reference tree: the stage
+ * is RECALLED from its published form (cv::undistortPoints' 5 iterations, cv::fisheye::undistortPoints' Newton steps, run7Point,
+ * computeError, checkSubset, RANSACPointSetRegistrator::run without a refit) and UNPINNED; tests/epi_ref.py is the restatement it
+ * is held to.  This library's own: the draws (a stateless counter-based generator - cv::RNG's cannot be reproduced), at most
+ * OVP_EPI_MAX_SUBSET_TRIES sets per hypothesis, the null space by elimination with complete pivoting, and that every one of
+ * max_iters hypotheses is evaluated on the device (the sequential loop's early stop is replayed over their counts). */
+#define OVP_EPI_MAX_ITERS 1024
+#define OVP_EPI_MAX_SUBSET_TRIES 8
+#define OVP_EPI_MIN_POINTS 10     /* :1319 */
+#define OVP_EPI_MODE_NORMALISED 0 /* the points are normalised coordinates already: passed through */
+#define OVP_EPI_MODE_RADTAN 1     /* intrinsics fx fy cx cy k1 k2 p1 p2 */
+#define OVP_EPI_MODE_EQUIDISTANT 2 /* intrinsics fx fy cx cy k1 k2 k3 k4 */
+typedef struct ovp_epipolar_opts {
+  int32_t mode;          /* OVP_EPI_MODE_* */
+  int32_t max_iters;     /* 1..OVP_EPI_MAX_ITERS; 1000 */
+  double intrinsics[8];
+  double threshold;      /* in normalised units, > 0: the caller's 2.0 / max(fx, fy) (:1341-1344) */
+  double confidence;     /* in (0, 1); 0.999 */
+  uint32_t seed;
+  uint32_t reserved;
+} ovp_epipolar_opts;
+typedef struct ovp_epipolar_info {
+  double F[9];           /* the winner, row-major, F33 = 1 unless it was tiny; zeros without a model */
+  int32_t best_count;    /* its inliers among all n points, status or not */
+  int32_t winner_h, winner_model; /* -1 without a model */
+  int32_t niters;        /* of the replayed loop, at its end */
+  int32_t n_with_model;  /* hypotheses that gave at least one model */
+  int32_t too_few;       /* n < OVP_EPI_MIN_POINTS (:1319-1323): the mask is all zeros */
+  int32_t no_model;      /* no hypothesis beat 6 inliers: the mask is all zeros */
+  int32_t stop;          /* the first hypothesis the replayed loop did not look at */
+} ovp_epipolar_info;
+void ovp_epipolar_defaults(ovp_epipolar_opts *o);
+/* n points: pts0 / pts1 [2n] f32 pixels of the previous and the current image (normalised values in mode 0), status [n] (NULL: all
+ * ones; the RANSAC sees every point whatever its status, :1333-1344).  Writes mask_out [n], uvn0 / uvn1 [2n] f32 (the undistorted
+ * coordinates) and info; any output may be NULL.  One upload, four launches (k_epi_undistort, k_epi_models, k_epi_count,
+ * k_epi_select), one publication through the tracker's mailbox: one enqueue, one wait.  f64 with contraction off; two runs give
+ * the same bytes.  Decided on the host with nothing enqueued and the outputs untouched: OVP_E_STATE without a tracker,
+ * OVP_E_CAPACITY for n > max_points, OVP_E_ARG for n < 0, a null input, a non-finite coordinate or intrinsic, an unknown mode, a
+ * threshold that is not positive and finite, a confidence outside (0, 1), max_iters outside 1..OVP_EPI_MAX_ITERS.  n = 0 returns
+ * at once; n < OVP_EPI_MIN_POINTS returns success with a zero mask and too_few (the coordinates are still undistorted). */
+int ovp_klt_epipolar(ovp_ctx *ctx, const ovp_epipolar_opts *opts, int n, const float *pts0, const float *pts1, const uint8_t *status,
+                     uint8_t *mask_out, float *uvn0, float *uvn1, ovp_epipolar_info *info);
 /* tests: what = "cur" / "prev": the bytes of pyramid level `level` of that half (rows packed); "equalized": level 0 of the current
  * half; "dims": int32 [width, height] of the level; "iters": uint8 [n][8] iterations per level of the last ovp_klt_track (none
  * behind an ovp_klt_detect, which takes the mailbox); "score" / "nms": uint8 [height][width], the level-0 score map of the last
@@ -993,7 +1036,11 @@ int ovp_klt_detect(ovp_ctx *ctx, int half, int num_features, int grid_x, int gri
  * caller's on level 0 of the current half - out holds float [2n] starting positions on entry and the refined ones on return;
  * "timer": level != 0 puts events around the kernels (and a stream synchronisation behind each entry) from the next call on,
  * "time": float GPU milliseconds of the last timed calls [equalise, pyramid launches together, k_klt_track, k_fast_score_nms,
- * k_fast_select, k_fast_subpix] - as many as cap holds, at least the first 3.  Returns the number of bytes (or < 0). */
+ * k_fast_select, k_fast_subpix, k_epi_undistort, k_epi_models, k_epi_count, k_epi_select] - as many as cap holds, at least the
+ * first 3.  Of the last ovp_klt_epipolar that ran its RANSAC (n >= OVP_EPI_MIN_POINTS; OVP_E_STATE before one; H its max_iters, level is
+ * ignored): "epi_samples"
+ * int32 [H][7] (-1 without a set), "epi_models" int32 [H] n_models then double [H][3][9] (the doubles start at the next multiple
+ * of 8 bytes), "epi_counts" int32 [H][3], "epi_table" int32 [n + 1].  Returns the number of bytes (or < 0). */
 long ovp_klt_debug(ovp_ctx *ctx, const char *what, int level, void *out, long cap);
 
 /* ---- diagnostics ---------------------------------------------------------------------------- */

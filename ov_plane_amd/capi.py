@@ -275,7 +275,20 @@ EXPORTS = [
     "ovp_cov_marginalize_many", "ovp_planes_merge_retire", "ovp_zupt_update",
     "ovp_propagate_and_clone",
     "ovp_klt_create", "ovp_klt_destroy", "ovp_klt_reset", "ovp_klt_feed_image", "ovp_klt_track", "ovp_klt_debug", "ovp_klt_detect",
+    "ovp_epipolar_defaults", "ovp_klt_epipolar",
 ]
+
+
+class EpipolarOpts(C.Structure):
+    """ovp_epipolar_opts"""
+    _fields_ = [("mode", C.c_int32), ("max_iters", C.c_int32), ("intrinsics", C.c_double * 8), ("threshold", C.c_double),
+                ("confidence", C.c_double), ("seed", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class EpipolarInfo(C.Structure):
+    """ovp_epipolar_info"""
+    _fields_ = [("F", C.c_double * 9), ("best_count", C.c_int32), ("winner_h", C.c_int32), ("winner_model", C.c_int32),
+                ("niters", C.c_int32), ("n_with_model", C.c_int32), ("too_few", C.c_int32), ("no_model", C.c_int32), ("stop", C.c_int32)]
 
 
 def lib():
@@ -404,6 +417,10 @@ def lib():
         L.ovp_klt_track.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ovp_klt_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int]
+        L.ovp_epipolar_defaults.restype = None
+        L.ovp_epipolar_defaults.argtypes = [C.c_void_p]
+        L.ovp_klt_epipolar.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]
         L.ovp_klt_debug.restype = C.c_long
         L.ovp_klt_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_long]
         _LIB = L
@@ -775,13 +792,69 @@ class KltTracker:
                 kp.append(p), ki.append(self.currid)
         return np.array(kp, dtype=np.float32).reshape(-1, 2), np.array(ki, dtype=np.int64)
 
-    def step(self, img, mask=None, hist="HISTOGRAM", detect=False):
+    CAMERA_MODES = {"normalised": 0, "radtan": 1, "equidistant": 2}
+
+    def epipolar(self, pts0, pts1, status=None, camera=None, **opts):
+        """ovp_klt_epipolar: the epipolar check of perform_matching (:1331-1350) on pts0 / pts1 [n, 2] f32 (pixels; normalised values
+        without a camera), status [n] (None: all ones).  camera: None, or (mode, intrinsics [8]) with mode "normalised", "radtan" or
+        "equidistant".  opts: threshold (default 2 / max(fx, fy), :1341-1344), confidence, max_iters, seed.  -> dict(mask [n] uint8,
+        uvn0 / uvn1 [n, 2] f32, F [3, 3], count, winner (h, model), niters, stop, n_with_model, too_few, no_model)"""
+        o = EpipolarOpts()
+        lib().ovp_epipolar_defaults(C.byref(o))
+        if camera is not None:
+            mode, intr = camera
+            o.mode = self.CAMERA_MODES[mode] if isinstance(mode, str) else int(mode)
+            o.intrinsics[:] = [float(v) for v in intr]
+            if o.mode:
+                o.threshold = 2.0 / max(float(intr[0]), float(intr[1]))
+        for k, v in opts.items():
+            if k not in ("threshold", "confidence", "max_iters", "seed"):
+                raise TypeError("unknown option %s" % k)
+            setattr(o, k, v)
+        p0 = np.ascontiguousarray(pts0, dtype=np.float32).reshape(-1, 2)
+        n = len(p0)
+        p1 = np.ascontiguousarray(pts1, dtype=np.float32).reshape(n, 2)
+        st = None if status is None else np.ascontiguousarray(status, dtype=np.uint8).reshape(n)
+        mask, u0, u1 = np.full(n, 255, dtype=np.uint8), np.full((n, 2), -1.0, dtype=np.float32), np.full((n, 2), -1.0, dtype=np.float32)
+        info = EpipolarInfo()
+        info.winner_h = -7
+        t0 = time.perf_counter()
+        rc = lib().ovp_klt_epipolar(self.ctx.handle, C.byref(o), n, p0.ctypes.data, p1.ctypes.data, None if st is None else st.ctypes.data,
+                                    mask.ctypes.data, u0.ctypes.data, u1.ctypes.data, C.byref(info))
+        self.last_epipolar_ms = 1e3 * (time.perf_counter() - t0)
+        self.last_epipolar_raw = (mask, u0, u1, info)  # (tests: untouched by a refusal)
+        _chk(rc, "ovp_klt_epipolar")
+        self._epi_shape = (int(o.max_iters), n)
+        if n == 0:
+            return dict(mask=mask, uvn0=u0, uvn1=u1, F=np.zeros((3, 3)), count=0, winner=(-1, -1), niters=0, stop=0, n_with_model=0,
+                        too_few=False, no_model=False)
+        return dict(mask=mask, uvn0=u0, uvn1=u1, F=np.array(info.F[:]).reshape(3, 3), count=int(info.best_count),
+                    winner=(int(info.winner_h), int(info.winner_model)), niters=int(info.niters), stop=int(info.stop),
+                    n_with_model=int(info.n_with_model), too_few=bool(info.too_few), no_model=bool(info.no_model))
+
+    def epipolar_stages(self):
+        """tests: what the kernels of the last epipolar() left -> dict(samples [H, 7], n_models [H], models [H, 3, 9], counts [H, 3],
+        table [n + 1])"""
+        H, n = self._epi_shape
+        off = (4 * H + 7) & ~7
+        m = self._debug(b"epi_models", 0, off + 8 * 27 * H)
+        return dict(samples=self._debug(b"epi_samples", 0, 28 * H, np.int32).reshape(H, 7).copy(),
+                    n_models=m[:4 * H].view(np.int32).copy(), models=m[off:].view(np.float64).reshape(H, 3, 9).copy(),
+                    counts=self._debug(b"epi_counts", 0, 12 * H, np.int32).reshape(H, 3).copy(),
+                    table=self._debug(b"epi_table", 0, 4 * (n + 1), np.int32).copy())
+
+    def step(self, img, mask=None, hist="HISTOGRAM", detect=False, epipolar=None):
         """feed_monocular :505-567 minus detection and the epipolar check: feeds img, tracks pts_last into it with guess = pts_last,
         keeps a point unless x < 0, y < 0, (int) x >= cols, (int) y >= rows, mask > 127 at the truncated pixel, or status 0.
         Returns (ids, pts) of the kept points, which are pts_last / ids_last from here on.
         detect=True is feed_monocular :477-567 minus the epipolar check: without points it detects on the current image and returns
-        (:477-491); otherwise it tops pts_last up on the previous half under the previous image's mask (:505-507), then tracks."""
+        (:477-491); otherwise it tops pts_last up on the previous half under the previous image's mask (:505-507), then tracks.
+        epipolar: None, or dict(camera=(mode, intrinsics), threshold=, confidence=, max_iters=, seed=): perform_matching in full
+        (:1299-1357) - fewer than 10 points go in: no KLT, nothing is kept (:1319-1323); none goes in: the reset of :520-530
+        (last_reset); otherwise mask_out = status & mask_rsc decides with the rules above, and last_uv_norm holds the kept points'
+        undistorted coordinates (:555)."""
         self.feed_image(img, hist)
+        self.last_uv_norm, self.last_reset = np.zeros((0, 2), dtype=np.float32), False
         self.last_match = (np.zeros((0, 2), dtype=np.float32), np.zeros(0, dtype=np.uint8))
         if detect:
             mask_prev, self._mask_last = self._mask_last, (None if mask is None else np.array(mask, dtype=np.uint8))
@@ -790,16 +863,28 @@ class KltTracker:
                 return self.ids_last.copy(), self.pts_last.copy()
             self.pts_last, self.ids_last = self.detect(1, mask_prev, self.pts_last, self.ids_last)
             self.last_topped = (self.ids_last.copy(), self.pts_last.copy())
+        if epipolar is not None and self._fed >= 2:
+            if len(self.ids_last) == 0:          # :1307 an empty mask -> :520-530
+                self.last_reset = True
+                return self.ids_last.copy(), self.pts_last.copy()
+            if len(self.ids_last) < 10:          # :1319-1323 all zeros, no KLT
+                self.ids_last, self.pts_last = np.zeros(0, dtype=np.int64), np.zeros((0, 2), dtype=np.float32)
+                return self.ids_last.copy(), self.pts_last.copy()
         if self._fed < 2 or len(self.ids_last) == 0:
             return self.ids_last.copy(), self.pts_last.copy()
         p, st = self.track(self.pts_last, self.pts_last)
         self.last_match = (p, st)  # of the points that went into this step, in their order
+        if epipolar is not None:
+            self.last_epipolar = self.epipolar(self.pts_last, p, st, **epipolar)
+            st, uvn = self.last_epipolar["mask"], self.last_epipolar["uvn1"]
         x, y = p[:, 0], p[:, 1]
         xi, yi = np.clip(x, 0, self.width - 1).astype(np.int64), np.clip(y, 0, self.height - 1).astype(np.int64)
         keep = (st != 0) & ~(x < 0) & ~(y < 0) & (np.trunc(x) < self.width) & (np.trunc(y) < self.height)
         if mask is not None:
             keep &= ~(np.asarray(mask)[yi, xi] > 127)
         self.ids_last, self.pts_last = self.ids_last[keep], p[keep]
+        if epipolar is not None:
+            self.last_uv_norm = uvn[keep]
         return self.ids_last.copy(), self.pts_last.copy()
 
     def _debug(self, what, level, nbytes, dtype=np.uint8):
@@ -826,9 +911,11 @@ class KltTracker:
         self._debug(b"timer", 1 if on else 0, 0)
 
     def kernel_ms(self):
-        """GPU milliseconds of the last timed calls: dict(equalize, pyramid, track, score_nms, select, subpix)"""
-        t = self._debug(b"time", 0, 24, np.float32)
-        return dict(zip(("equalize", "pyramid", "track", "score_nms", "select", "subpix"), (float(v) for v in t)))
+        """GPU milliseconds of the last timed calls: dict(equalize, pyramid, track, score_nms, select, subpix, epi_undistort,
+        epi_models, epi_count, epi_select)"""
+        t = self._debug(b"time", 0, 40, np.float32)
+        return dict(zip(("equalize", "pyramid", "track", "score_nms", "select", "subpix", "epi_undistort", "epi_models", "epi_count",
+                         "epi_select"), (float(v) for v in t)))
 
     def refine(self, xy):
         """tests: k_fast_subpix from the starting positions xy [n, 2] on level 0 of the current half -> [n, 2] f32"""

@@ -76,6 +76,13 @@ int ovph_run_klt_sequence(int device, int width, int height, int n_frames, const
 int ovph_run_klt_detect_sequence(int device, int width, int height, int n_frames, const uint8_t *frames, const uint8_t *mask,
                                  int pyr_levels, int win_size, int hist_method, int max_points, const int32_t *detector5, int32_t *n_kept,
                                  int64_t *kept_ids, float *kept_uv);
+// ovph_run_klt_sequence with the epipolar check on (feed_new_camera(.., false, true) under set_camera(mode, intrinsics8) and
+// set_epipolar_options(0.999, max_iters, seed)): per frame f additionally kept_uvn[f][n_pts][2], the kept points' undistorted
+// coordinates, and reset[f] (:520-530).
+int ovph_run_klt_epipolar_sequence(int device, int width, int height, int n_frames, const uint8_t *frames, const uint8_t *mask,
+                                   int pyr_levels, int win_size, int hist_method, int n_pts, const int64_t *ids, const float *uv,
+                                   int mode, const double *intrinsics8, int max_iters, uint32_t seed, int32_t *n_kept, int64_t *kept_ids,
+                                   float *kept_uv, float *kept_uvn, int32_t *reset);
 
 #ifdef __cplusplus
 }

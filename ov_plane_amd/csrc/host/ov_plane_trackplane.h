@@ -9,7 +9,10 @@
 // (:1326-1330, :1352-1356); both pyramids live in the tracker of the device context (ovp_klt_*).  add_points() seeds or tops up
 // pts_last / ids_last with a caller's points; perform_detection_monocular() is :1173-1297 on the device's candidates
 // (ovp_klt_detect: Grider_FAST and OpenCV are not in the reference tree, that stage is recalled and unpinned), and
-// feed_new_camera(.., detect = true) feed_monocular's use of it (:477-491, :505-507).
+// feed_new_camera(.., detect = true) feed_monocular's use of it (:477-491, :505-507).  perform_matching() is :1299-1357 in full -
+// perform_matching_klt, then the epipolar check on the device (ovp_klt_epipolar: recalled and unpinned, tests/epi_ref.py) under the
+// camera of set_camera() - and feed_new_camera(.., epipolar = true) feed_monocular's use of it (:510-567), the reset of :520-530
+// included; get_last_uv_norm() holds the kept points' undistorted coordinates (:555).
 #pragma once
 #include <array>
 #include <cmath>
@@ -195,12 +198,95 @@ class TrackPlane {
     return rc;
   }
 
+  // undistort_cv's camera: OVP_EPI_MODE_* and its 8 intrinsics; the threshold of :1341-1344 is 2 / max(fx, fy) (mode
+  // OVP_EPI_MODE_NORMALISED: the defaults' threshold, or the one of set_epipolar_options)
+  int set_camera(int mode, const double *intrinsics) {
+    if (!intrinsics || mode < OVP_EPI_MODE_NORMALISED || mode > OVP_EPI_MODE_EQUIDISTANT) return OVP_E_ARG;
+    _epi.mode = mode;
+    for (int k = 0; k < 8; ++k) _epi.intrinsics[k] = intrinsics[k];
+    if (mode != OVP_EPI_MODE_NORMALISED) _epi.threshold = 2.0 / std::max(intrinsics[0], intrinsics[1]);
+    return 0;
+  }
+  // the RANSAC's own options (:1344 passes 0.999; max_iters and the seed are this library's); threshold <= 0 keeps the camera's
+  void set_epipolar_options(double confidence, int max_iters, uint32_t seed, double threshold = 0.0) {
+    _epi.confidence = confidence, _epi.max_iters = max_iters, _epi.seed = seed;
+    if (threshold > 0.0) _epi.threshold = threshold;
+  }
+
+  // :1299-1357 on the host, the two device calls handed in (tests stub them): track(pts0, pts1, mask_klt) -> code is the KLT call,
+  // which moves pts1; epi(pts0, pts1, mask_klt, mask_out, uvn1) -> code the epipolar check, mask_out = mask_klt & mask_rsc.
+  // No points: mask_out stays empty (:1307); fewer than 10: all zeros and no KLT (:1319-1323).
+  template <class Track, class Epi>
+  static int matching(const std::vector<float> &pts0, std::vector<float> &pts1, std::vector<uint8_t> &mask_out, std::vector<float> &uvn1,
+                      Track &&track, Epi &&epi) {
+    mask_out.clear(), uvn1.clear();
+    if (pts0.size() != pts1.size() || (pts0.size() & 1)) return OVP_E_ARG;
+    const size_t n = pts0.size() / 2;
+    if (n == 0) return 0;
+    if (n < OVP_EPI_MIN_POINTS) {
+      mask_out.assign(n, 0);
+      return 0;
+    }
+    std::vector<uint8_t> mask_klt;
+    int rc = track(pts0, pts1, mask_klt);
+    if (rc) return rc;
+    mask_out.assign(n, 0), uvn1.assign(2 * n, 0.f);
+    return epi(pts0, pts1, mask_klt, mask_out, uvn1);
+  }
+
+  int perform_matching(const std::vector<float> &pts0, std::vector<float> &pts1, std::vector<uint8_t> &mask_out, std::vector<float> &uvn1) {
+    return matching(
+        pts0, pts1, mask_out, uvn1,
+        [&](const std::vector<float> &p0, std::vector<float> &p1, std::vector<uint8_t> &mk) { return perform_matching_klt(p0, p1, mk); },
+        [&](const std::vector<float> &p0, const std::vector<float> &p1, const std::vector<uint8_t> &mk, std::vector<uint8_t> &mo,
+            std::vector<float> &u1) {
+          return ovp_klt_epipolar(_gpu, &_epi, (int)mk.size(), p0.data(), p1.data(), mk.data(), mo.data(), nullptr, u1.data(), &_epi_info);
+        });
+  }
+
+  // feed_monocular :510-567 behind the top-up, on the host: matching(pts0, pts1, mask_out, uvn1) -> code is perform_matching.  An
+  // empty mask resets (:520-530); otherwise a point is kept unless x < 0, y < 0, (int) x >= w, (int) y >= h, it lies in the mask,
+  // or mask_out is 0.  match_pts / match_mask: what went in, moved, and its mask.
+  template <class Matching>
+  static int matching_frame(int w, int h, const uint8_t *mask, std::vector<size_t> &ids_last, std::vector<float> &pts_last,
+                            std::vector<float> &uvn_last, std::vector<float> &match_pts, std::vector<uint8_t> &match_mask, bool &reset,
+                            Matching &&matching) {
+    std::vector<float> pts_new = pts_last, uvn;  // :512
+    std::vector<uint8_t> mask_ll;
+    reset = false;
+    uvn_last.clear(), match_pts.clear(), match_mask.clear();
+    const int rc = matching(pts_last, pts_new, mask_ll, uvn);
+    if (rc) return rc;
+    if (mask_ll.empty()) {  // :520-530
+      pts_last.clear(), ids_last.clear();
+      reset = true;
+      return 0;
+    }
+    std::vector<float> good, good_n;
+    std::vector<size_t> good_ids;
+    for (size_t i = 0; i < ids_last.size(); ++i) {
+      const float x = pts_new[2 * i], y = pts_new[2 * i + 1];
+      if (x < 0 || y < 0 || (int)x >= w || (int)y >= h) continue;            // :538-540
+      if (mask && mask[(size_t)(int)y * w + (int)x] > 127) continue;          // :543-544
+      if (!mask_ll[i]) continue;                                               // :546
+      good.push_back(x), good.push_back(y), good_ids.push_back(ids_last[i]);
+      if (2 * i + 1 < uvn.size()) good_n.push_back(uvn[2 * i]), good_n.push_back(uvn[2 * i + 1]);  // :555
+    }
+    if (uvn.size() == pts_new.size()) match_pts = pts_new;  // (the KLT ran)
+    match_mask = mask_ll;
+    pts_last.swap(good), ids_last.swap(good_ids), uvn_last.swap(good_n);    // :560-567
+    return 0;
+  }
+
   // One camera image (8-bit, h rows of `stride` bytes) and its mask (h x w, NULL: none; a value above 127 masks the pixel):
   // :40-92 equalise and build the pyramid, then :514-567 track pts_last into it and keep a point unless x < 0, y < 0,
   // (int) x >= cols, (int) y >= rows, it lies in the mask, or its status is 0.  Returns 0 or an OVP_E_* code.
   // detect: feed_monocular :477-567 minus the epipolar check - without points, detection on this image and return (:477-491);
   // otherwise pts_last is topped up on the previous image under its mask (:505-507) before it is tracked.
-  int feed_new_camera(double time, const uint8_t *img, int w, int h, int stride, const uint8_t *mask = nullptr, bool detect = false) {
+  // epipolar: perform_matching in full decides (:510-567): fewer than 10 points keep nothing, none resets (last_reset()), and
+  // get_last_uv_norm() holds the kept points' undistorted coordinates.  Off by default: nothing existing changes.
+  int feed_new_camera(double time, const uint8_t *img, int w, int h, int stride, const uint8_t *mask = nullptr, bool detect = false,
+                      bool epipolar = false) {
     if (!_klt_made) {
       const int rc = ovp_klt_create(_gpu, w, h, _pyr_levels + 1, _win_size, _klt_max_points);
       if (rc) return rc;
@@ -220,6 +306,12 @@ class TrackPlane {
       rc = perform_detection_monocular(1, mask_prev.empty() ? nullptr : mask_prev.data(), _pts_last, _ids_last);
       if (rc) return rc;
     }
+    _uvn_last.clear(), _last_reset = false;
+    if (epipolar && _n_images >= 2)
+      return matching_frame(w, h, mask, _ids_last, _pts_last, _uvn_last, _match_pts, _match_mask, _last_reset,
+                            [&](const std::vector<float> &p0, std::vector<float> &p1, std::vector<uint8_t> &mo, std::vector<float> &u1) {
+                              return perform_matching(p0, p1, mo, u1);
+                            });
     if (_n_images < 2 || _ids_last.empty()) return 0;
     std::vector<float> pts_new = _pts_last;  // :512 pts_left_new = pts_left_old
     rc = perform_matching_klt(_pts_last, pts_new, _match_mask);
@@ -241,6 +333,9 @@ class TrackPlane {
   const std::vector<float> &get_last_pts() const { return _pts_last; }          // [2n]
   const std::vector<float> &get_last_match_pts() const { return _match_pts; }   // of the points that went into the last frame
   const std::vector<uint8_t> &get_last_match_mask() const { return _match_mask; }
+  const std::vector<float> &get_last_uv_norm() const { return _uvn_last; }     // [2n] of the kept points, with the check on
+  const ovp_epipolar_info &get_last_epipolar_info() const { return _epi_info; }
+  bool last_reset() const { return _last_reset; }
 
   // history of planes which have been merged into others (TrackPlane.h:145-149)
   std::map<size_t, std::set<size_t>> get_plane2oldplane() const {
@@ -271,6 +366,15 @@ class TrackPlane {
   size_t _currid = 0;
   bool _last_detected = false;
   std::vector<uint8_t> _mask_last;  // img_mask_last: the previous image's mask, for the top-up
+  // epipolar check
+  ovp_epipolar_opts _epi = [] {
+    ovp_epipolar_opts o;
+    ovp_epipolar_defaults(&o);
+    return o;
+  }();
+  ovp_epipolar_info _epi_info = {};
+  std::vector<float> _uvn_last;
+  bool _last_reset = false;
 };
 
 }  // namespace ov_plane

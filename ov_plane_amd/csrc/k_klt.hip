@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "k_fast.h"  // detection: k_fast_score_nms, k_fast_select, k_fast_subpix (ovp_klt_detect below)
+#include "k_epipolar.h"  // the epipolar check: the launches of k_epipolar.hip (ovp_klt_epipolar below)
 
 namespace {
 
@@ -247,6 +248,11 @@ struct Klt {
   DevBuf<unsigned> hist;
   DevBuf<unsigned char> score, nms;  // ovp_klt_detect: the level-0 score map and the same after suppression
   bool det_done = false;
+  DevBuf<int> epi_samples, epi_nmodels, epi_counts;  // ovp_klt_epipolar: what its kernels leave for ovp_klt_debug
+  DevBuf<double> epi_models;
+  std::vector<int32_t> epi_table;
+  int epi_H = 0;  // max_iters of the last ovp_klt_epipolar that ran its kernels (0: none)
+  hipEvent_t ev_epi[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   PinnedBuf<unsigned char> himg;  // the upload's staging, rows packed
   PinnedBuf<void> hstage;
   DevBuf<void> dstage, dres;
@@ -257,10 +263,12 @@ struct Klt {
   hipEvent_t ev_eq0 = nullptr, ev_eq1 = nullptr, ev_pyr1 = nullptr, ev_trk0 = nullptr, ev_trk1 = nullptr;  // timed mode
   hipEvent_t ev_det[4] = {nullptr, nullptr, nullptr, nullptr};
   bool up_pending = false, timed = false;
-  float ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // equalise, pyramid launches together, k_klt_track, k_fast_score_nms, k_fast_select, k_fast_subpix
+  // equalise, pyramid launches together, k_klt_track, k_fast_score_nms, k_fast_select, k_fast_subpix, then the four k_epi_* kernels
+  float ms[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int last_n = 0;
   ~Klt() {
-    for (hipEvent_t e : {ev_up, ev_eq0, ev_eq1, ev_pyr1, ev_trk0, ev_trk1, ev_det[0], ev_det[1], ev_det[2], ev_det[3]})
+    for (hipEvent_t e : {ev_up, ev_eq0, ev_eq1, ev_pyr1, ev_trk0, ev_trk1, ev_det[0], ev_det[1], ev_det[2], ev_det[3], ev_epi[0], ev_epi[1], ev_epi[2],
+                         ev_epi[3], ev_epi[4]})
       if (e) (void)hipEventDestroy(e);
   }
 };
@@ -290,14 +298,21 @@ extern "C" int ovp_klt_create(ovp_ctx* c, int width, int height, int n_levels, i
   HIPCHK(d->score.alloc((size_t)width * height));
   HIPCHK(d->nms.alloc((size_t)width * height));
   HIPCHK(d->himg.alloc((size_t)width * height));
-  d->stage_cap = 64 * 2 + sizeof(float) * 4 * (size_t)max_points;
-  d->res_cap = 64 * 3 + std::max(sizeof(float) * 2 + 1 + KLT_MAX_LEVELS, sizeof(int) * 3 + sizeof(float) * 2) * (size_t)max_points;  // a track's results or a detection's
+  // a track's points and guesses, or an epipolar check's two point sets, status and table
+  d->stage_cap = 64 * 4 + (sizeof(float) * 4 + 1 + sizeof(int)) * (size_t)max_points + sizeof(int);
+  // a track's results, a detection's, or an epipolar check's (mask, two coordinate sets, info)
+  d->res_cap = 64 * 4 + sizeof(EpiInfoDev) + std::max(sizeof(float) * 2 + 1 + KLT_MAX_LEVELS, sizeof(int) * 3 + sizeof(float) * 2) * (size_t)max_points;
+  HIPCHK(d->epi_samples.alloc((size_t)EPI_MAX_ITERS * 7));
+  HIPCHK(d->epi_nmodels.alloc(EPI_MAX_ITERS));
+  HIPCHK(d->epi_counts.alloc((size_t)EPI_MAX_ITERS * 3));
+  HIPCHK(d->epi_models.alloc((size_t)EPI_MAX_ITERS * 27));
   HIPCHK(d->hstage.alloc(d->stage_cap));
   HIPCHK(d->dstage.alloc(d->stage_cap));
   HIPCHK(d->dres.alloc(d->res_cap));
   HIPCHK(d->hres.alloc(d->res_cap));
   HIPCHK(hipEventCreateWithFlags(&d->ev_up, hipEventDisableTiming));
-  for (hipEvent_t* e : {&d->ev_eq0, &d->ev_eq1, &d->ev_pyr1, &d->ev_trk0, &d->ev_trk1, &d->ev_det[0], &d->ev_det[1], &d->ev_det[2], &d->ev_det[3]})
+  for (hipEvent_t* e : {&d->ev_eq0, &d->ev_eq1, &d->ev_pyr1, &d->ev_trk0, &d->ev_trk1, &d->ev_det[0], &d->ev_det[1], &d->ev_det[2], &d->ev_det[3],
+                        &d->ev_epi[0], &d->ev_epi[1], &d->ev_epi[2], &d->ev_epi[3], &d->ev_epi[4]})
     HIPCHK(hipEventCreate(e));
   c->klt = d;
   return 0;
@@ -510,10 +525,108 @@ extern "C" int ovp_klt_detect(ovp_ctx* c, int half, int num_features, int grid_x
   return 0;
 }
 
+extern "C" void ovp_epipolar_defaults(ovp_epipolar_opts* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->mode = OVP_EPI_MODE_NORMALISED, o->max_iters = 1000;
+  o->intrinsics[0] = o->intrinsics[1] = 1.0;
+  o->threshold = 2.0 / 458.654, o->confidence = 0.999, o->seed = 0u;
+}
+
+extern "C" int ovp_klt_epipolar(ovp_ctx* c, const ovp_epipolar_opts* o, int n, const float* pts0, const float* pts1, const uint8_t* status,
+                                uint8_t* mask_out, float* uvn0, float* uvn1, ovp_epipolar_info* info) {
+  static_assert(sizeof(EpiInfoDev) == sizeof(ovp_epipolar_info), "the device writes ovp_epipolar_info in place");
+  Klt* d = klt_of(c);
+  if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
+  // ---- every check before anything is touched or enqueued ----
+  if (!o || n < 0) return OVP_E_ARG;
+  if (o->mode != OVP_EPI_MODE_NORMALISED && o->mode != OVP_EPI_MODE_RADTAN && o->mode != OVP_EPI_MODE_EQUIDISTANT) return OVP_E_ARG;
+  if (!(o->threshold > 0.0) || !std::isfinite(o->threshold) || !(o->confidence > 0.0 && o->confidence < 1.0)) return OVP_E_ARG;
+  if (o->max_iters < 1 || o->max_iters > OVP_EPI_MAX_ITERS) return OVP_E_ARG;
+  for (double v : o->intrinsics)
+    if (!std::isfinite(v)) return OVP_E_ARG;
+  if (o->mode != OVP_EPI_MODE_NORMALISED && (o->intrinsics[0] == 0.0 || o->intrinsics[1] == 0.0)) return OVP_E_ARG;
+  if (n > d->max_points) return OVP_E_CAPACITY;
+  if (n == 0) return 0;
+  if (!pts0 || !pts1) return OVP_E_ARG;
+  for (int i = 0; i < 2 * n; ++i)
+    if (!std::isfinite(pts0[i]) || !std::isfinite(pts1[i])) return OVP_E_ARG;
+  const bool few = n < OVP_EPI_MIN_POINTS;
+  StageLayout L;
+  const size_t o_p0 = L.take(sizeof(float) * 2 * n), o_p1 = L.take(sizeof(float) * 2 * n), o_st = L.take(n), o_tab = L.take(sizeof(int) * (n + 1));
+  StageLayout R;
+  const size_t r_mask = R.take(n), r_u0 = R.take(sizeof(float) * 2 * n), r_u1 = R.take(sizeof(float) * 2 * n), r_info = R.take(sizeof(EpiInfoDev));
+  if (L.bytes() > d->stage_cap || R.bytes() > d->res_cap) return OVP_E_CAPACITY;  // (cannot happen below max_points)
+  // ---- from here on the call goes through ----
+  HIPCHK(hipSetDevice(c->device));
+  char* h = (char*)d->hstage.get();
+  memcpy(h + o_p0, pts0, sizeof(float) * 2 * n);
+  memcpy(h + o_p1, pts1, sizeof(float) * 2 * n);
+  for (int i = 0; i < n; ++i) h[o_st + i] = status ? (status[i] != 0) : 1;
+  std::vector<int32_t> table(n + 1, 0);
+  if (!few) ovp_epi_table(n, o->confidence, o->max_iters, table.data());
+  memcpy(h + o_tab, table.data(), sizeof(int) * (n + 1));
+  char *dv = (char*)d->dstage.get(), *dr = (char*)d->dres.get();
+  HIPCHK(hipMemcpyAsync(dv, h, L.bytes(), hipMemcpyHostToDevice, c->stream));
+  EpiLaunch a;
+  a.n = n, a.max_iters = o->max_iters, a.mode = o->mode, a.seed = o->seed;
+  for (int k = 0; k < 8; ++k) a.intr[k] = o->intrinsics[k];
+  a.thr2 = (float)(o->threshold * o->threshold);
+  a.pts0 = (const float*)(dv + o_p0), a.pts1 = (const float*)(dv + o_p1), a.status = (const unsigned char*)(dv + o_st);
+  a.table = (const int*)(dv + o_tab);
+  a.samples = d->epi_samples.get(), a.n_models = d->epi_nmodels.get(), a.models = d->epi_models.get(), a.counts = d->epi_counts.get();
+  a.mask = (unsigned char*)(dr + r_mask), a.uvn0 = (float*)(dr + r_u0), a.uvn1 = (float*)(dr + r_u1), a.info = (EpiInfoDev*)(dr + r_info);
+  a.ev = d->timed ? d->ev_epi : nullptr;
+  const int rl = ovp_epi_enqueue(a, c->stream);  // (a set below OVP_EPI_MIN_POINTS: the undistortion, a zero mask and too_few)
+  if (rl) return rl;
+  SeqChannel& ch = d->hres.channel(0);
+  const unsigned seq = ch.arm();
+  HIPCHK(ovp_launch_publish_block(dr, d->hres.dev(d->hres.payload()), R.bytes(), ch.word_dev(), seq, 0, c->stream));
+  const int rw = ch.wait(c->stream);
+  if (rw) return rw;
+  if (d->timed && !few) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 4; ++k) HIPCHK(hipEventElapsedTime(&d->ms[6 + k], d->ev_epi[k], d->ev_epi[k + 1]));
+  }
+  const char* hr = (const char*)d->hres.payload();
+  if (mask_out) memcpy(mask_out, hr + r_mask, n);
+  if (uvn0) memcpy(uvn0, hr + r_u0, sizeof(float) * 2 * n);
+  if (uvn1) memcpy(uvn1, hr + r_u1, sizeof(float) * 2 * n);
+  if (info) memcpy(info, hr + r_info, sizeof(*info));
+  d->last_n = 0;  // (the mailbox no longer holds a track's iterations)
+  if (!few) d->epi_H = o->max_iters, d->epi_table.swap(table);  // (what the debug reads belong to: one and the same run)
+  return 0;
+}
+
 extern "C" long ovp_klt_debug(ovp_ctx* c, const char* what, int level, void* out, long cap) {
   Klt* d = klt_of(c);
   if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
   if (!what || !out || cap < 0) return OVP_E_ARG;
+  if (!strncmp(what, "epi_", 4)) {
+    if (!d->epi_H) return OVP_E_STATE;
+    const size_t H = (size_t)d->epi_H;
+    if (!strcmp(what, "epi_table")) {
+      const size_t bytes = sizeof(int32_t) * d->epi_table.size();
+      if ((size_t)cap < bytes) return OVP_E_ARG;
+      memcpy(out, d->epi_table.data(), bytes);
+      return (long)bytes;
+    }
+    const void* src[2] = {nullptr, nullptr};
+    size_t bytes[2] = {0, 0};
+    if (!strcmp(what, "epi_samples")) src[0] = d->epi_samples.get(), bytes[0] = sizeof(int) * 7 * H;
+    else if (!strcmp(what, "epi_counts")) src[0] = d->epi_counts.get(), bytes[0] = sizeof(int) * 3 * H;
+    else if (!strcmp(what, "epi_models"))
+      src[0] = d->epi_nmodels.get(), bytes[0] = sizeof(int) * H, src[1] = d->epi_models.get(), bytes[1] = sizeof(double) * 27 * H;
+    else return OVP_E_ARG;
+    const size_t off1 = (bytes[0] + 7) & ~(size_t)7;
+    const size_t total = bytes[1] ? off1 + bytes[1] : bytes[0];
+    if ((size_t)cap < total) return OVP_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out, src[0], bytes[0], hipMemcpyDeviceToHost));
+    if (bytes[1]) HIPCHK(hipMemcpy((char*)out + off1, src[1], bytes[1], hipMemcpyDeviceToHost));
+    return (long)total;
+  }
   if (!strcmp(what, "timer")) {
     d->timed = level != 0;
     return 0;
