@@ -936,13 +936,14 @@ long ovp_active_tracks_debug(ovp_ctx *ctx, const char *what, int64_t id, double 
  * cv::calcOpticalFlowPyrLK call of perform_matching (:1299-1357).  OpenCV is not in the reference tree: the stage is restated from
  * its published form (Bouguet's pyramidal Lucas-Kanade with OpenCV's externally visible conventions: Scharr gradients, reflect-101
  * image borders, zero gradient borders, 30 iterations / 0.01 px, minEigThreshold 1e-4) and is UNPINNED; tests/klt_ref.py is the
- * restatement it is held to.  Detection (:1173-1297) is ovp_klt_detect below, the epipolar check (:1331-1350) ovp_klt_epipolar.  Not built: CLAHE,
- * stereo, the display images. */
+ * restatement it is held to.  Detection (:1173-1297) is ovp_klt_detect below, the epipolar check (:1331-1350) ovp_klt_epipolar, the
+ * intake options (histogram_method CLAHE :66-70, downsample_cameras core/VioManager.cpp:279-289) ovp_klt_feed_image_opts and
+ * ovp_klt_halve.  Not built: stereo, the display images. */
 #define OVP_KLT_MAX_POINTS 4096
 #define OVP_KLT_MAX_LEVELS 8
 #define OVP_KLT_HIST_NONE 0       /* TrackBase::HistogramMethod, in its order */
 #define OVP_KLT_HIST_HISTOGRAM 1
-#define OVP_KLT_HIST_CLAHE 2      /* not built: OVP_E_ARG */
+#define OVP_KLT_HIST_CLAHE 2      /* parameters needed: use ovp_klt_feed_image_opts (ovp_klt_feed_image: OVP_E_ARG) */
 /* One tracker per context (a second create that succeeds replaces the first, one that fails leaves the first in place and usable;
  * the tracker goes with ovp_ctx_destroy): two pyramids of n_levels images
  * (n_levels = maxLevel + 1: the reference's pyr_levels = 5 is 6; 1..OVP_KLT_MAX_LEVELS, every level at least 2 x 2), previous and
@@ -955,8 +956,42 @@ int ovp_klt_reset(ovp_ctx *ctx);
 /* :40-92 one 8-bit image (height rows of `stride` bytes): uploaded, equalised (:65; OVP_KLT_HIST_NONE skips it), the pyramid built
  * into the "current" half; the former current half is "previous" from here on.  One upload and one enqueue (histogram, LUT + apply,
  * one launch per level), no wait.  The image is copied before the call returns.  OVP_E_STATE without ovp_klt_create; OVP_E_ARG for
- * CLAHE, a null image, stride < width. */
+ * CLAHE (parameters needed: use ovp_klt_feed_image_opts), a null image, stride < width. */
 int ovp_klt_feed_image(ovp_ctx *ctx, const uint8_t *img, int stride, int hist_method);
+/* The intake options of one image: histogram_method (track_plane/TrackPlane.cpp:62-72; CLAHE :66-70 is
+ * cv::createCLAHE(10.0, Size(8, 8))->apply) and downsample_cameras (core/VioManager.cpp:279-289: cv::pyrDown of image and mask to
+ * Size(cols / 2.0, rows / 2.0) in front of the tracker; the reference's options loader halves the intrinsics to match,
+ * core/VioManagerOptions.h:252-264).  CLAHE is RECALLED from OpenCV's published clahe.cpp and UNPINNED; tests/clahe_ref.py is the
+ * restatement it is held to and names every convention (extension on both axes when either is not divisible, the clip limit's
+ * truncation and floor of 1, the strided residual, the LUT's and the blend's rounding half to even, weights from the unclamped tile
+ * index). */
+typedef struct ovp_klt_intake {
+  int hist_method;            /* OVP_KLT_HIST_NONE / _HISTOGRAM / _CLAHE */
+  double clahe_clip;          /* 10.0; 0: no clipping, as in OpenCV */
+  int clahe_tiles_x, clahe_tiles_y;   /* 8, 8; each 1..16 */
+  int downsample;             /* 0 / 1 */
+  int src_width, src_height;  /* size of the image handed over; with downsample the tracker's size is (src_width/2, src_height/2), integer division */
+} ovp_klt_intake;
+/* hist_method HISTOGRAM (TrackBase's default), clip 10.0 and 8 x 8 tiles (:67-68), no downsampling, a source size of 0 x 0: the
+ * caller names the size */
+void ovp_klt_intake_defaults(ovp_klt_intake *o);
+/* ovp_klt_feed_image under these options (:40-92 behind core/VioManager.cpp:279-289): one upload - with downsample of the full-size
+ * image (src_height rows of `stride` bytes), which k_klt_pyrdown halves to the tracker's size, the image the equalisation reads -
+ * then the equalisation (CLAHE: k_clahe_lut, one workgroup per tile, and k_clahe_apply; the tile LUTs stay readable through
+ * ovp_klt_debug "clahe_lut"), the pyramid, no wait.  Without downsample and with NONE or HISTOGRAM it leaves the current half
+ * bit-equal to ovp_klt_feed_image.  Integer outputs: two runs give the same bytes.  The first call that halves allocates the
+ * full-size buffers (and waits for the stream once).  Decided on the host with nothing touched: OVP_E_STATE without a tracker;
+ * OVP_E_ARG for a null argument, an unknown method, downsample outside 0..1, tiles outside 1..16, a clip that is negative or not
+ * finite, a source size other than the tracker's (with downsample: src_width / 2 or src_height / 2 other than the tracker's, or
+ * below 1), stride < src_width.  The tile geometry and the clip limit are checked for every method. */
+int ovp_klt_feed_image_opts(ovp_ctx *ctx, const uint8_t *img, int stride, const ovp_klt_intake *intake);
+/* core/VioManager.cpp:284-288 the second cv::pyrDown, the one on the mask (and the debug view of the image's halving): src
+ * (src_height rows of `stride` bytes) to dst [src_height / 2][src_width / 2], rows packed - the same 5-tap kernel, rounding and
+ * reflect-101 as a pyramid level, to floor(w / 2) x floor(h / 2) where a pyramid level has (w + 1) / 2.  The mask is consumed on
+ * the host (keep rule, detector), so this entry waits.  Any size up to 32768 x 32768, whatever the tracker's; it uses the tracker's
+ * buffers and stream: OVP_E_STATE without one.  OVP_E_ARG for a null argument, stride < src_width, src_width / 2 < 1 or
+ * src_height / 2 < 1. */
+int ovp_klt_halve(ovp_ctx *ctx, const uint8_t *src, int stride, int src_width, int src_height, uint8_t *dst);
 /* :1326-1330 n points of the previous image (pts_prev [2n] f32 pixels) into the current one, starting at guess [2n] (NULL: pts_prev,
  * as the reference passes pts1 = pts0 with OPTFLOW_USE_INITIAL_FLOW): pts_out [2n], status [n] (1 found; 0: the window left the
  * image at level 0 or the texture gate refused level 0 - pts_out then holds where the coarser levels left the point).  The error
@@ -1036,8 +1071,9 @@ int ovp_klt_epipolar(ovp_ctx *ctx, const ovp_epipolar_opts *opts, int n, const f
  * caller's on level 0 of the current half - out holds float [2n] starting positions on entry and the refined ones on return;
  * "timer": level != 0 puts events around the kernels (and a stream synchronisation behind each entry) from the next call on,
  * "time": float GPU milliseconds of the last timed calls [equalise, pyramid launches together, k_klt_track, k_fast_score_nms,
- * k_fast_select, k_fast_subpix, k_epi_undistort, k_epi_models, k_epi_count, k_epi_select] - as many as cap holds, at least the
- * first 3.  Of the last ovp_klt_epipolar that ran its RANSAC (n >= OVP_EPI_MIN_POINTS; OVP_E_STATE before one; H its max_iters, level is
+ * k_fast_select, k_fast_subpix, k_epi_undistort, k_epi_models, k_epi_count, k_epi_select, the intake's halving, k_clahe_lut,
+ * k_clahe_apply (the last three 0 where the last feed did not run them)] - as many as cap holds, at least the first 3.
+ * "clahe_lut": uint8 [tiles_y tiles_x][256], the tile LUTs of the last CLAHE feed (OVP_E_STATE before one).  Of the last ovp_klt_epipolar that ran its RANSAC (n >= OVP_EPI_MIN_POINTS; OVP_E_STATE before one; H its max_iters, level is
  * ignored): "epi_samples"
  * int32 [H][7] (-1 without a set), "epi_models" int32 [H] n_models then double [H][3][9] (the doubles start at the next multiple
  * of 8 bytes), "epi_counts" int32 [H][3], "epi_table" int32 [n + 1].  Returns the number of bytes (or < 0). */

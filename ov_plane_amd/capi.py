@@ -276,6 +276,7 @@ EXPORTS = [
     "ovp_propagate_and_clone",
     "ovp_klt_create", "ovp_klt_destroy", "ovp_klt_reset", "ovp_klt_feed_image", "ovp_klt_track", "ovp_klt_debug", "ovp_klt_detect",
     "ovp_epipolar_defaults", "ovp_klt_epipolar",
+    "ovp_klt_intake_defaults", "ovp_klt_feed_image_opts", "ovp_klt_halve",
 ]
 
 
@@ -289,6 +290,12 @@ class EpipolarInfo(C.Structure):
     """ovp_epipolar_info"""
     _fields_ = [("F", C.c_double * 9), ("best_count", C.c_int32), ("winner_h", C.c_int32), ("winner_model", C.c_int32),
                 ("niters", C.c_int32), ("n_with_model", C.c_int32), ("too_few", C.c_int32), ("no_model", C.c_int32), ("stop", C.c_int32)]
+
+
+class Intake(C.Structure):
+    """ovp_klt_intake"""
+    _fields_ = [("hist_method", C.c_int), ("clahe_clip", C.c_double), ("clahe_tiles_x", C.c_int), ("clahe_tiles_y", C.c_int),
+                ("downsample", C.c_int), ("src_width", C.c_int), ("src_height", C.c_int)]
 
 
 def lib():
@@ -421,6 +428,10 @@ def lib():
         L.ovp_epipolar_defaults.argtypes = [C.c_void_p]
         L.ovp_klt_epipolar.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]
+        L.ovp_klt_intake_defaults.restype = None
+        L.ovp_klt_intake_defaults.argtypes = [C.c_void_p]
+        L.ovp_klt_feed_image_opts.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.ovp_klt_halve.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.ovp_klt_debug.restype = C.c_long
         L.ovp_klt_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_long]
         _LIB = L
@@ -440,6 +451,19 @@ def trackplane_defaults(**over) -> TrackPlaneOpts:
         if k not in dict(TrackPlaneOpts._fields_):
             raise KeyError(k)
         setattr(o, k, v)
+    return o
+
+
+def intake_defaults(**over) -> Intake:
+    """the intake options' defaults (ovp_klt_intake_defaults: HISTOGRAM, clip 10, 8 x 8 tiles, no downsampling), with the named
+    fields replaced; hist_method also by name ("NONE", "HISTOGRAM", "CLAHE").  src_width / src_height left at 0 are filled in
+    from the image by KltTracker.feed_image_opts."""
+    o = Intake()
+    lib().ovp_klt_intake_defaults(C.byref(o))
+    for k, v in over.items():
+        if k not in dict(Intake._fields_):
+            raise KeyError(k)
+        setattr(o, k, KltTracker.HIST[v] if k == "hist_method" and isinstance(v, str) else v)
     return o
 
 
@@ -706,6 +730,43 @@ class KltTracker:
         _chk(rc, "ovp_klt_feed_image")
         self._fed += 1
 
+    def feed_image_opts(self, img, intake):
+        """ovp_klt_feed_image_opts: one 8-bit image under the intake options (intake_defaults) - [height, width], or with
+        intake.downsample the full-size image [2 height (+ 1), 2 width (+ 1)], halved on the device; does not wait for the device.
+        A source size of 0 in the intake is the image's."""
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim != 2:
+            raise ValueError("an 8-bit image is expected")
+        if img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+            img = np.ascontiguousarray(img)
+        o = Intake.from_buffer_copy(intake)
+        if o.src_width == 0 and o.src_height == 0:
+            o.src_height, o.src_width = img.shape
+        elif (o.src_height, o.src_width) != img.shape:
+            raise ValueError("the intake names a source of %d x %d" % (o.src_width, o.src_height))
+        t0 = time.perf_counter()
+        rc = lib().ovp_klt_feed_image_opts(self.ctx.handle, img.ctypes.data, int(img.strides[0]), C.byref(o))
+        self.last_feed_ms = 1e3 * (time.perf_counter() - t0)
+        _chk(rc, "ovp_klt_feed_image_opts")
+        self._fed += 1
+
+    def halve(self, img):
+        """ovp_klt_halve: cv::pyrDown of an 8-bit image or mask [h, w] to [h // 2, w // 2] on the device (downsample_cameras'
+        halving, core/VioManager.cpp:279-289); waits for the result"""
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim != 2:
+            raise ValueError("an 8-bit image is expected")
+        if img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+            img = np.ascontiguousarray(img)
+        h, w = img.shape
+        out = np.zeros((max(h // 2, 0), max(w // 2, 0)), dtype=np.uint8)
+        _chk(lib().ovp_klt_halve(self.ctx.handle, img.ctypes.data, int(img.strides[0]), w, h, out.ctypes.data), "ovp_klt_halve")
+        return out
+
+    def clahe_lut(self, tiles_x, tiles_y):
+        """tests: the tile LUTs of the last CLAHE feed -> [tiles_y, tiles_x, 256] uint8"""
+        return self._debug(b"clahe_lut", 0, 256 * tiles_x * tiles_y).reshape(tiles_y, tiles_x, 256).copy()
+
     def track(self, pts_prev, guess=None):
         """pts_prev [n, 2] of the previous image into the current one, from guess (None: pts_prev) -> (pts [n, 2] f32, status [n])"""
         p = np.ascontiguousarray(pts_prev, dtype=np.float32).reshape(-1, 2)
@@ -843,7 +904,7 @@ class KltTracker:
                     counts=self._debug(b"epi_counts", 0, 12 * H, np.int32).reshape(H, 3).copy(),
                     table=self._debug(b"epi_table", 0, 4 * (n + 1), np.int32).copy())
 
-    def step(self, img, mask=None, hist="HISTOGRAM", detect=False, epipolar=None):
+    def step(self, img, mask=None, hist="HISTOGRAM", detect=False, epipolar=None, intake=None):
         """feed_monocular :505-567 minus detection and the epipolar check: feeds img, tracks pts_last into it with guess = pts_last,
         keeps a point unless x < 0, y < 0, (int) x >= cols, (int) y >= rows, mask > 127 at the truncated pixel, or status 0.
         Returns (ids, pts) of the kept points, which are pts_last / ids_last from here on.
@@ -852,8 +913,16 @@ class KltTracker:
         epipolar: None, or dict(camera=(mode, intrinsics), threshold=, confidence=, max_iters=, seed=): perform_matching in full
         (:1299-1357) - fewer than 10 points go in: no KLT, nothing is kept (:1319-1323); none goes in: the reset of :520-530
         (last_reset); otherwise mask_out = status & mask_rsc decides with the rules above, and last_uv_norm holds the kept points'
-        undistorted coordinates (:555)."""
-        self.feed_image(img, hist)
+        undistorted coordinates (:555).
+        intake: None, or the intake options (intake_defaults): the image is fed through feed_image_opts (hist is not looked at),
+        and with intake.downsample img and mask are the full-size ones - the mask is halved on the device (halve) before the keep
+        rule and the detector use it (core/VioManager.cpp:279-289)."""
+        if intake is None:
+            self.feed_image(img, hist)
+        else:
+            self.feed_image_opts(img, intake)
+            if intake.downsample and mask is not None:
+                mask = self.halve(np.asarray(mask, dtype=np.uint8))
         self.last_uv_norm, self.last_reset = np.zeros((0, 2), dtype=np.float32), False
         self.last_match = (np.zeros((0, 2), dtype=np.float32), np.zeros(0, dtype=np.uint8))
         if detect:
@@ -912,10 +981,10 @@ class KltTracker:
 
     def kernel_ms(self):
         """GPU milliseconds of the last timed calls: dict(equalize, pyramid, track, score_nms, select, subpix, epi_undistort,
-        epi_models, epi_count, epi_select)"""
-        t = self._debug(b"time", 0, 40, np.float32)
+        epi_models, epi_count, epi_select, halve, clahe_lut, clahe_apply)"""
+        t = self._debug(b"time", 0, 52, np.float32)
         return dict(zip(("equalize", "pyramid", "track", "score_nms", "select", "subpix", "epi_undistort", "epi_models", "epi_count",
-                         "epi_select"), (float(v) for v in t)))
+                         "epi_select", "halve", "clahe_lut", "clahe_apply"), (float(v) for v in t)))
 
     def refine(self, xy):
         """tests: k_fast_subpix from the starting positions xy [n, 2] on level 0 of the current half -> [n, 2] f32"""

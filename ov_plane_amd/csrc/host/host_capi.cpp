@@ -1197,3 +1197,37 @@ extern "C" int ovph_run_klt_detect_sequence(int device, int width, int height, i
   ovp_ctx_destroy(gpu);
   return rc;
 }
+
+// TrackPlane's image half under the intake options, with its own detection, on a sequence of frames (host_capi.h)
+extern "C" int ovph_run_klt_intake_sequence(int device, int width, int height, int n_frames, const uint8_t *frames, const uint8_t *mask,
+                                            int pyr_levels, int win_size, int hist_method, int downsample, double clahe_clip, int tiles_x,
+                                            int tiles_y, int max_points, const int32_t *detector5, int32_t *n_kept, int64_t *kept_ids,
+                                            float *kept_uv) {
+  ovp_ctx *gpu = nullptr;
+  int rc = ovp_ctx_create(device, 64, 4, 8, nullptr, &gpu);
+  if (rc) return rc;
+  {
+    ovp_trackplane_opts to;
+    ovp_trackplane_defaults(&to);
+    TrackPlane tp(gpu, to);
+    rc = tp.ok() ? tp.set_klt_options(pyr_levels, win_size, hist_method, max_points) : OVP_E_STATE;
+    if (rc == 0) rc = tp.set_intake((TrackPlane::HistogramMethod)hist_method, downsample != 0, clahe_clip, tiles_x, tiles_y);
+    tp.set_detector_options(detector5[0], detector5[1], detector5[2], detector5[3], detector5[4]);
+    const size_t px = (size_t)width * height;
+    for (int f = 0; f < n_frames && rc == 0; ++f) {
+      rc = tp.feed_new_camera(0.1 * f, frames + px * f, width, height, width, mask, true);
+      if (rc) break;
+      const auto &ki = tp.get_last_ids();
+      const auto &kp = tp.get_last_pts();
+      if ((int)ki.size() > max_points) {
+        rc = OVP_E_CAPACITY;
+        break;
+      }
+      n_kept[f] = (int32_t)ki.size();
+      for (size_t i = 0; i < ki.size(); ++i) kept_ids[(size_t)f * max_points + i] = (int64_t)ki[i];
+      if (!kp.empty()) memcpy(kept_uv + 2 * (size_t)f * max_points, kp.data(), sizeof(float) * kp.size());
+    }
+  }
+  ovp_ctx_destroy(gpu);
+  return rc;
+}

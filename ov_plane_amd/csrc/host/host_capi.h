@@ -83,6 +83,13 @@ int ovph_run_klt_epipolar_sequence(int device, int width, int height, int n_fram
                                    int pyr_levels, int win_size, int hist_method, int n_pts, const int64_t *ids, const float *uv,
                                    int mode, const double *intrinsics8, int max_iters, uint32_t seed, int32_t *n_kept, int64_t *kept_ids,
                                    float *kept_uv, float *kept_uvn, int32_t *reset);
+// ovph_run_klt_detect_sequence under set_intake(hist_method, downsample, clahe_clip, tiles_x, tiles_y): the frames go through
+// ovp_klt_feed_image_opts - CLAHE included - and with downsample frames [n_frames][height][width] and the mask are the full-size
+// ones, halved on the device; the points are pixels of the (width / 2) x (height / 2) image.
+int ovph_run_klt_intake_sequence(int device, int width, int height, int n_frames, const uint8_t *frames, const uint8_t *mask,
+                                 int pyr_levels, int win_size, int hist_method, int downsample, double clahe_clip, int tiles_x,
+                                 int tiles_y, int max_points, const int32_t *detector5, int32_t *n_kept, int64_t *kept_ids,
+                                 float *kept_uv);
 
 #ifdef __cplusplus
 }

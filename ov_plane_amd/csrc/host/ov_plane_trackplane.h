@@ -12,7 +12,9 @@
 // feed_new_camera(.., detect = true) feed_monocular's use of it (:477-491, :505-507).  perform_matching() is :1299-1357 in full -
 // perform_matching_klt, then the epipolar check on the device (ovp_klt_epipolar: recalled and unpinned, tests/epi_ref.py) under the
 // camera of set_camera() - and feed_new_camera(.., epipolar = true) feed_monocular's use of it (:510-567), the reset of :520-530
-// included; get_last_uv_norm() holds the kept points' undistorted coordinates (:555).
+// included; get_last_uv_norm() holds the kept points' undistorted coordinates (:555).  set_intake() selects the histogram method by
+// TrackBase's names - CLAHE (:66-70) included, on the device: recalled and unpinned, tests/clahe_ref.py - and downsample_cameras
+// (core/VioManager.cpp:279-289): feed_new_camera() then takes the full-size image and mask and halves both on the device.
 #pragma once
 #include <array>
 #include <cmath>
@@ -97,6 +99,21 @@ class TrackPlane {
   int set_klt_options(int pyr_levels, int win_size, int histogram_method, int max_points) {
     if (_klt_made) return OVP_E_STATE;
     _pyr_levels = pyr_levels, _win_size = win_size, _hist = histogram_method, _klt_max_points = max_points;
+    return 0;
+  }
+
+  // ov_core::TrackBase::HistogramMethod, by its names and in its order (OVP_KLT_HIST_*)
+  enum HistogramMethod { NONE, HISTOGRAM, CLAHE };
+  // histogram_method and downsample_cameras of estimator_config.yaml; CLAHE's parameters are the reference's own (:67-68).  From
+  // here on feed_new_camera feeds through ovp_klt_feed_image_opts, and with `downsample` it takes the FULL-SIZE image and mask
+  // (core/VioManager.cpp:279-289) - the tracker's size is (w / 2, h / 2).  Before the first image.
+  int set_intake(HistogramMethod method, bool downsample, double clahe_clip = 10.0, int tiles_x = 8, int tiles_y = 8) {
+    if (_klt_made) return OVP_E_STATE;
+    if (method != NONE && method != HISTOGRAM && method != CLAHE) return OVP_E_ARG;
+    ovp_klt_intake_defaults(&_intake);
+    _intake.hist_method = (int)method, _intake.downsample = downsample ? 1 : 0;
+    _intake.clahe_clip = clahe_clip, _intake.clahe_tiles_x = tiles_x, _intake.clahe_tiles_y = tiles_y;
+    _hist = (int)method, _intake_set = true;
     return 0;
   }
 
@@ -199,7 +216,9 @@ class TrackPlane {
   }
 
   // undistort_cv's camera: OVP_EPI_MODE_* and its 8 intrinsics; the threshold of :1341-1344 is 2 / max(fx, fy) (mode
-  // OVP_EPI_MODE_NORMALISED: the defaults' threshold, or the one of set_epipolar_options)
+  // OVP_EPI_MODE_NORMALISED: the defaults' threshold, or the one of set_epipolar_options).  Under set_intake(.., downsample = true)
+  // the tracked points are pixels of the halved image: the caller passes the HALVED intrinsics (fx, fy, cx, cy over 2), as the
+  // reference's options loader does (core/VioManagerOptions.h:252-264).
   int set_camera(int mode, const double *intrinsics) {
     if (!intrinsics || mode < OVP_EPI_MODE_NORMALISED || mode > OVP_EPI_MODE_EQUIDISTANT) return OVP_E_ARG;
     _epi.mode = mode;
@@ -285,16 +304,35 @@ class TrackPlane {
   // otherwise pts_last is topped up on the previous image under its mask (:505-507) before it is tracked.
   // epipolar: perform_matching in full decides (:510-567): fewer than 10 points keep nothing, none resets (last_reset()), and
   // get_last_uv_norm() holds the kept points' undistorted coordinates.  Off by default: nothing existing changes.
+  // Under set_intake(.., downsample = true) img and mask are the full-size ones, w x h their size, and everything behind the
+  // halving - tracker, mask tests, points - is in pixels of the (w / 2) x (h / 2) image.
   int feed_new_camera(double time, const uint8_t *img, int w, int h, int stride, const uint8_t *mask = nullptr, bool detect = false,
                       bool epipolar = false) {
+    const bool halve = _intake_set && _intake.downsample;
+    const int src_w = w, src_h = h;
+    if (halve) w = src_w / 2, h = src_h / 2;
     if (!_klt_made) {
       const int rc = ovp_klt_create(_gpu, w, h, _pyr_levels + 1, _win_size, _klt_max_points);
       if (rc) return rc;
       _klt_made = true, _klt_w = w, _klt_h = h;
     }
     if (w != _klt_w || h != _klt_h) return OVP_E_ARG;
-    int rc = ovp_klt_feed_image(_gpu, img, stride, _hist);
+    int rc;
+    if (_intake_set) {
+      ovp_klt_intake in = _intake;
+      in.src_width = src_w, in.src_height = src_h;
+      rc = ovp_klt_feed_image_opts(_gpu, img, stride, &in);
+    } else {
+      rc = ovp_klt_feed_image(_gpu, img, stride, _hist);
+    }
     if (rc) return rc;
+    std::vector<uint8_t> mask_halved;
+    if (halve && mask) {  // core/VioManager.cpp:284-288
+      mask_halved.resize((size_t)w * h);
+      rc = ovp_klt_halve(_gpu, mask, src_w, src_w, src_h, mask_halved.data());
+      if (rc) return rc;
+      mask = mask_halved.data();
+    }
     _time_last = time;
     _match_pts.clear(), _match_mask.clear();
     ++_n_images;
@@ -357,6 +395,8 @@ class TrackPlane {
   bool _klt_made = false;
   int _pyr_levels = 5, _win_size = 15, _hist = OVP_KLT_HIST_HISTOGRAM, _klt_max_points = OVP_KLT_MAX_POINTS;
   int _klt_w = 0, _klt_h = 0, _n_images = 0;
+  ovp_klt_intake _intake = {};  // set_intake
+  bool _intake_set = false;
   double _time_last = 0.0;
   std::vector<size_t> _ids_last;
   std::vector<float> _pts_last, _match_pts;

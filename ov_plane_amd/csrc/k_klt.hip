@@ -5,7 +5,9 @@
 // held to, and names every recalled convention in one place.
 //   k_klt_hist      256-bin histogram of the uploaded image: integer atomics in LDS per workgroup, then global - order-independent
 //   k_klt_equalize  the LUT of cv::equalizeHist from that histogram (every workgroup builds its own copy), applied
-//   k_klt_pyrdown   one level of cv::pyrDown on 8-bit data: [1 4 6 4 1] x [1 4 6 4 1], reflect-101, (sum + 128) >> 8
+//   k_klt_pyrdown   one level of cv::pyrDown on 8-bit data: [1 4 6 4 1] x [1 4 6 4 1], reflect-101, (sum + 128) >> 8, to the size the
+//                   launch names: (w + 1) / 2 for a pyramid level, w / 2 for the intake's halving (downsample_cameras)
+//   k_clahe_lut, k_clahe_apply   histogram_method CLAHE (k_clahe.h), through ovp_klt_feed_image_opts
 //   k_klt_track     one wave per point, coarse to fine: a lane owns ceil(w^2 / 64) window pixels, the previous image's patch and its
 //                   two Scharr gradient patches stay in registers over a level's iterations, the current image is read with four
 //                   plain loads per pixel and iteration (every level of a 752 x 480 pyramid fits in L2), the five sums go through
@@ -246,6 +248,12 @@ struct Klt {
   size_t half_bytes = 0;
   DevBuf<unsigned char> pyr[2], raw;  // the two halves, swapped by index; the uploaded image in front of the equalisation
   DevBuf<unsigned> hist;
+  DevBuf<unsigned char> clahe_lut;  // ovp_klt_feed_image_opts: the tiles' LUTs [tiles_y tiles_x][256] of the last CLAHE feed
+  int lut_tiles = 0;                // tiles of that feed (0: none yet)
+  DevBuf<unsigned char> full;       // the full-size image in front of the halving; made by the first call that halves
+  PinnedBuf<unsigned char> hfull;   // its staging, rows packed
+  DevBuf<unsigned char> halved;     // ovp_klt_halve: its result, and the block it is read back through
+  PinnedBuf<unsigned char> hhalved;
   DevBuf<unsigned char> score, nms;  // ovp_klt_detect: the level-0 score map and the same after suppression
   bool det_done = false;
   DevBuf<int> epi_samples, epi_nmodels, epi_counts;  // ovp_klt_epipolar: what its kernels leave for ovp_klt_debug
@@ -262,13 +270,15 @@ struct Klt {
   hipEvent_t ev_up = nullptr;
   hipEvent_t ev_eq0 = nullptr, ev_eq1 = nullptr, ev_pyr1 = nullptr, ev_trk0 = nullptr, ev_trk1 = nullptr;  // timed mode
   hipEvent_t ev_det[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev_in0 = nullptr, ev_lut = nullptr;  // timed mode: in front of the halving, between k_clahe_lut and k_clahe_apply
   bool up_pending = false, timed = false;
-  // equalise, pyramid launches together, k_klt_track, k_fast_score_nms, k_fast_select, k_fast_subpix, then the four k_epi_* kernels
-  float ms[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  // equalise, pyramid launches together, k_klt_track, k_fast_score_nms, k_fast_select, k_fast_subpix, the four k_epi_* kernels, then
+  // the intake's halving, k_clahe_lut and k_clahe_apply
+  float ms[13] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int last_n = 0;
   ~Klt() {
     for (hipEvent_t e : {ev_up, ev_eq0, ev_eq1, ev_pyr1, ev_trk0, ev_trk1, ev_det[0], ev_det[1], ev_det[2], ev_det[3], ev_epi[0], ev_epi[1], ev_epi[2],
-                         ev_epi[3], ev_epi[4]})
+                         ev_epi[3], ev_epi[4], ev_in0, ev_lut})
       if (e) (void)hipEventDestroy(e);
   }
 };
@@ -276,6 +286,8 @@ struct Klt {
 Klt* klt_of(ovp_ctx* c) { return c ? (Klt*)c->klt.get() : nullptr; }
 
 }  // namespace
+
+#include "k_clahe.h"  // histogram_method CLAHE: k_clahe_lut, k_clahe_apply (behind klt_reflect, which they use)
 
 extern "C" int ovp_klt_create(ovp_ctx* c, int width, int height, int n_levels, int win, int max_points) {
   if (!c) return OVP_E_ARG;
@@ -295,6 +307,7 @@ extern "C" int ovp_klt_create(ovp_ctx* c, int width, int height, int n_levels, i
   for (auto& p : d->pyr) HIPCHK(p.alloc(off));
   HIPCHK(d->raw.alloc(((size_t)width * height + 255) & ~(size_t)255));
   HIPCHK(d->hist.alloc(256));
+  HIPCHK(d->clahe_lut.alloc((size_t)CLAHE_MAX_TILES * CLAHE_MAX_TILES * CLAHE_BINS));
   HIPCHK(d->score.alloc((size_t)width * height));
   HIPCHK(d->nms.alloc((size_t)width * height));
   HIPCHK(d->himg.alloc((size_t)width * height));
@@ -312,7 +325,7 @@ extern "C" int ovp_klt_create(ovp_ctx* c, int width, int height, int n_levels, i
   HIPCHK(d->hres.alloc(d->res_cap));
   HIPCHK(hipEventCreateWithFlags(&d->ev_up, hipEventDisableTiming));
   for (hipEvent_t* e : {&d->ev_eq0, &d->ev_eq1, &d->ev_pyr1, &d->ev_trk0, &d->ev_trk1, &d->ev_det[0], &d->ev_det[1], &d->ev_det[2], &d->ev_det[3],
-                        &d->ev_epi[0], &d->ev_epi[1], &d->ev_epi[2], &d->ev_epi[3], &d->ev_epi[4]})
+                        &d->ev_epi[0], &d->ev_epi[1], &d->ev_epi[2], &d->ev_epi[3], &d->ev_epi[4], &d->ev_in0, &d->ev_lut})
     HIPCHK(hipEventCreate(e));
   c->klt = d;
   return 0;
@@ -332,26 +345,59 @@ extern "C" int ovp_klt_reset(ovp_ctx* c) {
   if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
   d->fed = 0;  // (a half is overwritten when an image takes it)
   d->det_done = false;
+  d->lut_tiles = 0;
   return 0;
 }
 
-extern "C" int ovp_klt_feed_image(ovp_ctx* c, const uint8_t* img, int stride, int hist_method) {
-  Klt* d = klt_of(c);
-  if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
-  if (!img || stride < d->width) return OVP_E_ARG;
-  if (hist_method != OVP_KLT_HIST_NONE && hist_method != OVP_KLT_HIST_HISTOGRAM) return OVP_E_ARG;  // CLAHE is not built
+// the full-size image and its staging: made by the first call that halves, for the largest source a feed can hand over,
+// (2 w + 1) x (2 h + 1), or for ovp_klt_halve's own source when that is larger.  Growing waits for the stream, which may still read
+// the old block.
+static int klt_full_buffers(ovp_ctx* c, Klt* d, size_t count) {
+  count = std::max(count, (size_t)(2 * d->width + 1) * (2 * d->height + 1));
+  if (count <= d->full.capacity()) return 0;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(d->full.reserve(count, 0));
+  HIPCHK(d->hfull.reserve(count, 0));
+  return 0;
+}
+
+// the source of a call that halves: (sw / 2, sh / 2) is the tracker's size
+static bool klt_halves_to(const Klt* d, int sw, int sh) { return sw >= 2 && sh >= 2 && sw / 2 == d->width && sh / 2 == d->height; }
+
+// cv::pyrDown to an explicit size (the pyramid's (w + 1) / 2, or the intake's w / 2)
+static int klt_pyrdown(const unsigned char* src, int w, int h, unsigned char* dst, int wo, int ho, hipStream_t stream) {
+  const int m = wo * ho;
+  hipLaunchKernelGGL(k_klt_pyrdown, dim3((m + 255) / 256), dim3(256), 0, stream, src, w, h, dst, wo, ho);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// One image into the current half: upload (of the full-size image with `halve`), halving, equalisation, pyramid - every argument
+// checked by the caller.  sw x sh: the size of the image handed over.
+static int klt_feed(ovp_ctx* c, Klt* d, const uint8_t* img, int stride, int method, const ClaheGeom* clahe, bool halve, int sw, int sh) {
   HIPCHK(hipSetDevice(c->device));
+  if (halve) {
+    const int rf = klt_full_buffers(c, d, 0);
+    if (rf) return rf;
+  }
   if (d->up_pending) HIPCHK(hipEventSynchronize(d->ev_up));  // the staging block is free once the previous upload has left it
   const int w = d->width, h = d->height, n = w * h;
-  for (int y = 0; y < h; ++y) memcpy(d->himg.get() + (size_t)y * w, img + (size_t)y * stride, w);
+  unsigned char* stage = halve ? d->hfull.get() : d->himg.get();
+  for (int y = 0; y < sh; ++y) memcpy(stage + (size_t)y * sw, img + (size_t)y * stride, sw);
   const int nxt = d->cur ^ 1;  // the former current half becomes "previous" by index: nothing is copied
   unsigned char* lv0 = d->pyr[nxt].get();
-  const bool eq = hist_method == OVP_KLT_HIST_HISTOGRAM;
-  HIPCHK(hipMemcpyAsync(eq ? d->raw.get() : lv0, d->himg.get(), n, hipMemcpyHostToDevice, c->stream));
+  const bool eq = method != OVP_KLT_HIST_NONE;
+  unsigned char* in = eq ? d->raw.get() : lv0;  // what the equalisation reads, or level 0 itself
+  HIPCHK(hipMemcpyAsync(halve ? d->full.get() : in, stage, (size_t)sw * sh, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipEventRecord(d->ev_up, c->stream));
   d->up_pending = true;
+  if (halve) {  // core/VioManager.cpp:279-289 cv::pyrDown to (cols / 2, rows / 2)
+    if (d->timed) HIPCHK(hipEventRecord(d->ev_in0, c->stream));
+    const int rp = klt_pyrdown(d->full.get(), sw, sh, in, w, h, c->stream);
+    if (rp) return rp;
+  }
   if (d->timed) HIPCHK(hipEventRecord(d->ev_eq0, c->stream));
-  if (eq) {
+  if (method == OVP_KLT_HIST_HISTOGRAM) {
     HIPCHK(hipMemsetAsync(d->hist.get(), 0, 256 * sizeof(unsigned), c->stream));
     const int blocks = std::max(1, std::min(256, (n / 16 + 255) / 256));
     hipLaunchKernelGGL(k_klt_hist, dim3(blocks), dim3(256), 0, c->stream, (const unsigned char*)d->raw.get(), n, d->hist.get());
@@ -359,13 +405,20 @@ extern "C" int ovp_klt_feed_image(ovp_ctx* c, const uint8_t* img, int stride, in
     hipLaunchKernelGGL(k_klt_equalize, dim3(blocks), dim3(256), 0, c->stream, (const unsigned char*)d->raw.get(), lv0, n,
                        (const unsigned*)d->hist.get());
     HIPCHK(hipGetLastError());
+  } else if (method == OVP_KLT_HIST_CLAHE) {  // track_plane/TrackPlane.cpp:66-70
+    hipLaunchKernelGGL(k_clahe_lut, dim3(clahe->tiles_x * clahe->tiles_y), dim3(256), 0, c->stream, (const unsigned char*)d->raw.get(), *clahe,
+                       d->clahe_lut.get());
+    HIPCHK(hipGetLastError());
+    if (d->timed) HIPCHK(hipEventRecord(d->ev_lut, c->stream));
+    hipLaunchKernelGGL(k_clahe_apply, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const unsigned char*)d->raw.get(), *clahe,
+                       (const unsigned char*)d->clahe_lut.get(), lv0);
+    HIPCHK(hipGetLastError());
+    d->lut_tiles = clahe->tiles_x * clahe->tiles_y;
   }
   if (d->timed) HIPCHK(hipEventRecord(d->ev_eq1, c->stream));
   for (int l = 1; l < d->n_levels; ++l) {
-    const int m = d->lw[l] * d->lh[l];
-    hipLaunchKernelGGL(k_klt_pyrdown, dim3((m + 255) / 256), dim3(256), 0, c->stream, (const unsigned char*)(lv0 + d->loff[l - 1]),
-                       d->lw[l - 1], d->lh[l - 1], lv0 + d->loff[l], d->lw[l], d->lh[l]);
-    HIPCHK(hipGetLastError());
+    const int rp = klt_pyrdown(lv0 + d->loff[l - 1], d->lw[l - 1], d->lh[l - 1], lv0 + d->loff[l], d->lw[l], d->lh[l], c->stream);
+    if (rp) return rp;
   }
   d->cur = nxt;
   if (d->fed < 2) ++d->fed;
@@ -374,7 +427,72 @@ extern "C" int ovp_klt_feed_image(ovp_ctx* c, const uint8_t* img, int stride, in
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipEventElapsedTime(&d->ms[0], d->ev_eq0, d->ev_eq1));
     HIPCHK(hipEventElapsedTime(&d->ms[1], d->ev_eq1, d->ev_pyr1));
+    d->ms[10] = d->ms[11] = d->ms[12] = 0.f;
+    if (halve) HIPCHK(hipEventElapsedTime(&d->ms[10], d->ev_in0, d->ev_eq0));
+    if (method == OVP_KLT_HIST_CLAHE) {
+      HIPCHK(hipEventElapsedTime(&d->ms[11], d->ev_eq0, d->ev_lut));
+      HIPCHK(hipEventElapsedTime(&d->ms[12], d->ev_lut, d->ev_eq1));
+    }
   }
+  return 0;
+}
+
+extern "C" int ovp_klt_feed_image(ovp_ctx* c, const uint8_t* img, int stride, int hist_method) {
+  Klt* d = klt_of(c);
+  if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
+  if (!img || stride < d->width) return OVP_E_ARG;
+  // CLAHE takes parameters this entry has no place for: ovp_klt_feed_image_opts
+  if (hist_method != OVP_KLT_HIST_NONE && hist_method != OVP_KLT_HIST_HISTOGRAM) return OVP_E_ARG;
+  return klt_feed(c, d, img, stride, hist_method, nullptr, false, d->width, d->height);
+}
+
+extern "C" void ovp_klt_intake_defaults(ovp_klt_intake* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->hist_method = OVP_KLT_HIST_HISTOGRAM;                       // TrackBase's default
+  o->clahe_clip = 10.0, o->clahe_tiles_x = o->clahe_tiles_y = 8;  // track_plane/TrackPlane.cpp:67-68
+}
+
+extern "C" int ovp_klt_feed_image_opts(ovp_ctx* c, const uint8_t* img, int stride, const ovp_klt_intake* o) {
+  Klt* d = klt_of(c);
+  if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
+  // ---- every check before anything is touched or enqueued ----
+  if (!img || !o) return OVP_E_ARG;
+  if (o->hist_method != OVP_KLT_HIST_NONE && o->hist_method != OVP_KLT_HIST_HISTOGRAM && o->hist_method != OVP_KLT_HIST_CLAHE) return OVP_E_ARG;
+  if (o->downsample != 0 && o->downsample != 1) return OVP_E_ARG;
+  if (o->clahe_tiles_x < 1 || o->clahe_tiles_x > CLAHE_MAX_TILES || o->clahe_tiles_y < 1 || o->clahe_tiles_y > CLAHE_MAX_TILES) return OVP_E_ARG;
+  if (!std::isfinite(o->clahe_clip) || o->clahe_clip < 0.0) return OVP_E_ARG;
+  if (o->src_width < 1 || o->src_height < 1 || stride < o->src_width) return OVP_E_ARG;
+  if (o->downsample ? !klt_halves_to(d, o->src_width, o->src_height) : (o->src_width != d->width || o->src_height != d->height)) return OVP_E_ARG;
+  // ---- from here on the call goes through ----
+  ClaheGeom g;
+  clahe_geom(d->width, d->height, o->clahe_tiles_x, o->clahe_tiles_y, o->clahe_clip, &g);
+  return klt_feed(c, d, img, stride, o->hist_method, &g, o->downsample != 0, o->src_width, o->src_height);
+}
+
+extern "C" int ovp_klt_halve(ovp_ctx* c, const uint8_t* src, int stride, int src_width, int src_height, uint8_t* dst) {
+  Klt* d = klt_of(c);
+  if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
+  if (!src || !dst || stride < src_width || src_width / 2 < 1 || src_height / 2 < 1 || src_width > 32768 || src_height > 32768) return OVP_E_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  const int w = src_width / 2, h = src_height / 2;
+  const int rf = klt_full_buffers(c, d, (size_t)src_width * src_height);
+  if (rf) return rf;
+  if ((size_t)w * h > d->halved.capacity()) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(d->halved.reserve((size_t)w * h, 0));
+    HIPCHK(d->hhalved.reserve((size_t)w * h, 0));
+  }
+  if (d->up_pending) HIPCHK(hipEventSynchronize(d->ev_up));  // (a feed's upload may still read the staging block)
+  for (int y = 0; y < src_height; ++y) memcpy(d->hfull.get() + (size_t)y * src_width, src + (size_t)y * stride, src_width);
+  // `full` is free in stream order: a feed enqueued before has halved it by then, and this call returns when its own copies are done
+  HIPCHK(hipMemcpyAsync(d->full.get(), d->hfull.get(), (size_t)src_width * src_height, hipMemcpyHostToDevice, c->stream));
+  const int rp = klt_pyrdown(d->full.get(), src_width, src_height, d->halved.get(), w, h, c->stream);
+  if (rp) return rp;
+  HIPCHK(hipMemcpyAsync(d->hhalved.get(), d->halved.get(), (size_t)w * h, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  d->up_pending = false;
+  memcpy(dst, d->hhalved.get(), (size_t)w * h);
   return 0;
 }
 
@@ -632,7 +750,7 @@ extern "C" long ovp_klt_debug(ovp_ctx* c, const char* what, int level, void* out
     return 0;
   }
   if (!strcmp(what, "time")) {
-    if (cap < (long)(3 * sizeof(float))) return OVP_E_ARG;  // [3] of the tracker alone, [6] with the detector's kernels
+    if (cap < (long)(3 * sizeof(float))) return OVP_E_ARG;  // [3] of the tracker alone, [6] with the detector's kernels, .. [13]
     const size_t bytes = std::min((size_t)cap / sizeof(float), sizeof(d->ms) / sizeof(float)) * sizeof(float);
     memcpy(out, d->ms, bytes);
     return (long)bytes;
@@ -668,6 +786,15 @@ extern "C" long ovp_klt_debug(ovp_ctx* c, const char* what, int level, void* out
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(out, what[0] == 's' ? d->score.get() : d->nms.get(), bytes, hipMemcpyDeviceToHost));
+    return (long)bytes;
+  }
+  if (!strcmp(what, "clahe_lut")) {  // of the last CLAHE feed: [tiles_y tiles_x][256]
+    if (!d->lut_tiles) return OVP_E_STATE;
+    const size_t bytes = (size_t)d->lut_tiles * CLAHE_BINS;
+    if ((size_t)cap < bytes) return OVP_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out, d->clahe_lut.get(), bytes, hipMemcpyDeviceToHost));
     return (long)bytes;
   }
   if (!strcmp(what, "iters")) {  // of the last ovp_klt_track: [n][8] iterations per level (the mailbox still holds them)

@@ -486,6 +486,28 @@ def run_klt_detect_sequence(frames, mask, detector, pyr_levels=5, win=15, hist="
     return [dict(ids=kept_ids[f, :n_kept[f]].copy(), pts=kept_uv[f, :n_kept[f]].copy()) for f in range(K)]
 
 
+def run_klt_intake_sequence(frames, mask, detector, hist="CLAHE", downsample=False, clahe_clip=10.0, tiles=(8, 8), pyr_levels=5, win=15,
+                            max_points=512, device=0):
+    """run_klt_detect_sequence under TrackPlane::set_intake(hist, downsample, clahe_clip, tiles): the frames go through
+    ovp_klt_feed_image_opts, and with downsample frames and mask are the full-size ones (halved on the device; the points are pixels
+    of the halved image).  Returns a list of K dicts(ids, pts)."""
+    L = lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    K, h, w = fr.shape
+    mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(h, w)
+    d5 = np.array([detector[k] for k in ("num_features", "grid_x", "grid_y", "threshold", "min_px_dist")], dtype=np.int32)
+    n_kept = np.zeros(K, dtype=np.int32)
+    kept_ids, kept_uv = np.zeros((K, max_points), dtype=np.int64), np.zeros((K, max_points, 2), dtype=np.float32)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    rc = L.ovph_run_klt_intake_sequence(C.c_int(device), C.c_int(w), C.c_int(h), C.c_int(K), vp(fr), vp(mk), C.c_int(pyr_levels),
+                                        C.c_int(win), C.c_int({"NONE": 0, "HISTOGRAM": 1, "CLAHE": 2}[hist]), C.c_int(1 if downsample else 0),
+                                        C.c_double(clahe_clip), C.c_int(tiles[0]), C.c_int(tiles[1]), C.c_int(max_points), vp(d5),
+                                        vp(n_kept), vp(kept_ids), vp(kept_uv))
+    if rc:
+        raise RuntimeError("ovph_run_klt_intake_sequence failed with %d" % rc)
+    return [dict(ids=kept_ids[f, :n_kept[f]].copy(), pts=kept_uv[f, :n_kept[f]].copy()) for f in range(K)]
+
+
 def run_sequence(init, imu, frame_time, frames, po, sigma_px=1.0, chi2_mult=1.0, trace=False, plane_mode=0, plane_min_feat=20,
                  sigma_c=0.01):
     """Closed loop over several frames through the C++ host mirror (Propagator::propagate_and_clone ->
