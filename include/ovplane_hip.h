@@ -931,6 +931,91 @@ int ovp_active_tracks_update(ovp_ctx *ctx, const ovp_active_tracks_in *in, ovp_a
  * (or < 0). */
 long ovp_active_tracks_debug(ovp_ctx *ctx, const char *what, int64_t id, double *out, long cap);
 
+/* ---- feature database: a frame's tracks to the update's batch ------------------------------------ */
+/* ext ov_core::FeatureDatabase between the tracker and the updaters, as VioManager::do_feature_propagate_update uses it
+ * (core/VioManager.cpp:373-506, :855-869), and the cleaning of update/UpdaterMSCKF.cpp:74-100.  ov_core is not in the reference
+ * tree: the database's methods are RECALLED from their published form and UNPINNED; tests/featdb_ref.py is the restatement they
+ * are held to and names every recalled convention.  The call sites above are pinned.  One camera (camera 0), as ovp_state_tables:
+ * the camera filter of :386-403 is a no-op.  The table lives on the device - max_slots <= OVP_FEATDB_MAX_SLOTS feature slots (the
+ * tracker's point limit) of max_meas <= OVP_MAX_MEAS observations (time stamp f64, uv f32, uv_norm f32), a count, a to_delete flag
+ * and the id per slot; the id -> slot map and a shadow of the counts and time stamps are the host's, so that every refusal below
+ * is decided on the host with nothing touched.  The hash map's iteration order is replaced by this library's own rule: every list
+ * is in ascending feature id.  Integer decisions and copies only: two runs give the same bytes. */
+#define OVP_FEATDB_MAX_SLOTS 4096
+#define OVP_FEATDB_NONE 0     /* still tracked, not at the marginalisation time */
+#define OVP_FEATDB_LOST 1     /* :376 features_not_containing_newer(state->_timestamp, false, true) */
+#define OVP_FEATDB_MARG 2     /* :380 features_containing(state->margtimestep(), false, true); lost and marg is marg (:405-415) */
+#define OVP_FEATDB_MAXTRACK 3 /* :418-436 marg with more than max_clone_size measurements */
+#define OVP_FEATDB_FLAG_TOO_FEW 1  /* fewer than 2 measurements are left after the cleaning (update/UpdaterMSCKF.cpp:94) */
+#define OVP_FEATDB_FLAG_DELETED 2  /* Feature::to_delete */
+/* One database per context (a second create: OVP_E_STATE, the first stays; it goes with ovp_ctx_destroy).  OVP_E_ARG outside the
+ * limits.  _reset forgets every feature and the gathered batch. */
+int ovp_featdb_create(ovp_ctx *ctx, int max_slots, int max_meas);
+int ovp_featdb_destroy(ovp_ctx *ctx);
+int ovp_featdb_reset(ovp_ctx *ctx);
+/* ext FeatureDatabase::update_feature for the n observations of one frame (TrackBase feeds them one by one): ids [n] distinct
+ * (OVP_E_ARG otherwise), uv / uv_norm [2n] f32.  A new id takes a free slot; a feature whose to_delete is set keeps collecting
+ * measurements, as in the reference.  One upload, one launch (k_featdb_append, a thread per observation), no wait.
+ * OVP_E_CAPACITY with nothing touched: more live features than slots, or an id whose slot already holds max_meas observations. */
+int ovp_featdb_append(ovp_ctx *ctx, double timestamp, int n, const int64_t *ids, const float *uv, const float *uv_norm);
+typedef struct ovp_featdb_classify_in {
+  const double *clone_times; /* [n_clones] State::_clones_IMU's keys after cloning, ascending (update/UpdaterMSCKF.cpp:74-78) */
+  int n_clones;              /* <= OVP_MAX_MEAS */
+  int max_clone_size;        /* StateOptions::max_clone_size (:424) */
+  double t_now;              /* state->_timestamp (:376) */
+  double marg_time;          /* state->margtimestep() (state/State.h:70) */
+  int want_marg;             /* :379 clones > max_clone_size || clones > 5 */
+  int reserved;
+} ovp_featdb_classify_in;
+typedef struct ovp_featdb_classify_out {
+  int cap;          /* in: entries the arrays hold */
+  int n;            /* out: live features (set also when cap is too small: OVP_E_CAPACITY) */
+  int64_t *ids;     /* [cap] ascending */
+  int32_t *cls;     /* [cap] OVP_FEATDB_NONE / _LOST / _MARG / _MAXTRACK */
+  int32_t *count;   /* [cap] observations held */
+  int32_t *cleaned; /* [cap] observations left after ext Feature::clean_old_measurements(clone_times): those whose time stamp
+                       equals a clone time exactly */
+  uint8_t *flags;   /* [cap] OVP_FEATDB_FLAG_* */
+  int32_t totals[4]; /* lost, marg, maxtrack, to_delete */
+} ovp_featdb_classify_out;
+/* zeros, max_clone_size 11, want_marg 1 */
+void ovp_featdb_classify_defaults(ovp_featdb_classify_in *o);
+/* :373-436 and update/UpdaterMSCKF.cpp:74-100 for every live feature, nothing modified: "newer" is a last time stamp >= t_now,
+ * "containing" and the cleaning compare doubles exactly, both queries skip to_delete.  One upload, one launch (k_featdb_classify),
+ * one publication through the database's mailbox, one wait.  OVP_E_ARG: clone times not strictly ascending, a NaN. */
+int ovp_featdb_classify(ovp_ctx *ctx, const ovp_featdb_classify_in *in, ovp_featdb_classify_out *out);
+/* Feature::to_delete = true of the named features - what the updaters do to a feature they used or refused (e.g.
+ * update/UpdaterMSCKF.cpp:95).  An unknown id: OVP_E_ARG, nothing touched. */
+int ovp_featdb_mark_deleted(ovp_ctx *ctx, int n, const int64_t *ids);
+/* The ovp_feature_batch of the n named features, in the caller's order, built in the database's own device buffers and bound as
+ * ovp_batch_bind_device binds a caller's (replaces the host packing in front of ovp_batch_upload): per feature the observations
+ * that survive clean_old_measurements(clone_times), in stored order, as uv and uv_norm [n][max_meas][2], clone_idx (the index of
+ * the time stamp among clone_times, -1 = padding) and n_meas; the row pitch is the database's max_meas.  old_index == NULL: p_FinG
+ * is zero.  Otherwise p_FinG[f] is that of feature old_index[f] of the batch gathered before, bit for bit - the batch rebuilt from
+ * the survivors of a triangulation (update/UpdaterMSCKF.cpp:120-166 erases features).  One upload, one launch (k_featdb_gather, a
+ * wave per feature), no wait.  Refused with nothing touched: OVP_E_ARG for an unknown id, a feature with no observation left, one
+ * with more than the pitch, an old index outside the former batch; OVP_E_STATE for old_index without a former batch;
+ * OVP_E_CAPACITY for n above the slots or the context's n_feats_max.  n = 0 binds an empty batch. */
+int ovp_featdb_gather(ovp_ctx *ctx, int n, const int64_t *ids, const int *old_index, const double *clone_times, int n_clones);
+/* ovp_triangulate on the gathered batch, uv_norm read from the database's device buffer: the same kernel and launcher, no upload
+ * of measurements.  OVP_E_STATE unless the context's batch is the one ovp_featdb_gather bound last. */
+int ovp_featdb_triangulate(ovp_ctx *ctx, const ovp_triang_opts *opts, double *p_FinG_out, uint8_t *ok);
+/* :855 ext FeatureDatabase::cleanup() (do_cleanup != 0: every feature whose to_delete is set goes) and then :865
+ * cleanup_measurements(t) (t not NaN: every observation with a time stamp < t goes, the rest closes up in stored order, a
+ * feature left without observations goes).  One launch (k_featdb_cleanup), one publication - the new counts and the freed slots,
+ * which the host's map and shadow follow - one wait. */
+int ovp_featdb_cleanup(ovp_ctx *ctx, int do_cleanup, double measurements_before_or_nan);
+/* ext FeatureDatabase::get_feature (:472) and a test's read-back: *count = -1 for an id the database does not hold, otherwise its
+ * observations (as many as cap holds) in stored order; slot, to_delete, timestamps, uv [2 cap], uv_norm [2 cap] may be NULL.
+ * Synchronous. */
+int ovp_featdb_get(ovp_ctx *ctx, int64_t id, int *slot, int *count, int *to_delete, double *timestamps, float *uv, float *uv_norm,
+                   int cap);
+/* tests: what = "uv" / "uv_norm" / "clone_idx" / "n_meas" / "p_FinG": the gathered batch (OVP_E_STATE before one); "dims": int32
+ * [max_slots, max_meas, live features, gathered features or -1]; "cleanup": int64 [id, new count, freed] per feature that was live
+ * at the last ovp_featdb_cleanup; "timer": level != 0 puts events around the kernel of every call from the next one on (and a
+ * stream synchronisation behind it), "time": float GPU milliseconds of the last timed kernel.  Returns the number of bytes (or < 0). */
+long ovp_featdb_debug(ovp_ctx *ctx, const char *what, int level, void *out, long cap);
+
 /* ---- image front end: equalisation, image pyramid, pyramidal KLT ---------------------------------- */
 /* TrackPlane::feed_new_camera (track_plane/TrackPlane.cpp:40-92: cv::equalizeHist :65, cv::buildOpticalFlowPyramid) and the
  * cv::calcOpticalFlowPyrLK call of perform_matching (:1299-1357).  OpenCV is not in the reference tree: the stage is restated from

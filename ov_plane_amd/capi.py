@@ -277,7 +277,22 @@ EXPORTS = [
     "ovp_klt_create", "ovp_klt_destroy", "ovp_klt_reset", "ovp_klt_feed_image", "ovp_klt_track", "ovp_klt_debug", "ovp_klt_detect",
     "ovp_epipolar_defaults", "ovp_klt_epipolar",
     "ovp_klt_intake_defaults", "ovp_klt_feed_image_opts", "ovp_klt_halve",
+    "ovp_featdb_create", "ovp_featdb_destroy", "ovp_featdb_reset", "ovp_featdb_append", "ovp_featdb_classify_defaults",
+    "ovp_featdb_classify", "ovp_featdb_mark_deleted", "ovp_featdb_gather", "ovp_featdb_triangulate", "ovp_featdb_cleanup",
+    "ovp_featdb_get", "ovp_featdb_debug",
 ]
+
+
+class FeatDbClassifyIn(C.Structure):
+    """ovp_featdb_classify_in"""
+    _fields_ = [("clone_times", C.c_void_p), ("n_clones", C.c_int), ("max_clone_size", C.c_int), ("t_now", C.c_double),
+                ("marg_time", C.c_double), ("want_marg", C.c_int), ("reserved", C.c_int)]
+
+
+class FeatDbClassifyOut(C.Structure):
+    """ovp_featdb_classify_out"""
+    _fields_ = [("cap", C.c_int), ("n", C.c_int), ("ids", C.c_void_p), ("cls", C.c_void_p), ("count", C.c_void_p),
+                ("cleaned", C.c_void_p), ("flags", C.c_void_p), ("totals", C.c_int32 * 4)]
 
 
 class EpipolarOpts(C.Structure):
@@ -434,6 +449,20 @@ def lib():
         L.ovp_klt_halve.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.ovp_klt_debug.restype = C.c_long
         L.ovp_klt_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_long]
+        L.ovp_featdb_create.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.ovp_featdb_destroy.argtypes = [C.c_void_p]
+        L.ovp_featdb_reset.argtypes = [C.c_void_p]
+        L.ovp_featdb_append.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ovp_featdb_classify_defaults.restype = None
+        L.ovp_featdb_classify_defaults.argtypes = [C.c_void_p]
+        L.ovp_featdb_classify.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ovp_featdb_mark_deleted.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.ovp_featdb_gather.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.ovp_featdb_triangulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ovp_featdb_cleanup.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.ovp_featdb_get.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.ovp_featdb_debug.restype = C.c_long
+        L.ovp_featdb_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_long]
         _LIB = L
     return _LIB
 
@@ -686,6 +715,147 @@ class ActiveTracks:
     def kernel_ms(self):
         """GPU milliseconds of the last timed frame's kernel"""
         return float(self._debug(b"time", 0, 1)[0])
+
+
+FEATDB_NONE, FEATDB_LOST, FEATDB_MARG, FEATDB_MAXTRACK = 0, 1, 2, 3
+
+
+def featdb_select(ids, cls, landmark_ids, max_slam_features, slam_delay_ok):
+    """core/VioManager.cpp:373-506 on a published class table (ids ascending): feats_lost, feats_marg, the maxtracks left over, the
+    new SLAM features (the LAST valid_amount of the maxtracks, :447-460, on the ascending-id order) and the SLAM features to update;
+    landmarks_marg: the state's landmarks the database no longer holds (:466-480 should_marg).  One camera, no ArUco."""
+    pick = lambda c: [int(i) for i, k in zip(ids, cls) if k == c]  # noqa: E731
+    lost, marg, maxtracks = pick(FEATDB_LOST), pick(FEATDB_MARG), pick(FEATDB_MAXTRACK)
+    landmark_ids = [int(i) for i in landmark_ids]
+    slam = []
+    if max_slam_features > 0 and slam_delay_ok and len(landmark_ids) < max_slam_features:
+        valid = min(max_slam_features - len(landmark_ids), len(maxtracks))
+        if valid > 0:
+            slam, maxtracks = maxtracks[len(maxtracks) - valid:], maxtracks[:len(maxtracks) - valid]
+    live = set(int(i) for i in ids)
+    gone = [lm for lm in landmark_ids if lm not in live]
+    slam += [lm for lm in landmark_ids if lm in live]
+    left = set(landmark_ids) - set(gone)
+    return dict(lost=lost, marg=marg, maxtracks=maxtracks, slam_delayed=[i for i in slam if i not in left],
+                slam_update=[i for i in slam if i in left], landmarks_marg=gone)
+
+
+class FeatureDatabase:
+    """The feature database of a context (ovp_featdb_*): ext ov_core::FeatureDatabase on the device, under the reference's method
+    names.  update_feature takes one frame's observations at once; every list is in ascending feature id."""
+
+    def __init__(self, ctx, max_slots=4096, max_meas=32):
+        self.ctx, self.S, self.M = ctx, int(max_slots), int(max_meas)
+        _chk(lib().ovp_featdb_create(ctx.handle, self.S, self.M), "ovp_featdb_create")
+        self.table = None
+
+    def close(self):
+        _chk(lib().ovp_featdb_destroy(self.ctx.handle), "ovp_featdb_destroy")
+
+    def reset(self):
+        _chk(lib().ovp_featdb_reset(self.ctx.handle), "ovp_featdb_reset")
+
+    def update_feature(self, timestamp, ids, uv, uv_norm):
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        uv = np.ascontiguousarray(uv, dtype=np.float32)
+        uvn = np.ascontiguousarray(uv_norm, dtype=np.float32)
+        if uv.size != 2 * len(ids) or uvn.size != 2 * len(ids):
+            raise ValueError("uv and uv_norm hold one pair per id")
+        _chk(lib().ovp_featdb_append(self.ctx.handle, float(timestamp), len(ids), ids.ctypes.data, uv.ctypes.data, uvn.ctypes.data),
+             "ovp_featdb_append")
+
+    def classify(self, clone_times, t_now, marg_time, max_clone_size, want_marg):
+        ct = np.ascontiguousarray(clone_times, dtype=np.float64)
+        a = FeatDbClassifyIn()
+        lib().ovp_featdb_classify_defaults(C.byref(a))
+        a.clone_times, a.n_clones, a.max_clone_size = ct.ctypes.data, len(ct), int(max_clone_size)
+        a.t_now, a.marg_time, a.want_marg = float(t_now), float(marg_time), 1 if want_marg else 0
+        cap = self.S
+        ids, cls, cnt, cln = (np.zeros(cap, dtype=t) for t in (np.int64, np.int32, np.int32, np.int32))
+        fl = np.zeros(cap, dtype=np.uint8)
+        o = FeatDbClassifyOut(cap, 0, ids.ctypes.data, cls.ctypes.data, cnt.ctypes.data, cln.ctypes.data, fl.ctypes.data)
+        _chk(lib().ovp_featdb_classify(self.ctx.handle, C.byref(a), C.byref(o)), "ovp_featdb_classify")
+        n = o.n
+        self.table = dict(ids=ids[:n].copy(), cls=cls[:n].copy(), count=cnt[:n].copy(), cleaned=cln[:n].copy(), flags=fl[:n].copy(),
+                          totals=np.array(list(o.totals), dtype=np.int32))
+        return self.table
+
+    def features_not_containing_newer(self, timestamp):
+        """(timestamp, remove = false, skip_deleted = true)"""
+        r = self.classify([], timestamp, np.inf, 1 << 30, False)
+        return [int(i) for i in r["ids"][r["cls"] == FEATDB_LOST]]
+
+    def features_containing(self, timestamp):
+        """(timestamp, remove = false, skip_deleted = true)"""
+        r = self.classify([], -np.inf, timestamp, 1 << 30, True)
+        return [int(i) for i in r["ids"][r["cls"] == FEATDB_MARG]]
+
+    def select(self, state_times, t_now, max_clone_size, landmark_ids=(), max_slam_features=0, slam_delay_ok=True):
+        """core/VioManager.cpp:373-506: state_times are the clone times after cloning, ascending; the marginalisation time is the
+        oldest (state/State.h:70).  Returns featdb_select's lists, with the published table under "table"."""
+        st = np.asarray(state_times, dtype=np.float64)
+        want = len(st) > max_clone_size or len(st) > 5   # :379
+        t = self.classify(st, t_now, st[0] if len(st) else np.inf, max_clone_size, want)
+        return dict(featdb_select(t["ids"], t["cls"], landmark_ids, max_slam_features, slam_delay_ok), table=t)
+
+    def mark_deleted(self, ids):
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        _chk(lib().ovp_featdb_mark_deleted(self.ctx.handle, len(ids), ids.ctypes.data), "ovp_featdb_mark_deleted")
+
+    def gather(self, ids, clone_times, old_index=None):
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        ct = np.ascontiguousarray(clone_times, dtype=np.float64)
+        oi = None if old_index is None else np.ascontiguousarray(old_index, dtype=np.int32)
+        _chk(lib().ovp_featdb_gather(self.ctx.handle, len(ids), ids.ctypes.data, None if oi is None else oi.ctypes.data, ct.ctypes.data,
+                                     len(ct)), "ovp_featdb_gather")
+        self.ctx.n_feats = len(ids)
+
+    def _debug(self, what, dtype, count):
+        out = np.zeros(max(count, 1), dtype=dtype)
+        k = lib().ovp_featdb_debug(self.ctx.handle, what, 0, out.ctypes.data, out.nbytes)
+        if k < 0:
+            raise OvpError(int(k), "ovp_featdb_debug")
+        return out[: k // out.itemsize]
+
+    def dims(self):
+        return [int(v) for v in self._debug(b"dims", np.int32, 4)]
+
+    def gathered(self):
+        """the bound batch, read back: uv, uv_norm [F, M, 2], clone_idx [F, M], n_meas [F], p_FinG [F, 3]"""
+        F, M = self.dims()[3], self.M
+        if F < 0:
+            return None
+        return dict(uv=self._debug(b"uv", np.float32, 2 * F * M).reshape(F, M, 2), uv_norm=self._debug(b"uv_norm", np.float32, 2 * F * M).reshape(F, M, 2),
+                    clone_idx=self._debug(b"clone_idx", np.int32, F * M).reshape(F, M), n_meas=self._debug(b"n_meas", np.int32, F),
+                    p_FinG=self._debug(b"p_FinG", np.float64, 3 * F).reshape(F, 3))
+
+    def triangulate(self, opts=None):
+        """ovp_featdb_triangulate on the gathered batch; returns dict(p_FinG [F,3], ok [F])."""
+        o = opts if opts is not None else triang_defaults()
+        F = max(self.dims()[3], 0)   # the gathered batch's size, whatever the context's batch has become since
+        p = np.zeros((max(F, 1), 3))
+        ok = np.zeros(max(F, 1), dtype=np.uint8)
+        _chk(lib().ovp_featdb_triangulate(self.ctx.handle, C.byref(o), p.ctypes.data, ok.ctypes.data), "ovp_featdb_triangulate")
+        return dict(p_FinG=p[:F], ok=ok[:F].astype(bool))
+
+    def cleanup(self, do_cleanup=True, before=float("nan")):
+        """cleanup() and, with `before`, cleanup_measurements(before) behind it; returns int64 [n, 3]: id, new count, freed"""
+        _chk(lib().ovp_featdb_cleanup(self.ctx.handle, 1 if do_cleanup else 0, float(before)), "ovp_featdb_cleanup")
+        return self._debug(b"cleanup", np.int64, 3 * self.S).reshape(-1, 3)
+
+    def cleanup_measurements(self, timestamp):
+        return self.cleanup(False, timestamp)
+
+    def get_feature(self, fid):
+        M = self.M
+        slot, cnt, dele = C.c_int(-1), C.c_int(-1), C.c_int(0)
+        ts, uv, uvn = np.zeros(M), np.zeros((M, 2), dtype=np.float32), np.zeros((M, 2), dtype=np.float32)
+        _chk(lib().ovp_featdb_get(self.ctx.handle, int(fid), C.byref(slot), C.byref(cnt), C.byref(dele), ts.ctypes.data, uv.ctypes.data,
+                                  uvn.ctypes.data, M), "ovp_featdb_get")
+        if cnt.value < 0:
+            return None
+        n = cnt.value
+        return dict(count=n, to_delete=dele.value, ts=ts[:n], uv=uv[:n], uv_norm=uvn[:n], slot=slot.value)
 
 
 class KltTracker:

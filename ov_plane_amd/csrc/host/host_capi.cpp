@@ -33,7 +33,7 @@ extern "C" int ovph_run_opts_layout(int *offsets, int cap) {
                      OVPH_OFF(fit_max_cond), OVPH_OFF(fit_variant), OVPH_OFF(slam_rep), OVPH_OFF(slam_anchor), OVPH_OFF(feat_rep_slam),
                      OVPH_OFF(slam_plane), OVPH_OFF(cam1_q), OVPH_OFF(cam1_p), OVPH_OFF(cam1_intr), OVPH_OFF(cam_of_meas),
                      OVPH_OFF(general_features), OVPH_OFF(general_planes), OVPH_OFF(general_plane_init), OVPH_OFF(fused_plane_fit),
-                     OVPH_OFF(general_slam), OVPH_OFF(dinit_planes), OVPH_OFF(batched_retire), OVPH_OFF(p_noplane), OVPH_OFF(comm), OVPH_OFF(comm_rank),
+                     OVPH_OFF(general_slam), OVPH_OFF(dinit_planes), OVPH_OFF(batched_retire), OVPH_OFF(featdb), OVPH_OFF(p_noplane), OVPH_OFF(comm), OVPH_OFF(comm_rank),
                      OVPH_OFF(comm_world), OVPH_OFF(device), OVPH_OFF(seq_traj), OVPH_OFF(seq_posecov), OVPH_OFF(seq_uv_norm),
                      OVPH_OFF(seq_plane), OVPH_OFF(seq_plane_mode), OVPH_OFF(seq_plane_min_feat), OVPH_OFF(seq_sigma_c),
                      OVPH_OFF(seq_planes_in_state), OVPH_OFF(last_shard), OVPH_OFF(last_cam1)};
@@ -207,6 +207,28 @@ std::vector<std::shared_ptr<ov_core::Feature>> make_features(const HarnessState 
   return fv;
 }
 
+// A device database on the state's context holding every measurement of `fv`, fed as a tracker would: one update_feature per
+// clone time, oldest first, the features in the vector's order.
+int attach_fed_database(HarnessState &hs, const std::vector<std::shared_ptr<ov_core::Feature>> &fv) {
+  if (fv.size() > OVP_FEATDB_MAX_SLOTS) return OVP_E_CAPACITY;
+  auto db = std::make_shared<FeatureDatabase>(hs.state->gpu(), std::max<int>(1, (int)fv.size()), OVP_MAX_MEAS);
+  if (db->status()) return db->status();
+  for (double t : hs.times) {
+    std::vector<int64_t> ids;
+    std::vector<float> uv, uvn;
+    for (const auto &ft : fv)
+      for (size_t k = 0; k < ft->timestamps.size(); ++k)
+        if (ft->timestamps[k] == t && ft->cam_of(k) == 0 && ft->uvs_norm.size() == ft->uvs.size()) {
+          ids.push_back((int64_t)ft->featid);
+          uv.insert(uv.end(), {ft->uvs[2 * k], ft->uvs[2 * k + 1]});
+          uvn.insert(uvn.end(), {ft->uvs_norm[2 * k], ft->uvs_norm[2 * k + 1]});
+        }
+    if (int rc = db->update_feature(t, ids, uv, uvn)) return rc;
+  }
+  hs.state->_featdb = db;
+  return 0;
+}
+
 // Where export_state copies the state to; a nullptr member is skipped.  P is column-major at the state's size, which goes to n.
 struct StateOut {
   double *clone_q = nullptr, *clone_p = nullptr, *calib_q = nullptr, *calib_p = nullptr, *intr = nullptr;
@@ -300,6 +322,7 @@ extern "C" int ovph_run_msckf_update(int C, const double *clone_q, const double 
   so.gpu_general_features = o.general_features != 0;
   so.gpu_general_planes = o.general_planes != 0;
   so.gpu_fused_plane_fit = o.fused_plane_fit != 0;
+  so.gpu_featdb = o.featdb != 0;
   StateSpec sp;
   sp.C = C, sp.clone_q = clone_q, sp.clone_p = clone_p, sp.clone_q_fej = clone_q_fej, sp.clone_p_fej = clone_p_fej;
   sp.calib_q = calib_q, sp.calib_p = calib_p, sp.intr = intr, sp.second_camera = o.cam1_q != nullptr;
@@ -314,6 +337,8 @@ extern "C" int ovph_run_msckf_update(int C, const double *clone_q, const double 
   // unlike ovph_run_updater, the camera of a measurement is handed on whenever it is given, second camera or not
   auto fv = make_features(hs, F, M, uv, clone_idx, n_meas, p_FinG, 5000, o.cam_of_meas, o.uv_norm);
   const auto all = fv;
+  if (so.gpu_featdb)  // the tracker's side of StateOptions::gpu_featdb: the same observations, clone time by clone time
+    if (int rc = attach_fed_database(hs, fv)) return rc;
   std::vector<std::shared_ptr<ov_core::Feature>> fextra, fused;
   std::map<size_t, size_t> feat2plane;
   for (int f = 0; f < F; ++f)
@@ -1230,4 +1255,68 @@ extern "C" int ovph_run_klt_intake_sequence(int device, int width, int height, i
   }
   ovp_ctx_destroy(gpu);
   return rc;
+}
+
+// ov_plane::FeatureDatabase (ov_plane_featdb.h) on a sequence of frames, on a context of its own (host_capi.h)
+extern "C" int ovph_run_featdb_sequence(int device, int max_slots, int max_meas, int n_frames, const double *times, const int32_t *n_obs,
+                                        const int64_t *ids, const float *uv, const float *uv_norm, int max_clone_size,
+                                        int max_slam_features, int64_t *out, long cap, long *used) {
+  ovp_ctx *gpu = nullptr;
+  int rc = ovp_ctx_create(device, 32, 32, 64, nullptr, &gpu);
+  if (rc) return rc;
+  long at = 0;
+  auto put = [&](int64_t v) {
+    if (at < cap) out[at] = v;
+    ++at;
+  };
+  auto put_list = [&](const std::vector<int64_t> &v) {
+    put((int64_t)v.size());
+    for (int64_t x : v) put(x);
+  };
+  {
+    FeatureDatabase db(gpu, max_slots, max_meas);
+    rc = db.status();
+    std::vector<int64_t> landmarks;
+    size_t o = 0;
+    for (int f = 0; f < n_frames && !rc; ++f) {
+      const size_t n = (size_t)n_obs[f];
+      rc = db.update_feature(times[f], std::vector<int64_t>(ids + o, ids + o + n), std::vector<float>(uv + 2 * o, uv + 2 * (o + n)),
+                             std::vector<float>(uv_norm + 2 * o, uv_norm + 2 * (o + n)));
+      o += n;
+      if (rc) break;
+      const std::vector<double> window(times + std::max(0, f - max_clone_size), times + f + 1);
+      FeatDbSelection s;
+      FeatureDatabase::Table t;
+      if ((rc = db.select(window, times[f], max_clone_size, landmarks, max_slam_features, true, s, &t))) break;
+      put_list(t.ids);
+      for (const std::vector<int> *v : {&t.cls, &t.count, &t.cleaned}) put_list(std::vector<int64_t>(v->begin(), v->end()));
+      put_list(std::vector<int64_t>(t.flags.begin(), t.flags.end()));
+      for (int k = 0; k < 4; ++k) put(t.totals[k]);
+      for (const std::vector<int64_t> *v : {&s.lost, &s.marg, &s.maxtracks, &s.slam_delayed, &s.slam_update, &s.landmarks_marg}) put_list(*v);
+      // the two queries under the reference's names, and one feature read back
+      std::vector<int64_t> q;
+      if ((rc = db.features_not_containing_newer(times[f], q))) break;
+      put_list(q);
+      if ((rc = db.features_containing(window.front(), q))) break;
+      put_list(q);
+      FeatureDatabase::Feature ft;
+      const bool have = !t.ids.empty() && db.get_feature(t.ids.front(), ft);
+      put(have ? (int64_t)ft.timestamps.size() : -1);
+      put(have && ft.to_delete ? 1 : 0);
+      // what the updaters do with the selection, then :855-869
+      std::vector<int64_t> next;
+      for (int64_t lm : landmarks)
+        if (!std::count(s.landmarks_marg.begin(), s.landmarks_marg.end(), lm)) next.push_back(lm);
+      next.insert(next.end(), s.slam_delayed.begin(), s.slam_delayed.end());
+      landmarks = next;
+      std::vector<int64_t> chosen = s.lost;
+      for (const std::vector<int64_t> *v : {&s.marg, &s.maxtracks, &s.slam_delayed, &s.slam_update}) chosen.insert(chosen.end(), v->begin(), v->end());
+      if ((rc = db.mark_deleted(chosen))) break;
+      if ((rc = db.cleanup())) break;
+      if ((int)window.size() > max_clone_size && (rc = db.cleanup_measurements(window.front()))) break;
+    }
+  }
+  ovp_ctx_destroy(gpu);
+  if (used) *used = at;
+  return rc ? rc : (at > cap ? OVP_E_CAPACITY : 0);
 }

@@ -33,7 +33,7 @@ typedef struct ovph_run_opts {
   const double *cam1_q, *cam1_p, *cam1_intr;
   const int32_t *cam_of_meas;
   // StateOptions::gpu_<name>
-  int32_t general_features, general_planes, general_plane_init, fused_plane_fit, general_slam, dinit_planes, batched_retire;
+  int32_t general_features, general_planes, general_plane_init, fused_plane_fit, general_slam, dinit_planes, batched_retire, featdb;
   const double *p_noplane;  // mode 1: positions before plane refinement of the candidates (Feature::p_FinG_original, [F][3])
   // ovph_run_msckf_update: the State lives on `device` and the updater takes the sharded point loop on this communicator
   void *comm;
@@ -90,6 +90,17 @@ int ovph_run_klt_intake_sequence(int device, int width, int height, int n_frames
                                  int pyr_levels, int win_size, int hist_method, int downsample, double clahe_clip, int tiles_x,
                                  int tiles_y, int max_points, const int32_t *detector5, int32_t *n_kept, int64_t *kept_ids,
                                  float *kept_uv);
+
+// ov_plane::FeatureDatabase (ov_plane_featdb.h) on a context of its own on `device`: n_frames frames, frame f with n_obs[f]
+// observations (ids / uv / uv_norm concatenated) at times[f].  Per frame, as VioManager::do_feature_propagate_update goes
+// (core/VioManager.cpp:373-506, :855-869): update_feature, select over the last max_clone_size + 1 times, to_delete on everything
+// selected, cleanup(), and cleanup_measurements(oldest) once the window is full; new SLAM features join the landmark list, lost
+// landmarks leave it.  out receives per frame, every list as (length, items): the table's ids, cls, count, cleaned, flags, the four
+// totals, lost, marg, maxtracks, slam_delayed, slam_update, landmarks_marg, features_not_containing_newer(t),
+// features_containing(oldest), and (count, to_delete) of get_feature(first id) or (-1, 0).  *used = values written.
+int ovph_run_featdb_sequence(int device, int max_slots, int max_meas, int n_frames, const double *times, const int32_t *n_obs,
+                             const int64_t *ids, const float *uv, const float *uv_norm, int max_clone_size, int max_slam_features,
+                             int64_t *out, long cap, long *used);
 
 #ifdef __cplusplus
 }

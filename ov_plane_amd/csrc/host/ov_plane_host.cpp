@@ -68,6 +68,7 @@ State::State(StateOptions &options_) : _options(options_) {
 }
 
 State::~State() {
+  _featdb.reset();
   if (PlaneFitting::bound() == _gpu) PlaneFitting::bind(nullptr, 0);
   if (_gpu) ovp_ctx_destroy(_gpu);
 }

@@ -14,6 +14,7 @@
 
 #include "ov_types.h"
 #include "ovplane_hip.h"
+#include "ov_plane_featdb.h"
 
 namespace ov_plane {
 
@@ -92,6 +93,13 @@ struct StateOptions {
   // merge in sequence, then one compaction - and the bookkeeping, instead of a marginal download, a host gate, an EKFUpdate and
   // a marginalize per plane.  Not in the reference.
   bool gpu_batched_retire = false;
+  // The triangulation block every updater opens with (ov_plane_pack.cpp: triangulate_on_device) takes its camera-0 batch from the
+  // device feature database attached to the State (State::_featdb, ov_plane_featdb.h) instead of packing and uploading it:
+  // ovp_featdb_gather + ovp_featdb_triangulate in place of pack_features, ovp_batch_upload and ovp_triangulate with a host uv_norm.
+  // Taken when every feature of the call carries all its measurements in camera 0, none takes the general pass and the database
+  // holds every one of them with an observation in the window (otherwise the gather refuses with nothing touched and the call
+  // packs and uploads as before).  Not in the reference.
+  bool gpu_featdb = false;
   // UpdaterZeroVelocity::try_update: the chi2 test, the decision, the bias random walk and the update are one device pass
   // (ovp_zupt_update: one upload, one enqueue, one wait) instead of a marginal download, a 6 (n - 1)-row factorization on the host,
   // an EKFPropagation and an EKFUpdate of the stacked rows.  Not in the reference.
@@ -209,6 +217,9 @@ public:
   // simulation ground truth (state/State.h:120-121), read by UpdaterMSCKF::update when StateOptions::use_groundtruths is set
   std::unordered_map<size_t, std::array<double, 3>> _true_planes;
   std::unordered_map<size_t, std::array<double, 3>> _true_features;
+  // the device feature database on this State's context, attached by whoever feeds it the tracker's observations
+  // (StateOptions::gpu_featdb); it goes before the context does
+  std::shared_ptr<FeatureDatabase> _featdb;
   ovp_ctx *gpu() const { return _gpu; }  // the device context of the covariance (what TrackPlane's detector is created on)
 
 private:

@@ -48,9 +48,48 @@ void upload_camera_tables(const std::shared_ptr<State> &state) {
   pack_check(ovp_cameras_upload(state->gpu(), (int)cams.size(), cams.data()), "ovp_cameras_upload");
 }
 
+// StateOptions::gpu_featdb: the camera-0 batch comes from the device database - every feature whole, none for the general pass
+static bool featdb_can_carry(const FeatureVec &features, const TriangulationSite &site) {
+  for (const auto &f : features) {
+    if (!wants_triangulation(*f) || (site.mono && site.mono(*f) != Meas::ALL)) return false;
+    if (site.general && site.general(*f)) return false;
+  }
+  return true;
+}
+
+// false: the database does not hold every feature of the call with an observation in the window (the gather refused, nothing was
+// touched) - the caller packs and uploads as without the option
+static bool triangulate_from_featdb(const std::shared_ptr<State> &state, const CloneWindow &window,
+                                    const ov_core::FeatureInitializerOptions &fio, FeatureVec &features, const TriangulationSite &site) {
+  std::vector<int64_t> ids;
+  for (const auto &f : features) ids.push_back((int64_t)f->featid);
+  std::vector<double> times;
+  for (const auto &c : window.clone_slot) times.push_back(c.first);  // ascending: slot i of the tables is times[i]
+  const int rg = state->_featdb->gather(ids, times);
+  if (rg == OVP_E_ARG) return false;
+  pack_check(rg, "ovp_featdb_gather");
+  std::vector<double> pf;
+  std::vector<uint8_t> okv;
+  pack_check(state->_featdb->triangulate(make_triang_opts(fio), pf, okv, (int)ids.size()), "ovp_featdb_triangulate");
+  FeatureVec kept;
+  for (size_t f = 0; f < features.size(); ++f) {
+    if (!okv[f]) {
+      if (site.flag_failures) features[f]->to_delete = true;  // :161-165
+      continue;
+    }
+    memcpy(features[f]->p_FinG, &pf[3 * f], 3 * sizeof(double));
+    kept.push_back(features[f]);
+  }
+  features = kept;
+  return true;
+}
+
 void triangulate_on_device(const std::shared_ptr<State> &state, const CloneWindow &window, const ov_core::FeatureInitializerOptions &fio,
                            FeatureVec &features, const TriangulationSite &site) {
   if (!any_wants_triangulation(features)) return;
+  if (state->_options.gpu_featdb && state->_featdb && featdb_can_carry(features, site) &&
+      triangulate_from_featdb(state, window, fio, features, site))
+    return;
   PackSite mono;
   mono.which = site.mono;
   mono.with_uvn = true;

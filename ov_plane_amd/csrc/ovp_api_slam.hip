@@ -43,21 +43,7 @@ extern "C" int ovp_triangulate(ovp_ctx* c, const ovp_triang_opts* o, const float
   tp.n_meas = c->fp.n_meas;
   tp.n_feats = (int)F;
   tp.max_meas = (int)M;
-  tp.clone_R = c->clone_R;
-  tp.clone_p = c->clone_p;
-  tp.cal = c->cal;
-  tp.refine_features = o->refine_features;
-  tp.triangulate_1d = o->triangulate_1d;
-  tp.max_runs = o->max_runs;
-  tp.init_lamda = o->init_lamda;
-  tp.max_lamda = o->max_lamda;
-  tp.min_dx = o->min_dx;
-  tp.min_dcost = o->min_dcost;
-  tp.lam_mult = o->lam_mult;
-  tp.min_dist = o->min_dist;
-  tp.max_dist = o->max_dist;
-  tp.max_baseline = o->max_baseline;
-  tp.max_cond_number = o->max_cond_number;
+  fill_tri_params(tp, c, o);
   tp.p_FinG = c->p_FinG;  // the library's own buffer even when the batch was bound to caller memory
   tp.ok = (unsigned char*)ad + o_ok;
   HIPCHK(ovp_launch_triangulate(&tp, c->stream));

@@ -11,6 +11,7 @@
 //   k_plane_detect.hip plane detection from the tracked features: its kernels and its entry points
 //   k_delaunay.hip     the Delaunay triangulation of a frame's vertices in one workgroup (ovp_launch_delaunay, k_delaunay.h)
 //   k_active_tracks.hip re-triangulation of a frame's active tracks (ovp_active_tracks_*): its kernel and its entry points
+//   k_featdb.hip       the feature database (ovp_featdb_*): the track table, its kernels and entry points
 //   k_klt.hip          the image front end (ovp_klt_*): equalisation, image pyramid and pyramidal Lucas-Kanade, kernels and entry points
 //   k_retire.hip       a frame's retirements in one compaction, its plane merges in sequence in front of it: kernels and entry points
 //   k_zupt.hip         the zero-velocity update's gate, rows and apply kernels (entry point: ovp_zupt_update in ovp_api_ctx.hip)
@@ -282,6 +283,7 @@ struct ovp_ctx {
   std::shared_ptr<void> retire;  // ovp_cov_marginalize_many / ovp_planes_merge_retire (k_retire.hip): their staging, scratch and mailbox, made on first use
   std::shared_ptr<void> zupt;    // ovp_zupt_update (ovp_api_ctx.hip, k_zupt.hip): its staging and device blocks, made on first use
   std::shared_ptr<void> klt;     // ovp_klt_create (k_klt.hip): the two image pyramids, staging, result block and mailbox, freed with the context
+  std::shared_ptr<void> featdb;  // ovp_featdb_create (k_featdb.hip): the track table, the gathered batch, staging and mailbox, freed with the context
   std::shared_ptr<void> prop;    // ovp_propagate_and_clone (ovp_api_ctx.hip, k_propagate.hip): its staging, result block and mailbox, made on first use
 
   ovp_ctx() = default;
@@ -336,6 +338,26 @@ struct CalCols {
     for (int k = 0; k < OVP_MAX_CAMERAS; ++k) gp.cam_calib_id[k] = c->gen_calib_id[k], gp.cam_intr_id[k] = c->gen_intr_id[k];
   }
 };
+
+// ext FeatureInitializerOptions and the context's clone and calibration tables into the triangulation kernel's arguments; the
+// batch (uvn, clone_idx, n_meas, sizes) and the outputs are the caller's.  ovp_triangulate and ovp_featdb_triangulate share it.
+static inline void fill_tri_params(ovp::TriParams& tp, const ovp_ctx* c, const ovp_triang_opts* o) {
+  tp.clone_R = c->clone_R;
+  tp.clone_p = c->clone_p;
+  tp.cal = c->cal;
+  tp.refine_features = o->refine_features;
+  tp.triangulate_1d = o->triangulate_1d;
+  tp.max_runs = o->max_runs;
+  tp.init_lamda = o->init_lamda;
+  tp.max_lamda = o->max_lamda;
+  tp.min_dx = o->min_dx;
+  tp.min_dcost = o->min_dcost;
+  tp.lam_mult = o->lam_mult;
+  tp.min_dist = o->min_dist;
+  tp.max_dist = o->max_dist;
+  tp.max_baseline = o->max_baseline;
+  tp.max_cond_number = o->max_cond_number;
+}
 
 // Everything that writes the covariance calls this: the factor the plane loop left (Lkeep) and the bookkeeping of a staged point
 // update that was built but never applied (use_kept_factor / point_nl, set by ovp_msckf_build_gate_gram_async) no longer belong to P.

@@ -39,7 +39,7 @@ class RunOpts(C.Structure):
                 ("slam_anchor", C.c_int32), ("feat_rep_slam", C.c_int32), ("slam_plane", C.c_void_p), ("cam1_q", C.c_void_p),
                 ("cam1_p", C.c_void_p), ("cam1_intr", C.c_void_p), ("cam_of_meas", C.c_void_p), ("general_features", C.c_int32),
                 ("general_planes", C.c_int32), ("general_plane_init", C.c_int32), ("fused_plane_fit", C.c_int32),
-                ("general_slam", C.c_int32), ("dinit_planes", C.c_int32), ("batched_retire", C.c_int32), ("p_noplane", C.c_void_p), ("comm", C.c_void_p),
+                ("general_slam", C.c_int32), ("dinit_planes", C.c_int32), ("batched_retire", C.c_int32), ("featdb", C.c_int32), ("p_noplane", C.c_void_p), ("comm", C.c_void_p),
                 ("comm_rank", C.c_int32), ("comm_world", C.c_int32), ("device", C.c_int32), ("seq_traj", C.c_void_p),
                 ("seq_posecov", C.c_void_p), ("seq_uv_norm", C.c_void_p), ("seq_plane", C.c_void_p), ("seq_plane_mode", C.c_int32),
                 ("seq_plane_min_feat", C.c_int32), ("seq_sigma_c", C.c_double), ("seq_planes_in_state", C.c_int32),
@@ -91,7 +91,7 @@ def carries_option(name, L=None):
 
 
 def run_msckf_update(sc, triangulate=False, fit_planes=None, comm=None, rank=0, world=1, device=0, general_features=False,
-                     general_planes=False, fused_plane_fit=False):
+                     general_planes=False, fused_plane_fit=False, featdb=False):
     """Drives ov_plane::UpdaterMSCKF::update (C++ host classes over the C-ABI) on a synth.Scene.
     triangulate=True: the features carry uvs_norm and no position; the updater triangulates them first.
     fit_planes=dict(min_feat, max_cond, variant): no plane estimates are handed over - the updater fits the planes that are
@@ -103,9 +103,11 @@ def run_msckf_update(sc, triangulate=False, fit_planes=None, comm=None, rank=0, 
     general_planes: StateOptions::gpu_general_planes - on-plane features of that kind stay in the plane loop
     (ovp_msckf_plane_update_general) instead of going to the point update without their plane constraint.
     fused_plane_fit: StateOptions::gpu_fused_plane_fit - with fit_planes, every plane of the frame is fitted and refined by one
-    ovp_plane_fit_refine call, over on-plane features of any camera and any track length."""
+    ovp_plane_fit_refine call, over on-plane features of any camera and any track length.
+    featdb: StateOptions::gpu_featdb - with triangulate, the features' observations are fed to a device feature database and the
+    updater's triangulation block gathers and triangulates from it instead of packing and uploading the batch."""
     L = lib()
-    ro = RunOpts(sc, fit_planes, fused_plane_fit=fused_plane_fit, general_features=general_features, general_planes=general_planes,
+    ro = RunOpts(sc, fit_planes, featdb=featdb, fused_plane_fit=fused_plane_fit, general_features=general_features, general_planes=general_planes,
                  comm_rank=rank, comm_world=world, device=device)
     ro.comm = comm if comm else None
     if triangulate:
@@ -414,6 +416,46 @@ def run_plane_givens(op, H_f, H_x, H_cp, res):
     ro = L.ovph_run_plane_givens(C.c_int(op), C.c_int(rows), C.c_int(0 if H_f is None else H_f.shape[1]), p(Hf), C.c_int(cols),
                                  p(Hx), C.c_int(0 if H_cp is None else H_cp.shape[1]), p(Hc), p(r))
     return Hx[:ro].copy(), (Hc[:ro].copy() if H_cp is not None else None), r[:ro].copy()
+
+
+def run_featdb_sequence(frames, max_slots, max_meas, max_clone_size, max_slam_features=0, device=0):
+    """ovph_run_featdb_sequence: ov_plane::FeatureDatabase (C++ mirror) over frames = [(time, ids, uv, uv_norm)], through the frame
+    loop of core/VioManager.cpp:373-506, :855-869.  Returns per frame dict(table=dict(ids, cls, count, cleaned, flags, totals), lost,
+    marg, maxtracks, slam_delayed, slam_update, landmarks_marg, not_newer, containing, first=(count, to_delete))."""
+    L = lib()
+    times = np.ascontiguousarray([f[0] for f in frames], dtype=np.float64)
+    n_obs = np.ascontiguousarray([len(f[1]) for f in frames], dtype=np.int32)
+    cat = lambda k, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(f[k], dtype=dt).reshape(-1, w) for f in frames]) if frames else np.zeros((0, w), dt))  # noqa: E731
+    ids, uv, uvn = cat(1, np.int64, 1), cat(2, np.float32, 2), cat(3, np.float32, 2)
+    cap = len(frames) * (16 * max_slots + 64) + 64
+    out = np.zeros(cap, dtype=np.int64)
+    used = C.c_long(0)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    rc = L.ovph_run_featdb_sequence(C.c_int(device), C.c_int(max_slots), C.c_int(max_meas), C.c_int(len(frames)), p(times), p(n_obs), p(ids),
+                                    p(uv), p(uvn), C.c_int(max_clone_size), C.c_int(max_slam_features), p(out), C.c_long(cap), C.byref(used))
+    if rc != 0:
+        raise RuntimeError("ovph_run_featdb_sequence failed with %d" % rc)
+    at = [0]
+
+    def take_list():
+        n = int(out[at[0]])
+        v = out[at[0] + 1:at[0] + 1 + n].copy()
+        at[0] += 1 + n
+        return v
+    res = []
+    for _ in frames:
+        t = dict(ids=take_list(), cls=take_list().astype(np.int32), count=take_list().astype(np.int32), cleaned=take_list().astype(np.int32),
+                 flags=take_list().astype(np.uint8))
+        t["totals"] = out[at[0]:at[0] + 4].astype(np.int32)
+        at[0] += 4
+        r = dict(table=t)
+        for key in ("lost", "marg", "maxtracks", "slam_delayed", "slam_update", "landmarks_marg", "not_newer", "containing"):
+            r[key] = [int(v) for v in take_list()]
+        r["first"] = (int(out[at[0]]), int(out[at[0] + 1]))
+        at[0] += 2
+        res.append(r)
+    assert at[0] == used.value
+    return res
 
 
 def run_klt_sequence(frames, mask, ids, uv, pyr_levels=5, win=15, hist="HISTOGRAM", device=0):
