@@ -145,19 +145,15 @@ constexpr int MAX_OBS = OVP_MAX_CAMERAS * OVP_AT_MAX_POINTS, MAX_OUT = S + OVP_A
 struct ActiveTracks {
   DevBuf<double> A, b;
   DevBuf<int> count;
-  PinnedBuf<void> hstage;
-  DevBuf<void> dstage, dres;
+  Staged stage;  // the frame's tables
+  DevBuf<void> dres;
   Mailbox hres;  // the frame's results: payload from byte 0, channel 0
-  size_t stage_cap = 0, res_cap = 0;
-  hipEvent_t ev[2] = {};
+  size_t res_cap = 0;
+  OvpEvent ev[2];
   float ms = 0.f;
   bool timed = false;  // ovp_active_tracks_debug "timer": events around the kernel, read behind a stream synchronisation
   std::map<int64_t, int> slot_of;
   std::vector<int> free_slots;  // a stack, so which slot a feature takes is a function of the call sequence alone
-  ~ActiveTracks() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
   void forget() {
     slot_of.clear();
     free_slots.clear();
@@ -176,15 +172,13 @@ extern "C" int ovp_active_tracks_create(ovp_ctx* c) {
   HIPCHK(d->A.alloc((size_t)S * 6));
   HIPCHK(d->b.alloc((size_t)S * 3));
   HIPCHK(d->count.alloc(S));
-  d->stage_cap = 64 * 16 + sizeof(int) * ((size_t)S * 6 + MAX_OBS + OVP_AT_MAX_LANDMARKS) + S + OVP_AT_MAX_LANDMARKS +
-                 sizeof(double) * (2 * (size_t)MAX_OBS + 12 * OVP_MAX_CAMERAS + 24 + 27 * (size_t)OVP_AT_MAX_LANDMARKS) +
-                 sizeof(float) * 2 * (size_t)MAX_OBS;
+  HIPCHK(d->stage.alloc(64 * 16 + sizeof(int) * ((size_t)S * 6 + MAX_OBS + OVP_AT_MAX_LANDMARKS) + S + OVP_AT_MAX_LANDMARKS +
+                        sizeof(double) * (2 * (size_t)MAX_OBS + 12 * OVP_MAX_CAMERAS + 24 + 27 * (size_t)OVP_AT_MAX_LANDMARKS) +
+                        sizeof(float) * 2 * (size_t)MAX_OBS));
   d->res_cap = 64 * 4 + sizeof(double) * 6 * (size_t)MAX_OUT + MAX_OUT;
-  HIPCHK(d->hstage.alloc(d->stage_cap));
-  HIPCHK(d->dstage.alloc(d->stage_cap));
   HIPCHK(d->dres.alloc(d->res_cap));
   HIPCHK(d->hres.alloc(d->res_cap));
-  for (hipEvent_t& e : d->ev) HIPCHK(hipEventCreate(&e));
+  for (OvpEvent& e : d->ev) HIPCHK(e.create());
   d->forget();
   c->active_tracks = d;
   return 0;
@@ -261,7 +255,7 @@ extern "C" int ovp_active_tracks_update(ovp_ctx* c, const ovp_active_tracks_in* 
                o_lrel = L.take(nl), o_lpx = L.take(sizeof(int) * nl);
   StageLayout Rl;
   const size_t r_p = Rl.take(sizeof(double) * 3 * m), r_uvd = Rl.take(sizeof(double) * 3 * m), r_flag = Rl.take(m);
-  if (L.bytes() > d->stage_cap || Rl.bytes() > d->res_cap) return OVP_E_CAPACITY;  // (cannot happen below the limits above)
+  if (L.bytes() > d->stage.capacity() || Rl.bytes() > d->res_cap) return OVP_E_CAPACITY;  // (cannot happen below the limits above)
   // ---- from here on the call goes through ----
   HIPCHK(hipSetDevice(c->device));
   // :331-334 a feature not observed in this frame, or one that has become a landmark (:277-280), gives its slot back
@@ -272,7 +266,9 @@ extern "C" int ovp_active_tracks_update(ovp_ctx* c, const ovp_active_tracks_in* 
     } else
       ++it;
   if (m == 0) return 0;  // :338 nothing tracked and no landmark: the maps are empty
-  char* h = (char*)d->hstage.get();
+  int rc = 0;
+  char* h = d->stage.begin(L.bytes(), &rc);
+  if (!h) return rc;
   int* h_slot = (int*)(h + o_fslot);
   for (int i = 0; i < nf; ++i) {
     h[o_ffresh + i] = 0;
@@ -320,9 +316,9 @@ extern "C" int ovp_active_tracks_update(ovp_ctx* c, const ovp_active_tracks_in* 
     auto it = feat_of.find(in->slam_id[j]);
     ((int*)(h + o_lpx))[j] = it == feat_of.end() ? -1 : f_px[it->second];
   }
-  char* dv = (char*)d->dstage.get();
+  const char* dv = d->stage.dev();
   char* dr = (char*)d->dres.get();
-  HIPCHK(hipMemcpyAsync(dv, h, L.bytes(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(d->stage.send(L.bytes(), c->stream, Fence::CallerWaits));
   AtFrame f;
   f.A = d->A.get(), f.b = d->b.get(), f.count = d->count.get();
   f.nf = nf, f.nl = nl;
@@ -344,6 +340,7 @@ extern "C" int ovp_active_tracks_update(ovp_ctx* c, const ovp_active_tracks_in* 
   HIPCHK(ovp_launch_publish_block(d->dres.get(), d->hres.dev(d->hres.payload()), Rl.bytes(), ch.word_dev(), seq, 0, c->stream));
   const int rw = ch.wait(c->stream);
   if (rw) return rw;
+  d->stage.done();
   d->ms = 0.f;
   if (d->timed) {
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -190,11 +190,11 @@ struct FeatDb {
   DevBuf<int> g_ci, g_nm;
   DevBuf<double> g_p[2];
   int cur = 0, g_n = -1;  // the set the batch's p_FinG is; features gathered (-1: nothing gathered yet)
-  PinnedBuf<void> hstage;
-  DevBuf<void> dstage, dres;
+  Staged stage;  // no entry waits for its tables' copy alone: Fence::Event at every site
+  DevBuf<void> dres;
   Mailbox hres;
-  size_t stage_cap = 0, res_cap = 0;
-  hipEvent_t ev_stage = nullptr, ev[2] = {};
+  size_t res_cap = 0;
+  OvpEvent ev[2];
   bool timed = false;
   float ms = 0.f;
   // the host's shadow: id -> slot (ascending id is the order of every list), per slot the time stamps of its observations
@@ -207,10 +207,6 @@ struct FeatDb {
   std::vector<double> cls_times;
   std::vector<int> cls_cleaned;
   std::vector<long long> last_cleanup;  // [id, new count, freed] per slot that was live at the last ovp_featdb_cleanup (tests)
-  ~FeatDb() {
-    for (hipEvent_t e : {ev_stage, ev[0], ev[1]})
-      if (e) (void)hipEventDestroy(e);
-  }
   void forget() {
     slot_of.clear();
     free_slots.clear();
@@ -229,13 +225,6 @@ struct FeatDb {
 
 FeatDb* db_of(ovp_ctx* c) { return c ? (FeatDb*)c->featdb.get() : nullptr; }
 
-// the staging block is written by the host while the copy of the call before may still read it: wait for that copy, not the stream
-hipError_t stage_begin(FeatDb* d) { return hipEventSynchronize(d->ev_stage); }
-int stage_upload(ovp_ctx* c, FeatDb* d, size_t bytes) {
-  HIPCHK(hipMemcpyAsync(d->dstage.get(), d->hstage.get(), bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipEventRecord(d->ev_stage, c->stream));
-  return 0;
-}
 int publish_wait(ovp_ctx* c, FeatDb* d, size_t bytes) {
   SeqChannel& ch = d->hres.channel(0);
   const unsigned seq = ch.arm();
@@ -285,14 +274,11 @@ extern "C" int ovp_featdb_create(ovp_ctx* c, int max_slots, int max_meas) {
   HIPCHK(hipMemsetAsync(d->del.get(), 0, sizeof(int) * S, c->stream));
   // staging: the largest of [slot | fresh | id | uv | uv_norm] of a frame and [slot | old index | clone times] of a gather;
   // results: the largest of the class table, the cleanup table and [points | ok]
-  d->stage_cap = 64 * 8 + S * (sizeof(int) + 1 + sizeof(long long) + 2 * sizeof(float2)) + sizeof(double) * OVP_MAX_MEAS;
+  HIPCHK(d->stage.alloc(64 * 8 + S * (sizeof(int) + 1 + sizeof(long long) + 2 * sizeof(float2)) + sizeof(double) * OVP_MAX_MEAS));
   d->res_cap = 64 * 8 + S * (sizeof(long long) + 3 * sizeof(int) + 1 + 3 * sizeof(double)) + sizeof(int) * 4;
-  HIPCHK(d->hstage.alloc(d->stage_cap));
-  HIPCHK(d->dstage.alloc(d->stage_cap));
   HIPCHK(d->dres.alloc(d->res_cap));
   HIPCHK(d->hres.alloc(d->res_cap));
-  HIPCHK(hipEventCreateWithFlags(&d->ev_stage, hipEventDisableTiming));
-  for (hipEvent_t& e : d->ev) HIPCHK(hipEventCreate(&e));
+  for (OvpEvent& e : d->ev) HIPCHK(e.create());
   d->forget();
   c->featdb = d;
   return 0;
@@ -338,11 +324,12 @@ extern "C" int ovp_featdb_append(ovp_ctx* c, double timestamp, int n, const int6
   StageLayout L;
   const size_t o_slot = L.take(sizeof(int) * n), o_fresh = L.take(n), o_id = L.take(sizeof(long long) * n),
                o_uv = L.take(sizeof(float2) * n), o_uvn = L.take(sizeof(float2) * n);
-  if (L.bytes() > d->stage_cap) return OVP_E_CAPACITY;  // (n <= S after the checks above: cannot happen)
+  if (L.bytes() > d->stage.capacity()) return OVP_E_CAPACITY;  // (n <= S after the checks above: cannot happen)
   // ---- from here on the call goes through ----
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(stage_begin(d));
-  char* h = (char*)d->hstage.get();
+  int rs = 0;
+  char* h = d->stage.begin(L.bytes(), &rs);
+  if (!h) return rs;
   for (int i = 0; i < n; ++i) {
     auto it = d->slot_of.find(ids[i]);
     h[o_fresh + i] = it == d->slot_of.end();
@@ -357,9 +344,8 @@ extern "C" int ovp_featdb_append(ovp_ctx* c, double timestamp, int n, const int6
   memcpy(h + o_id, ids, sizeof(long long) * n);
   memcpy(h + o_uv, uv, sizeof(float2) * n);
   memcpy(h + o_uvn, uv_norm, sizeof(float2) * n);
-  const int ru = stage_upload(c, d, L.bytes());
-  if (ru) return ru;
-  const char* dv = (const char*)d->dstage.get();
+  HIPCHK(d->stage.send(L.bytes(), c->stream, Fence::Event));
+  const char* dv = d->stage.dev();
   if (d->timed) HIPCHK(hipEventRecord(d->ev[0], c->stream));
   hipLaunchKernelGGL(k_featdb_append, dim3((n + 255) / 256), dim3(256), 0, c->stream, d->table(), n, timestamp, (const int*)(dv + o_slot),
                      (const unsigned char*)(dv + o_fresh), (const long long*)(dv + o_id), (const float2*)(dv + o_uv),
@@ -382,12 +368,12 @@ extern "C" int ovp_featdb_mark_deleted(ovp_ctx* c, int n, const int64_t* ids) {
     if (!d->slot_of.count(ids[i])) return OVP_E_ARG;
   if (n == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(stage_begin(d));
-  int* h = (int*)d->hstage.get();
+  int rs = 0;
+  int* h = (int*)d->stage.begin(sizeof(int) * n, &rs);
+  if (!h) return rs;
   for (int i = 0; i < n; ++i) h[i] = d->slot_of[ids[i]];
-  const int ru = stage_upload(c, d, sizeof(int) * n);
-  if (ru) return ru;
-  hipLaunchKernelGGL(k_featdb_mark, dim3((n + 255) / 256), dim3(256), 0, c->stream, d->table(), n, (const int*)d->dstage.get());
+  HIPCHK(d->stage.send(sizeof(int) * n, c->stream, Fence::Event));
+  hipLaunchKernelGGL(k_featdb_mark, dim3((n + 255) / 256), dim3(256), 0, c->stream, d->table(), n, (const int*)d->stage.dev());
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -415,16 +401,16 @@ extern "C" int ovp_featdb_classify(ovp_ctx* c, const ovp_featdb_classify_in* in,
   const size_t o_slot = L.take(sizeof(int) * n), o_cl = L.take(sizeof(double) * OVP_MAX_MEAS);
   const size_t r_id = R.take(sizeof(long long) * n), r_cls = R.take(sizeof(int) * n), r_cnt = R.take(sizeof(int) * n),
                r_cln = R.take(sizeof(int) * n), r_fl = R.take(n), r_tot = R.take(sizeof(int) * 4);
-  if (L.bytes() > d->stage_cap || R.bytes() > d->res_cap) return OVP_E_CAPACITY;
+  if (L.bytes() > d->stage.capacity() || R.bytes() > d->res_cap) return OVP_E_CAPACITY;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(stage_begin(d));
-  char* h = (char*)d->hstage.get();
+  int rs = 0;
+  char* h = d->stage.begin(L.bytes(), &rs);
+  if (!h) return rs;
   int k = 0;
   for (const auto& e : d->slot_of) ((int*)(h + o_slot))[k++] = e.second;
   if (in->n_clones) memcpy(h + o_cl, in->clone_times, sizeof(double) * in->n_clones);
-  const int ru = stage_upload(c, d, L.bytes());
-  if (ru) return ru;
-  const char* dv = (const char*)d->dstage.get();
+  HIPCHK(d->stage.send(L.bytes(), c->stream, Fence::Event));
+  const char* dv = d->stage.dev();
   char* dr = (char*)d->dres.get();
   FdbClassify a;
   a.n = n, a.n_clones = in->n_clones, a.max_clone_size = in->max_clone_size, a.want_marg = in->want_marg != 0;
@@ -471,7 +457,7 @@ extern "C" int ovp_featdb_gather(ovp_ctx* c, int n, const int64_t* ids, const in
   }
   StageLayout L;
   const size_t o_slot = L.take(sizeof(int) * n), o_old = L.take(sizeof(int) * n), o_cl = L.take(sizeof(double) * OVP_MAX_MEAS);
-  if (L.bytes() > d->stage_cap) return OVP_E_CAPACITY;
+  if (L.bytes() > d->stage.capacity()) return OVP_E_CAPACITY;
   const int nxt = old_index ? 1 - d->cur : d->cur;
   // the context's batch is the database's buffers from here on, exactly as ovp_batch_bind_device binds a caller's - bound before
   // anything is enqueued, so that a refusal of the bind leaves the database as it was
@@ -482,14 +468,14 @@ extern "C" int ovp_featdb_gather(ovp_ctx* c, int n, const int64_t* ids, const in
   if (rb) return rb;
   HIPCHK(hipSetDevice(c->device));
   if (n > 0) {
-    HIPCHK(stage_begin(d));
-    char* h = (char*)d->hstage.get();
+    int rs = 0;
+    char* h = d->stage.begin(L.bytes(), &rs);
+    if (!h) return rs;
     for (int i = 0; i < n; ++i) ((int*)(h + o_slot))[i] = d->slot_of[ids[i]];
     if (old_index) memcpy(h + o_old, old_index, sizeof(int) * n);
     if (n_clones) memcpy(h + o_cl, clone_times, sizeof(double) * n_clones);
-    const int ru = stage_upload(c, d, L.bytes());
-    if (ru) return ru;
-    const char* dv = (const char*)d->dstage.get();
+    HIPCHK(d->stage.send(L.bytes(), c->stream, Fence::Event));
+    const char* dv = d->stage.dev();
     FdbGather g;
     g.n = n, g.n_clones = n_clones;
     g.slot = (const int*)(dv + o_slot), g.old_index = old_index ? (const int*)(dv + o_old) : nullptr;
@@ -554,17 +540,17 @@ extern "C" int ovp_featdb_cleanup(ovp_ctx* c, int do_cleanup, double measurement
   StageLayout L, R;
   L.take(sizeof(int) * n);
   const size_t r_cnt = R.take(sizeof(int) * n), r_fr = R.take(sizeof(int) * n);
-  if (L.bytes() > d->stage_cap || R.bytes() > d->res_cap) return OVP_E_CAPACITY;
+  if (L.bytes() > d->stage.capacity() || R.bytes() > d->res_cap) return OVP_E_CAPACITY;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(stage_begin(d));
-  int* h = (int*)d->hstage.get();
+  int rs = 0;
+  int* h = (int*)d->stage.begin(L.bytes(), &rs);
+  if (!h) return rs;
   int k = 0;
   for (const auto& e : d->slot_of) h[k++] = e.second;
-  const int ru = stage_upload(c, d, L.bytes());
-  if (ru) return ru;
+  HIPCHK(d->stage.send(L.bytes(), c->stream, Fence::Event));
   char* dr = (char*)d->dres.get();
   if (d->timed) HIPCHK(hipEventRecord(d->ev[0], c->stream));
-  hipLaunchKernelGGL(k_featdb_cleanup, dim3((n + 255) / 256), dim3(256), 0, c->stream, d->table(), n, (const int*)d->dstage.get(),
+  hipLaunchKernelGGL(k_featdb_cleanup, dim3((n + 255) / 256), dim3(256), 0, c->stream, d->table(), n, (const int*)d->stage.dev(),
                      do_cleanup ? 1 : 0, measurements_before_or_nan, (int*)(dr + r_cnt), (int*)(dr + r_fr));
   HIPCHK(hipGetLastError());
   if (d->timed) HIPCHK(hipEventRecord(d->ev[1], c->stream));

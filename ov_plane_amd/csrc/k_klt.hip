@@ -260,27 +260,21 @@ struct Klt {
   DevBuf<double> epi_models;
   std::vector<int32_t> epi_table;
   int epi_H = 0;  // max_iters of the last ovp_klt_epipolar that ran its kernels (0: none)
-  hipEvent_t ev_epi[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   PinnedBuf<unsigned char> himg;  // the upload's staging, rows packed
-  PinnedBuf<void> hstage;
-  DevBuf<void> dstage, dres;
+  UploadFence up;                 // ... the fence of himg and hfull alike (their copies go where the call says: no Staged)
+  Staged stage;                   // a track's or an epipolar check's tables
+  DevBuf<void> dres;
   Mailbox hres;
-  size_t stage_cap = 0, res_cap = 0;
+  size_t res_cap = 0;
   int cur = 0, fed = 0;  // index of the current half; images fed since create / reset
-  hipEvent_t ev_up = nullptr;
-  hipEvent_t ev_eq0 = nullptr, ev_eq1 = nullptr, ev_pyr1 = nullptr, ev_trk0 = nullptr, ev_trk1 = nullptr;  // timed mode
-  hipEvent_t ev_det[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_in0 = nullptr, ev_lut = nullptr;  // timed mode: in front of the halving, between k_clahe_lut and k_clahe_apply
-  bool up_pending = false, timed = false;
+  // timed mode (EV_IN0: in front of the halving, EV_LUT: between k_clahe_lut and k_clahe_apply)
+  enum { EV_EQ0, EV_EQ1, EV_PYR1, EV_TRK0, EV_TRK1, EV_DET, EV_EPI = EV_DET + 4, EV_IN0 = EV_EPI + 5, EV_LUT, EV_COUNT };
+  OvpEvent ev[EV_COUNT];
+  bool timed = false;
   // equalise, pyramid launches together, k_klt_track, k_fast_score_nms, k_fast_select, k_fast_subpix, the four k_epi_* kernels, then
   // the intake's halving, k_clahe_lut and k_clahe_apply
   float ms[13] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int last_n = 0;
-  ~Klt() {
-    for (hipEvent_t e : {ev_up, ev_eq0, ev_eq1, ev_pyr1, ev_trk0, ev_trk1, ev_det[0], ev_det[1], ev_det[2], ev_det[3], ev_epi[0], ev_epi[1], ev_epi[2],
-                         ev_epi[3], ev_epi[4], ev_in0, ev_lut})
-      if (e) (void)hipEventDestroy(e);
-  }
 };
 
 Klt* klt_of(ovp_ctx* c) { return c ? (Klt*)c->klt.get() : nullptr; }
@@ -312,21 +306,16 @@ extern "C" int ovp_klt_create(ovp_ctx* c, int width, int height, int n_levels, i
   HIPCHK(d->nms.alloc((size_t)width * height));
   HIPCHK(d->himg.alloc((size_t)width * height));
   // a track's points and guesses, or an epipolar check's two point sets, status and table
-  d->stage_cap = 64 * 4 + (sizeof(float) * 4 + 1 + sizeof(int)) * (size_t)max_points + sizeof(int);
+  HIPCHK(d->stage.alloc(64 * 4 + (sizeof(float) * 4 + 1 + sizeof(int)) * (size_t)max_points + sizeof(int)));
   // a track's results, a detection's, or an epipolar check's (mask, two coordinate sets, info)
   d->res_cap = 64 * 4 + sizeof(EpiInfoDev) + std::max(sizeof(float) * 2 + 1 + KLT_MAX_LEVELS, sizeof(int) * 3 + sizeof(float) * 2) * (size_t)max_points;
   HIPCHK(d->epi_samples.alloc((size_t)EPI_MAX_ITERS * 7));
   HIPCHK(d->epi_nmodels.alloc(EPI_MAX_ITERS));
   HIPCHK(d->epi_counts.alloc((size_t)EPI_MAX_ITERS * 3));
   HIPCHK(d->epi_models.alloc((size_t)EPI_MAX_ITERS * 27));
-  HIPCHK(d->hstage.alloc(d->stage_cap));
-  HIPCHK(d->dstage.alloc(d->stage_cap));
   HIPCHK(d->dres.alloc(d->res_cap));
   HIPCHK(d->hres.alloc(d->res_cap));
-  HIPCHK(hipEventCreateWithFlags(&d->ev_up, hipEventDisableTiming));
-  for (hipEvent_t* e : {&d->ev_eq0, &d->ev_eq1, &d->ev_pyr1, &d->ev_trk0, &d->ev_trk1, &d->ev_det[0], &d->ev_det[1], &d->ev_det[2], &d->ev_det[3],
-                        &d->ev_epi[0], &d->ev_epi[1], &d->ev_epi[2], &d->ev_epi[3], &d->ev_epi[4], &d->ev_in0, &d->ev_lut})
-    HIPCHK(hipEventCreate(e));
+  for (OvpEvent& e : d->ev) HIPCHK(e.create());
   c->klt = d;
   return 0;
 }
@@ -356,8 +345,9 @@ static int klt_full_buffers(ovp_ctx* c, Klt* d, size_t count) {
   count = std::max(count, (size_t)(2 * d->width + 1) * (2 * d->height + 1));
   if (count <= d->full.capacity()) return 0;
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(d->full.reserve(count, 0));
+  d->up.done();
   HIPCHK(d->hfull.reserve(count, 0));
+  HIPCHK(d->full.reserve(count, 0));  // (second: the capacity asked above is this one's)
   return 0;
 }
 
@@ -380,7 +370,7 @@ static int klt_feed(ovp_ctx* c, Klt* d, const uint8_t* img, int stride, int meth
     const int rf = klt_full_buffers(c, d, 0);
     if (rf) return rf;
   }
-  if (d->up_pending) HIPCHK(hipEventSynchronize(d->ev_up));  // the staging block is free once the previous upload has left it
+  HIPCHK(d->up.wait());
   const int w = d->width, h = d->height, n = w * h;
   unsigned char* stage = halve ? d->hfull.get() : d->himg.get();
   for (int y = 0; y < sh; ++y) memcpy(stage + (size_t)y * sw, img + (size_t)y * stride, sw);
@@ -389,14 +379,13 @@ static int klt_feed(ovp_ctx* c, Klt* d, const uint8_t* img, int stride, int meth
   const bool eq = method != OVP_KLT_HIST_NONE;
   unsigned char* in = eq ? d->raw.get() : lv0;  // what the equalisation reads, or level 0 itself
   HIPCHK(hipMemcpyAsync(halve ? d->full.get() : in, stage, (size_t)sw * sh, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipEventRecord(d->ev_up, c->stream));
-  d->up_pending = true;
+  HIPCHK(d->up.sent(c->stream, Fence::Event));
   if (halve) {  // core/VioManager.cpp:279-289 cv::pyrDown to (cols / 2, rows / 2)
-    if (d->timed) HIPCHK(hipEventRecord(d->ev_in0, c->stream));
+    if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_IN0], c->stream));
     const int rp = klt_pyrdown(d->full.get(), sw, sh, in, w, h, c->stream);
     if (rp) return rp;
   }
-  if (d->timed) HIPCHK(hipEventRecord(d->ev_eq0, c->stream));
+  if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_EQ0], c->stream));
   if (method == OVP_KLT_HIST_HISTOGRAM) {
     HIPCHK(hipMemsetAsync(d->hist.get(), 0, 256 * sizeof(unsigned), c->stream));
     const int blocks = std::max(1, std::min(256, (n / 16 + 255) / 256));
@@ -409,13 +398,13 @@ static int klt_feed(ovp_ctx* c, Klt* d, const uint8_t* img, int stride, int meth
     hipLaunchKernelGGL(k_clahe_lut, dim3(clahe->tiles_x * clahe->tiles_y), dim3(256), 0, c->stream, (const unsigned char*)d->raw.get(), *clahe,
                        d->clahe_lut.get());
     HIPCHK(hipGetLastError());
-    if (d->timed) HIPCHK(hipEventRecord(d->ev_lut, c->stream));
+    if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_LUT], c->stream));
     hipLaunchKernelGGL(k_clahe_apply, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const unsigned char*)d->raw.get(), *clahe,
                        (const unsigned char*)d->clahe_lut.get(), lv0);
     HIPCHK(hipGetLastError());
     d->lut_tiles = clahe->tiles_x * clahe->tiles_y;
   }
-  if (d->timed) HIPCHK(hipEventRecord(d->ev_eq1, c->stream));
+  if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_EQ1], c->stream));
   for (int l = 1; l < d->n_levels; ++l) {
     const int rp = klt_pyrdown(lv0 + d->loff[l - 1], d->lw[l - 1], d->lh[l - 1], lv0 + d->loff[l], d->lw[l], d->lh[l], c->stream);
     if (rp) return rp;
@@ -423,15 +412,15 @@ static int klt_feed(ovp_ctx* c, Klt* d, const uint8_t* img, int stride, int meth
   d->cur = nxt;
   if (d->fed < 2) ++d->fed;
   if (d->timed) {
-    HIPCHK(hipEventRecord(d->ev_pyr1, c->stream));
+    HIPCHK(hipEventRecord(d->ev[Klt::EV_PYR1], c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipEventElapsedTime(&d->ms[0], d->ev_eq0, d->ev_eq1));
-    HIPCHK(hipEventElapsedTime(&d->ms[1], d->ev_eq1, d->ev_pyr1));
+    HIPCHK(hipEventElapsedTime(&d->ms[0], d->ev[Klt::EV_EQ0], d->ev[Klt::EV_EQ1]));
+    HIPCHK(hipEventElapsedTime(&d->ms[1], d->ev[Klt::EV_EQ1], d->ev[Klt::EV_PYR1]));
     d->ms[10] = d->ms[11] = d->ms[12] = 0.f;
-    if (halve) HIPCHK(hipEventElapsedTime(&d->ms[10], d->ev_in0, d->ev_eq0));
+    if (halve) HIPCHK(hipEventElapsedTime(&d->ms[10], d->ev[Klt::EV_IN0], d->ev[Klt::EV_EQ0]));
     if (method == OVP_KLT_HIST_CLAHE) {
-      HIPCHK(hipEventElapsedTime(&d->ms[11], d->ev_eq0, d->ev_lut));
-      HIPCHK(hipEventElapsedTime(&d->ms[12], d->ev_lut, d->ev_eq1));
+      HIPCHK(hipEventElapsedTime(&d->ms[11], d->ev[Klt::EV_EQ0], d->ev[Klt::EV_LUT]));
+      HIPCHK(hipEventElapsedTime(&d->ms[12], d->ev[Klt::EV_LUT], d->ev[Klt::EV_EQ1]));
     }
   }
   return 0;
@@ -483,15 +472,16 @@ extern "C" int ovp_klt_halve(ovp_ctx* c, const uint8_t* src, int stride, int src
     HIPCHK(d->halved.reserve((size_t)w * h, 0));
     HIPCHK(d->hhalved.reserve((size_t)w * h, 0));
   }
-  if (d->up_pending) HIPCHK(hipEventSynchronize(d->ev_up));  // (a feed's upload may still read the staging block)
+  HIPCHK(d->up.wait());  // (a feed's upload may still read the staging block)
   for (int y = 0; y < src_height; ++y) memcpy(d->hfull.get() + (size_t)y * src_width, src + (size_t)y * stride, src_width);
   // `full` is free in stream order: a feed enqueued before has halved it by then, and this call returns when its own copies are done
   HIPCHK(hipMemcpyAsync(d->full.get(), d->hfull.get(), (size_t)src_width * src_height, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(d->up.sent(c->stream, Fence::CallerWaits));
   const int rp = klt_pyrdown(d->full.get(), src_width, src_height, d->halved.get(), w, h, c->stream);
   if (rp) return rp;
   HIPCHK(hipMemcpyAsync(d->hhalved.get(), d->halved.get(), (size_t)w * h, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  d->up_pending = false;
+  d->up.done();
   memcpy(dst, d->hhalved.get(), (size_t)w * h);
   return 0;
 }
@@ -511,14 +501,17 @@ extern "C" int ovp_klt_track(ovp_ctx* c, int n, const float* pts_prev, const flo
   const size_t o_pts = L.take(sizeof(float) * 2 * n), o_guess = L.take(sizeof(float) * 2 * n);
   StageLayout R;
   const size_t r_out = R.take(sizeof(float) * 2 * n), r_st = R.take(n), r_it = R.take((size_t)n * KLT_MAX_LEVELS);
-  if (L.bytes() > d->stage_cap || R.bytes() > d->res_cap) return OVP_E_CAPACITY;  // (cannot happen below max_points)
+  if (L.bytes() > d->stage.capacity() || R.bytes() > d->res_cap) return OVP_E_CAPACITY;  // (cannot happen below max_points)
   // ---- from here on the call goes through ----
   HIPCHK(hipSetDevice(c->device));
-  char* h = (char*)d->hstage.get();
+  int rc = 0;
+  char* h = d->stage.begin(L.bytes(), &rc);
+  if (!h) return rc;
   memcpy(h + o_pts, pts_prev, sizeof(float) * 2 * n);
   memcpy(h + o_guess, guess ? guess : pts_prev, sizeof(float) * 2 * n);  // :1329 the reference passes pts1 = pts0
-  char *dv = (char*)d->dstage.get(), *dr = (char*)d->dres.get();
-  HIPCHK(hipMemcpyAsync(dv, h, L.bytes(), hipMemcpyHostToDevice, c->stream));
+  const char* dv = d->stage.dev();
+  char* dr = (char*)d->dres.get();
+  HIPCHK(d->stage.send(L.bytes(), c->stream, Fence::CallerWaits));
   KltTrackArgs a;
   const unsigned char *pc = d->pyr[d->cur].get(), *pp = d->pyr[d->cur ^ 1].get();
   for (int l = 0; l < KLT_MAX_LEVELS; ++l) {
@@ -528,7 +521,7 @@ extern "C" int ovp_klt_track(ovp_ctx* c, int n, const float* pts_prev, const flo
   a.n_levels = d->n_levels, a.n = n, a.win = d->win;
   a.pts = (const float*)(dv + o_pts), a.guess = (const float*)(dv + o_guess);
   a.out = (float*)(dr + r_out), a.status = (unsigned char*)(dr + r_st), a.iters = (unsigned char*)(dr + r_it);
-  if (d->timed) HIPCHK(hipEventRecord(d->ev_trk0, c->stream));
+  if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_TRK0], c->stream));
   const dim3 grid((n + 3) / 4), block(256);
   const int npl = (d->win * d->win + 63) / 64;
   if (npl <= 1) hipLaunchKernelGGL(k_klt_track<1>, grid, block, 0, c->stream, a);
@@ -536,15 +529,16 @@ extern "C" int ovp_klt_track(ovp_ctx* c, int n, const float* pts_prev, const flo
   else if (npl <= 4) hipLaunchKernelGGL(k_klt_track<4>, grid, block, 0, c->stream, a);
   else hipLaunchKernelGGL(k_klt_track<7>, grid, block, 0, c->stream, a);
   HIPCHK(hipGetLastError());
-  if (d->timed) HIPCHK(hipEventRecord(d->ev_trk1, c->stream));
+  if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_TRK1], c->stream));
   SeqChannel& ch = d->hres.channel(0);
   const unsigned seq = ch.arm();
   HIPCHK(ovp_launch_publish_block(dr, d->hres.dev(d->hres.payload()), R.bytes(), ch.word_dev(), seq, 0, c->stream));
   const int rw = ch.wait(c->stream);
   if (rw) return rw;
+  d->stage.done();
   if (d->timed) {
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipEventElapsedTime(&d->ms[2], d->ev_trk0, d->ev_trk1));
+    HIPCHK(hipEventElapsedTime(&d->ms[2], d->ev[Klt::EV_TRK0], d->ev[Klt::EV_TRK1]));
   }
   const char* hr = (const char*)d->hres.payload();
   memcpy(pts_out, hr + r_out, sizeof(float) * 2 * n);
@@ -601,22 +595,22 @@ extern "C" int ovp_klt_detect(ovp_ctx* c, int half, int num_features, int grid_x
   HIPCHK(hipSetDevice(c->device));
   const unsigned char* img = d->pyr[half ? d->cur ^ 1 : d->cur].get();  // level 0 of that half
   char* dr = (char*)d->dres.get();
-  if (d->timed) HIPCHK(hipEventRecord(d->ev_det[0], c->stream));
+  if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_DET + 0], c->stream));
   hipLaunchKernelGGL(k_fast_score_nms, dim3((d->width + FAST_TW - 1) / FAST_TW, (d->height + FAST_TH - 1) / FAST_TH), dim3(256), 0, c->stream,
                      img, g, threshold, d->score.get(), d->nms.get());
   HIPCHK(hipGetLastError());
-  if (d->timed) HIPCHK(hipEventRecord(d->ev_det[1], c->stream));
+  if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_DET + 1], c->stream));
   hipLaunchKernelGGL(k_fast_select, dim3((unsigned)cells), dim3(256), 0, c->stream, (const unsigned char*)d->nms.get(), g, (int*)(dr + r_xy),
                      (int*)(dr + r_resp));
   HIPCHK(hipGetLastError());
-  if (d->timed) HIPCHK(hipEventRecord(d->ev_det[2], c->stream));
+  if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_DET + 2], c->stream));
   FastSubpixArgs a;
   a.img = img, a.cols = d->width, a.rows = d->height, a.n = n;
   a.xy = (const int*)(dr + r_xy), a.resp = (const int*)(dr + r_resp), a.out = (float*)(dr + r_ref), a.start = nullptr;
   fast_subpix_weights(a.w);
   hipLaunchKernelGGL(k_fast_subpix, dim3((n + 3) / 4), dim3(256), 0, c->stream, a);
   HIPCHK(hipGetLastError());
-  if (d->timed) HIPCHK(hipEventRecord(d->ev_det[3], c->stream));
+  if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_DET + 3], c->stream));
   SeqChannel& ch = d->hres.channel(0);
   const unsigned seq = ch.arm();
   HIPCHK(ovp_launch_publish_block(dr, d->hres.dev(d->hres.payload()), R.bytes(), ch.word_dev(), seq, 0, c->stream));
@@ -624,7 +618,7 @@ extern "C" int ovp_klt_detect(ovp_ctx* c, int half, int num_features, int grid_x
   if (rw) return rw;
   if (d->timed) {
     HIPCHK(hipStreamSynchronize(c->stream));
-    for (int k = 0; k < 3; ++k) HIPCHK(hipEventElapsedTime(&d->ms[3 + k], d->ev_det[k], d->ev_det[k + 1]));
+    for (int k = 0; k < 3; ++k) HIPCHK(hipEventElapsedTime(&d->ms[3 + k], d->ev[Klt::EV_DET + k], d->ev[Klt::EV_DET + k + 1]));
   }
   // the slots in output order (cell ascending, then selection order), the empty ones gone
   const char* hr = (const char*)d->hres.payload();
@@ -674,18 +668,21 @@ extern "C" int ovp_klt_epipolar(ovp_ctx* c, const ovp_epipolar_opts* o, int n, c
   const size_t o_p0 = L.take(sizeof(float) * 2 * n), o_p1 = L.take(sizeof(float) * 2 * n), o_st = L.take(n), o_tab = L.take(sizeof(int) * (n + 1));
   StageLayout R;
   const size_t r_mask = R.take(n), r_u0 = R.take(sizeof(float) * 2 * n), r_u1 = R.take(sizeof(float) * 2 * n), r_info = R.take(sizeof(EpiInfoDev));
-  if (L.bytes() > d->stage_cap || R.bytes() > d->res_cap) return OVP_E_CAPACITY;  // (cannot happen below max_points)
+  if (L.bytes() > d->stage.capacity() || R.bytes() > d->res_cap) return OVP_E_CAPACITY;  // (cannot happen below max_points)
   // ---- from here on the call goes through ----
   HIPCHK(hipSetDevice(c->device));
-  char* h = (char*)d->hstage.get();
+  int rc = 0;
+  char* h = d->stage.begin(L.bytes(), &rc);
+  if (!h) return rc;
   memcpy(h + o_p0, pts0, sizeof(float) * 2 * n);
   memcpy(h + o_p1, pts1, sizeof(float) * 2 * n);
   for (int i = 0; i < n; ++i) h[o_st + i] = status ? (status[i] != 0) : 1;
   std::vector<int32_t> table(n + 1, 0);
   if (!few) ovp_epi_table(n, o->confidence, o->max_iters, table.data());
   memcpy(h + o_tab, table.data(), sizeof(int) * (n + 1));
-  char *dv = (char*)d->dstage.get(), *dr = (char*)d->dres.get();
-  HIPCHK(hipMemcpyAsync(dv, h, L.bytes(), hipMemcpyHostToDevice, c->stream));
+  const char* dv = d->stage.dev();
+  char* dr = (char*)d->dres.get();
+  HIPCHK(d->stage.send(L.bytes(), c->stream, Fence::CallerWaits));
   EpiLaunch a;
   a.n = n, a.max_iters = o->max_iters, a.mode = o->mode, a.seed = o->seed;
   for (int k = 0; k < 8; ++k) a.intr[k] = o->intrinsics[k];
@@ -694,7 +691,9 @@ extern "C" int ovp_klt_epipolar(ovp_ctx* c, const ovp_epipolar_opts* o, int n, c
   a.table = (const int*)(dv + o_tab);
   a.samples = d->epi_samples.get(), a.n_models = d->epi_nmodels.get(), a.models = d->epi_models.get(), a.counts = d->epi_counts.get();
   a.mask = (unsigned char*)(dr + r_mask), a.uvn0 = (float*)(dr + r_u0), a.uvn1 = (float*)(dr + r_u1), a.info = (EpiInfoDev*)(dr + r_info);
-  a.ev = d->timed ? d->ev_epi : nullptr;
+  hipEvent_t ev_epi[5];
+  for (int k = 0; k < 5; ++k) ev_epi[k] = d->ev[Klt::EV_EPI + k];
+  a.ev = d->timed ? ev_epi : nullptr;
   const int rl = ovp_epi_enqueue(a, c->stream);  // (a set below OVP_EPI_MIN_POINTS: the undistortion, a zero mask and too_few)
   if (rl) return rl;
   SeqChannel& ch = d->hres.channel(0);
@@ -702,9 +701,10 @@ extern "C" int ovp_klt_epipolar(ovp_ctx* c, const ovp_epipolar_opts* o, int n, c
   HIPCHK(ovp_launch_publish_block(dr, d->hres.dev(d->hres.payload()), R.bytes(), ch.word_dev(), seq, 0, c->stream));
   const int rw = ch.wait(c->stream);
   if (rw) return rw;
+  d->stage.done();
   if (d->timed && !few) {
     HIPCHK(hipStreamSynchronize(c->stream));
-    for (int k = 0; k < 4; ++k) HIPCHK(hipEventElapsedTime(&d->ms[6 + k], d->ev_epi[k], d->ev_epi[k + 1]));
+    for (int k = 0; k < 4; ++k) HIPCHK(hipEventElapsedTime(&d->ms[6 + k], d->ev[Klt::EV_EPI + k], d->ev[Klt::EV_EPI + k + 1]));
   }
   const char* hr = (const char*)d->hres.payload();
   if (mask_out) memcpy(mask_out, hr + r_mask, n);

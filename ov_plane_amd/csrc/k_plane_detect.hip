@@ -277,11 +277,11 @@ struct Detector {
   ovp_trackplane_opts o;
   DevBuf<double> A, b, p, ring, avg;
   DevBuf<int> count, valid, ring_n;
-  PinnedBuf<void> hstage;
+  Staged stage;  // the tables of a stage
   Mailbox hres;  // the results of a stage: payload from byte 0, channel 0
-  DevBuf<void> dstage, dres;
-  size_t stage_cap = 0, res_cap = 0;
-  hipEvent_t ev[8] = {};
+  DevBuf<void> dres;
+  size_t res_cap = 0;
+  OvpEvent ev[8];
   float ms[4] = {0, 0, 0, 0};
   float ms_delaunay[2] = {0, 0};  // k_det_delaunay of the last timed frame / of the last timed ovp_delaunay_device
   bool timed = false;  // ovp_plane_detector_debug "timer": events around the kernels, read behind a stream synchronisation
@@ -304,10 +304,6 @@ struct Detector {
   int dev_hdr[OVP_DL_HDR] = {};
   int tri_source = 0;  // of the last ovp_plane_detect_planes: 0 the caller's, 1 ovp_delaunay_host, 2 the device's
   DetState st() const { return DetState{A.get(), b.get(), p.get(), count.get(), valid.get(), ring.get(), avg.get(), ring_n.get()}; }
-  ~Detector() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
   void forget() {
     slot_of.clear();
     free_slots.clear();
@@ -323,24 +319,22 @@ struct Detector {
 
 // ovp_delaunay_device: staging, result block and mailbox of its own (a context without a detector has none), made on first use
 struct DelaunayIo {
-  PinnedBuf<void> hstage;
-  DevBuf<void> dstage, dres;
+  Staged stage;
+  DevBuf<void> dres;
   Mailbox hres;
-  hipEvent_t ev[2] = {};
-  ~DelaunayIo() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  OvpEvent ev[2];
 };
 
 Detector* det_of(ovp_ctx* c) { return c ? (Detector*)c->plane_det.get() : nullptr; }
 
-// device result block -> pinned, waited for
+// device result block -> pinned, waited for: the stage's tables have been read by then
 int publish_and_wait(ovp_ctx* c, Detector* d, size_t bytes) {
   SeqChannel& ch = d->hres.channel(0);
   const unsigned seq = ch.arm();
   HIPCHK(ovp_launch_publish_block(d->dres.get(), d->hres.dev(d->hres.payload()), bytes, ch.word_dev(), seq, 0, c->stream));
-  return ch.wait(c->stream);
+  const int rw = ch.wait(c->stream);
+  if (!rw) d->stage.done();
+  return rw;
 }
 
 }  // namespace
@@ -370,15 +364,13 @@ extern "C" int ovp_plane_detector_create(ovp_ctx* c, const ovp_trackplane_opts* 
   HIPCHK(d->ring_n.alloc(S));
   // the largest of the three staged tables / result blocks (second call: triangles, two CSR lists, edge ends)
   // (and the first call's with the device triangulation: the pixel positions in, the header and the triangles out)
-  d->stage_cap = 64 * 16 + sizeof(int) * ((size_t)S * 4 + 3 * MAX_TRIS * 2 + 2 * MAX_EDGES + 2 * (S + 1)) + sizeof(double) * (2 * S + 12) +
-                 sizeof(float) * 2 * S;
+  HIPCHK(d->stage.alloc(64 * 16 + sizeof(int) * ((size_t)S * 4 + 3 * MAX_TRIS * 2 + 2 * MAX_EDGES + 2 * (S + 1)) +
+                        sizeof(double) * (2 * S + 12) + sizeof(float) * 2 * S));
   d->res_cap = 64 * 8 + sizeof(double) * 3 * MAX_TRIS + MAX_TRIS + MAX_EDGES + sizeof(double) * 3 * S + sizeof(int) * S +
                sizeof(int) * (OVP_DL_HDR + 3 * MAX_TRIS);
-  HIPCHK(d->hstage.alloc(d->stage_cap));
-  HIPCHK(d->dstage.alloc(d->stage_cap));
   HIPCHK(d->dres.alloc(d->res_cap));
   HIPCHK(d->hres.alloc(d->res_cap));
-  for (hipEvent_t& e : d->ev) HIPCHK(hipEventCreate(&e));
+  for (OvpEvent& e : d->ev) HIPCHK(e.create());
   HIPCHK(hipMemsetAsync(d->valid.get(), 0, sizeof(int) * S, c->stream));
   HIPCHK(hipMemsetAsync(d->ring_n.get(), 0, sizeof(int) * S, c->stream));
   HIPCHK(hipMemsetAsync(d->avg.get(), 0, sizeof(double) * 3 * S, c->stream));
@@ -438,8 +430,10 @@ extern "C" int ovp_plane_detect_triangulate(ovp_ctx* c, int n, const int64_t* id
   const int dl_cap = 2 * n;
   const size_t o_uv = dl ? L.take(sizeof(float) * 2 * n) : 0, r_dhdr = dl ? Rl.take(sizeof(int) * OVP_DL_HDR) : 0,
                r_dtri = dl ? Rl.take(sizeof(int) * 3 * dl_cap) : 0;
-  if (L.bytes() > d->stage_cap || Rl.bytes() > d->res_cap) return OVP_E_CAPACITY;
-  char* h = (char*)d->hstage.get();
+  if (Rl.bytes() > d->res_cap) return OVP_E_CAPACITY;
+  int rc = 0;
+  char* h = d->stage.begin(L.bytes(), &rc);
+  if (!h) return rc;
   int* h_slot = (int*)(h + o_slot);
   for (int i = 0; i < n; ++i) {
     auto it = d->slot_of.find(ids[i]);
@@ -457,9 +451,9 @@ extern "C" int ovp_plane_detect_triangulate(ovp_ctx* c, int n, const int64_t* id
   memcpy(h + o_pose + sizeof(double) * 9, p_CinG, sizeof(double) * 3);
   memcpy(d->pose, h + o_pose, sizeof(double) * 12);
   if (dl) memcpy(h + o_uv, uv, sizeof(float) * 2 * n);
-  char* dv = (char*)d->dstage.get();
+  const char* dv = d->stage.dev();
   char* dr = (char*)d->dres.get();
-  HIPCHK(hipMemcpyAsync(dv, h, L.bytes(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(d->stage.send(L.bytes(), c->stream, Fence::CallerWaits));
   if (d->timed) HIPCHK(hipEventRecord(d->ev[0], c->stream));
   hipLaunchKernelGGL(k_det_triangulate, dim3((n + 255) / 256), dim3(256), 0, c->stream, d->st(), n, (const int*)(dv + o_slot),
                      (const unsigned char*)(dv + o_fresh), (const double*)(dv + o_uvn), (const double*)(dv + o_pose),
@@ -537,11 +531,10 @@ extern "C" int ovp_delaunay_device(ovp_ctx* c, int n, const float* xy, int32_t* 
   if (!c->delaunay_io) {
     auto io = std::make_shared<DelaunayIo>();
     const size_t res = sizeof(int) * (OVP_DL_HDR + 3 * (size_t)MAX_TRIS);
-    HIPCHK(io->hstage.alloc(sizeof(float) * 2 * S));
-    HIPCHK(io->dstage.alloc(sizeof(float) * 2 * S));
+    HIPCHK(io->stage.alloc(sizeof(float) * 2 * S));
     HIPCHK(io->dres.alloc(res));
     HIPCHK(io->hres.alloc(res));
-    for (hipEvent_t& e : io->ev) HIPCHK(hipEventCreate(&e));
+    for (OvpEvent& e : io->ev) HIPCHK(e.create());
     c->delaunay_io = io;
   }
   DelaunayIo* io = (DelaunayIo*)c->delaunay_io.get();
@@ -549,10 +542,13 @@ extern "C" int ovp_delaunay_device(ovp_ctx* c, int n, const float* xy, int32_t* 
   const bool timed = d && d->timed;
   const int dl_cap = 2 * n;
   int* dhdr = (int*)io->dres.get();
-  memcpy(io->hstage.get(), xy, sizeof(float) * 2 * n);
-  HIPCHK(hipMemcpyAsync(io->dstage.get(), io->hstage.get(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
+  int rc = 0;
+  char* h = io->stage.begin(sizeof(float) * 2 * n, &rc);
+  if (!h) return rc;
+  memcpy(h, xy, sizeof(float) * 2 * n);
+  HIPCHK(io->stage.send(sizeof(float) * 2 * n, c->stream, Fence::CallerWaits));
   if (timed) HIPCHK(hipEventRecord(io->ev[0], c->stream));
-  HIPCHK(ovp_launch_delaunay(n, (const float*)io->dstage.get(), nullptr, dhdr, dhdr + OVP_DL_HDR, dl_cap, c->stream));
+  HIPCHK(ovp_launch_delaunay(n, (const float*)io->stage.dev(), nullptr, dhdr, dhdr + OVP_DL_HDR, dl_cap, c->stream));
   if (timed) HIPCHK(hipEventRecord(io->ev[1], c->stream));
   SeqChannel& ch = io->hres.channel(0);
   const unsigned seq = ch.arm();
@@ -560,6 +556,7 @@ extern "C" int ovp_delaunay_device(ovp_ctx* c, int n, const float* xy, int32_t* 
                                   0, c->stream));
   const int rw = ch.wait(c->stream);
   if (rw) return rw;
+  io->stage.done();
   if (timed) {
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipEventElapsedTime(&d->ms_delaunay[1], io->ev[0], io->ev[1]));
@@ -601,8 +598,9 @@ extern "C" int ovp_plane_detect_planes(ovp_ctx* c, int n_tris, const int32_t* tr
   if (3 * (size_t)nt * 2 > (size_t)MAX_EDGES) return OVP_E_CAPACITY;  // (directed neighbour edges: at most six per triangle)
   HIPCHK(hipSetDevice(c->device));
   const ovp_trackplane_opts& o = d->o;
-  char* h = (char*)d->hstage.get();
-  char* dv = (char*)d->dstage.get();
+  int rc = 0;
+  char* h = nullptr;  // (the staging block, taken anew for each of the call's two uploads)
+  const char* dv = d->stage.dev();
   char* dr = (char*)d->dres.get();
   const char* hr = (const char*)d->hres.payload();
   std::vector<std::vector<int>> nb(nv);  // feat_to_close_feat: neighbours, ascending feature id
@@ -634,7 +632,8 @@ extern "C" int ovp_plane_detect_planes(ovp_ctx* c, int n_tris, const int32_t* tr
                  o_ed = L.take(sizeof(int) * ne), o_pose = L.take(sizeof(double) * 12);
     StageLayout Rl;
     const size_t r_match = Rl.take(ne), r_trin = Rl.take(sizeof(double) * 3 * nt), r_triok = Rl.take(nt);
-    if (L.bytes() > d->stage_cap || Rl.bytes() > d->res_cap) return OVP_E_CAPACITY;
+    if (Rl.bytes() > d->res_cap) return OVP_E_CAPACITY;
+    if (!(h = d->stage.begin(L.bytes(), &rc))) return rc;
     d->have_frame = false;  // from here on the frame is consumed: the normal histories change
     memcpy(h + o_vslot, d->v_slot.data(), sizeof(int) * nv);
     memcpy(h + o_vpx, d->v_px.data(), sizeof(float) * 2 * nv);
@@ -651,7 +650,7 @@ extern "C" int ovp_plane_detect_planes(ovp_ctx* c, int n_tris, const int32_t* tr
     }
     vtp[nv] = at;
     memcpy(h + o_pose, d->pose, sizeof(double) * 12);
-    HIPCHK(hipMemcpyAsync(dv, h, L.bytes(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(d->stage.send(L.bytes(), c->stream, Fence::CallerWaits));
     if (d->timed) HIPCHK(hipEventRecord(d->ev[2], c->stream));
     hipLaunchKernelGGL(k_det_tri_normals, dim3((nt + 255) / 256), dim3(256), 0, c->stream, nt, (const int*)(dv + o_tris),
                        (const int*)(dv + o_vslot), (const float*)(dv + o_vpx), (const double*)d->p.get(), (const double*)(dv + o_pose),
@@ -745,10 +744,11 @@ extern "C" int ovp_plane_detect_planes(ovp_ctx* c, int n_tris, const int32_t* tr
       const size_t o_ptr = L.take(sizeof(int) * (np + 1)), o_sl = L.take(sizeof(int) * m);
       StageLayout Rl;
       const size_t r_d = Rl.take(sizeof(double) * m), r_f = Rl.take(m);
-      if (L.bytes() > d->stage_cap || Rl.bytes() > d->res_cap) return OVP_E_CAPACITY;
+      if (Rl.bytes() > d->res_cap) return OVP_E_CAPACITY;
+      if (!(h = d->stage.begin(L.bytes(), &rc))) return rc;
       memcpy(h + o_ptr, pl_ptr.data(), sizeof(int) * (np + 1));
       memcpy(h + o_sl, pl_slot.data(), sizeof(int) * m);
-      HIPCHK(hipMemcpyAsync(dv, h, L.bytes(), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(d->stage.send(L.bytes(), c->stream, Fence::CallerWaits));
       if (d->timed) HIPCHK(hipEventRecord(d->ev[5], c->stream));
       hipLaunchKernelGGL(k_det_spatial_filter, dim3(np), dim3(256), 0, c->stream, (const int*)(dv + o_ptr), (const int*)(dv + o_sl),
                          (const double*)d->p.get(), o.filter_num_feat, o.filter_z_thresh, (double*)(dr + r_d), (unsigned char*)(dr + r_f));
@@ -814,19 +814,21 @@ extern "C" int ovp_plane_spatial_filter(ovp_ctx* c, int n_planes, const int* fea
   const size_t o_ptr = L.take(sizeof(int) * (np + 1)), o_sl = L.take(sizeof(int) * mm), o_p = L.take(sizeof(double) * 3 * mm);
   StageLayout Rl;
   const size_t r_d = Rl.take(sizeof(double) * mm), r_f = Rl.take(mm);
-  if (L.bytes() > d->stage_cap || Rl.bytes() > d->res_cap) return OVP_E_CAPACITY;
+  if (L.bytes() > d->stage.capacity() || Rl.bytes() > d->res_cap) return OVP_E_CAPACITY;
   for (int i = 0; i < m; ++i) mean_dist[i] = 0.0, flagged[i] = 0;
   if (np == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
-  char* h = (char*)d->hstage.get();
-  char* dv = (char*)d->dstage.get();
+  int rc = 0;
+  char* h = d->stage.begin(L.bytes(), &rc);
+  if (!h) return rc;
+  const char* dv = d->stage.dev();
   char* dr = (char*)d->dres.get();
   memcpy(h + o_ptr, ptr.data(), sizeof(int) * (np + 1));
   for (int i = 0; i < mm; ++i) {
     ((int*)(h + o_sl))[i] = i;
     memcpy(h + o_p + sizeof(double) * 3 * i, p_FinG + 3 * (size_t)src[i], sizeof(double) * 3);
   }
-  HIPCHK(hipMemcpyAsync(dv, h, L.bytes(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(d->stage.send(L.bytes(), c->stream, Fence::CallerWaits));
   if (d->timed) HIPCHK(hipEventRecord(d->ev[5], c->stream));
   hipLaunchKernelGGL(k_det_spatial_filter, dim3(np), dim3(256), 0, c->stream, (const int*)(dv + o_ptr), (const int*)(dv + o_sl),
                      (const double*)(dv + o_p), filter_num_feat, filter_z_thresh, (double*)(dr + r_d), (unsigned char*)(dr + r_f));

@@ -26,6 +26,7 @@
 #include <vector>
 
 extern "C" int ovp_io_arena(ovp_ctx* c, size_t bytes, void** host, void** dev);  // ovp_api_ctx.hip: pinned host + device block per context
+extern "C" void ovp_io_arena_done(ovp_ctx* c);  // ... behind the wait for the copies that read and wrote it
 
 namespace ovp {
 
@@ -1234,6 +1235,7 @@ extern "C" int ovp_plane_fitting(ovp_ctx* c, const ovp_planefit_batch* b, double
   PF_HIPCHK(hipGetLastError());
   PF_HIPCHK(hipMemcpyAsync(hb + a_abcd, blob + a_abcd, total - a_abcd, hipMemcpyDeviceToHost, s));
   PF_HIPCHK(hipStreamSynchronize(s));
+  ovp_io_arena_done(c);
   memcpy(abcd, hb + a_abcd, sizeof(double) * 4 * (size_t)P);
   memcpy(inlier, hb + a_inl, (size_t)F);
   memcpy(ok, hb + a_ok, (size_t)P);
@@ -1353,6 +1355,7 @@ extern "C" int ovp_plane_optimize(ovp_ctx* c, const ovp_planeopt_batch* b, doubl
   PF_HIPCHK(hipGetLastError());
   PF_HIPCHK(hipMemcpyAsync(hb + o_cpo, blob + o_cpo, off - o_cpo, hipMemcpyDeviceToHost, s));
   PF_HIPCHK(hipStreamSynchronize(s));
+  ovp_io_arena_done(c);
 #ifdef OVP_PF_STAMPS
   {
     long long h[64 * 12];

@@ -183,32 +183,23 @@ __global__ __launch_bounds__(256) void k_plane_merge_apply(double* __restrict__ 
 
 // The entries' own buffers, made on first use and freed with the context.
 struct Retire {
-  PinnedBuf<void> hstage;
-  DevBuf<void> dstage;
+  Staged stage;          // the call's tables (a call that reports nothing does not wait: Fence::Event)
   DevBuf<double> dres, W;
   Mailbox hres;          // the merge results: payload from byte 0, channel 0
-  hipEvent_t ev = nullptr;  // behind the upload of hstage (ovp_cov_marginalize_many does not wait; the next call rewrites the block)
-  bool ev_armed = false;
-  size_t stage_cap = 0, res_doubles = 0;
+  size_t res_doubles = 0;
   int stride = 0;
-  ~Retire() {
-    if (ev) (void)hipEventDestroy(ev);
-  }
 };
 
 int retire_of(ovp_ctx* c, Retire** out) {
   if (!c->retire) {
     auto d = std::make_shared<Retire>();
     d->stride = round_up(4 + c->n_max, 8);
-    d->stage_cap = 64 * 8 + sizeof(int2) * (size_t)c->n_max + sizeof(int) * (4 * (size_t)RT_MAX_PAIRS + RT_MAX_PLANES) +
-                   sizeof(double) * 3 * RT_MAX_PLANES;
     d->res_doubles = (size_t)RT_MAX_PAIRS * d->stride;
-    HIPCHK(d->hstage.alloc(d->stage_cap));
-    HIPCHK(d->dstage.alloc(d->stage_cap));
+    HIPCHK(d->stage.alloc(64 * 8 + sizeof(int2) * (size_t)c->n_max + sizeof(int) * (4 * (size_t)RT_MAX_PAIRS + RT_MAX_PLANES) +
+                          sizeof(double) * 3 * RT_MAX_PLANES));
     HIPCHK(d->dres.alloc(d->res_doubles));
     HIPCHK(d->W.alloc(3 * (size_t)c->n_max + 8));
     HIPCHK(d->hres.alloc(sizeof(double) * d->res_doubles));
-    HIPCHK(hipEventCreateWithFlags(&d->ev, hipEventDisableTiming));
     c->retire = d;
   }
   *out = (Retire*)c->retire.get();
@@ -241,15 +232,6 @@ hipError_t launch_compact(const double* src, double* dst, int ld, int n_out, con
   return hipGetLastError();
 }
 
-// the staging block is free again once the copy of the call before has run
-int stage_free(Retire* d) {
-  if (d->ev_armed) {
-    HIPCHK(hipEventSynchronize(d->ev));
-    d->ev_armed = false;
-  }
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int ovp_cov_marginalize_many(ovp_ctx* c, int n_ranges, const int* ids, const int* sizes) {
@@ -266,12 +248,12 @@ extern "C" int ovp_cov_marginalize_many(ovp_ctx* c, int n_ranges, const int* ids
   HIPCHK(hipSetDevice(c->device));
   Retire* d = nullptr;
   if (const int rc = retire_of(c, &d)) return rc;
-  if (const int rc = stage_free(d)) return rc;
-  memcpy(d->hstage.get(), rg.data(), sizeof(int2) * n_ranges);
-  HIPCHK(hipMemcpyAsync(d->dstage.get(), d->hstage.get(), sizeof(int2) * n_ranges, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipEventRecord(d->ev, c->stream));
-  d->ev_armed = true;
-  HIPCHK(launch_compact(c->P, c->P_tmp, c->ld, n_out, (const int2*)d->dstage.get(), n_ranges, c->stream));
+  int rc = 0;
+  char* h = d->stage.begin(sizeof(int2) * n_ranges, &rc);
+  if (!h) return rc;
+  memcpy(h, rg.data(), sizeof(int2) * n_ranges);
+  HIPCHK(d->stage.send(sizeof(int2) * n_ranges, c->stream, Fence::Event));
+  HIPCHK(launch_compact(c->P, c->P_tmp, c->ld, n_out, (const int2*)d->stage.dev(), n_ranges, c->stream));
   c->P.swap(c->P_tmp);
   c->n = n_out;
   return 0;
@@ -323,13 +305,13 @@ extern "C" int ovp_planes_merge_retire(ovp_ctx* c, const ovp_plane_merge_in* in,
   HIPCHK(hipSetDevice(c->device));
   Retire* d = nullptr;
   if (const int rc = retire_of(c, &d)) return rc;
-  if (const int rc = stage_free(d)) return rc;
   StageLayout lay;
   const size_t o_rg = lay.take(sizeof(int2) * nr), o_pair = lay.take(sizeof(int) * 4 * np), o_col = lay.take(sizeof(int) * npl),
                o_cp = lay.take(sizeof(double) * 3 * npl);
-  if (lay.bytes() > d->stage_cap) return OVP_E_CAPACITY;  // (cannot happen below the limits above)
-  char* h = (char*)d->hstage.get();
-  char* dv = (char*)d->dstage.get();
+  int rc = 0;
+  char* h = d->stage.begin(lay.bytes(), &rc);  // (above the capacity: cannot happen below the limits above)
+  if (!h) return rc;
+  char* dv = d->stage.dev();
   hipStream_t s = c->stream;
   if (nr > 0) memcpy(h + o_rg, rg.data(), sizeof(int2) * nr);
   if (np > 0) memcpy(h + o_pair, pair.data(), sizeof(int) * 4 * np);
@@ -337,7 +319,8 @@ extern "C" int ovp_planes_merge_retire(ovp_ctx* c, const ovp_plane_merge_in* in,
     memcpy(h + o_col, in->plane_col, sizeof(int) * npl);
     memcpy(h + o_cp, in->cp, sizeof(double) * 3 * npl);
   }
-  HIPCHK(hipMemcpyAsync(dv, h, lay.bytes(), hipMemcpyHostToDevice, s));
+  // (nothing to report: the compaction alone does not wait, as ovp_cov_marginalize_many leaves it)
+  HIPCHK(d->stage.send(lay.bytes(), s, np == 0 ? Fence::Event : Fence::CallerWaits));
   MergeJob j;
   j.P = c->P, j.ld = c->ld, j.n = n, j.np = np, j.n_planes = npl, j.stride = d->stride;
   j.pair = (const int*)(dv + o_pair), j.plane_col = (const int*)(dv + o_col), j.cp = (double*)(dv + o_cp);
@@ -358,16 +341,14 @@ extern "C" int ovp_planes_merge_retire(ovp_ctx* c, const ovp_plane_merge_in* in,
     c->P.swap(c->P_tmp);
     c->n = n_out;
   }
-  if (np == 0) {  // nothing to report: the compaction alone, as ovp_cov_marginalize_many leaves it
-    HIPCHK(hipEventRecord(d->ev, s));
-    d->ev_armed = true;
-  } else {
+  if (np > 0) {
     SeqChannel& ch = d->hres.channel(0);
     const unsigned seq = ch.arm();
     HIPCHK(ovp_launch_publish_block(d->dres.get(), d->hres.dev(d->hres.payload()), sizeof(double) * (size_t)np * d->stride, ch.word_dev(),
                                     seq, 0, s));
     const int rw = ch.wait(s);
     if (rw) return rw;
+    d->stage.done();
   }
   bool neg = false;
   const double* hr = (const double*)d->hres.payload();

@@ -99,11 +99,11 @@ extern "C" int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int
     c->own_stream = true;
   }
   HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-  HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-  for (int i = 0; i < 6; ++i) HIPCHK(hipEventCreate(&c->ev_t[i]));
-  HIPCHK(hipEventCreate(&c->ev_k0));
-  HIPCHK(hipEventCreate(&c->ev_k1));
+  HIPCHK(c->ev_fork.create(hipEventDisableTiming));
+  HIPCHK(c->ev_join.create(hipEventDisableTiming));
+  for (OvpEvent& e : c->ev_t) HIPCHK(e.create());
+  HIPCHK(c->ev_k0.create());
+  HIPCHK(c->ev_k1.create());
   c->n_max = n_state_max;
   c->c_max = n_clones_max;
   c->f_max = n_feats_max;
@@ -140,9 +140,8 @@ extern "C" int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int
     c->so_cm = lay.take(sizeof(ovp::ColMap) * c->n_max);
     const size_t o = c->state_bytes = lay.bytes();
     HIPCHK(c->state_block.alloc(o));
-    HIPCHK(hipMemset(c->state_block, 0, o));
-    HIPCHK(c->h_state_stage.alloc(o));
-    char* b = (char*)c->state_block;
+    HIPCHK(hipMemset(c->state_block.dev(), 0, o));
+    char* b = c->state_block.dev();
     c->clone_R = (double*)(b + c->so_R);
     c->clone_R_fej = (double*)(b + c->so_Rf);
     c->clone_p = (double*)(b + c->so_p);
@@ -150,8 +149,6 @@ extern "C" int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int
     c->cal = (double*)(b + c->so_cal);
     c->clone_id = (int*)(b + c->so_id);
     c->colmap = (ovp::ColMap*)(b + c->so_cm);
-    HIPCHK(hipEventCreateWithFlags(&c->ev_state, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_batch, hipEventDisableTiming));
   }
   HIPCHK(c->chi2_table.alloc((size_t)OVP_CHI2_TABLE + 1));
   {
@@ -159,8 +156,7 @@ extern "C" int ovp_ctx_create(int device, int n_state_max, int n_clones_max, int
     const size_t F = (size_t)n_feats_max, M = OVP_MAX_MEAS;
     const size_t cap = sizeof(double) * 3 * F + sizeof(int) * F + sizeof(int) * F * M + sizeof(float) * 2 * F * M + 256;
     HIPCHK(c->batch_block.alloc(cap));
-    HIPCHK(c->h_batch_stage.alloc(cap));
-    c->p_FinG = (double*)c->batch_block;
+    c->p_FinG = (double*)c->batch_block.dev();
   }
   HIPCHK(c->G.alloc((size_t)3 * n_feats_max * c->ldg));
   HIPCHK(c->Bscr.alloc((size_t)n_feats_max * OVP_BSCR));
@@ -230,7 +226,6 @@ extern "C" int ovp_ctx_stream(ovp_ctx* c, void** stream) {
 extern "C" int ovp_cov_size(ovp_ctx* c) { return c ? c->n : OVP_E_ARG; }
 
 // ---- covariance residency ----------------------------------------------------------------------
-extern "C" int ovp_io_arena(ovp_ctx* c, size_t bytes, void** host, void** dev);
 
 // (upload / download / marginal / propagate go through the pinned arena: one contiguous copy each way.  A 2-D copy from
 //  pageable memory cost 90 us of host time at N = 130, a pageable copy per small array 8 us each.)
@@ -250,6 +245,7 @@ extern "C" int ovp_cov_upload(ovp_ctx* c, const double* P_host, int n, int ld) {
   }
   HIPCHK(hipMemcpyAsync(c->P, ah, bytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  c->io.done();
   c->n = n;
   c->have_cov = true;
   return 0;
@@ -274,6 +270,7 @@ extern "C" int ovp_cov_download(ovp_ctx* c, double* P_host, int n, int ld) {
   }
   HIPCHK(hipMemcpyAsync(ah, c->P, bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  c->io.done();
   for (int i = 0; i < n; ++i) memcpy(P_host + (size_t)i * ld, (const double*)ah + (size_t)i * c->ld, sizeof(double) * n);
   return 0;
 }
@@ -298,6 +295,7 @@ extern "C" int ovp_cov_marginal(ovp_ctx* c, const int* ids, const int* sizes, in
   HIPCHK(ovp_launch_gather_marginal(c->P, c->ld, (const int*)ad, m, (double*)((char*)ad + o_out), c->stream));
   HIPCHK(hipMemcpyAsync((char*)ah + o_out, (char*)ad + o_out, sizeof(double) * (size_t)m * m, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  c->io.done();
   memcpy(out_host, (char*)ah + o_out, sizeof(double) * (size_t)m * m);
   return 0;
 }
@@ -326,8 +324,9 @@ extern "C" int ovp_state_upload(ovp_ctx* c, const ovp_state_tables* st) {
     if (st->clone_id[i] < 0 || st->clone_id[i] + 6 > st->n_state) return OVP_E_ARG;
   // everything goes through ONE pinned block and ONE copy, no synchronisation (seven pageable copies + a sync cost ~50 us,
   // more than the GPU time of a small update)
-  HIPCHK(hipEventSynchronize(c->ev_state));  // the previous upload has left the staging block (normally long ago)
-  char* h = (char*)c->h_state_stage;
+  int rc = 0;
+  char* h = c->state_block.begin(c->state_bytes, &rc);
+  if (!h) return rc;
   double* R = (double*)(h + c->so_R);
   double* Rf = (double*)(h + c->so_Rf);
   for (int i = 0; i < C; ++i) {
@@ -365,8 +364,7 @@ extern "C" int ovp_state_upload(ovp_ctx* c, const ovp_state_tables* st) {
       m.kind = 2;
       m.idx = 6 + k;
     }
-  HIPCHK(hipMemcpyAsync(c->state_block, c->h_state_stage, c->state_bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipEventRecord(c->ev_state, c->stream));
+  HIPCHK(c->state_block.send(c->state_bytes, c->stream, Fence::Event));
   ovp::FeatParams& fp = c->fp;
   fp.clone_R = c->clone_R;
   fp.clone_p = c->clone_p;
@@ -387,17 +385,18 @@ extern "C" int ovp_state_upload(ovp_ctx* c, const ovp_state_tables* st) {
 // (triangulation, plane fitting, plane refinement): the inputs are packed into the host block and cross the bus in ONE copy, the
 // outputs come back in one.  The first versions issued a pageable copy per array (137 copy kernels per closed-loop frame with
 // planes, a quarter of its GPU time) and, in the plane-fitting entries, a hipMalloc / hipFree pair per call.
+// The callers enqueue the copies out of and into the pinned block themselves, on c->stream, and wait for them: c->io.done() stands
+// behind that wait.
 extern "C" int ovp_io_arena(ovp_ctx* c, size_t bytes, void** host, void** dev) {
   if (!c || !host || !dev) return OVP_E_ARG;
-  if (bytes > c->io_d.capacity()) {  // (io_d grows last: its capacity stands for both halves)
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(c->io_h.reserve(bytes, bytes / 2 + 4096));
-    HIPCHK(c->io_d.reserve(bytes, bytes / 2 + 4096));
-  }
-  *host = c->io_h;
-  *dev = c->io_d;
-  return 0;
+  HIPCHK(c->io.reserve(bytes, bytes / 2 + 4096, c->stream));
+  int rc = 0;
+  *host = c->io.begin(bytes, &rc);
+  *dev = c->io.dev();
+  if (!rc) HIPCHK(c->io.fence().sent(c->stream, Fence::CallerWaits));
+  return rc;
 }
+extern "C" void ovp_io_arena_done(ovp_ctx* c) { c->io.done(); }  // (for k_planefit.hip, which does not see the context)
 
 // ---- feature batch -----------------------------------------------------------------------------
 extern "C" int ovp_batch_upload(ovp_ctx* c, const ovp_feature_batch* b) {
@@ -410,20 +409,20 @@ extern "C" int ovp_batch_upload(ovp_ctx* c, const ovp_feature_batch* b) {
   const size_t o_p = lay.take(sizeof(double) * 3 * F), o_nm = lay.take(sizeof(int) * F), o_ci = lay.take(sizeof(int) * F * M),
                o_uv = lay.take(sizeof(float) * 2 * F * M), total = lay.bytes();
   if (total > c->batch_block.capacity()) return OVP_E_CAPACITY;
-  char* d = (char*)c->batch_block;
+  char* d = c->batch_block.dev();
   c->p_FinG = (double*)(d + o_p);
   c->n_meas = (int*)(d + o_nm);
   c->clone_idx = (int*)(d + o_ci);
   c->uv = (float*)(d + o_uv);
   if (F) {
-    HIPCHK(hipEventSynchronize(c->ev_batch));
-    char* h = (char*)c->h_batch_stage;
+    int rc = 0;
+    char* h = c->batch_block.begin(total, &rc);
+    if (!h) return rc;
     memcpy(h + o_p, b->p_FinG, sizeof(double) * 3 * F);
     memcpy(h + o_nm, b->n_meas, sizeof(int) * F);
     memcpy(h + o_ci, b->clone_idx, sizeof(int) * F * M);
     memcpy(h + o_uv, b->uv, sizeof(float) * 2 * F * M);
-    HIPCHK(hipMemcpyAsync(c->batch_block, c->h_batch_stage, total, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->ev_batch, c->stream));
+    HIPCHK(c->batch_block.send(total, c->stream, Fence::Event));
   }
   c->h_n_meas.assign(b->n_meas, b->n_meas + F);
   c->h_nmeas.assign(b->n_meas, b->n_meas + F);
@@ -518,6 +517,7 @@ extern "C" int ovp_cov_propagate(ovp_ctx* c, int new_start, int phi_size, const 
                                         c->flags + 1, ch.word_dev(), seq, c->stream));
     const int rw = ch.wait(c->stream);
     if (rw) return rw;
+    c->io.done();
     const int neg = (int)ch.aux();
     if (neg_diag) *neg_diag = neg;
     return neg ? OVP_E_NEGDIAG : 0;
@@ -555,19 +555,13 @@ extern "C" int ovp_cov_marginalize(ovp_ctx* c, int id, int size) {
 // ---- zero-velocity update (k_zupt.hip) ------------------------------------------------------------
 namespace {
 
-// The entry's own buffers, made on first use and freed with the context.  Every call waits for its result, so the staging block
-// is free again when the next one fills it.
+// The entry's own buffers, made on first use and freed with the context.
 struct Zupt {
-  PinnedBuf<void> hstage;
-  DevBuf<void> dstage;
+  Staged stage;  // [parameters | readings]
   DevBuf<double> work, Y, res;
   DevBuf<unsigned> ticket;
-  size_t o_rd = 0, stage_bytes = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // time_kernels: around the three kernels
-  ~Zupt() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  size_t o_rd = 0;
+  OvpEvent ev[4];  // time_kernels: around the three kernels
 };
 
 int zupt_of(ovp_ctx* c, Zupt** out) {
@@ -576,9 +570,7 @@ int zupt_of(ovp_ctx* c, Zupt** out) {
     StageLayout lay;
     lay.take(sizeof(ovp::ZuptParams));
     d->o_rd = lay.take(sizeof(double) * 7 * (size_t)OVP_ZUPT_MAX_READINGS);
-    d->stage_bytes = lay.bytes();
-    HIPCHK(d->hstage.alloc(d->stage_bytes));
-    HIPCHK(d->dstage.alloc(d->stage_bytes));
+    HIPCHK(d->stage.alloc(lay.bytes()));
     HIPCHK(d->work.alloc(OVP_ZW_DOUBLES));
     HIPCHK(d->Y.alloc(6 * (size_t)c->n_max + 8));
     HIPCHK(d->res.alloc(OVP_ZUPT_RES_HEAD + (size_t)c->n_max));
@@ -605,10 +597,13 @@ extern "C" int ovp_zupt_update(ovp_ctx* c, const ovp_zupt_in* in, double* dx_hos
   HIPCHK(hipSetDevice(c->device));
   Zupt* d = nullptr;
   if (const int rc = zupt_of(c, &d)) return rc;
-  if (in->time_kernels && !d->ev[0])
-    for (hipEvent_t& e : d->ev) HIPCHK(hipEventCreate(&e));
+  if (in->time_kernels)
+    for (OvpEvent& e : d->ev) HIPCHK(e.create());
   // ---- one staged block [parameters | readings], one copy ----
-  char* h = (char*)d->hstage.get();
+  const size_t bytes = d->o_rd + sizeof(double) * 7 * (size_t)nr;
+  int rc = 0;
+  char* h = d->stage.begin(bytes, &rc);
+  if (!h) return rc;
   ovp::ZuptParams zp;
   memset(&zp, 0, sizeof(zp));
   const double* Rv = in->R_GtoI;
@@ -633,18 +628,19 @@ extern "C" int ovp_zupt_update(ovp_ctx* c, const ovp_zupt_in* in, double* dx_hos
   zp.disparity_passed = in->disparity_passed != 0;
   memcpy(h, &zp, sizeof(zp));
   memcpy(h + d->o_rd, in->readings, sizeof(double) * 7 * (size_t)nr);
-  const size_t bytes = d->o_rd + sizeof(double) * 7 * (size_t)nr;
   hipStream_t s = c->stream;
-  char* dv = (char*)d->dstage.get();
-  HIPCHK(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, s));
+  const char* dv = d->stage.dev();
+  HIPCHK(d->stage.send(bytes, s, Fence::CallerWaits));
   // ---- one enqueue, one wait: the verdict and dx come back through the result mailbox's channel 2 ----
   SeqChannel& ch = c->h_res_block.channel(2);
   const unsigned seq = ch.arm();
   const double* hres = (const double*)((const char*)c->h_res_block.payload() + c->zupt_res_off);
+  hipEvent_t ev[4] = {d->ev[0], d->ev[1], d->ev[2], d->ev[3]};
   HIPCHK(ovp_launch_zupt(c->P, c->ld, n, in->imu_id, (const ovp::ZuptParams*)dv, (const double*)(dv + d->o_rd), d->work, d->Y, d->res,
-                         d->ticket, c->h_res_block.dev(hres), ch.word_dev(), seq, in->time_kernels ? d->ev : nullptr, s));
+                         d->ticket, c->h_res_block.dev(hres), ch.word_dev(), seq, in->time_kernels ? ev : nullptr, s));
   const int rw = ch.wait(s);
   if (rw) return rw;
+  d->stage.done();
   const bool acc = hres[0] != 0.0, neg = acc && hres[3] != 0.0, notspd = hres[4] != 0.0;
   if (acc) drop_kept_factor(c);  // (the covariance was written: a kept factor no longer belongs to it; a rejected call keeps it)
   memset(out, 0, sizeof(*out));
@@ -672,19 +668,13 @@ extern "C" int ovp_zupt_update(ovp_ctx* c, const ovp_zupt_in* in, double* dx_hos
 // ---- propagate and clone (k_propagate.hip) ---------------------------------------------------------
 namespace {
 
-// The entry's own buffers, made on first use and freed with the context.  Every call waits for its result, so the staging block
-// is free again when the next one fills it.
+// The entry's own buffers, made on first use and freed with the context.
 struct Prop {
-  PinnedBuf<void> hstage;
-  DevBuf<void> dstage;
+  Staged stage;  // [parameters | readings]
   DevBuf<double> res;
   Mailbox hres;  // payload: the result block, channel 0
-  size_t o_rd = 0, stage_bytes = 0;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // time_kernels: around the four steps
-  ~Prop() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  size_t o_rd = 0;
+  OvpEvent ev[5];  // time_kernels: around the four steps
 };
 
 int prop_of(ovp_ctx* c, Prop** out) {
@@ -693,9 +683,7 @@ int prop_of(ovp_ctx* c, Prop** out) {
     StageLayout lay;
     lay.take(sizeof(ovp::PropParams));
     d->o_rd = lay.take(sizeof(double) * 7 * (size_t)OVP_PROP_MAX_READINGS);
-    d->stage_bytes = lay.bytes();
-    HIPCHK(d->hstage.alloc(d->stage_bytes));
-    HIPCHK(d->dstage.alloc(d->stage_bytes));
+    HIPCHK(d->stage.alloc(lay.bytes()));
     HIPCHK(d->res.alloc(OVP_PR_DOUBLES));
     HIPCHK(d->hres.alloc(sizeof(double) * OVP_PR_DOUBLES));
     c->prop = d;
@@ -723,11 +711,14 @@ extern "C" int ovp_propagate_and_clone(ovp_ctx* c, const ovp_propagate_in* in, o
   HIPCHK(hipSetDevice(c->device));
   Prop* d = nullptr;
   if (const int rc = prop_of(c, &d)) return rc;
-  if (in->time_kernels && !d->ev[0])
-    for (hipEvent_t& e : d->ev) HIPCHK(hipEventCreate(&e));
+  if (in->time_kernels)
+    for (OvpEvent& e : d->ev) HIPCHK(e.create());
   drop_kept_factor(c);  // (writes the covariance: a kept factor no longer belongs to it)
   // ---- one staged block [parameters | readings], one copy ----
-  char* h = (char*)d->hstage.get();
+  const size_t bytes = d->o_rd + sizeof(double) * 7 * (size_t)nr;
+  int rc = 0;
+  char* h = d->stage.begin(bytes, &rc);
+  if (!h) return rc;
   ovp::PropParams pp;
   memset(&pp, 0, sizeof(pp));
   memcpy(pp.q, in->q, sizeof(pp.q));
@@ -749,15 +740,14 @@ extern "C" int ovp_propagate_and_clone(ovp_ctx* c, const ovp_propagate_in* in, o
   pp.do_fej = in->do_fej != 0;
   memcpy(h, &pp, sizeof(pp));
   if (nr > 0) memcpy(h + d->o_rd, in->readings, sizeof(double) * 7 * (size_t)nr);
-  const size_t bytes = d->o_rd + sizeof(double) * 7 * (size_t)nr;
   hipStream_t s = c->stream;
-  char* dv = (char*)d->dstage.get();
-  HIPCHK(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, s));
+  const char* dv = d->stage.dev();
+  HIPCHK(d->stage.send(bytes, s, Fence::CallerWaits));
   HIPCHK(hipMemsetAsync(c->flags + 1, 0, sizeof(int), s));
   // ---- one enqueue, one wait: integration -> EKFPropagation -> clone and time offset -> the result block ----
   SeqChannel& ch = d->hres.channel(0);
   const unsigned seq = ch.arm();
-  hipEvent_t* ev = in->time_kernels ? d->ev : nullptr;
+  const OvpEvent* ev = in->time_kernels ? d->ev : nullptr;
   double* res = d->res;
   memset(out, 0, sizeof(*out));
   out->clone_id = -1;
@@ -776,6 +766,7 @@ extern "C" int ovp_propagate_and_clone(ovp_ctx* c, const ovp_propagate_in* in, o
   if (ev) HIPCHK(hipEventRecord(ev[4], s));
   const int rw = ch.wait(s);
   if (rw) return rw;
+  d->stage.done();
   const double* hr = (const double*)d->hres.payload();
   memcpy(out->q, hr + OVP_PR_Q, sizeof(out->q));
   memcpy(out->p, hr + OVP_PR_P, sizeof(out->p));
@@ -861,8 +852,9 @@ extern "C" int ovp_cov_initialize(ovp_ctx* c, const double* Hx_init, const doubl
   const size_t res_doubles = 4 + (size_t)c->n_max + 8;
   int rc = plane2_buffers(c, bytes, res_doubles * sizeof(double));  // the plane loop's pinned staging and result blocks
   if (rc) return rc;
-  double* h = (double*)c->pl_hstage;
-  double* d = (double*)c->pl_dstage;
+  double* h = (double*)c->pl_stage.begin(bytes, &rc);
+  if (!h) return rc;
+  const double* d = (const double*)c->pl_stage.dev();
   for (int a = 0; a < cols; ++a) {
     double* row = h + oHt + (size_t)a * m;
     for (int i = 0; i < k; ++i) row[i] = Hx_init[(size_t)a * k + i];
@@ -883,7 +875,7 @@ extern "C" int ovp_cov_initialize(ovp_ctx* c, const double* Hx_init, const doubl
   double* dLi = dM + (size_t)n2 * m;
   double* dy = dLi + (size_t)rup * rup;
   if ((size_t)(dy + rup + 8 - c->smallbuf) > c->smallbuf.capacity()) return OVP_E_CAPACITY;
-  HIPCHK(hipMemcpyAsync(c->pl_dstage, c->pl_hstage, bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(c->pl_stage.send(bytes, s, Fence::CallerWaits));
   HIPCHK(ovp_launch_init_m(c->P, ld, n, did, cols, d + oHt, m, dM, s));
   HIPCHK(ovp_launch_init_core(c->P, ld, n, did, cols, d + oHt, k, rup, dM, d + oHi, d + oRk, d + oRes, r_iso > 0.0 ? r_iso : 1.0,
                               chi2_threshold, dLi, dy, dres, s));
@@ -895,6 +887,7 @@ extern "C" int ovp_cov_initialize(ovp_ctx* c, const double* Hx_init, const doubl
   {
     const int rf = ovp_fetch_to_hres(c, dres, sizeof(double) * (upd ? 4 + (size_t)n2 : 4), s);
     if (rf) return rf;
+    c->pl_stage.done();
   }
   const bool ok = hres[1] > 0.5;
   if (accepted) *accepted = ok ? 1 : 0;
@@ -931,9 +924,10 @@ extern "C" long ovp_debug_read(ovp_ctx* c, const char* name, void* host, long ma
   else if (!strcmp(name, "bn")) { src = c->pl_bn; bytes = (size_t)c->n_max * sizeof(double); if (!src) return OVP_E_STATE; }
   // camera tables on the device: camera 0's of ovp_state_upload / every camera's of ovp_cameras_upload ([k][20], layout of `cal`)
   // capacity of the pinned result block the small fetches share (ovp_fetch_to_hres), one size_t
-  else if (!strcmp(name, "pl_hres_cap")) {
+  // ... and of the staging block the per-call tables share (pl_stage)
+  else if (!strcmp(name, "pl_hres_cap") || !strcmp(name, "pl_stage_cap")) {
     if ((size_t)max_bytes < sizeof(size_t)) return OVP_E_ARG;
-    const size_t cap = c->pl_hres.capacity();
+    const size_t cap = name[3] == 'h' ? c->pl_hres.capacity() : c->pl_stage.capacity();
     memcpy(host, &cap, sizeof(size_t));
     return (long)sizeof(size_t);
   }
@@ -945,8 +939,8 @@ extern "C" long ovp_debug_read(ovp_ctx* c, const char* name, void* host, long ma
   else if (!strcmp(name, "gen_cal")) { src = c->gen_cal; bytes = (size_t)20 * c->gen_ncams * sizeof(double); if (!src) return OVP_E_STATE; }
   // plane table of the last ovp_slam_delayed_init_planes ([n_planes][8]: cp | cp_fej | id | -), valid until the next call that stages
   else if (!strcmp(name, "dinit_planes")) {
-    if (!c->pl_dstage || c->dinit_nplanes < 1) return OVP_E_STATE;
-    src = (const char*)c->pl_dstage + c->dinit_pltab_off;
+    if (!c->pl_stage.dev() || c->dinit_nplanes < 1) return OVP_E_STATE;
+    src = c->pl_stage.dev() + c->dinit_pltab_off;
     bytes = (size_t)8 * c->dinit_nplanes * sizeof(double);
   }
   else if (!strcmp(name, "chi2")) {
@@ -959,9 +953,9 @@ extern "C" long ovp_debug_read(ovp_ctx* c, const char* name, void* host, long ma
   else if (!strncmp(name, "bench_chol", 10)) {
     // diagnostics: average time of k_tilechol on the resident covariance; name = "bench_chol<skipmask>"
     ovp_dbg_tilechol_skip = atoi(name + 10);
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0);
-    hipEventCreate(&e1);
+    OvpEvent e0, e1;
+    e0.create();
+    e1.create();
     for (int i = 0; i < 3; ++i) ovp_launch_tilechol(c->P, c->L, c->Dinv, c->Ltp, c->n, c->ld, c->flags + 3, 0, c->stream);
     hipEventRecord(e0, c->stream);
     for (int i = 0; i < 20; ++i) ovp_launch_tilechol(c->P, c->L, c->Dinv, c->Ltp, c->n, c->ld, c->flags + 3, 0, c->stream);
@@ -971,8 +965,6 @@ extern "C" long ovp_debug_read(ovp_ctx* c, const char* name, void* host, long ma
     hipEventElapsedTime(&ms, e0, e1);
     ovp_dbg_tilechol_skip = 0;
     *(double*)host = ms / 20.0;
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
     return 8;
   }
   else if (!strcmp(name, "cycles_on")) return c->dbg_cycles.alloc((size_t)c->f_max * 10) != hipSuccess ? OVP_E_STATE : 0;

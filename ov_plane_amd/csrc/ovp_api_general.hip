@@ -161,6 +161,7 @@ extern "C" int ovp_msckf_general_features(ovp_ctx* c, const ovp_update_opts* o, 
   HIPCHK(ovp_launch_gen_pair(&g, (double*)(sd + s_A), (double*)(sd + s_b), c->stream));
   HIPCHK(hipMemcpyAsync(h + in_bytes, sd, out_bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  c->io.done();
   const char* r = h + in_bytes;
   const double* x2 = (const double*)(r + s_chi2);
   const unsigned char* acc = (const unsigned char*)(r + s_acc);
@@ -234,6 +235,7 @@ extern "C" int ovp_triangulate_general(ovp_ctx* c, const ovp_triang_opts* o, con
   HIPCHK(ovp_launch_triangulate_gen(&tp, (const int*)(d + o_cam), c->stream));
   HIPCHK(hipMemcpyAsync(h + o_p, d + o_p, total - o_p, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  c->io.done();
   if (p_FinG_out) memcpy(p_FinG_out, h + o_p, sizeof(double) * 3 * F);
   memcpy(ok, h + o_ok, F);
   return 0;
@@ -388,6 +390,7 @@ extern "C" int ovp_plane_fit_refine(ovp_ctx* c, const ovp_general_batch* b, cons
   const size_t out_end = j.refine ? total : o_cfs;  // (fit only: nothing behind the RANSAC's results was written)
   HIPCHK(hipMemcpyAsync(h + o_pose, d + o_pose, out_end - o_pose, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  c->io.done();
   if (out->poses) memcpy(out->poses, h + o_pose, sizeof(double) * 12 * NC * NK);
   const double* r_abcd = (const double*)(h + o_abcd);
   const unsigned char *r_inl = (const unsigned char*)(h + o_rinl), *r_ok = (const unsigned char*)(h + o_rok);

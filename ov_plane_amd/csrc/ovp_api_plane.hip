@@ -5,7 +5,7 @@
 #include "ovp_ctx.h"
 #include "k_plane_init2.h"
 
-// the loop's per-plane results and the buffers of a plane's front end (the per-call tables travel in c->pl_dstage, plane_stage_upload)
+// the loop's per-plane results and the buffers of a plane's front end (the per-call tables travel in c->pl_stage, plane_stage_upload)
 static int plane_buffers(ovp_ctx* c, int NP) {
   const size_t ld = (size_t)c->ld, np = (size_t)NP, n_max = (size_t)c->n_max;
   HIPCHK(c->pl_res.reserve(4 * np, 4 * 8));  // NP + 8 planes
@@ -128,11 +128,7 @@ int plane2_buffers(ovp_ctx* c, size_t stage_bytes, size_t res_bytes) {
     HIPCHK(c->pl_xflag.alloc(64));
     HIPCHK(hipMemset(c->pl_xflag, 0, sizeof(unsigned) * 64));
   }
-  if (stage_bytes > c->pl_dstage.capacity()) {  // (pl_dstage grows last: its capacity stands for both halves)
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(c->pl_hstage.reserve(stage_bytes, 4096));
-    HIPCHK(c->pl_dstage.reserve(stage_bytes, 4096));
-  }
+  HIPCHK(c->pl_stage.reserve(stage_bytes, 4096, c->stream));
   // (res_bytes is the callers' size of the whole result block, the line of the sequence word included)
   const size_t payload = res_bytes > Mailbox::LINE ? res_bytes - Mailbox::LINE : 0;
   if (payload > c->pl_hres.payload_capacity()) {
@@ -160,10 +156,9 @@ static int sub_tables_upload(ovp_ctx* c, const ovp_update_opts* o, const std::ve
   const size_t tab_bytes = sizeof(int) * (size_t)(c->c_max + 16) + sizeof(ovp::ColMap) * (size_t)c->n_max;
   const size_t blk_bytes = o_tab + tab_bytes;
   HIPCHK(c->pl_sub_tab.alloc(blk_bytes));
-  HIPCHK(c->pl_sub_htab.alloc(blk_bytes));
-  if (c->ev_subtab) HIPCHK(hipEventSynchronize(c->ev_subtab));  // the pinned block fed the copy of the previous call (long done)
-  else HIPCHK(hipEventCreateWithFlags(&c->ev_subtab, hipEventDisableTiming));
-  char* hb = (char*)c->pl_sub_htab;
+  int rc = 0;
+  char* hb = c->pl_sub_tab.begin(blk_bytes, &rc);
+  if (!hb) return rc;
   memset(hb, 0, blk_bytes);
   int* h_ids = (int*)(hb + o_ids);
   int* h_inv = (int*)(hb + o_inv);
@@ -193,12 +188,12 @@ static int sub_tables_upload(ovp_ctx* c, const ovp_update_opts* o, const std::ve
       t_cm[t->intr_sub + k].kind = 2;
       t_cm[t->intr_sub + k].idx = 6 + k;
     }
-  HIPCHK(hipMemcpyAsync(c->pl_sub_tab, hb, blk_bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(hipEventRecord(c->ev_subtab, s));
-  t->d_ids = (const int*)((char*)c->pl_sub_tab + o_ids);
-  t->d_inv = (const int*)((char*)c->pl_sub_tab + o_inv);
-  t->d_clone_id = (int*)((char*)c->pl_sub_tab + o_tab);
-  t->d_colmap = (ovp::ColMap*)((char*)c->pl_sub_tab + o_tab + sizeof(int) * (size_t)(c->c_max + 16));
+  HIPCHK(c->pl_sub_tab.send(blk_bytes, s, Fence::Event));
+  char* db = c->pl_sub_tab.dev();
+  t->d_ids = (const int*)(db + o_ids);
+  t->d_inv = (const int*)(db + o_inv);
+  t->d_clone_id = (int*)(db + o_tab);
+  t->d_colmap = (ovp::ColMap*)(db + o_tab + sizeof(int) * (size_t)(c->c_max + 16));
   return 0;
 }
 // the context's view of the state while a selection stands in for it, and back
@@ -235,12 +230,10 @@ static void sub_leave(ovp_ctx* c, const SubSaved& sv) {
   c->h_clone_id = sv.h_clone_id;
 }
 
-static hipError_t ensure_events(std::vector<hipEvent_t>& ev, size_t count) {  // the kernel timers' events, created on first use
-  while (ev.size() < count) {
-    hipEvent_t e;
-    if (hipError_t err = hipEventCreate(&e)) return err;
-    ev.push_back(e);
-  }
+static hipError_t ensure_events(std::vector<OvpEvent>& ev, size_t count) {  // the kernel timers' events, created on first use
+  if (ev.size() < count) ev.resize(count);
+  for (OvpEvent& e : ev)
+    if (hipError_t err = e.create()) return err;
   return hipSuccess;
 }
 
@@ -701,7 +694,7 @@ static int plane_group(const ovp_ctx* c, const ovp_update_opts* o, const ovp_pla
 }
 
 // ---- staging: ints [featlist | sid NP | perms NJ*n | slam_plane | slam_id], doubles [cp | cp_fej | slam_p | slam_p_fej] ----
-struct PlaneStage {  // device addresses of the tables inside c->pl_dstage
+struct PlaneStage {  // device addresses of the tables inside c->pl_stage
   const int *feat, *sid, *perm, *slam_plane, *slam_id;
   double *cp, *cp_fej, *slam_p, *slam_p_fej;
 };
@@ -711,12 +704,14 @@ static int plane_stage_upload(ovp_ctx* c, const ovp_plane_batch* pb, const Plane
   const size_t int_bytes = ((n_int * sizeof(int) + 15) / 16) * 16;
   const size_t n_dbl = 6 * (size_t)NP + 6 * (size_t)n_slam;
   const size_t stage_bytes = int_bytes + n_dbl * sizeof(double);
-  const int rc = plane2_buffers(c, stage_bytes, pre.res_bytes);  // (grows the staging block when this frame needs more)
+  int rc = plane2_buffers(c, stage_bytes, pre.res_bytes);  // (grows the staging block when this frame needs more)
   if (rc) return rc;
-  int* hi = (int*)c->pl_hstage;
-  double* hd = (double*)((char*)c->pl_hstage + int_bytes);
-  int* di = (int*)c->pl_dstage;
-  double* dd = (double*)((char*)c->pl_dstage + int_bytes);
+  char* h = c->pl_stage.begin(stage_bytes, &rc);
+  if (!h) return rc;
+  int* hi = (int*)h;
+  double* hd = (double*)(h + int_bytes);
+  int* di = (int*)c->pl_stage.dev();
+  double* dd = (double*)(c->pl_stage.dev() + int_bytes);
   size_t io = 0;
   st->feat = di + io;
   memcpy(hi + io, g.featlist.data(), sizeof(int) * g.featlist.size());
@@ -739,7 +734,7 @@ static int plane_stage_upload(ovp_ctx* c, const ovp_plane_batch* pb, const Plane
     memcpy(hd + 6 * NP, pb->slam_p, sizeof(double) * 3 * n_slam);
     memcpy(hd + 6 * NP + 3 * n_slam, pb->slam_p_fej, sizeof(double) * 3 * n_slam);
   }
-  HIPCHK(hipMemcpyAsync(c->pl_dstage, c->pl_hstage, stage_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c->pl_stage.send(stage_bytes, c->stream, Fence::CallerWaits));
   st->cp = dd;
   st->cp_fej = dd + 3 * NP;
   st->slam_p = dd + 6 * NP;
@@ -1318,6 +1313,8 @@ static int plane_loop(ovp_ctx* c, const ovp_update_opts* o_in, const ovp_plane_b
   const double t_enq = host_now_ms();
   rc = c->pl_hres.channel(0).wait(s);
   if (rc) return rc;
+  c->pl_stage.done();
+  c->io.done();  // (plane_gen_upload's tables)
   memcpy(c->h_flags, blk.flags, sizeof(int) * 4);
   plane_account(c, v.t_entry, pre.t_first, t_enq, NJ);
   bool retry_psd = false;

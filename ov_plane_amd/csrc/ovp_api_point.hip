@@ -699,8 +699,9 @@ extern "C" int ovp_ekf_update(ovp_ctx* c, const double* H_host, int rows, int co
     const size_t res_doubles = 4 + (size_t)c->n_max + 8;
     int rc = plane2_buffers(c, bytes, res_doubles * sizeof(double));
     if (rc) return rc;
-    double* h = (double*)c->pl_hstage;
-    double* d = (double*)c->pl_dstage;
+    double* h = (double*)c->pl_stage.begin(bytes, &rc);
+    if (!h) return rc;
+    const double* d = (const double*)c->pl_stage.dev();
     for (int a = 0; a < cols; ++a) memcpy(h + oHt + (size_t)a * rows, H_host + (size_t)a * ld, sizeof(double) * rows);  // = H^T row-major
     memcpy(h + oRes, res_host, sizeof(double) * rows);
     memcpy(h + oId, col_ids, sizeof(int) * cols);
@@ -710,7 +711,7 @@ extern "C" int ovp_ekf_update(ovp_ctx* c, const double* H_host, int rows, int co
     double* dLi = dM + (size_t)n * rows;
     double* dy = dLi + (size_t)rows * rows;
     if ((size_t)(dy + rows + 8 - c->smallbuf) > c->smallbuf.capacity()) return OVP_E_CAPACITY;
-    HIPCHK(hipMemcpyAsync(c->pl_dstage, c->pl_hstage, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c->pl_stage.send(bytes, s, Fence::CallerWaits));
     HIPCHK(ovp_launch_init_m(c->P, c->ld, n, did, cols, d + oHt, rows, dM, s));
     HIPCHK(ovp_launch_init_core(c->P, c->ld, n, did, cols, d + oHt, 0, rows, dM, d + oRes /* unused: k = 0 */, d + oRes, d + oRes, 1.0,
                                 1e300, dLi, dy, dres, s));
@@ -719,6 +720,7 @@ extern "C" int ovp_ekf_update(ovp_ctx* c, const double* H_host, int rows, int co
     {
       const int rf = ovp_fetch_to_hres(c, dres, sizeof(double) * (4 + (size_t)n), s);
       if (rf) return rf;
+      c->pl_stage.done();
     }
     if (info) {
       memset(info, 0, sizeof(*info));

@@ -52,6 +52,7 @@ extern "C" int ovp_triangulate(ovp_ctx* c, const ovp_triang_opts* o, const float
   HIPCHK(hipMemcpyAsync((char*)ah + o_p, c->p_FinG, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync((char*)ah + o_ok, (char*)ad + o_ok, F, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  c->io.done();
   if (p_FinG_out) memcpy(p_FinG_out, (char*)ah + o_p, sizeof(double) * 3 * F);
   memcpy(ok, (char*)ah + o_ok, F);
   return 0;
@@ -166,14 +167,16 @@ static void slam_stage_fill(const SlamUpdatePlan& p, const ovp_slam_batch* b, co
 // per-landmark results and of the blocks that do not fit LDS
 static int slam_stage_upload(ovp_ctx* c, const SlamUpdatePlan& p, const ovp_slam_batch* b, const int* cam_idx, SlamStage* st) {
   *st = slam_stage_layout(p, c->n, slam_res_doubles(c));
-  const int rc = plane2_buffers(c, st->bytes, st->res_doubles * sizeof(double) + st->lres_bytes + 64);
+  int rc = plane2_buffers(c, st->bytes, st->res_doubles * sizeof(double) + st->lres_bytes + 64);
   if (rc) return rc;
-  slam_stage_fill(p, b, cam_idx, *st, (char*)c->pl_hstage);
+  char* h = c->pl_stage.begin(st->bytes, &rc);
+  if (!h) return rc;
+  slam_stage_fill(p, b, cam_idx, *st, h);
   HIPCHK(c->Hd.reserve((size_t)p.gcols * p.m_total, 64));
   HIPCHK(c->resd.reserve((size_t)p.m_total, 64));
   HIPCHK(c->slam_res.reserve(st->lres_bytes, 4096));
   if (!p.h_in_lds) HIPCHK(c->slam_hscr.reserve((size_t)p.L * p.rows_max * p.cols_max, 64));
-  HIPCHK(hipMemcpyAsync(c->pl_dstage, c->pl_hstage, st->bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c->pl_stage.send(st->bytes, c->stream, Fence::CallerWaits));
   return 0;
 }
 
@@ -193,7 +196,7 @@ static SlamScratch slam_scratch(const ovp_ctx* c, const SlamUpdatePlan& p, const
 
 static ovp::SlamParams slam_params(const ovp_ctx* c, const ovp_update_opts* o, const SlamUpdatePlan& p, const SlamStage& st,
                                    const SlamScratch& k) {
-  const char* d = (const char*)c->pl_dstage;
+  const char* d = c->pl_stage.dev();
   ovp::SlamParams sp;
   memset(&sp, 0, sizeof(sp));
   sp.fp = c->fp;
@@ -247,7 +250,7 @@ static ovp::SlamParams slam_params(const ovp_ctx* c, const ovp_update_opts* o, c
 }
 
 static ovp::SlamGenParams slam_gen_params(const ovp_ctx* c, const ovp_update_opts* o, const ovp::SlamParams& sp, const SlamStage& st) {
-  const char* d = (const char*)c->pl_dstage;
+  const char* d = c->pl_stage.dev();
   ovp::SlamGenParams gp;
   memset(&gp, 0, sizeof(gp));
   gp.sp = sp;
@@ -292,12 +295,13 @@ static int slam_tail_sform(ovp_ctx* c, const SlamUpdatePlan& p, const ovp_slam_b
                            const SlamOut& out) {
   hipStream_t s = c->stream;
   const int n = c->n, rows = p.m_total;
-  const int* dgid = (const int*)((const char*)c->pl_dstage + st.gi);
+  const int* dgid = (const int*)(c->pl_stage.dev() + st.gi);
   HIPCHK(ovp_launch_init_core(c->P, c->ld, n, dgid, p.gcols, c->Hd, 0, rows, k.M, c->resd /* unused: k = 0 */, c->resd, c->resd, 1.0,
                               1e300, k.Li, k.y, k.res, s));
   HIPCHK(ovp_launch_init_update(c->P, c->P_tmp, c->ld, n, k.M, rows, 0, rows, k.Li, k.y, k.res, k.res + 4, s));
   const int rf = ovp_fetch_to_hres(c, k.res, st.res_doubles * sizeof(double) + st.lres_bytes, s);
   if (rf) return rf;
+  c->pl_stage.done();
   const double* hres = (const double*)c->pl_hres.payload();
   slam_finish_landmarks(p, b, (const char*)(hres + st.res_doubles), st.status, out);
   if (out.info) {
@@ -314,7 +318,7 @@ static int slam_tail_sform(ovp_ctx* c, const SlamUpdatePlan& p, const ovp_slam_b
 static int slam_tail_info(ovp_ctx* c, const SlamUpdatePlan& p, const ovp_slam_batch* b, const SlamStage& st, const SlamOut& out) {
   hipStream_t s = c->stream;
   const int n = c->n, gcols = p.gcols, m_total = p.m_total;
-  const int* dgid = (const int*)((const char*)c->pl_dstage + st.gi);
+  const int* dgid = (const int*)(c->pl_stage.dev() + st.gi);
   char* hl = (char*)c->pl_hres.payload() + st.res_doubles * sizeof(double);
   HIPCHK(c->Acc.alloc((size_t)c->n_max * c->n_max));
   HIPCHK(c->bcc.alloc((size_t)c->n_max));
@@ -335,6 +339,7 @@ static int slam_tail_info(ovp_ctx* c, const SlamUpdatePlan& p, const ovp_slam_ba
   HIPCHK(hipMemcpyAsync(c->h_flags, c->flags, sizeof(int) * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(hl, c->slam_res, st.lres_bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  c->pl_stage.done();
   slam_finish_landmarks(p, b, hl, st.status, out);
   if (c->h_flags[0]) {  // positive semi-definite prior: S-form instead of the factor of P
     const int rs = ekf_sform(c);
@@ -448,10 +453,12 @@ static int dinit_stage_upload(ovp_ctx* c, const DinitPlan& p, const DinitCands& 
                               DinitScratch* k) {
   const size_t NA = p.att.size(), rows_max = (size_t)p.rows_max, n_end = (size_t)p.n0 + 3 * p.L;
   *st = dinit_stage_layout(p, slam_res_doubles(c));
-  const int rc = plane2_buffers(c, st->bytes, sizeof(double) * st->res_doubles * NA + 64);
+  int rc = plane2_buffers(c, st->bytes, sizeof(double) * st->res_doubles * NA + 64);
   if (rc) return rc;
-  dinit_stage_fill(p, b, pl, *st, (char*)c->pl_hstage);
-  if (p.with_planes) {  // the plane table of the last call inside pl_dstage (ovp_debug_read "dinit_planes")
+  char* h = c->pl_stage.begin(st->bytes, &rc);
+  if (!h) return rc;
+  dinit_stage_fill(p, b, pl, *st, h);
+  if (p.with_planes) {  // the plane table of the last call inside pl_stage (ovp_debug_read "dinit_planes")
     c->dinit_pltab_off = st->pt;
     c->dinit_nplanes = p.n_pl;
   }
@@ -466,14 +473,14 @@ static int dinit_stage_upload(ovp_ctx* c, const DinitPlan& p, const DinitCands& 
   k->Hinv = k->y + rows_max + 8;
   k->Rk = k->Hinv + 12;
   k->resid = k->Rk + 12;
-  HIPCHK(hipMemcpyAsync(c->pl_dstage, c->pl_hstage, st->bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c->pl_stage.send(st->bytes, c->stream, Fence::CallerWaits));
   return 0;
 }
 
 // the three parameter structs of a call: everything but the per-attempt fields (dinit_enqueue_attempt)
 static ovp::DinitParams dinit_params(const ovp_ctx* c, const ovp_update_opts* o, const DinitPlan& p, const DinitStage& st,
                                      const DinitScratch& k) {
-  const char* d = (const char*)c->pl_dstage;
+  const char* d = c->pl_stage.dev();
   ovp::DinitParams dp;
   memset(&dp, 0, sizeof(dp));
   dp.fp = c->fp;
@@ -504,14 +511,14 @@ static ovp::DinitGenParams dinit_gen_params(const ovp_ctx* c, const ovp_update_o
   memset(&gp, 0, sizeof(gp));
   CalCols(c, o).fill_cameras_and_columns(gp);
   gp.n_cams = c->gen_ncams;
-  gp.cam_idx = (const int*)((const char*)c->pl_dstage + st.cam);
+  gp.cam_idx = (const int*)(c->pl_stage.dev() + st.cam);
   return gp;
 }
 
 static ovp::DinitPlaneParams dinit_plane_params(const ovp_ctx* c, const ovp_update_opts* o, const DinitPlan& p, const DinitStage& st) {
   ovp::DinitPlaneParams pp;  // (with planes only)
   memset(&pp, 0, sizeof(pp));
-  pp.tab = (double*)((char*)c->pl_dstage + st.pt);
+  pp.tab = (double*)(c->pl_stage.dev() + st.pt);
   pp.n_planes = p.n_pl;
   pp.white_c = 1.0 / o->sigma_constraint;
   return pp;
@@ -533,7 +540,7 @@ static int dinit_enqueue_attempt(ovp_ctx* c, const ovp_update_opts* o, const Din
                                  int a, DinitCall& k) {
   hipStream_t s = c->stream;
   const DinitAttempt& t = p.att[a];
-  const char* d = (const char*)c->pl_dstage;
+  const char* d = c->pl_stage.dev();
   const int n = p.n0 + 3 * t.l, rup = t.rows - 3;
   const bool second = t.skip_blk >= 0;  // attempt B: attempt A has committed the previous candidate
   const double* skip = second ? b.res0 + st.res_doubles * t.skip_blk : nullptr;
@@ -546,7 +553,7 @@ static int dinit_enqueue_attempt(ovp_ctx* c, const ovp_update_opts* o, const Din
   k.dp.fp.p_FinG = (const double*)(d + (second ? st.p2 : st.p));
   k.pp.slot = t.slot;
   k.pp.skip = skip;
-  const int* hids = (const int*)((const char*)c->pl_hstage + st.id) + (size_t)a * p.cols_max;
+  const int* hids = (const int*)(c->pl_stage.host() + st.id) + (size_t)a * p.cols_max;
   if (p.gen) {
     k.gp.cols = t.cols;
     memcpy(k.gp.idg, hids, sizeof(int) * t.cols);
@@ -573,7 +580,7 @@ static int dinit_enqueue_commit(ovp_ctx* c, const DinitPlan& p, const DinitStage
   k.dp.cand = -1;
   k.dp.n = p.n0 + 3 * p.L;
   k.dp.prev_res = b.res0 + st.res_doubles * (p.att.size() - 1);
-  k.dp.fp.p_FinG = (const double*)((const char*)c->pl_dstage + st.p);
+  k.dp.fp.p_FinG = (const double*)(c->pl_stage.dev() + st.p);
   k.pp.slot = 0;
   k.pp.skip = nullptr;
   HIPCHK(dinit_launch_rows(p, k, 64, c->stream));
@@ -645,6 +652,7 @@ static int slam_delayed_init_impl(ovp_ctx* c, const ovp_update_opts* o, const Di
   if (rc) return rc;
   rc = ovp_fetch_to_hres(c, k.res0, sizeof(double) * st.res_doubles * NA, c->stream);
   if (rc) return rc;
+  c->pl_stage.done();
   c->n = plan.n0 + 3 * plan.L;
   return dinit_unpack(c, plan, (const double*)c->pl_hres.payload(), st.res_doubles, out);
 }

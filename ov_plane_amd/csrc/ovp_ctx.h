@@ -16,7 +16,9 @@
 //   k_retire.hip       a frame's retirements in one compaction, its plane merges in sequence in front of it: kernels and entry points
 //   k_zupt.hip         the zero-velocity update's gate, rows and apply kernels (entry point: ovp_zupt_update in ovp_api_ctx.hip)
 //   k_propagate.hip    the IMU integration, clone-plus-time-offset and publishing kernels of ovp_propagate_and_clone (ovp_api_ctx.hip)
-// Results reach the host through ovp_mailbox.h (Mailbox / SeqChannel; the copy-and-post kernel is k_publish.hip).
+// Results reach the host through ovp_mailbox.h (Mailbox / SeqChannel; the copy-and-post kernel is k_publish.hip); host tables reach
+// the device through ovp_staged.h (Staged: pinned block, device block and the fence that says when the host may write again), and
+// every event is an OvpEvent from the same header.
 #pragma once
 #include "ovplane_hip.h"
 
@@ -34,6 +36,7 @@
 
 #include "ovp_buf.h"
 #include "ovp_mailbox.h"
+#include "ovp_staged.h"
 #include "ovp_kernels.h"
 #include "k_chol2.h"
 #include "k_plane2.h"
@@ -125,31 +128,20 @@ static const int OVP_TILECHOL_NMAX = 288;  // register-resident factorization li
 
 static inline int round_up(int v, int m) { return ((v + m - 1) / m) * m; }
 
-// Blocks of one staging buffer, each starting on a 64-byte line: take(bytes) returns the offset of the next block, bytes() the total.
-struct StageLayout {
-  size_t o = 0;
-  static size_t al(size_t v) { return (v + 63) & ~(size_t)63; }
-  size_t take(size_t bytes) {
-    const size_t at = o;
-    o = al(o + bytes);
-    return at;
-  }
-  size_t bytes() const { return o; }
-};
-
 // ------------------------------------------------------------------------------------------------
 struct ovp_ctx {
   int device = 0;
   hipStream_t stream = nullptr, stream2 = nullptr;
   bool own_stream = false;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipEvent_t ev_t[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  OvpEvent ev_fork, ev_join;
+  OvpEvent ev_t[6];
   int n_max = 0, c_max = 0, f_max = 0;
   int n = 0, ld = 0;  // current covariance size, leading dimension of every n x n buffer
-  // Memory: every buffer the context owns is a DevBuf / PinnedBuf (ovp_buf.h) and goes with the context; a raw pointer below is a
-  // view into one of them and says into which.
+  // Memory: every buffer the context owns is a DevBuf / PinnedBuf (ovp_buf.h), a Mailbox (ovp_mailbox.h) or a Staged (ovp_staged.h:
+  // a host table's pinned and device halves) and goes with the context; a raw pointer below is a view into one of them and says
+  // into which.
   DevBuf<double> P, P_tmp;
-  // state tables: views into state_block
+  // state tables: views into state_block's device half
   double *clone_R = nullptr, *clone_p = nullptr, *clone_R_fej = nullptr, *clone_p_fej = nullptr;
   int* clone_id = nullptr;
   double* cal = nullptr;  // [20] camera extrinsics / intrinsics values
@@ -157,7 +149,7 @@ struct ovp_ctx {
   DevBuf<double> chi2_table;
   ovp::FeatParams fp;
   bool have_state = false, have_cov = false, have_batch = false;
-  // feature batch: views into batch_block
+  // feature batch: views into batch_block's device half (or into the feature database's batch, ovp_batch_bind_device)
   float* uv = nullptr;
   int *clone_idx = nullptr, *n_meas = nullptr;
   double* p_FinG = nullptr;
@@ -189,7 +181,7 @@ struct ovp_ctx {
   DevBuf<void> slam_res;           // ovp_slam_update: per-landmark [chi2 | status]
   DevBuf<double> slam_hscr;        // ... blocks that do not fit LDS
   DevBuf<double> dinit_buf;        // ovp_slam_delayed_init: result blocks + shared scratch of the candidate loop
-  size_t dinit_pltab_off = 0;      // ovp_slam_delayed_init_planes: the plane table of the last call inside pl_dstage (debug read)
+  size_t dinit_pltab_off = 0;      // ovp_slam_delayed_init_planes: the plane table of the last call inside pl_stage (debug read)
   int dinit_nplanes = 0;
   int calib_id = -1, intr_id = -1;
   DevBuf<long long> dbg_cycles;
@@ -208,15 +200,13 @@ struct ovp_ctx {
   PinnedBuf<int> h_slot{true};        // [f_max] host-mapped: row block of a feature in the compacted rec / G of a point update (-1: none)
   bool pl_used_valid = false;         // pl_used refers to the uploaded batch
   // plane loop on a sub-state (n above the tile factorization's limit): accumulated pair, u rows, remapped id tables
-  PinnedBuf<void> io_h;                          // ovp_io_arena: pinned host block + device block of the small entry points
-  DevBuf<void> io_d;
+  Staged io;                                     // ovp_io_arena: pinned host block + device block of the small entry points
   DevBuf<double> pl_xbuf, pl_xy;                 // split plane solve: exported panels, [xzz(2) | y blocks]
   DevBuf<unsigned> pl_xflag;                     // [32 step flags | 2 sync words]
   DevBuf<double> pl_Asum, pl_U;
   DevBuf<double> pl_init_keep;                   // ovp_plane_init_general: [plane][3][nk + 4] plane rows of the extended pairs of the call
   DevBuf<int> pl_init_slot;                      // ... and the numbering of its accepted planes (k_plane_init2.hip)
-  DevBuf<void> pl_sub_tab;                       // [ids | inverse | clone ids | column map] of the loop's column order
-  PinnedBuf<void> pl_sub_htab;
+  Staged pl_sub_tab;                             // [ids | inverse | clone ids | column map] of the loop's column order
   // (what tells the plane loop's routes apart is an argument of the loop, PlaneLoopView in ovp_api_plane.hip, not context state)
   DevBuf<void> pl_gen_dev;                 // device: [marks | projected rows] of one plane's general features of the running loop
   // A factor of the RESIDENT covariance left behind by the plane loop (P = V^T V, Lkeep = V^T in the state's column order): the point
@@ -231,18 +221,14 @@ struct ovp_ctx {
   int point_boost_n = 0;
   int point_nl = 0;  // > 0: chol(P) of the running point update was taken in reversed index order (CholJob::flip) and the update's
                      // T = I + L^T A L is the identity outside its leading point_nl columns
-  hipEvent_t ev_subtab = nullptr;     // behind the upload of pl_sub_htab (the pinned block is rewritten by the next call)
-  PinnedBuf<void> pl_hstage;          // pinned host / device staging of the per-call tables
-  DevBuf<void> pl_dstage;
+  Staged pl_stage;                    // the per-call tables of the plane loop, the point update's sub-state and the SLAM entries
   Mailbox pl_hres;                    // the plane results and the small fetches (ovp_fetch_to_hres): payload from byte 0, channel 0
-  // one device block + one pinned staging block each for the pose tables and for the feature batch (a single copy per upload)
-  DevBuf<void> state_block, batch_block;
-  PinnedBuf<void> h_state_stage, h_batch_stage;
+  // the pose tables and the feature batch (a single copy per upload, an event behind it: the uploads do not wait)
+  Staged state_block, batch_block;
   size_t state_bytes = 0;
   size_t so_R = 0, so_Rf = 0, so_p = 0, so_pf = 0, so_cal = 0, so_id = 0, so_cm = 0;
-  hipEvent_t ev_state = nullptr, ev_batch = nullptr;
   int pl_ktimer = 0;  // 1 = events around every k_chol2 launch and around the loop, 2 = around the loop only
-  std::vector<hipEvent_t> pl_ev, pl_ev_loop;
+  std::vector<OvpEvent> pl_ev, pl_ev_loop;
   double pl_ktime_ms = 0.0;
   int pl_klaunches = 0;
   DevBuf<int> idbuf;         // scratch ints (ids)
@@ -270,7 +256,7 @@ struct ovp_ctx {
   bool timed = false;
   // dominant-kernel timer
   bool ktimer = false;
-  hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;
+  OvpEvent ev_k0, ev_k1;
   double ktime_ms = 0.0;
   int klaunches = 0;
   bool kpending = false;
@@ -289,11 +275,7 @@ struct ovp_ctx {
   ovp_ctx() = default;
   ovp_ctx(const ovp_ctx&) = delete;
   ovp_ctx& operator=(const ovp_ctx&) = delete;
-  ~ovp_ctx() {  // the events and the streams; the buffers free themselves behind this
-    for (hipEvent_t e : {ev_fork, ev_join, ev_t[0], ev_t[1], ev_t[2], ev_t[3], ev_t[4], ev_t[5], ev_k0, ev_k1, ev_state, ev_batch, ev_subtab})
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : pl_ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : pl_ev_loop) (void)hipEventDestroy(e);
+  ~ovp_ctx() {  // the streams; the events and the buffers free themselves behind this
     if (stream2) (void)hipStreamDestroy(stream2);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
