@@ -1149,6 +1149,58 @@ void ovp_epipolar_defaults(ovp_epipolar_opts *o);
  * at once; n < OVP_EPI_MIN_POINTS returns success with a zero mask and too_few (the coordinates are still undistorted). */
 int ovp_klt_epipolar(ovp_ctx *ctx, const ovp_epipolar_opts *opts, int n, const float *pts0, const float *pts1, const uint8_t *status,
                      uint8_t *mask_out, float *uvn0, float *uvn1, ovp_epipolar_info *info);
+/* The back half of TrackPlane::feed_monocular in one device pass (track_plane/TrackPlane.cpp:510-567): the temporal KLT
+ * (:515, :1326-1330), the epipolar check (:1331-1350), the keep rule (:536-551) and database->update_feature (:553-557), which
+ * ovp_klt_track, ovp_klt_epipolar, the caller's own keep rule and ovp_featdb_append carry out as four entries with host code between
+ * them.  The kernels in front are those entries' own, unchanged, reading the device-resident points and status; k_klt_keep_append
+ * (one workgroup) then applies the keep rule - mask_epi != 0, !(x < 0), !(y < 0), trunc(x) < cols, trunc(y) < rows, evaluated in
+ * float (no conversion overflows, a NaN is dropped), and mask[(int) y][(int) x] <= 127, read only behind the bounds test - compacts
+ * the survivors in order and, with to_database, appends each to the context's feature database: a known id to its slot, the k-th
+ * fresh survivor to the k-th slot ovp_featdb_append would hand out, so that slots, table and every later call equal the unfused
+ * sequence's byte for byte.  Integer decisions and copies behind the unchanged kernels: two runs give the same bytes.
+ * One upload (points, ids, per-candidate slot / fresh flag, the free-slot list, the RANSAC's table, the mask when given), N
+ * launches (k_klt_track; with check k_epi_undistort, k_epi_models, k_epi_count, k_epi_select, without it and with epi
+ * k_epi_undistort alone - of both point sets, the kernel as it is; k_klt_keep_append), one publication through the tracker's
+ * mailbox, one wait.  The first call (and the first with a mask) grows the tracker's staging - the mask's device buffer is its
+ * tail - and result block and waits for the stream once.
+ * The rules of feed_monocular, applied on the host before anything is enqueued: n = 0 returns at once with n_kept = 0; with check
+ * and n < OVP_EPI_MIN_POINTS the call succeeds with info.too_few, keep and mask_epi all zeros, no KLT and nothing appended
+ * (:1319-1323; pts_out, status and uvn are not written).
+ * Refused on the host with nothing enqueued, the outputs untouched and the database untouched - OVP_E_STATE: no tracker, fewer than
+ * two images fed, to_database without ovp_featdb_create; OVP_E_CAPACITY: n > max_points, with to_database a candidate whose slot
+ * already holds max_meas observations, or live features + fresh candidates above the slot count; OVP_E_ARG: a null input, n < 0,
+ * duplicate ids, a non-finite coordinate, mask_stride < width, epi == NULL with check or to_database, with to_database a NaN time
+ * stamp, anything ovp_klt_epipolar refuses in epi.  Both database conditions are STRICTER than the unfused sequence, which learns the
+ * survivors first and counts only those: a frame this entry refuses for capacity may pass there.
+ * A failure behind the checks (a HIP error of a launch or of the publication, a mailbox wait that fails) returns its code with the
+ * outputs unwritten; the staged upload is left for the next call's begin to wait out, which is safe.  NOT recovered: with
+ * to_database, if the wait fails after k_klt_keep_append has run, the device table may hold the frame's observations while the
+ * host's id -> slot map and shadow do not - the database is then out of step with the device and has to be reset (ovp_featdb_reset)
+ * or destroyed; nothing in the library repairs it.
+ * With the timer on ("timer" of ovp_klt_debug) the call fills its own slots of "time": k_klt_track, the epipolar slots (the four
+ * kernels with check; k_epi_undistort alone and three zeros without it; four zeros without epi) and k_klt_keep_append. */
+typedef struct ovp_klt_frame_in {
+  int n;                       /* points of the previous image, <= the tracker's max_points */
+  const float *pts_prev;       /* [2n] */
+  const int64_t *ids;          /* [n] distinct */
+  double timestamp;            /* message.timestamp (:556) */
+  const uint8_t *mask;         /* the current image's mask, the tracker's size, or NULL (no mask) */
+  int mask_stride;
+  const ovp_epipolar_opts *epi;/* camera mode + intrinsics (+ RANSAC options); NULL only if check == 0 && to_database == 0 */
+  int check;                   /* 1: perform_matching's epipolar check decides (mask_out = status & mask_rsc); 0: the status alone */
+  int to_database;             /* 1: the survivors are appended to the context's feature database */
+} ovp_klt_frame_in;
+typedef struct ovp_klt_frame_out {   /* every array may be NULL */
+  int n_kept;
+  uint8_t *keep;      /* [n] */
+  float   *pts_out;   /* [2n] where KLT left every point */
+  uint8_t *status;    /* [n] KLT status */
+  uint8_t *mask_epi;  /* [n] status & mask_rsc (== status when check == 0) */
+  float   *uvn;       /* [2n] undistort_cv of pts_out (only when epi != NULL) */
+  int32_t *kept_index;/* [n] the first n_kept entries: the indices of the survivors, ascending */
+  ovp_epipolar_info info; /* of the check; without it zeros and winner -1 */
+} ovp_klt_frame_out;
+int ovp_klt_match_frame(ovp_ctx *ctx, const ovp_klt_frame_in *in, ovp_klt_frame_out *out);
 /* tests: what = "cur" / "prev": the bytes of pyramid level `level` of that half (rows packed); "equalized": level 0 of the current
  * half; "dims": int32 [width, height] of the level; "iters": uint8 [n][8] iterations per level of the last ovp_klt_track (none
  * behind an ovp_klt_detect, which takes the mailbox); "score" / "nms": uint8 [height][width], the level-0 score map of the last
@@ -1157,7 +1209,9 @@ int ovp_klt_epipolar(ovp_ctx *ctx, const ovp_epipolar_opts *opts, int n, const f
  * "timer": level != 0 puts events around the kernels (and a stream synchronisation behind each entry) from the next call on,
  * "time": float GPU milliseconds of the last timed calls [equalise, pyramid launches together, k_klt_track, k_fast_score_nms,
  * k_fast_select, k_fast_subpix, k_epi_undistort, k_epi_models, k_epi_count, k_epi_select, the intake's halving, k_clahe_lut,
- * k_clahe_apply (the last three 0 where the last feed did not run them)] - as many as cap holds, at least the first 3.
+ * k_clahe_apply (the last three 0 where the last feed did not run them), k_klt_keep_append of the last ovp_klt_match_frame] - as
+ * many as cap holds, at least the first 3.  "frame_uv" / "frame_uvn": float [n_kept][2], the compacted survivors (pixels; undistorted,
+ * with epi) the last ovp_klt_match_frame published - OVP_E_STATE once another entry has taken the mailbox.
  * "clahe_lut": uint8 [tiles_y tiles_x][256], the tile LUTs of the last CLAHE feed (OVP_E_STATE before one).  Of the last ovp_klt_epipolar that ran its RANSAC (n >= OVP_EPI_MIN_POINTS; OVP_E_STATE before one; H its max_iters, level is
  * ignored): "epi_samples"
  * int32 [H][7] (-1 without a set), "epi_models" int32 [H] n_models then double [H][3][9] (the doubles start at the next multiple

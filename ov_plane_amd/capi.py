@@ -13,6 +13,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OVP_LIB_AB") or os.path.join(_HERE, "libovplane_hip.so")  # OVP_LIB_AB: another build of the same library (A/B timing runs)
 OVP_MAX_MEAS = 32
+OVP_EPI_MIN_POINTS = 10  # ovplane_hip.h (:1319)
 OVP_E_ARG, OVP_E_CAPACITY, OVP_E_NOTSPD, OVP_E_NEGDIAG, OVP_E_NODEVICE, OVP_E_STATE, OVP_E_TIMEOUT = -1, -2, -3, -4, -5, -6, -7
 
 
@@ -276,7 +277,7 @@ EXPORTS = [
     "ovp_propagate_and_clone",
     "ovp_klt_create", "ovp_klt_destroy", "ovp_klt_reset", "ovp_klt_feed_image", "ovp_klt_track", "ovp_klt_debug", "ovp_klt_detect",
     "ovp_epipolar_defaults", "ovp_klt_epipolar",
-    "ovp_klt_intake_defaults", "ovp_klt_feed_image_opts", "ovp_klt_halve",
+    "ovp_klt_intake_defaults", "ovp_klt_feed_image_opts", "ovp_klt_halve", "ovp_klt_match_frame",
     "ovp_featdb_create", "ovp_featdb_destroy", "ovp_featdb_reset", "ovp_featdb_append", "ovp_featdb_classify_defaults",
     "ovp_featdb_classify", "ovp_featdb_mark_deleted", "ovp_featdb_gather", "ovp_featdb_triangulate", "ovp_featdb_cleanup",
     "ovp_featdb_get", "ovp_featdb_debug",
@@ -305,6 +306,18 @@ class EpipolarInfo(C.Structure):
     """ovp_epipolar_info"""
     _fields_ = [("F", C.c_double * 9), ("best_count", C.c_int32), ("winner_h", C.c_int32), ("winner_model", C.c_int32),
                 ("niters", C.c_int32), ("n_with_model", C.c_int32), ("too_few", C.c_int32), ("no_model", C.c_int32), ("stop", C.c_int32)]
+
+
+class KltFrameIn(C.Structure):
+    """ovp_klt_frame_in"""
+    _fields_ = [("n", C.c_int), ("pts_prev", C.c_void_p), ("ids", C.c_void_p), ("timestamp", C.c_double), ("mask", C.c_void_p),
+                ("mask_stride", C.c_int), ("epi", C.c_void_p), ("check", C.c_int), ("to_database", C.c_int)]
+
+
+class KltFrameOut(C.Structure):
+    """ovp_klt_frame_out"""
+    _fields_ = [("n_kept", C.c_int), ("keep", C.c_void_p), ("pts_out", C.c_void_p), ("status", C.c_void_p), ("mask_epi", C.c_void_p),
+                ("uvn", C.c_void_p), ("kept_index", C.c_void_p), ("info", EpipolarInfo)]
 
 
 class Intake(C.Structure):
@@ -447,6 +460,7 @@ def lib():
         L.ovp_klt_intake_defaults.argtypes = [C.c_void_p]
         L.ovp_klt_feed_image_opts.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ovp_klt_halve.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.ovp_klt_match_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ovp_klt_debug.restype = C.c_long
         L.ovp_klt_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_long]
         L.ovp_featdb_create.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -878,6 +892,7 @@ class KltTracker:
         self.ids_last = np.zeros(0, dtype=np.int64)
         self.pts_last = np.zeros((0, 2), dtype=np.float32)
         self._fed = 0
+        self.camera = None       # (mode, intrinsics [8]): undistort_cv's camera for step(database=) without the epipolar check
 
     def close(self):
         _chk(lib().ovp_klt_destroy(self.ctx.handle), "ovp_klt_destroy")
@@ -1063,6 +1078,71 @@ class KltTracker:
                     winner=(int(info.winner_h), int(info.winner_model)), niters=int(info.niters), stop=int(info.stop),
                     n_with_model=int(info.n_with_model), too_few=bool(info.too_few), no_model=bool(info.no_model))
 
+    def _epipolar_opts(self, camera=None, **opts):
+        o = EpipolarOpts()
+        lib().ovp_epipolar_defaults(C.byref(o))
+        if camera is not None:
+            mode, intr = camera
+            o.mode = self.CAMERA_MODES[mode] if isinstance(mode, str) else int(mode)
+            o.intrinsics[:] = [float(v) for v in intr]
+            if o.mode:
+                o.threshold = 2.0 / max(float(intr[0]), float(intr[1]))
+        for k, v in opts.items():
+            if k not in ("threshold", "confidence", "max_iters", "seed"):
+                raise TypeError("unknown option %s" % k)
+            setattr(o, k, v)
+        return o
+
+    def match_frame(self, pts_prev, ids, timestamp=0.0, mask=None, epipolar=None, check=False, database=None, compacted=False):
+        """ovp_klt_match_frame: the back half of feed_monocular (:510-567) in one device pass - KLT from pts_prev [n, 2] with
+        guess = pts_prev, the epipolar check (check=True) or the undistortion alone, the keep rule under mask [height, width] (None:
+        none), and with database (a FeatureDatabase of this context) the survivors' update_feature.  epipolar: None, or
+        dict(camera=, threshold=, confidence=, max_iters=, seed=) as step takes it.  -> dict(n_kept, keep [n] bool, pts [n, 2],
+        status [n], mask [n], uvn [n, 2] (None without epipolar), kept_index [n_kept], info (EpipolarInfo), and with the check the
+        fields epipolar() returns).  compacted=True (tests) adds kept_uv / kept_uvn [n_kept, 2] as the device compacted them, read
+        back through two further debug calls; nothing above this entry needs them (pts[keep] and uvn[keep] are the same bytes)."""
+        p = np.ascontiguousarray(pts_prev, dtype=np.float32).reshape(-1, 2)
+        n = len(p)
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(n)
+        o = None if epipolar is None else self._epipolar_opts(**epipolar)
+        a = KltFrameIn()
+        a.n, a.pts_prev, a.ids, a.timestamp = n, p.ctypes.data, ids.ctypes.data, float(timestamp)
+        if mask is not None:
+            mask = np.asarray(mask)
+            if mask.dtype != np.uint8 or mask.shape != (self.height, self.width):
+                raise ValueError("an 8-bit mask of %d x %d is expected" % (self.width, self.height))
+            if mask.strides[1] != 1 or mask.strides[0] < self.width:
+                mask = np.ascontiguousarray(mask)
+            a.mask, a.mask_stride = mask.ctypes.data, int(mask.strides[0])
+        a.epi = None if o is None else C.addressof(o)
+        a.check, a.to_database = (1 if check else 0), (0 if database is None else 1)
+        m = max(n, 1)
+        keep, st, me = (np.full(m, 255, dtype=np.uint8) for _ in range(3))
+        out, uvn = np.full((m, 2), -1.0, dtype=np.float32), np.full((m, 2), -1.0, dtype=np.float32)
+        idx = np.full(m, -1, dtype=np.int32)
+        r = KltFrameOut()
+        r.n_kept, r.info.winner_h = -7, -7
+        r.keep, r.pts_out, r.status, r.mask_epi, r.uvn, r.kept_index = (v.ctypes.data for v in (keep, out, st, me, uvn, idx))
+        t0 = time.perf_counter()
+        rc = lib().ovp_klt_match_frame(self.ctx.handle, C.byref(a), C.byref(r))
+        self.last_frame_ms = 1e3 * (time.perf_counter() - t0)
+        self.last_frame_raw = (r, keep, out, st, me, uvn, idx)  # (tests: untouched by a refusal)
+        _chk(rc, "ovp_klt_match_frame")
+        k, info = r.n_kept, r.info
+        res = dict(n_kept=k, keep=keep[:n] != 0, pts=out[:n], status=st[:n], mask=me[:n], uvn=None if o is None else uvn[:n],
+                   kept_index=idx[:k].copy(), info=info)
+        if compacted:
+            ran = n > 0 and not (check and n < OVP_EPI_MIN_POINTS)   # (otherwise nothing was published)
+            none = np.zeros((0, 2), np.float32)
+            res.update(kept_uv=self._debug(b"frame_uv", 0, 8 * k, np.float32).reshape(-1, 2).copy() if ran else none,
+                       kept_uvn=self._debug(b"frame_uvn", 0, 8 * k, np.float32).reshape(-1, 2).copy() if ran and o is not None else none)
+        if check:
+            self._epi_shape = (int(o.max_iters), n)
+            res.update(F=np.array(info.F[:]).reshape(3, 3), count=int(info.best_count), winner=(int(info.winner_h), int(info.winner_model)),
+                       niters=int(info.niters), stop=int(info.stop), n_with_model=int(info.n_with_model), too_few=bool(info.too_few),
+                       no_model=bool(info.no_model), uvn1=res["uvn"])
+        return res
+
     def epipolar_stages(self):
         """tests: what the kernels of the last epipolar() left -> dict(samples [H, 7], n_models [H], models [H, 3, 9], counts [H, 3],
         table [n + 1])"""
@@ -1074,7 +1154,8 @@ class KltTracker:
                     counts=self._debug(b"epi_counts", 0, 12 * H, np.int32).reshape(H, 3).copy(),
                     table=self._debug(b"epi_table", 0, 4 * (n + 1), np.int32).copy())
 
-    def step(self, img, mask=None, hist="HISTOGRAM", detect=False, epipolar=None, intake=None):
+    def step(self, img, mask=None, hist="HISTOGRAM", detect=False, epipolar=None, intake=None, database=None, timestamp=None,
+             fused=False):
         """feed_monocular :505-567 minus detection and the epipolar check: feeds img, tracks pts_last into it with guess = pts_last,
         keeps a point unless x < 0, y < 0, (int) x >= cols, (int) y >= rows, mask > 127 at the truncated pixel, or status 0.
         Returns (ids, pts) of the kept points, which are pts_last / ids_last from here on.
@@ -1086,7 +1167,20 @@ class KltTracker:
         undistorted coordinates (:555).
         intake: None, or the intake options (intake_defaults): the image is fed through feed_image_opts (hist is not looked at),
         and with intake.downsample img and mask are the full-size ones - the mask is halved on the device (halve) before the keep
-        rule and the detector use it (core/VioManager.cpp:279-289)."""
+        rule and the detector use it (core/VioManager.cpp:279-289).
+        database: None, or the context's FeatureDatabase: the kept points go to database.update_feature(timestamp, ids, uv,
+        uv_norm) (:553-557); uv_norm needs a camera - epipolar=, or without the check the tracker's `camera` attribute
+        ((mode, intrinsics): the undistortion alone decides nothing).  fused=False: the existing entries, one after the other -
+        track, epipolar, the keep rule here, append.  fused=True: the same frame through ovp_klt_match_frame (match_frame), one
+        entry; last_match, last_uv_norm, last_epipolar (without the stage read-backs), last_reset and last_keep are filled alike."""
+        cam = None
+        if database is not None or fused:
+            if timestamp is None and database is not None:
+                raise ValueError("a database needs the frame's timestamp")
+            cam = epipolar if epipolar is not None else (None if self.camera is None else dict(camera=self.camera, max_iters=1))
+            if database is not None and cam is None:
+                raise ValueError("a database needs uv_norm: give epipolar= or set the tracker's camera")
+        self.last_keep = np.zeros(0, dtype=bool)
         if intake is None:
             self.feed_image(img, hist)
         else:
@@ -1111,19 +1205,36 @@ class KltTracker:
                 return self.ids_last.copy(), self.pts_last.copy()
         if self._fed < 2 or len(self.ids_last) == 0:
             return self.ids_last.copy(), self.pts_last.copy()
+        if fused:
+            r = self.match_frame(self.pts_last, self.ids_last, 0.0 if timestamp is None else timestamp, mask, cam,
+                                 check=epipolar is not None, database=database)
+            self.last_match, keep = (r["pts"], r["status"]), r["keep"]
+            if epipolar is not None:
+                self.last_epipolar = {k: v for k, v in r.items() if k in ("mask", "uvn1", "F", "count", "winner", "niters", "stop",
+                                                                          "n_with_model", "too_few", "no_model")}
+            self.last_keep = keep
+            self.ids_last, self.pts_last = self.ids_last[keep], r["pts"][keep]
+            if cam is not None:
+                self.last_uv_norm = r["uvn"][keep]
+            return self.ids_last.copy(), self.pts_last.copy()
         p, st = self.track(self.pts_last, self.pts_last)
         self.last_match = (p, st)  # of the points that went into this step, in their order
         if epipolar is not None:
             self.last_epipolar = self.epipolar(self.pts_last, p, st, **epipolar)
             st, uvn = self.last_epipolar["mask"], self.last_epipolar["uvn1"]
+        elif cam is not None:   # the undistortion alone: one hypothesis, its mask not looked at
+            uvn = self.epipolar(self.pts_last, p, st, **cam)["uvn1"]
         x, y = p[:, 0], p[:, 1]
         xi, yi = np.clip(x, 0, self.width - 1).astype(np.int64), np.clip(y, 0, self.height - 1).astype(np.int64)
         keep = (st != 0) & ~(x < 0) & ~(y < 0) & (np.trunc(x) < self.width) & (np.trunc(y) < self.height)
         if mask is not None:
             keep &= ~(np.asarray(mask)[yi, xi] > 127)
+        self.last_keep = keep
         self.ids_last, self.pts_last = self.ids_last[keep], p[keep]
-        if epipolar is not None:
+        if epipolar is not None or cam is not None:
             self.last_uv_norm = uvn[keep]
+        if database is not None:
+            database.update_feature(timestamp, self.ids_last, self.pts_last, self.last_uv_norm)   # :553-557
         return self.ids_last.copy(), self.pts_last.copy()
 
     def _debug(self, what, level, nbytes, dtype=np.uint8):
@@ -1151,10 +1262,10 @@ class KltTracker:
 
     def kernel_ms(self):
         """GPU milliseconds of the last timed calls: dict(equalize, pyramid, track, score_nms, select, subpix, epi_undistort,
-        epi_models, epi_count, epi_select, halve, clahe_lut, clahe_apply)"""
-        t = self._debug(b"time", 0, 52, np.float32)
+        epi_models, epi_count, epi_select, halve, clahe_lut, clahe_apply, keep_append)"""
+        t = self._debug(b"time", 0, 56, np.float32)
         return dict(zip(("equalize", "pyramid", "track", "score_nms", "select", "subpix", "epi_undistort", "epi_models", "epi_count",
-                         "epi_select", "halve", "clahe_lut", "clahe_apply"), (float(v) for v in t)))
+                         "epi_select", "halve", "clahe_lut", "clahe_apply", "keep_append"), (float(v) for v in t)))
 
     def refine(self, xy):
         """tests: k_fast_subpix from the starting positions xy [n, 2] on level 0 of the current half -> [n, 2] f32"""

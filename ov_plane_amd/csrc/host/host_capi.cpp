@@ -1191,6 +1191,55 @@ extern "C" int ovph_run_klt_epipolar_sequence(int device, int width, int height,
   return rc;
 }
 
+// TrackPlane::feed_monocular over the fused entry, with a feature database attached, on a sequence of frames (host_capi.h)
+extern "C" int ovph_run_klt_frame_sequence(int device, int width, int height, int n_frames, const uint8_t *frames, const uint8_t *mask,
+                                           const double *times, int pyr_levels, int win_size, int hist_method, int n_pts,
+                                           const int64_t *ids, const float *uv, int mode, const double *intrinsics8, int check,
+                                           int max_iters, uint32_t seed, int max_slots, int max_meas, int32_t *n_kept, int64_t *kept_ids,
+                                           float *kept_uv, float *kept_uvn, int32_t *reset, int32_t *db_slot, int32_t *db_count,
+                                           double *db_ts, float *db_uv, float *db_uvn) {
+  ovp_ctx *gpu = nullptr;
+  int rc = ovp_ctx_create(device, 64, 4, 8, nullptr, &gpu);
+  if (rc) return rc;
+  {
+    ovp_trackplane_opts to;
+    ovp_trackplane_defaults(&to);
+    TrackPlane tp(gpu, to);
+    ov_plane::FeatureDatabase db(gpu, max_slots, max_meas);
+    rc = tp.ok() ? db.status() : OVP_E_STATE;
+    if (rc == 0) rc = tp.set_klt_options(pyr_levels, win_size, hist_method, std::max(n_pts, 1));
+    if (rc == 0) rc = tp.set_camera(mode, intrinsics8);
+    tp.set_epipolar_options(0.999, max_iters, seed);
+    if (rc == 0) rc = tp.set_database(&db);
+    const size_t px = (size_t)width * height;
+    for (int f = 0; f < n_frames && rc == 0; ++f) {
+      rc = tp.feed_monocular(times[f], frames + px * f, width, height, width, mask, false, check != 0);
+      if (rc) break;
+      if (f == 0) {  // the caller's detection: its points, and their first observation (:477-491)
+        std::vector<size_t> id(ids, ids + n_pts);
+        std::vector<float> p(uv, uv + 2 * (size_t)n_pts);
+        tp.add_points(id, p);
+        rc = db.update_feature(times[0], std::vector<int64_t>(ids, ids + n_pts), p, p);
+        if (rc) break;
+      }
+      const auto &ki = tp.get_last_ids();
+      const auto &kp = tp.get_last_pts();
+      const auto &kn = tp.get_last_uv_norm();
+      n_kept[f] = (int32_t)ki.size(), reset[f] = tp.last_reset() ? 1 : 0;
+      for (size_t i = 0; i < ki.size(); ++i) kept_ids[(size_t)f * n_pts + i] = (int64_t)ki[i];
+      if (!kp.empty()) memcpy(kept_uv + 2 * (size_t)f * n_pts, kp.data(), sizeof(float) * kp.size());
+      if (!kn.empty()) memcpy(kept_uvn + 2 * (size_t)f * n_pts, kn.data(), sizeof(float) * kn.size());
+    }
+    for (int i = 0; i < n_pts && rc == 0; ++i) {  // the database's read-back
+      int del = 0;
+      rc = ovp_featdb_get(gpu, ids[i], db_slot + i, db_count + i, &del, db_ts + (size_t)i * max_meas, db_uv + 2 * (size_t)i * max_meas,
+                          db_uvn + 2 * (size_t)i * max_meas, max_meas);
+    }
+  }
+  ovp_ctx_destroy(gpu);
+  return rc;
+}
+
 // TrackPlane's image half with its own detection on a sequence of frames (host_capi.h)
 extern "C" int ovph_run_klt_detect_sequence(int device, int width, int height, int n_frames, const uint8_t *frames, const uint8_t *mask,
                                             int pyr_levels, int win_size, int hist_method, int max_points, const int32_t *detector5,

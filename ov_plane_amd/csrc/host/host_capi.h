@@ -83,6 +83,16 @@ int ovph_run_klt_epipolar_sequence(int device, int width, int height, int n_fram
                                    int pyr_levels, int win_size, int hist_method, int n_pts, const int64_t *ids, const float *uv,
                                    int mode, const double *intrinsics8, int max_iters, uint32_t seed, int32_t *n_kept, int64_t *kept_ids,
                                    float *kept_uv, float *kept_uvn, int32_t *reset);
+// TrackPlane::feed_monocular (ov_plane_trackplane.h) over the fused entry ovp_klt_match_frame, a FeatureDatabase(max_slots,
+// max_meas) attached through set_database: frame f at times[f], the points added behind the first frame together with their first
+// observation (uv_norm = uv), check = the epipolar check.  Per frame what ovph_run_klt_epipolar_sequence returns; at the end the
+// database's read-back of every input id: db_slot / db_count [n_pts] (count -1: not held), db_ts [n_pts][max_meas], db_uv / db_uvn
+// [n_pts][max_meas][2].
+int ovph_run_klt_frame_sequence(int device, int width, int height, int n_frames, const uint8_t *frames, const uint8_t *mask,
+                                const double *times, int pyr_levels, int win_size, int hist_method, int n_pts, const int64_t *ids,
+                                const float *uv, int mode, const double *intrinsics8, int check, int max_iters, uint32_t seed,
+                                int max_slots, int max_meas, int32_t *n_kept, int64_t *kept_ids, float *kept_uv, float *kept_uvn,
+                                int32_t *reset, int32_t *db_slot, int32_t *db_count, double *db_ts, float *db_uv, float *db_uvn);
 // ovph_run_klt_detect_sequence under set_intake(hist_method, downsample, clahe_clip, tiles_x, tiles_y): the frames go through
 // ovp_klt_feed_image_opts - CLAHE included - and with downsample frames [n_frames][height][width] and the mask are the full-size
 // ones, halved on the device; the points are pixels of the (width / 2) x (height / 2) image.

@@ -33,6 +33,7 @@ class FeatureDatabase {
   FeatureDatabase(const FeatureDatabase&) = delete;
   FeatureDatabase& operator=(const FeatureDatabase&) = delete;
   int status() const { return rc_; }  // of the create
+  ovp_ctx* context() const { return ctx_; }
 
   int update_feature(double timestamp, const std::vector<int64_t>& ids, const std::vector<float>& uv, const std::vector<float>& uv_norm) {
     if (uv.size() != 2 * ids.size() || uv_norm.size() != 2 * ids.size()) return OVP_E_ARG;

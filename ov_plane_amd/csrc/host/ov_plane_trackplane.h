@@ -15,6 +15,9 @@
 // included; get_last_uv_norm() holds the kept points' undistorted coordinates (:555).  set_intake() selects the histogram method by
 // TrackBase's names - CLAHE (:66-70) included, on the device: recalled and unpinned, tests/clahe_ref.py - and downsample_cameras
 // (core/VioManager.cpp:279-289): feed_new_camera() then takes the full-size image and mask and halves both on the device.
+// feed_monocular() is :463-567 over ONE entry (ovp_klt_match_frame): KLT, the epipolar check, the keep rule and, under
+// set_database(), database->update_feature of the survivors (:553-557) in one device pass - the same frame feed_new_camera walks
+// through ovp_klt_track, ovp_klt_epipolar and its own keep rule, byte for byte.
 #pragma once
 #include <array>
 #include <cmath>
@@ -24,6 +27,7 @@
 #include <vector>
 
 #include "ov_plane_delaunay.h"
+#include "ov_plane_featdb.h"  // the context's database, which feed_monocular() appends to on the device
 #include "ovplane_hip.h"
 
 namespace ov_plane {
@@ -224,6 +228,7 @@ class TrackPlane {
     _epi.mode = mode;
     for (int k = 0; k < 8; ++k) _epi.intrinsics[k] = intrinsics[k];
     if (mode != OVP_EPI_MODE_NORMALISED) _epi.threshold = 2.0 / std::max(intrinsics[0], intrinsics[1]);
+    _camera_set = true;
     return 0;
   }
   // the RANSAC's own options (:1344 passes 0.999; max_iters and the seed are this library's); threshold <= 0 keeps the camera's
@@ -308,42 +313,10 @@ class TrackPlane {
   // halving - tracker, mask tests, points - is in pixels of the (w / 2) x (h / 2) image.
   int feed_new_camera(double time, const uint8_t *img, int w, int h, int stride, const uint8_t *mask = nullptr, bool detect = false,
                       bool epipolar = false) {
-    const bool halve = _intake_set && _intake.downsample;
-    const int src_w = w, src_h = h;
-    if (halve) w = src_w / 2, h = src_h / 2;
-    if (!_klt_made) {
-      const int rc = ovp_klt_create(_gpu, w, h, _pyr_levels + 1, _win_size, _klt_max_points);
-      if (rc) return rc;
-      _klt_made = true, _klt_w = w, _klt_h = h;
-    }
-    if (w != _klt_w || h != _klt_h) return OVP_E_ARG;
-    int rc;
-    if (_intake_set) {
-      ovp_klt_intake in = _intake;
-      in.src_width = src_w, in.src_height = src_h;
-      rc = ovp_klt_feed_image_opts(_gpu, img, stride, &in);
-    } else {
-      rc = ovp_klt_feed_image(_gpu, img, stride, _hist);
-    }
-    if (rc) return rc;
     std::vector<uint8_t> mask_halved;
-    if (halve && mask) {  // core/VioManager.cpp:284-288
-      mask_halved.resize((size_t)w * h);
-      rc = ovp_klt_halve(_gpu, mask, src_w, src_w, src_h, mask_halved.data());
-      if (rc) return rc;
-      mask = mask_halved.data();
-    }
-    _time_last = time;
-    _match_pts.clear(), _match_mask.clear();
-    ++_n_images;
-    if (detect) {
-      std::vector<uint8_t> mask_prev;
-      mask_prev.swap(_mask_last);
-      if (mask) _mask_last.assign(mask, mask + (size_t)w * h);
-      if (_ids_last.empty()) return perform_detection_monocular(0, mask, _pts_last, _ids_last);
-      rc = perform_detection_monocular(1, mask_prev.empty() ? nullptr : mask_prev.data(), _pts_last, _ids_last);
-      if (rc) return rc;
-    }
+    bool finished = false;
+    int rc = feed_front(time, img, w, h, stride, mask, detect, mask_halved, finished);
+    if (rc || finished) return rc;
     _uvn_last.clear(), _last_reset = false;
     if (epipolar && _n_images >= 2)
       return matching_frame(w, h, mask, _ids_last, _pts_last, _uvn_last, _match_pts, _match_mask, _last_reset,
@@ -367,6 +340,64 @@ class TrackPlane {
     _pts_last.swap(good), _ids_last.swap(good_ids);  // :560-567
     return 0;
   }
+  // the feature database feed_monocular() appends the kept points to on the device (NULL: none).  The entry appends to the database
+  // of its context, so only that one can be attached: OVP_E_ARG for a database of another context, OVP_E_STATE for one whose create failed.
+  int set_database(FeatureDatabase *database) {
+    if (database && database->context() != _gpu) return OVP_E_ARG;
+    if (database && database->status() != 0) return OVP_E_STATE;
+    _database = database;
+    return 0;
+  }
+
+  // feed_monocular :463-567 over ovp_klt_match_frame - image and mask as feed_new_camera takes them, detect as there.  epipolar:
+  // perform_matching's check decides; without it the status alone, and uv_norm (get_last_uv_norm) comes from the undistortion
+  // alone when a camera is set.  With a database the kept points' observations are appended at `time` in the same device pass
+  // (a camera is needed: OVP_E_ARG without one).  The empty-set rules are feed_new_camera's: no points with the check resets
+  // (:520-530), fewer than ten keep nothing and run no KLT (:1319-1323).
+  int feed_monocular(double time, const uint8_t *img, int w, int h, int stride, const uint8_t *mask = nullptr, bool detect = false,
+                     bool epipolar = false) {
+    std::vector<uint8_t> mask_halved;
+    bool finished = false;
+    int rc = feed_front(time, img, w, h, stride, mask, detect, mask_halved, finished);
+    if (rc || finished) return rc;
+    _uvn_last.clear(), _last_reset = false;
+    const size_t n = _ids_last.size();
+    if (epipolar && _n_images >= 2) {
+      if (n == 0) {  // :1307 an empty mask -> :520-530
+        _last_reset = true;
+        return 0;
+      }
+      if (n < OVP_EPI_MIN_POINTS) {  // :1319-1323 all zeros, no KLT
+        _match_mask.assign(n, 0);
+        _pts_last.clear(), _ids_last.clear();
+        return 0;
+      }
+    }
+    if (_n_images < 2 || n == 0) return 0;
+    std::vector<int64_t> id64(_ids_last.begin(), _ids_last.end());
+    std::vector<uint8_t> keep(n), mask_epi(n);
+    std::vector<float> pts_new(2 * n), uvn(2 * n);
+    ovp_klt_frame_in in = {};
+    in.n = (int)n, in.pts_prev = _pts_last.data(), in.ids = id64.data(), in.timestamp = time;
+    in.mask = mask, in.mask_stride = w;
+    in.epi = (epipolar || _camera_set) ? &_epi : nullptr;
+    in.check = epipolar ? 1 : 0, in.to_database = _database ? 1 : 0;
+    ovp_klt_frame_out out = {};
+    out.keep = keep.data(), out.pts_out = pts_new.data(), out.mask_epi = mask_epi.data(), out.uvn = uvn.data();
+    rc = ovp_klt_match_frame(_gpu, &in, &out);
+    if (rc) return rc;
+    if (epipolar) _epi_info = out.info;
+    std::vector<float> good, good_n;
+    std::vector<size_t> good_ids;
+    for (size_t i = 0; i < n; ++i) {
+      if (!keep[i]) continue;
+      good.push_back(pts_new[2 * i]), good.push_back(pts_new[2 * i + 1]), good_ids.push_back(_ids_last[i]);
+      if (in.epi) good_n.push_back(uvn[2 * i]), good_n.push_back(uvn[2 * i + 1]);  // :555
+    }
+    _match_pts = pts_new, _match_mask = mask_epi;
+    _pts_last.swap(good), _ids_last.swap(good_ids), _uvn_last.swap(good_n);  // :560-567
+    return 0;
+  }
   const std::vector<size_t> &get_last_ids() const { return _ids_last; }
   const std::vector<float> &get_last_pts() const { return _pts_last; }          // [2n]
   const std::vector<float> &get_last_match_pts() const { return _match_pts; }   // of the points that went into the last frame
@@ -387,6 +418,52 @@ class TrackPlane {
   }
 
  private:
+  // the front of a frame, shared by feed_new_camera and feed_monocular: the tracker on first use, the image's intake (:40-92), the
+  // mask's halving and feed_monocular's use of the detection (:477-491, :505-507).  w, h and mask become the tracker's; finished:
+  // the frame ended with the first detection.
+  int feed_front(double time, const uint8_t *img, int &w, int &h, int stride, const uint8_t *&mask, bool detect,
+                 std::vector<uint8_t> &mask_halved, bool &finished) {
+    const bool halve = _intake_set && _intake.downsample;
+    const int src_w = w, src_h = h;
+    if (halve) w = src_w / 2, h = src_h / 2;
+    if (!_klt_made) {
+      const int rc = ovp_klt_create(_gpu, w, h, _pyr_levels + 1, _win_size, _klt_max_points);
+      if (rc) return rc;
+      _klt_made = true, _klt_w = w, _klt_h = h;
+    }
+    if (w != _klt_w || h != _klt_h) return OVP_E_ARG;
+    int rc;
+    if (_intake_set) {
+      ovp_klt_intake in = _intake;
+      in.src_width = src_w, in.src_height = src_h;
+      rc = ovp_klt_feed_image_opts(_gpu, img, stride, &in);
+    } else {
+      rc = ovp_klt_feed_image(_gpu, img, stride, _hist);
+    }
+    if (rc) return rc;
+    if (halve && mask) {  // core/VioManager.cpp:284-288
+      mask_halved.resize((size_t)w * h);
+      rc = ovp_klt_halve(_gpu, mask, src_w, src_w, src_h, mask_halved.data());
+      if (rc) return rc;
+      mask = mask_halved.data();
+    }
+    _time_last = time;
+    _match_pts.clear(), _match_mask.clear();
+    ++_n_images;
+    if (detect) {
+      std::vector<uint8_t> mask_prev;
+      mask_prev.swap(_mask_last);
+      if (mask) _mask_last.assign(mask, mask + (size_t)w * h);
+      if (_ids_last.empty()) {
+        finished = true;
+        return perform_detection_monocular(0, mask, _pts_last, _ids_last);
+      }
+      rc = perform_detection_monocular(1, mask_prev.empty() ? nullptr : mask_prev.data(), _pts_last, _ids_last);
+      if (rc) return rc;
+    }
+    return 0;
+  }
+
   ovp_ctx *_gpu;
   int _rc = 0;
   bool _have_pose = false, _device_delaunay = false;
@@ -415,6 +492,8 @@ class TrackPlane {
   ovp_epipolar_info _epi_info = {};
   std::vector<float> _uvn_last;
   bool _last_reset = false;
+  bool _camera_set = false;            // set_camera was called: feed_monocular undistorts without the check as well
+  FeatureDatabase *_database = nullptr;  // set_database
 };
 
 }  // namespace ov_plane

@@ -37,5 +37,7 @@ struct EpiLaunch {
 
 // the four launches on `stream`; 0 or an OVP_E_* code
 int ovp_epi_enqueue(const EpiLaunch& a, hipStream_t stream);
+// k_epi_undistort alone (both point sets, the kernel as it is): uvn0 / uvn1 of pts0 / pts1, nothing else written
+int ovp_epi_enqueue_undistort(const EpiLaunch& a, hipStream_t stream);
 // table[c] = RANSACUpdateNumIters(confidence, (n - c) / n, 7, max_iters), c = 0..n, with the host's libm
 void ovp_epi_table(int n, double confidence, int max_iters, int32_t* table);

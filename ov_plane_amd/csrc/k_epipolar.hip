@@ -357,6 +357,12 @@ int ovp_epi_enqueue(const EpiLaunch& a, hipStream_t stream) {
   return 0;
 }
 
+int ovp_epi_enqueue_undistort(const EpiLaunch& a, hipStream_t stream) {
+  if (a.n < 1) return OVP_E_ARG;
+  hipLaunchKernelGGL(k_epi_undistort, dim3((2 * a.n + 255) / 256), dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+
 static int epi_update_num_iters(double p, double ep, int model_points, int max_iters) {  // RANSACUpdateNumIters (recalled)
   p = std::min(std::max(p, 0.0), 1.0), ep = std::min(std::max(ep, 0.0), 1.0);
   double num = std::max(1.0 - p, DBL_MIN), denom = 1.0 - std::pow(1.0 - ep, model_points);

@@ -16,30 +16,17 @@
 
 #include <map>
 
-namespace {
+#include "host/ov_plane_frame_plan.h"  // the survivor / slot replay of a fused frame (ovp_featdb_frame_commit below)
+#include "k_klt_frame.h"  // FdbTable, fdb_append_one (shared with k_klt_keep_append), the database's side of ovp_klt_match_frame
 
-struct FdbTable {
-  double* ts;      // [S*M]
-  float2 *uv, *uvn;  // [S*M]
-  int *count, *del;  // [S]
-  long long* id;   // [S]
-  int M;
-};
+namespace {
 
 __global__ __launch_bounds__(256) void k_featdb_append(FdbTable t, int n, double stamp, const int* __restrict__ slot,
                                                        const unsigned char* __restrict__ fresh, const long long* __restrict__ ids,
                                                        const float2* __restrict__ uv, const float2* __restrict__ uvn) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const int s = slot[i];
-  // a slot a feature has just taken holds what its former owner left: the count starts at 0 and the flag is cleared
-  const int k = fresh[i] ? 0 : t.count[s];
-  if (k >= t.M) return;  // (the host has refused such a frame: never met)
-  if (fresh[i]) t.id[s] = ids[i], t.del[s] = 0;
-  t.ts[(size_t)s * t.M + k] = stamp;
-  t.uv[(size_t)s * t.M + k] = uv[i];
-  t.uvn[(size_t)s * t.M + k] = uvn[i];
-  t.count[s] = k + 1;
+  fdb_append_one(t, slot[i], fresh[i] != 0, ids[i], stamp, uv[i], uvn[i]);
 }
 
 __global__ __launch_bounds__(256) void k_featdb_mark(FdbTable t, int n, const int* __restrict__ slot) {
@@ -357,6 +344,47 @@ extern "C" int ovp_featdb_append(ovp_ctx* c, double timestamp, int n, const int6
     HIPCHK(hipEventElapsedTime(&d->ms, d->ev[0], d->ev[1]));
   }
   return 0;
+}
+
+// ---- the database's side of ovp_klt_match_frame (k_klt.hip): the plan in front of the enqueue, the shadow's replay behind the wait ----
+int ovp_featdb_frame_plan(ovp_ctx* c, double stamp, int n, const int64_t* ids, int32_t* slot, unsigned char* fresh, int32_t* free_slots,
+                          int* n_fresh, FdbTable* table) {
+  FeatDb* d = db_of(c);
+  if (!d) return OVP_E_STATE;
+  if (!(stamp == stamp)) return OVP_E_ARG;
+  int nf = 0;
+  for (int i = 0; i < n; ++i) {
+    auto it = d->slot_of.find(ids[i]);
+    fresh[i] = it == d->slot_of.end();
+    slot[i] = fresh[i] ? -1 : it->second;
+    if (fresh[i]) ++nf;
+    else if ((int)d->stamps[it->second].size() >= d->M) return OVP_E_CAPACITY;
+  }
+  if ((size_t)nf > d->free_slots.size()) return OVP_E_CAPACITY;
+  for (int k = 0; k < nf; ++k) free_slots[k] = d->free_slots[d->free_slots.size() - 1 - (size_t)k];  // the stack, from its top
+  *n_fresh = nf;
+  *table = d->table();
+  return 0;
+}
+
+void ovp_featdb_frame_commit(ovp_ctx* c, double stamp, int n, const int64_t* ids, const unsigned char* keep) {
+  FeatDb* d = db_of(c);
+  if (!d) return;
+  std::vector<int32_t> slot(n), free_list(d->free_slots.rbegin(), d->free_slots.rend());
+  std::vector<unsigned char> fresh(n);
+  for (int i = 0; i < n; ++i) {
+    auto it = d->slot_of.find(ids[i]);
+    fresh[i] = it == d->slot_of.end();
+    slot[i] = fresh[i] ? -1 : it->second;
+  }
+  const ov_plane::FramePlan p = ov_plane::frame_plan(n, keep, fresh.data(), slot.data(), free_list.data(), (int)free_list.size());
+  for (size_t k = 0; k < p.kept_index.size(); ++k) {
+    const int i = p.kept_index[k];
+    if (fresh[i]) d->slot_of.emplace(ids[i], p.slot[k]);
+    d->stamps[p.slot[k]].push_back(stamp);
+  }
+  d->free_slots.resize(d->free_slots.size() - (size_t)p.n_fresh_kept);
+  if (!p.kept_index.empty()) ++d->version;  // (ovp_featdb_append of no points changes nothing either)
 }
 
 extern "C" int ovp_featdb_mark_deleted(ovp_ctx* c, int n, const int64_t* ids) {

@@ -20,6 +20,7 @@
 
 #include "k_fast.h"  // detection: k_fast_score_nms, k_fast_select, k_fast_subpix (ovp_klt_detect below)
 #include "k_epipolar.h"  // the epipolar check: the launches of k_epipolar.hip (ovp_klt_epipolar below)
+#include "k_klt_frame.h"  // the fused hand-over: k_klt_keep_append and the database's side of it (ovp_klt_match_frame below)
 
 namespace {
 
@@ -268,13 +269,19 @@ struct Klt {
   size_t res_cap = 0;
   int cur = 0, fed = 0;  // index of the current half; images fed since create / reset
   // timed mode (EV_IN0: in front of the halving, EV_LUT: between k_clahe_lut and k_clahe_apply)
-  enum { EV_EQ0, EV_EQ1, EV_PYR1, EV_TRK0, EV_TRK1, EV_DET, EV_EPI = EV_DET + 4, EV_IN0 = EV_EPI + 5, EV_LUT, EV_COUNT };
+  enum { EV_EQ0, EV_EQ1, EV_PYR1, EV_TRK0, EV_TRK1, EV_DET, EV_EPI = EV_DET + 4, EV_IN0 = EV_EPI + 5, EV_LUT, EV_FRM0, EV_FRM1, EV_COUNT };
   OvpEvent ev[EV_COUNT];
   bool timed = false;
   // equalise, pyramid launches together, k_klt_track, k_fast_score_nms, k_fast_select, k_fast_subpix, the four k_epi_* kernels, then
-  // the intake's halving, k_clahe_lut and k_clahe_apply
-  float ms[13] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  // the intake's halving, k_clahe_lut and k_clahe_apply, and behind them k_klt_keep_append
+  float ms[14] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int last_n = 0;
+  // ovp_klt_match_frame: the survivors the last call published (offsets into the mailbox's payload), good while the mailbox's
+  // sequence number is still that call's
+  int frm_kept = -1;
+  unsigned frm_seq = 0;
+  bool frm_uvn = false;
+  size_t frm_uv_off = 0, frm_uvn_off = 0;
 };
 
 Klt* klt_of(ovp_ctx* c) { return c ? (Klt*)c->klt.get() : nullptr; }
@@ -716,6 +723,195 @@ extern "C" int ovp_klt_epipolar(ovp_ctx* c, const ovp_epipolar_opts* o, int n, c
   return 0;
 }
 
+// what ovp_klt_epipolar refuses in its options.  A second statement of that entry's own checks (the lines behind its "every check"
+// comment), because the entry itself stays as it is: a rule added there is added here, and
+// tests/test_klt_frame_gpu.py::test_option_refusals_equal_the_epipolar_entrys holds the two to the same verdict option by option.
+static bool klt_epi_opts_ok(const ovp_epipolar_opts* o) {
+  if (o->mode != OVP_EPI_MODE_NORMALISED && o->mode != OVP_EPI_MODE_RADTAN && o->mode != OVP_EPI_MODE_EQUIDISTANT) return false;
+  if (!(o->threshold > 0.0) || !std::isfinite(o->threshold) || !(o->confidence > 0.0 && o->confidence < 1.0)) return false;
+  if (o->max_iters < 1 || o->max_iters > OVP_EPI_MAX_ITERS) return false;
+  for (double v : o->intrinsics)
+    if (!std::isfinite(v)) return false;
+  return o->mode == OVP_EPI_MODE_NORMALISED || (o->intrinsics[0] != 0.0 && o->intrinsics[1] != 0.0);
+}
+
+extern "C" int ovp_klt_match_frame(ovp_ctx* c, const ovp_klt_frame_in* in, ovp_klt_frame_out* out) {
+  Klt* d = klt_of(c);
+  if (!c || !in || !out) return OVP_E_ARG;
+  if (!d) return OVP_E_STATE;
+  // ---- every check before anything is touched or enqueued ----
+  const int n = in->n;
+  const bool check = in->check != 0, to_db = in->to_database != 0;
+  if (n < 0) return OVP_E_ARG;
+  if (d->fed < 2 || (to_db && !c->featdb)) return OVP_E_STATE;
+  if (n > d->max_points) return OVP_E_CAPACITY;
+  if (!in->epi && (check || to_db)) return OVP_E_ARG;
+  if (in->epi && !klt_epi_opts_ok(in->epi)) return OVP_E_ARG;
+  if (in->mask && in->mask_stride < d->width) return OVP_E_ARG;
+  if (to_db && !(in->timestamp == in->timestamp)) return OVP_E_ARG;
+  if (n == 0) {
+    out->n_kept = 0;
+    return 0;
+  }
+  if (!in->pts_prev || !in->ids) return OVP_E_ARG;
+  for (int i = 0; i < 2 * n; ++i)
+    if (!std::isfinite(in->pts_prev[i])) return OVP_E_ARG;
+  {
+    std::vector<int64_t> sorted(in->ids, in->ids + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return OVP_E_ARG;  // the ids of a frame are distinct
+  }
+  if (check && n < OVP_EPI_MIN_POINTS) {  // :1319-1323 all zeros, no KLT; nothing is kept and nothing appended
+    out->n_kept = 0;
+    if (out->keep) memset(out->keep, 0, n);
+    if (out->mask_epi) memset(out->mask_epi, 0, n);
+    memset(&out->info, 0, sizeof(out->info));
+    out->info.winner_h = out->info.winner_model = -1, out->info.too_few = 1;
+    return 0;
+  }
+  std::vector<int32_t> slot, free_list;
+  std::vector<unsigned char> fresh;
+  int n_fresh = 0;
+  FdbTable table = {};
+  if (to_db) {
+    slot.resize(n), free_list.resize(n), fresh.resize(n);
+    const int rp = ovp_featdb_frame_plan(c, in->timestamp, n, in->ids, slot.data(), fresh.data(), free_list.data(), &n_fresh, &table);
+    if (rp) return rp;
+  }
+  const size_t mask_bytes = in->mask ? (size_t)d->width * d->height : 0;
+  StageLayout L;
+  const size_t o_pts = L.take(sizeof(float) * 2 * n), o_id = L.take(sizeof(long long) * n), o_slot = L.take(sizeof(int) * n),
+               o_fresh = L.take(n), o_free = L.take(sizeof(int) * n), o_tab = L.take(sizeof(int) * (n + 1)), o_mask = L.take(mask_bytes);
+  StageLayout R;
+  const size_t r_out = R.take(sizeof(float) * 2 * n), r_st = R.take(n), r_mepi = R.take(n), r_uvn = R.take(sizeof(float) * 2 * n),
+               r_keep = R.take(n), r_idx = R.take(sizeof(int) * n), r_kuv = R.take(sizeof(float) * 2 * n),
+               r_kuvn = R.take(sizeof(float) * 2 * n), r_nk = R.take(sizeof(int)), r_info = R.take(sizeof(EpiInfoDev)),
+               r_u0 = R.take(sizeof(float) * 2 * n), r_it = R.take((size_t)n * KLT_MAX_LEVELS);
+  // ---- from here on the call goes through ----
+  HIPCHK(hipSetDevice(c->device));
+  // the first fused call (or the first with a mask) grows the staging - the mask's device buffer is its tail - and the result block
+  // to a frame's size at max_points, and waits for the stream once
+  {
+    StageLayout LM, RM;
+    const size_t m = (size_t)d->max_points;
+    LM.take(8 * m), LM.take(8 * m), LM.take(4 * m), LM.take(m), LM.take(4 * m), LM.take(4 * (m + 1)), LM.take(mask_bytes);
+    RM.take(8 * m), RM.take(m), RM.take(m), RM.take(8 * m), RM.take(m), RM.take(4 * m), RM.take(8 * m), RM.take(8 * m), RM.take(4),
+        RM.take(sizeof(EpiInfoDev)), RM.take(8 * m), RM.take(m * KLT_MAX_LEVELS);
+    HIPCHK(d->stage.reserve(LM.bytes(), 0, c->stream));
+    if (RM.bytes() > d->res_cap) {
+      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(d->dres.reserve(RM.bytes(), 0));
+      HIPCHK(d->hres.reserve(RM.bytes(), 0));
+      d->res_cap = RM.bytes(), d->last_n = 0;
+    }
+  }
+  int rc = 0;
+  char* h = d->stage.begin(L.bytes(), &rc);
+  if (!h) return rc;
+  memcpy(h + o_pts, in->pts_prev, sizeof(float) * 2 * n);
+  memcpy(h + o_id, in->ids, sizeof(long long) * n);
+  if (to_db) {
+    memcpy(h + o_slot, slot.data(), sizeof(int) * n);
+    memcpy(h + o_fresh, fresh.data(), n);
+    memcpy(h + o_free, free_list.data(), sizeof(int) * n_fresh);
+  }
+  std::vector<int32_t> table_it(n + 1, 0);
+  if (check) {
+    ovp_epi_table(n, in->epi->confidence, in->epi->max_iters, table_it.data());
+    memcpy(h + o_tab, table_it.data(), sizeof(int) * (n + 1));
+  }
+  for (int y = 0; in->mask && y < d->height; ++y) memcpy(h + o_mask + (size_t)y * d->width, in->mask + (size_t)y * in->mask_stride, d->width);
+  const char* dv = d->stage.dev();
+  char* dr = (char*)d->dres.get();
+  HIPCHK(d->stage.send(L.bytes(), c->stream, Fence::CallerWaits));
+  // :1326-1330 k_klt_track, its output stays on the device
+  KltTrackArgs a;
+  const unsigned char *pc = d->pyr[d->cur].get(), *pp = d->pyr[d->cur ^ 1].get();
+  for (int l = 0; l < KLT_MAX_LEVELS; ++l) {
+    const int q = l < d->n_levels ? l : 0;
+    a.prev[l] = pp + d->loff[q], a.cur[l] = pc + d->loff[q], a.w[l] = d->lw[q], a.h[l] = d->lh[q];
+  }
+  a.n_levels = d->n_levels, a.n = n, a.win = d->win;
+  a.pts = a.guess = (const float*)(dv + o_pts);  // :1329 the reference passes pts1 = pts0
+  a.out = (float*)(dr + r_out), a.status = (unsigned char*)(dr + r_st), a.iters = (unsigned char*)(dr + r_it);
+  if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_TRK0], c->stream));
+  const dim3 grid((n + 3) / 4), block(256);
+  const int npl = (d->win * d->win + 63) / 64;
+  if (npl <= 1) hipLaunchKernelGGL(k_klt_track<1>, grid, block, 0, c->stream, a);
+  else if (npl <= 2) hipLaunchKernelGGL(k_klt_track<2>, grid, block, 0, c->stream, a);
+  else if (npl <= 4) hipLaunchKernelGGL(k_klt_track<4>, grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL(k_klt_track<7>, grid, block, 0, c->stream, a);
+  HIPCHK(hipGetLastError());
+  if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_TRK1], c->stream));
+  // :1331-1350 the epipolar kernels on the device-resident points and status; without the check the undistortion alone
+  if (in->epi) {
+    const ovp_epipolar_opts* o = in->epi;
+    EpiLaunch e;
+    e.n = n, e.max_iters = o->max_iters, e.mode = o->mode, e.seed = o->seed;
+    for (int k = 0; k < 8; ++k) e.intr[k] = o->intrinsics[k];
+    e.thr2 = (float)(o->threshold * o->threshold);
+    e.pts0 = (const float*)(dv + o_pts), e.pts1 = (const float*)(dr + r_out), e.status = (const unsigned char*)(dr + r_st);
+    e.table = (const int*)(dv + o_tab);
+    e.samples = d->epi_samples.get(), e.n_models = d->epi_nmodels.get(), e.models = d->epi_models.get(), e.counts = d->epi_counts.get();
+    e.mask = (unsigned char*)(dr + r_mepi), e.uvn0 = (float*)(dr + r_u0), e.uvn1 = (float*)(dr + r_uvn), e.info = (EpiInfoDev*)(dr + r_info);
+    hipEvent_t ev_epi[5];
+    for (int k = 0; k < 5; ++k) ev_epi[k] = d->ev[Klt::EV_EPI + k];
+    e.ev = d->timed && check ? ev_epi : nullptr;
+    if (d->timed && !check) HIPCHK(hipEventRecord(ev_epi[0], c->stream));
+    const int rl = check ? ovp_epi_enqueue(e, c->stream) : ovp_epi_enqueue_undistort(e, c->stream);
+    if (rl) return rl;
+    if (d->timed && !check) HIPCHK(hipEventRecord(ev_epi[1], c->stream));
+  }
+  // :536-557 the keep rule, the survivors and database->update_feature
+  KltFrameArgs f = {};
+  f.n = n, f.cols = d->width, f.rows = d->height, f.to_db = to_db ? 1 : 0;
+  f.pts = (const float2*)(dr + r_out), f.mask_epi = (const unsigned char*)(dr + (check ? r_mepi : r_st));
+  f.uvn = in->epi ? (const float2*)(dr + r_uvn) : nullptr;
+  f.mask = in->mask ? (const unsigned char*)(dv + o_mask) : nullptr;
+  f.slot = (const int*)(dv + o_slot), f.fresh = (const unsigned char*)(dv + o_fresh), f.ids = (const long long*)(dv + o_id);
+  f.free_slots = (const int*)(dv + o_free), f.stamp = in->timestamp, f.t = table;
+  f.keep = (unsigned char*)(dr + r_keep), f.kept_index = (int*)(dr + r_idx), f.kept_uv = (float2*)(dr + r_kuv);
+  f.kept_uvn = (float2*)(dr + r_kuvn), f.n_kept = (int*)(dr + r_nk);
+  if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_FRM0], c->stream));
+  const int rf = ovp_klt_frame_enqueue(f, c->stream);
+  if (rf) return rf;
+  if (d->timed) HIPCHK(hipEventRecord(d->ev[Klt::EV_FRM1], c->stream));
+  SeqChannel& ch = d->hres.channel(0);
+  const unsigned seq = ch.arm();
+  HIPCHK(ovp_launch_publish_block(dr, d->hres.dev(d->hres.payload()), r_u0, ch.word_dev(), seq, 0, c->stream));  // (up to the info block)
+  const int rw = ch.wait(c->stream);
+  if (rw) return rw;
+  d->stage.done();
+  if (d->timed) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipEventElapsedTime(&d->ms[2], d->ev[Klt::EV_TRK0], d->ev[Klt::EV_TRK1]));
+    // the epipolar slots are this call's: the four kernels with the check, the undistortion alone without it, zeros for what did not run
+    for (int k = 0; k < 4; ++k) d->ms[6 + k] = 0.0f;
+    for (int k = 0; in->epi && k < (check ? 4 : 1); ++k)
+      HIPCHK(hipEventElapsedTime(&d->ms[6 + k], d->ev[Klt::EV_EPI + k], d->ev[Klt::EV_EPI + k + 1]));
+    HIPCHK(hipEventElapsedTime(&d->ms[13], d->ev[Klt::EV_FRM0], d->ev[Klt::EV_FRM1]));
+  }
+  const char* hr = (const char*)d->hres.payload();
+  const unsigned char* keep = (const unsigned char*)(hr + r_keep);
+  const int n_kept = *(const int*)(hr + r_nk);
+  // the database's map and shadow follow the device: the same assignment, replayed over the published keep vector
+  if (to_db) ovp_featdb_frame_commit(c, in->timestamp, n, in->ids, keep);
+  out->n_kept = n_kept;
+  if (out->keep) memcpy(out->keep, keep, n);
+  if (out->pts_out) memcpy(out->pts_out, hr + r_out, sizeof(float) * 2 * n);
+  if (out->status) memcpy(out->status, hr + r_st, n);
+  if (out->mask_epi) memcpy(out->mask_epi, hr + (check ? r_mepi : r_st), n);
+  if (out->uvn && in->epi) memcpy(out->uvn, hr + r_uvn, sizeof(float) * 2 * n);
+  if (out->kept_index) memcpy(out->kept_index, hr + r_idx, sizeof(int) * (size_t)n_kept);
+  memset(&out->info, 0, sizeof(out->info));
+  out->info.winner_h = out->info.winner_model = -1;
+  if (check) memcpy(&out->info, hr + r_info, sizeof(out->info));
+  d->last_n = 0;  // (the mailbox no longer holds a track's iterations)
+  d->frm_kept = n_kept, d->frm_seq = seq, d->frm_uvn = in->epi != nullptr, d->frm_uv_off = r_kuv, d->frm_uvn_off = r_kuvn;
+  if (check) d->epi_H = in->epi->max_iters, d->epi_table.swap(table_it);
+  return 0;
+}
+
 extern "C" long ovp_klt_debug(ovp_ctx* c, const char* what, int level, void* out, long cap) {
   Klt* d = klt_of(c);
   if (!d) return c ? OVP_E_STATE : OVP_E_ARG;
@@ -750,9 +946,17 @@ extern "C" long ovp_klt_debug(ovp_ctx* c, const char* what, int level, void* out
     return 0;
   }
   if (!strcmp(what, "time")) {
-    if (cap < (long)(3 * sizeof(float))) return OVP_E_ARG;  // [3] of the tracker alone, [6] with the detector's kernels, .. [13]
+    if (cap < (long)(3 * sizeof(float))) return OVP_E_ARG;  // [3] of the tracker alone, [6] with the detector's kernels, .. [14]
     const size_t bytes = std::min((size_t)cap / sizeof(float), sizeof(d->ms) / sizeof(float)) * sizeof(float);
     memcpy(out, d->ms, bytes);
+    return (long)bytes;
+  }
+  if (!strcmp(what, "frame_uv") || !strcmp(what, "frame_uvn")) {  // the compacted survivors of the last ovp_klt_match_frame
+    const bool un = what[8] == 'n';
+    if (d->frm_kept < 0 || d->hres.channel(0).armed() != d->frm_seq || (un && !d->frm_uvn)) return OVP_E_STATE;
+    const size_t bytes = sizeof(float) * 2 * (size_t)d->frm_kept;
+    if ((size_t)cap < bytes) return OVP_E_ARG;
+    if (bytes) memcpy(out, (const char*)d->hres.payload() + (un ? d->frm_uvn_off : d->frm_uv_off), bytes);
     return (long)bytes;
   }
   if (!strcmp(what, "refine")) {  // k_fast_subpix on `level` points of the caller's: out holds float [2n] starts, then float [2n]

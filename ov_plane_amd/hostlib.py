@@ -508,6 +508,41 @@ def run_klt_epipolar_sequence(frames, mask, ids, uv, camera, max_iters=1000, see
                  reset=bool(reset[f])) for f in range(K)]
 
 
+def run_klt_frame_sequence(frames, mask, ids, uv, camera, times, check=True, max_iters=1000, seed=0, max_slots=64, max_meas=8,
+                           pyr_levels=5, win=15, hist="HISTOGRAM", device=0):
+    """ov_plane::TrackPlane::feed_monocular over the fused entry (ovp_klt_match_frame) with a FeatureDatabase attached: frames
+    [K, h, w] at times [K], one mask, the points added behind the first frame with their first observation; camera: (mode 0 / 1 / 2,
+    intrinsics [8]).  Returns (a list of K dicts(ids, pts, uv_norm, reset), the database's read-back {id: None or dict(slot, count,
+    ts, uv, uv_norm)})."""
+    L = lib()
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    K, h, w = fr.shape
+    mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(h, w)
+    id64 = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+    n = len(id64)
+    p = np.ascontiguousarray(uv, dtype=np.float32).reshape(n, 2)
+    intr = np.ascontiguousarray(camera[1], dtype=np.float64).reshape(8)
+    tm = np.ascontiguousarray(times, dtype=np.float64).reshape(K)
+    m, M = max(n, 1), int(max_meas)
+    n_kept, reset = np.zeros(K, dtype=np.int32), np.zeros(K, dtype=np.int32)
+    kept_ids, kept_uv, kept_uvn = np.zeros((K, m), dtype=np.int64), np.zeros((K, m, 2), dtype=np.float32), np.zeros((K, m, 2), dtype=np.float32)
+    slot, cnt = np.full(m, -1, dtype=np.int32), np.full(m, -1, dtype=np.int32)
+    ts, duv, duvn = np.zeros((m, M)), np.zeros((m, M, 2), dtype=np.float32), np.zeros((m, M, 2), dtype=np.float32)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    rc = L.ovph_run_klt_frame_sequence(C.c_int(device), C.c_int(w), C.c_int(h), C.c_int(K), vp(fr), vp(mk), vp(tm), C.c_int(pyr_levels),
+                                       C.c_int(win), C.c_int({"NONE": 0, "HISTOGRAM": 1, "CLAHE": 2}[hist]), C.c_int(n), vp(id64), vp(p),
+                                       C.c_int(int(camera[0])), vp(intr), C.c_int(1 if check else 0), C.c_int(max_iters), C.c_uint32(seed),
+                                       C.c_int(max_slots), C.c_int(M), vp(n_kept), vp(kept_ids), vp(kept_uv), vp(kept_uvn), vp(reset),
+                                       vp(slot), vp(cnt), vp(ts), vp(duv), vp(duvn))
+    if rc:
+        raise RuntimeError("ovph_run_klt_frame_sequence failed with %d" % rc)
+    per_frame = [dict(ids=kept_ids[f, :n_kept[f]].copy(), pts=kept_uv[f, :n_kept[f]].copy(), uv_norm=kept_uvn[f, :n_kept[f]].copy(),
+                      reset=bool(reset[f])) for f in range(K)]
+    db = {int(i): None if cnt[k] < 0 else dict(slot=int(slot[k]), count=int(cnt[k]), ts=ts[k, :cnt[k]].copy(), uv=duv[k, :cnt[k]].copy(),
+                                               uv_norm=duvn[k, :cnt[k]].copy()) for k, i in enumerate(id64)}
+    return per_frame, db
+
+
 def run_klt_detect_sequence(frames, mask, detector, pyr_levels=5, win=15, hist="HISTOGRAM", max_points=512, device=0):
     """ov_plane::TrackPlane's image half with its own detection (feed_new_camera(.., detect=True) from an empty tracker) on frames
     [K, h, w] uint8 with one mask [h, w] (None: none); detector: dict(num_features, grid_x, grid_y, threshold, min_px_dist).
