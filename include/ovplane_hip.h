@@ -1220,7 +1220,12 @@ long ovp_klt_debug(ovp_ctx *ctx, const char *what, int level, void *out, long ca
 
 /* ---- diagnostics ---------------------------------------------------------------------------- */
 /* copies an internal device buffer to host for tests: name in {"A","b","L","T","Lt","Y","G","rec","chi2",
- * "gramS","syrk"}; returns the byte count copied (or <0). */
+ * "gramS","syrk"}; returns the byte count copied (or <0).
+ * Of the last ovp_slam_update / ovp_slam_update_general (OVP_E_STATE before one), valid until the next call that uses the same
+ * scratch: "slam_cols" int32 [gcols], the call's column list; "slam_Ht" double [gcols][m_total], the stacked H^T (row g = state
+ * column slam_cols[g]); "slam_res" double [m_total]; "slam_M" double [n][m_total], M = P[:, columns] H^T, where the S-form ran
+ * (OVP_E_STATE behind the information form); "slam_dims" int32 [m_total, gcols, 1 where the S-form ran, 1 where the gate kept a
+ * landmark's block in LDS].  A call that fails before its gate leaves nothing to read (OVP_E_STATE). */
 long ovp_debug_read(ovp_ctx *ctx, const char *name, void *host, long max_bytes);
 /* like ovp_kernel_timer, for the dominant kernel of the plane loop (k_chol2: both factorizations, gate, solve and commit of one
  * plane): enable = 1: HIP events around every k_chol2 launch of ovp_msckf_plane_update AND around the whole loop; enable = 2: around

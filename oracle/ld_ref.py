@@ -11,6 +11,7 @@ feature), so it is the cross-check (tests/test_ld_ref_cpu.py), not the truth.
   chol / solve_lower / solve_upper / inv_spd / solve   the dense pieces (lower Cholesky, Gaussian elimination with pivoting)
   feature_pair                                         A_f = Hp^T Hp, b_f = Hp^T rp, |rp|^2 of one feature by the projector identity
   nullspace_rows                                       Hp, rp in a Householder basis of the left null space of H_f
+  householder_split                                    the same reflections with the top part kept: (H_L, H_R, res_L) and (Hp, rp)
   point_pair                                           the information pair of a set of point features, per-feature chi2 and dof
   update_from_pair                                     P+ = (I + P A)^-1 P = (P^-1 + A)^-1, dx = P+ b (no P^-1: singular priors too)
   update_from_pair_dropping                            the same on the pivot-dropping factor of A (the device's S-form retry)
@@ -109,8 +110,27 @@ def feature_pair(H_f, H_x, res):
     return sym(A), b, rr
 
 
+def householder_split(H_f, H_x, res):
+    """((H_L, H_R, res_L), (Hp, rp)): [H_f | H_x | res] under the Householder reflections that make H_f upper triangular.  The top
+    cols(H_f) rows are the system that initialises the feature (UpdaterHelper / StateHelper::initialize: H_L [nf, nf] upper
+    triangular, H_R, res_L), the bottom rows are the update rows nullspace_rows returns.  The basis is one of many (the reference
+    takes Givens rotations; any orthogonal Q = diag(Q1, Q2) in front of the two parts is as good).  These do NOT depend on it:
+    H_L^-1 res_L and H_L^-1 H_R (Q1 cancels), hence the initial value's correction, P_LL = H_L^-1 (H_R P H_R^T + I) H_L^-T and the
+    cross block -P H_R^T H_L^-T; Hp^T Hp, Hp^T rp and |rp|^2 (Q2 cancels), hence the chi2 of the bottom rows, dx and P+ of the
+    update with them (tests/test_ld_ref_cpu.py holds each against the oracle's Givens split)."""
+    nf = np.asarray(H_f).shape[1]
+    Hf, Hx, r = _householder(H_f, H_x, res)
+    return (np.triu(Hf[:nf]), Hx[:nf], r[:nf]), (Hx[nf:], r[nf:])
+
+
 def nullspace_rows(H_f, H_x, res):
     """(Hp, rp): [H_x | res] in a Householder basis of the left null space of H_f (rows - cols(H_f) rows)."""
+    nf = np.asarray(H_f).shape[1]
+    _, Hx, r = _householder(H_f, H_x, res)
+    return Hx[nf:], r[nf:]
+
+
+def _householder(H_f, H_x, res):
     Hf, Hx, r = np.array(H_f, dtype=LD), np.array(H_x, dtype=LD), np.array(res, dtype=LD)
     nf = Hf.shape[1]
     for k in range(nf):
@@ -124,7 +144,7 @@ def nullspace_rows(H_f, H_x, res):
         Hf[k:] -= np.outer(v, (2 / vv) * (v @ Hf[k:]))
         Hx[k:] -= np.outer(v, (2 / vv) * (v @ Hx[k:]))
         r[k:] -= v * ((2 / vv) * (v @ r[k:]))
-    return Hx[nf:], r[nf:]
+    return Hf, Hx, r
 
 
 def point_pair(sc, feats=None, P=None, with_chi2=True):

@@ -943,6 +943,30 @@ extern "C" long ovp_debug_read(ovp_ctx* c, const char* name, void* host, long ma
     src = c->pl_stage.dev() + c->dinit_pltab_off;
     bytes = (size_t)8 * c->dinit_nplanes * sizeof(double);
   }
+  // what the last ovp_slam_update / _general left in its scratch: the stacked H^T [columns of the call][stacked rows], the stacked
+  // residual, M_all = P[:, columns] H^T [n][stacked rows] (S-form calls only: OVP_E_STATE behind the information form) and the
+  // call's column list (int32, row g of H^T = state column slam_cols[g]); valid until the next call that uses these buffers
+  else if (!strcmp(name, "slam_Ht")) { src = c->Hd; bytes = c->slam_dbg_cols.size() * c->slam_dbg_rows * sizeof(double); if (!src || !bytes) return OVP_E_STATE; }
+  else if (!strcmp(name, "slam_res")) { src = c->resd; bytes = (size_t)c->slam_dbg_rows * sizeof(double); if (!src || !bytes) return OVP_E_STATE; }
+  else if (!strcmp(name, "slam_M")) {
+    if (!c->slam_dbg_sform || c->slam_dbg_rows < 1) return OVP_E_STATE;
+    src = (double*)c->smallbuf + c->slam_dbg_M;
+    bytes = (size_t)c->slam_dbg_n * c->slam_dbg_rows * sizeof(double);
+  }
+  else if (!strcmp(name, "slam_dims")) {  // int32 [stacked rows, columns of the call, S-form ran, H of a block in LDS]
+    if (c->slam_dbg_rows < 1) return OVP_E_STATE;
+    if (max_bytes < 16) return OVP_E_ARG;
+    const int d[4] = {c->slam_dbg_rows, (int)c->slam_dbg_cols.size(), c->slam_dbg_sform ? 1 : 0, c->slam_dbg_h_in_lds};
+    memcpy(host, d, 16);
+    return 16;
+  }
+  else if (!strcmp(name, "slam_cols")) {
+    bytes = c->slam_dbg_cols.size() * sizeof(int);
+    if (!bytes) return OVP_E_STATE;
+    if ((long)bytes > max_bytes) bytes = (size_t)max_bytes;
+    memcpy(host, c->slam_dbg_cols.data(), bytes);
+    return (long)bytes;
+  }
   else if (!strcmp(name, "chi2")) {
     hipStreamSynchronize(c->stream);
     bytes = (size_t)c->n_feats * sizeof(double);

@@ -320,6 +320,19 @@ static int slam_tail_info(ovp_ctx* c, const SlamUpdatePlan& p, const ovp_slam_ba
   const int n = c->n, gcols = p.gcols, m_total = p.m_total;
   const int* dgid = (const int*)(c->pl_stage.dev() + st.gi);
   char* hl = (char*)c->pl_hres.payload() + st.res_doubles * sizeof(double);
+  // nothing accepted: no update at all (update/UpdaterSLAM.cpp:661-663) - the information form of an empty stack would still
+  // rewrite the covariance as chol(P) chol(P)^T, equal to P only to rounding.  The statuses decide it, so they are fetched first.
+  HIPCHK(hipMemcpyAsync(hl, c->slam_res, st.lres_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  {
+    bool any = false;
+    for (int l = 0; l < p.L; ++l) any = any || ((const unsigned char*)(hl + st.status))[l] != 0;
+    if (!any) {
+      c->pl_stage.done();
+      slam_finish_landmarks(p, b, hl, st.status, out);
+      return 0;
+    }
+  }
   HIPCHK(c->Acc.alloc((size_t)c->n_max * c->n_max));
   HIPCHK(c->bcc.alloc((size_t)c->n_max));
   HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 4, s));
@@ -337,7 +350,6 @@ static int slam_tail_info(ovp_ctx* c, const SlamUpdatePlan& p, const ovp_slam_ba
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(c->h_dx, c->dx, sizeof(double) * n, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(c->h_flags, c->flags, sizeof(int) * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(hl, c->slam_res, st.lres_bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   c->pl_stage.done();
   slam_finish_landmarks(p, b, hl, st.status, out);
@@ -359,6 +371,10 @@ static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam
   drop_kept_factor(c);  // (writes the covariance: a kept factor no longer belongs to it)
   if (!c || !o || !b || b->n_landmarks < 0) return OVP_E_ARG;
   if (!c->have_state || !c->have_cov) return OVP_E_STATE;
+  c->slam_dbg_rows = 0;  // (a call that fails before its gate leaves nothing for ovp_debug_read "slam_*")
+  c->slam_dbg_sform = false;
+  c->slam_dbg_h_in_lds = 0;
+  c->slam_dbg_cols.clear();
   const int L = b->n_landmarks;
   if (out.info) memset(out.info, 0, sizeof(*out.info));
   if (out.dx) memset(out.dx, 0, sizeof(double) * c->n);
@@ -375,6 +391,12 @@ static int slam_update_impl(ovp_ctx* c, const ovp_update_opts* o, const ovp_slam
   rc = slam_stage_upload(c, plan, b, cam_idx, &st);
   if (rc) return rc;
   const SlamScratch k = slam_scratch(c, plan, st);
+  c->slam_dbg_rows = plan.m_total;  // (what ovp_debug_read "slam_*" reads back)
+  c->slam_dbg_n = c->n;
+  c->slam_dbg_sform = k.sform;
+  c->slam_dbg_h_in_lds = plan.h_in_lds;
+  c->slam_dbg_M = (size_t)(k.M - (double*)c->smallbuf);
+  c->slam_dbg_cols = plan.gids;
   rc = slam_enqueue_gate(c, o, plan, st, k);
   if (rc) return rc;
   return k.sform ? slam_tail_sform(c, plan, b, st, k, out) : slam_tail_info(c, plan, b, st, out);

@@ -183,6 +183,13 @@ struct ovp_ctx {
   DevBuf<double> dinit_buf;        // ovp_slam_delayed_init: result blocks + shared scratch of the candidate loop
   size_t dinit_pltab_off = 0;      // ovp_slam_delayed_init_planes: the plane table of the last call inside pl_stage (debug read)
   int dinit_nplanes = 0;
+  // ovp_slam_update: shape of what the last call left in Hd / resd / smallbuf (debug reads "slam_Ht", "slam_res", "slam_M",
+  // "slam_cols", "slam_dims"); sform: the S-form ran, so M_all stands at slam_dbg_M (doubles into smallbuf), [n][m_total];
+  // h_in_lds: the gate kept a landmark's block in LDS.  Zero from the entry of a call until its plan and staging have succeeded.
+  int slam_dbg_rows = 0, slam_dbg_n = 0, slam_dbg_h_in_lds = 0;
+  bool slam_dbg_sform = false;
+  size_t slam_dbg_M = 0;
+  std::vector<int> slam_dbg_cols;
   int calib_id = -1, intr_id = -1;
   DevBuf<long long> dbg_cycles;
   // plane path

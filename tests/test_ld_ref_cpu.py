@@ -80,6 +80,50 @@ def test_projector_pair_equals_the_householder_and_the_givens_pair():
         assert np.abs(ld_ref.ld(Hg.T @ rg) - Hp.T @ rp).max() <= 1e-14 * s * max(1.0, float(np.sqrt(rr)))
 
 
+def _givens_split(H_f, H_x, res):
+    """the reference's rotations (np_ref.nullspace_project_inplace) with the top rows kept: (H_L, H_R, res_L), (Hp, rp)"""
+    H_f, H_x, res = H_f.copy(), H_x.copy(), res.copy().reshape(-1, 1)
+    nf = H_f.shape[1]
+    for n in range(nf):
+        for m in range(H_f.shape[0] - 1, n, -1):
+            c, s = np_ref.make_givens(H_f[m - 1, n], H_f[m, n])
+            for M, c0 in ((H_f, n), (H_x, 0), (res, 0)):
+                np_ref._rot2(M, m - 1, c, s, c0)
+    return (np.triu(H_f[:nf]), H_x[:nf], res[:nf, 0]), (H_x[nf:], res[nf:, 0])
+
+
+def test_householder_split_invariants_against_the_givens_split():
+    """What ld_ref.householder_split names as independent of the basis, against the oracle's Givens split in double: H_L^-1 res_L,
+    H_L^-1 H_R, P_LL, the cross block, the chi2 of the bottom rows, and dx / P+ of the update with them.  Tolerances: the double
+    split's own rounding, 1e-12 relative to each quantity's largest element (kappa(H_L) of a 2- to 9-observation feature times
+    a few hundred roundings)."""
+    sc = make_scene(C=9, F=8, seed=5, ragged=True, min_meas=2)
+    P = ld_ref.ld(sc.P)
+    rel = lambda a, b: float(np.abs(ld_ref.ld(a) - b).max() / max(float(np.abs(b).max()), 1e-300))  # noqa: E731
+    for f in range(sc.F):
+        H_f, H_x, res, order = np_ref.feature_jacobian_full(sc, f)
+        cols = np_ref.order_cols(order)
+        (HL, HR, rL), (Hp, rp) = ld_ref.householder_split(H_f, H_x, res)
+        (gL, gR, grL), (gp, grp) = _givens_split(H_f, H_x, res)
+        assert np.abs(np.tril(HL, -1)).max() == 0 and HL.shape == (3, 3) and Hp.shape[0] == H_x.shape[0] - 3
+        Hp2, rp2 = ld_ref.nullspace_rows(H_f, H_x, res)
+        assert (Hp2 == Hp).all() and (rp2 == rp).all()
+        Li, gLi = ld_ref.solve_upper(HL, np.eye(3, dtype=ld_ref.LD)), np.linalg.inv(gL)
+        assert rel(gLi @ grL, Li @ rL) <= 1e-12 and rel(gLi @ gR, Li @ HR) <= 1e-12
+        t, _ = ld_ref.initialize_invertible(P, cols, HR, Li, np.eye(3))
+        g, _ = ld_ref.initialize_invertible(P, cols, gR, gLi, np.eye(3))
+        n = sc.N
+        assert rel(g[n:, n:], t[n:, n:]) <= 1e-12 and rel(g[:n, n:], t[:n, n:]) <= 1e-12
+        if Hp.shape[0] == 0:
+            continue
+        chi2 = lambda H, r: (lambda y: y @ y)(ld_ref.solve_lower(ld_ref.chol(ld_ref.sym(  # noqa: E731
+            ld_ref.ld(H) @ P[np.ix_(cols, cols)] @ ld_ref.ld(H).T + np.eye(len(r), dtype=ld_ref.LD))), ld_ref.ld(r)))
+        assert abs(chi2(gp, grp) - chi2(Hp, rp)) <= 1e-12 * max(1.0, float(chi2(Hp, rp)))
+        Pt, dxt = ld_ref.ekf_update_dense(P, cols, Hp, rp)
+        Pg, dxg = ld_ref.ekf_update_dense(P, cols, gp, grp)
+        assert rel(dxg, dxt) <= 1e-11 and ld_ref.rel_p(Pg, Pt) <= 1e-12
+
+
 @pytest.mark.parametrize("kw", [
     dict(C=7, F=24, seed=31, chi2_mult=1.0),
     dict(C=5, F=20, seed=32, ragged=True, min_meas=2, chi2_mult=1.0),

@@ -14,7 +14,11 @@ e_dev <= max(K * e_f64, floor), and e_dev stays below a hard ceiling far under t
   (c) the dense entry point ovp_ekf_update around the S-form row limit, both forms, and above the tile limit.
 
 K and the floors come from the first MI355X run: OBSERVED at the end of this file holds the error seen for every stage, the
-bound is HEADROOM (4x) over it."""
+bound is HEADROOM (4x) over it.
+
+The SLAM landmark update (ovp_slam_update, ovp_slam_update_general: rows, gate, M, S-form tail) is held to the same truth with
+bounds counted in roundings in tests/test_slam_precision_gpu.py (cases and derivations: tests/slam_precision_cases.py, the
+long-double rows: tests/slam_ref.py, the bounds on the CPU: tests/test_slam_precision_cpu.py)."""
 import numpy as np
 import pytest
 
