@@ -1225,7 +1225,12 @@ long ovp_klt_debug(ovp_ctx *ctx, const char *what, int level, void *out, long ca
  * scratch: "slam_cols" int32 [gcols], the call's column list; "slam_Ht" double [gcols][m_total], the stacked H^T (row g = state
  * column slam_cols[g]); "slam_res" double [m_total]; "slam_M" double [n][m_total], M = P[:, columns] H^T, where the S-form ran
  * (OVP_E_STATE behind the information form); "slam_dims" int32 [m_total, gcols, 1 where the S-form ran, 1 where the gate kept a
- * landmark's block in LDS].  A call that fails before its gate leaves nothing to read (OVP_E_STATE). */
+ * landmark's block in LDS].  A call that fails before its gate leaves nothing to read (OVP_E_STATE).
+ * "point_route": the route the last ovp_msckf_update / ovp_msckf_build_gate_gram_async planned (OVP_E_STATE before one), int32
+ * [feature launch: 0 fused with chol(P) in workgroup 0, 1 fused shape with workgroup 0 idle, 2 one wave per feature | chol(P): 0 none
+ * (the plane loop's factor), 1 workgroup 0, 2 side stream, 3 main stream behind the feature launch | second half: 0 tile kernels,
+ * 1 sub-state, 2 global-memory fallback | reversed-order factor | leading block of T | diagonal entries boosted | features that own
+ * rows | sub-state columns]; touches no stream. */
 long ovp_debug_read(ovp_ctx *ctx, const char *name, void *host, long max_bytes);
 /* like ovp_kernel_timer, for the dominant kernel of the plane loop (k_chol2: both factorizations, gate, solve and commit of one
  * plane): enable = 1: HIP events around every k_chol2 launch of ovp_msckf_plane_update AND around the whole loop; enable = 2: around

@@ -7,7 +7,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["ovp_api_ctx.hip", "ovp_api_point.hip", "ovp_api_rccl.hip", "ovp_api_plane.hip", "ovp_api_slam.hip", "ovp_api_general.hip", "k_feat.hip", "k_gram.hip", "k_ekf.hip", "k_init.hip", "k_tile.hip", "k_chol2.hip", "k_plane.hip", "k_plane2.hip", "k_triang.hip", "k_planefit.hip", "k_slam.hip", "k_dinit.hip", "k_feat_gen.hip", "k_plane_feat_gen.hip", "k_plane_detect.hip", "k_delaunay.hip", "k_plane_init2.hip", "k_publish.hip", "k_active_tracks.hip", "k_retire.hip", "k_zupt.hip", "k_propagate.hip", "k_klt.hip", "k_epipolar.hip", "k_featdb.hip", "k_klt_frame.hip"]
-HEADERS = ["ovp_ctx.h", "ovp_buf.h", "ovp_mailbox.h", "ovp_staged.h", "ovp_dev.h", "ovp_kernels.h", "ovp_feat_model.h", "ovp_lds_sizes.h", "ovp_slam_plan.h", "k_chol2.h", "k_plane2.h", "k_tile_body.h", "k_dpp.h", "k_slam.h", "k_slam_body.h", "k_dinit.h", "k_dinit_body.h", "k_init_body.h", "k_plane_gen.h", "k_plane_init2.h", "k_delaunay.h", "k_tri3.h", "k_fast.h", "k_clahe.h", "k_epipolar.h", "k_klt_frame.h", os.path.join("host", "ov_plane_delaunay.h"), os.path.join("host", "ov_plane_frame_plan.h"), os.path.join("..", "..", "include", "ovplane_hip.h")]
+HEADERS = ["ovp_ctx.h", "ovp_buf.h", "ovp_mailbox.h", "ovp_staged.h", "ovp_dev.h", "ovp_kernels.h", "ovp_feat_model.h", "ovp_lds_sizes.h", "ovp_slam_plan.h", "ovp_point_plan.h", "k_chol2.h", "k_plane2.h", "k_tile_body.h", "k_dpp.h", "k_slam.h", "k_slam_body.h", "k_dinit.h", "k_dinit_body.h", "k_init_body.h", "k_plane_gen.h", "k_plane_init2.h", "k_delaunay.h", "k_tri3.h", "k_fast.h", "k_clahe.h", "k_epipolar.h", "k_klt_frame.h", os.path.join("host", "ov_plane_delaunay.h"), os.path.join("host", "ov_plane_frame_plan.h"), os.path.join("..", "..", "include", "ovplane_hip.h")]
 OUT = os.path.join(_HERE, "libovplane_hip.so")
 
 

@@ -1036,7 +1036,7 @@ extern "C" hipError_t ovp_launch_feat_gate(const ovp::FeatParams* p, hipStream_t
 // 1 if ovp_launch_feat_chol can take this batch / matrix (otherwise: ovp_launch_feat_gate + ovp_launch_tilechol)
 extern "C" int ovp_feat_chol_supported(const ovp::FeatParams* p, int n) {
   const int nt = (n + 15) >> 4;
-  return p->n_feats > 0 && p->max_meas <= 30 && nt <= OVP_TC_MAX_TILES;
+  return p->n_feats > 0 && p->max_meas <= OVP_FEAT_CHOL_MAX_MEAS && nt <= OVP_TC_MAX_TILES;
 }
 
 // features the fused-shape launch takes in ONE round while leaving a CU per XCD to a kernel on another stream

@@ -960,6 +960,14 @@ extern "C" long ovp_debug_read(ovp_ctx* c, const char* name, void* host, long ma
     memcpy(host, d, 16);
     return 16;
   }
+  // the plan of the last ovp_msckf_build_gate_gram_async (ovp_point_plan.h), int32 [K1 kind, place of chol(P), tail form, flip, nl,
+  // boost_n, Fa, sub_ns]; no stream is touched
+  else if (!strcmp(name, "point_route")) {
+    if (c->point_route[0] < 0) return OVP_E_STATE;
+    if (max_bytes < (long)sizeof(c->point_route)) return OVP_E_ARG;
+    memcpy(host, c->point_route, sizeof(c->point_route));
+    return (long)sizeof(c->point_route);
+  }
   else if (!strcmp(name, "slam_cols")) {
     bytes = c->slam_dbg_cols.size() * sizeof(int);
     if (!bytes) return OVP_E_STATE;

@@ -1123,8 +1123,8 @@ static int plane_cov_product(ovp_ctx* c, const PlaneLoopView& v, size_t tstride,
   if (v.scatter_dst) {
     HIPCHK(ovp_launch_unpermute_pair(c->P, c->Y, ld, v.scatter_ids, n, v.scatter_dst, want_factor ? c->Lkeep : nullptr, ld,
                                      c->flags, v.boost ? c->boost_vec : nullptr, s));
-    c->kept_boost = want_factor && v.boost;  // Lkeep is a factor of P + diag(boost_vec): the point update on it
-                                             // takes the amounts off at its end (ekf_from_gram)
+    c->kept.boost = want_factor && v.boost;  // Lkeep is a factor of P + diag(boost_vec): the point update on it
+                                             // takes the amounts off at its end (point_enqueue_tail)
   } else if (want_factor) {
     HIPCHK(ovp_launch_factor_from_V(c->Y, ld, nullptr, n, c->Lkeep, ld, s));
   }
@@ -1212,7 +1212,7 @@ static int plane_unpack(ovp_ctx* c, const PlaneLoopView& v, const PlaneGroups& g
   }
   if (bad & 2) return OVP_E_TIMEOUT;
   if (bad) return OVP_E_NOTSPD;
-  c->have_factor = factor_enqueued;
+  c->kept.have = factor_enqueued;
   return 0;
 }
 
@@ -1331,7 +1331,7 @@ static int plane_update_entry(ovp_ctx* c, const ovp_update_opts* o, const ovp_pl
   if (!c->have_state || !c->have_cov || !c->have_batch) return OVP_E_STATE;
   if (c->h_n_meas.empty() && c->n_feats > 0) return OVP_E_STATE;  // needs ovp_batch_upload (host copy of the layout)
   v.t_entry = host_now_ms();
-  c->have_factor = false;
+  c->kept.have = false;
   c->pl_used_valid = false;
   const int rcu = ensure_pl_used(c);
   if (rcu) return rcu;
@@ -1477,7 +1477,7 @@ extern "C" int ovp_plane_init_general(ovp_ctx* c, const ovp_update_opts* o, cons
     v.gen_used = marks.data();
   }
   const int rc = plane_update_ordered(c, o, &pbi, v, PlaneOut{dxp.data(), ok.data(), plane_chi2, plane_dof, feat_used});
-  c->have_factor = false;  // (the loop's factor is the n x n block's; the state has grown)
+  c->kept.have = false;  // (the loop's factor is the n x n block's; the state has grown)
   if (rc) {
     if (feat_used && F) memset(feat_used, 0, (size_t)F);
     for (int pl = 0; pl < NP; ++pl) {

@@ -1,6 +1,7 @@
 // C-ABI shim, part 2 (see ovp_ctx.h): the point update - UpdaterMSCKF::update downstream of the plane loop
 // (update/UpdaterMSCKF.cpp:671-814, state/StateHelper.cpp:121-202) and StateHelper::EKFUpdate with a dense host H.
 #include "ovp_ctx.h"
+#include "ovp_point_plan.h"
 
 // Results go to the host without a copy command: the last kernel of an update writes the result block into the pinned mirror
 // (c->h_res_block, a Mailbox) and then the sequence number of its channel 0; ovp_msckf_fetch_results waits on that channel.
@@ -23,38 +24,39 @@ int set_substate(ovp_ctx* c, const std::vector<int>& ids) {
   return 0;
 }
 
+// k_chol2 in mode 0: the dense lower-triangular factor of A (n x n, leading dimension ld for both) into Ldense
+static ovp::Chol2Job dense_chol2_job(const double* A, int n, int ld, int* flag, double* Ldense) {
+  ovp::Chol2Job j;
+  memset(&j, 0, sizeof(j));
+  j.A = A;
+  j.n = n;
+  j.ld = ld;
+  j.mode = 0;
+  j.flag = flag;
+  j.Ldense = Ldense;
+  j.ldo = ld;
+  return j;
+}
+
+// Positive SEMI-definite A (state/StateHelper.cpp:159-187 never factors P, so the reference updates such a covariance - right after
+// StateHelper::clone the newest pose is an exact copy, :346-396).  ANY factor with L0 L0^T = A serves the identities the updates
+// stand on (P_k = L0 (I + L0^T A_k L0)^-1 L0^T is the matrix inversion lemma, no inverse of P in it): the pivot-dropping Cholesky
+// of the unit-diagonal form, L0 = D Lc with zero columns where A determines nothing.  unit: n x n scratch, dvec: n doubles.
+static int pivot_dropping_factor(ovp_ctx* c, const double* A, int n, int ld, double* unit, double* dvec, double* Lout, hipStream_t s) {
+  HIPCHK(ovp_launch_unit_diag(A, n, ld, unit, dvec, s));
+  ovp::Chol2Job j = dense_chol2_job(unit, n, ld, c->flags, Lout);
+  j.piv_floor = 1e-12;  // regular pivots of the unit-diagonal form are >= 1 / cond (1e-8 at worst), dropped ones rounding noise
+  HIPCHK(ovp_launch_chol2(&j, nullptr, nullptr, s));
+  HIPCHK(ovp_launch_scale_rows(Lout, n, ld, dvec, s));
+  return 0;
+}
+
 int chol_of_P(ovp_ctx* c, hipStream_t s, bool psd) {
   const int n = c->n, ld = c->ld;
-  if (psd && n <= ovp_chol2_max_n() + 1) {
-    // Positive SEMI-definite prior (plane loop, second attempt: state/StateHelper.cpp:159-187 never factors P, so the reference
-    // updates such a covariance - right after StateHelper::clone the newest pose is an exact copy, :346-396).  ANY factor with
-    // L0 L0^T = P serves the loop (P_k = L0 (I + L0^T A L0)^-1 L0^T is the matrix inversion lemma, no inverse of P in it): the
-    // pivot-dropping Cholesky of the unit-diagonal form, L0 = D Lc with zero columns where P determines nothing.
-    HIPCHK(ovp_launch_unit_diag(c->P, n, ld, c->W1, c->pl_crow, s));
-    ovp::Chol2Job j;
-    memset(&j, 0, sizeof(j));
-    j.A = c->W1;
-    j.n = n;
-    j.ld = ld;
-    j.mode = 0;
-    j.flag = c->flags;
-    j.piv_floor = 1e-12;  // regular pivots of the unit-diagonal form are >= 1 / cond (1e-8 at worst), dropped ones rounding noise
-    j.Ldense = c->L;
-    j.ldo = ld;
-    HIPCHK(ovp_launch_chol2(&j, nullptr, nullptr, s));
-    HIPCHK(ovp_launch_scale_rows(c->L, n, ld, c->pl_crow, s));
-    return 0;
-  }
+  if (psd && n <= ovp_chol2_max_n() + 1)  // (plane loop, second attempt)
+    return pivot_dropping_factor(c, c->P, n, ld, c->W1, c->pl_crow, c->L, s);
   if (n <= ovp_chol2_max_n() + 1) {  // dense factor from the second-generation kernel
-    ovp::Chol2Job j;
-    memset(&j, 0, sizeof(j));
-    j.A = c->P;
-    j.n = n;
-    j.ld = ld;
-    j.mode = 0;
-    j.flag = c->flags;
-    j.Ldense = c->L;
-    j.ldo = ld;
+    const ovp::Chol2Job j = dense_chol2_job(c->P, n, ld, c->flags, c->L);
     return (int)ovp_launch_chol2(&j, nullptr, nullptr, s);
   }
   if (n <= OVP_TILECHOL_NMAX) return (int)ovp_launch_tilechol(c->P, c->L, nullptr, nullptr, n, ld, c->flags, 0, s);
@@ -81,20 +83,9 @@ static int ekf_substate(ovp_ctx* c, bool psd = false) {
   // Pss+ = Ls (I + Ls^T A Ls)^-1 Ls^T exactly as the full-state path does it
   if (psd) {
     // second attempt behind a failed chol(Pss): positive SEMI-definite prior (an exact stochastic clone) - any factor with
-    // Ls Ls^T = Pss serves the identity above; the pivot-dropping Cholesky of the unit-diagonal form (cf. chol_of_P)
-    HIPCHK(ovp_launch_unit_diag(S_P, ns, lds, S_W, c->dx, s));
-    ovp::Chol2Job j;
-    memset(&j, 0, sizeof(j));
-    j.A = S_W;
-    j.n = ns;
-    j.ld = lds;
-    j.mode = 0;
-    j.flag = c->flags;
-    j.piv_floor = 1e-12;
-    j.Ldense = S_L;
-    j.ldo = lds;
-    HIPCHK(ovp_launch_chol2(&j, nullptr, nullptr, s));
-    HIPCHK(ovp_launch_scale_rows(S_L, ns, lds, c->dx, s));
+    // Ls Ls^T = Pss serves the identity above
+    const int rp = pivot_dropping_factor(c, S_P, ns, lds, S_W, c->dx, S_L, s);
+    if (rp) return rp;
   } else {
     HIPCHK(ovp_launch_tilechol(S_P, S_L, nullptr, nullptr, ns, lds, c->flags, 0, s));
   }
@@ -115,74 +106,62 @@ static int ekf_substate(ovp_ctx* c, bool psd = false) {
   return 0;
 }
 
-int ekf_from_gram(ovp_ctx* c, bool chol_p_done_on_stream2, bool publish) {
+// The update's last kernel: dx = P+ b, the boost amounts off the diagonal, the negative-diagonal check.  publish: its last block
+// also writes [flags | dx] into the pinned host block and posts channel 0 (no separate launch, no copy command).
+static int point_publish_dx(ovp_ctx* c, const double* boost, int boost_n, const int* cancel, bool publish) {
+  const int n = c->n;
+  const double* b = c->Ab + (size_t)n * c->ld;
+  if (!publish)
+    return (int)ovp_launch_dx_rows_boost(c->P, n, c->ld, b, c->dx, c->flags + 1, nullptr, nullptr, nullptr, 0, nullptr, 0u, boost, boost_n,
+                                         cancel, c->stream);
+  const int words = (int)((16 + sizeof(double) * (size_t)n + 7) / 8);
+  SeqChannel& ch = c->h_res_block.channel(0);
+  const unsigned seq = ch.arm();
+  HIPCHK(ovp_launch_dx_rows_boost(c->P, n, c->ld, b, c->dx, c->flags + 1, c->ticket, c->res_block, c->h_res_block.dev(c->h_flags), words,
+                                  ch.word_dev(), seq, boost, boost_n, cancel, c->stream));
+  c->point.pub_armed = true;
+  return 0;
+}
+
+// The second half of an information-form update: the pair [A | b] is in c->Ab and the factor t names is on its way on c->stream.
+// Its form follows the state's size and the sub-state set_substate left in the context, for every caller alike; a PointPlan's
+// `tail` / `sub_ns` say beforehand what that will be (set_substate on the plan's column list) and are there for the read-back.
+static int point_enqueue_tail(ovp_ctx* c, const PointTail& t, bool publish) {
   const int n = c->n, ld = c->ld;
-  if (!chol_p_done_on_stream2) {
-    int rc = chol_of_P(c, c->stream);
-    if (rc) return rc;
-  } else {
-    if (c->need_join) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-  }
-  const double* b = c->Ab + (size_t)n * ld;
+  c->kept = KeptFactor();  // P is about to change
   if (n <= OVP_TILECHOL_NMAX) {
     // W1 = A L ;  T = I + L^T W1 ;  Lt = chol(T) (+ inverses of its diagonal blocks).  L: chol(P), or the dense factor the plane
-    // loop left (any M with M M^T = P gives P+ = M (I + M^T A M)^-1 M^T)
-    const bool kept = c->use_kept_factor;
-    const double* Lf = kept ? c->Lkeep : c->L;
-    // leading block of T (reversed-order factor of P, see ovp_build_gate_gram_tail): n when the factor is the plain one
-    const int nl = (!kept && chol_p_done_on_stream2 && c->point_nl > 0 && c->point_nl < n) ? c->point_nl : n;
-    // diagonal amounts to take off at the end: CholJob::boost of the reversed-order factor (the first point_boost_n columns), or -
-    // on the factor the plane loop left, which is a factor of P + diag(boost_vec) - the loop's own (all n entries, zero where none)
-    const double* boost_ptr = kept ? (c->kept_boost ? c->boost_vec : nullptr) : c->boost;
-    const int boost_n = kept ? (c->kept_boost ? n : 0) : (nl < n ? c->point_boost_n : 0);
-    c->kept_boost = false;
-    c->use_kept_factor = false;
-    c->point_nl = 0;
-    c->point_boost_n = 0;
-    c->have_factor = false;  // P is about to change
+    // loop left (any M with M M^T = P gives P+ = M (I + M^T A M)^-1 M^T); with the reversed-order factor T is the identity outside
+    // its leading nl columns
+    const double* Lf = t.factor ? t.factor : (const double*)c->L;
+    const int nl = t.nl > 0 ? t.nl : n;
     HIPCHK(ovp_launch_gemm4(0, 0, n, nl, n, c->Ab, ld, Lf, ld, c->W1, ld, 0, 0, c->stream));
     HIPCHK(ovp_launch_gemm4(1, 0, nl, nl, n, Lf, ld, c->W1, ld, c->T, ld, 1, 1, c->stream));
     HIPCHK(chol_of_T(c, c->T, nl, ld, 0, nullptr, c->stream));
     // V = Lt^-1 L^T ;  P+ = V^T V ;  dx = P+ b
-    HIPCHK(ovp_launch_fwdsub_lead(c->Ltp, c->Dinv, Lf, c->Y, n, ld, kept ? 1 : (nl < n ? 2 : 0), nl, c->stream));
+    HIPCHK(ovp_launch_fwdsub_lead(c->Ltp, c->Dinv, Lf, c->Y, n, ld, t.dense, nl, c->stream));
     // (skipped on the device when a factorization failed: the resident covariance then stays what it was, OVP_E_NOTSPD)
     HIPCHK(ovp_launch_gemm4c(1, 0, n, n, n, c->Y, ld, c->Y, ld, c->P, ld, 0, 1, c->flags, c->stream));
-    if (publish) {
-      // the last block of the dx kernel also publishes [flags | dx] to the pinned host block (no separate launch)
-      const int words = (int)((16 + sizeof(double) * (size_t)n + 7) / 8);
-      SeqChannel& ch = c->h_res_block.channel(0);
-      const unsigned seq = ch.arm();
-      HIPCHK(ovp_launch_dx_rows_boost(c->P, n, ld, b, c->dx, c->flags + 1, c->ticket, c->res_block, c->h_res_block.dev(c->h_flags), words,
-                                      ch.word_dev(), seq, boost_ptr, boost_n, c->flags, c->stream));
-      c->pub_pending = true;
-    } else {
-      HIPCHK(ovp_launch_dx_rows_boost(c->P, n, ld, b, c->dx, c->flags + 1, nullptr, nullptr, nullptr, 0, nullptr, 0u, boost_ptr, boost_n,
-                                      c->flags, c->stream));
-    }
-    return 0;
+    return point_publish_dx(c, t.boost, t.boost_n, c->flags, publish);
   }
   if (substate_ok(c)) {
     int rc = ekf_substate(c);
     if (rc) return rc;
-    if (publish) {
-      const int words = (int)((16 + sizeof(double) * (size_t)n + 7) / 8);
-      SeqChannel& ch = c->h_res_block.channel(0);
-      const unsigned seq = ch.arm();
-      HIPCHK(ovp_launch_dx_rows(c->P, n, ld, b, c->dx, c->flags + 1, c->ticket, c->res_block, c->h_res_block.dev(c->h_flags), words,
-                                ch.word_dev(), seq, c->stream));
-      c->pub_pending = true;
-    } else {
-      HIPCHK(ovp_launch_dx_rows(c->P, n, ld, b, c->dx, c->flags + 1, nullptr, nullptr, nullptr, 0, nullptr, 0u, c->stream));
-    }
-    return 0;
+    return point_publish_dx(c, nullptr, 0, nullptr, publish);
   }
   // large-state fallback when the measurements touch more than 288 columns: global-memory factorization
   HIPCHK(ovp_launch_gemm(0, 0, n, n, n, c->Ab, ld, c->L, ld, c->W1, ld, 0, c->stream));
   HIPCHK(ovp_launch_gemm(1, 0, n, n, n, c->L, ld, c->W1, ld, c->T, ld, 1, c->stream));
   HIPCHK(ovp_launch_chol(c->T, c->Lt, n, ld, c->flags, 0, c->stream));
   HIPCHK(ovp_launch_trsm_right_lt(c->L, c->Lt, c->Y, n, ld, c->stream));
-  HIPCHK(ovp_launch_cov_finish(c->Y, n, ld, b, c->P, ld, c->dx, c->flags + 1, c->stream));
+  HIPCHK(ovp_launch_cov_finish(c->Y, n, ld, c->Ab + (size_t)n * ld, c->P, ld, c->dx, c->flags + 1, c->stream));
   return 0;
+}
+
+// for the entries that bring a pair of their own (ovp_ekf_update's information form, ovp_slam_update): chol(P) on the main stream
+int ekf_from_gram(ovp_ctx* c, const PointTail& t) {
+  const int rc = chol_of_P(c, c->stream);
+  return rc ? rc : point_enqueue_tail(c, t, false);
 }
 
 // Update of a covariance that is positive SEMI-definite (an exact stochastic clone before the next propagation, a zero-variance
@@ -190,6 +169,18 @@ int ekf_from_gram(ovp_ctx* c, bool chol_p_done_on_stream2, bool publish) {
 //   P+ = P - P H^T (H P H^T + I)^-1 H P,   with H := La^T, La La^T = A the (pivot-dropping) Cholesky factor of the information
 // matrix of the batch - H^T H = A and H^T r = b is all the update depends on.  S = I + La^T P La is positive definite whatever P is.
 // Runs after a failed chol(P) (flags[0]): the pair [A | b] is still in c->Ab, P was not touched (ovp_launch_gemm4c cancel flag).
+// the retry's ending: dx = P+ b, correction and flags to the host, the flag words cleared for the next update
+static int sform_finish(ovp_ctx* c) {
+  hipStream_t s = c->stream;
+  const int rc = point_publish_dx(c, nullptr, 0, nullptr, false);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(c->h_dx, c->dx, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(c->h_flags, c->flags, sizeof(int) * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 4, s));
+  return 0;
+}
+
 int ekf_sform(ovp_ctx* c) {
   const int n = c->n, ld = c->ld;
   hipStream_t s = c->stream;
@@ -198,28 +189,14 @@ int ekf_sform(ovp_ctx* c) {
     if (!substate_ok(c) || c->sub_ns > ovp_chol2_max_n()) return OVP_E_NOTSPD;
     HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 4, s));
     const int rs = ekf_substate(c, true);
-    if (rs) return rs;
-    HIPCHK(ovp_launch_dx_rows(c->P, n, ld, c->Ab + (size_t)n * ld, c->dx, c->flags + 1, nullptr, nullptr, nullptr, 0, nullptr, 0u, s));
-    HIPCHK(hipMemcpyAsync(c->h_dx, c->dx, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(c->h_flags, c->flags, sizeof(int) * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 4, s));
-    return 0;
+    return rs ? rs : sform_finish(c);
   }
   HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 4, s));
   HIPCHK(hipMemsetAsync(c->W1, 0, sizeof(double) * (size_t)n * ld, s));
   HIPCHK(ovp_launch_max_diag(c->Ab, n, ld, c->smallbuf, s));
-  ovp::Chol2Job j;
-  memset(&j, 0, sizeof(j));
-  j.A = c->Ab;
-  j.n = n;
-  j.ld = ld;
-  j.mode = 0;
-  j.flag = c->flags + 3;
+  ovp::Chol2Job j = dense_chol2_job(c->Ab, n, ld, c->flags + 3, c->W1);  // La (lower triangular, zero columns where a pivot was dropped)
   j.piv_floor = 1e-13;  // directions that carry less than 1e-13 of the largest diagonal entry count as unobserved
   j.floor_scale = c->smallbuf;
-  j.Ldense = c->W1;     // La (lower triangular, zero columns where a pivot was dropped)
-  j.ldo = ld;
   HIPCHK(ovp_launch_chol2(&j, nullptr, nullptr, s));
   HIPCHK(ovp_launch_gemm4(0, 0, n, n, n, c->P, ld, c->W1, ld, c->Y, ld, 0, 0, s));   // Wm = P La
   HIPCHK(ovp_launch_gemm4(1, 0, n, n, n, c->W1, ld, c->Y, ld, c->T, ld, 1, 1, s));   // S = I + La^T Wm
@@ -227,28 +204,7 @@ int ekf_sform(ovp_ctx* c) {
   HIPCHK(ovp_launch_fwdsub(c->Ltp, c->Dinv, c->Y, c->L, n, ld, 1, s));               // V = Ls^-1 Wm^T
   HIPCHK(ovp_launch_gemm4(1, 0, n, n, n, c->L, ld, c->L, ld, c->T, ld, 0, 1, s));    // V^T V
   HIPCHK(ovp_launch_sub_sym(c->P, c->T, n, ld, s));
-  HIPCHK(ovp_launch_dx_rows(c->P, n, ld, c->Ab + (size_t)n * ld, c->dx, c->flags + 1, nullptr, nullptr, nullptr, 0, nullptr, 0u, s));
-  HIPCHK(hipMemcpyAsync(c->h_dx, c->dx, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(c->h_flags, c->flags, sizeof(int) * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 4, s));
-  return 0;
-}
-
-int fill_feat_params(ovp_ctx* c, const ovp_update_opts* o);
-static int ovp_build_gate_gram_tail(ovp_ctx* c, int n, int F);
-
-extern "C" int ovp_msckf_build_gate_gram_async(ovp_ctx* c, const ovp_update_opts* o) {
-  if (!c || !o) return OVP_E_ARG;
-  if (!c->have_state || !c->have_cov || !c->have_batch) return OVP_E_STATE;
-  if (c->fp.n_clones < 1) return OVP_E_STATE;
-  const int n = c->n, F = c->n_feats;
-  {
-    int rc = fill_feat_params(c, o);
-    if (rc) return rc;
-  }
-  // (the flag words were cleared by the previous ovp_msckf_fetch_results, or at creation)
-  return ovp_build_gate_gram_tail(c, n, F);
+  return sform_finish(c);
 }
 
 int fill_feat_params(ovp_ctx* c, const ovp_update_opts* o) {
@@ -286,193 +242,167 @@ int fill_feat_params(ovp_ctx* c, const ovp_update_opts* o) {
   return 0;
 }
 
-static int build_gate_gram_tail_impl(ovp_ctx* c, int n, int F);
-static int ovp_build_gate_gram_tail(ovp_ctx* c, int n, int F) {
-  const int rc = build_gate_gram_tail_impl(c, n, F);
-  if (rc && c->need_join) {
-    // a failing exit behind the fork of chol(P): the main stream waits for the side stream before anything else is enqueued on it
-    // (the regular join sits in ekf_from_gram, which a failed build never reaches)
+// ---- the first half: plan (ovp_point_plan.h), then enqueue by stages ---------------------------------------------------------------
+// the three switches of the point update; read per call: the tests flip them inside one process
+static PointSwitches point_switches() {
+  PointSwitches sw;
+  const char* overlap_env = getenv("OVP_OVERLAP_MODE");
+  sw.overlap = overlap_env ? atoi(overlap_env) : 0;
+  sw.no_flip = getenv("OVP_POINT_NO_FLIP") != nullptr;
+  sw.no_boost = getenv("OVP_POINT_NO_BOOST") != nullptr;
+  return sw;
+}
+
+// what the planner reads: the context, and the options as fill_feat_params left them in c->fp
+static PointEnv point_env(ovp_ctx* c) {
+  PointEnv e;
+  e.n = c->n, e.F = c->n_feats, e.max_meas = c->max_meas;
+  e.clone_id = c->h_clone_id.data(), e.n_clones = (int)c->h_clone_id.size();
+  e.calmask = c->fp.calmask, e.calib_id = c->calib_id, e.intr_id = c->intr_id;
+  e.dense_cols = c->dense_cols.data(), e.n_dense = (int)c->dense_cols.size();
+  e.range_lo = c->range_lo, e.range_hi = c->range_hi;
+  e.used = c->h_pl_used.data();
+  e.used_valid = c->fp.skip != nullptr && c->pl_used_valid && (int)c->h_pl_used.size() == e.F;
+  e.have_factor = c->kept.have && c->Lkeep, e.factor_boosted = c->kept.boost;
+  e.rows_per_chunk = c->rows_per_chunk, e.n_split = c->n_split;
+  e.tilechol_nmax = OVP_TILECHOL_NMAX, e.chol2_max_n = ovp_chol2_max_n();
+  e.fused_max_tiles = OVP_TC_MAX_TILES, e.fused_max_meas = OVP_FEAT_CHOL_MAX_MEAS;  // (what ovp_feat_chol_supported compares against)
+  e.side_capacity = ovp_feat_chol_side_capacity();
+  e.sw = point_switches();
+  return e;
+}
+
+static PointTail point_tail(ovp_ctx* c, const PointPlan& p) {
+  PointTail t;
+  if (p.chol_p == CHOLP_NONE) t.factor = c->Lkeep;
+  t.nl = p.nl, t.dense = p.dense;
+  t.boost = p.boost == BOOST_CHOL ? (const double*)c->boost : p.boost == BOOST_LOOP ? (const double*)c->boost_vec : nullptr;
+  t.boost_n = p.boost_n;
+  return t;
+}
+
+// From the fork on the side stream may hold work of the update; its regular join is the second half's (or, with K2 over there, the
+// end of the first).  A failing exit in between makes the main stream wait here, before anything else is enqueued on it.
+struct SideJoin {
+  ovp_ctx* c;
+  bool armed = false;
+  ~SideJoin() {
+    if (!armed) return;
     (void)hipEventRecord(c->ev_join, c->stream2);
     (void)hipStreamWaitEvent(c->stream, c->ev_join, 0);
-    c->need_join = false;
   }
-  return rc;
+};
+
+// order and boost of a chol(P) of this update (CholJob / Chol2Job share the fields)
+template <class Job>
+static void point_chol_order(ovp_ctx* c, const PointPlan& p, Job* j) {
+  j->flip = p.flip ? 1 : 0;
+  if (p.boost != BOOST_CHOL) return;
+  j->boost = c->boost;
+  j->boost_n = p.boost_n;
+  j->boost_rel = 1e-9;
 }
-static int build_gate_gram_tail_impl(ovp_ctx* c, int n, int F) {
-  ovp::FeatParams& fp = c->fp;
-  // Round 5: the features that are not part of this update - consumed by an accepted plane (skip mask), outside this rank's index
-  // range - no longer occupy rows of rec / G (they used to write 16 KB of zeros each, which K2 then read): the host knows both sets,
-  // numbers the others in batch order and K1 reads its slot from host-mapped memory at the start of the feature wave; K2 runs on Fa
-  // features.  Same sums over the same rows in the same order, the chunks / splits of K2 group fewer of them (A/B in round 5: point update 0.2445 -> 0.2375 ms at config 3).
-  int Fa = F;
-  {
-    const bool ranged = c->range_lo >= 0;
-    const bool masked = fp.skip != nullptr && c->pl_used_valid && (int)c->h_pl_used.size() == F;
-    if ((ranged || masked) && F > 0) {
-      const int lo = ranged ? c->range_lo : 0, hi = ranged ? (c->range_hi < F ? c->range_hi : F) : F;
-      int k = 0;
-      for (int f = 0; f < F; ++f) c->h_slot[f] = (f >= lo && f < hi && !(masked && c->h_pl_used[f])) ? k++ : -1;
-      Fa = k;
-      fp.slot = c->h_slot.dev();
-      fp.n_out = Fa;
-    }
-  }
-  if (n > OVP_TILECHOL_NMAX) {  // the columns a point-feature batch can touch: clones, and calibration when it is estimated
-    std::vector<int> ids;
-    for (int cid : c->h_clone_id)
-      for (int k = 0; k < 6; ++k) ids.push_back(cid + k);
-    if (fp.calmask & 0x3Fu)
-      for (int k = 0; k < 6; ++k) ids.push_back(c->calib_id + k);
-    if (fp.calmask & (0xFFu << 6))
-      for (int k = 0; k < 8; ++k) ids.push_back(c->intr_id + k);
-    for (int dc : c->dense_cols) ids.push_back(dc);
-    std::sort(ids.begin(), ids.end());
-    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-    int rs = set_substate(c, ids);
-    if (rs) return rs;
-  }
-  // chol(P) does not depend on the measurements.  Default (mode 3): it rides in workgroup 0 of the fused feature kernel, on a
-  // CU of its own, and is hidden behind the features; K2 follows on the main stream and nothing forks or joins.
-  // Beside a one-wave-per-block K1 it must NOT run: K1 keeps every SIMD busy with two feature waves, and the CU that also
-  // hosts the eight Cholesky waves finishes its feature blocks ~40 % later, which is the kernel's duration (K1 112 -> 157 us).
-  // OVP_OVERLAP_MODE: 0 = no overlap, 1 = side stream beside K1, 2 = main stream after K1 with K2 beside it on the side
-  // stream (the fallback when the fused kernel cannot take the batch), 3 (default) = fused.  (Also tried: chol(P) as its own
-  // 160 KB-LDS launch on the side stream beside an 8-wave-workgroup K1 - the two launches did not overlap, K1 145 us.)
-  // Round 5, mode 4 (default up to 1976 features): the features keep the fused kernel's shape - eight feature waves per workgroup,
-  // each workgroup a CU of its own - but workgroup 0 factorizes nothing and returns at once; chol(P) runs as the second-generation
-  // kernel (k_chol2, mode 0, reversed order / diagonal boost as CholJob has them) on the side stream, on a CU the features leave
-  // free: 160 KB of LDS per feature workgroup keep the two off each other's SIMDs, and a round of 247 feature workgroups leaves a
-  // CU on EVERY XCD (ovp_launch_feat_chol) - with 255 the side kernel's workgroup finds no CU on the XCD it is sent to and the
-  // launches serialise (config 2, 2000 features: 316 against 274 us per update, measured), so above 1976 features mode 3 stays.
-  // Closed-loop session (11 clones, ~100 features): msckf update 0.276 -> 0.260 ms per frame.
-  const char* overlap_env = getenv("OVP_OVERLAP_MODE");  // (read per call: the tests switch it)
-  int overlap_mode = overlap_env ? atoi(overlap_env) : 4;
-  const bool fused_ok = c->n <= OVP_TILECHOL_NMAX && ovp_feat_chol_supported(&fp, c->n);
-  if (overlap_mode == 4 && !(fused_ok && c->n <= ovp_chol2_max_n() && F <= ovp_feat_chol_side_capacity())) overlap_mode = 3;
-  if (overlap_mode == 3 && !fused_ok) overlap_mode = 2;
-  c->need_join = (overlap_mode == 1 || overlap_mode == 2);
-  if (overlap_mode == 1) {
-    HIPCHK(hipEventRecord(c->ev_fork, c->stream));
-    HIPCHK(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-    int rc = chol_of_P(c, c->stream2);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(c->ev_join, c->stream2));
-  }
-  // K1.  Events on the main stream are kept to a minimum (each one costs microseconds between dependent kernels): with
-  // the kernel timer on, ev_k0 / ev_k1 bracket K1 and ev_k1 doubles as the fork point; otherwise one untimed fork event.
-  if (c->ktimer) HIPCHK(hipEventRecord(c->ev_k0, c->stream));
-  c->use_kept_factor = false;
-  c->point_nl = 0;
-  c->point_boost_n = 0;
-  if (overlap_mode == 3 || overlap_mode == 4) {
-    ovp::CholJob cj{c->P, c->L, nullptr, nullptr, c->n, c->ld, c->flags, 0, nullptr, 0, 0.0};
-    if (c->have_factor && c->Lkeep) {  // the plane loop left M with M M^T = P: no chol(P) (cj.n = 0), the update runs on M
-      cj.n = 0;
-      c->use_kept_factor = true;
-    } else {
-      // The batch's information matrix lives on the clones and the estimated calibration.  When everything in front of the first
-      // of those columns (the IMU block, dt) is untouched, the factor of P is taken in reversed index order: T = I + L^T A L is
-      // then the identity outside its leading n - s0 columns, and both products, chol(T) and the substitution shrink with it
-      // (config 2: 194 of 210 - 13 tile columns instead of 14) without a permutation of P.
-      const bool no_flip = getenv("OVP_POINT_NO_FLIP") != nullptr;  // (read per call: the tests switch it)
-      int s0 = c->n;
-      for (int cid : c->h_clone_id) s0 = cid < s0 ? cid : s0;
-      if (fp.calmask & 0x3Fu) s0 = c->calib_id < s0 ? c->calib_id : s0;
-      if (fp.calmask & (0xFFu << 6)) s0 = c->intr_id < s0 ? c->intr_id : s0;
-      for (int dc : c->dense_cols) s0 = dc < s0 ? dc : s0;  // (pending dense blocks may involve columns of their own: a second camera)
-      if (!no_flip && s0 >= 8 && s0 < c->n) {
-        cj.flip = 1;
-        c->point_nl = c->n - s0;
-        // the columns in front of the batch's take a relative diagonal boost inside the factorization that the end of the update
-        // takes off again (CholJob::boost): exact, and an exact stochastic clone (IMU pose == newest clone) factors on this path
-        const bool no_boost = getenv("OVP_POINT_NO_BOOST") != nullptr;  // (read per call: the tests switch it)
-        if (!no_boost && s0 <= 64) {
-          HIPCHK(c->boost.alloc(64));
-          cj.boost = c->boost;
-          cj.boost_n = s0;
-          cj.boost_rel = 1e-9;
-          c->point_boost_n = s0;
-        }
-      }
-    }
-    if (overlap_mode == 4 && cj.n > 0) {
-      ovp::Chol2Job j;
-      memset(&j, 0, sizeof(j));
-      j.A = c->P;
-      j.n = c->n;
-      j.ld = c->ld;
-      j.mode = 0;
-      j.flag = c->flags;
-      j.Ldense = c->L;
-      j.ldo = c->ld;
-      j.flip = cj.flip;
-      j.boost = cj.boost;
-      j.boost_n = cj.boost_n;
-      j.boost_rel = cj.boost_rel;
-      HIPCHK(hipEventRecord(c->ev_fork, c->stream));
-      c->need_join = true;  // (from here on the side stream may hold work: ovp_build_gate_gram_tail joins on a failing exit)
-      HIPCHK(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-      HIPCHK(ovp_launch_chol2(&j, nullptr, nullptr, c->stream2));
-      HIPCHK(hipEventRecord(c->ev_join, c->stream2));
-      cj.n = 0;
-    }
-    HIPCHK(ovp_launch_feat_chol(&fp, &cj, c->stream));
+
+// chol(P) outside the feature launch forks the side stream at fork_ev: as k_chol2 over there, in front of K1 (ev_join behind it) - or
+// on the main stream behind K1, and K2 goes over there (it is the shorter of the two branches: the join then never stalls the main
+// stream, and the cross-queue wake-up latency sits at the START of the side branch, off the critical path)
+static int point_enqueue_chol_p(ovp_ctx* c, const PointPlan& p, hipEvent_t fork_ev, SideJoin* side) {
+  HIPCHK(hipEventRecord(fork_ev, c->stream));
+  side->armed = true;
+  HIPCHK(hipStreamWaitEvent(c->stream2, fork_ev, 0));
+  if (p.chol_p == CHOLP_BEHIND_K1) return chol_of_P(c, c->stream);
+  ovp::Chol2Job j = dense_chol2_job(c->P, c->n, c->ld, c->flags, c->L);
+  point_chol_order(c, p, &j);
+  HIPCHK(ovp_launch_chol2(&j, nullptr, nullptr, c->stream2));
+  HIPCHK(hipEventRecord(c->ev_join, c->stream2));
+  return 0;
+}
+
+// K1: gate and rows of every feature.  The fused shape carries chol(P) in workgroup 0 (cj.n > 0) or leaves that workgroup idle.
+static int point_enqueue_k1(ovp_ctx* c, const PointPlan& p) {
+  if (p.k1 == K1_ONE_WAVE) return (int)ovp_launch_feat_gate(&c->fp, c->stream);
+  ovp::CholJob cj{c->P, c->L, nullptr, nullptr, p.k1 == K1_FUSED_CHOL ? c->n : 0, c->ld, c->flags, 0, nullptr, 0, 0.0};
+  point_chol_order(c, p, &cj);
+  return (int)ovp_launch_feat_chol(&c->fp, &cj, c->stream);
+}
+
+// K2 on the Fa features that own rows of rec / G (or a clear of the pair), then the pending dense pair
+static int point_enqueue_pair(ovp_ctx* c, const PointPlan& p, hipStream_t s) {
+  const int n = c->n;
+  if (!p.clear_Ab) {
+    int nsplit = p.nsplit;
+    HIPCHK(ovp_launch_gram_pair(c->rec, c->fp.n_clones, p.Fa, c->rows_per_chunk, p.used_chunks, c->gramS, c->G, 3 * p.Fa, c->ldg, n + 1,
+                                c->n_split, c->part, &nsplit, s));
+    HIPCHK(ovp_launch_reduce_gram(c->gramS, c->fp.n_clones, p.used_chunks, c->gramR, s));
+    HIPCHK(ovp_launch_assemble(c->gramR, c->fp.n_clones, 1, c->part, nsplit, c->colmap, n, c->Ab, c->ld, s));
   } else {
-    HIPCHK(ovp_launch_feat_gate(&fp, c->stream));
+    HIPCHK(hipMemsetAsync(c->Ab, 0, sizeof(double) * (size_t)(n + 1) * c->ld, s));
   }
-  hipEvent_t fork_ev = c->ev_fork;
-  if (c->ktimer) {
-    fork_ev = c->ev_k1;
-    c->kpending = true;
-  }
-  // K2 runs on the side stream in mode 2 (it is the shorter of the two branches: the join below then never stalls the
-  // main stream, and the cross-queue wake-up latency sits at the START of the side branch, off the critical path)
-  hipStream_t s2k = c->stream;
-  if (overlap_mode == 2) {
-    HIPCHK(hipEventRecord(fork_ev, c->stream));
-    HIPCHK(hipStreamWaitEvent(c->stream2, fork_ev, 0));
-    s2k = c->stream2;
-    int rc = chol_of_P(c, c->stream);
-    if (rc) return rc;
-  } else {
-    if (c->ktimer) HIPCHK(hipEventRecord(c->ev_k1, c->stream));
-    if (overlap_mode == 0) {
-      int rc = chol_of_P(c, c->stream);
-      if (rc) return rc;
-      HIPCHK(hipEventRecord(c->ev_join, c->stream));
-    }
-  }
-  // K2 (on the Fa features that own rows of rec / G)
-  const int used_chunks = Fa > 0 ? (2 * Fa + c->rows_per_chunk - 1) / c->rows_per_chunk : 0;
-  if (Fa > 0) {
-    int nsplit = (3 * Fa + 511) / 512;
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > c->n_split) nsplit = c->n_split;
-    HIPCHK(ovp_launch_gram_pair(c->rec, fp.n_clones, Fa, c->rows_per_chunk, used_chunks, c->gramS, c->G, 3 * Fa, c->ldg,
-                                n + 1, c->n_split, c->part, &nsplit, s2k));
-    HIPCHK(ovp_launch_reduce_gram(c->gramS, fp.n_clones, used_chunks, c->gramR, s2k));
-    HIPCHK(ovp_launch_assemble(c->gramR, fp.n_clones, 1, c->part, nsplit, c->colmap, n, c->Ab, c->ld, s2k));
-  } else {
-    HIPCHK(hipMemsetAsync(c->Ab, 0, sizeof(double) * (size_t)(n + 1) * c->ld, s2k));
-  }
-  if (!c->dense_cols.empty()) {
+  if (p.add_pair) {
     // the pair of the dense blocks accepted by ovp_msckf_dense_blocks joins the batch's (same update, update/UpdaterMSCKF.cpp:767-814)
     const int m = (int)c->dense_cols.size();
     HIPCHK(c->Acc.alloc((size_t)c->n_max * c->n_max));
     HIPCHK(c->bcc.alloc((size_t)c->n_max));
-    HIPCHK(hipMemcpyAsync(c->Acc, c->dense_A.data(), sizeof(double) * (size_t)m * m, hipMemcpyHostToDevice, s2k));
-    HIPCHK(hipMemcpyAsync(c->bcc, c->dense_b.data(), sizeof(double) * m, hipMemcpyHostToDevice, s2k));
-    HIPCHK(hipMemcpyAsync(c->idbuf, c->dense_cols.data(), sizeof(int) * m, hipMemcpyHostToDevice, s2k));
-    HIPCHK(ovp_launch_scatter_gram_add(c->Acc, c->bcc, m, c->idbuf, c->Ab, c->ld, n, s2k));
-    HIPCHK(hipStreamSynchronize(s2k));  // (the host vectors are pageable and about to be cleared; slow path)
+    HIPCHK(hipMemcpyAsync(c->Acc, c->dense_A.data(), sizeof(double) * (size_t)m * m, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->bcc, c->dense_b.data(), sizeof(double) * m, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->idbuf, c->dense_cols.data(), sizeof(int) * m, hipMemcpyHostToDevice, s));
+    HIPCHK(ovp_launch_scatter_gram_add(c->Acc, c->bcc, m, c->idbuf, c->Ab, c->ld, n, s));
+    HIPCHK(hipStreamSynchronize(s));  // (the host vectors are pageable and about to be cleared; slow path)
     c->dense_cols.clear();
   }
-  if (overlap_mode == 2) {
+  return 0;
+}
+
+static int point_enqueue_build(ovp_ctx* c, const PointPlan& p) {
+  SideJoin side{c};
+  if (c->n > OVP_TILECHOL_NMAX) {
+    const int rs = set_substate(c, p.sub_ids);
+    if (rs) return rs;
+  }
+  if (p.boost == BOOST_CHOL) HIPCHK(c->boost.alloc(64));
+  // Events on the main stream are kept to a minimum (each one costs microseconds between dependent kernels): with the kernel timer
+  // on, ev_k0 / ev_k1 bracket K1 and ev_k1 doubles as the fork point behind it; otherwise one untimed fork event.
+  if (c->ktimer) HIPCHK(hipEventRecord(c->ev_k0, c->stream));
+  int rc = p.chol_p == CHOLP_SIDE ? point_enqueue_chol_p(c, p, c->ev_fork, &side) : 0;
+  if (!rc) rc = point_enqueue_k1(c, p);
+  if (rc) return rc;
+  if (c->ktimer) c->point.k1_timed = true;
+  const bool k2_aside = p.chol_p == CHOLP_BEHIND_K1;
+  if (k2_aside) rc = point_enqueue_chol_p(c, p, c->ktimer ? c->ev_k1 : c->ev_fork, &side);
+  else if (c->ktimer) HIPCHK(hipEventRecord(c->ev_k1, c->stream));
+  if (!rc) rc = point_enqueue_pair(c, p, k2_aside ? c->stream2 : c->stream);
+  if (rc) return rc;
+  if (k2_aside) {
     // the Gram pair must be complete on the main stream when this call returns (the caller may all-reduce it there)
     HIPCHK(hipEventRecord(c->ev_join, c->stream2));
     HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
   }
+  side.armed = false;
+  c->point.tail = point_tail(c, p);
+  c->point.join_owed = p.join;
   return 0;
+}
+
+extern "C" int ovp_msckf_build_gate_gram_async(ovp_ctx* c, const ovp_update_opts* o) {
+  if (!c || !o) return OVP_E_ARG;
+  if (!c->have_state || !c->have_cov || !c->have_batch) return OVP_E_STATE;
+  if (c->fp.n_clones < 1) return OVP_E_STATE;
+  {
+    int rc = fill_feat_params(c, o);
+    if (rc) return rc;
+  }
+  c->point.tail = PointTail();  // (pub_armed and k1_timed are the fetch's to clear)
+  c->point.join_owed = false;
+  PointPlan p;
+  plan_point_update(point_env(c), c->h_slot.get(), &p);
+  const int route[8] = {p.k1, p.chol_p, p.tail, p.flip ? 1 : 0, p.nl, p.boost_n, p.Fa, p.sub_ns};
+  memcpy(c->point_route, route, sizeof(route));
+  if (p.slots) {  // K1 reads a feature's slot from host-mapped memory at the start of its wave
+    c->fp.slot = c->h_slot.dev();
+    c->fp.n_out = p.Fa;
+  }
+  // (the flag words were cleared by the previous ovp_msckf_fetch_results, or at creation)
+  return point_enqueue_build(c, p);
 }
 
 // Dense blocks beside the batch (see ovplane_hip.h): gates on the host against the marginal of the involved columns, pair kept for
@@ -590,7 +520,11 @@ extern "C" int ovp_gram_buffer(ovp_ctx* c, double** Ab_dev, int* n_rows, int* ld
 extern "C" int ovp_ekf_update_from_gram_async(ovp_ctx* c) {
   if (!c) return OVP_E_ARG;
   if (!c->have_cov) return OVP_E_STATE;
-  int rc = ekf_from_gram(c, true, true);
+  const PointPending pend = c->point;  // (consumed here: a second call without a build runs the plain tail)
+  c->point.tail = PointTail();
+  c->point.join_owed = false;
+  if (pend.join_owed) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
+  int rc = point_enqueue_tail(c, pend.tail, true);
   if (rc) return rc;
   if (c->ktimer) {
     HIPCHK(hipEventRecord(c->ev_t[3], c->stream));
@@ -607,13 +541,13 @@ extern "C" int ovp_msckf_fetch_results(ovp_ctx* c, double* dx_host, uint8_t* acc
     // [flags | dx] are published by the last block of the dx kernel (or, on the fallback path, by a publish kernel);
     // chi2 / accept were written into the pinned block by K1 itself
     SeqChannel& ch = c->h_res_block.channel(0);
-    if (!c->pub_pending) {
+    if (!c->point.pub_armed) {
       const size_t words = (16 + sizeof(double) * (size_t)n + 7) / 8;
       const unsigned seq = ch.arm();
       // (also clears the four flag words of the device block for the next update)
       HIPCHK(ovp_launch_publish_block(c->res_block, c->h_res_block.dev(c->h_flags), 8 * words, ch.word_dev(), seq, 2, c->stream));
     }
-    c->pub_pending = false;
+    c->point.pub_armed = false;
     const int rw = ch.wait(c->stream);
     if (rw) return rw;
   }
@@ -635,13 +569,13 @@ extern "C" int ovp_msckf_fetch_results(ovp_ctx* c, double* dx_host, uint8_t* acc
     hipEventElapsedTime(&c->last_ms[3], c->ev_k0, c->ev_t[3]);
     c->timed = false;
   }
-  if (c->kpending) {
+  if (c->point.k1_timed) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, c->ev_k0, c->ev_k1) == hipSuccess) {
       c->ktime_ms += ms;
       c->klaunches += 1;
     }
-    c->kpending = false;
+    c->point.k1_timed = false;
   }
   if (info) {
     memset(info, 0, sizeof(*info));
@@ -755,7 +689,7 @@ extern "C" int ovp_ekf_update(ovp_ctx* c, const double* H_host, int rows, int co
     int rs = set_substate(c, ids);
     if (rs) return rs;
   }
-  int rc = ekf_from_gram(c, false);
+  int rc = ekf_from_gram(c, PointTail());
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(c->h_dx, c->dx, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(c->h_flags, c->flags, sizeof(int) * 4, hipMemcpyDeviceToHost, c->stream));

@@ -346,7 +346,7 @@ static int slam_tail_info(ovp_ctx* c, const SlamUpdatePlan& p, const ovp_slam_ba
     const int rs = set_substate(c, ids);
     if (rs) return rs;
   }
-  const int rc = ekf_from_gram(c, false);
+  const int rc = ekf_from_gram(c, PointTail());
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(c->h_dx, c->dx, sizeof(double) * n, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(c->h_flags, c->flags, sizeof(int) * 4, hipMemcpyDeviceToHost, s));

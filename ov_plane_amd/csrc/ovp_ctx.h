@@ -2,7 +2,8 @@
 // the helpers the entry-point files share.  Not installed; the boundary is include/ovplane_hip.h.
 //   ovp_api_ctx.hip    context, covariance residency and bookkeeping (upload / marginal / propagate / clone / marginalize /
 //                      initialize), pose tables, feature batch, diagnostics
-//   ovp_api_point.hip  point update: K1 -> information pair -> EKF update (ovp_msckf_update and its staged form), ovp_ekf_update
+//   ovp_api_point.hip  point update: K1 -> information pair -> EKF update (ovp_msckf_update and its staged form), ovp_ekf_update;
+//                      what a call does is decided by the pure planner of ovp_point_plan.h, the stages enqueue a PointPlan
 //   ovp_api_rccl.hip   feature-sharded update over RCCL
 //   ovp_api_plane.hip  plane loop (ovp_msckf_plane_update) and plane initialisation (ovp_plane_init_general: the loop as its front,
 //                      k_plane_init2.hip as its tail; ovp_plane_init: the same without a general batch)
@@ -128,6 +129,31 @@ static const int OVP_TILECHOL_NMAX = 288;  // register-resident factorization li
 
 static inline int round_up(int v, int m) { return ((v + m - 1) / m) * m; }
 
+// What the second half of an information-form update (point_enqueue_tail, ovp_api_point.hip) runs on.  All zero = the plain tail: the
+// Cholesky factor of P in c->L, T = I + L^T A L on all n columns, nothing to take off the diagonal.
+struct PointTail {
+  const double* factor = nullptr;  // some M with M M^T = P (+ diag(boost)); nullptr: c->L
+  int nl = 0;                      // T is the identity outside its leading nl columns (reversed-order factor); 0: all n
+  int dense = 0;                   // k_fwdsub's dense mode for `factor`
+  const double* boost = nullptr;   // amounts the factorization added to the first boost_n diagonal entries: the last kernel takes them off
+  int boost_n = 0;
+};
+// The half-done point update: the staged C-ABI returns between ovp_msckf_build_gate_gram_async, ovp_ekf_update_from_gram_async and
+// ovp_msckf_fetch_results.  Written by those three only; all zero = nothing pending.
+struct PointPending {
+  PointTail tail;
+  bool join_owed = false;  // chol(P) / K2 of the update finish on stream2 (ev_join): the tail waits for them first
+  bool pub_armed = false;  // channel 0 of h_res_block is armed and a kernel of the update will post it (k_dx_rows)
+  bool k1_timed = false;   // ev_k0 / ev_k1 bracket the update's K1 (dominant-kernel timer)
+};
+// A factor of the RESIDENT covariance left behind by the plane loop (P = V^T V, Lkeep = V^T in the state's column order): the point
+// update that follows needs some M with M M^T = P, not the Cholesky factor, and skips chol(P).  boost: Lkeep is a factor of
+// P + diag(boost_vec), the point update on it takes the amounts off at its end.  Written by the plane loop, cleared by everything
+// that writes P (drop_kept_factor).
+struct KeptFactor {
+  bool have = false, boost = false;
+};
+
 // ------------------------------------------------------------------------------------------------
 struct ovp_ctx {
   int device = 0;
@@ -216,18 +242,14 @@ struct ovp_ctx {
   Staged pl_sub_tab;                             // [ids | inverse | clone ids | column map] of the loop's column order
   // (what tells the plane loop's routes apart is an argument of the loop, PlaneLoopView in ovp_api_plane.hip, not context state)
   DevBuf<void> pl_gen_dev;                 // device: [marks | projected rows] of one plane's general features of the running loop
-  // A factor of the RESIDENT covariance left behind by the plane loop (P = V^T V, Lkeep = V^T in the state's column order): the point
-  // update that follows needs some M with M M^T = P, not the Cholesky factor - chol(P) (the longer branch of the fused feature
-  // launch at N = 240) is skipped.  Cleared by everything that writes P.
   DevBuf<double> Lkeep;
-  bool have_factor = false, use_kept_factor = false;
+  KeptFactor kept;
   double clone_jitter = 0.0;  // ovp_cov_clone_jitter: relative inflation of a cloned block's diagonal (0 = exact copy, the reference)
   DevBuf<double> boost_vec;  // [n_max] k_gather_block_boost: the plane loop's diagonal boost by STATE column (zero where none)
-  bool kept_boost = false;  // Lkeep is a factor of P + diag(boost_vec): the point update on it takes the amounts off at its end
   DevBuf<double> boost;   // CholJob::boost: the amounts the reversed-order chol(P) added to the diagonal in front of the batch's columns
-  int point_boost_n = 0;
-  int point_nl = 0;  // > 0: chol(P) of the running point update was taken in reversed index order (CholJob::flip) and the update's
-                     // T = I + L^T A L is the identity outside its leading point_nl columns
+  // (what tells the point update's routes apart is a PointPlan, ovp_point_plan.h; what its second half needs of it is `point`)
+  PointPending point;
+  int point_route[8] = {-1, 0, 0, 0, 0, 0, 0, 0};  // the last point update's plan (ovp_debug_read "point_route"); [0] < 0: none yet
   Staged pl_stage;                    // the per-call tables of the plane loop, the point update's sub-state and the SLAM entries
   Mailbox pl_hres;                    // the plane results and the small fetches (ovp_fetch_to_hres): payload from byte 0, channel 0
   // the pose tables and the feature batch (a single copy per upload, an event behind it: the uploads do not wait)
@@ -253,8 +275,6 @@ struct ovp_ctx {
   Mailbox h_res_block;                                // ... its pinned mirror; channel 0: the point update, channel 1: ovp_cov_propagate,
                                                       // channel 2: ovp_zupt_update, whose block [head 8 | dx n_max] starts at zupt_res_off
   size_t zupt_res_off = 0;
-  bool pub_pending = false;      // channel 0 is armed and a kernel of the running update will post it (k_dx_rows)
-  bool need_join = false;     // chol(P) / K2 of the current update finish on stream2 (ev_join) rather than on the main stream
   DevBuf<unsigned> ticket;       // block counter of the publishing kernel
   std::vector<int> h_nmeas;                           // host copy of n_meas of the current batch (row count of `info`)
   bool h_nmeas_valid = false;
@@ -266,7 +286,6 @@ struct ovp_ctx {
   OvpEvent ev_k0, ev_k1;
   double ktime_ms = 0.0;
   int klaunches = 0;
-  bool kpending = false;
   // host-side clock of the two update entry points, accumulated (ovp_host_timing): plane loop [entry -> first launch | entry -> last
   // launch enqueued | wait for the device | calls], point update [enqueue | wait | calls]
   double host_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -348,15 +367,12 @@ static inline void fill_tri_params(ovp::TriParams& tp, const ovp_ctx* c, const o
   tp.max_cond_number = o->max_cond_number;
 }
 
-// Everything that writes the covariance calls this: the factor the plane loop left (Lkeep) and the bookkeeping of a staged point
-// update that was built but never applied (use_kept_factor / point_nl, set by ovp_msckf_build_gate_gram_async) no longer belong to P.
+// Everything that writes the covariance calls this: the factor the plane loop left (Lkeep) and the tail of a staged point update
+// that was built but never applied (set by ovp_msckf_build_gate_gram_async) no longer belong to P.
 static inline void drop_kept_factor(ovp_ctx* c) {
   if (!c) return;
-  c->have_factor = false;
-  c->use_kept_factor = false;
-  c->point_nl = 0;
-  c->point_boost_n = 0;
-  c->kept_boost = false;
+  c->kept = KeptFactor();
+  c->point.tail = PointTail();
   c->dense_cols.clear();  // (a pending dense pair was gated against the covariance that is being replaced)
 }
 
@@ -385,7 +401,7 @@ int ovp_fetch_to_hres(ovp_ctx* c, const void* dsrc, size_t bytes, hipStream_t s)
 int chol_of_P(ovp_ctx* c, hipStream_t s, bool psd = false);  // psd: pivot-dropping factor of a positive semi-definite P (plane path)
 hipError_t chol_of_T(ovp_ctx* c, const double* T, int n, int ld, int add_identity, const int* cond, hipStream_t s);
 int set_substate(ovp_ctx* c, const std::vector<int>& ids);
-int ekf_from_gram(ovp_ctx* c, bool chol_p_done_on_stream2, bool publish = false);
+int ekf_from_gram(ovp_ctx* c, const PointTail& t);  // chol(P) on the main stream, then the update on the pair in c->Ab
 int ekf_sform(ovp_ctx* c);
 // ovp_api_plane.hip
 int plane2_buffers(ovp_ctx* c, size_t stage_bytes, size_t res_bytes);

@@ -8,6 +8,7 @@
 #define OVP_MAX_CLONES 64
 #define OVP_GRAM_ELEMS 231   // 21*22/2: packed upper triangle of the per-clone 21x21 Gram
 #define OVP_TC_MAX_TILES 18  // tile rows the register-resident Cholesky handles (N <= 288)
+#define OVP_FEAT_CHOL_MAX_MEAS 30  // observations per feature the fused feature kernel takes (ovp_feat_chol_supported; the point planner's limit)
 #define OVP_BSCR 2112        // doubles of per-feature scratch for B (k_feat.hip LCOLS)
 // Plane-level gate (k_chol2.hip): weight of the expected energy of the reference's rounding-decided rows; 1 = the plain
 // expectation (rounds 2-5: +0.35 +- 0.06 above the mean of four roundings of the oracle).  Round 6: the weight that zeroes that
